@@ -908,6 +908,26 @@ def compact_line(full, full_path=None):
     return line
 
 
+def dump_outputs(learner, stats, out_dir):
+    """what the last timed learn() handed its caller, one DIR/<name>.npy per array: the returned statistics
+    (stat.<key>.npy, float64), the updated model incl. the z-filter (param.<name>.npy, float32) and the advantages and
+    returns it trained on (float32).  About 1.4 MB at the headline shape; the inputs are seeded, so two builds run with
+    the same arguments can be compared array for array."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {'stat.' + k: np.asarray(float(v), dtype=np.float64) for k, v in stats.items()}
+    for k, v in learner.model.state_dict().items():
+        arrays['param.' + k] = v.detach().float().cpu().numpy()
+    ws = learner._ws
+    arrays['advantages'] = ws.adv.detach().float().cpu().numpy().reshape(ws.key[0], -1)
+    arrays['returns'] = ws.ret.detach().float().cpu().numpy().reshape(ws.key[0], -1)
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= 64 << 20, 'outputs to dump are %d bytes, more than 64 MB' % total
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + '.npy'), a)
+    return sorted(arrays)
+
+
 def write_full(full, path):
     """the complete record (every configuration's full entry) as a file; returns the path written, or None"""
     if not path:
@@ -942,6 +962,9 @@ def main():
                          'would start after it are skipped (and say so)')
     ap.add_argument('--full-out', default=os.path.join(ROOT, 'gpurun_out', 'bench_full.json'),
                     help='the complete record (the stdout line is its <= 4 KB summary); "" to skip')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='write what the last timed step computed (statistics, updated parameters, advantages, '
+                         'returns) as DIR/<name>.npy')
     args = ap.parse_args()
 
     # `python bench.py --gpus N` with N > 1 and no launcher around it (the shape of the driver's N = 1 command):
@@ -1073,9 +1096,13 @@ def run(args, world, rank, local_rank, backend):
     if args.scaling == 'strong':
         learner, params, zstate, dbatch, batch, stats, dt = timed_run(strong_hi - strong_lo, strong_lo)
         total_rows = B
+        if args.dump_outputs and rank == 0:
+            dump_outputs(learner, stats, args.dump_outputs)
     else:
         learner, params, zstate, dbatch, batch, stats, dt = timed_run(B, 0)
         total_rows = world * B
+        if args.dump_outputs and rank == 0:
+            dump_outputs(learner, stats, args.dump_outputs)
         if world > 1:       # the same global batch of 1024 sub-trajectories split over the ranks
             sl, _, _, _, _, sstats, sdt = timed_run(strong_hi - strong_lo, strong_lo)
             strong = {'value': B * N * args.steps / sdt, 'unit': 'env-steps/s', 'ms_per_step': sdt / args.steps * 1e3,

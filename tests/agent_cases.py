@@ -49,7 +49,7 @@ def _ppo_setup(c):
                                        rnn_hidden=rnn[0] if rnn else 0, rnn_layers=rnn[1] if rnn else 1,
                                        **META['ppo_param_kw'], **pix_kw)
     zstate = synthetic.make_zfilter_state(c['D'], seed=5) if c.get('use_z', True) else None
-    return lc, ec, ppo_session_config('/tmp/surreal_amd_test'), params, zstate
+    return lc, ec, ppo_session_config(H.session_folder('surreal_amd_test')), params, zstate
 
 
 def _obs(c, g, t, i):
@@ -146,7 +146,7 @@ def _ddpg_setup(c):
                                                     tuple(c['ch']), seed=3)
     else:
         params = ddpg_oracle.make_ddpg_params(c['D'], c['A'], tuple(c['ah']), tuple(c['ch']), seed=3)
-    return lc, ec, ddpg_session_config(), params
+    return lc, ec, ddpg_session_config(H.session_folder('surreal_amd_ddpg')), params
 
 
 def check_ddpg_case(name):

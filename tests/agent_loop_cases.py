@@ -99,7 +99,7 @@ def check_case(name, monkeypatch):
     ec = ppo_env_config(D, A)
     ec.limit_episode_length = c['limit']
     ec.stochastic_eval = True
-    sc = ppo_session_config('/tmp/surreal_amd_test_agent_loop')
+    sc = ppo_session_config(H.session_folder('surreal_amd_test_agent_loop'))
     sc.agent.fetch_parameter_mode, sc.agent.fetch_parameter_interval = c['fetch_mode'], c['interval']
     sc.tensorplex.update_schedule.agent = 2
     sc.tensorplex.update_schedule.training_env = 2

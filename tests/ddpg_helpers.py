@@ -37,7 +37,7 @@ def make_learner(case, opts=None):
     pixel = tuple(case['pixel']) if case.get('pixel') else None
     if pixel is not None:
         lc.model.conv_spec.hidden_output_dim = case['conv_hidden']
-    sc = ddpg_session_config()
+    sc = ddpg_session_config(H.session_folder('surreal_amd_ddpg'))
     for k, v in (opts or {}).items():          # e.g. ddpg_row_schedule = False: the level schedule
         sc.learner[k] = v
     L = DDPGLearner(lc, ddpg_env_config(case['D'], case['A'], pixel=pixel), sc)
@@ -234,7 +234,7 @@ def check_sampling_into_staging(device):
               'dones': (torch.rand(n, generator=gen) < 0.05).float()}
     replays = []
     for _ in range(2):
-        R = UniformReplay(lc, ddpg_env_config(D, A), ddpg_session_config())
+        R = UniformReplay(lc, ddpg_env_config(D, A), ddpg_session_config(H.session_folder('surreal_amd_ddpg')))
         R.insert_batch({k: v.to(device) for k, v in fields.items()})
         replays.append(R)
 

@@ -9,6 +9,14 @@ from surreal_amd.main.ppo_configs import ppo_learner_config, ppo_env_config, ppo
 
 GOLDEN_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden')
 
+
+def session_folder(name):
+    """a learner's session folder (config.yml, checkpoints) under a temporary directory of this user's own: a fixed
+    path under /tmp can belong to another user's earlier run on a shared host"""
+    import tempfile
+    return os.path.join(tempfile.gettempdir(), 'surreal_amd_test_uid%d' % os.getuid(), name)
+
+
 # fp32 parity tolerance of BASELINE.json's north_star ("the same advantages / returns / losses
 # as the reference PyTorch CPU learner ... within 1e-5 fp32"): applied to advantages, returns,
 # critic values and every loss / KL / entropy / likelihood statistic.
@@ -190,7 +198,7 @@ def make_learner(case, params, zstate, cls=None, session_overrides=None):
         if k in hyper:
             lc.algo.network[k] = hyper[k]
     lc.replay.batch_size = shp['B']
-    sc = ppo_session_config()
+    sc = ppo_session_config(session_folder('surreal_amd'))
     for k, v in (session_overrides or {}).items():
         sc.learner[k] = v
     if case.get('pixel'):

@@ -100,41 +100,76 @@ def test_last_4k_of_stdout_parses(tmp_path):
 
 
 def test_reference_and_port_cpu_legs_agree(monkeypatch):
-    """bench.py's two CPU baselines on a small shape: the REFERENCE'S OWN learner (/root/reference under the
-    shims; `kind: reference`) and the restatement (`kind: port`) are the same arithmetic -- cpu_ppo times both, and the
-    statistics of one learn agree bit for bit (build container only: skipped where the reference tree does not exist)"""
+    """bench.py's two CPU baselines on a small shape: the REFERENCE'S OWN learner (the reference tree under the
+    shims; `kind: reference`) and the restatement (`kind: port`) are the same arithmetic.  The restatement's statistics
+    of one learn match the reference's as oracle/gen_golden_bench_legs.py recorded them (tests/golden/bench_cpu_legs.json,
+    within the BLAS tolerance of tests/test_oracle_golden.py); where the reference tree exists they also agree bit for
+    bit with a live run of it, and cpu_ppo times both legs -- elsewhere it times the port alone"""
     import copy
     import numpy as np
     import bench
     sys.path.insert(0, os.path.join(ROOT, 'oracle'))
-    import ref_shims
-    if not ref_shims.reference_available():
-        pytest.skip('no reference tree on this host')
-    monkeypatch.setenv('SMX_BENCH_REFERENCE', '1')
-    import gen_golden as G
+    import gen_golden_bench_legs as GL
     import ppo_oracle
-    from surreal_amd import synthetic
-    Bs, Ns, Ds, As = 6, 12, 9, 3
+    import ref_shims
+    have_ref = ref_shims.reference_available()
+    if have_ref:
+        monkeypatch.setenv('SMX_BENCH_REFERENCE', '1')
+        import gen_golden as G
+    golden = json.load(open(os.path.join(ROOT, 'tests', 'golden', 'bench_cpu_legs.json')))
+    spec = golden['spec']
+    Bs, Ns, Ds, As = spec['B'], spec['N'], spec['D'], spec['A']
     for rnn in (False, True):
-        F = 12 if rnn else 0
-        batch = synthetic.make_ppo_batch(Bs, Ns, Ds, As, seed=3, rnn_hidden=F)
-        params = synthetic.make_ppo_params(Ds, As, hidden=(24, 16), seed=1, rnn_hidden=F)
-        hyper = dict(n_step=Ns, kl_target=1e9, ppo_mode='adapt')
-        if rnn:
-            hyper.update(if_rnn_policy=True, horizon=4)
-        ref = ref_shims.import_reference()
-        Lr = G.build_reference_learner(ref, params, None, Bs, Ns, Ds, As, hyper)
-        bd = ref_shims.BeneDict(copy.deepcopy(batch))
-        bd = Lr._preprocess_batch_ppo(bd)
-        rs = Lr._optimize(bd.obs, bd.actions, bd.rewards, bd.obs_next, bd.persistent_infos, bd.onetime_infos, bd.dones)
+        batch, params, hyper = GL.case_inputs(spec, rnn)
         O = ppo_oracle.OraclePPOLearner(params, As, Bs, **hyper)
         os_ = O.learn(copy.deepcopy(batch))
-        for k, v in os_.items():
-            if k != '_lr':
-                assert float(rs[k]) == float(v) or (np.isnan(float(rs[k])) and np.isnan(float(v))), (rnn, k, rs[k], v)
-        # the timing leg itself: both kinds reported, the quoted value is the faster one
+        want = golden['stats']['lstm' if rnn else 'mlp']
+        assert sorted(want) == sorted(k for k in os_ if k != '_lr'), (rnn, sorted(want), sorted(os_))
+        for k, v in want.items():
+            np.testing.assert_allclose(float(os_[k]), v, atol=2e-6, rtol=2e-6, err_msg='%s rnn=%s' % (k, rnn))
+        if have_ref:
+            ref = ref_shims.import_reference()
+            Lr = G.build_reference_learner(ref, params, None, Bs, Ns, Ds, As, hyper)
+            bd = ref_shims.BeneDict(copy.deepcopy(batch))
+            bd = Lr._preprocess_batch_ppo(bd)
+            rs = Lr._optimize(bd.obs, bd.actions, bd.rewards, bd.obs_next, bd.persistent_infos, bd.onetime_infos, bd.dones)
+            for k, v in os_.items():
+                if k != '_lr':
+                    assert float(rs[k]) == float(v) or (np.isnan(float(rs[k])) and np.isnan(float(v))), (rnn, k, rs[k], v)
+        # the timing leg itself: both kinds reported where the reference exists, the quoted value is the faster one
         monkeypatch.setattr(bench, '_CPU_THREADS', [2])
         out = bench.cpu_ppo(Bs, Ns, Ds, As, rnn, None, params, batch, budget_s=4.0)
-        assert out['port']['value'] > 0 and out['reference']['value'] > 0
-        assert out['value'] == max(out['port']['value'], out['reference']['value'])
-        assert out['kind'] == ('reference' if out['reference']['value'] >= out['port']['value'] else 'port')
+        assert out['port']['value'] > 0
+        if have_ref:
+            assert out['reference']['value'] > 0
+            assert out['value'] == max(out['port']['value'], out['reference']['value'])
+            assert out['kind'] == ('reference' if out['reference']['value'] >= out['port']['value'] else 'port')
+        else:
+            assert 'reference' not in out and out['kind'] == 'port' and out['value'] == out['port']['value']
+
+
+def test_dump_outputs_writes_what_the_last_step_returned(tmp_path, cpu_double):
+    """--dump-outputs: the statistics learn() returned (float64), the updated model with its z-filter and the advantages /
+    returns of the step (float32), one DIR/<name>.npy each -- here on the torch-CPU kernel double at 8 sub-trajectories"""
+    import numpy as np
+    import bench
+    learner, _, _ = bench.build_learner('adapt', 0, B=8, use_graph=False)
+    dbatch, _ = bench.device_batch(learner, 0, B=8)
+    stats = learner.learn(dbatch)
+    out = tmp_path / 'out'
+    names = bench.dump_outputs(learner, stats, str(out))
+    assert sorted(p.name for p in out.iterdir()) == sorted(n + '.npy' for n in names)
+    for k, v in stats.items():
+        a = np.load(out / ('stat.%s.npy' % k))
+        assert a.dtype == np.float64 and a.shape == () and float(a) == float(v), k
+    sd = learner.model.state_dict()
+    assert 'z_filter.running_sum' in sd
+    for k, v in sd.items():
+        a = np.load(out / ('param.%s.npy' % k))
+        assert a.dtype == np.float32, k
+        np.testing.assert_array_equal(a, v.detach().cpu().numpy(), err_msg=k)
+    for k, v in (('advantages', learner._ws.adv), ('returns', learner._ws.ret)):
+        a = np.load(out / (k + '.npy'))
+        assert a.dtype == np.float32 and a.shape[0] == 8, (k, a.shape)
+        np.testing.assert_array_equal(a.reshape(-1), v.cpu().numpy().reshape(-1), err_msg=k)
+    assert len(names) == len(stats) + len(sd) + 2

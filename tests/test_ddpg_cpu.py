@@ -8,6 +8,7 @@ import pytest
 
 import ddpg_helpers as DH
 import ddpg_oracle
+from helpers import session_folder
 from surreal_amd import synthetic
 
 
@@ -73,14 +74,14 @@ def test_ddpg_every_switch_combination_constructs_and_learns(cpu_double):
         lc.replay.batch_size = 8
         if pixel:
             lc.model.conv_spec.hidden_output_dim = 8
-        L = DDPGLearner(lc, ddpg_env_config(5, 2, pixel=pixel), ddpg_session_config())
+        L = DDPGLearner(lc, ddpg_env_config(5, 2, pixel=pixel), ddpg_session_config(session_folder('surreal_amd_ddpg')))
         st = dict(L.learn(synthetic.make_ddpg_batch(8, 5, 2, seed=1, pixel=pixel)))
         assert np.isfinite(st['critic_loss']) and ('Q_policy2' in st) == double
     lc = ddpg_learner_config()
     lc.algo.network.target_update = {'type': 'weird'}
     from surreal_amd.session import ConfigError
     with pytest.raises(ConfigError):
-        DDPGLearner(lc, ddpg_env_config(5, 2), ddpg_session_config())
+        DDPGLearner(lc, ddpg_env_config(5, 2), ddpg_session_config(session_folder('surreal_amd_ddpg')))
 
 
 def test_ddpg_agent_replay_learner_loop(cpu_double):
@@ -95,7 +96,7 @@ def test_ddpg_agent_replay_learner_loop(cpu_double):
     lc = ddpg_learner_config()
     lc.model.actor_fc_hidden_sizes, lc.model.critic_fc_hidden_sizes = [24, 16], [32, 24]
     lc.replay.batch_size, lc.replay.memory_size, lc.replay.sampling_start_size = 8, 64, 10
-    ec, sc = ddpg_env_config(D, A, num_agents=2), ddpg_session_config()
+    ec, sc = ddpg_env_config(D, A, num_agents=2), ddpg_session_config(session_folder('surreal_amd_ddpg'))
     ec.limit_episode_length = 15
     replay = UniformReplay(lc, ec, sc)
     learner = DDPGLearner(lc, ec, sc)
@@ -128,7 +129,7 @@ def test_ddpg_pixel_agent_acts_on_camera_frames(cpu_double):
     g, c = DH.load('tiny_pixel_hard')
     L = DH.make_learner(c)
     lc = L.learner_config
-    ec, sc = ddpg_env_config(c['D'], c['A'], pixel=tuple(c['pixel'])), ddpg_session_config()
+    ec, sc = ddpg_env_config(c['D'], c['A'], pixel=tuple(c['pixel'])), ddpg_session_config(session_folder('surreal_amd_ddpg'))
     ag = DDPGAgent(lc, ec, sc, agent_id=0, agent_mode='eval_deterministic_local')
     ag.attach_learner(L)
     assert ag.fetch_parameter() and torch.equal(ag.model.perception_flat, L.model.perception_flat)
@@ -164,7 +165,7 @@ def test_frame_stack_preprocessor_joins_frame_lists(cpu_double):
     lc.replay.batch_size = 4
     ec = ddpg_env_config(3, 2, pixel=(2, 20, 24))
     ec.frame_stack_concatenate_on_env = False
-    L = DDPGLearner(lc, ec, ddpg_session_config())
+    L = DDPGLearner(lc, ec, ddpg_session_config(session_folder('surreal_amd_ddpg')))
     b = L._prefetcher_preprocess(exps)
     assert b['obs']['pixel']['camera0'].shape == (4, 2, 20, 24) and b['obs']['pixel']['camera0'].dtype == np.uint8
     assert b['obs_next']['pixel']['camera0'][2, 1, 0, 0] == 4 and b['obs']['low_dim']['flat_inputs'].shape == (4, 3)

@@ -188,7 +188,7 @@ def test_agent_wraps_its_env_with_the_monitors(cpu_double):
     get the eval monitor unless they are *_local"""
     from surreal_amd.agent import PPOAgent
     from surreal_amd.main.ppo_configs import ppo_learner_config, ppo_env_config, ppo_session_config
-    lc, ec, sc = ppo_learner_config(), ppo_env_config(5, 2), ppo_session_config('/tmp/surreal_amd_test')
+    lc, ec, sc = ppo_learner_config(), ppo_env_config(5, 2), ppo_session_config(H.session_folder('surreal_amd_test'))
     lc.algo.rnn.if_rnn_policy = False
     lc.algo.n_step, lc.algo.stride = 3, 3
     lc.model.actor_fc_hidden_sizes = lc.model.critic_fc_hidden_sizes = [8, 8]

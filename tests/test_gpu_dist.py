@@ -431,7 +431,9 @@ def _run_xchg(world, mode):
     return res
 
 
-@pytest.mark.parametrize('world', [2, 4, 8])
+# at most five ranks: with the test process itself, six processes then have the one GPU open, the most a shared GPU
+# allows (five also gives an odd world above four; the staging sizes up to eight ranks: test_abi_symbols.py)
+@pytest.mark.parametrize('world', [2, 4, 5])
 def test_peer_exchange_is_the_rank_ordered_sum_and_replays_in_a_graph(world):
     res = _run_xchg(world, 'protocol')
     print('\\npeer exchange, %d ranks on one GPU: memory %s, %.1f us per captured graph of 3 exchanges (2.1 MB all-reduce x 2 '

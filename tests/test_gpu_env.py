@@ -55,7 +55,7 @@ def _agent(env, cfg, hidden, pixel, seed):
     ec = ppo_env_config(D, A, pixel=cam)
     ec.obs_spec, ec.action_spec = cfg.obs_spec, cfg.action_spec       # what make_env resolved
     ec.limit_episode_length = 4
-    sc = ppo_session_config('/tmp/surreal_amd_test_gpu_env')
+    sc = ppo_session_config(H.session_folder('surreal_amd_test_gpu_env'))
     sc.tensorplex.update_schedule.training_env = 2
     np.random.seed(seed)
     ag = PPOAgent(lc, ec, sc, agent_id=3, agent_mode='training')

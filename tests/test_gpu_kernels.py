@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 import torch
 
+from helpers import session_folder
 from surreal_amd import _lib as L
 from cpu_kernels import TorchCpuKernels
 
@@ -685,7 +686,7 @@ def test_uint8_frames_stay_uint8_in_the_device_replay(K):
     uniform gather return the frames bit-exact and still uint8 -- what the CNN stem's im2col reads"""
     from surreal_amd.replay import FIFOReplay, UniformReplay
     from surreal_amd.main.ppo_configs import ppo_learner_config, ppo_env_config, ppo_session_config
-    lc, ec, sc = ppo_learner_config(), ppo_env_config(6, 2), ppo_session_config('/tmp/surreal_amd_test')
+    lc, ec, sc = ppo_learner_config(), ppo_env_config(6, 2), ppo_session_config(session_folder('surreal_amd_test'))
     lc.replay.memory_size, lc.replay.batch_size = 13, 4
     g = torch.Generator().manual_seed(3)
     frames = torch.randint(0, 255, (10, 4, 3, 12, 12), generator=g).to(torch.uint8).cuda()
@@ -1484,7 +1485,7 @@ def test_window_cut_fifo_round_trip_at_baseline_size(K):
     venv.slot = T
     lc = ppo_learner_config()
     lc.algo.n_step, lc.replay.batch_size, lc.replay.memory_size = T, n, 2 * n
-    ec, sc = ppo_env_config(D, A), ppo_session_config('/tmp/x')
+    ec, sc = ppo_env_config(D, A), ppo_session_config(session_folder('x'))
     for zero_copy in (False, True):
         f = FIFOReplay(lc, ec, sc)
         slots = f.reserve_batch(n, venv.window_shapes(T)) if zero_copy else None
@@ -1558,7 +1559,7 @@ def _rollout_setup(n, D, A, hidden, T, episode_len, use_z, deterministic, seed):
     lc.algo.rnn.if_rnn_policy = False
     lc.algo.use_z_filter = use_z
     lc.model.actor_fc_hidden_sizes = lc.model.critic_fc_hidden_sizes = list(hidden)
-    ec, sc = ppo_env_config(D, A), ppo_session_config('/tmp/surreal_amd_test_rollout')
+    ec, sc = ppo_env_config(D, A), ppo_session_config(session_folder('surreal_amd_test_rollout'))
     agent = PPOAgent(lc, ec, sc, agent_id=1, agent_mode='eval_deterministic_local' if deterministic else 'training')
     agent.model.load_params(synthetic.make_ppo_params(D, A, hidden=tuple(hidden), seed=seed, final_scale=2.0,
                                                       log_sig_spread=0.4))
@@ -1667,7 +1668,7 @@ def test_rollout_recorded_straight_into_the_replay_slots(K, n, D, A, hidden, T):
     lc = ppo_learner_config()
     lc.algo.n_step = lc.algo.stride = T
     lc.replay.batch_size, lc.replay.memory_size = n, 2 * n
-    ec, sc = ppo_env_config(D, A), ppo_session_config('/tmp/surreal_amd_test_rollout_into')
+    ec, sc = ppo_env_config(D, A), ppo_session_config(session_folder('surreal_amd_test_rollout_into'))
 
     def three_launch_path():
         venv = SyntheticVecEnv(n, D, A, episode_len=T, seeds=list(range(n)))

@@ -144,7 +144,7 @@ def test_experience_chunks_from_gpu_agents_feed_the_learner():
     lc.model.actor_fc_hidden_sizes = lc.model.critic_fc_hidden_sizes = [24, 16]
     lc.parameter_publish.exp_interval = 4
     lc.parameter_publish.min_publish_interval = 0.0
-    ec, sc = ppo_env_config(D, A), ppo_session_config('/tmp/surreal_amd_test_gpu_wire')
+    ec, sc = ppo_env_config(D, A), ppo_session_config(H.session_folder('surreal_amd_test_gpu_wire'))
     ec.limit_episode_length = 11
     replay = FIFOReplay(lc, ec, sc)
     learner = PPOLearner(lc, ec, sc)

@@ -47,7 +47,7 @@ def configs(B=2, N=4, stride=2, D=2, A=1, memory=4):
     lc.replay.batch_size, lc.replay.memory_size, lc.replay.sampling_start_size = B, memory, B
     lc.model.actor_fc_hidden_sizes = [24, 16]
     lc.model.critic_fc_hidden_sizes = [24, 16]
-    return lc, ppo_env_config(D, A), ppo_session_config('/tmp/surreal_amd_test')
+    return lc, ppo_env_config(D, A), ppo_session_config(H.session_folder('surreal_amd_test'))
 
 
 def test_fifo_replay_matches_reference():
@@ -643,7 +643,7 @@ def test_ddpg_agent_parameter_noise_in_the_fetch_path(cpu_double):
     lc.algo.exploration.param_noise_type = 'adaptive_normal'
     lc.algo.exploration.param_noise_sigma = 0.05
     lc.replay.batch_size = 4
-    ec, sc = ddpg_env_config(D, A), ddpg_session_config()
+    ec, sc = ddpg_env_config(D, A), ddpg_session_config(H.session_folder('surreal_amd_ddpg'))
     learner = DDPGLearner(lc, ec, sc)
     ag = DDPGAgent(lc, ec, sc, agent_id=1, agent_mode='training')
     ag.attach_learner(learner)
@@ -698,7 +698,7 @@ def test_aggregation_pool_fills_disjoint_row_ranges_of_one_shared_slot():
     pool = AggregationPool(stager, 3, synthetic.SyntheticExperienceSource(B, N, D, A, seed0=40, distinct=2, fresh=True),
                            functools.partial(ppo_aggregate_factory, dict(ec.obs_spec), dict(ec.action_spec)))
     try:
-        pf = PooledDataPrefetcher(ppo_session_config('/tmp/smx_pool_test'), B, pool)
+        pf = PooledDataPrefetcher(ppo_session_config(H.session_folder('smx_pool_test')), B, pool)
         pf.start()
         for k in range(4):
             got = pf.get()

@@ -268,7 +268,7 @@ def test_agent_replay_learner_loop_over_the_wire_formats(cpu_double):
     lc.model.actor_fc_hidden_sizes = lc.model.critic_fc_hidden_sizes = [24, 16]
     lc.parameter_publish.exp_interval = 3
     lc.parameter_publish.min_publish_interval = 0.0
-    ec, sc = ppo_env_config(D, A), ppo_session_config('/tmp/surreal_amd_test_wire')
+    ec, sc = ppo_env_config(D, A), ppo_session_config(H.session_folder('surreal_amd_test_wire'))
     ec.limit_episode_length = 11
     replay = FIFOReplay(lc, ec, sc)
     learner = PPOLearner(lc, ec, sc)

@@ -32,7 +32,7 @@ def check_reference_chunk_to_learn(expect_cuda):
     lc.algo.rnn.if_rnn_policy = False
     lc.replay.batch_size, lc.replay.memory_size, lc.replay.sampling_start_size = B, 16, B
     lc.model.actor_fc_hidden_sizes = lc.model.critic_fc_hidden_sizes = [24, 16]
-    ec, sc = ppo_env_config(D, A), ppo_session_config('/tmp/surreal_amd_test_gpu_wire_f2')
+    ec, sc = ppo_env_config(D, A), ppo_session_config(H.session_folder('surreal_amd_test_gpu_wire_f2'))
     S.set_global_serializer(pickle.dumps, pickle.loads)       # what the fixture was written with (see its generator)
     replay = FIFOReplay(lc, ec, sc)
     ExperienceCollector(replay._insert_wrapper).recv(fx['chunk'])
@@ -87,7 +87,7 @@ def check_host_fed_learner(expect_cuda):
     lc.algo.rnn.if_rnn_policy = False
     lc.replay.batch_size, lc.replay.memory_size, lc.replay.sampling_start_size = B, B * iters, B
     lc.model.actor_fc_hidden_sizes = lc.model.critic_fc_hidden_sizes = [24, 16]
-    ec, sc = ppo_env_config(D, A), ppo_session_config('/tmp/surreal_amd_test_host_fed')
+    ec, sc = ppo_env_config(D, A), ppo_session_config(H.session_folder('surreal_amd_test_host_fed'))
     params = synthetic.make_ppo_params(D, A, hidden=(24, 16), seed=3, final_scale=2.0, log_sig_spread=0.3)
     zstate = synthetic.make_zfilter_state(D, seed=4)
     rs = np.random.RandomState(8)
@@ -151,7 +151,7 @@ def check_preprocess_override_same_batches(expect_cuda):
     lc.algo.rnn.if_rnn_policy = False
     lc.replay.batch_size = B
     lc.model.actor_fc_hidden_sizes = lc.model.critic_fc_hidden_sizes = [16, 8]
-    ec, sc = ppo_env_config(D, A), ppo_session_config('/tmp/surreal_amd_test_override')
+    ec, sc = ppo_env_config(D, A), ppo_session_config(H.session_folder('surreal_amd_test_override'))
     calls = []
 
     class Scaled(PPOLearner):
@@ -209,7 +209,7 @@ def check_pooled_host_fed_learner(expect_cuda, workers=3):
     lc.algo.rnn.if_rnn_policy = False
     lc.replay.batch_size = B
     lc.model.actor_fc_hidden_sizes = lc.model.critic_fc_hidden_sizes = [24, 16]
-    ec, sc = ppo_env_config(D, A), ppo_session_config('/tmp/surreal_amd_test_pooled')
+    ec, sc = ppo_env_config(D, A), ppo_session_config(H.session_folder('surreal_amd_test_pooled'))
     params = synthetic.make_ppo_params(D, A, hidden=(24, 16), seed=3, final_scale=2.0, log_sig_spread=0.3)
     zstate = synthetic.make_zfilter_state(D, seed=4)
 
