@@ -62,11 +62,22 @@ def make_ddpg_pixel_params(low_dim, A, pixel, conv_hidden, actor_hidden, critic_
     return p
 
 
+def clip_reg_kwargs(hyper):
+    """the golden cases' short keys (actor_clip, critic_clip, actor_reg, critic_reg) as OracleDDPGLearner arguments"""
+    return dict(actor_gradient_value_clip=hyper.get('actor_clip', 1.0),
+                critic_gradient_value_clip=hyper.get('critic_clip', 5.0),
+                actor_regularization=hyper.get('actor_reg', 0.0), critic_regularization=hyper.get('critic_reg', 0.0))
+
+
 class OracleDDPGModel(object):
     def __init__(self, params):
         self.p = collections.OrderedDict(
             (k, torch.tensor(np.asarray(v), dtype=torch.float32).clone().requires_grad_(True))
             for k, v in params.items())
+
+    def critic_net_params(self):
+        # what the critic's clip_grad_value reaches: self.model.critic alone, not the perception (ddpg.py:308-309)
+        return [v for k, v in self.p.items() if k.startswith('critic.')]
 
     def actor_params(self):
         return [v for k, v in self.p.items() if k.startswith('actor.')]
@@ -192,7 +203,7 @@ class OracleDDPGLearner(object):
         critic_loss = self.critic_criterion(y_policy, y)
         critic_loss.backward()
         if self.clip_critic_gradient:
-            nn.utils.clip_grad_value_(m.critic_params(), self.critic_clip)
+            nn.utils.clip_grad_value_(m.critic_net_params(), self.critic_clip)
         self.critic_optim.step()
         if self.use_double_critic:                               # ddpg.py:312-319 (critic_loss is overwritten)
             for q in self.model2.critic_params():
@@ -200,7 +211,7 @@ class OracleDDPGLearner(object):
             critic_loss = self.critic_criterion(y_policy2, y)
             critic_loss.backward()
             if self.clip_critic_gradient:
-                nn.utils.clip_grad_value_(self.model2.critic_params(), self.critic_clip)
+                nn.utils.clip_grad_value_(self.model2.critic_net_params(), self.critic_clip)
             self.critic_optim2.step()
         for q in m.actor_params():
             q.grad = None

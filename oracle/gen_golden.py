@@ -311,6 +311,18 @@ _case('cfg5_rnn_clip', S['cfg5_synth1024'], (300, 200), dict(ppo_mode='clip', if
 _case('b1024_d17_rnn_adapt', dict(B=1024, N=128, D=17, A=6), (300, 200),
       dict(ppo_mode='adapt', if_rnn_policy=True, horizon=5, kl_target=1e9), rnn_hidden=100)
 
+# Adam's weight decay (actor_regularization / critic_regularization, ppo.py:159-168) on, with a gradient-norm clip that binds
+# in every epoch (max norm 0.05), and the same without clip_grad_norm_ (no grad_norm_* statistics then); the LSTM case covers
+# the stem's parameters, which step with the actor's optimiser
+_REG = dict(actor_regularization=0.01, critic_regularization=0.02)
+_case('cfg2_reg_clipnorm', S['cfg2_cheetah64'], (300, 200),
+      dict(ppo_mode='clip', kl_target=1e9, actor_gradient_norm_clip=0.05, critic_gradient_norm_clip=0.05, **_REG))
+_case('cfg2_reg_noclip', S['cfg2_cheetah64'], (300, 200),
+      dict(ppo_mode='adapt', clip_actor_gradient=False, clip_critic_gradient=False, **_REG))
+_case('tiny_rnn_reg_adapt', S['tiny'], (24, 16),
+      dict(ppo_mode='adapt', if_rnn_policy=True, horizon=4, actor_gradient_norm_clip=0.05, critic_gradient_norm_clip=0.05,
+           actor_regularization=0.05, critic_regularization=0.1), rnn_hidden=12)
+
 
 def checksum(params):
     return {k: [float(np.sum(v, dtype=np.float64)), float(np.sum(v.astype(np.float64) ** 2))]

@@ -118,8 +118,8 @@ def build_ref(params, D, A, ah, ch, hyper, params2=None, pixel=None, conv_hidden
     L.use_double_critic = bool(hyper.get('double_critic', False))
     L.use_action_regularization = bool(hyper.get('action_reg', False))
     L.gpu_ids, L._num_gpus = 'cpu', 0
-    L.clip_actor_gradient, L.actor_gradient_clip_value = True, 1.0
-    L.clip_critic_gradient, L.critic_gradient_clip_value = hyper.get('clip_critic', False), 5.0
+    L.clip_actor_gradient, L.actor_gradient_clip_value = True, hyper.get('actor_clip', 1.0)
+    L.clip_critic_gradient, L.critic_gradient_clip_value = hyper.get('clip_critic', False), hyper.get('critic_clip', 5.0)
     L.action_dim = A
     obs_spec = collections.OrderedDict()
     if pixel is not None:                                   # ddpg_net.py:37-44: the CNN perception
@@ -133,13 +133,16 @@ def build_ref(params, D, A, ah, ch, hyper, params2=None, pixel=None, conv_hidden
     inject(L.model, params)
     inject(L.model_target, params)
     L.critic_criterion = torch.nn.MSELoss()
-    L.critic_optim = torch.optim.Adam(L.model.get_critic_parameters(), lr=hyper['lr_critic'])
+    L.critic_optim = torch.optim.Adam(L.model.get_critic_parameters(), lr=hyper['lr_critic'],
+                                      weight_decay=hyper.get('critic_reg', 0.0))
     if L.use_double_critic:                                # ddpg.py:119-147, 162-166
         L.model2, L.model_target2 = mk(critic_only=True), mk(critic_only=True)
         inject(L.model2, params2)
         inject(L.model_target2, params2)
-        L.critic_optim2 = torch.optim.Adam(L.model2.get_critic_parameters(), lr=hyper['lr_critic'])
-    L.actor_optim = torch.optim.Adam(L.model.get_actor_parameters(), lr=hyper['lr_actor'])
+        L.critic_optim2 = torch.optim.Adam(L.model2.get_critic_parameters(), lr=hyper['lr_critic'],
+                                           weight_decay=hyper.get('critic_reg', 0.0))
+    L.actor_optim = torch.optim.Adam(L.model.get_actor_parameters(), lr=hyper['lr_actor'],
+                                     weight_decay=hyper.get('actor_reg', 0.0))
     L.target_update_type = hyper['target_update_type']
     L.target_update_counter = 0
     L.target_update_interval = hyper['target_update_interval']
@@ -200,6 +203,29 @@ CASES = {
     'cfg3_cheetah512_x502': dict(B=512, D=17, A=6, ah=(300, 200), ch=(400, 300), iters=502,
                                  hyper=dict(gamma=0.99, n_step=3, lr_actor=1e-4, lr_critic=1e-3,
                                             target_update_type='hard', target_update_interval=500)),
+    # weight decay (actor_regularization / critic_regularization: Adam's weight_decay, ddpg.py:152-166) on, and value
+    # clips that bind (clip near the median |g| of the case's first iterations: about half the elements clamped): the clamp, then the
+    # decay, then the step, in every Adam path.  Four iterations or more: Adam's first step is sign(g) * lr whatever the
+    # clip, the clip shows from the second.  tiny_reg_clip and mid_reg_clip take the row schedule.
+    'tiny_reg_clip': dict(B=16, D=5, A=2, ah=(24, 16), ch=(32, 24), iters=5,
+                          hyper=dict(gamma=0.99, n_step=3, lr_actor=1e-3, lr_critic=1e-2, target_update_type='hard',
+                                     target_update_interval=2, clip_critic=True, actor_clip=2e-4, critic_clip=5e-3,
+                                     actor_reg=0.05, critic_reg=0.1)),
+    # the perception CNN steps with the critic's optimiser (decay included) but is not clipped: the reference clips
+    # self.model.critic only (ddpg.py:308-309, 318-319)
+    'tiny_pixel_reg_clip': dict(B=12, D=4, A=2, ah=(24, 16), ch=(32, 24), iters=5, pixel=(2, 20, 24), conv_hidden=8,
+                                hyper=dict(gamma=0.99, n_step=3, lr_actor=1e-3, lr_critic=1e-2,
+                                           target_update_type='hard', target_update_interval=2, clip_critic=True,
+                                           actor_clip=2e-5, critic_clip=1e-3, actor_reg=0.02, critic_reg=0.05)),
+    'tiny_ln_td3_reg_clip': dict(B=21, D=7, A=3, ah=(24, 16), ch=(32, 24), iters=5,
+                                 hyper=dict(gamma=0.95, n_step=2, lr_actor=1e-3, lr_critic=1e-2, layernorm=True,
+                                            double_critic=True, action_reg=True, target_update_type='soft',
+                                            target_update_interval=1, tau=0.1, clip_critic=True, actor_clip=8e-3,
+                                            critic_clip=8e-2, actor_reg=0.05, critic_reg=0.1)),
+    'mid_reg_clip': dict(B=130, D=17, A=6, ah=(100, 68), ch=(132, 100), iters=4,
+                         hyper=dict(gamma=0.99, n_step=3, lr_actor=1e-4, lr_critic=1e-3, target_update_type='soft',
+                                    target_update_interval=1, tau=0.05, clip_critic=True, actor_clip=1.2e-4,
+                                    critic_clip=4e-3, actor_reg=0.01, critic_reg=0.02)),
 }
 
 
@@ -224,7 +250,7 @@ def main(only=None):
             use_action_regularization=hyper.get('action_reg', False), params2=params2, batch_size=c['B'],
             params=params, gamma=hyper['gamma'], n_step=hyper['n_step'], lr_actor=hyper['lr_actor'],
             lr_critic=hyper['lr_critic'], clip_critic_gradient=hyper.get('clip_critic', False),
-            target_update_type=hyper['target_update_type'],
+            **ddpg_oracle.clip_reg_kwargs(hyper), target_update_type=hyper['target_update_type'],
             target_update_interval=hyper['target_update_interval'], tau=hyper.get('tau', 1e-3))
         traces = []
         for it in range(c['iters']):

@@ -2,6 +2,7 @@
 // clip_adam_kernel) and by the weight-gradient launch that steps its own tiles (smx_gemm.hip: gemm32_adam_kernel) --
 // one source, so that both form the same bits.  Included inside an anonymous namespace, after smx_epoch_pack.inc.h.
 //   torch/nn/utils/clip_grad.py: clip_coef = max_norm / (total_norm + 1e-6), clamped to <= 1, always multiplied in
+//   (a NaN or inf gradient makes the norm NaN / inf and the step NaN, as in torch)
 //   torch/optim/adam.py _single_tensor_adam (the reference's optimisers: surreal/learner/ppo.py:120-135)
 #pragma once
 
@@ -36,7 +37,7 @@ __device__ __forceinline__ AdamCoef adam_coef_pre(const smx_ppo_ctrl_t& C, int w
 __device__ __forceinline__ float clip_coef(const smx_ppo_ctrl_t& C, int which, float norm) {
     const float max_norm = which ? C.critic_max_norm : C.actor_max_norm;
     float coef = 1.0f;
-    if (max_norm > 0.f) coef = fminf(max_norm / (norm + 1e-6f), 1.0f);
+    if (max_norm > 0.f) coef = norm == norm ? fminf(max_norm / (norm + 1e-6f), 1.0f) : norm;   // torch keeps a NaN norm
     return coef;
 }
 __device__ __forceinline__ AdamCoef adam_coef(const smx_ppo_ctrl_t& C, int which, float norm) {

@@ -42,7 +42,7 @@ __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ theta,
     const long i = (long)blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
     float g = grads[i];
-    if (clip_value > 0.f) g = fminf(fmaxf(g, -clip_value), clip_value);   // clip_grad_value_
+    if (clip_value > 0.f && g == g) g = fminf(fmaxf(g, -clip_value), clip_value);   // clip_grad_value_
     const float p = theta[i];
     if (wd != 0.f) g = g + wd * p;
     float mi = m[i], vi = v[i];
@@ -76,7 +76,7 @@ __global__ __launch_bounds__(256) void adam_dev_kernel(float* __restrict__ theta
     const float neg_step_size = coef[0], bc2_sqrt = coef[1];
     const float w1 = (float)(1.0 - 0.9), b2f = (float)0.999, w2 = (float)(1.0 - 0.999), eps = 1e-8f;
     float g = grads[i];
-    if (clip_value > 0.f) g = fminf(fmaxf(g, -clip_value), clip_value);   // clip_grad_value_
+    if (clip_value > 0.f && g == g) g = fminf(fmaxf(g, -clip_value), clip_value);   // clip_grad_value_
     const float p = theta[i];
     if (wd != 0.f) g = g + wd * p;
     float mi = m[i], vi = v[i];

@@ -429,7 +429,7 @@ __global__ __launch_bounds__(256) void ddpg_rows_update_kernel(UArgs U) {
     const float neg_step_size = coef[0], bc2_sqrt = coef[1];
     const float w1 = (float)(1.0 - 0.9), b2f = (float)0.999, w2 = (float)(1.0 - 0.999), eps = 1e-8f;
     float g = U.grads[i];
-    if (U.clip_value > 0.f) g = fminf(fmaxf(g, -U.clip_value), U.clip_value);   // clip_grad_value_
+    if (U.clip_value > 0.f && g == g) g = fminf(fmaxf(g, -U.clip_value), U.clip_value);   // clip_grad_value_
     const float p = U.theta[i];
     if (U.wd != 0.f) g = g + U.wd * p;
     float mi = U.m[i], vi = U.v[i];
@@ -508,7 +508,7 @@ __device__ __forceinline__ void ddpg_step_element(const UArgs& U, long i, float 
                                                   float neg_step_size, float bc2_sqrt, int upd, float& pn, float& tn,
                                                   bool& tw) {
     const float w1 = (float)(1.0 - 0.9), b2f = (float)0.999, w2 = (float)(1.0 - 0.999), eps = 1e-8f;
-    if (U.clip_value > 0.f) g = fminf(fmaxf(g, -U.clip_value), U.clip_value);
+    if (U.clip_value > 0.f && g == g) g = fminf(fmaxf(g, -U.clip_value), U.clip_value);
     if (U.wd != 0.f) g = g + U.wd * p;
     mi = mi + w1 * (g - mi);
     vi = vi * b2f + w2 * (g * g);

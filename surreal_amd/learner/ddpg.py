@@ -552,8 +552,9 @@ class DDPGLearner(Learner):
         K.adam_step_dev(m.critic_flat, ws.grads_c, self.critic_exp_avg, self.critic_exp_avg_sq,
                         ws.lr[1:2], ws.step, self.critic_regularization, self.critic_gradient_clip_value)
         if self.is_pixel_input:
+            # the critic's optimiser and decay, but no clip: ddpg.py:308-309 clips self.model.critic alone
             K.adam_step_dev(m.perception_flat, ws.grads_p, self.perc_exp_avg, self.perc_exp_avg_sq,
-                            ws.lr[1:2], ws.step, self.critic_regularization, self.critic_gradient_clip_value)
+                            ws.lr[1:2], ws.step, self.critic_regularization, 0.0)
         ws.q_policy.copy_(ws.q)
         if self.use_double_critic:           # ddpg.py:312-319
             m2 = self.model2
@@ -566,8 +567,9 @@ class DDPGLearner(Learner):
             K.adam_step_dev(m2.critic_flat, ws.grads_c2, self.critic2_exp_avg, self.critic2_exp_avg_sq,
                             ws.lr[1:2], ws.step, self.critic_regularization, self.critic_gradient_clip_value)
             if self.is_pixel_input:
+                # the critic's optimiser and decay, but no clip: ddpg.py:308-309 clips self.model.critic alone
                 K.adam_step_dev(m2.perception_flat, ws.grads_p2, self.perc2_exp_avg, self.perc2_exp_avg_sq,
-                                ws.lr[1:2], ws.step, self.critic_regularization, self.critic_gradient_clip_value)
+                                ws.lr[1:2], ws.step, self.critic_regularization, 0.0)
             K.ddpg_stats(ws.q2, ws.y2, rewards, actions, ws.q2, ws.stats2)    # (the SECOND critic's loss is what is reported)
             self._average_over_ranks(ws.stats2[:6])
         # ---- actor update through the UPDATED critic: loss = -mean Q(s, mu(s)); the features formed before the critic
@@ -668,8 +670,9 @@ class DDPGLearner(Learner):
         K.adam_step_dev(m.critic_flat, ws.grads_c, self.critic_exp_avg, self.critic_exp_avg_sq,
                         ws.lr[1:2], ws.step, self.critic_regularization, self.critic_gradient_clip_value)
         if self.is_pixel_input:
+            # the critic's optimiser and decay, but no clip: ddpg.py:308-309 clips self.model.critic alone
             K.adam_step_dev(m.perception_flat, ws.grads_p, self.perc_exp_avg, self.perc_exp_avg_sq,
-                            ws.lr[1:2], ws.step, self.critic_regularization, self.critic_gradient_clip_value)
+                            ws.lr[1:2], ws.step, self.critic_regularization, 0.0)
         ws.q_policy.copy_(ws.q)
         if self.use_double_critic:                       # ddpg.py:312-319
             m2 = self.model2
@@ -682,8 +685,9 @@ class DDPGLearner(Learner):
             K.adam_step_dev(m2.critic_flat, ws.grads_c2, self.critic2_exp_avg, self.critic2_exp_avg_sq,
                             ws.lr[1:2], ws.step, self.critic_regularization, self.critic_gradient_clip_value)
             if self.is_pixel_input:
+                # the critic's optimiser and decay, but no clip: ddpg.py:308-309 clips self.model.critic alone
                 K.adam_step_dev(m2.perception_flat, ws.grads_p2, self.perc2_exp_avg, self.perc2_exp_avg_sq,
-                                ws.lr[1:2], ws.step, self.critic_regularization, self.critic_gradient_clip_value)
+                                ws.lr[1:2], ws.step, self.critic_regularization, 0.0)
             # the reference reports the SECOND critic's loss as 'critic_loss' (it overwrites the
             # variable, ddpg.py:313) and adds Q_policy2
             K.ddpg_stats(ws.q2, ws.y2, rewards, actions, ws.q2, ws.stats2)

@@ -11,7 +11,9 @@ import ddpg_oracle
 
 DDPG_CASES = ['tiny_hard', 'tiny_soft_clipcritic', 'tiny_td3_hard', 'tiny_double_soft', 'tiny_pixel_hard',
               'tiny_pixel_td3_soft', 'cfg3_cheetah512', 'tiny_ln_hard', 'ln_soft_clipcritic', 'cfg3_cheetah512_x502',
-              'tiny_ln_td3_soft', 'tiny_ln_pixel_hard', 'tiny_ln_pixel_td3_soft']
+              'tiny_ln_td3_soft', 'tiny_ln_pixel_hard', 'tiny_ln_pixel_td3_soft',
+              # weight decay on and value clips that bind (oracle/gen_golden_ddpg.py)
+              'tiny_reg_clip', 'tiny_pixel_reg_clip', 'tiny_ln_td3_reg_clip', 'mid_reg_clip']
 
 
 def load(name):
@@ -28,6 +30,10 @@ def make_learner(case, opts=None):
     lc.algo.gamma, lc.algo.n_step = h['gamma'], h['n_step']
     lc.algo.network.lr_actor, lc.algo.network.lr_critic = h['lr_actor'], h['lr_critic']
     lc.algo.network.clip_critic_gradient = h.get('clip_critic', False)
+    lc.algo.network.actor_gradient_value_clip = h.get('actor_clip', 1.0)
+    lc.algo.network.critic_gradient_value_clip = h.get('critic_clip', 5.0)
+    lc.algo.network.actor_regularization = h.get('actor_reg', 0.0)
+    lc.algo.network.critic_regularization = h.get('critic_reg', 0.0)
     lc.algo.network.target_update = {'type': h['target_update_type'],
                                      'interval': h['target_update_interval'], 'tau': h.get('tau', 1e-3)}
     lc.algo.network.use_double_critic = bool(h.get('double_critic', False))
@@ -147,7 +153,8 @@ def make_oracle(case):
     return ddpg_oracle.OracleDDPGLearner(
         mk(3), gamma=h['gamma'], n_step=h['n_step'], lr_actor=h['lr_actor'], lr_critic=h['lr_critic'],
         clip_critic_gradient=h.get('clip_critic', False), target_update_type=h['target_update_type'],
-        target_update_interval=h['target_update_interval'], tau=h.get('tau', 1e-3), batch_size=case['B'])
+        target_update_interval=h['target_update_interval'], tau=h.get('tau', 1e-3), batch_size=case['B'],
+        **ddpg_oracle.clip_reg_kwargs(h))
 
 
 def load_oracle_state(L, O, steps):

@@ -194,7 +194,8 @@ def make_learner(case, params, zstate, cls=None, session_overrides=None):
     for k in ('kl_target', 'epoch_policy', 'epoch_baseline'):
         if k in hyper:
             lc.algo.consts[k] = hyper[k]
-    for k in ('lr_actor', 'lr_critic'):
+    for k in ('lr_actor', 'lr_critic', 'clip_actor_gradient', 'actor_gradient_norm_clip', 'clip_critic_gradient',
+              'critic_gradient_norm_clip', 'actor_regularization', 'critic_regularization'):
         if k in hyper:
             lc.algo.network[k] = hyper[k]
     lc.replay.batch_size = shp['B']

@@ -30,7 +30,7 @@ def test_ddpg_oracle_matches_reference_golden(name):
         clip_critic_gradient=h.get('clip_critic', False), target_update_type=h['target_update_type'],
         target_update_interval=h['target_update_interval'], tau=h.get('tau', 1e-3),
         use_double_critic=h.get('double_critic', False), use_action_regularization=h.get('action_reg', False),
-        params2=params2, batch_size=c['B'])
+        params2=params2, batch_size=c['B'], **ddpg_oracle.clip_reg_kwargs(h))
     ref = json.loads(str(g['trace_json']))
     for it in range(c['iters']):
         np.random.seed(1000 + it)
@@ -45,7 +45,7 @@ def test_ddpg_learner_host_logic(name, cpu_double):
     DH.run_and_check(name)
 
 
-@pytest.mark.parametrize('name', ['tiny_hard', 'tiny_soft_clipcritic', 'cfg3_cheetah512'])
+@pytest.mark.parametrize('name', ['tiny_hard', 'tiny_soft_clipcritic', 'cfg3_cheetah512', 'tiny_reg_clip', 'mid_reg_clip'])
 def test_ddpg_learner_host_logic_both_schedules(name, cpu_double):
     """the row-block schedule's host side (the default up to 1024 rows): which buffers the two chain launches and the
     weight-gradient launches share, and WHEN the packed weight copy is refreshed -- the double works from a snapshot of

@@ -19,13 +19,16 @@ def test_ddpg_resume_across_the_hard_update_at_configs2_size():
 ROWS_CASES = ['tiny_hard', 'tiny_soft_clipcritic', 'cfg3_cheetah512']     # low-dimensional, one critic, no LayerNorm
 
 
-@pytest.mark.parametrize('name', ROWS_CASES)
+@pytest.mark.parametrize('name', ROWS_CASES + ['tiny_reg_clip', 'mid_reg_clip'])
 def test_ddpg_learner_matches_reference_golden_both_schedules(name):
-    """the reference goldens through the row-block launches (the default up to 1024 rows) and through the level schedule
-    (session_config.learner.ddpg_row_schedule = False)"""
+    """the reference goldens through the row-block launches (the default up to 1024 rows), through the level schedule
+    (session_config.learner.ddpg_row_schedule = False) and layer by layer (ddpg_level_schedule = False as well); the
+    *_reg_clip cases carry weight decay and binding value clips into every one of these Adam paths"""
     L = DH.run_and_check(name)
     assert getattr(L._ws, 'rows_args', None) is not None
     L = DH.run_and_check(name, opts={'ddpg_row_schedule': False})
+    assert getattr(L._ws, 'rows_args', None) is None
+    L = DH.run_and_check(name, opts={'ddpg_row_schedule': False, 'ddpg_level_schedule': False})
     assert getattr(L._ws, 'rows_args', None) is None
     # ... and with the weight gradients as their own launch in front of the update launch (what several ranks run)
     L = DH.run_and_check(name, opts={'ddpg_rows_fused_update': False})
