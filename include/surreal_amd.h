@@ -1042,6 +1042,60 @@ typedef struct smx_synth_rollout {
 int32_t smx_synth_rollout_supported(int32_t D, int32_t H1, int32_t H2, int32_t A);
 int smx_synth_rollout_f32(const smx_synth_rollout_t* args, smx_stream_t stream);
 
+/* DDPG's acting loop on the device, recorded as n-step transitions straight into the uniform replay's ring: per step and
+ * actor a (all actors share the episode clock tau = args->t at the first step)
+ *   mu = tanh(MLP(s))                                      DDPGModel.actor (surreal/model/ddpg_net.py:13-95)
+ *   act = clip(mu, -1, 1), then                            DDPGAgent.act (surreal/agent/ddpg_agent.py:155-184)
+ *     gaussian: act = (float)((double)act + (0.0 + sigma_a * eps))                  (action_noise.py:14-23)
+ *     OU:       x = (x + (theta * (0 - x)) * dt) + (sigma_a * root_dt) * eps;        (action_noise.py:26-39; x = 0
+ *               act = (float)((double)act + x)                 when tau == 0: pre_episode, ddpg_agent.py:205-208)
+ *   act = clip(act, -1, 1); the synthetic environment step of smx_synth_env_step_f32
+ *   tau >= n_step - 1: transition j = tau - n_step + 1 closes (ExpSenderWrapperSSARNStepBootstrap,
+ *     surreal/env/exp_sender_wrapper.py:72-112): obs = s_j, actions = a_j, obs_next = s_{tau+1} (the terminal
+ *     observation before a reset), dones = d_tau, rewards = (float)(((r_j + g[e] r_{j+1}) + g[e] r_{j+2}) + ...) in
+ *     fp64 with the wrapper's discount exponents, g = gpow [n_step] (gamma ** e, fp64).  The k-th closing step of a call
+ *     writes actor a to row (cursor + k n + a) % capacity of obs / obs_next [capacity, D], actions [capacity, A],
+ *     rewards / dones [capacity]; the caller makes n * (closing steps) <= capacity (checked: SMX_E_SHAPE).
+ * carry_obs [n, n_step, D], carry_act [n, n_step, A], carry_rew [n, n_step]: the open transitions (slot tau % n_step),
+ * ou [n, A] (fp64): the OU processes -- both carry over between calls.  eps [steps, n, A] standard normals, sigmas [n]
+ * (fp64); neither is read with noise_type SMX_DDPG_NOISE_NONE (the deterministic agent modes). */
+#define SMX_DDPG_NOISE_NONE 0
+#define SMX_DDPG_NOISE_GAUSSIAN 1
+#define SMX_DDPG_NOISE_OU 2
+struct smx_ddpg_rollout {
+    const smx_mlp3_t* net;                 /* the actor (smx_synth_ddpg_rollout_f32 only) */
+    const float* packed;                   /* smx_epoch_pack_f32 of net (smx_synth_ddpg_rollout_f32 only) */
+    int32_t n, D, A, steps;
+    int32_t t, episode_len, n_step, noise_type;
+    int32_t actors_per_workgroup;          /* 4 | 8 | 16, 0: the smallest whose grid fits the CUs once */
+    int32_t reserved;
+    const float* eps;
+    const double* sigmas;
+    double theta, dt, root_dt;
+    const double* gpow;
+    double* ou;
+    float* state;                          /* [n, D] in / out */
+    const float* init_state;
+    float* carry_obs;
+    float* carry_act;
+    float* carry_rew;
+    float* obs;
+    float* obs_next;
+    float* actions;
+    float* rewards;
+    float* dones;
+    int64_t cursor, capacity;
+};
+/* shapes smx_synth_ddpg_rollout_f32 takes: A <= 32, H1 and H2 multiples of 4 up to 640, D <= 512 */
+int32_t smx_synth_ddpg_rollout_supported(int32_t D, int32_t H1, int32_t H2, int32_t A);
+/* all `steps` steps in ONE launch: a workgroup owns 4, 8 or 16 actors for the whole rollout, the actor's layers run on
+ * v_mfma_f32_4x4x1 from `packed` (smx_rows4_mma.inc.h: mu equals smx_epoch_forward_f32's to fp32 rounding of the layer
+ * sums; every block size gives the same bits) */
+int smx_synth_ddpg_rollout_f32(const struct smx_ddpg_rollout* args, smx_stream_t stream);
+/* ONE step (args->steps is ignored; eps [n, A]; the step's closing transitions go to the rows from args->cursor) given
+ * the actor's output mu [n, A] (row stride ld_mu) from any forward pass */
+int smx_synth_ddpg_step_f32(const struct smx_ddpg_rollout* args, const float* mu, int64_t ld_mu, smx_stream_t stream);
+
 /* ---------------------------------------------------------------------------
  * Data-parallel exchange between the learner ranks of one node over IPC-mapped peer buffers (xGMI loads): the
  * collectives N sharded learners need to equal the single reference learner -- the per-epoch

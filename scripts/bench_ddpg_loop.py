@@ -1,0 +1,142 @@
+"""DDPG's off-policy loop on one GPU with the actors on the device: SyntheticVecEnv.ddpg_rollout_into (act, explore,
+step and record n-step transitions straight into the uniform replay's ring), then sample_batch into the learner's
+staging buffers and learn().
+
+  1. the rollout alone, n actors x T steps, D -> H1 -> H2 -> A (default 1024 x 128, 17 -> 300 -> 200 -> 6), into a ring
+     of 1e6 rows: the persistent kernel (one launch) and the per-step path (one actor forward + one step launch per
+     step): ms per rollout, env-steps/s, and the share of the FP32 matrix peak the actor's FLOPs
+     2 n T (D H1 + H1 H2 + H2 A) take;
+  2. the loop: one rollout chunk, then `--learn-iters` learn iterations at batch 512 sampled with
+     sample_batch(512, out=learner.staging_fields(512)): env-steps/s and learner samples/s over the whole loop.
+
+Prints one JSON line per measurement (and a summary line)."""
+import argparse
+import json
+import os
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+import torch  # noqa: E402
+
+from surreal_amd.agent import DDPGAgent  # noqa: E402
+from surreal_amd.env.synthetic_env import SyntheticVecEnv  # noqa: E402
+from surreal_amd.learner.ddpg import DDPGLearner  # noqa: E402
+from surreal_amd.main.ddpg_configs import ddpg_learner_config, ddpg_env_config, ddpg_session_config  # noqa: E402
+from surreal_amd.replay import UniformReplay  # noqa: E402
+
+FP32_MATRIX_PEAK = 157.3e12        # MI355X, FLOP/s
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument('--actors', type=int, default=1024)
+    ap.add_argument('--steps', type=int, default=128)
+    ap.add_argument('--obs-dim', type=int, default=17)
+    ap.add_argument('--hidden', type=int, nargs=2, default=[300, 200])
+    ap.add_argument('--action-dim', type=int, default=6)
+    ap.add_argument('--capacity', type=int, default=1000000)
+    ap.add_argument('--reps', type=int, default=10)
+    ap.add_argument('--noise', default='ou_noise', choices=['normal', 'ou_noise'])
+    ap.add_argument('--loop-chunks', type=int, default=8)
+    ap.add_argument('--chunk-steps', type=int, default=16)
+    ap.add_argument('--learn-iters', type=int, default=16)
+    ap.add_argument('--batch', type=int, default=512)
+    args = ap.parse_args()
+    n, T, D, A = args.actors, args.steps, args.obs_dim, args.action_dim
+    H1, H2 = args.hidden
+    lc = ddpg_learner_config()
+    lc.model.actor_fc_hidden_sizes = [H1, H2]
+    lc.algo.exploration.noise_type = args.noise
+    lc.replay.memory_size = args.capacity
+    lc.replay.batch_size = args.batch
+    ec, sc = ddpg_env_config(D, A, num_agents=n), ddpg_session_config()
+    agent = DDPGAgent(lc, ec, sc, agent_id=0, agent_mode='training')
+    flops = 2.0 * n * T * (D * H1 + H1 * H2 + H2 * A)
+    venv = SyntheticVecEnv(n, D, A, episode_len=1000, device='cuda')
+    eps = torch.randn(T, n, A, device='cuda')
+    results = {}
+    for path in ('persistent', 'per_step'):
+        replay = UniformReplay(lc, ec, sc)
+        if path == 'per_step':              # the per-step path: what a LayerNorm actor or an unsupported shape takes
+            venv.K.synth_ddpg_rollout_supported = lambda net: False
+        try:
+            venv.reset()
+            venv.ddpg_rollout_into(agent, replay, T, eps=eps)           # warm-up (tables, packed copy, code)
+            torch.cuda.synchronize()
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            t0 = time.perf_counter()
+            e0.record()
+            for _ in range(args.reps):
+                venv.ddpg_rollout_into(agent, replay, T, eps=eps)
+            e1.record()
+            torch.cuda.synchronize()
+            wall = (time.perf_counter() - t0) / args.reps
+            dev = e0.elapsed_time(e1) / 1e3 / args.reps
+        finally:
+            if path == 'per_step':
+                del venv.K.synth_ddpg_rollout_supported
+        r = {'what': 'ddpg_rollout', 'path': path, 'actors': n, 'steps': T, 'shape': [D, H1, H2, A],
+             'ms_per_rollout': round(dev * 1e3, 4), 'wall_ms_per_rollout': round(wall * 1e3, 4),
+             'env_steps_per_s': n * T / dev, 'actor_tflops': flops / dev / 1e12,
+             'share_of_fp32_matrix_peak': flops / dev / FP32_MATRIX_PEAK, 'replay_rows': len(replay)}
+        results[path] = r
+        print(json.dumps(r), flush=True)
+
+    # ---- the off-policy loop: rollout chunk -> learn iterations from the ring ------------------------------------------
+    learner = DDPGLearner(lc, ec, sc)
+    replay = UniformReplay(lc, ec, sc)
+    venv.reset()
+    B, Tc = args.batch, args.chunk_steps
+    ceps = torch.randn(Tc, n, A, device='cuda')
+    venv.ddpg_rollout_into(agent, replay, Tc, eps=ceps)
+    stage = learner.staging_fields(B)
+
+    def learn_once():
+        f = replay.sample_batch(B, out=stage)
+        return learner.learn({'obs': {'low_dim': {'flat_inputs': f['obs']}},
+                              'obs_next': {'low_dim': {'flat_inputs': f['obs_next']}}, 'actions': f['actions'],
+                              'rewards': f['rewards'].view(B, 1), 'dones': f['dones'].view(B, 1)})
+    for _ in range(8):
+        st = learn_once()
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for _ in range(args.loop_chunks):
+        venv.ddpg_rollout_into(agent, replay, Tc, eps=ceps)
+        for _ in range(args.learn_iters):
+            st = learn_once()
+    st = dict(st)
+    torch.cuda.synchronize()
+    wall = time.perf_counter() - t0
+    loop = {'what': 'ddpg_offpolicy_loop', 'actors': n, 'chunk_steps': Tc, 'learn_iters_per_chunk': args.learn_iters,
+            'batch': B, 'chunks': args.loop_chunks, 'wall_s': round(wall, 4),
+            'env_steps_per_s': n * Tc * args.loop_chunks / wall,
+            'learner_samples_per_s': B * args.learn_iters * args.loop_chunks / wall,
+            'critic_loss': float(st['critic_loss']), 'replay_rows': len(replay)}
+    print(json.dumps(loop), flush=True)
+    # the persistent kernel at each forced block size (the automatic pick above: 4 actors per workgroup up to one
+    # workgroup per CU)
+    for apw in (4, 8, 16):
+        replay = UniformReplay(lc, ec, sc)
+        venv.reset()
+        venv.ddpg_rollout_into(agent, replay, T, eps=eps, actors_per_workgroup=apw)
+        torch.cuda.synchronize()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(args.reps):
+            venv.ddpg_rollout_into(agent, replay, T, eps=eps, actors_per_workgroup=apw)
+        e1.record()
+        torch.cuda.synchronize()
+        dev = e0.elapsed_time(e1) / 1e3 / args.reps
+        print(json.dumps({'what': 'ddpg_rollout', 'path': 'persistent', 'actors_per_workgroup': apw, 'actors': n,
+                          'steps': T, 'ms_per_rollout': round(dev * 1e3, 4), 'env_steps_per_s': n * T / dev,
+                          'share_of_fp32_matrix_peak': flops / dev / FP32_MATRIX_PEAK}), flush=True)
+    speedup = results['per_step']['ms_per_rollout'] / results['persistent']['ms_per_rollout']
+    print(json.dumps({'what': 'summary', 'persistent_ms': results['persistent']['ms_per_rollout'],
+                      'per_step_ms': results['per_step']['ms_per_rollout'], 'persistent_speedup': speedup}), flush=True)
+
+
+if __name__ == '__main__':
+    main()

@@ -155,6 +155,21 @@ class SynthRollout(Structure):
                 ('rew_roll', c_void_p), ('done_roll', c_void_p), ('pd_roll', c_void_p), ('obs_last', c_void_p)]
 
 
+class DdpgRollout(Structure):
+    """struct smx_ddpg_rollout (no typedef)"""
+    _fields_ = [('net', POINTER(Mlp3)), ('packed', c_void_p), ('n', c_int32), ('D', c_int32), ('A', c_int32),
+                ('steps', c_int32), ('t', c_int32), ('episode_len', c_int32), ('n_step', c_int32),
+                ('noise_type', c_int32), ('actors_per_workgroup', c_int32), ('reserved', c_int32),
+                ('eps', c_void_p), ('sigmas', c_void_p), ('theta', c_double), ('dt', c_double), ('root_dt', c_double),
+                ('gpow', c_void_p), ('ou', c_void_p), ('state', c_void_p), ('init_state', c_void_p),
+                ('carry_obs', c_void_p), ('carry_act', c_void_p), ('carry_rew', c_void_p), ('obs', c_void_p),
+                ('obs_next', c_void_p), ('actions', c_void_p), ('rewards', c_void_p), ('dones', c_void_p),
+                ('cursor', c_int64), ('capacity', c_int64)]
+
+
+SMX_DDPG_NOISE_NONE, SMX_DDPG_NOISE_GAUSSIAN, SMX_DDPG_NOISE_OU = 0, 1, 2
+
+
 class Xchg(Structure):
     """smx_xchg_t"""
     _fields_ = [('world', c_int32), ('rank', c_int32), ('capacity', c_int64), ('peer', c_void_p * 8)]
@@ -327,6 +342,9 @@ _SIGS = {
     'smx_synth_frame_u8': (c_int32, [_P, c_int64, c_int32, c_int32, c_int32, c_int32, c_int32, _P, c_int64, _P]),
     'smx_synth_rollout_supported': (c_int32, [c_int32, c_int32, c_int32, c_int32]),
     'smx_synth_rollout_f32': (c_int32, [POINTER(SynthRollout), _P]),
+    'smx_synth_ddpg_rollout_supported': (c_int32, [c_int32, c_int32, c_int32, c_int32]),
+    'smx_synth_ddpg_rollout_f32': (c_int32, [POINTER(DdpgRollout), _P]),
+    'smx_synth_ddpg_step_f32': (c_int32, [POINTER(DdpgRollout), _P, c_int64, _P]),
     'smx_xchg_bytes': (c_int64, [c_int64, c_int32]),
     'smx_xchg_alloc': (c_int32, [c_int64, c_double, POINTER(c_void_p), POINTER(c_int32), _P]),
     'smx_xchg_free': (c_int32, [_P]),

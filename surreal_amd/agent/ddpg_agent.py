@@ -39,6 +39,7 @@ class DDPGAgent(Agent):
         self.param_noise_alpha = ex.param_noise_alpha
         self.param_noise_target_stddev = ex.param_noise_target_stddev
         self.noise_type = ex.noise_type
+        self.max_sigma, self.theta, self.dt = ex.max_sigma, ex.theta, ex.dt
         n_agents = self.env_config.get('num_agents', 1)
         if n_agents == 1:
             self.sigma = ex.max_sigma / 3.0
@@ -66,9 +67,8 @@ class DDPGAgent(Agent):
             self.noise = NormalActionNoise(np.zeros(self.action_dim),
                                            np.ones(self.action_dim) * self.sigma)
         elif self.noise_type == 'ou_noise':
-            ex = self.learner_config.algo.exploration
             self.noise = OrnsteinUhlenbeckActionNoise(mu=np.zeros(self.action_dim), sigma=self.sigma,
-                                                      theta=ex.theta, dt=ex.dt)
+                                                      theta=self.theta, dt=self.dt)
         else:
             raise ConfigError('Noise type {} undefined.'.format(self.noise_type))
         if self.param_noise_type == 'normal':                # ddpg_agent.py:136-147
@@ -123,6 +123,15 @@ class DDPGAgent(Agent):
             s = self.sigma if sigmas is None else sigmas.view(-1, 1)
             a = a + eps * s
         return a.clamp_(-1.0, 1.0)
+
+    def batch_sigmas(self, n):
+        """fp64 [n] on the device: the exploration scale of actors 0 .. n-1 of a GPU by the rule each agent applies to
+        itself (ddpg_agent.py:78-84): max_sigma * (i / n), max_sigma / 3 for a single actor"""
+        if n == 1:
+            s = [self.max_sigma / 3.0]
+        else:
+            s = [self.max_sigma * (float(i) / n) for i in range(n)]
+        return torch.tensor(s, dtype=torch.float64, device=self.device)
 
     def module_dict(self, model=None):
         return {'ddpg': self.model if model is None else model}

@@ -104,10 +104,14 @@ class SyntheticVecEnv(object):
         self.t = 0
         self.rolls = None
         self.persistent = True        # rollout(): the one-launch kernel where the policy's shapes allow it
+        self._ddpg = {}               # ddpg_rollout_into(): the open n-step transitions and OU states of the actors
 
     def reset(self):
         self.state.copy_(self.init_state)
         self.t = 0
+        for k in ('carry_obs', 'carry_act', 'carry_rew', 'ou'):
+            if self._ddpg.get(k) is not None:
+                self._ddpg[k].zero_()
         return self.state
 
     def start_rollout(self, T, info_width=0):
@@ -254,6 +258,88 @@ class SyntheticVecEnv(object):
                         self.episode_len, T, 0, rolls, agent.model.z_filter if agent.use_z_filter else None)
         for _ in range(T):
             self.t = 0 if self.t + 1 >= self.episode_len else self.t + 1
+
+    def ddpg_rollout_into(self, agent, replay, T, eps=None, sigmas=None, actors_per_workgroup=0, reference=False):
+        """T steps of all actors under DDPGAgent `agent` (act: actor -> clip -> exploration noise -> clip,
+        ddpg_agent.py:155-184), their n-step transitions (ExpSenderWrapperSSARNStepBootstrap, exp_sender_wrapper.py:72-112)
+        written STRAIGHT INTO the uniform replay's device ring (reserve_ring / commit_ring) -> the number of rows written.
+        ONE launch (smx_synth_ddpg_rollout_f32) where the actor's shapes allow it, else one actor forward
+        (DDPGModel.forward_actor) and one step launch (smx_synth_ddpg_step_f32) per step.  Rollouts need not start at an
+        episode boundary: the open transitions and the OU states carry from call to call (reset() clears them).
+        eps [T, n, A] standard normals (default: drawn here in one launch); sigmas [n] fp64 (default
+        agent.batch_sigmas(n)); actors_per_workgroup: 4 | 8 | 16 forces the persistent kernel's block (0: automatic);
+        reference=True: the two-launch reference of the persistent kernel (smx_epoch_forward_f32 for the actor, then the
+        step launch) -- for parity tests, not the product loop."""
+        K, n, A = self.K, self.n, self.A
+        if self.pixel is not None or agent.model.is_pixel_input:
+            raise NotImplementedError('ddpg_rollout_into: low-dimensional observations only (no camera)')
+        if agent.param_noise_type == 'adaptive_normal':
+            raise NotImplementedError("ddpg_rollout_into: 'adaptive_normal' parameter noise measures an action distance "
+                                      "per act() on the host; use 'normal' parameter noise or none")
+        algo = agent.learner_config.algo
+        N, gamma = int(algo.n_step), algo.gamma
+        # the closing steps of this call (the clock is shared by all actors): n of them per closing step
+        m, t = 0, self.t
+        for _ in range(T):
+            m += t >= N - 1
+            t = 0 if t + 1 >= self.episode_len else t + 1
+        rows = n * m
+        if rows > replay.memory_size:
+            raise ValueError('ddpg_rollout_into: %d actors x %d closing steps = %d transitions exceed the replay '
+                             'capacity %d (two of them would share a row)' % (n, m, rows, replay.memory_size))
+        tables, cursor, cap = replay.reserve_ring(rows, {'obs': (self.D,), 'obs_next': (self.D,), 'actions': (A,),
+                                                         'rewards': (), 'dones': ()})
+        d = self._ddpg
+        if d.get('n_step') != N:
+            f = lambda *s: torch.zeros(*s, device=self.device)  # noqa: E731
+            d.update(n_step=N, carry_obs=f(n, N, self.D), carry_act=f(n, N, A), carry_rew=f(n, N),
+                     ou=torch.zeros(n, A, device=self.device, dtype=torch.float64))
+        if d.get('gamma') != gamma:
+            d['gamma'] = gamma
+            d['gpow'] = torch.tensor([pow(gamma, e) for e in range(N)], dtype=torch.float64, device=self.device)
+        deterministic = agent.agent_mode in ('eval_deterministic', 'eval_deterministic_local')
+        noise = L.SMX_DDPG_NOISE_NONE if deterministic else \
+            {'normal': L.SMX_DDPG_NOISE_GAUSSIAN, 'ou_noise': L.SMX_DDPG_NOISE_OU}[agent.noise_type]
+        if not deterministic:
+            if eps is None:
+                eps = torch.randn(T, n, A, device=self.device)
+            if sigmas is None:
+                sigmas = agent.batch_sigmas(n)
+            assert tuple(eps.shape) == (T, n, A) and sigmas.dtype == torch.float64 and sigmas.numel() == n
+            eps, sigmas = eps.contiguous(), sigmas.contiguous()
+        r = dict(state=self.state, init_state=self.init_state, t=self.t, episode_len=self.episode_len, n_step=N,
+                 noise_type=noise, eps=None if deterministic else eps, sigmas=None if deterministic else sigmas,
+                 theta=agent.theta, dt=agent.dt, root_dt=float(np.sqrt(agent.dt)), gpow=d['gpow'], ou=d['ou'],
+                 carry_obs=d['carry_obs'], carry_act=d['carry_act'], carry_rew=d['carry_rew'], tables=tables,
+                 cursor=cursor)
+        actor = agent.model.actor
+        persistent = not agent.model.use_layernorm and K.synth_ddpg_rollout_supported(actor)
+        if persistent or reference:
+            if d.get('pk') is None or d['pk'].numel() != K.epoch_packed_numel(actor):
+                d['pk'] = torch.zeros(K.epoch_packed_numel(actor), device=self.device)
+            K.epoch_pack([(actor, d['pk'])])        # (the agent's parameters only change between rollouts)
+        if persistent and not reference:
+            K.synth_ddpg_rollout(actor, d['pk'], r, T, actors_per_workgroup)
+            self.t = t
+        else:
+            if reference:
+                assert not agent.model.use_layernorm
+                mu = torch.empty(n, A, device=self.device)
+                ctrl = torch.zeros(L.CTRL_WORDS, device=self.device)
+            for s in range(T):
+                if reference:
+                    K.epoch_forward([dict(net=actor, packed=d['pk'], x=self.state, out=mu, act=L.SMX_ACT_TANH)],
+                                    None, ctrl, n)
+                else:
+                    mu = agent.model.forward_actor(self.state)
+                r['t'] = self.t
+                r['eps'] = None if deterministic else eps[s]
+                K.synth_ddpg_step(r, mu)
+                if self.t >= N - 1:
+                    r['cursor'] = (r['cursor'] + n) % cap
+                self.t = 0 if self.t + 1 >= self.episode_len else self.t + 1
+        replay.commit_ring(rows)
+        return rows
 
     def _rollout_stem(self, agent, eps):
         """policies with an LSTM and / or CNN stem: one batched act per step (PPOAgent.act_batch: the stem and the

@@ -643,6 +643,49 @@ class HipKernels(object):
         p.obs_last = L.ptr(r.get('obs_last'))          # rows_per_actor == steps: the replay's layout (obs_next apart)
         L.call('smx_synth_rollout_f32', ctypes.byref(p), self._st())
 
+    def synth_ddpg_rollout_supported(self, net):
+        return bool(self.lib.smx_synth_ddpg_rollout_supported(net.D, net.H1, net.H2, net.OUT))
+
+    @staticmethod
+    def _ddpg_args(r, steps, net=None, packed=None, actors_per_workgroup=0):
+        """struct smx_ddpg_rollout from the dict SyntheticVecEnv.ddpg_rollout_into builds: state / init_state [n, D],
+        t, episode_len, n_step, noise_type, eps, sigmas (fp64), theta / dt / root_dt, gpow (fp64 [n_step]), ou (fp64
+        [n, A]), carry_obs / carry_act / carry_rew, the ring tables by replay field name, cursor, capacity"""
+        n, D = r['state'].shape
+        tabs = r['tables']
+        p = L.DdpgRollout()
+        p.net = ctypes.pointer(net.desc) if net is not None else None
+        p.packed = L.ptr(packed)
+        p.n, p.D, p.A, p.steps = n, D, tabs['actions'].shape[1], int(steps)
+        p.t, p.episode_len, p.n_step, p.noise_type = int(r['t']), int(r['episode_len']), int(r['n_step']), \
+            int(r['noise_type'])
+        p.actors_per_workgroup = int(actors_per_workgroup)
+        p.eps, p.sigmas = L.ptr(r['eps']), L.ptr(r['sigmas'])
+        p.theta, p.dt, p.root_dt = float(r['theta']), float(r['dt']), float(r['root_dt'])
+        p.gpow, p.ou = L.ptr(r['gpow']), L.ptr(r['ou'])
+        p.state, p.init_state = L.ptr(r['state']), L.ptr(r['init_state'])
+        p.carry_obs, p.carry_act, p.carry_rew = L.ptr(r['carry_obs']), L.ptr(r['carry_act']), L.ptr(r['carry_rew'])
+        p.obs, p.obs_next, p.actions = L.ptr(tabs['obs']), L.ptr(tabs['obs_next']), L.ptr(tabs['actions'])
+        p.rewards, p.dones = L.ptr(tabs['rewards']), L.ptr(tabs['dones'])
+        p.cursor, p.capacity = int(r['cursor']), int(tabs['obs'].shape[0])
+        return p
+
+    def synth_ddpg_rollout(self, net, packed, r, steps, actors_per_workgroup=0):
+        """`steps` DDPG acting + environment steps of all actors with their n-step transitions written into the ring
+        tables, ONE launch (csrc/smx_ddpg_rollout.hip).  packed: epoch_pack of the actor `net`; r: see _ddpg_args
+        (eps [steps, n, A])"""
+        if r['eps'] is not None:
+            assert r['eps'].is_contiguous() and tuple(r['eps'].shape) == (steps, r['state'].shape[0], net.OUT)
+        p = self._ddpg_args(r, steps, net, packed, actors_per_workgroup)
+        L.call('smx_synth_ddpg_rollout_f32', ctypes.byref(p), self._st())
+
+    def synth_ddpg_step(self, r, mu):
+        """one step of synth_ddpg_rollout given the actor's output mu [n, A] (r['eps']: this step's [n, A] draws;
+        r['cursor']: where this step's closing transitions go)"""
+        A = mu.shape[1]
+        p = self._ddpg_args(r, 1)
+        L.call('smx_synth_ddpg_step_f32', ctypes.byref(p), L.ptr(mu), _row_stride(mu, A), self._st())
+
     def synth_env_step(self, state, init_state, actions, t, episode_len, slot, obs_roll, act_roll,
                        rew_roll, done_roll):
         n, D = state.shape

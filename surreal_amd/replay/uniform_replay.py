@@ -57,6 +57,24 @@ class UniformReplay(Replay):
         self._dev_len = min(self.memory_size, self._dev_len + n)
         self.cumulative_collected_count += n
 
+    def reserve_ring(self, rows, shapes):
+        """zero-copy insertion: -> (tables, cursor, capacity), tables = {field: [capacity, width] fp32 device table}
+        (created here on first use, like insert_batch) for a producer that writes `rows` rows itself at
+        (cursor + i) % capacity, i < rows; commit_ring(rows) then makes them part of the replay"""
+        if rows > self.memory_size:
+            raise ValueError('reserve_ring: %d rows do not fit a ring of %d' % (rows, self.memory_size))
+        tables = self._ensure_tables(self.memory_size, {k: torch.empty((0,) + tuple(s)) for k, s in shapes.items()})
+        for k, s in shapes.items():
+            if k not in tables or tables[k].shape != tuple(s) or tables[k].dtype != torch.float32:
+                raise ValueError('reserve_ring: field %r %s does not match the replay table' % (k, tuple(s)))
+        return {k: tables[k].data for k in shapes}, self._dev_next, self.memory_size
+
+    def commit_ring(self, rows):
+        """the `rows` rows written after reserve_ring: advance the cursor and the counters as insert_batch does"""
+        self._dev_next = (self._dev_next + rows) % self.memory_size
+        self._dev_len = min(self.memory_size, self._dev_len + rows)
+        self.cumulative_collected_count += rows
+
     def sample_indices(self, batch_size):
         """with-replacement uniform indices on the device (Philox4x32-10; the reference's
         Python Mersenne stream cannot be reproduced on a GPU -- distributional parity, and
