@@ -1005,8 +1005,9 @@ int smx_flatten_order_f32(const float* in, int32_t O, int32_t C, int32_t P,
 /* A whole device-resident rollout in ONE launch: `steps` iterations of [z-filter -> policy MLP -> DiagGauss sample ->
  * clip -> synthetic env step -> record] for all n actors (the per-step loop of surreal/agent/base.py:244-271 with
  * PPOAgent.act, surreal/agent/ppo_agent.py:106-154, and the recording of env/exp_sender_wrapper.py:153-264).  A
- * workgroup owns 4 actors for the whole rollout (8 from 1025 actors on, 16 beyond 2048: the smallest block whose grid fits
- * the CUs once); the policy layers run on FP32 MFMA (v_mfma_f32_4x4x1; 16x16x4 for 16-actor blocks) from `packed`
+ * workgroup owns actors_per_workgroup = 4, 8 or 16 actors for the whole rollout (0: 4, 8 from 1025 actors on, 16 beyond
+ * 2048 on 256 CUs -- the smallest block whose grid fits the CUs once; anything else: SMX_E_SHAPE); the policy layers
+ * run on FP32 MFMA (v_mfma_f32_4x4x1; 16x16x4 for 16-actor blocks) from `packed`
  * (smx_epoch_pack_f32 of `net`): the means equal smx_epoch_forward_f32's to fp32 rounding of the layer sums (another
  * summation order), 4- and 8-actor blocks bit for bit each other's; sampling, dynamics, recording and the z-filter use the
  * expressions of smx_synth_act_env_step_f32.
@@ -1038,6 +1039,7 @@ typedef struct smx_synth_rollout {
     float* done_roll;
     float* pd_roll;
     float* obs_last;
+    int32_t actors_per_workgroup;          /* 4 | 8 | 16, 0: the smallest whose grid fits the CUs once */
 } smx_synth_rollout_t;
 int32_t smx_synth_rollout_supported(int32_t D, int32_t H1, int32_t H2, int32_t A);
 int smx_synth_rollout_f32(const smx_synth_rollout_t* args, smx_stream_t stream);
@@ -1086,15 +1088,17 @@ struct smx_ddpg_rollout {
     float* dones;
     int64_t cursor, capacity;
 };
+typedef struct smx_ddpg_rollout smx_ddpg_rollout_t;
 /* shapes smx_synth_ddpg_rollout_f32 takes: A <= 32, H1 and H2 multiples of 4 up to 640, D <= 512 */
 int32_t smx_synth_ddpg_rollout_supported(int32_t D, int32_t H1, int32_t H2, int32_t A);
-/* all `steps` steps in ONE launch: a workgroup owns 4, 8 or 16 actors for the whole rollout, the actor's layers run on
- * v_mfma_f32_4x4x1 from `packed` (smx_rows4_mma.inc.h: mu equals smx_epoch_forward_f32's to fp32 rounding of the layer
- * sums; every block size gives the same bits) */
-int smx_synth_ddpg_rollout_f32(const struct smx_ddpg_rollout* args, smx_stream_t stream);
+/* all `steps` steps in ONE launch, in the persistent kernel shape of smx_synth_rollout_f32: a workgroup owns
+ * actors_per_workgroup = 4, 8 or 16 actors for the whole rollout (0: chosen as there; anything else: SMX_E_SHAPE), the
+ * actor's layers run on v_mfma_f32_4x4x1 from `packed` at every block size (smx_rows4_mma.inc.h: mu equals
+ * smx_epoch_forward_f32's to fp32 rounding of the layer sums; every block size gives the same bits) */
+int smx_synth_ddpg_rollout_f32(const smx_ddpg_rollout_t* args, smx_stream_t stream);
 /* ONE step (args->steps is ignored; eps [n, A]; the step's closing transitions go to the rows from args->cursor) given
  * the actor's output mu [n, A] (row stride ld_mu) from any forward pass */
-int smx_synth_ddpg_step_f32(const struct smx_ddpg_rollout* args, const float* mu, int64_t ld_mu, smx_stream_t stream);
+int smx_synth_ddpg_step_f32(const smx_ddpg_rollout_t* args, const float* mu, int64_t ld_mu, smx_stream_t stream);
 
 /* ---------------------------------------------------------------------------
  * Data-parallel exchange between the learner ranks of one node over IPC-mapped peer buffers (xGMI loads): the

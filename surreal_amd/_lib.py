@@ -152,11 +152,12 @@ class SynthRollout(Structure):
                 ('zsumsq', c_void_p), ('zcount', c_void_p), ('zeps', c_float), ('t', c_int32),
                 ('episode_len', c_int32), ('steps', c_int32), ('rows_per_actor', c_int32), ('slot', c_int32),
                 ('state', c_void_p), ('init_state', c_void_p), ('obs_roll', c_void_p), ('act_roll', c_void_p),
-                ('rew_roll', c_void_p), ('done_roll', c_void_p), ('pd_roll', c_void_p), ('obs_last', c_void_p)]
+                ('rew_roll', c_void_p), ('done_roll', c_void_p), ('pd_roll', c_void_p), ('obs_last', c_void_p),
+                ('actors_per_workgroup', c_int32)]
 
 
 class DdpgRollout(Structure):
-    """struct smx_ddpg_rollout (no typedef)"""
+    """smx_ddpg_rollout_t"""
     _fields_ = [('net', POINTER(Mlp3)), ('packed', c_void_p), ('n', c_int32), ('D', c_int32), ('A', c_int32),
                 ('steps', c_int32), ('t', c_int32), ('episode_len', c_int32), ('n_step', c_int32),
                 ('noise_type', c_int32), ('actors_per_workgroup', c_int32), ('reserved', c_int32),

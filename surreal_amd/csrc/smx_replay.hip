@@ -8,11 +8,7 @@
 
 namespace {
 
-__device__ __forceinline__ float zclamp(float x, float m, float s) {
-    float v = (x - m) / s;   // z_filter.py:77
-    if (v == v) v = fminf(fmaxf(v, -5.0f), 5.0f);
-    return v;
-}
+#include "smx_synth_env.inc.h"
 
 // copy `n` rows of `width` floats: dst row i <- src row map(i).  A wavefront moves one SEGMENT of
 // one row (ROW_SEG floats): a learner batch has few, very wide rows (1024 sub-trajectories of
@@ -296,9 +292,7 @@ __global__ __launch_bounds__(256) void synth_env_step_kernel(
     const float s = state[i];
     float ac = actions[a * A + (k % A)];
     ac = fminf(fmaxf(ac, -1.0f), 1.0f);
-    const float drift = 0.01f * (float)(((37 * k) % 17) - 8);
-    float sn = (0.9f * s + 0.5f * ac) + drift;
-    sn = fminf(fmaxf(sn, -10.0f), 10.0f);
+    const float sn = synth_next(s, ac, synth_drift(k));
     const bool done = (t + 1 >= episode_len);
     if (obs_roll) {
         obs_roll[(a * T + slot) * D + k] = s;
@@ -316,7 +310,7 @@ __global__ __launch_bounds__(256) void synth_env_step_kernel(
             float av = fminf(fmaxf(actions[a * A + j], -1.0f), 1.0f);
             q += (double)av * (double)av;
         }
-        if (rew_roll) rew_roll[a * T + slot] = (float)(-0.1 * q + 0.05 * (double)sn);
+        if (rew_roll) rew_roll[a * T + slot] = synth_reward(q, sn);
         if (done_roll) done_roll[a * T + slot] = done ? 1.0f : 0.0f;
     }
     state[i] = done ? init_state[i] : sn;
@@ -344,9 +338,7 @@ __global__ __launch_bounds__(256) void synth_act_env_step_kernel(smx_synth_act_s
     float mu, sd;
     const float ac = action(k % A, mu, sd);
     const float s = p.state[i];
-    const float drift = 0.01f * (float)(((37 * k) % 17) - 8);
-    float sn = (0.9f * s + 0.5f * ac) + drift;
-    sn = fminf(fmaxf(sn, -10.0f), 10.0f);
+    const float sn = synth_next(s, ac, synth_drift(k));
     const bool done = (p.t + 1 >= p.episode_len);
     if (p.obs_roll) {
         p.obs_roll[(a * T + slot) * D + k] = s;
@@ -366,7 +358,7 @@ __global__ __launch_bounds__(256) void synth_act_env_step_kernel(smx_synth_act_s
             const float av = action(j, m2, s2);
             q += (double)av * (double)av;
         }
-        if (p.rew_roll) p.rew_roll[a * T + slot] = (float)(-0.1 * q + 0.05 * (double)sn);
+        if (p.rew_roll) p.rew_roll[a * T + slot] = synth_reward(q, sn);
         if (p.done_roll) p.done_roll[a * T + slot] = done ? 1.0f : 0.0f;
     }
     const float next = done ? p.init_state[i] : sn;
@@ -374,11 +366,8 @@ __global__ __launch_bounds__(256) void synth_act_env_step_kernel(smx_synth_act_s
     if (p.xn_out) {
         float z = next;
         if (p.zsum) {
-            const float c = p.zcount[0];
-            const float m = p.zsum[k] / c;
-            const float var = p.zsumsq[k] / c - m * m;
-            float sz = sqrtf(var);
-            if (sz == sz) sz = fmaxf(sz, p.zeps);
+            float m, sz;
+            zfilter_stats(p.zsum, p.zsumsq, p.zcount, p.zeps, k, m, sz);
             z = zclamp(next, m, sz);
         }
         p.xn_out[i] = z;
@@ -430,9 +419,7 @@ __global__ __launch_bounds__(256) void synth_act_head_step_kernel(smx_synth_act_
         const long i = a * D + k;
         const float ac = s_act[k % A];
         const float s = p.state[i];
-        const float drift = 0.01f * (float)(((37 * k) % 17) - 8);
-        float sn = (0.9f * s + 0.5f * ac) + drift;
-        sn = fminf(fmaxf(sn, -10.0f), 10.0f);
+        const float sn = synth_next(s, ac, synth_drift(k));
         if (p.obs_roll) {
             p.obs_roll[(a * T + slot) * D + k] = s;
             if (slot + 1 < T) p.obs_roll[(a * T + slot + 1) * D + k] = sn;
@@ -440,7 +427,7 @@ __global__ __launch_bounds__(256) void synth_act_head_step_kernel(smx_synth_act_
         if (k == 0) {
             double q = 0.0;
             for (int j = 0; j < A; ++j) q += (double)s_act[j] * (double)s_act[j];
-            if (p.rew_roll) p.rew_roll[a * T + slot] = (float)(-0.1 * q + 0.05 * (double)sn);
+            if (p.rew_roll) p.rew_roll[a * T + slot] = synth_reward(q, sn);
             if (p.done_roll) p.done_roll[a * T + slot] = done ? 1.0f : 0.0f;
         }
         const float next = done ? p.init_state[i] : sn;
@@ -448,11 +435,8 @@ __global__ __launch_bounds__(256) void synth_act_head_step_kernel(smx_synth_act_
         if (p.xn_out) {
             float z = next;
             if (p.zsum) {
-                const float c = p.zcount[0];
-                const float m = p.zsum[k] / c;
-                const float var = p.zsumsq[k] / c - m * m;
-                float sz = sqrtf(var);
-                if (sz == sz) sz = fmaxf(sz, p.zeps);
+                float m, sz;
+                zfilter_stats(p.zsum, p.zsumsq, p.zcount, p.zeps, k, m, sz);
                 z = zclamp(next, m, sz);
             }
             p.xn_out[i] = z;

@@ -1,26 +1,40 @@
-// A whole device-resident rollout in ONE launch (surreal/agent/base.py:244-271 the per-step loop of a rollout
-// worker, surreal/agent/ppo_agent.py:106-154 act: z-filter -> policy MLP -> DiagGauss sample -> clip; the environment
-// step and the recording that surreal/env/exp_sender_wrapper.py:153-264 does on the host).
+// Device-resident rollouts in ONE launch, for PPO and for DDPG.  Actors are independent of each other, time steps are
+// not: so a workgroup OWNS 4, 8 or 16 actors and walks them through all steps by itself -- no per-step launch, no
+// grid-wide synchronisation.  The environment's state of its actors stays in registers for the whole rollout.  Per step:
+//   x tile (the observations of its actors, LDS)  ->  the three actor layers on FP32 MFMA with the fragment-order packed
+//   weights streamed from L2  ->  the head (per kernel)  ->  the synthetic environment's step for the block's actors  ->
+//   the recording (per kernel)  ->  the next observation straight into the x tile.
 //
-// Actors are independent of each other, time steps are not: so a workgroup OWNS 16 actors and walks them through all
-// T steps by itself -- no per-step launch, no grid-wide synchronisation.  Per step:
-//   x tile (z-filtered observations of its 16 actors, LDS)  ->  the three policy layers on v_mfma_f32_16x16x4_f32 with
-//   the fragment-order packed weights streamed from L2 (the row-block loop of smx_epoch_mma.inc.h, the same operations
-//   in the same order as smx_epoch_forward_f32: bit-identical means)  ->  the sampling head (mean, std * exp(noise),
-//   a = clip(mean + std * eps))  ->  the synthetic environment's step for the 16 actors (state kept in registers for
-//   the whole rollout)  ->  the transition recorded into the rollout tables [actors, T + 1, .]  ->  the next observation
-//   z-filtered straight into the x tile.
-// The per-step launches it replaces were 3 dependent launches of ~9.5 us each (two hidden layers as GEMM launches, then
-// head + step), 384 launches for T = 128; here a step is the MFMA issue time of one CU for 16 rows (~12 us at
-// D = 376, [300, 200]) and the chip runs 256 such workgroups side by side (4096 actors cost what 1024 do).
+//   smx_synth_rollout_f32       PPO (surreal/agent/base.py:244-271 the per-step loop of a rollout worker,
+//                               surreal/agent/ppo_agent.py:106-154 act: z-filter -> policy MLP -> DiagGauss sample ->
+//                               clip; the recording of surreal/env/exp_sender_wrapper.py:153-264 into rollout tables
+//                               [actors, T + 1, .]).  4 and 8 actors per workgroup run rollout_kernel<RG> on the 4-row
+//                               v_mfma_f32_4x4x1 loop of smx_rows4_mma.inc.h, 16 run rollout16_kernel on the 16x16x4 loop
+//                               of smx_epoch_mma.inc.h.
+//   smx_synth_ddpg_rollout_f32  DDPG (surreal/agent/ddpg_agent.py:155-184 act: actor -> clip -> + exploration noise ->
+//                               clip; surreal/agent/action_noise.py; the n-step transitions of
+//                               surreal/env/exp_sender_wrapper.py:72-112 ExpSenderWrapperSSARNStepBootstrap, which run on
+//                               the host there) recorded straight into the uniform replay's ring: ddpg_rollout_kernel on
+//                               the 4-row loop at every block size.
+//   smx_synth_ddpg_step_f32     one DDPG step for all actors given the actor's output mu [n, A] from any forward
+//                               (LayerNorm actors, unsupported shapes; with smx_epoch_forward_f32 the persistent kernel's
+//                               two-launch reference).
+//
+// The per-step launches the PPO rollout replaces were 3 dependent launches of ~9.5 us each (two hidden layers as GEMM
+// launches, then head + step), 384 launches for T = 128.
+//
+// DDPG's open transitions of an actor (observation, action, reward of its last n_step steps) live in a ring of n_step
+// slots in HBM, slot tau % n_step for episode step tau: every value is written and later read by the SAME lane, so no
+// barrier orders them, and they carry from one call to the next.  Transition j = tau - n_step + 1 closes at step tau;
+// the k-th closing step of a call writes actor a to ring row (cursor + k n + a) mod capacity.
 #include "smx_common.h"
-#include <stdlib.h>
 #include <string.h>
 
 namespace {
 #include "smx_epoch_pack.inc.h"
 #include "smx_epoch_mma.inc.h"
 #include "smx_rows4_mma.inc.h"
+#include "smx_synth_env.inc.h"
 
 // Phase timestamps exist only in a build with -DSMX_ROLLOUT_TIMING (scripts/bench_rollout.py); the product build has none.
 #ifdef SMX_ROLLOUT_TIMING
@@ -34,32 +48,233 @@ __device__ long long* g_rtbuf_dev = nullptr;
 #define RCYC(i) do { } while (0)
 #endif
 
-constexpr int RLDO = 36;          // row stride of the mean tile in LDS (<= 32 actions)
+constexpr int RLDO = 36;          // row stride of the output tile in LDS (<= 32 actions)
 constexpr int RMAX_A = 32;
-
-struct RollArgs {
-    const float *P1, *P2, *P3;                  // packed weights (smx_epoch_pack_f32)
-    const float *b1, *b2, *b3;
-    int D, H1, H2, A, out_act;
-    const float *log_var, *noise_scale, *eps;   // eps [T, n, A] or null (deterministic)
-    const float *zsum, *zsumsq, *zcount;        // z-filter running sums or null
-    float zeps;
-    float* state;                               // [n, D] in / out
-    const float* init_state;
-    int n, t0, episode_len, steps, R, slot0;    // R = rows per actor in the rollout tables
-    float *obs_roll, *act_roll, *rew_roll, *done_roll, *pd_roll, *obs_last;
-    int ldx, ldh1, ldh2, off_h1, off_h2, off_out, off_act, off_red3, off_z, lds_floats;
-};
-
-__device__ __forceinline__ float zclamp_r(float x, float m, float sd) {
-    float v = (x - m) / sd;                     // z_filter.py:77
-    if (v == v) v = fminf(fmaxf(v, -5.0f), 5.0f);
-    return v;
-}
-
 constexpr int RNWV = 8;           // two wavefronts per SIMD: the K loops have no barrier inside, so one wave's loads
 constexpr int RNTH = 64 * RNWV;   // and epilogue hide under the other's MFMAs
 constexpr int RKV = 8;            // observation elements a lane owns per row (D <= 64 RKV)
+constexpr int ROLL_MAX_LDS = 150 * 1024;
+constexpr int ROLL_EXCLUSIVE_LDS = 84 * 1024;   // one workgroup per CU: each streams the packed weights by itself
+
+// What every persistent kernel takes: the actor, the actors' states and the LDS layout (carve()).
+struct RollBase {
+    const float *P1, *P2, *P3;                  // packed weights (smx_epoch_pack_f32)
+    const float *b1, *b2, *b3;
+    int D, H1, H2, A, n, steps, t0, episode_len;
+    const float* eps;                           // this step's normal draws [steps, n, A] or null
+    float* state;                               // [n, D] in / out
+    const float* init_state;
+    int ldx, ldh1, ldh2, off_h1, off_h2, off_out, off_act, off_red3, off_z, off_kmod;
+};
+
+struct RollArgs : RollBase {
+    int out_act;
+    const float *log_var, *noise_scale;
+    const float *zsum, *zsumsq, *zcount;        // z-filter running sums or null
+    float zeps;
+    int R, slot0;                               // R = rows per actor in the rollout tables
+    float *obs_roll, *act_roll, *rew_roll, *done_roll, *pd_roll, *obs_last;
+};
+
+struct DArgs : RollBase {
+    int N, noise;
+    const double* sigmas;
+    double theta, dt, root_dt;
+    const double* gpow;
+    double* ou;
+    float *cobs, *cact, *crew;
+    float *obs, *obs_next, *act, *rew, *done;
+    long long cursor, capacity;
+};
+
+// ---- once per launch: clear the tiles (their padding columns and rows must read as zeros, the action tile's unused
+// columns too); k % A (an integer division per element and step otherwise) and, with the z-filter's running sums, its
+// mean | std go to the LDS tables at off_kmod and off_z
+__device__ __forceinline__ void clear_tiles(const RollBase& G, float* sm, int tid, const float* zsum, const float* zsumsq,
+                                            const float* zcount, float zeps) {
+    for (int i = tid; i < G.off_z; i += RNTH) sm[i] = 0.f;
+    float* zm = sm + G.off_z;
+    int* kmod = (int*)(sm + G.off_kmod);
+    for (int k = tid; k < G.D; k += RNTH) {
+        kmod[k] = k % G.A;
+        if (zsum) zfilter_stats(zsum, zsumsq, zcount, zeps, k, zm[k], zm[G.D + k]);
+    }
+}
+
+// The environment phase of an RB-actor block.  Wave wv steps the actor rows erow0 .. erow0 + RPW - 1 (RB >= 8) or the
+// part `part` of row erow0 (RB = 4: WPR waves share a row); a lane owns the elements k = lane + 64 (part + WPR i) of
+// them and keeps their raw state in registers for the whole rollout (RB = 16: two rows a wave, k = lane + 64 i).
+// COLS: the elements' action column and drift in registers too (else read from kmod and formed every step, where the
+// registers are short).
+template <int RB, bool COLS = true>
+struct EnvLanes {
+    static constexpr int WPR = RB < RNWV ? RNWV / RB : 1;   // wavefronts per actor row
+    static constexpr int RPW = RB > RNWV ? RB / RNWV : 1;   // actor rows per wavefront
+    static constexpr int KPL = RKV / WPR;                   // observation elements a lane owns per row
+    const int D, ldx;                           // (copies, not a reference to the kernel's arguments: fewer registers)
+    float* const state;
+    const float* const init_state;
+    float* xs;                                  // the x tile
+    const float* zm;                            // the z-filter's [D] mean | [D] std in LDS, or null: raw observations
+    const int* kmod;
+    long row0;
+    int nrows, lane, erow0, part;
+    float st[RPW][KPL];
+    int am[KPL];                                // the elements' action column k % A (COLS)
+    float dr[KPL];                              // their drift (COLS)
+
+    // the states of the block's actors to registers
+    __device__ __forceinline__ EnvLanes(const RollBase& G, float* sm, const float* zm_, int wv, int lane_)
+        : D(G.D), ldx(G.ldx), state(G.state), init_state(G.init_state), xs(sm), zm(zm_), kmod((const int*)(sm + G.off_kmod)),
+          row0((long)blockIdx.x * RB), lane(lane_), erow0(RPW * (wv / WPR)), part(wv % WPR) {
+        nrows = G.n - (int)row0;
+        if (nrows > RB) nrows = RB;
+#pragma unroll
+        for (int i = 0; i < KPL; ++i) {
+            const int k = kel(i);
+#pragma unroll
+            for (int rr = 0; rr < RPW; ++rr) {
+                const int r = erow0 + rr;
+                st[rr][i] = (k < D && r < nrows) ? state[(row0 + r) * D + k] : 0.f;
+            }
+        }
+    }
+    __device__ __forceinline__ int kel(int i) const { return lane + 64 * (part + WPR * i); }
+    __device__ __forceinline__ void put_x(int r, int k, float v) {
+        xs[r * ldx + k] = zm ? zclamp(v, zm[k], zm[D + k]) : v;
+    }
+    // behind the barrier that ends clear_tiles: the first x tile and the per-element constants
+    __device__ __forceinline__ void start() {
+#pragma unroll
+        for (int rr = 0; rr < RPW; ++rr) {
+            const int r = erow0 + rr;
+#pragma unroll
+            for (int i = 0; i < KPL; ++i) {
+                const int k = kel(i);
+                if (k < D && r < nrows) put_x(r, k, st[rr][i]);
+            }
+        }
+        if (COLS) {
+#pragma unroll
+            for (int i = 0; i < KPL; ++i) {
+                const int k = kel(i);
+                am[i] = k < D ? kmod[k] : 0;
+                dr[i] = synth_drift(k);
+            }
+        }
+    }
+    // One environment step of the block's actors from the clipped actions in s_act [RB][RMAX_A] (unused columns 0),
+    // the next state (the reset state when `done`) into the registers and the x tile.  The recording is the caller's:
+    // p = open(a) once per actor row, rec(a, p, k, s, sn) per element (state s, next state sn), close(a, p, reward).
+    template <typename Open, typename Rec, typename Close>
+    __device__ __forceinline__ void step(const float* s_act, bool done, Open open, Rec rec, Close close) {
+#pragma unroll
+        for (int rr = 0; rr < RPW; ++rr) {
+            const int r = erow0 + rr;                   // wave-uniform
+            if (r < nrows) {
+                const long a = row0 + r;
+                const auto p = open(a);
+                float sn0 = 0.f;
+#pragma unroll
+                for (int i = 0; i < KPL; ++i) {
+                    const int k = kel(i);
+                    if (k < D) {
+                        const float s = st[rr][i];
+                        const float sn = COLS ? synth_next(s, s_act[r * RMAX_A + am[i]], dr[i])
+                                              : synth_next(s, s_act[r * RMAX_A + kmod[k]], synth_drift(k));
+                        rec(a, p, k, s, sn);
+                        if (i == 0) sn0 = sn;
+                        const float next = done ? init_state[a * D + k] : sn;
+                        st[rr][i] = next;
+                        put_x(r, k, next);
+                    }
+                }
+                if (lane == 0 && part == 0) {           // (k == 0 lives in lane 0, i == 0 of the row's first wave)
+                    // sum_j a_j^2 in fp64, j ascending (the order of smx_synth_env_step_f32).  All RMAX_A reads are
+                    // issued up front (unused columns of the tile are zero and add +0.0): one LDS round trip, not A
+                    float av[RMAX_A];
+#pragma unroll
+                    for (int j = 0; j < RMAX_A; ++j) av[j] = s_act[r * RMAX_A + j];
+                    double q = 0.0;
+#pragma unroll
+                    for (int j = 0; j < RMAX_A; ++j) q += (double)av[j] * (double)av[j];
+                    close(a, p, synth_reward(q, sn0));
+                }
+            }
+        }
+    }
+    // the states the actors are left in
+    __device__ __forceinline__ void store() const {
+#pragma unroll
+        for (int rr = 0; rr < RPW; ++rr) {
+            const int r = erow0 + rr;
+#pragma unroll
+            for (int i = 0; i < KPL; ++i) {
+                const int k = kel(i);
+                if (k < D && r < nrows) state[(row0 + r) * D + k] = st[rr][i];
+            }
+        }
+    }
+};
+
+// The first nl actor layers of the block's 4 RG rows on the 4-row loop (smx_rows4_mma.inc.h), NT feature tiles a wave
+// per pass: bias, then ReLU on the hidden layers and act_f(., out_act) on the output layer.  The layer sums of a row do
+// not depend on RG or NT (k ascending within each kq class, then the classes meet).  after(l) follows layer l's barrier.
+template <int RG, int NT, typename After>
+__device__ __forceinline__ void layers4(const RollBase& G, float* sm, int nl, int out_act, int wv, int lane, After after) {
+    const int fm = lane & 15, kq = lane >> 4;
+#pragma unroll 1
+    for (int l = 0; l < nl; ++l) {
+        const float* Wp = l == 0 ? G.P1 : (l == 1 ? G.P2 : G.P3);
+        const float* bias = l == 0 ? G.b1 : (l == 1 ? G.b2 : G.b3);
+        const int H = l == 0 ? G.H1 : (l == 1 ? G.H2 : G.A);
+        const int K = l == 0 ? G.D : (l == 1 ? G.H1 : G.H2);
+        const float* in_lds = sm + (l == 0 ? 0 : (l == 1 ? G.off_h1 : G.off_h2));
+        const int ldi = l == 0 ? G.ldx : (l == 1 ? G.ldh1 : G.ldh2);
+        float* out_lds = sm + (l == 0 ? G.off_h1 : (l == 1 ? G.off_h2 : G.off_out));
+        const int ldo = l == 0 ? G.ldh1 : (l == 1 ? G.ldh2 : RLDO);
+        const int tiles = (H + 15) >> 4;
+        const int C2 = pack_chunks(K);
+        const rsrc_t rw = make_rsrc(Wp, (unsigned)tiles * (unsigned)C2 * 2048u);
+        const rsrc_t rbias = make_rsrc(bias, (unsigned)H * 4u);
+#pragma unroll 1
+        for (int tb = 0; tb < tiles; tb += RNWV * NT) {
+            const int t0 = tb + wv;
+            if (t0 >= tiles) continue;                            // (wave-uniform)
+            float bs[NT];
+#pragma unroll
+            for (int g = 0; g < NT; ++g) {
+                const int f = 16 * (t0 + RNWV * g) + fm;
+                bs[g] = ld4(rbias, (f < H) ? (unsigned)f * 4u : OOB);
+            }
+            f32x4 acc[NT][RG];
+#pragma unroll
+            for (int g = 0; g < NT; ++g)
+#pragma unroll
+                for (int r = 0; r < RG; ++r) acc[g][r] = (f32x4){0.f, 0.f, 0.f, 0.f};
+            fwd_tiles4<NT, RG, true>(acc, rw, tiles, C2, in_lds, ldi, t0, RNWV, lane);
+            // the kq groups meet; lane (fm, kq) then keeps row kq of every group: bias, activation, one word to LDS
+#pragma unroll
+            for (int g = 0; g < NT; ++g) {
+                const int f = 16 * (t0 + RNWV * g) + fm;
+                if (t0 + RNWV * g < tiles) {                      // (wave-uniform)
+#pragma unroll
+                    for (int r = 0; r < RG; ++r) {
+                        float z = meet_rows(acc[g][r]);
+                        z += bs[g];
+                        if (l == 2) z = act_f(z, out_act);
+                        else z = (z < 0.f) ? 0.f : z;
+                        out_lds[(4 * r + kq) * ldo + f] = (f < H) ? z : 0.f;
+                    }
+                }
+            }
+        }
+        SMX_LDS_BARRIER();
+        after(l);
+    }
+}
+
+// ---- PPO -------------------------------------------------------------------------------------------------------------
 
 // RG row groups of four actors per workgroup (round 6; smx_rows4_mma.inc.h).  1024 actors: RG = 1 -> 256 workgroups, one per
 // CU.  The host picks the smallest RG whose grid fits the chip once (more actors per workgroup = fewer passes over the
@@ -67,67 +282,23 @@ constexpr int RKV = 8;            // observation elements a lane owns per row (D
 template <int RG>
 __global__ __launch_bounds__(RNTH) void rollout_kernel(RollArgs G) {
     constexpr int RB = 4 * RG;                       // actors per workgroup
-    constexpr int WPR = RB < RNWV ? RNWV / RB : 1;   // wavefronts per actor row in the environment phase
-    constexpr int RPW = RB > RNWV ? RB / RNWV : 1;   // actor rows per wavefront
-    constexpr int KPL = RKV / WPR;                   // observation elements a lane owns per row
-    constexpr int NT = 3;                            // feature tiles a wave carries per pass
     extern __shared__ float sm[];
     const int tid = threadIdx.x, lane = tid & 63;
     const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int fm = lane & 15, kq = lane >> 4;
-    const long row0 = (long)blockIdx.x * RB;
-    int nrows = G.n - (int)row0;
-    if (nrows > RB) nrows = RB;
-    const int D = G.D, A = G.A, R = G.R;
-    float* xs = sm;
-    float* h1s = sm + G.off_h1;
-    float* h2s = sm + G.off_h2;
-    float* outs = sm + G.off_out;
+    const int A = G.A, R = G.R, D = G.D;
+    const float* h2s = sm + G.off_h2;
+    const float* outs = sm + G.off_out;
     float* s_act = sm + G.off_act;              // [RB][RMAX_A] clipped actions
-    const int ldx = G.ldx, ldh1 = G.ldh1, ldh2 = G.ldh2;
+    const int ldh2 = G.ldh2;
 
-    // ---- once: clear the tiles; the z-filter's mean / std and k % A (an integer division per element and step
-    // otherwise) go to LDS tables; the environment phase's lanes keep the raw state of their elements in registers for
-    // the whole rollout: wave wv owns rows RPW wv .. (RB >= 8) or the part `part` of row wv / WPR (RB = 4), a lane the
-    // elements k = lane + 64 (part + WPR i)
-    for (int i = tid; i < G.off_z; i += RNTH) sm[i] = 0.f;          // (incl. the action tile: its unused columns stay 0)
-    float* zm = sm + G.off_z;                   // [D] z-filter mean | [D] std | [D] k % A (as int)
-    float* zs = zm + D;
-    int* kmod = (int*)(zs + D);
-    for (int k = tid; k < D; k += RNTH) {
-        kmod[k] = k % A;
-        float m = 0.f, sz = 1.f;
-        if (G.zsum) {
-            const float c = G.zcount[0];
-            m = G.zsum[k] / c;
-            const float var = G.zsumsq[k] / c - m * m;
-            sz = sqrtf(var);
-            if (sz == sz) sz = fmaxf(sz, G.zeps);
-        }
-        zm[k] = m; zs[k] = sz;
-    }
-    const int erow0 = RPW * (wv / WPR), part = wv % WPR;
-    float st[RPW][KPL];
-#pragma unroll
-    for (int i = 0; i < KPL; ++i) {
-        const int k = lane + 64 * (part + WPR * i);
-#pragma unroll
-        for (int rr = 0; rr < RPW; ++rr) {
-            const int r = erow0 + rr;
-            st[rr][i] = (k < D && r < nrows) ? G.state[(row0 + r) * D + k] : 0.f;
-        }
-    }
+    clear_tiles(G, sm, tid, G.zsum, G.zsumsq, G.zcount, G.zeps);
+    EnvLanes<RB> E(G, sm, G.zsum ? sm + G.off_z : nullptr, wv, lane);
     SMX_LDS_BARRIER();
-#pragma unroll
-    for (int rr = 0; rr < RPW; ++rr) {
-        const int r = erow0 + rr;
-#pragma unroll
-        for (int i = 0; i < KPL; ++i) {
-            const int k = lane + 64 * (part + WPR * i);
-            if (k < D && r < nrows) xs[r * ldx + k] = G.zsum ? zclamp_r(st[rr][i], zm[k], zs[k]) : st[rr][i];
-        }
-    }
+    E.start();
     SMX_LDS_BARRIER();
+    const long row0 = E.row0;
+    const int nrows = E.nrows;
 
     // ---- the output layer (K = H2, <= 32 outputs) is a latency chain if two waves walk its chunks alone (measured: 5.0 k
     // cycles of a 36 k-cycle step for 2 tiles x 8 chunks).  Its K is split over the EIGHT waves instead: wave w owns chunk w
@@ -153,16 +324,6 @@ __global__ __launch_bounds__(RNTH) void rollout_kernel(RollArgs G) {
     const float b3v = G.b3[hj];
     float sd0 = expf(G.log_var[hj]);
     if (G.noise_scale && hr < nrows) sd0 = sd0 * G.noise_scale[row0 + hr];
-    // the environment phase's per-element constants: the action column k % A and the drift term (an LDS round trip in front
-    // of the action read and an integer modulo per element and step otherwise)
-    int am[KPL];
-    float dr[KPL];
-#pragma unroll
-    for (int i = 0; i < KPL; ++i) {
-        const int k = lane + 64 * (part + WPR * i);
-        am[i] = k < D ? kmod[k] : 0;
-        dr[i] = 0.01f * (float)(((37 * k) % 17) - 8);
-    }
     int t = G.t0;
     RWALL(12); RCYC(13);
 #pragma unroll 1
@@ -173,56 +334,8 @@ __global__ __launch_bounds__(RNTH) void rollout_kernel(RollArgs G) {
         // this step's normal draw of the lane's (row, action) pair, requested before the layers (consumed behind them)
         float ev = 0.f;
         if (G.eps && hr < nrows) ev = G.eps[((size_t)step * G.n + row0 + hr) * A + hj];
-        // ---- the three layers ------------------------------------------------------------------------------
-#pragma unroll 1
-        for (int l = 0; l < (l3res ? 2 : 3); ++l) {
-            const float* Wp = l == 0 ? G.P1 : (l == 1 ? G.P2 : G.P3);
-            const float* bias = l == 0 ? G.b1 : (l == 1 ? G.b2 : G.b3);
-            const int H = l == 0 ? G.H1 : (l == 1 ? G.H2 : A);
-            const int K = l == 0 ? D : (l == 1 ? G.H1 : G.H2);
-            const float* in_lds = l == 0 ? xs : (l == 1 ? h1s : h2s);
-            const int ldi = l == 0 ? ldx : (l == 1 ? ldh1 : ldh2);
-            float* out_lds = l == 0 ? h1s : (l == 1 ? h2s : outs);
-            const int ldo = l == 0 ? ldh1 : (l == 1 ? ldh2 : RLDO);
-            const int tiles = (H + 15) >> 4;
-            const int C2 = pack_chunks(K);
-            const rsrc_t rw = make_rsrc(Wp, (unsigned)tiles * (unsigned)C2 * 2048u);
-            const rsrc_t rbias = make_rsrc(bias, (unsigned)H * 4u);
-#pragma unroll 1
-            for (int tb = 0; tb < tiles; tb += RNWV * NT) {
-                const int t0 = tb + wv;
-                if (t0 >= tiles) continue;                            // (wave-uniform)
-                float bs[NT];
-#pragma unroll
-                for (int g = 0; g < NT; ++g) {
-                    const int f = 16 * (t0 + RNWV * g) + fm;
-                    bs[g] = ld4(rbias, (f < H) ? (unsigned)f * 4u : OOB);
-                }
-                f32x4 acc[NT][RG];
-#pragma unroll
-                for (int g = 0; g < NT; ++g)
-#pragma unroll
-                    for (int r = 0; r < RG; ++r) acc[g][r] = (f32x4){0.f, 0.f, 0.f, 0.f};
-                fwd_tiles4<NT, RG, true>(acc, rw, tiles, C2, in_lds, ldi, t0, RNWV, lane);
-                // the kq groups meet; lane (fm, kq) then keeps row kq of every group: bias, activation, one word to LDS
-#pragma unroll
-                for (int g = 0; g < NT; ++g) {
-                    const int f = 16 * (t0 + RNWV * g) + fm;
-                    if (t0 + RNWV * g < tiles) {                      // (wave-uniform)
-#pragma unroll
-                        for (int r = 0; r < RG; ++r) {
-                            float z = meet_rows(acc[g][r]);
-                            z += bs[g];
-                            if (l == 2) z = act_f(z, G.out_act);
-                            else z = (z < 0.f) ? 0.f : z;
-                            out_lds[(4 * r + kq) * ldo + f] = (f < H) ? z : 0.f;
-                        }
-                    }
-                }
-            }
-            SMX_LDS_BARRIER();
-            RSTAMP(1 + l);
-        }
+        // ---- the three layers (the output layer below when its weights are register-resident) -------------------
+        layers4<RG, 3>(G, sm, l3res ? 2 : 3, G.out_act, wv, lane, [&](int l) { RSTAMP(1 + l); });
         if (l3res) {
             // wave w: chunk w of the output layer against h2 (zero weights past the last chunk: a zero partial sum)
             const float* bp = h2s + (lane & 3) * ldh2 + 8 * kq + 32 * (wv < C3 ? wv : 0);
@@ -284,68 +397,30 @@ __global__ __launch_bounds__(RNTH) void rollout_kernel(RollArgs G) {
         SMX_LDS_BARRIER();
         RSTAMP(4);
         // ---- environment step of the actors (smx_synth_env_step_f32's expressions), recording, next x tile ------
-#pragma unroll
-        for (int rr = 0; rr < RPW; ++rr) {
-            const int r = erow0 + rr;                      // wave-uniform
-            if (r < nrows) {
-                const long a = row0 + r;
-                float* orow = G.obs_roll ? G.obs_roll + (a * R + slot) * D : nullptr;
-                float sn0 = 0.f;
-#pragma unroll
-                for (int i = 0; i < KPL; ++i) {
-                    const int k = lane + 64 * (part + WPR * i);
-                    if (k < D) {
-                        const float ac = s_act[r * RMAX_A + am[i]];
-                        const float s = st[rr][i];
-                        const float drift = dr[i];
-                        float sn = (0.9f * s + 0.5f * ac) + drift;
-                        sn = fminf(fmaxf(sn, -10.0f), 10.0f);
-                        if (orow) {
-                            __builtin_nontemporal_store(s, &orow[k]);
-                            // the observation AFTER the step: row slot + 1 -- which the next step of this launch writes
-                            // itself (the same value, or the reset state when the episode ended here), so only the
-                            // launch's last step stores it
-                            if (slot + 1 < R) { if (last_step) __builtin_nontemporal_store(sn, &orow[D + k]); }
-                            else if (G.obs_last) G.obs_last[a * D + k] = sn;     // (the replay's obs_next field)
-                        }
-                        if (i == 0) sn0 = sn;
-                        const float next = done ? G.init_state[a * D + k] : sn;
-                        st[rr][i] = next;
-                        xs[r * ldx + k] = G.zsum ? zclamp_r(next, zm[k], zs[k]) : next;
-                    }
-                }
-                if (lane == 0 && part == 0) {               // (k == 0 lives in lane 0, i == 0 of the row's first wave)
-                    // sum_j a_j^2 in fp64, j ascending (the order of smx_synth_env_step_f32).  All RMAX_A reads are
-                    // issued up front (unused columns of the tile are zero and add +0.0): one LDS round trip, not A
-                    float av[RMAX_A];
-#pragma unroll
-                    for (int j = 0; j < RMAX_A; ++j) av[j] = s_act[r * RMAX_A + j];
-                    double q = 0.0;
-#pragma unroll
-                    for (int j = 0; j < RMAX_A; ++j) q += (double)av[j] * (double)av[j];
-                    if (G.rew_roll) __builtin_nontemporal_store((float)(-0.1 * q + 0.05 * (double)sn0), &G.rew_roll[a * R + slot]);
-                    if (G.done_roll) __builtin_nontemporal_store(done ? 1.0f : 0.0f, &G.done_roll[a * R + slot]);
-                }
-            }
-        }
+        E.step(s_act, done,
+               [&](long a) { return G.obs_roll ? G.obs_roll + (a * R + slot) * D : nullptr; },
+               [&](long a, float* orow, int k, float s, float sn) {
+                   if (orow) {
+                       __builtin_nontemporal_store(s, &orow[k]);
+                       // the observation AFTER the step: row slot + 1 -- which the next step of this launch writes itself
+                       // (the same value, or the reset state when the episode ended here), so only the launch's last
+                       // step stores it
+                       if (slot + 1 < R) { if (last_step) __builtin_nontemporal_store(sn, &orow[D + k]); }
+                       else if (G.obs_last) G.obs_last[a * D + k] = sn;     // (the replay's obs_next field)
+                   }
+               },
+               [&](long a, float*, float rew) {
+                   if (G.rew_roll) __builtin_nontemporal_store(rew, &G.rew_roll[a * R + slot]);
+                   if (G.done_roll) __builtin_nontemporal_store(done ? 1.0f : 0.0f, &G.done_roll[a * R + slot]);
+               });
         t = done ? 0 : t + 1;
         SMX_LDS_BARRIER();
         RSTAMP(5);
     }
     RWALL(14); RCYC(15);
-    // ---- the states the actors are left in ---------------------------------------------------------------
-#pragma unroll
-    for (int rr = 0; rr < RPW; ++rr) {
-        const int r = erow0 + rr;
-#pragma unroll
-        for (int i = 0; i < KPL; ++i) {
-            const int k = lane + 64 * (part + WPR * i);
-            if (k < D && r < nrows) G.state[(row0 + r) * D + k] = st[rr][i];
-        }
-    }
+    E.store();
 }
 
-constexpr int RROWS = ER / RNWV;  // actor rows a wavefront steps in the environment phase
 constexpr int RTG = 3;            // feature tiles a wave carries per pass (register budget of two waves per SIMD)
 
 // More actors than 8 per CU (n > 2048 on 256 CUs): 16 actors per workgroup on v_mfma_f32_16x16x4_f32 (the row-block loop of
@@ -357,9 +432,6 @@ __global__ __launch_bounds__(RNTH) void rollout16_kernel(RollArgs G) {
     const int tid = threadIdx.x, lane = tid & 63;
     const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int fm = lane & 15, kq = lane >> 4;
-    const long row0 = (long)blockIdx.x * ER;
-    int nrows = G.n - (int)row0;
-    if (nrows > ER) nrows = ER;
     const int D = G.D, A = G.A, R = G.R;
     float* xs = sm;
     float* h1s = sm + G.off_h1;
@@ -368,46 +440,13 @@ __global__ __launch_bounds__(RNTH) void rollout16_kernel(RollArgs G) {
     float* s_act = sm + G.off_act;              // [16][RMAX_A] clipped actions
     const int ldx = G.ldx, ldh1 = G.ldh1, ldh2 = G.ldh2;
 
-    // ---- once: clear the tiles; the z-filter's mean / std and k % A (an integer division per element and step
-    // otherwise) go to LDS tables; a lane owns elements k = lane + 64 i of the actor rows 2 wv and 2 wv + 1 and keeps
-    // their raw state in registers for the whole rollout
-    for (int i = tid; i < G.off_z; i += RNTH) sm[i] = 0.f;          // (incl. the action tile: its unused columns stay 0)
-    float* zm = sm + G.off_z;                   // [D] z-filter mean | [D] std | [D] k % A (as int)
-    float* zs = zm + D;
-    int* kmod = (int*)(zs + D);
-    for (int k = tid; k < D; k += RNTH) {
-        kmod[k] = k % A;
-        float m = 0.f, sz = 1.f;
-        if (G.zsum) {
-            const float c = G.zcount[0];
-            m = G.zsum[k] / c;
-            const float var = G.zsumsq[k] / c - m * m;
-            sz = sqrtf(var);
-            if (sz == sz) sz = fmaxf(sz, G.zeps);
-        }
-        zm[k] = m; zs[k] = sz;
-    }
-    float st[RROWS][RKV];
-#pragma unroll
-    for (int i = 0; i < RKV; ++i) {
-        const int k = lane + 64 * i;
-#pragma unroll
-        for (int rr = 0; rr < RROWS; ++rr) {
-            const int r = RROWS * wv + rr;
-            st[rr][i] = (k < D && r < nrows) ? G.state[(row0 + r) * D + k] : 0.f;
-        }
-    }
+    clear_tiles(G, sm, tid, G.zsum, G.zsumsq, G.zcount, G.zeps);
+    EnvLanes<ER, false> E(G, sm, G.zsum ? sm + G.off_z : nullptr, wv, lane);
     SMX_LDS_BARRIER();
-#pragma unroll
-    for (int rr = 0; rr < RROWS; ++rr) {
-        const int r = RROWS * wv + rr;
-#pragma unroll
-        for (int i = 0; i < RKV; ++i) {
-            const int k = lane + 64 * i;
-            if (k < D && r < nrows) xs[r * ldx + k] = G.zsum ? zclamp_r(st[rr][i], zm[k], zs[k]) : st[rr][i];
-        }
-    }
+    E.start();
     SMX_LDS_BARRIER();
+    const long row0 = E.row0;
+    const int nrows = E.nrows;
 
     int t = G.t0;
     RWALL(12); RCYC(13);
@@ -490,96 +529,280 @@ __global__ __launch_bounds__(RNTH) void rollout16_kernel(RollArgs G) {
         SMX_LDS_BARRIER();
         RSTAMP(4);
         // ---- environment step of the 16 actors (smx_synth_env_step_f32's expressions), recording, next x tile ---
-#pragma unroll
-        for (int rr = 0; rr < RROWS; ++rr) {
-            const int r = RROWS * wv + rr;                 // wave-uniform
-            if (r < nrows) {
-                const long a = row0 + r;
-                float* orow = G.obs_roll ? G.obs_roll + (a * R + slot) * D : nullptr;
-                float sn0 = 0.f;
-#pragma unroll
-                for (int i = 0; i < RKV; ++i) {
-                    const int k = lane + 64 * i;
-                    if (k < D) {
-                        const float ac = s_act[r * RMAX_A + kmod[k]];
-                        const float s = st[rr][i];
-                        const float drift = 0.01f * (float)(((37 * k) % 17) - 8);
-                        float sn = (0.9f * s + 0.5f * ac) + drift;
-                        sn = fminf(fmaxf(sn, -10.0f), 10.0f);
-                        if (orow) {
-                            orow[k] = s;
-                            if (slot + 1 < R) orow[D + k] = sn;
-                            else if (G.obs_last) G.obs_last[a * D + k] = sn;     // (the replay's obs_next field)
-                        }
-                        if (i == 0) sn0 = sn;
-                        const float next = done ? G.init_state[a * D + k] : sn;
-                        st[rr][i] = next;
-                        xs[r * ldx + k] = G.zsum ? zclamp_r(next, zm[k], zs[k]) : next;
-                    }
-                }
-                if (lane == 0) {                            // (k == 0 lives in lane 0, i == 0)
-                    // sum_j a_j^2 in fp64, j ascending (the order of smx_synth_env_step_f32).  All RMAX_A reads are
-                    // issued up front (unused columns of the tile are zero and add +0.0): one LDS round trip, not A
-                    float av[RMAX_A];
-#pragma unroll
-                    for (int j = 0; j < RMAX_A; ++j) av[j] = s_act[r * RMAX_A + j];
-                    double q = 0.0;
-#pragma unroll
-                    for (int j = 0; j < RMAX_A; ++j) q += (double)av[j] * (double)av[j];
-                    if (G.rew_roll) G.rew_roll[a * R + slot] = (float)(-0.1 * q + 0.05 * (double)sn0);
-                    if (G.done_roll) G.done_roll[a * R + slot] = done ? 1.0f : 0.0f;
-                }
-            }
-        }
+        E.step(s_act, done,
+               [&](long a) { return G.obs_roll ? G.obs_roll + (a * R + slot) * D : nullptr; },
+               [&](long a, float* orow, int k, float s, float sn) {
+                   if (orow) {
+                       orow[k] = s;
+                       if (slot + 1 < R) orow[D + k] = sn;
+                       else if (G.obs_last) G.obs_last[a * D + k] = sn;     // (the replay's obs_next field)
+                   }
+               },
+               [&](long a, float*, float rew) {
+                   if (G.rew_roll) G.rew_roll[a * R + slot] = rew;
+                   if (G.done_roll) G.done_roll[a * R + slot] = done ? 1.0f : 0.0f;
+               });
         t = done ? 0 : t + 1;
         SMX_LDS_BARRIER();
         RSTAMP(5);
     }
     RWALL(14); RCYC(15);
-    // ---- the states the actors are left in ---------------------------------------------------------------
-#pragma unroll
-    for (int rr = 0; rr < RROWS; ++rr) {
-        const int r = RROWS * wv + rr;
-#pragma unroll
-        for (int i = 0; i < RKV; ++i) {
-            const int k = lane + 64 * i;
-            if (k < D && r < nrows) G.state[(row0 + r) * D + k] = st[rr][i];
+    E.store();
+}
+
+// ---- DDPG ------------------------------------------------------------------------------------------------------------
+
+__device__ __forceinline__ float clip1(float a) {
+    if (a == a) a = fminf(fmaxf(a, -1.0f), 1.0f);          // (numpy's clip keeps a NaN)
+    return a;
+}
+
+// ddpg_agent.py:176-184 on one (actor, action) pair: clip, the exploration noise in fp64 rounded once into the fp32
+// action (action += noise() on a float32 array), clip.  x: the pair's OU state, zeroed at the episode start (pre_episode,
+// ddpg_agent.py:205-208).  The expressions keep action_noise.py's evaluation order.
+__device__ __forceinline__ float explore(float mu, int noise, float e, double sig, double theta, double dt, double root_dt,
+                                         int tau, double& x) {
+    float a = clip1(mu);
+    if (noise == SMX_DDPG_NOISE_GAUSSIAN) {
+        a = (float)((double)a + (0.0 + sig * (double)e));
+    } else if (noise == SMX_DDPG_NOISE_OU) {
+        if (tau == 0) x = 0.0;
+        x = (x + (theta * (0.0 - x)) * dt) + (sig * root_dt) * (double)e;
+        a = (float)((double)a + x);
+    }
+    return clip1(a);
+}
+
+// the closing transition's reward: r_j + g[e] r_{j+1} + ..., left to right in fp64 (the host wrapper's `+=` sequence),
+// exponents as ExpSenderWrapperSSARNStepBootstrap._discount_exponent (the reference's ramp-up quirk included)
+__device__ __forceinline__ float nstep_reward(const float* crew_a, const double* gpow, int N, int tau) {
+    const int j = tau - N + 1;
+    double R = (double)crew_a[j % N];
+    for (int u = j + 1; u <= tau; ++u) {
+        const int e = (u >= N - 1) ? (u - j) : (N - 1 - j);
+        R = R + gpow[e] * (double)crew_a[u % N];
+    }
+    return (float)R;
+}
+
+__device__ __forceinline__ long long ring_row(const DArgs& G, int kemit, long a) {
+    return (G.cursor + (long long)kemit * G.n + a) % G.capacity;
+}
+
+// RG row groups of four actors per workgroup; NT feature tiles a wave carries per pass.  Every block size gives the same
+// bits (layers4).
+template <int RG, int NT>
+__global__ __launch_bounds__(RNTH) void ddpg_rollout_kernel(DArgs G) {
+    constexpr int RB = 4 * RG;                       // actors per workgroup
+    extern __shared__ float sm[];
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int D = G.D, A = G.A, N = G.N;
+    const float* outs = sm + G.off_out;
+    float* s_act = sm + G.off_act;                   // [RB][RMAX_A] the actions of this step (unused columns stay 0)
+
+    clear_tiles(G, sm, tid, nullptr, nullptr, nullptr, 0.f);
+    EnvLanes<RB> E(G, sm, nullptr, wv, lane);
+    SMX_LDS_BARRIER();
+    E.start();
+    // the head's (actor, action) pair of this lane: its sigma and OU state for the whole rollout
+    const int hr = tid / A, hj = tid - hr * A;       // RB x A <= 512 pairs
+    const bool head = hr < E.nrows;
+    const long ha = E.row0 + hr;
+    double sig = 0.0, x = 0.0;
+    if (head) {
+        if (G.noise != SMX_DDPG_NOISE_NONE) sig = G.sigmas[ha];
+        if (G.noise == SMX_DDPG_NOISE_OU) x = G.ou[ha * A + hj];
+    }
+    SMX_LDS_BARRIER();
+
+    int tau = G.t0, kemit = 0;
+#pragma unroll 1
+    for (int step = 0; step < G.steps; ++step) {
+        float ev = 0.f;                              // this step's draw, requested before the layers
+        if (G.eps && head) ev = G.eps[((size_t)step * G.n + ha) * A + hj];
+        // ---- the actor's three layers (ReLU, ReLU, tanh) --------------------------------------------------------
+        layers4<RG, NT>(G, sm, 3, SMX_ACT_TANH, wv, lane, [](int) {});
+        const bool emit = tau >= N - 1;
+        const int slot = tau % N, jslot = (tau + 1) % N;   // (transition j = tau - N + 1 sits in slot j % N)
+        const bool done = (tau + 1 >= G.episode_len);
+        // ---- exploration: one (actor, action) pair per lane ------------------------------------------------------
+        if (head) {
+            const float a = explore(outs[hr * RLDO + hj], G.noise, ev, sig, G.theta, G.dt, G.root_dt, tau, x);
+            s_act[hr * RMAX_A + hj] = a;
+            float* ca = G.cact + (size_t)ha * N * A + hj;
+            ca[(size_t)slot * A] = a;
+            if (emit) G.act[ring_row(G, kemit, ha) * A + hj] = ca[(size_t)jslot * A];
+        }
+        SMX_LDS_BARRIER();
+        // ---- environment step (smx_synth_env_step_f32's expressions), n-step record, next x tile -------------------
+        struct Row { long long row; float* co; };
+        E.step(s_act, done,
+               [&](long a) { return Row{emit ? ring_row(G, kemit, a) : 0, G.cobs + (size_t)a * N * D}; },
+               [&](long, const Row& p, int k, float s, float sn) {
+                   p.co[(size_t)slot * D + k] = s;
+                   if (emit) {
+                       G.obs[p.row * D + k] = p.co[(size_t)jslot * D + k];
+                       G.obs_next[p.row * D + k] = sn;
+                   }
+               },
+               [&](long a, const Row& p, float rew) {
+                   float* cr = G.crew + (size_t)a * N;
+                   cr[slot] = rew;
+                   if (emit) {
+                       G.rew[p.row] = nstep_reward(cr, G.gpow, N, tau);
+                       G.done[p.row] = done ? 1.0f : 0.0f;
+                   }
+               });
+        if (emit) ++kemit;
+        tau = done ? 0 : tau + 1;
+        SMX_LDS_BARRIER();
+    }
+    // ---- the states the actors and their noise processes are left in ------------------------------------------------
+    E.store();
+    if (head && G.noise == SMX_DDPG_NOISE_OU) G.ou[ha * A + hj] = x;
+}
+
+// one step for four actors per workgroup, one wavefront each, given mu [n, A] (ld_mu)
+constexpr int SA_MAX = 64;
+__global__ __launch_bounds__(256) void ddpg_step_kernel(DArgs G, const float* mu, long long ld_mu) {
+    __shared__ float s_act[4][SA_MAX];
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    const long a = (long)blockIdx.x * 4 + w;
+    const int D = G.D, A = G.A, N = G.N, tau = G.t0;
+    const bool live = a < G.n;
+    const bool emit = tau >= N - 1;
+    const int slot = tau % N, jslot = (tau + 1) % N;   // (transition j = tau - N + 1 sits in slot j % N)
+    const bool done = (tau + 1 >= G.episode_len);
+    const long long row = (live && emit) ? ring_row(G, 0, a) : 0;
+    if (live && lane < A) {
+        double x = 0.0, sig = 0.0;
+        if (G.noise != SMX_DDPG_NOISE_NONE) sig = G.sigmas[a];
+        if (G.noise == SMX_DDPG_NOISE_OU) x = G.ou[a * A + lane];
+        const float e = G.eps ? G.eps[a * A + lane] : 0.f;
+        const float v = explore(mu[a * ld_mu + lane], G.noise, e, sig, G.theta, G.dt, G.root_dt, tau, x);
+        if (G.noise == SMX_DDPG_NOISE_OU) G.ou[a * A + lane] = x;
+        s_act[w][lane] = v;
+        float* ca = G.cact + (size_t)a * N * A + lane;
+        ca[(size_t)slot * A] = v;
+        if (emit) G.act[row * A + lane] = ca[(size_t)jslot * A];
+    }
+    __syncthreads();
+    if (!live) return;
+    float* co = G.cobs + (size_t)a * N * D;
+    float sn0 = 0.f;
+    for (int k = lane; k < D; k += 64) {
+        const float s = G.state[a * D + k];
+        const float sn = synth_next(s, s_act[w][k % A], synth_drift(k));
+        co[(size_t)slot * D + k] = s;
+        if (emit) {
+            G.obs[row * D + k] = co[(size_t)jslot * D + k];
+            G.obs_next[row * D + k] = sn;
+        }
+        if (k == 0) sn0 = sn;
+        G.state[a * D + k] = done ? G.init_state[a * D + k] : sn;
+    }
+    if (lane == 0) {
+        double q = 0.0;
+        for (int j = 0; j < A; ++j) {
+            const double v = (double)s_act[w][j];
+            q += v * v;
+        }
+        float* cr = G.crew + (size_t)a * N;
+        cr[slot] = synth_reward(q, sn0);
+        if (emit) {
+            G.rew[row] = nstep_reward(cr, G.gpow, N, tau);
+            G.done[row] = done ? 1.0f : 0.0f;
         }
     }
 }
 
+// ---- host side -------------------------------------------------------------------------------------------------------
+
 inline int rr64(int v) { return (v + 63) & ~63; }
 
-// row strides = 16 mod 64 words: the rows of a group (a word's lanes: row l & 3, k offset 8 (l >> 4)) and the epilogue's
-// one-word stores (row kq, feature fm) fall on distinct banks of the 64.  A tile holds pack_chunks(K) * 32 + 8 columns at
-// least (the loop's last prefetch reads one chunk it does not use).
-// (16 rows on the 16x16x4 loop: a word's lanes are row l & 15 -- strides of 4 mod 64 spread them.)
-int carve(RollArgs& G, int RB) {
-    if (RB == 16) { G.ldx = rr64(G.D) + 4; G.ldh1 = rr64(G.H1) + 4; G.ldh2 = rr64(G.H2) + 4; }
+// The LDS layout of an RB-actor block: x | h1 | h2 | out | actions [RB][RMAX_A] | the split output layer's partial sums
+// [RNWV][RB][32] (split_out) | the z-filter's mean and std [2][D] (ztables) | k % A [D].  Everything before the z tables
+// is cleared at the start.
+// Row strides on the 4-row loop = 16 mod 64 words: the rows of a group (a word's lanes: row l & 3, k offset 8 (l >> 4)) and
+// the epilogue's one-word stores (row kq, feature fm) fall on distinct banks of the 64.  A tile holds pack_chunks(K) * 32
+// + 8 columns at least (the loop's last prefetch reads one chunk it does not use).  On the 16x16x4 loop (mma16) a word's
+// lanes are row l & 15: strides of 4 mod 64 spread them.
+int carve(RollBase& G, int RB, bool mma16, bool split_out, bool ztables) {
+    if (mma16) { G.ldx = rr64(G.D) + 4; G.ldh1 = rr64(G.H1) + 4; G.ldh2 = rr64(G.H2) + 4; }
     else { G.ldx = rr64(G.D + 40) + 16; G.ldh1 = rr64(G.H1 + 40) + 16; G.ldh2 = rr64(G.H2 + 40) + 16; }
     G.off_h1 = RB * G.ldx;
     G.off_h2 = G.off_h1 + RB * G.ldh1;
     G.off_out = G.off_h2 + RB * G.ldh2;
     G.off_act = G.off_out + RB * RLDO;
     G.off_red3 = G.off_act + RB * RMAX_A;
-    G.off_z = G.off_red3 + RNWV * RB * 32;
-    G.lds_floats = G.off_z + 3 * G.D;
-    return G.lds_floats * (int)sizeof(float);
+    G.off_z = G.off_red3 + (split_out ? RNWV * RB * 32 : 0);
+    G.off_kmod = G.off_z + (ztables ? 2 * G.D : 0);
+    return (G.off_kmod + G.D) * (int)sizeof(float);
 }
 
-int device_cus() {
-    static int cus = 0;
-    if (cus == 0) {
-        int dev = 0, v = 0;
-        if (hipGetDevice(&dev) == hipSuccess &&
-            hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0) cus = v;
-        else cus = 256;
+// the shapes a persistent kernel takes: A <= 32, H1 and H2 multiples of 4 up to 640, D <= 512, and the 16-actor block's
+// layout within the LDS limit
+int32_t supported(int32_t D, int32_t H1, int32_t H2, int32_t A, bool mma16, bool split_out, bool ztables) {
+    if (!(D > 0 && H1 > 0 && H2 > 0 && A > 0 && A <= RMAX_A && H1 % 4 == 0 && H2 % 4 == 0)) return 0;
+    if (!(H1 <= 640 && H2 <= 640 && D <= 64 * RKV)) return 0;
+    RollBase G;
+    memset(&G, 0, sizeof(G));
+    G.D = D; G.H1 = H1; G.H2 = H2; G.A = A;
+    return carve(G, 16, mma16, split_out, ztables) <= ROLL_MAX_LDS;
+}
+
+// actors per workgroup: `forced` (4 | 8 | 16), or for 0 the smallest of 4 and 8 whose grid fits the chip once, else 16
+int pick_block(int forced, int n) {
+    if (forced) return forced;
+    for (int c = 4; c <= 8; c *= 2)
+        if ((n + c - 1) / c <= smx_cu_count()) return c;
+    return 16;
+}
+
+// one workgroup of RNTH lanes per rb actors, with LDS for one workgroup per CU; each kernel's dynamic-LDS limit is raised
+// at its first launch
+template <auto K, typename Args>
+int launch(const Args& G, int rb, int lds, smx_stream_t stream) {
+    static const hipError_t attr = hipFuncSetAttribute((const void*)K, hipFuncAttributeMaxDynamicSharedMemorySize, ROLL_MAX_LDS);
+    (void)attr;
+    if (lds < ROLL_EXCLUSIVE_LDS) lds = ROLL_EXCLUSIVE_LDS;
+    hipLaunchKernelGGL(K, dim3((G.n + rb - 1) / rb), dim3(RNTH), lds, smx_s(stream), G);
+    SMX_LAUNCH_CHECK();
+    return SMX_OK;
+}
+
+// the fields both DDPG entry points take from the argument block
+int common_args(const smx_ddpg_rollout_t* a, DArgs& G) {
+    SMX_REQUIRE(a && a->state && a->init_state && a->gpow && a->carry_obs && a->carry_act && a->carry_rew, SMX_E_NULL);
+    SMX_REQUIRE(a->obs && a->obs_next && a->actions && a->rewards && a->dones, SMX_E_NULL);
+    SMX_REQUIRE(a->n > 0 && a->D > 0 && a->A > 0 && a->n_step > 0 && a->episode_len > 0 && a->t >= 0, SMX_E_SHAPE);
+    SMX_REQUIRE(a->capacity > 0 && a->cursor >= 0 && a->cursor < a->capacity, SMX_E_SHAPE);
+    SMX_REQUIRE(a->noise_type >= SMX_DDPG_NOISE_NONE && a->noise_type <= SMX_DDPG_NOISE_OU, SMX_E_SHAPE);
+    SMX_REQUIRE(a->noise_type == SMX_DDPG_NOISE_NONE || (a->eps && a->sigmas), SMX_E_NULL);
+    SMX_REQUIRE(a->noise_type != SMX_DDPG_NOISE_OU || a->ou, SMX_E_NULL);
+    memset(&G, 0, sizeof(G));
+    G.D = a->D; G.A = a->A; G.n = a->n; G.steps = a->steps; G.t0 = a->t; G.episode_len = a->episode_len;
+    G.N = a->n_step; G.noise = a->noise_type;
+    G.eps = a->noise_type == SMX_DDPG_NOISE_NONE ? nullptr : a->eps;
+    G.sigmas = a->sigmas; G.theta = a->theta; G.dt = a->dt; G.root_dt = a->root_dt;
+    G.gpow = a->gpow; G.ou = a->ou;
+    G.state = a->state; G.init_state = a->init_state;
+    G.cobs = a->carry_obs; G.cact = a->carry_act; G.crew = a->carry_rew;
+    G.obs = a->obs; G.obs_next = a->obs_next; G.act = a->actions; G.rew = a->rewards; G.done = a->dones;
+    G.cursor = a->cursor; G.capacity = a->capacity;
+    return SMX_OK;
+}
+
+// closing steps among `steps` steps from clock t
+long long emitting_steps(int t, int steps, int episode_len, int N) {
+    long long m = 0;
+    for (int s = 0; s < steps; ++s) {
+        if (t >= N - 1) ++m;
+        t = (t + 1 >= episode_len) ? 0 : t + 1;
     }
-    return cus;
+    return m;
 }
-
-constexpr int ROLL_MAX_LDS = 150 * 1024;
-constexpr int ROLL_EXCLUSIVE_LDS = 84 * 1024;
 
 }  // namespace
 
@@ -589,12 +812,7 @@ extern "C" void smx_rollout_debug_tbuf(void* p) { (void)hipMemcpyToSymbol(HIP_SY
 #endif
 
 extern "C" int32_t smx_synth_rollout_supported(int32_t D, int32_t H1, int32_t H2, int32_t A) {
-    if (!(D > 0 && H1 > 0 && H2 > 0 && A > 0 && A <= RMAX_A && H1 % 4 == 0 && H2 % 4 == 0)) return 0;
-    if (!(H1 <= 640 && H2 <= 640 && D <= 64 * RKV)) return 0;
-    RollArgs G;
-    memset(&G, 0, sizeof(G));
-    G.D = D; G.H1 = H1; G.H2 = H2; G.A = A;
-    return carve(G, 16) <= ROLL_MAX_LDS;
+    return supported(D, H1, H2, A, /*mma16=*/true, /*split_out=*/true, /*ztables=*/true);
 }
 
 extern "C" int smx_synth_rollout_f32(const smx_synth_rollout_t* a, smx_stream_t stream) {
@@ -602,6 +820,8 @@ extern "C" int smx_synth_rollout_f32(const smx_synth_rollout_t* a, smx_stream_t 
     const smx_mlp3_t& n = *a->net;
     SMX_REQUIRE(smx_synth_rollout_supported(n.D, n.H1, n.H2, n.OUT), SMX_E_UNSUPPORTED);
     SMX_REQUIRE(a->n > 0 && a->steps > 0 && a->episode_len > 0 && a->rows_per_actor > 0, SMX_E_SHAPE);
+    SMX_REQUIRE(a->actors_per_workgroup == 0 || a->actors_per_workgroup == 4 || a->actors_per_workgroup == 8 ||
+                a->actors_per_workgroup == 16, SMX_E_SHAPE);
     // (every roll table is indexed by slot + step: the bound holds whichever of them is recorded)
     const bool records = a->obs_roll || a->act_roll || a->rew_roll || a->done_roll || a->pd_roll;
     SMX_REQUIRE(a->slot >= 0 && (!records || a->slot + a->steps <= a->rows_per_actor), SMX_E_SHAPE);
@@ -620,30 +840,50 @@ extern "C" int smx_synth_rollout_f32(const smx_synth_rollout_t* a, smx_stream_t 
     G.n = a->n; G.t0 = a->t; G.episode_len = a->episode_len; G.steps = a->steps; G.R = a->rows_per_actor; G.slot0 = a->slot;
     G.obs_roll = a->obs_roll; G.act_roll = a->act_roll; G.rew_roll = a->rew_roll; G.done_roll = a->done_roll;
     G.pd_roll = a->pd_roll; G.obs_last = a->obs_last;
-    // 4 or 8 actors per workgroup while that grid fits the chip once, else 16 (SMX_ROLLOUT_RG = 1 | 2 | 4 overrides: measurements)
-    int rg = 4;
-    for (int c = 1; c <= 2; c *= 2)
-        if ((a->n + 4 * c - 1) / (4 * c) <= device_cus()) { rg = c; break; }
-    static int forced = -1;
-    if (forced < 0) {
-        const char* e = getenv("SMX_ROLLOUT_RG");
-        forced = e ? atoi(e) : 0;
-    }
-    if (forced == 1 || forced == 2 || forced == 4) rg = forced;
-    int lds = carve(G, 4 * rg);
-    // one workgroup per CU: each streams the packed weights through the CU's four SIMDs by itself
-    if (lds < ROLL_EXCLUSIVE_LDS) lds = ROLL_EXCLUSIVE_LDS;
-    static bool attr_set = false;
-    if (!attr_set) {
-        (void)hipFuncSetAttribute((const void*)rollout_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, ROLL_MAX_LDS);
-        (void)hipFuncSetAttribute((const void*)rollout_kernel<2>, hipFuncAttributeMaxDynamicSharedMemorySize, ROLL_MAX_LDS);
-        (void)hipFuncSetAttribute((const void*)rollout16_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, ROLL_MAX_LDS);
-        attr_set = true;
-    }
-    const int blocks = (a->n + 4 * rg - 1) / (4 * rg);
-    if (rg == 1) hipLaunchKernelGGL(rollout_kernel<1>, dim3(blocks), dim3(RNTH), lds, smx_s(stream), G);
-    else if (rg == 2) hipLaunchKernelGGL(rollout_kernel<2>, dim3(blocks), dim3(RNTH), lds, smx_s(stream), G);
-    else hipLaunchKernelGGL(rollout16_kernel, dim3(blocks), dim3(RNTH), lds, smx_s(stream), G);
+    const int rb = pick_block(a->actors_per_workgroup, a->n);
+    const int lds = carve(G, rb, /*mma16=*/rb == 16, /*split_out=*/true, /*ztables=*/true);
+    if (rb == 4) return launch<rollout_kernel<1>>(G, rb, lds, stream);
+    if (rb == 8) return launch<rollout_kernel<2>>(G, rb, lds, stream);
+    return launch<rollout16_kernel>(G, rb, lds, stream);
+}
+
+extern "C" int32_t smx_synth_ddpg_rollout_supported(int32_t D, int32_t H1, int32_t H2, int32_t A) {
+    return supported(D, H1, H2, A, /*mma16=*/false, /*split_out=*/false, /*ztables=*/false);
+}
+
+extern "C" int smx_synth_ddpg_rollout_f32(const smx_ddpg_rollout_t* a, smx_stream_t stream) {
+    SMX_REQUIRE(a && a->net && a->packed, SMX_E_NULL);
+    const smx_mlp3_t& net = *a->net;
+    SMX_REQUIRE(smx_synth_ddpg_rollout_supported(net.D, net.H1, net.H2, net.OUT), SMX_E_UNSUPPORTED);
+    SMX_REQUIRE(net.D == a->D && net.OUT == a->A && a->steps > 0, SMX_E_SHAPE);
+    SMX_REQUIRE(a->actors_per_workgroup == 0 || a->actors_per_workgroup == 4 || a->actors_per_workgroup == 8 ||
+                a->actors_per_workgroup == 16, SMX_E_SHAPE);
+    SMX_REQUIRE(((uintptr_t)a->packed & 15) == 0 && ((uintptr_t)net.b1 & 3) == 0, SMX_E_ALIGN);
+    DArgs G;
+    const int rc = common_args(a, G);
+    if (rc != SMX_OK) return rc;
+    // two workgroups must never write the same ring row: all n m rows of the call are distinct
+    SMX_REQUIRE((long long)a->n * emitting_steps(a->t, a->steps, a->episode_len, a->n_step) <= a->capacity, SMX_E_SHAPE);
+    G.P1 = a->packed;
+    G.P2 = a->packed + 4 * pack_off(net.D, net.H1, net.H2, net.OUT, 1);
+    G.P3 = a->packed + 4 * pack_off(net.D, net.H1, net.H2, net.OUT, 2);
+    G.b1 = net.b1; G.b2 = net.b2; G.b3 = net.b3; G.H1 = net.H1; G.H2 = net.H2;
+    const int rb = pick_block(a->actors_per_workgroup, a->n);
+    const int lds = carve(G, rb, /*mma16=*/false, /*split_out=*/false, /*ztables=*/false);
+    if (rb == 4) return launch<ddpg_rollout_kernel<1, 3>>(G, rb, lds, stream);
+    if (rb == 8) return launch<ddpg_rollout_kernel<2, 3>>(G, rb, lds, stream);
+    return launch<ddpg_rollout_kernel<4, 2>>(G, rb, lds, stream);
+}
+
+extern "C" int smx_synth_ddpg_step_f32(const smx_ddpg_rollout_t* a, const float* mu, int64_t ld_mu, smx_stream_t stream) {
+    SMX_REQUIRE(mu, SMX_E_NULL);
+    DArgs G;
+    const int rc = common_args(a, G);
+    if (rc != SMX_OK) return rc;
+    SMX_REQUIRE(a->A <= SA_MAX && ld_mu >= a->A, SMX_E_SHAPE);
+    SMX_REQUIRE((long long)a->n <= a->capacity, SMX_E_SHAPE);
+    G.steps = 1;
+    hipLaunchKernelGGL(ddpg_step_kernel, dim3((a->n + 3) / 4), dim3(256), 0, smx_s(stream), G, mu, (long long)ld_mu);
     SMX_LAUNCH_CHECK();
     return SMX_OK;
 }

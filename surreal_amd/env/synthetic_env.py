@@ -164,15 +164,16 @@ class SyntheticVecEnv(object):
         self.t = 0 if self.t + 1 >= self.episode_len else self.t + 1
         return self.state
 
-    def rollout(self, agent, eps=None):
+    def rollout(self, agent, eps=None, actors_per_workgroup=0):
         """A whole recorded rollout (start_rollout(T) first) under `agent`'s plain-MLP policy: ONE launch
-        (smx_synth_rollout_f32: 16 actors per workgroup through all T steps) where the shapes allow it, else
+        (smx_synth_rollout_f32: a workgroup owns 4, 8 or 16 actors through all T steps) where the shapes allow it, else
         THREE launches per environment step (the two hidden layers, then one launch that forms the policy mean,
         samples the action, steps every actor, records the transition and z-filters the next observation).
         Same numbers (1e-6: the layers' fp32 summation order differs between the two) as
         ``for t: agent.act_batch(state) -> step(actions, pds)``.
         eps: [T, n, A] standard-normal draws (default: drawn here in one launch; None-eps agents in
-        a deterministic mode ignore it)."""
+        a deterministic mode ignore it).  actors_per_workgroup: 4 | 8 | 16 forces the one-launch kernel's block (0:
+        automatic; 4 and 8 give the same bits, 16 sums the layers in another order)."""
         T, n, K = self.T, self.n, self.K
         assert self.slot == 0 and 'pds' in self.rolls, 'start_rollout(T, info_width=2 * A) first'
         deterministic = agent.agent_mode in ('eval_deterministic', 'eval_deterministic_local')
@@ -186,7 +187,7 @@ class SyntheticVecEnv(object):
         actor = agent.model.actor
         plain_mlp = not (agent.rnn_config.if_rnn_policy or agent.model.if_pixel)
         if plain_mlp and self.persistent and K.synth_rollout_supported(actor):
-            # ONE launch for the whole rollout: a workgroup owns 16 actors and walks them through all T steps
+            # ONE launch for the whole rollout: a workgroup owns 4, 8 or 16 actors and walks them through all T steps
             # (csrc/smx_rollout.hip).  The packed weight copy is refreshed here: the agent's parameters only change
             # between rollouts (fetch_parameter)
             if getattr(self, '_pk', None) is None or self._pk.numel() != K.epoch_packed_numel(actor):
@@ -194,7 +195,7 @@ class SyntheticVecEnv(object):
             K.epoch_pack([(actor, self._pk)])
             K.synth_rollout(actor, self._pk, L.SMX_ACT_TANH, self.state, self.init_state, log_var, noise,
                             None if deterministic else eps.contiguous(), self.t, self.episode_len, T, self.slot,
-                            self.rolls, zf)
+                            self.rolls, zf, actors_per_workgroup)
             self.slot += T
             for _ in range(T):
                 self.t = 0 if self.t + 1 >= self.episode_len else self.t + 1
@@ -234,12 +235,13 @@ class SyntheticVecEnv(object):
         return (self.persistent and self.pixel is None and not agent.rnn_config.if_rnn_policy and not agent.model.if_pixel
                 and self.K.synth_rollout_supported(agent.model.actor))
 
-    def rollout_into(self, agent, out, eps=None):
+    def rollout_into(self, agent, out, eps=None, actors_per_workgroup=0):
         """A whole rollout recorded STRAIGHT INTO a replay's slots (Replay.reserve_batch(n, window_shapes(T)) ->
         `out`: obs [n, T, D], obs_next [n, 1, D], actions [n, T, A], rewards / dones [n, T], pds [n, T, 2A]): with
         stride == n_step == T the moving-window rule (exp_sender_wrapper.py:209-228) makes the one window of an actor
         its rollout, so nothing is cut and nothing is copied -- the one-launch kernel writes the fields where the
-        learner will read them.  Starts at an episode boundary (reset() first), like start_rollout()."""
+        learner will read them.  Starts at an episode boundary (reset() first), like start_rollout().
+        actors_per_workgroup: as in rollout()."""
         K, n = self.K, self.n
         T = out['obs'].shape[1]
         assert self.t == 0 and T <= self.episode_len and self.can_rollout_into(agent)
@@ -255,7 +257,8 @@ class SyntheticVecEnv(object):
                  'pds': out['pds'], 'obs_last': out['obs_next']}
         K.synth_rollout(actor, self._pk, L.SMX_ACT_TANH, self.state, self.init_state, agent.model.log_var.view(-1),
                         agent.batch_noise(n).view(-1), None if deterministic else eps.contiguous(), self.t,
-                        self.episode_len, T, 0, rolls, agent.model.z_filter if agent.use_z_filter else None)
+                        self.episode_len, T, 0, rolls, agent.model.z_filter if agent.use_z_filter else None,
+                        actors_per_workgroup)
         for _ in range(T):
             self.t = 0 if self.t + 1 >= self.episode_len else self.t + 1
 

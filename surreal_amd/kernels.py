@@ -621,10 +621,11 @@ class HipKernels(object):
         return bool(self.lib.smx_synth_rollout_supported(net.D, net.H1, net.H2, net.OUT))
 
     def synth_rollout(self, net, packed, out_act, state, init_state, log_var, noise_scale, eps, t, episode_len,
-                      steps, slot, rolls, zfilter):
+                      steps, slot, rolls, zfilter, actors_per_workgroup=0):
         """`steps` acting + environment steps of all actors in ONE launch (csrc/smx_rollout.hip): a workgroup owns
-        16 actors for the whole rollout.  packed: epoch_pack of `net`; eps [steps, n, A] or None; rolls as in
-        synth_act_env_step ([n, T + 1, .] tables)."""
+        4, 8 or 16 actors for the whole rollout (actors_per_workgroup; 0: the smallest whose grid fits the CUs once).
+        packed: epoch_pack of `net`; eps [steps, n, A] or None; rolls as in synth_act_env_step ([n, T + 1, .]
+        tables)."""
         n, D = state.shape
         p = L.SynthRollout()
         p.net, p.packed, p.out_act, p.n = ctypes.pointer(net.desc), L.ptr(packed), int(out_act), n
@@ -641,6 +642,7 @@ class HipKernels(object):
         p.obs_roll, p.act_roll = L.ptr(r.get('obs')), L.ptr(r.get('actions'))
         p.rew_roll, p.done_roll, p.pd_roll = L.ptr(r.get('rewards')), L.ptr(r.get('dones')), L.ptr(r.get('pds'))
         p.obs_last = L.ptr(r.get('obs_last'))          # rows_per_actor == steps: the replay's layout (obs_next apart)
+        p.actors_per_workgroup = int(actors_per_workgroup)
         L.call('smx_synth_rollout_f32', ctypes.byref(p), self._st())
 
     def synth_ddpg_rollout_supported(self, net):
@@ -648,7 +650,7 @@ class HipKernels(object):
 
     @staticmethod
     def _ddpg_args(r, steps, net=None, packed=None, actors_per_workgroup=0):
-        """struct smx_ddpg_rollout from the dict SyntheticVecEnv.ddpg_rollout_into builds: state / init_state [n, D],
+        """smx_ddpg_rollout_t from the dict SyntheticVecEnv.ddpg_rollout_into builds: state / init_state [n, D],
         t, episode_len, n_step, noise_type, eps, sigmas (fp64), theta / dt / root_dt, gpow (fp64 [n_step]), ou (fp64
         [n, A]), carry_obs / carry_act / carry_rew, the ring tables by replay field name, cursor, capacity"""
         n, D = r['state'].shape
@@ -672,7 +674,7 @@ class HipKernels(object):
 
     def synth_ddpg_rollout(self, net, packed, r, steps, actors_per_workgroup=0):
         """`steps` DDPG acting + environment steps of all actors with their n-step transitions written into the ring
-        tables, ONE launch (csrc/smx_ddpg_rollout.hip).  packed: epoch_pack of the actor `net`; r: see _ddpg_args
+        tables, ONE launch (csrc/smx_rollout.hip).  packed: epoch_pack of the actor `net`; r: see _ddpg_args
         (eps [steps, n, A])"""
         if r['eps'] is not None:
             assert r['eps'].is_contiguous() and tuple(r['eps'].shape) == (steps, r['state'].shape[0], net.OUT)

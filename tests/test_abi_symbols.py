@@ -84,6 +84,7 @@ STRUCTS = {               # C typedef -> ctypes mirror in surreal_amd/_lib.py
     'smx_epoch_job_t': 'EpochJob', 'smx_epoch_pack_t': 'EpochPack', 'smx_epoch_prep_t': 'EpochPrep', 'smx_learn_epilogue_t': 'LearnEpilogue',
     'smx_xchg_t': 'Xchg', 'smx_synth_rollout_t': 'SynthRollout', 'smx_linear_job_t': 'LinearJob',
     'smx_gather_job_t': 'GatherJob', 'smx_ddpg_net_t': 'DdpgNet', 'smx_ddpg_rows_t': 'DdpgRows', 'smx_ddpg_update_t': 'DdpgUpdate',
+    'smx_ddpg_rollout_t': 'DdpgRollout',
 }
 
 
@@ -114,10 +115,21 @@ def test_struct_layouts_match_the_ctypes_mirrors(tmp_path):
         assert got[(cname, 'sizeof')] == ctypes.sizeof(cls), (cname, got[(cname, 'sizeof')], ctypes.sizeof(cls))
         for fname, _ in cls._fields_:
             assert got[(cname, fname)] == getattr(cls, fname).offset, (cname, fname)
-    # every struct typedef of the header has a mirror (anonymous `typedef struct {` and named ones)
+    # every struct typedef of the header has a mirror (anonymous `typedef struct {`, named ones, and a
+    # `typedef struct tag name;` after the struct)
     hdr = re.sub(r'/\*.*?\*/', '', open(os.path.join(ROOT, 'include', 'surreal_amd.h')).read(), flags=re.S)
     typedefs = set(re.findall(r'}\s*(smx_\w+_t)\s*;', hdr)) - {'smx_ppo_ctrl_t'}      # (addressed as words)
+    typedefs |= set(re.findall(r'typedef\s+struct\s+\w+\s+(smx_\w+_t)\s*;', hdr))
     assert typedefs == set(STRUCTS), (sorted(typedefs), sorted(STRUCTS))
+
+
+def test_ddpg_noise_defines_match_the_bindings():
+    """the SMX_DDPG_NOISE_* values smx_ddpg_rollout_t.noise_type takes, as the header defines them"""
+    from surreal_amd import _lib as L
+    hdr = open(os.path.join(ROOT, 'include', 'surreal_amd.h')).read()
+    assert (L.SMX_DDPG_NOISE_NONE, L.SMX_DDPG_NOISE_GAUSSIAN, L.SMX_DDPG_NOISE_OU) == tuple(
+        int(re.search(r'#define %s (\d+)' % k, hdr).group(1))
+        for k in ('SMX_DDPG_NOISE_NONE', 'SMX_DDPG_NOISE_GAUSSIAN', 'SMX_DDPG_NOISE_OU'))
 
 
 def test_ctypes_signatures_match_the_header():

@@ -1,9 +1,6 @@
 """CPU tier: SyntheticVecEnv.ddpg_rollout_into (DDPG acting + n-step transitions written into the uniform replay's
 ring) on the torch-CPU double of its kernels against the host path -- n SyntheticEnv + DDPGAgent +
-ExpSenderWrapperSSARNStepBootstrap stepped one by one -- bit for bit; its refusals; the ctypes mirror of
-struct smx_ddpg_rollout."""
-import ctypes
-import os
+ExpSenderWrapperSSARNStepBootstrap stepped one by one -- bit for bit; its refusals."""
 
 import numpy as np
 import pytest
@@ -11,7 +8,6 @@ import torch
 
 import ddpg_rollout_cases as DC
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 @pytest.fixture
@@ -170,33 +166,3 @@ def test_batch_sigmas_follow_the_per_agent_rule(ddpg_double):
         lci, eci, sci = DC.configs(5, 2, 7, max_sigma=0.7)
         assert float(s[i]) == DC.make_agent(lci, eci, sci, agent_id=i).sigma
     assert float(agent.batch_sigmas(1)[0]) == 0.7 / 3.0
-
-
-def test_ddpg_rollout_struct_layout_matches_the_ctypes_mirror(tmp_path):
-    """struct smx_ddpg_rollout crosses the C ABI by pointer: sizeof and every field's offset as gcc lays them out"""
-    import subprocess
-    from surreal_amd import _lib as L
-    cls = L.DdpgRollout
-    lines = ['#include <stdio.h>', '#include <stddef.h>', '#include "surreal_amd.h"', 'int main(void) {',
-             '  printf("sizeof %zu\\n", sizeof(struct smx_ddpg_rollout));']
-    for fname, _ in cls._fields_:
-        lines.append('  printf("%s %%zu\\n", offsetof(struct smx_ddpg_rollout, %s));' % (fname, fname))
-    lines += ['  return 0;', '}']
-    src = tmp_path / 'layout.c'
-    src.write_text('\n'.join(lines))
-    exe = tmp_path / 'layout'
-    subprocess.run(['gcc', '-I', os.path.join(ROOT, 'include'), str(src), '-o', str(exe)], check=True)
-    got = dict(ln.split() for ln in subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.splitlines())
-    assert int(got['sizeof']) == ctypes.sizeof(cls)
-    for fname, _ in cls._fields_:
-        assert int(got[fname]) == getattr(cls, fname).offset, fname
-    hdr = open(os.path.join(ROOT, 'include', 'surreal_amd.h')).read()
-    body = hdr[hdr.index('struct smx_ddpg_rollout {'):]
-    body = body[:body.index('};')]
-    import re
-    body = re.sub(r'/\*.*?\*/', '', body, flags=re.S)
-    names = re.findall(r'(\w+)\s*(?=[,;])', body)
-    assert names == [f for f, _ in cls._fields_]
-    assert (L.SMX_DDPG_NOISE_NONE, L.SMX_DDPG_NOISE_GAUSSIAN, L.SMX_DDPG_NOISE_OU) == tuple(
-        int(re.search(r'#define %s (\d+)' % k, hdr).group(1))
-        for k in ('SMX_DDPG_NOISE_NONE', 'SMX_DDPG_NOISE_GAUSSIAN', 'SMX_DDPG_NOISE_OU'))

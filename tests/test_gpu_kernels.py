@@ -1567,7 +1567,7 @@ def _rollout_setup(n, D, A, hidden, T, episode_len, use_z, deterministic, seed):
         agent.model.z_filter.load_state_dict(synthetic.make_zfilter_state(D, seed=seed + 1))
     eps = None if deterministic else torch.randn(T, n, A, generator=torch.Generator().manual_seed(seed)).cuda()
 
-    def run(how):
+    def run(how, actors_per_workgroup=0):
         venv = SyntheticVecEnv(n, D, A, episode_len=episode_len, seeds=list(range(n)))
         # (an episode may end inside the recorded span here: the kernels' reset path is exercised on purpose)
         venv.T, venv.slot = T, 0
@@ -1576,7 +1576,7 @@ def _rollout_setup(n, D, A, hidden, T, episode_len, use_z, deterministic, seed):
                       'pds': f(n, T + 1, 2 * A)}
         if how == 'persistent':
             venv.persistent = True
-            venv.rollout(agent, eps=eps)
+            venv.rollout(agent, eps=eps, actors_per_workgroup=actors_per_workgroup)
         elif how == 'reference':
             venv.rollout_reference(agent, eps)
         else:
@@ -1603,7 +1603,7 @@ def test_persistent_rollout_kernel(K, n, D, A, hidden, T, ep, use_z, det):
     the means, then smx_synth_act_env_step_f32) and the layered per-step path (GEMM launches per layer) record, to fp32
     rounding of the layer sums: the three sum a layer's products in three different orders.  Everything that is not a
     function of the means is exact: dones, the step counter, the zero pattern.  Every row-group count is run (the host
-    picks 1 for <= 1024 actors; SMX_ROLLOUT_RG forces it)."""
+    picks 1 for <= 1024 actors; actors_per_workgroup forces it)."""
     agent, run = _rollout_setup(n, D, A, hidden, T, ep, use_z, det, seed=11)
     assert K.synth_rollout_supported(agent.model.actor)
     ref, layered = run('reference'), run('layered')
@@ -1626,25 +1626,8 @@ def test_persistent_rollout_kernel_row_group_counts_agree(K, rg):
     """4 and 8 actors per workgroup are the same arithmetic per actor (a row group is independent of its neighbours in
     the workgroup): bit-identical recordings, incl. a partial last workgroup.  16 actors per workgroup (what more than
     2048 actors run on) is the 16x16x4 loop: equal to fp32 rounding of the layer sums."""
-    import subprocess
-    import sys
-    # the row-group override is read once per process: one child per forced value, compared through a file
-    code = r'''
-import sys, torch
-sys.path.insert(0, %r)
-import test_gpu_kernels as TK
-agent, run = TK._rollout_setup(37, 29, 5, (40, 24), 6, 4, True, False, seed=13)
-out = run('persistent')
-torch.save({k: v for k, v in out.items()}, sys.argv[1])
-''' % os.path.dirname(os.path.abspath(__file__))
-    import tempfile
-    outs = []
-    for force in ('0', str(rg)):
-        with tempfile.NamedTemporaryFile(suffix='.pt') as f:
-            env = dict(os.environ, SMX_ROLLOUT_RG=force)
-            r = subprocess.run([sys.executable, '-c', code, f.name], env=env, capture_output=True, text=True, timeout=300)
-            assert r.returncode == 0, r.stderr[-3000:]
-            outs.append(torch.load(f.name))
+    agent, run = _rollout_setup(37, 29, 5, (40, 24), 6, 4, True, False, seed=13)
+    outs = [run('persistent'), run('persistent', actors_per_workgroup=4 * rg)]
     for k in outs[0]:
         if k == 't':
             assert outs[0][k] == outs[1][k]
