@@ -1044,6 +1044,45 @@ typedef struct smx_synth_rollout {
 int32_t smx_synth_rollout_supported(int32_t D, int32_t H1, int32_t H2, int32_t A);
 int smx_synth_rollout_f32(const smx_synth_rollout_t* args, smx_stream_t stream);
 
+/* The same rollout for a PPO policy with a one-layer LSTM stem on low-dimensional observations (the reference's default
+ * policy: surreal/main/ppo_configs.py if_rnn_policy, rnn_layer 1), in ONE launch: per step and actor (all actors share
+ * the episode clock)
+ *   x = zfilter(s)                                     (or raw, as above)
+ *   g = W_ih x + b_ih + W_hh h + b_hh                   gate order i, f, g, o (ppo_net.py:143-152, 338-349)
+ *   c' = sigmoid(f) c + sigmoid(i) tanh(g);  h' = sigmoid(o) tanh(c')
+ *   mu = act(MLP(h')), the DiagGauss sample and clip, the synthetic environment step and its recording as above
+ * -- PPOAgent.act with the LSTM (surreal/agent/ppo_agent.py:106-154, ppo_net.py:317-354) for every actor and step.
+ * The kernel replaces a per-step act_batch (z-filter, smx_lstm_forward_f32 at T = 1, the actor, the sampling head,
+ * the step launch).  roll.net is the actor with roll.net->D == lstm->H; lstm_packed: smx_lstm_rollout_pack_f32 of lstm.
+ * hidden: the logical units (lstm->H is padded to a multiple of 4 with zero weights; the padded units stay zero and are
+ * never written): every state buffer below is [n, hidden].  h0 / c0 (nullable, both or neither: zeros) the state
+ * before the first step; hN / cN the state after the last; h_before / c_before (nullable) the state before the last
+ * step (what PPOAgent.batch_cells_before holds).  cell_roll [n, rows_per_actor, 2, hidden] (nullable): the state every
+ * actor held BEFORE each step, h then c, at row slot + step -- ppo_agent.py:133-135 onetime_infos.  Gates use
+ * smx_lstm_forward_f32's sigmoid and tanh; the gate sums run on the 4-row loop over K = [x | h] (another summation
+ * order than smx_lstm_forward_f32: equal to fp32 rounding).  4, 8 and 16 actors per workgroup give the same bits. */
+struct smx_synth_lstm_rollout {               /* (by tag: no typedef) */
+    smx_synth_rollout_t roll;
+    const smx_lstm_t* lstm;
+    const float* lstm_packed;
+    int32_t hidden, reserved;
+    const float* h0;
+    const float* c0;
+    float* hN;
+    float* cN;
+    float* h_before;
+    float* c_before;
+    float* cell_roll;
+};
+/* shapes smx_synth_lstm_rollout_f32 takes: those of smx_synth_rollout_supported with the actor's input H, H a multiple
+ * of 4 up to 128 */
+int32_t smx_synth_lstm_rollout_supported(int32_t D, int32_t H, int32_t H1, int32_t H2, int32_t A);
+/* floats of the gate pass's packed weights ([4H, D + H] in fragment order + the summed biases); 0 for bad shapes */
+int64_t smx_lstm_rollout_packed_floats(int32_t D, int32_t H);
+/* packed (16-byte aligned, smx_lstm_rollout_packed_floats) <- net; refresh it whenever the weights change */
+int smx_lstm_rollout_pack_f32(const smx_lstm_t* net, float* packed, smx_stream_t stream);
+int smx_synth_lstm_rollout_f32(const struct smx_synth_lstm_rollout* args, smx_stream_t stream);
+
 /* DDPG's acting loop on the device, recorded as n-step transitions straight into the uniform replay's ring: per step and
  * actor a (all actors share the episode clock tau = args->t at the first step)
  *   mu = tanh(MLP(s))                                      DDPGModel.actor (surreal/model/ddpg_net.py:13-95)

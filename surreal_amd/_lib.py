@@ -156,6 +156,13 @@ class SynthRollout(Structure):
                 ('actors_per_workgroup', c_int32)]
 
 
+class SynthLstmRollout(Structure):
+    """struct smx_synth_lstm_rollout"""
+    _fields_ = [('roll', SynthRollout), ('lstm', POINTER(Lstm)), ('lstm_packed', c_void_p), ('hidden', c_int32),
+                ('reserved', c_int32), ('h0', c_void_p), ('c0', c_void_p), ('hN', c_void_p), ('cN', c_void_p),
+                ('h_before', c_void_p), ('c_before', c_void_p), ('cell_roll', c_void_p)]
+
+
 class DdpgRollout(Structure):
     """smx_ddpg_rollout_t"""
     _fields_ = [('net', POINTER(Mlp3)), ('packed', c_void_p), ('n', c_int32), ('D', c_int32), ('A', c_int32),
@@ -343,6 +350,10 @@ _SIGS = {
     'smx_synth_frame_u8': (c_int32, [_P, c_int64, c_int32, c_int32, c_int32, c_int32, c_int32, _P, c_int64, _P]),
     'smx_synth_rollout_supported': (c_int32, [c_int32, c_int32, c_int32, c_int32]),
     'smx_synth_rollout_f32': (c_int32, [POINTER(SynthRollout), _P]),
+    'smx_synth_lstm_rollout_supported': (c_int32, [c_int32] * 5),
+    'smx_lstm_rollout_packed_floats': (c_int64, [c_int32, c_int32]),
+    'smx_lstm_rollout_pack_f32': (c_int32, [POINTER(Lstm), _P, _P]),
+    'smx_synth_lstm_rollout_f32': (c_int32, [POINTER(SynthLstmRollout), _P]),
     'smx_synth_ddpg_rollout_supported': (c_int32, [c_int32, c_int32, c_int32, c_int32]),
     'smx_synth_ddpg_rollout_f32': (c_int32, [POINTER(DdpgRollout), _P]),
     'smx_synth_ddpg_step_f32': (c_int32, [POINTER(DdpgRollout), _P, c_int64, _P]),

@@ -105,13 +105,7 @@ class PPOAgent(Agent):
             n = obs.shape[0]
         A = self.action_dim
         K = self.K
-        if self._batch_noise is None or self._batch_noise.shape[0] != n:
-            if self.agent_mode == 'training':
-                g = torch.Generator().manual_seed(1234 + int(self.agent_id))
-                u = (torch.rand(n, 1, generator=g) * 2 - 1) * self.log_sig_range
-            else:
-                u = torch.zeros(n, 1)
-            self._batch_noise = torch.exp(u).to(self.device)
+        self._ensure_batch_noise(n)
         if self.rnn_config.if_rnn_policy or self.model.if_pixel:
             # one LSTM step for all n actors; `batch_cells_before` is what every actor's
             # onetime_infos would hold for this step (its state BEFORE acting, :133-135)
@@ -160,11 +154,19 @@ class PPOAgent(Agent):
         self.K.mlp3_forward(self.model.actor, xn, ws.h1, ws.h2, out, L.SMX_ACT_TANH)
         return out
 
-    def batch_noise(self, n):
-        """per-actor exploration scale exp(noise_i) [n, 1] (ppo_agent.py:57-61, 139)"""
+    def _ensure_batch_noise(self, n):
         if self._batch_noise is None or self._batch_noise.shape[0] != n:
-            self.act_batch(torch.zeros(n, self.model.actor.D, device=self.device),
-                           eps=torch.zeros(n, self.action_dim, device=self.device))
+            if self.agent_mode == 'training':
+                g = torch.Generator().manual_seed(1234 + int(self.agent_id))
+                u = (torch.rand(n, 1, generator=g) * 2 - 1) * self.log_sig_range
+            else:
+                u = torch.zeros(n, 1)
+            self._batch_noise = torch.exp(u).to(self.device)
+
+    def batch_noise(self, n):
+        """per-actor exploration scale exp(noise_i) [n, 1] (ppo_agent.py:57-61, 139) -- without acting: a recurrent
+        agent's cells stay as they are"""
+        self._ensure_batch_noise(n)
         return self._batch_noise
 
     def module_dict(self):

@@ -11,6 +11,9 @@
 //                               [actors, T + 1, .]).  4 and 8 actors per workgroup run rollout_kernel<RG> on the 4-row
 //                               v_mfma_f32_4x4x1 loop of smx_rows4_mma.inc.h, 16 run rollout16_kernel on the 16x16x4 loop
 //                               of smx_epoch_mma.inc.h.
+//   smx_synth_lstm_rollout_f32  PPO with the one-layer LSTM stem in front of the policy MLP (ppo_net.py:317-354, the
+//                               reference's default policy): lstm_rollout_kernel<RG>, the PPO kernel body with the gate
+//                               and cell passes first in every step, on the 4-row loop at every block size.
 //   smx_synth_ddpg_rollout_f32  DDPG (surreal/agent/ddpg_agent.py:155-184 act: actor -> clip -> + exploration noise ->
 //                               clip; surreal/agent/action_noise.py; the n-step transitions of
 //                               surreal/env/exp_sender_wrapper.py:72-112 ExpSenderWrapperSSARNStepBootstrap, which run on
@@ -35,6 +38,7 @@ namespace {
 #include "smx_epoch_mma.inc.h"
 #include "smx_rows4_mma.inc.h"
 #include "smx_synth_env.inc.h"
+#include "smx_lstm_act.inc.h"
 
 // Phase timestamps exist only in a build with -DSMX_ROLLOUT_TIMING (scripts/bench_rollout.py); the product build has none.
 #ifdef SMX_ROLLOUT_TIMING
@@ -74,6 +78,15 @@ struct RollArgs : RollBase {
     float zeps;
     int R, slot0;                               // R = rows per actor in the rollout tables
     float *obs_roll, *act_roll, *rew_roll, *done_roll, *pd_roll, *obs_last;
+};
+
+// the LSTM stem in front of the PPO actor (lstm_rollout_kernel)
+struct LArgs : RollArgs {
+    const float *Pg, *bg;                       // the gate pass: [W_ih | 0 | W_hh] packed over K = Dp + H, b_ih + b_hh
+    int H, Hl, Dp, off_g, ldg, off_c;           // H: units (padded to 4), Hl: logical units; Dp = D rounded up to 4
+    const float *h0, *c0;                       // [n, Hl] or null (zeros)
+    float *hN, *cN, *h_before, *c_before;       // [n, Hl]: after the last step, before it (h_before / c_before nullable)
+    float* cell_roll;                           // [n, R, 2, Hl] the state before every step, or null
 };
 
 struct DArgs : RollBase {
@@ -217,22 +230,34 @@ struct EnvLanes {
     }
 };
 
+// A layer in front of the actor's (GATE: the LSTM gate pass): packed weights W, bias, H outputs over K inputs read from
+// the x tile, output tile at off_out (row stride ldo), no activation
+struct PreLayer {
+    const float* W;
+    const float* bias;
+    int H, K, off_out, ldo;
+};
+
 // The first nl actor layers of the block's 4 RG rows on the 4-row loop (smx_rows4_mma.inc.h), NT feature tiles a wave
 // per pass: bias, then ReLU on the hidden layers and act_f(., out_act) on the output layer.  The layer sums of a row do
 // not depend on RG or NT (k ascending within each kq class, then the classes meet).  after(l) follows layer l's barrier.
-template <int RG, int NT, typename After>
-__device__ __forceinline__ void layers4(const RollBase& G, float* sm, int nl, int out_act, int wv, int lane, After after) {
+// Layer 0 reads K0 inputs from column in0 on of the x tile (a plain MLP: the observation, in0 = 0, K0 = D).  GATE: layer
+// -1 = `pre` runs first, from column 0 of the x tile (after(-1) then follows its barrier).
+template <int RG, int NT, bool GATE = false, typename After>
+__device__ __forceinline__ void layers4(const RollBase& G, float* sm, int nl, int out_act, int wv, int lane, After after,
+                                        int in0, int K0, const PreLayer& pre = PreLayer{}) {
     const int fm = lane & 15, kq = lane >> 4;
 #pragma unroll 1
-    for (int l = 0; l < nl; ++l) {
-        const float* Wp = l == 0 ? G.P1 : (l == 1 ? G.P2 : G.P3);
-        const float* bias = l == 0 ? G.b1 : (l == 1 ? G.b2 : G.b3);
-        const int H = l == 0 ? G.H1 : (l == 1 ? G.H2 : G.A);
-        const int K = l == 0 ? G.D : (l == 1 ? G.H1 : G.H2);
-        const float* in_lds = sm + (l == 0 ? 0 : (l == 1 ? G.off_h1 : G.off_h2));
-        const int ldi = l == 0 ? G.ldx : (l == 1 ? G.ldh1 : G.ldh2);
-        float* out_lds = sm + (l == 0 ? G.off_h1 : (l == 1 ? G.off_h2 : G.off_out));
-        const int ldo = l == 0 ? G.ldh1 : (l == 1 ? G.ldh2 : RLDO);
+    for (int l = GATE ? -1 : 0; l < nl; ++l) {
+        const bool pl = GATE && l < 0;
+        const float* Wp = pl ? pre.W : (l == 0 ? G.P1 : (l == 1 ? G.P2 : G.P3));
+        const float* bias = pl ? pre.bias : (l == 0 ? G.b1 : (l == 1 ? G.b2 : G.b3));
+        const int H = pl ? pre.H : (l == 0 ? G.H1 : (l == 1 ? G.H2 : G.A));
+        const int K = pl ? pre.K : (l == 0 ? K0 : (l == 1 ? G.H1 : G.H2));
+        const float* in_lds = sm + (pl ? 0 : (l == 0 ? in0 : (l == 1 ? G.off_h1 : G.off_h2)));
+        const int ldi = pl ? G.ldx : (l == 0 ? G.ldx : (l == 1 ? G.ldh1 : G.ldh2));
+        float* out_lds = sm + (pl ? pre.off_out : (l == 0 ? G.off_h1 : (l == 1 ? G.off_h2 : G.off_out)));
+        const int ldo = pl ? pre.ldo : (l == 0 ? G.ldh1 : (l == 1 ? G.ldh2 : RLDO));
         const int tiles = (H + 15) >> 4;
         const int C2 = pack_chunks(K);
         const rsrc_t rw = make_rsrc(Wp, (unsigned)tiles * (unsigned)C2 * 2048u);
@@ -263,7 +288,7 @@ __device__ __forceinline__ void layers4(const RollBase& G, float* sm, int nl, in
                         float z = meet_rows(acc[g][r]);
                         z += bs[g];
                         if (l == 2) z = act_f(z, out_act);
-                        else z = (z < 0.f) ? 0.f : z;
+                        else if (!pl) z = (z < 0.f) ? 0.f : z;
                         out_lds[(4 * r + kq) * ldo + f] = (f < H) ? z : 0.f;
                     }
                 }
@@ -279,8 +304,13 @@ __device__ __forceinline__ void layers4(const RollBase& G, float* sm, int nl, in
 // RG row groups of four actors per workgroup (round 6; smx_rows4_mma.inc.h).  1024 actors: RG = 1 -> 256 workgroups, one per
 // CU.  The host picks the smallest RG whose grid fits the chip once (more actors per workgroup = fewer passes over the
 // packed weights per actor; fewer = more CUs at work).
-template <int RG>
-__global__ __launch_bounds__(RNTH) void rollout_kernel(RollArgs G) {
+// LSTM (lstm_rollout_kernel): every step first runs the stem on the same loop -- the gate pass, ONE 4-row layer over K =
+// Dp + H reading the x tile's row [x | 0 | h] against [W_ih | 0 | W_hh], gates to LDS; then the cell pass: thread q owns
+// the (row, unit) pairs q + RNTH i (at most RG of them for H <= 128) and keeps their cells in LDS slots no other thread
+// touches (registers are short at 16 actors); it writes h' back into the tile's h columns, where the actor's first
+// layer reads it.
+template <int RG, int NT, bool LSTM, bool COLS, typename Args>
+__device__ __forceinline__ void ppo_rollout(Args G) {
     constexpr int RB = 4 * RG;                       // actors per workgroup
     extern __shared__ float sm[];
     const int tid = threadIdx.x, lane = tid & 63;
@@ -293,12 +323,24 @@ __global__ __launch_bounds__(RNTH) void rollout_kernel(RollArgs G) {
     const int ldh2 = G.ldh2;
 
     clear_tiles(G, sm, tid, G.zsum, G.zsumsq, G.zcount, G.zeps);
-    EnvLanes<RB> E(G, sm, G.zsum ? sm + G.off_z : nullptr, wv, lane);
+    EnvLanes<RB, COLS> E(G, sm, G.zsum ? sm + G.off_z : nullptr, wv, lane);
     SMX_LDS_BARRIER();
     E.start();
     SMX_LDS_BARRIER();
     const long row0 = E.row0;
     const int nrows = E.nrows;
+    if constexpr (LSTM) {
+        float* cst = sm + G.off_c;
+#pragma unroll 1
+        for (int q = tid; q < RB * G.H; q += RNTH) {
+            const int r = q / G.H, j = q - r * G.H;
+            const bool rec = r < nrows && j < G.Hl;
+            const long o = (row0 + r) * G.Hl + j;
+            cst[q] = (rec && G.c0) ? G.c0[o] : 0.f;
+            if (rec && G.h0) sm[r * G.ldx + G.Dp + j] = G.h0[o];
+        }
+        SMX_LDS_BARRIER();
+    }
 
     // ---- the output layer (K = H2, <= 32 outputs) is a latency chain if two waves walk its chunks alone (measured: 5.0 k
     // cycles of a 36 k-cycle step for 2 tiles x 8 chunks).  Its K is split over the EIGHT waves instead: wave w owns chunk w
@@ -307,8 +349,10 @@ __global__ __launch_bounds__(RNTH) void rollout_kernel(RollArgs G) {
     // chunks (H2 > 256) or more than 2 tiles take the generic loop.
     const int tiles3 = (A + 15) >> 4, C3 = pack_chunks(G.H2);
     const bool l3res = C3 <= RNWV && tiles3 <= 2;
+    // (16-actor blocks: the register budget has no room for them -- re-read from L2 every step, the same words)
+    constexpr bool W3REG = RG < 4;
     float4 w3a[2], w3b[2];
-    {
+    auto load_w3 = [&]() {
         const rsrc_t rw3 = make_rsrc(G.P3, (unsigned)tiles3 * (unsigned)C3 * 2048u);
 #pragma unroll
         for (int g = 0; g < 2; ++g) {
@@ -317,7 +361,8 @@ __global__ __launch_bounds__(RNTH) void rollout_kernel(RollArgs G) {
             w3a[g] = ld16(rw3, o);
             w3b[g] = ld16(rw3, o == OOB ? OOB : o + 1024u);
         }
-    }
+    };
+    if (W3REG) load_w3();
     float* red3 = sm + G.off_red3;               // [RNWV][RB][32]: the waves' partial output sums
     // the sampling head's per-pair constants (the same expressions, formed once instead of every step)
     const int hr = tid / A, hj = tid - hr * A;            // RB x A <= 512 pairs
@@ -335,34 +380,82 @@ __global__ __launch_bounds__(RNTH) void rollout_kernel(RollArgs G) {
         float ev = 0.f;
         if (G.eps && hr < nrows) ev = G.eps[((size_t)step * G.n + row0 + hr) * A + hj];
         // ---- the three layers (the output layer below when its weights are register-resident) -------------------
-        layers4<RG, 3>(G, sm, l3res ? 2 : 3, G.out_act, wv, lane, [&](int l) { RSTAMP(1 + l); });
+        if constexpr (LSTM) {
+            const PreLayer gate{G.Pg, G.bg, 4 * G.H, G.Dp + G.H, G.off_g, G.ldg};
+            layers4<RG, NT, true>(G, sm, l3res ? 2 : 3, G.out_act, wv, lane, [&](int l) {
+                if (l >= 0) { RSTAMP(1 + l); return; }
+                RSTAMP(6);
+                // ---- the cell pass (smx_lstm.hip's gate functions and update order); records the state BEFORE the step
+                const float* gs = sm + G.off_g;
+                const int H = G.H, ldx = G.ldx, ldg = G.ldg, Hl = G.Hl;
+                float* cst = sm + G.off_c;
+#pragma unroll 1
+                for (int q = tid; q < RB * H; q += RNTH) {
+                    const int r = q / H, j = q - r * H;
+                    {
+                        const float* g = gs + r * ldg + j;
+                        const float gi = fast_sigm(g[0]), gf = fast_sigm(g[H]), gg = fast_tanh(g[2 * H]),
+                                    go = fast_sigm(g[3 * H]);
+                        const float c0 = cst[q];
+                        float c = gf * c0 + gi * gg;
+                        float h = go * fast_tanh(c);
+                        if (j >= Hl) c = h = 0.f;            // (a padded unit: exactly zero whatever its weights)
+                        float* hp = sm + r * ldx + G.Dp + j;
+                        if (r < nrows && j < Hl) {
+                            const long a = row0 + r;
+                            if (G.cell_roll) {
+                                float* cp = G.cell_roll + ((a * R + slot) * 2) * Hl + j;
+                                __builtin_nontemporal_store(*hp, cp);
+                                __builtin_nontemporal_store(c0, cp + Hl);
+                            }
+                            if (last_step && G.h_before) {
+                                G.h_before[a * Hl + j] = *hp;
+                                G.c_before[a * Hl + j] = c0;
+                            }
+                        }
+                        cst[q] = c;
+                        *hp = h;
+                    }
+                }
+                SMX_LDS_BARRIER();
+                RSTAMP(7);
+            }, G.Dp, G.H, gate);
+        } else {
+            layers4<RG, NT>(G, sm, l3res ? 2 : 3, G.out_act, wv, lane, [&](int l) { RSTAMP(1 + l); }, 0, G.D);
+        }
         if (l3res) {
+            if (!W3REG) load_w3();
             // wave w: chunk w of the output layer against h2 (zero weights past the last chunk: a zero partial sum)
-            const float* bp = h2s + (lane & 3) * ldh2 + 8 * kq + 32 * (wv < C3 ? wv : 0);
-            f32x4 a3[2][RG];
+            // (RC row groups at a time: the register budget of 16-actor blocks; a row group's sums do not depend on it)
+            constexpr int RC = RG < 4 ? RG : 1;
+#pragma unroll 1
+            for (int rg0 = 0; rg0 < RG; rg0 += RC) {
+            const float* bp = h2s + (lane & 3) * ldh2 + 8 * kq + 32 * (wv < C3 ? wv : 0) + 4 * rg0 * ldh2;
+            f32x4 a3[2][RC];
 #pragma unroll
             for (int g = 0; g < 2; ++g)
 #pragma unroll
-                for (int r = 0; r < RG; ++r) a3[g][r] = (f32x4){0.f, 0.f, 0.f, 0.f};
-            float4 x0[RG], x1[RG];
+                for (int r = 0; r < RC; ++r) a3[g][r] = (f32x4){0.f, 0.f, 0.f, 0.f};
+            float4 x0[RC], x1[RC];
 #pragma unroll
-            for (int r = 0; r < RG; ++r) {
+            for (int r = 0; r < RC; ++r) {
                 x0[r] = *(const float4*)(bp + 4 * r * ldh2);
                 x1[r] = *(const float4*)(bp + 4 * r * ldh2 + 4);
             }
 #define SMX_L3(X, W, E)                                                      \
             _Pragma("unroll") for (int g = 0; g < 2; ++g)                    \
-                _Pragma("unroll") for (int r = 0; r < RG; ++r) a3[g][r] = MFMA4(X[r].E, W[g].E, a3[g][r]);
+                _Pragma("unroll") for (int r = 0; r < RC; ++r) a3[g][r] = MFMA4(X[r].E, W[g].E, a3[g][r]);
             SMX_L3(x0, w3a, x) SMX_L3(x0, w3a, y) SMX_L3(x0, w3a, z) SMX_L3(x0, w3a, w)
             SMX_L3(x1, w3b, x) SMX_L3(x1, w3b, y) SMX_L3(x1, w3b, z) SMX_L3(x1, w3b, w)
 #undef SMX_L3
 #pragma unroll
             for (int g = 0; g < 2; ++g)
 #pragma unroll
-                for (int r = 0; r < RG; ++r) {
+                for (int r = 0; r < RC; ++r) {
                     const float z = meet_rows(a3[g][r]);
-                    red3[(wv * RB + 4 * r + kq) * 32 + 16 * g + fm] = z;
+                    red3[(wv * RB + 4 * (rg0 + r) + kq) * 32 + 16 * g + fm] = z;
                 }
+            }
             SMX_LDS_BARRIER();
             RSTAMP(3);
         }
@@ -419,6 +512,30 @@ __global__ __launch_bounds__(RNTH) void rollout_kernel(RollArgs G) {
     }
     RWALL(14); RCYC(15);
     E.store();
+    if constexpr (LSTM) {
+        const float* cst = sm + G.off_c;
+#pragma unroll 1
+        for (int q = tid; q < RB * G.H; q += RNTH) {
+            const int r = q / G.H, j = q - r * G.H;
+            if (r < nrows && j < G.Hl) {             // (h, c: the thread's own last writes to the tiles)
+                G.hN[(row0 + r) * G.Hl + j] = sm[r * G.ldx + G.Dp + j];
+                G.cN[(row0 + r) * G.Hl + j] = cst[q];
+            }
+        }
+    }
+}
+
+template <int RG>
+__global__ __launch_bounds__(RNTH) void rollout_kernel(RollArgs G) {
+    ppo_rollout<RG, 3, false, true>(G);
+}
+
+// 4, 8 and 16 actors per workgroup, all on the 4-row loop; every block size gives the same bits.  16 (the register
+// budget): two feature tiles a wave per pass, the environment lanes' per-element constants formed every step, the split
+// output layer's weights re-read every step and its row groups taken one at a time
+template <int RG>
+__global__ __launch_bounds__(RNTH) void lstm_rollout_kernel(LArgs G) {
+    ppo_rollout<RG, RG == 4 ? 2 : 3, true, RG < 4>(G);
 }
 
 constexpr int RTG = 3;            // feature tiles a wave carries per pass (register budget of two waves per SIMD)
@@ -622,7 +739,7 @@ __global__ __launch_bounds__(RNTH) void ddpg_rollout_kernel(DArgs G) {
         float ev = 0.f;                              // this step's draw, requested before the layers
         if (G.eps && head) ev = G.eps[((size_t)step * G.n + ha) * A + hj];
         // ---- the actor's three layers (ReLU, ReLU, tanh) --------------------------------------------------------
-        layers4<RG, NT>(G, sm, 3, SMX_ACT_TANH, wv, lane, [](int) {});
+        layers4<RG, NT>(G, sm, 3, SMX_ACT_TANH, wv, lane, [](int) {}, 0, G.D);
         const bool emit = tau >= N - 1;
         const int slot = tau % N, jslot = (tau + 1) % N;   // (transition j = tau - N + 1 sits in slot j % N)
         const bool done = (tau + 1 >= G.episode_len);
@@ -727,10 +844,12 @@ inline int rr64(int v) { return (v + 63) & ~63; }
 // Row strides on the 4-row loop = 16 mod 64 words: the rows of a group (a word's lanes: row l & 3, k offset 8 (l >> 4)) and
 // the epilogue's one-word stores (row kq, feature fm) fall on distinct banks of the 64.  A tile holds pack_chunks(K) * 32
 // + 8 columns at least (the loop's last prefetch reads one chunk it does not use).  On the 16x16x4 loop (mma16) a word's
-// lanes are row l & 15: strides of 4 mod 64 spread them.
-int carve(RollBase& G, int RB, bool mma16, bool split_out, bool ztables) {
-    if (mma16) { G.ldx = rr64(G.D) + 4; G.ldh1 = rr64(G.H1) + 4; G.ldh2 = rr64(G.H2) + 4; }
-    else { G.ldx = rr64(G.D + 40) + 16; G.ldh1 = rr64(G.H1 + 40) + 16; G.ldh2 = rr64(G.H2 + 40) + 16; }
+// lanes are row l & 15: strides of 4 mod 64 spread them.  xcols: the columns of the x tile its readers take as K (D;
+// the LSTM rollout's [x | 0 | h] row: Dp + rr64(H), so that the actor's first layer, reading from column Dp, stays
+// inside the row too).
+int carve(RollBase& G, int RB, bool mma16, bool split_out, bool ztables, int xcols) {
+    if (mma16) { G.ldx = rr64(xcols) + 4; G.ldh1 = rr64(G.H1) + 4; G.ldh2 = rr64(G.H2) + 4; }
+    else { G.ldx = rr64(xcols + 40) + 16; G.ldh1 = rr64(G.H1 + 40) + 16; G.ldh2 = rr64(G.H2 + 40) + 16; }
     G.off_h1 = RB * G.ldx;
     G.off_h2 = G.off_h1 + RB * G.ldh1;
     G.off_out = G.off_h2 + RB * G.ldh2;
@@ -749,7 +868,50 @@ int32_t supported(int32_t D, int32_t H1, int32_t H2, int32_t A, bool mma16, bool
     RollBase G;
     memset(&G, 0, sizeof(G));
     G.D = D; G.H1 = H1; G.H2 = H2; G.A = A;
-    return carve(G, 16, mma16, split_out, ztables) <= ROLL_MAX_LDS;
+    return carve(G, 16, mma16, split_out, ztables, D) <= ROLL_MAX_LDS;
+}
+
+// ---- LSTM stem ---------------------------------------------------------------------------------------------------
+
+__host__ __device__ inline int lstm_dp(int D) { return (D + 3) & ~3; }
+
+// The LSTM rollout's LDS: carve()'s layout with the x tile widened to [x | 0 | h], then the gate tile [RB][ldg]
+// (rewritten whole by every gate pass: not cleared) and the cells [RB H] (pair q = r H + j: written and read by thread
+// q mod RNTH alone)
+int carve_lstm(LArgs& G, int RB) {
+    G.Dp = lstm_dp(G.D);
+    carve(G, RB, /*mma16=*/false, /*split_out=*/true, /*ztables=*/true, G.Dp + rr64(G.H));
+    G.off_g = (G.off_kmod + G.D + 3) & ~3;
+    G.ldg = rr64(4 * G.H) + 16;
+    G.off_c = G.off_g + RB * G.ldg;
+    return (G.off_c + RB * G.H) * (int)sizeof(float);
+}
+
+// the gate pass's packed weights: [4H, Dp + H] = [W_ih | 0 | W_hh] in fragment order (smx_epoch_pack.inc.h), then
+// b_ih + b_hh [4H]
+long lstm_pack_floats(int D, int H) { return pack_words(4 * H, lstm_dp(D) + H) * 4 + 4 * (long)H; }
+
+__global__ void lstm_pack_kernel(smx_lstm_t net, float* packed) {
+    const int D = net.D, H = net.H, Dp = lstm_dp(D), K = Dp + H, C = pack_chunks(K);
+    const long nw = pack_words(4 * H, K) * 4;
+    for (long idx = (long)blockIdx.x * blockDim.x + threadIdx.x; idx < nw + 4 * H; idx += (long)gridDim.x * blockDim.x) {
+        if (idx >= nw) {
+            const int m = (int)(idx - nw);
+            packed[idx] = net.b_ih[m] + net.b_hh[m];
+            continue;
+        }
+        // float idx = (((t C + c) 2 + h) 64 + 16 kq + i) 4 + e holds X[16 t + i][32 c + 8 kq + 4 h + e] (pack_pos)
+        const int e = (int)(idx & 3), i = (int)((idx >> 2) & 15), kq = (int)((idx >> 6) & 3), h = (int)((idx >> 8) & 1);
+        const long tc = idx >> 9;
+        const int c = (int)(tc % C), t = (int)(tc / C);
+        const int m = 16 * t + i, k = 32 * c + 8 * kq + 4 * h + e;
+        float v = 0.f;
+        if (m < 4 * H) {
+            if (k < D) v = net.W_ih[(long)m * D + k];
+            else if (k >= Dp && k < K) v = net.W_hh[(long)m * H + (k - Dp)];
+        }
+        packed[idx] = v;
+    }
 }
 
 // actors per workgroup: `forced` (4 | 8 | 16), or for 0 the smallest of 4 and 8 whose grid fits the chip once, else 16
@@ -841,10 +1003,77 @@ extern "C" int smx_synth_rollout_f32(const smx_synth_rollout_t* a, smx_stream_t 
     G.obs_roll = a->obs_roll; G.act_roll = a->act_roll; G.rew_roll = a->rew_roll; G.done_roll = a->done_roll;
     G.pd_roll = a->pd_roll; G.obs_last = a->obs_last;
     const int rb = pick_block(a->actors_per_workgroup, a->n);
-    const int lds = carve(G, rb, /*mma16=*/rb == 16, /*split_out=*/true, /*ztables=*/true);
+    const int lds = carve(G, rb, /*mma16=*/rb == 16, /*split_out=*/true, /*ztables=*/true, G.D);
     if (rb == 4) return launch<rollout_kernel<1>>(G, rb, lds, stream);
     if (rb == 8) return launch<rollout_kernel<2>>(G, rb, lds, stream);
     return launch<rollout16_kernel>(G, rb, lds, stream);
+}
+
+extern "C" int32_t smx_synth_lstm_rollout_supported(int32_t D, int32_t H, int32_t H1, int32_t H2, int32_t A) {
+    if (!(H > 0 && H % 4 == 0 && H <= 128)) return 0;
+    if (!supported(D, H1, H2, A, /*mma16=*/false, /*split_out=*/true, /*ztables=*/true)) return 0;
+    LArgs G;
+    memset(&G, 0, sizeof(G));
+    G.D = D; G.H = H; G.H1 = H1; G.H2 = H2; G.A = A;
+    return carve_lstm(G, 16) <= ROLL_MAX_LDS;
+}
+
+extern "C" int64_t smx_lstm_rollout_packed_floats(int32_t D, int32_t H) {
+    if (D <= 0 || H <= 0 || H % 4) return 0;
+    return lstm_pack_floats(D, H);
+}
+
+extern "C" int smx_lstm_rollout_pack_f32(const smx_lstm_t* net, float* packed, smx_stream_t stream) {
+    SMX_REQUIRE(net && net->W_ih && net->W_hh && net->b_ih && net->b_hh && packed, SMX_E_NULL);
+    SMX_REQUIRE(net->D > 0 && net->H > 0 && net->H % 4 == 0, SMX_E_SHAPE);
+    const long total = lstm_pack_floats(net->D, net->H);
+    const int blocks = (int)((total + 255) / 256 < 1024 ? (total + 255) / 256 : 1024);
+    hipLaunchKernelGGL(lstm_pack_kernel, dim3(blocks), dim3(256), 0, smx_s(stream), *net, packed);
+    SMX_LAUNCH_CHECK();
+    return SMX_OK;
+}
+
+extern "C" int smx_synth_lstm_rollout_f32(const smx_synth_lstm_rollout* args, smx_stream_t stream) {
+    SMX_REQUIRE(args && args->lstm && args->lstm_packed && args->hN && args->cN, SMX_E_NULL);
+    const smx_synth_rollout_t* a = &args->roll;
+    SMX_REQUIRE(a->net && a->packed && a->log_var && a->state && a->init_state, SMX_E_NULL);
+    SMX_REQUIRE((args->h_before == nullptr) == (args->c_before == nullptr), SMX_E_NULL);
+    SMX_REQUIRE((args->h0 == nullptr) == (args->c0 == nullptr), SMX_E_NULL);
+    const smx_mlp3_t& n = *a->net;
+    const smx_lstm_t& l = *args->lstm;
+    SMX_REQUIRE(n.D == l.H && args->hidden > 0 && args->hidden <= l.H && l.H - args->hidden < 4, SMX_E_SHAPE);
+    SMX_REQUIRE(smx_synth_lstm_rollout_supported(l.D, l.H, n.H1, n.H2, n.OUT), SMX_E_UNSUPPORTED);
+    SMX_REQUIRE(a->n > 0 && a->steps > 0 && a->episode_len > 0 && a->rows_per_actor > 0, SMX_E_SHAPE);
+    SMX_REQUIRE(a->actors_per_workgroup == 0 || a->actors_per_workgroup == 4 || a->actors_per_workgroup == 8 ||
+                a->actors_per_workgroup == 16, SMX_E_SHAPE);
+    const bool records = a->obs_roll || a->act_roll || a->rew_roll || a->done_roll || a->pd_roll || args->cell_roll;
+    SMX_REQUIRE(a->slot >= 0 && (!records || a->slot + a->steps <= a->rows_per_actor), SMX_E_SHAPE);
+    SMX_REQUIRE(((uintptr_t)a->packed & 15) == 0 && ((uintptr_t)n.b1 & 3) == 0, SMX_E_ALIGN);
+    SMX_REQUIRE(((uintptr_t)args->lstm_packed & 15) == 0, SMX_E_ALIGN);
+    SMX_REQUIRE((a->zsum == nullptr) == (a->zsumsq == nullptr) && (a->zsum == nullptr) == (a->zcount == nullptr), SMX_E_NULL);
+    LArgs G;
+    memset(&G, 0, sizeof(G));
+    G.P1 = a->packed;
+    G.P2 = a->packed + 4 * pack_off(n.D, n.H1, n.H2, n.OUT, 1);
+    G.P3 = a->packed + 4 * pack_off(n.D, n.H1, n.H2, n.OUT, 2);
+    G.b1 = n.b1; G.b2 = n.b2; G.b3 = n.b3;
+    G.D = l.D; G.H1 = n.H1; G.H2 = n.H2; G.A = n.OUT; G.out_act = a->out_act;
+    G.log_var = a->log_var; G.noise_scale = a->noise_scale; G.eps = a->eps;
+    G.zsum = a->zsum; G.zsumsq = a->zsumsq; G.zcount = a->zcount; G.zeps = a->zeps;
+    G.state = a->state; G.init_state = a->init_state;
+    G.n = a->n; G.t0 = a->t; G.episode_len = a->episode_len; G.steps = a->steps; G.R = a->rows_per_actor; G.slot0 = a->slot;
+    G.obs_roll = a->obs_roll; G.act_roll = a->act_roll; G.rew_roll = a->rew_roll; G.done_roll = a->done_roll;
+    G.pd_roll = a->pd_roll; G.obs_last = a->obs_last;
+    G.H = l.H; G.Hl = args->hidden;
+    G.Pg = args->lstm_packed;
+    G.bg = args->lstm_packed + pack_words(4 * l.H, lstm_dp(l.D) + l.H) * 4;
+    G.h0 = args->h0; G.c0 = args->c0; G.hN = args->hN; G.cN = args->cN;
+    G.h_before = args->h_before; G.c_before = args->c_before; G.cell_roll = args->cell_roll;
+    const int rb = pick_block(a->actors_per_workgroup, a->n);
+    const int lds = carve_lstm(G, rb);
+    if (rb == 4) return launch<lstm_rollout_kernel<1>>(G, rb, lds, stream);
+    if (rb == 8) return launch<lstm_rollout_kernel<2>>(G, rb, lds, stream);
+    return launch<lstm_rollout_kernel<4>>(G, rb, lds, stream);
 }
 
 extern "C" int32_t smx_synth_ddpg_rollout_supported(int32_t D, int32_t H1, int32_t H2, int32_t A) {
@@ -869,7 +1098,7 @@ extern "C" int smx_synth_ddpg_rollout_f32(const smx_ddpg_rollout_t* a, smx_strea
     G.P3 = a->packed + 4 * pack_off(net.D, net.H1, net.H2, net.OUT, 2);
     G.b1 = net.b1; G.b2 = net.b2; G.b3 = net.b3; G.H1 = net.H1; G.H2 = net.H2;
     const int rb = pick_block(a->actors_per_workgroup, a->n);
-    const int lds = carve(G, rb, /*mma16=*/false, /*split_out=*/false, /*ztables=*/false);
+    const int lds = carve(G, rb, /*mma16=*/false, /*split_out=*/false, /*ztables=*/false, G.D);
     if (rb == 4) return launch<ddpg_rollout_kernel<1, 3>>(G, rb, lds, stream);
     if (rb == 8) return launch<ddpg_rollout_kernel<2, 3>>(G, rb, lds, stream);
     return launch<ddpg_rollout_kernel<4, 2>>(G, rb, lds, stream);

@@ -165,7 +165,8 @@ class SyntheticVecEnv(object):
         return self.state
 
     def rollout(self, agent, eps=None, actors_per_workgroup=0):
-        """A whole recorded rollout (start_rollout(T) first) under `agent`'s plain-MLP policy: ONE launch
+        """A whole recorded rollout (start_rollout(T) first) under `agent`'s plain-MLP policy (an LSTM-stem one:
+        _rollout_lstm where the kernel takes it, else _rollout_stem): ONE launch
         (smx_synth_rollout_f32: a workgroup owns 4, 8 or 16 actors through all T steps) where the shapes allow it, else
         THREE launches per environment step (the two hidden layers, then one launch that forms the policy mean,
         samples the action, steps every actor, records the transition and z-filters the next observation).
@@ -180,6 +181,8 @@ class SyntheticVecEnv(object):
         if eps is None and not deterministic:
             eps = torch.randn(T, n, self.A, device=self.device)
         if agent.rnn_config.if_rnn_policy or agent.model.if_pixel:
+            if self._lstm_persistent(agent):
+                return self._rollout_lstm(agent, None if deterministic else eps, actors_per_workgroup)
             return self._rollout_stem(agent, None if deterministic else eps)
         noise = agent.batch_noise(n).view(-1)
         zf = agent.model.z_filter if agent.use_z_filter else None
@@ -230,9 +233,51 @@ class SyntheticVecEnv(object):
             self.slot += 1
             self.t = 0 if self.t + 1 >= self.episode_len else self.t + 1
 
+    def _lstm_persistent(self, agent):
+        """an LSTM-stem policy the one-launch kernel runs: one layer, low-dimensional observations, shapes it takes,
+        a kernels object that has the entry point (else _rollout_stem)"""
+        return (self.persistent and self.pixel is None and agent.rnn_config.if_rnn_policy and not agent.model.if_pixel
+                and getattr(self.K, 'synth_lstm_rollout', None) is not None
+                and self.K.synth_lstm_rollout_supported(agent.model))
+
+    def _lstm_launch(self, agent, eps, steps, slot, rolls, actors_per_workgroup):
+        """the LSTM rollout launch from the zero state (a rollout starts at an episode boundary, as in _rollout_stem);
+        leaves the agent's batch cells where act_batch would have: _batch_cells the final (h, c), batch_cells_before the
+        state before the last step, each (1, n, Hl)"""
+        K, n, m = self.K, self.n, agent.model
+        Hl = m.rnn_hidden_logical
+        if getattr(self, '_pk', None) is None or self._pk.numel() != K.epoch_packed_numel(m.actor):
+            self._pk = torch.zeros(K.epoch_packed_numel(m.actor), device=self.device)
+        if getattr(self, '_lpk', None) is None or self._lpk.numel() != K.lstm_rollout_packed_numel(m.rnn):
+            self._lpk = torch.zeros(K.lstm_rollout_packed_numel(m.rnn), device=self.device)
+        K.epoch_pack([(m.actor, self._pk)])          # (the agent's parameters only change between rollouts)
+        K.lstm_rollout_pack(m.rnn, self._lpk)
+        f = lambda: torch.empty(1, n, Hl, device=self.device)  # noqa: E731
+        hN, cN, hB, cB = f(), f(), f(), f()
+        K.synth_lstm_rollout(m, self._pk, self._lpk, self.state, self.init_state, agent.batch_noise(n).view(-1),
+                             eps if eps is None else eps.contiguous(), self.t, self.episode_len, steps, slot, rolls,
+                             m.z_filter if agent.use_z_filter else None, hN, cN, h_before=hB, c_before=cB,
+                             actors_per_workgroup=actors_per_workgroup)
+        agent._batch_cells = (hN, cN)
+        agent.batch_cells_before = (hB, cB)
+        for _ in range(steps):
+            self.t = 0 if self.t + 1 >= self.episode_len else self.t + 1
+
+    def _rollout_lstm(self, agent, eps, actors_per_workgroup=0):
+        """rollout() for an LSTM-stem policy in ONE launch (smx_synth_lstm_rollout_f32): what _rollout_stem records,
+        the cells every actor held before each step included"""
+        T, n = self.T, self.n
+        if 'cells' not in self.rolls:
+            nl, F = agent.rnn_config.rnn_layer, agent.rnn_config.rnn_hidden
+            self.rolls['cells'] = torch.zeros(n, T + 1, 2, nl, F, device=self.device)
+        self._lstm_launch(agent, eps, T, self.slot, self.rolls, actors_per_workgroup)
+        self.slot += T
+
     def can_rollout_into(self, agent):
-        """rollout_into() needs the one-launch kernel: a plain-MLP policy whose shapes it takes"""
-        return (self.persistent and self.pixel is None and not agent.rnn_config.if_rnn_policy and not agent.model.if_pixel
+        """rollout_into() needs a one-launch kernel: a plain-MLP policy whose shapes it takes, or an LSTM-stem one"""
+        if agent.rnn_config.if_rnn_policy:
+            return self._lstm_persistent(agent)
+        return (self.persistent and self.pixel is None and not agent.model.if_pixel
                 and self.K.synth_rollout_supported(agent.model.actor))
 
     def rollout_into(self, agent, out, eps=None, actors_per_workgroup=0):
@@ -240,7 +285,8 @@ class SyntheticVecEnv(object):
         `out`: obs [n, T, D], obs_next [n, 1, D], actions [n, T, A], rewards / dones [n, T], pds [n, T, 2A]): with
         stride == n_step == T the moving-window rule (exp_sender_wrapper.py:209-228) makes the one window of an actor
         its rollout, so nothing is cut and nothing is copied -- the one-launch kernel writes the fields where the
-        learner will read them.  Starts at an episode boundary (reset() first), like start_rollout().
+        learner will read them.  Starts at an episode boundary (reset() first), like start_rollout().  An LSTM-stem
+        policy (window_shapes(T, agent)) also gets `out['cells']` [n, 2, 1, Hl]: the state at the window's first step.
         actors_per_workgroup: as in rollout()."""
         K, n = self.K, self.n
         T = out['obs'].shape[1]
@@ -249,6 +295,13 @@ class SyntheticVecEnv(object):
         deterministic = agent.agent_mode in ('eval_deterministic', 'eval_deterministic_local')
         if eps is None and not deterministic:
             eps = torch.randn(T, n, self.A, device=self.device)
+        if agent.rnn_config.if_rnn_policy:
+            # the window's onetime_infos: the state at its first step -- the zero state a rollout starts from
+            out['cells'].zero_()
+            rolls = {'obs': out['obs'], 'actions': out['actions'], 'rewards': out['rewards'], 'dones': out['dones'],
+                     'pds': out['pds'], 'obs_last': out['obs_next']}
+            self._lstm_launch(agent, None if deterministic else eps, T, 0, rolls, actors_per_workgroup)
+            return
         actor = agent.model.actor
         if getattr(self, '_pk', None) is None or self._pk.numel() != K.epoch_packed_numel(actor):
             self._pk = torch.zeros(K.epoch_packed_numel(actor), device=self.device)
@@ -388,8 +441,9 @@ class SyntheticVecEnv(object):
             self.slot += 1
             self.t = 0 if self.t + 1 >= self.episode_len else self.t + 1
 
-    def window_shapes(self, n_step):
-        """per-experience shape of every field emit_windows produces (for Replay.reserve_batch)"""
+    def window_shapes(self, n_step, agent=None):
+        """per-experience shape of every field emit_windows produces (for Replay.reserve_batch); with a recurrent
+        `agent` also its onetime_infos, 'cells' (2, rnn_layer, rnn_hidden)"""
         shp = {'obs': (n_step, self.D), 'obs_next': (1, self.D), 'actions': (n_step, self.A),
                'rewards': (n_step,), 'dones': (n_step,)}
         if self.rolls is not None and 'pds' in self.rolls:
@@ -398,6 +452,8 @@ class SyntheticVecEnv(object):
             C, H, Wd = self.pixel
             shp['pixel'] = (n_step, self.frame_stacks * C, H, Wd)
             shp['pixel_next'] = (1, self.frame_stacks * C, H, Wd)
+        if agent is not None and agent.rnn_config.if_rnn_policy:
+            shp['cells'] = (2, agent.rnn_config.rnn_layer, agent.rnn_config.rnn_hidden)
         return shp
 
     def emit_windows(self, n_step, stride, out=None):
@@ -445,7 +501,7 @@ class SyntheticVecEnv(object):
         if 'cells' in r:
             # onetime_infos: the LSTM state at the FIRST step of every window (exp_sender_wrapper.py:236-242)
             cw = r['cells'][0, 0].numel()
-            cells = f(n * W, 1, cw)
+            cells = out['cells'].view(n * W, 1, cw) if 'cells' in out else f(n * W, 1, cw)
             K.window_emit(r['cells'].view(n, T + 1, cw), 0, 1, stride, W, cells)
             out['cells'] = cells.view((n * W,) + tuple(r['cells'].shape[2:]))
         return out

@@ -645,6 +645,57 @@ class HipKernels(object):
         p.actors_per_workgroup = int(actors_per_workgroup)
         L.call('smx_synth_rollout_f32', ctypes.byref(p), self._st())
 
+    def synth_lstm_rollout_supported(self, model):
+        """a PPOModel whose policy smx_synth_lstm_rollout_f32 runs: one LSTM layer on low-dimensional observations,
+        shapes it takes"""
+        if not model.if_rnn or model.rnn_layers != 1 or model.if_pixel:
+            return False
+        a, r = model.actor, model.rnn
+        return a.D == r.H and bool(self.lib.smx_synth_lstm_rollout_supported(r.D, r.H, a.H1, a.H2, a.OUT))
+
+    def lstm_rollout_packed_numel(self, lstm):
+        return int(self.lib.smx_lstm_rollout_packed_floats(lstm.D, lstm.H))
+
+    def lstm_rollout_pack(self, lstm, packed):
+        """the gate pass's packed copy of an LstmParams (smx_lstm_rollout_pack_f32)"""
+        L.call('smx_lstm_rollout_pack_f32', ctypes.byref(lstm.desc), L.ptr(packed), self._st())
+
+    def synth_lstm_rollout(self, model, packed, lstm_packed, state, init_state, noise_scale, eps, t, episode_len, steps,
+                           slot, rolls, zfilter, hN, cN, h0=None, c0=None, h_before=None, c_before=None,
+                           actors_per_workgroup=0):
+        """synth_rollout for a PPOModel with a one-layer LSTM stem, ONE launch (smx_synth_lstm_rollout_f32): packed =
+        epoch_pack of model.actor, lstm_packed = lstm_rollout_pack of model.rnn; rolls may also hold 'cells'
+        [n, R, 2, 1, Hl] (the state before every step); h0 / c0 (None: zeros), hN / cN, h_before / c_before: [n, Hl]
+        contiguous, Hl = model.rnn_hidden_logical"""
+        actor, lstm = model.actor, model.rnn
+        n = state.shape[0]
+        Hl = model.rnn_hidden_logical
+        p = L.SynthLstmRollout()
+        q = p.roll
+        q.net, q.packed, q.out_act, q.n = ctypes.pointer(actor.desc), L.ptr(packed), L.SMX_ACT_TANH, n
+        q.log_var, q.noise_scale, q.eps = L.ptr(model.log_var), L.ptr(noise_scale), L.ptr(eps)
+        if eps is not None:
+            assert eps.is_contiguous() and tuple(eps.shape) == (steps, n, actor.OUT)
+        if zfilter is not None:
+            q.zsum, q.zsumsq, q.zcount = L.ptr(zfilter.running_sum), L.ptr(zfilter.running_sumsq), L.ptr(zfilter.count)
+            q.zeps = float(zfilter.eps)
+        r = rolls or {}
+        q.t, q.episode_len, q.steps, q.slot = int(t), int(episode_len), int(steps), int(slot)
+        q.rows_per_actor = r['obs'].shape[1] if 'obs' in r else (r['cells'].shape[1] if 'cells' in r else 1)
+        q.state, q.init_state = L.ptr(state), L.ptr(init_state)
+        q.obs_roll, q.act_roll = L.ptr(r.get('obs')), L.ptr(r.get('actions'))
+        q.rew_roll, q.done_roll, q.pd_roll = L.ptr(r.get('rewards')), L.ptr(r.get('dones')), L.ptr(r.get('pds'))
+        q.obs_last = L.ptr(r.get('obs_last'))
+        q.actors_per_workgroup = int(actors_per_workgroup)
+        for x in (h0, c0, hN, cN, h_before, c_before):
+            assert x is None or (x.is_contiguous() and x.numel() == n * Hl)
+        if 'cells' in r:
+            assert r['cells'].is_contiguous() and tuple(r['cells'].shape[2:]) == (2, 1, Hl)
+        p.lstm, p.lstm_packed, p.hidden = ctypes.pointer(lstm.desc), L.ptr(lstm_packed), Hl
+        p.h0, p.c0, p.hN, p.cN = L.ptr(h0), L.ptr(c0), L.ptr(hN), L.ptr(cN)
+        p.h_before, p.c_before, p.cell_roll = L.ptr(h_before), L.ptr(c_before), L.ptr(r.get('cells'))
+        L.call('smx_synth_lstm_rollout_f32', ctypes.byref(p), self._st())
+
     def synth_ddpg_rollout_supported(self, net):
         return bool(self.lib.smx_synth_ddpg_rollout_supported(net.D, net.H1, net.H2, net.OUT))
 
