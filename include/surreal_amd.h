@@ -1139,6 +1139,34 @@ int smx_synth_ddpg_rollout_f32(const smx_ddpg_rollout_t* args, smx_stream_t stre
  * the actor's output mu [n, A] (row stride ld_mu) from any forward pass */
 int smx_synth_ddpg_step_f32(const smx_ddpg_rollout_t* args, const float* mu, int64_t ld_mu, smx_stream_t stream);
 
+/* The same step for actors with a camera (the reference's pixel DDPG configurations, ddpg_configs.py:176-228:
+ * FrameStackWrapper in front of a CNN perception): smx_synth_ddpg_step_f32 on args->base (mu [n, A] = the actor's
+ * output on the perception of obs_pixel), and the frames in the same launch.  F = C*H*W bytes per frame, S =
+ * frame_stacks, tau = base.t, L = base.episode_len, Hd = hist_len >= n_step + S, p = hist_pos.
+ *   history:  hist[a, (p - tau + u) mod Hd] holds the raw frame of step u of the current episode, tau - Hd < u <= tau;
+ *   frame(u, s0)[c, y, x] = (37 c + 5 y + 11 x + 3 u + (int)(100 |s0|)) % 256        (smx_synth_frame_u8's rule)
+ *   stacked(u)[i] = frame of step max(u - S + 1 + i, 0), 0 <= i < S                     (stack_sources)
+ *   new = frame(tau + 1, s'_0): s' the next state before any reset (the terminal one when tau + 1 >= L)
+ * This launch writes
+ *   tau + 1 < L:   hist[a, (p + 1) mod Hd] = new;      obs_pixel[a] = stacked(tau + 1)
+ *   tau + 1 >= L:  hist[a, (p + 1) mod Hd] = frame(0, init_state[a, 0]);  obs_pixel[a] = that frame S times
+ *   tau >= n_step - 1, row = (base.cursor + a) % capacity, j = tau - n_step + 1:
+ *                  pixel[row] = stacked(j);  pixel_next[row] = stacked(tau + 1) (its last frame: new)
+ * so the caller's next call passes t = tau + 1 (0 after L) and p = (p + 1) mod Hd.  pixel / pixel_next are uint8
+ * [capacity, S*F], obs_pixel uint8 [n, S*F] (what the actors act on at the next step), hist uint8 [n, Hd, F]; the
+ * frames read (steps tau - n_step - S + 2 .. tau) never share a slot with the one written. */
+struct smx_ddpg_pixel_step {           /* (by tag: no typedef) */
+    smx_ddpg_rollout_t base;           /* steps, net, packed, actors_per_workgroup: ignored */
+    int32_t C, H, W, frame_stacks;
+    int32_t hist_len, hist_pos;
+    uint8_t* hist;
+    uint8_t* pixel;
+    uint8_t* pixel_next;
+    uint8_t* obs_pixel;
+};
+int smx_synth_ddpg_pixel_step(const struct smx_ddpg_pixel_step* args, const float* mu, int64_t ld_mu,
+                              smx_stream_t stream);
+
 /* ---------------------------------------------------------------------------
  * Data-parallel exchange between the learner ranks of one node over IPC-mapped peer buffers (xGMI loads): the
  * collectives N sharded learners need to equal the single reference learner -- the per-epoch

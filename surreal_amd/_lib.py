@@ -175,6 +175,13 @@ class DdpgRollout(Structure):
                 ('cursor', c_int64), ('capacity', c_int64)]
 
 
+class DdpgPixelStep(Structure):
+    """struct smx_ddpg_pixel_step"""
+    _fields_ = [('base', DdpgRollout), ('C', c_int32), ('H', c_int32), ('W', c_int32), ('frame_stacks', c_int32),
+                ('hist_len', c_int32), ('hist_pos', c_int32), ('hist', c_void_p), ('pixel', c_void_p),
+                ('pixel_next', c_void_p), ('obs_pixel', c_void_p)]
+
+
 SMX_DDPG_NOISE_NONE, SMX_DDPG_NOISE_GAUSSIAN, SMX_DDPG_NOISE_OU = 0, 1, 2
 
 
@@ -357,6 +364,7 @@ _SIGS = {
     'smx_synth_ddpg_rollout_supported': (c_int32, [c_int32, c_int32, c_int32, c_int32]),
     'smx_synth_ddpg_rollout_f32': (c_int32, [POINTER(DdpgRollout), _P]),
     'smx_synth_ddpg_step_f32': (c_int32, [POINTER(DdpgRollout), _P, c_int64, _P]),
+    'smx_synth_ddpg_pixel_step': (c_int32, [POINTER(DdpgPixelStep), _P, c_int64, _P]),
     'smx_xchg_bytes': (c_int64, [c_int64, c_int32]),
     'smx_xchg_alloc': (c_int32, [c_int64, c_double, POINTER(c_void_p), POINTER(c_int32), _P]),
     'smx_xchg_free': (c_int32, [_P]),

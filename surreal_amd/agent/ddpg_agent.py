@@ -7,6 +7,7 @@ Parameter-space noise (param_noise.py: 'normal' / 'adaptive_normal') perturbs th
 agent fetches, as ddpg_agent.py:136-153, 174-175.
 """
 import collections
+import collections.abc
 import copy
 import time
 
@@ -114,8 +115,11 @@ class DDPGAgent(Agent):
         return action.clip(-1, 1)
 
     def act_batch(self, obs, sigmas=None, eps=None, generator=None):
-        """obs [n, D] on the device -> actions [n, A]; sigmas [n] per-actor exploration scale
-        (default: this agent's sigma for all rows)"""
+        """obs [n, D] on the device, or for a camera agent the nested observation {'pixel': {'camera0': uint8 [n, C, H,
+        W]}, 'low_dim': {'flat_inputs': [n, D]}} (perception, then the actor) -> actions [n, A]; sigmas [n] per-actor
+        exploration scale (default: this agent's sigma for all rows)"""
+        if isinstance(obs, collections.abc.Mapping):
+            obs = self.model.forward_perception(obs)
         a = self.model.forward_actor(obs).clamp_(-1.0, 1.0)
         if self.agent_mode not in ['eval_deterministic', 'eval_deterministic_local']:
             if eps is None:

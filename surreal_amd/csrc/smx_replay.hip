@@ -275,8 +275,7 @@ __global__ __launch_bounds__(256) void synth_frame_kernel(const float* __restric
     const long a = i / per;
     const int e = (int)(i - a * per);
     const int c = e / (H * Wd), yx = e - c * (H * Wd), y = yx / Wd, x = yx - y * Wd;
-    const int shift = 3 * t + (int)(100.0 * (double)fabsf(s0[a * ld_s0]));
-    dst[a * ld_dst + e] = (unsigned char)((37 * c + 5 * y + 11 * x + shift) % 256);
+    dst[a * ld_dst + e] = synth_frame_px(c, y, x, synth_frame_shift(t, s0[a * ld_s0]));
 }
 
 // one thread per (actor, k); the reward needs the whole action row: lanes k < 1 compute it

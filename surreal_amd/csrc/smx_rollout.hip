@@ -22,6 +22,9 @@
 //   smx_synth_ddpg_step_f32     one DDPG step for all actors given the actor's output mu [n, A] from any forward
 //                               (LayerNorm actors, unsupported shapes; with smx_epoch_forward_f32 the persistent kernel's
 //                               two-launch reference).
+//   smx_synth_ddpg_pixel_step   the same step for actors with a camera, plus the frames: the new frame rendered into a
+//                               per-actor history, the closing transitions' stacked uint8 pixel / pixel_next into the ring,
+//                               the next acting observation (ddpg_pixel_step_kernel; the CNN perception runs between steps).
 //
 // The per-step launches the PPO rollout replaces were 3 dependent launches of ~9.5 us each (two hidden layers as GEMM
 // launches, then head + step), 384 launches for T = 128.
@@ -780,37 +783,38 @@ __global__ __launch_bounds__(RNTH) void ddpg_rollout_kernel(DArgs G) {
     if (head && G.noise == SMX_DDPG_NOISE_OU) G.ou[ha * A + hj] = x;
 }
 
-// one step for four actors per workgroup, one wavefront each, given mu [n, A] (ld_mu)
-constexpr int SA_MAX = 64;
-__global__ __launch_bounds__(256) void ddpg_step_kernel(DArgs G, const float* mu, long long ld_mu) {
-    __shared__ float s_act[4][SA_MAX];
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    const long a = (long)blockIdx.x * 4 + w;
-    const int D = G.D, A = G.A, N = G.N, tau = G.t0;
-    const bool live = a < G.n;
+// The one-step body both step kernels share, in two phases with a barrier between them.  Phase 1, lane = action j < A
+// of actor a: exploration, the open transition's action, the closing transition's (ring row `row`); the actions go to
+// s_act_w.  Phase 2, one wavefront: the environment step, the open observation and reward, the closing transition's
+// observations, reward and done; the actor's state advances (reset on done) -> element 0 of the next state before the
+// reset (lane 0; the terminal one on done).
+__device__ __forceinline__ void ddpg_step_act(const DArgs& G, const float* mu, long long ld_mu, long a, int lane,
+                                              long long row, float* s_act_w) {
+    const int A = G.A, N = G.N, tau = G.t0;
     const bool emit = tau >= N - 1;
     const int slot = tau % N, jslot = (tau + 1) % N;   // (transition j = tau - N + 1 sits in slot j % N)
+    double x = 0.0, sig = 0.0;
+    if (G.noise != SMX_DDPG_NOISE_NONE) sig = G.sigmas[a];
+    if (G.noise == SMX_DDPG_NOISE_OU) x = G.ou[a * A + lane];
+    const float e = G.eps ? G.eps[a * A + lane] : 0.f;
+    const float v = explore(mu[a * ld_mu + lane], G.noise, e, sig, G.theta, G.dt, G.root_dt, tau, x);
+    if (G.noise == SMX_DDPG_NOISE_OU) G.ou[a * A + lane] = x;
+    s_act_w[lane] = v;
+    float* ca = G.cact + (size_t)a * N * A + lane;
+    ca[(size_t)slot * A] = v;
+    if (emit) G.act[row * A + lane] = ca[(size_t)jslot * A];
+}
+
+__device__ __forceinline__ float ddpg_step_env(const DArgs& G, long a, int lane, long long row, const float* s_act_w) {
+    const int D = G.D, A = G.A, N = G.N, tau = G.t0;
+    const bool emit = tau >= N - 1;
+    const int slot = tau % N, jslot = (tau + 1) % N;
     const bool done = (tau + 1 >= G.episode_len);
-    const long long row = (live && emit) ? ring_row(G, 0, a) : 0;
-    if (live && lane < A) {
-        double x = 0.0, sig = 0.0;
-        if (G.noise != SMX_DDPG_NOISE_NONE) sig = G.sigmas[a];
-        if (G.noise == SMX_DDPG_NOISE_OU) x = G.ou[a * A + lane];
-        const float e = G.eps ? G.eps[a * A + lane] : 0.f;
-        const float v = explore(mu[a * ld_mu + lane], G.noise, e, sig, G.theta, G.dt, G.root_dt, tau, x);
-        if (G.noise == SMX_DDPG_NOISE_OU) G.ou[a * A + lane] = x;
-        s_act[w][lane] = v;
-        float* ca = G.cact + (size_t)a * N * A + lane;
-        ca[(size_t)slot * A] = v;
-        if (emit) G.act[row * A + lane] = ca[(size_t)jslot * A];
-    }
-    __syncthreads();
-    if (!live) return;
     float* co = G.cobs + (size_t)a * N * D;
     float sn0 = 0.f;
     for (int k = lane; k < D; k += 64) {
         const float s = G.state[a * D + k];
-        const float sn = synth_next(s, s_act[w][k % A], synth_drift(k));
+        const float sn = synth_next(s, s_act_w[k % A], synth_drift(k));
         co[(size_t)slot * D + k] = s;
         if (emit) {
             G.obs[row * D + k] = co[(size_t)jslot * D + k];
@@ -822,7 +826,7 @@ __global__ __launch_bounds__(256) void ddpg_step_kernel(DArgs G, const float* mu
     if (lane == 0) {
         double q = 0.0;
         for (int j = 0; j < A; ++j) {
-            const double v = (double)s_act[w][j];
+            const double v = (double)s_act_w[j];
             q += v * v;
         }
         float* cr = G.crew + (size_t)a * N;
@@ -831,6 +835,148 @@ __global__ __launch_bounds__(256) void ddpg_step_kernel(DArgs G, const float* mu
             G.rew[row] = nstep_reward(cr, G.gpow, N, tau);
             G.done[row] = done ? 1.0f : 0.0f;
         }
+    }
+    return sn0;
+}
+
+// one step for four actors per workgroup, one wavefront each, given mu [n, A] (ld_mu)
+constexpr int SA_MAX = 64;
+__global__ __launch_bounds__(256) void ddpg_step_kernel(DArgs G, const float* mu, long long ld_mu) {
+    __shared__ float s_act[4][SA_MAX];
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    const long a = (long)blockIdx.x * 4 + w;
+    const bool live = a < G.n;
+    const long long row = (live && G.t0 >= G.N - 1) ? ring_row(G, 0, a) : 0;
+    if (live && lane < G.A) ddpg_step_act(G, mu, ld_mu, a, lane, row, s_act[w]);
+    __syncthreads();
+    if (!live) return;
+    ddpg_step_env(G, a, lane, row, s_act[w]);
+}
+
+// ---- DDPG with a camera: the step above plus the frames ------------------------------------------------------------
+// Per actor a: a history of hist_len >= n_step + frame_stacks raw frames, the frame of episode step u (of the current
+// episode) in slot (hist_pos - tau + u) mod hist_len; the step's new frame goes to slot (hist_pos + 1) mod hist_len.
+// The stacked observation of step u is frames max(u - S + 1 + i, 0), i < S (stack_sources).  The frames this launch
+// reads (steps tau - n_step - S + 2 .. tau) never sit in the slot it writes, so no workgroup reads what another writes.
+//
+// Grid (1 + X, n).  Workgroup (0, a) runs the step of actor a (wavefront 0), then renders the one frame that needs the
+// next state -- step tau + 1's (the terminal frame on done) -- once, and stores it wherever it goes: the history (not on
+// done), the last frame of the closing transition's pixel_next, the last frame of the next acting observation (not on
+// done).  Workgroups (1 .. X, a) split the rest between them in units of U bytes (16: uint4 loads and stores; 1: frame
+// sizes or buffers not on 16 bytes): the history copies and, on done, the new episode's first frame (rendered from
+// init_state, which no workgroup writes).
+struct PArgs {
+    int C, H, W, S, hist_len, hist_pos, X;
+    long long F;                               // C H W bytes per frame
+    unsigned char *hist, *pix, *pix_next, *obs_pix;
+};
+
+// U bytes of frame (t, s0) from byte e0 (e0 + U <= C H W) into b
+template <int U>
+__device__ __forceinline__ void render_unit(const PArgs& P, long long e0, int shift, unsigned char* b) {
+    const int HW = P.H * P.W;
+    int c = (int)(e0 / HW);
+    const int r = (int)(e0 - (long long)c * HW);
+    int y = r / P.W, x = r - y * P.W;
+#pragma unroll
+    for (int i = 0; i < U; ++i) {
+        b[i] = synth_frame_px(c, y, x, shift);
+        if (++x == P.W) {
+            x = 0;
+            if (++y == P.H) { y = 0; ++c; }
+        }
+    }
+}
+
+template <int U>
+__device__ __forceinline__ void store_unit(unsigned char* dst, const unsigned char* b) {
+    if constexpr (U == 16) {
+        *(uint4*)dst = *(const uint4*)b;
+    } else {
+#pragma unroll
+        for (int i = 0; i < U; ++i) dst[i] = b[i];
+    }
+}
+
+template <int U>
+__device__ __forceinline__ void load_unit(const unsigned char* src, unsigned char* b) {
+    if constexpr (U == 16) {
+        *(uint4*)b = *(const uint4*)src;
+    } else {
+#pragma unroll
+        for (int i = 0; i < U; ++i) b[i] = src[i];
+    }
+}
+
+template <int U>
+__global__ __launch_bounds__(256) void ddpg_pixel_step_kernel(DArgs G, PArgs P, const float* mu, long long ld_mu) {
+    __shared__ float s_act[SA_MAX];
+    __shared__ float s_sn0;
+    const int tid = threadIdx.x, lane = tid & 63;
+    const long a = blockIdx.y;
+    const int N = G.N, S = P.S, tau = G.t0, Hd = P.hist_len;
+    const bool emit = tau >= N - 1, done = (tau + 1 >= G.episode_len);
+    const long long row = emit ? ring_row(G, 0, a) : 0;
+    const long long F = P.F, SF = (long long)S * F, nu = F / U;
+    unsigned char* hist_a = P.hist + (size_t)a * Hd * F;
+    const int wslot = (P.hist_pos + 1) % Hd;
+    alignas(16) unsigned char b[U];
+    if (blockIdx.x == 0) {
+        // ---- the low-dimensional step, then frame tau + 1 from the next state ----------------------------------
+        if (tid < 64 && lane < G.A) ddpg_step_act(G, mu, ld_mu, a, lane, row, s_act);
+        __syncthreads();
+        if (tid < 64) {
+            const float sn0 = ddpg_step_env(G, a, lane, row, s_act);
+            if (lane == 0) s_sn0 = sn0;
+        }
+        __syncthreads();
+        const int shift = synth_frame_shift(tau + 1, s_sn0);
+        unsigned char* d0 = done ? nullptr : hist_a + (size_t)wslot * F;
+        unsigned char* d1 = emit ? P.pix_next + (size_t)row * SF + (size_t)(S - 1) * F : nullptr;
+        unsigned char* d2 = done ? nullptr : P.obs_pix + (size_t)a * SF + (size_t)(S - 1) * F;
+        for (long long v = tid; v < nu; v += 256) {
+            render_unit<U>(P, v * U, shift, b);
+            if (d0) store_unit<U>(d0 + v * U, b);
+            if (d1) store_unit<U>(d1 + v * U, b);
+            if (d2) store_unit<U>(d2 + v * U, b);
+        }
+        return;
+    }
+    // ---- the copies: item q < nq is one destination frame -------------------------------------------------------
+    //   done:     q < 1 + S: the new episode's first frame -> history (q = 0), acting observation frame q - 1
+    //   not done: q < S - 1: acting observation frame q <- history, step tau + 2 - S + q
+    //   then (emit) 2 S - 1 items: pixel frame i <- step j - S + 1 + i; pixel_next frame i < S - 1 <- step tau + 2 - S + i
+    const int nfirst = done ? 1 + S : S - 1;
+    const int nq = nfirst + (emit ? 2 * S - 1 : 0);
+    const int j = tau - N + 1;
+    const int shift0 = synth_frame_shift(0, G.init_state[(size_t)a * G.D]);
+    const long long total = (long long)nq * nu, stride = (long long)P.X * 256;
+    for (long long g = (long long)(blockIdx.x - 1) * 256 + tid; g < total; g += stride) {
+        const int q = (int)(g / nu);
+        const long long e = (g - (long long)q * nu) * U;
+        unsigned char* dst;
+        int u = 0;                                   // the source step (unless first: the new episode's first frame)
+        const bool first = done && q < nfirst;
+        if (q < nfirst) {
+            if (done) dst = q == 0 ? hist_a + (size_t)wslot * F : P.obs_pix + (size_t)a * SF + (size_t)(q - 1) * F;
+            else { dst = P.obs_pix + (size_t)a * SF + (size_t)q * F; u = tau + 2 - S + q; }
+        } else if (q < nfirst + S) {
+            const int i = q - nfirst;
+            dst = P.pix + (size_t)row * SF + (size_t)i * F;
+            u = j - S + 1 + i;
+        } else {
+            const int i = q - nfirst - S;
+            dst = P.pix_next + (size_t)row * SF + (size_t)i * F;
+            u = tau + 2 - S + i;
+        }
+        if (first) {
+            render_unit<U>(P, e, shift0, b);
+        } else {
+            u = u < 0 ? 0 : u;
+            const int hs = ((P.hist_pos - tau + u) % Hd + Hd) % Hd;
+            load_unit<U>(hist_a + (size_t)hs * F + e, b);
+        }
+        store_unit<U>(dst + e, b);
     }
 }
 
@@ -1113,6 +1259,38 @@ extern "C" int smx_synth_ddpg_step_f32(const smx_ddpg_rollout_t* a, const float*
     SMX_REQUIRE((long long)a->n <= a->capacity, SMX_E_SHAPE);
     G.steps = 1;
     hipLaunchKernelGGL(ddpg_step_kernel, dim3((a->n + 3) / 4), dim3(256), 0, smx_s(stream), G, mu, (long long)ld_mu);
+    SMX_LAUNCH_CHECK();
+    return SMX_OK;
+}
+
+extern "C" int smx_synth_ddpg_pixel_step(const struct smx_ddpg_pixel_step* args, const float* mu, int64_t ld_mu,
+                                         smx_stream_t stream) {
+    SMX_REQUIRE(args && mu && args->hist && args->pixel && args->pixel_next && args->obs_pixel, SMX_E_NULL);
+    const smx_ddpg_rollout_t* a = &args->base;
+    DArgs G;
+    const int rc = common_args(a, G);
+    if (rc != SMX_OK) return rc;
+    SMX_REQUIRE(a->A <= SA_MAX && ld_mu >= a->A, SMX_E_SHAPE);
+    SMX_REQUIRE((long long)a->n <= a->capacity && a->n <= 65535, SMX_E_SHAPE);
+    SMX_REQUIRE(args->C > 0 && args->H > 0 && args->W > 0 && args->frame_stacks > 0, SMX_E_SHAPE);
+    SMX_REQUIRE(args->hist_len >= a->n_step + args->frame_stacks && args->hist_pos >= 0 &&
+                    args->hist_pos < args->hist_len, SMX_E_SHAPE);
+    G.steps = 1;
+    PArgs P;
+    memset(&P, 0, sizeof(P));
+    P.C = args->C; P.H = args->H; P.W = args->W; P.S = args->frame_stacks;
+    P.hist_len = args->hist_len; P.hist_pos = args->hist_pos;
+    P.F = (long long)args->C * args->H * args->W;
+    P.hist = args->hist; P.pix = args->pixel; P.pix_next = args->pixel_next; P.obs_pix = args->obs_pixel;
+    // the copy workgroups of an actor: ~32 KB of the at most 3 S frames each (one frame's units per workgroup at least)
+    const long long most = 3LL * P.S * P.F;
+    long long X = (most + 32767) / 32768;
+    P.X = (int)(X < 1 ? 1 : (X > 64 ? 64 : X));
+    const bool vec = P.F % 16 == 0 && (((uintptr_t)P.hist | (uintptr_t)P.pix | (uintptr_t)P.pix_next |
+                                        (uintptr_t)P.obs_pix) & 15) == 0;
+    const dim3 grid(1 + P.X, a->n);
+    if (vec) hipLaunchKernelGGL(ddpg_pixel_step_kernel<16>, grid, dim3(256), 0, smx_s(stream), G, P, mu, (long long)ld_mu);
+    else hipLaunchKernelGGL(ddpg_pixel_step_kernel<1>, grid, dim3(256), 0, smx_s(stream), G, P, mu, (long long)ld_mu);
     SMX_LAUNCH_CHECK();
     return SMX_OK;
 }

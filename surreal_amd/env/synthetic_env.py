@@ -109,9 +109,10 @@ class SyntheticVecEnv(object):
     def reset(self):
         self.state.copy_(self.init_state)
         self.t = 0
-        for k in ('carry_obs', 'carry_act', 'carry_rew', 'ou'):
+        for k in ('carry_obs', 'carry_act', 'carry_rew', 'ou', 'hist'):
             if self._ddpg.get(k) is not None:
                 self._ddpg[k].zero_()
+        self._ddpg['hist_pos'] = None         # (a camera's frame history is primed again at the next call)
         return self.state
 
     def start_rollout(self, T, info_width=0):
@@ -325,13 +326,36 @@ class SyntheticVecEnv(object):
         eps [T, n, A] standard normals (default: drawn here in one launch); sigmas [n] fp64 (default
         agent.batch_sigmas(n)); actors_per_workgroup: 4 | 8 | 16 forces the persistent kernel's block (0: automatic);
         reference=True: the two-launch reference of the persistent kernel (smx_epoch_forward_f32 for the actor, then the
-        step launch) -- for parity tests, not the product loop."""
+        step launch) -- for parity tests, not the product loop.
+        A camera agent on a camera env (frame_stacks S): per step the perception (DDPGModel.perception_into) of the
+        stacked frames, the actor, and ONE launch (smx_synth_ddpg_pixel_step) that also renders the step's frame into
+        a history of n_step + S raw frames per actor, writes the closing transitions' uint8 'pixel' / 'pixel_next'
+        [S*C, H, W] into the ring and the stacked observation of the next step.  The history carries from call to call
+        like the open transitions."""
         K, n, A = self.K, self.n, self.A
-        if self.pixel is not None or agent.model.is_pixel_input:
-            raise NotImplementedError('ddpg_rollout_into: low-dimensional observations only (no camera)')
+        camera = agent.model.is_pixel_input
+        if (self.pixel is not None) != camera:
+            raise NotImplementedError('ddpg_rollout_into: a camera on one side only (env %s, agent %s); both or neither'
+                                      % ('camera' if self.pixel else 'low-dimensional',
+                                         'camera' if camera else 'low-dimensional'))
         if agent.param_noise_type == 'adaptive_normal':
             raise NotImplementedError("ddpg_rollout_into: 'adaptive_normal' parameter noise measures an action distance "
                                       "per act() on the host; use 'normal' parameter noise or none")
+        shapes, dtypes = {'obs': (self.D,), 'obs_next': (self.D,), 'actions': (A,), 'rewards': (), 'dones': ()}, None
+        if camera:
+            C, H, W = self.pixel
+            S = self.frame_stacks
+            cam = tuple(int(v) for v in agent.obs_spec['pixel']['camera0'])
+            if cam != (S * C, H, W):
+                raise ValueError('ddpg_rollout_into: the agent\'s camera0 %s is not the env\'s stacked frame %s'
+                                 % (cam, (S * C, H, W)))
+            if agent.model.low_dim != self.D:
+                raise ValueError('ddpg_rollout_into: the agent\'s low_dim %d is not the env\'s %d'
+                                 % (agent.model.low_dim, self.D))
+            if reference:
+                raise ValueError('ddpg_rollout_into: reference=True has no camera path (no two-launch reference there)')
+            shapes.update(pixel=(S * C, H, W), pixel_next=(S * C, H, W))
+            dtypes = {'pixel': torch.uint8, 'pixel_next': torch.uint8}
         algo = agent.learner_config.algo
         N, gamma = int(algo.n_step), algo.gamma
         # the closing steps of this call (the clock is shared by all actors): n of them per closing step
@@ -343,13 +367,12 @@ class SyntheticVecEnv(object):
         if rows > replay.memory_size:
             raise ValueError('ddpg_rollout_into: %d actors x %d closing steps = %d transitions exceed the replay '
                              'capacity %d (two of them would share a row)' % (n, m, rows, replay.memory_size))
-        tables, cursor, cap = replay.reserve_ring(rows, {'obs': (self.D,), 'obs_next': (self.D,), 'actions': (A,),
-                                                         'rewards': (), 'dones': ()})
+        tables, cursor, cap = replay.reserve_ring(rows, shapes, dtypes)
         d = self._ddpg
         if d.get('n_step') != N:
             f = lambda *s: torch.zeros(*s, device=self.device)  # noqa: E731
             d.update(n_step=N, carry_obs=f(n, N, self.D), carry_act=f(n, N, A), carry_rew=f(n, N),
-                     ou=torch.zeros(n, A, device=self.device, dtype=torch.float64))
+                     ou=torch.zeros(n, A, device=self.device, dtype=torch.float64), hist=None)
         if d.get('gamma') != gamma:
             d['gamma'] = gamma
             d['gpow'] = torch.tensor([pow(gamma, e) for e in range(N)], dtype=torch.float64, device=self.device)
@@ -368,6 +391,10 @@ class SyntheticVecEnv(object):
                  theta=agent.theta, dt=agent.dt, root_dt=float(np.sqrt(agent.dt)), gpow=d['gpow'], ou=d['ou'],
                  carry_obs=d['carry_obs'], carry_act=d['carry_act'], carry_rew=d['carry_rew'], tables=tables,
                  cursor=cursor)
+        if camera:
+            self._ddpg_pixel_steps(agent, r, T, N, cap, deterministic, eps)
+            replay.commit_ring(rows)
+            return rows
         actor = agent.model.actor
         persistent = not agent.model.use_layernorm and K.synth_ddpg_rollout_supported(actor)
         if persistent or reference:
@@ -396,6 +423,42 @@ class SyntheticVecEnv(object):
                 self.t = 0 if self.t + 1 >= self.episode_len else self.t + 1
         replay.commit_ring(rows)
         return rows
+
+    def _ddpg_pixel_steps(self, agent, r, T, N, cap, deterministic, eps):
+        """ddpg_rollout_into's camera path: per step perception -> actor -> smx_synth_ddpg_pixel_step.  The history
+        (hist [n, N + S, C, H, W], the current step's frame in slot hist_pos) is primed on first use and after reset():
+        the current frame in every slot, the actors' first observation that frame S times (N + S + 1 launches, once)"""
+        from surreal_amd.model.cnn_stem import CnnStem
+        K, n, d, model = self.K, self.n, self._ddpg, agent.model
+        C, H, W = self.pixel
+        S = self.frame_stacks
+        Hd = N + S
+        if d.get('hist') is None or tuple(d['hist'].shape) != (n, Hd, C, H, W):
+            d['hist'] = torch.zeros((n, Hd, C, H, W), device=self.device, dtype=torch.uint8)
+            d['obs_pixel'] = torch.zeros((n, S * C, H, W), device=self.device, dtype=torch.uint8)
+            d['hist_pos'] = None
+        if d.get('hist_pos') is None:
+            for h in range(Hd):
+                K.synth_frames(self.state[:, 0], self.t, d['hist'][:, h])
+            K.frame_stack(d['hist'], S, 0, 1, 1, 1, d['obs_pixel'])
+            d['hist_pos'] = 0
+        p = model.cnn
+        key = (n, model.input_dim, p.C, p.H, p.W, p.c1, p.c2, p.feat)
+        if d.get('perc_key') != key:        # the perception's workspace, cached across steps and calls
+            d['perc_key'] = key
+            d['cnn_ws'] = CnnStem.workspace(model.cnn, n, self.device, backward=False)
+            d['x'] = torch.empty(n, model.input_dim, device=self.device)
+        r.update(hist=d['hist'], obs_pixel=d['obs_pixel'])
+        for s in range(T):
+            model.perception_into(d['obs_pixel'], self.state, d['cnn_ws'], d['x'])
+            mu = model.forward_actor(d['x'])
+            r['t'], r['hist_pos'] = self.t, d['hist_pos']
+            r['eps'] = None if deterministic else eps[s]
+            K.synth_ddpg_pixel_step(r, mu)
+            d['hist_pos'] = (d['hist_pos'] + 1) % Hd
+            if self.t >= N - 1:
+                r['cursor'] = (r['cursor'] + n) % cap
+            self.t = 0 if self.t + 1 >= self.episode_len else self.t + 1
 
     def _rollout_stem(self, agent, eps):
         """policies with an LSTM and / or CNN stem: one batched act per step (PPOAgent.act_batch: the stem and the

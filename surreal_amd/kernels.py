@@ -739,6 +739,29 @@ class HipKernels(object):
         p = self._ddpg_args(r, 1)
         L.call('smx_synth_ddpg_step_f32', ctypes.byref(p), L.ptr(mu), _row_stride(mu, A), self._st())
 
+    def synth_ddpg_pixel_step(self, r, mu):
+        """synth_ddpg_step for actors with a camera, in the same launch: r also holds hist uint8 [n, Hd, C, H, W] (the
+        raw frames, the current step's in slot hist_pos), obs_pixel uint8 [n, S*C, H, W] (receives the stacked
+        observation of the next step) and the ring tables 'pixel' / 'pixel_next' uint8 [capacity, S*C*H*W]
+        (include/surreal_amd.h smx_synth_ddpg_pixel_step)"""
+        n, Hd, C, H, W = r['hist'].shape
+        tabs = r['tables']
+        S = r['obs_pixel'].shape[1] // C
+        A = mu.shape[1]
+        for k in ('hist', 'obs_pixel'):
+            assert r[k].dtype == torch.uint8 and r[k].is_contiguous(), k
+        assert tuple(r['obs_pixel'].shape) == (n, S * C, H, W) and r['state'].shape[0] == n
+        for k in ('pixel', 'pixel_next'):
+            assert tabs[k].dtype == torch.uint8 and tabs[k].is_contiguous(), k
+            assert tuple(tabs[k].shape) == (tabs['obs'].shape[0], S * C * H * W), k
+        p = L.DdpgPixelStep()
+        p.base = self._ddpg_args(r, 1)
+        p.C, p.H, p.W, p.frame_stacks = C, H, W, S
+        p.hist_len, p.hist_pos = Hd, int(r['hist_pos'])
+        p.hist, p.obs_pixel = L.ptr(r['hist']), L.ptr(r['obs_pixel'])
+        p.pixel, p.pixel_next = L.ptr(tabs['pixel']), L.ptr(tabs['pixel_next'])
+        L.call('smx_synth_ddpg_pixel_step', ctypes.byref(p), L.ptr(mu), _row_stride(mu, A), self._st())
+
     def synth_env_step(self, state, init_state, actions, t, episode_len, slot, obs_roll, act_roll,
                        rew_roll, done_roll):
         n, D = state.shape

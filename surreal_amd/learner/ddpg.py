@@ -748,8 +748,10 @@ class DDPGLearner(Learner):
             if ws.s_pix is None or ws.s_pix.dtype != pix.dtype:
                 ws.s_pix, ws.s_pix_next = torch.empty_like(pix), torch.empty_like(pix_next)
                 ws.graph = None
-            ws.s_pix.copy_(pix)
-            ws.s_pix_next.copy_(pix_next)
+            for dst, src in ((ws.s_pix, pix), (ws.s_pix_next, pix_next)):     # (the same "same buffer" rule)
+                if not (src.data_ptr() == dst.data_ptr() and src.shape == dst.shape and src.stride() == dst.stride()
+                        and src.dtype == dst.dtype):
+                    dst.copy_(src)
             frames = (ws.s_pix, ws.s_pix_next)
         if self.use_action_regularization:
             # ddpg.py:268-274: policy_noise 0.2 clipped at 0.5, from numpy's global stream
@@ -783,13 +785,23 @@ class DDPGLearner(Learner):
         return self._collect_stats(ws)
 
     def staging_fields(self, batch_size):
-        """the buffers the captured iteration reads its batch from, by replay field name (low-dimensional observations):
+        """the buffers the captured iteration reads its batch from, by replay field name:
         ``replay.sample_batch(B, out=learner.staging_fields(B))`` gathers the sample where learn() would otherwise copy
-        it (five small copies per iteration, 6 % of one at batch 512)"""
-        if self.is_pixel_input:
-            raise NotImplementedError('staging_fields: low-dimensional observations')
-        ws = self._workspace(int(batch_size), self.model.input_dim)
-        return {'obs': ws.s_obs, 'obs_next': ws.s_next, 'actions': ws.s_act, 'rewards': ws.s_rew, 'dones': ws.s_done}
+        it (five small copies per iteration, 6 % of one at batch 512).  A camera learner also stages 'pixel' and
+        'pixel_next', uint8 [B] + obs_spec camera0 (allocated here on first use, kept while their dtype holds)"""
+        B = int(batch_size)
+        if not self.is_pixel_input:
+            ws = self._workspace(B, self.model.input_dim)
+            return {'obs': ws.s_obs, 'obs_next': ws.s_next, 'actions': ws.s_act, 'rewards': ws.s_rew,
+                    'dones': ws.s_done}
+        ws = self._workspace(B, self.model.low_dim)      # (_optimize keys it by the low-dimensional width)
+        cam = (B,) + tuple(int(v) for v in self.env_config.obs_spec['pixel']['camera0'])
+        if ws.s_pix is None or ws.s_pix.dtype != torch.uint8 or tuple(ws.s_pix.shape) != cam:
+            ws.s_pix = torch.empty(cam, device=self.device, dtype=torch.uint8)
+            ws.s_pix_next = torch.empty(cam, device=self.device, dtype=torch.uint8)
+            ws.graph = None
+        return {'obs': ws.s_obs, 'obs_next': ws.s_next, 'actions': ws.s_act, 'rewards': ws.s_rew, 'dones': ws.s_done,
+                'pixel': ws.s_pix, 'pixel_next': ws.s_pix_next}
 
     def _collect_stats(self, ws):
         """the iteration's one read-back; asynchronous on a GPU (resolved when looked at, at the latest

@@ -57,16 +57,20 @@ class UniformReplay(Replay):
         self._dev_len = min(self.memory_size, self._dev_len + n)
         self.cumulative_collected_count += n
 
-    def reserve_ring(self, rows, shapes):
-        """zero-copy insertion: -> (tables, cursor, capacity), tables = {field: [capacity, width] fp32 device table}
+    def reserve_ring(self, rows, shapes, dtypes=None):
+        """zero-copy insertion: -> (tables, cursor, capacity), tables = {field: [capacity, width] device table}
         (created here on first use, like insert_batch) for a producer that writes `rows` rows itself at
-        (cursor + i) % capacity, i < rows; commit_ring(rows) then makes them part of the replay"""
+        (cursor + i) % capacity, i < rows; commit_ring(rows) then makes them part of the replay.  dtypes: {field:
+        torch dtype} for the fields whose table is not fp32 (uint8 camera frames)"""
         if rows > self.memory_size:
             raise ValueError('reserve_ring: %d rows do not fit a ring of %d' % (rows, self.memory_size))
-        tables = self._ensure_tables(self.memory_size, {k: torch.empty((0,) + tuple(s)) for k, s in shapes.items()})
+        dtypes = dict(dtypes or {})
+        tables = self._ensure_tables(self.memory_size, {k: torch.empty((0,) + tuple(s), dtype=dtypes.get(k, torch.float32))
+                                                        for k, s in shapes.items()})
         for k, s in shapes.items():
-            if k not in tables or tables[k].shape != tuple(s) or tables[k].dtype != torch.float32:
-                raise ValueError('reserve_ring: field %r %s does not match the replay table' % (k, tuple(s)))
+            if k not in tables or tables[k].shape != tuple(s) or tables[k].dtype != dtypes.get(k, torch.float32):
+                raise ValueError('reserve_ring: field %r %s %s does not match the replay table'
+                                 % (k, tuple(s), dtypes.get(k, torch.float32)))
         return {k: tables[k].data for k in shapes}, self._dev_next, self.memory_size
 
     def commit_ring(self, rows):
