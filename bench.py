@@ -15,13 +15,19 @@ clip_grad_norm_, Adam), z-filter update, statistics read-back.  The KL early exi
 to the CPU baseline.  Weak scaling: each rank owns its own 1024
 sub-trajectories (actors shard across GPUs); gradients / loss sums / moments are all-reduced.
 
-Prints ONE JSON line on rank 0 (see the driver contract in the task description), with
-`roofline` for the dominant kernel (the fused FP32-MFMA critic pass), `step_roofline` for the whole
-learn() (71 GFLOP and 200.5 MB algorithmic per learn), `cpu_baseline`
+A plain run does what the headline needs and nothing more: it sets up, warms up, times the K steps,
+writes --dump-outputs if asked, and prints ONE JSON line on rank 0 with the headline and `step_roofline`
+for the whole learn() (71 GFLOP and 200.5 MB algorithmic per learn; priced from the
+timed steps, no run of its own).
+
+    python bench.py --gpus 1 --steps 20 --warmup 5 --full
+
+adds everything that takes runs of its own, and writes the complete record to --full-out:
+`roofline` for the dominant kernel (the fused FP32-MFMA critic pass, timed over launches of its own), `cpu_baseline`
 (oracle/ppo_oracle.py -- the CPU restatement of the reference learner, pinned bit-for-bit against
 the reference's own code -- timed on this host over a sweep of thread counts: the best and the
 single-thread figure), at N > 1 a `strong` entry (the SAME global batch of 1024 sub-trajectories
-split over the ranks) next to the weak-scaling headline, and at N = 1 `secondary` entries for the
+split over the ranks) next to the weak-scaling headline and the timed epoch all-reduce, and at N = 1 `secondary` entries for the
 other BASELINE configurations (PPO 64 x 128 HalfCheetah shapes with the MLP and with the reference's
 default LSTM policy -- the latter also at 1024 x 128 --, DDPG batch 512 off a 1e6-row uniform replay, PPO
 on 256 actors of 3x84x84 camera frames), the whole on-device loops (rollout -> windows -> FIFO -> learn,
@@ -949,19 +955,23 @@ def main():
     ap.add_argument('--steps', type=int, default=20)
     ap.add_argument('--warmup', type=int, default=5)
     ap.add_argument('--mode', default='adapt', choices=['adapt', 'clip'])
-    ap.add_argument('--no-cpu-baseline', action='store_true')
+    ap.add_argument('--full', action='store_true',
+                    help='also measure what the headline does not need: the dominant kernel\'s roofline, the CPU '
+                         'baseline, the other BASELINE configurations, at N > 1 the strong row and the epoch '
+                         'all-reduce; and write the complete record to --full-out')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='with --full: skip the CPU baselines')
     ap.add_argument('--no-graph', action='store_true')
     ap.add_argument('--scaling', default='weak', choices=['weak', 'strong'],
                     help='weak: 1024 sub-trajectories per GPU (the headline); strong: 1024 in total')
-    ap.add_argument('--no-secondary', action='store_true', help='skip the other BASELINE configurations')
+    ap.add_argument('--no-secondary', action='store_true', help='with --full: skip the other BASELINE configurations')
     ap.add_argument('--secondary', default='core', choices=['core', 'all'],
-                    help='core: the BASELINE configurations + the 1024-actor on-device loop (fits the default budget); '
-                         'all: also the 4096-actor / overlapped / pixel loops and the host-fed learner')
+                    help='with --full: core: the BASELINE configurations + the 1024-actor on-device loop (fits the '
+                         'default budget); all: also the 4096-actor / overlapped / pixel loops and the host-fed learner')
     ap.add_argument('--budget-s', type=float, default=70.0,
-                    help='wall-clock budget of the whole run: CPU baselines shrink to what is left, secondaries that '
-                         'would start after it are skipped (and say so)')
+                    help='with --full: wall-clock budget of the whole run: CPU baselines shrink to what is left, '
+                         'secondaries that would start after it are skipped (and say so)')
     ap.add_argument('--full-out', default=os.path.join(ROOT, 'gpurun_out', 'bench_full.json'),
-                    help='the complete record (the stdout line is its <= 4 KB summary); "" to skip')
+                    help='with --full: the complete record (the stdout line is its <= 4 KB summary); "" to skip')
     ap.add_argument('--dump-outputs', metavar='DIR', default=None,
                     help='write what the last timed step computed (statistics, updated parameters, advantages, '
                          'returns) as DIR/<name>.npy')
@@ -1103,7 +1113,7 @@ def run(args, world, rank, local_rank, backend):
         total_rows = world * B
         if args.dump_outputs and rank == 0:
             dump_outputs(learner, stats, args.dump_outputs)
-        if world > 1:       # the same global batch of 1024 sub-trajectories split over the ranks
+        if world > 1 and args.full:       # the same global batch of 1024 sub-trajectories split over the ranks
             sl, _, _, _, _, sstats, sdt = timed_run(strong_hi - strong_lo, strong_lo)
             strong = {'value': B * N * args.steps / sdt, 'unit': 'env-steps/s', 'ms_per_step': sdt / args.steps * 1e3,
                       'global_batch': B, 'B_per_gpu': strong_hi - strong_lo, 'hip_graph': bool(sl.use_graph),
@@ -1119,7 +1129,7 @@ def run(args, world, rank, local_rank, backend):
     # process group) and through the process group (RCCL) for comparison
     collective_us = collective_bytes = pg_us = None
     exchange_kind = getattr(learner, 'exchange_kind', None)
-    if world > 1 and getattr(ws, 'ar', None) is not None:
+    if args.full and world > 1 and getattr(ws, 'ar', None) is not None:
         def time_all_reduce(fn):
             for _ in range(5):
                 fn(ws.ar)
@@ -1136,7 +1146,9 @@ def run(args, world, rank, local_rank, backend):
         pg_us = time_all_reduce(dist.all_reduce)
         collective_us = time_all_reduce(learner._dist.all_reduce) if learner._dist.exchange is not None else pg_us
         collective_bytes = ws.ar.numel() * 4
-    kt = time_fused_kernel(learner, dbatch) if ws.key[0] == B and not (learner.if_rnn_policy or learner.model.if_pixel) else None
+    kt = None
+    if args.full and ws.key[0] == B and not (learner.if_rnn_policy or learner.model.if_pixel):
+        kt = time_fused_kernel(learner, dbatch)
     out = None
     if rank == 0:
         step_s = dt / args.steps
@@ -1215,7 +1227,7 @@ def run(args, world, rank, local_rank, backend):
                                              'priced like the large one: an upper bound)'}
         if strong is not None:
             out['strong'] = strong
-        if world == 1 and args.scaling == 'weak':
+        if args.full and world == 1 and args.scaling == 'weak':
             if not args.no_cpu_baseline:
                 out['cpu_baseline'] = cpu_baseline(args.mode, params, zstate, batch, budget_s=min(15.0, 0.25 * args.budget_s))
                 out['gpu_over_cpu'] = out['value'] / out['cpu_baseline']['value']
@@ -1226,7 +1238,7 @@ def run(args, world, rank, local_rank, backend):
                 torch.cuda.empty_cache()
                 out['secondary'] = secondaries(args.secondary, _T0 + args.budget_s, cpu=not args.no_cpu_baseline)
         out['bench_wall_s'] = time.time() - _T0
-        print(compact_line(out, write_full(out, args.full_out)), flush=True)
+        print(compact_line(out, write_full(out, args.full_out) if args.full else None), flush=True)
     if world > 1:
         dist.barrier()
         if getattr(learner, '_dist', None) is not None and learner._dist.exchange is not None:

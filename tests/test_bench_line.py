@@ -173,3 +173,27 @@ def test_dump_outputs_writes_what_the_last_step_returned(tmp_path, cpu_double):
         assert a.dtype == np.float32 and a.shape[0] == 8, (k, a.shape)
         np.testing.assert_array_equal(a.reshape(-1), v.cpu().numpy().reshape(-1), err_msg=k)
     assert len(names) == len(stats) + len(sd) + 2
+
+
+@pytest.mark.gpu
+def test_plain_run_times_the_headline_alone(tmp_path):
+    """a plain `bench.py --gpus 1` does what its headline needs: the contract's keys, value = env-steps of the timed
+    steps over their time, and no CPU baseline, secondary rows, kernel roofline or record file; --full adds the
+    roofline and the record (here without the CPU and secondary legs, which take a minute)"""
+    rec = tmp_path / 'full.json'
+    cmd = [sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '1', '--steps', '3', '--warmup', '1',
+           '--full-out', str(rec)]
+    for full in (False, True):
+        r = subprocess.run(cmd + (['--full', '--no-cpu-baseline', '--no-secondary'] if full else []), cwd=ROOT,
+                           capture_output=True, text=True, timeout=300)
+        lines = [ln for ln in r.stdout.splitlines() if ln.startswith('{')]
+        assert r.returncode == 0 and len(lines) == 1, r.stdout[-2000:] + r.stderr[-3000:]
+        d = json.loads(lines[0])
+        assert d['unit'] == 'env-steps/s' and d['higher_is_better'] is True and d['dtype'] == 'f32'
+        assert d['steps'] == 3 and d['warmup'] == 1 and d['ms_per_step'] > 0
+        assert d['value'] == pytest.approx(1024 * 128 / (d['ms_per_step'] * 1e-3), rel=1e-3)
+        assert 'cpu_baseline' not in d and 'secondary_summary' not in d
+        if full:
+            assert d['roofline']['frac'] > 0 and d['full_record'] and rec.exists()
+        else:
+            assert 'roofline' not in d and 'full_record' not in d and not rec.exists()

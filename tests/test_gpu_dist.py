@@ -241,7 +241,8 @@ def test_two_rank_hip_ddpg_equals_single_learner(name, peer):
 
 def test_bench_two_ranks_share_one_gpu():
     """bench.py's N = 2 code path (launch contract, rank sharding, barrier + max-over-ranks timing,
-    the single JSON line) rehearsed over gloo on one GPU; the number itself means nothing here"""
+    the single JSON line; with --full the strong row, the timed epoch all-reduce and the roofline) rehearsed
+    over gloo on one GPU; the number itself means nothing here"""
     import json
     import subprocess
     import sys
@@ -249,7 +250,7 @@ def test_bench_two_ranks_share_one_gpu():
     env = dict(os.environ, SMX_BENCH_BACKEND='gloo')
     cmd = [sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', '2',
            '--master-addr', '127.0.0.1', '--master-port', str(_free_port()),
-           os.path.join(root, 'bench.py'), '--gpus', '2', '--steps', '2', '--warmup', '1']
+           os.path.join(root, 'bench.py'), '--gpus', '2', '--steps', '2', '--warmup', '1', '--full']
     r = subprocess.run(cmd, env=env, cwd=root, capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith('{')]
