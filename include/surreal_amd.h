@@ -1083,6 +1083,54 @@ int64_t smx_lstm_rollout_packed_floats(int32_t D, int32_t H);
 int smx_lstm_rollout_pack_f32(const smx_lstm_t* net, float* packed, smx_stream_t stream);
 int smx_synth_lstm_rollout_f32(const struct smx_synth_lstm_rollout* args, smx_stream_t stream);
 
+/* The PPO rollouts above (base.lstm NULL: smx_synth_rollout_f32's plain-MLP policy from base.roll; else
+ * smx_synth_lstm_rollout_f32's one-layer LSTM stem) with every step exactly as there, recorded as the moving windows of
+ * ExpSenderWrapperMultiStepMovingWindowWithInfo (surreal/env/exp_sender_wrapper.py:153-264, restated in
+ * surreal_amd/env/exp_sender_wrapper.py) straight into the FIFO replay's ring instead of rollout tables.  Per actor a
+ * and episode step tau (all actors share the clock tau = base.roll.t at the first step, anywhere in an episode;
+ * N = n_step, adv = advance = min(stride, n_step), window_advance):
+ *   slot tau % N of the carry rings <- the state before the step (the raw observation), the action, the reward and
+ *     the pd [mu | sd] (exp_sender_wrapper.py:200-208 fills a queue of n_step); an LSTM policy's state (h, c) before
+ *     the step to slot (tau / adv) % S, S = ceil(N / adv), when tau % adv == 0 (onetime_infos, ppo_agent.py:133-135)
+ *   window j = tau + 1 - N closes at step tau when j >= 0 and j % adv == 0 (exp_sender_wrapper.py:209-228: the queue
+ *     is full, then `stride` entries are popped); at the k-th closing step of the call actor a's window goes to FIFO
+ *     row (cursor + k n + a) % capacity: obs [N, D], actions [N, A], rewards [N], dones [N], pds [N, 2A] in episode
+ *     order, obs_next [D] the observation after step tau (the terminal one before the reset, SyntheticEnv._step),
+ *     cells [2, hidden] (h then c; the replay's [2, 1, hidden]) the state before step j
+ *   windows never cross an episode: the clock restarts at 0 after the terminal step, so a partial window is dropped
+ *     (the wrapper's _reset, exp_sender_wrapper.py:192-197); the carry rings hold the open windows from one call to
+ *     the next (the caller clears them when it resets the environments), one call may span several episode ends
+ *   the LSTM state goes from h0 / c0 (nullable: zeros) to hN / cN across windows and episodes: the reference resets it
+ *     only in PPOAgent.__init__ (ppo_agent.py:168-181; Agent.main_loop, agent/base.py:244-271, never does);
+ *     h_before / c_before as in smx_synth_lstm_rollout_f32
+ * carry_obs [n, N, D], carry_act [n, N, A], carry_rew [n, N], carry_pd [n, N, 2A], carry_cells [n, S, 2, hidden]
+ * (LSTM only); obs [capacity, N, D], obs_next [capacity, D], actions [capacity, N, A], rewards / dones [capacity, N],
+ * pds [capacity, N, 2A], cells [capacity, 2, hidden] (LSTM only).  The caller makes n * (closing steps) <= capacity
+ * (checked: SMX_E_SHAPE).  base.roll's rollout tables, slot and rows_per_actor and base.cell_roll are not used.
+ * 4, 8 and 16 actors per workgroup (0: as there) all run the 4-row loop and give the same bits; the means equal those
+ * of smx_synth_rollout_f32 / smx_synth_lstm_rollout_f32 at 4 actors per workgroup bit for bit. */
+struct smx_synth_ppo_window_rollout {      /* (by tag: no typedef) */
+    struct smx_synth_lstm_rollout base;     /* base.lstm NULL: a plain-MLP policy (the stem's fields unused) */
+    int32_t n_step, advance;
+    float* carry_obs;
+    float* carry_act;
+    float* carry_rew;
+    float* carry_pd;
+    float* carry_cells;
+    float* obs;
+    float* obs_next;
+    float* actions;
+    float* rewards;
+    float* dones;
+    float* pds;
+    float* cells;
+    int64_t cursor, capacity;
+};
+/* shapes smx_synth_ppo_window_rollout_f32 takes: H == 0 a plain-MLP policy (those of smx_synth_rollout_supported, with
+ * 16-actor blocks on the 4-row loop), else those of smx_synth_lstm_rollout_supported */
+int32_t smx_synth_ppo_window_rollout_supported(int32_t D, int32_t H, int32_t H1, int32_t H2, int32_t A);
+int smx_synth_ppo_window_rollout_f32(const struct smx_synth_ppo_window_rollout* args, smx_stream_t stream);
+
 /* DDPG's acting loop on the device, recorded as n-step transitions straight into the uniform replay's ring: per step and
  * actor a (all actors share the episode clock tau = args->t at the first step)
  *   mu = tanh(MLP(s))                                      DDPGModel.actor (surreal/model/ddpg_net.py:13-95)

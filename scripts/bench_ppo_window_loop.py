@@ -1,0 +1,130 @@
+"""PPO moving-window rollouts (GPU box): SyntheticVecEnv.ppo_rollout_into (one launch that resumes mid-episode and writes
+every closing window into the FIFO) against rollout() of the same T (an episode-boundary rollout into [n, T + 1]
+tables, no windows), timed alternately in one process with device events after warm-up; then the loop at BASELINE
+configs[1]'s shape (64 actors, 128-step chunks of 1000-step episodes, the reference-default algo config): chunk ->
+ppo_rollout_into -> FIFOReplay.sample_batch(copy=False) -> PPOLearner.learn per batch.
+One JSON line per case: median / min / max over the repetitions.
+    python scripts/bench_ppo_window_loop.py [--reps 7] [--warmup 2] [--out FILE] [--quick]"""
+import argparse
+import json
+import os
+import statistics
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, 'tests'))
+import torch  # noqa: E402
+
+import ppo_window_cases as PW  # noqa: E402
+from surreal_amd.env import SyntheticVecEnv  # noqa: E402
+from surreal_amd.replay import FIFOReplay  # noqa: E402
+
+ROLLOUTS = [  # n, T, D, A, (H1, H2), rnn_hidden, (n_step, stride), episode_len
+    (1024, 128, 376, 17, (300, 200), None, (10, 10), 1000),
+    (1024, 128, 376, 17, (300, 200), None, (25, 20), 1000),
+    (1024, 128, 17, 6, (300, 200), 100, (25, 20), 1000),
+]
+
+
+def _stats(xs):
+    return {'median': statistics.median(xs), 'min': min(xs), 'max': max(xs)}
+
+
+def _timed(fn):
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record()
+    fn()
+    b.record()
+    b.synchronize()
+    return a.elapsed_time(b)
+
+
+def bench_rollouts(reps, warmup, shapes):
+    lines = []
+    for n, T, D, A, hidden, H, (N, stride), L in shapes:
+        agent, cfg = PW.make_agent(D, A, N, stride, hidden=hidden, rnn_hidden=H, memory_size=n * (T // min(N, stride)
+                                                                                                  + 2))
+        replay = FIFOReplay(*cfg)
+        win = SyntheticVecEnv(n, D, A, episode_len=L)
+        tab = SyntheticVecEnv(n, D, A, episode_len=L)
+        tab.start_rollout(T, info_width=2 * A)
+        eps = torch.randn(T, n, A, device='cuda')
+        times = {'window': [], 'rollout': []}
+        rows = []
+
+        def window():
+            rows.append(win.ppo_rollout_into(agent, replay, T, eps=eps))
+
+        def table():
+            tab.reset()
+            tab.slot = 0
+            agent._batch_cells = None
+            tab.rollout(agent, eps=eps)
+
+        for r in range(warmup + reps):
+            for name, fn in (('window', window), ('rollout', table)):
+                ms = _timed(fn)
+                if r >= warmup:
+                    times[name].append(ms)
+            while len(replay):                    # (the learner's pops: views, no launch)
+                replay.sample_batch(min(len(replay), replay.memory_size), copy=False)
+        w, t = _stats(times['window']), _stats(times['rollout'])
+        lines.append({'case': 'rollout', 'n': n, 'T': T, 'D': D, 'A': A, 'hidden': list(hidden), 'rnn_hidden': H,
+                      'n_step': N, 'stride': stride, 'episode_len': L, 'reps': reps,
+                      'windows_per_call': sorted(set(rows)), 'ppo_rollout_into_ms': w, 'rollout_ms': t,
+                      'ratio_median': w['median'] / t['median']})
+        print(json.dumps(lines[-1]), flush=True)
+    return lines
+
+
+def bench_loop(reps, warmup, n=64, T=128, L=1000, D=17, A=6):
+    """configs[1]'s shape with the reference-default algo config: env-steps/s of chunk -> FIFO -> learn"""
+    from surreal_amd.learner import PPOLearner
+    agent, cfg = PW.make_agent(D, A, 25, 20, hidden=(300, 200), rnn_hidden=100, memory_size=8 * n, batch_size=64)
+    lc, ec, sc = cfg
+    learner = PPOLearner(lc, ec, sc)
+    agent.attach_learner(learner)
+    agent.fetch_parameter()
+    replay = FIFOReplay(lc, ec, sc)
+    venv = SyntheticVecEnv(n, D, A, episode_len=L)
+    learned = [0]
+
+    def chunk():
+        venv.ppo_rollout_into(agent, replay, T)
+        while len(replay) >= lc.replay.batch_size:
+            learner.learn(venv.to_batch(replay.sample_batch(lc.replay.batch_size, copy=False)))
+            learned[0] += lc.replay.batch_size
+        agent.fetch_parameter()
+
+    times = []
+    for r in range(warmup + reps):
+        ms = _timed(chunk)
+        if r >= warmup:
+            times.append(ms)
+    s = _stats(times)
+    line = {'case': 'loop', 'n': n, 'T': T, 'episode_len': L, 'D': D, 'A': A, 'n_step': 25, 'stride': 20,
+            'rnn_hidden': 100, 'horizon': lc.algo.rnn.horizon, 'reps': reps, 'chunk_ms': s,
+            'env_steps_per_s': {'at_median': n * T / (s['median'] * 1e-3), 'at_min_ms': n * T / (s['min'] * 1e-3),
+                                'at_max_ms': n * T / (s['max'] * 1e-3)}, 'windows_learned': learned[0]}
+    print(json.dumps(line), flush=True)
+    return [line]
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument('--reps', type=int, default=7)
+    ap.add_argument('--warmup', type=int, default=2)
+    ap.add_argument('--out', default=None)
+    ap.add_argument('--quick', action='store_true', help='one repetition of each case (for a kernel trace)')
+    args = ap.parse_args()
+    reps, warmup = (1, 1) if args.quick else (args.reps, args.warmup)
+    lines = bench_rollouts(reps, warmup, ROLLOUTS) + bench_loop(reps, warmup)
+    if args.out:
+        with open(args.out, 'w') as f:
+            for ln in lines:
+                f.write(json.dumps(ln) + '\n')
+
+
+if __name__ == '__main__':
+    main()

@@ -163,6 +163,15 @@ class SynthLstmRollout(Structure):
                 ('h_before', c_void_p), ('c_before', c_void_p), ('cell_roll', c_void_p)]
 
 
+class SynthPpoWindowRollout(Structure):
+    """struct smx_synth_ppo_window_rollout"""
+    _fields_ = [('base', SynthLstmRollout), ('n_step', c_int32), ('advance', c_int32), ('carry_obs', c_void_p),
+                ('carry_act', c_void_p), ('carry_rew', c_void_p), ('carry_pd', c_void_p), ('carry_cells', c_void_p),
+                ('obs', c_void_p), ('obs_next', c_void_p), ('actions', c_void_p), ('rewards', c_void_p),
+                ('dones', c_void_p), ('pds', c_void_p), ('cells', c_void_p), ('cursor', c_int64),
+                ('capacity', c_int64)]
+
+
 class DdpgRollout(Structure):
     """smx_ddpg_rollout_t"""
     _fields_ = [('net', POINTER(Mlp3)), ('packed', c_void_p), ('n', c_int32), ('D', c_int32), ('A', c_int32),
@@ -361,6 +370,8 @@ _SIGS = {
     'smx_lstm_rollout_packed_floats': (c_int64, [c_int32, c_int32]),
     'smx_lstm_rollout_pack_f32': (c_int32, [POINTER(Lstm), _P, _P]),
     'smx_synth_lstm_rollout_f32': (c_int32, [POINTER(SynthLstmRollout), _P]),
+    'smx_synth_ppo_window_rollout_supported': (c_int32, [c_int32] * 5),
+    'smx_synth_ppo_window_rollout_f32': (c_int32, [POINTER(SynthPpoWindowRollout), _P]),
     'smx_synth_ddpg_rollout_supported': (c_int32, [c_int32, c_int32, c_int32, c_int32]),
     'smx_synth_ddpg_rollout_f32': (c_int32, [POINTER(DdpgRollout), _P]),
     'smx_synth_ddpg_step_f32': (c_int32, [POINTER(DdpgRollout), _P, c_int64, _P]),

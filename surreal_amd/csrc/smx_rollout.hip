@@ -92,6 +92,18 @@ struct LArgs : RollArgs {
     float* cell_roll;                           // [n, R, 2, Hl] the state before every step, or null
 };
 
+// the windowed PPO rollouts (ppo_window_kernel, lstm_window_kernel): the carry rings of the open windows and the FIFO's
+// tables the closing windows go to
+struct WinArgs {
+    int N, adv, S;                              // n_step, window advance min(stride, n_step), cell slots ceil(N / adv)
+    float *cobs, *cact, *crew, *cpd;            // [n, N, D | A | 1 | 2A]: step tau in slot tau % N
+    float* ccell;                               // [n, S, 2, Hl]: the state before window start tau in slot (tau / adv) % S
+    float *obs, *obs_next, *act, *rew, *done, *pd, *cells;   // [capacity, N D | D | N A | N | N | N 2A | 2 Hl]
+    long long cursor, capacity;
+};
+struct RollArgsW : RollArgs { WinArgs W; };
+struct LArgsW : LArgs { WinArgs W; };
+
 struct DArgs : RollBase {
     int N, noise;
     const double* sigmas;
@@ -304,6 +316,37 @@ __device__ __forceinline__ void layers4(const RollBase& G, float* sm, int nl, in
 
 // ---- PPO -------------------------------------------------------------------------------------------------------------
 
+// the FIFO row of actor a's window at the k-th closing step of the launch: (cursor + k n + a) % capacity, given
+// base = (cursor + k n) % capacity (a < n <= capacity: one wrap at most)
+__device__ __forceinline__ long long win_row(const WinArgs& W, long long base, long a) {
+    const long long r = base + a;
+    return r >= W.capacity ? r - W.capacity : r;
+}
+
+// A closing window's N steps from a carry ring to its FIFO row: ld(slot, c) reads column c of ring slot `slot`, st(u, c,
+// v) stores it as step u of the window (streaming).  The window's first step sits in slot `first`; U steps' C columns are
+// loaded before any of them is stored, so that U C loads are in flight (the ring was written steps ago: L2 or HBM).
+template <int U, int C, typename Ld, typename St>
+__device__ __forceinline__ void copy_window(int N, int first, Ld ld, St st) {
+#pragma unroll 1
+    for (int u0 = 0; u0 < N; u0 += U) {
+        int s0 = first + u0;
+        s0 = s0 >= N ? s0 - N : s0;
+        float v[U][C];
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const int s = s0 + u >= N ? s0 + u - N : s0 + u;
+#pragma unroll
+            for (int c = 0; c < C; ++c) v[u][c] = (u0 + u < N) ? ld(s, c) : 0.f;
+        }
+#pragma unroll
+        for (int u = 0; u < U; ++u)
+            if (u0 + u < N)
+#pragma unroll
+                for (int c = 0; c < C; ++c) st(u0 + u, c, v[u][c]);
+    }
+}
+
 // RG row groups of four actors per workgroup (round 6; smx_rows4_mma.inc.h).  1024 actors: RG = 1 -> 256 workgroups, one per
 // CU.  The host picks the smallest RG whose grid fits the chip once (more actors per workgroup = fewer passes over the
 // packed weights per actor; fewer = more CUs at work).
@@ -312,7 +355,15 @@ __device__ __forceinline__ void layers4(const RollBase& G, float* sm, int nl, in
 // the (row, unit) pairs q + RNTH i (at most RG of them for H <= 128) and keeps their cells in LDS slots no other thread
 // touches (registers are short at 16 actors); it writes h' back into the tile's h columns, where the actor's first
 // layer reads it.
-template <int RG, int NT, bool LSTM, bool COLS, typename Args>
+// WIN (ppo_window_kernel, lstm_window_kernel; Args carries a WinArgs W): the same steps, recorded as moving windows
+// instead of rollout tables.  Step tau of an actor goes to slot tau % N of its carry rings (the state before it, the
+// action, the reward, the pd; an LSTM state before every window start tau % adv == 0 to slot (tau / adv) % S) -- each
+// value written and later read by the SAME lane, as DDPG's open transitions, so no barrier orders them and they carry
+// from one launch to the next.  At the step that closes window j = tau + 1 - N (j >= 0, j % adv == 0), the lanes that
+// wrote its steps copy them into the FIFO row (cursor + k n + a) % capacity (k: the closing steps of the launch before
+// this one), with obs_next the observation after the step (the terminal one before a reset) and the window's dones 0
+// but the last (= done: a window never crosses an episode, the clock restarts at 0).
+template <int RG, int NT, bool LSTM, bool COLS, bool WIN = false, typename Args>
 __device__ __forceinline__ void ppo_rollout(Args G) {
     constexpr int RB = 4 * RG;                       // actors per workgroup
     extern __shared__ float sm[];
@@ -373,11 +424,23 @@ __device__ __forceinline__ void ppo_rollout(Args G) {
     float sd0 = expf(G.log_var[hj]);
     if (G.noise_scale && hr < nrows) sd0 = sd0 * G.noise_scale[row0 + hr];
     int t = G.t0;
+    long long wbase = 0;                         // (WIN) (cursor + k n) % capacity after k closing steps
+    if constexpr (WIN) wbase = G.W.cursor;
     RWALL(12); RCYC(13);
 #pragma unroll 1
     for (int step = 0; step < G.steps; ++step) {
         const int slot = G.slot0 + step;
         const bool last_step = step + 1 == G.steps;
+        // (WIN) this step's ring slot, whether it starts a window / closes one, the closing window's first slot
+        int wslot = 0, wfirst = 0;
+        bool wstart = false, wclose = false;
+        if constexpr (WIN) {
+            const int wj = t + 1 - G.W.N;
+            wslot = t % G.W.N;
+            wfirst = (t + 1) % G.W.N;
+            wstart = t % G.W.adv == 0;
+            wclose = wj >= 0 && wj % G.W.adv == 0;
+        }
         RSTAMP(0);
         // this step's normal draw of the lane's (row, action) pair, requested before the layers (consumed behind them)
         float ev = 0.f;
@@ -414,6 +477,21 @@ __device__ __forceinline__ void ppo_rollout(Args G) {
                             if (last_step && G.h_before) {
                                 G.h_before[a * Hl + j] = *hp;
                                 G.c_before[a * Hl + j] = c0;
+                            }
+                            if constexpr (WIN) {
+                                const WinArgs& W = G.W;
+                                float* cc = W.ccell + (size_t)a * W.S * 2 * Hl + j;
+                                if (wstart) {
+                                    float* cw = cc + (size_t)((t / W.adv) % W.S) * 2 * Hl;
+                                    cw[0] = *hp;
+                                    cw[Hl] = c0;
+                                }
+                                if (wclose) {
+                                    const float* cr = cc + (size_t)(((t + 1 - W.N) / W.adv) % W.S) * 2 * Hl;
+                                    float* d = W.cells + win_row(W, wbase, a) * 2 * Hl + j;
+                                    __builtin_nontemporal_store(cr[0], d);
+                                    __builtin_nontemporal_store(cr[Hl], d + Hl);
+                                }
                             }
                         }
                         cst[q] = c;
@@ -482,6 +560,7 @@ __device__ __forceinline__ void ppo_rollout(Args G) {
             float act = G.eps ? ev * sd + mu : mu;
             if (act == act) act = fminf(fmaxf(act, -1.0f), 1.0f);
             s_act[hr * RMAX_A + hj] = act;
+            if constexpr (!WIN) {
             // (the rollout tables are written once and read by a later launch: streaming stores, so that 3 MB of them per
             // step do not push the packed weights -- re-read by every workgroup every step -- out of the L2s)
             if (G.act_roll) __builtin_nontemporal_store(act, &G.act_roll[(a * R + slot) * A + hj]);
@@ -489,10 +568,33 @@ __device__ __forceinline__ void ppo_rollout(Args G) {
                 __builtin_nontemporal_store(mu, &G.pd_roll[(a * R + slot) * 2 * A + hj]);
                 __builtin_nontemporal_store(sd, &G.pd_roll[(a * R + slot) * 2 * A + A + hj]);
             }
+            } else {
+                // the pair's action and pd into the ring (plain stores: read back within N steps), the window's N of
+                // them into the FIFO row when one closes
+                const WinArgs& W = G.W;
+                const int N = W.N;
+                float* ca = W.cact + (size_t)a * N * A + hj;
+                float* cp = W.cpd + (size_t)a * N * 2 * A + hj;
+                ca[(size_t)wslot * A] = act;
+                cp[(size_t)wslot * 2 * A] = mu;
+                cp[(size_t)wslot * 2 * A + A] = sd;
+                if (wclose) {
+                    const long long row = win_row(W, wbase, a);
+                    float* da = W.act + (row * N) * A + hj;
+                    float* dp = W.pd + (row * N) * 2 * A + hj;
+                    copy_window<8, 3>(N, wfirst,
+                        [&](int s, int c) { return c == 0 ? ca[(size_t)s * A] : cp[(size_t)s * 2 * A + (c - 1) * A]; },
+                        [&](int u, int c, float v) {
+                            if (c == 0) __builtin_nontemporal_store(v, da + (size_t)u * A);
+                            else __builtin_nontemporal_store(v, dp + (size_t)u * 2 * A + (c - 1) * A);
+                        });
+                }
+            }
         }
         SMX_LDS_BARRIER();
         RSTAMP(4);
         // ---- environment step of the actors (smx_synth_env_step_f32's expressions), recording, next x tile ------
+        if constexpr (!WIN) {
         E.step(s_act, done,
                [&](long a) { return G.obs_roll ? G.obs_roll + (a * R + slot) * D : nullptr; },
                [&](long a, float* orow, int k, float s, float sn) {
@@ -509,6 +611,55 @@ __device__ __forceinline__ void ppo_rollout(Args G) {
                    if (G.rew_roll) __builtin_nontemporal_store(rew, &G.rew_roll[a * R + slot]);
                    if (G.done_roll) __builtin_nontemporal_store(done ? 1.0f : 0.0f, &G.done_roll[a * R + slot]);
                });
+        } else {
+            // the state before the step into the ring, obs_next (the next state before any reset) and the window's
+            // rewards and dones into the FIFO row when one closes; its observations below
+            const WinArgs& W = G.W;
+            const int N = W.N;
+            struct Row { float* co; long long row; };
+            E.step(s_act, done,
+                   [&](long a) { return Row{W.cobs + ((size_t)a * N + wslot) * D, wclose ? win_row(W, wbase, a) : 0}; },
+                   [&](long, const Row& p, int k, float s, float sn) {
+                       p.co[k] = s;
+                       if (wclose) __builtin_nontemporal_store(sn, &W.obs_next[p.row * D + k]);
+                   },
+                   [&](long a, const Row& p, float rew) {
+                       float* cr = W.crew + (size_t)a * N;
+                       cr[wslot] = rew;
+                       if (wclose) {
+                           float* dr = W.rew + p.row * N;
+                           float* dd = W.done + p.row * N;
+                           copy_window<8, 1>(N, wfirst, [&](int s, int) { return cr[s]; },
+                                             [&](int u, int, float v) {
+                                                 __builtin_nontemporal_store(v, dr + u);
+                                                 __builtin_nontemporal_store((done && u == N - 1) ? 1.0f : 0.0f, dd + u);
+                                             });
+                       }
+                   });
+            if (wclose) {
+                // the window's observations: every lane copies the elements it wrote, RPW rows of KPL each
+                using EL = decltype(E);
+#pragma unroll
+                for (int rr = 0; rr < EL::RPW; ++rr) {
+                    const int r = E.erow0 + rr;
+                    if (r < nrows) {
+                        const long a = row0 + r;
+                        const float* co = W.cobs + (size_t)a * N * D;
+                        float* dst = W.obs + win_row(W, wbase, a) * N * D;
+                        copy_window<32 / EL::KPL, EL::KPL>(N, wfirst,
+                            [&](int s, int i) { const int k = E.kel(i); return k < D ? co[(size_t)s * D + k] : 0.f; },
+                            [&](int u, int i, float v) {
+                                const int k = E.kel(i);
+                                if (k < D) __builtin_nontemporal_store(v, &dst[(size_t)u * D + k]);
+                            });
+                    }
+                }
+            }
+            if (wclose) {
+                wbase += G.n;
+                wbase = wbase >= G.W.capacity ? wbase - G.W.capacity : wbase;
+            }
+        }
         t = done ? 0 : t + 1;
         SMX_LDS_BARRIER();
         RSTAMP(5);
@@ -539,6 +690,18 @@ __global__ __launch_bounds__(RNTH) void rollout_kernel(RollArgs G) {
 template <int RG>
 __global__ __launch_bounds__(RNTH) void lstm_rollout_kernel(LArgs G) {
     ppo_rollout<RG, RG == 4 ? 2 : 3, true, RG < 4>(G);
+}
+
+// The windowed rollouts (smx_synth_ppo_window_rollout_f32): the two kernels above recording moving windows into the
+// FIFO; the plain-MLP policy on the 4-row loop at 16 actors too (as the LSTM kernel), so 4, 8 and 16 give the same bits
+template <int RG>
+__global__ __launch_bounds__(RNTH) void ppo_window_kernel(RollArgsW G) {
+    ppo_rollout<RG, RG == 4 ? 2 : 3, false, RG < 4, true>(G);
+}
+
+template <int RG>
+__global__ __launch_bounds__(RNTH) void lstm_window_kernel(LArgsW G) {
+    ppo_rollout<RG, RG == 4 ? 2 : 3, true, RG < 4, true>(G);
 }
 
 constexpr int RTG = 3;            // feature tiles a wave carries per pass (register budget of two waves per SIMD)
@@ -1112,6 +1275,32 @@ long long emitting_steps(int t, int steps, int episode_len, int N) {
     return m;
 }
 
+// closing steps of moving windows (n_step N, advance adv) among `steps` steps from clock t
+long long window_closing_steps(int t, int steps, int episode_len, int N, int adv) {
+    long long m = 0;
+    for (int s = 0; s < steps; ++s) {
+        const int j = t + 1 - N;
+        if (j >= 0 && j % adv == 0) ++m;
+        t = (t + 1 >= episode_len) ? 0 : t + 1;
+    }
+    return m;
+}
+
+// the fields of a PPO rollout's argument block the windowed kernels take (the rollout tables, slot and rows_per_actor
+// are not used)
+void roll_fields(const smx_synth_rollout_t* a, int D, RollArgs& G) {
+    const smx_mlp3_t& n = *a->net;
+    G.P1 = a->packed;
+    G.P2 = a->packed + 4 * pack_off(n.D, n.H1, n.H2, n.OUT, 1);
+    G.P3 = a->packed + 4 * pack_off(n.D, n.H1, n.H2, n.OUT, 2);
+    G.b1 = n.b1; G.b2 = n.b2; G.b3 = n.b3;
+    G.D = D; G.H1 = n.H1; G.H2 = n.H2; G.A = n.OUT; G.out_act = a->out_act;
+    G.log_var = a->log_var; G.noise_scale = a->noise_scale; G.eps = a->eps;
+    G.zsum = a->zsum; G.zsumsq = a->zsumsq; G.zcount = a->zcount; G.zeps = a->zeps;
+    G.state = a->state; G.init_state = a->init_state;
+    G.n = a->n; G.t0 = a->t; G.episode_len = a->episode_len; G.steps = a->steps;
+}
+
 }  // namespace
 
 #ifdef SMX_ROLLOUT_TIMING
@@ -1220,6 +1409,76 @@ extern "C" int smx_synth_lstm_rollout_f32(const smx_synth_lstm_rollout* args, sm
     if (rb == 4) return launch<lstm_rollout_kernel<1>>(G, rb, lds, stream);
     if (rb == 8) return launch<lstm_rollout_kernel<2>>(G, rb, lds, stream);
     return launch<lstm_rollout_kernel<4>>(G, rb, lds, stream);
+}
+
+extern "C" int32_t smx_synth_ppo_window_rollout_supported(int32_t D, int32_t H, int32_t H1, int32_t H2, int32_t A) {
+    if (H == 0) return supported(D, H1, H2, A, /*mma16=*/false, /*split_out=*/true, /*ztables=*/true);
+    return smx_synth_lstm_rollout_supported(D, H, H1, H2, A);
+}
+
+extern "C" int smx_synth_ppo_window_rollout_f32(const smx_synth_ppo_window_rollout* args, smx_stream_t stream) {
+    SMX_REQUIRE(args, SMX_E_NULL);
+    const smx_synth_lstm_rollout& b = args->base;
+    const smx_synth_rollout_t* a = &b.roll;
+    const bool lstm = b.lstm != nullptr;
+    SMX_REQUIRE(a->net && a->packed && a->log_var && a->state && a->init_state, SMX_E_NULL);
+    SMX_REQUIRE(args->carry_obs && args->carry_act && args->carry_rew && args->carry_pd, SMX_E_NULL);
+    SMX_REQUIRE(args->obs && args->obs_next && args->actions && args->rewards && args->dones && args->pds, SMX_E_NULL);
+    SMX_REQUIRE(!lstm || (b.lstm_packed && b.hN && b.cN && args->carry_cells && args->cells), SMX_E_NULL);
+    SMX_REQUIRE((b.h_before == nullptr) == (b.c_before == nullptr), SMX_E_NULL);
+    SMX_REQUIRE((b.h0 == nullptr) == (b.c0 == nullptr), SMX_E_NULL);
+    SMX_REQUIRE((a->zsum == nullptr) == (a->zsumsq == nullptr) && (a->zsum == nullptr) == (a->zcount == nullptr), SMX_E_NULL);
+    const smx_mlp3_t& n = *a->net;
+    if (lstm) {
+        const smx_lstm_t& l = *b.lstm;
+        SMX_REQUIRE(n.D == l.H && b.hidden > 0 && b.hidden <= l.H && l.H - b.hidden < 4, SMX_E_SHAPE);
+        SMX_REQUIRE(smx_synth_ppo_window_rollout_supported(l.D, l.H, n.H1, n.H2, n.OUT), SMX_E_UNSUPPORTED);
+    } else {
+        SMX_REQUIRE(smx_synth_ppo_window_rollout_supported(n.D, 0, n.H1, n.H2, n.OUT), SMX_E_UNSUPPORTED);
+    }
+    SMX_REQUIRE(a->n > 0 && a->steps > 0 && a->episode_len > 0 && a->t >= 0 && a->t < a->episode_len, SMX_E_SHAPE);
+    SMX_REQUIRE(a->actors_per_workgroup == 0 || a->actors_per_workgroup == 4 || a->actors_per_workgroup == 8 ||
+                a->actors_per_workgroup == 16, SMX_E_SHAPE);
+    SMX_REQUIRE(args->n_step > 0 && args->advance > 0 && args->advance <= args->n_step, SMX_E_SHAPE);
+    SMX_REQUIRE(args->capacity > 0 && args->cursor >= 0 && args->cursor < args->capacity, SMX_E_SHAPE);
+    // two workgroups must never write the same FIFO row: all n m rows of the call are distinct
+    SMX_REQUIRE((long long)a->n * window_closing_steps(a->t, a->steps, a->episode_len, args->n_step, args->advance) <=
+                    args->capacity, SMX_E_SHAPE);
+    SMX_REQUIRE(((uintptr_t)a->packed & 15) == 0 && ((uintptr_t)n.b1 & 3) == 0, SMX_E_ALIGN);
+    SMX_REQUIRE(!lstm || ((uintptr_t)b.lstm_packed & 15) == 0, SMX_E_ALIGN);
+    WinArgs W;
+    memset(&W, 0, sizeof(W));
+    W.N = args->n_step; W.adv = args->advance; W.S = (W.N + W.adv - 1) / W.adv;
+    W.cobs = args->carry_obs; W.cact = args->carry_act; W.crew = args->carry_rew; W.cpd = args->carry_pd;
+    W.ccell = args->carry_cells;
+    W.obs = args->obs; W.obs_next = args->obs_next; W.act = args->actions; W.rew = args->rewards; W.done = args->dones;
+    W.pd = args->pds; W.cells = args->cells;
+    W.cursor = args->cursor; W.capacity = args->capacity;
+    const int rb = pick_block(a->actors_per_workgroup, a->n);
+    if (!lstm) {
+        RollArgsW G;
+        memset(&G, 0, sizeof(G));
+        roll_fields(a, n.D, G);
+        G.W = W;
+        const int lds = carve(G, rb, /*mma16=*/false, /*split_out=*/true, /*ztables=*/true, G.D);
+        if (rb == 4) return launch<ppo_window_kernel<1>>(G, rb, lds, stream);
+        if (rb == 8) return launch<ppo_window_kernel<2>>(G, rb, lds, stream);
+        return launch<ppo_window_kernel<4>>(G, rb, lds, stream);
+    }
+    const smx_lstm_t& l = *b.lstm;
+    LArgsW G;
+    memset(&G, 0, sizeof(G));
+    roll_fields(a, l.D, G);
+    G.H = l.H; G.Hl = b.hidden;
+    G.Pg = b.lstm_packed;
+    G.bg = b.lstm_packed + pack_words(4 * l.H, lstm_dp(l.D) + l.H) * 4;
+    G.h0 = b.h0; G.c0 = b.c0; G.hN = b.hN; G.cN = b.cN;
+    G.h_before = b.h_before; G.c_before = b.c_before;
+    G.W = W;
+    const int lds = carve_lstm(G, rb);
+    if (rb == 4) return launch<lstm_window_kernel<1>>(G, rb, lds, stream);
+    if (rb == 8) return launch<lstm_window_kernel<2>>(G, rb, lds, stream);
+    return launch<lstm_window_kernel<4>>(G, rb, lds, stream);
 }
 
 extern "C" int32_t smx_synth_ddpg_rollout_supported(int32_t D, int32_t H1, int32_t H2, int32_t A) {

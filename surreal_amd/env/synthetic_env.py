@@ -105,6 +105,7 @@ class SyntheticVecEnv(object):
         self.rolls = None
         self.persistent = True        # rollout(): the one-launch kernel where the policy's shapes allow it
         self._ddpg = {}               # ddpg_rollout_into(): the open n-step transitions and OU states of the actors
+        self._ppo = {}                # ppo_rollout_into(): the open moving windows of the actors
 
     def reset(self):
         self.state.copy_(self.init_state)
@@ -113,6 +114,7 @@ class SyntheticVecEnv(object):
             if self._ddpg.get(k) is not None:
                 self._ddpg[k].zero_()
         self._ddpg['hist_pos'] = None         # (a camera's frame history is primed again at the next call)
+        self._ppo = {}                        # (the open windows: a new episode has none)
         return self.state
 
     def start_rollout(self, T, info_width=0):
@@ -315,6 +317,112 @@ class SyntheticVecEnv(object):
                         actors_per_workgroup)
         for _ in range(T):
             self.t = 0 if self.t + 1 >= self.episode_len else self.t + 1
+
+    def _ppo_window_refusal(self, agent):
+        """why ppo_rollout_into cannot take `agent` -> (exception class, message), or None"""
+        m = agent.model
+        if self.pixel is not None or m.if_pixel:
+            return NotImplementedError, 'ppo_rollout_into: camera observations are not supported (low-dimensional only)'
+        if agent.rnn_config.if_rnn_policy and agent.rnn_config.rnn_layer != 1:
+            return NotImplementedError, ('ppo_rollout_into: rnn_layer %d; the windowed rollout runs one LSTM layer'
+                                         % agent.rnn_config.rnn_layer)
+        if getattr(self.K, 'synth_ppo_window_rollout', None) is None:
+            return NotImplementedError, 'ppo_rollout_into: the kernels object has no synth_ppo_window_rollout'
+        if not self.K.synth_ppo_window_rollout_supported(m):
+            return ValueError, ('ppo_rollout_into: policy shapes the persistent kernel refuses (A <= 32, hidden sizes '
+                                'multiples of 4 up to 640, D <= 512, LSTM units up to 128; smx_synth_ppo_window_rollout_'
+                                'supported)')
+        return None
+
+    def can_ppo_rollout_into(self, agent):
+        """ppo_rollout_into() takes `agent`: a plain-MLP or one-layer LSTM policy on low-dimensional observations whose
+        shapes the windowed kernel takes"""
+        return self._ppo_window_refusal(agent) is None
+
+    def ppo_rollout_into(self, agent, replay, T, eps=None, actors_per_workgroup=0):
+        """T steps of all actors under PPOAgent `agent` (act: z-filter -> [LSTM ->] policy MLP -> DiagGauss sample ->
+        clip, ppo_agent.py:106-154), their moving windows (ExpSenderWrapperMultiStepMovingWindowWithInfo,
+        exp_sender_wrapper.py:153-264; n_step / stride of the agent's algo config) written STRAIGHT INTO the FIFO
+        replay's device ring (FIFOReplay.reserve_ring / commit_ring) -> the number of windows written.  ONE launch
+        (smx_synth_ppo_window_rollout_f32).  Resumes wherever the actors are: the open windows carry from call to call
+        (reset() clears them), T may be any length, windows never cross an episode.  An LSTM policy's state comes from
+        agent._batch_cells (zeros when None) and is left there after the last step (batch_cells_before: the state
+        before it), as act_batch leaves it; it is never reset at episode ends, as in the reference.
+        eps [T, n, A] standard normals (default: drawn here in one launch; deterministic agent modes use none);
+        actors_per_workgroup: 4 | 8 | 16 forces the kernel's block (0: automatic; every block size gives the same bits)."""
+        refusal = self._ppo_window_refusal(agent)
+        if refusal is not None:
+            raise refusal[0](refusal[1])
+        T = int(T)
+        if T < 1:
+            raise ValueError('ppo_rollout_into: T must be positive, got %d' % T)
+        from surreal_amd.env.exp_sender_wrapper import window_advance
+        K, n, D, A, m = self.K, self.n, self.D, self.A, agent.model
+        algo = agent.learner_config.algo
+        N, adv = int(algo.n_step), window_advance(algo.n_step, algo.stride)
+        rnn = bool(agent.rnn_config.if_rnn_policy)
+        Hl = m.rnn_hidden_logical if rnn else 0
+        c = self._ppo
+        key = (N, adv, D, A, Hl)
+        if c.get('key') != key or c.get('t') != self.t:
+            if self.t != 0:
+                raise ValueError('ppo_rollout_into: the open windows of clock %d are not held (the environments were '
+                                 'stepped outside ppo_rollout_into, or n_step / stride changed); reset() first' % self.t)
+            f = lambda *s: torch.zeros(*s, device=self.device)  # noqa: E731
+            c.clear()
+            c.update(key=key, carry={'obs': f(n, N, D), 'actions': f(n, N, A), 'rewards': f(n, N), 'pds': f(n, N, 2 * A)})
+            if rnn:
+                c['carry']['cells'] = f(n, -(-N // adv), 2, Hl)
+        # the closing steps of this call (the clock is shared by all actors): n windows each
+        closing, t = 0, self.t
+        for _ in range(T):
+            j = t + 1 - N
+            closing += j >= 0 and j % adv == 0
+            t = 0 if t + 1 >= self.episode_len else t + 1
+        rows = n * closing
+        if rows > replay.memory_size + 3:
+            raise ValueError('ppo_rollout_into: %d actors x %d closing steps = %d windows exceed the FIFO capacity %d '
+                             '(two of them would share a row)' % (n, closing, rows, replay.memory_size + 3))
+        shapes = {'obs': (N, D), 'obs_next': (1, D), 'actions': (N, A), 'rewards': (N,), 'dones': (N,),
+                  'pds': (N, 2 * A)}
+        if rnn:
+            shapes['cells'] = (2, 1, Hl)
+        tables, cursor, _ = replay.reserve_ring(rows, shapes)
+        deterministic = agent.agent_mode in ('eval_deterministic', 'eval_deterministic_local')
+        if deterministic:
+            eps = None
+        else:
+            if eps is None:
+                eps = torch.randn(T, n, A, device=self.device)
+            assert tuple(eps.shape) == (T, n, A)
+            eps = eps.contiguous()
+        if getattr(self, '_pk', None) is None or self._pk.numel() != K.epoch_packed_numel(m.actor):
+            self._pk = torch.zeros(K.epoch_packed_numel(m.actor), device=self.device)
+        K.epoch_pack([(m.actor, self._pk)])          # (every call: the agent's parameters change between chunks)
+        zf = m.z_filter if agent.use_z_filter else None
+        noise = agent.batch_noise(n).view(-1)
+        if rnn:
+            if getattr(self, '_lpk', None) is None or self._lpk.numel() != K.lstm_rollout_packed_numel(m.rnn):
+                self._lpk = torch.zeros(K.lstm_rollout_packed_numel(m.rnn), device=self.device)
+            K.lstm_rollout_pack(m.rnn, self._lpk)
+            cells = agent._batch_cells
+            h0, c0 = (None, None) if cells is None or cells[0].shape[1] != n else \
+                (cells[0].contiguous(), cells[1].contiguous())
+            e = lambda: torch.empty(1, n, Hl, device=self.device)  # noqa: E731
+            hN, cN, hB, cB = e(), e(), e(), e()
+            K.synth_ppo_window_rollout(m, self._pk, self._lpk, self.state, self.init_state, noise, eps, self.t,
+                                       self.episode_len, T, N, adv, c['carry'], tables, cursor, zf, hN=hN, cN=cN,
+                                       h0=h0, c0=c0, h_before=hB, c_before=cB,
+                                       actors_per_workgroup=actors_per_workgroup)
+            agent._batch_cells = (hN, cN)
+            agent.batch_cells_before = (hB, cB)
+        else:
+            K.synth_ppo_window_rollout(m, self._pk, None, self.state, self.init_state, noise, eps, self.t,
+                                       self.episode_len, T, N, adv, c['carry'], tables, cursor, zf,
+                                       actors_per_workgroup=actors_per_workgroup)
+        replay.commit_ring(rows)
+        self.t = c['t'] = t
+        return rows
 
     def ddpg_rollout_into(self, agent, replay, T, eps=None, sigmas=None, actors_per_workgroup=0, reference=False):
         """T steps of all actors under DDPGAgent `agent` (act: actor -> clip -> exploration noise -> clip,

@@ -696,6 +696,60 @@ class HipKernels(object):
         p.h_before, p.c_before, p.cell_roll = L.ptr(h_before), L.ptr(c_before), L.ptr(r.get('cells'))
         L.call('smx_synth_lstm_rollout_f32', ctypes.byref(p), self._st())
 
+    def synth_ppo_window_rollout_supported(self, model):
+        """a PPOModel whose policy smx_synth_ppo_window_rollout_f32 runs: a plain MLP, or one LSTM layer, on
+        low-dimensional observations, shapes it takes"""
+        if model.if_pixel or (model.if_rnn and model.rnn_layers != 1):
+            return False
+        a = model.actor
+        if not model.if_rnn:
+            return bool(self.lib.smx_synth_ppo_window_rollout_supported(a.D, 0, a.H1, a.H2, a.OUT))
+        r = model.rnn
+        return a.D == r.H and bool(self.lib.smx_synth_ppo_window_rollout_supported(r.D, r.H, a.H1, a.H2, a.OUT))
+
+    def synth_ppo_window_rollout(self, model, packed, lstm_packed, state, init_state, noise_scale, eps, t, episode_len,
+                                 steps, n_step, advance, carry, tables, cursor, zfilter, hN=None, cN=None, h0=None,
+                                 c0=None, h_before=None, c_before=None, actors_per_workgroup=0):
+        """`steps` steps of synth_rollout (model.rnn None) / synth_lstm_rollout recorded as moving windows of n_step
+        steps, `advance` apart, straight into a FIFO ring, ONE launch (smx_synth_ppo_window_rollout_f32).
+        carry: the open windows {'obs' [n, n_step, D], 'actions' [n, n_step, A], 'rewards' [n, n_step], 'pds'
+        [n, n_step, 2A], 'cells' [n, ceil(n_step / advance), 2, Hl] (LSTM)}; tables: the ring by replay field name
+        ('obs' [capacity, n_step * D], 'obs_next', 'actions', 'rewards', 'dones', 'pds', 'cells' (LSTM)); the k-th
+        closing step writes actor a to row (cursor + k n + a) % capacity.  h0 / c0 (None: zeros), hN / cN (LSTM),
+        h_before / c_before: [n, Hl] contiguous, Hl = model.rnn_hidden_logical"""
+        actor = model.actor
+        n = state.shape[0]
+        lstm = model.rnn if model.if_rnn else None
+        p = L.SynthPpoWindowRollout()
+        q = p.base.roll
+        q.net, q.packed, q.out_act, q.n = ctypes.pointer(actor.desc), L.ptr(packed), L.SMX_ACT_TANH, n
+        q.log_var, q.noise_scale, q.eps = L.ptr(model.log_var), L.ptr(noise_scale), L.ptr(eps)
+        if eps is not None:
+            assert eps.is_contiguous() and tuple(eps.shape) == (steps, n, actor.OUT)
+        if zfilter is not None:
+            q.zsum, q.zsumsq, q.zcount = L.ptr(zfilter.running_sum), L.ptr(zfilter.running_sumsq), L.ptr(zfilter.count)
+            q.zeps = float(zfilter.eps)
+        q.t, q.episode_len, q.steps = int(t), int(episode_len), int(steps)
+        q.state, q.init_state = L.ptr(state), L.ptr(init_state)
+        q.actors_per_workgroup = int(actors_per_workgroup)
+        if lstm is not None:
+            Hl = model.rnn_hidden_logical
+            for x in (h0, c0, hN, cN, h_before, c_before):
+                assert x is None or (x.is_contiguous() and x.numel() == n * Hl)
+            p.base.lstm, p.base.lstm_packed, p.base.hidden = ctypes.pointer(lstm.desc), L.ptr(lstm_packed), Hl
+            p.base.h0, p.base.c0, p.base.hN, p.base.cN = L.ptr(h0), L.ptr(c0), L.ptr(hN), L.ptr(cN)
+            p.base.h_before, p.base.c_before = L.ptr(h_before), L.ptr(c_before)
+        for k, x in list(carry.items()) + list(tables.items()):
+            assert x.is_contiguous() and x.dtype == torch.float32, k
+        p.n_step, p.advance = int(n_step), int(advance)
+        p.carry_obs, p.carry_act, p.carry_rew = L.ptr(carry['obs']), L.ptr(carry['actions']), L.ptr(carry['rewards'])
+        p.carry_pd, p.carry_cells = L.ptr(carry['pds']), L.ptr(carry.get('cells'))
+        p.obs, p.obs_next, p.actions = L.ptr(tables['obs']), L.ptr(tables['obs_next']), L.ptr(tables['actions'])
+        p.rewards, p.dones, p.pds = L.ptr(tables['rewards']), L.ptr(tables['dones']), L.ptr(tables['pds'])
+        p.cells = L.ptr(tables.get('cells'))
+        p.cursor, p.capacity = int(cursor), int(tables['obs'].shape[0])
+        L.call('smx_synth_ppo_window_rollout_f32', ctypes.byref(p), self._st())
+
     def synth_ddpg_rollout_supported(self, net):
         return bool(self.lib.smx_synth_ddpg_rollout_supported(net.D, net.H1, net.H2, net.OUT))
 

@@ -89,6 +89,33 @@ class FIFOReplay(Replay):
         self._count += n
         self.cumulative_collected_count += n
 
+    def reserve_ring(self, rows, shapes, dtypes=None):
+        """zero-copy insertion of `rows` experiences that may wrap: -> (tables, cursor, capacity), tables = {field:
+        [capacity, width] device table} (created here on first use, like insert_batch) for a producer that writes row i
+        < rows at (cursor + i) % capacity itself (SyntheticVecEnv.ppo_rollout_into); commit_ring(rows) then appends
+        them as insert_batch of the same rows would, the oldest dropped on overflow.  dtypes: {field: torch dtype} for
+        the fields whose table is not fp32"""
+        cap = self.memory_size + 3
+        if rows > cap:
+            raise ValueError('reserve_ring: %d rows do not fit a ring of %d' % (rows, cap))
+        dtypes = dict(dtypes or {})
+        tables = self._ensure_tables(cap, {k: torch.empty((0,) + tuple(s), dtype=dtypes.get(k, torch.float32))
+                                           for k, s in shapes.items()})
+        for k, s in shapes.items():
+            if k not in tables or tables[k].shape != tuple(s) or tables[k].dtype != dtypes.get(k, torch.float32):
+                raise ValueError('reserve_ring: field %r %s %s does not match the replay table'
+                                 % (k, tuple(s), dtypes.get(k, torch.float32)))
+        return {k: tables[k].data for k in shapes}, (self._head + self._count) % cap, cap
+
+    def commit_ring(self, rows):
+        """the `rows` rows written after reserve_ring: head, count and counters as insert_batch moves them"""
+        cap = self.memory_size + 3
+        assert 0 <= rows <= cap
+        overflow = max(0, self._count + rows - cap)
+        self._head = (self._head + overflow) % cap
+        self._count = min(cap, self._count + rows)
+        self.cumulative_collected_count += rows
+
     def sample_batch(self, batch_size, copy=True):
         """pops the `batch_size` oldest device-tier experiences -> {name: [batch, ...]}.
         copy=False returns VIEWS of the table when the popped rows are contiguous: valid until the
