@@ -1215,6 +1215,65 @@ struct smx_ddpg_pixel_step {           /* (by tag: no typedef) */
 int smx_synth_ddpg_pixel_step(const struct smx_ddpg_pixel_step* args, const float* mu, int64_t ld_mu,
                               smx_stream_t stream);
 
+/* ONE step of PPO's moving windows for actors with a camera (the reference's pixel PPO configuration: FrameStackWrapper,
+ * surreal/env/wrapper.py:407-472, in front of the CNN stem; PPOAgent.act, surreal/agent/ppo_agent.py:106-154; the
+ * windows of ExpSenderWrapperMultiStepMovingWindowWithInfo, surreal/env/exp_sender_wrapper.py:153-264), given the
+ * policy mean mu [n, A] (row stride ld_mu) of the layers before it -- the per-step record launch of the windowed
+ * rollout whose perception, LSTM step and actor run between two of them.  Per actor a, tau = t, N = n_step,
+ * adv = advance, S = frame_stacks, F = C*H*W, Hd = hist_len >= N + S, p = hist_pos:
+ *   head:   sd = exp(log_var) * noise_scale[a] (noise_scale NULL: 1), action = clip(eps * sd + mu, -1, 1) (eps NULL:
+ *           clip(mu)), pd = [mu | sd]                                        (smx_diaggauss_sample_f32's expressions)
+ *   step:   smx_synth_env_step_f32's dynamics, state in / out (init_state after the terminal step)
+ *   rings:  slot tau % N of carry_obs / carry_act / carry_rew / carry_pd <- the state before the step, the action, the
+ *           reward, the pd; when tau % adv == 0 and h_before / c_before [n, hidden] are given, slot
+ *           (tau / adv) % ceil(N / adv) of carry_cells <- them (smx_synth_ppo_window_rollout's layout and slot rule)
+ *   frames: the history and stacking rule of smx_synth_ddpg_pixel_step: new = frame(tau + 1, s'_0);
+ *           tau + 1 < L:  hist[a, (p + 1) mod Hd] = new, obs_pixel[a] = stacked(tau + 1); else the new episode's first
+ *           frame frame(0, init_state[a, 0]) there and S times in obs_pixel[a]
+ *   window j = tau + 1 - N closes when j >= 0 and j % adv == 0, into row (cursor + a) % capacity (the caller advances
+ *           cursor by n per closing step): obs [N, D], actions [N, A], rewards [N], pds [N, 2A] out of the rings in
+ *           episode order, dones [N] 0 but the last (1 when tau + 1 >= L), obs_next [D] the observation after the step
+ *           (the terminal one), cells [2, hidden] from the ring slot of j (cells NULL: not written),
+ *           pixel [N, S*F] = stacked(j + u) for window step u, pixel_next [S*F] = stacked(tau + 1)
+ * so the caller's next call passes t = tau + 1 (0 after L) and p = (p + 1) mod Hd.  The frames read (steps
+ * tau - N - S + 2 .. tau) never share a slot with the one written.  A <= SMX_PPO_PIXEL_STEP_MAX_A
+ * (SMX_E_UNSUPPORTED), n <= capacity, n <= 65535.  copy_workgroups: the workgroups per actor that move frames (0: sized
+ * by the bytes this step moves -- a closing step has (N + 1) S - 1 destination frames more than any other). */
+#define SMX_PPO_PIXEL_STEP_MAX_A 64
+struct smx_synth_ppo_pixel_window_step {   /* (by tag: no typedef) */
+    int32_t n, D, A, hidden;               /* hidden: the LSTM's units (0: a policy without one) */
+    int32_t t, episode_len, n_step, advance;
+    const float* log_var;                  /* [A] */
+    const float* noise_scale;              /* [n] or NULL */
+    const float* eps;                      /* [n, A] standard normals, or NULL (the deterministic agent modes) */
+    float* state;                          /* [n, D] in / out */
+    const float* init_state;
+    const float* h_before;                 /* [n, hidden] the LSTM state the step started from, or NULL */
+    const float* c_before;
+    float* carry_obs;
+    float* carry_act;
+    float* carry_rew;
+    float* carry_pd;
+    float* carry_cells;                    /* NULL without an LSTM */
+    float* obs;
+    float* obs_next;
+    float* actions;
+    float* rewards;
+    float* dones;
+    float* pds;
+    float* cells;                          /* NULL without an LSTM */
+    int64_t cursor, capacity;
+    int32_t C, H, W, frame_stacks;
+    int32_t hist_len, hist_pos;
+    int32_t copy_workgroups, reserved;
+    uint8_t* hist;                         /* [n, Hd, F] */
+    uint8_t* pixel;                        /* [capacity, N, S*F] */
+    uint8_t* pixel_next;                   /* [capacity, S*F] */
+    uint8_t* obs_pixel;                    /* [n, S*F] */
+};
+int smx_synth_ppo_pixel_window_step(const struct smx_synth_ppo_pixel_window_step* args, const float* mu, int64_t ld_mu,
+                                    smx_stream_t stream);
+
 /* ---------------------------------------------------------------------------
  * Data-parallel exchange between the learner ranks of one node over IPC-mapped peer buffers (xGMI loads): the
  * collectives N sharded learners need to equal the single reference learner -- the per-epoch

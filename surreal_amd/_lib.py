@@ -191,7 +191,20 @@ class DdpgPixelStep(Structure):
                 ('pixel_next', c_void_p), ('obs_pixel', c_void_p)]
 
 
+class SynthPpoPixelWindowStep(Structure):
+    """struct smx_synth_ppo_pixel_window_step"""
+    _fields_ = ([(n, c_int32) for n in ('n', 'D', 'A', 'hidden', 't', 'episode_len', 'n_step', 'advance')] +
+                [(n, c_void_p) for n in ('log_var', 'noise_scale', 'eps', 'state', 'init_state', 'h_before', 'c_before',
+                                         'carry_obs', 'carry_act', 'carry_rew', 'carry_pd', 'carry_cells', 'obs',
+                                         'obs_next', 'actions', 'rewards', 'dones', 'pds', 'cells')] +
+                [('cursor', c_int64), ('capacity', c_int64)] +
+                [(n, c_int32) for n in ('C', 'H', 'W', 'frame_stacks', 'hist_len', 'hist_pos', 'copy_workgroups',
+                                        'reserved')] +
+                [(n, c_void_p) for n in ('hist', 'pixel', 'pixel_next', 'obs_pixel')])
+
+
 SMX_DDPG_NOISE_NONE, SMX_DDPG_NOISE_GAUSSIAN, SMX_DDPG_NOISE_OU = 0, 1, 2
+SMX_PPO_PIXEL_STEP_MAX_A = 64            # the actions smx_synth_ppo_pixel_window_step takes
 
 
 class Xchg(Structure):
@@ -376,6 +389,7 @@ _SIGS = {
     'smx_synth_ddpg_rollout_f32': (c_int32, [POINTER(DdpgRollout), _P]),
     'smx_synth_ddpg_step_f32': (c_int32, [POINTER(DdpgRollout), _P, c_int64, _P]),
     'smx_synth_ddpg_pixel_step': (c_int32, [POINTER(DdpgPixelStep), _P, c_int64, _P]),
+    'smx_synth_ppo_pixel_window_step': (c_int32, [POINTER(SynthPpoPixelWindowStep), _P, c_int64, _P]),
     'smx_xchg_bytes': (c_int64, [c_int64, c_int32]),
     'smx_xchg_alloc': (c_int32, [c_int64, c_double, POINTER(c_void_p), POINTER(c_int32), _P]),
     'smx_xchg_free': (c_int32, [_P]),

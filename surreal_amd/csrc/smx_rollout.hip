@@ -25,6 +25,9 @@
 //   smx_synth_ddpg_pixel_step   the same step for actors with a camera, plus the frames: the new frame rendered into a
 //                               per-actor history, the closing transitions' stacked uint8 pixel / pixel_next into the ring,
 //                               the next acting observation (ddpg_pixel_step_kernel; the CNN perception runs between steps).
+//   smx_synth_ppo_pixel_window_step  one PPO step for actors with a camera given the policy mean: head, step, the moving
+//                               windows' carry rings and frame history, the closing windows' fields and stacked uint8
+//                               pixel / pixel_next into the FIFO's ring (ppo_pixel_window_step_kernel).
 //
 // The per-step launches the PPO rollout replaces were 3 dependent launches of ~9.5 us each (two hidden layers as GEMM
 // launches, then head + step), 384 launches for T = 128.
@@ -1143,6 +1146,174 @@ __global__ __launch_bounds__(256) void ddpg_pixel_step_kernel(DArgs G, PArgs P, 
     }
 }
 
+// ---- PPO with a camera: one step of the moving windows plus the frames ---------------------------------------------
+// The record launch of the per-step camera path (the CNN perception, the LSTM step and the actor's layers run between
+// two of them): the sampling head, the environment step, WinArgs' carry rings and -- at a closing step -- the window
+// into its FIFO row W.cursor + a, as ppo_rollout<WIN> does them; the frames as ddpg_pixel_step_kernel does, with the
+// same history (slot rule and proof above PArgs: a closing window reads the frames of steps tau - N - S + 2 .. tau, the
+// launch writes the slot of step tau + 1 - hist_len <= tau - N - S + 1).
+//
+// Grid (1 + X, n).  Workgroup (0, a): thread j < A owns action j (head, rings, the window's actions and pds), then
+// thread k owns state element k (+ 256 i), thread 0 the reward and thread j < Hl the cell pair j -- every ring value
+// is written and read back by the same thread; then all render frame tau + 1 from the next state (the terminal frame
+// on done).  Workgroups (1 .. X, a) split the other destination frames in units of U bytes: the next acting
+// observation's older frames (on done: the new episode's first frame, rendered from init_state), and at a closing
+// step the window's N S stacked frames and pixel_next's S - 1 older ones.
+struct PWArgs {
+    int n, D, A, Hl, t0, episode_len;
+    const float *log_var, *noise_scale, *eps;
+    float* state;
+    const float* init_state;
+    const float *h_before, *c_before;          // [n, Hl] the LSTM state before this step, or null
+    WinArgs W;                                 // (W.cursor: the row of actor 0 at this step)
+};
+
+template <int U>
+__global__ __launch_bounds__(256) void ppo_pixel_window_step_kernel(PWArgs G, PArgs P, const float* mu, long long ld_mu) {
+    __shared__ float s_act[SA_MAX];
+    __shared__ float s_sn0;
+    const WinArgs& W = G.W;
+    const int tid = threadIdx.x;
+    const long a = blockIdx.y;
+    const int N = W.N, S = P.S, tau = G.t0, Hd = P.hist_len, D = G.D, A = G.A;
+    const int j = tau + 1 - N;                       // the window that ends with this step, if one starts there
+    const bool wclose = j >= 0 && j % W.adv == 0, done = (tau + 1 >= G.episode_len);
+    const int wslot = tau % N, wfirst = (tau + 1) % N;
+    const long long row = wclose ? win_row(W, W.cursor, a) : 0;
+    const long long F = P.F, SF = (long long)S * F, nu = F / U;
+    unsigned char* hist_a = P.hist + (size_t)a * Hd * F;
+    const int hslot = (P.hist_pos + 1) % Hd;
+    alignas(16) unsigned char b[U];
+    if (blockIdx.x == 0) {
+        // ---- the sampling head (smx_diaggauss_sample_f32's expressions): one action per thread ----------------------
+        if (tid < A) {
+            const float m = mu[a * ld_mu + tid];
+            float sd = expf(G.log_var[tid]);
+            if (G.noise_scale) sd = sd * G.noise_scale[a];
+            float act = G.eps ? G.eps[a * A + tid] * sd + m : m;
+            if (act == act) act = fminf(fmaxf(act, -1.0f), 1.0f);
+            s_act[tid] = act;
+            float* ca = W.cact + (size_t)a * N * A + tid;
+            float* cp = W.cpd + (size_t)a * N * 2 * A + tid;
+            ca[(size_t)wslot * A] = act;
+            cp[(size_t)wslot * 2 * A] = m;
+            cp[(size_t)wslot * 2 * A + A] = sd;
+            if (wclose) {
+                float* da = W.act + (row * N) * A + tid;
+                float* dp = W.pd + (row * N) * 2 * A + tid;
+                copy_window<8, 3>(N, wfirst,
+                    [&](int s, int c) { return c == 0 ? ca[(size_t)s * A] : cp[(size_t)s * 2 * A + (c - 1) * A]; },
+                    [&](int u, int c, float v) {
+                        if (c == 0) da[(size_t)u * A] = v;
+                        else dp[(size_t)u * 2 * A + (c - 1) * A] = v;
+                    });
+            }
+        }
+        __syncthreads();
+        // ---- the environment step (smx_synth_env_step_f32's expressions), the rings, the closing window -------------
+        float* co = W.cobs + (size_t)a * N * D;
+        float sn0 = 0.f;
+        for (int k = tid; k < D; k += 256) {
+            const float s = G.state[a * D + k];
+            const float sn = synth_next(s, s_act[k % A], synth_drift(k));
+            co[(size_t)wslot * D + k] = s;
+            if (wclose) {
+                W.obs_next[row * D + k] = sn;
+                float* dst = W.obs + row * N * D + k;
+                copy_window<8, 1>(N, wfirst, [&](int s_, int) { return co[(size_t)s_ * D + k]; },
+                                  [&](int u, int, float v) { dst[(size_t)u * D] = v; });
+            }
+            if (k == 0) sn0 = sn;
+            G.state[a * D + k] = done ? G.init_state[a * D + k] : sn;
+        }
+        if (tid == 0) {
+            double q = 0.0;
+            for (int c = 0; c < A; ++c) {
+                const double v = (double)s_act[c];
+                q += v * v;
+            }
+            float* cr = W.crew + (size_t)a * N;
+            cr[wslot] = synth_reward(q, sn0);
+            if (wclose) {
+                float* dr = W.rew + row * N;
+                float* dd = W.done + row * N;
+                copy_window<8, 1>(N, wfirst, [&](int s_, int) { return cr[s_]; },
+                                  [&](int u, int, float v) {
+                                      dr[u] = v;
+                                      dd[u] = (done && u == N - 1) ? 1.0f : 0.0f;
+                                  });
+            }
+            s_sn0 = sn0;
+        }
+        if (W.ccell) {
+            const int Hl = G.Hl;
+            float* cc = W.ccell + (size_t)a * W.S * 2 * Hl;
+            for (int c = tid; c < Hl; c += 256) {
+                if (G.h_before && tau % W.adv == 0) {
+                    float* cw = cc + (size_t)((tau / W.adv) % W.S) * 2 * Hl + c;
+                    cw[0] = G.h_before[a * Hl + c];
+                    cw[Hl] = G.c_before[a * Hl + c];
+                }
+                if (wclose && W.cells) {
+                    const float* cr = cc + (size_t)((j / W.adv) % W.S) * 2 * Hl + c;
+                    float* d = W.cells + row * 2 * Hl + c;
+                    d[0] = cr[0];
+                    d[Hl] = cr[Hl];
+                }
+            }
+        }
+        __syncthreads();
+        // ---- frame tau + 1 from the next state, once, to wherever it goes -----------------------------------------
+        const int shift = synth_frame_shift(tau + 1, s_sn0);
+        unsigned char* d0 = done ? nullptr : hist_a + (size_t)hslot * F;
+        unsigned char* d1 = wclose ? P.pix_next + (size_t)row * SF + (size_t)(S - 1) * F : nullptr;
+        unsigned char* d2 = done ? nullptr : P.obs_pix + (size_t)a * SF + (size_t)(S - 1) * F;
+        for (long long v = tid; v < nu; v += 256) {
+            render_unit<U>(P, v * U, shift, b);
+            if (d0) store_unit<U>(d0 + v * U, b);
+            if (d1) store_unit<U>(d1 + v * U, b);
+            if (d2) store_unit<U>(d2 + v * U, b);
+        }
+        return;
+    }
+    // ---- the copies: item q < nq is one destination frame -------------------------------------------------------
+    //   done:     q < 1 + S: the new episode's first frame -> history (q = 0), acting observation frame q - 1
+    //   not done: q < S - 1: acting observation frame q <- history, step tau + 2 - S + q
+    //   then (closing) N S items: frame i of window step u <- step j + u - S + 1 + i;
+    //                  S - 1 items: pixel_next frame i <- step tau + 2 - S + i          (steps < 0: step 0)
+    const int nfirst = done ? 1 + S : S - 1;
+    const int nq = nfirst + (wclose ? (N + 1) * S - 1 : 0);
+    const int shift0 = synth_frame_shift(0, G.init_state[(size_t)a * D]);
+    const long long total = (long long)nq * nu, stride = (long long)P.X * 256;
+    for (long long g = (long long)(blockIdx.x - 1) * 256 + tid; g < total; g += stride) {
+        const int q = (int)(g / nu);
+        const long long e = (g - (long long)q * nu) * U;
+        unsigned char* dst;
+        int u = 0;                                   // the source step (unless first: the new episode's first frame)
+        const bool first = done && q < nfirst;
+        if (q < nfirst) {
+            if (done) dst = q == 0 ? hist_a + (size_t)hslot * F : P.obs_pix + (size_t)a * SF + (size_t)(q - 1) * F;
+            else { dst = P.obs_pix + (size_t)a * SF + (size_t)q * F; u = tau + 2 - S + q; }
+        } else if (q < nfirst + N * S) {
+            const int i = q - nfirst;                // = (window step) S + (stacked frame)
+            dst = P.pix + (size_t)row * N * SF + (size_t)i * F;
+            u = j + i / S - S + 1 + i % S;
+        } else {
+            const int i = q - nfirst - N * S;
+            dst = P.pix_next + (size_t)row * SF + (size_t)i * F;
+            u = tau + 2 - S + i;
+        }
+        if (first) {
+            render_unit<U>(P, e, shift0, b);
+        } else {
+            u = u < 0 ? 0 : u;
+            const int hs = ((P.hist_pos - tau + u) % Hd + Hd) % Hd;
+            load_unit<U>(hist_a + (size_t)hs * F + e, b);
+        }
+        store_unit<U>(dst + e, b);
+    }
+}
+
 // ---- host side -------------------------------------------------------------------------------------------------------
 
 inline int rr64(int v) { return (v + 63) & ~63; }
@@ -1550,6 +1721,65 @@ extern "C" int smx_synth_ddpg_pixel_step(const struct smx_ddpg_pixel_step* args,
     const dim3 grid(1 + P.X, a->n);
     if (vec) hipLaunchKernelGGL(ddpg_pixel_step_kernel<16>, grid, dim3(256), 0, smx_s(stream), G, P, mu, (long long)ld_mu);
     else hipLaunchKernelGGL(ddpg_pixel_step_kernel<1>, grid, dim3(256), 0, smx_s(stream), G, P, mu, (long long)ld_mu);
+    SMX_LAUNCH_CHECK();
+    return SMX_OK;
+}
+
+extern "C" int smx_synth_ppo_pixel_window_step(const struct smx_synth_ppo_pixel_window_step* args, const float* mu,
+                                               int64_t ld_mu, smx_stream_t stream) {
+    SMX_REQUIRE(args && mu && args->log_var && args->state && args->init_state, SMX_E_NULL);
+    SMX_REQUIRE(args->carry_obs && args->carry_act && args->carry_rew && args->carry_pd, SMX_E_NULL);
+    SMX_REQUIRE(args->obs && args->obs_next && args->actions && args->rewards && args->dones && args->pds, SMX_E_NULL);
+    SMX_REQUIRE(args->hist && args->pixel && args->pixel_next && args->obs_pixel, SMX_E_NULL);
+    SMX_REQUIRE((args->h_before == nullptr) == (args->c_before == nullptr), SMX_E_NULL);
+    // an LSTM policy's cells: the ring whenever a state comes in or a window's cells go out
+    SMX_REQUIRE((!args->h_before && !args->cells) || args->carry_cells, SMX_E_NULL);
+    SMX_REQUIRE(args->n > 0 && args->n <= 65535 && args->D > 0 && args->A > 0 && args->hidden >= 0, SMX_E_SHAPE);
+    SMX_REQUIRE(!args->carry_cells || args->hidden > 0, SMX_E_SHAPE);
+    SMX_REQUIRE(args->A <= SMX_PPO_PIXEL_STEP_MAX_A, SMX_E_UNSUPPORTED);
+    SMX_REQUIRE(ld_mu >= args->A, SMX_E_SHAPE);
+    SMX_REQUIRE(args->episode_len > 0 && args->t >= 0 && args->t < args->episode_len, SMX_E_SHAPE);
+    SMX_REQUIRE(args->n_step > 0 && args->advance > 0 && args->advance <= args->n_step, SMX_E_SHAPE);
+    SMX_REQUIRE(args->capacity > 0 && args->cursor >= 0 && args->cursor < args->capacity, SMX_E_SHAPE);
+    SMX_REQUIRE((long long)args->n <= args->capacity, SMX_E_SHAPE);       // (one row per actor: all distinct)
+    SMX_REQUIRE(args->C > 0 && args->H > 0 && args->W > 0 && args->frame_stacks > 0, SMX_E_SHAPE);
+    SMX_REQUIRE(args->hist_len >= args->n_step + args->frame_stacks && args->hist_pos >= 0 &&
+                    args->hist_pos < args->hist_len, SMX_E_SHAPE);
+    SMX_REQUIRE(args->copy_workgroups >= 0 && args->copy_workgroups <= 1024, SMX_E_SHAPE);
+    static_assert(SMX_PPO_PIXEL_STEP_MAX_A <= SA_MAX, "the action tile of the step kernels");
+    PWArgs G;
+    memset(&G, 0, sizeof(G));
+    G.n = args->n; G.D = args->D; G.A = args->A; G.Hl = args->hidden; G.t0 = args->t; G.episode_len = args->episode_len;
+    G.log_var = args->log_var; G.noise_scale = args->noise_scale; G.eps = args->eps;
+    G.state = args->state; G.init_state = args->init_state;
+    G.h_before = args->h_before; G.c_before = args->c_before;
+    WinArgs& W = G.W;
+    W.N = args->n_step; W.adv = args->advance; W.S = (W.N + W.adv - 1) / W.adv;
+    W.cobs = args->carry_obs; W.cact = args->carry_act; W.crew = args->carry_rew; W.cpd = args->carry_pd;
+    W.ccell = args->carry_cells;
+    W.obs = args->obs; W.obs_next = args->obs_next; W.act = args->actions; W.rew = args->rewards; W.done = args->dones;
+    W.pd = args->pds; W.cells = args->cells;
+    W.cursor = args->cursor; W.capacity = args->capacity;
+    PArgs P;
+    memset(&P, 0, sizeof(P));
+    P.C = args->C; P.H = args->H; P.W = args->W; P.S = args->frame_stacks;
+    P.hist_len = args->hist_len; P.hist_pos = args->hist_pos;
+    P.F = (long long)args->C * args->H * args->W;
+    P.hist = args->hist; P.pix = args->pixel; P.pix_next = args->pixel_next; P.obs_pix = args->obs_pixel;
+    // the copy workgroups of an actor, per step: ~32 KB each of the destination frames THIS step has -- (N + 1) S - 1
+    // more at a closing step than the S - 1 (S + 1 on done) of any other
+    const int j = args->t + 1 - args->n_step;
+    const bool wclose = j >= 0 && j % args->advance == 0, done = args->t + 1 >= args->episode_len;
+    const long long items = (done ? 1 + P.S : P.S - 1) + (wclose ? (long long)(W.N + 1) * P.S - 1 : 0);
+    const long long X = (items * P.F + 32767) / 32768;
+    P.X = args->copy_workgroups ? args->copy_workgroups : (int)(X < 1 ? 1 : (X > 64 ? 64 : X));
+    const bool vec = P.F % 16 == 0 && (((uintptr_t)P.hist | (uintptr_t)P.pix | (uintptr_t)P.pix_next |
+                                        (uintptr_t)P.obs_pix) & 15) == 0;
+    const dim3 grid(1 + P.X, args->n);
+    if (vec) hipLaunchKernelGGL(ppo_pixel_window_step_kernel<16>, grid, dim3(256), 0, smx_s(stream), G, P, mu,
+                                (long long)ld_mu);
+    else hipLaunchKernelGGL(ppo_pixel_window_step_kernel<1>, grid, dim3(256), 0, smx_s(stream), G, P, mu,
+                            (long long)ld_mu);
     SMX_LAUNCH_CHECK();
     return SMX_OK;
 }

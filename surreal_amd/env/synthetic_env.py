@@ -19,6 +19,7 @@ Dynamics (all fp32, no fused multiply-add):
     done   = (t + 1 >= episode_len)
 """
 import collections
+import types
 
 import numpy as np
 import torch
@@ -321,11 +322,28 @@ class SyntheticVecEnv(object):
     def _ppo_window_refusal(self, agent):
         """why ppo_rollout_into cannot take `agent` -> (exception class, message), or None"""
         m = agent.model
-        if self.pixel is not None or m.if_pixel:
-            return NotImplementedError, 'ppo_rollout_into: camera observations are not supported (low-dimensional only)'
+        if (self.pixel is not None) != bool(m.if_pixel):
+            return NotImplementedError, ('ppo_rollout_into: a camera on one side only (env %s, agent %s); both or neither'
+                                         % ('camera' if self.pixel else 'low-dimensional',
+                                            'camera' if m.if_pixel else 'low-dimensional'))
         if agent.rnn_config.if_rnn_policy and agent.rnn_config.rnn_layer != 1:
             return NotImplementedError, ('ppo_rollout_into: rnn_layer %d; the windowed rollout runs one LSTM layer'
                                          % agent.rnn_config.rnn_layer)
+        if m.if_pixel:
+            if getattr(self.K, 'synth_ppo_pixel_window_step', None) is None:
+                return NotImplementedError, 'ppo_rollout_into: the kernels object has no synth_ppo_pixel_window_step'
+            C, H, W = self.pixel
+            S = self.frame_stacks
+            cam = tuple(int(v) for v in agent.obs_spec['pixel']['camera0'])
+            if cam != (S * C, H, W):
+                return ValueError, ('ppo_rollout_into: the agent\'s camera0 %s is not the env\'s stacked frame %s'
+                                    % (cam, (S * C, H, W)))
+            if m.low_dim != self.D:
+                return ValueError, 'ppo_rollout_into: the agent\'s low_dim %d is not the env\'s %d' % (m.low_dim, self.D)
+            if not self.K.synth_ppo_pixel_window_step_supported(self.A):
+                return ValueError, ('ppo_rollout_into: %d actions; the camera step launch takes A <= %d '
+                                    '(SMX_PPO_PIXEL_STEP_MAX_A)' % (self.A, L.SMX_PPO_PIXEL_STEP_MAX_A))
+            return None
         if getattr(self.K, 'synth_ppo_window_rollout', None) is None:
             return NotImplementedError, 'ppo_rollout_into: the kernels object has no synth_ppo_window_rollout'
         if not self.K.synth_ppo_window_rollout_supported(m):
@@ -336,7 +354,8 @@ class SyntheticVecEnv(object):
 
     def can_ppo_rollout_into(self, agent):
         """ppo_rollout_into() takes `agent`: a plain-MLP or one-layer LSTM policy on low-dimensional observations whose
-        shapes the windowed kernel takes"""
+        shapes the windowed kernel takes, or a camera policy (CNN stem, with or without one LSTM layer) on an env with
+        the same camera"""
         return self._ppo_window_refusal(agent) is None
 
     def ppo_rollout_into(self, agent, replay, T, eps=None, actors_per_workgroup=0):
@@ -349,7 +368,12 @@ class SyntheticVecEnv(object):
         agent._batch_cells (zeros when None) and is left there after the last step (batch_cells_before: the state
         before it), as act_batch leaves it; it is never reset at episode ends, as in the reference.
         eps [T, n, A] standard normals (default: drawn here in one launch; deterministic agent modes use none);
-        actors_per_workgroup: 4 | 8 | 16 forces the kernel's block (0: automatic; every block size gives the same bits)."""
+        actors_per_workgroup: 4 | 8 | 16 forces the kernel's block (0: automatic; every block size gives the same bits).
+        A camera agent on a camera env (frame_stacks S) runs step by step instead (_ppo_pixel_steps): the perception of
+        the stacked frames (PPOModel.perception_into), one LSTM step, the actor, and ONE launch
+        (smx_synth_ppo_pixel_window_step) that samples, steps, keeps the carry rings and a history of n_step + S raw
+        frames per actor, and writes the closing windows with their uint8 'pixel' [n_step, S*C, H, W] / 'pixel_next'
+        [1, S*C, H, W] into the ring.  The history carries from call to call like the open windows."""
         refusal = self._ppo_window_refusal(agent)
         if refusal is not None:
             raise refusal[0](refusal[1])
@@ -362,8 +386,9 @@ class SyntheticVecEnv(object):
         N, adv = int(algo.n_step), window_advance(algo.n_step, algo.stride)
         rnn = bool(agent.rnn_config.if_rnn_policy)
         Hl = m.rnn_hidden_logical if rnn else 0
+        camera = bool(m.if_pixel)
         c = self._ppo
-        key = (N, adv, D, A, Hl)
+        key = (N, adv, D, A, Hl) + ((self.pixel, self.frame_stacks) if camera else ())
         if c.get('key') != key or c.get('t') != self.t:
             if self.t != 0:
                 raise ValueError('ppo_rollout_into: the open windows of clock %d are not held (the environments were '
@@ -387,7 +412,15 @@ class SyntheticVecEnv(object):
                   'pds': (N, 2 * A)}
         if rnn:
             shapes['cells'] = (2, 1, Hl)
-        tables, cursor, _ = replay.reserve_ring(rows, shapes)
+        dtypes = None
+        if camera:
+            if n > replay.memory_size + 3:      # (the step launch gives every actor a row of its own)
+                raise ValueError('ppo_rollout_into: %d actors exceed the FIFO capacity %d' % (n, replay.memory_size + 3))
+            C, H, W = self.pixel
+            S = self.frame_stacks
+            shapes.update(pixel=(N, S * C, H, W), pixel_next=(1, S * C, H, W))
+            dtypes = {'pixel': torch.uint8, 'pixel_next': torch.uint8}
+        tables, cursor, cap = replay.reserve_ring(rows, shapes, dtypes)
         deterministic = agent.agent_mode in ('eval_deterministic', 'eval_deterministic_local')
         if deterministic:
             eps = None
@@ -396,6 +429,11 @@ class SyntheticVecEnv(object):
                 eps = torch.randn(T, n, A, device=self.device)
             assert tuple(eps.shape) == (T, n, A)
             eps = eps.contiguous()
+        if camera:
+            self._ppo_pixel_steps(agent, T, N, adv, tables, cursor, cap, eps)
+            replay.commit_ring(rows)
+            c['t'] = self.t
+            return rows
         if getattr(self, '_pk', None) is None or self._pk.numel() != K.epoch_packed_numel(m.actor):
             self._pk = torch.zeros(K.epoch_packed_numel(m.actor), device=self.device)
         K.epoch_pack([(m.actor, self._pk)])          # (every call: the agent's parameters change between chunks)
@@ -423,6 +461,79 @@ class SyntheticVecEnv(object):
         replay.commit_ring(rows)
         self.t = c['t'] = t
         return rows
+
+    def _ppo_pixel_steps(self, agent, T, N, adv, tables, cursor, cap, eps):
+        """ppo_rollout_into's camera path: per step perception -> [one LSTM step ->] actor -> the record launch.  The
+        history (hist [n, N + S, C, H, W], the current step's frame in slot hist_pos) lives with the carry rings in
+        self._ppo and is primed with them (first use, after reset()) as _ddpg_pixel_steps primes it; the perception's
+        and the LSTM's buffers are cached across steps and calls."""
+        K, n, c, m = self.K, self.n, self._ppo, agent.model
+        C, H, W = self.pixel
+        S = self.frame_stacks
+        Hd = N + S
+        rnn = bool(m.if_rnn)
+        Hp, Hl = (m.rnn_hidden, m.rnn_hidden_logical) if rnn else (0, 0)
+        if c.get('hist') is None:
+            c['hist'] = torch.zeros((n, Hd, C, H, W), device=self.device, dtype=torch.uint8)
+            c['obs_pixel'] = torch.zeros((n, S * C, H, W), device=self.device, dtype=torch.uint8)
+            for h in range(Hd):
+                K.synth_frames(self.state[:, 0], self.t, c['hist'][:, h])
+            K.frame_stack(c['hist'], S, 0, 1, 1, 1, c['obs_pixel'])
+            c['hist_pos'] = 0
+        actor, p = m.actor, m.cnn
+        key = (n, m.stem_in, p.C, p.H, p.W, p.c1, p.c2, p.feat, Hp, Hl, actor.H1, actor.H2, actor.OUT)
+        w = getattr(self, '_ppo_ws', None)
+        if w is None or w.key != key:
+            f = lambda *s: torch.empty(*s, device=self.device)  # noqa: E731
+            w = self._ppo_ws = types.SimpleNamespace(
+                key=key, perc=m.perception_workspace(n, self.device), x=f(n, m.stem_in), h1=f(n, actor.H1),
+                h2=f(n, actor.H2), mean=f(n, actor.OUT))
+            if rnn:
+                w.gates, w.out, w.cs = f(n, 4 * Hp), f(n, Hp), f(n, Hp)
+                w.hc = [(torch.zeros(n, Hp, device=self.device), torch.zeros(n, Hp, device=self.device))
+                        for _ in range(2)]
+                w.before = (f(n, Hl), f(n, Hl)) if Hl != Hp else None
+        r = dict(state=self.state, init_state=self.init_state, episode_len=self.episode_len, n_step=N, advance=adv,
+                 log_var=m.log_var.view(-1), noise_scale=agent.batch_noise(n).view(-1), carry=c['carry'], tables=tables,
+                 cursor=cursor, hist=c['hist'], obs_pixel=c['obs_pixel'])
+        cur = 0
+        if rnn:
+            # the state the agent holds (zeros when none) into the padded buffers; a padded unit stays exactly zero
+            # (its weights are zeros, PPOModel.__init__)
+            cells = agent._batch_cells
+            for buf, src in zip(w.hc[0], cells if cells is not None and cells[0].shape[1] == n else (None, None)):
+                buf.zero_()
+                if src is not None:
+                    buf[:, :Hl].copy_(src.reshape(n, Hl))
+        for s in range(T):
+            m.perception_into(c['obs_pixel'], self.state, w.perc, w.x)
+            feat = w.x
+            if rnn:
+                (h, cc), (hn, cn) = w.hc[cur], w.hc[1 - cur]
+                K.lstm_forward(m.rnn, w.x, n, 1, h, cc, w.gates, w.out, w.cs, None, hn, cn)
+                if w.before is not None:                       # (the step launch reads [n, Hl] rows)
+                    w.before[0].copy_(h[:, :Hl])
+                    w.before[1].copy_(cc[:, :Hl])
+                    r['h_before'], r['c_before'] = w.before
+                else:
+                    r['h_before'], r['c_before'] = h, cc
+                cur = 1 - cur
+                feat = w.out
+            K.mlp3_forward(actor, feat, w.h1, w.h2, w.mean, L.SMX_ACT_TANH)
+            r['t'], r['hist_pos'] = self.t, c['hist_pos']
+            r['eps'] = None if eps is None else eps[s]
+            K.synth_ppo_pixel_window_step(r, w.mean)
+            c['hist_pos'] = (c['hist_pos'] + 1) % Hd
+            j = self.t + 1 - N
+            if j >= 0 and j % adv == 0:
+                r['cursor'] = (r['cursor'] + n) % cap
+            self.t = 0 if self.t + 1 >= self.episode_len else self.t + 1
+        if rnn:
+            # as act_batch leaves them: the final state and the state before the last step, (1, n, Hl) each, the
+            # agent's own tensors (the buffers here are written again by the next call)
+            own = lambda x: x[:, :Hl].clone().view(1, n, Hl)  # noqa: E731
+            agent._batch_cells = tuple(own(x) for x in w.hc[cur])
+            agent.batch_cells_before = tuple(own(x) for x in w.hc[1 - cur])
 
     def ddpg_rollout_into(self, agent, replay, T, eps=None, sigmas=None, actors_per_workgroup=0, reference=False):
         """T steps of all actors under DDPGAgent `agent` (act: actor -> clip -> exploration noise -> clip,

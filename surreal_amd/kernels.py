@@ -816,6 +816,62 @@ class HipKernels(object):
         p.pixel, p.pixel_next = L.ptr(tabs['pixel']), L.ptr(tabs['pixel_next'])
         L.call('smx_synth_ddpg_pixel_step', ctypes.byref(p), L.ptr(mu), _row_stride(mu, A), self._st())
 
+    @staticmethod
+    def synth_ppo_pixel_window_step_supported(A):
+        """the actions smx_synth_ppo_pixel_window_step takes (one thread each, A <= SMX_PPO_PIXEL_STEP_MAX_A)"""
+        return 0 < A <= L.SMX_PPO_PIXEL_STEP_MAX_A
+
+    def synth_ppo_pixel_window_step(self, r, mu, copy_workgroups=0):
+        """ONE step of the windowed PPO rollout for actors with a camera given the policy mean mu [n, A] (row-strided
+        view allowed): head, environment step, carry rings, frame history and -- at a closing step -- the windows into
+        the FIFO's ring from row r['cursor'] (include/surreal_amd.h smx_synth_ppo_pixel_window_step).  r: state /
+        init_state [n, D], t, episode_len, n_step, advance, log_var [A], noise_scale [n] or None, eps [n, A] or None,
+        h_before / c_before [n, Hl] or None, carry {'obs', 'actions', 'rewards', 'pds' (, 'cells')}, tables (the ring by
+        replay field name, 'pixel' [capacity, n_step * S*C*H*W] and 'pixel_next' [capacity, S*C*H*W] uint8 among
+        them), cursor, hist uint8 [n, Hd, C, H, W] (the current step's frame in slot hist_pos), obs_pixel uint8
+        [n, S*C, H, W] (receives the stacked observation of the next step)"""
+        n, Hd, C, H, W = r['hist'].shape
+        D, A = r['state'].shape[1], mu.shape[1]
+        tabs, carry = r['tables'], r['carry']
+        S = r['obs_pixel'].shape[1] // C
+        N = int(r['n_step'])
+        cap = tabs['obs'].shape[0]
+        for k in ('hist', 'obs_pixel'):
+            assert r[k].dtype == torch.uint8 and r[k].is_contiguous(), k
+        assert tuple(r['obs_pixel'].shape) == (n, S * C, H, W) and r['state'].shape[0] == n
+        for k, w in (('pixel', N * S * C * H * W), ('pixel_next', S * C * H * W)):
+            assert tabs[k].dtype == torch.uint8 and tabs[k].is_contiguous() and tuple(tabs[k].shape) == (cap, w), k
+        for k, x in list(carry.items()) + [(k, x) for k, x in tabs.items() if k not in ('pixel', 'pixel_next')]:
+            assert x.is_contiguous() and x.dtype == torch.float32, k
+        assert tuple(tabs['obs'].shape) == (cap, N * D) and tuple(carry['obs'].shape) == (n, N, D)
+        hb, cb = r.get('h_before'), r.get('c_before')
+        Hl = 0
+        if 'cells' in carry:
+            Hl = carry['cells'].shape[-1]
+            assert tuple(carry['cells'].shape) == (n, -(-N // int(r['advance'])), 2, Hl)
+            for x in (hb, cb):
+                assert x is None or (x.is_contiguous() and x.numel() == n * Hl)
+            assert 'cells' not in tabs or tabs['cells'].shape[1] == 2 * Hl
+        if r.get('eps') is not None:
+            assert r['eps'].is_contiguous() and tuple(r['eps'].shape) == (n, A)
+        p = L.SynthPpoPixelWindowStep()
+        p.n, p.D, p.A, p.hidden = n, D, A, Hl
+        p.t, p.episode_len, p.n_step, p.advance = int(r['t']), int(r['episode_len']), N, int(r['advance'])
+        p.log_var, p.noise_scale, p.eps = L.ptr(r['log_var']), L.ptr(r.get('noise_scale')), L.ptr(r.get('eps'))
+        p.state, p.init_state = L.ptr(r['state']), L.ptr(r['init_state'])
+        p.h_before, p.c_before = L.ptr(hb), L.ptr(cb)
+        p.carry_obs, p.carry_act, p.carry_rew = L.ptr(carry['obs']), L.ptr(carry['actions']), L.ptr(carry['rewards'])
+        p.carry_pd, p.carry_cells = L.ptr(carry['pds']), L.ptr(carry.get('cells'))
+        p.obs, p.obs_next, p.actions = L.ptr(tabs['obs']), L.ptr(tabs['obs_next']), L.ptr(tabs['actions'])
+        p.rewards, p.dones, p.pds = L.ptr(tabs['rewards']), L.ptr(tabs['dones']), L.ptr(tabs['pds'])
+        p.cells = L.ptr(tabs.get('cells'))
+        p.cursor, p.capacity = int(r['cursor']), cap
+        p.C, p.H, p.W, p.frame_stacks = C, H, W, S
+        p.hist_len, p.hist_pos, p.copy_workgroups = Hd, int(r['hist_pos']), int(copy_workgroups)
+        p.hist, p.obs_pixel = L.ptr(r['hist']), L.ptr(r['obs_pixel'])
+        p.pixel, p.pixel_next = L.ptr(tabs['pixel']), L.ptr(tabs['pixel_next'])
+        L.call('smx_synth_ppo_pixel_window_step', ctypes.byref(p), L.ptr(mu), _row_stride(mu, A), self._st())
+
     def synth_env_step(self, state, init_state, actions, t, episode_len, slot, obs_roll, act_roll,
                        rew_roll, done_roll):
         n, D = state.shape

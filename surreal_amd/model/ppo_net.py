@@ -9,6 +9,7 @@ is a single launch and a data-parallel gradient all-reduce is a single collectiv
 """
 import collections
 import ctypes
+import types
 
 import numpy as np
 import torch
@@ -340,6 +341,25 @@ class PPOModel(object):
         out = torch.empty(rows, net.OUT, device=x.device)
         self.K.mlp3_forward(net, x2, h1, h2, out, out_act)
         return out, shape
+
+    def perception_workspace(self, rows, device):
+        """what perception_into needs for `rows` observations: the CNN stem's forward workspace and the filtered
+        low-dimensional part (the caller keeps it across steps)"""
+        return types.SimpleNamespace(cnn=CnnStem.workspace(self.cnn, rows, device, backward=False),
+                                     z=torch.empty(rows, self.low_dim, device=device))
+
+    def perception_into(self, pixel, low_dim, ws, x):
+        """x [rows, low_dim + cnn_feature_dim] = [z-filter(low_dim) | CNN(pixel / 255)]: the stem input _stem forms
+        (ppo_net.py:268-275) for an acting step, the z-filter from the running sums in one launch, nothing allocated.
+        pixel uint8 [rows, S*C, H, W] contiguous, low_dim [rows, low_dim], ws: perception_workspace(rows)"""
+        rows, D = x.shape[0], self.low_dim
+        if self.use_z_filter:
+            zf = self.z_filter
+            self.K.zfilter_forward_sums(low_dim, zf.running_sum, zf.running_sumsq, zf.count, zf.eps, ws.z)
+            x[:, :D].copy_(ws.z)
+        else:
+            x[:, :D].copy_(low_dim)
+        self._cnn_stem.forward(self.cnn, pixel, rows, ws.cnn, x[:, D:])
 
     def _stem(self, obs, cells, want_cells=False):
         """low-dim concat -> z-filter -> [LSTM]  (ppo_net.py:262-279).  With the LSTM stem the
