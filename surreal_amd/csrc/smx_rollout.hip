@@ -29,6 +29,11 @@
 //                               windows' carry rings and frame history, the closing windows' fields and stacked uint8
 //                               pixel / pixel_next into the FIFO's ring (ppo_pixel_window_step_kernel).
 //
+// Layout: the persistent kernels (PPO, then DDPG), the step kernels (the two camera ones share their frame half:
+// frame_ctx / render_next_frame / copy_frames), then the host side: carve() and launch(), the argument fills (net_fields,
+// roll_fields, table_fields, lstm_fields, win_fields, pixel_fields), the rules the entry points share (*_ok, *_pointers),
+// the entry points.
+//
 // The per-step launches the PPO rollout replaces were 3 dependent launches of ~9.5 us each (two hidden layers as GEMM
 // launches, then head + step), 384 launches for T = 128.
 //
@@ -1074,19 +1079,96 @@ __device__ __forceinline__ void load_unit(const unsigned char* src, unsigned cha
     }
 }
 
+// The frame half of both camera step kernels.  An actor's frames at step tau:
+struct FrameCtx {
+    long long F, SF, nu;                       // bytes per frame, per stacked observation; units of U bytes per frame
+    unsigned char *hist_a, *hnew;              // the actor's history; its slot for the frame of step tau + 1
+    int tau;
+    bool done;
+};
+
+template <int U>
+__device__ __forceinline__ FrameCtx frame_ctx(const PArgs& P, long a, int tau, bool done) {
+    FrameCtx C;
+    C.F = P.F; C.SF = (long long)P.S * P.F; C.nu = P.F / U;
+    C.hist_a = P.hist + (size_t)a * P.hist_len * P.F;
+    C.hnew = C.hist_a + (size_t)((P.hist_pos + 1) % P.hist_len) * P.F;
+    C.tau = tau; C.done = done;
+    return C;
+}
+
+// workgroup 0's tail: frame tau + 1 from the next state (sn0), rendered once and stored wherever it goes: the history
+// and the next acting observation's last frame (not on done), at a closing step pixel_next's last frame of ring row `row`
+template <int U>
+__device__ __forceinline__ void render_next_frame(const PArgs& P, const FrameCtx& C, long a, float sn0, bool closing,
+                                                  long long row) {
+    const int shift = synth_frame_shift(C.tau + 1, sn0);
+    const size_t last = (size_t)(P.S - 1) * C.F;
+    unsigned char* d0 = C.done ? nullptr : C.hnew;
+    unsigned char* d1 = closing ? P.pix_next + (size_t)row * C.SF + last : nullptr;
+    unsigned char* d2 = C.done ? nullptr : P.obs_pix + (size_t)a * C.SF + last;
+    alignas(16) unsigned char b[U];
+    for (long long v = threadIdx.x; v < C.nu; v += 256) {
+        render_unit<U>(P, v * U, shift, b);
+        if (d0) store_unit<U>(d0 + v * U, b);
+        if (d1) store_unit<U>(d1 + v * U, b);
+        if (d2) store_unit<U>(d2 + v * U, b);
+    }
+}
+
+// the copy workgroups (blockIdx.x >= 1): item q < nq is one destination frame
+//   done:     q < 1 + S: the new episode's first frame (rendered from s0 = init_state[a][0]) -> history (q = 0), acting
+//             observation frame q - 1
+//   not done: q < S - 1: acting observation frame q <- history, step tau + 2 - S + q
+//   then at a closing step the kernel's npix items -- pixel(i, dst, u): destination and source step of item i -- and
+//   S - 1 items: pixel_next frame i of ring row `row` <- step tau + 2 - S + i                  (steps < 0: step 0)
+template <int U, typename Pixel>
+__device__ __forceinline__ void copy_frames(const PArgs& P, const FrameCtx& C, long a, float s0, bool closing,
+                                            long long row, int npix, Pixel pixel) {
+    const int S = P.S, tau = C.tau, Hd = P.hist_len;
+    const long long F = C.F, SF = C.SF, nu = C.nu;
+    const int nfirst = C.done ? 1 + S : S - 1;
+    const int nq = nfirst + (closing ? npix + S - 1 : 0);
+    const int shift0 = synth_frame_shift(0, s0);
+    const long long total = (long long)nq * nu, stride = (long long)P.X * 256;
+    alignas(16) unsigned char b[U];
+    for (long long g = (long long)(blockIdx.x - 1) * 256 + threadIdx.x; g < total; g += stride) {
+        const int q = (int)(g / nu);
+        const long long e = (g - (long long)q * nu) * U;
+        unsigned char* dst;
+        int u = 0;                                   // the source step (unless first: the new episode's first frame)
+        const bool first = C.done && q < nfirst;
+        if (q < nfirst) {
+            if (C.done) dst = q == 0 ? C.hnew : P.obs_pix + (size_t)a * SF + (size_t)(q - 1) * F;
+            else { dst = P.obs_pix + (size_t)a * SF + (size_t)q * F; u = tau + 2 - S + q; }
+        } else if (q < nfirst + npix) {
+            pixel(q - nfirst, dst, u);
+        } else {
+            const int i = q - nfirst - npix;
+            dst = P.pix_next + (size_t)row * SF + (size_t)i * F;
+            u = tau + 2 - S + i;
+        }
+        if (first) {
+            render_unit<U>(P, e, shift0, b);
+        } else {
+            u = u < 0 ? 0 : u;
+            const int hs = ((P.hist_pos - tau + u) % Hd + Hd) % Hd;
+            load_unit<U>(C.hist_a + (size_t)hs * F + e, b);
+        }
+        store_unit<U>(dst + e, b);
+    }
+}
+
 template <int U>
 __global__ __launch_bounds__(256) void ddpg_pixel_step_kernel(DArgs G, PArgs P, const float* mu, long long ld_mu) {
     __shared__ float s_act[SA_MAX];
     __shared__ float s_sn0;
     const int tid = threadIdx.x, lane = tid & 63;
     const long a = blockIdx.y;
-    const int N = G.N, S = P.S, tau = G.t0, Hd = P.hist_len;
-    const bool emit = tau >= N - 1, done = (tau + 1 >= G.episode_len);
+    const int N = G.N, S = P.S, tau = G.t0;
+    const bool emit = tau >= N - 1;
     const long long row = emit ? ring_row(G, 0, a) : 0;
-    const long long F = P.F, SF = (long long)S * F, nu = F / U;
-    unsigned char* hist_a = P.hist + (size_t)a * Hd * F;
-    const int wslot = (P.hist_pos + 1) % Hd;
-    alignas(16) unsigned char b[U];
+    const FrameCtx C = frame_ctx<U>(P, a, tau, tau + 1 >= G.episode_len);
     if (blockIdx.x == 0) {
         // ---- the low-dimensional step, then frame tau + 1 from the next state ----------------------------------
         if (tid < 64 && lane < G.A) ddpg_step_act(G, mu, ld_mu, a, lane, row, s_act);
@@ -1096,54 +1178,15 @@ __global__ __launch_bounds__(256) void ddpg_pixel_step_kernel(DArgs G, PArgs P, 
             if (lane == 0) s_sn0 = sn0;
         }
         __syncthreads();
-        const int shift = synth_frame_shift(tau + 1, s_sn0);
-        unsigned char* d0 = done ? nullptr : hist_a + (size_t)wslot * F;
-        unsigned char* d1 = emit ? P.pix_next + (size_t)row * SF + (size_t)(S - 1) * F : nullptr;
-        unsigned char* d2 = done ? nullptr : P.obs_pix + (size_t)a * SF + (size_t)(S - 1) * F;
-        for (long long v = tid; v < nu; v += 256) {
-            render_unit<U>(P, v * U, shift, b);
-            if (d0) store_unit<U>(d0 + v * U, b);
-            if (d1) store_unit<U>(d1 + v * U, b);
-            if (d2) store_unit<U>(d2 + v * U, b);
-        }
+        render_next_frame<U>(P, C, a, s_sn0, emit, row);
         return;
     }
-    // ---- the copies: item q < nq is one destination frame -------------------------------------------------------
-    //   done:     q < 1 + S: the new episode's first frame -> history (q = 0), acting observation frame q - 1
-    //   not done: q < S - 1: acting observation frame q <- history, step tau + 2 - S + q
-    //   then (emit) 2 S - 1 items: pixel frame i <- step j - S + 1 + i; pixel_next frame i < S - 1 <- step tau + 2 - S + i
-    const int nfirst = done ? 1 + S : S - 1;
-    const int nq = nfirst + (emit ? 2 * S - 1 : 0);
+    // the closing transition j's S items: pixel frame i <- step j - S + 1 + i
     const int j = tau - N + 1;
-    const int shift0 = synth_frame_shift(0, G.init_state[(size_t)a * G.D]);
-    const long long total = (long long)nq * nu, stride = (long long)P.X * 256;
-    for (long long g = (long long)(blockIdx.x - 1) * 256 + tid; g < total; g += stride) {
-        const int q = (int)(g / nu);
-        const long long e = (g - (long long)q * nu) * U;
-        unsigned char* dst;
-        int u = 0;                                   // the source step (unless first: the new episode's first frame)
-        const bool first = done && q < nfirst;
-        if (q < nfirst) {
-            if (done) dst = q == 0 ? hist_a + (size_t)wslot * F : P.obs_pix + (size_t)a * SF + (size_t)(q - 1) * F;
-            else { dst = P.obs_pix + (size_t)a * SF + (size_t)q * F; u = tau + 2 - S + q; }
-        } else if (q < nfirst + S) {
-            const int i = q - nfirst;
-            dst = P.pix + (size_t)row * SF + (size_t)i * F;
-            u = j - S + 1 + i;
-        } else {
-            const int i = q - nfirst - S;
-            dst = P.pix_next + (size_t)row * SF + (size_t)i * F;
-            u = tau + 2 - S + i;
-        }
-        if (first) {
-            render_unit<U>(P, e, shift0, b);
-        } else {
-            u = u < 0 ? 0 : u;
-            const int hs = ((P.hist_pos - tau + u) % Hd + Hd) % Hd;
-            load_unit<U>(hist_a + (size_t)hs * F + e, b);
-        }
-        store_unit<U>(dst + e, b);
-    }
+    copy_frames<U>(P, C, a, G.init_state[(size_t)a * G.D], emit, row, S, [&](int i, unsigned char*& dst, int& u) {
+        dst = P.pix + (size_t)row * C.SF + (size_t)i * C.F;
+        u = j - S + 1 + i;
+    });
 }
 
 // ---- PPO with a camera: one step of the moving windows plus the frames ---------------------------------------------
@@ -1175,15 +1218,12 @@ __global__ __launch_bounds__(256) void ppo_pixel_window_step_kernel(PWArgs G, PA
     const WinArgs& W = G.W;
     const int tid = threadIdx.x;
     const long a = blockIdx.y;
-    const int N = W.N, S = P.S, tau = G.t0, Hd = P.hist_len, D = G.D, A = G.A;
+    const int N = W.N, S = P.S, tau = G.t0, D = G.D, A = G.A;
     const int j = tau + 1 - N;                       // the window that ends with this step, if one starts there
     const bool wclose = j >= 0 && j % W.adv == 0, done = (tau + 1 >= G.episode_len);
     const int wslot = tau % N, wfirst = (tau + 1) % N;
     const long long row = wclose ? win_row(W, W.cursor, a) : 0;
-    const long long F = P.F, SF = (long long)S * F, nu = F / U;
-    unsigned char* hist_a = P.hist + (size_t)a * Hd * F;
-    const int hslot = (P.hist_pos + 1) % Hd;
-    alignas(16) unsigned char b[U];
+    const FrameCtx C = frame_ctx<U>(P, a, tau, done);
     if (blockIdx.x == 0) {
         // ---- the sampling head (smx_diaggauss_sample_f32's expressions): one action per thread ----------------------
         if (tid < A) {
@@ -1264,54 +1304,14 @@ __global__ __launch_bounds__(256) void ppo_pixel_window_step_kernel(PWArgs G, PA
         }
         __syncthreads();
         // ---- frame tau + 1 from the next state, once, to wherever it goes -----------------------------------------
-        const int shift = synth_frame_shift(tau + 1, s_sn0);
-        unsigned char* d0 = done ? nullptr : hist_a + (size_t)hslot * F;
-        unsigned char* d1 = wclose ? P.pix_next + (size_t)row * SF + (size_t)(S - 1) * F : nullptr;
-        unsigned char* d2 = done ? nullptr : P.obs_pix + (size_t)a * SF + (size_t)(S - 1) * F;
-        for (long long v = tid; v < nu; v += 256) {
-            render_unit<U>(P, v * U, shift, b);
-            if (d0) store_unit<U>(d0 + v * U, b);
-            if (d1) store_unit<U>(d1 + v * U, b);
-            if (d2) store_unit<U>(d2 + v * U, b);
-        }
+        render_next_frame<U>(P, C, a, s_sn0, wclose, row);
         return;
     }
-    // ---- the copies: item q < nq is one destination frame -------------------------------------------------------
-    //   done:     q < 1 + S: the new episode's first frame -> history (q = 0), acting observation frame q - 1
-    //   not done: q < S - 1: acting observation frame q <- history, step tau + 2 - S + q
-    //   then (closing) N S items: frame i of window step u <- step j + u - S + 1 + i;
-    //                  S - 1 items: pixel_next frame i <- step tau + 2 - S + i          (steps < 0: step 0)
-    const int nfirst = done ? 1 + S : S - 1;
-    const int nq = nfirst + (wclose ? (N + 1) * S - 1 : 0);
-    const int shift0 = synth_frame_shift(0, G.init_state[(size_t)a * D]);
-    const long long total = (long long)nq * nu, stride = (long long)P.X * 256;
-    for (long long g = (long long)(blockIdx.x - 1) * 256 + tid; g < total; g += stride) {
-        const int q = (int)(g / nu);
-        const long long e = (g - (long long)q * nu) * U;
-        unsigned char* dst;
-        int u = 0;                                   // the source step (unless first: the new episode's first frame)
-        const bool first = done && q < nfirst;
-        if (q < nfirst) {
-            if (done) dst = q == 0 ? hist_a + (size_t)hslot * F : P.obs_pix + (size_t)a * SF + (size_t)(q - 1) * F;
-            else { dst = P.obs_pix + (size_t)a * SF + (size_t)q * F; u = tau + 2 - S + q; }
-        } else if (q < nfirst + N * S) {
-            const int i = q - nfirst;                // = (window step) S + (stacked frame)
-            dst = P.pix + (size_t)row * N * SF + (size_t)i * F;
-            u = j + i / S - S + 1 + i % S;
-        } else {
-            const int i = q - nfirst - N * S;
-            dst = P.pix_next + (size_t)row * SF + (size_t)i * F;
-            u = tau + 2 - S + i;
-        }
-        if (first) {
-            render_unit<U>(P, e, shift0, b);
-        } else {
-            u = u < 0 ? 0 : u;
-            const int hs = ((P.hist_pos - tau + u) % Hd + Hd) % Hd;
-            load_unit<U>(hist_a + (size_t)hs * F + e, b);
-        }
-        store_unit<U>(dst + e, b);
-    }
+    // the closing window's N S items: frame i % S of window step i / S <- step j + i / S - S + 1 + i % S
+    copy_frames<U>(P, C, a, G.init_state[(size_t)a * D], wclose, row, N * S, [&](int i, unsigned char*& dst, int& u) {
+        dst = P.pix + (size_t)row * N * C.SF + (size_t)i * C.F;
+        u = j + i / S - S + 1 + i % S;
+    });
 }
 
 // ---- host side -------------------------------------------------------------------------------------------------------
@@ -1414,6 +1414,14 @@ int launch(const Args& G, int rb, int lds, smx_stream_t stream) {
     return SMX_OK;
 }
 
+// the same for a block of rb = 4 | 8 | 16 actors: each has its own instantiation
+template <auto K4, auto K8, auto K16, typename Args>
+int launch(const Args& G, int rb, int lds, smx_stream_t stream) {
+    if (rb == 4) return launch<K4>(G, rb, lds, stream);
+    if (rb == 8) return launch<K8>(G, rb, lds, stream);
+    return launch<K16>(G, rb, lds, stream);
+}
+
 // the fields both DDPG entry points take from the argument block
 int common_args(const smx_ddpg_rollout_t* a, DArgs& G) {
     SMX_REQUIRE(a && a->state && a->init_state && a->gpow && a->carry_obs && a->carry_act && a->carry_rew, SMX_E_NULL);
@@ -1436,41 +1444,136 @@ int common_args(const smx_ddpg_rollout_t* a, DArgs& G) {
     return SMX_OK;
 }
 
-// closing steps among `steps` steps from clock t
-long long emitting_steps(int t, int steps, int episode_len, int N) {
+// the steps among `steps` steps from clock t whose clock `closes` accepts
+template <typename Closes>
+long long closing_steps(int t, int steps, int episode_len, Closes closes) {
     long long m = 0;
     for (int s = 0; s < steps; ++s) {
-        if (t >= N - 1) ++m;
+        if (closes(t)) ++m;
         t = (t + 1 >= episode_len) ? 0 : t + 1;
     }
     return m;
 }
 
-// closing steps of moving windows (n_step N, advance adv) among `steps` steps from clock t
-long long window_closing_steps(int t, int steps, int episode_len, int N, int adv) {
-    long long m = 0;
-    for (int s = 0; s < steps; ++s) {
-        const int j = t + 1 - N;
-        if (j >= 0 && j % adv == 0) ++m;
-        t = (t + 1 >= episode_len) ? 0 : t + 1;
-    }
-    return m;
+// a moving window (n_step N, advance adv) closes at clock t
+inline bool window_closes(int t, int N, int adv) { return t + 1 >= N && (t + 1 - N) % adv == 0; }
+
+// ---- the argument blocks -> the kernels' arguments -----------------------------------------------------------------
+
+// the actor of every persistent kernel: the packed weights' three layers, the biases, the hidden widths
+void net_fields(const smx_mlp3_t& n, const float* packed, RollBase& G) {
+    G.P1 = packed;
+    G.P2 = packed + 4 * pack_off(n.D, n.H1, n.H2, n.OUT, 1);
+    G.P3 = packed + 4 * pack_off(n.D, n.H1, n.H2, n.OUT, 2);
+    G.b1 = n.b1; G.b2 = n.b2; G.b3 = n.b3; G.H1 = n.H1; G.H2 = n.H2;
 }
 
-// the fields of a PPO rollout's argument block the windowed kernels take (the rollout tables, slot and rows_per_actor
-// are not used)
+// every PPO kernel's network, shapes (D: the observation's width), head, z-filter, state and clock
 void roll_fields(const smx_synth_rollout_t* a, int D, RollArgs& G) {
-    const smx_mlp3_t& n = *a->net;
-    G.P1 = a->packed;
-    G.P2 = a->packed + 4 * pack_off(n.D, n.H1, n.H2, n.OUT, 1);
-    G.P3 = a->packed + 4 * pack_off(n.D, n.H1, n.H2, n.OUT, 2);
-    G.b1 = n.b1; G.b2 = n.b2; G.b3 = n.b3;
-    G.D = D; G.H1 = n.H1; G.H2 = n.H2; G.A = n.OUT; G.out_act = a->out_act;
+    net_fields(*a->net, a->packed, G);
+    G.D = D; G.A = a->net->OUT; G.out_act = a->out_act;
     G.log_var = a->log_var; G.noise_scale = a->noise_scale; G.eps = a->eps;
     G.zsum = a->zsum; G.zsumsq = a->zsumsq; G.zcount = a->zcount; G.zeps = a->zeps;
     G.state = a->state; G.init_state = a->init_state;
     G.n = a->n; G.t0 = a->t; G.episode_len = a->episode_len; G.steps = a->steps;
 }
+
+// the rollout tables (the windowed kernels have none)
+void table_fields(const smx_synth_rollout_t* a, RollArgs& G) {
+    G.R = a->rows_per_actor; G.slot0 = a->slot;
+    G.obs_roll = a->obs_roll; G.act_roll = a->act_roll; G.rew_roll = a->rew_roll; G.done_roll = a->done_roll;
+    G.pd_roll = a->pd_roll; G.obs_last = a->obs_last;
+}
+
+// the LSTM stem (cell_roll apart: the rollout tables' kernel alone records it)
+void lstm_fields(const smx_synth_lstm_rollout& b, LArgs& G) {
+    const smx_lstm_t& l = *b.lstm;
+    G.H = l.H; G.Hl = b.hidden;
+    G.Pg = b.lstm_packed; G.bg = b.lstm_packed + pack_words(4 * l.H, lstm_dp(l.D) + l.H) * 4;
+    G.h0 = b.h0; G.c0 = b.c0; G.hN = b.hN; G.cN = b.cN; G.h_before = b.h_before; G.c_before = b.c_before;
+}
+
+// the moving windows of either windowed argument block
+template <typename Block>
+WinArgs win_fields(const Block& a) {
+    WinArgs W;
+    memset(&W, 0, sizeof(W));
+    W.N = a.n_step; W.adv = a.advance; W.S = (W.N + W.adv - 1) / W.adv;
+    W.cobs = a.carry_obs; W.cact = a.carry_act; W.crew = a.carry_rew; W.cpd = a.carry_pd; W.ccell = a.carry_cells;
+    W.obs = a.obs; W.obs_next = a.obs_next; W.act = a.actions; W.rew = a.rewards; W.done = a.dones; W.pd = a.pds;
+    W.cells = a.cells; W.cursor = a.cursor; W.capacity = a.capacity;
+    return W;
+}
+
+// the camera of either step argument block, with X copy workgroups per actor: ~32 KB each of `frames` destination frames
+template <typename Block>
+PArgs pixel_fields(const Block& a, long long frames) {
+    PArgs P;
+    memset(&P, 0, sizeof(P));
+    P.C = a.C; P.H = a.H; P.W = a.W; P.S = a.frame_stacks; P.hist_len = a.hist_len; P.hist_pos = a.hist_pos;
+    P.F = (long long)a.C * a.H * a.W;
+    P.hist = a.hist; P.pix = a.pixel; P.pix_next = a.pixel_next; P.obs_pix = a.obs_pixel;
+    const long long X = (frames * P.F + 32767) / 32768;
+    P.X = (int)(X < 1 ? 1 : (X > 64 ? 64 : X));
+    return P;
+}
+
+// a camera step kernel on the grid (1 + X, n): K16 copies 16 bytes a lane where the frame size and every frame buffer
+// allow it, else K1 single bytes
+template <auto K16, auto K1, typename Args>
+int launch_pixel(const Args& G, const PArgs& P, int n, const float* mu, int64_t ld_mu, smx_stream_t stream) {
+    const bool vec = P.F % 16 == 0 && (((uintptr_t)P.hist | (uintptr_t)P.pix | (uintptr_t)P.pix_next |
+                                        (uintptr_t)P.obs_pix) & 15) == 0;
+    hipLaunchKernelGGL(vec ? K16 : K1, dim3(1 + P.X, n), dim3(256), 0, smx_s(stream), G, P, mu, (long long)ld_mu);
+    SMX_LAUNCH_CHECK();
+    return SMX_OK;
+}
+
+// ---- the rules the entry points share (the SMX_REQUIRE at the call names the code) ---------------------------------
+
+bool block_ok(int apw) { return apw == 0 || apw == 4 || apw == 8 || apw == 16; }      // actors_per_workgroup
+bool roll_pointers(const smx_synth_rollout_t* a) { return a->net && a->packed && a->log_var && a->state && a->init_state; }
+// the z-filter's running sums: all three or none
+bool zfilter_ok(const smx_synth_rollout_t* a) {
+    return (a->zsum == nullptr) == (a->zsumsq == nullptr) && (a->zsum == nullptr) == (a->zcount == nullptr);
+}
+// the packed weights on 16 bytes (lstm_packed: null where there is no stem), the biases on 4
+bool aligned_ok(const float* packed, const float* b1, const float* lstm_packed) {
+    return (((uintptr_t)packed | (uintptr_t)lstm_packed) & 15) == 0 && ((uintptr_t)b1 & 3) == 0;
+}
+// sizes, block size, and slot + steps within the tables' rows whenever one of them (`cells`: the LSTM's) is recorded:
+// every roll table is indexed by slot + step, so the bound holds whichever of them is
+bool rollout_shape_ok(const smx_synth_rollout_t* a, const void* cells) {
+    const bool records = a->obs_roll || a->act_roll || a->rew_roll || a->done_roll || a->pd_roll || cells;
+    return a->n > 0 && a->steps > 0 && a->episode_len > 0 && a->rows_per_actor > 0 && block_ok(a->actors_per_workgroup) &&
+           a->slot >= 0 && (!records || a->slot + a->steps <= a->rows_per_actor);
+}
+bool cell_pairs_ok(const float* h0, const float* c0, const float* h_before, const float* c_before) {
+    return (h_before == nullptr) == (c_before == nullptr) && (h0 == nullptr) == (c0 == nullptr);
+}
+// the actor reads the stem's output; `hidden` logical units of the H padded ones (padding < 4)
+bool lstm_shape_ok(const smx_mlp3_t& n, const smx_lstm_t& l, int hidden) {
+    return n.D == l.H && hidden > 0 && hidden <= l.H && l.H - hidden < 4;
+}
+template <typename Block>
+bool window_pointers(const Block& a) {
+    return a.carry_obs && a.carry_act && a.carry_rew && a.carry_pd && a.obs && a.obs_next && a.actions && a.rewards &&
+           a.dones && a.pds;
+}
+template <typename Block>
+bool window_shape_ok(const Block& a) {
+    return a.n_step > 0 && a.advance > 0 && a.advance <= a.n_step && a.capacity > 0 && a.cursor >= 0 && a.cursor < a.capacity;
+}
+// the frame buffers, the frame, and a history long enough that no launch reads the slot it writes (proof above PArgs)
+template <typename Block>
+bool pixel_pointers(const Block& a) { return a.hist && a.pixel && a.pixel_next && a.obs_pixel; }
+template <typename Block>
+bool pixel_shape_ok(const Block& a, int n_step) {
+    return a.C > 0 && a.H > 0 && a.W > 0 && a.frame_stacks > 0 && a.hist_len >= n_step + a.frame_stacks &&
+           a.hist_pos >= 0 && a.hist_pos < a.hist_len;
+}
+// what the step launches ask of mu [n, A] (ld_mu) and of the ring: one row per actor, all distinct
+bool step_shape_ok(int n, int A, int64_t ld_mu, long long capacity) { return A <= SA_MAX && ld_mu >= A && n <= capacity; }
 
 }  // namespace
 
@@ -1484,35 +1587,19 @@ extern "C" int32_t smx_synth_rollout_supported(int32_t D, int32_t H1, int32_t H2
 }
 
 extern "C" int smx_synth_rollout_f32(const smx_synth_rollout_t* a, smx_stream_t stream) {
-    SMX_REQUIRE(a && a->net && a->packed && a->log_var && a->state && a->init_state, SMX_E_NULL);
+    SMX_REQUIRE(a && roll_pointers(a), SMX_E_NULL);
     const smx_mlp3_t& n = *a->net;
     SMX_REQUIRE(smx_synth_rollout_supported(n.D, n.H1, n.H2, n.OUT), SMX_E_UNSUPPORTED);
-    SMX_REQUIRE(a->n > 0 && a->steps > 0 && a->episode_len > 0 && a->rows_per_actor > 0, SMX_E_SHAPE);
-    SMX_REQUIRE(a->actors_per_workgroup == 0 || a->actors_per_workgroup == 4 || a->actors_per_workgroup == 8 ||
-                a->actors_per_workgroup == 16, SMX_E_SHAPE);
-    // (every roll table is indexed by slot + step: the bound holds whichever of them is recorded)
-    const bool records = a->obs_roll || a->act_roll || a->rew_roll || a->done_roll || a->pd_roll;
-    SMX_REQUIRE(a->slot >= 0 && (!records || a->slot + a->steps <= a->rows_per_actor), SMX_E_SHAPE);
-    SMX_REQUIRE(((uintptr_t)a->packed & 15) == 0 && ((uintptr_t)n.b1 & 3) == 0, SMX_E_ALIGN);
-    SMX_REQUIRE((a->zsum == nullptr) == (a->zsumsq == nullptr) && (a->zsum == nullptr) == (a->zcount == nullptr), SMX_E_NULL);
+    SMX_REQUIRE(rollout_shape_ok(a, nullptr), SMX_E_SHAPE);
+    SMX_REQUIRE(aligned_ok(a->packed, n.b1, nullptr), SMX_E_ALIGN);
+    SMX_REQUIRE(zfilter_ok(a), SMX_E_NULL);
     RollArgs G;
     memset(&G, 0, sizeof(G));
-    G.P1 = a->packed;
-    G.P2 = a->packed + 4 * pack_off(n.D, n.H1, n.H2, n.OUT, 1);
-    G.P3 = a->packed + 4 * pack_off(n.D, n.H1, n.H2, n.OUT, 2);
-    G.b1 = n.b1; G.b2 = n.b2; G.b3 = n.b3;
-    G.D = n.D; G.H1 = n.H1; G.H2 = n.H2; G.A = n.OUT; G.out_act = a->out_act;
-    G.log_var = a->log_var; G.noise_scale = a->noise_scale; G.eps = a->eps;
-    G.zsum = a->zsum; G.zsumsq = a->zsumsq; G.zcount = a->zcount; G.zeps = a->zeps;
-    G.state = a->state; G.init_state = a->init_state;
-    G.n = a->n; G.t0 = a->t; G.episode_len = a->episode_len; G.steps = a->steps; G.R = a->rows_per_actor; G.slot0 = a->slot;
-    G.obs_roll = a->obs_roll; G.act_roll = a->act_roll; G.rew_roll = a->rew_roll; G.done_roll = a->done_roll;
-    G.pd_roll = a->pd_roll; G.obs_last = a->obs_last;
+    roll_fields(a, n.D, G);
+    table_fields(a, G);
     const int rb = pick_block(a->actors_per_workgroup, a->n);
     const int lds = carve(G, rb, /*mma16=*/rb == 16, /*split_out=*/true, /*ztables=*/true, G.D);
-    if (rb == 4) return launch<rollout_kernel<1>>(G, rb, lds, stream);
-    if (rb == 8) return launch<rollout_kernel<2>>(G, rb, lds, stream);
-    return launch<rollout16_kernel>(G, rb, lds, stream);
+    return launch<rollout_kernel<1>, rollout_kernel<2>, rollout16_kernel>(G, rb, lds, stream);
 }
 
 extern "C" int32_t smx_synth_lstm_rollout_supported(int32_t D, int32_t H, int32_t H1, int32_t H2, int32_t A) {
@@ -1542,44 +1629,24 @@ extern "C" int smx_lstm_rollout_pack_f32(const smx_lstm_t* net, float* packed, s
 extern "C" int smx_synth_lstm_rollout_f32(const smx_synth_lstm_rollout* args, smx_stream_t stream) {
     SMX_REQUIRE(args && args->lstm && args->lstm_packed && args->hN && args->cN, SMX_E_NULL);
     const smx_synth_rollout_t* a = &args->roll;
-    SMX_REQUIRE(a->net && a->packed && a->log_var && a->state && a->init_state, SMX_E_NULL);
-    SMX_REQUIRE((args->h_before == nullptr) == (args->c_before == nullptr), SMX_E_NULL);
-    SMX_REQUIRE((args->h0 == nullptr) == (args->c0 == nullptr), SMX_E_NULL);
+    SMX_REQUIRE(roll_pointers(a), SMX_E_NULL);
+    SMX_REQUIRE(cell_pairs_ok(args->h0, args->c0, args->h_before, args->c_before), SMX_E_NULL);
     const smx_mlp3_t& n = *a->net;
     const smx_lstm_t& l = *args->lstm;
-    SMX_REQUIRE(n.D == l.H && args->hidden > 0 && args->hidden <= l.H && l.H - args->hidden < 4, SMX_E_SHAPE);
+    SMX_REQUIRE(lstm_shape_ok(n, l, args->hidden), SMX_E_SHAPE);
     SMX_REQUIRE(smx_synth_lstm_rollout_supported(l.D, l.H, n.H1, n.H2, n.OUT), SMX_E_UNSUPPORTED);
-    SMX_REQUIRE(a->n > 0 && a->steps > 0 && a->episode_len > 0 && a->rows_per_actor > 0, SMX_E_SHAPE);
-    SMX_REQUIRE(a->actors_per_workgroup == 0 || a->actors_per_workgroup == 4 || a->actors_per_workgroup == 8 ||
-                a->actors_per_workgroup == 16, SMX_E_SHAPE);
-    const bool records = a->obs_roll || a->act_roll || a->rew_roll || a->done_roll || a->pd_roll || args->cell_roll;
-    SMX_REQUIRE(a->slot >= 0 && (!records || a->slot + a->steps <= a->rows_per_actor), SMX_E_SHAPE);
-    SMX_REQUIRE(((uintptr_t)a->packed & 15) == 0 && ((uintptr_t)n.b1 & 3) == 0, SMX_E_ALIGN);
-    SMX_REQUIRE(((uintptr_t)args->lstm_packed & 15) == 0, SMX_E_ALIGN);
-    SMX_REQUIRE((a->zsum == nullptr) == (a->zsumsq == nullptr) && (a->zsum == nullptr) == (a->zcount == nullptr), SMX_E_NULL);
+    SMX_REQUIRE(rollout_shape_ok(a, args->cell_roll), SMX_E_SHAPE);
+    SMX_REQUIRE(aligned_ok(a->packed, n.b1, args->lstm_packed), SMX_E_ALIGN);
+    SMX_REQUIRE(zfilter_ok(a), SMX_E_NULL);
     LArgs G;
     memset(&G, 0, sizeof(G));
-    G.P1 = a->packed;
-    G.P2 = a->packed + 4 * pack_off(n.D, n.H1, n.H2, n.OUT, 1);
-    G.P3 = a->packed + 4 * pack_off(n.D, n.H1, n.H2, n.OUT, 2);
-    G.b1 = n.b1; G.b2 = n.b2; G.b3 = n.b3;
-    G.D = l.D; G.H1 = n.H1; G.H2 = n.H2; G.A = n.OUT; G.out_act = a->out_act;
-    G.log_var = a->log_var; G.noise_scale = a->noise_scale; G.eps = a->eps;
-    G.zsum = a->zsum; G.zsumsq = a->zsumsq; G.zcount = a->zcount; G.zeps = a->zeps;
-    G.state = a->state; G.init_state = a->init_state;
-    G.n = a->n; G.t0 = a->t; G.episode_len = a->episode_len; G.steps = a->steps; G.R = a->rows_per_actor; G.slot0 = a->slot;
-    G.obs_roll = a->obs_roll; G.act_roll = a->act_roll; G.rew_roll = a->rew_roll; G.done_roll = a->done_roll;
-    G.pd_roll = a->pd_roll; G.obs_last = a->obs_last;
-    G.H = l.H; G.Hl = args->hidden;
-    G.Pg = args->lstm_packed;
-    G.bg = args->lstm_packed + pack_words(4 * l.H, lstm_dp(l.D) + l.H) * 4;
-    G.h0 = args->h0; G.c0 = args->c0; G.hN = args->hN; G.cN = args->cN;
-    G.h_before = args->h_before; G.c_before = args->c_before; G.cell_roll = args->cell_roll;
+    roll_fields(a, l.D, G);
+    table_fields(a, G);
+    lstm_fields(*args, G);
+    G.cell_roll = args->cell_roll;
     const int rb = pick_block(a->actors_per_workgroup, a->n);
     const int lds = carve_lstm(G, rb);
-    if (rb == 4) return launch<lstm_rollout_kernel<1>>(G, rb, lds, stream);
-    if (rb == 8) return launch<lstm_rollout_kernel<2>>(G, rb, lds, stream);
-    return launch<lstm_rollout_kernel<4>>(G, rb, lds, stream);
+    return launch<lstm_rollout_kernel<1>, lstm_rollout_kernel<2>, lstm_rollout_kernel<4>>(G, rb, lds, stream);
 }
 
 extern "C" int32_t smx_synth_ppo_window_rollout_supported(int32_t D, int32_t H, int32_t H1, int32_t H2, int32_t A) {
@@ -1592,64 +1659,36 @@ extern "C" int smx_synth_ppo_window_rollout_f32(const smx_synth_ppo_window_rollo
     const smx_synth_lstm_rollout& b = args->base;
     const smx_synth_rollout_t* a = &b.roll;
     const bool lstm = b.lstm != nullptr;
-    SMX_REQUIRE(a->net && a->packed && a->log_var && a->state && a->init_state, SMX_E_NULL);
-    SMX_REQUIRE(args->carry_obs && args->carry_act && args->carry_rew && args->carry_pd, SMX_E_NULL);
-    SMX_REQUIRE(args->obs && args->obs_next && args->actions && args->rewards && args->dones && args->pds, SMX_E_NULL);
+    SMX_REQUIRE(roll_pointers(a) && window_pointers(*args), SMX_E_NULL);
     SMX_REQUIRE(!lstm || (b.lstm_packed && b.hN && b.cN && args->carry_cells && args->cells), SMX_E_NULL);
-    SMX_REQUIRE((b.h_before == nullptr) == (b.c_before == nullptr), SMX_E_NULL);
-    SMX_REQUIRE((b.h0 == nullptr) == (b.c0 == nullptr), SMX_E_NULL);
-    SMX_REQUIRE((a->zsum == nullptr) == (a->zsumsq == nullptr) && (a->zsum == nullptr) == (a->zcount == nullptr), SMX_E_NULL);
+    SMX_REQUIRE(cell_pairs_ok(b.h0, b.c0, b.h_before, b.c_before) && zfilter_ok(a), SMX_E_NULL);
     const smx_mlp3_t& n = *a->net;
-    if (lstm) {
-        const smx_lstm_t& l = *b.lstm;
-        SMX_REQUIRE(n.D == l.H && b.hidden > 0 && b.hidden <= l.H && l.H - b.hidden < 4, SMX_E_SHAPE);
-        SMX_REQUIRE(smx_synth_ppo_window_rollout_supported(l.D, l.H, n.H1, n.H2, n.OUT), SMX_E_UNSUPPORTED);
-    } else {
-        SMX_REQUIRE(smx_synth_ppo_window_rollout_supported(n.D, 0, n.H1, n.H2, n.OUT), SMX_E_UNSUPPORTED);
-    }
+    SMX_REQUIRE(!lstm || lstm_shape_ok(n, *b.lstm, b.hidden), SMX_E_SHAPE);
+    SMX_REQUIRE(smx_synth_ppo_window_rollout_supported(lstm ? b.lstm->D : n.D, lstm ? b.lstm->H : 0, n.H1, n.H2, n.OUT),
+                SMX_E_UNSUPPORTED);
     SMX_REQUIRE(a->n > 0 && a->steps > 0 && a->episode_len > 0 && a->t >= 0 && a->t < a->episode_len, SMX_E_SHAPE);
-    SMX_REQUIRE(a->actors_per_workgroup == 0 || a->actors_per_workgroup == 4 || a->actors_per_workgroup == 8 ||
-                a->actors_per_workgroup == 16, SMX_E_SHAPE);
-    SMX_REQUIRE(args->n_step > 0 && args->advance > 0 && args->advance <= args->n_step, SMX_E_SHAPE);
-    SMX_REQUIRE(args->capacity > 0 && args->cursor >= 0 && args->cursor < args->capacity, SMX_E_SHAPE);
+    SMX_REQUIRE(block_ok(a->actors_per_workgroup) && window_shape_ok(*args), SMX_E_SHAPE);
     // two workgroups must never write the same FIFO row: all n m rows of the call are distinct
-    SMX_REQUIRE((long long)a->n * window_closing_steps(a->t, a->steps, a->episode_len, args->n_step, args->advance) <=
-                    args->capacity, SMX_E_SHAPE);
-    SMX_REQUIRE(((uintptr_t)a->packed & 15) == 0 && ((uintptr_t)n.b1 & 3) == 0, SMX_E_ALIGN);
-    SMX_REQUIRE(!lstm || ((uintptr_t)b.lstm_packed & 15) == 0, SMX_E_ALIGN);
-    WinArgs W;
-    memset(&W, 0, sizeof(W));
-    W.N = args->n_step; W.adv = args->advance; W.S = (W.N + W.adv - 1) / W.adv;
-    W.cobs = args->carry_obs; W.cact = args->carry_act; W.crew = args->carry_rew; W.cpd = args->carry_pd;
-    W.ccell = args->carry_cells;
-    W.obs = args->obs; W.obs_next = args->obs_next; W.act = args->actions; W.rew = args->rewards; W.done = args->dones;
-    W.pd = args->pds; W.cells = args->cells;
-    W.cursor = args->cursor; W.capacity = args->capacity;
+    const long long m = closing_steps(a->t, a->steps, a->episode_len,
+                                      [&](int t) { return window_closes(t, args->n_step, args->advance); });
+    SMX_REQUIRE((long long)a->n * m <= args->capacity, SMX_E_SHAPE);
+    SMX_REQUIRE(aligned_ok(a->packed, n.b1, lstm ? b.lstm_packed : nullptr), SMX_E_ALIGN);
     const int rb = pick_block(a->actors_per_workgroup, a->n);
     if (!lstm) {
         RollArgsW G;
         memset(&G, 0, sizeof(G));
         roll_fields(a, n.D, G);
-        G.W = W;
+        G.W = win_fields(*args);
         const int lds = carve(G, rb, /*mma16=*/false, /*split_out=*/true, /*ztables=*/true, G.D);
-        if (rb == 4) return launch<ppo_window_kernel<1>>(G, rb, lds, stream);
-        if (rb == 8) return launch<ppo_window_kernel<2>>(G, rb, lds, stream);
-        return launch<ppo_window_kernel<4>>(G, rb, lds, stream);
+        return launch<ppo_window_kernel<1>, ppo_window_kernel<2>, ppo_window_kernel<4>>(G, rb, lds, stream);
     }
-    const smx_lstm_t& l = *b.lstm;
     LArgsW G;
     memset(&G, 0, sizeof(G));
-    roll_fields(a, l.D, G);
-    G.H = l.H; G.Hl = b.hidden;
-    G.Pg = b.lstm_packed;
-    G.bg = b.lstm_packed + pack_words(4 * l.H, lstm_dp(l.D) + l.H) * 4;
-    G.h0 = b.h0; G.c0 = b.c0; G.hN = b.hN; G.cN = b.cN;
-    G.h_before = b.h_before; G.c_before = b.c_before;
-    G.W = W;
+    roll_fields(a, b.lstm->D, G);
+    lstm_fields(b, G);
+    G.W = win_fields(*args);
     const int lds = carve_lstm(G, rb);
-    if (rb == 4) return launch<lstm_window_kernel<1>>(G, rb, lds, stream);
-    if (rb == 8) return launch<lstm_window_kernel<2>>(G, rb, lds, stream);
-    return launch<lstm_window_kernel<4>>(G, rb, lds, stream);
+    return launch<lstm_window_kernel<1>, lstm_window_kernel<2>, lstm_window_kernel<4>>(G, rb, lds, stream);
 }
 
 extern "C" int32_t smx_synth_ddpg_rollout_supported(int32_t D, int32_t H1, int32_t H2, int32_t A) {
@@ -1661,23 +1700,18 @@ extern "C" int smx_synth_ddpg_rollout_f32(const smx_ddpg_rollout_t* a, smx_strea
     const smx_mlp3_t& net = *a->net;
     SMX_REQUIRE(smx_synth_ddpg_rollout_supported(net.D, net.H1, net.H2, net.OUT), SMX_E_UNSUPPORTED);
     SMX_REQUIRE(net.D == a->D && net.OUT == a->A && a->steps > 0, SMX_E_SHAPE);
-    SMX_REQUIRE(a->actors_per_workgroup == 0 || a->actors_per_workgroup == 4 || a->actors_per_workgroup == 8 ||
-                a->actors_per_workgroup == 16, SMX_E_SHAPE);
-    SMX_REQUIRE(((uintptr_t)a->packed & 15) == 0 && ((uintptr_t)net.b1 & 3) == 0, SMX_E_ALIGN);
+    SMX_REQUIRE(block_ok(a->actors_per_workgroup), SMX_E_SHAPE);
+    SMX_REQUIRE(aligned_ok(a->packed, net.b1, nullptr), SMX_E_ALIGN);
     DArgs G;
     const int rc = common_args(a, G);
     if (rc != SMX_OK) return rc;
     // two workgroups must never write the same ring row: all n m rows of the call are distinct
-    SMX_REQUIRE((long long)a->n * emitting_steps(a->t, a->steps, a->episode_len, a->n_step) <= a->capacity, SMX_E_SHAPE);
-    G.P1 = a->packed;
-    G.P2 = a->packed + 4 * pack_off(net.D, net.H1, net.H2, net.OUT, 1);
-    G.P3 = a->packed + 4 * pack_off(net.D, net.H1, net.H2, net.OUT, 2);
-    G.b1 = net.b1; G.b2 = net.b2; G.b3 = net.b3; G.H1 = net.H1; G.H2 = net.H2;
+    const long long m = closing_steps(a->t, a->steps, a->episode_len, [&](int t) { return t >= a->n_step - 1; });
+    SMX_REQUIRE((long long)a->n * m <= a->capacity, SMX_E_SHAPE);
+    net_fields(net, a->packed, G);
     const int rb = pick_block(a->actors_per_workgroup, a->n);
     const int lds = carve(G, rb, /*mma16=*/false, /*split_out=*/false, /*ztables=*/false, G.D);
-    if (rb == 4) return launch<ddpg_rollout_kernel<1, 3>>(G, rb, lds, stream);
-    if (rb == 8) return launch<ddpg_rollout_kernel<2, 3>>(G, rb, lds, stream);
-    return launch<ddpg_rollout_kernel<4, 2>>(G, rb, lds, stream);
+    return launch<ddpg_rollout_kernel<1, 3>, ddpg_rollout_kernel<2, 3>, ddpg_rollout_kernel<4, 2>>(G, rb, lds, stream);
 }
 
 extern "C" int smx_synth_ddpg_step_f32(const smx_ddpg_rollout_t* a, const float* mu, int64_t ld_mu, smx_stream_t stream) {
@@ -1685,8 +1719,7 @@ extern "C" int smx_synth_ddpg_step_f32(const smx_ddpg_rollout_t* a, const float*
     DArgs G;
     const int rc = common_args(a, G);
     if (rc != SMX_OK) return rc;
-    SMX_REQUIRE(a->A <= SA_MAX && ld_mu >= a->A, SMX_E_SHAPE);
-    SMX_REQUIRE((long long)a->n <= a->capacity, SMX_E_SHAPE);
+    SMX_REQUIRE(step_shape_ok(a->n, a->A, ld_mu, a->capacity), SMX_E_SHAPE);
     G.steps = 1;
     hipLaunchKernelGGL(ddpg_step_kernel, dim3((a->n + 3) / 4), dim3(256), 0, smx_s(stream), G, mu, (long long)ld_mu);
     SMX_LAUNCH_CHECK();
@@ -1695,91 +1728,48 @@ extern "C" int smx_synth_ddpg_step_f32(const smx_ddpg_rollout_t* a, const float*
 
 extern "C" int smx_synth_ddpg_pixel_step(const struct smx_ddpg_pixel_step* args, const float* mu, int64_t ld_mu,
                                          smx_stream_t stream) {
-    SMX_REQUIRE(args && mu && args->hist && args->pixel && args->pixel_next && args->obs_pixel, SMX_E_NULL);
+    SMX_REQUIRE(args && mu && pixel_pointers(*args), SMX_E_NULL);
     const smx_ddpg_rollout_t* a = &args->base;
     DArgs G;
     const int rc = common_args(a, G);
     if (rc != SMX_OK) return rc;
-    SMX_REQUIRE(a->A <= SA_MAX && ld_mu >= a->A, SMX_E_SHAPE);
-    SMX_REQUIRE((long long)a->n <= a->capacity && a->n <= 65535, SMX_E_SHAPE);
-    SMX_REQUIRE(args->C > 0 && args->H > 0 && args->W > 0 && args->frame_stacks > 0, SMX_E_SHAPE);
-    SMX_REQUIRE(args->hist_len >= a->n_step + args->frame_stacks && args->hist_pos >= 0 &&
-                    args->hist_pos < args->hist_len, SMX_E_SHAPE);
+    SMX_REQUIRE(step_shape_ok(a->n, a->A, ld_mu, a->capacity) && a->n <= 65535, SMX_E_SHAPE);
+    SMX_REQUIRE(pixel_shape_ok(*args, a->n_step), SMX_E_SHAPE);
     G.steps = 1;
-    PArgs P;
-    memset(&P, 0, sizeof(P));
-    P.C = args->C; P.H = args->H; P.W = args->W; P.S = args->frame_stacks;
-    P.hist_len = args->hist_len; P.hist_pos = args->hist_pos;
-    P.F = (long long)args->C * args->H * args->W;
-    P.hist = args->hist; P.pix = args->pixel; P.pix_next = args->pixel_next; P.obs_pix = args->obs_pixel;
-    // the copy workgroups of an actor: ~32 KB of the at most 3 S frames each (one frame's units per workgroup at least)
-    const long long most = 3LL * P.S * P.F;
-    long long X = (most + 32767) / 32768;
-    P.X = (int)(X < 1 ? 1 : (X > 64 ? 64 : X));
-    const bool vec = P.F % 16 == 0 && (((uintptr_t)P.hist | (uintptr_t)P.pix | (uintptr_t)P.pix_next |
-                                        (uintptr_t)P.obs_pix) & 15) == 0;
-    const dim3 grid(1 + P.X, a->n);
-    if (vec) hipLaunchKernelGGL(ddpg_pixel_step_kernel<16>, grid, dim3(256), 0, smx_s(stream), G, P, mu, (long long)ld_mu);
-    else hipLaunchKernelGGL(ddpg_pixel_step_kernel<1>, grid, dim3(256), 0, smx_s(stream), G, P, mu, (long long)ld_mu);
-    SMX_LAUNCH_CHECK();
-    return SMX_OK;
+    // (the copy workgroups: sized for the at most 3 S frames of a closing step; one frame's units each at least)
+    const PArgs P = pixel_fields(*args, 3LL * args->frame_stacks);
+    return launch_pixel<ddpg_pixel_step_kernel<16>, ddpg_pixel_step_kernel<1>>(G, P, a->n, mu, ld_mu, stream);
 }
 
 extern "C" int smx_synth_ppo_pixel_window_step(const struct smx_synth_ppo_pixel_window_step* args, const float* mu,
                                                int64_t ld_mu, smx_stream_t stream) {
     SMX_REQUIRE(args && mu && args->log_var && args->state && args->init_state, SMX_E_NULL);
-    SMX_REQUIRE(args->carry_obs && args->carry_act && args->carry_rew && args->carry_pd, SMX_E_NULL);
-    SMX_REQUIRE(args->obs && args->obs_next && args->actions && args->rewards && args->dones && args->pds, SMX_E_NULL);
-    SMX_REQUIRE(args->hist && args->pixel && args->pixel_next && args->obs_pixel, SMX_E_NULL);
-    SMX_REQUIRE((args->h_before == nullptr) == (args->c_before == nullptr), SMX_E_NULL);
+    SMX_REQUIRE(window_pointers(*args) && pixel_pointers(*args), SMX_E_NULL);
+    SMX_REQUIRE(cell_pairs_ok(nullptr, nullptr, args->h_before, args->c_before), SMX_E_NULL);
     // an LSTM policy's cells: the ring whenever a state comes in or a window's cells go out
     SMX_REQUIRE((!args->h_before && !args->cells) || args->carry_cells, SMX_E_NULL);
     SMX_REQUIRE(args->n > 0 && args->n <= 65535 && args->D > 0 && args->A > 0 && args->hidden >= 0, SMX_E_SHAPE);
     SMX_REQUIRE(!args->carry_cells || args->hidden > 0, SMX_E_SHAPE);
     SMX_REQUIRE(args->A <= SMX_PPO_PIXEL_STEP_MAX_A, SMX_E_UNSUPPORTED);
-    SMX_REQUIRE(ld_mu >= args->A, SMX_E_SHAPE);
-    SMX_REQUIRE(args->episode_len > 0 && args->t >= 0 && args->t < args->episode_len, SMX_E_SHAPE);
-    SMX_REQUIRE(args->n_step > 0 && args->advance > 0 && args->advance <= args->n_step, SMX_E_SHAPE);
-    SMX_REQUIRE(args->capacity > 0 && args->cursor >= 0 && args->cursor < args->capacity, SMX_E_SHAPE);
-    SMX_REQUIRE((long long)args->n <= args->capacity, SMX_E_SHAPE);       // (one row per actor: all distinct)
-    SMX_REQUIRE(args->C > 0 && args->H > 0 && args->W > 0 && args->frame_stacks > 0, SMX_E_SHAPE);
-    SMX_REQUIRE(args->hist_len >= args->n_step + args->frame_stacks && args->hist_pos >= 0 &&
-                    args->hist_pos < args->hist_len, SMX_E_SHAPE);
-    SMX_REQUIRE(args->copy_workgroups >= 0 && args->copy_workgroups <= 1024, SMX_E_SHAPE);
     static_assert(SMX_PPO_PIXEL_STEP_MAX_A <= SA_MAX, "the action tile of the step kernels");
+    SMX_REQUIRE(args->episode_len > 0 && args->t >= 0 && args->t < args->episode_len, SMX_E_SHAPE);
+    SMX_REQUIRE(window_shape_ok(*args) && step_shape_ok(args->n, args->A, ld_mu, args->capacity), SMX_E_SHAPE);
+    SMX_REQUIRE(pixel_shape_ok(*args, args->n_step), SMX_E_SHAPE);
+    SMX_REQUIRE(args->copy_workgroups >= 0 && args->copy_workgroups <= 1024, SMX_E_SHAPE);
     PWArgs G;
     memset(&G, 0, sizeof(G));
     G.n = args->n; G.D = args->D; G.A = args->A; G.Hl = args->hidden; G.t0 = args->t; G.episode_len = args->episode_len;
     G.log_var = args->log_var; G.noise_scale = args->noise_scale; G.eps = args->eps;
     G.state = args->state; G.init_state = args->init_state;
     G.h_before = args->h_before; G.c_before = args->c_before;
-    WinArgs& W = G.W;
-    W.N = args->n_step; W.adv = args->advance; W.S = (W.N + W.adv - 1) / W.adv;
-    W.cobs = args->carry_obs; W.cact = args->carry_act; W.crew = args->carry_rew; W.cpd = args->carry_pd;
-    W.ccell = args->carry_cells;
-    W.obs = args->obs; W.obs_next = args->obs_next; W.act = args->actions; W.rew = args->rewards; W.done = args->dones;
-    W.pd = args->pds; W.cells = args->cells;
-    W.cursor = args->cursor; W.capacity = args->capacity;
-    PArgs P;
-    memset(&P, 0, sizeof(P));
-    P.C = args->C; P.H = args->H; P.W = args->W; P.S = args->frame_stacks;
-    P.hist_len = args->hist_len; P.hist_pos = args->hist_pos;
-    P.F = (long long)args->C * args->H * args->W;
-    P.hist = args->hist; P.pix = args->pixel; P.pix_next = args->pixel_next; P.obs_pix = args->obs_pixel;
-    // the copy workgroups of an actor, per step: ~32 KB each of the destination frames THIS step has -- (N + 1) S - 1
-    // more at a closing step than the S - 1 (S + 1 on done) of any other
-    const int j = args->t + 1 - args->n_step;
-    const bool wclose = j >= 0 && j % args->advance == 0, done = args->t + 1 >= args->episode_len;
-    const long long items = (done ? 1 + P.S : P.S - 1) + (wclose ? (long long)(W.N + 1) * P.S - 1 : 0);
-    const long long X = (items * P.F + 32767) / 32768;
-    P.X = args->copy_workgroups ? args->copy_workgroups : (int)(X < 1 ? 1 : (X > 64 ? 64 : X));
-    const bool vec = P.F % 16 == 0 && (((uintptr_t)P.hist | (uintptr_t)P.pix | (uintptr_t)P.pix_next |
-                                        (uintptr_t)P.obs_pix) & 15) == 0;
-    const dim3 grid(1 + P.X, args->n);
-    if (vec) hipLaunchKernelGGL(ppo_pixel_window_step_kernel<16>, grid, dim3(256), 0, smx_s(stream), G, P, mu,
-                                (long long)ld_mu);
-    else hipLaunchKernelGGL(ppo_pixel_window_step_kernel<1>, grid, dim3(256), 0, smx_s(stream), G, P, mu,
-                            (long long)ld_mu);
-    SMX_LAUNCH_CHECK();
-    return SMX_OK;
+    G.W = win_fields(*args);
+    // the copy workgroups of this step: its destination frames -- (N + 1) S - 1 more at a closing step than the S - 1
+    // (S + 1 on done) of any other
+    const int S = args->frame_stacks;
+    const bool done = args->t + 1 >= args->episode_len;
+    PArgs P = pixel_fields(*args, (done ? 1 + S : S - 1) +
+                                      (window_closes(args->t, args->n_step, args->advance)
+                                           ? (long long)(args->n_step + 1) * S - 1 : 0));
+    if (args->copy_workgroups) P.X = args->copy_workgroups;
+    return launch_pixel<ppo_pixel_window_step_kernel<16>, ppo_pixel_window_step_kernel<1>>(G, P, args->n, mu, ld_mu, stream);
 }

@@ -118,6 +118,89 @@ class SyntheticVecEnv(object):
         self._ppo = {}                        # (the open windows: a new episode has none)
         return self.state
 
+    def _clock_walk(self, k):
+        """the shared clock at each of the next k steps and after them (k + 1 values): an episode ends at episode_len"""
+        ts = [self.t]
+        for _ in range(k):
+            ts.append(0 if ts[-1] + 1 >= self.episode_len else ts[-1] + 1)
+        return ts
+
+    def _advance(self, k=1):
+        self.t = self._clock_walk(k)[-1]
+
+    def _closing_steps(self, T, closes):
+        """-> (how many of the next T steps close something: closes(clock), the clock after them)"""
+        ts = self._clock_walk(T)
+        return sum(bool(closes(t)) for t in ts[:-1]), ts[-1]
+
+    def _draws(self, agent, eps, T):
+        """the standard-normal draws of T steps, [T, n, A] contiguous: `eps`, by default drawn here in one launch; None
+        in the deterministic agent modes"""
+        if agent.agent_mode in ('eval_deterministic', 'eval_deterministic_local'):
+            return None
+        if eps is None:
+            eps = torch.randn(T, self.n, self.A, device=self.device)
+        return eps.contiguous()
+
+    def _packed(self, attr, numel, pack):
+        """the cached buffer `attr` of numel floats, (re)allocated when the size changed and packed again: the agent's
+        parameters change between calls"""
+        buf = getattr(self, attr, None)
+        if buf is None or buf.numel() != numel:
+            buf = torch.zeros(numel, device=self.device)
+            setattr(self, attr, buf)
+        pack(buf)
+        return buf
+
+    def _pack_actor(self, actor):
+        return self._packed('_pk', self.K.epoch_packed_numel(actor), lambda b: self.K.epoch_pack([(actor, b)]))
+
+    def _pack_lstm(self, rnn):
+        return self._packed('_lpk', self.K.lstm_rollout_packed_numel(rnn), lambda b: self.K.lstm_rollout_pack(rnn, b))
+
+    def _cell_outputs(self, Hl):
+        """the LSTM launches' hN / cN / h_before / c_before, (1, n, Hl) each, by argument name"""
+        return {k: torch.empty(1, self.n, Hl, device=self.device) for k in ('hN', 'cN', 'h_before', 'c_before')}
+
+    @staticmethod
+    def _hand_cells(agent, c):
+        """leaves _cell_outputs' tensors where act_batch would have: the final (h, c) and the state before the last step"""
+        agent._batch_cells = (c['hN'], c['cN'])
+        agent.batch_cells_before = (c['h_before'], c['c_before'])
+
+    def _camera_refusal(self, who, agent, camera):
+        """the method `who` needs env and agent to agree on the camera -> (exception class, message), or None"""
+        if (self.pixel is not None) != camera:
+            return NotImplementedError, ('%s: a camera on one side only (env %s, agent %s); both or neither'
+                                         % (who, 'camera' if self.pixel else 'low-dimensional',
+                                            'camera' if camera else 'low-dimensional'))
+        if camera:
+            C, H, W = self.pixel
+            S = self.frame_stacks
+            cam = tuple(int(v) for v in agent.obs_spec['pixel']['camera0'])
+            if cam != (S * C, H, W):
+                return ValueError, ('%s: the agent\'s camera0 %s is not the env\'s stacked frame %s'
+                                    % (who, cam, (S * C, H, W)))
+            if agent.model.low_dim != self.D:
+                return ValueError, '%s: the agent\'s low_dim %d is not the env\'s %d' % (who, agent.model.low_dim, self.D)
+        return None
+
+    def _frame_history(self, c, Hd):
+        """the camera paths' frame history in the store dict c: 'hist' [n, Hd, C, H, W] (the current step's frame in
+        slot 'hist_pos') and 'obs_pixel', the stacked acting observation; primed on first use and after reset() with the
+        current frame in every slot, the observation that frame S times (Hd + 1 launches, once)"""
+        K, n, S = self.K, self.n, self.frame_stacks
+        C, H, W = self.pixel
+        if c.get('hist') is None or tuple(c['hist'].shape) != (n, Hd, C, H, W):
+            c['hist'] = torch.zeros((n, Hd, C, H, W), device=self.device, dtype=torch.uint8)
+            c['obs_pixel'] = torch.zeros((n, S * C, H, W), device=self.device, dtype=torch.uint8)
+            c['hist_pos'] = None
+        if c.get('hist_pos') is None:
+            for h in range(Hd):
+                K.synth_frames(self.state[:, 0], self.t, c['hist'][:, h])
+            K.frame_stack(c['hist'], S, 0, 1, 1, 1, c['obs_pixel'])
+            c['hist_pos'] = 0
+
     def start_rollout(self, T, info_width=0):
         """allocate a device rollout of T steps.  Every roll has T + 1 rows per actor (the
         observation roll needs the observation after the last step; the others leave their last
@@ -165,7 +248,7 @@ class SyntheticVecEnv(object):
         else:
             self.K.synth_env_step(self.state, self.init_state, actions, self.t, self.episode_len, 0,
                                   None, None, None, None)
-        self.t = 0 if self.t + 1 >= self.episode_len else self.t + 1
+        self._advance()
         return self.state
 
     def rollout(self, agent, eps=None, actors_per_workgroup=0):
@@ -181,13 +264,11 @@ class SyntheticVecEnv(object):
         automatic; 4 and 8 give the same bits, 16 sums the layers in another order)."""
         T, n, K = self.T, self.n, self.K
         assert self.slot == 0 and 'pds' in self.rolls, 'start_rollout(T, info_width=2 * A) first'
-        deterministic = agent.agent_mode in ('eval_deterministic', 'eval_deterministic_local')
-        if eps is None and not deterministic:
-            eps = torch.randn(T, n, self.A, device=self.device)
+        eps = self._draws(agent, eps, T)
         if agent.rnn_config.if_rnn_policy or agent.model.if_pixel:
             if self._lstm_persistent(agent):
-                return self._rollout_lstm(agent, None if deterministic else eps, actors_per_workgroup)
-            return self._rollout_stem(agent, None if deterministic else eps)
+                return self._rollout_lstm(agent, eps, actors_per_workgroup)
+            return self._rollout_stem(agent, eps)
         noise = agent.batch_noise(n).view(-1)
         zf = agent.model.z_filter if agent.use_z_filter else None
         log_var = agent.model.log_var.view(-1)
@@ -197,15 +278,10 @@ class SyntheticVecEnv(object):
             # ONE launch for the whole rollout: a workgroup owns 4, 8 or 16 actors and walks them through all T steps
             # (csrc/smx_rollout.hip).  The packed weight copy is refreshed here: the agent's parameters only change
             # between rollouts (fetch_parameter)
-            if getattr(self, '_pk', None) is None or self._pk.numel() != K.epoch_packed_numel(actor):
-                self._pk = torch.zeros(K.epoch_packed_numel(actor), device=self.device)
-            K.epoch_pack([(actor, self._pk)])
-            K.synth_rollout(actor, self._pk, L.SMX_ACT_TANH, self.state, self.init_state, log_var, noise,
-                            None if deterministic else eps.contiguous(), self.t, self.episode_len, T, self.slot,
-                            self.rolls, zf, actors_per_workgroup)
+            K.synth_rollout(actor, self._pack_actor(actor), L.SMX_ACT_TANH, self.state, self.init_state, log_var, noise,
+                            eps, self.t, self.episode_len, T, self.slot, self.rolls, zf, actors_per_workgroup)
             self.slot += T
-            for _ in range(T):
-                self.t = 0 if self.t + 1 >= self.episode_len else self.t + 1
+            self._advance(T)
             return
         if getattr(self, '_xn', None) is None:
             self._xn = torch.empty(n, self.D, device=self.device)
@@ -224,18 +300,18 @@ class SyntheticVecEnv(object):
                 K.linear(self._xn, 1, v['W1'], 1, v['b1'], self._h1, n, actor.H1, actor.D, act=L.SMX_ACT_RELU)
                 K.linear(self._h1, 1, v['W2'], 1, v['b2'], self._h2, n, actor.H2, actor.H1, act=L.SMX_ACT_RELU)
                 K.synth_act_env_step_head(v['W3'], v['b3'], self._h2, L.SMX_ACT_TANH, self.state, self.init_state,
-                                          log_var, noise, None if deterministic else eps[t], self.t,
+                                          log_var, noise, None if eps is None else eps[t], self.t,
                                           self.episode_len, self.slot, self.rolls, zf, self._xn)
                 self.slot += 1
-                self.t = 0 if self.t + 1 >= self.episode_len else self.t + 1
+                self._advance()
             return
         for t in range(T):                     # four launches per step: three policy layers + the step launch
             mean = agent.policy_mean(self._xn)
             K.synth_act_env_step(self.state, self.init_state, mean, log_var, noise,
-                                 None if deterministic else eps[t], self.t, self.episode_len, self.slot,
+                                 None if eps is None else eps[t], self.t, self.episode_len, self.slot,
                                  self.rolls, zf, self._xn)
             self.slot += 1
-            self.t = 0 if self.t + 1 >= self.episode_len else self.t + 1
+            self._advance()
 
     def _lstm_persistent(self, agent):
         """an LSTM-stem policy the one-launch kernel runs: one layer, low-dimensional observations, shapes it takes,
@@ -248,24 +324,15 @@ class SyntheticVecEnv(object):
         """the LSTM rollout launch from the zero state (a rollout starts at an episode boundary, as in _rollout_stem);
         leaves the agent's batch cells where act_batch would have: _batch_cells the final (h, c), batch_cells_before the
         state before the last step, each (1, n, Hl)"""
-        K, n, m = self.K, self.n, agent.model
-        Hl = m.rnn_hidden_logical
-        if getattr(self, '_pk', None) is None or self._pk.numel() != K.epoch_packed_numel(m.actor):
-            self._pk = torch.zeros(K.epoch_packed_numel(m.actor), device=self.device)
-        if getattr(self, '_lpk', None) is None or self._lpk.numel() != K.lstm_rollout_packed_numel(m.rnn):
-            self._lpk = torch.zeros(K.lstm_rollout_packed_numel(m.rnn), device=self.device)
-        K.epoch_pack([(m.actor, self._pk)])          # (the agent's parameters only change between rollouts)
-        K.lstm_rollout_pack(m.rnn, self._lpk)
-        f = lambda: torch.empty(1, n, Hl, device=self.device)  # noqa: E731
-        hN, cN, hB, cB = f(), f(), f(), f()
-        K.synth_lstm_rollout(m, self._pk, self._lpk, self.state, self.init_state, agent.batch_noise(n).view(-1),
-                             eps if eps is None else eps.contiguous(), self.t, self.episode_len, steps, slot, rolls,
-                             m.z_filter if agent.use_z_filter else None, hN, cN, h_before=hB, c_before=cB,
-                             actors_per_workgroup=actors_per_workgroup)
-        agent._batch_cells = (hN, cN)
-        agent.batch_cells_before = (hB, cB)
-        for _ in range(steps):
-            self.t = 0 if self.t + 1 >= self.episode_len else self.t + 1
+        m = agent.model
+        pk, lpk = self._pack_actor(m.actor), self._pack_lstm(m.rnn)
+        cells = self._cell_outputs(m.rnn_hidden_logical)
+        self.K.synth_lstm_rollout(m, pk, lpk, self.state, self.init_state, agent.batch_noise(self.n).view(-1), eps,
+                                  self.t, self.episode_len, steps, slot, rolls,
+                                  m.z_filter if agent.use_z_filter else None,
+                                  actors_per_workgroup=actors_per_workgroup, **cells)
+        self._hand_cells(agent, cells)
+        self._advance(steps)
 
     def _rollout_lstm(self, agent, eps, actors_per_workgroup=0):
         """rollout() for an LSTM-stem policy in ONE launch (smx_synth_lstm_rollout_f32): what _rollout_stem records,
@@ -296,50 +363,32 @@ class SyntheticVecEnv(object):
         T = out['obs'].shape[1]
         assert self.t == 0 and T <= self.episode_len and self.can_rollout_into(agent)
         assert tuple(out['obs'].shape) == (n, T, self.D) and all(out[k].is_contiguous() for k in out)
-        deterministic = agent.agent_mode in ('eval_deterministic', 'eval_deterministic_local')
-        if eps is None and not deterministic:
-            eps = torch.randn(T, n, self.A, device=self.device)
+        eps = self._draws(agent, eps, T)
+        rolls = {'obs': out['obs'], 'actions': out['actions'], 'rewards': out['rewards'], 'dones': out['dones'],
+                 'pds': out['pds'], 'obs_last': out['obs_next']}
         if agent.rnn_config.if_rnn_policy:
             # the window's onetime_infos: the state at its first step -- the zero state a rollout starts from
             out['cells'].zero_()
-            rolls = {'obs': out['obs'], 'actions': out['actions'], 'rewards': out['rewards'], 'dones': out['dones'],
-                     'pds': out['pds'], 'obs_last': out['obs_next']}
-            self._lstm_launch(agent, None if deterministic else eps, T, 0, rolls, actors_per_workgroup)
+            self._lstm_launch(agent, eps, T, 0, rolls, actors_per_workgroup)
             return
         actor = agent.model.actor
-        if getattr(self, '_pk', None) is None or self._pk.numel() != K.epoch_packed_numel(actor):
-            self._pk = torch.zeros(K.epoch_packed_numel(actor), device=self.device)
-        K.epoch_pack([(actor, self._pk)])
-        rolls = {'obs': out['obs'], 'actions': out['actions'], 'rewards': out['rewards'], 'dones': out['dones'],
-                 'pds': out['pds'], 'obs_last': out['obs_next']}
-        K.synth_rollout(actor, self._pk, L.SMX_ACT_TANH, self.state, self.init_state, agent.model.log_var.view(-1),
-                        agent.batch_noise(n).view(-1), None if deterministic else eps.contiguous(), self.t,
-                        self.episode_len, T, 0, rolls, agent.model.z_filter if agent.use_z_filter else None,
-                        actors_per_workgroup)
-        for _ in range(T):
-            self.t = 0 if self.t + 1 >= self.episode_len else self.t + 1
+        K.synth_rollout(actor, self._pack_actor(actor), L.SMX_ACT_TANH, self.state, self.init_state,
+                        agent.model.log_var.view(-1), agent.batch_noise(n).view(-1), eps, self.t, self.episode_len, T, 0,
+                        rolls, agent.model.z_filter if agent.use_z_filter else None, actors_per_workgroup)
+        self._advance(T)
 
     def _ppo_window_refusal(self, agent):
         """why ppo_rollout_into cannot take `agent` -> (exception class, message), or None"""
         m = agent.model
-        if (self.pixel is not None) != bool(m.if_pixel):
-            return NotImplementedError, ('ppo_rollout_into: a camera on one side only (env %s, agent %s); both or neither'
-                                         % ('camera' if self.pixel else 'low-dimensional',
-                                            'camera' if m.if_pixel else 'low-dimensional'))
+        refusal = self._camera_refusal('ppo_rollout_into', agent, bool(m.if_pixel))
+        if refusal is not None:
+            return refusal
         if agent.rnn_config.if_rnn_policy and agent.rnn_config.rnn_layer != 1:
             return NotImplementedError, ('ppo_rollout_into: rnn_layer %d; the windowed rollout runs one LSTM layer'
                                          % agent.rnn_config.rnn_layer)
         if m.if_pixel:
             if getattr(self.K, 'synth_ppo_pixel_window_step', None) is None:
                 return NotImplementedError, 'ppo_rollout_into: the kernels object has no synth_ppo_pixel_window_step'
-            C, H, W = self.pixel
-            S = self.frame_stacks
-            cam = tuple(int(v) for v in agent.obs_spec['pixel']['camera0'])
-            if cam != (S * C, H, W):
-                return ValueError, ('ppo_rollout_into: the agent\'s camera0 %s is not the env\'s stacked frame %s'
-                                    % (cam, (S * C, H, W)))
-            if m.low_dim != self.D:
-                return ValueError, 'ppo_rollout_into: the agent\'s low_dim %d is not the env\'s %d' % (m.low_dim, self.D)
             if not self.K.synth_ppo_pixel_window_step_supported(self.A):
                 return ValueError, ('ppo_rollout_into: %d actions; the camera step launch takes A <= %d '
                                     '(SMX_PPO_PIXEL_STEP_MAX_A)' % (self.A, L.SMX_PPO_PIXEL_STEP_MAX_A))
@@ -399,11 +448,7 @@ class SyntheticVecEnv(object):
             if rnn:
                 c['carry']['cells'] = f(n, -(-N // adv), 2, Hl)
         # the closing steps of this call (the clock is shared by all actors): n windows each
-        closing, t = 0, self.t
-        for _ in range(T):
-            j = t + 1 - N
-            closing += j >= 0 and j % adv == 0
-            t = 0 if t + 1 >= self.episode_len else t + 1
+        closing, t = self._closing_steps(T, lambda t: t + 1 - N >= 0 and (t + 1 - N) % adv == 0)
         rows = n * closing
         if rows > replay.memory_size + 3:
             raise ValueError('ppo_rollout_into: %d actors x %d closing steps = %d windows exceed the FIFO capacity %d '
@@ -421,43 +466,26 @@ class SyntheticVecEnv(object):
             shapes.update(pixel=(N, S * C, H, W), pixel_next=(1, S * C, H, W))
             dtypes = {'pixel': torch.uint8, 'pixel_next': torch.uint8}
         tables, cursor, cap = replay.reserve_ring(rows, shapes, dtypes)
-        deterministic = agent.agent_mode in ('eval_deterministic', 'eval_deterministic_local')
-        if deterministic:
-            eps = None
-        else:
-            if eps is None:
-                eps = torch.randn(T, n, A, device=self.device)
-            assert tuple(eps.shape) == (T, n, A)
-            eps = eps.contiguous()
+        eps = self._draws(agent, eps, T)
+        assert eps is None or tuple(eps.shape) == (T, n, A)
         if camera:
             self._ppo_pixel_steps(agent, T, N, adv, tables, cursor, cap, eps)
             replay.commit_ring(rows)
             c['t'] = self.t
             return rows
-        if getattr(self, '_pk', None) is None or self._pk.numel() != K.epoch_packed_numel(m.actor):
-            self._pk = torch.zeros(K.epoch_packed_numel(m.actor), device=self.device)
-        K.epoch_pack([(m.actor, self._pk)])          # (every call: the agent's parameters change between chunks)
+        pk, lpk, cells = self._pack_actor(m.actor), None, {}
         zf = m.z_filter if agent.use_z_filter else None
         noise = agent.batch_noise(n).view(-1)
         if rnn:
-            if getattr(self, '_lpk', None) is None or self._lpk.numel() != K.lstm_rollout_packed_numel(m.rnn):
-                self._lpk = torch.zeros(K.lstm_rollout_packed_numel(m.rnn), device=self.device)
-            K.lstm_rollout_pack(m.rnn, self._lpk)
-            cells = agent._batch_cells
-            h0, c0 = (None, None) if cells is None or cells[0].shape[1] != n else \
-                (cells[0].contiguous(), cells[1].contiguous())
-            e = lambda: torch.empty(1, n, Hl, device=self.device)  # noqa: E731
-            hN, cN, hB, cB = e(), e(), e(), e()
-            K.synth_ppo_window_rollout(m, self._pk, self._lpk, self.state, self.init_state, noise, eps, self.t,
-                                       self.episode_len, T, N, adv, c['carry'], tables, cursor, zf, hN=hN, cN=cN,
-                                       h0=h0, c0=c0, h_before=hB, c_before=cB,
-                                       actors_per_workgroup=actors_per_workgroup)
-            agent._batch_cells = (hN, cN)
-            agent.batch_cells_before = (hB, cB)
-        else:
-            K.synth_ppo_window_rollout(m, self._pk, None, self.state, self.init_state, noise, eps, self.t,
-                                       self.episode_len, T, N, adv, c['carry'], tables, cursor, zf,
-                                       actors_per_workgroup=actors_per_workgroup)
+            lpk = self._pack_lstm(m.rnn)
+            held = agent._batch_cells
+            cells = self._cell_outputs(Hl)
+            if held is not None and held[0].shape[1] == n:
+                cells.update(h0=held[0].contiguous(), c0=held[1].contiguous())
+        K.synth_ppo_window_rollout(m, pk, lpk, self.state, self.init_state, noise, eps, self.t, self.episode_len, T, N,
+                                   adv, c['carry'], tables, cursor, zf, actors_per_workgroup=actors_per_workgroup, **cells)
+        if rnn:
+            self._hand_cells(agent, cells)
         replay.commit_ring(rows)
         self.t = c['t'] = t
         return rows
@@ -468,18 +496,10 @@ class SyntheticVecEnv(object):
         self._ppo and is primed with them (first use, after reset()) as _ddpg_pixel_steps primes it; the perception's
         and the LSTM's buffers are cached across steps and calls."""
         K, n, c, m = self.K, self.n, self._ppo, agent.model
-        C, H, W = self.pixel
-        S = self.frame_stacks
-        Hd = N + S
+        Hd = N + self.frame_stacks
         rnn = bool(m.if_rnn)
         Hp, Hl = (m.rnn_hidden, m.rnn_hidden_logical) if rnn else (0, 0)
-        if c.get('hist') is None:
-            c['hist'] = torch.zeros((n, Hd, C, H, W), device=self.device, dtype=torch.uint8)
-            c['obs_pixel'] = torch.zeros((n, S * C, H, W), device=self.device, dtype=torch.uint8)
-            for h in range(Hd):
-                K.synth_frames(self.state[:, 0], self.t, c['hist'][:, h])
-            K.frame_stack(c['hist'], S, 0, 1, 1, 1, c['obs_pixel'])
-            c['hist_pos'] = 0
+        self._frame_history(c, Hd)
         actor, p = m.actor, m.cnn
         key = (n, m.stem_in, p.C, p.H, p.W, p.c1, p.c2, p.feat, Hp, Hl, actor.H1, actor.H2, actor.OUT)
         w = getattr(self, '_ppo_ws', None)
@@ -527,7 +547,7 @@ class SyntheticVecEnv(object):
             j = self.t + 1 - N
             if j >= 0 and j % adv == 0:
                 r['cursor'] = (r['cursor'] + n) % cap
-            self.t = 0 if self.t + 1 >= self.episode_len else self.t + 1
+            self._advance()
         if rnn:
             # as act_batch leaves them: the final state and the state before the last step, (1, n, Hl) each, the
             # agent's own tensors (the buffers here are written again by the next call)
@@ -553,10 +573,9 @@ class SyntheticVecEnv(object):
         like the open transitions."""
         K, n, A = self.K, self.n, self.A
         camera = agent.model.is_pixel_input
-        if (self.pixel is not None) != camera:
-            raise NotImplementedError('ddpg_rollout_into: a camera on one side only (env %s, agent %s); both or neither'
-                                      % ('camera' if self.pixel else 'low-dimensional',
-                                         'camera' if camera else 'low-dimensional'))
+        refusal = self._camera_refusal('ddpg_rollout_into', agent, camera)
+        if refusal is not None:
+            raise refusal[0](refusal[1])
         if agent.param_noise_type == 'adaptive_normal':
             raise NotImplementedError("ddpg_rollout_into: 'adaptive_normal' parameter noise measures an action distance "
                                       "per act() on the host; use 'normal' parameter noise or none")
@@ -564,13 +583,6 @@ class SyntheticVecEnv(object):
         if camera:
             C, H, W = self.pixel
             S = self.frame_stacks
-            cam = tuple(int(v) for v in agent.obs_spec['pixel']['camera0'])
-            if cam != (S * C, H, W):
-                raise ValueError('ddpg_rollout_into: the agent\'s camera0 %s is not the env\'s stacked frame %s'
-                                 % (cam, (S * C, H, W)))
-            if agent.model.low_dim != self.D:
-                raise ValueError('ddpg_rollout_into: the agent\'s low_dim %d is not the env\'s %d'
-                                 % (agent.model.low_dim, self.D))
             if reference:
                 raise ValueError('ddpg_rollout_into: reference=True has no camera path (no two-launch reference there)')
             shapes.update(pixel=(S * C, H, W), pixel_next=(S * C, H, W))
@@ -578,10 +590,7 @@ class SyntheticVecEnv(object):
         algo = agent.learner_config.algo
         N, gamma = int(algo.n_step), algo.gamma
         # the closing steps of this call (the clock is shared by all actors): n of them per closing step
-        m, t = 0, self.t
-        for _ in range(T):
-            m += t >= N - 1
-            t = 0 if t + 1 >= self.episode_len else t + 1
+        m, t = self._closing_steps(T, lambda t: t >= N - 1)
         rows = n * m
         if rows > replay.memory_size:
             raise ValueError('ddpg_rollout_into: %d actors x %d closing steps = %d transitions exceed the replay '
@@ -595,18 +604,17 @@ class SyntheticVecEnv(object):
         if d.get('gamma') != gamma:
             d['gamma'] = gamma
             d['gpow'] = torch.tensor([pow(gamma, e) for e in range(N)], dtype=torch.float64, device=self.device)
-        deterministic = agent.agent_mode in ('eval_deterministic', 'eval_deterministic_local')
+        eps = self._draws(agent, eps, T)
+        deterministic = eps is None
         noise = L.SMX_DDPG_NOISE_NONE if deterministic else \
             {'normal': L.SMX_DDPG_NOISE_GAUSSIAN, 'ou_noise': L.SMX_DDPG_NOISE_OU}[agent.noise_type]
         if not deterministic:
-            if eps is None:
-                eps = torch.randn(T, n, A, device=self.device)
             if sigmas is None:
                 sigmas = agent.batch_sigmas(n)
             assert tuple(eps.shape) == (T, n, A) and sigmas.dtype == torch.float64 and sigmas.numel() == n
-            eps, sigmas = eps.contiguous(), sigmas.contiguous()
+            sigmas = sigmas.contiguous()
         r = dict(state=self.state, init_state=self.init_state, t=self.t, episode_len=self.episode_len, n_step=N,
-                 noise_type=noise, eps=None if deterministic else eps, sigmas=None if deterministic else sigmas,
+                 noise_type=noise, eps=eps, sigmas=None if deterministic else sigmas,
                  theta=agent.theta, dt=agent.dt, root_dt=float(np.sqrt(agent.dt)), gpow=d['gpow'], ou=d['ou'],
                  carry_obs=d['carry_obs'], carry_act=d['carry_act'], carry_rew=d['carry_rew'], tables=tables,
                  cursor=cursor)
@@ -639,7 +647,7 @@ class SyntheticVecEnv(object):
                 K.synth_ddpg_step(r, mu)
                 if self.t >= N - 1:
                     r['cursor'] = (r['cursor'] + n) % cap
-                self.t = 0 if self.t + 1 >= self.episode_len else self.t + 1
+                self._advance()
         replay.commit_ring(rows)
         return rows
 
@@ -649,18 +657,8 @@ class SyntheticVecEnv(object):
         the current frame in every slot, the actors' first observation that frame S times (N + S + 1 launches, once)"""
         from surreal_amd.model.cnn_stem import CnnStem
         K, n, d, model = self.K, self.n, self._ddpg, agent.model
-        C, H, W = self.pixel
-        S = self.frame_stacks
-        Hd = N + S
-        if d.get('hist') is None or tuple(d['hist'].shape) != (n, Hd, C, H, W):
-            d['hist'] = torch.zeros((n, Hd, C, H, W), device=self.device, dtype=torch.uint8)
-            d['obs_pixel'] = torch.zeros((n, S * C, H, W), device=self.device, dtype=torch.uint8)
-            d['hist_pos'] = None
-        if d.get('hist_pos') is None:
-            for h in range(Hd):
-                K.synth_frames(self.state[:, 0], self.t, d['hist'][:, h])
-            K.frame_stack(d['hist'], S, 0, 1, 1, 1, d['obs_pixel'])
-            d['hist_pos'] = 0
+        Hd = N + self.frame_stacks
+        self._frame_history(d, Hd)
         p = model.cnn
         key = (n, model.input_dim, p.C, p.H, p.W, p.c1, p.c2, p.feat)
         if d.get('perc_key') != key:        # the perception's workspace, cached across steps and calls
@@ -677,7 +675,7 @@ class SyntheticVecEnv(object):
             d['hist_pos'] = (d['hist_pos'] + 1) % Hd
             if self.t >= N - 1:
                 r['cursor'] = (r['cursor'] + n) % cap
-            self.t = 0 if self.t + 1 >= self.episode_len else self.t + 1
+            self._advance()
 
     def _rollout_stem(self, agent, eps):
         """policies with an LSTM and / or CNN stem: one batched act per step (PPOAgent.act_batch: the stem and the
@@ -721,7 +719,7 @@ class SyntheticVecEnv(object):
             K.synth_act_env_step(self.state, self.init_state, mean, agent.model.log_var.view(-1), noise,
                                  None if eps is None else eps[t], self.t, self.episode_len, self.slot, self.rolls, zf, xn)
             self.slot += 1
-            self.t = 0 if self.t + 1 >= self.episode_len else self.t + 1
+            self._advance()
 
     def window_shapes(self, n_step, agent=None):
         """per-experience shape of every field emit_windows produces (for Replay.reserve_batch); with a recurrent

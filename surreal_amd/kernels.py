@@ -620,29 +620,77 @@ class HipKernels(object):
     def synth_rollout_supported(self, net):
         return bool(self.lib.smx_synth_rollout_supported(net.D, net.H1, net.H2, net.OUT))
 
+    @staticmethod
+    def _roll_args(q, net, packed, out_act, state, init_state, log_var, noise_scale, eps, t, episode_len, steps, zfilter,
+                   actors_per_workgroup, rolls=None, slot=0):
+        """fills the SynthRollout `q`: the network, the head, the z-filter, state and clock, and (rolls: dict as in
+        synth_act_env_step, also 'obs_last' / 'cells') the rollout tables"""
+        n = state.shape[0]
+        q.net, q.packed, q.out_act, q.n = ctypes.pointer(net.desc), L.ptr(packed), int(out_act), n
+        q.log_var, q.noise_scale, q.eps = L.ptr(log_var), L.ptr(noise_scale), L.ptr(eps)
+        if eps is not None:
+            assert eps.is_contiguous() and tuple(eps.shape) == (steps, n, net.OUT)
+        if zfilter is not None:
+            q.zsum, q.zsumsq, q.zcount = L.ptr(zfilter.running_sum), L.ptr(zfilter.running_sumsq), L.ptr(zfilter.count)
+            q.zeps = float(zfilter.eps)
+        q.t, q.episode_len, q.steps, q.slot = int(t), int(episode_len), int(steps), int(slot)
+        q.state, q.init_state = L.ptr(state), L.ptr(init_state)
+        q.actors_per_workgroup = int(actors_per_workgroup)
+        if rolls is not None:
+            r = rolls
+            q.rows_per_actor = r['obs'].shape[1] if 'obs' in r else (r['cells'].shape[1] if 'cells' in r else 1)
+            q.obs_roll, q.act_roll = L.ptr(r.get('obs')), L.ptr(r.get('actions'))
+            q.rew_roll, q.done_roll, q.pd_roll = L.ptr(r.get('rewards')), L.ptr(r.get('dones')), L.ptr(r.get('pds'))
+            q.obs_last = L.ptr(r.get('obs_last'))      # rows_per_actor == steps: the replay's layout (obs_next apart)
+
+    @staticmethod
+    def _lstm_args(p, model, lstm_packed, n, hN, cN, h0, c0, h_before, c_before):
+        """fills the LSTM block of the SynthLstmRollout `p`; the states [n, Hl] contiguous"""
+        Hl = model.rnn_hidden_logical
+        for x in (h0, c0, hN, cN, h_before, c_before):
+            assert x is None or (x.is_contiguous() and x.numel() == n * Hl)
+        p.lstm, p.lstm_packed, p.hidden = ctypes.pointer(model.rnn.desc), L.ptr(lstm_packed), Hl
+        p.h0, p.c0, p.hN, p.cN = L.ptr(h0), L.ptr(c0), L.ptr(hN), L.ptr(cN)
+        p.h_before, p.c_before = L.ptr(h_before), L.ptr(c_before)
+
+    @staticmethod
+    def _window_args(p, n_step, advance, carry, tables, cursor):
+        """fills the moving-window block of `p`: the carry rings, the FIFO's tables by replay field name, the cursor"""
+        p.n_step, p.advance = int(n_step), int(advance)
+        p.carry_obs, p.carry_act, p.carry_rew = L.ptr(carry['obs']), L.ptr(carry['actions']), L.ptr(carry['rewards'])
+        p.carry_pd, p.carry_cells = L.ptr(carry['pds']), L.ptr(carry.get('cells'))
+        p.obs, p.obs_next, p.actions = L.ptr(tables['obs']), L.ptr(tables['obs_next']), L.ptr(tables['actions'])
+        p.rewards, p.dones, p.pds = L.ptr(tables['rewards']), L.ptr(tables['dones']), L.ptr(tables['pds'])
+        p.cells = L.ptr(tables.get('cells'))
+        p.cursor, p.capacity = int(cursor), int(tables['obs'].shape[0])
+
+    @staticmethod
+    def _camera_args(p, r, frames_per_row):
+        """checks and fills the camera block of `p` from r['hist'] [n, Hd, C, H, W], r['obs_pixel'] [n, S*C, H, W],
+        r['hist_pos'] and the ring's 'pixel' (frames_per_row stacked frames a row) / 'pixel_next' (one) uint8 tables"""
+        n, Hd, C, H, W = r['hist'].shape
+        tabs = r['tables']
+        S = r['obs_pixel'].shape[1] // C
+        for k in ('hist', 'obs_pixel'):
+            assert r[k].dtype == torch.uint8 and r[k].is_contiguous(), k
+        assert tuple(r['obs_pixel'].shape) == (n, S * C, H, W) and r['state'].shape[0] == n
+        for k, w in (('pixel', frames_per_row * S * C * H * W), ('pixel_next', S * C * H * W)):
+            assert tabs[k].dtype == torch.uint8 and tabs[k].is_contiguous(), k
+            assert tuple(tabs[k].shape) == (tabs['obs'].shape[0], w), k
+        p.C, p.H, p.W, p.frame_stacks = C, H, W, S
+        p.hist_len, p.hist_pos = Hd, int(r['hist_pos'])
+        p.hist, p.obs_pixel = L.ptr(r['hist']), L.ptr(r['obs_pixel'])
+        p.pixel, p.pixel_next = L.ptr(tabs['pixel']), L.ptr(tabs['pixel_next'])
+
     def synth_rollout(self, net, packed, out_act, state, init_state, log_var, noise_scale, eps, t, episode_len,
                       steps, slot, rolls, zfilter, actors_per_workgroup=0):
         """`steps` acting + environment steps of all actors in ONE launch (csrc/smx_rollout.hip): a workgroup owns
         4, 8 or 16 actors for the whole rollout (actors_per_workgroup; 0: the smallest whose grid fits the CUs once).
         packed: epoch_pack of `net`; eps [steps, n, A] or None; rolls as in synth_act_env_step ([n, T + 1, .]
         tables)."""
-        n, D = state.shape
         p = L.SynthRollout()
-        p.net, p.packed, p.out_act, p.n = ctypes.pointer(net.desc), L.ptr(packed), int(out_act), n
-        p.log_var, p.noise_scale, p.eps = L.ptr(log_var), L.ptr(noise_scale), L.ptr(eps)
-        if eps is not None:
-            assert eps.is_contiguous() and tuple(eps.shape) == (steps, n, net.OUT)
-        if zfilter is not None:
-            p.zsum, p.zsumsq, p.zcount = L.ptr(zfilter.running_sum), L.ptr(zfilter.running_sumsq), L.ptr(zfilter.count)
-            p.zeps = float(zfilter.eps)
-        r = rolls or {}
-        p.t, p.episode_len, p.steps, p.slot = int(t), int(episode_len), int(steps), int(slot)
-        p.rows_per_actor = r['obs'].shape[1] if 'obs' in r else 1
-        p.state, p.init_state = L.ptr(state), L.ptr(init_state)
-        p.obs_roll, p.act_roll = L.ptr(r.get('obs')), L.ptr(r.get('actions'))
-        p.rew_roll, p.done_roll, p.pd_roll = L.ptr(r.get('rewards')), L.ptr(r.get('dones')), L.ptr(r.get('pds'))
-        p.obs_last = L.ptr(r.get('obs_last'))          # rows_per_actor == steps: the replay's layout (obs_next apart)
-        p.actors_per_workgroup = int(actors_per_workgroup)
+        self._roll_args(p, net, packed, out_act, state, init_state, log_var, noise_scale, eps, t, episode_len, steps,
+                        zfilter, actors_per_workgroup, rolls or {}, slot)
         L.call('smx_synth_rollout_f32', ctypes.byref(p), self._st())
 
     def synth_lstm_rollout_supported(self, model):
@@ -667,33 +715,14 @@ class HipKernels(object):
         epoch_pack of model.actor, lstm_packed = lstm_rollout_pack of model.rnn; rolls may also hold 'cells'
         [n, R, 2, 1, Hl] (the state before every step); h0 / c0 (None: zeros), hN / cN, h_before / c_before: [n, Hl]
         contiguous, Hl = model.rnn_hidden_logical"""
-        actor, lstm = model.actor, model.rnn
-        n = state.shape[0]
-        Hl = model.rnn_hidden_logical
-        p = L.SynthLstmRollout()
-        q = p.roll
-        q.net, q.packed, q.out_act, q.n = ctypes.pointer(actor.desc), L.ptr(packed), L.SMX_ACT_TANH, n
-        q.log_var, q.noise_scale, q.eps = L.ptr(model.log_var), L.ptr(noise_scale), L.ptr(eps)
-        if eps is not None:
-            assert eps.is_contiguous() and tuple(eps.shape) == (steps, n, actor.OUT)
-        if zfilter is not None:
-            q.zsum, q.zsumsq, q.zcount = L.ptr(zfilter.running_sum), L.ptr(zfilter.running_sumsq), L.ptr(zfilter.count)
-            q.zeps = float(zfilter.eps)
         r = rolls or {}
-        q.t, q.episode_len, q.steps, q.slot = int(t), int(episode_len), int(steps), int(slot)
-        q.rows_per_actor = r['obs'].shape[1] if 'obs' in r else (r['cells'].shape[1] if 'cells' in r else 1)
-        q.state, q.init_state = L.ptr(state), L.ptr(init_state)
-        q.obs_roll, q.act_roll = L.ptr(r.get('obs')), L.ptr(r.get('actions'))
-        q.rew_roll, q.done_roll, q.pd_roll = L.ptr(r.get('rewards')), L.ptr(r.get('dones')), L.ptr(r.get('pds'))
-        q.obs_last = L.ptr(r.get('obs_last'))
-        q.actors_per_workgroup = int(actors_per_workgroup)
-        for x in (h0, c0, hN, cN, h_before, c_before):
-            assert x is None or (x.is_contiguous() and x.numel() == n * Hl)
+        p = L.SynthLstmRollout()
+        self._roll_args(p.roll, model.actor, packed, L.SMX_ACT_TANH, state, init_state, model.log_var, noise_scale, eps,
+                        t, episode_len, steps, zfilter, actors_per_workgroup, r, slot)
+        self._lstm_args(p, model, lstm_packed, state.shape[0], hN, cN, h0, c0, h_before, c_before)
         if 'cells' in r:
-            assert r['cells'].is_contiguous() and tuple(r['cells'].shape[2:]) == (2, 1, Hl)
-        p.lstm, p.lstm_packed, p.hidden = ctypes.pointer(lstm.desc), L.ptr(lstm_packed), Hl
-        p.h0, p.c0, p.hN, p.cN = L.ptr(h0), L.ptr(c0), L.ptr(hN), L.ptr(cN)
-        p.h_before, p.c_before, p.cell_roll = L.ptr(h_before), L.ptr(c_before), L.ptr(r.get('cells'))
+            assert r['cells'].is_contiguous() and tuple(r['cells'].shape[2:]) == (2, 1, model.rnn_hidden_logical)
+        p.cell_roll = L.ptr(r.get('cells'))
         L.call('smx_synth_lstm_rollout_f32', ctypes.byref(p), self._st())
 
     def synth_ppo_window_rollout_supported(self, model):
@@ -717,37 +746,14 @@ class HipKernels(object):
         ('obs' [capacity, n_step * D], 'obs_next', 'actions', 'rewards', 'dones', 'pds', 'cells' (LSTM)); the k-th
         closing step writes actor a to row (cursor + k n + a) % capacity.  h0 / c0 (None: zeros), hN / cN (LSTM),
         h_before / c_before: [n, Hl] contiguous, Hl = model.rnn_hidden_logical"""
-        actor = model.actor
-        n = state.shape[0]
-        lstm = model.rnn if model.if_rnn else None
         p = L.SynthPpoWindowRollout()
-        q = p.base.roll
-        q.net, q.packed, q.out_act, q.n = ctypes.pointer(actor.desc), L.ptr(packed), L.SMX_ACT_TANH, n
-        q.log_var, q.noise_scale, q.eps = L.ptr(model.log_var), L.ptr(noise_scale), L.ptr(eps)
-        if eps is not None:
-            assert eps.is_contiguous() and tuple(eps.shape) == (steps, n, actor.OUT)
-        if zfilter is not None:
-            q.zsum, q.zsumsq, q.zcount = L.ptr(zfilter.running_sum), L.ptr(zfilter.running_sumsq), L.ptr(zfilter.count)
-            q.zeps = float(zfilter.eps)
-        q.t, q.episode_len, q.steps = int(t), int(episode_len), int(steps)
-        q.state, q.init_state = L.ptr(state), L.ptr(init_state)
-        q.actors_per_workgroup = int(actors_per_workgroup)
-        if lstm is not None:
-            Hl = model.rnn_hidden_logical
-            for x in (h0, c0, hN, cN, h_before, c_before):
-                assert x is None or (x.is_contiguous() and x.numel() == n * Hl)
-            p.base.lstm, p.base.lstm_packed, p.base.hidden = ctypes.pointer(lstm.desc), L.ptr(lstm_packed), Hl
-            p.base.h0, p.base.c0, p.base.hN, p.base.cN = L.ptr(h0), L.ptr(c0), L.ptr(hN), L.ptr(cN)
-            p.base.h_before, p.base.c_before = L.ptr(h_before), L.ptr(c_before)
+        self._roll_args(p.base.roll, model.actor, packed, L.SMX_ACT_TANH, state, init_state, model.log_var, noise_scale,
+                        eps, t, episode_len, steps, zfilter, actors_per_workgroup)
+        if model.if_rnn:
+            self._lstm_args(p.base, model, lstm_packed, state.shape[0], hN, cN, h0, c0, h_before, c_before)
         for k, x in list(carry.items()) + list(tables.items()):
             assert x.is_contiguous() and x.dtype == torch.float32, k
-        p.n_step, p.advance = int(n_step), int(advance)
-        p.carry_obs, p.carry_act, p.carry_rew = L.ptr(carry['obs']), L.ptr(carry['actions']), L.ptr(carry['rewards'])
-        p.carry_pd, p.carry_cells = L.ptr(carry['pds']), L.ptr(carry.get('cells'))
-        p.obs, p.obs_next, p.actions = L.ptr(tables['obs']), L.ptr(tables['obs_next']), L.ptr(tables['actions'])
-        p.rewards, p.dones, p.pds = L.ptr(tables['rewards']), L.ptr(tables['dones']), L.ptr(tables['pds'])
-        p.cells = L.ptr(tables.get('cells'))
-        p.cursor, p.capacity = int(cursor), int(tables['obs'].shape[0])
+        self._window_args(p, n_step, advance, carry, tables, cursor)
         L.call('smx_synth_ppo_window_rollout_f32', ctypes.byref(p), self._st())
 
     def synth_ddpg_rollout_supported(self, net):
@@ -798,23 +804,10 @@ class HipKernels(object):
         raw frames, the current step's in slot hist_pos), obs_pixel uint8 [n, S*C, H, W] (receives the stacked
         observation of the next step) and the ring tables 'pixel' / 'pixel_next' uint8 [capacity, S*C*H*W]
         (include/surreal_amd.h smx_synth_ddpg_pixel_step)"""
-        n, Hd, C, H, W = r['hist'].shape
-        tabs = r['tables']
-        S = r['obs_pixel'].shape[1] // C
-        A = mu.shape[1]
-        for k in ('hist', 'obs_pixel'):
-            assert r[k].dtype == torch.uint8 and r[k].is_contiguous(), k
-        assert tuple(r['obs_pixel'].shape) == (n, S * C, H, W) and r['state'].shape[0] == n
-        for k in ('pixel', 'pixel_next'):
-            assert tabs[k].dtype == torch.uint8 and tabs[k].is_contiguous(), k
-            assert tuple(tabs[k].shape) == (tabs['obs'].shape[0], S * C * H * W), k
         p = L.DdpgPixelStep()
+        self._camera_args(p, r, 1)
         p.base = self._ddpg_args(r, 1)
-        p.C, p.H, p.W, p.frame_stacks = C, H, W, S
-        p.hist_len, p.hist_pos = Hd, int(r['hist_pos'])
-        p.hist, p.obs_pixel = L.ptr(r['hist']), L.ptr(r['obs_pixel'])
-        p.pixel, p.pixel_next = L.ptr(tabs['pixel']), L.ptr(tabs['pixel_next'])
-        L.call('smx_synth_ddpg_pixel_step', ctypes.byref(p), L.ptr(mu), _row_stride(mu, A), self._st())
+        L.call('smx_synth_ddpg_pixel_step', ctypes.byref(p), L.ptr(mu), _row_stride(mu, mu.shape[1]), self._st())
 
     @staticmethod
     def synth_ppo_pixel_window_step_supported(A):
@@ -830,17 +823,12 @@ class HipKernels(object):
         replay field name, 'pixel' [capacity, n_step * S*C*H*W] and 'pixel_next' [capacity, S*C*H*W] uint8 among
         them), cursor, hist uint8 [n, Hd, C, H, W] (the current step's frame in slot hist_pos), obs_pixel uint8
         [n, S*C, H, W] (receives the stacked observation of the next step)"""
-        n, Hd, C, H, W = r['hist'].shape
-        D, A = r['state'].shape[1], mu.shape[1]
+        n, D, A = r['state'].shape[0], r['state'].shape[1], mu.shape[1]
         tabs, carry = r['tables'], r['carry']
-        S = r['obs_pixel'].shape[1] // C
         N = int(r['n_step'])
         cap = tabs['obs'].shape[0]
-        for k in ('hist', 'obs_pixel'):
-            assert r[k].dtype == torch.uint8 and r[k].is_contiguous(), k
-        assert tuple(r['obs_pixel'].shape) == (n, S * C, H, W) and r['state'].shape[0] == n
-        for k, w in (('pixel', N * S * C * H * W), ('pixel_next', S * C * H * W)):
-            assert tabs[k].dtype == torch.uint8 and tabs[k].is_contiguous() and tuple(tabs[k].shape) == (cap, w), k
+        p = L.SynthPpoPixelWindowStep()
+        self._camera_args(p, r, N)
         for k, x in list(carry.items()) + [(k, x) for k, x in tabs.items() if k not in ('pixel', 'pixel_next')]:
             assert x.is_contiguous() and x.dtype == torch.float32, k
         assert tuple(tabs['obs'].shape) == (cap, N * D) and tuple(carry['obs'].shape) == (n, N, D)
@@ -854,22 +842,13 @@ class HipKernels(object):
             assert 'cells' not in tabs or tabs['cells'].shape[1] == 2 * Hl
         if r.get('eps') is not None:
             assert r['eps'].is_contiguous() and tuple(r['eps'].shape) == (n, A)
-        p = L.SynthPpoPixelWindowStep()
         p.n, p.D, p.A, p.hidden = n, D, A, Hl
-        p.t, p.episode_len, p.n_step, p.advance = int(r['t']), int(r['episode_len']), N, int(r['advance'])
+        p.t, p.episode_len = int(r['t']), int(r['episode_len'])
         p.log_var, p.noise_scale, p.eps = L.ptr(r['log_var']), L.ptr(r.get('noise_scale')), L.ptr(r.get('eps'))
         p.state, p.init_state = L.ptr(r['state']), L.ptr(r['init_state'])
         p.h_before, p.c_before = L.ptr(hb), L.ptr(cb)
-        p.carry_obs, p.carry_act, p.carry_rew = L.ptr(carry['obs']), L.ptr(carry['actions']), L.ptr(carry['rewards'])
-        p.carry_pd, p.carry_cells = L.ptr(carry['pds']), L.ptr(carry.get('cells'))
-        p.obs, p.obs_next, p.actions = L.ptr(tabs['obs']), L.ptr(tabs['obs_next']), L.ptr(tabs['actions'])
-        p.rewards, p.dones, p.pds = L.ptr(tabs['rewards']), L.ptr(tabs['dones']), L.ptr(tabs['pds'])
-        p.cells = L.ptr(tabs.get('cells'))
-        p.cursor, p.capacity = int(r['cursor']), cap
-        p.C, p.H, p.W, p.frame_stacks = C, H, W, S
-        p.hist_len, p.hist_pos, p.copy_workgroups = Hd, int(r['hist_pos']), int(copy_workgroups)
-        p.hist, p.obs_pixel = L.ptr(r['hist']), L.ptr(r['obs_pixel'])
-        p.pixel, p.pixel_next = L.ptr(tabs['pixel']), L.ptr(tabs['pixel_next'])
+        self._window_args(p, N, r['advance'], carry, tabs, r['cursor'])
+        p.copy_workgroups = int(copy_workgroups)
         L.call('smx_synth_ppo_pixel_window_step', ctypes.byref(p), L.ptr(mu), _row_stride(mu, A), self._st())
 
     def synth_env_step(self, state, init_state, actions, t, episode_len, slot, obs_roll, act_roll,

@@ -179,10 +179,6 @@ def host_ring(agent, lc, ec, sc, n, episode_len, eps_all, capacity, pixel, stack
     return ring, total
 
 
-def device_ring(replay):
-    return {k: replay._tables[k].data.detach().cpu().numpy() for k in FIELDS}
-
-
 def render(pixel, t, s0):
     """SyntheticEnv._frame for step count t and first state component s0"""
     from surreal_amd.env.synthetic_env import SyntheticEnv

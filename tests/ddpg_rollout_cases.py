@@ -179,7 +179,3 @@ def host_ring(agent, lc, ec, sc, n, episode_len, eps_all, capacity):
             cursor = (cursor + n) % capacity
             total += n
     return ring, total
-
-
-def device_ring(replay):
-    return {k: replay._tables[k].data.detach().cpu().numpy() for k in FIELDS}

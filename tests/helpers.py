@@ -1,6 +1,7 @@
 """shared helpers for the parity tests (tests only)"""
 import json
 import os
+import subprocess
 
 import numpy as np
 
@@ -392,3 +393,39 @@ def assert_fp64_seed_distribution(hip, ref, floor=LOOSE_RTOL):
                                  'share_median': float(np.median(h) / b_med)}
         assert h.max() <= b_max, '%s: worst seed %.3g from float64, bound %.3g (reference worst %.3g)' % (key, h.max(), b_max, r.max())
         assert np.median(h) <= b_med, '%s: median %.3g from float64, bound %.3g' % (key, np.median(h), b_med)
+
+
+def _offsets(tmp_path, cname, cls):
+    """{field: offset, 'sizeof': size} of the C struct `cname` (include/surreal_amd.h) as gcc lays it out, for the fields
+    of its ctypes mirror `cls`"""
+    lines = ['#include <stdio.h>', '#include <stddef.h>', '#include "surreal_amd.h"', 'int main(void) {',
+             '  printf("sizeof %%zu\\n", sizeof(%s));' % cname]
+    for fname, _ in cls._fields_:
+        lines.append('  printf("%s %%zu\\n", offsetof(%s, %s));' % (fname, cname, fname))
+    lines += ['  return 0;', '}']
+    src = tmp_path / 'layout.c'
+    src.write_text('\n'.join(lines))
+    exe = tmp_path / 'layout'
+    include = os.path.join(os.path.dirname(os.path.dirname(GOLDEN_DIR)), 'include')
+    subprocess.run(['gcc', '-I', include, str(src), '-o', str(exe)], check=True)
+    out = subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout
+    return {k: int(v) for k, v in (ln.split() for ln in out.splitlines())}
+
+
+def tensors_to(r, dev):
+    """a step launch's argument dict with every tensor (one level of nested dicts included) contiguous on `dev`"""
+    import torch
+    out = {}
+    for k, v in r.items():
+        if torch.is_tensor(v):
+            out[k] = v.to(dev).contiguous()
+        elif isinstance(v, dict):
+            out[k] = {kk: vv.to(dev).contiguous() for kk, vv in v.items()}
+        else:
+            out[k] = v
+    return out
+
+
+def device_ring(replay, fields=None):
+    """a replay's whole device ring {field: np [capacity, width]} (fields: default every table)"""
+    return {k: replay._tables[k].data.detach().cpu().numpy() for k in (fields or replay._tables)}

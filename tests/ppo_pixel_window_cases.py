@@ -185,23 +185,6 @@ def host_windows(agent, cfg, n, D, episode_len, steps, eps_all, pixel, stacks, d
     return {k: np.stack(v) if v else np.zeros((0,)) for k, v in out.items()}
 
 
-def device_ring(replay):
-    """the FIFO's whole ring {field: np [capacity, width]}"""
-    return {k: t.data.detach().cpu().numpy() for k, t in replay._tables.items()}
-
-
-def closing_steps(t, steps, episode_len, n_step, stride):
-    """the episode clocks of the closing steps among `steps` steps from clock t, in order"""
-    from surreal_amd.env.exp_sender_wrapper import window_advance
-    adv, out = window_advance(n_step, stride), []
-    for _ in range(steps):
-        j = t + 1 - n_step
-        if j >= 0 and j % adv == 0:
-            out.append(t)
-        t = 0 if t + 1 >= episode_len else t + 1
-    return out
-
-
 def frames_from_record(ring, rows_by_step, n, n_step, stacks, pixel):
     """The pixel [n_step, S*C, H, W] / pixel_next [1, S*C, H, W] rows the device should hold, from the low-dimensional
     states it recorded next to them.  rows_by_step: [(episode clock tau of the closing step, first ring row of its n

@@ -173,15 +173,21 @@ def make_agent(D, A, n_step, stride, hidden=(24, 16), rnn_hidden=None, use_z=Tru
     return agent, (lc, ec, sc)
 
 
-def closing_count(t, steps, episode_len, n_step, stride):
-    """closing steps among `steps` steps from clock t (the host's count)"""
+def closing_steps(t, steps, episode_len, n_step, stride):
+    """the episode clocks of the closing steps among `steps` steps from clock t, in order"""
     from surreal_amd.env.exp_sender_wrapper import window_advance
-    adv, m = window_advance(n_step, stride), 0
+    adv, out = window_advance(n_step, stride), []
     for _ in range(steps):
         j = t + 1 - n_step
-        m += j >= 0 and j % adv == 0
+        if j >= 0 and j % adv == 0:
+            out.append(t)
         t = 0 if t + 1 >= episode_len else t + 1
-    return m
+    return out
+
+
+def closing_count(t, steps, episode_len, n_step, stride):
+    """closing steps among `steps` steps from clock t (the host's count)"""
+    return len(closing_steps(t, steps, episode_len, n_step, stride))
 
 
 def host_windows(agent, cfg, n, D, episode_len, steps, eps_all, device='cpu'):

@@ -5,13 +5,14 @@ reserve_ring's dtypes, a camera learner's staging buffers and the C ABI of the n
 import ctypes
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 import torch
 
 import ddpg_pixel_rollout_cases as PC
+import helpers as H
+from helpers import _offsets
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -57,7 +58,7 @@ def check_against_host(K, n=3, D=5, A=2, pixel=(2, 20, 24), stacks=3, episode_le
     assert written == total
     assert len(replay) == min(capacity, total) and replay._dev_next == total % capacity
     assert replay.cumulative_collected_count == total
-    got = PC.device_ring(replay)
+    got = H.device_ring(replay, PC.FIELDS)
     assert got['pixel'].dtype == np.uint8 and got['pixel_next'].dtype == np.uint8
     if total:
         assert_rings_equal(got, want)
@@ -218,20 +219,6 @@ def test_act_batch_takes_the_nested_camera_observation(pixel_double):
         assert np.array_equal(got[i], want), i
     x = agent.model.forward_perception(obs)                  # the tensor form is unchanged
     assert np.array_equal(agent.act_batch(x).numpy(), got)
-
-
-def _offsets(tmp_path, cname, cls):
-    lines = ['#include <stdio.h>', '#include <stddef.h>', '#include "surreal_amd.h"', 'int main(void) {',
-             '  printf("sizeof %%zu\\n", sizeof(%s));' % cname]
-    for fname, _ in cls._fields_:
-        lines.append('  printf("%s %%zu\\n", offsetof(%s, %s));' % (fname, cname, fname))
-    lines += ['  return 0;', '}']
-    src = tmp_path / 'layout.c'
-    src.write_text('\n'.join(lines))
-    exe = tmp_path / 'layout'
-    subprocess.run(['gcc', '-I', os.path.join(ROOT, 'include'), str(src), '-o', str(exe)], check=True)
-    out = subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout
-    return {k: int(v) for k, v in (ln.split() for ln in out.splitlines())}
 
 
 def test_pixel_step_struct_matches_the_ctypes_mirror(tmp_path):

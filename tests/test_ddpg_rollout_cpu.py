@@ -7,6 +7,7 @@ import pytest
 import torch
 
 import ddpg_rollout_cases as DC
+import helpers as H
 
 
 
@@ -58,7 +59,7 @@ def check_against_host(K, n=3, D=7, A=3, episode_len=9, calls=(5, 7, 4), capacit
     assert len(replay) == min(capacity, total) and replay._dev_next == total % capacity
     assert replay.cumulative_collected_count == total
     if total:
-        assert_rings_equal(DC.device_ring(replay), want, atol)
+        assert_rings_equal(H.device_ring(replay, DC.FIELDS), want, atol)
     return total
 
 
@@ -112,7 +113,7 @@ def test_ddpg_rollout_reference_path_agrees(ddpg_double):
         replay = UniformReplay(lc, ec, sc)
         w = venv.ddpg_rollout_into(agent, replay, 7, eps=eps[:7], reference=ref)
         w += venv.ddpg_rollout_into(agent, replay, 5, eps=eps[7:], reference=ref)
-        out.append((w, DC.device_ring(replay), venv.state.clone()))
+        out.append((w, H.device_ring(replay, DC.FIELDS), venv.state.clone()))
     assert out[0][0] == out[1][0] == n * (5 + 3)
     assert_rings_equal(out[1][1], out[0][1], atol=1e-6)
     assert torch.allclose(out[0][2], out[1][2], atol=1e-6, rtol=0)

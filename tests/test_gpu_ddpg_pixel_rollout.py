@@ -16,6 +16,7 @@ import pytest
 import torch
 
 import ddpg_pixel_rollout_cases as PC
+import helpers as H
 from surreal_amd import _lib as L
 from surreal_amd.env.synthetic_env import SyntheticVecEnv
 from surreal_amd.replay import UniformReplay
@@ -48,18 +49,6 @@ def _step_inputs(n, D, A, pixel, S, N, tau, episode_len, cap, cursor, noise, see
     return r, mu
 
 
-def _to(r, dev):
-    out = {}
-    for k, v in r.items():
-        if torch.is_tensor(v):
-            out[k] = v.to(dev).contiguous()
-        elif isinstance(v, dict):
-            out[k] = {kk: vv.to(dev).contiguous() for kk, vv in v.items()}
-        else:
-            out[k] = v
-    return out
-
-
 @pytest.mark.parametrize('pixel', [(3, 36, 36), (1, 21, 22)])
 @pytest.mark.parametrize('tau,noise', [(0, L.SMX_DDPG_NOISE_OU), (1, L.SMX_DDPG_NOISE_GAUSSIAN),
                                        (4, L.SMX_DDPG_NOISE_OU), (7, L.SMX_DDPG_NOISE_NONE),
@@ -70,8 +59,8 @@ def test_pixel_step_matches_the_double(pixel, tau, noise, n, S, N):
     from surreal_amd import kernels as KN
     D, A, cap = 17, 6, 300
     r, mu = _step_inputs(n, D, A, pixel, S, N, tau, 9, cap, cap - n // 2, noise, seed=tau + 7 * n)
-    want = _to(r, 'cpu')
-    got = _to(r, 'cuda')
+    want = H.tensors_to(r, 'cpu')
+    got = H.tensors_to(r, 'cuda')
     PC.DdpgPixelRolloutCpuKernels().synth_ddpg_pixel_step(want, mu.clone())
     KN.HipKernels().synth_ddpg_pixel_step(got, mu.cuda())
     torch.cuda.synchronize()
@@ -116,7 +105,7 @@ def test_device_path_matches_host_path(n, n_step, stacks, noise):
         written += venv.ddpg_rollout_into(agent, replay, T, eps=torch.as_tensor(eps_all[s0:s0 + T]).cuda())
         s0 += T
     torch.cuda.synchronize()
-    ring = PC.device_ring(replay)
+    ring = H.device_ring(replay, PC.FIELDS)
     want, total = PC.host_ring(agent, lc, ec, sc, n, L_, eps_all, capacity, pixel, stacks)
     assert written == total == n * len(closing) and len(replay) == total
     for k in PC.DC.FIELDS:

@@ -12,6 +12,7 @@ import pytest
 import torch
 
 import ddpg_rollout_cases as DC
+import helpers as H
 from surreal_amd.env.synthetic_env import SyntheticVecEnv
 from surreal_amd.replay import UniformReplay
 
@@ -29,7 +30,7 @@ def device_run(agent, lc, ec, sc, n, episode_len, eps, calls, **kw):
     torch.cuda.synchronize()
     extra = {k: venv._ddpg[k].cpu().numpy() for k in ('ou', 'carry_obs', 'carry_act', 'carry_rew')}
     extra['state'] = venv.state.cpu().numpy()
-    return written, replay, DC.device_ring(replay), extra
+    return written, replay, H.device_ring(replay, DC.FIELDS), extra
 
 
 def compare(got, want, written, capacity, atol):
@@ -88,7 +89,7 @@ def test_persistent_kernel_wraps_the_ring():
         replay = UniformReplay(lc, ec, sc)
         w = sum(venv.ddpg_rollout_into(agent, replay, 2, eps=eps[2 * i:2 * i + 2], reference=ref) for i in range(3))
         w += venv.ddpg_rollout_into(agent, replay, 1, eps=eps[6:], reference=ref)
-        outs.append((w, replay._dev_next, len(replay), DC.device_ring(replay)))
+        outs.append((w, replay._dev_next, len(replay), H.device_ring(replay, DC.FIELDS)))
     assert outs[0][:3] == outs[1][:3] == (5 * n, 5 * n % 100, 100)
     for k in DC.FIELDS:
         np.testing.assert_allclose(outs[0][3][k], outs[1][3][k], atol=2e-6, rtol=0, err_msg=k)

@@ -13,6 +13,7 @@ import numpy as np
 import pytest
 import torch
 
+import helpers as H
 import ppo_pixel_window_cases as PP
 import ppo_window_cases as PW
 
@@ -48,18 +49,6 @@ def _step_inputs(n, D, A, pixel, S, N, adv, tau, episode_len, cap, cursor, Hl, c
     return r, mu
 
 
-def _to(r, dev):
-    out = {}
-    for k, v in r.items():
-        if torch.is_tensor(v):
-            out[k] = v.to(dev).contiguous()
-        elif isinstance(v, dict):
-            out[k] = {kk: vv.to(dev).contiguous() for kk, vv in v.items()}
-        else:
-            out[k] = v
-    return out
-
-
 # episodes of 12, (n_step, advance) = (4, 2): windows close at tau = 3, 5, 7, 9, 11 (the terminal step); (5, 5): at 4 and 9,
 # so tau = 11 ends an episode without a closing window.  (tau, N, adv, Hl, cells given, eps given)
 STEPS = [(2, 4, 2, 12, True, True),          # a window start, nothing closes
@@ -81,7 +70,7 @@ def test_step_matches_the_double(pixel, tau, N, adv, Hl, cells, eps, n, S):
     D, A, cap = 17, 6, 300
     cursor = cap - n // 2                                        # the rows wrap
     r, mu = _step_inputs(n, D, A, pixel, S, N, adv, tau, 12, cap, cursor, Hl, cells, eps, seed=tau + 7 * n + N)
-    want, got = _to(r, 'cpu'), _to(r, 'cuda')
+    want, got = H.tensors_to(r, 'cpu'), H.tensors_to(r, 'cuda')
     PP.PpoPixelWindowCpuKernels().synth_ppo_pixel_window_step(want, mu.clone())
     KN.HipKernels().synth_ppo_pixel_window_step(got, mu.cuda())
     torch.cuda.synchronize()
@@ -124,7 +113,7 @@ def test_device_path_matches_host_path(n, n_step, stride, rnn_hidden, stacks, us
     L_ = {7: 19, 5: 20, 4: 12, 25: 45}[n_step]
     calls = [L_ - 3, 5, L_ + 2, L_ // 2]
     steps = sum(calls)
-    closing = PP.closing_steps(0, steps, L_, n_step, stride)
+    closing = PW.closing_steps(0, steps, L_, n_step, stride)
     total = n * len(closing)
     assert steps > 2 * L_ and L_ - 1 in closing
     kw = dict(hidden=(64, 32), rnn_hidden=rnn_hidden, use_z=use_z, feat=32, memory_size=total + 7, final_scale=1.0)
@@ -140,7 +129,7 @@ def test_device_path_matches_host_path(n, n_step, stride, rnn_hidden, stacks, us
         s0 += T
     torch.cuda.synchronize()
     assert written == total == want['obs'].shape[0] == len(replay)
-    ring = PP.device_ring(replay)
+    ring = H.device_ring(replay)
     floats = [k for k in want if k not in ('pixel', 'pixel_next', 'dones')]
     for k in floats:
         g, w = ring[k][:total].reshape(want[k].shape), want[k]

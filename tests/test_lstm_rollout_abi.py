@@ -1,24 +1,8 @@
 """CPU tier: struct smx_synth_lstm_rollout as gcc lays it out (include/surreal_amd.h) against its ctypes mirror, and
 the host-side shape rules of its entry points (no GPU needed)."""
 import ctypes
-import os
-import subprocess
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def _offsets(tmp_path, cname, cls):
-    lines = ['#include <stdio.h>', '#include <stddef.h>', '#include "surreal_amd.h"', 'int main(void) {',
-             '  printf("sizeof %%zu\\n", sizeof(%s));' % cname]
-    for fname, _ in cls._fields_:
-        lines.append('  printf("%s %%zu\\n", offsetof(%s, %s));' % (fname, cname, fname))
-    lines += ['  return 0;', '}']
-    src = tmp_path / 'layout.c'
-    src.write_text('\n'.join(lines))
-    exe = tmp_path / 'layout'
-    subprocess.run(['gcc', '-I', os.path.join(ROOT, 'include'), str(src), '-o', str(exe)], check=True)
-    out = subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout
-    return {k: int(v) for k, v in (ln.split() for ln in out.splitlines())}
+from helpers import _offsets
 
 
 def test_lstm_rollout_struct_matches_the_ctypes_mirror(tmp_path):

@@ -11,9 +11,10 @@ import numpy as np
 import pytest
 import torch
 
+import helpers as H
 import ppo_pixel_window_cases as PP
 import ppo_window_cases as PW
-from test_lstm_rollout_abi import _offsets
+from helpers import _offsets
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PIXEL = (2, 20, 24)
@@ -70,7 +71,7 @@ def test_windows_equal_the_host_wrapper(pixel_double, rnn_hidden, use_z, n_step,
                                                          use_z=use_z)
     steps = sum(chunks)
     assert pixel_double.pixel_steps == steps and pixel_double.window_launches == 0
-    closing = PP.closing_steps(0, steps, episode_len, n_step, stride)
+    closing = PW.closing_steps(0, steps, episode_len, n_step, stride)
     assert episode_len - 1 in closing                                  # windows that close at a terminal step
     assert rows == n * len(closing) == want['obs'].shape[0] > 0
     keys = set(PP.FIELDS) | ({'cells'} if rnn_hidden else set())
@@ -139,7 +140,7 @@ def test_one_call_equals_uneven_chunks(pixel_double, rnn_hidden):
             s0 += T
         outs.append((rows, _state_of(venv, agent, replay)))
     (ra, a), (rb, b) = outs
-    assert ra == rb == n * len(PP.closing_steps(0, steps, L_, 7, 3)) and set(a) == set(b)
+    assert ra == rb == n * len(PW.closing_steps(0, steps, L_, 7, 3)) and set(a) == set(b)
     for k in a:
         assert torch.equal(a[k], b[k]), k
 
@@ -163,7 +164,7 @@ def test_ring_wraps_and_untouched_rows_stay_zero(pixel_double):
             s0 += T
         cap = memory_size + 3
         assert rows == total and (total > cap) == (memory_size == 20) and len(replay) == min(total, cap)
-        ring = PP.device_ring(replay)
+        ring = H.device_ring(replay)
         for i in range(max(0, total - cap), total):        # the last `cap` windows are where the device put them
             for k in want:
                 _assert_bits(ring[k][i % cap], want[k][i].reshape(-1), (k, i))

@@ -4,7 +4,7 @@ import ctypes
 
 import pytest
 
-from test_lstm_rollout_abi import _offsets
+from helpers import _offsets
 
 SMX_E_NULL, SMX_E_SHAPE, SMX_E_UNSUPPORTED = -1, -2, -3
 
