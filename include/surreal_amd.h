@@ -737,10 +737,33 @@ int smx_synth_frame_u8(const float* s0, int64_t ld_s0, int32_t n, int32_t C, int
  *   done_roll[a, slot] = (t + 1 >= episode_len); on done the state resets to
  *   init_state[a, :] (a fresh episode), mirroring Agent.main_loop's reset.
  * Rolls may be NULL (pure stepping). */
+
+/* The episode monitor of the device actors (surreal/env/monitor.py:11-75 EpisodeMonitor, which wraps one host env):
+ * what every launch that evaluates the synthetic reward keeps per actor a when ep_reward != NULL, from call to call:
+ *   every step:  ep_reward[a] += (double)reward (the fp32 reward of the step, added in step order); ep_steps[a] += 1
+ *   on done:     e = ep_count[a]; done_reward[a, e % capacity] = ep_reward[a]; done_steps[a, e % capacity] = ep_steps[a];
+ *                ep_count[a] = e + 1; ep_reward[a] = 0; ep_steps[a] = 0
+ * so ep_reward / ep_steps [n] are the open episode, ep_count [n] the episodes finished since the monitor was attached,
+ * done_reward / done_steps [n, capacity] a ring of the last `capacity` finished episodes per actor.  One lane owns an
+ * actor's words (the lane that forms its reward), no atomics: a sum depends on the order of its steps only.  The
+ * persistent kernels hold the open pair in LDS over their steps (HBM at entry, at a closing step and at exit).
+ * ep_reward == NULL: no monitor -- the launch does exactly what it does without one (all five pointers or none, and
+ * capacity > 0, else SMX_E_NULL / SMX_E_SHAPE). */
+struct smx_episode_monitor {               /* (by tag: no typedef) */
+    double* ep_reward;
+    int32_t* ep_steps;
+    int64_t* ep_count;
+    double* done_reward;
+    int32_t* done_steps;
+    int32_t capacity, reserved;
+};
+
+/* mon: NULL, or the episode monitor above */
 int smx_synth_env_step_f32(float* state, const float* init_state, const float* actions,
                            int32_t n, int32_t D, int32_t A, int32_t t, int32_t episode_len,
                            int32_t slot, int32_t T, float* obs_roll, float* act_roll,
-                           float* rew_roll, float* done_roll, smx_stream_t stream);
+                           float* rew_roll, float* done_roll, const struct smx_episode_monitor* mon,
+                           smx_stream_t stream);
 
 /* One launch between two policy forwards of a device-resident rollout: the acting head
  * (smx_diaggauss_sample_f32 on `mean`), the environment step above with the sampled action, and the
@@ -766,6 +789,7 @@ typedef struct smx_synth_act_step {
     const float* zcount;
     float zeps, reserved_f;
     float* xn_out;
+    struct smx_episode_monitor mon;        /* mon.ep_reward NULL: none */
 } smx_synth_act_step_t;
 int smx_synth_act_env_step_f32(const smx_synth_act_step_t* args, smx_stream_t stream);
 /* The same launch with the policy's output layer folded in (PPOAgent.act's last Linear + Tanh, surreal/model/
@@ -1040,6 +1064,7 @@ typedef struct smx_synth_rollout {
     float* pd_roll;
     float* obs_last;
     int32_t actors_per_workgroup;          /* 4 | 8 | 16, 0: the smallest whose grid fits the CUs once */
+    struct smx_episode_monitor mon;        /* mon.ep_reward NULL: none */
 } smx_synth_rollout_t;
 int32_t smx_synth_rollout_supported(int32_t D, int32_t H1, int32_t H2, int32_t A);
 int smx_synth_rollout_f32(const smx_synth_rollout_t* args, smx_stream_t stream);
@@ -1174,6 +1199,7 @@ struct smx_ddpg_rollout {
     float* rewards;
     float* dones;
     int64_t cursor, capacity;
+    struct smx_episode_monitor mon;        /* mon.ep_reward NULL: none */
 };
 typedef struct smx_ddpg_rollout smx_ddpg_rollout_t;
 /* shapes smx_synth_ddpg_rollout_f32 takes: A <= 32, H1 and H2 multiples of 4 up to 640, D <= 512 */
@@ -1270,6 +1296,7 @@ struct smx_synth_ppo_pixel_window_step {   /* (by tag: no typedef) */
     uint8_t* pixel;                        /* [capacity, N, S*F] */
     uint8_t* pixel_next;                   /* [capacity, S*F] */
     uint8_t* obs_pixel;                    /* [n, S*F] */
+    struct smx_episode_monitor mon;        /* mon.ep_reward NULL: none */
 };
 int smx_synth_ppo_pixel_window_step(const struct smx_synth_ppo_pixel_window_step* args, const float* mu, int64_t ld_mu,
                                     smx_stream_t stream);

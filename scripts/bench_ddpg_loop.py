@@ -44,6 +44,10 @@ def main():
     ap.add_argument('--chunk-steps', type=int, default=16)
     ap.add_argument('--learn-iters', type=int, default=16)
     ap.add_argument('--batch', type=int, default=512)
+    ap.add_argument('--episode-len', type=int, default=1000)
+    ap.add_argument('--monitor', action='store_true',
+                    help='attach the on-device episode monitor: every line also carries mean_episode_return, the mean of '
+                         'the last 10 polled episode returns per actor (null before an episode has finished)')
     args = ap.parse_args()
     n, T, D, A = args.actors, args.steps, args.obs_dim, args.action_dim
     H1, H2 = args.hidden
@@ -55,7 +59,14 @@ def main():
     ec, sc = ddpg_env_config(D, A, num_agents=n), ddpg_session_config()
     agent = DDPGAgent(lc, ec, sc, agent_id=0, agent_mode='training')
     flops = 2.0 * n * T * (D * H1 + H1 * H2 + H2 * A)
-    venv = SyntheticVecEnv(n, D, A, episode_len=1000, device='cuda')
+    venv = SyntheticVecEnv(n, D, A, episode_len=args.episode_len, device='cuda')
+    mon = venv.attach_monitor() if args.monitor else None
+
+    def returns(line):
+        if mon is not None:
+            mon.poll()
+            line.update(mean_episode_return=mon.mean_reward(last=10), episodes=mon.num_episodes, monitor=True)
+        return line
     eps = torch.randn(T, n, A, device='cuda')
     results = {}
     for path in ('persistent', 'per_step'):
@@ -82,7 +93,7 @@ def main():
              'ms_per_rollout': round(dev * 1e3, 4), 'wall_ms_per_rollout': round(wall * 1e3, 4),
              'env_steps_per_s': n * T / dev, 'actor_tflops': flops / dev / 1e12,
              'share_of_fp32_matrix_peak': flops / dev / FP32_MATRIX_PEAK, 'replay_rows': len(replay)}
-        results[path] = r
+        results[path] = returns(r)
         print(json.dumps(r), flush=True)
 
     # ---- the off-policy loop: rollout chunk -> learn iterations from the ring ------------------------------------------
@@ -115,7 +126,7 @@ def main():
             'env_steps_per_s': n * Tc * args.loop_chunks / wall,
             'learner_samples_per_s': B * args.learn_iters * args.loop_chunks / wall,
             'critic_loss': float(st['critic_loss']), 'replay_rows': len(replay)}
-    print(json.dumps(loop), flush=True)
+    print(json.dumps(returns(loop)), flush=True)
     # the persistent kernel at each forced block size (the automatic pick above: 4 actors per workgroup up to one
     # workgroup per CU)
     for apw in (4, 8, 16):

@@ -40,7 +40,7 @@ def _timed(fn):
     return a.elapsed_time(b)
 
 
-def bench_rollouts(reps, warmup, shapes):
+def bench_rollouts(reps, warmup, shapes, monitor=False):
     lines = []
     for n, T, D, A, hidden, H, (N, stride), L in shapes:
         agent, cfg = PW.make_agent(D, A, N, stride, hidden=hidden, rnn_hidden=H, memory_size=n * (T // min(N, stride)
@@ -48,6 +48,7 @@ def bench_rollouts(reps, warmup, shapes):
         replay = FIFOReplay(*cfg)
         win = SyntheticVecEnv(n, D, A, episode_len=L)
         tab = SyntheticVecEnv(n, D, A, episode_len=L)
+        mon = win.attach_monitor() if monitor else None
         tab.start_rollout(T, info_width=2 * A)
         eps = torch.randn(T, n, A, device='cuda')
         times = {'window': [], 'rollout': []}
@@ -74,11 +75,14 @@ def bench_rollouts(reps, warmup, shapes):
                       'n_step': N, 'stride': stride, 'episode_len': L, 'reps': reps,
                       'windows_per_call': sorted(set(rows)), 'ppo_rollout_into_ms': w, 'rollout_ms': t,
                       'ratio_median': w['median'] / t['median']})
+        if mon is not None:
+            mon.poll()
+            lines[-1].update(mean_episode_return=mon.mean_reward(last=10), episodes=mon.num_episodes)
         print(json.dumps(lines[-1]), flush=True)
     return lines
 
 
-def bench_loop(reps, warmup, n=64, T=128, L=1000, D=17, A=6):
+def bench_loop(reps, warmup, n=64, T=128, L=1000, D=17, A=6, monitor=False):
     """configs[1]'s shape with the reference-default algo config: env-steps/s of chunk -> FIFO -> learn"""
     from surreal_amd.learner import PPOLearner
     agent, cfg = PW.make_agent(D, A, 25, 20, hidden=(300, 200), rnn_hidden=100, memory_size=8 * n, batch_size=64)
@@ -88,6 +92,7 @@ def bench_loop(reps, warmup, n=64, T=128, L=1000, D=17, A=6):
     agent.fetch_parameter()
     replay = FIFOReplay(lc, ec, sc)
     venv = SyntheticVecEnv(n, D, A, episode_len=L)
+    mon = venv.attach_monitor() if monitor else None
     learned = [0]
 
     def chunk():
@@ -107,6 +112,9 @@ def bench_loop(reps, warmup, n=64, T=128, L=1000, D=17, A=6):
             'rnn_hidden': 100, 'horizon': lc.algo.rnn.horizon, 'reps': reps, 'chunk_ms': s,
             'env_steps_per_s': {'at_median': n * T / (s['median'] * 1e-3), 'at_min_ms': n * T / (s['min'] * 1e-3),
                                 'at_max_ms': n * T / (s['max'] * 1e-3)}, 'windows_learned': learned[0]}
+    if mon is not None:
+        mon.poll()
+        line.update(mean_episode_return=mon.mean_reward(last=10), episodes=mon.num_episodes)
     print(json.dumps(line), flush=True)
     return [line]
 
@@ -117,9 +125,12 @@ def main():
     ap.add_argument('--warmup', type=int, default=2)
     ap.add_argument('--out', default=None)
     ap.add_argument('--quick', action='store_true', help='one repetition of each case (for a kernel trace)')
+    ap.add_argument('--monitor', action='store_true',
+                    help='attach the on-device episode monitor: every line also carries mean_episode_return, the mean of '
+                         'the last 10 polled episode returns per actor (null before an episode has finished)')
     args = ap.parse_args()
     reps, warmup = (1, 1) if args.quick else (args.reps, args.warmup)
-    lines = bench_rollouts(reps, warmup, ROLLOUTS) + bench_loop(reps, warmup)
+    lines = bench_rollouts(reps, warmup, ROLLOUTS, args.monitor) + bench_loop(reps, warmup, monitor=args.monitor)
     if args.out:
         with open(args.out, 'w') as f:
             for ln in lines:

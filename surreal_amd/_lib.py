@@ -145,6 +145,12 @@ class GatherJob(Structure):
     _fields_ = [('table', c_void_p), ('dst', c_void_p), ('row_bytes', c_int64)]
 
 
+class EpisodeMonitor(Structure):
+    """struct smx_episode_monitor"""
+    _fields_ = [('ep_reward', c_void_p), ('ep_steps', c_void_p), ('ep_count', c_void_p), ('done_reward', c_void_p),
+                ('done_steps', c_void_p), ('capacity', c_int32), ('reserved', c_int32)]
+
+
 class SynthRollout(Structure):
     """smx_synth_rollout_t"""
     _fields_ = [('net', POINTER(Mlp3)), ('packed', c_void_p), ('out_act', c_int32), ('n', c_int32),
@@ -153,7 +159,7 @@ class SynthRollout(Structure):
                 ('episode_len', c_int32), ('steps', c_int32), ('rows_per_actor', c_int32), ('slot', c_int32),
                 ('state', c_void_p), ('init_state', c_void_p), ('obs_roll', c_void_p), ('act_roll', c_void_p),
                 ('rew_roll', c_void_p), ('done_roll', c_void_p), ('pd_roll', c_void_p), ('obs_last', c_void_p),
-                ('actors_per_workgroup', c_int32)]
+                ('actors_per_workgroup', c_int32), ('mon', EpisodeMonitor)]
 
 
 class SynthLstmRollout(Structure):
@@ -181,7 +187,7 @@ class DdpgRollout(Structure):
                 ('gpow', c_void_p), ('ou', c_void_p), ('state', c_void_p), ('init_state', c_void_p),
                 ('carry_obs', c_void_p), ('carry_act', c_void_p), ('carry_rew', c_void_p), ('obs', c_void_p),
                 ('obs_next', c_void_p), ('actions', c_void_p), ('rewards', c_void_p), ('dones', c_void_p),
-                ('cursor', c_int64), ('capacity', c_int64)]
+                ('cursor', c_int64), ('capacity', c_int64), ('mon', EpisodeMonitor)]
 
 
 class DdpgPixelStep(Structure):
@@ -200,7 +206,7 @@ class SynthPpoPixelWindowStep(Structure):
                 [('cursor', c_int64), ('capacity', c_int64)] +
                 [(n, c_int32) for n in ('C', 'H', 'W', 'frame_stacks', 'hist_len', 'hist_pos', 'copy_workgroups',
                                         'reserved')] +
-                [(n, c_void_p) for n in ('hist', 'pixel', 'pixel_next', 'obs_pixel')])
+                [(n, c_void_p) for n in ('hist', 'pixel', 'pixel_next', 'obs_pixel')] + [('mon', EpisodeMonitor)])
 
 
 SMX_DDPG_NOISE_NONE, SMX_DDPG_NOISE_GAUSSIAN, SMX_DDPG_NOISE_OU = 0, 1, 2
@@ -220,7 +226,8 @@ class SynthActStep(Structure):
                 ('slot', c_int32), ('T', c_int32), ('reserved', c_int32),
                 ('obs_roll', c_void_p), ('act_roll', c_void_p), ('rew_roll', c_void_p),
                 ('done_roll', c_void_p), ('pd_roll', c_void_p), ('zsum', c_void_p), ('zsumsq', c_void_p),
-                ('zcount', c_void_p), ('zeps', c_float), ('reserved_f', c_float), ('xn_out', c_void_p)]
+                ('zcount', c_void_p), ('zeps', c_float), ('reserved_f', c_float), ('xn_out', c_void_p),
+                ('mon', EpisodeMonitor)]
 
 
 # smx_ppo_ctrl_t as 16 x 4-byte words: index of each field (floats 0-9, int32 10-15)
@@ -339,7 +346,7 @@ _SIGS = {
                                       c_int32, _P, _P]),
     'smx_synth_act_env_step_f32': (c_int32, [POINTER(SynthActStep), _P]),
     'smx_synth_env_step_f32': (c_int32, [_P, _P, _P, c_int32, c_int32, c_int32, c_int32, c_int32,
-                                         c_int32, c_int32, _P, _P, _P, _P, _P]),
+                                         c_int32, c_int32, _P, _P, _P, _P, POINTER(EpisodeMonitor), _P]),
     'smx_ddpg_critic_loss_f32': (c_int32, [_P, _P, _P, _P, c_float, c_int64, _P, _P, _P]),
     'smx_tanh_backward_f32': (c_int32, [_P, _P, c_int64, _P, _P]),
     'smx_fill_f32': (c_int32, [_P, c_int64, c_float, _P]),

@@ -5,6 +5,7 @@
 // is one [capacity, width] fp32 table in HBM and insert/sample are coalesced row copies: one
 // wavefront moves one row with 16-byte lanes when the width allows.
 #include "smx_common.h"
+#include <string.h>
 
 namespace {
 
@@ -283,7 +284,7 @@ __global__ __launch_bounds__(256) void synth_env_step_kernel(
     float* __restrict__ state, const float* __restrict__ init_state,
     const float* __restrict__ actions, int n, int D, int A, int t, int episode_len, int slot, int T,
     float* __restrict__ obs_roll, float* __restrict__ act_roll, float* __restrict__ rew_roll,
-    float* __restrict__ done_roll) {
+    float* __restrict__ done_roll, smx_episode_monitor mon) {
     const long i = (long)blockIdx.x * 256 + threadIdx.x;
     if (i >= (long)n * D) return;
     const long a = i / D;
@@ -309,8 +310,10 @@ __global__ __launch_bounds__(256) void synth_env_step_kernel(
             float av = fminf(fmaxf(actions[a * A + j], -1.0f), 1.0f);
             q += (double)av * (double)av;
         }
-        if (rew_roll) rew_roll[a * T + slot] = synth_reward(q, sn);
+        const float rew = synth_reward(q, sn);
+        if (rew_roll) rew_roll[a * T + slot] = rew;
         if (done_roll) done_roll[a * T + slot] = done ? 1.0f : 0.0f;
+        if (mon.ep_reward) episode_account(mon, a, rew, done);
     }
     state[i] = done ? init_state[i] : sn;
 }
@@ -357,8 +360,10 @@ __global__ __launch_bounds__(256) void synth_act_env_step_kernel(smx_synth_act_s
             const float av = action(j, m2, s2);
             q += (double)av * (double)av;
         }
-        if (p.rew_roll) p.rew_roll[a * T + slot] = synth_reward(q, sn);
+        const float rew = synth_reward(q, sn);
+        if (p.rew_roll) p.rew_roll[a * T + slot] = rew;
         if (p.done_roll) p.done_roll[a * T + slot] = done ? 1.0f : 0.0f;
+        if (p.mon.ep_reward) episode_account(p.mon, a, rew, done);
     }
     const float next = done ? p.init_state[i] : sn;
     p.state[i] = next;
@@ -426,8 +431,10 @@ __global__ __launch_bounds__(256) void synth_act_head_step_kernel(smx_synth_act_
         if (k == 0) {
             double q = 0.0;
             for (int j = 0; j < A; ++j) q += (double)s_act[j] * (double)s_act[j];
-            if (p.rew_roll) p.rew_roll[a * T + slot] = synth_reward(q, sn);
+            const float rew = synth_reward(q, sn);
+            if (p.rew_roll) p.rew_roll[a * T + slot] = rew;
             if (p.done_roll) p.done_roll[a * T + slot] = done ? 1.0f : 0.0f;
+            if (p.mon.ep_reward) episode_account(p.mon, a, rew, done);
         }
         const float next = done ? p.init_state[i] : sn;
         p.state[i] = next;
@@ -615,6 +622,8 @@ extern "C" int smx_synth_act_env_step_f32(const smx_synth_act_step_t* args, smx_
     SMX_REQUIRE(p.n > 0 && p.D > 0 && p.A > 0 && p.A <= p.D && p.T > 0 && p.slot >= 0 && p.slot < p.T &&
                     p.episode_len > 0 && p.ld_mean >= p.A && (!p.eps || p.ld_eps >= p.A), SMX_E_SHAPE);
     SMX_REQUIRE(!p.zsum || (p.zsumsq && p.zcount && p.xn_out), SMX_E_NULL);
+    SMX_REQUIRE(episode_pointers_ok(p.mon), SMX_E_NULL);
+    SMX_REQUIRE(episode_shape_ok(p.mon), SMX_E_SHAPE);
     const long total = (long)p.n * p.D;
     hipLaunchKernelGGL(synth_act_env_step_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0,
                        smx_s(stream), p);
@@ -631,6 +640,8 @@ extern "C" int smx_synth_act_env_step_head_f32(const smx_synth_act_step_t* args,
     SMX_REQUIRE(p.n > 0 && p.D > 0 && p.A > 0 && p.A <= 32 && p.A <= p.D && p.T > 0 && p.slot >= 0 && p.slot < p.T &&
                     p.episode_len > 0 && H2 > 0 && ld_h2 >= H2 && (!p.eps || p.ld_eps >= p.A), SMX_E_SHAPE);
     SMX_REQUIRE(!p.zsum || (p.zsumsq && p.zcount && p.xn_out), SMX_E_NULL);
+    SMX_REQUIRE(episode_pointers_ok(p.mon), SMX_E_NULL);
+    SMX_REQUIRE(episode_shape_ok(p.mon), SMX_E_SHAPE);
     hipLaunchKernelGGL(synth_act_head_step_kernel, dim3((unsigned)p.n), dim3(256), 0, smx_s(stream), p, W3, b3, h2,
                        (long)ld_h2, H2, out_act);
     SMX_LAUNCH_CHECK();
@@ -641,14 +652,19 @@ extern "C" int smx_synth_env_step_f32(float* state, const float* init_state, con
                                       int32_t n, int32_t D, int32_t A, int32_t t,
                                       int32_t episode_len, int32_t slot, int32_t T, float* obs_roll,
                                       float* act_roll, float* rew_roll, float* done_roll,
-                                      smx_stream_t stream) {
+                                      const struct smx_episode_monitor* mon, smx_stream_t stream) {
     SMX_REQUIRE(state && init_state && actions, SMX_E_NULL);
     SMX_REQUIRE(n > 0 && D > 0 && A > 0 && A <= D && T > 0 && slot >= 0 && slot < T && episode_len > 0,
                 SMX_E_SHAPE);
+    smx_episode_monitor M;
+    memset(&M, 0, sizeof(M));
+    if (mon) M = *mon;
+    SMX_REQUIRE(episode_pointers_ok(M), SMX_E_NULL);
+    SMX_REQUIRE(episode_shape_ok(M), SMX_E_SHAPE);
     const long total = (long)n * D;
     hipLaunchKernelGGL(synth_env_step_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0,
                        smx_s(stream), state, init_state, actions, n, D, A, t, episode_len, slot, T,
-                       obs_roll, act_roll, rew_roll, done_roll);
+                       obs_roll, act_roll, rew_roll, done_roll, M);
     SMX_LAUNCH_CHECK();
     return SMX_OK;
 }

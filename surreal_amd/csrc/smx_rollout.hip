@@ -41,6 +41,10 @@
 // slots in HBM, slot tau % n_step for episode step tau: every value is written and later read by the SAME lane, so no
 // barrier orders them, and they carry from one call to the next.  Transition j = tau - n_step + 1 closes at step tau;
 // the k-th closing step of a call writes actor a to ring row (cursor + k n + a) mod capacity.
+//
+// Episode monitor (struct smx_episode_monitor; mon.ep_reward null: none): the lane that forms an actor's reward also keeps
+// its open episode's fp64 reward sum and length (episode_step, smx_synth_env.inc.h) -- in LDS behind the layout in the
+// persistent kernels (HBM at entry, at a closing step, at exit), in HBM in the step kernels.
 #include "smx_common.h"
 #include <string.h>
 
@@ -80,6 +84,8 @@ struct RollBase {
     float* state;                               // [n, D] in / out
     const float* init_state;
     int ldx, ldh1, ldh2, off_h1, off_h2, off_out, off_act, off_red3, off_z, off_kmod;
+    smx_episode_monitor mon;                    // mon.ep_reward null: none
+    int off_ep;                                 // the open episodes of the block's actors in LDS (carve_episodes())
 };
 
 struct RollArgs : RollBase {
@@ -153,6 +159,9 @@ struct EnvLanes {
     float* xs;                                  // the x tile
     const float* zm;                            // the z-filter's [D] mean | [D] std in LDS, or null: raw observations
     const int* kmod;
+    const smx_episode_monitor mon;              // (touched at entry, at closing steps and at exit only)
+    double* ep_reward;                          // [RB] the open episodes' sums, then [RB] int their steps, in LDS: each
+    int* ep_steps;                              // pair is read and written by the lane that forms its actor's reward
     long row0;
     int nrows, lane, erow0, part;
     float st[RPW][KPL];
@@ -162,9 +171,20 @@ struct EnvLanes {
     // the states of the block's actors to registers
     __device__ __forceinline__ EnvLanes(const RollBase& G, float* sm, const float* zm_, int wv, int lane_)
         : D(G.D), ldx(G.ldx), state(G.state), init_state(G.init_state), xs(sm), zm(zm_), kmod((const int*)(sm + G.off_kmod)),
+          mon(G.mon), ep_reward((double*)(sm + G.off_ep)), ep_steps((int*)(sm + G.off_ep + 2 * RB)),
           row0((long)blockIdx.x * RB), lane(lane_), erow0(RPW * (wv / WPR)), part(wv % WPR) {
         nrows = G.n - (int)row0;
         if (nrows > RB) nrows = RB;
+        if (mon.ep_reward && owner()) {
+#pragma unroll
+            for (int rr = 0; rr < RPW; ++rr) {
+                const int r = erow0 + rr;
+                if (r < nrows) {
+                    ep_reward[r] = mon.ep_reward[row0 + r];
+                    ep_steps[r] = mon.ep_steps[row0 + r];
+                }
+            }
+        }
 #pragma unroll
         for (int i = 0; i < KPL; ++i) {
             const int k = kel(i);
@@ -176,6 +196,8 @@ struct EnvLanes {
         }
     }
     __device__ __forceinline__ int kel(int i) const { return lane + 64 * (part + WPR * i); }
+    // the lane that forms the rewards of the wave's actor rows (k == 0 lives in lane 0, i == 0 of a row's first wave)
+    __device__ __forceinline__ bool owner() const { return lane == 0 && part == 0; }
     __device__ __forceinline__ void put_x(int r, int k, float v) {
         xs[r * ldx + k] = zm ? zclamp(v, zm[k], zm[D + k]) : v;
     }
@@ -225,7 +247,7 @@ struct EnvLanes {
                         put_x(r, k, next);
                     }
                 }
-                if (lane == 0 && part == 0) {           // (k == 0 lives in lane 0, i == 0 of the row's first wave)
+                if (owner()) {
                     // sum_j a_j^2 in fp64, j ascending (the order of smx_synth_env_step_f32).  All RMAX_A reads are
                     // issued up front (unused columns of the tile are zero and add +0.0): one LDS round trip, not A
                     float av[RMAX_A];
@@ -234,7 +256,9 @@ struct EnvLanes {
                     double q = 0.0;
 #pragma unroll
                     for (int j = 0; j < RMAX_A; ++j) q += (double)av[j] * (double)av[j];
-                    close(a, p, synth_reward(q, sn0));
+                    const float rew = synth_reward(q, sn0);
+                    close(a, p, rew);
+                    if (mon.ep_reward) episode_step(mon, a, ep_reward[r], ep_steps[r], rew, done);
                 }
             }
         }
@@ -248,6 +272,10 @@ struct EnvLanes {
             for (int i = 0; i < KPL; ++i) {
                 const int k = kel(i);
                 if (k < D && r < nrows) state[(row0 + r) * D + k] = st[rr][i];
+            }
+            if (mon.ep_reward && owner() && r < nrows) {
+                mon.ep_reward[row0 + r] = ep_reward[r];
+                mon.ep_steps[row0 + r] = ep_steps[r];
             }
         }
     }
@@ -1001,11 +1029,13 @@ __device__ __forceinline__ float ddpg_step_env(const DArgs& G, long a, int lane,
             q += v * v;
         }
         float* cr = G.crew + (size_t)a * N;
-        cr[slot] = synth_reward(q, sn0);
+        const float rew = synth_reward(q, sn0);
+        cr[slot] = rew;
         if (emit) {
             G.rew[row] = nstep_reward(cr, G.gpow, N, tau);
             G.done[row] = done ? 1.0f : 0.0f;
         }
+        if (G.mon.ep_reward) episode_account(G.mon, a, rew, done);
     }
     return sn0;
 }
@@ -1209,6 +1239,7 @@ struct PWArgs {
     const float* init_state;
     const float *h_before, *c_before;          // [n, Hl] the LSTM state before this step, or null
     WinArgs W;                                 // (W.cursor: the row of actor 0 at this step)
+    smx_episode_monitor mon;                   // mon.ep_reward null: none
 };
 
 template <int U>
@@ -1273,7 +1304,8 @@ __global__ __launch_bounds__(256) void ppo_pixel_window_step_kernel(PWArgs G, PA
                 q += v * v;
             }
             float* cr = W.crew + (size_t)a * N;
-            cr[wslot] = synth_reward(q, sn0);
+            const float rew = synth_reward(q, sn0);
+            cr[wslot] = rew;
             if (wclose) {
                 float* dr = W.rew + row * N;
                 float* dd = W.done + row * N;
@@ -1283,6 +1315,7 @@ __global__ __launch_bounds__(256) void ppo_pixel_window_step_kernel(PWArgs G, PA
                                       dd[u] = (done && u == N - 1) ? 1.0f : 0.0f;
                                   });
             }
+            if (G.mon.ep_reward) episode_account(G.mon, a, rew, done);
             s_sn0 = sn0;
         }
         if (W.ccell) {
@@ -1351,6 +1384,15 @@ int32_t supported(int32_t D, int32_t H1, int32_t H2, int32_t A, bool mma16, bool
     return carve(G, 16, mma16, split_out, ztables, D) <= ROLL_MAX_LDS;
 }
 
+// With a monitor the open episodes of the block's rb actors follow the layout of `lds` bytes: [rb] fp64 sums on 8 bytes,
+// then [rb] int32 step counts -> the bytes with them (without one: `lds` as it is, and the kernels never read off_ep)
+constexpr int ROLL_EP_LDS = 8 + 16 * 12;         // (what 16 actors add at most: launch()'s dynamic-LDS limit has it)
+int carve_episodes(RollBase& G, int rb, int lds) {
+    if (!G.mon.ep_reward) return lds;
+    G.off_ep = ((lds + 7) & ~7) / (int)sizeof(float);
+    return G.off_ep * (int)sizeof(float) + rb * 12;
+}
+
 // ---- LSTM stem ---------------------------------------------------------------------------------------------------
 
 __host__ __device__ inline int lstm_dp(int D) { return (D + 3) & ~3; }
@@ -1406,10 +1448,13 @@ int pick_block(int forced, int n) {
 // at its first launch
 template <auto K, typename Args>
 int launch(const Args& G, int rb, int lds, smx_stream_t stream) {
-    static const hipError_t attr = hipFuncSetAttribute((const void*)K, hipFuncAttributeMaxDynamicSharedMemorySize, ROLL_MAX_LDS);
+    static const hipError_t attr = hipFuncSetAttribute((const void*)K, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                                       ROLL_MAX_LDS + ROLL_EP_LDS);
     (void)attr;
+    Args A = G;
+    lds = carve_episodes(A, rb, lds);
     if (lds < ROLL_EXCLUSIVE_LDS) lds = ROLL_EXCLUSIVE_LDS;
-    hipLaunchKernelGGL(K, dim3((G.n + rb - 1) / rb), dim3(RNTH), lds, smx_s(stream), G);
+    hipLaunchKernelGGL(K, dim3((A.n + rb - 1) / rb), dim3(RNTH), lds, smx_s(stream), A);
     SMX_LAUNCH_CHECK();
     return SMX_OK;
 }
@@ -1431,7 +1476,10 @@ int common_args(const smx_ddpg_rollout_t* a, DArgs& G) {
     SMX_REQUIRE(a->noise_type >= SMX_DDPG_NOISE_NONE && a->noise_type <= SMX_DDPG_NOISE_OU, SMX_E_SHAPE);
     SMX_REQUIRE(a->noise_type == SMX_DDPG_NOISE_NONE || (a->eps && a->sigmas), SMX_E_NULL);
     SMX_REQUIRE(a->noise_type != SMX_DDPG_NOISE_OU || a->ou, SMX_E_NULL);
+    SMX_REQUIRE(episode_pointers_ok(a->mon), SMX_E_NULL);
+    SMX_REQUIRE(episode_shape_ok(a->mon), SMX_E_SHAPE);
     memset(&G, 0, sizeof(G));
+    G.mon = a->mon;
     G.D = a->D; G.A = a->A; G.n = a->n; G.steps = a->steps; G.t0 = a->t; G.episode_len = a->episode_len;
     G.N = a->n_step; G.noise = a->noise_type;
     G.eps = a->noise_type == SMX_DDPG_NOISE_NONE ? nullptr : a->eps;
@@ -1476,6 +1524,7 @@ void roll_fields(const smx_synth_rollout_t* a, int D, RollArgs& G) {
     G.zsum = a->zsum; G.zsumsq = a->zsumsq; G.zcount = a->zcount; G.zeps = a->zeps;
     G.state = a->state; G.init_state = a->init_state;
     G.n = a->n; G.t0 = a->t; G.episode_len = a->episode_len; G.steps = a->steps;
+    G.mon = a->mon;
 }
 
 // the rollout tables (the windowed kernels have none)
@@ -1532,7 +1581,9 @@ int launch_pixel(const Args& G, const PArgs& P, int n, const float* mu, int64_t 
 // ---- the rules the entry points share (the SMX_REQUIRE at the call names the code) ---------------------------------
 
 bool block_ok(int apw) { return apw == 0 || apw == 4 || apw == 8 || apw == 16; }      // actors_per_workgroup
-bool roll_pointers(const smx_synth_rollout_t* a) { return a->net && a->packed && a->log_var && a->state && a->init_state; }
+bool roll_pointers(const smx_synth_rollout_t* a) {
+    return a->net && a->packed && a->log_var && a->state && a->init_state && episode_pointers_ok(a->mon);
+}
 // the z-filter's running sums: all three or none
 bool zfilter_ok(const smx_synth_rollout_t* a) {
     return (a->zsum == nullptr) == (a->zsumsq == nullptr) && (a->zsum == nullptr) == (a->zcount == nullptr);
@@ -1546,7 +1597,7 @@ bool aligned_ok(const float* packed, const float* b1, const float* lstm_packed) 
 bool rollout_shape_ok(const smx_synth_rollout_t* a, const void* cells) {
     const bool records = a->obs_roll || a->act_roll || a->rew_roll || a->done_roll || a->pd_roll || cells;
     return a->n > 0 && a->steps > 0 && a->episode_len > 0 && a->rows_per_actor > 0 && block_ok(a->actors_per_workgroup) &&
-           a->slot >= 0 && (!records || a->slot + a->steps <= a->rows_per_actor);
+           a->slot >= 0 && (!records || a->slot + a->steps <= a->rows_per_actor) && episode_shape_ok(a->mon);
 }
 bool cell_pairs_ok(const float* h0, const float* c0, const float* h_before, const float* c_before) {
     return (h_before == nullptr) == (c_before == nullptr) && (h0 == nullptr) == (c0 == nullptr);
@@ -1667,7 +1718,7 @@ extern "C" int smx_synth_ppo_window_rollout_f32(const smx_synth_ppo_window_rollo
     SMX_REQUIRE(smx_synth_ppo_window_rollout_supported(lstm ? b.lstm->D : n.D, lstm ? b.lstm->H : 0, n.H1, n.H2, n.OUT),
                 SMX_E_UNSUPPORTED);
     SMX_REQUIRE(a->n > 0 && a->steps > 0 && a->episode_len > 0 && a->t >= 0 && a->t < a->episode_len, SMX_E_SHAPE);
-    SMX_REQUIRE(block_ok(a->actors_per_workgroup) && window_shape_ok(*args), SMX_E_SHAPE);
+    SMX_REQUIRE(block_ok(a->actors_per_workgroup) && window_shape_ok(*args) && episode_shape_ok(a->mon), SMX_E_SHAPE);
     // two workgroups must never write the same FIFO row: all n m rows of the call are distinct
     const long long m = closing_steps(a->t, a->steps, a->episode_len,
                                       [&](int t) { return window_closes(t, args->n_step, args->advance); });
@@ -1744,7 +1795,7 @@ extern "C" int smx_synth_ddpg_pixel_step(const struct smx_ddpg_pixel_step* args,
 extern "C" int smx_synth_ppo_pixel_window_step(const struct smx_synth_ppo_pixel_window_step* args, const float* mu,
                                                int64_t ld_mu, smx_stream_t stream) {
     SMX_REQUIRE(args && mu && args->log_var && args->state && args->init_state, SMX_E_NULL);
-    SMX_REQUIRE(window_pointers(*args) && pixel_pointers(*args), SMX_E_NULL);
+    SMX_REQUIRE(window_pointers(*args) && pixel_pointers(*args) && episode_pointers_ok(args->mon), SMX_E_NULL);
     SMX_REQUIRE(cell_pairs_ok(nullptr, nullptr, args->h_before, args->c_before), SMX_E_NULL);
     // an LSTM policy's cells: the ring whenever a state comes in or a window's cells go out
     SMX_REQUIRE((!args->h_before && !args->cells) || args->carry_cells, SMX_E_NULL);
@@ -1755,7 +1806,7 @@ extern "C" int smx_synth_ppo_pixel_window_step(const struct smx_synth_ppo_pixel_
     SMX_REQUIRE(args->episode_len > 0 && args->t >= 0 && args->t < args->episode_len, SMX_E_SHAPE);
     SMX_REQUIRE(window_shape_ok(*args) && step_shape_ok(args->n, args->A, ld_mu, args->capacity), SMX_E_SHAPE);
     SMX_REQUIRE(pixel_shape_ok(*args, args->n_step), SMX_E_SHAPE);
-    SMX_REQUIRE(args->copy_workgroups >= 0 && args->copy_workgroups <= 1024, SMX_E_SHAPE);
+    SMX_REQUIRE(args->copy_workgroups >= 0 && args->copy_workgroups <= 1024 && episode_shape_ok(args->mon), SMX_E_SHAPE);
     PWArgs G;
     memset(&G, 0, sizeof(G));
     G.n = args->n; G.D = args->D; G.A = args->A; G.Hl = args->hidden; G.t0 = args->t; G.episode_len = args->episode_len;
@@ -1763,6 +1814,7 @@ extern "C" int smx_synth_ppo_pixel_window_step(const struct smx_synth_ppo_pixel_
     G.state = args->state; G.init_state = args->init_state;
     G.h_before = args->h_before; G.c_before = args->c_before;
     G.W = win_fields(*args);
+    G.mon = args->mon;
     // the copy workgroups of this step: its destination frames -- (N + 1) S - 1 more at a closing step than the S - 1
     // (S + 1 on done) of any other
     const int S = args->frame_stacks;

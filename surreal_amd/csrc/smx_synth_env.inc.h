@@ -39,3 +39,39 @@ __device__ __forceinline__ float zclamp(float x, float m, float sd) {
     if (v == v) v = fminf(fmaxf(v, -5.0f), 5.0f);
     return v;
 }
+
+// ---- the episode monitor (struct smx_episode_monitor, include/surreal_amd.h) ----------------------------------------
+// The one rule every kernel that evaluates synth_reward applies when a monitor is attached (M.ep_reward != null), by
+// the ONE lane that formed actor a's reward: the step's fp32 reward joins the open episode's fp64 sum in step order;
+// on done the pair goes to slot (finished episodes) % capacity of the actor's ring and the open pair clears.  open_reward /
+// open_steps: the open pair wherever the caller holds it between steps (LDS in the persistent kernels, else HBM through
+// episode_account).  Plain stores by the owning lane only: no atomics, so a sum depends on the order of its steps alone.
+__device__ __forceinline__ void episode_step(const smx_episode_monitor& M, long a, double& open_reward, int& open_steps,
+                                             float reward, bool done) {
+    const double sum = open_reward + (double)reward;
+    const int steps = open_steps + 1;
+    if (done) {
+        const long long e = M.ep_count[a];
+        const size_t slot = (size_t)a * M.capacity + (size_t)(e % M.capacity);
+        M.done_reward[slot] = sum;
+        M.done_steps[slot] = steps;
+        M.ep_count[a] = e + 1;
+    }
+    open_reward = done ? 0.0 : sum;
+    open_steps = done ? 0 : steps;
+}
+
+// one step of an actor whose open pair lives in HBM between launches (the per-step kernels)
+__device__ __forceinline__ void episode_account(const smx_episode_monitor& M, long a, float reward, bool done) {
+    double open_reward = M.ep_reward[a];
+    int open_steps = M.ep_steps[a];
+    episode_step(M, a, open_reward, open_steps, reward, done);
+    M.ep_reward[a] = open_reward;
+    M.ep_steps[a] = open_steps;
+}
+
+// what the entry points ask of a monitor: none, or all five pointers (SMX_E_NULL) and a ring of at least one slot
+inline bool episode_pointers_ok(const smx_episode_monitor& M) {
+    return !M.ep_reward || (M.ep_steps && M.ep_count && M.done_reward && M.done_steps);
+}
+inline bool episode_shape_ok(const smx_episode_monitor& M) { return !M.ep_reward || M.capacity > 0; }

@@ -12,6 +12,9 @@ where a report goes and what happens after it, so they share ``_PeriodicReport``
   EvalTensorplexMonitor       the same under 'eval/<id>' (update_schedule.eval_env), then sleeps
                               eval_env_sleep seconds and fetches fresh parameters
 
+``DeviceEpisodeMonitor`` / ``DeviceTrainingMonitor`` are the same bookkeeping and the training reports for the actors
+of a ``SyntheticVecEnv``, whose steps run on the device and never pass through a host ``Env``.
+
 The tensorplex process of the reference is replaced by any object with
 ``add_scalars(dict, global_step=...)`` (default: the in-memory ScalarRecorder the learners use).
 """
@@ -173,3 +176,153 @@ class EvalTensorplexMonitor(_TensorplexReport):
         super().report(avg_reward, avg_speed)
         self._sleep(self._throttle_sleep)
         self._fetch_parameter()
+
+
+class DeviceEpisodeMonitor(object):
+    """EpisodeMonitor for the actors of a SyntheticVecEnv, kept on the device (struct smx_episode_monitor,
+    include/surreal_amd.h): every launch that steps the environments adds each actor's step reward to its open
+    episode -- fp64, in step order, by the one lane that formed the reward -- and on done moves the (reward, steps)
+    pair into the actor's ring of the last `capacity` finished episodes.  Nothing crosses to the host until poll().
+
+    Made by SyntheticVecEnv.attach_monitor(capacity=...).  All words live in ONE buffer so that poll() is one copy:
+    ep_reward fp64 [n] | ep_count int64 [n] | done_reward fp64 [n, capacity] | ep_steps int32 [n] | done_steps int32
+    [n, capacity].  The rings are actor-major: finished episode e of actor a sits at [a, e % capacity], an actor's ring
+    is one contiguous run that only its owning lane writes.
+
+    episode_rewards / episode_steps: per-actor lists, as EpisodeMonitor's (each reward round(x, 6)); num_episodes: the
+    finished episodes of all actors, dropped ones included; total_steps: the environment steps of all actors since
+    the monitor was attached (counted on the host: n per step); dropped: finished episodes that left a ring before a
+    poll() saw them (more than `capacity` of one actor between two polls)."""
+
+    def __init__(self, n, capacity, device):
+        import torch
+        if int(capacity) < 1:
+            raise ValueError('DeviceEpisodeMonitor: capacity must be positive, got %r' % (capacity,))
+        self.n, self.capacity = int(n), int(capacity)
+        n, c = self.n, self.capacity
+        words = 2 * n + n * c                                    # the 8-byte fields
+        self._buf = torch.zeros(words + (n + n * c + 1) // 2, dtype=torch.int64, device=device)
+        b = self._buf
+        self.ep_reward = b[:n].view(torch.float64)
+        self.ep_count = b[n:2 * n]
+        self.done_reward = b[2 * n:words].view(torch.float64).view(n, c)
+        i32 = b[words:].view(torch.int32)
+        self.ep_steps = i32[:n]
+        self.done_steps = i32[n:n + n * c].view(n, c)
+        self.episode_rewards = [[] for _ in range(n)]
+        self.episode_steps = [[] for _ in range(n)]
+        self.counts = [0] * n                                    # finished episodes of each actor at the last poll
+        self.dropped_by_actor = [0] * n
+        self.total_steps = 0
+        self.steps_per_actor = 0
+
+    def count_steps(self, k):
+        """the env stepped every actor k times (SyntheticVecEnv calls this; the device is not asked)"""
+        self.steps_per_actor += int(k)
+        self.total_steps += int(k) * self.n
+
+    def clear_open(self):
+        """drops the open episode of every actor (EpisodeMonitor._reset); the finished ones stay"""
+        self.ep_reward.zero_()
+        self.ep_steps.zero_()
+
+    @property
+    def num_episodes(self):
+        return sum(self.counts)
+
+    @property
+    def dropped(self):
+        return sum(self.dropped_by_actor)
+
+    def poll(self):
+        """ONE device -> host read of the counters and rings -> the episodes finished since the last poll, as
+        (actor, reward, steps) in actor order, each actor's oldest first.  An actor that finished more than `capacity`
+        episodes since then lost the oldest: they are counted in `dropped`, the `capacity` newest are reported."""
+        n, c = self.n, self.capacity
+        host = self._buf.cpu()
+        words = 2 * n + n * c
+        counts = host[n:2 * n].tolist()
+        rewards = host[2 * n:words].view(self.done_reward.dtype).view(n, c).tolist()
+        steps = host[words:].view(self.done_steps.dtype)[n:n + n * c].view(n, c).tolist()
+        new = []
+        for a in range(n):
+            first, last = self.counts[a], counts[a]
+            if last - first > c:
+                self.dropped_by_actor[a] += last - first - c
+                first = last - c
+            for e in range(first, last):
+                r, s = round(rewards[a][e % c], 6), steps[a][e % c]
+                self.episode_rewards[a].append(r)
+                self.episode_steps[a].append(s)
+                new.append((a, r, s))
+            self.counts[a] = last
+        return new
+
+    def open_episodes(self):
+        """(reward fp64 [n], steps int32 [n]) of the open episodes now, as host tensors (a second read; for tests)"""
+        return self.ep_reward.cpu(), self.ep_steps.cpu()
+
+    def mean_reward(self, last=10):
+        """the mean over the last `last` polled episode rewards of every actor together (None before the first)"""
+        xs = [r for per_actor in self.episode_rewards for r in per_actor[-int(last):]]
+        return _mean(xs) if xs else None
+
+
+class _DeviceActorReport(TrainingTensorplexMonitor):
+    """TrainingTensorplexMonitor for one actor of a DeviceEpisodeMonitor: the same period, mean, tags and global_step,
+    fed with polled episodes instead of wrapping an env"""
+
+    def __init__(self, owner, agent_id, session_config, separate_plots, tensorplex):
+        super().__init__(None, agent_id, session_config, separate_plots, tensorplex)
+        self._owner = owner
+        self._finished = 0
+
+    @property
+    def num_episodes(self):
+        return self._finished
+
+    def step_per_sec(self, average_episodes):
+        return self._owner.step_per_s
+
+    def feed(self, reward, steps, skipped=0):
+        for _ in range(skipped):                     # episodes that left the ring unseen still count towards a period
+            self._finished += 1
+            self._due()
+        self.episode_rewards.append(reward)
+        self.episode_steps.append(steps)
+        self._finished += 1
+        self._on_episode_end()
+
+
+class DeviceTrainingMonitor(object):
+    """What n TrainingTensorplexMonitor(agent_id=i) around n host envs would report, for the actors of a
+    SyntheticVecEnv: on each poll(), for actor i and every training_env-th of its episodes, ':reward' (the mean of its
+    last training_env episode rewards) and 'step_per_s' under 'agent/<i>' with global_step = that actor's episode
+    count.  tensorplex None: one ScalarRecorder per actor (reports[i].tensorplex), else the one object all share.
+
+    step_per_s: the device keeps no per-episode wall clock, so this is the environment steps of one actor per second
+    of wall time between the last two polls -- not the host monitor's per-episode figure."""
+
+    def __init__(self, env, session_config, tensorplex=None, separate_plots=True):
+        self.env = env
+        self.monitor = env.monitor if getattr(env, 'monitor', None) is not None else env.attach_monitor()
+        self.reports = [_DeviceActorReport(self, i, session_config, separate_plots, tensorplex)
+                        for i in range(self.monitor.n)]
+        self.step_per_s = 0.0
+        self._t_poll, self._steps_poll = time.time(), self.monitor.steps_per_actor
+        self._dropped_seen = list(self.monitor.dropped_by_actor)
+
+    def poll(self):
+        m = self.monitor
+        new = m.poll()
+        now = time.time()
+        self.step_per_s = (m.steps_per_actor - self._steps_poll) / (now - self._t_poll + 1e-7)
+        self._t_poll, self._steps_poll = now, m.steps_per_actor
+        for a, reward, steps in new:
+            skipped = m.dropped_by_actor[a] - self._dropped_seen[a]
+            self._dropped_seen[a] = m.dropped_by_actor[a]
+            self.reports[a].feed(reward, steps, skipped)
+        return new
+
+    def mean_reward(self, last=10):
+        return self.monitor.mean_reward(last)

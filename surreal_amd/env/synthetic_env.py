@@ -107,10 +107,35 @@ class SyntheticVecEnv(object):
         self.persistent = True        # rollout(): the one-launch kernel where the policy's shapes allow it
         self._ddpg = {}               # ddpg_rollout_into(): the open n-step transitions and OU states of the actors
         self._ppo = {}                # ppo_rollout_into(): the open moving windows of the actors
+        self.monitor = None           # attach_monitor(): the actors' episode returns, kept by the step launches
+
+    def attach_monitor(self, capacity=16):
+        """-> a DeviceEpisodeMonitor (env/monitor.py) that every stepping launch from now on feeds: per actor the open
+        episode's reward sum and length, and a ring of its last `capacity` finished episodes -- on the device, carried
+        from call to call like the open windows; poll() it for the episodes.  Starts empty: the steps an open episode
+        took before this call are not in it."""
+        from .monitor import DeviceEpisodeMonitor
+        self.monitor = DeviceEpisodeMonitor(self.n, capacity, self.device)
+        return self.monitor
+
+    def detach_monitor(self):
+        """the launches stop feeding the monitor (which keeps what it has) -> it"""
+        m, self.monitor = self.monitor, None
+        return m
+
+    def _mon(self, k=0):
+        """the keyword a stepping launch takes when a monitor is attached (none otherwise: kernels objects that know
+        no monitors are called as before), k env steps of every actor counted on the way"""
+        if self.monitor is None:
+            return {}
+        self.monitor.count_steps(k)
+        return {'monitor': self.monitor}
 
     def reset(self):
         self.state.copy_(self.init_state)
         self.t = 0
+        if self.monitor is not None:
+            self.monitor.clear_open()         # (EpisodeMonitor._reset: an unfinished episode is dropped)
         for k in ('carry_obs', 'carry_act', 'carry_rew', 'ou', 'hist'):
             if self._ddpg.get(k) is not None:
                 self._ddpg[k].zero_()
@@ -237,7 +262,7 @@ class SyntheticVecEnv(object):
         r = self.rolls
         if r is not None and self.slot < self.T:
             self.K.synth_env_step(self.state, self.init_state, actions, self.t, self.episode_len,
-                                  self.slot, r['obs'], r['actions'], r['rewards'], r['dones'])
+                                  self.slot, r['obs'], r['actions'], r['rewards'], r['dones'], **self._mon(1))
             if pds is not None and pds.data_ptr() != r['pds'][:, self.slot].data_ptr():
                 r['pds'][:, self.slot] = pds         # (an agent may have written the slot in place)
             self.slot += 1
@@ -247,7 +272,7 @@ class SyntheticVecEnv(object):
                 self.K.synth_frames(r['obs'][:, self.slot, 0], self.t + 1, self.frames[:, self.slot])
         else:
             self.K.synth_env_step(self.state, self.init_state, actions, self.t, self.episode_len, 0,
-                                  None, None, None, None)
+                                  None, None, None, None, **self._mon(1))
         self._advance()
         return self.state
 
@@ -279,7 +304,8 @@ class SyntheticVecEnv(object):
             # (csrc/smx_rollout.hip).  The packed weight copy is refreshed here: the agent's parameters only change
             # between rollouts (fetch_parameter)
             K.synth_rollout(actor, self._pack_actor(actor), L.SMX_ACT_TANH, self.state, self.init_state, log_var, noise,
-                            eps, self.t, self.episode_len, T, self.slot, self.rolls, zf, actors_per_workgroup)
+                            eps, self.t, self.episode_len, T, self.slot, self.rolls, zf, actors_per_workgroup,
+                            **self._mon(T))
             self.slot += T
             self._advance(T)
             return
@@ -301,7 +327,7 @@ class SyntheticVecEnv(object):
                 K.linear(self._h1, 1, v['W2'], 1, v['b2'], self._h2, n, actor.H2, actor.H1, act=L.SMX_ACT_RELU)
                 K.synth_act_env_step_head(v['W3'], v['b3'], self._h2, L.SMX_ACT_TANH, self.state, self.init_state,
                                           log_var, noise, None if eps is None else eps[t], self.t,
-                                          self.episode_len, self.slot, self.rolls, zf, self._xn)
+                                          self.episode_len, self.slot, self.rolls, zf, self._xn, **self._mon(1))
                 self.slot += 1
                 self._advance()
             return
@@ -309,7 +335,7 @@ class SyntheticVecEnv(object):
             mean = agent.policy_mean(self._xn)
             K.synth_act_env_step(self.state, self.init_state, mean, log_var, noise,
                                  None if eps is None else eps[t], self.t, self.episode_len, self.slot,
-                                 self.rolls, zf, self._xn)
+                                 self.rolls, zf, self._xn, **self._mon(1))
             self.slot += 1
             self._advance()
 
@@ -330,7 +356,7 @@ class SyntheticVecEnv(object):
         self.K.synth_lstm_rollout(m, pk, lpk, self.state, self.init_state, agent.batch_noise(self.n).view(-1), eps,
                                   self.t, self.episode_len, steps, slot, rolls,
                                   m.z_filter if agent.use_z_filter else None,
-                                  actors_per_workgroup=actors_per_workgroup, **cells)
+                                  actors_per_workgroup=actors_per_workgroup, **cells, **self._mon(steps))
         self._hand_cells(agent, cells)
         self._advance(steps)
 
@@ -374,7 +400,8 @@ class SyntheticVecEnv(object):
         actor = agent.model.actor
         K.synth_rollout(actor, self._pack_actor(actor), L.SMX_ACT_TANH, self.state, self.init_state,
                         agent.model.log_var.view(-1), agent.batch_noise(n).view(-1), eps, self.t, self.episode_len, T, 0,
-                        rolls, agent.model.z_filter if agent.use_z_filter else None, actors_per_workgroup)
+                        rolls, agent.model.z_filter if agent.use_z_filter else None, actors_per_workgroup,
+                        **self._mon(T))
         self._advance(T)
 
     def _ppo_window_refusal(self, agent):
@@ -483,7 +510,8 @@ class SyntheticVecEnv(object):
             if held is not None and held[0].shape[1] == n:
                 cells.update(h0=held[0].contiguous(), c0=held[1].contiguous())
         K.synth_ppo_window_rollout(m, pk, lpk, self.state, self.init_state, noise, eps, self.t, self.episode_len, T, N,
-                                   adv, c['carry'], tables, cursor, zf, actors_per_workgroup=actors_per_workgroup, **cells)
+                                   adv, c['carry'], tables, cursor, zf, actors_per_workgroup=actors_per_workgroup, **cells,
+                                   **self._mon(T))
         if rnn:
             self._hand_cells(agent, cells)
         replay.commit_ring(rows)
@@ -542,7 +570,7 @@ class SyntheticVecEnv(object):
             K.mlp3_forward(actor, feat, w.h1, w.h2, w.mean, L.SMX_ACT_TANH)
             r['t'], r['hist_pos'] = self.t, c['hist_pos']
             r['eps'] = None if eps is None else eps[s]
-            K.synth_ppo_pixel_window_step(r, w.mean)
+            K.synth_ppo_pixel_window_step(r, w.mean, **self._mon(1))
             c['hist_pos'] = (c['hist_pos'] + 1) % Hd
             j = self.t + 1 - N
             if j >= 0 and j % adv == 0:
@@ -629,7 +657,7 @@ class SyntheticVecEnv(object):
                 d['pk'] = torch.zeros(K.epoch_packed_numel(actor), device=self.device)
             K.epoch_pack([(actor, d['pk'])])        # (the agent's parameters only change between rollouts)
         if persistent and not reference:
-            K.synth_ddpg_rollout(actor, d['pk'], r, T, actors_per_workgroup)
+            K.synth_ddpg_rollout(actor, d['pk'], r, T, actors_per_workgroup, **self._mon(T))
             self.t = t
         else:
             if reference:
@@ -644,7 +672,7 @@ class SyntheticVecEnv(object):
                     mu = agent.model.forward_actor(self.state)
                 r['t'] = self.t
                 r['eps'] = None if deterministic else eps[s]
-                K.synth_ddpg_step(r, mu)
+                K.synth_ddpg_step(r, mu, **self._mon(1))
                 if self.t >= N - 1:
                     r['cursor'] = (r['cursor'] + n) % cap
                 self._advance()
@@ -671,7 +699,7 @@ class SyntheticVecEnv(object):
             mu = model.forward_actor(d['x'])
             r['t'], r['hist_pos'] = self.t, d['hist_pos']
             r['eps'] = None if deterministic else eps[s]
-            K.synth_ddpg_pixel_step(r, mu)
+            K.synth_ddpg_pixel_step(r, mu, **self._mon(1))
             d['hist_pos'] = (d['hist_pos'] + 1) % Hd
             if self.t >= N - 1:
                 r['cursor'] = (r['cursor'] + n) % cap
@@ -717,7 +745,8 @@ class SyntheticVecEnv(object):
         for t in range(T):
             K.epoch_forward([dict(net=actor, packed=pk, x=xn, out=mean, act=L.SMX_ACT_TANH)], None, ctrl, n)
             K.synth_act_env_step(self.state, self.init_state, mean, agent.model.log_var.view(-1), noise,
-                                 None if eps is None else eps[t], self.t, self.episode_len, self.slot, self.rolls, zf, xn)
+                                 None if eps is None else eps[t], self.t, self.episode_len, self.slot, self.rolls, zf, xn,
+                                 **self._mon(1))
             self.slot += 1
             self._advance()
 

@@ -581,10 +581,28 @@ class HipKernels(object):
         L.call('smx_synth_frame_u8', L.ptr(s0), s0.stride(0), n, C, H, W, int(t), L.ptr(dst), dst.stride(0), self._st())
 
     @staticmethod
-    def _synth_act_step(state, init_state, mean, A, log_var, noise_scale, eps, t, episode_len, slot, rolls, zfilter,
-                        xn_out):
+    def _monitor_args(monitor, n):
+        """struct smx_episode_monitor of a DeviceEpisodeMonitor (surreal_amd/env/monitor.py) over n actors; None: the
+        null monitor, with which every launch does what it does without one"""
+        q = L.EpisodeMonitor()
+        if monitor is not None:
+            m = monitor
+            assert m.n == n and m.ep_reward.dtype == torch.float64 and m.done_reward.dtype == torch.float64
+            assert m.ep_steps.dtype == torch.int32 and m.done_steps.dtype == torch.int32 and m.ep_count.dtype == torch.int64
+            assert m.ep_reward.numel() == m.ep_steps.numel() == m.ep_count.numel() == n
+            assert m.done_reward.numel() == m.done_steps.numel() == n * m.capacity
+            for x in (m.ep_reward, m.ep_steps, m.ep_count, m.done_reward, m.done_steps):
+                assert x.is_contiguous()
+            q.ep_reward, q.ep_steps, q.ep_count = L.ptr(m.ep_reward), L.ptr(m.ep_steps), L.ptr(m.ep_count)
+            q.done_reward, q.done_steps, q.capacity = L.ptr(m.done_reward), L.ptr(m.done_steps), int(m.capacity)
+        return q
+
+    @classmethod
+    def _synth_act_step(cls, state, init_state, mean, A, log_var, noise_scale, eps, t, episode_len, slot, rolls, zfilter,
+                        xn_out, monitor=None):
         n, D = state.shape
         p = L.SynthActStep()
+        p.mon = cls._monitor_args(monitor, n)
         p.state, p.init_state = L.ptr(state), L.ptr(init_state)
         p.mean, p.ld_mean, p.log_var = L.ptr(mean), (0 if mean is None else _row_stride(mean, A)), L.ptr(log_var)
         p.noise_scale, p.eps = L.ptr(noise_scale), L.ptr(eps)
@@ -601,28 +619,29 @@ class HipKernels(object):
         return p
 
     def synth_act_env_step(self, state, init_state, mean, log_var, noise_scale, eps, t, episode_len,
-                           slot, rolls, zfilter, xn_out):
+                           slot, rolls, zfilter, xn_out, monitor=None):
         """acting head + env step + next observation's z-filter, one launch (see the header);
-        rolls: dict obs / actions / rewards / dones [/ pds] or None; zfilter: ZFilter or None"""
+        rolls: dict obs / actions / rewards / dones [/ pds] or None; zfilter: ZFilter or None; monitor: a
+        DeviceEpisodeMonitor or None (every synth_* launch below takes one the same way)"""
         p = self._synth_act_step(state, init_state, mean, mean.shape[1], log_var, noise_scale, eps, t, episode_len,
-                                 slot, rolls, zfilter, xn_out)
+                                 slot, rolls, zfilter, xn_out, monitor)
         L.call('smx_synth_act_env_step_f32', ctypes.byref(p), self._st())
 
     def synth_act_env_step_head(self, W3, b3, h2, out_act, state, init_state, log_var, noise_scale, eps, t,
-                                episode_len, slot, rolls, zfilter, xn_out):
+                                episode_len, slot, rolls, zfilter, xn_out, monitor=None):
         """the same launch with the policy's output layer folded in: mean = act(h2 . W3^T + b3) formed per actor"""
         A, H2 = W3.shape
         p = self._synth_act_step(state, init_state, None, A, log_var, noise_scale, eps, t, episode_len, slot, rolls,
-                                 zfilter, xn_out)
+                                 zfilter, xn_out, monitor)
         L.call('smx_synth_act_env_step_head_f32', ctypes.byref(p), L.ptr(W3), L.ptr(b3), L.ptr(h2),
                _row_stride(h2, H2), H2, int(out_act), self._st())
 
     def synth_rollout_supported(self, net):
         return bool(self.lib.smx_synth_rollout_supported(net.D, net.H1, net.H2, net.OUT))
 
-    @staticmethod
-    def _roll_args(q, net, packed, out_act, state, init_state, log_var, noise_scale, eps, t, episode_len, steps, zfilter,
-                   actors_per_workgroup, rolls=None, slot=0):
+    @classmethod
+    def _roll_args(cls, q, net, packed, out_act, state, init_state, log_var, noise_scale, eps, t, episode_len, steps,
+                   zfilter, actors_per_workgroup, rolls=None, slot=0, monitor=None):
         """fills the SynthRollout `q`: the network, the head, the z-filter, state and clock, and (rolls: dict as in
         synth_act_env_step, also 'obs_last' / 'cells') the rollout tables"""
         n = state.shape[0]
@@ -636,6 +655,7 @@ class HipKernels(object):
         q.t, q.episode_len, q.steps, q.slot = int(t), int(episode_len), int(steps), int(slot)
         q.state, q.init_state = L.ptr(state), L.ptr(init_state)
         q.actors_per_workgroup = int(actors_per_workgroup)
+        q.mon = cls._monitor_args(monitor, n)
         if rolls is not None:
             r = rolls
             q.rows_per_actor = r['obs'].shape[1] if 'obs' in r else (r['cells'].shape[1] if 'cells' in r else 1)
@@ -683,14 +703,14 @@ class HipKernels(object):
         p.pixel, p.pixel_next = L.ptr(tabs['pixel']), L.ptr(tabs['pixel_next'])
 
     def synth_rollout(self, net, packed, out_act, state, init_state, log_var, noise_scale, eps, t, episode_len,
-                      steps, slot, rolls, zfilter, actors_per_workgroup=0):
+                      steps, slot, rolls, zfilter, actors_per_workgroup=0, monitor=None):
         """`steps` acting + environment steps of all actors in ONE launch (csrc/smx_rollout.hip): a workgroup owns
         4, 8 or 16 actors for the whole rollout (actors_per_workgroup; 0: the smallest whose grid fits the CUs once).
         packed: epoch_pack of `net`; eps [steps, n, A] or None; rolls as in synth_act_env_step ([n, T + 1, .]
         tables)."""
         p = L.SynthRollout()
         self._roll_args(p, net, packed, out_act, state, init_state, log_var, noise_scale, eps, t, episode_len, steps,
-                        zfilter, actors_per_workgroup, rolls or {}, slot)
+                        zfilter, actors_per_workgroup, rolls or {}, slot, monitor)
         L.call('smx_synth_rollout_f32', ctypes.byref(p), self._st())
 
     def synth_lstm_rollout_supported(self, model):
@@ -710,7 +730,7 @@ class HipKernels(object):
 
     def synth_lstm_rollout(self, model, packed, lstm_packed, state, init_state, noise_scale, eps, t, episode_len, steps,
                            slot, rolls, zfilter, hN, cN, h0=None, c0=None, h_before=None, c_before=None,
-                           actors_per_workgroup=0):
+                           actors_per_workgroup=0, monitor=None):
         """synth_rollout for a PPOModel with a one-layer LSTM stem, ONE launch (smx_synth_lstm_rollout_f32): packed =
         epoch_pack of model.actor, lstm_packed = lstm_rollout_pack of model.rnn; rolls may also hold 'cells'
         [n, R, 2, 1, Hl] (the state before every step); h0 / c0 (None: zeros), hN / cN, h_before / c_before: [n, Hl]
@@ -718,7 +738,7 @@ class HipKernels(object):
         r = rolls or {}
         p = L.SynthLstmRollout()
         self._roll_args(p.roll, model.actor, packed, L.SMX_ACT_TANH, state, init_state, model.log_var, noise_scale, eps,
-                        t, episode_len, steps, zfilter, actors_per_workgroup, r, slot)
+                        t, episode_len, steps, zfilter, actors_per_workgroup, r, slot, monitor)
         self._lstm_args(p, model, lstm_packed, state.shape[0], hN, cN, h0, c0, h_before, c_before)
         if 'cells' in r:
             assert r['cells'].is_contiguous() and tuple(r['cells'].shape[2:]) == (2, 1, model.rnn_hidden_logical)
@@ -738,7 +758,7 @@ class HipKernels(object):
 
     def synth_ppo_window_rollout(self, model, packed, lstm_packed, state, init_state, noise_scale, eps, t, episode_len,
                                  steps, n_step, advance, carry, tables, cursor, zfilter, hN=None, cN=None, h0=None,
-                                 c0=None, h_before=None, c_before=None, actors_per_workgroup=0):
+                                 c0=None, h_before=None, c_before=None, actors_per_workgroup=0, monitor=None):
         """`steps` steps of synth_rollout (model.rnn None) / synth_lstm_rollout recorded as moving windows of n_step
         steps, `advance` apart, straight into a FIFO ring, ONE launch (smx_synth_ppo_window_rollout_f32).
         carry: the open windows {'obs' [n, n_step, D], 'actions' [n, n_step, A], 'rewards' [n, n_step], 'pds'
@@ -748,7 +768,7 @@ class HipKernels(object):
         h_before / c_before: [n, Hl] contiguous, Hl = model.rnn_hidden_logical"""
         p = L.SynthPpoWindowRollout()
         self._roll_args(p.base.roll, model.actor, packed, L.SMX_ACT_TANH, state, init_state, model.log_var, noise_scale,
-                        eps, t, episode_len, steps, zfilter, actors_per_workgroup)
+                        eps, t, episode_len, steps, zfilter, actors_per_workgroup, monitor=monitor)
         if model.if_rnn:
             self._lstm_args(p.base, model, lstm_packed, state.shape[0], hN, cN, h0, c0, h_before, c_before)
         for k, x in list(carry.items()) + list(tables.items()):
@@ -759,8 +779,8 @@ class HipKernels(object):
     def synth_ddpg_rollout_supported(self, net):
         return bool(self.lib.smx_synth_ddpg_rollout_supported(net.D, net.H1, net.H2, net.OUT))
 
-    @staticmethod
-    def _ddpg_args(r, steps, net=None, packed=None, actors_per_workgroup=0):
+    @classmethod
+    def _ddpg_args(cls, r, steps, net=None, packed=None, actors_per_workgroup=0, monitor=None):
         """smx_ddpg_rollout_t from the dict SyntheticVecEnv.ddpg_rollout_into builds: state / init_state [n, D],
         t, episode_len, n_step, noise_type, eps, sigmas (fp64), theta / dt / root_dt, gpow (fp64 [n_step]), ou (fp64
         [n, A]), carry_obs / carry_act / carry_rew, the ring tables by replay field name, cursor, capacity"""
@@ -781,32 +801,33 @@ class HipKernels(object):
         p.obs, p.obs_next, p.actions = L.ptr(tabs['obs']), L.ptr(tabs['obs_next']), L.ptr(tabs['actions'])
         p.rewards, p.dones = L.ptr(tabs['rewards']), L.ptr(tabs['dones'])
         p.cursor, p.capacity = int(r['cursor']), int(tabs['obs'].shape[0])
+        p.mon = cls._monitor_args(monitor, n)
         return p
 
-    def synth_ddpg_rollout(self, net, packed, r, steps, actors_per_workgroup=0):
+    def synth_ddpg_rollout(self, net, packed, r, steps, actors_per_workgroup=0, monitor=None):
         """`steps` DDPG acting + environment steps of all actors with their n-step transitions written into the ring
         tables, ONE launch (csrc/smx_rollout.hip).  packed: epoch_pack of the actor `net`; r: see _ddpg_args
         (eps [steps, n, A])"""
         if r['eps'] is not None:
             assert r['eps'].is_contiguous() and tuple(r['eps'].shape) == (steps, r['state'].shape[0], net.OUT)
-        p = self._ddpg_args(r, steps, net, packed, actors_per_workgroup)
+        p = self._ddpg_args(r, steps, net, packed, actors_per_workgroup, monitor)
         L.call('smx_synth_ddpg_rollout_f32', ctypes.byref(p), self._st())
 
-    def synth_ddpg_step(self, r, mu):
+    def synth_ddpg_step(self, r, mu, monitor=None):
         """one step of synth_ddpg_rollout given the actor's output mu [n, A] (r['eps']: this step's [n, A] draws;
         r['cursor']: where this step's closing transitions go)"""
         A = mu.shape[1]
-        p = self._ddpg_args(r, 1)
+        p = self._ddpg_args(r, 1, monitor=monitor)
         L.call('smx_synth_ddpg_step_f32', ctypes.byref(p), L.ptr(mu), _row_stride(mu, A), self._st())
 
-    def synth_ddpg_pixel_step(self, r, mu):
+    def synth_ddpg_pixel_step(self, r, mu, monitor=None):
         """synth_ddpg_step for actors with a camera, in the same launch: r also holds hist uint8 [n, Hd, C, H, W] (the
         raw frames, the current step's in slot hist_pos), obs_pixel uint8 [n, S*C, H, W] (receives the stacked
         observation of the next step) and the ring tables 'pixel' / 'pixel_next' uint8 [capacity, S*C*H*W]
         (include/surreal_amd.h smx_synth_ddpg_pixel_step)"""
         p = L.DdpgPixelStep()
         self._camera_args(p, r, 1)
-        p.base = self._ddpg_args(r, 1)
+        p.base = self._ddpg_args(r, 1, monitor=monitor)
         L.call('smx_synth_ddpg_pixel_step', ctypes.byref(p), L.ptr(mu), _row_stride(mu, mu.shape[1]), self._st())
 
     @staticmethod
@@ -814,7 +835,7 @@ class HipKernels(object):
         """the actions smx_synth_ppo_pixel_window_step takes (one thread each, A <= SMX_PPO_PIXEL_STEP_MAX_A)"""
         return 0 < A <= L.SMX_PPO_PIXEL_STEP_MAX_A
 
-    def synth_ppo_pixel_window_step(self, r, mu, copy_workgroups=0):
+    def synth_ppo_pixel_window_step(self, r, mu, copy_workgroups=0, monitor=None):
         """ONE step of the windowed PPO rollout for actors with a camera given the policy mean mu [n, A] (row-strided
         view allowed): head, environment step, carry rings, frame history and -- at a closing step -- the windows into
         the FIFO's ring from row r['cursor'] (include/surreal_amd.h smx_synth_ppo_pixel_window_step).  r: state /
@@ -849,16 +870,18 @@ class HipKernels(object):
         p.h_before, p.c_before = L.ptr(hb), L.ptr(cb)
         self._window_args(p, N, r['advance'], carry, tabs, r['cursor'])
         p.copy_workgroups = int(copy_workgroups)
+        p.mon = self._monitor_args(monitor, n)
         L.call('smx_synth_ppo_pixel_window_step', ctypes.byref(p), L.ptr(mu), _row_stride(mu, A), self._st())
 
     def synth_env_step(self, state, init_state, actions, t, episode_len, slot, obs_roll, act_roll,
-                       rew_roll, done_roll):
+                       rew_roll, done_roll, monitor=None):
         n, D = state.shape
         A = actions.shape[1]
         T = obs_roll.shape[1] if obs_roll is not None else 1
         L.call('smx_synth_env_step_f32', L.ptr(state), L.ptr(init_state), L.ptr(actions), n, D, A,
                int(t), int(episode_len), int(slot), T, L.ptr(obs_roll), L.ptr(act_roll),
-               L.ptr(rew_roll), L.ptr(done_roll), self._st())
+               L.ptr(rew_roll), L.ptr(done_roll),
+               None if monitor is None else ctypes.byref(self._monitor_args(monitor, n)), self._st())
 
 
     # ---- generic dense layer + DDPG pieces ---------------------------------------------------
