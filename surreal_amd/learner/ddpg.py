@@ -37,6 +37,7 @@ from surreal_amd import _lib as L
 from surreal_amd import kernels as KN
 from surreal_amd.learner.aggregator import SSARAggregator, FrameStackPreprocessor
 from surreal_amd.learner.base import Learner, DeferredStats
+from surreal_amd.learner.dist import _dist_info, setup_peer_exchange
 from surreal_amd.model.ddpg_net import DDPGModel
 from surreal_amd.session import ConfigError
 
@@ -58,7 +59,6 @@ class DDPGLearner(Learner):
         self._target_update_init()
         # data-parallel: every rank owns batch_size samples of the global batch (uniform replay shards
         # per GPU, ddpg_configs.py:89-93 / SURVEY.md 8(e)); gradients are averaged before each Adam step
-        from surreal_amd.learner.ppo import _dist_info
         self._dist, self.world_size, self.rank = _dist_info()
         # several ranks: the iteration is ONE hipGraph too when its exchanges run as kernels over IPC-mapped peer buffers
         # (PeerExchange, set up and self-checked with the workspace); on the process group (RCCL) the launches stay eager
@@ -245,22 +245,12 @@ class DDPGLearner(Learner):
         shards: SURVEY.md 8(e) "same pattern, 2 grad all-reduces per iteration") as kernels over IPC-mapped peer buffers
         -- set up and SELF-CHECKED once, collectively; any failure leaves the process group in place and the launches
         eager.  session_config.learner.peer_exchange = False keeps the process group."""
-        d = self._dist
-        d.err_word = ws.xerr
-        want = bool(self.session_config.learner.get('peer_exchange', True)) and self.device != 'cpu'
         need = max(64, ws.grads_c.numel(), ws.grads_a.numel(),
                    ws.grads_p.numel() if self.is_pixel_input else 0,
                    ws.grads_c2.numel() if self.use_double_critic else 0)
-        if want and (d.exchange is None or d.exchange.capacity < need):
-            if d.exchange is not None:
-                d._d.barrier()
-                d.exchange.close()
-                d.exchange = None
-            from surreal_amd.distributed.peer_exchange import PeerExchange
-            d.exchange = PeerExchange.create(d._d, need, timeout_s=float(self.session_config.learner.get(
-                'peer_exchange_timeout_s', 5.0)))
-        self.exchange_kind = 'peer buffers (%s)' % d.exchange.check_message if d.exchange is not None else 'process group'
-        if d.exchange is None:
+        setup_peer_exchange(self, ws.xerr, need)
+        self.exchange_kind = self._dist.kind()
+        if self._dist.exchange is None:
             self.use_graph = False            # process-group collectives are not captured
 
     def _critic_backward(self, ws, x, B, model=None, dz3=None, xcat=None, h2c=None, gc=None):

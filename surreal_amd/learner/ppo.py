@@ -38,6 +38,7 @@ from surreal_amd import _lib as L
 from surreal_amd import kernels as KN
 from surreal_amd.learner.aggregator import MultistepAggregatorWithInfo
 from surreal_amd.learner.base import Learner, DeferredStats
+from surreal_amd.learner.dist import _SegmentedGraph, _dist_info, setup_peer_exchange
 from surreal_amd.model.ppo_net import DiagGauss, PPOModel
 
 
@@ -71,104 +72,18 @@ class LinearWithMinLR(object):
         self.n, self.lr = int(sd['n']), float(sd['lr'])
 
 
-class _SegmentedGraph(object):
-    """A learn() on several ranks as hipGraph SEGMENTS with the collectives issued between them: the
-    kernels (and the few torch ops) between two collectives are captured once and replayed, RCCL is
-    called eagerly on the same stream.  One learn of the benchmark is ~70 launches; issued one by
-    one from Python they cost more host time than the GPU needs to run them, which a single-rank
-    learner never pays (its whole step is one graph)."""
-
-    def __init__(self):
-        self.items = []
-        self.pool = torch.cuda.graph_pool_handle()      # one pool: a segment's temporaries outlive it
-        self._cur = None
-
-    def _open(self):
-        g = torch.cuda.CUDAGraph()
-        # thread_local: the process group's watchdog thread queries events while we capture; under the
-        # default (global) mode a HIP call from ANY thread invalidates the capture
-        ctx = torch.cuda.graph(g, pool=self.pool, capture_error_mode='thread_local')
-        ctx.__enter__()
-        self._cur = (g, ctx)
-
-    def _close(self):
-        g, ctx = self._cur
-        ctx.__exit__(None, None, None)
-        self.items.append(g)
-        self._cur = None
-
-    def capture(self, fn, dist_proxy):
-        dist_proxy.recorder = self
-        self._open()
-        try:
-            fn()
-        finally:
-            self._close()
-            dist_proxy.recorder = None
-
-    def collective(self, thunk):
-        """called by the distributed proxy while capturing: cut the graph here (the collective is NOT
-        executed during the capture pass -- the kernels around it are not either)"""
-        self._close()
-        self.items.append(thunk)
-        self._open()
-
-    def replay(self):
-        for it in self.items:
-            if isinstance(it, torch.cuda.CUDAGraph):
-                it.replay()
-            else:
-                it()
-
-
-class _CountingDist(object):
-    """torch.distributed with a counter on the collectives a learn() issues (reported by bench.py), a hook
-    for _SegmentedGraph, and -- when the ranks share a node -- the fp32 exchanges routed through
-    surreal_amd.distributed.PeerExchange (one kernel on the learner's stream, part of its graph) instead of
-    the process group (an eager RCCL call that cuts the graph)."""
-
-    def __init__(self, dist):
-        self._d = dist
-        self.count = 0
-        self.recorder = None
-        self.exchange = None         # PeerExchange, once a workspace has set it up and checked it
-        self.err_word = None         # device int32 a timed-out exchange raises (the learner's control block)
-
-    def _run(self, name, a, k):
-        def thunk():
-            self.count += 1
-            return getattr(self._d, name)(*a, **k)
-        if self.recorder is not None:
-            self.recorder.collective(thunk)
-            return None
-        return thunk()
-
-    def _peer_ok(self, *tensors):
-        ex = self.exchange
-        return ex is not None and all(t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and
-                                      t.numel() <= ex.capacity and t.data_ptr() % 16 == 0 for t in tensors)
-
-    def all_reduce(self, t, *a, **k):
-        if not a and not k and self._peer_ok(t):
-            self.count += 1
-            return self.exchange.all_reduce(t, err=self.err_word)
-        return self._run('all_reduce', (t,) + a, k)
-
-    def all_gather_into_tensor(self, out, t, *a, **k):
-        if not a and not k and self._peer_ok(out, t):
-            self.count += 1
-            return self.exchange.all_gather_into_tensor(out, t, err=self.err_word)
-        return self._run('all_gather_into_tensor', (out, t) + a, k)
-
-    def __getattr__(self, name):
-        return getattr(self._d, name)
-
-
-def _dist_info():
-    import torch.distributed as dist
-    if dist.is_available() and dist.is_initialized():
-        return _CountingDist(dist), dist.get_world_size(), dist.get_rank()
-    return None, 1, 0
+def _stats_layout(Ep, Ev, n_sync):
+    """The statistics block (ws.scal on the device, its host copy in _decode_stats) as named slices, and its length:
+    ctrl | policy stats | sync words (+ KL slots) | value stats | advantage moments | return moments | fin | rf_state.
+    The kernels and a captured graph address these regions, so neither their order nor the two spare runs change."""
+    lay, o = types.SimpleNamespace(), 0
+    for name, n in (('ctrl', L.CTRL_WORDS), ('pstats', (Ep + 1) * L.PS_STRIDE), ('sync', n_sync),
+                    ('vstats', Ev * L.VS_STRIDE), ('adv_mom', 3), ('ret_mom', 3), ('spare', 2), ('fin', 4),
+                    ('rf_state', 3), ('spare_end', 1)):
+        setattr(lay, name, slice(o, o + n))
+        o += n
+    lay.total = o
+    return lay
 
 
 class PPOLearner(Learner):
@@ -227,6 +142,7 @@ class PPOLearner(Learner):
             self.clip_lower = self.clip_range[0]
         else:
             raise ValueError('ppo_mode must be "adapt" or "clip", got %r' % (self.ppo_mode,))
+        self._mode = L.SMX_PPO_CLIP if self.ppo_mode == 'clip' else L.SMX_PPO_ADAPT
         # learning-rate annealing (ppo.py:121-125)
         anneal = algo.network.anneal
         self.min_lr = anneal.min_lr
@@ -305,68 +221,87 @@ class PPOLearner(Learner):
         return (max(self.epoch_policy, self.epoch_baseline) + 1 + 3) & ~3
 
     # ======================================================================================
-    # workspace
+    # workspace: one function per concern, each region and each alias decided in one place
     # ======================================================================================
     def _workspace(self, B, N, D, A, pix_dtype=None):
         key = (B, N, D, A, pix_dtype)
         if self._ws is not None and self._ws.key == key:
             return self._ws
-        dev, K = self.device, self.K
-        f = lambda *s: torch.empty(*s, device=dev, dtype=torch.float32)  # noqa: E731
         ws = types.SimpleNamespace()
         ws.key = key
-        act, cri = self.model.actor, self.model.critic
-        rnn = self.if_rnn_policy
-        pixel = self.model.if_pixel
-        stem = rnn or pixel
-        E = N - self.horizon + 1 if rnn else 1           # ppo.py:398-400, 521-537
-        ws.E = E
+        ws.E = N - self.horizon + 1 if self.if_rnn_policy else 1           # ppo.py:398-400, 521-537
+        ws.rows = B * ws.E
+        ws.stem = self.if_rnn_policy or self.model.if_pixel       # a stem shared by both optimiser groups
+        self._ws_scalars(ws)
+        self._ws_critic_pass(ws)
+        self._ws_epochs(ws)
+        self._ws_exchange(ws)
+        self._ws = ws
+        self._graphs = {}
+        return ws
+
+    def _f(self, *shape):
+        return torch.empty(*shape, device=self.device, dtype=torch.float32)
+
+    def _ft(self, n, rows):
+        """a transposed copy [features, rows] feeding the weight-gradient GEMMs (K-contiguous)
+        (row stride padded off the power of two: all 32 rows of a fragment load would
+        otherwise land on one cache set / memory channel)"""
+        return torch.zeros(n, rows + 16, device=self.device, dtype=torch.float32)[:, :rows]
+
+    def _ws_scalars(self, ws):
+        """the statistics block (_stats_layout) and the views the launches take of it; the reward filter's buffers"""
+        dev, K, B = self.device, self.K, ws.key[0]
         Ep, Ev = self.epoch_policy, self.epoch_baseline
-        # scalars block: ctrl | policy stats | in-launch counters of the fused forward + backward epochs | value stats | moments
-        # (+ per launch and row block of the fused forward + backward epochs: an 8-byte slot)
-        n_slots = 0 if (self.if_rnn_policy or self.model.if_pixel or self.world_size > 1) else \
+        # per launch and row block of the fused forward + backward epochs: an 8-byte slot behind the sync words
+        n_slots = 0 if (ws.stem or self.world_size > 1) else \
             2 * (max(Ep, Ev) + 1) * ((B + 15) // 16)
         if n_slots > (1 << 19):
             # (the slots sit in the range epoch_prepare zeroes per learn, which the kernel bounds at 2^20 words: batches of
             # more than ~380 k sub-trajectories run the two-launch epochs, which need none)
             n_slots = 0
-        n_sync = self._sync_words() + n_slots
-        n_scal = L.CTRL_WORDS + (Ep + 1) * L.PS_STRIDE + n_sync + Ev * L.VS_STRIDE + 12 + 4
-        ws.scal = torch.zeros(n_scal, device=dev, dtype=torch.float32)
-        o = 0
-        ws.ctrl_f = ws.scal[o:o + L.CTRL_WORDS]; o += L.CTRL_WORDS
+        ws.n_slots = n_slots
+        lay = ws.layout = _stats_layout(Ep, Ev, self._sync_words() + n_slots)
+        ws.scal = torch.zeros(lay.total, device=dev, dtype=torch.float32)
+        ws.ctrl_f = ws.scal[lay.ctrl]
         ws.ctrl_i = ws.ctrl_f.view(torch.int32)
-        ws.pstats = ws.scal[o:o + (Ep + 1) * L.PS_STRIDE].view(Ep + 1, L.PS_STRIDE); o += (Ep + 1) * L.PS_STRIDE
-        ws.sync = ws.scal[o:o + n_sync].view(torch.int32); o += n_sync       # one word per epoch launch, zeroed per learn
-        ws.kl_slots = ws.sync[self._sync_words():self._sync_words() + n_slots].view(-1, 2 * ((B + 15) // 16)) \
-            if n_slots else None
-        ws.n_sync = n_sync
-        ws.vstats = ws.scal[o:o + Ev * L.VS_STRIDE].view(Ev, L.VS_STRIDE); o += Ev * L.VS_STRIDE
-        ws.adv_mom = ws.scal[o:o + 3]; o += 3
-        ws.ret_mom = ws.scal[o:o + 3]; o += 3
-        ws.fin = ws.scal[o + 2:o + 6]          # mean log_var, z-filter means (final_stats)
+        ws.pstats = ws.scal[lay.pstats].view(Ep + 1, L.PS_STRIDE)
+        ws.sync = ws.scal[lay.sync].view(torch.int32)       # one word per epoch launch, zeroed per learn
+        ws.kl_slots = ws.sync[self._sync_words():].view(-1, 2 * ((B + 15) // 16)) if n_slots else None
+        ws.vstats = ws.scal[lay.vstats].view(Ev, L.VS_STRIDE)
+        ws.adv_mom, ws.ret_mom = ws.scal[lay.adv_mom], ws.scal[lay.ret_mom]
+        ws.fin = ws.scal[lay.fin]              # mean log_var, z-filter means (final_stats)
         # RewardFilter's {count, running_sum, running_sumsq} (reward_filter.py:28-31): in the statistics block,
         # so the reported reward mean needs no read-back of its own; survives a change of workspace
-        ws.rf_state = ws.scal[o + 6:o + 9]
+        ws.rf_state = ws.scal[lay.rf_state]
         if self._ws is not None:
             ws.rf_state.copy_(self._ws.rf_state)
         else:
             ws.rf_state.copy_(torch.tensor([1e-5, 0.0, 0.0]))
         if self.filter_rewards:
-            ws.rew = torch.empty(B, N, device=dev, dtype=torch.float32)
+            ws.rew = torch.empty(B, ws.key[1], device=dev, dtype=torch.float32)
             ws.rf_part = torch.zeros(K.reward_filter_partials(), device=dev, dtype=torch.float64)
             ws.rf_ticket = torch.zeros(1, device=dev, dtype=torch.int32)
             ws.rf_sums = torch.zeros(3, device=dev, dtype=torch.float32)
         ws.stop = ws.ctrl_i[L.C_STOP:L.C_STOP + 1]
-        # stop flag + epochs_done + reserved words + the policy statistics rows: one contiguous run
-        ws.zero_block = ws.scal[L.C_STOP:L.CTRL_WORDS + (Ep + 1) * L.PS_STRIDE + n_sync]
+        ws.xerr = ws.ctrl_i[L.C_XCHG_ERR:L.C_XCHG_ERR + 1]
+        # stop flag + epochs_done + reserved words + the policy statistics rows + the sync words: one contiguous run
+        ws.zero_block = ws.scal[L.C_STOP:lay.sync.stop]
+        # where an epoch's optimiser step leaves the gradient norms: [e] is epoch e's one-word slot
+        ws.gnorm_a = ws.pstats[:, L.PS_GRADNORM:L.PS_GRADNORM + 1]
+        ws.gnorm_c = ws.vstats[:, L.VS_GRADNORM:L.VS_GRADNORM + 1]
         # keep the optimiser step counters of a previous workspace
         if self._ws is not None:
             ws.ctrl_i[L.C_STEP_ACTOR:L.C_STEP_CRITIC + 1].copy_(
                 self._ws.ctrl_i[L.C_STEP_ACTOR:L.C_STEP_CRITIC + 1])
         self._ctrl_host = None
-        # critic pass + GAE
-        ws.packed = None if stem else f(K.mlp3_packed_numel(cri))
+        ws.ticket = torch.zeros(2, dtype=torch.int32, device=dev)
+
+    def _ws_critic_pass(self, ws):
+        """critic pass + GAE"""
+        f, dev, cri = self._f, self.device, self.model.critic
+        B, N, D = ws.key[:3]
+        ws.packed = None if ws.stem else f(self.K.mlp3_packed_numel(cri))
         ws.vals = f(B * (N + 1))
         # fused-kernel tail split (see _enqueue_gae): rounds of 128-row workgroups over the CUs
         n_cu = 256
@@ -374,18 +309,22 @@ class PPOLearner(Learner):
             n_cu = torch.cuda.get_device_properties(torch.cuda.current_device()).multi_processor_count
         rounds = lambda rows: -(-(-(-rows // 128)) // n_cu)  # noqa: E731
         ws.split_tail = bool(self.session_config.learner.get('split_critic_tail', True)) and \
-            rounds(B * (N + 1)) > rounds(B * N) and not stem
+            rounds(B * (N + 1)) > rounds(B * N) and not ws.stem
         ws.xnext = f(B, D)
         ws.h1t, ws.h2t = f(B, cri.H1), f(B, cri.H2)      # critic over the obs_next rows
-        ws.adv = f(B * E)
-        ws.ret = f(B * E)
+        ws.adv = f(ws.rows)
+        ws.ret = f(ws.rows)
         idx = torch.tensor(range(N), dtype=torch.float32)
         ws.gpow = torch.pow(self.gamma, idx).to(dev)     # ppo.py:372-374, built as the reference does
         ws.lpow = torch.pow(self.lam, idx).to(dev)
         ws.mom_parts = f(self.world_size, 3)
-        # epochs
-        rows = B * E
-        ws.rows = rows
+
+    def _ws_epochs(self, ws):
+        """what the epochs read and write per row, and which schedule runs them"""
+        f, ft, K = self._f, self._ft, self.K
+        act, cri = self.model.actor, self.model.critic
+        B, _, D, A = ws.key[:4]
+        rows = ws.rows
         Dx = self.model.stem_in       # D, or D + cnn_feature_dim with pixel observations
         ws.xn = f(rows, Dx)           # z-filtered step-0 observations [| CNN features] (model filter)
         ws.xr = f(rows, Dx)           # same through the reference-policy filter / stem
@@ -396,72 +335,18 @@ class PPOLearner(Learner):
         ws.g_surr, ws.g_kl, ws.dz3a = f(rows, A), f(rows, A), f(rows, A)
         ws.dz2a, ws.dz1a = f(rows, act.H2), f(rows, act.H1)
         ws.dz3c, ws.dz2c, ws.dz1c = f(rows), f(rows, cri.H2), f(rows, cri.H1)
-        if stem:
-            R1 = B * (N + 1)
-            ws.h0 = ws.c0 = ws.cnn_it = ws.cnn_gae = ws.frames_it = None
-            ws.low_it = f(rows, D)                    # obs[:, :E] (raw: also feeds z_update)
-            ws.act_it, ws.beh_it = f(rows, A), f(rows, 2 * A)
-            ws.ztmp = f(R1, D)
-            ws.lcat, ws.xcat = f(B, N + 1, D), f(R1, Dx)     # critic pass over cat(obs, obs_next)
-            ws.h1G, ws.h2G = f(R1, cri.H1), f(R1, cri.H2)
-            n_sk = max(K.mlp3_backward_ws_floats(n, rows) for n in (act, cri))
-            ws.mlp_sk = f(n_sk) if n_sk else None          # split-K partials of the MLP weight gradients over B x T rows
-            # scratch for the packed weights of the fused many-row forward (K.mlp3_forward(pack=...): one launch instead
-            # of three layer GEMMs from FUSED_ROWS_MIN rows on; the shapes it does not take keep the layered path)
-            try:
-                ws.pack_stem = f(max(K.mlp3_packed_numel(n) for n in (act, cri)))
-            except Exception:
-                ws.pack_stem = None
-            n_z = K.zfilter_update_ws_floats(rows, D)
-            ws.zscratch = f(n_z) if n_z else None          # the z-update's chunk sums over B * E rows (K.zfilter_update)
-            n_pt = max(K.mlp3_dgrad_rows_ws_floats(n) for n in (act, cri))
-            ws.packT_stem = f(n_pt) if n_pt else None    # ... and of the fused many-row data gradients (K.mlp3_backward)
-            if rnn:
-                # LSTM stem (ppo_net.py:143-152): sequence buffers for the epoch passes (T = E)
-                # and for the critic pass (T = N + 1, ppo.py:376-386)
-                F = self.model.rnn_hidden
-                nl = self.model.rnn_layers
-                ws.h0L, ws.c0L = f(nl, B, F), f(nl, B, F)          # agent-side state of every layer
-                ws.h0, ws.c0 = ws.h0L[0], ws.c0L[0]
-                ws.gates, ws.lo, ws.cs, ws.hp, ws.dlo = f(rows, 4 * F), f(rows, F), f(rows, F), f(rows, F), f(rows, F)
-                ws.gatesG, ws.loG, ws.csG = f(R1, 4 * F), f(R1, F), f(R1, F)
-                # stacked layers above the first: their own sequence buffers (layer l reads layer l-1's lo)
-                ws.upper = [types.SimpleNamespace(gates=f(rows, 4 * F), lo=f(rows, F), cs=f(rows, F),
-                                                  hp=f(rows, F), dlo=f(rows, F)) for _ in range(nl - 1)]
-                ws.loG2 = f(R1, F) if nl > 1 else None
-                n_sk = max(K.lstm_backward_ws_floats(r, B, E) for r in self.model.rnns)
-                ws.lstm_sk = f(n_sk) if n_sk else None
-            if pixel:
-                # CNN stem (builders.py:8-33): frames stay in their source dtype (uint8 from the
-                # cameras); the critic pass runs the stem in chunks to bound the patch matrices
-                from surreal_amd.model.cnn_stem import CnnStem
-                cnn = self.model.cnn
-                cam = (cnn.C, cnn.H, cnn.W)
-                ws.frames_it = torch.empty((rows,) + cam, device=dev, dtype=pix_dtype)
-                ws.fcat = torch.empty((B, N + 1) + cam, device=dev, dtype=pix_dtype)
-                ws.dxn = torch.zeros(rows, Dx, device=dev)
-                chunk = int(self.session_config.learner.get('cnn_chunk_frames', 2048))
-                ws.cnn_it = CnnStem.workspace(cnn, rows, dev, backward=True)
-                ws.cnn_it.sk = self.model._cnn_stem.splitk_workspace(cnn, rows, dev)
-                ws.cnn_gae = ws.cnn_it if rows >= min(chunk, R1) else \
-                    CnnStem.workspace(cnn, min(chunk, R1), dev, backward=False)
+        if ws.stem:
+            self._ws_stem(ws)
         else:
-            # transposed copies [features, rows] feeding the weight-gradient GEMMs (K-contiguous)
-            # (row stride padded off the power of two: all 32 rows of a fragment load would
-            # otherwise land on one cache set / memory channel)
-            ldT = rows + 16
-            ft = lambda n: torch.zeros(n, ldT, device=dev, dtype=torch.float32)[:, :rows]  # noqa: E731
-            ws.xnT = ft(D)
-            ws.h1aT, ws.h2aT, ws.dz3aT = ft(act.H1), ft(act.H2), ft(A)
-            ws.dz2aT, ws.dz1aT = ft(act.H2), ft(act.H1)
-            ws.h1cT, ws.h2cT, ws.dz3cT = ft(cri.H1), ft(cri.H2), ft(1)
-            ws.dz2cT, ws.dz1cT = ft(cri.H2), ft(cri.H1)
-        # one buffer for both groups' gradients: a data-parallel lock-step epoch all-reduces it once
-        n_a, n_c = self.model.actor_flat.numel(), self.model.critic_flat.numel()
+            ws.xnT = ft(D, rows)
+            ws.h1aT, ws.h2aT, ws.dz3aT = ft(act.H1, rows), ft(act.H2, rows), ft(A, rows)
+            ws.dz2aT, ws.dz1aT = ft(act.H2, rows), ft(act.H1, rows)
+            ws.h1cT, ws.h2cT, ws.dz3cT = ft(cri.H1, rows), ft(cri.H2, rows), ft(1, rows)
+            ws.dz2cT, ws.dz1cT = ft(cri.H2, rows), ft(cri.H1, rows)
         ws.nblk_p = K.loss_blocks(rows)
         # fused row-block epochs: plain MLP policy, shapes the kernels take; on several ranks the
         # paired-epoch schedule with one collective per epoch (epoch_policy == epoch_baseline)
-        ws.fused = (self.fused_epochs and not stem and
+        ws.fused = (self.fused_epochs and not ws.stem and
                     (self.world_size == 1 or self.epoch_policy == self.epoch_baseline) and
                     K.epoch_supported(act, cri))
         # ... and an updating epoch's forward + loss + data gradients as ONE launch (single rank; several ranks need the
@@ -474,37 +359,110 @@ class PPOLearner(Learner):
         # (set it on shared GPUs) -- and runs the two-launch form: same results, one more launch per epoch.
         ws.fb = (ws.fused and self.world_size == 1 and bool(self.session_config.learner.get('fused_fwdbwd', True)) and
                  bool(self.session_config.learner.get('exclusive_device', True)) and not getattr(self, '_fb_timed_out', False) and
-                 n_slots > 0 and K.epoch_fwdbwd_supported(act, cri))
-        vblocks = K.epoch_blocks if ws.fused else K.value_loss_blocks     # value-loss moments per 16 / 256 rows
-        ws.nblk_v = vblocks(rows)
+                 ws.n_slots > 0 and K.epoch_fwdbwd_supported(act, cri))
+        ws.vblocks = K.epoch_blocks if ws.fused else K.value_loss_blocks     # value-loss moments per 16 / 256 rows
+        ws.nblk_v = ws.vblocks(rows)
         # single rank: GAE + normalisation and the end-of-learn statistics are one launch each
         ws.merged_tail = ws.fused and self.world_size == 1
-        ws.ticket = torch.zeros(2, dtype=torch.int32, device=dev)
         if ws.fused:
             assert ws.nblk_p == K.epoch_blocks(rows)
             # the weights in the forward kernel's fragment order (model, critic, reference policy)
-            ws.pk_actor = torch.zeros(K.epoch_packed_numel(act), device=dev)
-            ws.pk_critic = torch.zeros(K.epoch_packed_numel(cri), device=dev)
-            ws.pk_ref = torch.zeros(K.epoch_packed_numel(act), device=dev)
+            ws.pk_actor = torch.zeros(K.epoch_packed_numel(act), device=self.device)
+            ws.pk_critic = torch.zeros(K.epoch_packed_numel(cri), device=self.device)
+            ws.pk_ref = torch.zeros(K.epoch_packed_numel(act), device=self.device)
         ws.pstride = 8 + 2 * A
+
+    def _ws_stem(self, ws):
+        """the sequence, frame and scratch buffers of a policy with an LSTM and / or a CNN stem"""
+        f, dev, K = self._f, self.device, self.K
+        act, cri = self.model.actor, self.model.critic
+        B, N, D, A, pix_dtype = ws.key
+        rows, Dx = ws.rows, self.model.stem_in
+        R1 = B * (N + 1)
+        ws.h0 = ws.c0 = ws.cnn_it = ws.cnn_gae = ws.frames_it = None
+        ws.low_it = f(rows, D)                    # obs[:, :E] (raw: also feeds z_update)
+        ws.act_it, ws.beh_it = f(rows, A), f(rows, 2 * A)
+        ws.ztmp = f(R1, D)
+        ws.lcat, ws.xcat = f(B, N + 1, D), f(R1, Dx)     # critic pass over cat(obs, obs_next)
+        ws.h1G, ws.h2G = f(R1, cri.H1), f(R1, cri.H2)
+        n_sk = max(K.mlp3_backward_ws_floats(n, rows) for n in (act, cri))
+        ws.mlp_sk = f(n_sk) if n_sk else None          # split-K partials of the MLP weight gradients over B x T rows
+        # scratch for the packed weights of the fused many-row forward (K.mlp3_forward(pack=...): one launch instead
+        # of three layer GEMMs from FUSED_ROWS_MIN rows on; the shapes it does not take keep the layered path)
+        try:
+            ws.pack_stem = f(max(K.mlp3_packed_numel(n) for n in (act, cri)))
+        except Exception:
+            ws.pack_stem = None
+        n_z = K.zfilter_update_ws_floats(rows, D)
+        ws.zscratch = f(n_z) if n_z else None          # the z-update's chunk sums over B * E rows (K.zfilter_update)
+        n_pt = max(K.mlp3_dgrad_rows_ws_floats(n) for n in (act, cri))
+        ws.packT_stem = f(n_pt) if n_pt else None    # ... and of the fused many-row data gradients (K.mlp3_backward)
+        if self.if_rnn_policy:
+            # LSTM stem (ppo_net.py:143-152): sequence buffers for the epoch passes (T = E)
+            # and for the critic pass (T = N + 1, ppo.py:376-386)
+            F = self.model.rnn_hidden
+            nl = self.model.rnn_layers
+            ws.h0L, ws.c0L = f(nl, B, F), f(nl, B, F)          # agent-side state of every layer
+            ws.h0, ws.c0 = ws.h0L[0], ws.c0L[0]
+            ws.gates, ws.lo, ws.cs, ws.hp, ws.dlo = f(rows, 4 * F), f(rows, F), f(rows, F), f(rows, F), f(rows, F)
+            ws.gatesG, ws.loG, ws.csG = f(R1, 4 * F), f(R1, F), f(R1, F)
+            # stacked layers above the first: their own sequence buffers (layer l reads layer l-1's lo)
+            ws.upper = [types.SimpleNamespace(gates=f(rows, 4 * F), lo=f(rows, F), cs=f(rows, F),
+                                              hp=f(rows, F), dlo=f(rows, F)) for _ in range(nl - 1)]
+            ws.loG2 = f(R1, F) if nl > 1 else None
+            n_sk = max(K.lstm_backward_ws_floats(r, B, ws.E) for r in self.model.rnns)
+            ws.lstm_sk = f(n_sk) if n_sk else None
+        if self.model.if_pixel:
+            # CNN stem (builders.py:8-33): frames stay in their source dtype (uint8 from the
+            # cameras); the critic pass runs the stem in chunks to bound the patch matrices
+            from surreal_amd.model.cnn_stem import CnnStem
+            cnn = self.model.cnn
+            cam = (cnn.C, cnn.H, cnn.W)
+            ws.frames_it = torch.empty((rows,) + cam, device=dev, dtype=pix_dtype)
+            ws.fcat = torch.empty((B, N + 1) + cam, device=dev, dtype=pix_dtype)
+            ws.dxn = torch.zeros(rows, Dx, device=dev)
+            chunk = int(self.session_config.learner.get('cnn_chunk_frames', 2048))
+            ws.cnn_it = CnnStem.workspace(cnn, rows, dev, backward=True)
+            ws.cnn_it.sk = self.model._cnn_stem.splitk_workspace(cnn, rows, dev)
+            ws.cnn_gae = ws.cnn_it if rows >= min(chunk, R1) else \
+                CnnStem.workspace(cnn, min(chunk, R1), dev, backward=False)
+
+    def _ws_exchange(self, ws):
+        """the gradients, the loss and value partial sums, and what several ranks exchange: which buffer each of them
+        lives in depends on the exchange that carries it, so all of that is decided here"""
+        f, ft, dev, K = self._f, self._ft, self.device, self.K
+        act, cri = self.model.actor, self.model.critic
+        B, _, D, A = ws.key[:4]
+        rows, W = ws.rows, self.world_size
+        Ev = self.epoch_baseline
+        n_a, n_c = self.model.actor_flat.numel(), self.model.critic_flat.numel()
         # batch means are over the GLOBAL batch: ranks may hold different numbers of sub-trajectories
         # (B not divisible by the world size), so the totals are exchanged once per workspace.  A
         # rank's batch shape may therefore only change in a learn() where every rank's does.
         ws.n_total, ws.B_total, nblk_p_all = rows, B, ws.nblk_p
-        if self.world_size > 1:
+        if W > 1:
             mine = torch.tensor([rows, B], dtype=torch.int64, device=dev)
-            every = torch.empty(2 * self.world_size, dtype=torch.int64, device=dev)
+            every = torch.empty(2 * W, dtype=torch.int64, device=dev)
             self._dist.all_gather_into_tensor(every, mine)
             every = every.view(-1, 2).tolist()
             ws.n_total, ws.B_total = sum(r for r, _ in every), sum(b for _, b in every)
-            ws.nblk_v = max(vblocks(r) for r, _ in every)
+            ws.nblk_v = max(ws.vblocks(r) for r, _ in every)
             nblk_p_all = max(K.loss_blocks(r) for r, _ in every)
-        ws.dp_epoch = self.world_size > 1 and not stem
+        ws.dp_epoch = W > 1 and not ws.stem
         ws.tail_deferred = ws.dp_epoch and self.epoch_policy >= self.epoch_baseline
+        # Stem policies on several ranks, clip mode: ONE exchange per policy epoch.  Nothing in the clip gradient depends on
+        # the batch (dz3 = g_surr / n), so the loss sums travel WITH the gradient -- [actor group's gradient | loss sums] is
+        # one buffer, one all-reduce -- and the statistics, log_var's gradient and the KL early-exit flag are formed from
+        # the global sums behind it, in front of the optimiser launch that honours the flag (_stem_policy_update).  Adapt
+        # mode keeps two: its KL coefficient needs the global KL BEFORE the backward pass, and the two-right-hand-side
+        # form that avoids that would run the stem's backward twice.
+        ws.stem_one_exchange = bool(ws.stem and W > 1 and self.ppo_mode == 'clip' and
+                                    self.session_config.learner.get('stem_one_exchange', True))
+        al = lambda n: (n + 3) & ~3  # noqa: E731
+        # one buffer for both groups' gradients: a data-parallel lock-step epoch all-reduces it once
         if ws.dp_epoch:
             # [surrogate share of the actor gradient | critic gradient | KL share (adapt) | loss
-            # partial rows]: everything an epoch exchanges, in ONE all-reduce (_enqueue_lockstep_epochs)
-            al = lambda n: (n + 3) & ~3  # noqa: E731
+            # partial rows]: everything an epoch exchanges, in ONE all-reduce (_enqueue_dp_epoch_tail)
             adapt = self.ppo_mode != 'clip'
             off_k = al(n_a + n_c)
             off_p = off_k + (al(act.numel) if adapt else 0)
@@ -515,7 +473,7 @@ class PPOLearner(Learner):
             ws.ppart_ar = ws.ar[off_p:].view(nblk_p_all, ws.pstride)
             if adapt:
                 ws.dz3k, ws.dz2k, ws.dz1k = f(rows, A), f(rows, act.H2), f(rows, act.H1)
-                ws.dz3kT, ws.dz2kT, ws.dz1kT = ft(A), ft(act.H2), ft(act.H1)
+                ws.dz3kT, ws.dz2kT, ws.dz1kT = ft(A, rows), ft(act.H2, rows), ft(act.H1, rows)
                 ws.sumsq_k = torch.zeros(K.mlp3_backward_partials(act), device=dev)
             # what the end of a learn exchanges, packed into one all-gather (_enqueue_tail_exchange):
             # [loss sums of the final policy pass | value-loss moments of all epochs | return
@@ -524,70 +482,39 @@ class PPOLearner(Learner):
             cuts = np.cumsum([0, ws.pstride, Ev * ws.nblk_v * 8, 3, nz]).tolist()
             ws.tail_cuts = cuts
             ws.tail_pack = torch.zeros(cuts[-1], device=dev)
-            ws.tail_gather = f(self.world_size, cuts[-1])
+            ws.tail_gather = f(W, cuts[-1])
             ws.tp_ppart = ws.tail_pack[:cuts[1]].view(1, ws.pstride)
             ws.vpart_loc_all = ws.tail_pack[cuts[1]:cuts[2]].view(Ev, ws.nblk_v, 8)
             ws.tp_ret = ws.tail_pack[cuts[2]:cuts[3]]
             ws.zsum = f(nz) if nz else None
         else:
             ws.grads_all = torch.zeros(n_a + n_c, device=dev)
+            ws.vpart_loc_all = torch.zeros(Ev, ws.nblk_v, 8, device=dev)   # lock-step: gathered once per learn
         ws.grads_a, ws.grads_c = ws.grads_all[:n_a], ws.grads_all[n_a:]
         ws.ppart = f(ws.nblk_p, ws.pstride)
         ws.ppart_sum = f(1, ws.pstride)
         ws.ppart_fold = f(64, ws.pstride)
-        # Stem policies on several ranks, clip mode: ONE exchange per policy epoch.  Nothing in the clip gradient depends on
-        # the batch (dz3 = g_surr / n), so the loss sums travel WITH the gradient -- [actor group's gradient | loss sums] is
-        # one buffer, one all-reduce -- and the statistics, log_var's gradient and the KL early-exit flag are formed from
-        # the global sums behind it, in front of the optimiser launch that honours the flag (_stem_policy_update).  Adapt
-        # mode keeps two: its KL coefficient needs the global KL BEFORE the backward pass, and the two-right-hand-side
-        # form that avoids that would run the stem's backward twice.
-        ws.stem_one_exchange = bool(stem and self.world_size > 1 and self.ppo_mode == 'clip' and
-                                    self.session_config.learner.get('stem_one_exchange', True))
         if ws.stem_one_exchange:
-            ws.ar_pol = torch.zeros(((n_a + 3) & ~3) + ws.pstride, device=dev)
+            ws.ar_pol = torch.zeros(al(n_a) + ws.pstride, device=dev)
             ws.grads_a = ws.ar_pol[:n_a]
-            ws.ppart_sum = ws.ar_pol[(n_a + 3) & ~3:].view(1, ws.pstride)
+            ws.ppart_sum = ws.ar_pol[al(n_a):].view(1, ws.pstride)
         # partial rows a rank does not fill stay zero (count 0: skipped by the merge)
-        ws.vpart = torch.zeros(Ev, self.world_size * ws.nblk_v, 8, device=dev)
+        ws.vpart = torch.zeros(Ev, W * ws.nblk_v, 8, device=dev)
         ws.vpart_local = torch.zeros(ws.nblk_v, 8, device=dev)
-        if not ws.dp_epoch:
-            ws.vpart_loc_all = torch.zeros(Ev, ws.nblk_v, 8, device=dev)   # lock-step: gathered once per learn
-        ws.vgather = f(self.world_size, Ev, ws.nblk_v, 8)
+        ws.vgather = f(W, Ev, ws.nblk_v, 8)
         ws.np_a = K.mlp3_backward_partials(act)
         ws.np_c = K.mlp3_backward_partials(cri)
         ws.sumsq_a = torch.zeros(max(ws.np_a + 1, K.sumsq_blocks(ws.grads_a.numel())), device=dev)
         ws.sumsq_c = torch.zeros(max(ws.np_c, K.sumsq_blocks(ws.grads_c.numel())), device=dev)
+        # log_var's gradient (behind the actor MLP's) and the slot its square goes to (behind the MLP's partials)
+        ws.dlogvar = ws.grads_a[act.numel:act.numel + A]
+        ws.dlogvar_sumsq = ws.sumsq_a[ws.np_a:ws.np_a + 1]
         if self.use_z_filter:
             ws.zdelta = ws.tail_pack[ws.tail_cuts[3]:] if ws.dp_epoch else torch.zeros(2 * D + 1, device=dev)
-        ws.xerr = ws.ctrl_i[L.C_XCHG_ERR:L.C_XCHG_ERR + 1]
-        if self.world_size > 1:
-            self._setup_peer_exchange(ws, n_a + n_c)
-        self._ws = ws
-        self._graphs = {}
-        return ws
-
-    def _setup_peer_exchange(self, ws, n_grads):
-        """several ranks on one node: the fp32 exchanges of a learn() as kernels over IPC-mapped peer buffers
-        (surreal_amd.distributed.PeerExchange) -- set up and SELF-CHECKED once, collectively; any failure leaves
-        the process group (RCCL) in place.  session_config.learner.peer_exchange = False keeps RCCL."""
-        d = self._dist
-        d.err_word = ws.xerr
-        want = bool(self.session_config.learner.get('peer_exchange', True)) and self.device != 'cpu'
-        need = max(ws.ar.numel() if ws.dp_epoch else n_grads, 64)
-        if getattr(ws, 'tail_gather', None) is not None:
-            need = max(need, ws.tail_gather.numel())
-        if not want:
-            return
-        if d.exchange is not None and d.exchange.capacity >= need:
-            return
-        if d.exchange is not None:
-            d._d.barrier()
-            d.exchange.close()
-            d.exchange = None
-        from surreal_amd.distributed.peer_exchange import PeerExchange
-        d.exchange = PeerExchange.create(d._d, need, timeout_s=float(self.session_config.learner.get(
-            'peer_exchange_timeout_s', 5.0)))
-        self.exchange_kind = 'peer buffers (%s)' % d.exchange.check_message if d.exchange is not None else 'process group'
+        if W > 1:
+            need = max(64, ws.ar.numel(), ws.tail_gather.numel()) if ws.dp_epoch else max(64, n_a + n_c)
+            if setup_peer_exchange(self, ws.xerr, need):
+                self.exchange_kind = self._dist.kind()
 
     # ======================================================================================
     # batch handling
@@ -671,23 +598,26 @@ class PPOLearner(Learner):
     def _enqueue_gae_from_values(self, ws, obs, rewards, dones):
         K = self.K
         B, N, D = obs.shape
+        vals, tail = (ws.vals[:B * N], ws.vals[B * N:]) if ws.split_tail else (ws.vals, None)
         if ws.merged_tail and self.norm_adv:
-            K.gae_norm(ws.vals[:B * N] if ws.split_tail else ws.vals, rewards, dones, ws.gpow, ws.lpow, self.gamma,
-                       self.gamma ** N, B, N, N, ws.adv, ws.ret, ws.adv_mom, 1e-4, ws.ticket[0:1],
-                       values_tail=ws.vals[B * N:] if ws.split_tail else None)
+            K.gae_norm(vals, rewards, dones, ws.gpow, ws.lpow, self.gamma, self.gamma ** N, B, N, N, ws.adv, ws.ret,
+                       ws.adv_mom, 1e-4, ws.ticket[0:1], values_tail=tail)
             return
-        if ws.split_tail:
-            K.gae(ws.vals[:B * N], rewards, dones, ws.gpow, ws.lpow, self.gamma, self.gamma ** N,
-                  B, N, N, ws.adv, ws.ret, values_tail=ws.vals[B * N:])
-        else:
-            K.gae(ws.vals, rewards, dones, ws.gpow, ws.lpow, self.gamma, self.gamma ** N, B, N, N,
-                  ws.adv, ws.ret)
+        K.gae(vals, rewards, dones, ws.gpow, ws.lpow, self.gamma, self.gamma ** N, B, N, N, ws.adv, ws.ret,
+              values_tail=tail)
+        self._enqueue_adv_normalize(ws)
+
+    def _enqueue_moments(self, ws, x, out):
+        """mean, variance and count of x over the GLOBAL batch: every rank's moments, merged in rank order"""
+        self.K.moments(x, out)
+        if self.world_size > 1:
+            self._dist.all_gather_into_tensor(ws.mom_parts.view(-1), out.clone())
+            self.K.moments_merge(ws.mom_parts, out)
+
+    def _enqueue_adv_normalize(self, ws):
         if self.norm_adv:
-            K.moments(ws.adv, ws.adv_mom)
-            if self.world_size > 1:
-                self._dist.all_gather_into_tensor(ws.mom_parts.view(-1), ws.adv_mom.clone())
-                K.moments_merge(ws.mom_parts, ws.adv_mom)
-            K.adv_normalize(ws.adv, ws.adv_mom, 1e-4)
+            self._enqueue_moments(ws, ws.adv, ws.adv_mom)
+            self.K.adv_normalize(ws.adv, ws.adv_mom, 1e-4)
 
     def _enqueue_lockstep_epochs(self, ws, actions0, behave0, first_extra=(), after_first=None):
         """Policy epoch e and value epoch e advance together: the reference runs the two loops
@@ -696,8 +626,6 @@ class PPOLearner(Learner):
         early exit only masks the actor's share (its jobs carry the device stop flag)."""
         K, m = self.K, self.model
         Ep, Ev = self.epoch_policy, self.epoch_baseline
-        mode = L.SMX_PPO_CLIP if self.ppo_mode == 'clip' else L.SMX_PPO_ADAPT
-        A = self.action_dim
         W = self.world_size
         n_total = ws.n_total
         aj = dict(net=m.actor, x=ws.xn, h1=ws.h1a, h2=ws.h2a, out=ws.mean, act=L.SMX_ACT_TANH,
@@ -715,35 +643,31 @@ class PPOLearner(Learner):
             if e == 0 and after_first is not None:
                 after_first()
             if ws.dp_epoch and pol_u and val:
-                self._enqueue_dp_epoch(ws, e, mode, aj, cj, actions0, behave0)
+                self._enqueue_dp_epoch(ws, e, aj, cj, actions0, behave0)
                 continue
             if pol_f and W == 1:
                 # one ABI call: policy loss and value loss share a launch, then the policy finalize
-                K.epoch_losses(mode, ws.mean, m.log_var.view(-1), actions0, behave0, ws.ref_pol, ws.adv,
+                K.epoch_losses(self._mode, ws.mean, m.log_var.view(-1), actions0, behave0, ws.ref_pol, ws.adv,
                                ws.ctrl_f, ws.g_surr, ws.g_kl, ws.ppart, e > 0, pol_u, ws.dz3a,
-                               ws.grads_a[m.actor.numel:m.actor.numel + A],
-                               ws.sumsq_a[ws.np_a:ws.np_a + 1], ws.pstats[e], dz3_t=ws.dz3aT,
+                               ws.dlogvar, ws.dlogvar_sumsq, ws.pstats[e], dz3_t=ws.dz3aT,
                                values=ws.vpred if val else None, returns=ws.ret, v_dz3=ws.dz3c,
                                v_partials=ws.vpart[e] if val else None)
-            elif pol_f and ws.tail_deferred and not pol_u and not val:
-                # the final, forward-only policy pass: its loss sums travel with the end-of-learn
-                # exchange (_enqueue_tail_exchange), which also runs its finalize
-                K.policy_loss(mode, ws.mean, m.log_var.view(-1), actions0, behave0, ws.ref_pol,
-                              ws.adv, ws.ctrl_f, ws.g_surr, ws.g_kl, ws.ppart)
-                torch.sum(ws.ppart, 0, keepdim=True, out=ws.tp_ppart)
-                continue
             elif pol_f:
-                K.policy_loss(mode, ws.mean, m.log_var.view(-1), actions0, behave0, ws.ref_pol,
+                K.policy_loss(self._mode, ws.mean, m.log_var.view(-1), actions0, behave0, ws.ref_pol,
                               ws.adv, ws.ctrl_f, ws.g_surr, ws.g_kl, ws.ppart)
+                if ws.tail_deferred and not pol_u and not val:
+                    # the final, forward-only policy pass: its loss sums travel with the end-of-learn
+                    # exchange (_enqueue_tail_exchange), which also runs its finalize
+                    torch.sum(ws.ppart, 0, keepdim=True, out=ws.tp_ppart)
+                    continue
                 part, nblk = ws.ppart, ws.nblk_p
                 if W > 1:
                     torch.sum(ws.ppart, 0, keepdim=True, out=ws.ppart_sum)
                     self._dist.all_reduce(ws.ppart_sum)
                     part, nblk = ws.ppart_sum, 1
-                K.policy_finalize(mode, part, nblk, ws.g_surr, ws.g_kl, m.log_var.view(-1), n_total,
+                K.policy_finalize(self._mode, part, nblk, ws.g_surr, ws.g_kl, m.log_var.view(-1), n_total,
                                   ws.ctrl_f, e > 0, pol_u, ws.dz3a,
-                                  ws.grads_a[m.actor.numel:m.actor.numel + A],
-                                  ws.sumsq_a[ws.np_a:ws.np_a + 1], ws.pstats[e], dz3_t=ws.dz3aT)
+                                  ws.dlogvar, ws.dlogvar_sumsq, ws.pstats[e], dz3_t=ws.dz3aT)
             if val and not (pol_f and W == 1):
                 # the value-loss partial sums only feed statistics: every epoch's stay local and
                 # are gathered once at the end of the learn
@@ -758,7 +682,7 @@ class PPOLearner(Learner):
                     # all-reduced loss partials and is global already: exactly one copy may enter
                     # the sum (exact for any world size)
                     if self.rank != 0:
-                        ws.grads_a[m.actor.numel:m.actor.numel + A].zero_()
+                        ws.dlogvar.zero_()
                     self._dist.all_reduce(ws.grads_all)
                 elif pol_u:
                     self._dist.all_reduce(ws.grads_a[:m.actor.numel])
@@ -770,26 +694,22 @@ class PPOLearner(Learner):
                 if val:
                     K.sumsq_partials(ws.grads_c, ws.sumsq_c)
                     np_c = K.sumsq_blocks(ws.grads_c.numel())
-            if pol_u and val:        # both groups step in one launch
-                K.clip_adam_pair((m.actor_flat, ws.grads_a, self.actor_exp_avg, self.actor_exp_avg_sq,
-                                  ws.sumsq_a, np_a, True, ws.pstats[e, L.PS_GRADNORM:L.PS_GRADNORM + 1]),
-                                 (m.critic_flat, ws.grads_c, self.critic_exp_avg, self.critic_exp_avg_sq,
-                                  ws.sumsq_c, np_c, False, ws.vstats[e, L.VS_GRADNORM:L.VS_GRADNORM + 1]),
-                                 ws.ctrl_f)
-            elif pol_u:
-                K.clip_adam(m.actor_flat, ws.grads_a, self.actor_exp_avg, self.actor_exp_avg_sq,
-                            ws.sumsq_a, np_a, ws.ctrl_f, 0, True,
-                            ws.pstats[e, L.PS_GRADNORM:L.PS_GRADNORM + 1])
-            elif val:
-                K.clip_adam(m.critic_flat, ws.grads_c, self.critic_exp_avg, self.critic_exp_avg_sq,
-                            ws.sumsq_c, np_c, ws.ctrl_f, 1, False,
-                            ws.vstats[e, L.VS_GRADNORM:L.VS_GRADNORM + 1])
+            self._enqueue_adam(ws, e, pol_u, val, np_a, np_c)
         if ws.tail_deferred:
             return
+        self._enqueue_value_finalize(ws)
+
+    def _enqueue_value_finalize(self, ws, gathered=None):
+        """the value epochs' statistics from the value-loss moments of every epoch.  On several ranks the epochs left
+        them local: they are gathered here, once per learn (gathered: they have been already, [rank, epoch, block, 8]),
+        and laid out per epoch in rank order"""
+        Ev, W = self.epoch_baseline, self.world_size
         if W > 1:
-            self._dist.all_gather_into_tensor(ws.vgather.view(-1), ws.vpart_loc_all.view(-1))
-            ws.vpart.view(Ev, W, ws.nblk_v, 8).copy_(ws.vgather.permute(1, 0, 2, 3))
-        K.value_finalize(ws.vpart, Ev, ws.vpart.shape[1], ws.vstats, L.VS_STRIDE)
+            if gathered is None:
+                self._dist.all_gather_into_tensor(ws.vgather.view(-1), ws.vpart_loc_all.view(-1))
+                gathered = ws.vgather
+            ws.vpart.view(Ev, W, ws.nblk_v, 8).copy_(gathered.permute(1, 0, 2, 3))
+        self.K.value_finalize(ws.vpart, Ev, ws.vpart.shape[1], ws.vstats, L.VS_STRIDE)
 
     def _clear_foreign_partials(self, ws):
         """The all-reduce sums ws.ar in place, so afterwards EVERY loss-partial row holds the global sum --
@@ -806,8 +726,6 @@ class PPOLearner(Learner):
         the layered schedule takes nine.  Same arithmetic contract as _enqueue_lockstep_epochs."""
         K, m = self.K, self.model
         Ep, Ev = self.epoch_policy, self.epoch_baseline
-        mode = L.SMX_PPO_CLIP if self.ppo_mode == 'clip' else L.SMX_PPO_ADAPT
-        A = self.action_dim
         n_total = ws.n_total
         # the reference policy and the critic's obs_next rows: one forward-only launch, then GAE
         pre = [dict(net=ref_job['net'], packed=ws.pk_ref, x=ref_job['x'], out=ref_job['out'], act=L.SMX_ACT_TANH)]
@@ -822,15 +740,15 @@ class PPOLearner(Learner):
                   dz3=ws.dz3c, dz3T=ws.dz3c, dz2T=ws.dz2cT, dz1T=ws.dz1cT, xT=ws.xnT, grads=ws.grads_c,
                   sumsq=ws.sumsq_c)         # OUT = 1: dz3^T is dz3 itself
         dp = ws.dp_epoch                     # several ranks: one all-reduce per epoch (see _enqueue_dp_epoch)
-        adapt = mode == L.SMX_PPO_ADAPT
+        pack = ((m.actor, ws.pk_actor), (m.critic, ws.pk_critic))       # a paired step refreshes both packed copies
+        adapt = self.ppo_mode != 'clip'
 
         def loss_args(e):
-            return dict(mode=mode, rows=ws.rows, log_var=m.log_var.view(-1), actions=actions0, behave=behave0,
+            return dict(mode=self._mode, rows=ws.rows, log_var=m.log_var.view(-1), actions=actions0, behave=behave0,
                         ref=ws.ref_pol, adv=ws.adv, g_surr=ws.g_surr, g_kl=ws.g_kl,
                         partials=ws.ppart_ar if dp and e < Ep else ws.ppart,
                         check_stop=e > 0, will_update=e < Ep,
-                        dlogvar=ws.grads_a[m.actor.numel:m.actor.numel + A],
-                        dlogvar_sumsq=ws.sumsq_a[ws.np_a:ws.np_a + 1], stats=ws.pstats[min(e, Ep)],
+                        dlogvar=ws.dlogvar, dlogvar_sumsq=ws.dlogvar_sumsq, stats=ws.pstats[min(e, Ep)],
                         returns=ws.ret, v_dz3=ws.dz3c,
                         v_partials=(ws.vpart_loc_all if dp else ws.vpart)[min(e, Ev - 1)], v_will_update=True)
 
@@ -852,25 +770,15 @@ class PPOLearner(Learner):
                 K.epoch_forward([aj, cj], loss, ws.ctrl_f, n_total)
                 K.epoch_backward(rhs + [cj], loss, ws.ctrl_f, n_total)
                 K.mlp3_wgrad_multi(rhs + [cj])
-                self._dist.all_reduce(ws.ar)
-                K.epoch_combine(mode, ws.ppart_ar, ws.ppart_ar.shape[0], n_total, m.log_var.view(-1), ws.ctrl_f,
-                                e > 0, True, ws.pstats[e], ws.grads_a, ws.grads_k if adapt else None,
-                                m.actor.numel, ws.sumsq_a, ws.grads_c, ws.sumsq_c)
-                K.clip_adam_pair((m.actor_flat, ws.grads_a, self.actor_exp_avg, self.actor_exp_avg_sq,
-                                  ws.sumsq_a, K.sumsq_blocks(ws.grads_a.numel()), True,
-                                  ws.pstats[e, L.PS_GRADNORM:L.PS_GRADNORM + 1]),
-                                 (m.critic_flat, ws.grads_c, self.critic_exp_avg, self.critic_exp_avg_sq,
-                                  ws.sumsq_c, K.sumsq_blocks(ws.grads_c.numel()), False,
-                                  ws.vstats[e, L.VS_GRADNORM:L.VS_GRADNORM + 1]),
-                                 ws.ctrl_f, pack=((m.actor, ws.pk_actor), (m.critic, ws.pk_critic)))
+                self._enqueue_dp_epoch_tail(ws, e, pack=pack)
             return
 
         for e in range(max(Ep + 1, Ev)):
             pol_f, pol_u, val = e <= Ep, e < Ep, e < Ev
             loss = loss_args(e)
+            bj = ([aj] if pol_u else []) + ([cj] if val else [])         # the jobs that update in this epoch
             if ws.fb and (pol_u or not pol_f) and (pol_u or val):
                 # forward + loss + data gradients of every job of the epoch in ONE launch (smx_epoch_fwdbwd_f32)
-                bj = ([aj] if pol_u else []) + ([cj] if val else [])
                 K.epoch_fwdbwd(bj, loss, ws.ctrl_f, n_total, ws.sync[e:e + 1], ws.kl_slots[e])
                 K.mlp3_wgrad_multi(bj)
             else:
@@ -878,28 +786,13 @@ class PPOLearner(Learner):
                 if pol_f and not pol_u:
                     K.epoch_backward([aj], loss, ws.ctrl_f, n_total)       # statistics + early exit only
                 if pol_u or val:
-                    bj = ([aj] if pol_u else []) + ([cj] if val else [])
                     K.epoch_backward(bj, loss, ws.ctrl_f, n_total)
                     K.mlp3_wgrad_multi(bj)
-            np_a, np_c = ws.np_a + 1, ws.np_c
-            if pol_u and val:        # both groups step in one launch
-                K.clip_adam_pair((m.actor_flat, ws.grads_a, self.actor_exp_avg, self.actor_exp_avg_sq,
-                                  ws.sumsq_a, np_a, True, ws.pstats[e, L.PS_GRADNORM:L.PS_GRADNORM + 1]),
-                                 (m.critic_flat, ws.grads_c, self.critic_exp_avg, self.critic_exp_avg_sq,
-                                  ws.sumsq_c, np_c, False, ws.vstats[e, L.VS_GRADNORM:L.VS_GRADNORM + 1]),
-                                 ws.ctrl_f, pack=((m.actor, ws.pk_actor), (m.critic, ws.pk_critic)))
-            elif pol_u:
-                K.clip_adam(m.actor_flat, ws.grads_a, self.actor_exp_avg, self.actor_exp_avg_sq,
-                            ws.sumsq_a, np_a, ws.ctrl_f, 0, True,
-                            ws.pstats[e, L.PS_GRADNORM:L.PS_GRADNORM + 1])
-            elif val:
-                K.clip_adam(m.critic_flat, ws.grads_c, self.critic_exp_avg, self.critic_exp_avg_sq,
-                            ws.sumsq_c, np_c, ws.ctrl_f, 1, False,
-                            ws.vstats[e, L.VS_GRADNORM:L.VS_GRADNORM + 1])
+            self._enqueue_adam(ws, e, pol_u, val, ws.np_a + 1, ws.np_c, pack=pack)
             if pol_u != val:         # (an unpaired step -- epoch_policy != epoch_baseline -- repacks separately)
                 K.epoch_pack([(m.actor, ws.pk_actor)] if pol_u else [(m.critic, ws.pk_critic)])
         if not ws.merged_tail:
-            K.value_finalize(ws.vpart, Ev, ws.vpart.shape[1], ws.vstats, L.VS_STRIDE)
+            self._enqueue_value_finalize(ws)
 
     def _enqueue_tail_exchange(self, ws, obs0, actions0, behave0):
         """end of a data-parallel lock-step learn: ONE all-gather carries the final policy pass's
@@ -908,7 +801,6 @@ class PPOLearner(Learner):
         order, so the replicas stay bit-identical"""
         K, m, W = self.K, self.model, self.world_size
         Ep, Ev, D = self.epoch_policy, self.epoch_baseline, obs0.shape[1]
-        mode = L.SMX_PPO_CLIP if self.ppo_mode == 'clip' else L.SMX_PPO_ADAPT
         c = ws.tail_cuts
         K.moments(ws.ret, ws.tp_ret)                           # _avg_return_targ (ppo.py:571)
         if self.use_z_filter:                                  # model.z_update(obs_iter)  (ppo.py:578-579)
@@ -917,30 +809,26 @@ class PPOLearner(Learner):
         self._dist.all_gather_into_tensor(ws.tail_gather.view(-1), ws.tail_pack)
         G = ws.tail_gather
         torch.sum(G[:, :c[1]], 0, keepdim=True, out=ws.ppart_sum)
-        K.policy_finalize(mode, ws.ppart_sum, 1, ws.g_surr, ws.g_kl, m.log_var.view(-1), ws.n_total,
+        K.policy_finalize(self._mode, ws.ppart_sum, 1, ws.g_surr, ws.g_kl, m.log_var.view(-1), ws.n_total,
                           ws.ctrl_f, Ep > 0, False, ws.dz3a,
-                          ws.grads_a[m.actor.numel:m.actor.numel + self.action_dim],
-                          ws.sumsq_a[ws.np_a:ws.np_a + 1], ws.pstats[Ep], dz3_t=ws.dz3aT)
-        ws.vpart.view(Ev, W, ws.nblk_v, 8).copy_(G[:, c[1]:c[2]].reshape(W, Ev, ws.nblk_v, 8).permute(1, 0, 2, 3))
-        K.value_finalize(ws.vpart, Ev, ws.vpart.shape[1], ws.vstats, L.VS_STRIDE)
+                          ws.dlogvar, ws.dlogvar_sumsq, ws.pstats[Ep], dz3_t=ws.dz3aT)
+        self._enqueue_value_finalize(ws, gathered=G[:, c[1]:c[2]].reshape(W, Ev, ws.nblk_v, 8))
         ws.mom_parts.copy_(G[:, c[2]:c[3]])
         K.moments_merge(ws.mom_parts, ws.ret_mom)
         if self.use_z_filter:
             torch.sum(G[:, c[3]:], 0, out=ws.zsum)
-            m.z_filter.running_sum += ws.zsum[:D]
-            m.z_filter.running_sumsq += ws.zsum[D:2 * D]
-            m.z_filter.count += ws.zsum[2 * D:]
+            self._z_add(ws.zsum)
 
-    def _enqueue_dp_epoch(self, ws, e, mode, aj, cj, actions0, behave0):
+    def _enqueue_dp_epoch(self, ws, e, aj, cj, actions0, behave0):
         """One lock-step epoch on several ranks with ONE collective.  The loss
         gradient is linear in dz3 = (g_surr + c_kl * g_kl) / n and only c_kl needs the global mean
         KL, so the backward pass runs on both right-hand sides (a third job in the same three
         launches) and the combination is formed after the all-reduce of
         [G_surr | G_critic | G_kl | loss partial rows]."""
         K, m = self.K, self.model
-        adapt = mode == L.SMX_PPO_ADAPT
+        adapt = self.ppo_mode != 'clip'
         self._clear_foreign_partials(ws)
-        K.epoch_losses_dp(mode, ws.mean, m.log_var.view(-1), actions0, behave0, ws.ref_pol, ws.adv,
+        K.epoch_losses_dp(self._mode, ws.mean, m.log_var.view(-1), actions0, behave0, ws.ref_pol, ws.adv,
                           ws.ctrl_f, ws.dz3a, ws.dz3k if adapt else ws.g_kl, ws.ppart_ar, ws.n_total,
                           g_surr_t=ws.dz3aT, g_kl_t=ws.dz3kT if adapt else None, values=ws.vpred,
                           returns=ws.ret, v_dz3=ws.dz3c, v_partials=ws.vpart_loc_all[e])
@@ -949,17 +837,32 @@ class PPOLearner(Learner):
             jobs.append(dict(aj, dz3=ws.dz3k, dz2=ws.dz2k, dz1=ws.dz1k, grads=ws.grads_k,
                              sumsq=ws.sumsq_k, dz3T=ws.dz3kT, dz2T=ws.dz2kT, dz1T=ws.dz1kT))
         K.mlp3_backward_multi(jobs + [cj])
+        self._enqueue_dp_epoch_tail(ws, e)
+
+    def _enqueue_dp_epoch_tail(self, ws, e, pack=None):
+        """what ends a data-parallel lock-step epoch, layered or fused: ONE all-reduce of [gradients | loss partial rows],
+        the combination formed from the global sums, and both groups' optimiser step"""
+        K, m = self.K, self.model
         self._dist.all_reduce(ws.ar)
-        K.epoch_combine(mode, ws.ppart_ar, ws.ppart_ar.shape[0], ws.n_total, m.log_var.view(-1), ws.ctrl_f,
-                        e > 0, True, ws.pstats[e], ws.grads_a, ws.grads_k if adapt else None,
+        K.epoch_combine(self._mode, ws.ppart_ar, ws.ppart_ar.shape[0], ws.n_total, m.log_var.view(-1), ws.ctrl_f,
+                        e > 0, True, ws.pstats[e], ws.grads_a, ws.grads_k if self.ppo_mode != 'clip' else None,
                         m.actor.numel, ws.sumsq_a, ws.grads_c, ws.sumsq_c)
-        K.clip_adam_pair((m.actor_flat, ws.grads_a, self.actor_exp_avg, self.actor_exp_avg_sq,
-                          ws.sumsq_a, K.sumsq_blocks(ws.grads_a.numel()), True,
-                          ws.pstats[e, L.PS_GRADNORM:L.PS_GRADNORM + 1]),
-                         (m.critic_flat, ws.grads_c, self.critic_exp_avg, self.critic_exp_avg_sq,
-                          ws.sumsq_c, K.sumsq_blocks(ws.grads_c.numel()), False,
-                          ws.vstats[e, L.VS_GRADNORM:L.VS_GRADNORM + 1]),
-                         ws.ctrl_f)
+        self._enqueue_adam(ws, e, True, True, K.sumsq_blocks(ws.grads_a.numel()), K.sumsq_blocks(ws.grads_c.numel()),
+                           pack=pack)
+
+    def _enqueue_adam(self, ws, e, actor, critic, np_a, np_c, pack=None):
+        """the optimiser step of epoch e: clip-norm + Adam of the actor group (which honours the KL early exit), of the
+        critic group, or of both in one launch; np_a / np_c: how many sum-of-squares partials each group's norm has;
+        pack (pair form): the step also refreshes the fused epoch kernels' packed weights"""
+        K, m = self.K, self.model
+        a = (m.actor_flat, ws.grads_a, self.actor_exp_avg, self.actor_exp_avg_sq, ws.sumsq_a, np_a)
+        c = (m.critic_flat, ws.grads_c, self.critic_exp_avg, self.critic_exp_avg_sq, ws.sumsq_c, np_c)
+        if actor and critic:
+            K.clip_adam_pair(a + (True, ws.gnorm_a[e]), c + (False, ws.gnorm_c[e]), ws.ctrl_f, pack=pack)
+        elif actor:
+            K.clip_adam(*a, ws.ctrl_f, 0, True, ws.gnorm_a[e])
+        elif critic:
+            K.clip_adam(*c, ws.ctrl_f, 1, False, ws.gnorm_c[e])
 
     def _enqueue_reward_filter(self, ws, rewards):
         """rewards * reward_scale, then RewardFilter.forward and .update (ppo.py:452-455,
@@ -1052,22 +955,7 @@ class PPOLearner(Learner):
                              v_partials=ws.vpart, n_epochs=self.epoch_baseline, nblk=ws.vpart.shape[1],
                              v_stats=ws.vstats, stats_stride=L.VS_STRIDE)
             return
-        K.moments(ws.ret, ws.ret_mom)           # _avg_return_targ (ppo.py:571)
-        if self.world_size > 1:
-            self._dist.all_gather_into_tensor(ws.mom_parts.view(-1), ws.ret_mom.clone())
-            K.moments_merge(ws.mom_parts, ws.ret_mom)
-        if self.use_z_filter:                   # model.z_update(obs_iter)  (ppo.py:578-579)
-            if self.world_size > 1:
-                ws.zdelta.zero_()
-                K.zfilter_update(obs0, ws.zdelta[:D], ws.zdelta[D:2 * D], ws.zdelta[2 * D:], B)
-                self._dist.all_reduce(ws.zdelta)
-                m.z_filter.running_sum += ws.zdelta[:D]
-                m.z_filter.running_sumsq += ws.zdelta[D:2 * D]
-                m.z_filter.count += ws.zdelta[2 * D:]
-            else:
-                K.zfilter_update(obs0, m.z_filter.running_sum, m.z_filter.running_sumsq,
-                                 m.z_filter.count, B)
-        self._enqueue_final_stats(ws)
+        self._enqueue_learn_stats(ws, obs0, B, None)
 
     # ======================================================================================
     # Policies with a shared stem: the LSTM stem (algo.rnn.if_rnn_policy, the reference
@@ -1118,12 +1006,7 @@ class PPOLearner(Learner):
         H = self.horizon if rnn else N
         K.gae(ws.vals, rewards, dones, ws.gpow, ws.lpow, self.gamma, self.gamma ** H, B, N, H,
               ws.adv, ws.ret)
-        if self.norm_adv:
-            K.moments(ws.adv, ws.adv_mom)
-            if self.world_size > 1:
-                self._dist.all_gather_into_tensor(ws.mom_parts.view(-1), ws.adv_mom.clone())
-                K.moments_merge(ws.mom_parts, ws.adv_mom)
-            K.adv_normalize(ws.adv, ws.adv_mom, 1e-4)
+        self._enqueue_adv_normalize(ws)
 
     def _lstm_forward_only(self, ws, mm, xin, B, T, gates, cs, lo_a, lo_b):
         """the LSTM stack without anything kept for a backward pass (critic pass, reference policy):
@@ -1152,12 +1035,10 @@ class PPOLearner(Learner):
         return x
 
     def _stem_policy_forward(self, ws, e):
-        K, m = self.K, self.model
-        A, W = self.action_dim, self.world_size
-        mode = L.SMX_PPO_CLIP if self.ppo_mode == 'clip' else L.SMX_PPO_ADAPT
+        K, m, W = self.K, self.model, self.world_size
         x = self._stem_forward(ws, m, ws.xn, ws.stop)
         K.mlp3_forward(m.actor, x, ws.h1a, ws.h2a, ws.mean, L.SMX_ACT_TANH, ws.stop, pack=ws.pack_stem)
-        K.policy_loss(mode, ws.mean, m.log_var.view(-1), ws.act_it, ws.beh_it, ws.ref_pol, ws.adv,
+        K.policy_loss(self._mode, ws.mean, m.log_var.view(-1), ws.act_it, ws.beh_it, ws.ref_pol, ws.adv,
                       ws.ctrl_f, ws.g_surr, ws.g_kl, ws.ppart)
         part, nblk = ws.ppart, ws.nblk_p
         if W > 1 and ws.stem_one_exchange and e < self.epoch_policy:
@@ -1174,10 +1055,9 @@ class PPOLearner(Learner):
             # thousands of partial rows (B * E ~ 10^5): folded to 64 first -- every workgroup of the finalize walks them all
             K.partials_fold(ws.ppart, nblk, ws.ppart_fold, ws.ctrl_f)
             part, nblk = ws.ppart_fold, ws.ppart_fold.shape[0]
-        K.policy_finalize(mode, part, nblk, ws.g_surr, ws.g_kl, m.log_var.view(-1), ws.n_total,
+        K.policy_finalize(self._mode, part, nblk, ws.g_surr, ws.g_kl, m.log_var.view(-1), ws.n_total,
                           ws.ctrl_f, e > 0, e < self.epoch_policy, ws.dz3a,
-                          ws.grads_a[m.actor.numel:m.actor.numel + A],
-                          ws.sumsq_a[ws.np_a:ws.np_a + 1], ws.pstats[e])
+                          ws.dlogvar, ws.dlogvar_sumsq, ws.pstats[e])
 
     def _stem_backward(self, ws, net, h1, h2, dz3, dz2, dz1, g_mlp, g_cnn, g_rnn, stop):
         """MLP backward, then back through the stems it sits on"""
@@ -1224,13 +1104,10 @@ class PPOLearner(Learner):
             # [gradient | loss sums] in one all-reduce; then the finalize on the GLOBAL sums: statistics, log_var's gradient
             # (into its slot of the gradient, which the exchange left holding garbage: zero it first -- every rank the same),
             # the early-exit flag and the step counter, once, in front of the optimiser launch
-            A = self.action_dim
-            mode = L.SMX_PPO_CLIP
             ws.grads_a[n_mlp:n0].zero_()
             self._dist.all_reduce(ws.ar_pol)
-            K.policy_finalize(mode, ws.ppart_sum, 1, ws.g_surr, ws.g_kl, m.log_var.view(-1), ws.n_total,
-                              ws.ctrl_f, e > 0, True, ws.dz3a, ws.grads_a[n_mlp:n_mlp + A],
-                              ws.sumsq_a[ws.np_a:ws.np_a + 1], ws.pstats[e])
+            K.policy_finalize(self._mode, ws.ppart_sum, 1, ws.g_surr, ws.g_kl, m.log_var.view(-1), ws.n_total,
+                              ws.ctrl_f, e > 0, True, ws.dz3a, ws.dlogvar, ws.dlogvar_sumsq, ws.pstats[e])
         elif self.world_size > 1:
             # ONE all-reduce for the MLP and the stem.  log_var's gradient (between them) was built from
             # all-reduced loss sums and is global already: exactly one copy may enter the sum
@@ -1238,9 +1115,7 @@ class PPOLearner(Learner):
                 ws.grads_a[n_mlp:n0].zero_()
             self._dist.all_reduce(ws.grads_a)
         K.sumsq_partials(ws.grads_a, ws.sumsq_a)
-        K.clip_adam(m.actor_flat, ws.grads_a, self.actor_exp_avg, self.actor_exp_avg_sq,
-                    ws.sumsq_a, K.sumsq_blocks(ws.grads_a.numel()), ws.ctrl_f, 0, True,
-                    ws.pstats[e, L.PS_GRADNORM:L.PS_GRADNORM + 1])
+        self._enqueue_adam(ws, e, True, False, K.sumsq_blocks(ws.grads_a.numel()), None)
 
     def _stem_value_epoch(self, ws, e):
         K, m = self.K, self.model
@@ -1256,9 +1131,7 @@ class PPOLearner(Learner):
         if self.world_size > 1:
             self._dist.all_reduce(ws.grads_c)
         K.sumsq_partials(ws.grads_c, ws.sumsq_c)
-        K.clip_adam(m.critic_flat, ws.grads_c, self.critic_exp_avg, self.critic_exp_avg_sq,
-                    ws.sumsq_c, K.sumsq_blocks(ws.grads_c.numel()), ws.ctrl_f, 1, False,
-                    ws.vstats[e, L.VS_GRADNORM:L.VS_GRADNORM + 1])
+        self._enqueue_adam(ws, e, False, True, None, K.sumsq_blocks(ws.grads_c.numel()))
 
     def _enqueue_optimize_stem(self, ws, obs, obs_next, actions, rewards, dones, pds, pix, pix_next,
                                pre_zeroed=False):
@@ -1297,27 +1170,29 @@ class PPOLearner(Learner):
             self._stem_policy_forward(ws, e + 1)
         for e in range(self.epoch_baseline):
             self._stem_value_epoch(ws, e)
-        if self.world_size > 1:
-            Ev, W = self.epoch_baseline, self.world_size
-            self._dist.all_gather_into_tensor(ws.vgather.view(-1), ws.vpart_loc_all.view(-1))
-            ws.vpart.view(Ev, W, ws.nblk_v, 8).copy_(ws.vgather.permute(1, 0, 2, 3))
-        K.value_finalize(ws.vpart, self.epoch_baseline, ws.vpart.shape[1], ws.vstats, L.VS_STRIDE)
+        self._enqueue_value_finalize(ws)
+        self._enqueue_learn_stats(ws, ws.low_it, B * E, ws.zscratch)
 
-        K.moments(ws.ret, ws.ret_mom)           # _avg_return_targ (ppo.py:571)
-        if self.world_size > 1:
-            self._dist.all_gather_into_tensor(ws.mom_parts.view(-1), ws.ret_mom.clone())
-            K.moments_merge(ws.mom_parts, ws.ret_mom)
-        if self.use_z_filter:                   # model.z_update(obs_iter)  (ppo.py:578-579)
-            if self.world_size > 1:
-                ws.zdelta.zero_()
-                K.zfilter_update(ws.low_it, ws.zdelta[:D], ws.zdelta[D:2 * D], ws.zdelta[2 * D:], B * E, ws=ws.zscratch)
-                self._dist.all_reduce(ws.zdelta)
-                m.z_filter.running_sum += ws.zdelta[:D]
-                m.z_filter.running_sumsq += ws.zdelta[D:2 * D]
-                m.z_filter.count += ws.zdelta[2 * D:]
-            else:
-                K.zfilter_update(ws.low_it, m.z_filter.running_sum, m.z_filter.running_sumsq,
-                                 m.z_filter.count, B * E, ws=ws.zscratch)
+    def _z_add(self, sums):
+        """[column sums | column sums of squares | count] of the global batch into the model's z-filter"""
+        zf, D = self.model.z_filter, (sums.numel() - 1) // 2
+        zf.running_sum += sums[:D]
+        zf.running_sumsq += sums[D:2 * D]
+        zf.count += sums[2 * D:]
+
+    def _enqueue_learn_stats(self, ws, x, n_rows, scratch):
+        """the end of a learn: _avg_return_targ (ppo.py:571), model.z_update(obs_iter) over the n_rows raw rows x
+        (ppo.py:578-579; several ranks: the column sums of the GLOBAL batch, all-reduced), and the reported means"""
+        K, D = self.K, ws.key[2]
+        self._enqueue_moments(ws, ws.ret, ws.ret_mom)
+        if self.use_z_filter and self.world_size > 1:
+            ws.zdelta.zero_()
+            K.zfilter_update(x, ws.zdelta[:D], ws.zdelta[D:2 * D], ws.zdelta[2 * D:], n_rows, ws=scratch)
+            self._dist.all_reduce(ws.zdelta)
+            self._z_add(ws.zdelta)
+        elif self.use_z_filter:
+            zf = self.model.z_filter        # it exists only with use_z_filter
+            K.zfilter_update(x, zf.running_sum, zf.running_sumsq, zf.count, n_rows, ws=scratch)
         self._enqueue_final_stats(ws)
 
     def _enqueue_final_stats(self, ws):
@@ -1350,71 +1225,77 @@ class PPOLearner(Learner):
                 ws.h0L.zero_(); ws.c0L.zero_()
             ws.h0L[:, :, :Fl].copy_(onetime_infos[0].reshape(B, nl, Fl).transpose(0, 1))
             ws.c0L[:, :, :Fl].copy_(onetime_infos[1].reshape(B, nl, Fl).transpose(0, 1))
-        if self.use_graph:
-            # A captured graph is bound to the addresses of its inputs.  The first batch is captured
-            # in place (a pointer-stable feed -- device-resident replay, the benchmark -- never pays
-            # a copy).  As soon as a batch arrives somewhere else the learner switches, once, to
-            # staging buffers of its own: every later batch is copied in (one pass over the batch,
-            # ~0.1 ms at 226 MB) and the graph captured on the staging buffers is replayed --
-            # instead of re-capturing ~130 launches for every new address.
-            key = tuple(t.data_ptr() for t in args)
-            g = self._graphs.get(key)
-            if g is None and len(self._graphs) >= getattr(self, 'graph_input_sets', 1):
-                if getattr(ws, 'staged', None) is None:
-                    ws.staged = tuple(torch.empty_like(t) for t in args)
-                for dst, src in zip(ws.staged, args):
-                    dst.copy_(src)
-                args = ws.staged
-                key = tuple(t.data_ptr() for t in args)
-                g = self._graphs.get(key)
-            if g is None:
-                # warm-up run outside capture (lazy module loads, hipFuncSetAttribute), on a
-                # snapshot of the mutable state so that the captured replay is the first real step
-                snap = self._snapshot_state()
-                self._enqueue_optimize(ws, *args)
-                torch.cuda.synchronize()
-                self._restore_state(snap)
-                g = torch.cuda.CUDAGraph() if self.world_size == 1 else _SegmentedGraph()
-                # no cyclic garbage collection while the stream is capturing: a collection that
-                # frees some earlier learner's graph or device tensors calls hipFree / graph
-                # destructors in the middle of the capture, which aborts the process
-                gc_was_enabled = gc.isenabled()
-                gc.collect()
-                gc.disable()
-                c_cap = self._dist.count if self._dist is not None else 0
-                try:
-                    if self.world_size == 1:
-                        with torch.cuda.graph(g):
-                            self._enqueue_optimize(ws, *args)
-                    else:
-                        try:
-                            g.capture(lambda: self._enqueue_optimize(ws, *args), self._dist)
-                        except Exception as e:      # e.g. a runtime that refuses to capture next to RCCL
-                            self.log.warning('graph segments unavailable (%r): eager launches from here on', e)
-                            g = None
-                            self.use_graph = False
-                finally:
-                    if gc_was_enabled:
-                        gc.enable()
-                self._restore_state(snap)
-                if g is None:
-                    self._enqueue_optimize(ws, *args)
-                    return self._collect_stats(ws)
-                # exchanges that run as kernels INSIDE the graph (PeerExchange) were counted while they were captured,
-                # not executed: a replay re-runs them, so it re-counts them (the process group's calls count themselves)
-                if self._dist is not None:
-                    g.in_graph_collectives = self._dist.count - c_cap
-                    self._dist.count = c_cap
-                if getattr(ws, 'staged', None) is not None and args is ws.staged:
-                    self._graphs = {key: g}          # staging mode: the in-place graph is retired
-                else:
-                    self._graphs[key] = g
+        g, args = self._graph_for(ws, args) if self.use_graph else (None, args)
+        if g is not None:
             g.replay()
             if self._dist is not None:
                 self._dist.count += getattr(g, 'in_graph_collectives', 0)
         else:
             self._enqueue_optimize(ws, *args)
         return self._collect_stats(ws)
+
+    def _graph_for(self, ws, args):
+        """-> (the captured step, the input tensors it is bound to); the step is None where capture is not to be had
+        (the launches then run eagerly, from here on)"""
+        # A captured graph is bound to the addresses of its inputs.  The first batch is captured
+        # in place (a pointer-stable feed -- device-resident replay, the benchmark -- never pays
+        # a copy).  As soon as a batch arrives somewhere else the learner switches, once, to
+        # staging buffers of its own: every later batch is copied in (one pass over the batch,
+        # ~0.1 ms at 226 MB) and the graph captured on the staging buffers is replayed --
+        # instead of re-capturing ~130 launches for every new address.
+        key = tuple(t.data_ptr() for t in args)
+        g = self._graphs.get(key)
+        if g is None and len(self._graphs) >= getattr(self, 'graph_input_sets', 1):
+            if getattr(ws, 'staged', None) is None:
+                ws.staged = tuple(torch.empty_like(t) for t in args)
+            for dst, src in zip(ws.staged, args):
+                dst.copy_(src)
+            args = ws.staged
+            key = tuple(t.data_ptr() for t in args)
+            g = self._graphs.get(key)
+        if g is not None:
+            return g, args
+        # warm-up run outside capture (lazy module loads, hipFuncSetAttribute), on a
+        # snapshot of the mutable state so that the captured replay is the first real step
+        snap = self._snapshot_state()
+        self._enqueue_optimize(ws, *args)
+        torch.cuda.synchronize()
+        self._restore_state(snap)
+        g = torch.cuda.CUDAGraph() if self.world_size == 1 else _SegmentedGraph()
+        # no cyclic garbage collection while the stream is capturing: a collection that
+        # frees some earlier learner's graph or device tensors calls hipFree / graph
+        # destructors in the middle of the capture, which aborts the process
+        gc_was_enabled = gc.isenabled()
+        gc.collect()
+        gc.disable()
+        c_cap = self._dist.count if self._dist is not None else 0
+        try:
+            if self.world_size == 1:
+                with torch.cuda.graph(g):
+                    self._enqueue_optimize(ws, *args)
+            else:
+                try:
+                    g.capture(lambda: self._enqueue_optimize(ws, *args), self._dist)
+                except Exception as e:      # e.g. a runtime that refuses to capture next to RCCL
+                    self.log.warning('graph segments unavailable (%r): eager launches from here on', e)
+                    g = None
+                    self.use_graph = False
+        finally:
+            if gc_was_enabled:
+                gc.enable()
+        self._restore_state(snap)
+        if g is None:
+            return None, args
+        # exchanges that run as kernels INSIDE the graph (PeerExchange) were counted while they were captured,
+        # not executed: a replay re-runs them, so it re-counts them (the process group's calls count themselves)
+        if self._dist is not None:
+            g.in_graph_collectives = self._dist.count - c_cap
+            self._dist.count = c_cap
+        if getattr(ws, 'staged', None) is not None and args is ws.staged:
+            self._graphs = {key: g}          # staging mode: the in-place graph is retired
+        else:
+            self._graphs[key] = g
+        return g, args
 
     def _snapshot_state(self):
         m = self.model
@@ -1464,10 +1345,9 @@ class PPOLearner(Learner):
         when first looked at -- at the latest right after the NEXT learn() has been enqueued -- so
         the GPU never waits for the read-back and the Python that decodes it."""
         snap = {'beta': getattr(self, 'beta', None), 'clip_epsilon': getattr(self, 'clip_epsilon', None),
-                'lr': self.actor_lr_scheduler.get_lr()[0],       # (each mode defines only its own)
-                'n_sync': ws.n_sync}
+                'lr': self.actor_lr_scheduler.get_lr()[0]}       # (each mode defines only its own)
         if not self.lazy_stats:
-            return self._decode_stats(ws.scal.cpu(), snap)
+            return self._decode_stats(ws.scal.cpu(), snap, ws.layout)
         self._flush_stats()                        # the previous learn's, now that this one is queued
         if getattr(ws, 'scal_host', None) is None:
             ws.scal_host = torch.empty(ws.scal.shape, dtype=ws.scal.dtype, pin_memory=True)
@@ -1475,29 +1355,27 @@ class PPOLearner(Learner):
         ev = torch.cuda.Event()
         ev.record()
         handle = DeferredStats(self._flush_stats)
-        self._pending_stats = (ev, ws.scal_host, snap, handle)
+        self._pending_stats = (ev, ws.scal_host, snap, ws.layout, handle)
         return handle
 
     def _flush_stats(self):
         """wait for the read-back in flight (if any) and decode it"""
         pend, self._pending_stats = self._pending_stats, None
         if pend is not None:
-            ev, host, snap, handle = pend
+            ev, host, snap, lay, handle = pend
             ev.synchronize()
-            handle._value = self._decode_stats(host, snap)
+            handle._value = self._decode_stats(host, snap, lay)
 
-    def _decode_stats(self, scal, snap):
-        """host copy of the statistics block -> the reference's stats dict
-        (ppo.py:219-224, 278-284, 328-331, 559-586)"""
-        ctrl_i = scal[:L.CTRL_WORDS].view(torch.int32)
-        o = L.CTRL_WORDS
+    def _decode_stats(self, scal, snap, lay):
+        """host copy of the statistics block (laid out as `lay`, the _stats_layout of the workspace it came from) -> the
+        reference's stats dict (ppo.py:219-224, 278-284, 328-331, 559-586)"""
+        ctrl_i = scal[lay.ctrl].view(torch.int32)
         Ep, Ev = self.epoch_policy, self.epoch_baseline
-        ps = scal[o:o + (Ep + 1) * L.PS_STRIDE].view(Ep + 1, L.PS_STRIDE).numpy(); o += (Ep + 1) * L.PS_STRIDE
-        o += snap['n_sync']
-        vs = scal[o:o + Ev * L.VS_STRIDE].view(Ev, L.VS_STRIDE).numpy(); o += Ev * L.VS_STRIDE
-        ret_mom = scal[o + 3:o + 6].numpy()
-        fin = scal[o + 8:o + 12].numpy()
-        rf = scal[o + 12:o + 15].numpy()
+        ps = scal[lay.pstats].view(Ep + 1, L.PS_STRIDE).numpy()
+        vs = scal[lay.vstats].view(Ev, L.VS_STRIDE).numpy()
+        ret_mom = scal[lay.ret_mom].numpy()
+        fin = scal[lay.fin].numpy()
+        rf = scal[lay.rf_state].numpy()
         if int(ctrl_i[L.C_SYNC_ERR]) != 0:
             # the device is shared after all: from the next learn() on, the two-launch form (no in-launch wait).  The
             # parameters hold the state after the last COMPLETE epoch of the failed learn (every later Adam step of it
