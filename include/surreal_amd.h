@@ -758,6 +758,34 @@ struct smx_episode_monitor {               /* (by tag: no typedef) */
     int32_t capacity, reserved;
 };
 
+/* The exploration noise of the device actors as a counter-based stream: the standard normal of (seed, global actor id
+ * g, draw step s, action component j) is a pure function of the four, formed inside the launch that consumes it
+ * (csrc/smx_philox.inc.h has the expressions):
+ *   x[0..3] = Philox4x32-10(counter = (g, low32(s), high32(s), j >> 2), key = (low32(seed), high32(seed)))
+ *   the pair p = (j & 3) >> 1 of words: u0 = ((x[2p] >> 8) + 0.5) 2^-24, u1 = ((x[2p + 1] >> 8) + 0.5) 2^-24 (never 0 or 1)
+ *   r = sqrtf(-2 logf(u0)), angle = 2 pi u1 (sincospif(2 u1)); normal = r cos(angle) for even j, r sin(angle) for odd j
+ * so one Philox block gives components 4q .. 4q + 3 by two Box-Muller pairs; |normal| <= sqrt(-2 ln 2^-25) ~ 5.887.
+ * THE RULE of every launch that takes `eps` and a stream `noise`:
+ *   eps != NULL:                   eps is used exactly as without a stream;
+ *   eps == NULL, noise.enabled:    the draw of local actor a, the call's k-th step (0 in a one-step launch) and
+ *                                  component j is normal(seed, actor_base + a, step + k, j);
+ *   eps == NULL, !noise.enabled:   the launch is deterministic (the zero struct: what it did before there were streams);
+ *   smx_ddpg_rollout.noise_type == SMX_DDPG_NOISE_NONE reads neither.
+ * An actor's draws depend on its global id and the draw step only: not on n, on the steps of a call, on how a run is cut
+ * into calls or on how the actors are split over launches (actor_base: the global id of the launch's actor 0).  With
+ * enabled set, actor_base < 0 or actor_base + n > 2^32: SMX_E_SHAPE.  The four argument blocks that carry a stream hold it
+ * by value right in front of `mon`, which stays their last member. */
+struct smx_noise_stream {                  /* (by tag: no typedef) */
+    uint64_t seed;
+    int64_t actor_base;                    /* global id of local actor 0 */
+    int64_t step;                          /* draw step of the call's first step */
+    int32_t enabled, reserved;
+};
+/* out [steps, n, A] <- the draws a launch on `noise` over n actors forms for its `steps` steps (the same inline function;
+ * noise->enabled is not read).  For the paths that sample outside these launches, and for tests. */
+int smx_noise_fill_f32(const struct smx_noise_stream* noise, int32_t steps, int32_t n, int32_t A, float* out,
+                       smx_stream_t stream);
+
 /* mon: NULL, or the episode monitor above */
 int smx_synth_env_step_f32(float* state, const float* init_state, const float* actions,
                            int32_t n, int32_t D, int32_t A, int32_t t, int32_t episode_len,
@@ -769,7 +797,7 @@ int smx_synth_env_step_f32(float* state, const float* init_state, const float* a
  * (smx_diaggauss_sample_f32 on `mean`), the environment step above with the sampled action, and the
  * z-filter of the NEXT observation (smx_zfilter_forward_sums_f32) into xn_out -- what the next
  * policy forward reads.  pd_roll [n, T, 2A] receives the action_infos distribution; eps == NULL:
- * deterministic; zsum == NULL: xn_out = the raw next observation; rolls may be NULL. */
+ * deterministic, or the draws of `noise` (the rule at struct smx_noise_stream); zsum == NULL: xn_out = the raw next observation; rolls may be NULL. */
 typedef struct smx_synth_act_step {
     float* state;
     const float* init_state;
@@ -789,7 +817,8 @@ typedef struct smx_synth_act_step {
     const float* zcount;
     float zeps, reserved_f;
     float* xn_out;
-    struct smx_episode_monitor mon;        /* mon.ep_reward NULL: none */
+    struct smx_noise_stream noise;         /* eps NULL and noise.enabled: the draws are formed in the launch */
+    struct smx_episode_monitor mon;        /* mon.ep_reward NULL: none (stays the last member) */
 } smx_synth_act_step_t;
 int smx_synth_act_env_step_f32(const smx_synth_act_step_t* args, smx_stream_t stream);
 /* The same launch with the policy's output layer folded in (PPOAgent.act's last Linear + Tanh, surreal/model/
@@ -1035,7 +1064,7 @@ int smx_flatten_order_f32(const float* in, int32_t O, int32_t C, int32_t P,
  * (smx_epoch_pack_f32 of `net`): the means equal smx_epoch_forward_f32's to fp32 rounding of the layer sums (another
  * summation order), 4- and 8-actor blocks bit for bit each other's; sampling, dynamics, recording and the z-filter use the
  * expressions of smx_synth_act_env_step_f32.
- * eps [steps, n, A] standard normals (NULL: deterministic); zsum/zsumsq/zcount: the z-filter's running sums (NULL:
+ * eps [steps, n, A] standard normals (NULL: deterministic, or the draws of `noise`); zsum/zsumsq/zcount: the z-filter's running sums (NULL:
  * raw observations); rolls [n, rows_per_actor, .] (any may be NULL); state [n, D] is read at the start and left at
  * the state after the last step; t: the episode clock at the first step.
  * obs_last [n, D] (nullable): where the observation AFTER row rows_per_actor - 1 goes.  With rows_per_actor = steps + 1
@@ -1064,7 +1093,8 @@ typedef struct smx_synth_rollout {
     float* pd_roll;
     float* obs_last;
     int32_t actors_per_workgroup;          /* 4 | 8 | 16, 0: the smallest whose grid fits the CUs once */
-    struct smx_episode_monitor mon;        /* mon.ep_reward NULL: none */
+    struct smx_noise_stream noise;         /* eps NULL and noise.enabled: the draws are formed in the launch */
+    struct smx_episode_monitor mon;        /* mon.ep_reward NULL: none (stays the last member) */
 } smx_synth_rollout_t;
 int32_t smx_synth_rollout_supported(int32_t D, int32_t H1, int32_t H2, int32_t A);
 int smx_synth_rollout_f32(const smx_synth_rollout_t* args, smx_stream_t stream);
@@ -1172,7 +1202,8 @@ int smx_synth_ppo_window_rollout_f32(const struct smx_synth_ppo_window_rollout* 
  *     rewards / dones [capacity]; the caller makes n * (closing steps) <= capacity (checked: SMX_E_SHAPE).
  * carry_obs [n, n_step, D], carry_act [n, n_step, A], carry_rew [n, n_step]: the open transitions (slot tau % n_step),
  * ou [n, A] (fp64): the OU processes -- both carry over between calls.  eps [steps, n, A] standard normals, sigmas [n]
- * (fp64); neither is read with noise_type SMX_DDPG_NOISE_NONE (the deterministic agent modes). */
+ * (fp64); neither is read with noise_type SMX_DDPG_NOISE_NONE (the deterministic agent modes).  eps NULL with another
+ * noise_type: the draws of `noise`, which must then be enabled (SMX_E_NULL). */
 #define SMX_DDPG_NOISE_NONE 0
 #define SMX_DDPG_NOISE_GAUSSIAN 1
 #define SMX_DDPG_NOISE_OU 2
@@ -1199,7 +1230,8 @@ struct smx_ddpg_rollout {
     float* rewards;
     float* dones;
     int64_t cursor, capacity;
-    struct smx_episode_monitor mon;        /* mon.ep_reward NULL: none */
+    struct smx_noise_stream noise;         /* eps NULL and noise.enabled: the draws are formed in the launch */
+    struct smx_episode_monitor mon;        /* mon.ep_reward NULL: none (stays the last member) */
 };
 typedef struct smx_ddpg_rollout smx_ddpg_rollout_t;
 /* shapes smx_synth_ddpg_rollout_f32 takes: A <= 32, H1 and H2 multiples of 4 up to 640, D <= 512 */
@@ -1271,7 +1303,7 @@ struct smx_synth_ppo_pixel_window_step {   /* (by tag: no typedef) */
     int32_t t, episode_len, n_step, advance;
     const float* log_var;                  /* [A] */
     const float* noise_scale;              /* [n] or NULL */
-    const float* eps;                      /* [n, A] standard normals, or NULL (the deterministic agent modes) */
+    const float* eps;                      /* [n, A] standard normals, or NULL (deterministic, or the draws of `noise`) */
     float* state;                          /* [n, D] in / out */
     const float* init_state;
     const float* h_before;                 /* [n, hidden] the LSTM state the step started from, or NULL */
@@ -1296,7 +1328,8 @@ struct smx_synth_ppo_pixel_window_step {   /* (by tag: no typedef) */
     uint8_t* pixel;                        /* [capacity, N, S*F] */
     uint8_t* pixel_next;                   /* [capacity, S*F] */
     uint8_t* obs_pixel;                    /* [n, S*F] */
-    struct smx_episode_monitor mon;        /* mon.ep_reward NULL: none */
+    struct smx_noise_stream noise;         /* eps NULL and noise.enabled: the draws are formed in the launch */
+    struct smx_episode_monitor mon;        /* mon.ep_reward NULL: none (stays the last member) */
 };
 int smx_synth_ppo_pixel_window_step(const struct smx_synth_ppo_pixel_window_step* args, const float* mu, int64_t ld_mu,
                                     smx_stream_t stream);

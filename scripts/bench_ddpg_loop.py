@@ -48,6 +48,9 @@ def main():
     ap.add_argument('--monitor', action='store_true',
                     help='attach the on-device episode monitor: every line also carries mean_episode_return, the mean of '
                          'the last 10 polled episode returns per actor (null before an episode has finished)')
+    ap.add_argument('--device-noise', action='store_true',
+                    help='draw the exploration noise inside the launches from the env\'s Philox stream (attach_noise): no '
+                         'eps tensor is made or read')
     args = ap.parse_args()
     n, T, D, A = args.actors, args.steps, args.obs_dim, args.action_dim
     H1, H2 = args.hidden
@@ -67,7 +70,9 @@ def main():
             mon.poll()
             line.update(mean_episode_return=mon.mean_reward(last=10), episodes=mon.num_episodes, monitor=True)
         return line
-    eps = torch.randn(T, n, A, device='cuda')
+    if args.device_noise:
+        venv.attach_noise(seed=1)
+    eps = None if args.device_noise else torch.randn(T, n, A, device='cuda')
     results = {}
     for path in ('persistent', 'per_step'):
         replay = UniformReplay(lc, ec, sc)
@@ -101,7 +106,7 @@ def main():
     replay = UniformReplay(lc, ec, sc)
     venv.reset()
     B, Tc = args.batch, args.chunk_steps
-    ceps = torch.randn(Tc, n, A, device='cuda')
+    ceps = None if args.device_noise else torch.randn(Tc, n, A, device='cuda')
     venv.ddpg_rollout_into(agent, replay, Tc, eps=ceps)
     stage = learner.staging_fields(B)
 

@@ -1,7 +1,7 @@
 """LSTM-stem PPO rollouts (GPU box): the per-step stem path (_rollout_stem: act_batch + step launch per step) against
 the one-launch kernel (smx_synth_lstm_rollout_f32), timed alternately in one process with device events after warm-up.
 One JSON line per shape: median / min / max ms per rollout of each path over the repetitions.
-    python scripts/bench_lstm_rollout.py [--reps 7] [--out FILE]"""
+    python scripts/bench_lstm_rollout.py [--reps 7] [--out FILE] [--device-noise]"""
 import argparse
 import json
 import os
@@ -27,12 +27,17 @@ def main():
     ap.add_argument('--reps', type=int, default=7)
     ap.add_argument('--warmup', type=int, default=2)
     ap.add_argument('--out', default=None)
+    ap.add_argument('--device-noise', action='store_true',
+                    help='draw the exploration noise inside the launches from the env\'s Philox stream (attach_noise): no '
+                         'eps tensor; the stem path gets the same numbers from the fill kernel')
     args = ap.parse_args()
     lines = []
     for n, T, D, A, hidden, H in SHAPES:
         agent, _ = LC.make_agent(D, A, hidden=hidden, rnn_hidden=H, T=T, n=n)
         venv = SyntheticVecEnv(n, D, A, episode_len=T)
-        eps = torch.randn(T, n, A, device='cuda')
+        eps = None if args.device_noise else torch.randn(T, n, A, device='cuda')
+        if args.device_noise:
+            venv.attach_noise(seed=1)
         times = {'stem': [], 'one_launch': []}
 
         def once(persistent):
@@ -52,7 +57,8 @@ def main():
                 e1.record()
                 torch.cuda.synchronize()
                 times[name].append(e0.elapsed_time(e1))
-        rec = {'n': n, 'T': T, 'D': D, 'A': A, 'hidden': list(hidden), 'rnn_hidden': H, 'reps': args.reps}
+        rec = {'n': n, 'T': T, 'D': D, 'A': A, 'hidden': list(hidden), 'rnn_hidden': H, 'reps': args.reps,
+               'device_noise': bool(args.device_noise)}
         for name, v in times.items():
             v = sorted(v)
             rec[name + '_ms'] = {'median': v[len(v) // 2], 'min': v[0], 'max': v[-1]}

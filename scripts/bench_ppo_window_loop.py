@@ -40,7 +40,7 @@ def _timed(fn):
     return a.elapsed_time(b)
 
 
-def bench_rollouts(reps, warmup, shapes, monitor=False):
+def bench_rollouts(reps, warmup, shapes, monitor=False, device_noise=False):
     lines = []
     for n, T, D, A, hidden, H, (N, stride), L in shapes:
         agent, cfg = PW.make_agent(D, A, N, stride, hidden=hidden, rnn_hidden=H, memory_size=n * (T // min(N, stride)
@@ -50,7 +50,10 @@ def bench_rollouts(reps, warmup, shapes, monitor=False):
         tab = SyntheticVecEnv(n, D, A, episode_len=L)
         mon = win.attach_monitor() if monitor else None
         tab.start_rollout(T, info_width=2 * A)
-        eps = torch.randn(T, n, A, device='cuda')
+        eps = None if device_noise else torch.randn(T, n, A, device='cuda')
+        if device_noise:
+            win.attach_noise(seed=1)
+            tab.attach_noise(seed=1)
         times = {'window': [], 'rollout': []}
         rows = []
 
@@ -72,7 +75,7 @@ def bench_rollouts(reps, warmup, shapes, monitor=False):
                 replay.sample_batch(min(len(replay), replay.memory_size), copy=False)
         w, t = _stats(times['window']), _stats(times['rollout'])
         lines.append({'case': 'rollout', 'n': n, 'T': T, 'D': D, 'A': A, 'hidden': list(hidden), 'rnn_hidden': H,
-                      'n_step': N, 'stride': stride, 'episode_len': L, 'reps': reps,
+                      'n_step': N, 'stride': stride, 'episode_len': L, 'reps': reps, 'device_noise': device_noise,
                       'windows_per_call': sorted(set(rows)), 'ppo_rollout_into_ms': w, 'rollout_ms': t,
                       'ratio_median': w['median'] / t['median']})
         if mon is not None:
@@ -82,7 +85,7 @@ def bench_rollouts(reps, warmup, shapes, monitor=False):
     return lines
 
 
-def bench_loop(reps, warmup, n=64, T=128, L=1000, D=17, A=6, monitor=False):
+def bench_loop(reps, warmup, n=64, T=128, L=1000, D=17, A=6, monitor=False, device_noise=False):
     """configs[1]'s shape with the reference-default algo config: env-steps/s of chunk -> FIFO -> learn"""
     from surreal_amd.learner import PPOLearner
     agent, cfg = PW.make_agent(D, A, 25, 20, hidden=(300, 200), rnn_hidden=100, memory_size=8 * n, batch_size=64)
@@ -93,6 +96,8 @@ def bench_loop(reps, warmup, n=64, T=128, L=1000, D=17, A=6, monitor=False):
     replay = FIFOReplay(lc, ec, sc)
     venv = SyntheticVecEnv(n, D, A, episode_len=L)
     mon = venv.attach_monitor() if monitor else None
+    if device_noise:
+        venv.attach_noise(seed=1)
     learned = [0]
 
     def chunk():
@@ -109,7 +114,7 @@ def bench_loop(reps, warmup, n=64, T=128, L=1000, D=17, A=6, monitor=False):
             times.append(ms)
     s = _stats(times)
     line = {'case': 'loop', 'n': n, 'T': T, 'episode_len': L, 'D': D, 'A': A, 'n_step': 25, 'stride': 20,
-            'rnn_hidden': 100, 'horizon': lc.algo.rnn.horizon, 'reps': reps, 'chunk_ms': s,
+            'rnn_hidden': 100, 'horizon': lc.algo.rnn.horizon, 'reps': reps, 'device_noise': device_noise, 'chunk_ms': s,
             'env_steps_per_s': {'at_median': n * T / (s['median'] * 1e-3), 'at_min_ms': n * T / (s['min'] * 1e-3),
                                 'at_max_ms': n * T / (s['max'] * 1e-3)}, 'windows_learned': learned[0]}
     if mon is not None:
@@ -128,9 +133,13 @@ def main():
     ap.add_argument('--monitor', action='store_true',
                     help='attach the on-device episode monitor: every line also carries mean_episode_return, the mean of '
                          'the last 10 polled episode returns per actor (null before an episode has finished)')
+    ap.add_argument('--device-noise', action='store_true',
+                    help='draw the exploration noise inside the launches from the env\'s Philox stream (attach_noise): no '
+                         'eps tensor is made or read')
     args = ap.parse_args()
     reps, warmup = (1, 1) if args.quick else (args.reps, args.warmup)
-    lines = bench_rollouts(reps, warmup, ROLLOUTS, args.monitor) + bench_loop(reps, warmup, monitor=args.monitor)
+    lines = bench_rollouts(reps, warmup, ROLLOUTS, args.monitor, args.device_noise) + \
+        bench_loop(reps, warmup, monitor=args.monitor, device_noise=args.device_noise)
     if args.out:
         with open(args.out, 'w') as f:
             for ln in lines:

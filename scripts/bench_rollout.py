@@ -1,7 +1,8 @@
 """micro-benchmark of the persistent rollout kernel (GPU box): time per rollout at 1024 / 4096 actors and, with a
 timing build (-DSMX_ROLLOUT_TIMING, loaded through SMX_LIB_PATH), where one step of a workgroup goes and the shader
 clock the chip actually ran at (cycle counter against the 100 MHz wall clock).
-    python scripts/bench_rollout.py [actors ...]"""
+    python scripts/bench_rollout.py [--device-noise] [actors ...]
+--device-noise: the exploration noise drawn inside the launch from the env's Philox stream (attach_noise), no eps tensor."""
 import ctypes, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, 'tests'))
@@ -17,9 +18,12 @@ D, A, T = 376, 17, 128
 lc = ppo_learner_config(); lc.algo.rnn.if_rnn_policy = False
 agent = PPOAgent(lc, ppo_env_config(D, A), ppo_session_config('/tmp/surreal_amd_bench_rollout'), agent_id=0, agent_mode='training')
 timing = hasattr(K.lib, 'smx_rollout_debug_tbuf')
-for n in [int(a) for a in sys.argv[1:]] or [1024, 4096]:
+device_noise = '--device-noise' in sys.argv
+for n in [int(a) for a in sys.argv[1:] if a != '--device-noise'] or [1024, 4096]:
     venv = SyntheticVecEnv(n, D, A, episode_len=T)
-    eps = torch.randn(T, n, A, device='cuda')
+    eps = None if device_noise else torch.randn(T, n, A, device='cuda')
+    if device_noise:
+        venv.attach_noise(seed=1)
     tb = torch.zeros(((n + 3) // 4) * 16, dtype=torch.int64, device="cuda")     # (one row of 16 stamps per workgroup; 4 actors each at most)
     if timing:
         K.lib.smx_rollout_debug_tbuf.argtypes = [ctypes.c_void_p]

@@ -151,6 +151,12 @@ class EpisodeMonitor(Structure):
                 ('done_steps', c_void_p), ('capacity', c_int32), ('reserved', c_int32)]
 
 
+class NoiseStream(Structure):
+    """struct smx_noise_stream"""
+    _fields_ = [('seed', c_uint64), ('actor_base', c_int64), ('step', c_int64), ('enabled', c_int32),
+                ('reserved', c_int32)]
+
+
 class SynthRollout(Structure):
     """smx_synth_rollout_t"""
     _fields_ = [('net', POINTER(Mlp3)), ('packed', c_void_p), ('out_act', c_int32), ('n', c_int32),
@@ -159,7 +165,7 @@ class SynthRollout(Structure):
                 ('episode_len', c_int32), ('steps', c_int32), ('rows_per_actor', c_int32), ('slot', c_int32),
                 ('state', c_void_p), ('init_state', c_void_p), ('obs_roll', c_void_p), ('act_roll', c_void_p),
                 ('rew_roll', c_void_p), ('done_roll', c_void_p), ('pd_roll', c_void_p), ('obs_last', c_void_p),
-                ('actors_per_workgroup', c_int32), ('mon', EpisodeMonitor)]
+                ('actors_per_workgroup', c_int32), ('noise', NoiseStream), ('mon', EpisodeMonitor)]
 
 
 class SynthLstmRollout(Structure):
@@ -187,7 +193,7 @@ class DdpgRollout(Structure):
                 ('gpow', c_void_p), ('ou', c_void_p), ('state', c_void_p), ('init_state', c_void_p),
                 ('carry_obs', c_void_p), ('carry_act', c_void_p), ('carry_rew', c_void_p), ('obs', c_void_p),
                 ('obs_next', c_void_p), ('actions', c_void_p), ('rewards', c_void_p), ('dones', c_void_p),
-                ('cursor', c_int64), ('capacity', c_int64), ('mon', EpisodeMonitor)]
+                ('cursor', c_int64), ('capacity', c_int64), ('noise', NoiseStream), ('mon', EpisodeMonitor)]
 
 
 class DdpgPixelStep(Structure):
@@ -206,7 +212,8 @@ class SynthPpoPixelWindowStep(Structure):
                 [('cursor', c_int64), ('capacity', c_int64)] +
                 [(n, c_int32) for n in ('C', 'H', 'W', 'frame_stacks', 'hist_len', 'hist_pos', 'copy_workgroups',
                                         'reserved')] +
-                [(n, c_void_p) for n in ('hist', 'pixel', 'pixel_next', 'obs_pixel')] + [('mon', EpisodeMonitor)])
+                [(n, c_void_p) for n in ('hist', 'pixel', 'pixel_next', 'obs_pixel')] + [('noise', NoiseStream),
+                                                                                   ('mon', EpisodeMonitor)])
 
 
 SMX_DDPG_NOISE_NONE, SMX_DDPG_NOISE_GAUSSIAN, SMX_DDPG_NOISE_OU = 0, 1, 2
@@ -227,7 +234,7 @@ class SynthActStep(Structure):
                 ('obs_roll', c_void_p), ('act_roll', c_void_p), ('rew_roll', c_void_p),
                 ('done_roll', c_void_p), ('pd_roll', c_void_p), ('zsum', c_void_p), ('zsumsq', c_void_p),
                 ('zcount', c_void_p), ('zeps', c_float), ('reserved_f', c_float), ('xn_out', c_void_p),
-                ('mon', EpisodeMonitor)]
+                ('noise', NoiseStream), ('mon', EpisodeMonitor)]
 
 
 # smx_ppo_ctrl_t as 16 x 4-byte words: index of each field (floats 0-9, int32 10-15)
@@ -339,6 +346,7 @@ _SIGS = {
     'smx_ring_insert_f32': (c_int32, [_P, c_int64, c_int32, c_int64, _P, c_int64, _P]),
     'smx_gather_rows_f32': (c_int32, [_P, c_int64, c_int32, _P, c_int64, _P, _P]),
     'smx_philox4x32_10': (c_int32, [_P, c_int64, _P, _P]),
+    'smx_noise_fill_f32': (c_int32, [POINTER(NoiseStream), c_int32, c_int32, c_int32, _P, _P]),
     'smx_uniform_indices': (c_int32, [_P, c_int64, c_int64, c_uint64, c_uint64, _P]),
     'smx_uniform_gather_multi': (c_int32, [POINTER(GatherJob), c_int32, c_int64, c_int64, _P, c_int64, c_uint64, c_uint64,
                                            _P, _P]),

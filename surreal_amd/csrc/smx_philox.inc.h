@@ -1,0 +1,67 @@
+// Philox4x32-10 (Salmon et al. 2011) and the rollouts' exploration-noise stream built on it: the one definition the
+// replay sampler (smx_replay.hip) and every launch that samples an action (smx_replay.hip's per-step kernels,
+// smx_rollout.hip's persistent rollouts and step kernels, the fill kernel) evaluate.  Included inside an anonymous
+// namespace, after include/surreal_amd.h (struct smx_noise_stream).
+
+__device__ __forceinline__ void philox_round(uint32_t (&c)[4], uint32_t k0, uint32_t k1) {
+    const uint64_t p0 = (uint64_t)0xD2511F53u * c[0];
+    const uint64_t p1 = (uint64_t)0xCD9E8D57u * c[2];
+    const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c[1] ^ k0;
+    const uint32_t n1 = (uint32_t)p1;
+    const uint32_t n2 = (uint32_t)(p0 >> 32) ^ c[3] ^ k1;
+    const uint32_t n3 = (uint32_t)p0;
+    c[0] = n0; c[1] = n1; c[2] = n2; c[3] = n3;
+}
+
+// the ten rounds on counter c with key (k0, k1), in place
+__device__ __forceinline__ void philox4x32_10(uint32_t (&c)[4], uint32_t k0, uint32_t k1) {
+#pragma unroll
+    for (int r = 0; r < 10; ++r) {
+        philox_round(c, k0, k1);
+        k0 += 0x9E3779B9u;
+        k1 += 0xBB67AE85u;
+    }
+}
+
+// ---- the noise stream (struct smx_noise_stream, include/surreal_amd.h) ----------------------------------------------
+// The standard normal of (seed, global actor id g < 2^32, draw step s, action component j): a pure function of the four.
+//   x[0..3] = philox4x32_10(counter = (g, low32(s), high32(s), j >> 2), key = (low32(seed), high32(seed)))
+//   pair p = (j & 3) >> 1 takes the words x[2p], x[2p + 1]:
+//   u0 = ((float)(x[2p] >> 8) + 0.5f) * 0x1p-24f          (24 bits, exact in fp32; in (0, 1), never 0 or 1)
+//   u1 = ((float)(x[2p + 1] >> 8) + 0.5f) * 0x1p-24f
+//   r  = sqrtf(-2.0f * logf(u0));   (sn, cs) = sincospif(2.0f * u1)          (angle 2 pi u1; 2 u1 is exact)
+//   normal = (j & 1) ? r * sn : r * cs
+// so the four words of one block give components 4q .. 4q + 3 by two Box-Muller pairs, and |normal| <=
+// sqrt(-2 ln 2^-25) ~ 5.887.  The accurate library functions, no fast intrinsics; the build does not contract: every
+// caller gets the same bits.  Each (actor, component) lane runs its own ten rounds (a step's ~200 VALU instructions
+// against the 32 k cycles of its layers).
+__device__ __forceinline__ float noise_normal(uint64_t seed, uint32_t g, uint64_t s, int j) {
+    uint32_t c[4] = {g, (uint32_t)s, (uint32_t)(s >> 32), (uint32_t)j >> 2};
+    philox4x32_10(c, (uint32_t)seed, (uint32_t)(seed >> 32));
+    const bool hi = (j & 2) != 0;
+    const uint32_t x0 = hi ? c[2] : c[0], x1 = hi ? c[3] : c[1];
+    const float u0 = ((float)(x0 >> 8) + 0.5f) * 0x1p-24f;
+    const float u1 = ((float)(x1 >> 8) + 0.5f) * 0x1p-24f;
+    const float r = sqrtf(-2.0f * logf(u0));
+    float sn, cs;
+    sincospif(2.0f * u1, &sn, &cs);
+    return (j & 1) ? r * sn : r * cs;
+}
+
+// the draw of local actor a at the call's k-th step, component j
+__device__ __forceinline__ float noise_draw(const smx_noise_stream& N, long a, int k, int j) {
+    return noise_normal(N.seed, (uint32_t)(N.actor_base + a), (uint64_t)(N.step + k), j);
+}
+
+// THE RULE of a sampling launch (include/surreal_amd.h): eps wins; else the stream when enabled; else no noise
+__host__ __device__ inline bool noise_on(const float* eps, const smx_noise_stream& N) {
+    return eps != nullptr || N.enabled != 0;
+}
+// a noisy launch's draw for (local actor a, the call's k-th step, component j): element i of eps, else the stream's
+__device__ __forceinline__ float noise_pick(const float* eps, size_t i, const smx_noise_stream& N, long a, int k, int j) {
+    return eps ? eps[i] : noise_draw(N, a, k, j);
+}
+// what the entry points ask of a stream over n actors: every global actor id in [0, 2^32) (SMX_E_SHAPE)
+inline bool noise_shape_ok(const smx_noise_stream& N, long long n) {
+    return !N.enabled || (N.actor_base >= 0 && N.actor_base + n <= (1LL << 32));
+}

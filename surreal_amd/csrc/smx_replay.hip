@@ -10,6 +10,7 @@
 namespace {
 
 #include "smx_synth_env.inc.h"
+#include "smx_philox.inc.h"
 
 // copy `n` rows of `width` floats: dst row i <- src row map(i).  A wavefront moves one SEGMENT of
 // one row (ROW_SEG floats): a learner batch has few, very wide rows (1024 sub-trajectories of
@@ -96,17 +97,7 @@ __global__ __launch_bounds__(256) void gather_rows_kernel(const float* __restric
               [](long i) { return i; });
 }
 
-// Philox4x32-10 (Salmon et al. 2011), counter = (offset + i, 0), key = seed
-__device__ __forceinline__ void philox_round(uint32_t (&c)[4], uint32_t k0, uint32_t k1) {
-    const uint64_t p0 = (uint64_t)0xD2511F53u * c[0];
-    const uint64_t p1 = (uint64_t)0xCD9E8D57u * c[2];
-    const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c[1] ^ k0;
-    const uint32_t n1 = (uint32_t)p1;
-    const uint32_t n2 = (uint32_t)(p0 >> 32) ^ c[3] ^ k1;
-    const uint32_t n3 = (uint32_t)p0;
-    c[0] = n0; c[1] = n1; c[2] = n2; c[3] = n3;
-}
-
+// the uniform sampler: Philox4x32-10 (smx_philox.inc.h), counter = (offset + i, 0), key = seed
 __global__ __launch_bounds__(256) void uniform_indices_kernel(int64_t* __restrict__ idx, long n,
                                                               uint64_t len, uint64_t seed,
                                                               uint64_t offset) {
@@ -114,13 +105,7 @@ __global__ __launch_bounds__(256) void uniform_indices_kernel(int64_t* __restric
     if (i >= n) return;
     const uint64_t ctr = offset + (uint64_t)i;
     uint32_t c[4] = {(uint32_t)ctr, (uint32_t)(ctr >> 32), 0u, 0u};
-    uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        philox_round(c, k0, k1);
-        k0 += 0x9E3779B9u;
-        k1 += 0xBB67AE85u;
-    }
+    philox4x32_10(c, (uint32_t)seed, (uint32_t)(seed >> 32));
     // 64 random bits -> [0, len) by 128-bit multiply-high (bias < len / 2^64)
     const uint64_t r64 = ((uint64_t)c[0] << 32) | c[1];
     idx[i] = (int64_t)__umul64hi(r64, len);
@@ -131,25 +116,23 @@ __global__ __launch_bounds__(256) void philox_kat_kernel(const uint32_t* __restr
     const long i = (long)blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
     uint32_t c[4] = {ck[6 * i], ck[6 * i + 1], ck[6 * i + 2], ck[6 * i + 3]};
-    uint32_t k0 = ck[6 * i + 4], k1 = ck[6 * i + 5];
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        philox_round(c, k0, k1);
-        k0 += 0x9E3779B9u;
-        k1 += 0xBB67AE85u;
-    }
+    philox4x32_10(c, ck[6 * i + 4], ck[6 * i + 5]);
     out[4 * i] = c[0]; out[4 * i + 1] = c[1]; out[4 * i + 2] = c[2]; out[4 * i + 3] = c[3];
+}
+
+// the noise stream's draws as a tensor: out[k, a, j] = what a launch on N draws for (local actor a, its k-th step, j)
+__global__ __launch_bounds__(256) void noise_fill_kernel(smx_noise_stream N, int n, int A, long total, float* __restrict__ out) {
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= total) return;
+    const long ka = i / A;
+    const int j = (int)(i - ka * A);
+    const int k = (int)(ka / n);
+    out[i] = noise_draw(N, ka - (long)k * n, k, j);
 }
 
 __device__ __forceinline__ long philox_index(uint64_t ctr, uint64_t len, uint64_t seed) {
     uint32_t c[4] = {(uint32_t)ctr, (uint32_t)(ctr >> 32), 0u, 0u};
-    uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        philox_round(c, k0, k1);
-        k0 += 0x9E3779B9u;
-        k1 += 0xBB67AE85u;
-    }
+    philox4x32_10(c, (uint32_t)seed, (uint32_t)(seed >> 32));
     const uint64_t r64 = ((uint64_t)c[0] << 32) | c[1];
     return (long)__umul64hi(r64, len);
 }
@@ -329,11 +312,12 @@ __global__ __launch_bounds__(256) void synth_act_env_step_kernel(smx_synth_act_s
     const long a = i / D;
     const int k = (int)(i - a * D);
     const float nz = p.noise_scale ? p.noise_scale[a] : 1.0f;
+    const bool noisy = noise_on(p.eps, p.noise);
     auto action = [&](int j, float& mu, float& sd) {
         mu = p.mean[a * p.ld_mean + j];
         sd = expf(p.log_var[j]);
         if (p.noise_scale) sd = sd * nz;
-        float act = p.eps ? p.eps[a * p.ld_eps + j] * sd + mu : mu;
+        float act = noisy ? noise_pick(p.eps, a * p.ld_eps + j, p.noise, a, 0, j) * sd + mu : mu;
         if (act == act) act = fminf(fmaxf(act, -1.0f), 1.0f);
         return act;
     };
@@ -407,7 +391,7 @@ __global__ __launch_bounds__(256) void synth_act_head_step_kernel(smx_synth_act_
             const float nz = p.noise_scale ? p.noise_scale[a] : 1.0f;
             float sd = expf(p.log_var[j]);
             if (p.noise_scale) sd = sd * nz;
-            float act = p.eps ? p.eps[a * p.ld_eps + j] * sd + mu : mu;
+            float act = noise_on(p.eps, p.noise) ? noise_pick(p.eps, a * p.ld_eps + j, p.noise, a, 0, j) * sd + mu : mu;
             if (act == act) act = fminf(fmaxf(act, -1.0f), 1.0f);
             s_act[j] = act;
             if (p.act_roll) p.act_roll[(a * T + slot) * A + j] = act;
@@ -502,6 +486,20 @@ extern "C" int smx_philox4x32_10(const uint32_t* ctr_key, int64_t n, uint32_t* o
     SMX_REQUIRE(ctr_key && out, SMX_E_NULL);
     SMX_REQUIRE(n > 0, SMX_E_SHAPE);
     hipLaunchKernelGGL(philox_kat_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, smx_s(stream), ctr_key, (long)n, out);
+    SMX_LAUNCH_CHECK();
+    return SMX_OK;
+}
+
+extern "C" int smx_noise_fill_f32(const struct smx_noise_stream* noise, int32_t steps, int32_t n, int32_t A, float* out,
+                                  smx_stream_t stream) {
+    SMX_REQUIRE(noise && out, SMX_E_NULL);
+    smx_noise_stream N = *noise;
+    N.enabled = 1;
+    SMX_REQUIRE(steps > 0 && n > 0 && A > 0 && noise_shape_ok(N, n), SMX_E_SHAPE);
+    const long total = (long)steps * n * A;
+    SMX_REQUIRE((total + 255) / 256 <= 0x7fffffffL, SMX_E_SHAPE);
+    hipLaunchKernelGGL(noise_fill_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, smx_s(stream), N, n, A, total,
+                       out);
     SMX_LAUNCH_CHECK();
     return SMX_OK;
 }
@@ -623,7 +621,7 @@ extern "C" int smx_synth_act_env_step_f32(const smx_synth_act_step_t* args, smx_
                     p.episode_len > 0 && p.ld_mean >= p.A && (!p.eps || p.ld_eps >= p.A), SMX_E_SHAPE);
     SMX_REQUIRE(!p.zsum || (p.zsumsq && p.zcount && p.xn_out), SMX_E_NULL);
     SMX_REQUIRE(episode_pointers_ok(p.mon), SMX_E_NULL);
-    SMX_REQUIRE(episode_shape_ok(p.mon), SMX_E_SHAPE);
+    SMX_REQUIRE(episode_shape_ok(p.mon) && noise_shape_ok(p.noise, p.n), SMX_E_SHAPE);
     const long total = (long)p.n * p.D;
     hipLaunchKernelGGL(synth_act_env_step_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0,
                        smx_s(stream), p);
@@ -641,7 +639,7 @@ extern "C" int smx_synth_act_env_step_head_f32(const smx_synth_act_step_t* args,
                     p.episode_len > 0 && H2 > 0 && ld_h2 >= H2 && (!p.eps || p.ld_eps >= p.A), SMX_E_SHAPE);
     SMX_REQUIRE(!p.zsum || (p.zsumsq && p.zcount && p.xn_out), SMX_E_NULL);
     SMX_REQUIRE(episode_pointers_ok(p.mon), SMX_E_NULL);
-    SMX_REQUIRE(episode_shape_ok(p.mon), SMX_E_SHAPE);
+    SMX_REQUIRE(episode_shape_ok(p.mon) && noise_shape_ok(p.noise, p.n), SMX_E_SHAPE);
     hipLaunchKernelGGL(synth_act_head_step_kernel, dim3((unsigned)p.n), dim3(256), 0, smx_s(stream), p, W3, b3, h2,
                        (long)ld_h2, H2, out_act);
     SMX_LAUNCH_CHECK();

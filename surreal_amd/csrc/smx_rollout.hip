@@ -45,6 +45,10 @@
 // Episode monitor (struct smx_episode_monitor; mon.ep_reward null: none): the lane that forms an actor's reward also keeps
 // its open episode's fp64 reward sum and length (episode_step, smx_synth_env.inc.h) -- in LDS behind the layout in the
 // persistent kernels (HBM at entry, at a closing step, at exit), in HBM in the step kernels.
+//
+// Exploration noise (struct smx_noise_stream): a sampling head takes its lane's draw from eps when there is one, else --
+// noise.enabled -- forms it itself where it requested the eps word before (noise_pick, smx_philox.inc.h: ten Philox
+// rounds and one Box-Muller element per (actor, component) lane and step), else samples nothing.
 #include "smx_common.h"
 #include <string.h>
 
@@ -53,6 +57,7 @@ namespace {
 #include "smx_epoch_mma.inc.h"
 #include "smx_rows4_mma.inc.h"
 #include "smx_synth_env.inc.h"
+#include "smx_philox.inc.h"
 #include "smx_lstm_act.inc.h"
 
 // Phase timestamps exist only in a build with -DSMX_ROLLOUT_TIMING (scripts/bench_rollout.py); the product build has none.
@@ -81,6 +86,7 @@ struct RollBase {
     const float *b1, *b2, *b3;
     int D, H1, H2, A, n, steps, t0, episode_len;
     const float* eps;                           // this step's normal draws [steps, n, A] or null
+    smx_noise_stream nstream;                   // eps null and nstream.enabled: the draws are formed here (noise_draw)
     float* state;                               // [n, D] in / out
     const float* init_state;
     int ldx, ldh1, ldh2, off_h1, off_h2, off_out, off_act, off_red3, off_z, off_kmod;
@@ -459,6 +465,7 @@ __device__ __forceinline__ void ppo_rollout(Args G) {
     const float b3v = G.b3[hj];
     float sd0 = expf(G.log_var[hj]);
     if (G.noise_scale && hr < nrows) sd0 = sd0 * G.noise_scale[row0 + hr];
+    const bool noisy = noise_on(G.eps, G.nstream);
     int t = G.t0;
     long long wbase = 0;                         // (WIN) (cursor + k n) % capacity after k closing steps
     if constexpr (WIN) wbase = G.W.cursor;
@@ -480,7 +487,7 @@ __device__ __forceinline__ void ppo_rollout(Args G) {
         RSTAMP(0);
         // this step's normal draw of the lane's (row, action) pair, requested before the layers (consumed behind them)
         float ev = 0.f;
-        if (G.eps && hr < nrows) ev = G.eps[((size_t)step * G.n + row0 + hr) * A + hj];
+        if (noisy && hr < nrows) ev = noise_pick(G.eps, ((size_t)step * G.n + row0 + hr) * A + hj, G.nstream, row0 + hr, step, hj);
         // ---- the three layers (the output layer below when its weights are register-resident) -------------------
         if constexpr (LSTM) {
             const PreLayer gate{G.Pg, G.bg, 4 * G.H, G.Dp + G.H, G.off_g, G.ldg};
@@ -593,7 +600,7 @@ __device__ __forceinline__ void ppo_rollout(Args G) {
                 mu = outs[hr * RLDO + hj];
             }
             const float sd = sd0;
-            float act = G.eps ? ev * sd + mu : mu;
+            float act = noisy ? ev * sd + mu : mu;
             if (act == act) act = fminf(fmaxf(act, -1.0f), 1.0f);
             s_act[hr * RMAX_A + hj] = act;
             if constexpr (!WIN) {
@@ -767,6 +774,7 @@ __global__ __launch_bounds__(RNTH) void rollout16_kernel(RollArgs G) {
     const long row0 = E.row0;
     const int nrows = E.nrows;
 
+    const bool noisy = noise_on(G.eps, G.nstream);
     int t = G.t0;
     RWALL(12); RCYC(13);
 #pragma unroll 1
@@ -776,7 +784,7 @@ __global__ __launch_bounds__(RNTH) void rollout16_kernel(RollArgs G) {
         // this step's normal draw of the lane's (row, action) pair, requested before the layers (consumed behind them)
         const int hr = tid / A, hj = tid - hr * A;        // 16 x A <= 512 pairs
         float ev = 0.f;
-        if (G.eps && hr < nrows) ev = G.eps[((size_t)step * G.n + row0 + hr) * A + hj];
+        if (noisy && hr < nrows) ev = noise_pick(G.eps, ((size_t)step * G.n + row0 + hr) * A + hj, G.nstream, row0 + hr, step, hj);
         // ---- the three layers: the loop of epoch_fwd_kernel without its global stores ---------------------
 #pragma unroll 1
         for (int l = 0; l < 3; ++l) {
@@ -836,7 +844,7 @@ __global__ __launch_bounds__(RNTH) void rollout16_kernel(RollArgs G) {
             const float mu = outs[hr * RLDO + hj];
             float sd = expf(G.log_var[hj]);
             if (G.noise_scale) sd = sd * G.noise_scale[a];
-            float act = G.eps ? ev * sd + mu : mu;
+            float act = noisy ? ev * sd + mu : mu;
             if (act == act) act = fminf(fmaxf(act, -1.0f), 1.0f);
             s_act[hr * RMAX_A + hj] = act;
             if (G.act_roll) G.act_roll[(a * R + slot) * A + hj] = act;
@@ -935,11 +943,12 @@ __global__ __launch_bounds__(RNTH) void ddpg_rollout_kernel(DArgs G) {
     }
     SMX_LDS_BARRIER();
 
+    const bool noisy = noise_on(G.eps, G.nstream);     // (never with SMX_DDPG_NOISE_NONE: common_args)
     int tau = G.t0, kemit = 0;
 #pragma unroll 1
     for (int step = 0; step < G.steps; ++step) {
         float ev = 0.f;                              // this step's draw, requested before the layers
-        if (G.eps && head) ev = G.eps[((size_t)step * G.n + ha) * A + hj];
+        if (noisy && head) ev = noise_pick(G.eps, ((size_t)step * G.n + ha) * A + hj, G.nstream, ha, step, hj);
         // ---- the actor's three layers (ReLU, ReLU, tanh) --------------------------------------------------------
         layers4<RG, NT>(G, sm, 3, SMX_ACT_TANH, wv, lane, [](int) {}, 0, G.D);
         const bool emit = tau >= N - 1;
@@ -995,7 +1004,7 @@ __device__ __forceinline__ void ddpg_step_act(const DArgs& G, const float* mu, l
     double x = 0.0, sig = 0.0;
     if (G.noise != SMX_DDPG_NOISE_NONE) sig = G.sigmas[a];
     if (G.noise == SMX_DDPG_NOISE_OU) x = G.ou[a * A + lane];
-    const float e = G.eps ? G.eps[a * A + lane] : 0.f;
+    const float e = noise_on(G.eps, G.nstream) ? noise_pick(G.eps, a * A + lane, G.nstream, a, 0, lane) : 0.f;
     const float v = explore(mu[a * ld_mu + lane], G.noise, e, sig, G.theta, G.dt, G.root_dt, tau, x);
     if (G.noise == SMX_DDPG_NOISE_OU) G.ou[a * A + lane] = x;
     s_act_w[lane] = v;
@@ -1235,6 +1244,7 @@ __global__ __launch_bounds__(256) void ddpg_pixel_step_kernel(DArgs G, PArgs P, 
 struct PWArgs {
     int n, D, A, Hl, t0, episode_len;
     const float *log_var, *noise_scale, *eps;
+    smx_noise_stream nstream;                  // eps null and nstream.enabled: the draws are formed here (noise_draw)
     float* state;
     const float* init_state;
     const float *h_before, *c_before;          // [n, Hl] the LSTM state before this step, or null
@@ -1261,7 +1271,7 @@ __global__ __launch_bounds__(256) void ppo_pixel_window_step_kernel(PWArgs G, PA
             const float m = mu[a * ld_mu + tid];
             float sd = expf(G.log_var[tid]);
             if (G.noise_scale) sd = sd * G.noise_scale[a];
-            float act = G.eps ? G.eps[a * A + tid] * sd + m : m;
+            float act = noise_on(G.eps, G.nstream) ? noise_pick(G.eps, a * A + tid, G.nstream, a, 0, tid) * sd + m : m;
             if (act == act) act = fminf(fmaxf(act, -1.0f), 1.0f);
             s_act[tid] = act;
             float* ca = W.cact + (size_t)a * N * A + tid;
@@ -1474,15 +1484,16 @@ int common_args(const smx_ddpg_rollout_t* a, DArgs& G) {
     SMX_REQUIRE(a->n > 0 && a->D > 0 && a->A > 0 && a->n_step > 0 && a->episode_len > 0 && a->t >= 0, SMX_E_SHAPE);
     SMX_REQUIRE(a->capacity > 0 && a->cursor >= 0 && a->cursor < a->capacity, SMX_E_SHAPE);
     SMX_REQUIRE(a->noise_type >= SMX_DDPG_NOISE_NONE && a->noise_type <= SMX_DDPG_NOISE_OU, SMX_E_SHAPE);
-    SMX_REQUIRE(a->noise_type == SMX_DDPG_NOISE_NONE || (a->eps && a->sigmas), SMX_E_NULL);
+    SMX_REQUIRE(a->noise_type == SMX_DDPG_NOISE_NONE || (noise_on(a->eps, a->noise) && a->sigmas), SMX_E_NULL);
     SMX_REQUIRE(a->noise_type != SMX_DDPG_NOISE_OU || a->ou, SMX_E_NULL);
     SMX_REQUIRE(episode_pointers_ok(a->mon), SMX_E_NULL);
-    SMX_REQUIRE(episode_shape_ok(a->mon), SMX_E_SHAPE);
+    SMX_REQUIRE(episode_shape_ok(a->mon) && noise_shape_ok(a->noise, a->n), SMX_E_SHAPE);
     memset(&G, 0, sizeof(G));
     G.mon = a->mon;
     G.D = a->D; G.A = a->A; G.n = a->n; G.steps = a->steps; G.t0 = a->t; G.episode_len = a->episode_len;
     G.N = a->n_step; G.noise = a->noise_type;
     G.eps = a->noise_type == SMX_DDPG_NOISE_NONE ? nullptr : a->eps;
+    if (a->noise_type != SMX_DDPG_NOISE_NONE) G.nstream = a->noise;       // (NONE reads neither)
     G.sigmas = a->sigmas; G.theta = a->theta; G.dt = a->dt; G.root_dt = a->root_dt;
     G.gpow = a->gpow; G.ou = a->ou;
     G.state = a->state; G.init_state = a->init_state;
@@ -1525,6 +1536,7 @@ void roll_fields(const smx_synth_rollout_t* a, int D, RollArgs& G) {
     G.state = a->state; G.init_state = a->init_state;
     G.n = a->n; G.t0 = a->t; G.episode_len = a->episode_len; G.steps = a->steps;
     G.mon = a->mon;
+    G.nstream = a->noise;
 }
 
 // the rollout tables (the windowed kernels have none)
@@ -1597,7 +1609,8 @@ bool aligned_ok(const float* packed, const float* b1, const float* lstm_packed) 
 bool rollout_shape_ok(const smx_synth_rollout_t* a, const void* cells) {
     const bool records = a->obs_roll || a->act_roll || a->rew_roll || a->done_roll || a->pd_roll || cells;
     return a->n > 0 && a->steps > 0 && a->episode_len > 0 && a->rows_per_actor > 0 && block_ok(a->actors_per_workgroup) &&
-           a->slot >= 0 && (!records || a->slot + a->steps <= a->rows_per_actor) && episode_shape_ok(a->mon);
+           a->slot >= 0 && (!records || a->slot + a->steps <= a->rows_per_actor) && episode_shape_ok(a->mon) &&
+           noise_shape_ok(a->noise, a->n);
 }
 bool cell_pairs_ok(const float* h0, const float* c0, const float* h_before, const float* c_before) {
     return (h_before == nullptr) == (c_before == nullptr) && (h0 == nullptr) == (c0 == nullptr);
@@ -1719,6 +1732,7 @@ extern "C" int smx_synth_ppo_window_rollout_f32(const smx_synth_ppo_window_rollo
                 SMX_E_UNSUPPORTED);
     SMX_REQUIRE(a->n > 0 && a->steps > 0 && a->episode_len > 0 && a->t >= 0 && a->t < a->episode_len, SMX_E_SHAPE);
     SMX_REQUIRE(block_ok(a->actors_per_workgroup) && window_shape_ok(*args) && episode_shape_ok(a->mon), SMX_E_SHAPE);
+    SMX_REQUIRE(noise_shape_ok(a->noise, a->n), SMX_E_SHAPE);
     // two workgroups must never write the same FIFO row: all n m rows of the call are distinct
     const long long m = closing_steps(a->t, a->steps, a->episode_len,
                                       [&](int t) { return window_closes(t, args->n_step, args->advance); });
@@ -1807,6 +1821,7 @@ extern "C" int smx_synth_ppo_pixel_window_step(const struct smx_synth_ppo_pixel_
     SMX_REQUIRE(window_shape_ok(*args) && step_shape_ok(args->n, args->A, ld_mu, args->capacity), SMX_E_SHAPE);
     SMX_REQUIRE(pixel_shape_ok(*args, args->n_step), SMX_E_SHAPE);
     SMX_REQUIRE(args->copy_workgroups >= 0 && args->copy_workgroups <= 1024 && episode_shape_ok(args->mon), SMX_E_SHAPE);
+    SMX_REQUIRE(noise_shape_ok(args->noise, args->n), SMX_E_SHAPE);
     PWArgs G;
     memset(&G, 0, sizeof(G));
     G.n = args->n; G.D = args->D; G.A = args->A; G.Hl = args->hidden; G.t0 = args->t; G.episode_len = args->episode_len;
@@ -1815,6 +1830,7 @@ extern "C" int smx_synth_ppo_pixel_window_step(const struct smx_synth_ppo_pixel_
     G.h_before = args->h_before; G.c_before = args->c_before;
     G.W = win_fields(*args);
     G.mon = args->mon;
+    G.nstream = args->noise;
     // the copy workgroups of this step: its destination frames -- (N + 1) S - 1 more at a closing step than the S - 1
     // (S + 1 on done) of any other
     const int S = args->frame_stacks;

@@ -268,6 +268,38 @@ class DeviceEpisodeMonitor(object):
         return _mean(xs) if xs else None
 
 
+class DeviceNoise(object):
+    """The exploration noise of a SyntheticVecEnv's actors as a counter-based stream (struct smx_noise_stream,
+    include/surreal_amd.h): the standard normal of (seed, actor_base + a, step + k, j) for actor a, the k-th step from
+    now and action component j is a pure function of the four (Philox4x32-10 and Box-Muller), formed inside the launch
+    that consumes it.  Made by SyntheticVecEnv.attach_noise(seed, actor_base).
+
+    step: the draw step of the env's next step -- one host integer all actors share, advanced by the env with every
+    stepping call, never rewound by reset() (a new episode gets new noise); read it for a checkpoint, set it to resume
+    (or to see the same draws again)."""
+
+    def __init__(self, seed, actor_base, n, A, kernels, device):
+        self.seed, self.actor_base, self.step = int(seed), int(actor_base), 0
+        if not 0 <= self.seed < 1 << 64:
+            raise ValueError('DeviceNoise: seed must fit 64 bits, got %r' % (seed,))
+        if self.actor_base < 0 or self.actor_base + int(n) > 1 << 32:
+            raise ValueError('DeviceNoise: global actor ids %d .. %d leave [0, 2^32)'
+                             % (self.actor_base, self.actor_base + int(n) - 1))
+        self.n, self.A, self.K, self.device = int(n), int(A), kernels, device
+
+    def at(self, ahead=0):
+        """(seed, actor_base, draw step `ahead` steps from now): what a launch's `noise=` keyword takes"""
+        return (self.seed, self.actor_base, self.step + int(ahead))
+
+    def draws(self, T, n=None, A=None):
+        """-> [T, n, A] fp32 on the device: the draws the env's next T steps use (smx_noise_fill_f32: the launches'
+        own function, the same bits), without advancing the counter.  n, A: the env's by default"""
+        import torch
+        out = torch.empty(int(T), self.n if n is None else int(n), self.A if A is None else int(A), device=self.device)
+        self.K.noise_fill(self.at(), out)
+        return out
+
+
 class _DeviceActorReport(TrainingTensorplexMonitor):
     """TrainingTensorplexMonitor for one actor of a DeviceEpisodeMonitor: the same period, mean, tags and global_step,
     fed with polled episodes instead of wrapping an env"""

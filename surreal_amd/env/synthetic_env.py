@@ -108,6 +108,7 @@ class SyntheticVecEnv(object):
         self._ddpg = {}               # ddpg_rollout_into(): the open n-step transitions and OU states of the actors
         self._ppo = {}                # ppo_rollout_into(): the open moving windows of the actors
         self.monitor = None           # attach_monitor(): the actors' episode returns, kept by the step launches
+        self.noise = None             # attach_noise(): the exploration noise as a per-actor stream, drawn by the launches
 
     def attach_monitor(self, capacity=16):
         """-> a DeviceEpisodeMonitor (env/monitor.py) that every stepping launch from now on feeds: per actor the open
@@ -130,6 +131,34 @@ class SyntheticVecEnv(object):
             return {}
         self.monitor.count_steps(k)
         return {'monitor': self.monitor}
+
+    def attach_noise(self, seed, actor_base=0):
+        """-> a DeviceNoise (env/monitor.py): from now on a stepping call that gets no `eps` draws its exploration noise
+        inside its launches, the standard normal of (seed, actor_base + a, draw step, component) for actor a (struct
+        smx_noise_stream, include/surreal_amd.h) -- no [T, n, A] tensor is made.  The draw step is one host counter all
+        actors share (DeviceNoise.step, readable and settable): every stepping call advances it by its env steps,
+        whether or not its draws came from the stream; reset() does not rewind it.  An actor's noise then depends on
+        its global id and the step count alone: not on n, T, the cut of a run into calls or the split of the actors
+        over envs (actor_base: the global id of this env's actor 0).  An explicit `eps` still wins; the deterministic
+        agent modes still draw nothing."""
+        from .monitor import DeviceNoise
+        self.noise = DeviceNoise(seed, actor_base, self.n, self.A, self.K, self.device)
+        return self.noise
+
+    def detach_noise(self):
+        """the calls draw with torch.randn again -> the stream (which keeps its counter)"""
+        m, self.noise = self.noise, None
+        return m
+
+    def _noi(self, k, on=False):
+        """the keyword a stepping launch takes when its draws come from the attached stream (`on`: what _draws
+        answered; none otherwise: kernels objects that know no streams are called as before); the stream's clock moves
+        on by the k env steps of the launch either way"""
+        if self.noise is None:
+            return {}
+        at = self.noise.at()
+        self.noise.step += int(k)
+        return {'noise': at} if on else {}
 
     def reset(self):
         self.state.copy_(self.init_state)
@@ -159,13 +188,16 @@ class SyntheticVecEnv(object):
         return sum(bool(closes(t)) for t in ts[:-1]), ts[-1]
 
     def _draws(self, agent, eps, T):
-        """the standard-normal draws of T steps, [T, n, A] contiguous: `eps`, by default drawn here in one launch; None
-        in the deterministic agent modes"""
+        """-> (the standard-normal draws of T steps, [T, n, A] contiguous: `eps`, by default drawn here in one launch;
+        whether the launches draw from the attached stream instead).  (None, False) in the deterministic agent modes;
+        (None, True) with a stream attached and no `eps`: the launches get it through _noi"""
         if agent.agent_mode in ('eval_deterministic', 'eval_deterministic_local'):
-            return None
+            return None, False
         if eps is None:
+            if self.noise is not None:
+                return None, True
             eps = torch.randn(T, self.n, self.A, device=self.device)
-        return eps.contiguous()
+        return eps.contiguous(), False
 
     def _packed(self, attr, numel, pack):
         """the cached buffer `attr` of numel floats, (re)allocated when the size changed and packed again: the agent's
@@ -262,7 +294,8 @@ class SyntheticVecEnv(object):
         r = self.rolls
         if r is not None and self.slot < self.T:
             self.K.synth_env_step(self.state, self.init_state, actions, self.t, self.episode_len,
-                                  self.slot, r['obs'], r['actions'], r['rewards'], r['dones'], **self._mon(1))
+                                  self.slot, r['obs'], r['actions'], r['rewards'], r['dones'], **self._mon(1),
+                                  **self._noi(1))
             if pds is not None and pds.data_ptr() != r['pds'][:, self.slot].data_ptr():
                 r['pds'][:, self.slot] = pds         # (an agent may have written the slot in place)
             self.slot += 1
@@ -272,7 +305,7 @@ class SyntheticVecEnv(object):
                 self.K.synth_frames(r['obs'][:, self.slot, 0], self.t + 1, self.frames[:, self.slot])
         else:
             self.K.synth_env_step(self.state, self.init_state, actions, self.t, self.episode_len, 0,
-                                  None, None, None, None, **self._mon(1))
+                                  None, None, None, None, **self._mon(1), **self._noi(1))
         self._advance()
         return self.state
 
@@ -289,11 +322,11 @@ class SyntheticVecEnv(object):
         automatic; 4 and 8 give the same bits, 16 sums the layers in another order)."""
         T, n, K = self.T, self.n, self.K
         assert self.slot == 0 and 'pds' in self.rolls, 'start_rollout(T, info_width=2 * A) first'
-        eps = self._draws(agent, eps, T)
+        eps, ns = self._draws(agent, eps, T)
         if agent.rnn_config.if_rnn_policy or agent.model.if_pixel:
             if self._lstm_persistent(agent):
-                return self._rollout_lstm(agent, eps, actors_per_workgroup)
-            return self._rollout_stem(agent, eps)
+                return self._rollout_lstm(agent, eps, actors_per_workgroup, ns)
+            return self._rollout_stem(agent, eps, ns)
         noise = agent.batch_noise(n).view(-1)
         zf = agent.model.z_filter if agent.use_z_filter else None
         log_var = agent.model.log_var.view(-1)
@@ -305,7 +338,7 @@ class SyntheticVecEnv(object):
             # between rollouts (fetch_parameter)
             K.synth_rollout(actor, self._pack_actor(actor), L.SMX_ACT_TANH, self.state, self.init_state, log_var, noise,
                             eps, self.t, self.episode_len, T, self.slot, self.rolls, zf, actors_per_workgroup,
-                            **self._mon(T))
+                            **self._mon(T), **self._noi(T, ns))
             self.slot += T
             self._advance(T)
             return
@@ -327,7 +360,8 @@ class SyntheticVecEnv(object):
                 K.linear(self._h1, 1, v['W2'], 1, v['b2'], self._h2, n, actor.H2, actor.H1, act=L.SMX_ACT_RELU)
                 K.synth_act_env_step_head(v['W3'], v['b3'], self._h2, L.SMX_ACT_TANH, self.state, self.init_state,
                                           log_var, noise, None if eps is None else eps[t], self.t,
-                                          self.episode_len, self.slot, self.rolls, zf, self._xn, **self._mon(1))
+                                          self.episode_len, self.slot, self.rolls, zf, self._xn, **self._mon(1),
+                                          **self._noi(1, ns))
                 self.slot += 1
                 self._advance()
             return
@@ -335,7 +369,7 @@ class SyntheticVecEnv(object):
             mean = agent.policy_mean(self._xn)
             K.synth_act_env_step(self.state, self.init_state, mean, log_var, noise,
                                  None if eps is None else eps[t], self.t, self.episode_len, self.slot,
-                                 self.rolls, zf, self._xn, **self._mon(1))
+                                 self.rolls, zf, self._xn, **self._mon(1), **self._noi(1, ns))
             self.slot += 1
             self._advance()
 
@@ -346,7 +380,7 @@ class SyntheticVecEnv(object):
                 and getattr(self.K, 'synth_lstm_rollout', None) is not None
                 and self.K.synth_lstm_rollout_supported(agent.model))
 
-    def _lstm_launch(self, agent, eps, steps, slot, rolls, actors_per_workgroup):
+    def _lstm_launch(self, agent, eps, steps, slot, rolls, actors_per_workgroup, ns=False):
         """the LSTM rollout launch from the zero state (a rollout starts at an episode boundary, as in _rollout_stem);
         leaves the agent's batch cells where act_batch would have: _batch_cells the final (h, c), batch_cells_before the
         state before the last step, each (1, n, Hl)"""
@@ -356,18 +390,19 @@ class SyntheticVecEnv(object):
         self.K.synth_lstm_rollout(m, pk, lpk, self.state, self.init_state, agent.batch_noise(self.n).view(-1), eps,
                                   self.t, self.episode_len, steps, slot, rolls,
                                   m.z_filter if agent.use_z_filter else None,
-                                  actors_per_workgroup=actors_per_workgroup, **cells, **self._mon(steps))
+                                  actors_per_workgroup=actors_per_workgroup, **cells, **self._mon(steps),
+                                  **self._noi(steps, ns))
         self._hand_cells(agent, cells)
         self._advance(steps)
 
-    def _rollout_lstm(self, agent, eps, actors_per_workgroup=0):
+    def _rollout_lstm(self, agent, eps, actors_per_workgroup=0, ns=False):
         """rollout() for an LSTM-stem policy in ONE launch (smx_synth_lstm_rollout_f32): what _rollout_stem records,
         the cells every actor held before each step included"""
         T, n = self.T, self.n
         if 'cells' not in self.rolls:
             nl, F = agent.rnn_config.rnn_layer, agent.rnn_config.rnn_hidden
             self.rolls['cells'] = torch.zeros(n, T + 1, 2, nl, F, device=self.device)
-        self._lstm_launch(agent, eps, T, self.slot, self.rolls, actors_per_workgroup)
+        self._lstm_launch(agent, eps, T, self.slot, self.rolls, actors_per_workgroup, ns)
         self.slot += T
 
     def can_rollout_into(self, agent):
@@ -389,19 +424,19 @@ class SyntheticVecEnv(object):
         T = out['obs'].shape[1]
         assert self.t == 0 and T <= self.episode_len and self.can_rollout_into(agent)
         assert tuple(out['obs'].shape) == (n, T, self.D) and all(out[k].is_contiguous() for k in out)
-        eps = self._draws(agent, eps, T)
+        eps, ns = self._draws(agent, eps, T)
         rolls = {'obs': out['obs'], 'actions': out['actions'], 'rewards': out['rewards'], 'dones': out['dones'],
                  'pds': out['pds'], 'obs_last': out['obs_next']}
         if agent.rnn_config.if_rnn_policy:
             # the window's onetime_infos: the state at its first step -- the zero state a rollout starts from
             out['cells'].zero_()
-            self._lstm_launch(agent, eps, T, 0, rolls, actors_per_workgroup)
+            self._lstm_launch(agent, eps, T, 0, rolls, actors_per_workgroup, ns)
             return
         actor = agent.model.actor
         K.synth_rollout(actor, self._pack_actor(actor), L.SMX_ACT_TANH, self.state, self.init_state,
                         agent.model.log_var.view(-1), agent.batch_noise(n).view(-1), eps, self.t, self.episode_len, T, 0,
                         rolls, agent.model.z_filter if agent.use_z_filter else None, actors_per_workgroup,
-                        **self._mon(T))
+                        **self._mon(T), **self._noi(T, ns))
         self._advance(T)
 
     def _ppo_window_refusal(self, agent):
@@ -493,10 +528,10 @@ class SyntheticVecEnv(object):
             shapes.update(pixel=(N, S * C, H, W), pixel_next=(1, S * C, H, W))
             dtypes = {'pixel': torch.uint8, 'pixel_next': torch.uint8}
         tables, cursor, cap = replay.reserve_ring(rows, shapes, dtypes)
-        eps = self._draws(agent, eps, T)
+        eps, ns = self._draws(agent, eps, T)
         assert eps is None or tuple(eps.shape) == (T, n, A)
         if camera:
-            self._ppo_pixel_steps(agent, T, N, adv, tables, cursor, cap, eps)
+            self._ppo_pixel_steps(agent, T, N, adv, tables, cursor, cap, eps, ns)
             replay.commit_ring(rows)
             c['t'] = self.t
             return rows
@@ -511,14 +546,14 @@ class SyntheticVecEnv(object):
                 cells.update(h0=held[0].contiguous(), c0=held[1].contiguous())
         K.synth_ppo_window_rollout(m, pk, lpk, self.state, self.init_state, noise, eps, self.t, self.episode_len, T, N,
                                    adv, c['carry'], tables, cursor, zf, actors_per_workgroup=actors_per_workgroup, **cells,
-                                   **self._mon(T))
+                                   **self._mon(T), **self._noi(T, ns))
         if rnn:
             self._hand_cells(agent, cells)
         replay.commit_ring(rows)
         self.t = c['t'] = t
         return rows
 
-    def _ppo_pixel_steps(self, agent, T, N, adv, tables, cursor, cap, eps):
+    def _ppo_pixel_steps(self, agent, T, N, adv, tables, cursor, cap, eps, ns=False):
         """ppo_rollout_into's camera path: per step perception -> [one LSTM step ->] actor -> the record launch.  The
         history (hist [n, N + S, C, H, W], the current step's frame in slot hist_pos) lives with the carry rings in
         self._ppo and is primed with them (first use, after reset()) as _ddpg_pixel_steps primes it; the perception's
@@ -570,7 +605,7 @@ class SyntheticVecEnv(object):
             K.mlp3_forward(actor, feat, w.h1, w.h2, w.mean, L.SMX_ACT_TANH)
             r['t'], r['hist_pos'] = self.t, c['hist_pos']
             r['eps'] = None if eps is None else eps[s]
-            K.synth_ppo_pixel_window_step(r, w.mean, **self._mon(1))
+            K.synth_ppo_pixel_window_step(r, w.mean, **self._mon(1), **self._noi(1, ns))
             c['hist_pos'] = (c['hist_pos'] + 1) % Hd
             j = self.t + 1 - N
             if j >= 0 and j % adv == 0:
@@ -632,14 +667,15 @@ class SyntheticVecEnv(object):
         if d.get('gamma') != gamma:
             d['gamma'] = gamma
             d['gpow'] = torch.tensor([pow(gamma, e) for e in range(N)], dtype=torch.float64, device=self.device)
-        eps = self._draws(agent, eps, T)
-        deterministic = eps is None
+        eps, ns = self._draws(agent, eps, T)
+        deterministic = eps is None and not ns
         noise = L.SMX_DDPG_NOISE_NONE if deterministic else \
             {'normal': L.SMX_DDPG_NOISE_GAUSSIAN, 'ou_noise': L.SMX_DDPG_NOISE_OU}[agent.noise_type]
         if not deterministic:
             if sigmas is None:
                 sigmas = agent.batch_sigmas(n)
-            assert tuple(eps.shape) == (T, n, A) and sigmas.dtype == torch.float64 and sigmas.numel() == n
+            assert eps is None or tuple(eps.shape) == (T, n, A)
+            assert sigmas.dtype == torch.float64 and sigmas.numel() == n
             sigmas = sigmas.contiguous()
         r = dict(state=self.state, init_state=self.init_state, t=self.t, episode_len=self.episode_len, n_step=N,
                  noise_type=noise, eps=eps, sigmas=None if deterministic else sigmas,
@@ -647,7 +683,7 @@ class SyntheticVecEnv(object):
                  carry_obs=d['carry_obs'], carry_act=d['carry_act'], carry_rew=d['carry_rew'], tables=tables,
                  cursor=cursor)
         if camera:
-            self._ddpg_pixel_steps(agent, r, T, N, cap, deterministic, eps)
+            self._ddpg_pixel_steps(agent, r, T, N, cap, eps, ns)
             replay.commit_ring(rows)
             return rows
         actor = agent.model.actor
@@ -657,7 +693,7 @@ class SyntheticVecEnv(object):
                 d['pk'] = torch.zeros(K.epoch_packed_numel(actor), device=self.device)
             K.epoch_pack([(actor, d['pk'])])        # (the agent's parameters only change between rollouts)
         if persistent and not reference:
-            K.synth_ddpg_rollout(actor, d['pk'], r, T, actors_per_workgroup, **self._mon(T))
+            K.synth_ddpg_rollout(actor, d['pk'], r, T, actors_per_workgroup, **self._mon(T), **self._noi(T, ns))
             self.t = t
         else:
             if reference:
@@ -671,15 +707,15 @@ class SyntheticVecEnv(object):
                 else:
                     mu = agent.model.forward_actor(self.state)
                 r['t'] = self.t
-                r['eps'] = None if deterministic else eps[s]
-                K.synth_ddpg_step(r, mu, **self._mon(1))
+                r['eps'] = None if eps is None else eps[s]
+                K.synth_ddpg_step(r, mu, **self._mon(1), **self._noi(1, ns))
                 if self.t >= N - 1:
                     r['cursor'] = (r['cursor'] + n) % cap
                 self._advance()
         replay.commit_ring(rows)
         return rows
 
-    def _ddpg_pixel_steps(self, agent, r, T, N, cap, deterministic, eps):
+    def _ddpg_pixel_steps(self, agent, r, T, N, cap, eps, ns=False):
         """ddpg_rollout_into's camera path: per step perception -> actor -> smx_synth_ddpg_pixel_step.  The history
         (hist [n, N + S, C, H, W], the current step's frame in slot hist_pos) is primed on first use and after reset():
         the current frame in every slot, the actors' first observation that frame S times (N + S + 1 launches, once)"""
@@ -698,14 +734,14 @@ class SyntheticVecEnv(object):
             model.perception_into(d['obs_pixel'], self.state, d['cnn_ws'], d['x'])
             mu = model.forward_actor(d['x'])
             r['t'], r['hist_pos'] = self.t, d['hist_pos']
-            r['eps'] = None if deterministic else eps[s]
-            K.synth_ddpg_pixel_step(r, mu, **self._mon(1))
+            r['eps'] = None if eps is None else eps[s]
+            K.synth_ddpg_pixel_step(r, mu, **self._mon(1), **self._noi(1, ns))
             d['hist_pos'] = (d['hist_pos'] + 1) % Hd
             if self.t >= N - 1:
                 r['cursor'] = (r['cursor'] + n) % cap
             self._advance()
 
-    def _rollout_stem(self, agent, eps):
+    def _rollout_stem(self, agent, eps, ns=False):
         """policies with an LSTM and / or CNN stem: one batched act per step (PPOAgent.act_batch: the stem and the
         MLP for all actors at once) on the stacked observation, then the step launch; the LSTM state every actor
         held BEFORE each step is recorded (what the window that starts there carries as onetime_infos,
@@ -717,8 +753,10 @@ class SyntheticVecEnv(object):
             nl, F = agent.rnn_config.rnn_layer, agent.rnn_config.rnn_hidden
             self.rolls['cells'] = torch.zeros(n, T + 1, 2, nl, F, device=self.device)
         for t in range(T):
-            a, pd = agent.act_batch(self.observation(), eps=None if eps is None else eps[t],
-                                    out_pd=self.rolls['pds'][:, self.slot])
+            # (act_batch forms the sample, not one of the step launches: with a stream, its draws for this step from the
+            # fill kernel -- the numbers a launch would have formed; step() below moves the stream's clock)
+            e = self.noise.draws(1)[0] if ns else (None if eps is None else eps[t])
+            a, pd = agent.act_batch(self.observation(), eps=e, out_pd=self.rolls['pds'][:, self.slot])
             if rnn:
                 h, c = agent.batch_cells_before                   # (layers, n, hidden) each
                 self.rolls['cells'][:, self.slot, 0].copy_(h.permute(1, 0, 2))
@@ -746,7 +784,7 @@ class SyntheticVecEnv(object):
             K.epoch_forward([dict(net=actor, packed=pk, x=xn, out=mean, act=L.SMX_ACT_TANH)], None, ctrl, n)
             K.synth_act_env_step(self.state, self.init_state, mean, agent.model.log_var.view(-1), noise,
                                  None if eps is None else eps[t], self.t, self.episode_len, self.slot, self.rolls, zf, xn,
-                                 **self._mon(1))
+                                 **self._mon(1), **self._noi(1))
             self.slot += 1
             self._advance()
 

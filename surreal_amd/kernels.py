@@ -597,12 +597,30 @@ class HipKernels(object):
             q.done_reward, q.done_steps, q.capacity = L.ptr(m.done_reward), L.ptr(m.done_steps), int(m.capacity)
         return q
 
+    @staticmethod
+    def _noise_args(noise):
+        """struct smx_noise_stream of a (seed, actor_base, step) triple (DeviceNoise.at, surreal_amd/env/monitor.py):
+        the stream a launch forms its draws from when it gets no eps; None: the zero struct, no stream"""
+        q = L.NoiseStream()
+        if noise is not None:
+            q.seed, q.actor_base, q.step = (int(v) for v in noise)
+            q.enabled = 1
+        return q
+
+    def noise_fill(self, noise, out):
+        """out [steps, n, A] fp32 contiguous <- the draws a launch on the stream `noise` = (seed, actor_base, step)
+        forms for n actors over `steps` steps (smx_noise_fill_f32)"""
+        steps, n, A = out.shape
+        assert out.is_contiguous() and out.dtype == torch.float32
+        L.call('smx_noise_fill_f32', ctypes.byref(self._noise_args(noise)), steps, n, A, L.ptr(out), self._st())
+
     @classmethod
     def _synth_act_step(cls, state, init_state, mean, A, log_var, noise_scale, eps, t, episode_len, slot, rolls, zfilter,
-                        xn_out, monitor=None):
+                        xn_out, monitor=None, noise=None):
         n, D = state.shape
         p = L.SynthActStep()
         p.mon = cls._monitor_args(monitor, n)
+        p.noise = cls._noise_args(noise)
         p.state, p.init_state = L.ptr(state), L.ptr(init_state)
         p.mean, p.ld_mean, p.log_var = L.ptr(mean), (0 if mean is None else _row_stride(mean, A)), L.ptr(log_var)
         p.noise_scale, p.eps = L.ptr(noise_scale), L.ptr(eps)
@@ -619,20 +637,21 @@ class HipKernels(object):
         return p
 
     def synth_act_env_step(self, state, init_state, mean, log_var, noise_scale, eps, t, episode_len,
-                           slot, rolls, zfilter, xn_out, monitor=None):
+                           slot, rolls, zfilter, xn_out, monitor=None, noise=None):
         """acting head + env step + next observation's z-filter, one launch (see the header);
         rolls: dict obs / actions / rewards / dones [/ pds] or None; zfilter: ZFilter or None; monitor: a
-        DeviceEpisodeMonitor or None (every synth_* launch below takes one the same way)"""
+        DeviceEpisodeMonitor or None; noise: (seed, actor_base, step) of the stream the launch draws from when eps is
+        None, or None (every synth_* launch below that samples takes both the same way)"""
         p = self._synth_act_step(state, init_state, mean, mean.shape[1], log_var, noise_scale, eps, t, episode_len,
-                                 slot, rolls, zfilter, xn_out, monitor)
+                                 slot, rolls, zfilter, xn_out, monitor, noise)
         L.call('smx_synth_act_env_step_f32', ctypes.byref(p), self._st())
 
     def synth_act_env_step_head(self, W3, b3, h2, out_act, state, init_state, log_var, noise_scale, eps, t,
-                                episode_len, slot, rolls, zfilter, xn_out, monitor=None):
+                                episode_len, slot, rolls, zfilter, xn_out, monitor=None, noise=None):
         """the same launch with the policy's output layer folded in: mean = act(h2 . W3^T + b3) formed per actor"""
         A, H2 = W3.shape
         p = self._synth_act_step(state, init_state, None, A, log_var, noise_scale, eps, t, episode_len, slot, rolls,
-                                 zfilter, xn_out, monitor)
+                                 zfilter, xn_out, monitor, noise)
         L.call('smx_synth_act_env_step_head_f32', ctypes.byref(p), L.ptr(W3), L.ptr(b3), L.ptr(h2),
                _row_stride(h2, H2), H2, int(out_act), self._st())
 
@@ -641,7 +660,7 @@ class HipKernels(object):
 
     @classmethod
     def _roll_args(cls, q, net, packed, out_act, state, init_state, log_var, noise_scale, eps, t, episode_len, steps,
-                   zfilter, actors_per_workgroup, rolls=None, slot=0, monitor=None):
+                   zfilter, actors_per_workgroup, rolls=None, slot=0, monitor=None, noise=None):
         """fills the SynthRollout `q`: the network, the head, the z-filter, state and clock, and (rolls: dict as in
         synth_act_env_step, also 'obs_last' / 'cells') the rollout tables"""
         n = state.shape[0]
@@ -656,6 +675,7 @@ class HipKernels(object):
         q.state, q.init_state = L.ptr(state), L.ptr(init_state)
         q.actors_per_workgroup = int(actors_per_workgroup)
         q.mon = cls._monitor_args(monitor, n)
+        q.noise = cls._noise_args(noise)
         if rolls is not None:
             r = rolls
             q.rows_per_actor = r['obs'].shape[1] if 'obs' in r else (r['cells'].shape[1] if 'cells' in r else 1)
@@ -703,14 +723,14 @@ class HipKernels(object):
         p.pixel, p.pixel_next = L.ptr(tabs['pixel']), L.ptr(tabs['pixel_next'])
 
     def synth_rollout(self, net, packed, out_act, state, init_state, log_var, noise_scale, eps, t, episode_len,
-                      steps, slot, rolls, zfilter, actors_per_workgroup=0, monitor=None):
+                      steps, slot, rolls, zfilter, actors_per_workgroup=0, monitor=None, noise=None):
         """`steps` acting + environment steps of all actors in ONE launch (csrc/smx_rollout.hip): a workgroup owns
         4, 8 or 16 actors for the whole rollout (actors_per_workgroup; 0: the smallest whose grid fits the CUs once).
         packed: epoch_pack of `net`; eps [steps, n, A] or None; rolls as in synth_act_env_step ([n, T + 1, .]
         tables)."""
         p = L.SynthRollout()
         self._roll_args(p, net, packed, out_act, state, init_state, log_var, noise_scale, eps, t, episode_len, steps,
-                        zfilter, actors_per_workgroup, rolls or {}, slot, monitor)
+                        zfilter, actors_per_workgroup, rolls or {}, slot, monitor, noise)
         L.call('smx_synth_rollout_f32', ctypes.byref(p), self._st())
 
     def synth_lstm_rollout_supported(self, model):
@@ -730,7 +750,7 @@ class HipKernels(object):
 
     def synth_lstm_rollout(self, model, packed, lstm_packed, state, init_state, noise_scale, eps, t, episode_len, steps,
                            slot, rolls, zfilter, hN, cN, h0=None, c0=None, h_before=None, c_before=None,
-                           actors_per_workgroup=0, monitor=None):
+                           actors_per_workgroup=0, monitor=None, noise=None):
         """synth_rollout for a PPOModel with a one-layer LSTM stem, ONE launch (smx_synth_lstm_rollout_f32): packed =
         epoch_pack of model.actor, lstm_packed = lstm_rollout_pack of model.rnn; rolls may also hold 'cells'
         [n, R, 2, 1, Hl] (the state before every step); h0 / c0 (None: zeros), hN / cN, h_before / c_before: [n, Hl]
@@ -738,7 +758,7 @@ class HipKernels(object):
         r = rolls or {}
         p = L.SynthLstmRollout()
         self._roll_args(p.roll, model.actor, packed, L.SMX_ACT_TANH, state, init_state, model.log_var, noise_scale, eps,
-                        t, episode_len, steps, zfilter, actors_per_workgroup, r, slot, monitor)
+                        t, episode_len, steps, zfilter, actors_per_workgroup, r, slot, monitor, noise)
         self._lstm_args(p, model, lstm_packed, state.shape[0], hN, cN, h0, c0, h_before, c_before)
         if 'cells' in r:
             assert r['cells'].is_contiguous() and tuple(r['cells'].shape[2:]) == (2, 1, model.rnn_hidden_logical)
@@ -758,7 +778,8 @@ class HipKernels(object):
 
     def synth_ppo_window_rollout(self, model, packed, lstm_packed, state, init_state, noise_scale, eps, t, episode_len,
                                  steps, n_step, advance, carry, tables, cursor, zfilter, hN=None, cN=None, h0=None,
-                                 c0=None, h_before=None, c_before=None, actors_per_workgroup=0, monitor=None):
+                                 c0=None, h_before=None, c_before=None, actors_per_workgroup=0, monitor=None,
+                                 noise=None):
         """`steps` steps of synth_rollout (model.rnn None) / synth_lstm_rollout recorded as moving windows of n_step
         steps, `advance` apart, straight into a FIFO ring, ONE launch (smx_synth_ppo_window_rollout_f32).
         carry: the open windows {'obs' [n, n_step, D], 'actions' [n, n_step, A], 'rewards' [n, n_step], 'pds'
@@ -768,7 +789,7 @@ class HipKernels(object):
         h_before / c_before: [n, Hl] contiguous, Hl = model.rnn_hidden_logical"""
         p = L.SynthPpoWindowRollout()
         self._roll_args(p.base.roll, model.actor, packed, L.SMX_ACT_TANH, state, init_state, model.log_var, noise_scale,
-                        eps, t, episode_len, steps, zfilter, actors_per_workgroup, monitor=monitor)
+                        eps, t, episode_len, steps, zfilter, actors_per_workgroup, monitor=monitor, noise=noise)
         if model.if_rnn:
             self._lstm_args(p.base, model, lstm_packed, state.shape[0], hN, cN, h0, c0, h_before, c_before)
         for k, x in list(carry.items()) + list(tables.items()):
@@ -780,7 +801,7 @@ class HipKernels(object):
         return bool(self.lib.smx_synth_ddpg_rollout_supported(net.D, net.H1, net.H2, net.OUT))
 
     @classmethod
-    def _ddpg_args(cls, r, steps, net=None, packed=None, actors_per_workgroup=0, monitor=None):
+    def _ddpg_args(cls, r, steps, net=None, packed=None, actors_per_workgroup=0, monitor=None, noise=None):
         """smx_ddpg_rollout_t from the dict SyntheticVecEnv.ddpg_rollout_into builds: state / init_state [n, D],
         t, episode_len, n_step, noise_type, eps, sigmas (fp64), theta / dt / root_dt, gpow (fp64 [n_step]), ou (fp64
         [n, A]), carry_obs / carry_act / carry_rew, the ring tables by replay field name, cursor, capacity"""
@@ -802,32 +823,33 @@ class HipKernels(object):
         p.rewards, p.dones = L.ptr(tabs['rewards']), L.ptr(tabs['dones'])
         p.cursor, p.capacity = int(r['cursor']), int(tabs['obs'].shape[0])
         p.mon = cls._monitor_args(monitor, n)
+        p.noise = cls._noise_args(noise)
         return p
 
-    def synth_ddpg_rollout(self, net, packed, r, steps, actors_per_workgroup=0, monitor=None):
+    def synth_ddpg_rollout(self, net, packed, r, steps, actors_per_workgroup=0, monitor=None, noise=None):
         """`steps` DDPG acting + environment steps of all actors with their n-step transitions written into the ring
         tables, ONE launch (csrc/smx_rollout.hip).  packed: epoch_pack of the actor `net`; r: see _ddpg_args
         (eps [steps, n, A])"""
         if r['eps'] is not None:
             assert r['eps'].is_contiguous() and tuple(r['eps'].shape) == (steps, r['state'].shape[0], net.OUT)
-        p = self._ddpg_args(r, steps, net, packed, actors_per_workgroup, monitor)
+        p = self._ddpg_args(r, steps, net, packed, actors_per_workgroup, monitor, noise)
         L.call('smx_synth_ddpg_rollout_f32', ctypes.byref(p), self._st())
 
-    def synth_ddpg_step(self, r, mu, monitor=None):
+    def synth_ddpg_step(self, r, mu, monitor=None, noise=None):
         """one step of synth_ddpg_rollout given the actor's output mu [n, A] (r['eps']: this step's [n, A] draws;
         r['cursor']: where this step's closing transitions go)"""
         A = mu.shape[1]
-        p = self._ddpg_args(r, 1, monitor=monitor)
+        p = self._ddpg_args(r, 1, monitor=monitor, noise=noise)
         L.call('smx_synth_ddpg_step_f32', ctypes.byref(p), L.ptr(mu), _row_stride(mu, A), self._st())
 
-    def synth_ddpg_pixel_step(self, r, mu, monitor=None):
+    def synth_ddpg_pixel_step(self, r, mu, monitor=None, noise=None):
         """synth_ddpg_step for actors with a camera, in the same launch: r also holds hist uint8 [n, Hd, C, H, W] (the
         raw frames, the current step's in slot hist_pos), obs_pixel uint8 [n, S*C, H, W] (receives the stacked
         observation of the next step) and the ring tables 'pixel' / 'pixel_next' uint8 [capacity, S*C*H*W]
         (include/surreal_amd.h smx_synth_ddpg_pixel_step)"""
         p = L.DdpgPixelStep()
         self._camera_args(p, r, 1)
-        p.base = self._ddpg_args(r, 1, monitor=monitor)
+        p.base = self._ddpg_args(r, 1, monitor=monitor, noise=noise)
         L.call('smx_synth_ddpg_pixel_step', ctypes.byref(p), L.ptr(mu), _row_stride(mu, mu.shape[1]), self._st())
 
     @staticmethod
@@ -835,7 +857,7 @@ class HipKernels(object):
         """the actions smx_synth_ppo_pixel_window_step takes (one thread each, A <= SMX_PPO_PIXEL_STEP_MAX_A)"""
         return 0 < A <= L.SMX_PPO_PIXEL_STEP_MAX_A
 
-    def synth_ppo_pixel_window_step(self, r, mu, copy_workgroups=0, monitor=None):
+    def synth_ppo_pixel_window_step(self, r, mu, copy_workgroups=0, monitor=None, noise=None):
         """ONE step of the windowed PPO rollout for actors with a camera given the policy mean mu [n, A] (row-strided
         view allowed): head, environment step, carry rings, frame history and -- at a closing step -- the windows into
         the FIFO's ring from row r['cursor'] (include/surreal_amd.h smx_synth_ppo_pixel_window_step).  r: state /
@@ -871,6 +893,7 @@ class HipKernels(object):
         self._window_args(p, N, r['advance'], carry, tabs, r['cursor'])
         p.copy_workgroups = int(copy_workgroups)
         p.mon = self._monitor_args(monitor, n)
+        p.noise = self._noise_args(noise)
         L.call('smx_synth_ppo_pixel_window_step', ctypes.byref(p), L.ptr(mu), _row_stride(mu, A), self._st())
 
     def synth_env_step(self, state, init_state, actions, t, episode_len, slot, obs_roll, act_roll,
