@@ -1245,6 +1245,65 @@ int smx_synth_ddpg_rollout_f32(const smx_ddpg_rollout_t* args, smx_stream_t stre
  * the actor's output mu [n, A] (row stride ld_mu) from any forward pass */
 int smx_synth_ddpg_step_f32(const smx_ddpg_rollout_t* args, const float* mu, int64_t ld_mu, smx_stream_t stream);
 
+/* Parameter-space noise of the device actors (surreal/agent/param_noise.py): a population of perturbed actors, one per
+ * AGENT -- a group of consecutive actors that share one perturbation, as the actors of one reference agent process do
+ * (an agent here spans at least the 4 actors of one MFMA row block, where the reference's spans one environment).  The
+ * perturbation is a pure function: for global agent id g = agent_base + p, generation q and element i of the actor's flat
+ * parameters W1 [H1, D] | b1 | W2 [H2, H1] | b2 | W3 [OUT, H2] | b3 (row-major each: the order DDPGModel keeps them in)
+ *   z = component i & 3 of Philox4x32-10(counter = (g, q, i >> 2, 0x504E0001), key = (low32(seed), high32(seed))),
+ *       through the word -> normal conversion of struct smx_noise_stream (the same inline function; the fixed fourth
+ *       counter word keeps these blocks apart from the exploration stream's, whose fourth word is j >> 2 < 16)
+ *   perturbed_i = w_i + (float)sigma[p] * z            in fp32, the product first; the build does not contract
+ * `net` is read, never written.  g and q must lie in [0, 2^32) (SMX_E_SHAPE). */
+struct smx_param_noise {                   /* (by tag: no typedef) */
+    const smx_mlp3_t* net;                 /* the clean actor */
+    uint64_t seed;
+    int64_t agent_base;                    /* global id of agent 0 */
+    int64_t generation;
+    int32_t agents;                        /* P */
+    int32_t adaptive;                      /* refresh: != 0 adapts sigma first (when acts > 0) */
+    int64_t acts;                          /* refresh: act() calls since the last one */
+    double alpha, target;                  /* refresh, adaptive */
+    double* sigma;                         /* [P] fp64, in / out */
+    const double* dist;                    /* [P] fp64: the action distances (refresh, adaptive and acts > 0) */
+    float* packed_pop;                     /* refresh: [P, packed_stride] out, 16-byte aligned */
+    int64_t packed_stride;                 /* floats, >= smx_param_noise_copy_floats(..), a multiple of 4 */
+};
+/* floats of one agent's copy: [smx_epoch_pack_f32's layout of the actor | b1 | b2 | b3], rounded up to 64 */
+int64_t smx_param_noise_copy_floats(int32_t D, int32_t H1, int32_t H2, int32_t OUT);
+/* out [H1 D + H1 + H2 H1 + H2 + OUT H2 + OUT] <- agent p's perturbed flat parameters (packed_pop, dist, acts: not read) */
+int smx_param_noise_fill_f32(const struct smx_param_noise* pn, int32_t p, float* out, smx_stream_t stream);
+/* AdaptiveNormalParameterNoise.apply / NormalParameterNoise.apply for all P agents, no host synchronisation, at most two
+ * launches: with adaptive != 0 and acts > 0 first, in a launch of its own,
+ *   sigma[p] <- dist[p] / acts > target ? sigma[p] / alpha : sigma[p] * alpha      (fp64; param_noise.py:65-70)
+ * then the copy of every agent's perturbed actor into packed_pop + p * packed_stride: the five blocks of
+ * smx_epoch_pack_f32 bit for bit as it lays out a net holding the perturbed parameters (its padding exactly zero: noise
+ * goes to logical elements only), the perturbed biases b1 | b2 | b3 behind them, zeros up to copy_floats. */
+int smx_param_noise_refresh_f32(const struct smx_param_noise* pn, smx_stream_t stream);
+
+/* smx_synth_ddpg_rollout_f32 on a population: base.n = agents * actors_per_agent actors, actors_per_agent a multiple of
+ * 4; the workgroup that owns actors [a0, a0 + block) runs the actor's layers from the copy of agent a0 /
+ * actors_per_agent in packed_pop (smx_param_noise_refresh_f32's layout, biases included), so the block size must divide
+ * actors_per_agent: base.actors_per_workgroup = 0 takes the size smx_synth_ddpg_rollout_f32 would if it divides, else
+ * the next smaller of 16 / 8 / 4 that does; a forced size that does not divide: SMX_E_SHAPE.  Everything else is that
+ * launch, bit for bit: an agent's actors see what a launch over them alone would with base.packed = its copy.
+ * measure_step: -1, or the step of the call (< base.steps) at which the workgroup that holds an agent's FIRST actor also
+ * evaluates the clean actor (base.net, base.packed) on that actor's observation and stores
+ *   dist[p] = sqrt(sum_j ((double)(mu_j - clean_j))^2)      (fp64 sum, j ascending; mu, clean: the tanh outputs in fp32,
+ *                                                            before clip and noise: ddpg_agent.py:173-175, one action pair)
+ * Other steps and other workgroups do nothing for it; dist is written only by a call that measures. */
+struct smx_ddpg_population_rollout {       /* (by tag: no typedef) */
+    smx_ddpg_rollout_t base;
+    const float* packed_pop;               /* [agents, packed_stride] */
+    int64_t packed_stride;
+    int32_t actors_per_agent, agents;
+    int32_t measure_step, reserved;
+    double* dist;                          /* [agents] fp64 (measure_step >= 0) */
+};
+/* the block size the launch takes for n actors (0: refused, SMX_E_SHAPE there); forced = base.actors_per_workgroup */
+int32_t smx_synth_ddpg_population_block(int32_t n, int32_t actors_per_agent, int32_t forced);
+int smx_synth_ddpg_population_rollout_f32(const struct smx_ddpg_population_rollout* args, smx_stream_t stream);
+
 /* The same step for actors with a camera (the reference's pixel DDPG configurations, ddpg_configs.py:176-228:
  * FrameStackWrapper in front of a CNN perception): smx_synth_ddpg_step_f32 on args->base (mu [n, A] = the actor's
  * output on the perception of obs_pixel), and the frames in the same launch.  F = C*H*W bytes per frame, S =

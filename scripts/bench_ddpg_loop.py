@@ -9,6 +9,11 @@ staging buffers and learn().
   2. the loop: one rollout chunk, then `--learn-iters` learn iterations at batch 512 sampled with
      sample_batch(512, out=learner.staging_fields(512)): env-steps/s and learner samples/s over the whole loop.
 
+With --calls N: only N single `ddpg_rollout_into` calls, each as a user makes it and timed by itself -> one line with
+their median (and, with --param-noise, the time of DeviceParamNoise.refresh()).  --param-noise attaches per-agent
+parameter-space noise (attach_param_noise, --actors-per-agent K actors an agent): the population launch; it needs --calls,
+since the per-step path and the plain kernel's forced blocks have no such launch.
+
 Prints one JSON line per measurement (and a summary line)."""
 import argparse
 import json
@@ -51,12 +56,22 @@ def main():
     ap.add_argument('--device-noise', action='store_true',
                     help='draw the exploration noise inside the launches from the env\'s Philox stream (attach_noise): no '
                          'eps tensor is made or read')
+    ap.add_argument('--param-noise', action='store_true',
+                    help='attach per-agent parameter-space noise (adaptive_normal): every agent acts from its own perturbed '
+                         'copy of the actor, made and measured on the device; needs --calls')
+    ap.add_argument('--actors-per-agent', type=int, default=4, help='actors that share one perturbation (a multiple of 4)')
+    ap.add_argument('--calls', type=int, default=0, help='time this many single rollout calls, print their median and stop')
+    ap.add_argument('--label', default='', help='copied into the --calls line')
     args = ap.parse_args()
+    if args.param_noise and not args.calls:
+        ap.error('--param-noise measures single calls: give --calls N')
     n, T, D, A = args.actors, args.steps, args.obs_dim, args.action_dim
     H1, H2 = args.hidden
     lc = ddpg_learner_config()
     lc.model.actor_fc_hidden_sizes = [H1, H2]
     lc.algo.exploration.noise_type = args.noise
+    if args.param_noise:
+        lc.algo.exploration.param_noise_type = 'adaptive_normal'
     lc.replay.memory_size = args.capacity
     lc.replay.batch_size = args.batch
     ec, sc = ddpg_env_config(D, A, num_agents=n), ddpg_session_config()
@@ -73,6 +88,8 @@ def main():
     if args.device_noise:
         venv.attach_noise(seed=1)
     eps = None if args.device_noise else torch.randn(T, n, A, device='cuda')
+    if args.calls:
+        return single_calls(args, agent, venv, UniformReplay(lc, ec, sc), eps)
     results = {}
     for path in ('persistent', 'per_step'):
         replay = UniformReplay(lc, ec, sc)
@@ -152,6 +169,38 @@ def main():
     speedup = results['per_step']['ms_per_rollout'] / results['persistent']['ms_per_rollout']
     print(json.dumps({'what': 'summary', 'persistent_ms': results['persistent']['ms_per_rollout'],
                       'per_step_ms': results['per_step']['ms_per_rollout'], 'persistent_speedup': speedup}), flush=True)
+
+
+def timed(f, k):
+    """k calls of f, each between its own pair of events -> their times in ms"""
+    ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(k)]
+    torch.cuda.synchronize()
+    for e0, e1 in ev:
+        e0.record()
+        f()
+        e1.record()
+    torch.cuda.synchronize()
+    return sorted(e0.elapsed_time(e1) for e0, e1 in ev)
+
+
+def single_calls(args, agent, venv, replay, eps):
+    n, T = args.actors, args.steps
+    pn = venv.attach_param_noise(agent, seed=2, actors_per_agent=args.actors_per_agent) if args.param_noise else None
+    call = lambda: venv.ddpg_rollout_into(agent, replay, T, eps=eps)  # noqa: E731
+    for _ in range(3):
+        call()
+    ms = timed(call, args.calls)
+    line = {'what': 'ddpg_rollout_calls', 'label': args.label, 'actors': n, 'steps': T, 'calls': args.calls,
+            'param_noise': bool(pn), 'actors_per_agent': args.actors_per_agent if pn else None,
+            'agents': pn.agents if pn else None, 'median_ms': round(ms[len(ms) // 2], 4),
+            'fastest_tenth_ms': round(ms[len(ms) // 10], 4), 'slowest_ms': round(ms[-1], 4),
+            'env_steps_per_s': n * T / (ms[len(ms) // 2] / 1e3)}
+    if pn is not None:
+        pn.refresh()
+        rs = timed(pn.refresh, 20)
+        line.update(refresh_median_ms=round(rs[len(rs) // 2], 4), refresh_slowest_ms=round(rs[-1], 4),
+                    population_mb=round(pn.pop.numel() * 4 / 1e6, 2))
+    print(json.dumps(line), flush=True)
 
 
 if __name__ == '__main__':

@@ -196,6 +196,20 @@ class DdpgRollout(Structure):
                 ('cursor', c_int64), ('capacity', c_int64), ('noise', NoiseStream), ('mon', EpisodeMonitor)]
 
 
+class ParamNoise(Structure):
+    """struct smx_param_noise"""
+    _fields_ = [('net', POINTER(Mlp3)), ('seed', c_uint64), ('agent_base', c_int64), ('generation', c_int64),
+                ('agents', c_int32), ('adaptive', c_int32), ('acts', c_int64), ('alpha', c_double), ('target', c_double),
+                ('sigma', c_void_p), ('dist', c_void_p), ('packed_pop', c_void_p), ('packed_stride', c_int64)]
+
+
+class DdpgPopulationRollout(Structure):
+    """struct smx_ddpg_population_rollout"""
+    _fields_ = [('base', DdpgRollout), ('packed_pop', c_void_p), ('packed_stride', c_int64),
+                ('actors_per_agent', c_int32), ('agents', c_int32), ('measure_step', c_int32), ('reserved', c_int32),
+                ('dist', c_void_p)]
+
+
 class DdpgPixelStep(Structure):
     """struct smx_ddpg_pixel_step"""
     _fields_ = [('base', DdpgRollout), ('C', c_int32), ('H', c_int32), ('W', c_int32), ('frame_stacks', c_int32),
@@ -404,6 +418,11 @@ _SIGS = {
     'smx_synth_ddpg_rollout_f32': (c_int32, [POINTER(DdpgRollout), _P]),
     'smx_synth_ddpg_step_f32': (c_int32, [POINTER(DdpgRollout), _P, c_int64, _P]),
     'smx_synth_ddpg_pixel_step': (c_int32, [POINTER(DdpgPixelStep), _P, c_int64, _P]),
+    'smx_param_noise_copy_floats': (c_int64, [c_int32, c_int32, c_int32, c_int32]),
+    'smx_param_noise_fill_f32': (c_int32, [POINTER(ParamNoise), c_int32, _P, _P]),
+    'smx_param_noise_refresh_f32': (c_int32, [POINTER(ParamNoise), _P]),
+    'smx_synth_ddpg_population_block': (c_int32, [c_int32, c_int32, c_int32]),
+    'smx_synth_ddpg_population_rollout_f32': (c_int32, [POINTER(DdpgPopulationRollout), _P]),
     'smx_synth_ppo_pixel_window_step': (c_int32, [POINTER(SynthPpoPixelWindowStep), _P, c_int64, _P]),
     'smx_xchg_bytes': (c_int64, [c_int64, c_int32]),
     'smx_xchg_alloc': (c_int32, [c_int64, c_double, POINTER(c_void_p), POINTER(c_int32), _P]),

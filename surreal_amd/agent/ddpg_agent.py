@@ -35,6 +35,7 @@ class DDPGAgent(Agent):
         self.frame_stack_concatenate_on_env = self.env_config.get('frame_stack_concatenate_on_env', True)
         ex = self.learner_config.algo.exploration
         self.param_noise = None                              # ddpg_agent.py:68-72
+        self.device_param_noise = False      # SyntheticVecEnv.attach_param_noise: the perturbation is made on the device
         self.param_noise_type = ex.param_noise_type
         self.param_noise_sigma = ex.param_noise_sigma
         self.param_noise_alpha = ex.param_noise_alpha
@@ -83,7 +84,7 @@ class DDPGAgent(Agent):
 
     def on_parameter_fetched(self, params, info):         # ddpg_agent.py:149-153
         params = super().on_parameter_fetched(params, info)
-        if self.param_noise:
+        if self.param_noise and not self.device_param_noise:
             if any(torch.is_tensor(v) for sd in params.values() for v in sd.values()):
                 # the in-process hand-off passes device snapshots: noise acts on their wire form
                 # ({module: {name: ndarray}}, module_dict.py:34-45)

@@ -893,20 +893,10 @@ __device__ __forceinline__ void pack_word(const PackArgs& P, long i) {
 #pragma unroll
     for (int k = 1; k < MAX_EJOBS; ++k) pi += (k < P.count && i >= P.n[k].base) ? 1 : 0;
     const PackNet N = P.n[pi];
-    long w = i - N.base;
-    int bn = 0;
-#pragma unroll
-    for (int k = 1; k < 5; ++k) bn += (w >= pack_off(N.D, N.H1, N.H2, N.OUT, k)) ? 1 : 0;
-    w -= pack_off(N.D, N.H1, N.H2, N.OUT, bn);
-    const float* W = bn == 0 ? N.W1 : ((bn == 1 || bn == 3) ? N.W2 : N.W3);
-    const bool tr = bn >= 3;
-    const int M = bn == 0 ? N.H1 : (bn == 1 ? N.H2 : (bn == 2 ? N.OUT : (bn == 3 ? N.H1 : N.H2)));
-    const int K = bn == 0 ? N.D : (bn == 1 ? N.H1 : (bn == 2 ? N.H2 : (bn == 3 ? N.H2 : N.OUT)));
-    const int C2 = pack_chunks(K);
-    const int lane = (int)(w & 63), half = (int)((w >> 6) & 1);
-    const long tc = w >> 7;
-    const int c = (int)(tc % C2), t = (int)(tc / C2);
-    const int m = 16 * t + (lane & 15), k = 32 * c + 8 * (lane >> 4) + 4 * half;
+    const PackSrc s = pack_decode(N.D, N.H1, N.H2, N.OUT, i - N.base);
+    const float* W = s.bn == 0 ? N.W1 : ((s.bn == 1 || s.bn == 3) ? N.W2 : N.W3);
+    const bool tr = s.tr;
+    const int M = s.M, K = s.K, m = s.m, k = s.k;
     float v[4] = {0.f, 0.f, 0.f, 0.f};
     if (m < M) {
 #pragma unroll

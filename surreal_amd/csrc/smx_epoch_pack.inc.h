@@ -27,3 +27,34 @@ __host__ __device__ inline long pack_pos(int K, int m, int k) {
     const long word = ((long)((m >> 4) * pack_chunks(K) + (k >> 5)) * 2 + ((kk >> 2) & 1)) * 64 + (kk >> 3) * 16 + (m & 15);
     return word * 4 + (kk & 3);
 }
+
+// 16-byte word w of a net's copy: block bn, and the four elements X[m][k .. k + 3] of its matrix X [M, K] it holds
+// (zeros past M or K) -- the layer's weights, or (tr) their transpose: X[m][k] = W[k][m], W [K, M]
+struct PackSrc {
+    int bn, M, K, m, k;
+    bool tr;
+};
+__host__ __device__ inline PackSrc pack_decode(int D, int H1, int H2, int OUT, long w) {
+    PackSrc s;
+    s.bn = 0;
+#pragma unroll
+    for (int b = 1; b < 5; ++b) s.bn += (w >= pack_off(D, H1, H2, OUT, b)) ? 1 : 0;
+    w -= pack_off(D, H1, H2, OUT, s.bn);
+    s.tr = s.bn >= 3;
+    s.M = s.bn == 0 ? H1 : (s.bn == 1 ? H2 : (s.bn == 2 ? OUT : (s.bn == 3 ? H1 : H2)));
+    s.K = s.bn == 0 ? D : (s.bn == 1 ? H1 : (s.bn == 2 ? H2 : (s.bn == 3 ? H2 : OUT)));
+    const int C2 = pack_chunks(s.K);
+    const int lane = (int)(w & 63), half = (int)((w >> 6) & 1);
+    const long tc = w >> 7;
+    const int c = (int)(tc % C2), t = (int)(tc / C2);
+    s.m = 16 * t + (lane & 15);
+    s.k = 32 * c + 8 * (lane >> 4) + 4 * half;
+    return s;
+}
+
+// One agent's copy in a population of perturbed actors (smx_param_noise_refresh_f32 writes them, the population
+// rollout of smx_rollout.hip reads them): [the net's copy above | b1 | b2 | b3], rounded up to 64 floats
+__host__ __device__ inline long pop_bias_off(int D, int H1, int H2, int OUT) { return 4 * pack_off(D, H1, H2, OUT, 5); }
+__host__ __device__ inline long pop_copy_floats(int D, int H1, int H2, int OUT) {
+    return (pop_bias_off(D, H1, H2, OUT) + H1 + H2 + OUT + 63) & ~63L;
+}

@@ -35,17 +35,22 @@ __device__ __forceinline__ void philox4x32_10(uint32_t (&c)[4], uint32_t k0, uin
 // sqrt(-2 ln 2^-25) ~ 5.887.  The accurate library functions, no fast intrinsics; the build does not contract: every
 // caller gets the same bits.  Each (actor, component) lane runs its own ten rounds (a step's ~200 VALU instructions
 // against the 32 k cycles of its layers).
-__device__ __forceinline__ float noise_normal(uint64_t seed, uint32_t g, uint64_t s, int j) {
-    uint32_t c[4] = {g, (uint32_t)s, (uint32_t)(s >> 32), (uint32_t)j >> 2};
-    philox4x32_10(c, (uint32_t)seed, (uint32_t)(seed >> 32));
+// the word -> normal conversion above on a finished Philox block x: component j & 3 of its four normals
+__device__ __forceinline__ float philox_normal(const uint32_t (&x)[4], int j) {
     const bool hi = (j & 2) != 0;
-    const uint32_t x0 = hi ? c[2] : c[0], x1 = hi ? c[3] : c[1];
+    const uint32_t x0 = hi ? x[2] : x[0], x1 = hi ? x[3] : x[1];
     const float u0 = ((float)(x0 >> 8) + 0.5f) * 0x1p-24f;
     const float u1 = ((float)(x1 >> 8) + 0.5f) * 0x1p-24f;
     const float r = sqrtf(-2.0f * logf(u0));
     float sn, cs;
     sincospif(2.0f * u1, &sn, &cs);
     return (j & 1) ? r * sn : r * cs;
+}
+
+__device__ __forceinline__ float noise_normal(uint64_t seed, uint32_t g, uint64_t s, int j) {
+    uint32_t c[4] = {g, (uint32_t)s, (uint32_t)(s >> 32), (uint32_t)j >> 2};
+    philox4x32_10(c, (uint32_t)seed, (uint32_t)(seed >> 32));
+    return philox_normal(c, j);
 }
 
 // the draw of local actor a at the call's k-th step, component j
@@ -64,4 +69,16 @@ __device__ __forceinline__ float noise_pick(const float* eps, size_t i, const sm
 // what the entry points ask of a stream over n actors: every global actor id in [0, 2^32) (SMX_E_SHAPE)
 inline bool noise_shape_ok(const smx_noise_stream& N, long long n) {
     return !N.enabled || (N.actor_base >= 0 && N.actor_base + n <= (1LL << 32));
+}
+
+// ---- parameter-space noise (struct smx_param_noise, include/surreal_amd.h) -------------------------------------------
+// The standard normal of (seed, global agent id g < 2^32, generation q < 2^32, element i of the actor's flat parameters
+// W1 | b1 | W2 | b2 | W3 | b3, each row-major: the order DDPGModel keeps them in): component i & 3 of the block at counter
+// (g, q, i >> 2, PARAM_NOISE_TAG) under the same key, through philox_normal.  The exploration stream's fourth counter
+// word is j >> 2 < 16 (at most 64 action components), so the two never share a block, whatever the seed.
+constexpr uint32_t PARAM_NOISE_TAG = 0x504E0001u;
+__device__ __forceinline__ float param_noise_normal(uint64_t seed, uint32_t g, uint32_t q, uint32_t i) {
+    uint32_t c[4] = {g, q, i >> 2, PARAM_NOISE_TAG};
+    philox4x32_10(c, (uint32_t)seed, (uint32_t)(seed >> 32));
+    return philox_normal(c, (int)(i & 3u));
 }

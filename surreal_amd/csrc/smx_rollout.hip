@@ -19,6 +19,10 @@
 //                               surreal/env/exp_sender_wrapper.py:72-112 ExpSenderWrapperSSARNStepBootstrap, which run on
 //                               the host there) recorded straight into the uniform replay's ring: ddpg_rollout_kernel on
 //                               the 4-row loop at every block size.
+//   smx_synth_ddpg_population_rollout_f32   the same launch over a population of perturbed actors (parameter-space
+//                               noise, smx_param_noise.hip): ddpg_rollout_kernel<RG, NT, true>, each workgroup's layers run
+//                               from the copy of the agent its actors belong to; one step of the call can measure the
+//                               agents' action distance against the clean actor.
 //   smx_synth_ddpg_step_f32     one DDPG step for all actors given the actor's output mu [n, A] from any forward
 //                               (LayerNorm actors, unsupported shapes; with smx_epoch_forward_f32 the persistent kernel's
 //                               two-launch reference).
@@ -51,6 +55,7 @@
 // rounds and one Box-Muller element per (actor, component) lane and step), else samples nothing.
 #include "smx_common.h"
 #include <string.h>
+#include <type_traits>
 
 namespace {
 #include "smx_epoch_pack.inc.h"
@@ -133,6 +138,14 @@ struct DArgs : RollBase {
     float *cobs, *cact, *crew;
     float *obs, *obs_next, *act, *rew, *done;
     long long cursor, capacity;
+};
+
+// the population rollout (ddpg_rollout_kernel<RG, NT, true>): every agent -- apa consecutive actors -- has its own copy
+struct PopArgs : DArgs {
+    RollBase popnet;                            // what layers4 reads, the weights and biases those of AGENT 0's copy
+    long long stride;                           // floats from one agent's copy to the next (pop_copy_floats at least)
+    int apa, measure_step;                      // actors per agent; the step that measures the action distance or -1
+    double* dist;                               // [agents]
 };
 
 // ---- once per launch: clear the tiles (their padding columns and rows must read as zeros, the action tile's unused
@@ -299,16 +312,17 @@ struct PreLayer {
 // per pass: bias, then ReLU on the hidden layers and act_f(., out_act) on the output layer.  The layer sums of a row do
 // not depend on RG or NT (k ascending within each kq class, then the classes meet).  after(l) follows layer l's barrier.
 // Layer 0 reads K0 inputs from column in0 on of the x tile (a plain MLP: the observation, in0 = 0, K0 = D).  GATE: layer
-// -1 = `pre` runs first, from column 0 of the x tile (after(-1) then follows its barrier).
+// -1 = `pre` runs first, from column 0 of the x tile (after(-1) then follows its barrier).  shift: floats added to every
+// weight and bias pointer (the population rollout: from agent 0's copy to the workgroup's agent's).
 template <int RG, int NT, bool GATE = false, typename After>
 __device__ __forceinline__ void layers4(const RollBase& G, float* sm, int nl, int out_act, int wv, int lane, After after,
-                                        int in0, int K0, const PreLayer& pre = PreLayer{}) {
+                                        int in0, int K0, const PreLayer& pre = PreLayer{}, size_t shift = 0) {
     const int fm = lane & 15, kq = lane >> 4;
 #pragma unroll 1
     for (int l = GATE ? -1 : 0; l < nl; ++l) {
         const bool pl = GATE && l < 0;
-        const float* Wp = pl ? pre.W : (l == 0 ? G.P1 : (l == 1 ? G.P2 : G.P3));
-        const float* bias = pl ? pre.bias : (l == 0 ? G.b1 : (l == 1 ? G.b2 : G.b3));
+        const float* Wp = (pl ? pre.W : (l == 0 ? G.P1 : (l == 1 ? G.P2 : G.P3))) + shift;
+        const float* bias = (pl ? pre.bias : (l == 0 ? G.b1 : (l == 1 ? G.b2 : G.b3))) + shift;
         const int H = pl ? pre.H : (l == 0 ? G.H1 : (l == 1 ? G.H2 : G.A));
         const int K = pl ? pre.K : (l == 0 ? K0 : (l == 1 ? G.H1 : G.H2));
         const float* in_lds = sm + (pl ? 0 : (l == 0 ? in0 : (l == 1 ? G.off_h1 : G.off_h2)));
@@ -918,8 +932,12 @@ __device__ __forceinline__ long long ring_row(const DArgs& G, int kemit, long a)
 
 // RG row groups of four actors per workgroup; NT feature tiles a wave carries per pass.  Every block size gives the same
 // bits (layers4).
-template <int RG, int NT>
-__global__ __launch_bounds__(RNTH) void ddpg_rollout_kernel(DArgs G) {
+// POP (smx_synth_ddpg_population_rollout_f32; 4 RG divides the actors per agent): the same body with the layers run from
+// the agent's copy.  At step measure_step the workgroups that hold an agent's first actor (a workgroup-uniform branch:
+// layers4 has barriers) first run the clean actor -- G's own -- on the same x tile and keep that actor's outputs, then
+// store the L2 distance of the two outputs of that one actor.
+template <int RG, int NT, bool POP = false>
+__global__ __launch_bounds__(RNTH) void ddpg_rollout_kernel(std::conditional_t<POP, PopArgs, DArgs> G) {
     constexpr int RB = 4 * RG;                       // actors per workgroup
     extern __shared__ float sm[];
     const int tid = threadIdx.x, lane = tid & 63;
@@ -944,13 +962,39 @@ __global__ __launch_bounds__(RNTH) void ddpg_rollout_kernel(DArgs G) {
     SMX_LDS_BARRIER();
 
     const bool noisy = noise_on(G.eps, G.nstream);     // (never with SMX_DDPG_NOISE_NONE: common_args)
+    // (POP) floats from agent 0's copy, which G.popnet points into, to the copy of this workgroup's agent
+    size_t shift = 0;
+    if constexpr (POP) shift = (size_t)(E.row0 / G.apa) * G.stride;
     int tau = G.t0, kemit = 0;
 #pragma unroll 1
     for (int step = 0; step < G.steps; ++step) {
         float ev = 0.f;                              // this step's draw, requested before the layers
         if (noisy && head) ev = noise_pick(G.eps, ((size_t)step * G.n + ha) * A + hj, G.nstream, ha, step, hj);
+        bool measure = false;
+        float clean = 0.f;
+        if constexpr (POP) {
+            measure = step == G.measure_step && E.row0 % G.apa == 0;
+            if (measure) {
+                layers4<RG, NT>(G, sm, 3, SMX_ACT_TANH, wv, lane, [](int) {}, 0, G.D);
+                // (row 0's outputs; the layers below write the output tile again only behind two more barriers)
+                if (tid < A) clean = outs[tid];
+            }
+        }
         // ---- the actor's three layers (ReLU, ReLU, tanh) --------------------------------------------------------
-        layers4<RG, NT>(G, sm, 3, SMX_ACT_TANH, wv, lane, [](int) {}, 0, G.D);
+        if constexpr (POP) layers4<RG, NT>(G.popnet, sm, 3, SMX_ACT_TANH, wv, lane, [](int) {}, 0, G.D, PreLayer{}, shift);
+        else layers4<RG, NT>(G, sm, 3, SMX_ACT_TANH, wv, lane, [](int) {}, 0, G.D);
+        if constexpr (POP) {
+            if (measure && wv == 0) {
+                // ddpg_agent.py:173-175 on the agent's first actor: the fp32 differences squared and summed in fp64
+                const float d = tid < A ? outs[tid] - clean : 0.f;
+                double q = 0.0;
+                for (int j = 0; j < A; ++j) {
+                    const double dj = (double)__shfl(d, j);
+                    q += dj * dj;
+                }
+                if (lane == 0) G.dist[E.row0 / G.apa] = sqrt(q);
+            }
+        }
         const bool emit = tau >= N - 1;
         const int slot = tau % N, jslot = (tau + 1) % N;   // (transition j = tau - N + 1 sits in slot j % N)
         const bool done = (tau + 1 >= G.episode_len);
@@ -1454,6 +1498,15 @@ int pick_block(int forced, int n) {
     return 16;
 }
 
+// the same for a population whose agents span apa actors (a multiple of 4): a block never spans two agents, so its size
+// divides apa -- the automatic choice steps down from pick_block's until it does; a forced size that does not: 0
+int pick_population_block(int forced, int n, int apa) {
+    int c = pick_block(forced, n);
+    if (forced) return apa % c == 0 ? c : 0;
+    while (apa % c) c /= 2;
+    return c;
+}
+
 // one workgroup of RNTH lanes per rb actors, with LDS for one workgroup per CU; each kernel's dynamic-LDS limit is raised
 // at its first launch
 template <auto K, typename Args>
@@ -1760,23 +1813,65 @@ extern "C" int32_t smx_synth_ddpg_rollout_supported(int32_t D, int32_t H1, int32
     return supported(D, H1, H2, A, /*mma16=*/false, /*split_out=*/false, /*ztables=*/false);
 }
 
-extern "C" int smx_synth_ddpg_rollout_f32(const smx_ddpg_rollout_t* a, smx_stream_t stream) {
+// what both persistent DDPG entry points ask of the block and take from it (the block size and the launch are theirs)
+static int persistent_ddpg_args(const smx_ddpg_rollout_t* a, DArgs& G) {
     SMX_REQUIRE(a && a->net && a->packed, SMX_E_NULL);
     const smx_mlp3_t& net = *a->net;
     SMX_REQUIRE(smx_synth_ddpg_rollout_supported(net.D, net.H1, net.H2, net.OUT), SMX_E_UNSUPPORTED);
     SMX_REQUIRE(net.D == a->D && net.OUT == a->A && a->steps > 0, SMX_E_SHAPE);
     SMX_REQUIRE(block_ok(a->actors_per_workgroup), SMX_E_SHAPE);
     SMX_REQUIRE(aligned_ok(a->packed, net.b1, nullptr), SMX_E_ALIGN);
-    DArgs G;
     const int rc = common_args(a, G);
     if (rc != SMX_OK) return rc;
     // two workgroups must never write the same ring row: all n m rows of the call are distinct
     const long long m = closing_steps(a->t, a->steps, a->episode_len, [&](int t) { return t >= a->n_step - 1; });
     SMX_REQUIRE((long long)a->n * m <= a->capacity, SMX_E_SHAPE);
     net_fields(net, a->packed, G);
+    return SMX_OK;
+}
+
+extern "C" int smx_synth_ddpg_rollout_f32(const smx_ddpg_rollout_t* a, smx_stream_t stream) {
+    DArgs G;
+    const int rc = persistent_ddpg_args(a, G);
+    if (rc != SMX_OK) return rc;
     const int rb = pick_block(a->actors_per_workgroup, a->n);
     const int lds = carve(G, rb, /*mma16=*/false, /*split_out=*/false, /*ztables=*/false, G.D);
     return launch<ddpg_rollout_kernel<1, 3>, ddpg_rollout_kernel<2, 3>, ddpg_rollout_kernel<4, 2>>(G, rb, lds, stream);
+}
+
+extern "C" int32_t smx_synth_ddpg_population_block(int32_t n, int32_t actors_per_agent, int32_t forced) {
+    if (n <= 0 || actors_per_agent <= 0 || actors_per_agent % 4 || !block_ok(forced)) return 0;
+    return pick_population_block(forced, n, actors_per_agent);
+}
+
+extern "C" int smx_synth_ddpg_population_rollout_f32(const struct smx_ddpg_population_rollout* args, smx_stream_t stream) {
+    SMX_REQUIRE(args && args->packed_pop, SMX_E_NULL);
+    const smx_ddpg_rollout_t* a = &args->base;
+    PopArgs G;
+    memset(&G, 0, sizeof(G));
+    const int rc = persistent_ddpg_args(a, G);
+    if (rc != SMX_OK) return rc;
+    const smx_mlp3_t& net = *a->net;
+    const int apa = args->actors_per_agent;
+    SMX_REQUIRE(apa > 0 && apa % 4 == 0 && args->agents > 0 && (long long)args->agents * apa == a->n, SMX_E_SHAPE);
+    SMX_REQUIRE(args->measure_step >= -1 && args->measure_step < a->steps, SMX_E_SHAPE);
+    SMX_REQUIRE(args->measure_step < 0 || args->dist, SMX_E_NULL);
+    SMX_REQUIRE(args->packed_stride >= pop_copy_floats(net.D, net.H1, net.H2, net.OUT) && args->packed_stride % 4 == 0,
+                SMX_E_SHAPE);
+    SMX_REQUIRE(((uintptr_t)args->packed_pop & 15) == 0, SMX_E_ALIGN);
+    const int rb = pick_population_block(a->actors_per_workgroup, a->n, apa);
+    SMX_REQUIRE(rb > 0, SMX_E_SHAPE);
+    G.stride = args->packed_stride; G.apa = apa; G.measure_step = args->measure_step; G.dist = args->dist;
+    const int lds = carve(G, rb, /*mma16=*/false, /*split_out=*/false, /*ztables=*/false, G.D);
+    // agent 0's copy in the same tiles: its packed blocks as net_fields lays a net's out, its biases behind them
+    G.popnet = G;
+    smx_mlp3_t copy0 = net;
+    copy0.b1 = args->packed_pop + pop_bias_off(net.D, net.H1, net.H2, net.OUT);
+    copy0.b2 = copy0.b1 + net.H1;
+    copy0.b3 = copy0.b2 + net.H2;
+    net_fields(copy0, args->packed_pop, G.popnet);
+    return launch<ddpg_rollout_kernel<1, 3, true>, ddpg_rollout_kernel<2, 3, true>, ddpg_rollout_kernel<4, 2, true>>(
+        G, rb, lds, stream);
 }
 
 extern "C" int smx_synth_ddpg_step_f32(const smx_ddpg_rollout_t* a, const float* mu, int64_t ld_mu, smx_stream_t stream) {

@@ -7,4 +7,5 @@ from .adapters import (ObsTransform, GymAdapter, RobosuiteWrapper, DMControlAdap
                        ObservationConcatenationWrapper, TransposeWrapper, GrayscaleWrapper,
                        make_env, make_env_config, wrap_gym, wrap_robosuite, wrap_dm_control)
 from .monitor import (EpisodeMonitor, ConsoleMonitor, TrainingTensorplexMonitor,
-                      EvalTensorplexMonitor, DeviceEpisodeMonitor, DeviceTrainingMonitor, DeviceNoise)
+                      EvalTensorplexMonitor, DeviceEpisodeMonitor, DeviceTrainingMonitor, DeviceNoise,
+                      DeviceParamNoise)

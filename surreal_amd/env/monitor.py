@@ -300,6 +300,91 @@ class DeviceNoise(object):
         return out
 
 
+class DeviceParamNoise(object):
+    """Parameter-space noise (agent/param_noise.py: 'normal' / 'adaptive_normal') for the actors of a SyntheticVecEnv, on
+    the device.  The env's n actors form n / actors_per_agent AGENTS of consecutive actors that share one perturbation,
+    as the actors of one reference agent process do -- an agent here spans at least 4 actors (one MFMA row block) where
+    the reference's spans one environment.  Agent p (global id agent_base + p) acts from its own perturbed copy of the
+    agent's actor, element i of the flat parameters W1 | b1 | W2 | b2 | W3 | b3 being w_i + (float)sigma[p] *
+    z(seed, agent_base + p, generation, i): a pure function (struct smx_param_noise, include/surreal_amd.h).  Made by
+    SyntheticVecEnv.attach_param_noise(agent, seed, actors_per_agent, agent_base).
+
+    On the device: sigma fp64 [P], dist fp64 [P] (the action distance of each agent's first actor, written by the
+    rollout launch at its measuring step), pop fp32 [P, copy floats] (the packed copies the launch reads).  On the host,
+    readable and settable: generation (the perturbation in pop), acts (act() calls per actor since the last refresh).
+
+    refresh() is on_parameter_fetched: call it whenever the agent's parameters changed."""
+
+    def __init__(self, agent, seed, actors_per_agent, agent_base, n, kernels, device):
+        import torch
+        self.type = agent.param_noise_type
+        if self.type not in ('normal', 'adaptive_normal'):
+            raise ValueError('DeviceParamNoise: the agent\'s param_noise_type is %r; \'normal\' or \'adaptive_normal\''
+                             % (self.type,))
+        self.seed, self.agent_base, self.actors_per_agent = int(seed), int(agent_base), int(actors_per_agent)
+        if not 0 <= self.seed < 1 << 64:
+            raise ValueError('DeviceParamNoise: seed must fit 64 bits, got %r' % (seed,))
+        if self.actors_per_agent <= 0 or self.actors_per_agent % 4 or int(n) % self.actors_per_agent:
+            raise ValueError('DeviceParamNoise: actors_per_agent must be a multiple of 4 that divides the %d actors, got %d'
+                             % (n, self.actors_per_agent))
+        self.agents = int(n) // self.actors_per_agent
+        if self.agent_base < 0 or self.agent_base + self.agents > 1 << 32:
+            raise ValueError('DeviceParamNoise: global agent ids %d .. %d leave [0, 2^32)'
+                             % (self.agent_base, self.agent_base + self.agents - 1))
+        self.agent, self.K, self.device = agent, kernels, device
+        self.adaptive = self.type == 'adaptive_normal'
+        self.alpha, self.target = float(agent.param_noise_alpha), float(agent.param_noise_target_stddev)
+        self.compute_dist_interval = 10          # AdaptiveNormalParameterNoise's default, which DDPGAgent leaves
+        self.sigma = torch.full((self.agents,), float(agent.param_noise_sigma), dtype=torch.float64, device=device)
+        self.dist = torch.zeros(self.agents, dtype=torch.float64, device=device)
+        self.pop = torch.zeros(self.agents, kernels.param_noise_copy_numel(agent.model.actor), device=device)
+        self.generation, self.acts = -1, 0
+        self.refresh()                           # generation 0; no act yet: no adaptation
+
+    def refresh(self):
+        """the device form of on_parameter_fetched, no host synchronisation: with 'adaptive_normal' and acts > 0 every
+        agent's sigma is divided (dist / acts > target_stddev) or multiplied by alpha; then all agents are perturbed
+        again from the agent's current clean actor under generation + 1; acts = 0"""
+        if self.generation + 1 >= 1 << 32:
+            raise ValueError('DeviceParamNoise: generation %d leaves [0, 2^32)' % (self.generation + 1))
+        self.generation += 1
+        self.K.param_noise_refresh(self.agent.model.actor, self)
+        self.acts = 0
+
+    def measure_step(self, T):
+        """the step of a call of T steps that measures the action distance: the last s with (acts + s) %
+        compute_dist_interval == 0 (the reference overwrites its distance at every such act, param_noise.py:59-63: only
+        the last one before a refresh counts); -1: none, and always for 'normal'"""
+        if not self.adaptive:
+            return -1
+        k = self.compute_dist_interval
+        s = (int(T) - 1) - (self.acts + int(T) - 1) % k
+        return s if s >= 0 else -1
+
+    def perturbed(self, p):
+        """-> {'W1', 'b1', 'W2', 'b2', 'W3', 'b3'}: agent p's perturbed actor parameters under the current generation
+        and sigma, as tensors (smx_param_noise_fill_f32: the function the copies in pop are made of)"""
+        import collections
+        import torch
+        actor = self.agent.model.actor
+        flat = torch.empty(actor.numel, device=self.device)
+        self.K.param_noise_fill(actor, self, p, flat)
+        out, o = collections.OrderedDict(), 0
+        for k, v in actor.views.items():
+            out[k] = flat[o:o + v.numel()].view(v.shape)
+            o += v.numel()
+        return out
+
+    def state_dict(self):
+        return {'sigma': self.sigma.cpu(), 'dist': self.dist.cpu(), 'pop': self.pop.cpu(),
+                'generation': self.generation, 'acts': self.acts}
+
+    def load_state_dict(self, sd):
+        for k in ('sigma', 'dist', 'pop'):
+            getattr(self, k).copy_(sd[k])
+        self.generation, self.acts = int(sd['generation']), int(sd['acts'])
+
+
 class _DeviceActorReport(TrainingTensorplexMonitor):
     """TrainingTensorplexMonitor for one actor of a DeviceEpisodeMonitor: the same period, mean, tags and global_step,
     fed with polled episodes instead of wrapping an env"""

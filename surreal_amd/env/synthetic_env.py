@@ -109,6 +109,7 @@ class SyntheticVecEnv(object):
         self._ppo = {}                # ppo_rollout_into(): the open moving windows of the actors
         self.monitor = None           # attach_monitor(): the actors' episode returns, kept by the step launches
         self.noise = None             # attach_noise(): the exploration noise as a per-actor stream, drawn by the launches
+        self.param_noise = None       # attach_param_noise(): per-agent parameter-space noise for ddpg_rollout_into
 
     def attach_monitor(self, capacity=16):
         """-> a DeviceEpisodeMonitor (env/monitor.py) that every stepping launch from now on feeds: per actor the open
@@ -148,6 +149,25 @@ class SyntheticVecEnv(object):
     def detach_noise(self):
         """the calls draw with torch.randn again -> the stream (which keeps its counter)"""
         m, self.noise = self.noise, None
+        return m
+
+    def attach_param_noise(self, agent, seed, actors_per_agent=4, agent_base=0):
+        """-> a DeviceParamNoise (env/monitor.py) of DDPGAgent `agent`'s parameter-space noise ('normal' or
+        'adaptive_normal': its type, sigma, alpha and target_stddev): from now on ddpg_rollout_into runs every group of
+        actors_per_agent consecutive actors (a multiple of 4) -- an AGENT, global id agent_base + its index -- from its
+        own perturbed copy of the actor, made on the device, and with 'adaptive_normal' measures the action distance
+        inside the launch.  The agent's host noise is switched off (on_parameter_fetched no longer perturbs: its model
+        stays clean, nothing is perturbed twice); call refresh() on the returned object after every parameter fetch."""
+        from .monitor import DeviceParamNoise
+        self.param_noise = DeviceParamNoise(agent, seed, actors_per_agent, agent_base, self.n, self.K, self.device)
+        agent.device_param_noise = True
+        return self.param_noise
+
+    def detach_param_noise(self):
+        """ddpg_rollout_into does what it did before; the agent's host noise is on again -> the DeviceParamNoise"""
+        m, self.param_noise = self.param_noise, None
+        if m is not None:
+            m.agent.device_param_noise = False
         return m
 
     def _noi(self, k, on=False):
@@ -633,15 +653,29 @@ class SyntheticVecEnv(object):
         stacked frames, the actor, and ONE launch (smx_synth_ddpg_pixel_step) that also renders the step's frame into
         a history of n_step + S raw frames per actor, writes the closing transitions' uint8 'pixel' / 'pixel_next'
         [S*C, H, W] into the ring and the stacked observation of the next step.  The history carries from call to call
-        like the open transitions."""
+        like the open transitions.
+        With a DeviceParamNoise attached (attach_param_noise): ONE launch too (smx_synth_ddpg_population_rollout_f32),
+        every agent's actors acting from their agent's perturbed copy; with 'adaptive_normal' the call's last step s
+        with (acts + s) % compute_dist_interval == 0 also measures each agent's action distance; acts += T."""
         K, n, A = self.K, self.n, self.A
         camera = agent.model.is_pixel_input
         refusal = self._camera_refusal('ddpg_rollout_into', agent, camera)
         if refusal is not None:
             raise refusal[0](refusal[1])
-        if agent.param_noise_type == 'adaptive_normal':
+        pn = self.param_noise
+        if pn is not None:
+            why = ('a camera agent (the perception would need perturbing too)' if camera else
+                   'a LayerNorm actor' if agent.model.use_layernorm else
+                   'an actor shape the one-launch rollout does not take' if
+                   not K.synth_ddpg_rollout_supported(agent.model.actor) else
+                   'reference=True (the two-launch reference has one actor)' if reference else None)
+            if why is not None:
+                raise NotImplementedError('ddpg_rollout_into: no device parameter noise for ' + why)
+            if agent is not pn.agent:
+                raise ValueError('ddpg_rollout_into: the attached parameter noise belongs to another agent')
+        elif agent.param_noise_type == 'adaptive_normal':
             raise NotImplementedError("ddpg_rollout_into: 'adaptive_normal' parameter noise measures an action distance "
-                                      "per act() on the host; use 'normal' parameter noise or none")
+                                      "per act() on the host; use 'normal' parameter noise, none, or attach_param_noise")
         shapes, dtypes = {'obs': (self.D,), 'obs_next': (self.D,), 'actions': (A,), 'rewards': (), 'dones': ()}, None
         if camera:
             C, H, W = self.pixel
@@ -692,7 +726,12 @@ class SyntheticVecEnv(object):
             if d.get('pk') is None or d['pk'].numel() != K.epoch_packed_numel(actor):
                 d['pk'] = torch.zeros(K.epoch_packed_numel(actor), device=self.device)
             K.epoch_pack([(actor, d['pk'])])        # (the agent's parameters only change between rollouts)
-        if persistent and not reference:
+        if pn is not None:
+            K.synth_ddpg_population_rollout(actor, d['pk'], r, T, pn, pn.measure_step(T), actors_per_workgroup,
+                                            **self._mon(T), **self._noi(T, ns))
+            pn.acts += T
+            self.t = t
+        elif persistent and not reference:
             K.synth_ddpg_rollout(actor, d['pk'], r, T, actors_per_workgroup, **self._mon(T), **self._noi(T, ns))
             self.t = t
         else:

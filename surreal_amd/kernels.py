@@ -835,6 +835,55 @@ class HipKernels(object):
         p = self._ddpg_args(r, steps, net, packed, actors_per_workgroup, monitor, noise)
         L.call('smx_synth_ddpg_rollout_f32', ctypes.byref(p), self._st())
 
+    # ---- parameter-space noise on the device (csrc/smx_param_noise.hip; DeviceParamNoise, env/monitor.py) ----
+    def param_noise_copy_numel(self, net):
+        """floats of one agent's copy in the population buffer: epoch_pack's layout, then the biases"""
+        return int(self.lib.smx_param_noise_copy_floats(net.D, net.H1, net.H2, net.OUT))
+
+    @staticmethod
+    def _param_noise_args(net, pn):
+        """struct smx_param_noise of the clean actor `net` and a DeviceParamNoise-like `pn`: seed, agent_base,
+        generation, acts, adaptive, alpha, target, sigma / dist (fp64 [P]), pop ([P, stride] fp32)"""
+        q = L.ParamNoise()
+        q.net = ctypes.pointer(net.desc)
+        q.seed, q.agent_base, q.generation = int(pn.seed), int(pn.agent_base), int(pn.generation)
+        q.agents, q.adaptive, q.acts = int(pn.agents), int(bool(pn.adaptive)), int(pn.acts)
+        q.alpha, q.target = float(pn.alpha), float(pn.target)
+        assert pn.sigma.dtype == torch.float64 and pn.dist.dtype == torch.float64
+        assert pn.sigma.numel() == pn.dist.numel() == q.agents and pn.sigma.is_contiguous() and pn.dist.is_contiguous()
+        assert pn.pop.dtype == torch.float32 and pn.pop.is_contiguous() and pn.pop.shape[0] == q.agents
+        q.sigma, q.dist, q.packed_pop, q.packed_stride = L.ptr(pn.sigma), L.ptr(pn.dist), L.ptr(pn.pop), pn.pop.shape[1]
+        return q
+
+    def param_noise_fill(self, net, pn, p, out):
+        """out [numel of the actor's flat parameters] <- agent p's perturbed parameters (smx_param_noise_fill_f32)"""
+        assert out.is_contiguous() and out.dtype == torch.float32 and out.numel() == net.numel
+        L.call('smx_param_noise_fill_f32', ctypes.byref(self._param_noise_args(net, pn)), int(p), L.ptr(out), self._st())
+
+    def param_noise_refresh(self, net, pn):
+        """the device form of on_parameter_fetched for all agents of `pn` (smx_param_noise_refresh_f32): the adaptive
+        rule on sigma when pn.adaptive and pn.acts > 0, then every agent's copy of the perturbed `net` into pn.pop"""
+        L.call('smx_param_noise_refresh_f32', ctypes.byref(self._param_noise_args(net, pn)), self._st())
+
+    def synth_ddpg_population_block(self, n, actors_per_agent, forced=0):
+        """the block size the population launch takes (0: it refuses)"""
+        return int(self.lib.smx_synth_ddpg_population_block(int(n), int(actors_per_agent), int(forced)))
+
+    def synth_ddpg_population_rollout(self, net, packed, r, steps, pn, measure_step=-1, actors_per_workgroup=0,
+                                      monitor=None, noise=None):
+        """synth_ddpg_rollout with every agent of `pn` (pn.actors_per_agent consecutive actors) acting from its own
+        copy in pn.pop; net / packed: the clean actor, evaluated at step measure_step (-1: never) for pn.dist"""
+        if r['eps'] is not None:
+            assert r['eps'].is_contiguous() and tuple(r['eps'].shape) == (steps, r['state'].shape[0], net.OUT)
+        p = L.DdpgPopulationRollout()
+        p.base = self._ddpg_args(r, steps, net, packed, actors_per_workgroup, monitor, noise)
+        assert pn.pop.dtype == torch.float32 and pn.pop.is_contiguous() and pn.dist.dtype == torch.float64
+        assert pn.pop.shape[0] == pn.agents == pn.dist.numel()
+        p.packed_pop, p.packed_stride = L.ptr(pn.pop), pn.pop.shape[1]
+        p.actors_per_agent, p.agents, p.measure_step = int(pn.actors_per_agent), int(pn.agents), int(measure_step)
+        p.dist = L.ptr(pn.dist)
+        L.call('smx_synth_ddpg_population_rollout_f32', ctypes.byref(p), self._st())
+
     def synth_ddpg_step(self, r, mu, monitor=None, noise=None):
         """one step of synth_ddpg_rollout given the actor's output mu [n, A] (r['eps']: this step's [n, A] draws;
         r['cursor']: where this step's closing transitions go)"""

@@ -1,0 +1,257 @@
+"""GPU tier (-m gpu): per-agent parameter-space noise in the one-launch DDPG rollout
+(SyntheticVecEnv.attach_param_noise -> DeviceParamNoise; smx_param_noise_*_f32, smx_synth_ddpg_population_rollout_f32).
+
+Shapes: the actor 5 -> 12 -> 8 -> 3 (D no multiple of 4, both hidden widths below one 16-feature tile), n_step 3,
+episode_len 5 against T = 7 (a call crosses an episode end), 16 actors."""
+import copy
+
+import numpy as np
+import pytest
+import torch
+
+import ddpg_rollout_cases as DC
+import episode_monitor_cases as EM
+import helpers as H
+import noise_ref as NR
+import param_noise_ref as PR
+
+pytestmark = pytest.mark.gpu
+
+SEED, PSEED = 0x9E3779B97F4A7C15, 0xD1B54A32D192ED03
+D, HID, A = 5, (12, 8), 3
+EP, N_STEP, T, N = 5, 3, 7, 16
+CLOSING = 3                                    # of the clocks 0 1 2 3 4 0 1 of a call of 7, those >= n_step - 1
+SIG = torch.linspace(0.05, 0.8, N, dtype=torch.float64)          # the actors' exploration scales, by global actor id
+# The existing DDPG rollout test holds the persistent kernel's float fields to 2e-6 (test_gpu_ddpg_rollout.py); a distance
+# is formed from two such outputs of A components each: 2 sqrt(A) of it.
+DIST_ATOL = 2e-6 * 2 * np.sqrt(A)              # 6.93e-6
+
+
+def make(n, ptype, noise_type='normal', apa=4, agent_base=0, actor_base=0, attach=True, params=None):
+    """-> (agent, venv, replay, DeviceParamNoise or None): n actors with the global ids actor_base .., their env seeds
+    those ids, the episode monitor and the exploration stream attached"""
+    from surreal_amd.env import SyntheticVecEnv
+    from surreal_amd.replay import UniformReplay
+    lc, ec, sc = DC.configs(D, A, n, hidden=HID, n_step=N_STEP, noise_type=noise_type, param_noise_type=ptype,
+                            memory_size=4096, theta=2.0, dt=0.02, folder='surreal_amd_param_noise')
+    agent = DC.make_agent(lc, ec, sc, w3_scale=1.0)
+    if params is not None:
+        for k, v in params.items():
+            agent.model.actor.views[k].copy_(v)
+    venv = SyntheticVecEnv(n, D, A, episode_len=EP, seeds=list(range(actor_base, actor_base + n)))
+    venv.attach_monitor(capacity=4)
+    venv.attach_noise(SEED, actor_base=actor_base)
+    pn = venv.attach_param_noise(agent, PSEED, actors_per_agent=apa, agent_base=agent_base) if attach else None
+    return agent, venv, UniformReplay(lc, ec, sc), pn
+
+
+def run(agent, venv, replay, calls, actor_base=0, **kw):
+    n = venv.n
+    sig = SIG[actor_base:actor_base + n].cuda()
+    rows = sum(venv.ddpg_rollout_into(agent, replay, t, sigmas=sig, **kw) for t in calls)
+    return final(venv, replay, rows)
+
+
+def final(venv, replay, rows):
+    """every byte a run leaves, per actor: the ring rows [closing step, actor, .], the env state, the OU and carry
+    tensors, the monitor"""
+    torch.cuda.synchronize()
+    n = venv.n
+    out = {'ring_' + k: torch.as_tensor(v[:rows].reshape(rows // n, n, -1)).transpose(0, 1).contiguous()
+           for k, v in H.device_ring(replay, DC.FIELDS).items()}
+    out['state'] = venv.state.cpu()
+    out.update({k: venv._ddpg[k].cpu() for k in ('ou', 'carry_obs', 'carry_act', 'carry_rew')})
+    out.update({'mon_' + k: v.reshape(n, -1) for k, v in EM.monitor_state(venv.monitor).items()})
+    return out
+
+
+def same_bytes(got, want, lo=0, hi=None):
+    """`want` (a run over the actors lo .. hi - 1 alone) against those actors of `got`"""
+    assert set(got) == set(want)
+    for k in want:
+        g = got[k][lo:hi].contiguous()
+        assert g.shape == want[k].shape and g.dtype == want[k].dtype, k
+        assert torch.equal(g.view(torch.uint8), want[k].contiguous().view(torch.uint8)), k
+
+
+def per_agent_reference(pn, p, apa, calls, noise_type, agent_base=0):
+    """the existing launch on agent p's actors alone, from an agent whose model holds perturbed(p)"""
+    lo = (agent_base + p) * apa
+    agent, venv, replay, _ = make(apa, None, noise_type, actor_base=lo, attach=False, params=pn.perturbed(p))
+    return run(agent, venv, replay, calls, actor_base=lo)
+
+
+# ---- 1. the fill ---------------------------------------------------------------------------------------------------------
+
+def test_fill_matches_the_restatement_and_differs_by_agent_generation_and_stream():
+    agent, venv, _, pn = make(12, 'normal', agent_base=2)
+    assert pn.agents == 3 and pn.generation == 0
+    clean = agent.model.actor_flat[:agent.model.actor.numel].cpu().numpy()
+    seen = []
+    for q in (0, 1):
+        if q:
+            pn.refresh()
+        assert pn.generation == q
+        for p in range(3):
+            got = torch.cat([v.reshape(-1) for v in pn.perturbed(p).values()]).cpu().numpy()
+            want = PR.perturbed_flat(clean, agent.param_noise_sigma, PSEED, 2 + p, q)
+            d = float(np.abs(got.astype(np.float64) - want).max())
+            print('smx_param_noise_fill_f32 agent %d generation %d: max |difference| %.3g (atol 4e-7)' % (2 + p, q, d))
+            assert d <= 4e-7
+            seen.append(got)
+    for i in range(len(seen)):
+        for j in range(i):
+            assert not np.array_equal(seen[i], seen[j]), (i, j)
+    # the same seed as an exploration stream: other Philox blocks, other numbers
+    z = (seen[0] - clean) / np.float32(agent.param_noise_sigma)
+    e = venv.noise.__class__(PSEED, 2, 1, A, venv.K, venv.device).draws(1, 1, 32).cpu().numpy().ravel()
+    assert (np.abs(z[:32] - e) < 1e-2).sum() <= 2               # (two streams of normals meet that close by chance)
+    assert np.abs(e - NR.draws(PSEED, 2, 0, 1, 1, 32).ravel()).max() <= 1e-5
+    assert torch.equal(agent.model.actor_flat[:clean.size].cpu(), torch.as_tensor(clean))       # read, never written
+
+
+# ---- 2. the packed copies -------------------------------------------------------------------------------------------------
+
+def test_packed_copies_are_epoch_pack_of_the_perturbed_nets_with_zero_pads():
+    agent, venv, _, pn = make(N, 'adaptive_normal')
+    K, actor = venv.K, agent.model.actor
+    numel = K.epoch_packed_numel(actor)
+    twin = copy.deepcopy(agent.model)
+    ones = torch.zeros(numel, device='cuda')
+    for v in twin.actor.views.values():
+        v.fill_(1.0)
+    K.epoch_pack([(twin.actor, ones)])
+    pad = ones == 0
+    assert pad.any() and (~pad).sum() == 2 * (12 * 5 + 8 * 12 + 3 * 8) - 12 * 5        # W1 W2 W3 and W2^T W3^T
+    for p in range(pn.agents):
+        pert = pn.perturbed(p)
+        for k, v in pert.items():
+            twin.actor.views[k].copy_(v)
+        want = torch.zeros(numel, device='cuda')
+        K.epoch_pack([(twin.actor, want)])
+        got = pn.pop[p]
+        assert torch.equal(got[:numel].view(torch.int32), want.view(torch.int32)), p
+        assert not got[:numel][pad].view(torch.int32).any()
+        b = torch.cat([pert['b1'], pert['b2'], pert['b3']])
+        assert torch.equal(got[numel:numel + b.numel()].view(torch.int32), b.view(torch.int32))
+        assert not got[numel + b.numel():].view(torch.int32).any()
+
+
+# ---- 3. the population launch against per-agent launches --------------------------------------------------------------------
+
+@pytest.mark.parametrize('noise_type', ['normal', 'ou_noise'])
+def test_population_launch_leaves_the_bytes_of_per_agent_launches(noise_type):
+    agent, venv, replay, pn = make(N, 'adaptive_normal', noise_type)
+    one = run(agent, venv, replay, (T,))
+    assert one['ring_obs'].shape == (N, CLOSING, D) and pn.acts == T
+    for p in range(4):
+        same_bytes(one, per_agent_reference(pn, p, 4, (T,), noise_type), 4 * p, 4 * p + 4)
+    agent, venv, replay, _ = make(N, 'adaptive_normal', noise_type)
+    same_bytes(one, run(agent, venv, replay, (3, 4)))
+    # differently perturbed agents do act differently
+    assert not torch.equal(one['ring_actions'][0:4], one['ring_actions'][4:8])
+
+
+def test_agents_of_eight_actors_under_every_block_size_that_divides_them():
+    from surreal_amd._lib import SmxError
+    outs = []
+    for apw in (4, 8):
+        agent, venv, replay, pn = make(N, 'normal', apa=8)
+        assert pn.agents == 2
+        outs.append(run(agent, venv, replay, (T,), actors_per_workgroup=apw))
+    same_bytes(outs[0], outs[1])
+    for p in range(2):
+        same_bytes(outs[0], per_agent_reference(pn, p, 8, (T,), 'normal'), 8 * p, 8 * p + 8)
+    agent, venv, replay, pn = make(N, 'normal', apa=8)
+    with pytest.raises(SmxError, match='rc=-2 '):               # SMX_E_SHAPE
+        venv.ddpg_rollout_into(agent, replay, T, sigmas=SIG.cuda(), actors_per_workgroup=16)
+
+
+# ---- 4. sharding -----------------------------------------------------------------------------------------------------------
+
+def test_two_envs_of_two_agents_leave_the_bytes_of_one_env_of_four():
+    agent, venv, replay, _ = make(N, 'adaptive_normal')
+    whole = run(agent, venv, replay, (T,))
+    for half in range(2):
+        agent, venv, replay, pn = make(8, 'adaptive_normal', agent_base=2 * half, actor_base=8 * half)
+        same_bytes(whole, run(agent, venv, replay, (T,), actor_base=8 * half), 8 * half, 8 * half + 8)
+
+
+# ---- 5. the distance, 6. the adaptation ----------------------------------------------------------------------------------
+
+def _measured_run(ptype='adaptive_normal'):
+    agent, venv, replay, pn = make(N, ptype)
+    pn.compute_dist_interval = 3
+    pn.dist.fill_(-1.0)
+    return agent, venv, replay, pn
+
+
+def test_distance_is_measured_at_the_last_qualifying_step_on_the_first_actor():
+    agent, venv, replay, pn = _measured_run()
+    assert pn.measure_step(T) == 6
+    run(agent, venv, replay, (T,))
+    dist = pn.dist.cpu().numpy()
+    # the observations before step 6: a twin's state after 6 steps (3 + 4 == 7: the same trajectory)
+    twin = make(N, 'adaptive_normal')
+    run(twin[0], twin[1], twin[2], (6,))
+    obs = twin[1].state.cpu().numpy()
+    clean = {k: v.cpu().numpy() for k, v in agent.model.actor.views.items()}
+    for p in range(4):
+        noisy = {k: v.cpu().numpy() for k, v in pn.perturbed(p).items()}
+        want = PR.action_distance(clean, noisy, obs[4 * p])
+        print('agent %d: dist %.9g, float64 restatement %.9g, |difference| %.3g (atol %.3g)'
+              % (p, dist[p], want, abs(dist[p] - want), DIST_ATOL))
+        assert want > 1e-4 and abs(dist[p] - want) <= DIST_ATOL
+    # clocks 7 and 8: no multiple of 3, nothing measured, dist untouched
+    assert pn.acts == 7 and pn.measure_step(2) == -1
+    venv.ddpg_rollout_into(agent, replay, 2, sigmas=SIG.cuda())
+    torch.cuda.synchronize()
+    assert np.array_equal(pn.dist.cpu().numpy(), dist) and pn.acts == 9
+
+
+def test_refresh_adapts_sigma_by_the_python_rule_on_the_measured_distance():
+    agent, venv, replay, pn = _measured_run()
+    run(agent, venv, replay, (T,))
+    dist = [float(v) for v in pn.dist.cpu()]
+    per_act = sorted(d / T for d in dist)
+    pn.target = 0.5 * (per_act[1] + per_act[2])                  # two agents above, two below
+    sigma0, gen = [float(v) for v in pn.sigma.cpu()], pn.generation
+    before = pn.perturbed(0)['W1'].clone()
+    pn.refresh()
+    want = [PR.adapt(s, d, T, pn.target, pn.alpha) for s, d in zip(sigma0, dist)]
+    got = [float(v) for v in pn.sigma.cpu()]
+    assert got == want and len({w > s for w, s in zip(want, sigma0)}) == 2
+    assert pn.acts == 0 and pn.generation == gen + 1
+    assert not torch.equal(pn.perturbed(0)['W1'], before)
+    # 'normal': sigma stays, nothing is ever measured
+    agent, venv, replay, pn = _measured_run('normal')
+    assert pn.measure_step(T) == -1
+    run(agent, venv, replay, (T,))
+    pn.refresh()
+    assert torch.equal(pn.sigma.cpu(), torch.full((4,), agent.param_noise_sigma, dtype=torch.float64))
+    assert torch.equal(pn.dist.cpu(), torch.full((4,), -1.0, dtype=torch.float64)) and pn.generation == 1
+
+
+# ---- 7. checkpoint -------------------------------------------------------------------------------------------------------
+
+def test_state_dict_into_a_new_env_continues_with_the_same_bytes():
+    a = _measured_run()
+    whole = run(a[0], a[1], a[2], (T,))
+    dist = a[3].dist.cpu()
+    a = _measured_run()
+    run(a[0], a[1], a[2], (3,))
+    sd = copy.deepcopy(a[3].state_dict())
+    assert set(sd) == {'sigma', 'dist', 'pop', 'generation', 'acts'} and sd['acts'] == 3 and sd['generation'] == 0
+    # a new env brought to the same env state, its parameter noise somewhere else entirely
+    b = _measured_run()
+    run(b[0], b[1], b[2], (3,))
+    b[3].refresh()
+    b[3].sigma.mul_(3.0)
+    b[3].refresh()
+    b[3].acts = 1
+    b[3].load_state_dict(sd)
+    assert b[3].generation == 0 and b[3].acts == 3
+    b[1].ddpg_rollout_into(b[0], b[2], 4, sigmas=SIG.cuda())
+    same_bytes(whole, final(b[1], b[2], N * CLOSING))
+    assert torch.equal(b[3].dist.cpu(), dist)
+    assert torch.equal(b[3].pop, a[3].pop) and torch.equal(b[3].sigma, a[3].sigma)
