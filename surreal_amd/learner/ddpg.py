@@ -23,8 +23,12 @@ kernels) runs on camera0 / 255, its features go in front of the low-dim vector, 
 the critic loss (Adam with the critic's hyper-parameters) and follows the target updates; the actor
 update reuses the features formed before the critic step, as the reference does.
 
-use_layernorm (default off) runs layer by layer (_enqueue_iteration_ln), with every other switch (round 6: the double critic
-and camera observations too); torchx's LayerNorm semantics are unpinned (its source is absent): taken as
+Three launch schedules (_schedule): row blocks and dependency levels for low-dimensional observations with one critic, and
+the layer-by-layer one (_enqueue_iteration_layers) that carries every switch.  What belongs to one critic -- model, target,
+buffers, gradients, Adam group -- is one record (_critic_workspace): the second critic's update is the first one's code.
+
+use_layernorm (default off) runs layer by layer too, with every other switch: the variant lives in DDPGModel's passes
+(actor_forward ... actor_backward), the learner's iteration is the same.  torchx's LayerNorm semantics are unpinned (its source is absent): taken as
 torch.nn.LayerNorm over the features.
 """
 import gc
@@ -40,6 +44,23 @@ from surreal_amd.learner.base import Learner, DeferredStats
 from surreal_amd.learner.dist import _dist_info, setup_peer_exchange
 from surreal_amd.model.ddpg_net import DDPGModel
 from surreal_amd.session import ConfigError
+
+
+def _grad_views(flat, named_params):
+    """views by parameter name into a flat gradient buffer laid out like the parameters' own"""
+    views, o = {}, 0
+    for name, v in named_params:
+        views[name] = flat[o:o + v.numel()].view(v.shape)
+        o += v.numel()
+    return views
+
+
+def _stage(dst, src):
+    """copy src into the staging buffer dst unless it IS dst -- the SAME buffer, not merely the same address: a strided /
+    reshaped view that starts at the staging buffer's address is copied like any other source"""
+    if not (src.data_ptr() == dst.data_ptr() and src.shape == dst.shape and src.stride() == dst.stride()
+            and src.dtype == dst.dtype):
+        dst.copy_(src)
 
 
 class DDPGLearner(Learner):
@@ -85,21 +106,19 @@ class DDPGLearner(Learner):
         self.model = DDPGModel(**mk)
         self.model_target = DDPGModel(**mk)
         self.model_target.load_state_dict(self.model.state_dict())       # hard_update (ddpg.py:175-176)
-        z = torch.zeros_like
         self.is_pixel_input = self.model.is_pixel_input
-        if self.is_pixel_input:         # the perception CNN is in the critic's optimiser (ddpg_net.py:57-61)
-            self.perc_exp_avg, self.perc_exp_avg_sq = z(self.model.perception_flat), z(self.model.perception_flat)
+        # Adam's (exp_avg, exp_avg_sq) per optimiser group; the perception CNN is in the critic's optimiser (ddpg_net.py:57-61)
+        moments = lambda flat: None if flat is None else (torch.zeros_like(flat), torch.zeros_like(flat))  # noqa: E731
+        self.actor_exp_avg, self.actor_exp_avg_sq = moments(self.model.actor_flat)
+        self.critic_exp_avg, self.critic_exp_avg_sq = moments(self.model.critic_flat)
+        self.perception_moments = moments(self.model.perception_flat)
         if self.use_double_critic:
             # TD3's second critic (ddpg.py:119-147, 162-166, 177-178): own parameters, optimiser, target
             self.model2 = DDPGModel(critic_only=True, **mk)
             self.model_target2 = DDPGModel(critic_only=True, **mk)
             self.model_target2.load_state_dict(self.model2.state_dict())
-            self.critic2_exp_avg, self.critic2_exp_avg_sq = z(self.model2.critic_flat), z(self.model2.critic_flat)
-            if self.is_pixel_input:
-                self.perc2_exp_avg = z(self.model2.perception_flat)
-                self.perc2_exp_avg_sq = z(self.model2.perception_flat)
-        self.actor_exp_avg, self.actor_exp_avg_sq = z(self.model.actor_flat), z(self.model.actor_flat)
-        self.critic_exp_avg, self.critic_exp_avg_sq = z(self.model.critic_flat), z(self.model.critic_flat)
+            self.critic2_moments = moments(self.model2.critic_flat)
+            self.perception2_moments = moments(self.model2.perception_flat)
         self.actor_step = 0
         self.critic_step = 0
         self.frame_stack_concatenate_on_env = self.env_config.get('frame_stack_concatenate_on_env', True)
@@ -153,30 +172,50 @@ class DDPGLearner(Learner):
     def _workspace(self, B, D):
         if self._ws is not None and self._ws.key == (B, D):
             return self._ws
-        m, A = self.model, self.action_dim
+        m, mt, A = self.model, self.model_target, self.action_dim
         f = lambda *s: torch.empty(*s, device=self.device, dtype=torch.float32)  # noqa: E731
         ws = types.SimpleNamespace(key=(B, D))
         a, c1, c2 = m.actor, m.c1, m.c2
-        ws.h1a, ws.h2a, ws.act = f(B, a.H1), f(B, a.H2), f(B, A)        # actor forward (s or s')
-        ws.xcat, ws.h2c, ws.q = f(B, c1 + A), f(B, c2), f(B)            # critic forward
-        ws.q_next, ws.y, ws.dz3 = f(B), f(B), f(B)
-        ws.dz2, ws.dxcat = f(B, c2), f(B, c1 + A)
-        ws.q_actor, ws.dz3a, ws.dz2a, ws.dz1a = f(B), f(B, A), f(B, a.H2), f(B, a.H1)
-        ws.grads_c = torch.zeros_like(m.critic_flat)
-        ws.grads_a = torch.zeros_like(m.actor_flat)
-        ws.gc = {}
-        o = 0
-        for name, v in m.critic.items():
-            ws.gc[name] = ws.grads_c[o:o + v.numel()].view(v.shape)
-            o += v.numel()
-        ws.stats = torch.zeros(8, device=self.device)
         # the Adam step count and the learning rates live on the device: one captured hipGraph of
         # the iteration is replayed while they change (smx_adam_step_dev_f32)
         ws.step = torch.full((1,), self.critic_step, dtype=torch.int32, device=self.device)
         ws.dev_step = self.critic_step
         ws.lr = torch.tensor([self.lr_actor, self.lr_critic], dtype=torch.float32, device=self.device)
         ws.lr_host = (self.lr_actor, self.lr_critic)
-        ws.q_policy = f(B)
+        ws.act, ws.q_next, ws.q_actor, ws.q_policy = f(B, A), f(B), f(B), f(B)
+        if self.is_pixel_input:
+            ws.dxin = f(B, m.input_dim)
+            ws.cnn_sk = m._cnn_stem.splitk_workspace(m.cnn, B, self.device)
+            ws.s_pix = ws.s_pix_next = None              # staged frames (allocated in their dtype)
+        c = self._critic_workspace(ws, m, mt, (self.critic_exp_avg, self.critic_exp_avg_sq), self.perception_moments)
+        ws.critics = [c]
+        if self.use_double_critic:
+            ws.critics.append(self._critic_workspace(ws, self.model2, self.model_target2, self.critic2_moments,
+                                                     self.perception2_moments))
+            ws.q_next2, ws.stats2 = f(B), ws.critics[1].stats
+        ws.bw = m.backward_workspace(B, self.device)          # (one critic or the actor at a time)
+        ws.dz2, ws.dxcat, ws.dz3a, ws.dz2a, ws.dz1a = ws.bw.dz2, ws.bw.dxcat, ws.bw.dz3a, ws.bw.dz2a, ws.bw.dz1a
+        # the first critic's buffers under the names the row and level schedules know them by: its (and the actor's)
+        # forward workspace -- h1a, h2a, xcat, h2c without LayerNorm --, gradients, Q, y, dLoss/dQ, statistics
+        for k, v in vars(c.w).items():
+            setattr(ws, k, v)
+        ws.grads_c, ws.gc, ws.q, ws.y, ws.dz3, ws.stats = c.grads, c.gv, c.q, c.y, c.dz3, c.stats
+        ws.grads_a = torch.zeros_like(m.actor_flat)
+        ws.ga = _grad_views(ws.grads_a, list(a.views.items()) + list(m.actor_ln.items()))
+        ws.adam_actor = (m.actor_flat, ws.grads_a, self.actor_exp_avg, self.actor_exp_avg_sq, ws.lr[0:1],
+                         self.actor_regularization, self.actor_gradient_clip_value)
+        # (target, source) buffers of the target-network update (ddpg.py:344-352): actor + critic as the one buffer they
+        # share when both models have it, then the perception CNN, the second critic and its perception CNN
+        if getattr(mt, 'ac_flat', None) is not None and getattr(m, 'ac_flat', None) is not None:
+            ws.target_pairs = [(mt.ac_flat, m.ac_flat)]
+        else:
+            ws.target_pairs = [(mt.actor_flat, m.actor_flat), (mt.critic_flat, m.critic_flat)]
+        if self.is_pixel_input:
+            ws.target_pairs.append((mt.perception_flat, m.perception_flat))
+        for second in ws.critics[1:]:
+            ws.target_pairs.append((second.target.critic_flat, second.model.critic_flat))
+            if self.is_pixel_input:
+                ws.target_pairs.append((second.target.perception_flat, second.model.perception_flat))
         # the levelled schedule (_enqueue_iteration_levels) keeps the four forward chains of an iteration apart: target
         # actor, target critic, critic, actor each have their own activations, so independent layers share a launch
         ws.h1a_t, ws.h2a_t = f(B, a.H1), f(B, a.H2)
@@ -184,50 +223,9 @@ class DDPGLearner(Learner):
         ws.xcat_a, ws.h2c_a = f(B, c1 + A), f(B, c2)
         ws.dz3_actor = torch.full((B,), -1.0 / B, device=self.device)       # d(-mean Q) / dQ  (ddpg.py:331)
         # the batch is staged into fixed buffers (5 small copies) so that the graph's pointers hold
-        A = self.action_dim
         ws.s_obs, ws.s_next, ws.s_act, ws.s_rew, ws.s_done = f(B, D), f(B, D), f(B, A), f(B), f(B)
         if self.use_action_regularization:
             ws.s_noise, ws.act_n = f(B, A), f(B, A)
-        if self.use_double_critic:
-            ws.xcat2, ws.h2c2, ws.q2, ws.q_next2 = f(B, c1 + A), f(B, c2), f(B), f(B)
-            ws.y2, ws.dz3_2 = f(B), f(B)
-            ws.grads_c2 = torch.zeros_like(self.model2.critic_flat)
-            ws.gc2 = {}
-            o = 0
-            for name, v in self.model2.critic.items():
-                ws.gc2[name] = ws.grads_c2[o:o + v.numel()].view(v.shape)
-                o += v.numel()
-            ws.stats2 = torch.zeros(8, device=self.device)
-        if self.is_pixel_input:
-            from surreal_amd.model.cnn_stem import CnnStem
-            cnn = m.cnn
-            Dx = m.input_dim
-            ws.xf, ws.xnf, ws.dxin = f(B, Dx), f(B, Dx), f(B, Dx)
-            ws.cnn = CnnStem.workspace(cnn, B, self.device, backward=True)
-            ws.cnn.sk = m._cnn_stem.splitk_workspace(cnn, B, self.device)
-            ws.cnn_t = CnnStem.workspace(cnn, B, self.device, backward=False)
-            ws.grads_p = torch.zeros_like(m.perception_flat)
-            if self.use_double_critic:
-                ws.xf2, ws.xnf2 = f(B, Dx), f(B, Dx)
-                ws.cnn2 = CnnStem.workspace(cnn, B, self.device, backward=True)
-                ws.cnn2.sk = ws.cnn.sk
-                ws.cnn_t2 = CnnStem.workspace(cnn, B, self.device, backward=False)
-                ws.grads_p2 = torch.zeros_like(m.perception_flat)
-            ws.s_pix = ws.s_pix_next = None              # staged frames (allocated in their dtype)
-        if self.use_layernorm:
-            ws.ln, ws.ln_t = m.ln_workspace(B, self.device), self.model_target.ln_workspace(B, self.device)
-            if self.use_double_critic:
-                ws.ln2, ws.ln_t2 = self.model2.ln_workspace(B, self.device), self.model_target2.ln_workspace(B, self.device)
-                ws.xcat_t2 = f(B, c1 + A)
-            ws.dn2, ws.dz1c = f(B, c2), f(B, c1)
-            ws.dn2a, ws.dn1a = f(B, a.H2), f(B, a.H1)
-            ws.ln_ws = f(max(self.K.layernorm_backward_ws_floats(B, k) for k in (c1, c2, a.H1, a.H2)))
-            ws.ln_scr = f(2 * max(c1, c2))
-            ws.ga = {}
-            o = 0
-            for name, v in list(m.actor.views.items()) + list(m.actor_ln.items()):
-                ws.ga[name] = ws.grads_a[o:o + v.numel()].view(v.shape)
-                o += v.numel()
         ws.graph = None
         self._rank_weight = 1.0
         ws.xerr = torch.zeros(1, dtype=torch.int32, device=self.device) if self.device != 'cpu' else None
@@ -240,48 +238,56 @@ class DDPGLearner(Learner):
         self._ws = ws
         return ws
 
+    def _critic_workspace(self, ws, model, target, moments, perception_moments):
+        """what belongs to ONE critic: model and target, their forward workspaces, Q / y / dLoss/dQ, the gradient buffer
+        with its views by parameter name, the statistics block and the Adam group (parameters, gradients, exp_avg,
+        exp_avg_sq, lr slot, decay, value clip: _enqueue_adam) -- with camera observations its perception CNN's features
+        of s / s', workspaces, gradients and Adam group as well"""
+        B = ws.key[0]
+        f = lambda *s: torch.empty(*s, device=self.device, dtype=torch.float32)  # noqa: E731
+        c = types.SimpleNamespace(model=model, target=target, q=f(B), y=f(B), dz3=f(B),
+                                  stats=torch.zeros(8, device=self.device), grads=torch.zeros_like(model.critic_flat))
+        c.w = model.workspace(B, self.device)
+        c.w_t = target.target_workspace(c.w, B, self.device)
+        c.gv = _grad_views(c.grads, model.critic.items())
+        c.adam = (model.critic_flat, c.grads) + moments + (ws.lr[1:2], self.critic_regularization,
+                                                           self.critic_gradient_clip_value)
+        c.adam_p = None
+        if self.is_pixel_input:
+            from surreal_amd.model.cnn_stem import CnnStem
+            c.xf, c.xnf = f(B, model.input_dim), f(B, model.input_dim)
+            c.cnn = CnnStem.workspace(model.cnn, B, self.device, backward=True)
+            c.cnn.sk = ws.cnn_sk
+            c.cnn_t = CnnStem.workspace(model.cnn, B, self.device, backward=False)
+            c.grads_p = torch.zeros_like(model.perception_flat)
+            # the critic's optimiser and decay, but no clip: ddpg.py:308-309 clips self.model.critic alone
+            c.adam_p = (model.perception_flat, c.grads_p) + perception_moments + (ws.lr[1:2], self.critic_regularization, 0.0)
+        return c
+
     def _setup_peer_exchange(self, ws):
         """several ranks on one node: the gradient / statistics all-reduces of an iteration (ddpg.py:244-400 run on
         shards: SURVEY.md 8(e) "same pattern, 2 grad all-reduces per iteration") as kernels over IPC-mapped peer buffers
         -- set up and SELF-CHECKED once, collectively; any failure leaves the process group in place and the launches
         eager.  session_config.learner.peer_exchange = False keeps the process group."""
-        need = max(64, ws.grads_c.numel(), ws.grads_a.numel(),
-                   ws.grads_p.numel() if self.is_pixel_input else 0,
-                   ws.grads_c2.numel() if self.use_double_critic else 0)
-        setup_peer_exchange(self, ws.xerr, need)
+        groups = [ws.adam_actor] + [g for c in ws.critics for g in (c.adam, c.adam_p) if g is not None]
+        setup_peer_exchange(self, ws.xerr, max([64] + [grads.numel() for _, grads, *_ in groups]))
         self.exchange_kind = self._dist.kind()
         if self._dist.exchange is None:
             self.use_graph = False            # process-group collectives are not captured
 
-    def _critic_backward(self, ws, x, B, model=None, dz3=None, xcat=None, h2c=None, gc=None):
-        """gradients of a critic's parameters from dz3 (dLoss/dQ; default: the first critic's
-        buffers); leaves dLoss/d(xcat) in ws.dxcat (its last A columns are dLoss/d(action))"""
-        K, m, A = self.K, model or self.model, self.action_dim
-        xcat = ws.xcat if xcat is None else xcat
-        h2c = ws.h2c if h2c is None else h2c
-        gc = ws.gc if gc is None else gc
-        c, c1, c2, D = m.critic, m.c1, m.c2, x.shape[1]
-        dz3 = (ws.dz3 if dz3 is None else dz3).view(B, 1)
-        K.linear(dz3, 1, c['W3'], 0, None, ws.dz2, B, c2, 1, relu_mask=h2c, lda=1, ldb=c2)
-        # d/d(relu(layer1)) masked by relu', into the first c1 columns of dxcat
-        K.linear(ws.dz2, 1, c['W2'], 0, None, ws.dxcat, B, c1, c2, relu_mask=xcat, ldb=c1 + A,
-                 ldc=c1 + A)
-        # d/d(action) into the last A columns (no mask)
-        K.linear(ws.dz2, 1, c['W2'][:, c1:], 0, None, ws.dxcat[:, c1:], B, A, c2, ldb=c1 + A,
-                 ldc=c1 + A)
-        K.linear_wgrad(ws.dxcat, x, gc['W1'], gc['b1'], c1, D, B, ldz=c1 + A)
-        K.linear_wgrad(ws.dz2, xcat, gc['W2'], gc['b2'], c2, c1 + A, B)
-        K.linear_wgrad(dz3, h2c, gc['W3'], gc['b3'], 1, c2, B, ldz=1)
+    def _enqueue_adam(self, ws, group):
+        """one optimiser group's Adam step (the actor's, a critic's, a critic's perception CNN's); step count and lr are
+        read on the device"""
+        flat, grads, exp_avg, exp_avg_sq, lr, decay, clip = group
+        self.K.adam_step_dev(flat, grads, exp_avg, exp_avg_sq, lr, ws.step, decay, clip)
 
-    def _perception_backward(self, ws, model, xin, cnn_ws, grads_p):
-        """the critic loss's gradient through the perception CNN (ddpg.py:304-308: critic_loss.backward()
-        reaches model.perception): d(critic layer 1 input) = dz1 . W1, masked by the feature ReLU,
-        then the stem's own backward; ws.dxcat must still hold this critic's dz1"""
-        K, A = self.K, self.action_dim
-        c1, Dx = model.c1, model.input_dim
-        K.linear(ws.dxcat, 1, model.critic['W1'], 0, None, ws.dxin, xin.shape[0], Dx, c1, relu_mask=xin,
-                 lda=c1 + A, ldb=Dx)
-        model._cnn_stem.backward(model.cnn, xin.shape[0], cnn_ws, ws.dxin[:, :model.feat_dim], grads_p)
+    def _enqueue_target_update(self, ws):
+        """ddpg.py:389-428"""
+        for tgt, src in ws.target_pairs:
+            if self.target_update_type == 'soft':
+                self.K.soft_update(tgt, src, self.target_update_tau)
+            else:
+                self.K.hard_update_every(tgt, src, ws.step, self.target_update_interval)
 
     def _average_over_ranks(self, t):
         """a per-rank mean -> the mean over the global batch: weighted by the rank's share of it, then
@@ -296,7 +302,7 @@ class DDPGLearner(Learner):
         depend on each other share a launch (smx_linear_multi_f32), and so do a level's weight gradients --
         22 dependent launches where the layer-by-layer schedule takes ~40 (each ~6 us at batch 512: the
         iteration is launch-latency bound).  The arithmetic of every layer is the same kernel with the same
-        operands as in _enqueue_iteration: identical results.
+        operands as in _enqueue_iteration_layers: identical results.
         The actor's forward pass for ITS update (ddpg.py:326-329) only reads the actor's parameters, which the
         critic update does not touch, so it rides in levels 1-3."""
         K, m, mt, A = self.K, self.model, self.model_target, self.action_dim
@@ -342,8 +348,7 @@ class DDPGLearner(Learner):
                         ('wgrad', ws.dz2, ws.xcat, ws.gc['W2'], ws.gc['b2'], c2, ld, B, {})])
         K.linear_wgrad(ws.dxcat, x, ws.gc['W1'], ws.gc['b1'], c1, D, B, ldz=ld)
         # 10
-        K.adam_step_dev(m.critic_flat, ws.grads_c, self.critic_exp_avg, self.critic_exp_avg_sq,
-                        ws.lr[1:2], ws.step, self.critic_regularization, self.critic_gradient_clip_value)
+        self._enqueue_adam(ws, ws.critics[0].adam)
         # 11-13: Q(s, mu(s)) through the UPDATED critic; d(-mean Q)/d(layer 2) needs only that pass's ReLU mask
         K.linear(x, 1, c['W1'], 1, c['b1'], ws.xcat_a, B, c1, D, act=R, ldc=ld)
         K.linear(ws.xcat_a, 1, c['W2'], 1, c['b2'], ws.h2c_a, B, c2, ld, act=R)
@@ -355,14 +360,9 @@ class DDPGLearner(Learner):
         K.tanh_backward(ws.dz3a, ws.act, ws.dz3a)
         # 16-18: actor backward (data gradients, weight gradients), 19: its Adam step
         K.mlp3_backward(m.actor, x, ws.h1a, ws.h2a, ws.dz3a, ws.dz2a, ws.dz1a, ws.grads_a, None)
-        K.adam_step_dev(m.actor_flat, ws.grads_a, self.actor_exp_avg, self.actor_exp_avg_sq,
-                        ws.lr[0:1], ws.step, self.actor_regularization, self.actor_gradient_clip_value)
+        self._enqueue_adam(ws, ws.adam_actor)
         K.ddpg_stats(ws.q, ws.y, rewards, actions, ws.q_actor, ws.stats)
-        for tgt, src in self._target_pairs(mt, m):
-            if self.target_update_type == 'soft':
-                K.soft_update(tgt, src, self.target_update_tau)
-            else:
-                K.hard_update_every(tgt, src, ws.step, self.target_update_interval)
+        self._enqueue_target_update(ws)
 
     def _rows_dims(self, D, rows=None):
         """(D, A, H1, H2, c1, c2) when the row-block kernels take these shapes (for a batch of `rows`), else None"""
@@ -380,11 +380,6 @@ class DDPGLearner(Learner):
         ws.rows_versions = None          # nothing packed yet
         if getattr(ws, 'stats_slots', None) is None:
             ws.stats_slots = torch.zeros(2, 8, pin_memory=torch.cuda.is_available())
-        if not hasattr(ws, 'ga'):
-            ws.ga, o = {}, 0
-            for name, v in m.actor.views.items():
-                ws.ga[name] = ws.grads_a[o:o + v.numel()].view(v.shape)
-                o += v.numel()
         nets = {'actor': m.actor.views, 'critic': m.critic, 'target_actor': mt.actor.views, 'target_critic': mt.critic}
         io = dict(x=x, x_next=xn, actions=actions, rewards=rewards, dones=done, xcat=ws.xcat, h2c=ws.h2c, q=ws.q,
                   q_next=ws.q_next, y=ws.y, dz3=ws.dz3, dz2=ws.dz2, dxcat=ws.dxcat, h1a=ws.h1a, h2a=ws.h2a, act=ws.act,
@@ -456,177 +451,44 @@ class DDPGLearner(Learner):
             self.K.ddpg_rows_pack(args)
             ws.rows_versions = self._rows_versions()
 
-    @staticmethod
-    def _target_pairs(mt, m):
-        """(target, source) buffers of the target-network update (ddpg.py:344-352): actor + critic as the one buffer they
-        share when both models have it"""
-        if getattr(mt, 'ac_flat', None) is not None and getattr(m, 'ac_flat', None) is not None:
-            return ((mt.ac_flat, m.ac_flat),)
-        return ((mt.actor_flat, m.actor_flat), (mt.critic_flat, m.critic_flat))
+    def _enqueue_critic_update(self, ws, c, x):
+        """critic c's step from c.dz3 = dLoss/dQ: backward -> perception backward -> rank averaging -> Adam on the critic
+        -> Adam on its perception CNN"""
+        dz1, ld = c.model.critic_backward(x, c.w, ws.bw, c.dz3, c.gv)
+        if self.is_pixel_input:
+            # the critic loss's gradient through the perception CNN (ddpg.py:304-308: critic_loss.backward() reaches
+            # model.perception): d(critic layer 1 input) = dz1 . W1, masked by the feature ReLU, then the stem's own backward
+            model, B = c.model, x.shape[0]
+            self.K.linear(dz1, 1, model.critic['W1'], 0, None, ws.dxin, B, model.input_dim, model.c1, relu_mask=x, lda=ld,
+                          ldb=model.input_dim)
+            model._cnn_stem.backward(model.cnn, B, c.cnn, ws.dxin[:, :model.feat_dim], c.grads_p)
+            self._average_over_ranks(c.grads_p)
+        self._average_over_ranks(c.grads)
+        self._enqueue_adam(ws, c.adam)
+        if self.is_pixel_input:
+            self._enqueue_adam(ws, c.adam_p)
 
-    def _critic_backward_ln(self, ws, model, lw, x, xcat, dz3, gc):
-        """gradients of a LayerNorm critic's parameters from dz3 = dLoss/dQ [B] (builders.py:58-84 with use_layernorm,
-        backwards); leaves dLoss/d(layer-1 pre-LayerNorm output) in ws.dz1c (the perception CNN's way in)"""
-        K, A = self.K, self.action_dim
-        B, D = x.shape
-        c, c1, c2 = model.critic, model.c1, model.c2
-        ld = c1 + A
-        dz3 = dz3.view(B, 1)
-        K.linear_wgrad(dz3, lw.c_n2, gc['W3'], gc['b3'], 1, c2, B, ldz=1)
-        K.linear(dz3, 1, c['W3'], 0, None, ws.dn2, B, c2, 1, lda=1, ldb=c2)                 # d/d(LN2 output)
-        K.layernorm_backward(ws.dn2, lw.c_a2, lw.cm2, lw.cr2, c['ln2.W'], ws.dz2, gc['ln2.W'], gc['ln2.b'], ws.ln_ws,
-                             relu_mask=True)
-        K.linear_wgrad(ws.dz2, xcat, gc['W2'], gc['b2'], c2, c1 + A, B)
-        K.linear(ws.dz2, 1, c['W2'], 0, None, ws.dxcat, B, c1 + A, c2, ldb=ld, ldc=ld)        # d/d([LN1 output | action])
-        K.layernorm_backward(ws.dxcat[:, :c1], lw.c_a1, lw.cm1, lw.cr1, c['ln1.W'], ws.dz1c, gc['ln1.W'], gc['ln1.b'],
-                             ws.ln_ws, relu_mask=True)
-        K.linear_wgrad(ws.dz1c, x, gc['W1'], gc['b1'], c1, D, B)
-
-    def _perception_backward_ln(self, ws, model, xin, cnn_ws, grads_p):
-        """the critic loss through the perception CNN in front of a LayerNorm critic: d(layer-1 input) = dz1c . W1 under the
-        feature ReLU, then the stem's own backward (ws.dz1c still holds THIS critic's layer-1 gradient)"""
-        K = self.K
-        c1, Dx = model.c1, model.input_dim
-        K.linear(ws.dz1c, 1, model.critic['W1'], 0, None, ws.dxin, xin.shape[0], Dx, c1, relu_mask=xin, ldb=Dx)
-        model._cnn_stem.backward(model.cnn, xin.shape[0], cnn_ws, ws.dxin[:, :model.feat_dim], grads_p)
-
-    def _enqueue_iteration_ln(self, ws, x, xn, actions, rewards, done, pix=None, pix_next=None):
-        """one DDPG iteration (ddpg.py:244-352) with use_layernorm = True: every hidden ReLU is followed by a LayerNorm
-        (builders.py:42-48, 65-75), so the networks run layer by layer (smx_linear_f32 + smx_layernorm_*_f32) and the
-        LayerNorms' affine parameters are part of the optimiser groups.  With the TD3 switches (a second LayerNorm critic
-        with its own target and optimiser, ddpg.py:119-147, 266-283, 312-319) and camera observations (the perception CNN
-        in front of both networks, trained by the critic loss, ddpg_net.py:37-88) as in the plain schedule."""
-        K, m, mt, A = self.K, self.model, self.model_target, self.action_dim
+    def _enqueue_iteration_layers(self, ws, x, xn, actions, rewards, done, pix=None, pix_next=None):
+        """one DDPG iteration (ddpg.py:244-352) layer by layer, with every switch: camera observations (the perception CNN
+        in front of both networks, trained by the critic loss, ddpg_net.py:37-88), the TD3 double critic and action
+        regularisation (ddpg.py:119-147, 266-283, 312-319), several ranks -- and use_layernorm, which the model's passes
+        (DDPGModel.actor_forward ... actor_backward) keep to themselves"""
+        K, m, mt = self.K, self.model, self.model_target
         B = x.shape[0]
-        low, low_next = x, xn
-        if self.is_pixel_input:
-            mt.perception_into(pix_next, low_next, ws.cnn_t, ws.xnf)
-            m.perception_into(pix, low, ws.cnn, ws.xf)
-            x, xn = ws.xf, ws.xnf
-        D = x.shape[1]
-        lw, lt = ws.ln, ws.ln_t
-        c, c1, c2, ld = m.critic, m.c1, m.c2, m.c1 + A
-        a, av, aln = m.actor, m.actor.views, m.actor_ln
-        gamma_n = pow(self.discount_factor, self.n_step)
-        # ---- target: y = r + gamma^n * Q'(s', mu'(s')) * (1 - done) ----
-        mt.actor_forward_ln(xn, lt, ws.act)
-        mt.critic_forward_ln(xn, ws.act, lt, ws.xcat_t, ws.q_next)
-        q_next = ws.q_next
-        if self.use_double_critic:           # y = min of the two targets; the noise reaches only the second (ddpg.py:266-283)
-            a2 = ws.act
-            if self.use_action_regularization:
-                torch.add(ws.act, ws.s_noise, out=ws.act_n)
-                ws.act_n.clamp_(-1.0, 1.0)
-                a2 = ws.act_n
-            xn2 = xn
-            if self.is_pixel_input:
-                self.model_target2.perception_into(pix_next, low_next, ws.cnn_t2, ws.xnf2)
-                xn2 = ws.xnf2
-            self.model_target2.critic_forward_ln(xn2, a2, ws.ln_t2, ws.xcat_t2, ws.q_next2)
-            torch.minimum(ws.q_next, ws.q_next2, out=ws.q_next2)
-            q_next = ws.q_next2
-        # ---- critic update(s) ----
-        m.critic_forward_ln(x, actions, lw, ws.xcat, ws.q)
-        x2 = x
-        if self.use_double_critic:
-            if self.is_pixel_input:
-                self.model2.perception_into(pix, low, ws.cnn2, ws.xf2)
-                x2 = ws.xf2
-            self.model2.critic_forward_ln(x2, actions, ws.ln2, ws.xcat2, ws.q2)
-        K.ddpg_critic_loss_step(ws.q, q_next, rewards, done, gamma_n, ws.y, ws.dz3, ws.step)
-        self._critic_backward_ln(ws, m, lw, x, ws.xcat, ws.dz3, ws.gc)
-        if self.is_pixel_input:
-            self._perception_backward_ln(ws, m, x, ws.cnn, ws.grads_p)
-            self._average_over_ranks(ws.grads_p)
-        self._average_over_ranks(ws.grads_c)
-        K.adam_step_dev(m.critic_flat, ws.grads_c, self.critic_exp_avg, self.critic_exp_avg_sq,
-                        ws.lr[1:2], ws.step, self.critic_regularization, self.critic_gradient_clip_value)
-        if self.is_pixel_input:
-            # the critic's optimiser and decay, but no clip: ddpg.py:308-309 clips self.model.critic alone
-            K.adam_step_dev(m.perception_flat, ws.grads_p, self.perc_exp_avg, self.perc_exp_avg_sq,
-                            ws.lr[1:2], ws.step, self.critic_regularization, 0.0)
-        ws.q_policy.copy_(ws.q)
-        if self.use_double_critic:           # ddpg.py:312-319
-            m2 = self.model2
-            K.ddpg_critic_loss(ws.q2, q_next, rewards, done, gamma_n, ws.y2, ws.dz3_2)
-            self._critic_backward_ln(ws, m2, ws.ln2, x2, ws.xcat2, ws.dz3_2, ws.gc2)
-            if self.is_pixel_input:
-                self._perception_backward_ln(ws, m2, x2, ws.cnn2, ws.grads_p2)
-                self._average_over_ranks(ws.grads_p2)
-            self._average_over_ranks(ws.grads_c2)
-            K.adam_step_dev(m2.critic_flat, ws.grads_c2, self.critic2_exp_avg, self.critic2_exp_avg_sq,
-                            ws.lr[1:2], ws.step, self.critic_regularization, self.critic_gradient_clip_value)
-            if self.is_pixel_input:
-                # the critic's optimiser and decay, but no clip: ddpg.py:308-309 clips self.model.critic alone
-                K.adam_step_dev(m2.perception_flat, ws.grads_p2, self.perc2_exp_avg, self.perc2_exp_avg_sq,
-                                ws.lr[1:2], ws.step, self.critic_regularization, 0.0)
-            K.ddpg_stats(ws.q2, ws.y2, rewards, actions, ws.q2, ws.stats2)    # (the SECOND critic's loss is what is reported)
-            self._average_over_ranks(ws.stats2[:6])
-        # ---- actor update through the UPDATED critic: loss = -mean Q(s, mu(s)); the features formed before the critic
-        # step are reused (ddpg.py:287, 326-327: perception.detach()) ----
-        dz3 = ws.dz3.view(B, 1)
-        m.actor_forward_ln(x, lw, ws.act)
-        m.critic_forward_ln(x, ws.act, lw, ws.xcat, ws.q_actor)
-        K.fill(ws.dz3, -1.0 / B)
-        K.linear(dz3, 1, c['W3'], 0, None, ws.dn2, B, c2, 1, lda=1, ldb=c2)
-        K.layernorm_backward(ws.dn2, lw.c_a2, lw.cm2, lw.cr2, c['ln2.W'], ws.dz2, ws.ln_scr[:c2], ws.ln_scr[c2:2 * c2],
-                             ws.ln_ws, relu_mask=True)                                        # (critic gradients discarded)
-        K.linear(ws.dz2, 1, c['W2'][:, c1:], 0, None, ws.dxcat[:, c1:], B, A, c2, ldb=ld, ldc=ld)   # d/d(action)
-        ws.dz3a.copy_(ws.dxcat[:, c1:])
-        K.tanh_backward(ws.dz3a, ws.act, ws.dz3a)
-        ga = ws.ga
-        K.linear_wgrad(ws.dz3a, lw.n2, ga['W3'], ga['b3'], A, a.H2, B)
-        K.linear(ws.dz3a, 1, av['W3'], 0, None, ws.dn2a, B, a.H2, A, ldb=a.H2)
-        K.layernorm_backward(ws.dn2a, lw.a2, lw.am2, lw.ar2, aln['ln2.W'], ws.dz2a, ga['ln2.W'], ga['ln2.b'], ws.ln_ws,
-                             relu_mask=True)
-        K.linear_wgrad(ws.dz2a, lw.n1, ga['W2'], ga['b2'], a.H2, a.H1, B)
-        K.linear(ws.dz2a, 1, av['W2'], 0, None, ws.dn1a, B, a.H1, a.H2, ldb=a.H1)
-        K.layernorm_backward(ws.dn1a, lw.a1, lw.am1, lw.ar1, aln['ln1.W'], ws.dz1a, ga['ln1.W'], ga['ln1.b'], ws.ln_ws,
-                             relu_mask=True)
-        K.linear_wgrad(ws.dz1a, x, ga['W1'], ga['b1'], a.H1, D, B)
-        self._average_over_ranks(ws.grads_a)
-        K.adam_step_dev(m.actor_flat, ws.grads_a, self.actor_exp_avg, self.actor_exp_avg_sq,
-                        ws.lr[0:1], ws.step, self.actor_regularization, self.actor_gradient_clip_value)
-        K.ddpg_stats(ws.q_policy, ws.y, rewards, actions, ws.q_actor, ws.stats)
-        self._average_over_ranks(ws.stats[:6])
-        pairs = list(self._target_pairs(mt, m))
-        if self.is_pixel_input:
-            pairs.append((mt.perception_flat, m.perception_flat))
-        if self.use_double_critic:
-            pairs.append((self.model_target2.critic_flat, self.model2.critic_flat))
-            if self.is_pixel_input:
-                pairs.append((self.model_target2.perception_flat, self.model2.perception_flat))
-        for tgt, src in pairs:
-            if self.target_update_type == 'soft':
-                K.soft_update(tgt, src, self.target_update_tau)
-            else:
-                K.hard_update_every(tgt, src, ws.step, self.target_update_interval)
-
-    def _enqueue_iteration(self, ws, x, xn, actions, rewards, done, pix=None, pix_next=None):
-        """one DDPG iteration (ddpg.py:244-352) as a launch sequence without host round trips"""
-        if self.use_layernorm:
-            return self._enqueue_iteration_ln(ws, x, xn, actions, rewards, done, pix, pix_next)
-        if not (self.is_pixel_input or self.use_double_critic):
-            rows = self.row_schedule if self.row_schedule is not None else x.shape[0] <= 1024
-            if rows and self._rows_dims(x.shape[1], x.shape[0]) is not None:
-                return self._enqueue_iteration_rows(ws, x, xn, actions, rewards, done)
-            if self.level_schedule and self.world_size == 1:
-                return self._enqueue_iteration_levels(ws, x, xn, actions, rewards, done)
-        K, m, mt, A = self.K, self.model, self.model_target, self.action_dim
-        B = x.shape[0]
+        c, c2 = ws.critics[0], ws.critics[1] if self.use_double_critic else None
         low, low_next = x, xn
         if self.is_pixel_input:
             # forward_perception (ddpg_net.py:67-78): [CNN(camera0 / 255) | low_dim]; the model's own
             # features are formed ONCE, before the critic update, and reused by the actor update
             # (ddpg.py:287, 326-327: perception.detach())
-            mt.perception_into(pix_next, low_next, ws.cnn_t, ws.xnf)
-            m.perception_into(pix, low, ws.cnn, ws.xf)
-            x, xn = ws.xf, ws.xnf
+            mt.perception_into(pix_next, low_next, c.cnn_t, c.xnf)
+            m.perception_into(pix, low, c.cnn, c.xf)
+            x, xn = c.xf, c.xnf
         # ---- target: y = r + gamma^n * Q'(s', mu'(s')) * (1 - done) ----
-        K.mlp3_forward(mt.actor, xn, ws.h1a, ws.h2a, ws.act, L.SMX_ACT_TANH)
-        mt.critic_forward_into(xn, ws.act, ws.xcat, ws.h2c, ws.q_next)
+        mt.actor_forward(xn, c.w_t, ws.act)
+        mt.critic_forward(xn, ws.act, c.w_t, ws.q_next)
         q_next, gamma_n = ws.q_next, pow(self.discount_factor, self.n_step)
-        if self.use_double_critic:
+        if c2 is not None:
             # TD3 (ddpg.py:266-283): y = min(y1, y2), the second target critic evaluated at the target
             # policy's action -- with clipped noise added when action regularisation is on (the
             # reference adds it AFTER the first critic's target was formed, so only y2 sees it).
@@ -638,80 +500,60 @@ class DDPGLearner(Learner):
                 a2 = ws.act_n
             xn2 = xn
             if self.is_pixel_input:                  # the second target has its own perception
-                self.model_target2.perception_into(pix_next, low_next, ws.cnn_t2, ws.xnf2)
-                xn2 = ws.xnf2
-            self.model_target2.critic_forward_into(xn2, a2, ws.xcat2, ws.h2c2, ws.q_next2)
+                c2.target.perception_into(pix_next, low_next, c2.cnn_t, c2.xnf)
+                xn2 = c2.xnf
+            c2.target.critic_forward(xn2, a2, c2.w_t, ws.q_next2)
             torch.minimum(ws.q_next, ws.q_next2, out=ws.q_next2)
             q_next = ws.q_next2
         # ---- critic update(s) ----
-        m.critic_forward_into(x, actions, ws.xcat, ws.h2c, ws.q)
+        m.critic_forward(x, actions, c.w, c.q)
         x2 = x
-        if self.use_double_critic:
+        if c2 is not None:
             if self.is_pixel_input:
-                self.model2.perception_into(pix, low, ws.cnn2, ws.xf2)
-                x2 = ws.xf2
-            self.model2.critic_forward_into(x2, actions, ws.xcat2, ws.h2c2, ws.q2)
-        K.ddpg_critic_loss_step(ws.q, q_next, rewards, done, gamma_n, ws.y, ws.dz3, ws.step)
-        self._critic_backward(ws, x, B)
-        if self.is_pixel_input:
-            self._perception_backward(ws, m, x, ws.cnn, ws.grads_p)
-            self._average_over_ranks(ws.grads_p)
-        self._average_over_ranks(ws.grads_c)
-        K.adam_step_dev(m.critic_flat, ws.grads_c, self.critic_exp_avg, self.critic_exp_avg_sq,
-                        ws.lr[1:2], ws.step, self.critic_regularization, self.critic_gradient_clip_value)
-        if self.is_pixel_input:
-            # the critic's optimiser and decay, but no clip: ddpg.py:308-309 clips self.model.critic alone
-            K.adam_step_dev(m.perception_flat, ws.grads_p, self.perc_exp_avg, self.perc_exp_avg_sq,
-                            ws.lr[1:2], ws.step, self.critic_regularization, 0.0)
-        ws.q_policy.copy_(ws.q)
-        if self.use_double_critic:                       # ddpg.py:312-319
-            m2 = self.model2
-            K.ddpg_critic_loss(ws.q2, q_next, rewards, done, gamma_n, ws.y2, ws.dz3_2)
-            self._critic_backward(ws, x2, B, model=m2, dz3=ws.dz3_2, xcat=ws.xcat2, h2c=ws.h2c2, gc=ws.gc2)
-            if self.is_pixel_input:
-                self._perception_backward(ws, m2, x2, ws.cnn2, ws.grads_p2)
-                self._average_over_ranks(ws.grads_p2)
-            self._average_over_ranks(ws.grads_c2)
-            K.adam_step_dev(m2.critic_flat, ws.grads_c2, self.critic2_exp_avg, self.critic2_exp_avg_sq,
-                            ws.lr[1:2], ws.step, self.critic_regularization, self.critic_gradient_clip_value)
-            if self.is_pixel_input:
-                # the critic's optimiser and decay, but no clip: ddpg.py:308-309 clips self.model.critic alone
-                K.adam_step_dev(m2.perception_flat, ws.grads_p2, self.perc2_exp_avg, self.perc2_exp_avg_sq,
-                                ws.lr[1:2], ws.step, self.critic_regularization, 0.0)
+                c2.model.perception_into(pix, low, c2.cnn, c2.xf)
+                x2 = c2.xf
+            c2.model.critic_forward(x2, actions, c2.w, c2.q)
+        K.ddpg_critic_loss_step(c.q, q_next, rewards, done, gamma_n, c.y, c.dz3, ws.step)
+        self._enqueue_critic_update(ws, c, x)
+        ws.q_policy.copy_(c.q)
+        if c2 is not None:                               # ddpg.py:312-319
+            K.ddpg_critic_loss(c2.q, q_next, rewards, done, gamma_n, c2.y, c2.dz3)
+            self._enqueue_critic_update(ws, c2, x2)
             # the reference reports the SECOND critic's loss as 'critic_loss' (it overwrites the
             # variable, ddpg.py:313) and adds Q_policy2
-            K.ddpg_stats(ws.q2, ws.y2, rewards, actions, ws.q2, ws.stats2)
-            self._average_over_ranks(ws.stats2[:6])
+            K.ddpg_stats(c2.q, c2.y, rewards, actions, c2.q, c2.stats)
+            self._average_over_ranks(c2.stats[:6])
         # ---- actor update through the UPDATED critic: loss = -mean Q(s, mu(s)) ----
-        K.mlp3_forward(m.actor, x, ws.h1a, ws.h2a, ws.act, L.SMX_ACT_TANH)
-        m.critic_forward_into(x, ws.act, ws.xcat, ws.h2c, ws.q_actor)
-        K.fill(ws.dz3, -1.0 / B)
-        c, c1, c2 = m.critic, m.c1, m.c2
-        K.linear(ws.dz3.view(B, 1), 1, c['W3'], 0, None, ws.dz2, B, c2, 1, relu_mask=ws.h2c, lda=1,
-                 ldb=c2)
-        K.linear(ws.dz2, 1, c['W2'][:, c1:], 0, None, ws.dxcat[:, c1:], B, A, c2, ldb=c1 + A,
-                 ldc=c1 + A)
-        ws.dz3a.copy_(ws.dxcat[:, c1:])        # dense [B, A]
-        K.tanh_backward(ws.dz3a, ws.act, ws.dz3a)
-        K.mlp3_backward(m.actor, x, ws.h1a, ws.h2a, ws.dz3a, ws.dz2a, ws.dz1a, ws.grads_a, None)
+        m.actor_forward(x, c.w, ws.act)
+        m.critic_forward(x, ws.act, c.w, ws.q_actor)
+        K.fill(c.dz3, -1.0 / B)
+        m.actor_backward(x, c.w, ws.bw, c.dz3, ws.act, ws.ga, ws.grads_a)
         self._average_over_ranks(ws.grads_a)
-        K.adam_step_dev(m.actor_flat, ws.grads_a, self.actor_exp_avg, self.actor_exp_avg_sq,
-                        ws.lr[0:1], ws.step, self.actor_regularization, self.actor_gradient_clip_value)
-        K.ddpg_stats(ws.q_policy, ws.y, rewards, actions, ws.q_actor, ws.stats)
-        self._average_over_ranks(ws.stats[:6])       # means over the global batch (max |a| stays local)
-        # ---- target networks (ddpg.py:389-428) ----
-        pairs = list(self._target_pairs(mt, m))
-        if self.is_pixel_input:
-            pairs.append((mt.perception_flat, m.perception_flat))
-        if self.use_double_critic:
-            pairs.append((self.model_target2.critic_flat, self.model2.critic_flat))
-            if self.is_pixel_input:
-                pairs.append((self.model_target2.perception_flat, self.model2.perception_flat))
-        for tgt, src in pairs:
-            if self.target_update_type == 'soft':
-                K.soft_update(tgt, src, self.target_update_tau)
-            else:
-                K.hard_update_every(tgt, src, ws.step, self.target_update_interval)
+        self._enqueue_adam(ws, ws.adam_actor)
+        K.ddpg_stats(ws.q_policy, c.y, rewards, actions, ws.q_actor, c.stats)
+        self._average_over_ranks(c.stats[:6])       # means over the global batch (max |a| stays local)
+        self._enqueue_target_update(ws)
+
+    def _schedule(self, B, D):
+        """which launch schedule an iteration on B rows of D inputs takes -- 'rows' (row blocks), 'levels' (dependency
+        levels) or 'layers' (layer by layer: every switch).  Asked at each enqueue: level_schedule / row_schedule may be
+        set after construction"""
+        if not (self.use_layernorm or self.is_pixel_input or self.use_double_critic):
+            rows = self.row_schedule if self.row_schedule is not None else B <= 1024
+            if rows and self._rows_dims(D, B) is not None:
+                return 'rows'
+            if self.level_schedule and self.world_size == 1:
+                return 'levels'
+        return 'layers'
+
+    def _enqueue_iteration(self, ws, x, xn, actions, rewards, done, pix=None, pix_next=None):
+        """one DDPG iteration (ddpg.py:244-352) as a launch sequence without host round trips"""
+        schedule = self._schedule(*x.shape)
+        if schedule == 'rows':
+            return self._enqueue_iteration_rows(ws, x, xn, actions, rewards, done)
+        if schedule == 'levels':
+            return self._enqueue_iteration_levels(ws, x, xn, actions, rewards, done)
+        return self._enqueue_iteration_layers(ws, x, xn, actions, rewards, done, pix, pix_next)
 
     def _optimize(self, obs, actions, rewards, obs_next, done):       # ddpg.py:244-352
         x = obs['low_dim']['flat_inputs']
@@ -725,23 +567,18 @@ class DDPGLearner(Learner):
             ws.lr_host = (self.lr_actor, self.lr_critic)
             ws.lr.copy_(torch.tensor(ws.lr_host, dtype=torch.float32))
         # (a batch sampled straight into staging_fields() is already where the captured iteration reads it)
-        for dst, src in ((ws.s_obs, x), (ws.s_next, xn), (ws.s_act, actions.reshape(B, -1)), (ws.s_rew, rewards.reshape(-1)),
-                         (ws.s_done, done.reshape(-1))):
-            # "already staged" means the SAME buffer, not merely the same address: a strided / reshaped view that starts at
-            # the staging buffer's address is copied like any other source
-            if not (src.data_ptr() == dst.data_ptr() and src.shape == dst.shape and src.stride() == dst.stride()
-                    and src.dtype == dst.dtype):
-                dst.copy_(src)
+        _stage(ws.s_obs, x)
+        _stage(ws.s_next, xn)
+        _stage(ws.s_act, actions.reshape(B, -1))
+        _stage(ws.s_rew, rewards.reshape(-1))
+        _stage(ws.s_done, done.reshape(-1))
         frames = ()
         if self.is_pixel_input:
             pix, pix_next = obs['pixel']['camera0'], obs_next['pixel']['camera0']
             if ws.s_pix is None or ws.s_pix.dtype != pix.dtype:
-                ws.s_pix, ws.s_pix_next = torch.empty_like(pix), torch.empty_like(pix_next)
-                ws.graph = None
-            for dst, src in ((ws.s_pix, pix), (ws.s_pix_next, pix_next)):     # (the same "same buffer" rule)
-                if not (src.data_ptr() == dst.data_ptr() and src.shape == dst.shape and src.stride() == dst.stride()
-                        and src.dtype == dst.dtype):
-                    dst.copy_(src)
+                self._alloc_frame_staging(ws, pix.shape, pix.dtype)
+            _stage(ws.s_pix, pix)
+            _stage(ws.s_pix_next, pix_next)
             frames = (ws.s_pix, ws.s_pix_next)
         if self.use_action_regularization:
             # ddpg.py:268-274: policy_noise 0.2 clipped at 0.5, from numpy's global stream
@@ -774,24 +611,26 @@ class DDPGLearner(Learner):
             self.target_update_counter += 1
         return self._collect_stats(ws)
 
+    def _alloc_frame_staging(self, ws, shape, dtype):
+        """the staged camera frames of s and s' (again): the captured iteration read the old ones, so the graph goes"""
+        ws.s_pix = torch.empty(tuple(shape), device=self.device, dtype=dtype)
+        ws.s_pix_next = torch.empty(tuple(shape), device=self.device, dtype=dtype)
+        ws.graph = None
+
     def staging_fields(self, batch_size):
         """the buffers the captured iteration reads its batch from, by replay field name:
         ``replay.sample_batch(B, out=learner.staging_fields(B))`` gathers the sample where learn() would otherwise copy
         it (five small copies per iteration, 6 % of one at batch 512).  A camera learner also stages 'pixel' and
         'pixel_next', uint8 [B] + obs_spec camera0 (allocated here on first use, kept while their dtype holds)"""
         B = int(batch_size)
-        if not self.is_pixel_input:
-            ws = self._workspace(B, self.model.input_dim)
-            return {'obs': ws.s_obs, 'obs_next': ws.s_next, 'actions': ws.s_act, 'rewards': ws.s_rew,
-                    'dones': ws.s_done}
         ws = self._workspace(B, self.model.low_dim)      # (_optimize keys it by the low-dimensional width)
-        cam = (B,) + tuple(int(v) for v in self.env_config.obs_spec['pixel']['camera0'])
-        if ws.s_pix is None or ws.s_pix.dtype != torch.uint8 or tuple(ws.s_pix.shape) != cam:
-            ws.s_pix = torch.empty(cam, device=self.device, dtype=torch.uint8)
-            ws.s_pix_next = torch.empty(cam, device=self.device, dtype=torch.uint8)
-            ws.graph = None
-        return {'obs': ws.s_obs, 'obs_next': ws.s_next, 'actions': ws.s_act, 'rewards': ws.s_rew, 'dones': ws.s_done,
-                'pixel': ws.s_pix, 'pixel_next': ws.s_pix_next}
+        fields = {'obs': ws.s_obs, 'obs_next': ws.s_next, 'actions': ws.s_act, 'rewards': ws.s_rew, 'dones': ws.s_done}
+        if self.is_pixel_input:
+            cam = (B,) + tuple(int(v) for v in self.env_config.obs_spec['pixel']['camera0'])
+            if ws.s_pix is None or ws.s_pix.dtype != torch.uint8 or tuple(ws.s_pix.shape) != cam:
+                self._alloc_frame_staging(ws, cam, torch.uint8)
+            fields['pixel'], fields['pixel_next'] = ws.s_pix, ws.s_pix_next
+        return fields
 
     def _collect_stats(self, ws):
         """the iteration's one read-back; asynchronous on a GPU (resolved when looked at, at the latest

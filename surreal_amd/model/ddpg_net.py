@@ -13,6 +13,7 @@ features are concatenated IN FRONT of the low-dim vector; it trains with the cri
 One flat fp32 parameter buffer per network (actor / critic / perception).
 """
 import collections
+import types
 
 import numpy as np
 import torch
@@ -174,35 +175,60 @@ class DDPGModel(object):
         self.perception_into(frames, obs['low_dim']['flat_inputs'] if self.low_dim else None, cws, out)
         return out
 
-    # ---- the LayerNorm variant: layer by layer, the LayerNorm inputs and row statistics kept for a backward pass ----
-    def _ln_workspace_cached(self, rows, device):
-        """the per-step act path (forward_actor / forward_critic): one workspace per (rows, device), not ~14 allocations
-        per call"""
+    # ---- actor / critic passes in a workspace: ONE calling shape, the plain and the LayerNorm variant behind it ----
+    def _workspace_cached(self, rows, device):
+        """the per-step act path (forward_actor / forward_critic): one workspace per (rows, device), not an allocation
+        per buffer and call"""
         key = (int(rows), str(device))
-        cache = self.__dict__.setdefault('_ln_ws_cache', {})
+        cache = self.__dict__.setdefault('_ws_cache', {})
         if key not in cache:
             if len(cache) > 8:
                 cache.clear()
-            cache[key] = self.ln_workspace(rows, device)
+            cache[key] = self.workspace(rows, device)
         return cache[key]
 
-    def ln_workspace(self, rows, device=None):
-        """buffers of one actor and one critic pass with LayerNorm (activations in front of each LayerNorm, its outputs,
-        row means / reciprocal standard deviations)"""
-        import types
+    def workspace(self, rows, device=None):
+        """what one actor and one critic pass keep for a backward pass: the hidden activations h1a / h2a and xcat =
+        [layer 1 | action] / h2c -- with LayerNorm the activations in front of each LayerNorm, its outputs and the row
+        means / reciprocal standard deviations instead"""
         f = lambda *s: torch.empty(*s, device=device or self.device)  # noqa: E731
-        w = types.SimpleNamespace()
-        if self.actor is not None:
-            a = self.actor
+        w = types.SimpleNamespace(xcat=f(rows, self.c1 + self.action_dim))
+        a = self.actor
+        if not self.use_layernorm:
+            if a is not None:
+                w.h1a, w.h2a = f(rows, a.H1), f(rows, a.H2)
+            w.h2c = f(rows, self.c2)
+            return w
+        if a is not None:
             w.a1, w.n1, w.a2, w.n2 = f(rows, a.H1), f(rows, a.H1), f(rows, a.H2), f(rows, a.H2)
             w.am1, w.ar1, w.am2, w.ar2 = f(rows), f(rows), f(rows), f(rows)
         w.c_a1, w.c_a2, w.c_n2 = f(rows, self.c1), f(rows, self.c2), f(rows, self.c2)
         w.cm1, w.cr1, w.cm2, w.cr2 = f(rows), f(rows), f(rows), f(rows)
         return w
 
-    def actor_forward_ln(self, x, w, out):
-        """out = tanh(fc3(LN(relu(fc2(LN(relu(fc1 x)))))))   (builders.py:35-56 with use_layernorm)"""
-        K, a, v, ln = self.K, self.actor, self.actor.views, self.actor_ln
+    def target_workspace(self, w, rows, device=None):
+        """where a target copy of the network whose passes run in `w` runs: the plain variant's target passes go through
+        `w` itself, ahead of the network's own; the LayerNorm variant keeps them apart"""
+        return self.workspace(rows, device) if self.use_layernorm else w
+
+    def backward_workspace(self, rows, device=None):
+        """scratch of critic_backward / actor_backward (one at a time: every critic of a learner shares it)"""
+        f = lambda *s: torch.empty(*s, device=device or self.device)  # noqa: E731
+        a, A, c1, c2 = self.actor, self.action_dim, self.c1, self.c2
+        s = types.SimpleNamespace(dz2=f(rows, c2), dxcat=f(rows, c1 + A), dz3a=f(rows, A), dz2a=f(rows, a.H2),
+                                  dz1a=f(rows, a.H1))
+        if self.use_layernorm:
+            s.dn2, s.dz1c, s.dn2a, s.dn1a = f(rows, c2), f(rows, c1), f(rows, a.H2), f(rows, a.H1)
+            s.ln_ws = f(max(self.K.layernorm_backward_ws_floats(rows, k) for k in (c1, c2, a.H1, a.H2)))
+            s.ln_scr = f(2 * max(c1, c2))
+        return s
+
+    def actor_forward(self, x, w, out):
+        """out = tanh(fc3(relu(fc2(relu(fc1 x))))), a LayerNorm behind each ReLU with use_layernorm (builders.py:35-56)"""
+        K, a = self.K, self.actor
+        if not self.use_layernorm:
+            return K.mlp3_forward(a, x, w.h1a, w.h2a, out, 2)
+        v, ln = a.views, self.actor_ln
         rows, D = x.shape
         K.linear(x, 1, v['W1'], 1, v['b1'], w.a1, rows, a.H1, D, act=1)
         K.layernorm_forward(w.a1, ln['ln1.W'], ln['ln1.b'], self.ln_eps, w.n1, w.am1, w.ar1)
@@ -210,11 +236,18 @@ class DDPGModel(object):
         K.layernorm_forward(w.a2, ln['ln2.W'], ln['ln2.b'], self.ln_eps, w.n2, w.am2, w.ar2)
         K.linear(w.n2, 1, v['W3'], 1, v['b3'], out, rows, a.OUT, a.H2, act=2)
 
-    def critic_forward_ln(self, x, action, w, xcat, q):
-        """xcat [rows, c1 + A] receives LN(relu(fc1 x)) | action; q [rows]   (builders.py:58-84 with use_layernorm)"""
+    def critic_forward(self, x, action, w, q):
+        """q [rows] = Q(x, action); w.xcat [rows, c1 + A] receives (LN of) relu(fc1 x) | action   (builders.py:58-84)"""
         K, c = self.K, self.critic
         rows, D = x.shape
         A, c1, c2 = self.action_dim, self.c1, self.c2
+        xcat = w.xcat
+        if not self.use_layernorm:
+            K.linear(x, 1, c['W1'], 1, c['b1'], xcat, rows, c1, D, act=1, ldc=c1 + A)
+            xcat[:, c1:].copy_(action)
+            K.linear(xcat, 1, c['W2'], 1, c['b2'], w.h2c, rows, c2, c1 + A, act=1)
+            K.linear(w.h2c, 1, c['W3'], 1, c['b3'], q.view(rows, 1), rows, 1, c2, act=0)
+            return
         K.linear(x, 1, c['W1'], 1, c['b1'], w.c_a1, rows, c1, D, act=1)
         K.layernorm_forward(w.c_a1, c['ln1.W'], c['ln1.b'], self.ln_eps, xcat[:, :c1], w.cm1, w.cr1)
         xcat[:, c1:].copy_(action)
@@ -222,40 +255,73 @@ class DDPGModel(object):
         K.layernorm_forward(w.c_a2, c['ln2.W'], c['ln2.b'], self.ln_eps, w.c_n2, w.cm2, w.cr2)
         K.linear(w.c_n2, 1, c['W3'], 1, c['b3'], q.view(rows, 1), rows, 1, c2, act=0)
 
-    def forward_actor(self, x):
-        a = self.actor
-        rows = x.shape[0]
-        if self.use_layernorm:
-            out = torch.empty(rows, a.OUT, device=x.device)
-            self.actor_forward_ln(x.contiguous(), self._ln_workspace_cached(rows, x.device), out)
-            return out
-        h1 = torch.empty(rows, a.H1, device=x.device)
-        h2 = torch.empty(rows, a.H2, device=x.device)
-        out = torch.empty(rows, a.OUT, device=x.device)
-        self.K.mlp3_forward(a, x.contiguous(), h1, h2, out, 2)
-        return out
-
-    def critic_forward_into(self, x, action, xcat, h2, q):
-        """xcat [rows, c1+A] receives relu(layer1) | action; h2 [rows, c2]; q [rows]"""
+    def critic_backward(self, x, w, s, dq, g):
+        """gradients g (views by parameter name) of the critic's parameters from dq = dLoss/dQ [rows], behind
+        critic_forward(x, ., w, .); dLoss/d(action) is left in the last A columns of s.dxcat.
+        -> (dLoss/d(layer 1's output in front of its ReLU), its leading dimension): the perception CNN's way in"""
         K, c = self.K, self.critic
         rows, D = x.shape
         A, c1, c2 = self.action_dim, self.c1, self.c2
-        K.linear(x, 1, c['W1'], 1, c['b1'], xcat, rows, c1, D, act=1, ldc=c1 + A)
-        xcat[:, c1:].copy_(action)
-        K.linear(xcat, 1, c['W2'], 1, c['b2'], h2, rows, c2, c1 + A, act=1)
-        K.linear(h2, 1, c['W3'], 1, c['b3'], q.view(rows, 1), rows, 1, c2, act=0)
+        ld = c1 + A
+        dq = dq.view(rows, 1)
+        if not self.use_layernorm:
+            K.linear(dq, 1, c['W3'], 0, None, s.dz2, rows, c2, 1, relu_mask=w.h2c, lda=1, ldb=c2)
+            # d/d(relu(layer1)) masked by relu', into the first c1 columns of dxcat
+            K.linear(s.dz2, 1, c['W2'], 0, None, s.dxcat, rows, c1, c2, relu_mask=w.xcat, ldb=ld, ldc=ld)
+            # d/d(action) into the last A columns (no mask)
+            K.linear(s.dz2, 1, c['W2'][:, c1:], 0, None, s.dxcat[:, c1:], rows, A, c2, ldb=ld, ldc=ld)
+            K.linear_wgrad(s.dxcat, x, g['W1'], g['b1'], c1, D, rows, ldz=ld)
+            K.linear_wgrad(s.dz2, w.xcat, g['W2'], g['b2'], c2, ld, rows)
+            K.linear_wgrad(dq, w.h2c, g['W3'], g['b3'], 1, c2, rows, ldz=1)
+            return s.dxcat, ld
+        K.linear_wgrad(dq, w.c_n2, g['W3'], g['b3'], 1, c2, rows, ldz=1)
+        K.linear(dq, 1, c['W3'], 0, None, s.dn2, rows, c2, 1, lda=1, ldb=c2)                 # d/d(LN2 output)
+        K.layernorm_backward(s.dn2, w.c_a2, w.cm2, w.cr2, c['ln2.W'], s.dz2, g['ln2.W'], g['ln2.b'], s.ln_ws, relu_mask=True)
+        K.linear_wgrad(s.dz2, w.xcat, g['W2'], g['b2'], c2, ld, rows)
+        K.linear(s.dz2, 1, c['W2'], 0, None, s.dxcat, rows, ld, c2, ldb=ld, ldc=ld)        # d/d([LN1 output | action])
+        K.layernorm_backward(s.dxcat[:, :c1], w.c_a1, w.cm1, w.cr1, c['ln1.W'], s.dz1c, g['ln1.W'], g['ln1.b'], s.ln_ws,
+                             relu_mask=True)
+        K.linear_wgrad(s.dz1c, x, g['W1'], g['b1'], c1, D, rows)
+        return s.dz1c, c1
+
+    def actor_backward(self, x, w, s, dq, act, g, g_flat):
+        """gradients of the actor's parameters (g_flat, g its views by name) from dq = dLoss/dQ(x, act) [rows], behind
+        actor_forward(x, w, act) and critic_forward(x, act, w, .); the critic's own gradients are not formed"""
+        K, a, c = self.K, self.actor, self.critic
+        rows, D = x.shape
+        A, c1, c2 = self.action_dim, self.c1, self.c2
+        ld = c1 + A
+        dq = dq.view(rows, 1)
+        if not self.use_layernorm:
+            K.linear(dq, 1, c['W3'], 0, None, s.dz2, rows, c2, 1, relu_mask=w.h2c, lda=1, ldb=c2)
+        else:
+            K.linear(dq, 1, c['W3'], 0, None, s.dn2, rows, c2, 1, lda=1, ldb=c2)
+            K.layernorm_backward(s.dn2, w.c_a2, w.cm2, w.cr2, c['ln2.W'], s.dz2, s.ln_scr[:c2], s.ln_scr[c2:2 * c2], s.ln_ws,
+                                 relu_mask=True)
+        K.linear(s.dz2, 1, c['W2'][:, c1:], 0, None, s.dxcat[:, c1:], rows, A, c2, ldb=ld, ldc=ld)   # d/d(action)
+        s.dz3a.copy_(s.dxcat[:, c1:])        # dense [rows, A]
+        K.tanh_backward(s.dz3a, act, s.dz3a)
+        if not self.use_layernorm:
+            return K.mlp3_backward(a, x, w.h1a, w.h2a, s.dz3a, s.dz2a, s.dz1a, g_flat, None)
+        v, ln = a.views, self.actor_ln
+        K.linear_wgrad(s.dz3a, w.n2, g['W3'], g['b3'], A, a.H2, rows)
+        K.linear(s.dz3a, 1, v['W3'], 0, None, s.dn2a, rows, a.H2, A, ldb=a.H2)
+        K.layernorm_backward(s.dn2a, w.a2, w.am2, w.ar2, ln['ln2.W'], s.dz2a, g['ln2.W'], g['ln2.b'], s.ln_ws, relu_mask=True)
+        K.linear_wgrad(s.dz2a, w.n1, g['W2'], g['b2'], a.H2, a.H1, rows)
+        K.linear(s.dz2a, 1, v['W2'], 0, None, s.dn1a, rows, a.H1, a.H2, ldb=a.H1)
+        K.layernorm_backward(s.dn1a, w.a1, w.am1, w.ar1, ln['ln1.W'], s.dz1a, g['ln1.W'], g['ln1.b'], s.ln_ws, relu_mask=True)
+        K.linear_wgrad(s.dz1a, x, g['W1'], g['b1'], a.H1, D, rows)
+
+    def forward_actor(self, x):
+        rows = x.shape[0]
+        out = torch.empty(rows, self.actor.OUT, device=x.device)
+        self.actor_forward(x.contiguous(), self._workspace_cached(rows, x.device), out)
+        return out
 
     def forward_critic(self, x, action):
         rows = x.shape[0]
-        if self.use_layernorm:
-            xcat = torch.empty(rows, self.c1 + self.action_dim, device=x.device)
-            q = torch.empty(rows, device=x.device)
-            self.critic_forward_ln(x.contiguous(), action, self._ln_workspace_cached(rows, x.device), xcat, q)
-            return q.view(rows, 1)
-        xcat = torch.empty(rows, self.c1 + self.action_dim, device=x.device)
-        h2 = torch.empty(rows, self.c2, device=x.device)
         q = torch.empty(rows, device=x.device)
-        self.critic_forward_into(x.contiguous(), action, xcat, h2, q)
+        self.critic_forward(x.contiguous(), action, self._workspace_cached(rows, x.device), q)
         return q.view(rows, 1)
 
     def __deepcopy__(self, memo):
