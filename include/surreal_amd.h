@@ -1304,6 +1304,47 @@ struct smx_ddpg_population_rollout {       /* (by tag: no typedef) */
 int32_t smx_synth_ddpg_population_block(int32_t n, int32_t actors_per_agent, int32_t forced);
 int smx_synth_ddpg_population_rollout_f32(const struct smx_ddpg_population_rollout* args, smx_stream_t stream);
 
+/* The one-launch rollouts for an actor with a LayerNorm behind each hidden ReLU (DDPGModel, use_layernorm):
+ *   h1 = LN1(relu(W1 x + b1)), h2 = LN2(relu(W2 h1 + b2)), mu = tanh(W3 h2 + b3)
+ * LN as smx_layernorm_forward_f32 (torch.nn.LayerNorm(F): biased variance, eps inside the square root, elementwise
+ * affine), in its summation order: given the same ReLU row, the normalised row has that function's bits, at every block
+ * size.  ln: ln1.W [H1] | ln1.b [H1] | ln2.W [H2] | ln2.b [H2], contiguous (the tail of DDPGModel's actor parameters);
+ * eps > 0.  Everything else is smx_synth_ddpg_rollout_f32 on `base`. */
+struct smx_ddpg_ln_rollout {               /* (by tag: no typedef) */
+    smx_ddpg_rollout_t base;
+    const float* ln;
+    float eps;
+    int32_t reserved;
+};
+/* shapes smx_synth_ddpg_ln_rollout_f32 takes: those of smx_synth_ddpg_rollout_supported whose 16-actor layout still
+ * holds the 2 (H1 + H2) LayerNorm floats */
+int32_t smx_synth_ddpg_ln_rollout_supported(int32_t D, int32_t H1, int32_t H2, int32_t A);
+int smx_synth_ddpg_ln_rollout_f32(const struct smx_ddpg_ln_rollout* args, smx_stream_t stream);
+
+/* Parameter-space noise over a LayerNorm actor: the flat parameters of struct smx_param_noise go on with ln1.W | ln1.b |
+ * ln2.W | ln2.b (element indices i behind b3's: the first six arrays keep theirs, so they are perturbed as without a
+ * LayerNorm), the same rule.  An agent's copy: smx_param_noise_refresh_f32's, the perturbed four behind the biases, zeros
+ * up to smx_param_noise_ln_copy_floats (a multiple of 64); base.packed_stride >= that. */
+struct smx_param_noise_ln {                /* (by tag: no typedef) */
+    struct smx_param_noise base;
+    const float* ln;                       /* the clean ln1.W | ln1.b | ln2.W | ln2.b */
+};
+int64_t smx_param_noise_ln_copy_floats(int32_t D, int32_t H1, int32_t H2, int32_t OUT);
+/* out [.. + OUT + 2 (H1 + H2)] <- agent p's perturbed flat parameters */
+int smx_param_noise_ln_fill_f32(const struct smx_param_noise_ln* pn, int32_t p, float* out, smx_stream_t stream);
+int smx_param_noise_ln_refresh_f32(const struct smx_param_noise_ln* pn, smx_stream_t stream);
+
+/* smx_synth_ddpg_population_rollout_f32 for a LayerNorm actor: pop.packed_pop holds smx_param_noise_ln_refresh_f32's
+ * copies, every agent's layers and LayerNorms run from its copy; the clean actor of the measuring step is pop.base.net,
+ * pop.base.packed and ln. */
+struct smx_ddpg_ln_population_rollout {    /* (by tag: no typedef) */
+    struct smx_ddpg_population_rollout pop;
+    const float* ln;
+    float eps;
+    int32_t reserved;
+};
+int smx_synth_ddpg_ln_population_rollout_f32(const struct smx_ddpg_ln_population_rollout* args, smx_stream_t stream);
+
 /* The same step for actors with a camera (the reference's pixel DDPG configurations, ddpg_configs.py:176-228:
  * FrameStackWrapper in front of a CNN perception): smx_synth_ddpg_step_f32 on args->base (mu [n, A] = the actor's
  * output on the perception of obs_pixel), and the frames in the same launch.  F = C*H*W bytes per frame, S =

@@ -12,7 +12,9 @@ staging buffers and learn().
 With --calls N: only N single `ddpg_rollout_into` calls, each as a user makes it and timed by itself -> one line with
 their median (and, with --param-noise, the time of DeviceParamNoise.refresh()).  --param-noise attaches per-agent
 parameter-space noise (attach_param_noise, --actors-per-agent K actors an agent): the population launch; it needs --calls,
-since the per-step path and the plain kernel's forced blocks have no such launch.
+since the per-step path and the plain kernel's forced blocks have no such launch.  --layernorm: a LayerNorm actor
+(use_layernorm, random gains and biases), combinable with --param-noise and --device-noise; with --calls, --per-step times
+its per-step path (reference=True) instead of the one launch.
 
 Prints one JSON line per measurement (and a summary line)."""
 import argparse
@@ -60,15 +62,20 @@ def main():
                     help='attach per-agent parameter-space noise (adaptive_normal): every agent acts from its own perturbed '
                          'copy of the actor, made and measured on the device; needs --calls')
     ap.add_argument('--actors-per-agent', type=int, default=4, help='actors that share one perturbation (a multiple of 4)')
+    ap.add_argument('--layernorm', action='store_true', help='a LayerNorm behind each hidden ReLU of the actor and critic')
+    ap.add_argument('--per-step', action='store_true', help='with --layernorm --calls: the per-step path (reference=True)')
     ap.add_argument('--calls', type=int, default=0, help='time this many single rollout calls, print their median and stop')
     ap.add_argument('--label', default='', help='copied into the --calls line')
     args = ap.parse_args()
     if args.param_noise and not args.calls:
         ap.error('--param-noise measures single calls: give --calls N')
+    if args.per_step and not (args.layernorm and args.calls and not args.param_noise):
+        ap.error('--per-step goes with --layernorm --calls N, without --param-noise')
     n, T, D, A = args.actors, args.steps, args.obs_dim, args.action_dim
     H1, H2 = args.hidden
     lc = ddpg_learner_config()
     lc.model.actor_fc_hidden_sizes = [H1, H2]
+    lc.model.use_layernorm = args.layernorm
     lc.algo.exploration.noise_type = args.noise
     if args.param_noise:
         lc.algo.exploration.param_noise_type = 'adaptive_normal'
@@ -76,6 +83,9 @@ def main():
     lc.replay.batch_size = args.batch
     ec, sc = ddpg_env_config(D, A, num_agents=n), ddpg_session_config()
     agent = DDPGAgent(lc, ec, sc, agent_id=0, agent_mode='training')
+    if args.layernorm:                         # (the defaults 1 / 0 would time an affine step of ones and zeros)
+        for k, v in agent.model.actor_ln.items():
+            v.copy_(torch.rand_like(v) + 0.5 if k.endswith('.W') else 0.1 * torch.randn_like(v))
     flops = 2.0 * n * T * (D * H1 + H1 * H2 + H2 * A)
     venv = SyntheticVecEnv(n, D, A, episode_len=args.episode_len, device='cuda')
     mon = venv.attach_monitor() if args.monitor else None
@@ -94,7 +104,7 @@ def main():
     for path in ('persistent', 'per_step'):
         replay = UniformReplay(lc, ec, sc)
         if path == 'per_step':              # the per-step path: what a LayerNorm actor or an unsupported shape takes
-            venv.K.synth_ddpg_rollout_supported = lambda net: False
+            venv.K.synth_ddpg_rollout_supported = venv.K.synth_ddpg_ln_rollout_supported = lambda net: False
         try:
             venv.reset()
             venv.ddpg_rollout_into(agent, replay, T, eps=eps)           # warm-up (tables, packed copy, code)
@@ -110,7 +120,7 @@ def main():
             dev = e0.elapsed_time(e1) / 1e3 / args.reps
         finally:
             if path == 'per_step':
-                del venv.K.synth_ddpg_rollout_supported
+                del venv.K.synth_ddpg_rollout_supported, venv.K.synth_ddpg_ln_rollout_supported
         r = {'what': 'ddpg_rollout', 'path': path, 'actors': n, 'steps': T, 'shape': [D, H1, H2, A],
              'ms_per_rollout': round(dev * 1e3, 4), 'wall_ms_per_rollout': round(wall * 1e3, 4),
              'env_steps_per_s': n * T / dev, 'actor_tflops': flops / dev / 1e12,
@@ -186,12 +196,12 @@ def timed(f, k):
 def single_calls(args, agent, venv, replay, eps):
     n, T = args.actors, args.steps
     pn = venv.attach_param_noise(agent, seed=2, actors_per_agent=args.actors_per_agent) if args.param_noise else None
-    call = lambda: venv.ddpg_rollout_into(agent, replay, T, eps=eps)  # noqa: E731
+    call = lambda: venv.ddpg_rollout_into(agent, replay, T, eps=eps, reference=args.per_step)  # noqa: E731
     for _ in range(3):
         call()
     ms = timed(call, args.calls)
     line = {'what': 'ddpg_rollout_calls', 'label': args.label, 'actors': n, 'steps': T, 'calls': args.calls,
-            'param_noise': bool(pn), 'actors_per_agent': args.actors_per_agent if pn else None,
+            'layernorm': args.layernorm, 'per_step': args.per_step, 'param_noise': bool(pn), 'actors_per_agent': args.actors_per_agent if pn else None,
             'agents': pn.agents if pn else None, 'median_ms': round(ms[len(ms) // 2], 4),
             'fastest_tenth_ms': round(ms[len(ms) // 10], 4), 'slowest_ms': round(ms[-1], 4),
             'env_steps_per_s': n * T / (ms[len(ms) // 2] / 1e3)}

@@ -210,6 +210,21 @@ class DdpgPopulationRollout(Structure):
                 ('dist', c_void_p)]
 
 
+class DdpgLnRollout(Structure):
+    """struct smx_ddpg_ln_rollout"""
+    _fields_ = [('base', DdpgRollout), ('ln', c_void_p), ('eps', c_float), ('reserved', c_int32)]
+
+
+class ParamNoiseLn(Structure):
+    """struct smx_param_noise_ln"""
+    _fields_ = [('base', ParamNoise), ('ln', c_void_p)]
+
+
+class DdpgLnPopulationRollout(Structure):
+    """struct smx_ddpg_ln_population_rollout"""
+    _fields_ = [('pop', DdpgPopulationRollout), ('ln', c_void_p), ('eps', c_float), ('reserved', c_int32)]
+
+
 class DdpgPixelStep(Structure):
     """struct smx_ddpg_pixel_step"""
     _fields_ = [('base', DdpgRollout), ('C', c_int32), ('H', c_int32), ('W', c_int32), ('frame_stacks', c_int32),
@@ -423,6 +438,12 @@ _SIGS = {
     'smx_param_noise_refresh_f32': (c_int32, [POINTER(ParamNoise), _P]),
     'smx_synth_ddpg_population_block': (c_int32, [c_int32, c_int32, c_int32]),
     'smx_synth_ddpg_population_rollout_f32': (c_int32, [POINTER(DdpgPopulationRollout), _P]),
+    'smx_synth_ddpg_ln_rollout_supported': (c_int32, [c_int32, c_int32, c_int32, c_int32]),
+    'smx_synth_ddpg_ln_rollout_f32': (c_int32, [POINTER(DdpgLnRollout), _P]),
+    'smx_param_noise_ln_copy_floats': (c_int64, [c_int32, c_int32, c_int32, c_int32]),
+    'smx_param_noise_ln_fill_f32': (c_int32, [POINTER(ParamNoiseLn), c_int32, _P, _P]),
+    'smx_param_noise_ln_refresh_f32': (c_int32, [POINTER(ParamNoiseLn), _P]),
+    'smx_synth_ddpg_ln_population_rollout_f32': (c_int32, [POINTER(DdpgLnPopulationRollout), _P]),
     'smx_synth_ppo_pixel_window_step': (c_int32, [POINTER(SynthPpoPixelWindowStep), _P, c_int64, _P]),
     'smx_xchg_bytes': (c_int64, [c_int64, c_int32]),
     'smx_xchg_alloc': (c_int32, [c_int64, c_double, POINTER(c_void_p), POINTER(c_int32), _P]),

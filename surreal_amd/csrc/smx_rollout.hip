@@ -23,6 +23,8 @@
 //                               noise, smx_param_noise.hip): ddpg_rollout_kernel<RG, NT, true>, each workgroup's layers run
 //                               from the copy of the agent its actors belong to; one step of the call can measure the
 //                               agents' action distance against the clean actor.
+//   smx_synth_ddpg_ln_rollout_f32 / smx_synth_ddpg_ln_population_rollout_f32   both for an actor with a LayerNorm behind
+//                               each hidden ReLU: ddpg_rollout_kernel<RG, NT, POP, true>, ln_rows over the hidden tiles
 //   smx_synth_ddpg_step_f32     one DDPG step for all actors given the actor's output mu [n, A] from any forward
 //                               (LayerNorm actors, unsupported shapes; with smx_epoch_forward_f32 the persistent kernel's
 //                               two-launch reference).
@@ -147,6 +149,18 @@ struct PopArgs : DArgs {
     int apa, measure_step;                      // actors per agent; the step that measures the action distance or -1
     double* dist;                               // [agents]
 };
+
+// a LayerNorm behind each hidden ReLU (ddpg_rollout_kernel<RG, NT, POP, true>): g = ln1.W [H1] | ln1.b [H1] | ln2.W [H2]
+// | ln2.b [H2] of the clean actor; pop: the same block of AGENT 0's copy (the population rollout)
+struct LnTail {
+    const float *g, *pop;
+    float eps;
+    int off;                                    // the block the workgroup's layers use, in LDS (carve_ln())
+};
+struct DLnArgs : DArgs { LnTail ln; };
+struct PopLnArgs : PopArgs { LnTail ln; };
+template <bool POP, bool LN>
+using DdpgArgs = std::conditional_t<LN, std::conditional_t<POP, PopLnArgs, DLnArgs>, std::conditional_t<POP, PopArgs, DArgs>>;
 
 // ---- once per launch: clear the tiles (their padding columns and rows must read as zeros, the action tile's unused
 // columns too); k % A (an integer division per element and step otherwise) and, with the z-filter's running sums, its
@@ -930,14 +944,58 @@ __device__ __forceinline__ long long ring_row(const DArgs& G, int kemit, long a)
     return (G.cursor + (long long)kemit * G.n + a) % G.capacity;
 }
 
+// LayerNorm over the F features of the block's RB rows of a hidden tile, in place (behind the barrier that ends the
+// layer; the caller barriers after it).  One wavefront owns a row, the rows dealt over the RNWV waves; lane j takes the
+// columns j + 64 c, c ascending, and the expressions are layernorm_fwd_kernel's (smx_ddpg.hip), its zero terms for the
+// columns past F left out: given the same row the result has the bits smx_layernorm_forward_f32 produces, whatever RB
+// and whichever wave.  Only columns < F are written: the tile's padding stays zero.  A lane's columns are consecutive
+// words across the wave: no bank is hit twice.  gb = gamma [F] | beta [F].
+constexpr int RLN_MAXC = 10;                         // columns per lane: H1, H2 <= 640
+template <int RB>
+__device__ __forceinline__ void ln_rows(float* tile, int ld, int F, const float* gb, float eps, int wv, int lane) {
+#pragma unroll 1
+    for (int r = wv; r < RB; r += RNWV) {
+        float* xr = tile + r * ld;
+        float v[RLN_MAXC];
+        float s = 0.f;
+#pragma unroll
+        for (int c = 0; c < RLN_MAXC; ++c) {
+            if (64 * c >= F) break;                  // (wave-uniform)
+            const int j = lane + 64 * c;
+            v[c] = (j < F) ? xr[j] : 0.f;
+            s += v[c];
+        }
+        const float m = smx_wave_sum(s) / (float)F;
+        float q = 0.f;
+#pragma unroll
+        for (int c = 0; c < RLN_MAXC; ++c) {
+            if (64 * c >= F) break;
+            const int j = lane + 64 * c;
+            const float d = (j < F) ? v[c] - m : 0.f;
+            q += d * d;
+        }
+        const float rs = 1.0f / sqrtf(smx_wave_sum(q) / (float)F + eps);
+#pragma unroll
+        for (int c = 0; c < RLN_MAXC; ++c) {
+            if (64 * c >= F) break;
+            const int j = lane + 64 * c;
+            if (j < F) xr[j] = ((v[c] - m) * rs) * gb[j] + gb[F + j];
+        }
+    }
+}
+
 // RG row groups of four actors per workgroup; NT feature tiles a wave carries per pass.  Every block size gives the same
 // bits (layers4).
 // POP (smx_synth_ddpg_population_rollout_f32; 4 RG divides the actors per agent): the same body with the layers run from
 // the agent's copy.  At step measure_step the workgroups that hold an agent's first actor (a workgroup-uniform branch:
 // layers4 has barriers) first run the clean actor -- G's own -- on the same x tile and keep that actor's outputs, then
 // store the L2 distance of the two outputs of that one actor.
-template <int RG, int NT, bool POP = false>
-__global__ __launch_bounds__(RNTH) void ddpg_rollout_kernel(std::conditional_t<POP, PopArgs, DArgs> G) {
+// LN (smx_synth_ddpg_ln_rollout_f32, smx_synth_ddpg_ln_population_rollout_f32): the same body with ln_rows behind the
+// barrier of each hidden layer and a barrier of its own behind it.  The gains and biases the workgroup's layers use --
+// the clean actor's, or (POP) its agent's perturbed ones -- are copied to LDS once; the clean actor of a measuring step
+// reads its own from memory.
+template <int RG, int NT, bool POP = false, bool LN = false>
+__global__ __launch_bounds__(RNTH) void ddpg_rollout_kernel(DdpgArgs<POP, LN> G) {
     constexpr int RB = 4 * RG;                       // actors per workgroup
     extern __shared__ float sm[];
     const int tid = threadIdx.x, lane = tid & 63;
@@ -965,6 +1023,31 @@ __global__ __launch_bounds__(RNTH) void ddpg_rollout_kernel(std::conditional_t<P
     // (POP) floats from agent 0's copy, which G.popnet points into, to the copy of this workgroup's agent
     size_t shift = 0;
     if constexpr (POP) shift = (size_t)(E.row0 / G.apa) * G.stride;
+    // (LN) the actor's three layers from `net`, a LayerNorm behind each hidden one; gb: ln1.W | ln1.b | ln2.W | ln2.b
+    auto actor =[&](const RollBase& net, size_t sh, const float* gb) {
+        if constexpr (LN) {
+            layers4<RG, NT>(net, sm, 3, SMX_ACT_TANH, wv, lane, [&](int l) {
+                if (l < 2) {
+                    ln_rows<RB>(sm + (l == 0 ? G.off_h1 : G.off_h2), l == 0 ? G.ldh1 : G.ldh2, l == 0 ? G.H1 : G.H2,
+                                gb + (l == 0 ? 0 : 2 * G.H1), G.ln.eps, wv, lane);
+                    SMX_LDS_BARRIER();
+                }
+            }, 0, G.D, PreLayer{}, sh);
+        }
+    };
+    const float* gb = nullptr;
+    if constexpr (LN) {
+        const float* src = G.ln.g;
+        if constexpr (POP) src = G.ln.pop + shift;
+#ifdef SMX_LN_PARAMS_L2
+        gb = src;                                    // (A/B builds only: the gains and biases read from memory every step)
+#else
+        float* dst = sm + G.ln.off;
+        for (int i = tid; i < 2 * (G.H1 + G.H2); i += RNTH) dst[i] = src[i];
+        gb = dst;
+        SMX_LDS_BARRIER();
+#endif
+    }
     int tau = G.t0, kemit = 0;
 #pragma unroll 1
     for (int step = 0; step < G.steps; ++step) {
@@ -975,13 +1058,16 @@ __global__ __launch_bounds__(RNTH) void ddpg_rollout_kernel(std::conditional_t<P
         if constexpr (POP) {
             measure = step == G.measure_step && E.row0 % G.apa == 0;
             if (measure) {
-                layers4<RG, NT>(G, sm, 3, SMX_ACT_TANH, wv, lane, [](int) {}, 0, G.D);
+                if constexpr (LN) actor(G, 0, G.ln.g);
+                else layers4<RG, NT>(G, sm, 3, SMX_ACT_TANH, wv, lane, [](int) {}, 0, G.D);
                 // (row 0's outputs; the layers below write the output tile again only behind two more barriers)
                 if (tid < A) clean = outs[tid];
             }
         }
         // ---- the actor's three layers (ReLU, ReLU, tanh) --------------------------------------------------------
-        if constexpr (POP) layers4<RG, NT>(G.popnet, sm, 3, SMX_ACT_TANH, wv, lane, [](int) {}, 0, G.D, PreLayer{}, shift);
+        if constexpr (LN && POP) actor(G.popnet, shift, gb);
+        else if constexpr (LN) actor(G, 0, gb);
+        else if constexpr (POP) layers4<RG, NT>(G.popnet, sm, 3, SMX_ACT_TANH, wv, lane, [](int) {}, 0, G.D, PreLayer{}, shift);
         else layers4<RG, NT>(G, sm, 3, SMX_ACT_TANH, wv, lane, [](int) {}, 0, G.D);
         if constexpr (POP) {
             if (measure && wv == 0) {
@@ -1438,6 +1524,12 @@ int32_t supported(int32_t D, int32_t H1, int32_t H2, int32_t A, bool mma16, bool
     return carve(G, 16, mma16, split_out, ztables, D) <= ROLL_MAX_LDS;
 }
 
+// The LayerNorm rollouts keep ln1.W | ln1.b | ln2.W | ln2.b behind the layout of `lds` bytes -> the bytes with them
+int carve_ln(const RollBase& G, LnTail& ln, int lds) {
+    ln.off = lds / (int)sizeof(float);
+    return lds + 2 * (G.H1 + G.H2) * (int)sizeof(float);
+}
+
 // With a monitor the open episodes of the block's rb actors follow the layout of `lds` bytes: [rb] fp64 sums on 8 bytes,
 // then [rb] int32 step counts -> the bytes with them (without one: `lds` as it is, and the kernels never read off_ep)
 constexpr int ROLL_EP_LDS = 8 + 16 * 12;         // (what 16 actors add at most: launch()'s dynamic-LDS limit has it)
@@ -1839,16 +1931,51 @@ extern "C" int smx_synth_ddpg_rollout_f32(const smx_ddpg_rollout_t* a, smx_strea
     return launch<ddpg_rollout_kernel<1, 3>, ddpg_rollout_kernel<2, 3>, ddpg_rollout_kernel<4, 2>>(G, rb, lds, stream);
 }
 
+extern "C" int32_t smx_synth_ddpg_ln_rollout_supported(int32_t D, int32_t H1, int32_t H2, int32_t A) {
+    if (!smx_synth_ddpg_rollout_supported(D, H1, H2, A)) return 0;
+    DLnArgs G;
+    memset(&G, 0, sizeof(G));
+    G.D = D; G.H1 = H1; G.H2 = H2; G.A = A;
+    return carve_ln(G, G.ln, carve(G, 16, /*mma16=*/false, /*split_out=*/false, /*ztables=*/false, D)) <= ROLL_MAX_LDS;
+}
+
+// what both LayerNorm entry points ask of the gains and biases
+static int ln_args(const smx_mlp3_t& net, const float* ln, float eps, LnTail& T) {
+    SMX_REQUIRE(ln, SMX_E_NULL);
+    SMX_REQUIRE(smx_synth_ddpg_ln_rollout_supported(net.D, net.H1, net.H2, net.OUT), SMX_E_UNSUPPORTED);
+    SMX_REQUIRE(eps > 0.f, SMX_E_SHAPE);
+    SMX_REQUIRE(((uintptr_t)ln & 3) == 0, SMX_E_ALIGN);
+    T.g = ln; T.eps = eps;
+    return SMX_OK;
+}
+
+extern "C" int smx_synth_ddpg_ln_rollout_f32(const struct smx_ddpg_ln_rollout* args, smx_stream_t stream) {
+    SMX_REQUIRE(args, SMX_E_NULL);
+    const smx_ddpg_rollout_t* a = &args->base;
+    DLnArgs G;
+    memset(&G, 0, sizeof(G));
+    int rc = persistent_ddpg_args(a, G);
+    if (rc != SMX_OK) return rc;
+    LnTail T = {};
+    rc = ln_args(*a->net, args->ln, args->eps, T);
+    if (rc != SMX_OK) return rc;
+    G.ln = T;
+    const int rb = pick_block(a->actors_per_workgroup, a->n);
+    const int lds = carve_ln(G, G.ln, carve(G, rb, /*mma16=*/false, /*split_out=*/false, /*ztables=*/false, G.D));
+    return launch<ddpg_rollout_kernel<1, 3, false, true>, ddpg_rollout_kernel<2, 3, false, true>,
+                  ddpg_rollout_kernel<4, 2, false, true>>(G, rb, lds, stream);
+}
+
 extern "C" int32_t smx_synth_ddpg_population_block(int32_t n, int32_t actors_per_agent, int32_t forced) {
     if (n <= 0 || actors_per_agent <= 0 || actors_per_agent % 4 || !block_ok(forced)) return 0;
     return pick_population_block(forced, n, actors_per_agent);
 }
 
-extern "C" int smx_synth_ddpg_population_rollout_f32(const struct smx_ddpg_population_rollout* args, smx_stream_t stream) {
+// what both population entry points ask of the block and take from it: the block size `rb`, the LDS layout (-> its
+// bytes in `lds`), agent 0's copy as popnet; copy_floats: what one agent's copy holds
+static int population_args(const struct smx_ddpg_population_rollout* args, long copy_floats, PopArgs& G, int& rb, int& lds) {
     SMX_REQUIRE(args && args->packed_pop, SMX_E_NULL);
     const smx_ddpg_rollout_t* a = &args->base;
-    PopArgs G;
-    memset(&G, 0, sizeof(G));
     const int rc = persistent_ddpg_args(a, G);
     if (rc != SMX_OK) return rc;
     const smx_mlp3_t& net = *a->net;
@@ -1856,13 +1983,12 @@ extern "C" int smx_synth_ddpg_population_rollout_f32(const struct smx_ddpg_popul
     SMX_REQUIRE(apa > 0 && apa % 4 == 0 && args->agents > 0 && (long long)args->agents * apa == a->n, SMX_E_SHAPE);
     SMX_REQUIRE(args->measure_step >= -1 && args->measure_step < a->steps, SMX_E_SHAPE);
     SMX_REQUIRE(args->measure_step < 0 || args->dist, SMX_E_NULL);
-    SMX_REQUIRE(args->packed_stride >= pop_copy_floats(net.D, net.H1, net.H2, net.OUT) && args->packed_stride % 4 == 0,
-                SMX_E_SHAPE);
+    SMX_REQUIRE(args->packed_stride >= copy_floats && args->packed_stride % 4 == 0, SMX_E_SHAPE);
     SMX_REQUIRE(((uintptr_t)args->packed_pop & 15) == 0, SMX_E_ALIGN);
-    const int rb = pick_population_block(a->actors_per_workgroup, a->n, apa);
+    rb = pick_population_block(a->actors_per_workgroup, a->n, apa);
     SMX_REQUIRE(rb > 0, SMX_E_SHAPE);
     G.stride = args->packed_stride; G.apa = apa; G.measure_step = args->measure_step; G.dist = args->dist;
-    const int lds = carve(G, rb, /*mma16=*/false, /*split_out=*/false, /*ztables=*/false, G.D);
+    lds = carve(G, rb, /*mma16=*/false, /*split_out=*/false, /*ztables=*/false, G.D);
     // agent 0's copy in the same tiles: its packed blocks as net_fields lays a net's out, its biases behind them
     G.popnet = G;
     smx_mlp3_t copy0 = net;
@@ -1870,8 +1996,38 @@ extern "C" int smx_synth_ddpg_population_rollout_f32(const struct smx_ddpg_popul
     copy0.b2 = copy0.b1 + net.H1;
     copy0.b3 = copy0.b2 + net.H2;
     net_fields(copy0, args->packed_pop, G.popnet);
+    return SMX_OK;
+}
+
+extern "C" int smx_synth_ddpg_population_rollout_f32(const struct smx_ddpg_population_rollout* args, smx_stream_t stream) {
+    PopArgs G;
+    memset(&G, 0, sizeof(G));
+    int rb = 0, lds = 0;
+    SMX_REQUIRE(args && args->base.net, SMX_E_NULL);
+    const smx_mlp3_t& net = *args->base.net;
+    const int rc = population_args(args, pop_copy_floats(net.D, net.H1, net.H2, net.OUT), G, rb, lds);
+    if (rc != SMX_OK) return rc;
     return launch<ddpg_rollout_kernel<1, 3, true>, ddpg_rollout_kernel<2, 3, true>, ddpg_rollout_kernel<4, 2, true>>(
         G, rb, lds, stream);
+}
+
+extern "C" int smx_synth_ddpg_ln_population_rollout_f32(const struct smx_ddpg_ln_population_rollout* args,
+                                                        smx_stream_t stream) {
+    PopLnArgs G;
+    memset(&G, 0, sizeof(G));
+    int rb = 0, lds = 0;
+    SMX_REQUIRE(args && args->pop.base.net, SMX_E_NULL);
+    const smx_mlp3_t& net = *args->pop.base.net;
+    int rc = population_args(&args->pop, pop_ln_copy_floats(net.D, net.H1, net.H2, net.OUT), G, rb, lds);
+    if (rc != SMX_OK) return rc;
+    LnTail T = {};
+    rc = ln_args(net, args->ln, args->eps, T);
+    if (rc != SMX_OK) return rc;
+    T.pop = args->pop.packed_pop + pop_ln_off(net.D, net.H1, net.H2, net.OUT);
+    G.ln = T;
+    lds = carve_ln(G, G.ln, lds);
+    return launch<ddpg_rollout_kernel<1, 3, true, true>, ddpg_rollout_kernel<2, 3, true, true>,
+                  ddpg_rollout_kernel<4, 2, true, true>>(G, rb, lds, stream);
 }
 
 extern "C" int smx_synth_ddpg_step_f32(const smx_ddpg_rollout_t* a, const float* mu, int64_t ld_mu, smx_stream_t stream) {

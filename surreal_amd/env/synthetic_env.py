@@ -642,19 +642,22 @@ class SyntheticVecEnv(object):
         """T steps of all actors under DDPGAgent `agent` (act: actor -> clip -> exploration noise -> clip,
         ddpg_agent.py:155-184), their n-step transitions (ExpSenderWrapperSSARNStepBootstrap, exp_sender_wrapper.py:72-112)
         written STRAIGHT INTO the uniform replay's device ring (reserve_ring / commit_ring) -> the number of rows written.
-        ONE launch (smx_synth_ddpg_rollout_f32) where the actor's shapes allow it, else one actor forward
-        (DDPGModel.forward_actor) and one step launch (smx_synth_ddpg_step_f32) per step.  Rollouts need not start at an
+        ONE launch (smx_synth_ddpg_rollout_f32; a LayerNorm actor: smx_synth_ddpg_ln_rollout_f32) where the actor's
+        shapes allow it, else one actor forward (DDPGModel.forward_actor) and one step launch (smx_synth_ddpg_step_f32)
+        per step.  Rollouts need not start at an
         episode boundary: the open transitions and the OU states carry from call to call (reset() clears them).
         eps [T, n, A] standard normals (default: drawn here in one launch); sigmas [n] fp64 (default
         agent.batch_sigmas(n)); actors_per_workgroup: 4 | 8 | 16 forces the persistent kernel's block (0: automatic);
         reference=True: the two-launch reference of the persistent kernel (smx_epoch_forward_f32 for the actor, then the
-        step launch) -- for parity tests, not the product loop.
+        step launch) -- for parity tests, not the product loop; with a LayerNorm actor: the per-step path
+        (forward_actor, then the step launch).
         A camera agent on a camera env (frame_stacks S): per step the perception (DDPGModel.perception_into) of the
         stacked frames, the actor, and ONE launch (smx_synth_ddpg_pixel_step) that also renders the step's frame into
         a history of n_step + S raw frames per actor, writes the closing transitions' uint8 'pixel' / 'pixel_next'
         [S*C, H, W] into the ring and the stacked observation of the next step.  The history carries from call to call
         like the open transitions.
-        With a DeviceParamNoise attached (attach_param_noise): ONE launch too (smx_synth_ddpg_population_rollout_f32),
+        With a DeviceParamNoise attached (attach_param_noise): ONE launch too (smx_synth_ddpg_population_rollout_f32 /
+        smx_synth_ddpg_ln_population_rollout_f32),
         every agent's actors acting from their agent's perturbed copy; with 'adaptive_normal' the call's last step s
         with (acts + s) % compute_dist_interval == 0 also measures each agent's action distance; acts += T."""
         K, n, A = self.K, self.n, self.A
@@ -663,11 +666,16 @@ class SyntheticVecEnv(object):
         if refusal is not None:
             raise refusal[0](refusal[1])
         pn = self.param_noise
+        # a LayerNorm actor has entry points of its own; kernels that do not offer them leave it where it was: on the
+        # per-step path, and refused under a parameter noise
+        ln = bool(agent.model.use_layernorm)
+        ln_launch = ln and not camera and hasattr(K, 'synth_ddpg_ln_rollout')
+        supported = K.synth_ddpg_ln_rollout_supported if ln_launch else K.synth_ddpg_rollout_supported
         if pn is not None:
+            ln_pop = ln_launch and pn.ln and hasattr(K, 'synth_ddpg_ln_population_rollout')
             why = ('a camera agent (the perception would need perturbing too)' if camera else
-                   'a LayerNorm actor' if agent.model.use_layernorm else
-                   'an actor shape the one-launch rollout does not take' if
-                   not K.synth_ddpg_rollout_supported(agent.model.actor) else
+                   'a LayerNorm actor' if ln and not ln_pop else
+                   'an actor shape the one-launch rollout does not take' if not supported(agent.model.actor) else
                    'reference=True (the two-launch reference has one actor)' if reference else None)
             if why is not None:
                 raise NotImplementedError('ddpg_rollout_into: no device parameter noise for ' + why)
@@ -720,27 +728,36 @@ class SyntheticVecEnv(object):
             self._ddpg_pixel_steps(agent, r, T, N, cap, eps, ns)
             replay.commit_ring(rows)
             return rows
-        actor = agent.model.actor
-        persistent = not agent.model.use_layernorm and K.synth_ddpg_rollout_supported(actor)
-        if persistent or reference:
+        actor, model = agent.model.actor, agent.model
+        persistent = (ln_launch or not ln) and supported(actor)
+        two_launch = reference and not ln         # (a LayerNorm actor's reference is the per-step path itself)
+        if persistent or two_launch:
             if d.get('pk') is None or d['pk'].numel() != K.epoch_packed_numel(actor):
                 d['pk'] = torch.zeros(K.epoch_packed_numel(actor), device=self.device)
             K.epoch_pack([(actor, d['pk'])])        # (the agent's parameters only change between rollouts)
         if pn is not None:
-            K.synth_ddpg_population_rollout(actor, d['pk'], r, T, pn, pn.measure_step(T), actors_per_workgroup,
-                                            **self._mon(T), **self._noi(T, ns))
+            if ln:
+                K.synth_ddpg_ln_population_rollout(actor, d['pk'], model.actor_ln_flat, model.ln_eps, r, T, pn,
+                                                   pn.measure_step(T), actors_per_workgroup, **self._mon(T),
+                                                   **self._noi(T, ns))
+            else:
+                K.synth_ddpg_population_rollout(actor, d['pk'], r, T, pn, pn.measure_step(T), actors_per_workgroup,
+                                                **self._mon(T), **self._noi(T, ns))
             pn.acts += T
             self.t = t
         elif persistent and not reference:
-            K.synth_ddpg_rollout(actor, d['pk'], r, T, actors_per_workgroup, **self._mon(T), **self._noi(T, ns))
+            if ln:
+                K.synth_ddpg_ln_rollout(actor, d['pk'], model.actor_ln_flat, model.ln_eps, r, T, actors_per_workgroup,
+                                        **self._mon(T), **self._noi(T, ns))
+            else:
+                K.synth_ddpg_rollout(actor, d['pk'], r, T, actors_per_workgroup, **self._mon(T), **self._noi(T, ns))
             self.t = t
         else:
-            if reference:
-                assert not agent.model.use_layernorm
+            if two_launch:
                 mu = torch.empty(n, A, device=self.device)
                 ctrl = torch.zeros(L.CTRL_WORDS, device=self.device)
             for s in range(T):
-                if reference:
+                if two_launch:
                     K.epoch_forward([dict(net=actor, packed=d['pk'], x=self.state, out=mu, act=L.SMX_ACT_TANH)],
                                     None, ctrl, n)
                 else:

@@ -835,6 +835,25 @@ class HipKernels(object):
         p = self._ddpg_args(r, steps, net, packed, actors_per_workgroup, monitor, noise)
         L.call('smx_synth_ddpg_rollout_f32', ctypes.byref(p), self._st())
 
+    # ---- the same for a LayerNorm actor; ln: ln1.W | ln1.b | ln2.W | ln2.b contiguous (DDPGModel.actor_ln_flat) ----
+    def synth_ddpg_ln_rollout_supported(self, net):
+        return bool(self.lib.smx_synth_ddpg_ln_rollout_supported(net.D, net.H1, net.H2, net.OUT))
+
+    @staticmethod
+    def _ln_ptr(net, ln):
+        assert ln.dtype == torch.float32 and ln.is_contiguous() and ln.numel() == 2 * (net.H1 + net.H2)
+        return L.ptr(ln)
+
+    def synth_ddpg_ln_rollout(self, net, packed, ln, ln_eps, r, steps, actors_per_workgroup=0, monitor=None, noise=None):
+        """synth_ddpg_rollout with a LayerNorm (gains and biases `ln`, eps `ln_eps`) behind each hidden ReLU of `net`,
+        ONE launch (smx_synth_ddpg_ln_rollout_f32)"""
+        if r['eps'] is not None:
+            assert r['eps'].is_contiguous() and tuple(r['eps'].shape) == (steps, r['state'].shape[0], net.OUT)
+        p = L.DdpgLnRollout()
+        p.base = self._ddpg_args(r, steps, net, packed, actors_per_workgroup, monitor, noise)
+        p.ln, p.eps = self._ln_ptr(net, ln), float(ln_eps)
+        L.call('smx_synth_ddpg_ln_rollout_f32', ctypes.byref(p), self._st())
+
     # ---- parameter-space noise on the device (csrc/smx_param_noise.hip; DeviceParamNoise, env/monitor.py) ----
     def param_noise_copy_numel(self, net):
         """floats of one agent's copy in the population buffer: epoch_pack's layout, then the biases"""
@@ -865,6 +884,26 @@ class HipKernels(object):
         rule on sigma when pn.adaptive and pn.acts > 0, then every agent's copy of the perturbed `net` into pn.pop"""
         L.call('smx_param_noise_refresh_f32', ctypes.byref(self._param_noise_args(net, pn)), self._st())
 
+    def param_noise_ln_copy_numel(self, net):
+        """floats of one agent's copy of a LayerNorm actor: param_noise_copy_numel's, then the LayerNorm parameters"""
+        return int(self.lib.smx_param_noise_ln_copy_floats(net.D, net.H1, net.H2, net.OUT))
+
+    def _param_noise_ln_args(self, net, ln, pn):
+        q = L.ParamNoiseLn()
+        q.base = self._param_noise_args(net, pn)
+        q.ln = self._ln_ptr(net, ln)
+        return q
+
+    def param_noise_ln_fill(self, net, ln, pn, p, out):
+        """param_noise_fill over the flat parameters of a LayerNorm actor: out [net.numel + ln.numel()]"""
+        assert out.is_contiguous() and out.dtype == torch.float32 and out.numel() == net.numel + ln.numel()
+        L.call('smx_param_noise_ln_fill_f32', ctypes.byref(self._param_noise_ln_args(net, ln, pn)), int(p), L.ptr(out),
+               self._st())
+
+    def param_noise_ln_refresh(self, net, ln, pn):
+        """param_noise_refresh for a LayerNorm actor: the copies in pn.pop carry the perturbed `ln` behind the biases"""
+        L.call('smx_param_noise_ln_refresh_f32', ctypes.byref(self._param_noise_ln_args(net, ln, pn)), self._st())
+
     def synth_ddpg_population_block(self, n, actors_per_agent, forced=0):
         """the block size the population launch takes (0: it refuses)"""
         return int(self.lib.smx_synth_ddpg_population_block(int(n), int(actors_per_agent), int(forced)))
@@ -875,6 +914,10 @@ class HipKernels(object):
         copy in pn.pop; net / packed: the clean actor, evaluated at step measure_step (-1: never) for pn.dist"""
         if r['eps'] is not None:
             assert r['eps'].is_contiguous() and tuple(r['eps'].shape) == (steps, r['state'].shape[0], net.OUT)
+        p = self._population_args(net, packed, r, steps, pn, measure_step, actors_per_workgroup, monitor, noise)
+        L.call('smx_synth_ddpg_population_rollout_f32', ctypes.byref(p), self._st())
+
+    def _population_args(self, net, packed, r, steps, pn, measure_step, actors_per_workgroup, monitor, noise):
         p = L.DdpgPopulationRollout()
         p.base = self._ddpg_args(r, steps, net, packed, actors_per_workgroup, monitor, noise)
         assert pn.pop.dtype == torch.float32 and pn.pop.is_contiguous() and pn.dist.dtype == torch.float64
@@ -882,7 +925,18 @@ class HipKernels(object):
         p.packed_pop, p.packed_stride = L.ptr(pn.pop), pn.pop.shape[1]
         p.actors_per_agent, p.agents, p.measure_step = int(pn.actors_per_agent), int(pn.agents), int(measure_step)
         p.dist = L.ptr(pn.dist)
-        L.call('smx_synth_ddpg_population_rollout_f32', ctypes.byref(p), self._st())
+        return p
+
+    def synth_ddpg_ln_population_rollout(self, net, packed, ln, ln_eps, r, steps, pn, measure_step=-1,
+                                         actors_per_workgroup=0, monitor=None, noise=None):
+        """synth_ddpg_population_rollout for a LayerNorm actor: pn.pop holds param_noise_ln_refresh's copies; ln, ln_eps:
+        the clean actor's, as synth_ddpg_ln_rollout takes them"""
+        if r['eps'] is not None:
+            assert r['eps'].is_contiguous() and tuple(r['eps'].shape) == (steps, r['state'].shape[0], net.OUT)
+        p = L.DdpgLnPopulationRollout()
+        p.pop = self._population_args(net, packed, r, steps, pn, measure_step, actors_per_workgroup, monitor, noise)
+        p.ln, p.eps = self._ln_ptr(net, ln), float(ln_eps)
+        L.call('smx_synth_ddpg_ln_population_rollout_f32', ctypes.byref(p), self._st())
 
     def synth_ddpg_step(self, r, mu, monitor=None, noise=None):
         """one step of synth_ddpg_rollout given the actor's output mu [n, A] (r['eps']: this step's [n, A] draws;

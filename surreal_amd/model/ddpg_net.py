@@ -76,6 +76,7 @@ class DDPGModel(object):
             self.actor_flat = self.ac_flat[:na]
             self.actor = Mlp3Params(self.actor_flat, 0, D, ah[0], ah[1], A)
             self.actor_ln = collections.OrderedDict()
+            self.actor_ln_flat = self.actor_flat[n_mlp:]      # ln1.W | ln1.b | ln2.W | ln2.b (empty without LayerNorm)
             if use_layernorm:
                 o = n_mlp
                 for name, k in (('ln1.W', ah[0]), ('ln1.b', ah[0]), ('ln2.W', ah[1]), ('ln2.b', ah[1])):
