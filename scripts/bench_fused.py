@@ -1,5 +1,4 @@
-"""time the fused critic pass (131 072 step rows x 376 -> 300 -> 200 -> 1, z-filter on) on the GPU box;
-SMX_FUSED32=1 python scripts/bench_fused.py keeps the 32-row kernel for comparison"""
+"""time the fused critic pass (131 072 step rows x 376 -> 300 -> 200 -> 1, z-filter on) on the GPU box"""
 import sys, os
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -28,8 +27,7 @@ for _ in range(n): fn()
 e1.record(); torch.cuda.synchronize()
 t = e0.elapsed_time(e1) / n
 fl = 2.0 * B * N * (D * H1 + H1 * H2 + H2)
-print('fused critic (%s): %.4f ms  %.1f TFLOP/s  frac %.3f' % ('32-row' if os.environ.get('SMX_FUSED32') else '16-row',
-      t, fl / t / 1e9, fl / t / 1e9 / 157.3))
+print('fused critic (16-row): %.4f ms  %.1f TFLOP/s  frac %.3f' % (t, fl / t / 1e9, fl / t / 1e9 / 157.3))
 if os.environ.get('SMX_FUSED_TBUF'):
     import ctypes, numpy as np
     lib = K.lib

@@ -1,5 +1,5 @@
 """time smx_linear_f32 on the stems' big shapes (tests/diag/gemm_tile_cases.py); run it with SMX_GEMM_ROWS_ONLY=1 for
-gemm_rows_kernel (the A/B switch of csrc/smx_gemm.hip::launch_tiles)"""
+gemm_rows_kernel (csrc/smx_gemm.hip::launch_tiles: the switch of the tile / rows bit-equality test)"""
 import os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, 'tests', 'diag'))

@@ -1,6 +1,5 @@
 """the MLP on top of a stem over B*E rows (126 976 x 100 -> 300 -> 200 -> A at the 1024 x 128 LSTM shapes): forward
-layered vs fused (K.mlp3_forward(pack=...)), backward (data gradients + split-K weight gradients; SMX_WGRAD_TILED=1 in the
-environment keeps the weight gradients on the tiled GEMM for the A/B)
+layered vs fused (K.mlp3_forward(pack=...)), backward (data gradients + split-K weight gradients)
     python scripts/bench_stem_mlp.py [rows D A]"""
 import os
 import sys
@@ -45,8 +44,7 @@ print('forward layered: %8.1f us  %6.1f TFLOP/s' % (t, fl / t / 1e6))
 t = timed(lambda: K.mlp3_forward(net, x, h1, h2, out, L.SMX_ACT_TANH, pack=pack))
 print('forward fused  : %8.1f us  %6.1f TFLOP/s' % (t, fl / t / 1e6))
 t = timed(lambda: K.mlp3_backward(net, x, h1, h2, dz3, dz2, dz1, grads, None, ws=ws))
-print('backward layered dgrad + split-K wgrad%s: %8.1f us  %6.1f TFLOP/s' % (
-    ' (tiled)' if os.environ.get('SMX_WGRAD_TILED') else '', t, (2 * fl - 2.0 * rows * D * H1) / t / 1e6))
+print('backward layered dgrad + split-K wgrad: %8.1f us  %6.1f TFLOP/s' % (t, (2 * fl - 2.0 * rows * D * H1) / t / 1e6))
 npt = K.mlp3_dgrad_rows_ws_floats(net)
 if npt:
     packT, dx = f(npt), f(rows, D)

@@ -11,7 +11,6 @@
 //     a GEMM over patch rows writes), torch flattens channel-first, so the Linear's weight is
 //     re-indexed [out, c*P + p] <-> [out, p*C + c].
 #include "smx_common.h"
-#include <stdlib.h>
 
 namespace {
 
@@ -1046,9 +1045,7 @@ extern "C" int smx_conv_cl_dgrad_f32(const float* dy, int64_t F, int32_t C, int3
         cout <= 16 ? (cout % 4 == 0 ? conv_cl_dgrad_kernel<1, true> : conv_cl_dgrad_kernel<1, false>)
                    : (cout % 4 == 0 ? conv_cl_dgrad_kernel<2, true> : conv_cl_dgrad_kernel<2, false>);
     // stride 2, even maps (the reference's geometry): tiles of 2 x 2 cells, one gather for the four parity classes
-    // (SMX_CONV_DGRAD_CLASSES=1 keeps the class-major kernel for A/B runs)
-    static const bool classes = getenv("SMX_CONV_DGRAD_CLASSES") != nullptr;
-    if (!classes && stride == 2 && Hin % 2 == 0 && Win % 2 == 0)
+    if (stride == 2 && Hin % 2 == 0 && Win % 2 == 0)
         kern = cout <= 16 ? (cout % 4 == 0 ? conv_cl_dgrad_cells_kernel<1, true> : conv_cl_dgrad_cells_kernel<1, false>)
                           : (cout % 4 == 0 ? conv_cl_dgrad_cells_kernel<2, true> : conv_cl_dgrad_cells_kernel<2, false>);
     hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(256), 0, smx_s(stream), dy, g, (long long)F, W, cout, relu_of,

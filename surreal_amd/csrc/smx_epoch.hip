@@ -32,7 +32,6 @@
 // The weight gradients (sums over ALL rows) stay a GEMM launch (smx_gemm.hip), clip-norm + Adam
 // one more: 4 dependent launches per epoch instead of 9.
 #include "smx_common.h"
-#include <stdlib.h>
 #include <string.h>
 
 // workgroup barrier for data exchanged through LDS: does NOT wait for the wave's global stores
@@ -1167,8 +1166,7 @@ static int fill_args(EArgs& G, const smx_epoch_job_t* jobs, int32_t njobs, const
     }
     if (!backward && njobs == 2 && fsplit == 1) {         // two jobs of equal size on the two halves of the XCDs (xcd_job_order)
         const int nb0 = smx_epoch_blocks(jobs[0].rows), nb1 = smx_epoch_blocks(jobs[1].rows);
-        static const bool off = getenv("SMX_EPOCH_NO_XSPLIT") != nullptr;     // A/B switch for measurements
-        if (nb0 == nb1 && (nb0 & 3) == 0 && !off) G.xsplit = nb0;
+        if (nb0 == nb1 && (nb0 & 3) == 0) G.xsplit = nb0;
     }
     // LDS carve-up: [x tile | h1 tile | h2 tile | out tile | K-split partials | loss scratch]
     // (the K loops run over an even number of 32-wide chunks: rows are zero padded to 64 columns)

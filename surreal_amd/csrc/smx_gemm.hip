@@ -759,7 +759,9 @@ inline bool tile_mode_of(const float* X, int ld, int kc, int mode, int& out) {
 
 // -> true when the batch was taken (rc = the launch's result)
 inline bool launch_tiles(GemmBatch& G, hipStream_t st, int& rc) {
-    static const bool off = getenv("SMX_GEMM_ROWS_ONLY") != nullptr;     // A/B switch for measurements
+    // the library's one environment read: tests/test_gpu_kernels.py::test_linear_tile_kernel_* runs the same problems on
+    // gemm_rows_kernel in a child process to pin the two kernels to the same bits
+    static const bool off = getenv("SMX_GEMM_ROWS_ONLY") != nullptr;
     if (off) return false;
     int am = -1, bm = -1;
     for (int k = 0; k < G.n; ++k) {
@@ -781,7 +783,7 @@ inline bool launch_tiles(GemmBatch& G, hipStream_t st, int& rc) {
 // tile kernel's operand rules)?  Callers that MERGE batches ask first: a merge must not move a problem to another kernel
 // (another summation order).
 inline bool wgrad_batch_takes_tiles(const GemmBatch& G) {
-    static const bool off = getenv("SMX_GEMM_ROWS_ONLY") != nullptr;
+    static const bool off = getenv("SMX_GEMM_ROWS_ONLY") != nullptr;     // (as in launch_tiles)
     if (off) return false;
     bool wide = true;
     long wgs = 0;
@@ -1067,8 +1069,7 @@ extern "C" int smx_linear_wgrad_splitk_f32(const float* dZ, int32_t ldz, const f
     G.p[0].c_split = (long)M * N;
     // every chunk must be non-empty
     while ((long)(G.p[0].splits - 1) * G.p[0].k_chunk >= rows) --G.p[0].splits;
-    static const bool tiled_only = getenv("SMX_WGRAD_TILED") != nullptr;
-    if (!tiled_only && smx_wgrad_rows_eligible(dZ, ldz, X, ldx, M, N, rows)) {
+    if (smx_wgrad_rows_eligible(dZ, ldz, X, ldx, M, N, rows)) {
         // the whole dW in one workgroup's registers, every operand row read once (smx_wgrad.hip)
         // (a dW wider than one workgroup's registers -- the LSTM's dW_ih at 376 inputs: 400 x 376 -- goes as column groups,
         // each a problem of the same launch that re-reads dZ)
@@ -1101,11 +1102,9 @@ extern "C" int smx_linear_wgrad_splitk_pair_f32(const float* dZ, int32_t ldz, in
     SMX_REQUIRE(M > 0 && N1 > 0 && N2 > 0 && rows > 0 && ldz >= M && ldx1 >= N1 && ldx2 >= N2, SMX_E_SHAPE);
     const int S1 = pick_splits(M, N1, rows), S2 = pick_splits(M, N2, rows);
     const int64_t need1 = S1 > 1 ? (int64_t)S1 * ((int64_t)M * N1 + M) : 0, need2 = S2 > 1 ? (int64_t)S2 * ((int64_t)M * N2 + M) : 0;
-    static const bool tiled_only = getenv("SMX_WGRAD_TILED") != nullptr;
-    static const bool no_pair = getenv("SMX_WGRAD_NO_PAIR") != nullptr;       // A/B switch
-    bool pair = !no_pair && S1 > 1 && S2 > 1 && ws && ws_floats >= need1 + need2;
-    pair = pair && (tiled_only || (!smx_wgrad_rows_eligible(dZ, ldz, X1, ldx1, M, N1, rows) &&
-                                   !smx_wgrad_rows_eligible(dZ, ldz, X2, ldx2, M, N2, rows)));
+    bool pair = S1 > 1 && S2 > 1 && ws && ws_floats >= need1 + need2;
+    pair = pair && !smx_wgrad_rows_eligible(dZ, ldz, X1, ldx1, M, N1, rows) &&
+           !smx_wgrad_rows_eligible(dZ, ldz, X2, ldx2, M, N2, rows);
     GemmBatch G, G1, G2;
     float* part[2] = {ws, ws + need1};
     if (pair) {
@@ -1350,10 +1349,9 @@ static int mlp3_wgrads_splitk(const smx_mlp3_t* net, const float* x, const float
     float* gdst = grads;
     float* wsp = ws;
     // three launches at most: the wide layers straight from the row-major operands (smx_wgrad.hip: the whole dW in one
-    // workgroup's registers; SMX_WGRAD_TILED=1 keeps them on the tiled GEMM for A/B runs), layers wide enough for
+    // workgroup's registers), layers wide enough for
     // the 64 x 64 tile kernel but not for that one, and the rest (the output layer: 1 - 17 rows of dW3) on 32 x 32 tiles
     // -- launch_batch() takes a batch to one kernel as a whole
-    static const bool tiled_only = getenv("SMX_WGRAD_TILED") != nullptr;
     GemmBatch Gw, Gr;
     WgradBatch Gd;
     Gw.n = Gr.n = Gd.n = 0;
@@ -1367,7 +1365,7 @@ static int mlp3_wgrads_splitk(const smx_mlp3_t* net, const float* x, const float
         float* bpart = wsp + (size_t)S * M * N;
         wsp = bpart + (size_t)S * M;
         int gw;
-        if (!tiled_only && smx_wgrad_rows_eligible(dz[l], M, in[l], N, M, N, R) && smx_wgrad_rows_groups(M, N, &gw) == 1) {
+        if (smx_wgrad_rows_eligible(dz[l], M, in[l], N, M, N, R) && smx_wgrad_rows_groups(M, N, &gw) == 1) {
             WgradProb& P = Gd.p[Gd.n++];
             P.A = dz[l]; P.B = in[l]; P.Cpart = wpart; P.bpart = bpart;
             P.M = M; P.N = N; P.lda = M; P.ldb = N; P.rows = R;

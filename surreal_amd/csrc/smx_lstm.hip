@@ -3,19 +3,21 @@
 //
 // Batch rows are independent, time steps are not, so the recurrence is ONE launch: a workgroup
 // owns a few batch rows and walks the whole sequence with h/c resident on chip.
-//   * the input half of the gates, x . W_ih^T + b_ih, has no time dependence: one GEMM over all
-//     B*T rows (smx_linear_f32) before the recurrent kernel;
-//   * per step the recurrent half h_{t-1} . W_hh^T with h_{t-1} read from LDS:
-//     H <= 128 (the reference default is 100), B < 512: ONE row per workgroup on the vector ALU, a unit's four gates in a
-//     quad of lanes with their W_hh rows in REGISTERS for the whole sequence (lstm_fwdk / lstm_bwdk_kernel; the kernels
-//     they replaced remain behind SMX_LSTM_V1 / _QUAD / _MFMA4 for A/B runs); B >= 512 (H <= 112): FOUR rows per
-//     workgroup on v_mfma_f32_4x4x1 (lstm_fwdm / lstm_bwdm_kernel, round 5); larger H: 16 rows on FP32 MFMA 16x16x4, W_hh
-//     fragments re-read from L2 every step;
+//   * the input half of the gates, x . W_ih^T + b_ih, has no time dependence: with D <= 20 inputs (and H <= 112) it is
+//     formed inside the recurrence from weights in registers (FOLD), else by one GEMM over all B*T rows
+//     (smx_linear_f32) before the recurrent kernel;
+//   * per step the recurrent half h_{t-1} . W_hh^T with h_{t-1} read from LDS, on one of three kernel families
+//     (lstm_plan() below is the one selection rule of forward and backward):
+//       k       H <= 128 (the reference default is 100): ONE row per workgroup on the vector ALU (two at B >= 512), a
+//               unit's four gates in a quad of lanes with their W_hh rows in REGISTERS for the whole sequence
+//               (lstm_fwdk / lstm_bwdk_kernel);
+//       m       H <= 112 and B >= 512: FOUR rows per workgroup on v_mfma_f32_4x4x1 (lstm_fwdm / lstm_bwdm_kernel);
+//       16-row  larger H: 16 rows on FP32 MFMA 16x16x4, W_hh fragments re-read from L2 every step
+//               (lstm_fwd / lstm_bwd_kernel);
 //   * the cell update is elementwise on a fixed (row, unit) -> thread map; h_t goes back to LDS.
-// Backward is the mirror image (t = T-1 .. 0, dh_rec = dgates_t . W_hh on MFMA), followed by the
+// Backward is the mirror image (t = T-1 .. 0, dh_rec = dgates_t . W_hh), followed by the
 // weight-gradient GEMMs over all B*T rows (split-K).
 #include "smx_common.h"
-#include <stdlib.h>
 
 namespace {
 
@@ -47,7 +49,7 @@ struct FwdArgs {
     int D;
 };
 
-// ---- 16-row workgroups on 16x16x4 MFMA: the large-H variant (112 < H <= 384).  W_hh does not fit
+// ---- 16-row workgroups on 16x16x4 MFMA: the large-H variant (128 < H <= 384).  W_hh does not fit
 // the register file, so its fragments are re-read from L2 every step; the cell state lives in LDS.
 // KG: 16-wide k groups covering H (H <= 16*KG).
 template <int KG>
@@ -218,346 +220,20 @@ __global__ __launch_bounds__(NT) void lstm_bwd_kernel(BwdArgs a) {
     }
 }
 
-// ===========================================================================================
-// 4-row formulation (H <= 112): the same recurrence on v_mfma_f32_4x4x1_16b_f32.  One instruction
-// is 16 independent 4x4 outer products (K = 1): block b of lane l = 4b + j multiplies the 4 batch
-// rows h[i][k] (A operand, lane & 3 = i, the same for every block) with gate column 64w + l of
-// W_hh (B operand, lane = column) -- 4 rows x 64 columns per instruction at the same FLOP rate as
-// the 16x16x4 form, but a workgroup now owns 4 batch rows instead of 16: four times the
-// workgroups (B = 64 -> 16, B = 1024 -> 256 = the whole chip) and a quarter of the serial work
-// per time step.  Wave w keeps W_hh[64w + lane][0..H) in registers for the whole sequence.
-// ===========================================================================================
 #define MFMA4(a, b, c) __builtin_amdgcn_mfma_f32_4x4x1f32((a), (b), (c), 0, 0, 0)
 // barrier between phases that exchange data through LDS only (__syncthreads() also drains the global stores)
 #define LSTM_LDS_BARRIER() asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory")
 
-constexpr int RB4 = 4;
-
-// KQ: 4-wide k groups covering H (H <= 4*KQ)
-template <int KQ>
-__global__ __launch_bounds__(NT) void lstm_fwd4_kernel(FwdArgs a) {
-    extern __shared__ float smem[];
-    if (a.stop && *a.stop) return;
-    const int H = a.H, G = 4 * H, T = a.T;
-    constexpr int HS = KQ * 4 + 4;             // h row stride in LDS (columns >= H stay zero)
-    constexpr int GS = NWV * 64 + 4;           // gate row stride (every wave writes its 64 columns)
-    float* hs = smem;                          // [4][HS]
-    float* gh = smem + RB4 * HS;               // [4][GS]
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int row0 = blockIdx.x * RB4;
-    const int col = wv * 64 + lane;            // gate column of this lane
-
-    float4 wq[KQ];
-#pragma unroll
-    for (int q = 0; q < KQ; ++q)
-        wq[q] = (col < G && 4 * q < H)
-                    ? *reinterpret_cast<const float4*>(a.W_hh + (size_t)col * H + 4 * q)
-                    : make_float4(0.f, 0.f, 0.f, 0.f);
-    const float bias = (col < G) ? a.b_hh[col] : 0.f;
-
-    for (int idx = tid; idx < RB4 * HS; idx += NT) hs[idx] = 0.f;
-    __syncthreads();
-    // one (row, unit) element per thread
-    const int erow = tid / H, ej = tid - erow * H;
-    const bool ev = tid < RB4 * H;
-    const bool inb = ev && row0 + erow < a.B;
-    const unsigned eoff = inb ? (unsigned)(row0 + erow) * (unsigned)(T * H) + (unsigned)ej : 0u;
-    float creg = (inb && a.c0) ? a.c0[(size_t)(row0 + erow) * H + ej] : 0.f;
-    if (inb && a.h0) hs[erow * HS + ej] = a.h0[(size_t)(row0 + erow) * H + ej];
-    __syncthreads();
-
-    const float* hrow = hs + (lane & 3) * HS;
-    for (int t = 0; t < T; ++t) {
-        float gx0 = 0.f, gx1 = 0.f, gx2 = 0.f, gx3 = 0.f;
-        if (inb) {
-            const unsigned og = (eoff - ej + (unsigned)(t * H)) * 4u + ej;
-            gx0 = a.gates[og]; gx1 = a.gates[og + (unsigned)H];
-            gx2 = a.gates[og + (unsigned)(2 * H)]; gx3 = a.gates[og + (unsigned)(3 * H)];
-        }
-        if (wv * 64 < G) {                     // wave-uniform: waves past the last gate column idle
-            f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-            for (int q = 0; q < KQ; ++q) {
-                const float4 hv = *reinterpret_cast<const float4*>(hrow + 4 * q);
-                acc = MFMA4(hv.x, wq[q].x, acc);
-                acc = MFMA4(hv.y, wq[q].y, acc);
-                acc = MFMA4(hv.z, wq[q].z, acc);
-                acc = MFMA4(hv.w, wq[q].w, acc);
-            }
-#pragma unroll
-            for (int r = 0; r < 4; ++r) gh[r * GS + col] = acc[r] + bias;
-        }
-        __syncthreads();
-        if (ev) {
-            const float* g = gh + erow * GS + ej;
-            const float gi = sigm(gx0 + g[0]);
-            const float gf = sigm(gx1 + g[H]);
-            const float gg = tanhf(gx2 + g[2 * H]);
-            const float go = sigm(gx3 + g[3 * H]);
-            const float c = gf * creg + gi * gg;
-            const float h = go * tanhf(c);
-            if (inb) {
-                const unsigned oh = eoff + (unsigned)(t * H);
-                const unsigned og = (oh - ej) * 4u + ej;
-                a.gates[og] = gi; a.gates[og + (unsigned)H] = gf;
-                a.gates[og + (unsigned)(2 * H)] = gg; a.gates[og + (unsigned)(3 * H)] = go;
-                a.out[oh] = h;
-                a.cs[oh] = c;
-                if (a.hprev) a.hprev[oh] = hs[erow * HS + ej];
-                creg = c;
-                hs[erow * HS + ej] = h;
-            }
-        }
-        __syncthreads();
-    }
-    if (inb) {
-        if (a.hN) a.hN[(size_t)(row0 + erow) * H + ej] = hs[erow * HS + ej];
-        if (a.cN) a.cN[(size_t)(row0 + erow) * H + ej] = creg;
-    }
-}
-
-// Backward: dh_rec[4][H] = dgates_t[4][4H] . W_hh[4H][H].  The K = 4H sum is split over the four
-// gate blocks: wave w handles gate block w & 3 for hidden columns 64 (w >> 2) + lane and keeps its
-// W_hh slice in registers; the four partial sums meet in LDS and are added in a fixed order by the
-// next step's elementwise phase.
-template <int KQ>
-__global__ __launch_bounds__(NT) void lstm_bwd4_kernel(BwdArgs a) {
-    extern __shared__ float smem[];
-    if (a.stop && *a.stop) return;
-    const int H = a.H, G = 4 * H, T = a.T;
-    constexpr int DS = 4 * (KQ * 4) + 4;       // dgates row stride: four gate blocks of KQ*4 (zero padded)
-    constexpr int PS = 128 + 4;                // partial row stride (two 64-column groups)
-    float* dg = smem;                          // [4][DS]   block q at columns [q*KQ*4, q*KQ*4 + H)
-    float* part = smem + RB4 * DS;             // [4 gate blocks][4 rows][PS]
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int row0 = blockIdx.x * RB4;
-    const int gb = wv & 3, cg = wv >> 2;
-    const int n = cg * 64 + lane;              // hidden column of this lane
-
-    float4 wq[KQ];
-#pragma unroll
-    for (int q = 0; q < KQ; ++q) {
-        float4 w = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (n < H && 4 * q < H) {
-            const float* p = a.W_hh + ((size_t)gb * H + 4 * q) * H + n;
-            w.x = p[0]; w.y = p[H]; w.z = p[2 * (size_t)H]; w.w = p[3 * (size_t)H];
-        }
-        wq[q] = w;
-    }
-    for (int idx = tid; idx < RB4 * DS + 4 * RB4 * PS; idx += NT) smem[idx] = 0.f;
-    const int erow = tid / H, ej = tid - erow * H;
-    const bool ev = tid < RB4 * H;
-    const bool inb = ev && row0 + erow < a.B;
-    const unsigned eoff = inb ? (unsigned)(row0 + erow) * (unsigned)(T * H) + (unsigned)ej : 0u;
-    float dcreg = 0.f;
-    __syncthreads();
-
-    const float* drow = dg + (lane & 3) * DS + gb * (KQ * 4);
-    for (int t = T - 1; t >= 0; --t) {
-        if (inb) {
-            const unsigned oh = eoff + (unsigned)(t * H);
-            const unsigned og = (oh - ej) * 4u + ej;
-            const float gi = a.gates[og], gf = a.gates[og + (unsigned)H];
-            const float gg = a.gates[og + (unsigned)(2 * H)], go = a.gates[og + (unsigned)(3 * H)];
-            const float c = a.cs[oh];
-            const float cp = (t > 0) ? a.cs[oh - (unsigned)H]
-                                     : (a.c0 ? a.c0[(size_t)(row0 + erow) * H + ej] : 0.f);
-            const float* pp = part + erow * PS + ej;
-            const float dhr = ((pp[0] + pp[RB4 * PS]) + pp[2 * RB4 * PS]) + pp[3 * RB4 * PS];
-            const float dh = a.dout[oh] + dhr;
-            const float tc = tanhf(c);
-            const float dc = dcreg + (dh * go) * (1.f - tc * tc);
-            const float dgi = (dc * gg) * (gi * (1.f - gi));
-            const float dgf = (dc * cp) * (gf * (1.f - gf));
-            const float dgg = (dc * gi) * (1.f - gg * gg);
-            const float dgo = (dh * tc) * (go * (1.f - go));
-            dcreg = dc * gf;
-            a.dgates[og] = dgi; a.dgates[og + (unsigned)H] = dgf;
-            a.dgates[og + (unsigned)(2 * H)] = dgg; a.dgates[og + (unsigned)(3 * H)] = dgo;
-            float* gl = dg + erow * DS + ej;
-            gl[0] = dgi; gl[KQ * 4] = dgf; gl[2 * KQ * 4] = dgg; gl[3 * KQ * 4] = dgo;
-        }
-        __syncthreads();
-        if (t > 0 && cg * 64 < H) {
-            f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-            for (int q = 0; q < KQ; ++q) {
-                const float4 dv = *reinterpret_cast<const float4*>(drow + 4 * q);
-                acc = MFMA4(dv.x, wq[q].x, acc);
-                acc = MFMA4(dv.y, wq[q].y, acc);
-                acc = MFMA4(dv.z, wq[q].z, acc);
-                acc = MFMA4(dv.w, wq[q].w, acc);
-            }
-#pragma unroll
-            for (int r = 0; r < 4; ++r) part[(gb * RB4 + r) * PS + n] = acc[r];
-        }
-        __syncthreads();
-    }
-}
-
 // ===========================================================================================
-// ONE batch row per workgroup, on the vector ALU (H <= 128).  Training runs B sequences of N - horizon + 1 (124)
-// steps 43 times per learn: at B = 64 the 4-row MFMA kernels keep 16 CUs busy for ~2.1 us per step, of which the
-// matrix pipe needs ~0.9 (a v_mfma_f32_4x4x1 pass computes 4 rows whether it has them or not) and the five
-// transcendentals per (row, unit) thread ~0.8.  Here thread `col` owns gate column col with W_hh[col][0..H) in
-// registers: H fused multiply-adds against h_{t-1} broadcast from LDS, then ITS gate's one activation; the H unit
-// threads then form c_t, h_t.  Per step: ~100 FMAs + 1 transcendental + 2 short barriers + 2 transcendentals on the
-// unit threads -- and B workgroups instead of B / 4.  Same FLOP rate per row as the MFMA form (H = 100: 40 k MACs per
-// row-step = 312 cycles of a CU's FP32 lanes vs 350 of its matrix pipes per row).  Measured: 14.7 -> 11.1 ms per
-// learn at 64 x 128, 26.5 -> 22.8 at 256 x 128 (SMX_LSTM_MFMA4=1 selects the 4-row kernels for comparison).
-// ===========================================================================================
-template <int HQ>          // H <= 4 HQ
-__global__ __launch_bounds__(NT) void lstm_fwd1_kernel(FwdArgs a) {
-    if (a.stop && *a.stop) return;
-    __shared__ float4 hs4[HQ];                 // h_{t-1}, zero padded
-    __shared__ float gact[4 * 4 * HQ];         // activated gates of the step
-    float* hs = reinterpret_cast<float*>(hs4);
-    const int H = a.H, G = 4 * H, T = a.T;
-    const int tid = threadIdx.x;
-    const int b = blockIdx.x;
-    const bool colv = tid < G, unit = tid < H;
-    float4 w[HQ];
-#pragma unroll
-    for (int q = 0; q < HQ; ++q)
-        w[q] = (colv && 4 * q < H) ? *reinterpret_cast<const float4*>(a.W_hh + (size_t)tid * H + 4 * q)
-                                   : make_float4(0.f, 0.f, 0.f, 0.f);
-    const float bias = colv ? a.b_hh[tid] : 0.f;
-    const bool is_g = tid >= 2 * H && tid < 3 * H;     // the cell candidate: tanh; the other gates: sigmoid
-    if (tid < 4 * HQ) hs[tid] = (unit && a.h0) ? a.h0[(size_t)b * H + tid] : 0.f;
-    float creg = (unit && a.c0) ? a.c0[(size_t)b * H + tid] : 0.f;
-    const size_t gbase = (size_t)b * T * G, hbase = (size_t)b * T * H;
-    float gx = colv ? a.gates[gbase + tid] : 0.f;      // the input half of step 0 (smx_linear_f32)
-    __syncthreads();
-    for (int t = 0; t < T; ++t) {
-        float acc0 = 0.f, acc1 = 0.f;
-#pragma unroll
-        for (int q = 0; q < HQ; ++q) {
-            const float4 hv = hs4[q];
-            acc0 = __builtin_fmaf(hv.x, w[q].x, acc0);
-            acc1 = __builtin_fmaf(hv.y, w[q].y, acc1);
-            acc0 = __builtin_fmaf(hv.z, w[q].z, acc0);
-            acc1 = __builtin_fmaf(hv.w, w[q].w, acc1);
-        }
-        const float pre = gx + ((acc0 + acc1) + bias);
-        const float act = is_g ? tanhf(pre) : sigm(pre);
-        if (colv) {
-            gact[tid] = act;
-            a.gates[gbase + (size_t)t * G + tid] = act;
-        }
-        gx = (colv && t + 1 < T) ? a.gates[gbase + (size_t)(t + 1) * G + tid] : 0.f;
-        LSTM_LDS_BARRIER();
-        if (unit) {
-            const float gi = gact[tid], gf = gact[H + tid], gg = gact[2 * H + tid], go = gact[3 * H + tid];
-            const float c = gf * creg + gi * gg;
-            const float h = go * tanhf(c);
-            const size_t oh = hbase + (size_t)t * H + tid;
-            a.out[oh] = h;
-            a.cs[oh] = c;
-            if (a.hprev) a.hprev[oh] = hs[tid];
-            creg = c;
-            hs[tid] = h;
-        }
-        LSTM_LDS_BARRIER();
-    }
-    if (unit) {
-        if (a.hN) a.hN[(size_t)b * H + tid] = hs[tid];
-        if (a.cN) a.cN[(size_t)b * H + tid] = creg;
-    }
-}
-
-// backward of the same: thread (gb = tid / H, n = tid % H) keeps W_hh[gb H + k][n], k < H, in registers and forms gate
-// block gb's share of dh_rec[n]; the four shares are added in a fixed order by the unit threads of the next step
-template <int HQ>
-__global__ __launch_bounds__(NT) void lstm_bwd1_kernel(BwdArgs a) {
-    if (a.stop && *a.stop) return;
-    __shared__ float4 dg4[4][HQ];              // dgates of the step, gate block gb at dg4[gb] (zero padded)
-    __shared__ float part[4][4 * HQ];
-    const int H = a.H, G = 4 * H, T = a.T;
-    const int tid = threadIdx.x;
-    const int b = blockIdx.x;
-    const bool colv = tid < G, unit = tid < H;
-    const int gb = colv ? tid / H : 0, n = colv ? tid - gb * H : 0;
-    float4 w[HQ];
-#pragma unroll
-    for (int q = 0; q < HQ; ++q) {
-        float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (colv && 4 * q < H) {
-            const float* p = a.W_hh + ((size_t)gb * H + 4 * q) * H + n;
-            v = make_float4(p[0], p[H], p[2 * (size_t)H], p[3 * (size_t)H]);
-        }
-        w[q] = v;
-    }
-    for (int idx = tid; idx < 4 * 4 * HQ; idx += NT) {
-        reinterpret_cast<float*>(dg4)[idx] = 0.f;
-        reinterpret_cast<float*>(part)[idx] = 0.f;
-    }
-    const size_t gbase = (size_t)b * T * G, hbase = (size_t)b * T * H;
-    float dcreg = 0.f;
-    float gi = 0.f, gf = 0.f, gg = 0.f, go = 0.f, c = 0.f, cp = 0.f, dout = 0.f;
-    auto fetch = [&](int t, float& xi, float& xf, float& xg, float& xo, float& xcp, float& xd) {
-        const size_t og = gbase + (size_t)t * G + tid, oh = hbase + (size_t)t * H + tid;
-        xi = a.gates[og]; xf = a.gates[og + H]; xg = a.gates[og + 2 * (size_t)H]; xo = a.gates[og + 3 * (size_t)H];
-        xcp = (t > 0) ? a.cs[oh - H] : (a.c0 ? a.c0[(size_t)b * H + tid] : 0.f);
-        xd = a.dout[oh];
-    };
-    if (unit) {
-        fetch(T - 1, gi, gf, gg, go, cp, dout);
-        c = a.cs[hbase + (size_t)(T - 1) * H + tid];
-    }
-    __syncthreads();
-    float* dg = reinterpret_cast<float*>(dg4);
-    for (int t = T - 1; t >= 0; --t) {
-        float ni = 0.f, nf = 0.f, ng = 0.f, no = 0.f, ncp = 0.f, nd = 0.f;
-        if (unit && t > 0) fetch(t - 1, ni, nf, ng, no, ncp, nd);      // the next step's inputs: requested early
-        if (unit) {
-            const float dhr = ((part[0][tid] + part[1][tid]) + part[2][tid]) + part[3][tid];
-            const float dh = dout + dhr;
-            const float tc = tanhf(c);
-            const float dc = dcreg + (dh * go) * (1.f - tc * tc);
-            const float dgi = (dc * gg) * (gi * (1.f - gi));
-            const float dgf = (dc * cp) * (gf * (1.f - gf));
-            const float dgg = (dc * gi) * (1.f - gg * gg);
-            const float dgo = (dh * tc) * (go * (1.f - go));
-            dcreg = dc * gf;
-            const size_t og = gbase + (size_t)t * G + tid;
-            a.dgates[og] = dgi; a.dgates[og + H] = dgf;
-            a.dgates[og + 2 * (size_t)H] = dgg; a.dgates[og + 3 * (size_t)H] = dgo;
-            dg[tid] = dgi; dg[4 * HQ + tid] = dgf; dg[8 * HQ + tid] = dgg; dg[12 * HQ + tid] = dgo;
-        }
-        LSTM_LDS_BARRIER();
-        if (t > 0 && colv) {
-            float acc0 = 0.f, acc1 = 0.f;
-#pragma unroll
-            for (int q = 0; q < HQ; ++q) {
-                const float4 dv = dg4[gb][q];
-                acc0 = __builtin_fmaf(dv.x, w[q].x, acc0);
-                acc1 = __builtin_fmaf(dv.y, w[q].y, acc1);
-                acc0 = __builtin_fmaf(dv.z, w[q].z, acc0);
-                acc1 = __builtin_fmaf(dv.w, w[q].w, acc1);
-            }
-            part[gb][n] = acc0 + acc1;
-        }
-        c = cp;
-        gi = ni; gf = nf; gg = ng; go = no; cp = ncp; dout = nd;
-        LSTM_LDS_BARRIER();
-    }
-}
-
-// ===========================================================================================
-// The same one-row-per-workgroup recurrence with the four gates of a hidden unit in ADJACENT LANES (thread 4 n + g:
-// unit n, gate g).  What that buys per time step:
-//   * the gates of a unit meet through DPP quad broadcasts -- no LDS round trip and no barrier between the gate
-//     activations and the cell update, which all four lanes of a quad now form redundantly (on all eight waves instead
-//     of two waves working while six wait);
+// ONE batch row per workgroup on the vector ALU (H <= 128), the four lanes of a quad working for ONE hidden unit.
+// Training runs B sequences of N - horizon + 1 (124) steps 43 times per learn; at B = 64 a step is a latency chain on
+// 64 CUs, not a throughput problem, and a matrix instruction that computes 4 or 16 rows whether it has them or not buys
+// nothing.  Here W_hh sits in registers for the whole sequence (H = 100: 100 weights per lane), and per time step:
+//   * the gates of a unit meet through DPP quad moves -- no LDS round trip and no barrier between the gate
+//     activations and the cell update, which all four lanes of a quad form redundantly;
 //   * h_t (forward) / the step's dgates (backward) ping-pong between two LDS buffers, so ONE barrier per step is
 //     enough (a buffer is rewritten two steps later, behind the barrier of the step in between);
-//   * backward: a quad's four partial sums of dh_rec stay in registers and are added by DPP in the fixed order
-//     ((p0 + p1) + p2) + p3 -- the LDS exchange and its barrier are gone;
-//   * the H multiply-adds per lane are packed two to an instruction (v_pk_fma_f32), same two accumulation chains.
-// Every value is formed by the same operations in the same order as in lstm_fwd1 / lstm_bwd1_kernel (bit-identical
-// results); SMX_LSTM_V1=1 selects those for A/B runs.
+//   * the multiply-adds are packed two to an instruction (v_pk_fma_f32), on two accumulation chains.
 // ===========================================================================================
 typedef float v2f __attribute__((ext_vector_type(2)));
 
@@ -566,72 +242,6 @@ __device__ __forceinline__ float quad_bcast(float v) {      // lane G of every q
     return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), G * 0x55, 0xf, 0xf, true));
 }
 
-template <int HQ>          // H <= 4 HQ
-__global__ __launch_bounds__(NT) void lstm_fwdq_kernel(FwdArgs a) {
-    if (a.stop && *a.stop) return;
-    __shared__ float4 hs4[2][HQ];              // h_{t-1} / h_t, zero padded
-    const int H = a.H, G = 4 * H, T = a.T;
-    const int tid = threadIdx.x;
-    const int b = blockIdx.x;
-    const bool colv = tid < G;
-    const int n = tid >> 2, g = tid & 3;
-    const int col = colv ? g * H + n : 0;
-    float4 w[HQ];
-#pragma unroll
-    for (int q = 0; q < HQ; ++q)
-        w[q] = (colv && 4 * q < H) ? *reinterpret_cast<const float4*>(a.W_hh + (size_t)col * H + 4 * q)
-                                   : make_float4(0.f, 0.f, 0.f, 0.f);
-    const float bias = colv ? a.b_hh[col] : 0.f;
-    const bool is_g = g == 2;                  // the cell candidate: tanh; the other gates: sigmoid
-    float* hs = reinterpret_cast<float*>(hs4);
-    for (int i = tid; i < 2 * 4 * HQ; i += NT) hs[i] = 0.f;
-    __syncthreads();
-    if (colv && g == 0 && a.h0) hs[n] = a.h0[(size_t)b * H + n];
-    float creg = (colv && a.c0) ? a.c0[(size_t)b * H + n] : 0.f;
-    const size_t gbase = (size_t)b * T * G, hbase = (size_t)b * T * H;
-    float gx = colv ? a.gates[gbase + col] : 0.f;      // the input half of step 0 (smx_linear_f32)
-    __syncthreads();
-    for (int t = 0; t < T; ++t) {
-        const int p = t & 1;
-        v2f acc = {0.f, 0.f};
-#pragma unroll
-        for (int q = 0; q < HQ; ++q) {
-            const float4 hv = hs4[p][q];
-            acc = __builtin_elementwise_fma((v2f){hv.x, hv.y}, (v2f){w[q].x, w[q].y}, acc);
-            acc = __builtin_elementwise_fma((v2f){hv.z, hv.w}, (v2f){w[q].z, w[q].w}, acc);
-        }
-        const float pre = gx + ((acc.x + acc.y) + bias);
-        const float act = is_g ? tanhf(pre) : sigm(pre);
-        if (colv) a.gates[gbase + (size_t)t * G + col] = act;
-        gx = (colv && t + 1 < T) ? a.gates[gbase + (size_t)(t + 1) * G + col] : 0.f;
-        const float gi = quad_bcast<0>(act), gf = quad_bcast<1>(act), gg = quad_bcast<2>(act), go = quad_bcast<3>(act);
-        const float c = gf * creg + gi * gg;
-        const float h = go * tanhf(c);
-        creg = c;
-        if (colv && g == 0) {
-            const size_t oh = hbase + (size_t)t * H + n;
-            a.out[oh] = h;
-            a.cs[oh] = c;
-            if (a.hprev) a.hprev[oh] = hs[p * 4 * HQ + n];
-            hs[(1 - p) * 4 * HQ + n] = h;
-        }
-        LSTM_LDS_BARRIER();
-    }
-    if (colv && g == 0) {
-        if (a.hN) a.hN[(size_t)b * H + n] = hs[(T & 1) * 4 * HQ + n];
-        if (a.cN) a.cN[(size_t)b * H + n] = creg;
-    }
-}
-
-// ===========================================================================================
-// Forward recurrence with the K SUM of a hidden unit split over its quad (thread 4 n + kq: unit n, k-quarter kq, all
-// four gates).  In lstm_fwdq_kernel every lane reads ALL of h_{t-1} from LDS each step: 25 ds_read_b128 per lane whose
-// data return -- 64 lanes x 16 bytes per instruction, broadcast or not -- is 8 cycles of the CU's one LDS pipe each:
-// 8 wavefronts x 25 x 8 = 1600 cycles of a 2100-cycle step.  Here a lane reads only ITS quarter of h (7 reads, 450
-// cycles per step and CU), multiplies it with the four gates' weights (the same 4 H / 4 = 100 weights per lane, in
-// registers), and the quad's partial sums meet by a DPP reduce-scatter: lane kq ends with gate kq's sum in the fixed
-// order (q0 + q1) + (q2 + q3), activates it, and the cell update proceeds as in lstm_fwdq_kernel.
-// ===========================================================================================
 #include "smx_lstm_act.inc.h"
 
 __device__ __forceinline__ float quad_xor1(float v) {       // lane ^ 1 inside the quad
@@ -641,6 +251,14 @@ __device__ __forceinline__ float quad_xor2(float v) {       // lane ^ 2 inside t
     return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x4E, 0xf, 0xf, true));
 }
 
+// Forward: the K SUM of a hidden unit is split over its quad (thread 4 n + kq: unit n, k-quarter kq, all four gates).
+// A lane reads only ITS quarter of h_{t-1} from LDS (7 ds_read_b128, 450 cycles per step and CU; all of h in every lane
+// would be 25 reads whose data return -- 64 lanes x 16 bytes per instruction, broadcast or not -- is 8 cycles of the
+// CU's one LDS pipe each: 8 wavefronts x 25 x 8 = 1600 cycles of a 2100-cycle step), multiplies it with the four gates'
+// weights (4 H / 4 = 100 weights per lane, in registers), and the quad's partial sums meet by a DPP reduce-scatter: lane
+// kq ends with gate kq's sum in the fixed order (q0 + q1) + (q2 + q3) and activates it; the quad broadcasts the four
+// activations and every lane forms c_t, h_t.
+//
 // RW batch rows per workgroup (rows RW b .. RW b + RW - 1) share the weights in registers: a step's latency chain
 // (LDS read -> FMAs -> quad reduce -> activation -> LDS write -> barrier, ~1700 cycles of which the FMAs are a quarter)
 // is walked once for RW rows.  One row per workgroup keeps 1024 rows in FOUR rounds of 256 workgroups at 0.18 of the
@@ -724,7 +342,7 @@ __global__ __launch_bounds__(NT) void lstm_fwdk_kernel(FwdArgs a) {
     }
     const unsigned ucol = (unsigned)col, un = (unsigned)n;
     // the input half of the gates (smx_linear_f32 wrote it) is requested FOUR steps ahead: the [B, T, 4H] buffer does not
-    // stay in L2 between the GEMM and this kernel, and a request made one step ahead -- as in lstm_fwdq_kernel -- makes
+    // stay in L2 between the GEMM and this kernel, and a request made one step ahead makes
     // every 0.9 us step wait for a memory round trip of about that length.  Four named registers (per row) rotated by
     // unrolling.
     float gx0[RW], gx1[RW], gx2[RW], gx3[RW];
@@ -836,87 +454,15 @@ __global__ __launch_bounds__(NT) void lstm_fwdk_kernel(FwdArgs a) {
     }
 }
 
-template <int HQ>
-__global__ __launch_bounds__(NT) void lstm_bwdq_kernel(BwdArgs a) {
-    if (a.stop && *a.stop) return;
-    __shared__ float4 dg4[2][4][HQ];           // the step's dgates, gate block gb at dg4[p][gb] (zero padded)
-    const int H = a.H, G = 4 * H, T = a.T;
-    const int tid = threadIdx.x;
-    const int b = blockIdx.x;
-    const bool colv = tid < G;
-    const int n = colv ? tid >> 2 : 0, gb = tid & 3;
-    float4 w[HQ];
-#pragma unroll
-    for (int q = 0; q < HQ; ++q) {
-        float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (colv && 4 * q < H) {
-            const float* p = a.W_hh + ((size_t)gb * H + 4 * q) * H + n;
-            v = make_float4(p[0], p[H], p[2 * (size_t)H], p[3 * (size_t)H]);
-        }
-        w[q] = v;
-    }
-    float* dg = reinterpret_cast<float*>(dg4);
-    for (int idx = tid; idx < 2 * 4 * 4 * HQ; idx += NT) dg[idx] = 0.f;
-    const size_t gbase = (size_t)b * T * G, hbase = (size_t)b * T * H;
-    float dcreg = 0.f, share = 0.f;            // share: this lane's gate block's part of dh_rec[n] (previous step)
-    float gmine = 0.f, c = 0.f, cp = 0.f, dout = 0.f;
-    auto fetch = [&](int t, float& xg, float& xcp, float& xd) {
-        const size_t oh = hbase + (size_t)t * H + n;
-        xg = a.gates[gbase + (size_t)t * G + (size_t)gb * H + n];      // this lane's own gate of unit n
-        xcp = (t > 0) ? a.cs[oh - H] : (a.c0 ? a.c0[(size_t)b * H + n] : 0.f);
-        xd = a.dout[oh];
-    };
-    if (colv) {
-        fetch(T - 1, gmine, cp, dout);
-        c = a.cs[hbase + (size_t)(T - 1) * H + n];
-    }
-    __syncthreads();
-    for (int t = T - 1; t >= 0; --t) {
-        const int p = t & 1;
-        float ng = 0.f, ncp = 0.f, nd = 0.f;
-        if (colv && t > 0) fetch(t - 1, ng, ncp, nd);              // the next step's inputs: requested early
-        const float gi = quad_bcast<0>(gmine), gf = quad_bcast<1>(gmine), gg = quad_bcast<2>(gmine),
-                    go = quad_bcast<3>(gmine);
-        const float dhr = ((quad_bcast<0>(share) + quad_bcast<1>(share)) + quad_bcast<2>(share)) + quad_bcast<3>(share);
-        const float dh = dout + dhr;
-        const float tc = fast_tanh(c);             // (the forward pass formed h with the same function)
-        const float dc = dcreg + (dh * go) * (1.f - tc * tc);
-        const float dgi = (dc * gg) * (gi * (1.f - gi));
-        const float dgf = (dc * cp) * (gf * (1.f - gf));
-        const float dgg = (dc * gi) * (1.f - gg * gg);
-        const float dgo = (dh * tc) * (go * (1.f - go));
-        dcreg = dc * gf;
-        const float mine = gb == 0 ? dgi : (gb == 1 ? dgf : (gb == 2 ? dgg : dgo));
-        if (colv) {
-            a.dgates[gbase + (size_t)t * G + (size_t)gb * H + n] = mine;
-            dg[((p * 4 + gb) * 4 * HQ) + n] = mine;
-        }
-        LSTM_LDS_BARRIER();
-        share = 0.f;
-        if (t > 0 && colv) {
-            v2f acc = {0.f, 0.f};
-#pragma unroll
-            for (int q = 0; q < HQ; ++q) {
-                const float4 dv = dg4[p][gb][q];
-                acc = __builtin_elementwise_fma((v2f){dv.x, dv.y}, (v2f){w[q].x, w[q].y}, acc);
-                acc = __builtin_elementwise_fma((v2f){dv.z, dv.w}, (v2f){w[q].z, w[q].w}, acc);
-            }
-            share = acc.x + acc.y;
-        }
-        c = cp;
-        gmine = ng; cp = ncp; dout = nd;
-    }
-}
-
 // ===========================================================================================
-// Backward recurrence with TWO hidden units per 8 lanes in the dh_rec product.  In lstm_bwdq_kernel lane (n, gb) reads
-// the 100 dgates of gate block gb -- 25 ds_read_b128 whose data return (64 lanes x 16 bytes = 8 cycles of the CU's LDS
-// pipe each, x 8 wavefronts = 1600 cycles) bounds the 2470-cycle step.  Here the eight lanes of two adjacent quads
-// (units 2 p and 2 p + 1) split the K = 4 H sum eight ways -- lane e takes half (e & 1) of gate block e >> 1 -- and
-// each forms the partial sums of BOTH units from the words it reads: 13 reads per lane, the same 100 weights in
-// registers.  The partials meet by DPP: the two quads swap the other unit's partial (row_shl / row_shr 4), then each
-// quad adds its four in the fixed order (l0 + l1) + (l2 + l3).  The element-wise half of the step is that of
-// lstm_bwdq_kernel (thread 4 n + gb).
+// Backward of the same.  Element-wise half of a step on thread 4 n + gb (gate gb of unit n): the quad broadcasts the
+// unit's four gates, every lane forms dc and the four dgates and stores ITS gate's.  The product dh_rec = dgates . W_hh
+// takes TWO hidden units per 8 lanes: a lane that read the 100 dgates of one gate block by itself would issue 25
+// ds_read_b128 whose data return (64 lanes x 16 bytes = 8 cycles of the CU's LDS pipe each, x 8 wavefronts = 1600
+// cycles) bounds the step.  Here the eight lanes of two adjacent quads (units 2 p and 2 p + 1) split the K = 4 H sum
+// eight ways -- lane e takes half (e & 1) of gate block e >> 1 -- and each forms the partial sums of BOTH units from the
+// words it reads: 13 reads per lane, the same 100 weights in registers.  The partials meet by DPP: the two quads swap
+// the other unit's partial (row_shl / row_shr 4), then each quad adds its four in the fixed order (l0 + l1) + (l2 + l3).
 // ===========================================================================================
 __device__ __forceinline__ float row_from_plus4(float v) {   // lane i <- lane i + 4 (inside a 16-lane row)
     return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x104, 0xf, 0xf, true));
@@ -1061,13 +607,11 @@ __global__ __launch_bounds__(NT) void lstm_bwdk_kernel(BwdArgs a) {
 }
 
 // ===========================================================================================
-// Round 5: FOUR batch rows per workgroup on v_mfma_f32_4x4x1_16B (H <= 112), for B >= 1024 -- where every CU holds a
-// workgroup, the recurrence is throughput-, not latency-bound, and the vector kernels above spend 0.45 of a step issuing
-// multiply-adds (lstm_fwdk / lstm_bwdk at four rows: 2.7 - 2.9 us per step and CU).  One v_mfma_f32_4x4x1 is 16
-// independent 4 x 4 outer products: lane 4 b + i supplies row i of block b's A, lane 4 b + j column j of its B, and holds
-// column j of its 4 x 4 result.  Round 2's 4-row kernels (lstm_fwd4 / lstm_bwd4_kernel above, SMX_LSTM_MFMA4=1) used it with
-// gate columns in lane order; their results met in LDS, with two barriers and libm's expf / tanhf per step.  Here the
-// blocks are laid out so that NOTHING crosses wavefronts inside a step:
+// FOUR batch rows per workgroup on v_mfma_f32_4x4x1_16B (H <= 112), for B >= 512 -- where every CU holds a workgroup, the
+// recurrence is throughput-, not latency-bound, and the vector kernels above spend 0.45 of a step issuing multiply-adds
+// (lstm_fwdk / lstm_bwdk at four rows: 2.7 - 2.9 us per step and CU).  One v_mfma_f32_4x4x1 is 16 independent 4 x 4
+// outer products: lane 4 b + i supplies row i of block b's A, lane 4 b + j column j of its B, and holds column j of its
+// 4 x 4 result.  The blocks are laid out so that NOTHING crosses wavefronts inside a step:
 //   forward   block b of wave w = hidden unit 16 w + b, its columns j = the unit's four gates (B = W_hh[j H + unit][k] in
 //             registers, A = h_{t-1}[i][k] from LDS, the same for every block).  A lane then holds gate j of its unit for
 //             the 4 rows, activates them (hardware exp2 / rcp), the quad exchanges gates by DPP, and lane j forms c_t, h_t
@@ -1076,7 +620,7 @@ __global__ __launch_bounds__(NT) void lstm_bwdk_kernel(BwdArgs a) {
 //   backward  dh_rec = dgates . W_hh: block b = (gate block gb = b >> 2, column quad c = b & 3): A = dgates_t[i][gb H + k]
 //             from LDS, B = W_hh[gb H + k][16 w + 4 c + j]; the four gate blocks' partial sums of a column sit 16 lanes
 //             apart and meet by two cross-lane adds; lane (gb, c, j) then does the element-wise step of ROW gb of its
-//             column.  The step's inputs are requested one step ahead.  ONE barrier per step.
+//             column.  The step's inputs are requested two steps ahead.  ONE barrier per step.
 // Four accumulators per lane (k mod 4) instead of one chain of 100 dependent MFMAs, added (x + y) + (z + w).
 // ===========================================================================================
 // acc += A-row (LDS, 4 KQ floats) x the lane's weights, k mod 4 on four accumulators.  The operand words are requested a GROUP
@@ -1366,16 +910,63 @@ __global__ __launch_bounds__(NT) void lstm_bwdm_kernel(BwdArgs a) {
 #undef SMX_BWDM_FETCH
 }
 
-constexpr int KQ4 = 28;          // 4-row kernels: H <= 112
-
-inline size_t lds4_fwd(int kq) { return (size_t)RB4 * ((kq * 4 + 4) + (NWV * 64 + 4)) * sizeof(float); }
-inline size_t lds4_bwd(int kq) { return (size_t)(RB4 * (16 * kq + 4) + 4 * RB4 * (128 + 4)) * sizeof(float); }
-
 constexpr int KG_MAX = 24;       // 16-row kernels: H <= 384 (LDS-bound)
 
 inline size_t lds_bytes(int kg, int H) {
     const int HS = kg * 16 + 4, GS = ((4 * H + 15) & ~15) + 4;
     return (size_t)RB * (HS + GS + H) * sizeof(float);
+}
+
+// ---- which kernel runs: a function of (B, D, H) alone, the same for forward and backward -------------------------------
+//   forward, in order:   H <= 112 && B >= 512   lstm_fwdm_kernel<25 | 28, fold> (25: H <= 100), four rows per workgroup
+//                        H <= 112               lstm_fwdk_kernel<7, 1, fold>
+//                        H <= 128               lstm_fwdk_kernel<8, B >= 512 ? 2 : 1, false>
+//                        else                   lstm_fwd_kernel<KG_MAX>, 16 rows per workgroup
+//   fold = H <= 112 && D <= 20: the input half of the gates is formed inside the recurrence; else smx_linear_f32 writes it
+//          for every (b, t) at once in front of it
+//   backward, in order:  H <= 112 && B >= 512   lstm_bwdm_kernel<25 | 28>
+//                        H <= 104               lstm_bwdk_kernel<13, 1>
+//                        H <= 128               lstm_bwdk_kernel<16, B >= 512 ? 2 : 1>
+//                        else                   lstm_bwd_kernel<KG_MAX>
+// (the vector kernels take two rows per workgroup only for 112 < H <= 128: at H <= 112 those batches are the m family's;
+// four rows per workgroup with FOLD's 20 extra weights would be 256 registers and spills)
+//
+// MROWS_MIN_B: from 512 sequences on, several rows per workgroup.  lstm_fwdm / lstm_bwdm_kernel measured against the
+// vector kernels at 128 steps: 23.2 vs 23.7 ms per learn at 512 sequences, 28.7 vs 38.3 at 768, 34.0 vs 39.2 at 1024 -- and
+// 17.7 vs 13.8 at 256, where one row per workgroup fills the chip.
+constexpr int64_t MROWS_MIN_B = 512;
+
+enum LstmFamily { LSTM_M, LSTM_K, LSTM_ROWS16 };
+
+struct LstmPlan {
+    LstmFamily family;
+    int fwd_w, bwd_w;      // instantiation width: m KQ / KQ, k Q4 / HH, 16-row KG / KG
+    int rows;              // batch rows per workgroup
+    bool fold;
+};
+
+inline LstmPlan lstm_plan(int64_t B, int D, int H) {
+    LstmPlan p;
+    const bool many = B >= MROWS_MIN_B;
+    p.fold = H <= 112 && D <= 20;
+    if (H <= 112 && many) {
+        p.family = LSTM_M; p.fwd_w = p.bwd_w = H <= 100 ? 25 : 28; p.rows = 4;
+    } else if (H <= 128) {
+        p.family = LSTM_K; p.fwd_w = H <= 112 ? 7 : 8; p.bwd_w = H <= 104 ? 13 : 16; p.rows = many ? 2 : 1;
+    } else {
+        p.family = LSTM_ROWS16; p.fwd_w = p.bwd_w = KG_MAX; p.rows = RB;
+    }
+    return p;
+}
+
+// the 16-row kernels' dynamic LDS exceeds the default limit: raised once per kernel
+template <typename Kern>
+inline hipError_t allow_rows16_lds(Kern kern, bool& done) {
+    if (done) return hipSuccess;
+    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
+                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes(KG_MAX, 16 * KG_MAX));
+    done = e == hipSuccess;
+    return e;
 }
 
 }  // namespace
@@ -1389,14 +980,8 @@ extern "C" int smx_lstm_forward_f32(const smx_lstm_t* net, const float* x, int64
     const int H = net->H, D = net->D;
     SMX_REQUIRE(B > 0 && T > 0 && H > 0 && D > 0 && B * T * 4 * H < (1ll << 31), SMX_E_SHAPE);
     SMX_REQUIRE(H % 4 == 0 && H <= 16 * KG_MAX, SMX_E_UNSUPPORTED);
-    static const bool mfma4 = getenv("SMX_LSTM_MFMA4") != nullptr;
-    static const bool v1 = getenv("SMX_LSTM_V1") != nullptr;       // the LDS-exchange one-row kernels, for A/B runs
-    static const bool quad = getenv("SMX_LSTM_QUAD") != nullptr;   // every lane reads all of h (the round-3 first form)
-    static const bool nofold = getenv("SMX_LSTM_NOFOLD") != nullptr;
-    // D <= 20 on the default H <= 112 kernel: the input half of the gates is formed inside the recurrence (FOLD);
-    // else for every (b, t) at once by a GEMM launch in front of it
-    const bool fold = !nofold && !mfma4 && !v1 && !quad && H <= 112 && D <= 20;
-    if (!fold) {
+    const LstmPlan p = lstm_plan(B, D, H);
+    if (!p.fold) {
         int rc = smx_linear_f32(x, D, 1, net->W_ih, D, 1, net->b_ih, gates, 4 * H, (int32_t)(B * T),
                                 4 * H, D, SMX_ACT_NONE, nullptr, stop_flag, stream);
         if (rc) return rc;
@@ -1406,56 +991,28 @@ extern "C" int smx_lstm_forward_f32(const smx_lstm_t* net, const float* x, int64
     a.cs = cs; a.hprev = hprev; a.hN = hN; a.cN = cN; a.stop = stop_flag;
     a.B = (int)B; a.T = T; a.H = H;
     a.x = x; a.W_ih = net->W_ih; a.b_ih = net->b_ih; a.D = D;
-    const int blocks = (int)((B + RB - 1) / RB);
-    // H <= 128: one row per workgroup on the vector ALU (SMX_LSTM_MFMA4=1 keeps the 4-row MFMA kernels for A/B runs)
-    // B >= 512: four rows per workgroup on the matrix pipes (lstm_fwdm_kernel; measured against the vector kernels at
-    // 128 steps: 23.2 vs 23.7 ms per learn at 512 sequences, 28.7 vs 38.3 at 768, 34.0 vs 39.2 at 1024 -- and 17.7 vs 13.8
-    // at 256, where one row per workgroup fills the chip).  SMX_LSTM_NO_MROWS=1 keeps the vector kernels for A/B runs
-    static const bool no_mrows = getenv("SMX_LSTM_NO_MROWS") != nullptr;
-    static const long mrows_min = getenv("SMX_LSTM_MROWS_MIN") ? atol(getenv("SMX_LSTM_MROWS_MIN")) : 512;   // (measurements)
-    const bool mrows = !no_mrows && !mfma4 && !v1 && !quad && H <= 112 && B >= mrows_min;
-    if (mrows) {
-        const dim3 grid((unsigned)((B + 3) / 4));
-        if (fold && H <= 100) hipLaunchKernelGGL((lstm_fwdm_kernel<25, true>), grid, dim3(NT), 0, smx_s(stream), a);
-        else if (fold) hipLaunchKernelGGL((lstm_fwdm_kernel<28, true>), grid, dim3(NT), 0, smx_s(stream), a);
-        else if (H <= 100) hipLaunchKernelGGL((lstm_fwdm_kernel<25, false>), grid, dim3(NT), 0, smx_s(stream), a);
-        else hipLaunchKernelGGL((lstm_fwdm_kernel<28, false>), grid, dim3(NT), 0, smx_s(stream), a);
-    } else if (fold) {
-        // (four rows per workgroup with the 20 extra weights: 256 registers and spills -- two it is)
-        if (B >= 512) hipLaunchKernelGGL((lstm_fwdk_kernel<7, 2, true>), dim3((unsigned)((B + 1) / 2)), dim3(NT), 0, smx_s(stream), a);
-        else hipLaunchKernelGGL((lstm_fwdk_kernel<7, 1, true>), dim3((unsigned)B), dim3(NT), 0, smx_s(stream), a);
-    } else if (!mfma4 && !v1 && !quad && H <= 112) {
-        // (B >= 512 reaches this only with SMX_LSTM_NO_MROWS: two rows per workgroup)
-        if (B >= 512) hipLaunchKernelGGL((lstm_fwdk_kernel<7, 2, false>), dim3((unsigned)((B + 1) / 2)), dim3(NT), 0, smx_s(stream), a);
-        else hipLaunchKernelGGL((lstm_fwdk_kernel<7, 1, false>), dim3((unsigned)B), dim3(NT), 0, smx_s(stream), a);
-    } else if (!mfma4 && !v1 && !quad && H <= 128) {
-        if (B >= 512) hipLaunchKernelGGL((lstm_fwdk_kernel<8, 2, false>), dim3((unsigned)((B + 1) / 2)), dim3(NT), 0, smx_s(stream), a);
-        else hipLaunchKernelGGL((lstm_fwdk_kernel<8, 1, false>), dim3((unsigned)B), dim3(NT), 0, smx_s(stream), a);
-    } else if (!mfma4 && !v1 && H <= 100) {
-        hipLaunchKernelGGL((lstm_fwdq_kernel<25>), dim3((unsigned)B), dim3(NT), 0, smx_s(stream), a);
-    } else if (!mfma4 && !v1 && H <= 128) {
-        hipLaunchKernelGGL((lstm_fwdq_kernel<32>), dim3((unsigned)B), dim3(NT), 0, smx_s(stream), a);
-    } else if (!mfma4 && H <= 100) {
-        hipLaunchKernelGGL((lstm_fwd1_kernel<25>), dim3((unsigned)B), dim3(NT), 0, smx_s(stream), a);
-    } else if (!mfma4 && H <= 128) {
-        hipLaunchKernelGGL((lstm_fwd1_kernel<32>), dim3((unsigned)B), dim3(NT), 0, smx_s(stream), a);
-    } else if (H <= 100) {
-        hipLaunchKernelGGL((lstm_fwd4_kernel<25>), dim3((unsigned)((B + RB4 - 1) / RB4)), dim3(NT),
-                           lds4_fwd(25), smx_s(stream), a);
-    } else if (H <= 4 * KQ4) {
-        hipLaunchKernelGGL((lstm_fwd4_kernel<KQ4>), dim3((unsigned)((B + RB4 - 1) / RB4)), dim3(NT),
-                           lds4_fwd(KQ4), smx_s(stream), a);
-    } else {
+    const dim3 grid((unsigned)((B + p.rows - 1) / p.rows)), block(NT);
+    hipStream_t st = smx_s(stream);
+    switch (p.family) {
+    case LSTM_M:
+        if (p.fwd_w == 25 && p.fold) hipLaunchKernelGGL((lstm_fwdm_kernel<25, true>), grid, block, 0, st, a);
+        else if (p.fwd_w == 25) hipLaunchKernelGGL((lstm_fwdm_kernel<25, false>), grid, block, 0, st, a);
+        else if (p.fold) hipLaunchKernelGGL((lstm_fwdm_kernel<28, true>), grid, block, 0, st, a);
+        else hipLaunchKernelGGL((lstm_fwdm_kernel<28, false>), grid, block, 0, st, a);
+        break;
+    case LSTM_K:
+        if (p.fwd_w == 7 && p.fold) hipLaunchKernelGGL((lstm_fwdk_kernel<7, 1, true>), grid, block, 0, st, a);
+        else if (p.fwd_w == 7) hipLaunchKernelGGL((lstm_fwdk_kernel<7, 1, false>), grid, block, 0, st, a);
+        else if (p.rows == 2) hipLaunchKernelGGL((lstm_fwdk_kernel<8, 2, false>), grid, block, 0, st, a);
+        else hipLaunchKernelGGL((lstm_fwdk_kernel<8, 1, false>), grid, block, 0, st, a);
+        break;
+    case LSTM_ROWS16: {
         static bool attr_set = false;
-        if (!attr_set) {
-            hipError_t e = hipFuncSetAttribute(
-                reinterpret_cast<const void*>(&lstm_fwd_kernel<KG_MAX>),
-                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes(KG_MAX, 16 * KG_MAX));
-            if (e != hipSuccess) return (int)e;
-            attr_set = true;
-        }
-        hipLaunchKernelGGL((lstm_fwd_kernel<KG_MAX>), dim3(blocks), dim3(NT),
-                           lds_bytes(KG_MAX, H), smx_s(stream), a);
+        const hipError_t e = allow_rows16_lds(&lstm_fwd_kernel<KG_MAX>, attr_set);
+        if (e != hipSuccess) return (int)e;
+        hipLaunchKernelGGL((lstm_fwd_kernel<KG_MAX>), grid, block, lds_bytes(KG_MAX, H), st, a);
+        break;
+    }
     }
     SMX_LAUNCH_CHECK();
     return SMX_OK;
@@ -1474,47 +1031,26 @@ extern "C" int smx_lstm_backward_f32(const smx_lstm_t* net, const float* x, int6
     BwdArgs a;
     a.W_hh = net->W_hh; a.c0 = c0; a.gates = gates; a.cs = cs; a.dout = dout; a.dgates = dgates;
     a.stop = stop_flag; a.B = (int)B; a.T = T; a.H = H;
-    const int blocks = (int)((B + RB - 1) / RB);
-    static const bool mfma4 = getenv("SMX_LSTM_MFMA4") != nullptr;
-    static const bool v1 = getenv("SMX_LSTM_V1") != nullptr;
-    static const bool quad = getenv("SMX_LSTM_QUAD") != nullptr;
-    static const bool no_mrows = getenv("SMX_LSTM_NO_MROWS") != nullptr;
-    static const long mrows_min = getenv("SMX_LSTM_MROWS_MIN") ? atol(getenv("SMX_LSTM_MROWS_MIN")) : 512;
-    if (!no_mrows && !mfma4 && !v1 && !quad && H <= 112 && B >= mrows_min) {
-        const dim3 grid((unsigned)((B + 3) / 4));
-        if (H <= 100) hipLaunchKernelGGL((lstm_bwdm_kernel<25>), grid, dim3(NT), 0, smx_s(stream), a);
-        else hipLaunchKernelGGL((lstm_bwdm_kernel<28>), grid, dim3(NT), 0, smx_s(stream), a);
-    } else if (!mfma4 && !v1 && !quad && H <= 104) {
-        if (B >= 512) hipLaunchKernelGGL((lstm_bwdk_kernel<13, 2>), dim3((unsigned)((B + 1) / 2)), dim3(NT), 0, smx_s(stream), a);
-        else hipLaunchKernelGGL((lstm_bwdk_kernel<13, 1>), dim3((unsigned)B), dim3(NT), 0, smx_s(stream), a);
-    } else if (!mfma4 && !v1 && !quad && H <= 128) {
-        if (B >= 512) hipLaunchKernelGGL((lstm_bwdk_kernel<16, 2>), dim3((unsigned)((B + 1) / 2)), dim3(NT), 0, smx_s(stream), a);
-        else hipLaunchKernelGGL((lstm_bwdk_kernel<16, 1>), dim3((unsigned)B), dim3(NT), 0, smx_s(stream), a);
-    } else if (!mfma4 && !v1 && H <= 100) {
-        hipLaunchKernelGGL((lstm_bwdq_kernel<25>), dim3((unsigned)B), dim3(NT), 0, smx_s(stream), a);
-    } else if (!mfma4 && !v1 && H <= 128) {
-        hipLaunchKernelGGL((lstm_bwdq_kernel<32>), dim3((unsigned)B), dim3(NT), 0, smx_s(stream), a);
-    } else if (!mfma4 && H <= 100) {
-        hipLaunchKernelGGL((lstm_bwd1_kernel<25>), dim3((unsigned)B), dim3(NT), 0, smx_s(stream), a);
-    } else if (!mfma4 && H <= 128) {
-        hipLaunchKernelGGL((lstm_bwd1_kernel<32>), dim3((unsigned)B), dim3(NT), 0, smx_s(stream), a);
-    } else if (H <= 100) {
-        hipLaunchKernelGGL((lstm_bwd4_kernel<25>), dim3((unsigned)((B + RB4 - 1) / RB4)), dim3(NT),
-                           lds4_bwd(25), smx_s(stream), a);
-    } else if (H <= 4 * KQ4) {
-        hipLaunchKernelGGL((lstm_bwd4_kernel<KQ4>), dim3((unsigned)((B + RB4 - 1) / RB4)), dim3(NT),
-                           lds4_bwd(KQ4), smx_s(stream), a);
-    } else {
+    const LstmPlan p = lstm_plan(B, D, H);
+    const dim3 grid((unsigned)((B + p.rows - 1) / p.rows)), block(NT);
+    hipStream_t st = smx_s(stream);
+    switch (p.family) {
+    case LSTM_M:
+        if (p.bwd_w == 25) hipLaunchKernelGGL((lstm_bwdm_kernel<25>), grid, block, 0, st, a);
+        else hipLaunchKernelGGL((lstm_bwdm_kernel<28>), grid, block, 0, st, a);
+        break;
+    case LSTM_K:
+        if (p.bwd_w == 13) hipLaunchKernelGGL((lstm_bwdk_kernel<13, 1>), grid, block, 0, st, a);
+        else if (p.rows == 2) hipLaunchKernelGGL((lstm_bwdk_kernel<16, 2>), grid, block, 0, st, a);
+        else hipLaunchKernelGGL((lstm_bwdk_kernel<16, 1>), grid, block, 0, st, a);
+        break;
+    case LSTM_ROWS16: {
         static bool attr_set = false;
-        if (!attr_set) {
-            hipError_t e = hipFuncSetAttribute(
-                reinterpret_cast<const void*>(&lstm_bwd_kernel<KG_MAX>),
-                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes(KG_MAX, 16 * KG_MAX));
-            if (e != hipSuccess) return (int)e;
-            attr_set = true;
-        }
-        hipLaunchKernelGGL((lstm_bwd_kernel<KG_MAX>), dim3(blocks), dim3(NT),
-                           lds_bytes(KG_MAX, H), smx_s(stream), a);
+        const hipError_t e = allow_rows16_lds(&lstm_bwd_kernel<KG_MAX>, attr_set);
+        if (e != hipSuccess) return (int)e;
+        hipLaunchKernelGGL((lstm_bwd_kernel<KG_MAX>), grid, block, lds_bytes(KG_MAX, H), st, a);
+        break;
+    }
     }
     SMX_LAUNCH_CHECK();
     // grads = [dW_ih (4H x D) | dW_hh (4H x H) | db_ih (4H) | db_hh (4H)]  (nn.LSTM parameter order)

@@ -19,7 +19,6 @@
 //   * FP32 MFMA (exact fp32, no bf16/xf32): 1e-5 parity with the CPU reference is the contract.
 #include "smx_common.h"
 #include "smx_mlp3_fused.inc.h"
-#include <stdlib.h>
 #include <string.h>
 
 namespace {
@@ -652,11 +651,9 @@ extern "C" int smx_mlp3_forward_fused_f32(const float* packed, int32_t D, int32_
              (T1 == 0 || ((uintptr_t)x_tail & 15) == 0) &&
              (zmean == nullptr || ((((uintptr_t)zmean | (uintptr_t)zstd) & 15) == 0));
     if (nt1 == 2) return launch_fused<2, 2>(A, smx_s(stream));
-    // 16-row wavefronts (smx_mlp3_rows16.hip) where the shape allows; SMX_FUSED32=1 keeps the 32-row
-    // kernel for A/B measurements (scripts/bench_gemm.py)
-    static const bool force32 = getenv("SMX_FUSED32") != nullptr;
+    // 16-row wavefronts (smx_mlp3_rows16.hip) where the shape allows
     if (g_exact_zfilter && zmean) A.xvec = 0;
-    if (!force32 && A.xvec) {
+    if (A.xvec) {
         const int rc = smx_rows16_launch(A, H1, H2, smx_s(stream));
         if (rc != SMX_E_UNSUPPORTED) return rc;
     }

@@ -958,24 +958,30 @@ def test_mlp3_multi_jobs_with_transposed_operands(K, rows, D):
 # ---- LSTM stem: smx_lstm_forward_f32 / smx_lstm_backward_f32 vs torch.nn.LSTM (ATen CPU fp32,
 # the op the reference calls, ppo_net.py:146-149) and vs the double's statement of the contract
 @pytest.mark.parametrize('B,T,D,H,cells', [
+    # B < 512, H <= 104, D <= 20: lstm_fwdk_kernel<7, 1, true> (input projection folded in) / lstm_bwdk_kernel<13, 1>
     (2, 21, 17, 100, True),      # cfg1 epochs: E = 25 - 5 + 1
     (2, 26, 17, 100, True),      # cfg1 critic pass: N + 1
     (5, 4, 7, 12, True),         # tiny golden
     (37, 9, 17, 100, False),     # ragged rows, zero initial state
     (64, 21, 17, 100, True),     # cfg2-sized batch
-    (6, 7, 9, 108, True),        # 100 < H <= 112: the wider 4-row instantiation
-    (1024, 3, 17, 100, True),    # B >= 512: four rows per workgroup on v_mfma_f32_4x4x1 (lstm_fwdm / bwdm): 256 workgroups
+    (6, 7, 9, 108, True),        # 104 < H <= 112: fwdk<7, 1, true> with the wider lstm_bwdk_kernel<16, 1>
+    (1024, 3, 17, 100, True),    # B >= 512: four rows per workgroup on v_mfma_f32_4x4x1 (lstm_fwdm<25, true> / bwdm<25>): 256 workgroups
     (1027, 6, 17, 100, True),    # ... with a ragged last workgroup (3 of 4 rows)
-    (1026, 4, 9, 108, True),     # ... the 100 < H <= 112 instantiation
-    (1025, 3, 24, 100, False),   # ... with the input projection as a GEMM in front (D > 20)
+    (1026, 4, 9, 108, True),     # ... the 100 < H <= 112 instantiation (lstm_fwdm<28, true> / bwdm<28>)
+    (1025, 3, 24, 100, False),   # ... with the input projection as a GEMM in front (D > 20): lstm_fwdm<25, false>
     (1024, 1, 17, 100, True),    # ... a single step (1024 actors acting): every clamped prefetch index is 0
     (600, 2, 17, 100, True),     # ... two steps
-    (40, 1, 17, 100, True), (40, 2, 17, 100, False),     # ... and the same on the vector kernels
-    (1030, 5, 24, 112, True),    # ... both
+    (40, 1, 17, 100, True), (40, 2, 17, 100, False),     # ... and the same on the vector kernels (fwdk<7, 1, true> / bwdk<13, 1>)
+    (1030, 5, 24, 112, True),    # ... both: lstm_fwdm<28, false> / bwdm<28> at the last H of the four-row kernels
     (515, 7, 17, 100, False),    # ... ragged (3 of 4 rows in the last workgroup), zero initial state
-    (513, 5, 9, 128, True),      # 112 < H <= 128 at B >= 512: the vector kernels, two rows per workgroup
-    (3, 5, 9, 128, True),        # H > 112: 16-row kernels, W_hh fragments re-read every step
-    (20, 6, 11, 256, True),
+    (513, 5, 9, 128, True),      # 112 < H <= 128 at B >= 512: the vector kernels, two rows per workgroup (fwdk<8, 2, false> / bwdk<16, 2>)
+    (3, 5, 9, 128, True),        # 112 < H <= 128, B < 512: lstm_fwdk_kernel<8, 1, false> / lstm_bwdk_kernel<16, 1>, the last H of both
+    (20, 6, 11, 256, True),      # H > 128: the 16-row kernels (lstm_fwd / lstm_bwd_kernel<KG_MAX>), W_hh fragments re-read every step
+    (5, 3, 24, 12, True),        # lstm_fwdk_kernel<7, 1, false>: the projection GEMM in front at B < 512, H <= 112, D > 20
+    (3, 2, 5, 112, True),        # the last H of fwdk<7> with fold, bwdk<16, 1>
+    (3, 2, 5, 116, False),       # the first H of fwdk<8>, zero initial state
+    (3, 2, 5, 104, True),        # the last H of bwdk<13>
+    (3, 2, 20, 100, True), (3, 2, 21, 100, True),        # both sides of the fold boundary D <= 20
 ])
 def test_lstm_forward_backward_match_aten(K, B, T, D, H, cells):
     from surreal_amd.model.ppo_net import LstmParams
