@@ -46,7 +46,7 @@ enum {
 enum { SMX_ACT_NONE = 0, SMX_ACT_RELU = 1, SMX_ACT_TANH = 2 };
 enum { SMX_PPO_CLIP = 0, SMX_PPO_ADAPT = 1 };
 
-int smx_abi_version(void);
+int smx_abi_version(void);   /* 2 (1: the DDPG rollout and the parameter noise had an entry point per actor variant) */
 const char* smx_error_string(int code);
 
 /* ---------------------------------------------------------------------------
@@ -1234,13 +1234,52 @@ struct smx_ddpg_rollout {
     struct smx_episode_monitor mon;        /* mon.ep_reward NULL: none (stays the last member) */
 };
 typedef struct smx_ddpg_rollout smx_ddpg_rollout_t;
-/* shapes smx_synth_ddpg_rollout_f32 takes: A <= 32, H1 and H2 multiples of 4 up to 640, D <= 512 */
-int32_t smx_synth_ddpg_rollout_supported(int32_t D, int32_t H1, int32_t H2, int32_t A);
+
+/* What the actor of smx_synth_ddpg_rollout_f32 may be beyond the plain three layers; the two pointers switch
+ * independently, and a block with both NULL is the plain actor.
+ * ln: a LayerNorm behind each hidden ReLU (DDPGModel, use_layernorm):
+ *   h1 = LN1(relu(W1 x + b1)), h2 = LN2(relu(W2 h1 + b2)), mu = tanh(W3 h2 + b3)
+ * LN as smx_layernorm_forward_f32 (torch.nn.LayerNorm(F): biased variance, eps inside the square root, elementwise
+ * affine), in its summation order: given the same ReLU row, the normalised row has that function's bits, at every block
+ * size.  ln: ln1.W [H1] | ln1.b [H1] | ln2.W [H2] | ln2.b [H2], contiguous (the tail of DDPGModel's actor parameters), on
+ * 4 bytes (SMX_E_ALIGN); ln_eps > 0 (SMX_E_SHAPE).
+ * packed_pop: a population of perturbed actors (struct smx_param_noise below): args->n = agents * actors_per_agent
+ * actors, actors_per_agent a multiple of 4; the workgroup that owns actors [a0, a0 + block) runs the actor's layers
+ * (with ln: its LayerNorms too) from the copy of agent a0 / actors_per_agent in packed_pop [agents, packed_stride]
+ * (smx_param_noise_refresh_f32's layout for the same ln; packed_stride >= smx_param_noise_copy_floats(.., ln != NULL), a
+ * multiple of 4; 16-byte aligned), so the block size must divide actors_per_agent: args->actors_per_workgroup = 0
+ * takes the size the plain launch would if it divides, else the next smaller of 16 / 8 / 4 that does; a forced size
+ * that does not divide: SMX_E_SHAPE.  Everything else is the plain launch, bit for bit: an agent's actors see what a
+ * launch over them alone would with args->packed = its copy.
+ * measure_step: -1, or the step of the call (< args->steps) at which the workgroup that holds an agent's FIRST actor also
+ * evaluates the clean actor (args->net, args->packed, ln) on that actor's observation and stores
+ *   dist[p] = sqrt(sum_j ((double)(mu_j - clean_j))^2)      (fp64 sum, j ascending; mu, clean: the tanh outputs in fp32,
+ *                                                            before clip and noise: ddpg_agent.py:173-175, one action pair)
+ * Other steps and other workgroups do nothing for it; dist is written only by a call that measures.  Without packed_pop
+ * the fields from packed_stride on are not read. */
+struct smx_ddpg_actor_variant {            /* (by tag: no typedef) */
+    const float* ln;                       /* NULL: no LayerNorm */
+    float ln_eps;
+    int32_t reserved;
+    const float* packed_pop;               /* NULL: one actor for all */
+    int64_t packed_stride;
+    int32_t actors_per_agent, agents;
+    int32_t measure_step, reserved2;
+    double* dist;                          /* [agents] fp64 (measure_step >= 0) */
+};
+/* shapes smx_synth_ddpg_rollout_f32 takes: A <= 32, H1 and H2 multiples of 4 up to 640, D <= 512; ln != 0: those of
+ * them whose 16-actor layout still holds the 2 (H1 + H2) LayerNorm floats */
+int32_t smx_synth_ddpg_rollout_supported(int32_t D, int32_t H1, int32_t H2, int32_t A, int32_t ln);
 /* all `steps` steps in ONE launch, in the persistent kernel shape of smx_synth_rollout_f32: a workgroup owns
  * actors_per_workgroup = 4, 8 or 16 actors for the whole rollout (0: chosen as there; anything else: SMX_E_SHAPE), the
  * actor's layers run on v_mfma_f32_4x4x1 from `packed` at every block size (smx_rows4_mma.inc.h: mu equals
- * smx_epoch_forward_f32's to fp32 rounding of the layer sums; every block size gives the same bits) */
-int smx_synth_ddpg_rollout_f32(const smx_ddpg_rollout_t* args, smx_stream_t stream);
+ * smx_epoch_forward_f32's to fp32 rounding of the layer sums; every block size gives the same bits).  variant NULL: the
+ * plain actor.  Every argument check is made before anything is launched. */
+int smx_synth_ddpg_rollout_f32(const smx_ddpg_rollout_t* args, const struct smx_ddpg_actor_variant* variant,
+                               smx_stream_t stream);
+/* the block size the launch takes for a population of n actors (0: refused, SMX_E_SHAPE there); forced =
+ * args->actors_per_workgroup */
+int32_t smx_synth_ddpg_population_block(int32_t n, int32_t actors_per_agent, int32_t forced);
 /* ONE step (args->steps is ignored; eps [n, A]; the step's closing transitions go to the rows from args->cursor) given
  * the actor's output mu [n, A] (row stride ld_mu) from any forward pass */
 int smx_synth_ddpg_step_f32(const smx_ddpg_rollout_t* args, const float* mu, int64_t ld_mu, smx_stream_t stream);
@@ -1254,7 +1293,9 @@ int smx_synth_ddpg_step_f32(const smx_ddpg_rollout_t* args, const float* mu, int
  *       through the word -> normal conversion of struct smx_noise_stream (the same inline function; the fixed fourth
  *       counter word keeps these blocks apart from the exploration stream's, whose fourth word is j >> 2 < 16)
  *   perturbed_i = w_i + (float)sigma[p] * z            in fp32, the product first; the build does not contract
- * `net` is read, never written.  g and q must lie in [0, 2^32) (SMX_E_SHAPE). */
+ * `net` is read, never written.  g and q must lie in [0, 2^32) (SMX_E_SHAPE).
+ * A LayerNorm actor (ln: the clean ln1.W | ln1.b | ln2.W | ln2.b): the flat parameters go on with those four (element
+ * indices i behind b3's: the first six arrays keep theirs, so they are perturbed as without a LayerNorm), the same rule. */
 struct smx_param_noise {                   /* (by tag: no typedef) */
     const smx_mlp3_t* net;                 /* the clean actor */
     uint64_t seed;
@@ -1267,83 +1308,23 @@ struct smx_param_noise {                   /* (by tag: no typedef) */
     double* sigma;                         /* [P] fp64, in / out */
     const double* dist;                    /* [P] fp64: the action distances (refresh, adaptive and acts > 0) */
     float* packed_pop;                     /* refresh: [P, packed_stride] out, 16-byte aligned */
-    int64_t packed_stride;                 /* floats, >= smx_param_noise_copy_floats(..), a multiple of 4 */
+    int64_t packed_stride;                 /* floats, >= smx_param_noise_copy_floats(.., ln != NULL), a multiple of 4 */
+    const float* ln;                       /* NULL: a plain actor */
 };
-/* floats of one agent's copy: [smx_epoch_pack_f32's layout of the actor | b1 | b2 | b3], rounded up to 64 */
-int64_t smx_param_noise_copy_floats(int32_t D, int32_t H1, int32_t H2, int32_t OUT);
-/* out [H1 D + H1 + H2 H1 + H2 + OUT H2 + OUT] <- agent p's perturbed flat parameters (packed_pop, dist, acts: not read) */
+/* floats of one agent's copy: [smx_epoch_pack_f32's layout of the actor | b1 | b2 | b3], with ln != 0 [| ln1.W | ln1.b |
+ * ln2.W | ln2.b], rounded up to 64 */
+int64_t smx_param_noise_copy_floats(int32_t D, int32_t H1, int32_t H2, int32_t OUT, int32_t ln);
+/* out [H1 D + H1 + H2 H1 + H2 + OUT H2 + OUT (+ 2 (H1 + H2) with ln)] <- agent p's perturbed flat parameters (packed_pop,
+ * dist, acts: not read) */
 int smx_param_noise_fill_f32(const struct smx_param_noise* pn, int32_t p, float* out, smx_stream_t stream);
 /* AdaptiveNormalParameterNoise.apply / NormalParameterNoise.apply for all P agents, no host synchronisation, at most two
  * launches: with adaptive != 0 and acts > 0 first, in a launch of its own,
  *   sigma[p] <- dist[p] / acts > target ? sigma[p] / alpha : sigma[p] * alpha      (fp64; param_noise.py:65-70)
  * then the copy of every agent's perturbed actor into packed_pop + p * packed_stride: the five blocks of
  * smx_epoch_pack_f32 bit for bit as it lays out a net holding the perturbed parameters (its padding exactly zero: noise
- * goes to logical elements only), the perturbed biases b1 | b2 | b3 behind them, zeros up to copy_floats. */
+ * goes to logical elements only), the perturbed biases b1 | b2 | b3 behind them, with ln the perturbed four behind the
+ * biases, zeros up to copy_floats. */
 int smx_param_noise_refresh_f32(const struct smx_param_noise* pn, smx_stream_t stream);
-
-/* smx_synth_ddpg_rollout_f32 on a population: base.n = agents * actors_per_agent actors, actors_per_agent a multiple of
- * 4; the workgroup that owns actors [a0, a0 + block) runs the actor's layers from the copy of agent a0 /
- * actors_per_agent in packed_pop (smx_param_noise_refresh_f32's layout, biases included), so the block size must divide
- * actors_per_agent: base.actors_per_workgroup = 0 takes the size smx_synth_ddpg_rollout_f32 would if it divides, else
- * the next smaller of 16 / 8 / 4 that does; a forced size that does not divide: SMX_E_SHAPE.  Everything else is that
- * launch, bit for bit: an agent's actors see what a launch over them alone would with base.packed = its copy.
- * measure_step: -1, or the step of the call (< base.steps) at which the workgroup that holds an agent's FIRST actor also
- * evaluates the clean actor (base.net, base.packed) on that actor's observation and stores
- *   dist[p] = sqrt(sum_j ((double)(mu_j - clean_j))^2)      (fp64 sum, j ascending; mu, clean: the tanh outputs in fp32,
- *                                                            before clip and noise: ddpg_agent.py:173-175, one action pair)
- * Other steps and other workgroups do nothing for it; dist is written only by a call that measures. */
-struct smx_ddpg_population_rollout {       /* (by tag: no typedef) */
-    smx_ddpg_rollout_t base;
-    const float* packed_pop;               /* [agents, packed_stride] */
-    int64_t packed_stride;
-    int32_t actors_per_agent, agents;
-    int32_t measure_step, reserved;
-    double* dist;                          /* [agents] fp64 (measure_step >= 0) */
-};
-/* the block size the launch takes for n actors (0: refused, SMX_E_SHAPE there); forced = base.actors_per_workgroup */
-int32_t smx_synth_ddpg_population_block(int32_t n, int32_t actors_per_agent, int32_t forced);
-int smx_synth_ddpg_population_rollout_f32(const struct smx_ddpg_population_rollout* args, smx_stream_t stream);
-
-/* The one-launch rollouts for an actor with a LayerNorm behind each hidden ReLU (DDPGModel, use_layernorm):
- *   h1 = LN1(relu(W1 x + b1)), h2 = LN2(relu(W2 h1 + b2)), mu = tanh(W3 h2 + b3)
- * LN as smx_layernorm_forward_f32 (torch.nn.LayerNorm(F): biased variance, eps inside the square root, elementwise
- * affine), in its summation order: given the same ReLU row, the normalised row has that function's bits, at every block
- * size.  ln: ln1.W [H1] | ln1.b [H1] | ln2.W [H2] | ln2.b [H2], contiguous (the tail of DDPGModel's actor parameters);
- * eps > 0.  Everything else is smx_synth_ddpg_rollout_f32 on `base`. */
-struct smx_ddpg_ln_rollout {               /* (by tag: no typedef) */
-    smx_ddpg_rollout_t base;
-    const float* ln;
-    float eps;
-    int32_t reserved;
-};
-/* shapes smx_synth_ddpg_ln_rollout_f32 takes: those of smx_synth_ddpg_rollout_supported whose 16-actor layout still
- * holds the 2 (H1 + H2) LayerNorm floats */
-int32_t smx_synth_ddpg_ln_rollout_supported(int32_t D, int32_t H1, int32_t H2, int32_t A);
-int smx_synth_ddpg_ln_rollout_f32(const struct smx_ddpg_ln_rollout* args, smx_stream_t stream);
-
-/* Parameter-space noise over a LayerNorm actor: the flat parameters of struct smx_param_noise go on with ln1.W | ln1.b |
- * ln2.W | ln2.b (element indices i behind b3's: the first six arrays keep theirs, so they are perturbed as without a
- * LayerNorm), the same rule.  An agent's copy: smx_param_noise_refresh_f32's, the perturbed four behind the biases, zeros
- * up to smx_param_noise_ln_copy_floats (a multiple of 64); base.packed_stride >= that. */
-struct smx_param_noise_ln {                /* (by tag: no typedef) */
-    struct smx_param_noise base;
-    const float* ln;                       /* the clean ln1.W | ln1.b | ln2.W | ln2.b */
-};
-int64_t smx_param_noise_ln_copy_floats(int32_t D, int32_t H1, int32_t H2, int32_t OUT);
-/* out [.. + OUT + 2 (H1 + H2)] <- agent p's perturbed flat parameters */
-int smx_param_noise_ln_fill_f32(const struct smx_param_noise_ln* pn, int32_t p, float* out, smx_stream_t stream);
-int smx_param_noise_ln_refresh_f32(const struct smx_param_noise_ln* pn, smx_stream_t stream);
-
-/* smx_synth_ddpg_population_rollout_f32 for a LayerNorm actor: pop.packed_pop holds smx_param_noise_ln_refresh_f32's
- * copies, every agent's layers and LayerNorms run from its copy; the clean actor of the measuring step is pop.base.net,
- * pop.base.packed and ln. */
-struct smx_ddpg_ln_population_rollout {    /* (by tag: no typedef) */
-    struct smx_ddpg_population_rollout pop;
-    const float* ln;
-    float eps;
-    int32_t reserved;
-};
-int smx_synth_ddpg_ln_population_rollout_f32(const struct smx_ddpg_ln_population_rollout* args, smx_stream_t stream);
 
 /* The same step for actors with a camera (the reference's pixel DDPG configurations, ddpg_configs.py:176-228:
  * FrameStackWrapper in front of a CNN perception): smx_synth_ddpg_step_f32 on args->base (mu [n, A] = the actor's

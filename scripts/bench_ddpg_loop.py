@@ -104,7 +104,7 @@ def main():
     for path in ('persistent', 'per_step'):
         replay = UniformReplay(lc, ec, sc)
         if path == 'per_step':              # the per-step path: what a LayerNorm actor or an unsupported shape takes
-            venv.K.synth_ddpg_rollout_supported = venv.K.synth_ddpg_ln_rollout_supported = lambda net: False
+            venv.K.synth_ddpg_rollout_supported = lambda net, ln=False: False
         try:
             venv.reset()
             venv.ddpg_rollout_into(agent, replay, T, eps=eps)           # warm-up (tables, packed copy, code)
@@ -120,7 +120,7 @@ def main():
             dev = e0.elapsed_time(e1) / 1e3 / args.reps
         finally:
             if path == 'per_step':
-                del venv.K.synth_ddpg_rollout_supported, venv.K.synth_ddpg_ln_rollout_supported
+                del venv.K.synth_ddpg_rollout_supported
         r = {'what': 'ddpg_rollout', 'path': path, 'actors': n, 'steps': T, 'shape': [D, H1, H2, A],
              'ms_per_rollout': round(dev * 1e3, 4), 'wall_ms_per_rollout': round(wall * 1e3, 4),
              'env_steps_per_s': n * T / dev, 'actor_tflops': flops / dev / 1e12,

@@ -196,33 +196,19 @@ class DdpgRollout(Structure):
                 ('cursor', c_int64), ('capacity', c_int64), ('noise', NoiseStream), ('mon', EpisodeMonitor)]
 
 
+class DdpgActorVariant(Structure):
+    """struct smx_ddpg_actor_variant"""
+    _fields_ = [('ln', c_void_p), ('ln_eps', c_float), ('reserved', c_int32), ('packed_pop', c_void_p),
+                ('packed_stride', c_int64), ('actors_per_agent', c_int32), ('agents', c_int32),
+                ('measure_step', c_int32), ('reserved2', c_int32), ('dist', c_void_p)]
+
+
 class ParamNoise(Structure):
     """struct smx_param_noise"""
     _fields_ = [('net', POINTER(Mlp3)), ('seed', c_uint64), ('agent_base', c_int64), ('generation', c_int64),
                 ('agents', c_int32), ('adaptive', c_int32), ('acts', c_int64), ('alpha', c_double), ('target', c_double),
-                ('sigma', c_void_p), ('dist', c_void_p), ('packed_pop', c_void_p), ('packed_stride', c_int64)]
-
-
-class DdpgPopulationRollout(Structure):
-    """struct smx_ddpg_population_rollout"""
-    _fields_ = [('base', DdpgRollout), ('packed_pop', c_void_p), ('packed_stride', c_int64),
-                ('actors_per_agent', c_int32), ('agents', c_int32), ('measure_step', c_int32), ('reserved', c_int32),
-                ('dist', c_void_p)]
-
-
-class DdpgLnRollout(Structure):
-    """struct smx_ddpg_ln_rollout"""
-    _fields_ = [('base', DdpgRollout), ('ln', c_void_p), ('eps', c_float), ('reserved', c_int32)]
-
-
-class ParamNoiseLn(Structure):
-    """struct smx_param_noise_ln"""
-    _fields_ = [('base', ParamNoise), ('ln', c_void_p)]
-
-
-class DdpgLnPopulationRollout(Structure):
-    """struct smx_ddpg_ln_population_rollout"""
-    _fields_ = [('pop', DdpgPopulationRollout), ('ln', c_void_p), ('eps', c_float), ('reserved', c_int32)]
+                ('sigma', c_void_p), ('dist', c_void_p), ('packed_pop', c_void_p), ('packed_stride', c_int64),
+                ('ln', c_void_p)]
 
 
 class DdpgPixelStep(Structure):
@@ -429,21 +415,14 @@ _SIGS = {
     'smx_synth_lstm_rollout_f32': (c_int32, [POINTER(SynthLstmRollout), _P]),
     'smx_synth_ppo_window_rollout_supported': (c_int32, [c_int32] * 5),
     'smx_synth_ppo_window_rollout_f32': (c_int32, [POINTER(SynthPpoWindowRollout), _P]),
-    'smx_synth_ddpg_rollout_supported': (c_int32, [c_int32, c_int32, c_int32, c_int32]),
-    'smx_synth_ddpg_rollout_f32': (c_int32, [POINTER(DdpgRollout), _P]),
+    'smx_synth_ddpg_rollout_supported': (c_int32, [c_int32, c_int32, c_int32, c_int32, c_int32]),
+    'smx_synth_ddpg_rollout_f32': (c_int32, [POINTER(DdpgRollout), POINTER(DdpgActorVariant), _P]),
+    'smx_synth_ddpg_population_block': (c_int32, [c_int32, c_int32, c_int32]),
     'smx_synth_ddpg_step_f32': (c_int32, [POINTER(DdpgRollout), _P, c_int64, _P]),
     'smx_synth_ddpg_pixel_step': (c_int32, [POINTER(DdpgPixelStep), _P, c_int64, _P]),
-    'smx_param_noise_copy_floats': (c_int64, [c_int32, c_int32, c_int32, c_int32]),
+    'smx_param_noise_copy_floats': (c_int64, [c_int32, c_int32, c_int32, c_int32, c_int32]),
     'smx_param_noise_fill_f32': (c_int32, [POINTER(ParamNoise), c_int32, _P, _P]),
     'smx_param_noise_refresh_f32': (c_int32, [POINTER(ParamNoise), _P]),
-    'smx_synth_ddpg_population_block': (c_int32, [c_int32, c_int32, c_int32]),
-    'smx_synth_ddpg_population_rollout_f32': (c_int32, [POINTER(DdpgPopulationRollout), _P]),
-    'smx_synth_ddpg_ln_rollout_supported': (c_int32, [c_int32, c_int32, c_int32, c_int32]),
-    'smx_synth_ddpg_ln_rollout_f32': (c_int32, [POINTER(DdpgLnRollout), _P]),
-    'smx_param_noise_ln_copy_floats': (c_int64, [c_int32, c_int32, c_int32, c_int32]),
-    'smx_param_noise_ln_fill_f32': (c_int32, [POINTER(ParamNoiseLn), c_int32, _P, _P]),
-    'smx_param_noise_ln_refresh_f32': (c_int32, [POINTER(ParamNoiseLn), _P]),
-    'smx_synth_ddpg_ln_population_rollout_f32': (c_int32, [POINTER(DdpgLnPopulationRollout), _P]),
     'smx_synth_ppo_pixel_window_step': (c_int32, [POINTER(SynthPpoPixelWindowStep), _P, c_int64, _P]),
     'smx_xchg_bytes': (c_int64, [c_int64, c_int32]),
     'smx_xchg_alloc': (c_int32, [c_int64, c_double, POINTER(c_void_p), POINTER(c_int32), _P]),

@@ -58,7 +58,7 @@ __host__ __device__ inline long pop_bias_off(int D, int H1, int H2, int OUT) { r
 __host__ __device__ inline long pop_copy_floats(int D, int H1, int H2, int OUT) {
     return (pop_bias_off(D, H1, H2, OUT) + H1 + H2 + OUT + 63) & ~63L;
 }
-// The copy of a LayerNorm actor (smx_param_noise_ln_refresh_f32): [the net's copy | b1 | b2 | b3 | ln1.W | ln1.b | ln2.W |
+// The copy of a LayerNorm actor (smx_param_noise_refresh_f32 with ln): [the net's copy | b1 | b2 | b3 | ln1.W | ln1.b | ln2.W |
 // ln2.b], rounded up to 64 floats
 __host__ __device__ inline long pop_ln_off(int D, int H1, int H2, int OUT) { return pop_bias_off(D, H1, H2, OUT) + H1 + H2 + OUT; }
 __host__ __device__ inline long pop_ln_copy_floats(int D, int H1, int H2, int OUT) {

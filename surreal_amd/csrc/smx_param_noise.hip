@@ -16,11 +16,10 @@
 //                                perturbed weights | b1 | b2 | b3] (smx_epoch_pack.inc.h, pop_copy_floats) into
 //                                packed_pop + p * packed_stride.  Noise goes to logical elements only: the layout's
 //                                padding is written as zeros.
-//   smx_param_noise_ln_fill_f32 / smx_param_noise_ln_refresh_f32   the same for a LayerNorm actor: the flat parameters go
-//                                on with ln1.W [H1] | ln1.b [H1] | ln2.W [H2] | ln2.b [H2] (DDPGModel's order), perturbed
-//                                by the same rule under their own indices i, and an agent's copy with the perturbed
-//                                four behind its biases (pop_ln_copy_floats).  The indices of the first six arrays are
-//                                what they are without a LayerNorm.
+//   A LayerNorm actor (pn->ln): the flat parameters go on with ln1.W [H1] | ln1.b [H1] | ln2.W [H2] | ln2.b [H2]
+//                                (DDPGModel's order), perturbed by the same rule under their own indices i, and an
+//                                agent's copy carries the perturbed four behind its biases (pop_ln_copy_floats).  The
+//                                indices of the first six arrays are what they are without a LayerNorm.
 #include "smx_common.h"
 
 namespace {
@@ -114,18 +113,18 @@ __global__ __launch_bounds__(256) void param_noise_pack_kernel(PNArgs P) {
     *(float4*)(P.pop + (size_t)p * P.stride + 4 * w) = make_float4(v[0], v[1], v[2], v[3]);
 }
 
-// what every entry point asks of the block and takes from it; ln: the LayerNorm block of the clean actor or null
-int fill_args(const struct smx_param_noise* a, const float* ln, PNArgs& P) {
+// what every entry point asks of the block and takes from it
+int fill_args(const struct smx_param_noise* a, PNArgs& P) {
     SMX_REQUIRE(a && a->net && a->sigma, SMX_E_NULL);
     const smx_mlp3_t& n = *a->net;
     SMX_REQUIRE(n.W1 && n.b1 && n.W2 && n.b2 && n.W3 && n.b3, SMX_E_NULL);
     SMX_REQUIRE(n.D > 0 && n.H1 > 0 && n.H2 > 0 && n.OUT > 0 && a->agents > 0, SMX_E_SHAPE);
     SMX_REQUIRE((long long)n.H1 * n.D + (long long)n.H2 * n.H1 + (long long)n.OUT * n.H2 + n.H1 + n.H2 + n.OUT +
-                    (ln ? 2LL * (n.H1 + n.H2) : 0) < (1LL << 31), SMX_E_SHAPE);
+                    (a->ln ? 2LL * (n.H1 + n.H2) : 0) < (1LL << 31), SMX_E_SHAPE);
     // every global agent id and the generation in [0, 2^32): one counter word each
     SMX_REQUIRE(a->agent_base >= 0 && a->agent_base + a->agents <= (1LL << 32), SMX_E_SHAPE);
     SMX_REQUIRE(a->generation >= 0 && a->generation < (1LL << 32), SMX_E_SHAPE);
-    P.ln = ln;
+    P.ln = a->ln;
     P.W1 = n.W1; P.b1 = n.b1; P.W2 = n.W2; P.b2 = n.b2; P.W3 = n.W3; P.b3 = n.b3;
     P.D = n.D; P.H1 = n.H1; P.H2 = n.H2; P.A = n.OUT;
     P.seed = a->seed; P.g0 = (uint32_t)a->agent_base; P.q = (uint32_t)a->generation;
@@ -135,15 +134,14 @@ int fill_args(const struct smx_param_noise* a, const float* ln, PNArgs& P) {
 
 }  // namespace
 
-extern "C" int64_t smx_param_noise_copy_floats(int32_t D, int32_t H1, int32_t H2, int32_t A) {
+extern "C" int64_t smx_param_noise_copy_floats(int32_t D, int32_t H1, int32_t H2, int32_t A, int32_t ln) {
     if (D <= 0 || H1 <= 0 || H2 <= 0 || A <= 0) return 0;
-    return pop_copy_floats(D, H1, H2, A);
+    return ln ? pop_ln_copy_floats(D, H1, H2, A) : pop_copy_floats(D, H1, H2, A);
 }
 
-// fill and refresh of either form (ln null: the plain actor's)
-static int fill(const struct smx_param_noise* a, const float* ln, int32_t p, float* out, smx_stream_t stream) {
+extern "C" int smx_param_noise_fill_f32(const struct smx_param_noise* a, int32_t p, float* out, smx_stream_t stream) {
     PNArgs P;
-    const int rc = fill_args(a, ln, P);
+    const int rc = fill_args(a, P);
     if (rc != SMX_OK) return rc;
     SMX_REQUIRE(out, SMX_E_NULL);
     SMX_REQUIRE(p >= 0 && p < a->agents, SMX_E_SHAPE);
@@ -153,13 +151,13 @@ static int fill(const struct smx_param_noise* a, const float* ln, int32_t p, flo
     return SMX_OK;
 }
 
-static int refresh(const struct smx_param_noise* a, const float* ln, smx_stream_t stream) {
+extern "C" int smx_param_noise_refresh_f32(const struct smx_param_noise* a, smx_stream_t stream) {
     PNArgs P;
-    const int rc = fill_args(a, ln, P);
+    const int rc = fill_args(a, P);
     if (rc != SMX_OK) return rc;
     SMX_REQUIRE(a->packed_pop, SMX_E_NULL);
     SMX_REQUIRE(a->agents <= 65535 && a->acts >= 0, SMX_E_SHAPE);
-    const long copy = ln ? pop_ln_copy_floats(P.D, P.H1, P.H2, P.A) : pop_copy_floats(P.D, P.H1, P.H2, P.A);
+    const long copy = smx_param_noise_copy_floats(P.D, P.H1, P.H2, P.A, a->ln != nullptr);
     SMX_REQUIRE(a->packed_stride >= copy && a->packed_stride % 4 == 0, SMX_E_SHAPE);
     SMX_REQUIRE(((uintptr_t)a->packed_pop & 15) == 0, SMX_E_ALIGN);
     if (a->adaptive && a->acts > 0) {
@@ -173,27 +171,4 @@ static int refresh(const struct smx_param_noise* a, const float* ln, smx_stream_
                        smx_s(stream), P);
     SMX_LAUNCH_CHECK();
     return SMX_OK;
-}
-
-extern "C" int smx_param_noise_fill_f32(const struct smx_param_noise* a, int32_t p, float* out, smx_stream_t stream) {
-    return fill(a, nullptr, p, out, stream);
-}
-
-extern "C" int smx_param_noise_refresh_f32(const struct smx_param_noise* a, smx_stream_t stream) {
-    return refresh(a, nullptr, stream);
-}
-
-extern "C" int64_t smx_param_noise_ln_copy_floats(int32_t D, int32_t H1, int32_t H2, int32_t A) {
-    if (D <= 0 || H1 <= 0 || H2 <= 0 || A <= 0) return 0;
-    return pop_ln_copy_floats(D, H1, H2, A);
-}
-
-extern "C" int smx_param_noise_ln_fill_f32(const struct smx_param_noise_ln* a, int32_t p, float* out, smx_stream_t stream) {
-    SMX_REQUIRE(a && a->ln, SMX_E_NULL);
-    return fill(&a->base, a->ln, p, out, stream);
-}
-
-extern "C" int smx_param_noise_ln_refresh_f32(const struct smx_param_noise_ln* a, smx_stream_t stream) {
-    SMX_REQUIRE(a && a->ln, SMX_E_NULL);
-    return refresh(&a->base, a->ln, stream);
 }

@@ -19,12 +19,12 @@
 //                               surreal/env/exp_sender_wrapper.py:72-112 ExpSenderWrapperSSARNStepBootstrap, which run on
 //                               the host there) recorded straight into the uniform replay's ring: ddpg_rollout_kernel on
 //                               the 4-row loop at every block size.
-//   smx_synth_ddpg_population_rollout_f32   the same launch over a population of perturbed actors (parameter-space
-//                               noise, smx_param_noise.hip): ddpg_rollout_kernel<RG, NT, true>, each workgroup's layers run
-//                               from the copy of the agent its actors belong to; one step of the call can measure the
-//                               agents' action distance against the clean actor.
-//   smx_synth_ddpg_ln_rollout_f32 / smx_synth_ddpg_ln_population_rollout_f32   both for an actor with a LayerNorm behind
-//                               each hidden ReLU: ddpg_rollout_kernel<RG, NT, POP, true>, ln_rows over the hidden tiles
+//                               With a struct smx_ddpg_actor_variant the same launch runs over a population of
+//                               perturbed actors (packed_pop; parameter-space noise, smx_param_noise.hip):
+//                               ddpg_rollout_kernel<RG, NT, true>, each workgroup's layers run from the copy of the agent
+//                               its actors belong to, and one step of the call can measure the agents' action distance
+//                               against the clean actor; and for an actor with a LayerNorm behind each hidden ReLU (ln):
+//                               ddpg_rollout_kernel<RG, NT, POP, true>, ln_rows over the hidden tiles.
 //   smx_synth_ddpg_step_f32     one DDPG step for all actors given the actor's output mu [n, A] from any forward
 //                               (LayerNorm actors, unsupported shapes; with smx_epoch_forward_f32 the persistent kernel's
 //                               two-launch reference).
@@ -986,11 +986,11 @@ __device__ __forceinline__ void ln_rows(float* tile, int ld, int F, const float*
 
 // RG row groups of four actors per workgroup; NT feature tiles a wave carries per pass.  Every block size gives the same
 // bits (layers4).
-// POP (smx_synth_ddpg_population_rollout_f32; 4 RG divides the actors per agent): the same body with the layers run from
+// POP (variant->packed_pop; 4 RG divides the actors per agent): the same body with the layers run from
 // the agent's copy.  At step measure_step the workgroups that hold an agent's first actor (a workgroup-uniform branch:
 // layers4 has barriers) first run the clean actor -- G's own -- on the same x tile and keep that actor's outputs, then
 // store the L2 distance of the two outputs of that one actor.
-// LN (smx_synth_ddpg_ln_rollout_f32, smx_synth_ddpg_ln_population_rollout_f32): the same body with ln_rows behind the
+// LN (variant->ln): the same body with ln_rows behind the
 // barrier of each hidden layer and a barrier of its own behind it.  The gains and biases the workgroup's layers use --
 // the clean actor's, or (POP) its agent's perturbed ones -- are copied to LDS once; the clean actor of a measuring step
 // reads its own from memory.
@@ -1901,15 +1901,25 @@ extern "C" int smx_synth_ppo_window_rollout_f32(const smx_synth_ppo_window_rollo
     return launch<lstm_window_kernel<1>, lstm_window_kernel<2>, lstm_window_kernel<4>>(G, rb, lds, stream);
 }
 
-extern "C" int32_t smx_synth_ddpg_rollout_supported(int32_t D, int32_t H1, int32_t H2, int32_t A) {
-    return supported(D, H1, H2, A, /*mma16=*/false, /*split_out=*/false, /*ztables=*/false);
+extern "C" int32_t smx_synth_ddpg_rollout_supported(int32_t D, int32_t H1, int32_t H2, int32_t A, int32_t ln) {
+    if (!supported(D, H1, H2, A, /*mma16=*/false, /*split_out=*/false, /*ztables=*/false)) return 0;
+    if (!ln) return 1;
+    DLnArgs G;
+    memset(&G, 0, sizeof(G));
+    G.D = D; G.H1 = H1; G.H2 = H2; G.A = A;
+    return carve_ln(G, G.ln, carve(G, 16, /*mma16=*/false, /*split_out=*/false, /*ztables=*/false, D)) <= ROLL_MAX_LDS;
 }
 
-// what both persistent DDPG entry points ask of the block and take from it (the block size and the launch are theirs)
+extern "C" int32_t smx_synth_ddpg_population_block(int32_t n, int32_t actors_per_agent, int32_t forced) {
+    if (n <= 0 || actors_per_agent <= 0 || actors_per_agent % 4 || !block_ok(forced)) return 0;
+    return pick_population_block(forced, n, actors_per_agent);
+}
+
+// what the persistent DDPG launch asks of the block and takes from it, whatever the actor
 static int persistent_ddpg_args(const smx_ddpg_rollout_t* a, DArgs& G) {
     SMX_REQUIRE(a && a->net && a->packed, SMX_E_NULL);
     const smx_mlp3_t& net = *a->net;
-    SMX_REQUIRE(smx_synth_ddpg_rollout_supported(net.D, net.H1, net.H2, net.OUT), SMX_E_UNSUPPORTED);
+    SMX_REQUIRE(smx_synth_ddpg_rollout_supported(net.D, net.H1, net.H2, net.OUT, 0), SMX_E_UNSUPPORTED);
     SMX_REQUIRE(net.D == a->D && net.OUT == a->A && a->steps > 0, SMX_E_SHAPE);
     SMX_REQUIRE(block_ok(a->actors_per_workgroup), SMX_E_SHAPE);
     SMX_REQUIRE(aligned_ok(a->packed, net.b1, nullptr), SMX_E_ALIGN);
@@ -1922,112 +1932,71 @@ static int persistent_ddpg_args(const smx_ddpg_rollout_t* a, DArgs& G) {
     return SMX_OK;
 }
 
-extern "C" int smx_synth_ddpg_rollout_f32(const smx_ddpg_rollout_t* a, smx_stream_t stream) {
-    DArgs G;
-    const int rc = persistent_ddpg_args(a, G);
-    if (rc != SMX_OK) return rc;
-    const int rb = pick_block(a->actors_per_workgroup, a->n);
-    const int lds = carve(G, rb, /*mma16=*/false, /*split_out=*/false, /*ztables=*/false, G.D);
-    return launch<ddpg_rollout_kernel<1, 3>, ddpg_rollout_kernel<2, 3>, ddpg_rollout_kernel<4, 2>>(G, rb, lds, stream);
-}
-
-extern "C" int32_t smx_synth_ddpg_ln_rollout_supported(int32_t D, int32_t H1, int32_t H2, int32_t A) {
-    if (!smx_synth_ddpg_rollout_supported(D, H1, H2, A)) return 0;
-    DLnArgs G;
-    memset(&G, 0, sizeof(G));
-    G.D = D; G.H1 = H1; G.H2 = H2; G.A = A;
-    return carve_ln(G, G.ln, carve(G, 16, /*mma16=*/false, /*split_out=*/false, /*ztables=*/false, D)) <= ROLL_MAX_LDS;
-}
-
-// what both LayerNorm entry points ask of the gains and biases
-static int ln_args(const smx_mlp3_t& net, const float* ln, float eps, LnTail& T) {
-    SMX_REQUIRE(ln, SMX_E_NULL);
-    SMX_REQUIRE(smx_synth_ddpg_ln_rollout_supported(net.D, net.H1, net.H2, net.OUT), SMX_E_UNSUPPORTED);
-    SMX_REQUIRE(eps > 0.f, SMX_E_SHAPE);
-    SMX_REQUIRE(((uintptr_t)ln & 3) == 0, SMX_E_ALIGN);
-    T.g = ln; T.eps = eps;
+// what a population asks of the variant and takes from it (-> the block size `rb`); copy_floats: what one agent's copy
+// holds
+static int population_args(const smx_ddpg_rollout_t* a, const smx_ddpg_actor_variant& v, long copy_floats, PopArgs& G,
+                           int& rb) {
+    const int apa = v.actors_per_agent;
+    SMX_REQUIRE(apa > 0 && apa % 4 == 0 && v.agents > 0 && (long long)v.agents * apa == a->n, SMX_E_SHAPE);
+    SMX_REQUIRE(v.measure_step >= -1 && v.measure_step < a->steps, SMX_E_SHAPE);
+    SMX_REQUIRE(v.measure_step < 0 || v.dist, SMX_E_NULL);
+    SMX_REQUIRE(v.packed_stride >= copy_floats && v.packed_stride % 4 == 0, SMX_E_SHAPE);
+    SMX_REQUIRE(((uintptr_t)v.packed_pop & 15) == 0, SMX_E_ALIGN);
+    rb = pick_population_block(a->actors_per_workgroup, a->n, apa);
+    SMX_REQUIRE(rb > 0, SMX_E_SHAPE);
+    G.stride = v.packed_stride; G.apa = apa; G.measure_step = v.measure_step; G.dist = v.dist;
     return SMX_OK;
 }
 
-extern "C" int smx_synth_ddpg_ln_rollout_f32(const struct smx_ddpg_ln_rollout* args, smx_stream_t stream) {
-    SMX_REQUIRE(args, SMX_E_NULL);
-    const smx_ddpg_rollout_t* a = &args->base;
-    DLnArgs G;
+// what a LayerNorm asks of the gains and biases
+static int ln_args(const smx_mlp3_t& net, const smx_ddpg_actor_variant& v, LnTail& T) {
+    SMX_REQUIRE(smx_synth_ddpg_rollout_supported(net.D, net.H1, net.H2, net.OUT, 1), SMX_E_UNSUPPORTED);
+    SMX_REQUIRE(v.ln_eps > 0.f, SMX_E_SHAPE);
+    SMX_REQUIRE(((uintptr_t)v.ln & 3) == 0, SMX_E_ALIGN);
+    T.g = v.ln; T.eps = v.ln_eps;
+    return SMX_OK;
+}
+
+// the launch for one of the four actors: the block's checks, then the population's, then the LayerNorm's
+template <bool POP, bool LN>
+static int ddpg_rollout(const smx_ddpg_rollout_t* a, const smx_ddpg_actor_variant& v, smx_stream_t stream) {
+    DdpgArgs<POP, LN> G;
     memset(&G, 0, sizeof(G));
     int rc = persistent_ddpg_args(a, G);
     if (rc != SMX_OK) return rc;
-    LnTail T = {};
-    rc = ln_args(*a->net, args->ln, args->eps, T);
-    if (rc != SMX_OK) return rc;
-    G.ln = T;
-    const int rb = pick_block(a->actors_per_workgroup, a->n);
-    const int lds = carve_ln(G, G.ln, carve(G, rb, /*mma16=*/false, /*split_out=*/false, /*ztables=*/false, G.D));
-    return launch<ddpg_rollout_kernel<1, 3, false, true>, ddpg_rollout_kernel<2, 3, false, true>,
-                  ddpg_rollout_kernel<4, 2, false, true>>(G, rb, lds, stream);
-}
-
-extern "C" int32_t smx_synth_ddpg_population_block(int32_t n, int32_t actors_per_agent, int32_t forced) {
-    if (n <= 0 || actors_per_agent <= 0 || actors_per_agent % 4 || !block_ok(forced)) return 0;
-    return pick_population_block(forced, n, actors_per_agent);
-}
-
-// what both population entry points ask of the block and take from it: the block size `rb`, the LDS layout (-> its
-// bytes in `lds`), agent 0's copy as popnet; copy_floats: what one agent's copy holds
-static int population_args(const struct smx_ddpg_population_rollout* args, long copy_floats, PopArgs& G, int& rb, int& lds) {
-    SMX_REQUIRE(args && args->packed_pop, SMX_E_NULL);
-    const smx_ddpg_rollout_t* a = &args->base;
-    const int rc = persistent_ddpg_args(a, G);
-    if (rc != SMX_OK) return rc;
     const smx_mlp3_t& net = *a->net;
-    const int apa = args->actors_per_agent;
-    SMX_REQUIRE(apa > 0 && apa % 4 == 0 && args->agents > 0 && (long long)args->agents * apa == a->n, SMX_E_SHAPE);
-    SMX_REQUIRE(args->measure_step >= -1 && args->measure_step < a->steps, SMX_E_SHAPE);
-    SMX_REQUIRE(args->measure_step < 0 || args->dist, SMX_E_NULL);
-    SMX_REQUIRE(args->packed_stride >= copy_floats && args->packed_stride % 4 == 0, SMX_E_SHAPE);
-    SMX_REQUIRE(((uintptr_t)args->packed_pop & 15) == 0, SMX_E_ALIGN);
-    rb = pick_population_block(a->actors_per_workgroup, a->n, apa);
-    SMX_REQUIRE(rb > 0, SMX_E_SHAPE);
-    G.stride = args->packed_stride; G.apa = apa; G.measure_step = args->measure_step; G.dist = args->dist;
-    lds = carve(G, rb, /*mma16=*/false, /*split_out=*/false, /*ztables=*/false, G.D);
-    // agent 0's copy in the same tiles: its packed blocks as net_fields lays a net's out, its biases behind them
-    G.popnet = G;
-    smx_mlp3_t copy0 = net;
-    copy0.b1 = args->packed_pop + pop_bias_off(net.D, net.H1, net.H2, net.OUT);
-    copy0.b2 = copy0.b1 + net.H1;
-    copy0.b3 = copy0.b2 + net.H2;
-    net_fields(copy0, args->packed_pop, G.popnet);
-    return SMX_OK;
+    int rb = POP ? 0 : pick_block(a->actors_per_workgroup, a->n);
+    if constexpr (POP) {
+        rc = population_args(a, v, LN ? pop_ln_copy_floats(net.D, net.H1, net.H2, net.OUT)
+                                      : pop_copy_floats(net.D, net.H1, net.H2, net.OUT), G, rb);
+        if (rc != SMX_OK) return rc;
+    }
+    if constexpr (LN) {
+        rc = ln_args(net, v, G.ln);
+        if (rc != SMX_OK) return rc;
+        if constexpr (POP) G.ln.pop = v.packed_pop + pop_ln_off(net.D, net.H1, net.H2, net.OUT);
+    }
+    int lds = carve(G, rb, /*mma16=*/false, /*split_out=*/false, /*ztables=*/false, G.D);
+    if constexpr (POP) {
+        // agent 0's copy in the same tiles: its packed blocks as net_fields lays a net's out, its biases behind them
+        G.popnet = G;
+        smx_mlp3_t copy0 = net;
+        copy0.b1 = v.packed_pop + pop_bias_off(net.D, net.H1, net.H2, net.OUT);
+        copy0.b2 = copy0.b1 + net.H1;
+        copy0.b3 = copy0.b2 + net.H2;
+        net_fields(copy0, v.packed_pop, G.popnet);
+    }
+    if constexpr (LN) lds = carve_ln(G, G.ln, lds);
+    return launch<ddpg_rollout_kernel<1, 3, POP, LN>, ddpg_rollout_kernel<2, 3, POP, LN>,
+                  ddpg_rollout_kernel<4, 2, POP, LN>>(G, rb, lds, stream);
 }
 
-extern "C" int smx_synth_ddpg_population_rollout_f32(const struct smx_ddpg_population_rollout* args, smx_stream_t stream) {
-    PopArgs G;
-    memset(&G, 0, sizeof(G));
-    int rb = 0, lds = 0;
-    SMX_REQUIRE(args && args->base.net, SMX_E_NULL);
-    const smx_mlp3_t& net = *args->base.net;
-    const int rc = population_args(args, pop_copy_floats(net.D, net.H1, net.H2, net.OUT), G, rb, lds);
-    if (rc != SMX_OK) return rc;
-    return launch<ddpg_rollout_kernel<1, 3, true>, ddpg_rollout_kernel<2, 3, true>, ddpg_rollout_kernel<4, 2, true>>(
-        G, rb, lds, stream);
-}
-
-extern "C" int smx_synth_ddpg_ln_population_rollout_f32(const struct smx_ddpg_ln_population_rollout* args,
-                                                        smx_stream_t stream) {
-    PopLnArgs G;
-    memset(&G, 0, sizeof(G));
-    int rb = 0, lds = 0;
-    SMX_REQUIRE(args && args->pop.base.net, SMX_E_NULL);
-    const smx_mlp3_t& net = *args->pop.base.net;
-    int rc = population_args(&args->pop, pop_ln_copy_floats(net.D, net.H1, net.H2, net.OUT), G, rb, lds);
-    if (rc != SMX_OK) return rc;
-    LnTail T = {};
-    rc = ln_args(net, args->ln, args->eps, T);
-    if (rc != SMX_OK) return rc;
-    T.pop = args->pop.packed_pop + pop_ln_off(net.D, net.H1, net.H2, net.OUT);
-    G.ln = T;
-    lds = carve_ln(G, G.ln, lds);
-    return launch<ddpg_rollout_kernel<1, 3, true, true>, ddpg_rollout_kernel<2, 3, true, true>,
-                  ddpg_rollout_kernel<4, 2, true, true>>(G, rb, lds, stream);
+extern "C" int smx_synth_ddpg_rollout_f32(const smx_ddpg_rollout_t* a, const struct smx_ddpg_actor_variant* variant,
+                                          smx_stream_t stream) {
+    static const smx_ddpg_actor_variant plain = {};
+    const smx_ddpg_actor_variant& v = variant ? *variant : plain;
+    if (v.packed_pop) return v.ln ? ddpg_rollout<true, true>(a, v, stream) : ddpg_rollout<true, false>(a, v, stream);
+    return v.ln ? ddpg_rollout<false, true>(a, v, stream) : ddpg_rollout<false, false>(a, v, stream);
 }
 
 extern "C" int smx_synth_ddpg_step_f32(const smx_ddpg_rollout_t* a, const float* mu, int64_t ld_mu, smx_stream_t stream) {

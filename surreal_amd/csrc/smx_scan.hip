@@ -710,7 +710,7 @@ extern "C" int smx_ppo_learn_epilogue_f32(const smx_learn_epilogue_t* a, smx_str
     return SMX_OK;
 }
 
-extern "C" int smx_abi_version(void) { return 1; }
+extern "C" int smx_abi_version(void) { return 2; }
 
 extern "C" const char* smx_error_string(int code) {
     switch (code) {

@@ -308,9 +308,9 @@ class DeviceParamNoise(object):
     agent's actor, element i of the flat parameters W1 | b1 | W2 | b2 | W3 | b3 being w_i + (float)sigma[p] *
     z(seed, agent_base + p, generation, i): a pure function (struct smx_param_noise, include/surreal_amd.h).  Made by
     SyntheticVecEnv.attach_param_noise(agent, seed, actors_per_agent, agent_base).
-    A LayerNorm actor (`ln`; where the kernels offer param_noise_ln_refresh): the flat parameters go on with ln1.W | ln1.b
-    | ln2.W | ln2.b, perturbed by the same rule -- the reference perturbs every fetched array (param_noise.py:14-24) -- and
-    every copy in pop carries them behind its biases.
+    A LayerNorm actor (`ln`; where the kernels run one: kernels.ddpg_ln_launch): the flat parameters go on with ln1.W |
+    ln1.b | ln2.W | ln2.b, perturbed by the same rule -- the reference perturbs every fetched array
+    (param_noise.py:14-24) -- and every copy in pop carries them behind its biases.
 
     On the device: sigma fp64 [P], dist fp64 [P] (the action distance of each agent's first actor, written by the
     rollout launch at its measuring step), pop fp32 [P, copy floats] (the packed copies the launch reads).  On the host,
@@ -340,12 +340,16 @@ class DeviceParamNoise(object):
         self.compute_dist_interval = 10          # AdaptiveNormalParameterNoise's default, which DDPGAgent leaves
         self.sigma = torch.full((self.agents,), float(agent.param_noise_sigma), dtype=torch.float64, device=device)
         self.dist = torch.zeros(self.agents, dtype=torch.float64, device=device)
-        # (kernels without the LayerNorm entries: the plain copies, and ddpg_rollout_into refuses a LayerNorm actor)
-        self.ln = bool(agent.model.use_layernorm) and hasattr(kernels, 'param_noise_ln_refresh')
-        copy_numel = kernels.param_noise_ln_copy_numel if self.ln else kernels.param_noise_copy_numel
-        self.pop = torch.zeros(self.agents, copy_numel(agent.model.actor), device=device)
+        # (kernels that run no LayerNorm actor: the plain copies, and ddpg_rollout_into refuses a LayerNorm actor)
+        from surreal_amd.kernels import ddpg_ln_launch
+        self.ln = bool(agent.model.use_layernorm) and ddpg_ln_launch(kernels)
+        self.pop = torch.zeros(self.agents, kernels.param_noise_copy_numel(agent.model.actor, ln=self.ln), device=device)
         self.generation, self.acts = -1, 0
         self.refresh()                           # generation 0; no act yet: no adaptation
+
+    def _ln(self):
+        """the clean actor's LayerNorm gains and biases as the kernels take them, None for a plain actor"""
+        return self.agent.model.actor_ln_flat if self.ln else None
 
     def refresh(self):
         """the device form of on_parameter_fetched, no host synchronisation: with 'adaptive_normal' and acts > 0 every
@@ -354,11 +358,7 @@ class DeviceParamNoise(object):
         if self.generation + 1 >= 1 << 32:
             raise ValueError('DeviceParamNoise: generation %d leaves [0, 2^32)' % (self.generation + 1))
         self.generation += 1
-        model = self.agent.model
-        if self.ln:
-            self.K.param_noise_ln_refresh(model.actor, model.actor_ln_flat, self)
-        else:
-            self.K.param_noise_refresh(model.actor, self)
+        self.K.param_noise_refresh(self.agent.model.actor, self, ln=self._ln())
         self.acts = 0
 
     def measure_step(self, T):
@@ -373,19 +373,14 @@ class DeviceParamNoise(object):
 
     def perturbed(self, p):
         """-> {'W1', 'b1', 'W2', 'b2', 'W3', 'b3'}, with a LayerNorm actor also {'ln1.W', 'ln1.b', 'ln2.W', 'ln2.b'}:
-        agent p's perturbed actor parameters under the current generation and sigma, as tensors (smx_param_noise_fill_f32
-        / smx_param_noise_ln_fill_f32: the function the copies in pop are made of)"""
+        agent p's perturbed actor parameters under the current generation and sigma, as tensors
+        (smx_param_noise_fill_f32: the function the copies in pop are made of)"""
         import collections
         import torch
         model, actor = self.agent.model, self.agent.model.actor
-        views = list(actor.views.items())
-        if self.ln:
-            views += list(model.actor_ln.items())
-            flat = torch.empty(actor.numel + model.actor_ln_flat.numel(), device=self.device)
-            self.K.param_noise_ln_fill(actor, model.actor_ln_flat, self, p, flat)
-        else:
-            flat = torch.empty(actor.numel, device=self.device)
-            self.K.param_noise_fill(actor, self, p, flat)
+        views = list(actor.views.items()) + (list(model.actor_ln.items()) if self.ln else [])
+        flat = torch.empty(sum(v.numel() for _, v in views), device=self.device)
+        self.K.param_noise_fill(actor, self, p, flat, ln=self._ln())
         out, o = collections.OrderedDict(), 0
         for k, v in views:
             out[k] = flat[o:o + v.numel()].view(v.shape)

@@ -638,58 +638,70 @@ class SyntheticVecEnv(object):
             agent._batch_cells = tuple(own(x) for x in w.hc[cur])
             agent.batch_cells_before = tuple(own(x) for x in w.hc[1 - cur])
 
+    def _ddpg_route(self, agent, reference):
+        """how ddpg_rollout_into runs `agent` -> (route, refusal): 'camera' (the per-step camera path), 'launch' (ONE
+        launch), 'two_launch' (the persistent kernel's two-launch reference) or 'steps' (forward_actor and a step launch
+        per step); refusal (exception class, message) or None.  A LayerNorm actor takes the launch where the kernels run
+        one (kernels.ddpg_ln_launch); else it stays on the per-step path, refused under a parameter noise."""
+        K, model, pn = self.K, agent.model, self.param_noise
+        camera = model.is_pixel_input
+        refusal = self._camera_refusal('ddpg_rollout_into', agent, camera)
+        if refusal is not None:
+            return None, refusal
+        ln = bool(model.use_layernorm)
+        ln_launch = ln and not camera and KN.ddpg_ln_launch(K)
+        # the launch takes the actor: its kind, then its shapes (kernels that run no LayerNorm are not asked about one)
+        supported = not camera and (ln_launch or not ln) and K.synth_ddpg_rollout_supported(
+            model.actor, **(dict(ln=True) if ln_launch else {}))
+        refuse = lambda cls, why: (None, (cls, 'ddpg_rollout_into: ' + why))  # noqa: E731
+        if pn is not None:
+            why = ('a camera agent (the perception would need perturbing too)' if camera else
+                   'a LayerNorm actor' if ln and not (ln_launch and pn.ln) else
+                   'an actor shape the one-launch rollout does not take' if not supported else
+                   'reference=True (the two-launch reference has one actor)' if reference else None)
+            if why is not None:
+                return refuse(NotImplementedError, 'no device parameter noise for ' + why)
+            if agent is not pn.agent:
+                return refuse(ValueError, 'the attached parameter noise belongs to another agent')
+        elif agent.param_noise_type == 'adaptive_normal':
+            return refuse(NotImplementedError, "'adaptive_normal' parameter noise measures an action distance per act() "
+                          "on the host; use 'normal' parameter noise, none, or attach_param_noise")
+        if camera and reference:
+            return refuse(ValueError, 'reference=True has no camera path (no two-launch reference there)')
+        if camera:
+            return 'camera', None
+        if supported and not reference:
+            return 'launch', None
+        return ('two_launch' if reference and not ln else 'steps'), None
+
     def ddpg_rollout_into(self, agent, replay, T, eps=None, sigmas=None, actors_per_workgroup=0, reference=False):
         """T steps of all actors under DDPGAgent `agent` (act: actor -> clip -> exploration noise -> clip,
         ddpg_agent.py:155-184), their n-step transitions (ExpSenderWrapperSSARNStepBootstrap, exp_sender_wrapper.py:72-112)
         written STRAIGHT INTO the uniform replay's device ring (reserve_ring / commit_ring) -> the number of rows written.
-        ONE launch (smx_synth_ddpg_rollout_f32; a LayerNorm actor: smx_synth_ddpg_ln_rollout_f32) where the actor's
-        shapes allow it, else one actor forward (DDPGModel.forward_actor) and one step launch (smx_synth_ddpg_step_f32)
-        per step.  Rollouts need not start at an
-        episode boundary: the open transitions and the OU states carry from call to call (reset() clears them).
-        eps [T, n, A] standard normals (default: drawn here in one launch); sigmas [n] fp64 (default
-        agent.batch_sigmas(n)); actors_per_workgroup: 4 | 8 | 16 forces the persistent kernel's block (0: automatic);
-        reference=True: the two-launch reference of the persistent kernel (smx_epoch_forward_f32 for the actor, then the
-        step launch) -- for parity tests, not the product loop; with a LayerNorm actor: the per-step path
-        (forward_actor, then the step launch).
+        Rollouts need not start at an episode boundary: the open transitions and the OU states carry from call to call
+        (reset() clears them).  eps [T, n, A] standard normals (default: drawn here in one launch); sigmas [n] fp64
+        (default agent.batch_sigmas(n)); actors_per_workgroup: 4 | 8 | 16 forces the persistent kernel's block (0:
+        automatic).  _ddpg_route decides among:
+        ONE launch (smx_synth_ddpg_rollout_f32) where the actor's shapes allow it: a plain actor or, its gains and biases
+        in the launch's actor variant, a LayerNorm one.  With a DeviceParamNoise attached (attach_param_noise) the variant
+        also holds the population: every agent's actors act from their agent's perturbed copy; with 'adaptive_normal' the
+        call's last step s with (acts + s) % compute_dist_interval == 0 also measures each agent's action distance;
+        acts += T.  Other shapes: per step one actor forward (DDPGModel.forward_actor) and one step launch
+        (smx_synth_ddpg_step_f32).  reference=True: the two-launch reference of the persistent kernel
+        (smx_epoch_forward_f32 for the actor, then the step launch) -- for parity tests, not the product loop; with a
+        LayerNorm actor: the per-step path.
         A camera agent on a camera env (frame_stacks S): per step the perception (DDPGModel.perception_into) of the
         stacked frames, the actor, and ONE launch (smx_synth_ddpg_pixel_step) that also renders the step's frame into
         a history of n_step + S raw frames per actor, writes the closing transitions' uint8 'pixel' / 'pixel_next'
         [S*C, H, W] into the ring and the stacked observation of the next step.  The history carries from call to call
-        like the open transitions.
-        With a DeviceParamNoise attached (attach_param_noise): ONE launch too (smx_synth_ddpg_population_rollout_f32 /
-        smx_synth_ddpg_ln_population_rollout_f32),
-        every agent's actors acting from their agent's perturbed copy; with 'adaptive_normal' the call's last step s
-        with (acts + s) % compute_dist_interval == 0 also measures each agent's action distance; acts += T."""
-        K, n, A = self.K, self.n, self.A
-        camera = agent.model.is_pixel_input
-        refusal = self._camera_refusal('ddpg_rollout_into', agent, camera)
+        like the open transitions."""
+        route, refusal = self._ddpg_route(agent, reference)
         if refusal is not None:
             raise refusal[0](refusal[1])
-        pn = self.param_noise
-        # a LayerNorm actor has entry points of its own; kernels that do not offer them leave it where it was: on the
-        # per-step path, and refused under a parameter noise
-        ln = bool(agent.model.use_layernorm)
-        ln_launch = ln and not camera and hasattr(K, 'synth_ddpg_ln_rollout')
-        supported = K.synth_ddpg_ln_rollout_supported if ln_launch else K.synth_ddpg_rollout_supported
-        if pn is not None:
-            ln_pop = ln_launch and pn.ln and hasattr(K, 'synth_ddpg_ln_population_rollout')
-            why = ('a camera agent (the perception would need perturbing too)' if camera else
-                   'a LayerNorm actor' if ln and not ln_pop else
-                   'an actor shape the one-launch rollout does not take' if not supported(agent.model.actor) else
-                   'reference=True (the two-launch reference has one actor)' if reference else None)
-            if why is not None:
-                raise NotImplementedError('ddpg_rollout_into: no device parameter noise for ' + why)
-            if agent is not pn.agent:
-                raise ValueError('ddpg_rollout_into: the attached parameter noise belongs to another agent')
-        elif agent.param_noise_type == 'adaptive_normal':
-            raise NotImplementedError("ddpg_rollout_into: 'adaptive_normal' parameter noise measures an action distance "
-                                      "per act() on the host; use 'normal' parameter noise, none, or attach_param_noise")
+        K, n, A, pn = self.K, self.n, self.A, self.param_noise
         shapes, dtypes = {'obs': (self.D,), 'obs_next': (self.D,), 'actions': (A,), 'rewards': (), 'dones': ()}, None
-        if camera:
-            C, H, W = self.pixel
-            S = self.frame_stacks
-            if reference:
-                raise ValueError('ddpg_rollout_into: reference=True has no camera path (no two-launch reference there)')
+        if route == 'camera':
+            (C, H, W), S = self.pixel, self.frame_stacks
             shapes.update(pixel=(S * C, H, W), pixel_next=(S * C, H, W))
             dtypes = {'pixel': torch.uint8, 'pixel_next': torch.uint8}
         algo = agent.learner_config.algo
@@ -724,44 +736,32 @@ class SyntheticVecEnv(object):
                  theta=agent.theta, dt=agent.dt, root_dt=float(np.sqrt(agent.dt)), gpow=d['gpow'], ou=d['ou'],
                  carry_obs=d['carry_obs'], carry_act=d['carry_act'], carry_rew=d['carry_rew'], tables=tables,
                  cursor=cursor)
-        if camera:
-            self._ddpg_pixel_steps(agent, r, T, N, cap, eps, ns)
-            replay.commit_ring(rows)
-            return rows
         actor, model = agent.model.actor, agent.model
-        persistent = (ln_launch or not ln) and supported(actor)
-        two_launch = reference and not ln         # (a LayerNorm actor's reference is the per-step path itself)
-        if persistent or two_launch:
+        if route in ('launch', 'two_launch'):
             if d.get('pk') is None or d['pk'].numel() != K.epoch_packed_numel(actor):
                 d['pk'] = torch.zeros(K.epoch_packed_numel(actor), device=self.device)
             K.epoch_pack([(actor, d['pk'])])        # (the agent's parameters only change between rollouts)
-        if pn is not None:
-            if ln:
-                K.synth_ddpg_ln_population_rollout(actor, d['pk'], model.actor_ln_flat, model.ln_eps, r, T, pn,
-                                                   pn.measure_step(T), actors_per_workgroup, **self._mon(T),
-                                                   **self._noi(T, ns))
-            else:
-                K.synth_ddpg_population_rollout(actor, d['pk'], r, T, pn, pn.measure_step(T), actors_per_workgroup,
-                                                **self._mon(T), **self._noi(T, ns))
-            pn.acts += T
-            self.t = t
-        elif persistent and not reference:
-            if ln:
-                K.synth_ddpg_ln_rollout(actor, d['pk'], model.actor_ln_flat, model.ln_eps, r, T, actors_per_workgroup,
-                                        **self._mon(T), **self._noi(T, ns))
-            else:
-                K.synth_ddpg_rollout(actor, d['pk'], r, T, actors_per_workgroup, **self._mon(T), **self._noi(T, ns))
+        if route == 'camera':
+            self._ddpg_pixel_steps(agent, r, T, N, cap, eps, ns)
+        elif route == 'launch':
+            variant = dict(ln=model.actor_ln_flat, ln_eps=model.ln_eps) if model.use_layernorm else {}    # (plain: none)
+            if pn is not None:
+                variant.update(pn=pn, measure_step=pn.measure_step(T))
+            K.synth_ddpg_rollout(actor, d['pk'], r, T, actors_per_workgroup, **variant, **self._mon(T),
+                                 **self._noi(T, ns))
+            if pn is not None:
+                pn.acts += T
             self.t = t
         else:
-            if two_launch:
+            if route == 'two_launch':
                 mu = torch.empty(n, A, device=self.device)
                 ctrl = torch.zeros(L.CTRL_WORDS, device=self.device)
             for s in range(T):
-                if two_launch:
+                if route == 'two_launch':
                     K.epoch_forward([dict(net=actor, packed=d['pk'], x=self.state, out=mu, act=L.SMX_ACT_TANH)],
                                     None, ctrl, n)
                 else:
-                    mu = agent.model.forward_actor(self.state)
+                    mu = model.forward_actor(self.state)
                 r['t'] = self.t
                 r['eps'] = None if eps is None else eps[s]
                 K.synth_ddpg_step(r, mu, **self._mon(1), **self._noi(1, ns))

@@ -22,6 +22,13 @@ def _row_stride(view, width):
     return view.stride(0) if view.shape[0] > 1 else max(view.stride(0), width)
 
 
+def ddpg_ln_launch(kernels):
+    """whether `kernels` runs a LayerNorm DDPG actor in the one-launch rollout and under the device parameter noise
+    (the ln arguments of synth_ddpg_rollout and param_noise_*): its `ddpg_ln_launch` attribute; an object without
+    one does not.  A property of the kernels object alone, never of an actor's shape."""
+    return bool(getattr(kernels, 'ddpg_ln_launch', False))
+
+
 class HipKernels(object):
     name = 'hip'
 
@@ -797,8 +804,12 @@ class HipKernels(object):
         self._window_args(p, n_step, advance, carry, tables, cursor)
         L.call('smx_synth_ppo_window_rollout_f32', ctypes.byref(p), self._st())
 
-    def synth_ddpg_rollout_supported(self, net):
-        return bool(self.lib.smx_synth_ddpg_rollout_supported(net.D, net.H1, net.H2, net.OUT))
+    # a LayerNorm actor runs in the one-launch DDPG rollout and under the parameter noise (ddpg_ln_launch(), above)
+    ddpg_ln_launch = True
+
+    def synth_ddpg_rollout_supported(self, net, ln=False):
+        """the actor shapes synth_ddpg_rollout takes; ln: with a LayerNorm behind each hidden ReLU"""
+        return bool(self.lib.smx_synth_ddpg_rollout_supported(net.D, net.H1, net.H2, net.OUT, int(bool(ln))))
 
     @classmethod
     def _ddpg_args(cls, r, steps, net=None, packed=None, actors_per_workgroup=0, monitor=None, noise=None):
@@ -826,117 +837,78 @@ class HipKernels(object):
         p.noise = cls._noise_args(noise)
         return p
 
-    def synth_ddpg_rollout(self, net, packed, r, steps, actors_per_workgroup=0, monitor=None, noise=None):
-        """`steps` DDPG acting + environment steps of all actors with their n-step transitions written into the ring
-        tables, ONE launch (csrc/smx_rollout.hip).  packed: epoch_pack of the actor `net`; r: see _ddpg_args
-        (eps [steps, n, A])"""
-        if r['eps'] is not None:
-            assert r['eps'].is_contiguous() and tuple(r['eps'].shape) == (steps, r['state'].shape[0], net.OUT)
-        p = self._ddpg_args(r, steps, net, packed, actors_per_workgroup, monitor, noise)
-        L.call('smx_synth_ddpg_rollout_f32', ctypes.byref(p), self._st())
-
-    # ---- the same for a LayerNorm actor; ln: ln1.W | ln1.b | ln2.W | ln2.b contiguous (DDPGModel.actor_ln_flat) ----
-    def synth_ddpg_ln_rollout_supported(self, net):
-        return bool(self.lib.smx_synth_ddpg_ln_rollout_supported(net.D, net.H1, net.H2, net.OUT))
-
     @staticmethod
     def _ln_ptr(net, ln):
+        """ln: None, or ln1.W | ln1.b | ln2.W | ln2.b contiguous (DDPGModel.actor_ln_flat)"""
+        if ln is None:
+            return None
         assert ln.dtype == torch.float32 and ln.is_contiguous() and ln.numel() == 2 * (net.H1 + net.H2)
         return L.ptr(ln)
 
-    def synth_ddpg_ln_rollout(self, net, packed, ln, ln_eps, r, steps, actors_per_workgroup=0, monitor=None, noise=None):
-        """synth_ddpg_rollout with a LayerNorm (gains and biases `ln`, eps `ln_eps`) behind each hidden ReLU of `net`,
-        ONE launch (smx_synth_ddpg_ln_rollout_f32)"""
+    @staticmethod
+    def _population_ptrs(pn):
+        """-> (pop, its row stride, dist) of a DeviceParamNoise-like `pn`: pop fp32 [P, stride], dist fp64 [P]"""
+        assert pn.pop.dtype == torch.float32 and pn.pop.is_contiguous() and pn.dist.dtype == torch.float64
+        assert pn.pop.shape[0] == int(pn.agents) == pn.dist.numel() and pn.dist.is_contiguous()
+        return L.ptr(pn.pop), pn.pop.shape[1], L.ptr(pn.dist)
+
+    def synth_ddpg_rollout(self, net, packed, r, steps, actors_per_workgroup=0, monitor=None, noise=None, ln=None,
+                           ln_eps=0.0, pn=None, measure_step=-1):
+        """`steps` DDPG acting + environment steps of all actors with their n-step transitions written into the ring
+        tables, ONE launch (smx_synth_ddpg_rollout_f32, csrc/smx_rollout.hip).  packed: epoch_pack of the actor `net`;
+        r: see _ddpg_args (eps [steps, n, A]).
+        ln, ln_eps: a LayerNorm (gains and biases, eps) behind each hidden ReLU of `net`.
+        pn: every agent of `pn` (pn.actors_per_agent consecutive actors) acts from its own copy in pn.pop
+        (param_noise_refresh's, for the same ln); net / packed / ln are the clean actor, evaluated at step measure_step
+        (-1: never) for pn.dist"""
         if r['eps'] is not None:
             assert r['eps'].is_contiguous() and tuple(r['eps'].shape) == (steps, r['state'].shape[0], net.OUT)
-        p = L.DdpgLnRollout()
-        p.base = self._ddpg_args(r, steps, net, packed, actors_per_workgroup, monitor, noise)
-        p.ln, p.eps = self._ln_ptr(net, ln), float(ln_eps)
-        L.call('smx_synth_ddpg_ln_rollout_f32', ctypes.byref(p), self._st())
+        p = self._ddpg_args(r, steps, net, packed, actors_per_workgroup, monitor, noise)
+        v = L.DdpgActorVariant()
+        v.ln, v.ln_eps = self._ln_ptr(net, ln), float(ln_eps)
+        if pn is not None:
+            v.packed_pop, v.packed_stride, v.dist = self._population_ptrs(pn)
+            v.actors_per_agent, v.agents, v.measure_step = int(pn.actors_per_agent), int(pn.agents), int(measure_step)
+        L.call('smx_synth_ddpg_rollout_f32', ctypes.byref(p), ctypes.byref(v), self._st())
 
-    # ---- parameter-space noise on the device (csrc/smx_param_noise.hip; DeviceParamNoise, env/monitor.py) ----
-    def param_noise_copy_numel(self, net):
-        """floats of one agent's copy in the population buffer: epoch_pack's layout, then the biases"""
-        return int(self.lib.smx_param_noise_copy_floats(net.D, net.H1, net.H2, net.OUT))
+    def synth_ddpg_population_block(self, n, actors_per_agent, forced=0):
+        """the block size the launch takes for a population (0: it refuses)"""
+        return int(self.lib.smx_synth_ddpg_population_block(int(n), int(actors_per_agent), int(forced)))
 
-    @staticmethod
-    def _param_noise_args(net, pn):
-        """struct smx_param_noise of the clean actor `net` and a DeviceParamNoise-like `pn`: seed, agent_base,
+    # ---- parameter-space noise on the device (csrc/smx_param_noise.hip; DeviceParamNoise, env/monitor.py); ln: as above,
+    # the flat parameters then go on with it and every copy carries the perturbed four behind its biases ----
+    def param_noise_copy_numel(self, net, ln=False):
+        """floats of one agent's copy in the population buffer: epoch_pack's layout, then the biases, then (ln) the
+        LayerNorm parameters"""
+        return int(self.lib.smx_param_noise_copy_floats(net.D, net.H1, net.H2, net.OUT, int(bool(ln))))
+
+    @classmethod
+    def _param_noise_args(cls, net, pn, ln):
+        """struct smx_param_noise of the clean actor `net` (, `ln`) and a DeviceParamNoise-like `pn`: seed, agent_base,
         generation, acts, adaptive, alpha, target, sigma / dist (fp64 [P]), pop ([P, stride] fp32)"""
         q = L.ParamNoise()
         q.net = ctypes.pointer(net.desc)
         q.seed, q.agent_base, q.generation = int(pn.seed), int(pn.agent_base), int(pn.generation)
         q.agents, q.adaptive, q.acts = int(pn.agents), int(bool(pn.adaptive)), int(pn.acts)
         q.alpha, q.target = float(pn.alpha), float(pn.target)
-        assert pn.sigma.dtype == torch.float64 and pn.dist.dtype == torch.float64
-        assert pn.sigma.numel() == pn.dist.numel() == q.agents and pn.sigma.is_contiguous() and pn.dist.is_contiguous()
-        assert pn.pop.dtype == torch.float32 and pn.pop.is_contiguous() and pn.pop.shape[0] == q.agents
-        q.sigma, q.dist, q.packed_pop, q.packed_stride = L.ptr(pn.sigma), L.ptr(pn.dist), L.ptr(pn.pop), pn.pop.shape[1]
+        assert pn.sigma.dtype == torch.float64 and pn.sigma.numel() == q.agents and pn.sigma.is_contiguous()
+        q.sigma, q.ln = L.ptr(pn.sigma), cls._ln_ptr(net, ln)
+        q.packed_pop, q.packed_stride, q.dist = cls._population_ptrs(pn)
         return q
 
-    def param_noise_fill(self, net, pn, p, out):
-        """out [numel of the actor's flat parameters] <- agent p's perturbed parameters (smx_param_noise_fill_f32)"""
-        assert out.is_contiguous() and out.dtype == torch.float32 and out.numel() == net.numel
-        L.call('smx_param_noise_fill_f32', ctypes.byref(self._param_noise_args(net, pn)), int(p), L.ptr(out), self._st())
-
-    def param_noise_refresh(self, net, pn):
-        """the device form of on_parameter_fetched for all agents of `pn` (smx_param_noise_refresh_f32): the adaptive
-        rule on sigma when pn.adaptive and pn.acts > 0, then every agent's copy of the perturbed `net` into pn.pop"""
-        L.call('smx_param_noise_refresh_f32', ctypes.byref(self._param_noise_args(net, pn)), self._st())
-
-    def param_noise_ln_copy_numel(self, net):
-        """floats of one agent's copy of a LayerNorm actor: param_noise_copy_numel's, then the LayerNorm parameters"""
-        return int(self.lib.smx_param_noise_ln_copy_floats(net.D, net.H1, net.H2, net.OUT))
-
-    def _param_noise_ln_args(self, net, ln, pn):
-        q = L.ParamNoiseLn()
-        q.base = self._param_noise_args(net, pn)
-        q.ln = self._ln_ptr(net, ln)
-        return q
-
-    def param_noise_ln_fill(self, net, ln, pn, p, out):
-        """param_noise_fill over the flat parameters of a LayerNorm actor: out [net.numel + ln.numel()]"""
-        assert out.is_contiguous() and out.dtype == torch.float32 and out.numel() == net.numel + ln.numel()
-        L.call('smx_param_noise_ln_fill_f32', ctypes.byref(self._param_noise_ln_args(net, ln, pn)), int(p), L.ptr(out),
+    def param_noise_fill(self, net, pn, p, out, ln=None):
+        """out [numel of the actor's flat parameters, ln's included] <- agent p's perturbed parameters
+        (smx_param_noise_fill_f32)"""
+        assert out.is_contiguous() and out.dtype == torch.float32
+        assert out.numel() == net.numel + (0 if ln is None else ln.numel())
+        L.call('smx_param_noise_fill_f32', ctypes.byref(self._param_noise_args(net, pn, ln)), int(p), L.ptr(out),
                self._st())
 
-    def param_noise_ln_refresh(self, net, ln, pn):
-        """param_noise_refresh for a LayerNorm actor: the copies in pn.pop carry the perturbed `ln` behind the biases"""
-        L.call('smx_param_noise_ln_refresh_f32', ctypes.byref(self._param_noise_ln_args(net, ln, pn)), self._st())
-
-    def synth_ddpg_population_block(self, n, actors_per_agent, forced=0):
-        """the block size the population launch takes (0: it refuses)"""
-        return int(self.lib.smx_synth_ddpg_population_block(int(n), int(actors_per_agent), int(forced)))
-
-    def synth_ddpg_population_rollout(self, net, packed, r, steps, pn, measure_step=-1, actors_per_workgroup=0,
-                                      monitor=None, noise=None):
-        """synth_ddpg_rollout with every agent of `pn` (pn.actors_per_agent consecutive actors) acting from its own
-        copy in pn.pop; net / packed: the clean actor, evaluated at step measure_step (-1: never) for pn.dist"""
-        if r['eps'] is not None:
-            assert r['eps'].is_contiguous() and tuple(r['eps'].shape) == (steps, r['state'].shape[0], net.OUT)
-        p = self._population_args(net, packed, r, steps, pn, measure_step, actors_per_workgroup, monitor, noise)
-        L.call('smx_synth_ddpg_population_rollout_f32', ctypes.byref(p), self._st())
-
-    def _population_args(self, net, packed, r, steps, pn, measure_step, actors_per_workgroup, monitor, noise):
-        p = L.DdpgPopulationRollout()
-        p.base = self._ddpg_args(r, steps, net, packed, actors_per_workgroup, monitor, noise)
-        assert pn.pop.dtype == torch.float32 and pn.pop.is_contiguous() and pn.dist.dtype == torch.float64
-        assert pn.pop.shape[0] == pn.agents == pn.dist.numel()
-        p.packed_pop, p.packed_stride = L.ptr(pn.pop), pn.pop.shape[1]
-        p.actors_per_agent, p.agents, p.measure_step = int(pn.actors_per_agent), int(pn.agents), int(measure_step)
-        p.dist = L.ptr(pn.dist)
-        return p
-
-    def synth_ddpg_ln_population_rollout(self, net, packed, ln, ln_eps, r, steps, pn, measure_step=-1,
-                                         actors_per_workgroup=0, monitor=None, noise=None):
-        """synth_ddpg_population_rollout for a LayerNorm actor: pn.pop holds param_noise_ln_refresh's copies; ln, ln_eps:
-        the clean actor's, as synth_ddpg_ln_rollout takes them"""
-        if r['eps'] is not None:
-            assert r['eps'].is_contiguous() and tuple(r['eps'].shape) == (steps, r['state'].shape[0], net.OUT)
-        p = L.DdpgLnPopulationRollout()
-        p.pop = self._population_args(net, packed, r, steps, pn, measure_step, actors_per_workgroup, monitor, noise)
-        p.ln, p.eps = self._ln_ptr(net, ln), float(ln_eps)
-        L.call('smx_synth_ddpg_ln_population_rollout_f32', ctypes.byref(p), self._st())
+    def param_noise_refresh(self, net, pn, ln=None):
+        """the device form of on_parameter_fetched for all agents of `pn` (smx_param_noise_refresh_f32): the adaptive
+        rule on sigma when pn.adaptive and pn.acts > 0, then every agent's copy of the perturbed `net` (, `ln`) into
+        pn.pop"""
+        L.call('smx_param_noise_refresh_f32', ctypes.byref(self._param_noise_args(net, pn, ln)), self._st())
 
     def synth_ddpg_step(self, r, mu, monitor=None, noise=None):
         """one step of synth_ddpg_rollout given the actor's output mu [n, A] (r['eps']: this step's [n, A] draws;

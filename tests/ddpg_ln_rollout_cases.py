@@ -3,8 +3,9 @@ SyntheticVecEnv.ddpg_rollout_into with a LayerNorm actor (use_layernorm=True) on
 device parameter noise; shared by the CPU tier (test_ddpg_ln_rollout_cpu.py) and the GPU tier
 (test_gpu_ddpg_ln_rollout.py):
 
-  * ``DdpgLnRolloutCpuKernels`` -- the torch-CPU double with the LayerNorm entry points (synth_ddpg_ln_rollout*,
-    param_noise_ln_*) on top of the parameter-noise double; its fills are the float64 Philox restatement rounded to fp32;
+  * ``DdpgLnRolloutCpuKernels`` -- the torch-CPU double that runs a LayerNorm actor (the ln arguments of
+    synth_ddpg_rollout and param_noise_*) on top of the parameter-noise double; its fills are the float64 Philox
+    restatement rounded to fp32;
   * ``set_layernorm`` -- random gains and biases (the defaults 1 / 0 would let a wrong affine step pass);
   * ``actor_out`` / ``action_distance`` -- the LayerNorm actor in float64;
   * ``make`` / ``run`` / ``final`` / ``same_bytes`` -- an env with its agent and replay, calls of ddpg_rollout_into, every
@@ -38,14 +39,15 @@ def closing(steps, t0=0, episode_len=EP, n_step=N_STEP):
 
 class DdpgLnRolloutCpuKernels(TP.ParamNoiseCpuKernels):
     name = 'torch-cpu-double+ddpg-ln-rollout'
+    ddpg_ln_launch = True
     _step = DC.DdpgRolloutCpuKernels.synth_ddpg_step      # (the launches' own steps: not the env's per-step calls)
 
     def __init__(self, *a, **kw):
         super().__init__(*a, **kw)
         self.ln_launches, self.ln_refreshes = [], []
 
-    def synth_ddpg_ln_rollout_supported(self, net):
-        return self.synth_ddpg_rollout_supported(net)
+    def synth_ddpg_rollout_supported(self, net, ln=False):
+        return super().synth_ddpg_rollout_supported(net)
 
     def _mu_ln(self, net, W, ln, eps, state):
         F = torch.nn.functional
@@ -60,7 +62,14 @@ class DdpgLnRolloutCpuKernels(TP.ParamNoiseCpuKernels):
             rows.append(torch.tanh(F.linear(h2, W['W3'], W['b3'])))
         return torch.cat(rows)
 
-    def synth_ddpg_ln_rollout(self, net, packed, ln, ln_eps, r, steps, actors_per_workgroup=0):
+    def synth_ddpg_rollout(self, net, packed, r, steps, actors_per_workgroup=0, ln=None, ln_eps=0.0, pn=None,
+                           measure_step=-1):
+        if ln is None:
+            return super().synth_ddpg_rollout(net, packed, r, steps, actors_per_workgroup, pn=pn,
+                                              measure_step=measure_step)
+        if pn is not None:
+            self.launches.append(dict(steps=steps, measure_step=measure_step, acts=pn.acts, t=int(r['t']),
+                                      actors_per_workgroup=actors_per_workgroup, ln=True))
         assert actors_per_workgroup in (0, 4, 8, 16) and ln.numel() == 2 * (net.H1 + net.H2)
         self.ln_launches.append(dict(steps=steps, t=int(r['t'])))
         n, cap = r['state'].shape[0], r['tables']['obs'].shape[0]
@@ -83,23 +92,16 @@ class DdpgLnRolloutCpuKernels(TP.ParamNoiseCpuKernels):
         z = PR.normal(pn.seed, pn.agent_base + p, pn.generation, np.arange(flat.numel())).astype(np.float32)
         out.copy_(flat + torch.as_tensor(sg * z))
 
-    def param_noise_fill(self, net, pn, p, out):
-        self._fill(torch.cat([net.views[k].reshape(-1) for k in PR.ORDER]), pn, p, out)
+    def param_noise_fill(self, net, pn, p, out, ln=None):
+        self._fill(torch.cat([net.views[k].reshape(-1) for k in PR.ORDER] + ([] if ln is None else [ln])), pn, p, out)
 
-    def param_noise_ln_fill(self, net, ln, pn, p, out):
-        self._fill(torch.cat([net.views[k].reshape(-1) for k in PR.ORDER] + [ln]), pn, p, out)
+    def param_noise_copy_numel(self, net, ln=False):
+        return 64 + (2 * (net.H1 + net.H2) + 63) // 64 * 64 if ln else super().param_noise_copy_numel(net)
 
-    def param_noise_ln_copy_numel(self, net):
-        return 64 + (2 * (net.H1 + net.H2) + 63) // 64 * 64
-
-    def param_noise_ln_refresh(self, net, ln, pn):
+    def param_noise_refresh(self, net, pn, ln=None):
+        if ln is None:
+            return super().param_noise_refresh(net, pn)
         self.ln_refreshes.append(dict(generation=pn.generation, acts=pn.acts, ln=ln.numel()))
-
-    def synth_ddpg_ln_population_rollout(self, net, packed, ln, ln_eps, r, steps, pn, measure_step=-1,
-                                         actors_per_workgroup=0):
-        self.launches.append(dict(steps=steps, measure_step=measure_step, acts=pn.acts, t=int(r['t']),
-                                  actors_per_workgroup=actors_per_workgroup, ln=True))
-        self.synth_ddpg_ln_rollout(net, packed, ln, ln_eps, r, steps, actors_per_workgroup)
 
 
 def set_layernorm(agent, seed=7):

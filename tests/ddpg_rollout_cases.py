@@ -22,6 +22,7 @@ FIELDS = ('obs', 'obs_next', 'actions', 'rewards', 'dones')
 
 class DdpgRolloutCpuKernels(TorchCpuKernels):
     name = 'torch-cpu-double+ddpg-rollout'
+    ddpg_ln_launch = False        # (kernels.ddpg_ln_launch: no LayerNorm actor in the launch; the camera double inherits it)
 
     def synth_ddpg_rollout_supported(self, net):
         return (net.OUT <= 32 and net.H1 % 4 == 0 and net.H2 % 4 == 0 and net.H1 <= 640 and net.H2 <= 640

@@ -26,7 +26,7 @@ def test_library_exports_every_declared_symbol():
         assert hasattr(lib, n), 'include/surreal_amd.h declares %s but the .so does not export it' % n
     # and the ctypes binding covers exactly the header
     assert sorted(_lib.EXPORTED_SYMBOLS) == names
-    assert _lib.load().smx_abi_version() == 1
+    assert _lib.load().smx_abi_version() == 2
 
 
 def test_ctrl_struct_layout_matches_binding():

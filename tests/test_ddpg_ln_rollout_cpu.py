@@ -1,5 +1,5 @@
-"""CPU tier: a LayerNorm actor in SyntheticVecEnv.ddpg_rollout_into on a torch-CPU double that offers the LayerNorm entry
-points (ddpg_ln_rollout_cases.DdpgLnRolloutCpuKernels): which path a call takes, the one-launch double against the host
+"""CPU tier: a LayerNorm actor in SyntheticVecEnv.ddpg_rollout_into on a torch-CPU double that runs one in the launch
+(ddpg_ln_rollout_cases.DdpgLnRolloutCpuKernels): which path a call takes, the one-launch double against the host
 path, the perturbed parameters of a LayerNorm actor against the float64 restatement, the checkpoint, the layout of the new
 argument blocks."""
 import ctypes
@@ -31,7 +31,7 @@ def K():
 
 @pytest.fixture
 def K_without():
-    """the existing double: no LayerNorm entry points"""
+    """the existing double: no LayerNorm actor in the launch (ddpg_ln_launch False)"""
     KN, prev = use(DC.DdpgRolloutCpuKernels())
     yield KN.default_kernels()
     KN.set_default_kernels(*prev)
@@ -100,7 +100,7 @@ def test_perturbed_parameters_of_a_layernorm_actor(K):
     agent, venv, _, pn, _ = LC.make(12, SHAPE, ptype='normal', device='cpu', kernels=K, attach=True, agent_base=2)
     assert pn.ln and pn.agents == 3 and K.ln_refreshes == [dict(generation=0, acts=0, ln=2 * (24 + 16))]
     assert K.refreshes == []
-    assert pn.pop.shape == (3, K.param_noise_ln_copy_numel(agent.model.actor))
+    assert pn.pop.shape == (3, K.param_noise_copy_numel(agent.model.actor, ln=True))
     plain_agent, plain_env, _, plain, _ = LC.make(12, SHAPE, ptype='normal', device='cpu', kernels=K, attach=True,
                                                   agent_base=2, layernorm=False)
     assert not plain.ln and len(K.refreshes) == 1
@@ -134,7 +134,7 @@ def test_state_dict_round_trip(K):
     pn.acts = 5
     sd = {k: (v.clone() if torch.is_tensor(v) else v) for k, v in pn.state_dict().items()}
     assert set(sd) == {'sigma', 'dist', 'pop', 'generation', 'acts'}
-    assert sd['pop'].shape[1] == K.param_noise_ln_copy_numel(agent.model.actor)
+    assert sd['pop'].shape[1] == K.param_noise_copy_numel(agent.model.actor, ln=True)
     other = LC.make(8, SHAPE, ptype='adaptive_normal', device='cpu', kernels=K, attach=True)[3]
     other.refresh()
     other.load_state_dict(sd)
@@ -165,17 +165,18 @@ def test_population_launch_of_a_layernorm_actor_and_its_refusals(K):
 
 def test_new_argument_blocks_match_their_ctypes_mirrors(tmp_path):
     from surreal_amd import _lib as L
-    for cname, cls in (('struct smx_ddpg_ln_rollout', L.DdpgLnRollout), ('struct smx_param_noise_ln', L.ParamNoiseLn),
-                       ('struct smx_ddpg_ln_population_rollout', L.DdpgLnPopulationRollout)):
-        got = H._offsets(tmp_path, cname, cls)
-        assert got['sizeof'] == ctypes.sizeof(cls), cname
+    got = {}
+    for cname, cls in (('struct smx_ddpg_actor_variant', L.DdpgActorVariant), ('struct smx_param_noise', L.ParamNoise)):
+        sub = tmp_path / cname.split()[-1]
+        sub.mkdir()
+        got[cls] = H._offsets(sub, cname, cls)
+        assert got[cls]['sizeof'] == ctypes.sizeof(cls), cname
         for f, _ in cls._fields_:
-            assert got[f] == getattr(cls, f).offset, (cname, f)
-    # the existing blocks come first and are what they were
-    assert L.DdpgLnRollout.base.offset == 0 and L.DdpgLnRollout.ln.offset == ctypes.sizeof(L.DdpgRollout)
-    assert L.ParamNoiseLn.base.offset == 0 and L.ParamNoiseLn.ln.offset == ctypes.sizeof(L.ParamNoise)
-    assert L.DdpgLnPopulationRollout.pop.offset == 0
-    assert L.DdpgLnPopulationRollout.ln.offset == ctypes.sizeof(L.DdpgPopulationRollout)
+            assert got[cls][f] == getattr(cls, f).offset, (cname, f)
+    # the LayerNorm block leads the variant; in the parameter noise it trails the existing fields, which are where they were
+    assert L.DdpgActorVariant.ln.offset == 0 and L.DdpgActorVariant.ln_eps.offset == 8
+    assert L.ParamNoise._fields_[-1][0] == 'ln'
+    assert L.ParamNoise.ln.offset == L.ParamNoise.packed_stride.offset + 8 == ctypes.sizeof(L.ParamNoise) - 8
 
 
 def test_supported_shapes_include_the_layernorm_floats():
@@ -184,11 +185,11 @@ def test_supported_shapes_include_the_layernorm_floats():
     lib = L.load()
     for shape in LC.SHAPES:
         D, H1, H2, A = shape
-        assert lib.smx_synth_ddpg_ln_rollout_supported(D, H1, H2, A) == 1
-    assert lib.smx_synth_ddpg_ln_rollout_supported(512, 640, 640, 32) == 1       # the largest plain shape still fits
-    assert lib.smx_synth_ddpg_ln_rollout_supported(17, 302, 200, 6) == 0
-    assert lib.smx_synth_ddpg_ln_rollout_supported(17, 644, 200, 6) == 0
-    assert lib.smx_synth_ddpg_ln_rollout_supported(17, 300, 200, 33) == 0
-    assert lib.smx_param_noise_ln_copy_floats(5, 12, 8, 3) % 64 == 0
-    assert lib.smx_param_noise_ln_copy_floats(5, 12, 8, 3) >= lib.smx_param_noise_copy_floats(5, 12, 8, 3) + 40 - 63
-    assert lib.smx_param_noise_ln_copy_floats(0, 12, 8, 3) == 0
+        assert lib.smx_synth_ddpg_rollout_supported(D, H1, H2, A, 1) == 1
+    assert lib.smx_synth_ddpg_rollout_supported(512, 640, 640, 32, 1) == 1       # the largest plain shape still fits
+    assert lib.smx_synth_ddpg_rollout_supported(17, 302, 200, 6, 1) == 0
+    assert lib.smx_synth_ddpg_rollout_supported(17, 644, 200, 6, 1) == 0
+    assert lib.smx_synth_ddpg_rollout_supported(17, 300, 200, 33, 1) == 0
+    assert lib.smx_param_noise_copy_floats(5, 12, 8, 3, 1) % 64 == 0
+    assert lib.smx_param_noise_copy_floats(5, 12, 8, 3, 1) >= lib.smx_param_noise_copy_floats(5, 12, 8, 3, 0) + 40 - 63
+    assert lib.smx_param_noise_copy_floats(0, 12, 8, 3, 1) == 0

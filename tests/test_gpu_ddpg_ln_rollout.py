@@ -1,5 +1,5 @@
-"""GPU tier (-m gpu): a LayerNorm actor on the one-launch DDPG rollout (smx_synth_ddpg_ln_rollout_f32) and under a device
-parameter noise (smx_param_noise_ln_*_f32, smx_synth_ddpg_ln_population_rollout_f32).
+"""GPU tier (-m gpu): a LayerNorm actor on the one-launch DDPG rollout (smx_synth_ddpg_rollout_f32 with the `ln` of a
+struct smx_ddpg_actor_variant) and under a device parameter noise (smx_param_noise_*_f32 with `ln`, the variant's packed_pop).
 
 Actor shapes (ddpg_ln_rollout_cases): 5 -> 12 -> 8 -> 3, 17 -> 76 -> 132 -> 6, 17 -> 300 -> 200 -> 6, 17 -> 640 -> 640 -> 6;
 37 actors (a partial last block at 4, 8 and 16), episodes of 11 against calls of 9 + 13 + 6, n_step 3; the default shape
@@ -173,7 +173,7 @@ def test_packed_copies_carry_the_perturbed_layernorm_parameters_with_zero_pads()
     agent, venv, _, pn = population(16, 'adaptive_normal')
     K, actor = venv.K, agent.model.actor
     numel = K.epoch_packed_numel(actor)
-    assert pn.pop.shape[1] == K.param_noise_ln_copy_numel(actor) and pn.pop.shape[1] % 64 == 0
+    assert pn.pop.shape[1] == K.param_noise_copy_numel(actor, ln=True) and pn.pop.shape[1] % 64 == 0
     twin = copy.deepcopy(agent.model)
     for p in range(pn.agents):
         pert = pn.perturbed(p)
@@ -229,3 +229,33 @@ def test_distance_of_the_layernorm_actors_and_the_adaptation():
     want = [PR.adapt(s, d, 9, pn.target, pn.alpha) for s, d in zip(sigma0, dist)]
     assert [float(v) for v in pn.sigma.cpu()] == want and len({w > s for w, s in zip(want, sigma0)}) == 2
     assert pn.acts == 0 and pn.generation == gen + 1
+
+
+# ---- the one entry point: no variant and an empty one -------------------------------------------------------------------
+
+def test_no_variant_and_an_empty_variant_leave_the_same_bytes():
+    """smx_synth_ddpg_rollout_f32 with variant = NULL against a variant whose pointers are both NULL (what the facade
+    passes for a plain actor): the plain launch either way.  5 -> 12 -> 8 -> 3, 8 actors, one call of 9 steps"""
+    import ctypes
+    from surreal_amd import _lib as L
+
+    def null_variant(K):
+        def launch(net, packed, r, steps, actors_per_workgroup=0, monitor=None, noise=None):
+            p = K._ddpg_args(r, steps, net, packed, actors_per_workgroup, monitor, noise)
+            L.call('smx_synth_ddpg_rollout_f32', ctypes.byref(p), None, K._st())
+            calls.append(steps)
+        return launch
+    outs, calls = [], []
+    for null in (True, False):
+        agent, venv, replay, _, _ = LC.make(8, LC.TINY, 'ou_noise', layernorm=False, capacity=256)
+        if null:
+            venv.K.synth_ddpg_rollout = null_variant(venv.K)
+        try:
+            rows = LC.run(agent, venv, replay, (9,), eps=eps_for(8, 3, 9))
+        finally:
+            if null:
+                del venv.K.synth_ddpg_rollout
+        assert rows == 8 * LC.closing(9)
+        outs.append(LC.final(venv, replay, rows))
+    assert calls == [9] and float(outs[0]['ring_actions'].abs().sum()) > 0
+    LC.same_bytes(outs[0], outs[1])

@@ -1,5 +1,5 @@
 """GPU tier (-m gpu): per-agent parameter-space noise in the one-launch DDPG rollout
-(SyntheticVecEnv.attach_param_noise -> DeviceParamNoise; smx_param_noise_*_f32, smx_synth_ddpg_population_rollout_f32).
+(SyntheticVecEnv.attach_param_noise -> DeviceParamNoise; smx_param_noise_*_f32, smx_synth_ddpg_rollout_f32 on a population).
 
 Shapes: the actor 5 -> 12 -> 8 -> 3 (D no multiple of 4, both hidden widths below one 16-feature tile), n_step 3,
 episode_len 5 against T = 7 (a call crosses an episode end), 16 actors."""

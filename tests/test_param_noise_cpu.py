@@ -26,16 +26,17 @@ class ParamNoiseCpuKernels(PC.DdpgPixelRolloutCpuKernels):
         super().__init__(*a, **kw)
         self.refreshes, self.launches = [], []
 
-    def param_noise_copy_numel(self, net):
+    def param_noise_copy_numel(self, net, ln=False):
         return 64
 
-    def param_noise_refresh(self, net, pn):
+    def param_noise_refresh(self, net, pn, ln=None):
         self.refreshes.append(dict(generation=pn.generation, acts=pn.acts, adaptive=pn.adaptive))
 
-    def synth_ddpg_population_rollout(self, net, packed, r, steps, pn, measure_step=-1, actors_per_workgroup=0):
-        self.launches.append(dict(steps=steps, measure_step=measure_step, acts=pn.acts, t=int(r['t']),
-                                  actors_per_workgroup=actors_per_workgroup))
-        self.synth_ddpg_rollout(net, packed, r, steps, actors_per_workgroup)
+    def synth_ddpg_rollout(self, net, packed, r, steps, actors_per_workgroup=0, pn=None, measure_step=-1):
+        if pn is not None:
+            self.launches.append(dict(steps=steps, measure_step=measure_step, acts=pn.acts, t=int(r['t']),
+                                      actors_per_workgroup=actors_per_workgroup))
+        super().synth_ddpg_rollout(net, packed, r, steps, actors_per_workgroup)
 
 
 @pytest.fixture
@@ -179,15 +180,56 @@ def test_attach_switches_the_agents_host_noise_off(K):
 
 def test_new_argument_blocks_match_their_ctypes_mirrors(tmp_path):
     from surreal_amd import _lib as L
-    for cname, cls in (('struct smx_param_noise', L.ParamNoise),
-                       ('struct smx_ddpg_population_rollout', L.DdpgPopulationRollout)):
-        got = H._offsets(tmp_path, cname, cls)
+    for cname, cls in (('struct smx_param_noise', L.ParamNoise), ('struct smx_ddpg_actor_variant', L.DdpgActorVariant),
+                       ('smx_ddpg_rollout_t', L.DdpgRollout)):
+        sub = tmp_path / cname.split()[-1]
+        sub.mkdir()
+        got = H._offsets(sub, cname, cls)
         assert got['sizeof'] == ctypes.sizeof(cls), cname
         for f, _ in cls._fields_:
             assert got[f] == getattr(cls, f).offset, (cname, f)
-    # smx_ddpg_rollout_t comes first and is what it was: `mon` its last member
-    assert L.DdpgPopulationRollout.base.offset == 0 and L.DdpgRollout._fields_[-1][0] == 'mon'
-    assert ctypes.sizeof(L.DdpgRollout) == L.DdpgPopulationRollout.packed_pop.offset
+    # smx_ddpg_rollout_t is what it was, `mon` its last member: the variant travels beside it, not behind it
+    assert L.DdpgRollout._fields_[-1][0] == 'mon'
+    assert L.DdpgRollout.mon.offset + ctypes.sizeof(L.EpisodeMonitor) == ctypes.sizeof(L.DdpgRollout)
+
+
+SMX_E_NULL, SMX_E_SHAPE, SMX_E_ALIGN = -1, -2, -5
+
+
+def test_actor_variant_is_refused_before_any_launch():
+    """the one rollout entry point's checks of struct smx_ddpg_actor_variant (host side: no GPU needed, and nothing a
+    launch could succeed on -- every pointer is a fake)"""
+    from surreal_amd import _lib as L
+    lib = L.load()
+    fake = ctypes.c_void_p(4096)
+    net = L.Mlp3()
+    for f in ('W1', 'b1', 'W2', 'b2', 'W3', 'b3'):
+        setattr(net, f, fake)
+    net.D, net.H1, net.H2, net.OUT = 17, 300, 200, 6      # (1000 LayerNorm floats: the two copies differ in size)
+    p = L.DdpgRollout()
+    for f in ('packed', 'state', 'init_state', 'gpow', 'carry_obs', 'carry_act', 'carry_rew', 'obs', 'obs_next',
+              'actions', 'rewards', 'dones'):
+        setattr(p, f, fake)
+    p.net = ctypes.pointer(net)
+    p.n, p.D, p.A, p.steps, p.n_step, p.episode_len, p.capacity = 8, 17, 6, 9, 3, 11, 4096
+
+    def rc(**fields):
+        v = L.DdpgActorVariant()
+        for k, x in fields.items():
+            setattr(v, k, x)
+        return lib.smx_synth_ddpg_rollout_f32(ctypes.byref(p), ctypes.byref(v), None)
+    copy = {ln: lib.smx_param_noise_copy_floats(17, 300, 200, 6, ln) for ln in (0, 1)}
+    assert copy[1] > copy[0] > 0
+    pop = dict(packed_pop=fake, actors_per_agent=4, agents=2, measure_step=-1, packed_stride=copy[1])
+    assert rc(ln=fake, ln_eps=0.0) == SMX_E_SHAPE and rc(ln=fake, ln_eps=-1e-5) == SMX_E_SHAPE
+    assert rc(ln=ctypes.c_void_p(4098), ln_eps=1e-5) == SMX_E_ALIGN
+    # the stride bound is that of the ln actually passed
+    assert rc(**dict(pop, packed_stride=copy[0] - 4)) == SMX_E_SHAPE
+    assert rc(**dict(pop, packed_stride=copy[1] - 4, ln=fake, ln_eps=1e-5)) == SMX_E_SHAPE
+    # (a plain population takes the plain copy's stride: it gets as far as the next check, the copies' alignment)
+    assert copy[1] - 4 >= copy[0] and rc(**dict(pop, packed_stride=copy[0], packed_pop=ctypes.c_void_p(4104))) == SMX_E_ALIGN
+    assert rc(**dict(pop, measure_step=0)) == SMX_E_NULL and rc(**dict(pop, measure_step=0, ln=fake, ln_eps=1e-5)) == SMX_E_NULL
+    assert rc(**dict(pop, agents=3)) == SMX_E_SHAPE and rc(**dict(pop, actors_per_agent=8)) == SMX_E_SHAPE
 
 
 def test_restatement_uses_the_fixed_fourth_counter_word():
