@@ -23,6 +23,14 @@ def _f(x):
 class TorchCpuKernels(object):
     name = 'torch-cpu-double'
 
+    @staticmethod
+    def lib_supported(query, *dims):
+        """a shape predicate of the one-launch rollouts: the library's own query.  It is host arithmetic (the widths, D
+        and the LDS layout against its budget) that loads and runs without a GPU, so the doubles' host logic routes a
+        shape exactly as the HIP tier does (test_rollout_envelope_cpu.py holds the two equal over a grid)"""
+        from surreal_amd import _lib as L
+        return bool(getattr(L.load(), query)(*[int(d) for d in dims]))
+
     # ---- z-filter -----------------------------------------------------------------------
     def zfilter_stats(self, rs, rsq, cnt, eps, mean_out, std_out):
         mean = rs / cnt
@@ -375,7 +383,9 @@ class TorchCpuKernels(object):
             dst[a] = ((base + shift) % 256).to(torch.uint8)
 
     def synth_rollout_supported(self, net):
-        return False                 # the double walks the rollout step by step (SyntheticVecEnv's layered path)
+        # NOT smx_synth_rollout_supported's mirror: the double has no synth_rollout to route to, so a plain-MLP rollout
+        # walks SyntheticVecEnv's layered per-step path at every shape (the other one-launch predicates are the library's)
+        return False
 
     def reward_filter(self, rewards, scale, state, eps, out, partials, ticket, use_filter=True, update=True, sums=None):
         x = rewards * _f(scale)

@@ -46,9 +46,6 @@ class DdpgLnRolloutCpuKernels(TP.ParamNoiseCpuKernels):
         super().__init__(*a, **kw)
         self.ln_launches, self.ln_refreshes = [], []
 
-    def synth_ddpg_rollout_supported(self, net, ln=False):
-        return super().synth_ddpg_rollout_supported(net)
-
     def _mu_ln(self, net, W, ln, eps, state):
         F = torch.nn.functional
         H1, H2 = net.H1, net.H2

@@ -24,9 +24,8 @@ class DdpgRolloutCpuKernels(TorchCpuKernels):
     name = 'torch-cpu-double+ddpg-rollout'
     ddpg_ln_launch = False        # (kernels.ddpg_ln_launch: no LayerNorm actor in the launch; the camera double inherits it)
 
-    def synth_ddpg_rollout_supported(self, net):
-        return (net.OUT <= 32 and net.H1 % 4 == 0 and net.H2 % 4 == 0 and net.H1 <= 640 and net.H2 <= 640
-                and net.D <= 512)
+    def synth_ddpg_rollout_supported(self, net, ln=False):
+        return self.lib_supported('smx_synth_ddpg_rollout_supported', net.D, net.H1, net.H2, net.OUT, bool(ln))
 
     def _mu_rows(self, net, W, b, state):
         F = torch.nn.functional

@@ -24,9 +24,10 @@ class LstmRolloutCpuKernels(TorchCpuKernels):
         self.lstm_launches = 0
 
     def synth_lstm_rollout_supported(self, model):
-        a = model.actor
-        return (model.if_rnn and model.rnn_layers == 1 and not model.if_pixel and a.D == model.rnn.H
-                and model.rnn.H <= 128 and a.OUT <= 32 and a.H1 % 4 == 0 and a.H2 % 4 == 0)
+        if not model.if_rnn or model.rnn_layers != 1 or model.if_pixel:
+            return False
+        a, r = model.actor, model.rnn
+        return a.D == r.H and self.lib_supported('smx_synth_lstm_rollout_supported', r.D, r.H, a.H1, a.H2, a.OUT)
 
     def lstm_rollout_packed_numel(self, lstm):
         return 4

@@ -30,12 +30,12 @@ class PpoWindowCpuKernels(LC.LstmRolloutCpuKernels):
         self.window_launches = 0
 
     def synth_ppo_window_rollout_supported(self, model):
-        if model.if_pixel:
+        if model.if_pixel or (model.if_rnn and model.rnn_layers != 1):
             return False
-        if model.if_rnn:
-            return self.synth_lstm_rollout_supported(model)
-        a = model.actor
-        return a.OUT <= 32 and a.H1 % 4 == 0 and a.H2 % 4 == 0 and a.H1 <= 640 and a.H2 <= 640 and a.D <= 512
+        a, r = model.actor, model.rnn
+        if not model.if_rnn:
+            return self.lib_supported('smx_synth_ppo_window_rollout_supported', a.D, 0, a.H1, a.H2, a.OUT)
+        return a.D == r.H and self.lib_supported('smx_synth_ppo_window_rollout_supported', r.D, r.H, a.H1, a.H2, a.OUT)
 
     def _act_step(self, model, state, h, c, noise_scale, eps_s, zfilter):
         """act_batch's ops for all actors -> (actions, pd, h', c')"""
