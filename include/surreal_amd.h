@@ -886,7 +886,7 @@ int smx_ddpg_stats_f32(const float* q, const float* y, const float* rewards,
                        const float* actions, int32_t ld_act, int32_t A, const float* q_actor,
                        int64_t rows, float* stats, smx_stream_t stream);
 
-/* --- one DDPG iteration on ROW BLOCKS (round 5; surreal/learner/ddpg.py:244-352, low-dimensional observations, one critic) ---
+/* --- one DDPG iteration on ROW BLOCKS (round 5; surreal/learner/ddpg.py:244-352, low-dimensional observations, one critic or TD3's two) ---
  * The layer-by-layer schedule above is ~19 dependent launches of 512-row problems.  Batch rows are independent up to the
  * weight gradients, so a workgroup carries FOUR rows through whole chains (round 6: the v_mfma_f32_4x4x1 loop of the
  * rollout kernel, the chain as a table of layer steps in the kernel arguments; the learner uses it up to 1024 rows per rank):
@@ -900,10 +900,34 @@ int smx_ddpg_stats_f32(const float* q, const float* y, const float* rewards,
  * launches declared above around smx_ddpg_rows_update_f32 (several), on the same row-major buffers.  Weights are read from a copy in MFMA fragment order (`packed`,
  * smx_ddpg_rows_packed_floats floats, 16-byte aligned) which smx_ddpg_rows_pack_f32 refreshes from the row-major
  * parameters: every network (SMX_DDPG_PACK_ALL) or the critic's blocks only.  xcat / dxcat have row stride c1 + A.
- * H1, H2, c1, c2 multiples of 4, A <= 32: smx_ddpg_rows_supported; otherwise SMX_E_UNSUPPORTED. */
+ * H1, H2, c1, c2 multiples of 4, A <= 32: smx_ddpg_rows_supported; otherwise SMX_E_UNSUPPORTED.
+ *
+ * TD3 (ddpg.py:119-147, 266-283, 312-319: use_double_critic, use_action_regularization) on the same rows: args->second
+ * names the second critic, its target, a packed buffer of their own (smx_ddpg_rows_second_packed_floats floats: critic 2's
+ * W1, W2, W3 and the first c1 rows of W2^T, target critic 2's W1, W2, W3; refreshed by SMX_DDPG_PACK_SECOND) and its
+ * row-major buffers.  NULL: one critic, everything below as before.
+ *   smx_ddpg_rows_critic_td3_f32  mu'(s'); Q1'(s', mu') and Q2'(s', clamp(mu' + noise, -1, 1)) (noise [rows, A] or NULL:
+ *                             the second target alone sees it, fp32 add then clamp); y = min(y1, y2), each formed as
+ *                             above (-> y; q_next = Q1', q_next2 = min(Q1', Q2')); *step += 1 once; per critic k:
+ *                             Qk(s, a), dz3_k = 2 (Qk - y) / rows and its data gradients; mu(s) for the actor phase
+ *   smx_ddpg_rows_actor_f32   unchanged: the actor goes through the first critic only (ddpg.py:325-328)
+ *   SMX_DDPG_GROUP_CRITIC2    the second critic's step in smx_ddpg_rows_update_f32 / _wgrad_update_f32 (dxcat2 / dz2_2 /
+ *                             dz3_2 against x / xcat2 / h2c2), its target and both copies inside packed2
+ * With second->stats2 the statistics workgroup also forms a second block as smx_ddpg_stats_f32 would for (q2, y) (the
+ * reference reports the second critic's loss and Q_policy2); update->stats_host is then [2][16]: slot (*step & 1), the
+ * first block in words 0 .. 6, the second in words 8 .. 14.
+ * smx_ddpg_rows_second_supported: the shapes' LDS budget with y kept between the two losses, and every row-major buffer
+ * of `rows` rows within the 31-bit byte offsets the launches address them by. */
 typedef struct smx_ddpg_net {          /* nn.Linear layouts: W [out, in] row-major */
     const float *W1, *b1, *W2, *b2, *W3, *b3;
 } smx_ddpg_net_t;
+struct smx_ddpg_rows_second {
+    smx_ddpg_net_t critic2, target_critic2;
+    float* packed2;
+    const float* noise;                                        /* [rows, A] or NULL */
+    float *xcat2, *h2c2, *q2, *q_next2, *dz3_2, *dz2_2, *dxcat2;   /* critic phase, out (xcat2 / dxcat2: row stride c1 + A) */
+    float* stats2;                                             /* [7] or NULL */
+};
 typedef struct smx_ddpg_rows {
     int64_t rows;
     int32_t D, A, H1, H2, c1, c2;      /* actor D -> H1 -> H2 -> A (tanh); critic D -> c1, [c1 | A] -> c2 -> 1 */
@@ -915,8 +939,9 @@ typedef struct smx_ddpg_rows {
     float *h1a, *h2a, *act;                                    /* critic phase out, actor phase in */
     float *q_actor, *dz3a, *dz2a, *dz1a;                       /* actor phase, out */
     int32_t* step;                                             /* device Adam step counter (may be NULL) */
+    const struct smx_ddpg_rows_second* second;                 /* TD3's second critic; NULL: one critic */
 } smx_ddpg_rows_t;
-enum { SMX_DDPG_PACK_ALL = 0, SMX_DDPG_PACK_CRITIC = 1 };
+enum { SMX_DDPG_PACK_ALL = 0, SMX_DDPG_PACK_CRITIC = 1, SMX_DDPG_PACK_SECOND = 2 };   /* ALL / CRITIC: args->packed only */
 int32_t smx_ddpg_rows_supported(int32_t D, int32_t A, int32_t H1, int32_t H2, int32_t c1, int32_t c2);   /* on 4-row blocks */
 /* ... for a batch of `rows` (the same answer for every row count since the 16-row kernels of round 5 are gone) */
 int32_t smx_ddpg_rows_supported_at(int32_t D, int32_t A, int32_t H1, int32_t H2, int32_t c1, int32_t c2, int64_t rows);
@@ -924,6 +949,9 @@ int64_t smx_ddpg_rows_packed_floats(int32_t D, int32_t A, int32_t H1, int32_t H2
 int smx_ddpg_rows_pack_f32(const smx_ddpg_rows_t* args, int32_t which, smx_stream_t stream);
 int smx_ddpg_rows_critic_f32(const smx_ddpg_rows_t* args, smx_stream_t stream);
 int smx_ddpg_rows_actor_f32(const smx_ddpg_rows_t* args, smx_stream_t stream);
+int32_t smx_ddpg_rows_second_supported(int32_t D, int32_t A, int32_t H1, int32_t H2, int32_t c1, int32_t c2, int64_t rows);
+int64_t smx_ddpg_rows_second_packed_floats(int32_t D, int32_t A, int32_t H1, int32_t H2, int32_t c1, int32_t c2);
+int smx_ddpg_rows_critic_td3_f32(const smx_ddpg_rows_t* args, smx_stream_t stream);
 
 /* One optimiser group's step of the row schedule in ONE launch (round 6): Adam exactly as smx_adam_step_dev_f32
  * (torch.optim.Adam after clip_grad_value_: ddpg.py:310-311, 332-333), then the group's target network -- soft
@@ -946,7 +974,7 @@ typedef struct smx_ddpg_update {
     float* stats_host;                 /* with stats, may be NULL: device-accessible HOST memory [2][8]; the same seven words also
                                           go to slot (*step & 1) -- the caller reads them after the launch without a copy */
 } smx_ddpg_update_t;
-enum { SMX_DDPG_GROUP_ACTOR = 0, SMX_DDPG_GROUP_CRITIC = 1 };
+enum { SMX_DDPG_GROUP_ACTOR = 0, SMX_DDPG_GROUP_CRITIC = 1, SMX_DDPG_GROUP_CRITIC2 = 2 };
 int smx_ddpg_rows_update_f32(const smx_ddpg_rows_t* args, int32_t group, const smx_ddpg_update_t* update,
                              smx_stream_t stream);
 /* The same step with the group's weight gradients formed in the SAME launch (one rank: nothing to exchange between them):

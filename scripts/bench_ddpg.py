@@ -1,9 +1,28 @@
 """DDPG secondary metric: samples/sec = 512 / wall(sample + learn) at
 BASELINE configs[2] (HalfCheetah shapes D=17, A=6, uniform replay, batch 512), device-resident
-replay shard; and the oracle (reference ATen path) on the host CPU beside it."""
-import sys, os, time, copy
+replay shard; and the oracle (reference ATen path) on the host CPU beside it.
+
+    --td3                          use_double_critic + use_action_regularization
+    --row-schedule on|off|unset    session_config.learner.ddpg_row_schedule (unset: the learner's own choice)
+    --ab NAME[,NAME...]            timing rounds only, the named variants interleaved inside every round -- td3_layers, td3_rows,
+                                   plain (the default learner): --rounds rounds of --calls learn() calls each, one JSON line per
+                                   variant (ms per call of every round, their median, min and max) appended to --jsonl
+    --tree PATH                    import surreal_amd from another checkout (the parent commit beside this one, same job)
+    --label TEXT                   goes into the JSON lines
+"""
+import argparse, json, sys, os, time, copy
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, 'tests')); sys.path.insert(0, os.path.join(ROOT, 'oracle'))
+ap = argparse.ArgumentParser()
+ap.add_argument('--td3', action='store_true')
+ap.add_argument('--row-schedule', choices=['on', 'off', 'unset'], default='unset')
+ap.add_argument('--ab', default='')
+ap.add_argument('--rounds', type=int, default=5)
+ap.add_argument('--calls', type=int, default=300)
+ap.add_argument('--jsonl', default='')
+ap.add_argument('--tree', default=ROOT)
+ap.add_argument('--label', default='')
+opt = ap.parse_args()
+sys.path.insert(0, os.path.abspath(opt.tree)); sys.path.insert(0, os.path.join(ROOT, 'tests')); sys.path.insert(0, os.path.join(ROOT, 'oracle'))
 import numpy as np
 import torch
 from surreal_amd import synthetic
@@ -11,8 +30,47 @@ from surreal_amd.main.ddpg_configs import ddpg_learner_config, ddpg_env_config, 
 from surreal_amd.learner.ddpg import DDPGLearner
 
 B, D, A = 512, 17, 6
-lc = ddpg_learner_config(); lc.replay.batch_size = B
-L = DDPGLearner(lc, ddpg_env_config(D, A), ddpg_session_config())
+
+
+def make_learner(td3, row_schedule):
+    lc = ddpg_learner_config(); lc.replay.batch_size = B
+    lc.algo.network.use_double_critic = lc.algo.network.use_action_regularization = bool(td3)
+    sc = ddpg_session_config()
+    if row_schedule != 'unset':
+        sc.learner['ddpg_row_schedule'] = row_schedule == 'on'
+    return lc, DDPGLearner(lc, ddpg_env_config(D, A), sc)
+
+
+if opt.ab:
+    variants = {'td3_layers': (True, 'off'), 'td3_rows': (True, 'on'), 'plain': (False, 'unset')}
+    names = [n for n in opt.ab.split(',') if n]
+    learners = {n: make_learner(*variants[n])[1] for n in names}
+    batches = {n: [learners[n].preprocess(synthetic.make_ddpg_batch(B, D, A, seed=s)) for s in range(8)] for n in names}
+    for n in names:
+        for i in range(20): learners[n].learn(batches[n][i % 8])
+    torch.cuda.synchronize()
+    ms = {n: [] for n in names}
+    for r in range(opt.rounds):
+        for n in names:
+            L, bs = learners[n], batches[n]
+            for i in range(10): L.learn(bs[i % 8])
+            torch.cuda.synchronize(); t0 = time.perf_counter()
+            for i in range(opt.calls): L.learn(bs[i % 8])
+            torch.cuda.synchronize(); ms[n].append((time.perf_counter() - t0) / opt.calls * 1e3)
+    for n in names:
+        L = learners[n]
+        rec = {'variant': n, 'label': opt.label, 'batch': B, 'D': D, 'A': A, 'calls_per_round': opt.calls, 'rounds': opt.rounds,
+               'schedule': L._schedule(B, D), 'graph': L._ws.graph is not None, 'ms_per_learn_rounds': [round(v, 5) for v in ms[n]],
+               'ms_per_learn_median': round(float(np.median(ms[n])), 5), 'ms_min': round(min(ms[n]), 5), 'ms_max': round(max(ms[n]), 5)}
+        line = json.dumps(rec)
+        print(line)
+        if opt.jsonl:
+            with open(opt.jsonl, 'a') as f:
+                f.write(line + '\n')
+    sys.exit(0)
+
+lc, L = make_learner(opt.td3, opt.row_schedule)
+print('schedule: %s (td3 %s, ddpg_row_schedule %s)' % (L._schedule(B, D), opt.td3, opt.row_schedule))
 batches = [L.preprocess(synthetic.make_ddpg_batch(B, D, A, seed=s)) for s in range(8)]
 for i in range(20): L.learn(batches[i % 8])
 torch.cuda.synchronize(); t0 = time.perf_counter(); n = 300
@@ -53,7 +111,9 @@ print('DDPG sample(512 of 1e6) + learn: %.3f ms/iter  %.3g samples/s  (hipGraph 
 try:
     import ddpg_oracle
     params = ddpg_oracle.make_ddpg_params(D, A, (300, 200), (400, 300), seed=3)
-    O = ddpg_oracle.OracleDDPGLearner(params, A) if hasattr(ddpg_oracle, 'OracleDDPGLearner') else None
+    td3 = dict(use_double_critic=True, use_action_regularization=True, batch_size=B,
+               params2=ddpg_oracle.make_ddpg_params(D, A, (300, 200), (400, 300), seed=4)) if opt.td3 else {}
+    O = ddpg_oracle.OracleDDPGLearner(params, A, **td3) if hasattr(ddpg_oracle, 'OracleDDPGLearner') else None
     if O is not None:
         hb = [synthetic.make_ddpg_batch(B, D, A, seed=s) for s in range(8)]
         for i in range(5): O.learn(copy.deepcopy(hb[i % 8]))

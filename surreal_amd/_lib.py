@@ -130,6 +130,13 @@ class DdpgUpdate(Structure):
                 [(n, c_float) for n in ('weight_decay', 'clip_value', 'tau')] + [('interval', c_int32), ('stats', c_void_p), ('stats_host', c_void_p)])
 
 
+class DdpgRowsSecond(Structure):
+    """struct smx_ddpg_rows_second"""
+    _fields_ = ([(n, DdpgNet) for n in ('critic2', 'target_critic2')] +
+                [(n, c_void_p) for n in ('packed2', 'noise', 'xcat2', 'h2c2', 'q2', 'q_next2', 'dz3_2', 'dz2_2', 'dxcat2',
+                                         'stats2')])
+
+
 class DdpgRows(Structure):
     """smx_ddpg_rows_t"""
     _fields_ = ([('rows', c_int64)] + [(n, c_int32) for n in ('D', 'A', 'H1', 'H2', 'c1', 'c2')] +
@@ -137,7 +144,8 @@ class DdpgRows(Structure):
                 [(n, c_void_p) for n in ('packed', 'x', 'x_next', 'actions', 'rewards', 'dones')] +
                 [('gamma_n', c_float)] +
                 [(n, c_void_p) for n in ('xcat', 'h2c', 'q', 'q_next', 'y', 'dz3', 'dz2', 'dxcat', 'h1a', 'h2a', 'act',
-                                         'q_actor', 'dz3a', 'dz2a', 'dz1a', 'step')])
+                                         'q_actor', 'dz3a', 'dz2a', 'dz1a', 'step')] +
+                [('second', POINTER(DdpgRowsSecond))])
 
 
 class GatherJob(Structure):
@@ -385,6 +393,9 @@ _SIGS = {
     'smx_ddpg_rows_pack_f32': (c_int32, [_P, c_int32, _P]),
     'smx_ddpg_rows_critic_f32': (c_int32, [_P, _P]),
     'smx_ddpg_rows_actor_f32': (c_int32, [_P, _P]),
+    'smx_ddpg_rows_second_supported': (c_int32, [c_int32] * 6 + [c_int64]),
+    'smx_ddpg_rows_second_packed_floats': (c_int64, [c_int32] * 6),
+    'smx_ddpg_rows_critic_td3_f32': (c_int32, [_P, _P]),
     'smx_ddpg_rows_update_f32': (c_int32, [_P, c_int32, _P, _P]),
     'smx_ddpg_rows_wgrad_update_f32': (c_int32, [_P, c_int32, _P, _P]),
     'smx_ddpg_stats_f32': (c_int32, [_P, _P, _P, _P, c_int32, c_int32, _P, c_int64, _P, _P]),

@@ -13,6 +13,16 @@
 //                             gradients dz2, dz1
 //   ddpg_rows_wgrad_update    the same for the actor;  [statistics: smx_ddpg_stats_f32]
 //
+// TD3 (ddpg.py:119-147, 266-283, 312-319: a second critic, clipped noise on the target policy's action) is the same
+// schedule with a longer first chain and one more group:
+//
+//   ddpg_rows4_kernel<2>      target actor -> both target critics (the second at the noised, clamped action);  y = min of
+//                             the two Bellman targets;  each critic's Q(s, a), dLoss/dQ against that y and data gradients;
+//                             the actor's forward pass (20 layers; td3_critic_program)
+//   ddpg_rows_wgrad_update    critic 1;  ddpg_rows_wgrad_update  critic 2 (its blocks live in a packed buffer of their own)
+//   ddpg_rows4_kernel<1>      unchanged: the actor goes through critic 1 only
+//   ddpg_rows_wgrad_update    the actor;  [statistics: a second block for (q2, y) by the same workgroup]
+//
 // Activations and gradients that the weight-gradient launches read go to HBM row-major, exactly the buffers of the
 // layer-by-layer schedule.  Products are summed in the MFMA loop's order (32-wide K chunks, k ascending per lane group),
 // not in smx_linear_f32's: results agree with the layered schedule to fp32 rounding, not bit for bit.
@@ -76,6 +86,13 @@ struct RArgs {
     // LDS carve-up (float offsets)
     int ldx, ldA, ldB, ldC, oX, oXn, oA, oB, oC, oO, oO2, oO3, oZ, oS, oR, total;
     long long* tbuf;              // SMX_DDPG_TIMING builds
+    // TD3 (ddpg_rows4_kernel<2> only): the second critic and its target, the clipped noise of the target policy's action
+    RNet c2n, tc2;
+    PMat c2W2Tlo;
+    const float* c2W3;                    // the second critic's output layer, row-major [c2]
+    const float* noise;                   // [rows][A] or null
+    float *xcat2, *h2c2, *q2, *q_next2, *dz3_2, *dz2_2, *dxcat2;
+    int oY;                               // the Bellman target, kept for the second critic's loss
 };
 
 __device__ __forceinline__ void zero_lds(int total) {
@@ -107,8 +124,8 @@ __device__ __forceinline__ void stage_rows(const float* __restrict__ src, int ld
 //    wavefronts instead of leaving 64 - 80 dependent products to one: a wave takes ceil(C2 / 8) chunks, the eight partial
 //    sums meet through LDS in wave order (k ascending inside a wave's chunks: a fixed order, not the full-K order)
 // ---------------------------------------------------------------------------------------------------------------
-enum { P_NONE = 0, P_TC_CAT, P_C_CAT, P_LOSS, P_A_CAT, P_A_DQ, P_A_TANH };
-constexpr int MAX_STEPS = 13;
+enum { P_NONE = 0, P_TC_CAT, P_C_CAT, P_LOSS, P_A_CAT, P_A_DQ, P_A_TANH, P_TC2_CAT, P_C2_CAT, P_LOSS2 };
+constexpr int MAX_STEPS = 20;        // the TD3 critic chain
 
 struct Step {
     const float* W;               // packed weights
@@ -120,6 +137,7 @@ struct Prog {
     int n;
     Step s[MAX_STEPS];
 };
+static_assert(sizeof(RArgs) + sizeof(Prog) < 4096, "both go by value in the kernel arguments");
 
 #ifdef SMX_DDPG_TIMING
 #define PSTAMP(k, i) do { if (G.tbuf && threadIdx.x == 0) G.tbuf[(size_t)blockIdx.x * 128 + 16 + 5 * (k) + (i)] = (long long)__builtin_readcyclecounter(); } while (0)
@@ -127,6 +145,8 @@ struct Prog {
 #define PSTAMP(k, i) do { } while (0)
 #endif
 
+// PHASE 0: the critic chain, 1: the actor chain, 2: the critic chain of TD3 (two critics, y = min of their targets; its
+// rules exist in that instantiation only)
 template <int PHASE>
 __global__ __launch_bounds__(DNTH) void ddpg_rows4_kernel(RArgs G, Prog P) {
     extern __shared__ float sm[];
@@ -143,7 +163,7 @@ __global__ __launch_bounds__(DNTH) void ddpg_rows4_kernel(RArgs G, Prog P) {
     __syncthreads();
     stage_rows(G.x, G.D, G.D, row0, nrows, G.oX, G.ldx);
     float rew = 0.f, dn = 0.f;
-    if (PHASE == 0) {
+    if (PHASE == 0 || PHASE == 2) {
         stage_rows(G.xn, G.D, G.D, row0, nrows, G.oXn, G.ldx);
         if (tid < nrows) { rew = G.rewards[row0 + tid]; dn = G.dones[row0 + tid]; }
     } else {
@@ -295,6 +315,70 @@ __global__ __launch_bounds__(DNTH) void ddpg_rows4_kernel(RArgs G, Prog P) {
                     v = (sm[G.oB + n * G.ldB + j] > 0.f) ? v : 0.f;
                     sm[G.oA + n * G.ldA + j] = v;
                     if (n < nrows) G.dz2[(size_t)(row0 + n) * c2 + j] = v;
+                }
+                SMX_LDS_BARRIER();
+            }
+        } else if (PHASE == 2) {
+            if (post == P_TC_CAT || post == P_TC2_CAT) {
+                // [h1' | mu'(s')] for the first target critic; the second sees the action under the clipped noise:
+                // min(max(mu' + noise, -1), 1), an fp32 add then the clamp (ddpg.py:266-283 adds it after Q1' was formed)
+                if (tid < RB * A) {
+                    const int n = tid / A, j = tid - n * A;
+                    float v = sm[G.oO + n * LDO + j];
+                    if (post == P_TC2_CAT && G.noise) {
+                        const float nz = (n < nrows) ? G.noise[(size_t)(row0 + n) * A + j] : 0.f;
+                        v = fminf(fmaxf(v + nz, -1.0f), 1.0f);
+                    }
+                    sm[G.oC + n * G.ldC + c1 + j] = v;
+                }
+                SMX_LDS_BARRIER();
+            } else if (post == P_C_CAT || post == P_C2_CAT) {      // [h1 | a] and its row-major copy, per critic
+                float* xc = post == P_C_CAT ? G.xcat : G.xcat2;
+                if (tid < RB * A) {
+                    const int n = tid / A, j = tid - n * A;
+                    const float v = (n < nrows) ? G.actions[(size_t)(row0 + n) * A + j] : 0.f;
+                    sm[G.oC + n * G.ldC + c1 + j] = v;
+                    if (n < nrows) xc[(size_t)(row0 + n) * ldc + c1 + j] = v;
+                }
+                SMX_LDS_BARRIER();
+            } else if (post == P_LOSS || post == P_LOSS2) {
+                // first critic: y = min(y1, y2) of the two targets, each formed as the one-critic rule forms it (r + t is
+                // monotone in Q': the same value as the Bellman target of min(Q1', Q2')); y stays in LDS for the second
+                const bool first = post == P_LOSS;
+                if (tid < RB) {
+                    const float q = sm[G.oO + tid * LDO];
+                    float yy;
+                    if (first) {
+                        const float qn1 = sm[G.oO2 + tid * LDO], qn2 = sm[G.oO3 + tid * LDO];
+                        const float t1 = (G.gamma_n * qn1) * (1.0f - dn), t2 = (G.gamma_n * qn2) * (1.0f - dn);
+                        const float y1 = rew + t1, y2 = rew + t2;
+                        yy = fminf(y1, y2);
+                        sm[G.oY + tid] = yy;
+                        if (tid < nrows) {
+                            G.q_next[row0 + tid] = qn1;
+                            G.q_next2[row0 + tid] = fminf(qn1, qn2);
+                            G.y[row0 + tid] = yy;
+                        }
+                    } else {
+                        yy = sm[G.oY + tid];
+                    }
+                    const float d3 = (2.0f * (q - yy)) / (float)G.rows;
+                    sm[G.oS + tid] = (tid < nrows) ? d3 : 0.f;
+                    if (tid < nrows) {
+                        (first ? G.q : G.q2)[row0 + tid] = q;
+                        (first ? G.dz3 : G.dz3_2)[row0 + tid] = d3;
+                    }
+                }
+                if (first && blockIdx.x == 0 && tid == 0 && G.step) *G.step += 1;      // ONE Adam step count for all groups
+                SMX_LDS_BARRIER();
+                const float* W3 = first ? G.cW3 : G.c2W3;
+                float* dz2 = first ? G.dz2 : G.dz2_2;
+                for (int idx = tid; idx < RB * c2; idx += DNTH) {
+                    const int n = idx / c2, j = idx - n * c2;
+                    float v = sm[G.oS + n] * W3[j];
+                    v = (sm[G.oB + n * G.ldB + j] > 0.f) ? v : 0.f;
+                    sm[G.oA + n * G.ldA + j] = v;
+                    if (n < nrows) dz2[(size_t)(row0 + n) * c2 + j] = v;
                 }
                 SMX_LDS_BARRIER();
             }
@@ -491,7 +575,9 @@ struct WUArgs {
     int rows;
     // optional: the iteration's statistics as one more workgroup of this launch (the last one of the iteration)
     float* stats;
-    float* stats_host;            // host-mapped mirror, two slots of 8 floats: slot *step & 1
+    float* stats_host;            // host-mapped mirror, two slots of 8 floats: slot *step & 1 (of 16 with a second critic)
+    float* stats2;                // TD3: a second block, as smx_ddpg_stats_f32 forms it for (q2, y)
+    const float* s_q2;
     const float *s_q, *s_y, *s_rewards, *s_actions, *s_q_actor;
     int s_A, tiles;
     long long* tbuf;              // SMX_DDPG_TIMING builds
@@ -539,9 +625,12 @@ __global__ __launch_bounds__(64 * WNW) void ddpg_rows_wgrad_update_kernel(WUArgs
     const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int i = lane & 15, g = lane >> 4;
     if ((int)blockIdx.x == G.tiles) {               // the workgroup behind the last tile: the statistics
-        float* mirror = G.stats_host ? G.stats_host + 8 * (*G.U.step & 1) : nullptr;
+        float* mirror = G.stats_host ? G.stats_host + (G.stats2 ? 16 : 8) * (*G.U.step & 1) : nullptr;
         ddpg_stats_block<64 * WNW>(G.s_q, G.s_y, G.s_rewards, G.s_actions, G.s_A, G.s_A, G.s_q_actor, (long)G.rows, G.stats,
                                    mirror);
+        if (G.stats2)
+            ddpg_stats_block<64 * WNW>(G.s_q2, G.s_y, G.s_rewards, G.s_actions, G.s_A, G.s_A, G.s_q2, (long)G.rows, G.stats2,
+                                       mirror ? mirror + 8 : nullptr);
         return;
     }
     WSTAMP(0);
@@ -715,9 +804,24 @@ long block_base(const Dims& d, int b) {          // in 16-byte words
     return o;
 }
 
+// the second critic's blocks (TD3) live in a buffer of their own, so the sixteen above stay where they are.  No W2^T hi:
+// nothing differentiates the second critic with respect to the action
+enum { B2_CW1, B2_CW2, B2_CW3, B2_CW2TLO, B2_TCW1, B2_TCW2, B2_TCW3, B2_COUNT };
+const int second_as_first[B2_COUNT] = {B_CW1, B_CW2, B_CW3, B_CW2TLO, B_TCW1, B_TCW2, B_TCW3};      // (same shapes)
+
+long block2_base(const Dims& d, int b) {         // in 16-byte words
+    long o = 0;
+    for (int k = 0; k < b; ++k) {
+        int M, K;
+        block_shape(d, second_as_first[k], M, K);
+        o += pack_words(M, K);
+    }
+    return o;
+}
+
 long long* g_tbuf = nullptr;
 
-int lds_floats(const Dims& d, RArgs* G) {
+int lds_floats(const Dims& d, RArgs* G, bool td3 = false) {
     constexpr int RB = RBLK;
     const int pad = 16;             // row strides = 16 mod 64: the 16 (row, kq) readers of the 4-row loop on distinct banks
     const int ldx = r64(d.D) + pad;
@@ -736,19 +840,20 @@ int lds_floats(const Dims& d, RArgs* G) {
     const int oZ = o; o += RB * LDK4;
     const int oS = o; o += 16;
     const int oR = o; o += DNWV * 2 * 4 * 16;      // the split-K layers' partial sums
+    const int oY = o; o += td3 ? 16 : 0;           // TD3: y between the two critics' losses
     o += 128;                     // the K loop's prefetch reads up to two chunks past a tile's last row
     if (G) {
         G->ldx = ldx; G->ldA = ldA; G->ldB = ldB; G->ldC = ldC;
         G->oX = oX; G->oXn = oXn; G->oA = oA; G->oB = oB; G->oC = oC; G->oO = oO; G->oO2 = oO2; G->oO3 = oO3;
-        G->oZ = oZ; G->oS = oS; G->oR = oR; G->total = o;
+        G->oZ = oZ; G->oS = oS; G->oR = oR; G->oY = oY; G->total = o;
     }
     return o;
 }
 
-bool dims_ok(const Dims& d) {
+bool dims_ok(const Dims& d, bool td3 = false) {
     return d.D > 0 && d.A > 0 && d.A <= 32 && d.H1 > 0 && d.H2 > 0 && d.c1 > 0 && d.c2 > 0 && d.D <= 2048 &&
            d.H1 % 4 == 0 && d.H2 % 4 == 0 && d.c1 % 4 == 0 && d.c2 % 4 == 0 && d.H1 <= 1024 && d.H2 <= 1024 &&
-           d.c1 <= 1024 && d.c2 <= 1024 && lds_floats(d, nullptr) * (int)sizeof(float) <= MAX_LDS;
+           d.c1 <= 1024 && d.c2 <= 1024 && lds_floats(d, nullptr, td3) * (int)sizeof(float) <= MAX_LDS;
 }
 
 Dims dims_of(const smx_ddpg_rows_t& a) {
@@ -764,12 +869,29 @@ PMat pmat(const smx_ddpg_rows_t& a, const Dims& d, int b) {
     return m;
 }
 
-int fill(RArgs& G, const smx_ddpg_rows_t* a) {
+// every row-major output is addressed through a buffer descriptor: 31-bit byte offsets
+bool offsets_ok(const Dims& d, int64_t rows) {
+    int widest = d.c1 + d.A;
+    widest = d.H1 > widest ? d.H1 : widest;
+    widest = d.c2 > widest ? d.c2 : widest;
+    widest = d.H2 > widest ? d.H2 : widest;
+    widest = d.D > widest ? d.D : widest;
+    return rows * widest * 4 < (1ll << 31);
+}
+
+PMat pmat2(const smx_ddpg_rows_second& s, const Dims& d, int b) {
+    PMat m;
+    block_shape(d, second_as_first[b], m.M, m.K);
+    m.P = s.packed2 + 4 * block2_base(d, b);
+    return m;
+}
+
+int fill(RArgs& G, const smx_ddpg_rows_t* a, bool td3 = false) {
     SMX_REQUIRE(a && a->packed, SMX_E_NULL);
     const Dims d = dims_of(*a);
     SMX_REQUIRE(a->rows > 0 && a->rows < (1 << 24), SMX_E_SHAPE);
-    SMX_REQUIRE(dims_ok(d), SMX_E_UNSUPPORTED);
-    {   // every row-major output is addressed through a buffer descriptor: 31-bit byte offsets
+    SMX_REQUIRE(dims_ok(d, td3), SMX_E_UNSUPPORTED);
+    {
         int widest = d.c1 + d.A;
         widest = d.H1 > widest ? d.H1 : widest;
         widest = d.c2 > widest ? d.c2 : widest;
@@ -799,8 +921,27 @@ int fill(RArgs& G, const smx_ddpg_rows_t* a) {
     G.dxcat = a->dxcat; G.h1a = a->h1a; G.h2a = a->h2a; G.act = a->act;
     G.q_actor = a->q_actor; G.dz3a = a->dz3a; G.dz2a = a->dz2a; G.dz1a = a->dz1a;
     G.step = a->step;
-    lds_floats(d, &G);
+    lds_floats(d, &G, td3);
     G.tbuf = g_tbuf;
+    if (td3) {
+        const smx_ddpg_rows_second* s = a->second;
+        SMX_REQUIRE(s && s->packed2, SMX_E_NULL);
+        SMX_REQUIRE(((uintptr_t)s->packed2 & 15) == 0, SMX_E_ALIGN);
+        SMX_REQUIRE(offsets_ok(d, a->rows), SMX_E_SHAPE);
+        const smx_ddpg_net_t* n2[2] = {&s->critic2, &s->target_critic2};
+        RNet* r2[2] = {&G.c2n, &G.tc2};
+        const int w1b[2] = {B2_CW1, B2_TCW1};
+        for (int k = 0; k < 2; ++k) {
+            SMX_REQUIRE(n2[k]->W1 && n2[k]->b1 && n2[k]->W2 && n2[k]->b2 && n2[k]->W3 && n2[k]->b3, SMX_E_NULL);
+            r2[k]->b1 = n2[k]->b1; r2[k]->b2 = n2[k]->b2; r2[k]->b3 = n2[k]->b3;
+            r2[k]->W1 = pmat2(*s, d, w1b[k]); r2[k]->W2 = pmat2(*s, d, w1b[k] + 1); r2[k]->W3 = pmat2(*s, d, w1b[k] + 2);
+        }
+        G.c2W2Tlo = pmat2(*s, d, B2_CW2TLO);
+        G.c2W3 = s->critic2.W3;
+        G.noise = s->noise;
+        G.xcat2 = s->xcat2; G.h2c2 = s->h2c2; G.q2 = s->q2; G.q_next2 = s->q_next2; G.dz3_2 = s->dz3_2;
+        G.dz2_2 = s->dz2_2; G.dxcat2 = s->dxcat2;
+    }
     return SMX_OK;
 }
 
@@ -845,7 +986,37 @@ void actor_program(const RArgs& G, Prog& P) {
     P.s[n].mask_off = G.oC; P.s[n].ldm = G.ldC; ++n;
     P.n = n;
 }
-static_assert(MAX_STEPS >= 13, "the critic chain has 13 layers");
+
+// TD3's critic chain (ddpg.py:266-283, 312-319): both target critics (the second at the noised action), then each
+// critic's forward pass, loss and data gradients against y = min(y1, y2), then the actor's forward pass
+void td3_critic_program(const RArgs& G, Prog& P) {
+    const int ldc = G.c1 + G.A;
+    int n = 0;
+    P.s[n++] = step(G.oXn, G.ldx, G.ta.W1, G.ta.b1, A_RELU, G.oA, G.ldA, nullptr, 0, P_NONE);         // mu'(s')
+    P.s[n++] = step(G.oA, G.ldA, G.ta.W2, G.ta.b2, A_RELU, G.oB, G.ldB, nullptr, 0, P_NONE);
+    P.s[n++] = step(G.oB, G.ldB, G.ta.W3, G.ta.b3, A_TANH, G.oO, LDO, nullptr, 0, P_NONE);
+    P.s[n++] = step(G.oXn, G.ldx, G.tc.W1, G.tc.b1, A_RELU, G.oC, G.ldC, nullptr, 0, P_TC_CAT);       // Q1'(s', mu'(s'))
+    P.s[n++] = step(G.oC, G.ldC, G.tc.W2, G.tc.b2, A_RELU, G.oB, G.ldB, nullptr, 0, P_NONE);
+    P.s[n++] = step(G.oB, G.ldB, G.tc.W3, G.tc.b3, A_NONE, G.oO2, LDO, nullptr, 0, P_NONE);
+    P.s[n++] = step(G.oXn, G.ldx, G.tc2.W1, G.tc2.b1, A_RELU, G.oC, G.ldC, nullptr, 0, P_TC2_CAT);    // Q2'(s', clamp(mu' + noise))
+    P.s[n++] = step(G.oC, G.ldC, G.tc2.W2, G.tc2.b2, A_RELU, G.oB, G.ldB, nullptr, 0, P_NONE);
+    P.s[n++] = step(G.oB, G.ldB, G.tc2.W3, G.tc2.b3, A_NONE, G.oO3, LDO, nullptr, 0, P_NONE);
+    P.s[n++] = step(G.oX, G.ldx, G.c.W1, G.c.b1, A_RELU, G.oC, G.ldC, G.xcat, ldc, P_C_CAT);          // Q1(s, a)
+    P.s[n++] = step(G.oC, G.ldC, G.c.W2, G.c.b2, A_RELU, G.oB, G.ldB, G.h2c, G.c2, P_NONE);
+    P.s[n++] = step(G.oB, G.ldB, G.c.W3, G.c.b3, A_NONE, G.oO, LDO, nullptr, 0, P_LOSS);              // -> y, dz3, dz2
+    P.s[n] = step(G.oA, G.ldA, G.cW2Tlo, nullptr, A_MASK, -1, 0, G.dxcat, ldc, P_NONE);               // dz1
+    P.s[n].mask_off = G.oC; P.s[n].ldm = G.ldC; ++n;
+    P.s[n++] = step(G.oX, G.ldx, G.c2n.W1, G.c2n.b1, A_RELU, G.oC, G.ldC, G.xcat2, ldc, P_C2_CAT);    // Q2(s, a)
+    P.s[n++] = step(G.oC, G.ldC, G.c2n.W2, G.c2n.b2, A_RELU, G.oB, G.ldB, G.h2c2, G.c2, P_NONE);
+    P.s[n++] = step(G.oB, G.ldB, G.c2n.W3, G.c2n.b3, A_NONE, G.oO, LDO, nullptr, 0, P_LOSS2);         // -> its dz3, dz2 (kept y)
+    P.s[n] = step(G.oA, G.ldA, G.c2W2Tlo, nullptr, A_MASK, -1, 0, G.dxcat2, ldc, P_NONE);
+    P.s[n].mask_off = G.oC; P.s[n].ldm = G.ldC; ++n;
+    P.s[n++] = step(G.oX, G.ldx, G.a.W1, G.a.b1, A_RELU, G.oA, G.ldA, G.h1a, G.H1, P_NONE);           // mu(s), kept
+    P.s[n++] = step(G.oA, G.ldA, G.a.W2, G.a.b2, A_RELU, G.oB, G.ldB, G.h2a, G.H2, P_NONE);
+    P.s[n++] = step(G.oB, G.ldB, G.a.W3, G.a.b3, A_TANH, -1, 0, G.act, G.A, P_NONE);
+    P.n = n;
+}
+static_assert(MAX_STEPS >= 20, "the TD3 critic chain has 20 layers");
 
 int set_lds(const void* fn, int bytes) {
     return (int)hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
@@ -874,10 +1045,54 @@ extern "C" int64_t smx_ddpg_rows_packed_floats(int32_t D, int32_t A, int32_t H1,
     return dims_ok(d) ? 4 * block_base(d, B_COUNT) : 0;
 }
 
+extern "C" int32_t smx_ddpg_rows_second_supported(int32_t D, int32_t A, int32_t H1, int32_t H2, int32_t c1, int32_t c2,
+                                                  int64_t rows) {
+    Dims d;
+    d.D = D; d.A = A; d.H1 = H1; d.H2 = H2; d.c1 = c1; d.c2 = c2;
+    return rows > 0 && rows < (1 << 24) && dims_ok(d, true) && offsets_ok(d, rows) ? 1 : 0;
+}
+
+extern "C" int64_t smx_ddpg_rows_second_packed_floats(int32_t D, int32_t A, int32_t H1, int32_t H2, int32_t c1, int32_t c2) {
+    Dims d;
+    d.D = D; d.A = A; d.H1 = H1; d.H2 = H2; d.c1 = c1; d.c2 = c2;
+    return dims_ok(d, true) ? 4 * block2_base(d, B2_COUNT) : 0;
+}
+
+namespace {
+// the second critic's seven blocks into ITS packed buffer
+int pack_second(const smx_ddpg_rows_t* a, const Dims& d, smx_stream_t stream) {
+    const smx_ddpg_rows_second* s = a->second;
+    SMX_REQUIRE(s && s->packed2, SMX_E_NULL);
+    SMX_REQUIRE(dims_ok(d, true), SMX_E_UNSUPPORTED);
+    SMX_REQUIRE(((uintptr_t)s->packed2 & 15) == 0, SMX_E_ALIGN);
+    const int ldc = d.c1 + d.A;
+    const float* src[B2_COUNT] = {s->critic2.W1, s->critic2.W2, s->critic2.W3, s->critic2.W2,
+                                  s->target_critic2.W1, s->target_critic2.W2, s->target_critic2.W3};
+    const int ld[B2_COUNT] = {d.D, ldc, d.c2, ldc, d.D, ldc, d.c2};
+    const int tr[B2_COUNT] = {0, 0, 0, 1, 0, 0, 0};
+    PArgs P;
+    memset(&P, 0, sizeof(P));
+    P.packed = s->packed2;
+    P.count = B2_COUNT;
+    for (int b = 0; b < B2_COUNT; ++b) {
+        SMX_REQUIRE(src[b], SMX_E_NULL);
+        PItem& it = P.it[b];
+        it.src = src[b]; it.ld = ld[b]; it.tr = tr[b];
+        block_shape(d, second_as_first[b], it.M, it.K);
+        it.base = block2_base(d, b);
+    }
+    P.total = block2_base(d, B2_COUNT);
+    hipLaunchKernelGGL(ddpg_pack_kernel, dim3((unsigned)((P.total + 255) / 256)), dim3(256), 0, smx_s(stream), P);
+    SMX_LAUNCH_CHECK();
+    return SMX_OK;
+}
+}  // namespace
+
 extern "C" int smx_ddpg_rows_pack_f32(const smx_ddpg_rows_t* a, int32_t which, smx_stream_t stream) {
     SMX_REQUIRE(a && a->packed, SMX_E_NULL);
     const Dims d = dims_of(*a);
     SMX_REQUIRE(dims_ok(d), SMX_E_UNSUPPORTED);
+    if (which == SMX_DDPG_PACK_SECOND) return pack_second(a, d, stream);
     SMX_REQUIRE(which == SMX_DDPG_PACK_ALL || which == SMX_DDPG_PACK_CRITIC, SMX_E_SHAPE);
     const int ldc = d.c1 + d.A;
     const float* src[B_COUNT] = {a->actor.W1, a->actor.W2, a->actor.W3, a->actor.W3, a->actor.W2,
@@ -926,6 +1141,30 @@ extern "C" int smx_ddpg_rows_critic_f32(const smx_ddpg_rows_t* a, smx_stream_t s
     return SMX_OK;
 }
 
+extern "C" int smx_ddpg_rows_critic_td3_f32(const smx_ddpg_rows_t* a, smx_stream_t stream) {
+    RArgs G;
+    const int rc = fill(G, a, true);
+    if (rc) return rc;
+    const smx_ddpg_rows_second* s = a->second;
+    SMX_REQUIRE(a->x && a->x_next && a->actions && a->rewards && a->dones, SMX_E_NULL);
+    SMX_REQUIRE(a->xcat && a->h2c && a->q && a->q_next && a->y && a->dz3 && a->dz2 && a->dxcat && a->h1a && a->h2a &&
+                    a->act, SMX_E_NULL);
+    SMX_REQUIRE(s->xcat2 && s->h2c2 && s->q2 && s->q_next2 && s->dz3_2 && s->dz2_2 && s->dxcat2, SMX_E_NULL);
+    const int bytes = G.total * (int)sizeof(float);
+    static int set = 0;
+    if (set < bytes) {
+        const int e = set_lds((const void*)ddpg_rows4_kernel<2>, bytes);
+        if (e) return e;
+        set = bytes;
+    }
+    Prog P;
+    memset(&P, 0, sizeof(P));
+    td3_critic_program(G, P);
+    hipLaunchKernelGGL(ddpg_rows4_kernel<2>, dim3((unsigned)((G.rows + RBLK - 1) / RBLK)), dim3(DNTH), bytes, smx_s(stream), G, P);
+    SMX_LAUNCH_CHECK();
+    return SMX_OK;
+}
+
 extern "C" int smx_ddpg_rows_actor_f32(const smx_ddpg_rows_t* a, smx_stream_t stream) {
     RArgs G;
     const int rc = fill(G, a);
@@ -949,8 +1188,36 @@ extern "C" int smx_ddpg_rows_actor_f32(const smx_ddpg_rows_t* a, smx_stream_t st
 namespace {
 int fill_update(UArgs& U, const smx_ddpg_rows_t* a, int32_t group, const smx_ddpg_update_t* u, const Dims& d) {
     SMX_REQUIRE(u->theta && u->grads && u->exp_avg && u->exp_avg_sq && u->lr && u->step, SMX_E_NULL);
-    SMX_REQUIRE(group == SMX_DDPG_GROUP_ACTOR || group == SMX_DDPG_GROUP_CRITIC, SMX_E_SHAPE);
+    SMX_REQUIRE(group == SMX_DDPG_GROUP_ACTOR || group == SMX_DDPG_GROUP_CRITIC || group == SMX_DDPG_GROUP_CRITIC2,
+                SMX_E_SHAPE);
     SMX_REQUIRE(u->n > 0 && u->interval >= 0 && (u->target == nullptr || u->interval > 0 || u->tau > 0.f), SMX_E_SHAPE);
+    if (group == SMX_DDPG_GROUP_CRITIC2) {
+        // the second critic: its own networks and packed buffer, the first critic's shapes; W2^T's low block only
+        const smx_ddpg_rows_second* s = a->second;
+        SMX_REQUIRE(s && s->packed2, SMX_E_NULL);
+        SMX_REQUIRE(dims_ok(d, true), SMX_E_UNSUPPORTED);
+        SMX_REQUIRE(s->critic2.W1 && s->critic2.W2 && s->critic2.W3, SMX_E_NULL);
+        memset(&U, 0, sizeof(U));
+        U.theta = u->theta; U.grads = u->grads; U.m = u->exp_avg; U.v = u->exp_avg_sq; U.target = u->target;
+        U.packed = s->packed2; U.n = u->n; U.lr = u->lr; U.step = u->step; U.wd = u->weight_decay;
+        U.clip_value = u->clip_value; U.tau = u->tau; U.interval = u->interval;
+        const float* W[3] = {s->critic2.W1, s->critic2.W2, s->critic2.W3};
+        const float* TW[3] = {s->target_critic2.W1, s->target_critic2.W2, s->target_critic2.W3};
+        for (int j = 0; j < 3; ++j) {
+            UMat& X = U.mat[j];
+            block_shape(d, second_as_first[B2_CW1 + j], X.M, X.K);
+            X.off = W[j] - u->theta;
+            SMX_REQUIRE(X.off >= 0 && X.off + (long)X.M * X.K <= u->n, SMX_E_SHAPE);
+            if (u->target) SMX_REQUIRE(TW[j] && TW[j] - u->target == X.off, SMX_E_SHAPE);
+            X.base = 4 * block2_base(d, B2_CW1 + j);
+            X.base_tgt = 4 * block2_base(d, B2_TCW1 + j);
+            X.base_t0 = X.base_t1 = -1;
+            X.split = X.K;
+        }
+        U.mat[1].base_t0 = 4 * block2_base(d, B2_CW2TLO);
+        U.mat[1].split = d.c1;
+        return SMX_OK;
+    }
     const bool cr = group == SMX_DDPG_GROUP_CRITIC;
     const smx_ddpg_net_t& net = cr ? a->critic : a->actor;
     const smx_ddpg_net_t& tnet = cr ? a->target_critic : a->target_actor;
@@ -1013,14 +1280,17 @@ extern "C" int smx_ddpg_rows_wgrad_update_f32(const smx_ddpg_rows_t* a, int32_t 
     G.U.grads_out = const_cast<float*>(u->grads);
     G.rows = (int)a->rows;
     G.tbuf = g_tbuf;
-    const bool cr = group == SMX_DDPG_GROUP_CRITIC;
-    const smx_ddpg_net_t& net = cr ? a->critic : a->actor;
-    const smx_ddpg_net_t& tnet = cr ? a->target_critic : a->target_actor;
+    const bool c2nd = group == SMX_DDPG_GROUP_CRITIC2;
+    const bool cr = group == SMX_DDPG_GROUP_CRITIC || c2nd;
+    const smx_ddpg_rows_second* s2 = a->second;                      // (fill_update has checked it for the second critic)
+    const smx_ddpg_net_t& net = c2nd ? s2->critic2 : cr ? a->critic : a->actor;
+    const smx_ddpg_net_t& tnet = c2nd ? s2->target_critic2 : cr ? a->target_critic : a->target_actor;
     const int ldc = d.c1 + d.A;
     // (gradient, input) of the three layers: the buffers the chain launches wrote
-    const float* dz[3] = {cr ? a->dxcat : a->dz1a, cr ? a->dz2 : a->dz2a, cr ? a->dz3 : a->dz3a};
+    const float* dz[3] = {c2nd ? s2->dxcat2 : cr ? a->dxcat : a->dz1a, c2nd ? s2->dz2_2 : cr ? a->dz2 : a->dz2a,
+                          c2nd ? s2->dz3_2 : cr ? a->dz3 : a->dz3a};
     const int ldz[3] = {cr ? ldc : d.H1, cr ? d.c2 : d.H2, cr ? 1 : d.A};
-    const float* x[3] = {a->x, cr ? a->xcat : a->h1a, cr ? a->h2c : a->h2a};
+    const float* x[3] = {a->x, c2nd ? s2->xcat2 : cr ? a->xcat : a->h1a, c2nd ? s2->h2c2 : cr ? a->h2c : a->h2a};
     const int ldx[3] = {d.D, cr ? ldc : d.H1, cr ? d.c2 : d.H2};
     const float* b[3] = {net.b1, net.b2, net.b3};
     const float* tb[3] = {tnet.b1, tnet.b2, tnet.b3};
@@ -1050,6 +1320,10 @@ extern "C" int smx_ddpg_rows_wgrad_update_f32(const smx_ddpg_rows_t* a, int32_t 
         G.stats = u->stats; G.s_q = a->q; G.s_y = a->y; G.s_rewards = a->rewards; G.s_actions = a->actions;
         G.s_q_actor = a->q_actor; G.s_A = d.A;
         G.stats_host = u->stats_host;
+        if (s2 && s2->stats2) {          // the second critic's block, (q2, y), by the same workgroup
+            SMX_REQUIRE(s2->q2, SMX_E_NULL);
+            G.stats2 = s2->stats2; G.s_q2 = s2->q2;
+        }
     }
     hipLaunchKernelGGL(ddpg_rows_wgrad_update_kernel, dim3((unsigned)(tiles + (u->stats ? 1 : 0))), dim3(64 * WNW), 0,
                        smx_s(stream), G);

@@ -22,6 +22,13 @@ def _row_stride(view, width):
     return view.stride(0) if view.shape[0] > 1 else max(view.stride(0), width)
 
 
+def ddpg_rows_td3(kernels):
+    """whether this kernels object runs TD3 (a second critic, clipped noise on the target action) on the row schedule --
+    the ddpg_rows_second_* / ddpg_rows_critic_td3 methods below: its `ddpg_rows_td3` attribute; an object without it
+    (an older CPU double) keeps a double-critic learner on the layer-by-layer schedule"""
+    return bool(getattr(kernels, 'ddpg_rows_td3', False))
+
+
 def ddpg_ln_launch(kernels):
     """whether `kernels` runs a LayerNorm DDPG actor in the one-launch rollout and under the device parameter noise
     (the ln arguments of synth_ddpg_rollout and param_noise_*): its `ddpg_ln_launch` attribute; an object without
@@ -806,6 +813,8 @@ class HipKernels(object):
 
     # a LayerNorm actor runs in the one-launch DDPG rollout and under the parameter noise (ddpg_ln_launch(), above)
     ddpg_ln_launch = True
+    # TD3 on the row schedule (ddpg_rows_td3(), above)
+    ddpg_rows_td3 = True
 
     def synth_ddpg_rollout_supported(self, net, ln=False):
         """the actor shapes synth_ddpg_rollout takes; ln: with a LayerNorm behind each hidden ReLU"""
@@ -1114,9 +1123,40 @@ class HipKernels(object):
     def ddpg_rows_actor(self, args):
         L.call('smx_ddpg_rows_actor_f32', ctypes.byref(args), self._st())
 
+    # TD3: the second critic rides in args.second (smx_ddpg_rows_second); the single-critic calls around it are unchanged
+    def ddpg_rows_second_supported(self, D, A, H1, H2, c1, c2, rows):
+        return bool(self.lib.smx_ddpg_rows_second_supported(D, A, H1, H2, c1, c2, int(rows)))
+
+    def ddpg_rows_second_packed_floats(self, D, A, H1, H2, c1, c2):
+        return int(self.lib.smx_ddpg_rows_second_packed_floats(D, A, H1, H2, c1, c2))
+
+    def ddpg_rows_second(self, args, nets2, packed2, io2):
+        """attach the second critic to a ddpg_rows_args block.  nets2: {'critic2' | 'target_critic2': {'W1' ... 'b3'}};
+        packed2: ddpg_rows_second_packed_floats floats; io2: noise (or None), xcat2, h2c2, q2, q_next2, dz3_2, dz2_2, dxcat2,
+        stats2 (or None).  Returns args."""
+        s = L.DdpgRowsSecond()
+        for name in ('critic2', 'target_critic2'):
+            n = getattr(s, name)
+            for k in ('W1', 'b1', 'W2', 'b2', 'W3', 'b3'):
+                setattr(n, k, nets2[name][k].data_ptr())
+        s.packed2 = packed2.data_ptr()
+        for k in ('noise', 'xcat2', 'h2c2', 'q2', 'q_next2', 'dz3_2', 'dz2_2', 'dxcat2', 'stats2'):
+            t = io2.get(k)
+            assert t is None or t.is_contiguous(), k
+            setattr(s, k, None if t is None else t.data_ptr())
+        args.second = ctypes.pointer(s)
+        args._refs2 = (s, nets2, packed2, io2)
+        return args
+
+    def ddpg_rows_pack_second(self, args):
+        L.call('smx_ddpg_rows_pack_f32', ctypes.byref(args), 2, self._st())
+
+    def ddpg_rows_critic_td3(self, args):
+        L.call('smx_ddpg_rows_critic_td3_f32', ctypes.byref(args), self._st())
+
     def ddpg_rows_update(self, args, group, theta, grads, exp_avg, exp_avg_sq, lr, step, weight_decay, clip_value,
                          target=None, tau=0.0, interval=0, wgrad=False, stats=None, stats_host=None):
-        """smx_ddpg_rows_update_f32 (wgrad: smx_ddpg_rows_wgrad_update_f32, which forms the gradients first): Adam on the group ('actor' | 'critic'), its target network's update (soft with tau,
+        """smx_ddpg_rows_update_f32 (wgrad: smx_ddpg_rows_wgrad_update_f32, which forms the gradients first): Adam on the group ('actor' | 'critic' | 'critic2', TD3's second), its target network's update (soft with tau,
         or hard every `interval` iterations of *step; target None: none) and the fragment-order copies of both"""
         u = L.DdpgUpdate()
         u.theta, u.grads, u.exp_avg, u.exp_avg_sq = (t.data_ptr() for t in (theta, grads, exp_avg, exp_avg_sq))
@@ -1128,10 +1168,12 @@ class HipKernels(object):
         assert stats is None or wgrad
         u.stats = None if stats is None else stats.data_ptr()
         assert stats_host is None or (stats is not None and stats_host.is_pinned() and stats_host.numel() >= 16)
+        # (a second statistics block doubles the slots: include/surreal_amd.h)
+        assert stats_host is None or not (bool(args.second) and args.second.contents.stats2) or stats_host.numel() >= 32
         u.stats_host = None if stats_host is None else stats_host.data_ptr()
         u.weight_decay, u.clip_value, u.tau, u.interval = float(weight_decay or 0.0), float(clip_value or 0.0), float(tau), int(interval)
         L.call('smx_ddpg_rows_wgrad_update_f32' if wgrad else 'smx_ddpg_rows_update_f32', ctypes.byref(args),
-               {'actor': 0, 'critic': 1}[group], ctypes.byref(u), self._st())
+               {'actor': 0, 'critic': 1, 'critic2': 2}[group], ctypes.byref(u), self._st())
 
 
     # ---- LSTM stem ----------------------------------------------------------------------------

@@ -24,7 +24,8 @@ the critic loss (Adam with the critic's hyper-parameters) and follows the target
 update reuses the features formed before the critic step, as the reference does.
 
 Three launch schedules (_schedule): row blocks and dependency levels for low-dimensional observations with one critic, and
-the layer-by-layer one (_enqueue_iteration_layers) that carries every switch.  What belongs to one critic -- model, target,
+the layer-by-layer one (_enqueue_iteration_layers) that carries every switch.  TD3 without LayerNorm on low-dimensional
+observations also runs on the row blocks when session_config.learner.ddpg_row_schedule is True (5 launches; opt-in).  What belongs to one critic -- model, target,
 buffers, gradients, Adam group -- is one record (_critic_workspace): the second critic's update is the first one's code.
 
 use_layernorm (default off) runs layer by layer too, with every other switch: the variant lives in DDPGModel's passes
@@ -368,6 +369,9 @@ class DDPGLearner(Learner):
         """(D, A, H1, H2, c1, c2) when the row-block kernels take these shapes (for a batch of `rows`), else None"""
         m = self.model
         dims = (D, self.action_dim, m.actor.H1, m.actor.H2, m.c1, m.c2)
+        if self.use_double_critic and not (rows is not None and KN.ddpg_rows_td3(self.K)
+                                           and self.K.ddpg_rows_second_supported(*dims, rows)):
+            return None              # (TD3's chain keeps y between the two losses and addresses more buffers)
         return dims if self.K.ddpg_rows_supported(*dims, rows=rows) else None
 
     def _rows_args(self, ws, x, xn, actions, rewards, done):
@@ -378,24 +382,40 @@ class DDPGLearner(Learner):
         dims = self._rows_dims(x.shape[1], x.shape[0])
         ws.rows_packed = torch.zeros(K.ddpg_rows_packed_floats(*dims), device=self.device)
         ws.rows_versions = None          # nothing packed yet
-        if getattr(ws, 'stats_slots', None) is None:
-            ws.stats_slots = torch.zeros(2, 8, pin_memory=torch.cuda.is_available())
+        if getattr(ws, 'stats_slots', None) is None:      # (two blocks of 8 per slot with a second critic)
+            ws.stats_slots = torch.zeros(2, 16 if self.use_double_critic else 8, pin_memory=torch.cuda.is_available())
         nets = {'actor': m.actor.views, 'critic': m.critic, 'target_actor': mt.actor.views, 'target_critic': mt.critic}
         io = dict(x=x, x_next=xn, actions=actions, rewards=rewards, dones=done, xcat=ws.xcat, h2c=ws.h2c, q=ws.q,
                   q_next=ws.q_next, y=ws.y, dz3=ws.dz3, dz2=ws.dz2, dxcat=ws.dxcat, h1a=ws.h1a, h2a=ws.h2a, act=ws.act,
                   q_actor=ws.q_actor, dz3a=ws.dz3a, dz2a=ws.dz2a, dz1a=ws.dz1a, step=ws.step)
         ws.rows_args = K.ddpg_rows_args(dims, nets, ws.rows_packed, io, pow(self.discount_factor, self.n_step))
+        if self.use_double_critic:
+            # TD3: the second critic's networks, its own packed buffer and its own buffers -- dz2 / dxcat too (ws.bw is
+            # one critic's at a time; here both critics' data gradients exist before either weight-gradient launch)
+            s = ws.critics[1]
+            B, c1, c2, A = x.shape[0], m.c1, m.c2, self.action_dim
+            ws.rows_packed2 = torch.zeros(K.ddpg_rows_second_packed_floats(*dims), device=self.device)
+            ws.dz2_2 = torch.zeros(B, c2, device=self.device)
+            ws.dxcat2 = torch.zeros(B, c1 + A, device=self.device)
+            nets2 = {'critic2': s.model.critic, 'target_critic2': s.target.critic}
+            io2 = dict(noise=ws.s_noise if self.use_action_regularization else None, xcat2=s.w.xcat, h2c2=s.w.h2c, q2=s.q,
+                       q_next2=ws.q_next2, dz3_2=s.dz3, dz2_2=ws.dz2_2, dxcat2=ws.dxcat2, stats2=s.stats)
+            ws.rows_args = K.ddpg_rows_second(ws.rows_args, nets2, ws.rows_packed2, io2)
         ws.rows_key = (x.data_ptr(), xn.data_ptr(), actions.data_ptr(), rewards.data_ptr(), done.data_ptr())
         return ws.rows_args
 
     def _enqueue_iteration_rows(self, ws, x, xn, actions, rewards, done):
-        """One DDPG iteration (ddpg.py:244-352; low-dimensional observations, one critic) on ROW BLOCKS: a
+        """One DDPG iteration (ddpg.py:244-352; low-dimensional observations, one critic -- TD3's two below) on ROW BLOCKS: a
         workgroup carries 4 batch rows through whole chains -- target actor -> target critic -> y, critic -> loss ->
         its data gradients, and the actor's forward pass in one launch; Q(s, mu(s)) through the updated critic -> the
         actor's data gradients in a second (smx_ddpg_rows.hip).  Weight gradients (sums over all rows), Adam, the
         target update and the statistics are the launches of the other schedules, on the same buffers: 10 launches where
         the level schedule takes 22.  The MFMA loop sums a layer's products in another order than smx_linear_f32:
-        equal to the level schedule within fp32 rounding (tests/test_gpu_ddpg.py), not bit for bit."""
+        equal to the level schedule within fp32 rounding (tests/test_gpu_ddpg.py), not bit for bit.
+        TD3 (use_double_critic, with or without action regularisation): the critic chain carries both target critics --
+        the second at the noised, clamped action --, y = min of the two targets and both critics' losses and data
+        gradients (smx_ddpg_rows_critic_td3_f32); the second critic's step is a third update launch between the first
+        critic's and the actor chain, which goes through the first critic only.  5 launches, no ATen arithmetic."""
         K, m, mt, A = self.K, self.model, self.model_target, self.action_dim
         B, D = x.shape
         c1, c2, ld = m.c1, m.c2, m.c1 + A
@@ -412,7 +432,11 @@ class DDPGLearner(Learner):
         # one rank: a group's weight gradients and its step are ONE launch (value clipping needs no norm over the group);
         # several: the gradients are averaged over the ranks between them
         fuse = self.world_size == 1 and self.rows_fused_update
-        K.ddpg_rows_critic(args)
+        second = ws.critics[1] if self.use_double_critic else None
+        if second is not None:
+            K.ddpg_rows_critic_td3(args)
+        else:
+            K.ddpg_rows_critic(args)
         if not fuse:
             K.linear_multi([('wgrad', ws.dxcat, x, gc['W1'], gc['b1'], c1, D, B, dict(ldz=ld)),
                             ('wgrad', ws.dz2, ws.xcat, gc['W2'], gc['b2'], c2, ld, B, {}),
@@ -421,6 +445,16 @@ class DDPGLearner(Learner):
         K.ddpg_rows_update(args, 'critic', m.critic_flat, ws.grads_c, self.critic_exp_avg, self.critic_exp_avg_sq,
                            ws.lr[1:2], ws.step, self.critic_regularization, self.critic_gradient_clip_value,
                            target=mt.critic_flat, wgrad=fuse, **tgt)
+        if second is not None:
+            g2, w2 = second.gv, second.w
+            if not fuse:
+                K.linear_multi([('wgrad', ws.dxcat2, x, g2['W1'], g2['b1'], c1, D, B, dict(ldz=ld)),
+                                ('wgrad', ws.dz2_2, w2.xcat, g2['W2'], g2['b2'], c2, ld, B, {}),
+                                ('wgrad', second.dz3.view(B, 1), w2.h2c, g2['W3'], g2['b3'], 1, c2, B, dict(ldz=1))])
+                self._average_over_ranks(second.grads)
+            K.ddpg_rows_update(args, 'critic2', second.model.critic_flat, second.grads, self.critic2_moments[0],
+                               self.critic2_moments[1], ws.lr[1:2], ws.step, self.critic_regularization,
+                               self.critic_gradient_clip_value, target=second.target.critic_flat, wgrad=fuse, **tgt)
         K.ddpg_rows_actor(args)
         if not fuse:
             K.linear_multi([('wgrad', ws.dz1a, x, ga['W1'], ga['b1'], H1, D, B, {}),
@@ -435,13 +469,19 @@ class DDPGLearner(Learner):
         if not fuse:                 # (fused: the statistics are one more workgroup of the actor's launch)
             K.ddpg_stats(ws.q, ws.y, rewards, actions, ws.q_actor, ws.stats)
             self._average_over_ranks(ws.stats[:6])
+            if second is not None:       # the second critic's loss and Q_policy2, as the layer schedule reports them
+                K.ddpg_stats(second.q, ws.y, rewards, actions, second.q, second.stats)
+                self._average_over_ranks(second.stats[:6])
         ws.rows_versions = self._rows_versions()
 
     def _rows_versions(self):
-        """torch's write counters of the four parameter buffers: the HIP launches do not move them (raw pointers), anything
-        that writes parameters through torch does"""
+        """torch's write counters of the four parameter buffers (six with a second critic): the HIP launches do not move
+        them (raw pointers), anything that writes parameters through torch does"""
         m, mt = self.model, self.model_target
-        return tuple(int(t._version) for t in (m.actor_flat, m.critic_flat, mt.actor_flat, mt.critic_flat))
+        flats = [m.actor_flat, m.critic_flat, mt.actor_flat, mt.critic_flat]
+        if self.use_double_critic:
+            flats += [self.model2.critic_flat, self.model_target2.critic_flat]
+        return tuple(int(t._version) for t in flats)
 
     def _rows_refresh(self, ws):
         """the row schedule's fragment-order copies follow the parameters through ddpg_rows_update only: repack all of
@@ -449,6 +489,8 @@ class DDPGLearner(Learner):
         args = getattr(ws, 'rows_args', None)
         if args is not None and getattr(ws, 'rows_versions', None) != self._rows_versions():
             self.K.ddpg_rows_pack(args)
+            if self.use_double_critic:
+                self.K.ddpg_rows_pack_second(args)
             ws.rows_versions = self._rows_versions()
 
     def _enqueue_critic_update(self, ws, c, x):
@@ -538,7 +580,11 @@ class DDPGLearner(Learner):
         """which launch schedule an iteration on B rows of D inputs takes -- 'rows' (row blocks), 'levels' (dependency
         levels) or 'layers' (layer by layer: every switch).  Asked at each enqueue: level_schedule / row_schedule may be
         set after construction"""
-        if not (self.use_layernorm or self.is_pixel_input or self.use_double_critic):
+        if not (self.use_layernorm or self.is_pixel_input):
+            if self.use_double_critic:
+                # TD3 takes the rows only when asked to (ddpg_row_schedule = True), where the kernels run it and the
+                # shapes fit; unset, it stays layer by layer as before -- and there are no levels for two critics
+                return 'rows' if self.row_schedule is True and self._rows_dims(D, B) is not None else 'layers'
             rows = self.row_schedule if self.row_schedule is not None else B <= 1024
             if rows and self._rows_dims(D, B) is not None:
                 return 'rows'
@@ -644,14 +690,16 @@ class DDPGLearner(Learner):
             # the row schedule's last launch wrote the statistics into host-mapped memory itself (slot = the iteration's
             # Adam step & 1: the slot of the iteration before is still being read): no copy launch
             host0 = ws.stats_slots[self.critic_step & 1]
+            host1 = host0[8:] if self.use_double_critic else None      # (the second block of the slot)
         else:
             ws.stats_host[0].copy_(ws.stats, non_blocking=True)
             host0 = ws.stats_host[0]
+            host1 = ws.stats_host[1] if self.use_double_critic else None
         if ws.xerr is not None and self.world_size > 1:      # a peer exchange that timed out in this iteration
             ws.stats_host[2, :1].view(torch.int32).copy_(ws.xerr, non_blocking=True)
         else:
             ws.stats_host[2].zero_()
-        if self.use_double_critic:
+        if self.use_double_critic and not getattr(ws, 'stats_zero_copy', False):
             ws.stats_host[1].copy_(ws.stats2, non_blocking=True)
         # (two events in turn, recorded on a Stream object cached per raw handle: Event() + record() through
         # torch.cuda.current_stream() were 15 us of host time per iteration)
@@ -663,19 +711,19 @@ class DDPGLearner(Learner):
         ws.ev_turn ^= 1
         ev.record(ws.ev_stream)
         handle = DeferredStats(self._flush_stats)
-        self._pending_stats = (ev, ws.stats_host, handle, host0)
+        self._pending_stats = (ev, ws.stats_host, handle, host0, host1)
         return handle
 
     def _flush_stats(self):
         pend, self._pending_stats = self._pending_stats, None
         if pend is not None:
-            ev, host, handle, host0 = pend
+            ev, host, handle, host0, host1 = pend
             ev.synchronize()
             if int(host[2, :1].view(torch.int32)[0]) != 0:
                 raise RuntimeError('a peer exchange timed out in the last DDPG iteration: error word 0x%x (0x100 | phase << 4 '
                                    '| peer) -- a rank died or fell behind by more than the timeout'
                                    % (int(host[2, :1].view(torch.int32)[0]) & 0xffff))
-            handle._value = self._decode_stats(host0, host[1] if self.use_double_critic else None)
+            handle._value = self._decode_stats(host0, host1)
 
     def _decode_stats(self, st, st2):
         st = st.numpy()
