@@ -917,7 +917,26 @@ int smx_ddpg_stats_f32(const float* q, const float* y, const float* rewards,
  * reference reports the second critic's loss and Q_policy2); update->stats_host is then [2][16]: slot (*step & 1), the
  * first block in words 0 .. 6, the second in words 8 .. 14.
  * smx_ddpg_rows_second_supported: the shapes' LDS budget with y kept between the two losses, and every row-major buffer
- * of `rows` rows within the 31-bit byte offsets the launches address them by. */
+ * of `rows` rows within the 31-bit byte offsets the launches address them by.
+ *
+ * use_layernorm (model_builders/builders.py:42-48, 65-75: Linear -> ReLU -> LayerNorm on both hidden layers of actor and
+ * critic; ddpg.py:244-352) on the same rows, one critic: args->ln names the four networks' gains and biases (read
+ * row-major, no packed copy), eps and the extra row-major buffers.  NULL: no LayerNorm, everything as before.  With it
+ *   smx_ddpg_rows_critic_f32 / _actor_f32  the same chains with a LayerNorm rule behind every hidden layer (the bits
+ *                             of smx_layernorm_forward_f32 given the same row) and its backward rule (those of
+ *                             smx_layernorm_backward_f32 with relu_mask) behind the backward products.  xcat[:, :c1], h2c,
+ *                             h1a, h2a receive the LayerNorm OUTPUTS -- what the weight gradients multiply --, the
+ *                             activations in front go to c_a1, c_a2, a1, a2 with each row's mean and rstd; dz2, dz2a, dz1a
+ *                             are the gradients at the ReLUs' inputs as before, the critic's dz1 goes to dz1c [rows, c1] and
+ *                             dxcat[:, :c1] keeps d/d(LayerNorm 1's output); dn2, dn2a, dn1a the other three.  The actor
+ *                             chain goes back through the updated critic's second LayerNorm only.
+ *   smx_ddpg_rows_wgrad_update_f32  also forms dgamma = sum_rows dn xhat and dbeta = sum_rows dn of the group's two
+ *                             LayerNorms (further workgroups of the launch, a fixed summation order, no atomics) and steps
+ *                             them: update->n covers the dense layers and, behind them, the four LayerNorm vectors.
+ * Every other entry that takes smx_ddpg_rows_t returns SMX_E_UNSUPPORTED with ln set (smx_ddpg_rows_critic_td3_f32,
+ * smx_ddpg_rows_update_f32), and so does `second` together with `ln`; smx_ddpg_rows_pack_f32 packs the dense weights as
+ * before.  smx_ddpg_rows_ln_supported: what smx_ddpg_rows_supported_at says, narrowed by the LDS budget with the
+ * pre-LayerNorm and dn tiles kept, and every row-major buffer within 31-bit byte offsets. */
 typedef struct smx_ddpg_net {          /* nn.Linear layouts: W [out, in] row-major */
     const float *W1, *b1, *W2, *b2, *W3, *b3;
 } smx_ddpg_net_t;
@@ -927,6 +946,17 @@ struct smx_ddpg_rows_second {
     const float* noise;                                        /* [rows, A] or NULL */
     float *xcat2, *h2c2, *q2, *q_next2, *dz3_2, *dz2_2, *dxcat2;   /* critic phase, out (xcat2 / dxcat2: row stride c1 + A) */
     float* stats2;                                             /* [7] or NULL */
+};
+struct smx_ddpg_ln_net {               /* the two LayerNorms of a network: gain and bias behind layer 1 [H1 | c1], layer 2 [H2 | c2] */
+    const float *g1, *b1, *g2, *b2;
+};
+struct smx_ddpg_rows_ln {
+    struct smx_ddpg_ln_net actor, critic, target_actor, target_critic;
+    float eps;
+    float *c_a1, *cm1, *cr1, *c_a2, *cm2, *cr2;                /* critic phase, out: [rows, c1], [rows] x 2, [rows, c2], [rows] x 2 */
+    float *dn2, *dz1c;                                         /* critic phase, out: [rows, c2], [rows, c1] */
+    float *a1, *am1, *ar1, *a2, *am2, *ar2;                    /* critic phase out, actor phase in: [rows, H1], .., [rows, H2], .. */
+    float *dn2a, *dn1a;                                        /* actor phase, out: [rows, H2], [rows, H1] */
 };
 typedef struct smx_ddpg_rows {
     int64_t rows;
@@ -940,6 +970,7 @@ typedef struct smx_ddpg_rows {
     float *q_actor, *dz3a, *dz2a, *dz1a;                       /* actor phase, out */
     int32_t* step;                                             /* device Adam step counter (may be NULL) */
     const struct smx_ddpg_rows_second* second;                 /* TD3's second critic; NULL: one critic */
+    const struct smx_ddpg_rows_ln* ln;                         /* use_layernorm; NULL: none */
 } smx_ddpg_rows_t;
 enum { SMX_DDPG_PACK_ALL = 0, SMX_DDPG_PACK_CRITIC = 1, SMX_DDPG_PACK_SECOND = 2 };   /* ALL / CRITIC: args->packed only */
 int32_t smx_ddpg_rows_supported(int32_t D, int32_t A, int32_t H1, int32_t H2, int32_t c1, int32_t c2);   /* on 4-row blocks */
@@ -952,6 +983,7 @@ int smx_ddpg_rows_actor_f32(const smx_ddpg_rows_t* args, smx_stream_t stream);
 int32_t smx_ddpg_rows_second_supported(int32_t D, int32_t A, int32_t H1, int32_t H2, int32_t c1, int32_t c2, int64_t rows);
 int64_t smx_ddpg_rows_second_packed_floats(int32_t D, int32_t A, int32_t H1, int32_t H2, int32_t c1, int32_t c2);
 int smx_ddpg_rows_critic_td3_f32(const smx_ddpg_rows_t* args, smx_stream_t stream);
+int32_t smx_ddpg_rows_ln_supported(int32_t D, int32_t A, int32_t H1, int32_t H2, int32_t c1, int32_t c2, int64_t rows);
 
 /* One optimiser group's step of the row schedule in ONE launch (round 6): Adam exactly as smx_adam_step_dev_f32
  * (torch.optim.Adam after clip_grad_value_: ddpg.py:310-311, 332-333), then the group's target network -- soft

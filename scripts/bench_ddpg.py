@@ -3,9 +3,10 @@ BASELINE configs[2] (HalfCheetah shapes D=17, A=6, uniform replay, batch 512), d
 replay shard; and the oracle (reference ATen path) on the host CPU beside it.
 
     --td3                          use_double_critic + use_action_regularization
+    --layernorm                    use_layernorm (one critic; with --row-schedule on: the LayerNorm chains of the row schedule)
     --row-schedule on|off|unset    session_config.learner.ddpg_row_schedule (unset: the learner's own choice)
     --ab NAME[,NAME...]            timing rounds only, the named variants interleaved inside every round -- td3_layers, td3_rows,
-                                   plain (the default learner): --rounds rounds of --calls learn() calls each, one JSON line per
+                                   ln_layers, ln_rows, plain (the default learner): --rounds rounds of --calls learn() calls each, one JSON line per
                                    variant (ms per call of every round, their median, min and max) appended to --jsonl
     --tree PATH                    import surreal_amd from another checkout (the parent commit beside this one, same job)
     --label TEXT                   goes into the JSON lines
@@ -14,6 +15,7 @@ import argparse, json, sys, os, time, copy
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ap = argparse.ArgumentParser()
 ap.add_argument('--td3', action='store_true')
+ap.add_argument('--layernorm', action='store_true')
 ap.add_argument('--row-schedule', choices=['on', 'off', 'unset'], default='unset')
 ap.add_argument('--ab', default='')
 ap.add_argument('--rounds', type=int, default=5)
@@ -32,8 +34,9 @@ from surreal_amd.learner.ddpg import DDPGLearner
 B, D, A = 512, 17, 6
 
 
-def make_learner(td3, row_schedule):
+def make_learner(td3, row_schedule, layernorm=False):
     lc = ddpg_learner_config(); lc.replay.batch_size = B
+    lc.model.use_layernorm = bool(layernorm)
     lc.algo.network.use_double_critic = lc.algo.network.use_action_regularization = bool(td3)
     sc = ddpg_session_config()
     if row_schedule != 'unset':
@@ -42,7 +45,8 @@ def make_learner(td3, row_schedule):
 
 
 if opt.ab:
-    variants = {'td3_layers': (True, 'off'), 'td3_rows': (True, 'on'), 'plain': (False, 'unset')}
+    variants = {'td3_layers': (True, 'off'), 'td3_rows': (True, 'on'), 'plain': (False, 'unset'),
+                'ln_layers': (False, 'off', True), 'ln_rows': (False, 'on', True)}
     names = [n for n in opt.ab.split(',') if n]
     learners = {n: make_learner(*variants[n])[1] for n in names}
     batches = {n: [learners[n].preprocess(synthetic.make_ddpg_batch(B, D, A, seed=s)) for s in range(8)] for n in names}
@@ -69,8 +73,8 @@ if opt.ab:
                 f.write(line + '\n')
     sys.exit(0)
 
-lc, L = make_learner(opt.td3, opt.row_schedule)
-print('schedule: %s (td3 %s, ddpg_row_schedule %s)' % (L._schedule(B, D), opt.td3, opt.row_schedule))
+lc, L = make_learner(opt.td3, opt.row_schedule, opt.layernorm)
+print('schedule: %s (td3 %s, layernorm %s, ddpg_row_schedule %s)' % (L._schedule(B, D), opt.td3, opt.layernorm, opt.row_schedule))
 batches = [L.preprocess(synthetic.make_ddpg_batch(B, D, A, seed=s)) for s in range(8)]
 for i in range(20): L.learn(batches[i % 8])
 torch.cuda.synchronize(); t0 = time.perf_counter(); n = 300
@@ -110,7 +114,7 @@ torch.cuda.synchronize(); ds = (time.perf_counter() - t0) / n
 print('DDPG sample(512 of 1e6) + learn: %.3f ms/iter  %.3g samples/s  (hipGraph %s)' % (ds * 1e3, B / ds, L._ws.graph is not None))
 try:
     import ddpg_oracle
-    params = ddpg_oracle.make_ddpg_params(D, A, (300, 200), (400, 300), seed=3)
+    params = ddpg_oracle.make_ddpg_params(D, A, (300, 200), (400, 300), seed=3, layernorm=opt.layernorm)
     td3 = dict(use_double_critic=True, use_action_regularization=True, batch_size=B,
                params2=ddpg_oracle.make_ddpg_params(D, A, (300, 200), (400, 300), seed=4)) if opt.td3 else {}
     O = ddpg_oracle.OracleDDPGLearner(params, A, **td3) if hasattr(ddpg_oracle, 'OracleDDPGLearner') else None

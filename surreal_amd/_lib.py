@@ -137,6 +137,18 @@ class DdpgRowsSecond(Structure):
                                          'stats2')])
 
 
+class DdpgLnNet(Structure):
+    """struct smx_ddpg_ln_net"""
+    _fields_ = [(n, c_void_p) for n in ('g1', 'b1', 'g2', 'b2')]
+
+
+class DdpgRowsLn(Structure):
+    """struct smx_ddpg_rows_ln"""
+    _fields_ = ([(n, DdpgLnNet) for n in ('actor', 'critic', 'target_actor', 'target_critic')] + [('eps', c_float)] +
+                [(n, c_void_p) for n in ('c_a1', 'cm1', 'cr1', 'c_a2', 'cm2', 'cr2', 'dn2', 'dz1c', 'a1', 'am1', 'ar1', 'a2',
+                                         'am2', 'ar2', 'dn2a', 'dn1a')])
+
+
 class DdpgRows(Structure):
     """smx_ddpg_rows_t"""
     _fields_ = ([('rows', c_int64)] + [(n, c_int32) for n in ('D', 'A', 'H1', 'H2', 'c1', 'c2')] +
@@ -145,7 +157,7 @@ class DdpgRows(Structure):
                 [('gamma_n', c_float)] +
                 [(n, c_void_p) for n in ('xcat', 'h2c', 'q', 'q_next', 'y', 'dz3', 'dz2', 'dxcat', 'h1a', 'h2a', 'act',
                                          'q_actor', 'dz3a', 'dz2a', 'dz1a', 'step')] +
-                [('second', POINTER(DdpgRowsSecond))])
+                [('second', POINTER(DdpgRowsSecond)), ('ln', POINTER(DdpgRowsLn))])
 
 
 class GatherJob(Structure):
@@ -396,6 +408,7 @@ _SIGS = {
     'smx_ddpg_rows_second_supported': (c_int32, [c_int32] * 6 + [c_int64]),
     'smx_ddpg_rows_second_packed_floats': (c_int64, [c_int32] * 6),
     'smx_ddpg_rows_critic_td3_f32': (c_int32, [_P, _P]),
+    'smx_ddpg_rows_ln_supported': (c_int32, [c_int32] * 6 + [c_int64]),
     'smx_ddpg_rows_update_f32': (c_int32, [_P, c_int32, _P, _P]),
     'smx_ddpg_rows_wgrad_update_f32': (c_int32, [_P, c_int32, _P, _P]),
     'smx_ddpg_stats_f32': (c_int32, [_P, _P, _P, _P, c_int32, c_int32, _P, c_int64, _P, _P]),

@@ -23,6 +23,19 @@
 //   ddpg_rows4_kernel<1>      unchanged: the actor goes through critic 1 only
 //   ddpg_rows_wgrad_update    the actor;  [statistics: a second block for (q2, y) by the same workgroup]
 //
+// use_layernorm (builders.py:42-48, 65-75: Linear -> ReLU -> LayerNorm on every hidden layer; one critic) is the same
+// four launches: LayerNorm is a rule BEHIND a hidden layer's step, not a layer (ddpg_rows4_ln_kernel<0>, <1>; the three
+// instantiations above keep their code):
+//
+//   forward    behind the barrier that ends the layer the block's 4 rows are normalised in LDS (ln_rows of
+//              smx_ln_rows.inc.h, shared with the rollout: the bits of smx_layernorm_forward_f32 given the same row); the
+//              pre-LayerNorm tile stays in LDS beside the output, both go to HBM with the row's mean and rstd
+//   backward   layernorm_bwd_kernel's expressions, one wave per row, from the dn / pre-LayerNorm tiles and the statistics
+//              in LDS: the gradient at the ReLU's input (the x > 0 mask folded in) to LDS and HBM
+//   gradients  dgamma = sum_rows dn xhat, dbeta = sum_rows dn: further workgroups of the group's gradient-and-step
+//              launch, behind the tiles and in front of the statistics workgroup; no atomics
+// The gains and biases are read row-major from the parameter buffers, as the dense biases are: no packed copy.
+//
 // Activations and gradients that the weight-gradient launches read go to HBM row-major, exactly the buffers of the
 // layer-by-layer schedule.  Products are summed in the MFMA loop's order (32-wide K chunks, k ascending per lane group),
 // not in smx_linear_f32's: results agree with the layered schedule to fp32 rounding, not bit for bit.
@@ -41,6 +54,7 @@ namespace {
 #include "smx_epoch_mma.inc.h"
 #include "smx_rows4_mma.inc.h"
 #include "smx_ddpg_stats.inc.h"
+#include "smx_ln_rows.inc.h"
 
 constexpr int DNWV = 8;           // wavefronts per workgroup: two per SIMD (one's loads hide under the other's MFMAs)
 constexpr int DNTH = 64 * DNWV;
@@ -137,7 +151,110 @@ struct Prog {
     int n;
     Step s[MAX_STEPS];
 };
-static_assert(sizeof(RArgs) + sizeof(Prog) < 4096, "both go by value in the kernel arguments");
+
+// LayerNorm (ddpg_rows4_ln_kernel): what the step's LayerNorm rule needs, beside the step.  FWD: the layer has written
+// relu(z) to the pre-LayerNorm tile (its out tile) and to HBM (its g); the rule writes the normalised rows to tile `t`
+// and to `n`, the statistics to slot `st` of the LDS statistics and to mean / rstd.  BWD: the layer (or the loss rule)
+// has left dn in tile `d`; the rule writes the gradient at the ReLU's input to tile `t` (< 0: none) and to `n`.
+enum { LN_NONE = 0, LN_FWD = 1, LN_BWD = 2 };
+constexpr int LN_STEPS = 13;         // the LayerNorm critic chain
+constexpr int LNR_MAXC = 16;         // columns per lane: F <= 1024, as layernorm_fwd_kernel
+struct LnStep {
+    const float *gamma, *beta;    // (BWD: gamma only)
+    float* n;                     // HBM [rows][ldn] or null
+    float *mean, *rstd;           // FWD: HBM [rows] or null
+    int kind, F, ldn;
+    int p_off, ldp;               // the pre-LayerNorm tile
+    int t_off, ldt;
+    int d_off, ldd;
+    int st;
+};
+struct LnProg {
+    LnStep s[LN_STEPS];
+    float eps;
+    float* dn2;                                       // critic chain: d/d(LayerNorm 2's output) [rows][c2]
+    const float *a1, *a2, *am1, *ar1, *am2, *ar2;     // actor chain: the actor's pre-LayerNorm rows and statistics
+    int oP1, ldP1, oP2, ldP2, oD, ldD, oM;            // LDS (float offsets): two pre-LayerNorm tiles, dn, statistics [4][2][4]
+};
+static_assert(sizeof(RArgs) + sizeof(Prog) + sizeof(LnProg) < 4096, "all go by value in the kernel arguments");
+
+// The rule's fields are wanted BEHIND the layer's K loop: at an offset the compiler cannot see through, or it loads them
+// at the head of the step (the chain's own before the loop over the steps) and keeps two dozen scalar registers occupied
+// across the K loop, which is at the register file's limit as it is
+__device__ __forceinline__ const LnStep& ln_late(const LnProg* Q, int si) {
+    asm volatile("" : "+s"(si));
+    return Q->s[si];
+}
+__device__ __forceinline__ const LnProg* ln_late(const LnProg* Q) {
+    int z = 0;
+    asm volatile("" : "+s"(z));
+    return (const LnProg*)((const char*)Q + z);
+}
+
+__device__ __forceinline__ int behind_here(int v) {      // the same value, formed no earlier than this point
+    asm volatile("" : "+v"(v));
+    return v;
+}
+
+struct LnEmitRows {               // ln_rows' outputs beside the LDS tile
+    float* n;
+    int ldn;
+    float *mean, *rstd, *st;      // st: LDS [2][RBLK]
+    long row0;
+    int nrows, lane;
+    __device__ __forceinline__ void value(int r, int j, float y) const {
+        if (n && r < nrows) n[(size_t)(row0 + r) * ldn + j] = y;
+    }
+    __device__ __forceinline__ void stats(int r, float m, float rs) const {
+        if (lane == 0) {
+            st[r] = m;
+            st[RBLK + r] = rs;
+            if (mean && r < nrows) { mean[row0 + r] = m; rstd[row0 + r] = rs; }
+        }
+    }
+};
+
+// the LayerNorm's backward rule on the block's rows: layernorm_bwd_kernel's expressions and order (smx_ddpg.hip; its zero
+// terms for the columns past F left out), one wave per row -- g = dn gamma, the two wave sums, rs ((g - m1) - xhat m2), the
+// x > 0 mask of the ReLU in front.  Given the same dn, pre-LayerNorm row and statistics: its bits.
+__device__ __forceinline__ void ln_bwd_rows(const float* dn, int ldd, const float* pre, int ldp, const float* st, int F,
+                                            const float* __restrict__ gamma, float* tz, int ldt, float* gz, int ldg,
+                                            long row0, int nrows, int wv, int lane) {
+#pragma unroll 1
+    for (int r = wv; r < RBLK; r += DNWV) {
+        const float m = st[r], rs = st[RBLK + r];
+        const float* xr = pre + r * ldp;
+        const float* dr = dn + r * ldd;
+        float g[LNR_MAXC];           // (x and xhat are formed again from LDS in the second pass: the same bits)
+        float s1 = 0.f, s2 = 0.f;
+#pragma unroll
+        for (int c = 0; c < LNR_MAXC; ++c) {
+            if (64 * c >= F) break;                  // (wave-uniform)
+            const int j = lane + 64 * c;
+            const bool in = j < F;
+            const float xv = in ? xr[j] : 0.f;
+            const float d = in ? dr[j] : 0.f;
+            const float xh = in ? (xv - m) * rs : 0.f;
+            g[c] = in ? d * gamma[in ? j : 0] : 0.f;
+            s1 += g[c];
+            s2 += g[c] * xh;
+        }
+        const float m1 = smx_wave_sum(s1) / (float)F, m2 = smx_wave_sum(s2) / (float)F;
+#pragma unroll
+        for (int c = 0; c < LNR_MAXC; ++c) {
+            if (64 * c >= F) break;
+            const int j = lane + 64 * c;
+            if (j < F) {
+                const float xv = xr[j];
+                const float xh = (xv - m) * rs;
+                float v = rs * ((g[c] - m1) - xh * m2);
+                v = (xv > 0.f) ? v : 0.f;
+                if (tz) tz[r * ldt + j] = v;
+                if (gz && r < nrows) gz[(size_t)(row0 + r) * ldg + j] = v;
+            }
+        }
+    }
+}
 
 #ifdef SMX_DDPG_TIMING
 #define PSTAMP(k, i) do { if (G.tbuf && threadIdx.x == 0) G.tbuf[(size_t)blockIdx.x * 128 + 16 + 5 * (k) + (i)] = (long long)__builtin_readcyclecounter(); } while (0)
@@ -147,8 +264,9 @@ static_assert(sizeof(RArgs) + sizeof(Prog) < 4096, "both go by value in the kern
 
 // PHASE 0: the critic chain, 1: the actor chain, 2: the critic chain of TD3 (two critics, y = min of their targets; its
 // rules exist in that instantiation only)
-template <int PHASE>
-__global__ __launch_bounds__(DNTH) void ddpg_rows4_kernel(RArgs G, Prog P) {
+// LN: the LayerNorm variant (PHASE 0, 1), its rules behind `if constexpr (LN)`; Q is null without
+template <int PHASE, bool LN>
+__device__ __forceinline__ void ddpg_rows4_chain(const RArgs& G, const Prog& P, const LnProg* Q) {
     extern __shared__ float sm[];
     constexpr int RB = RBLK;
     const int tid = threadIdx.x, lane = tid & 63;
@@ -276,16 +394,29 @@ __global__ __launch_bounds__(DNTH) void ddpg_rows4_kernel(RArgs G, Prog P) {
 
         // ---- what follows the layer in its chain ----
         const int post = S.post;
+        // LayerNorm: the rules' thread-derived indices and addresses are formed HERE, behind the K loop -- carried across it
+        // (as the plain chains carry them) they no longer fit beside the loop's registers
+        const int tp = LN ? behind_here(tid) : tid;
+        if constexpr (LN) {
+            // Linear -> ReLU -> LayerNorm: the rows the layer has just finished, normalised from the pre-LayerNorm tile
+            const LnStep& T = ln_late(Q, si);
+            if (T.kind == LN_FWD) {
+                const LnEmitRows emit = {T.n, T.ldn, T.mean, T.rstd, sm + Q->oM + 2 * RB * T.st, row0, nrows, lane};
+                ln_rows<RB, DNWV, LNR_MAXC>(sm + T.p_off, T.ldp, sm + T.t_off, T.ldt, T.F, T.gamma, T.beta, Q->eps, wv, lane,
+                                            emit);
+                SMX_LDS_BARRIER();
+            }
+        }
         if (PHASE == 0) {
             if (post == P_TC_CAT) {            // [h1' | mu'(s')]: the action behind the first c1 columns of the concat tile
-                if (tid < RB * A) {
-                    const int n = tid / A, j = tid - n * A;
+                if (tp < RB * A) {
+                    const int n = tp / A, j = tp - n * A;
                     sm[G.oC + n * G.ldC + c1 + j] = sm[G.oO + n * LDO + j];
                 }
                 SMX_LDS_BARRIER();
             } else if (post == P_C_CAT) {      // [h1 | a] and its row-major copy
-                if (tid < RB * A) {
-                    const int n = tid / A, j = tid - n * A;
+                if (tp < RB * A) {
+                    const int n = tp / A, j = tp - n * A;
                     const float v = (n < nrows) ? G.actions[(size_t)(row0 + n) * A + j] : 0.f;
                     sm[G.oC + n * G.ldC + c1 + j] = v;
                     if (n < nrows) G.xcat[(size_t)(row0 + n) * ldc + c1 + j] = v;
@@ -293,28 +424,33 @@ __global__ __launch_bounds__(DNTH) void ddpg_rows4_kernel(RArgs G, Prog P) {
                 SMX_LDS_BARRIER();
             } else if (post == P_LOSS) {
                 // y = r + gamma^n Q' (1 - done) (ddpg.py:279); dLoss/dQ of the mean squared error (ddpg.py:307-308)
-                if (tid < RB) {
-                    const float qn = sm[G.oO2 + tid * LDO], q = sm[G.oO + tid * LDO];
+                if (tp < RB) {
+                    const float qn = sm[G.oO2 + tp * LDO], q = sm[G.oO + tp * LDO];
                     const float t = (G.gamma_n * qn) * (1.0f - dn);
                     const float yy = rew + t;
                     const float d3 = (2.0f * (q - yy)) / (float)G.rows;
-                    sm[G.oS + tid] = (tid < nrows) ? d3 : 0.f;
-                    if (tid < nrows) {
-                        G.q[row0 + tid] = q;
-                        G.q_next[row0 + tid] = qn;
-                        G.y[row0 + tid] = yy;
-                        G.dz3[row0 + tid] = d3;
+                    sm[G.oS + tp] = (tp < nrows) ? d3 : 0.f;
+                    if (tp < nrows) {
+                        G.q[row0 + tp] = q;
+                        G.q_next[row0 + tp] = qn;
+                        G.y[row0 + tp] = yy;
+                        G.dz3[row0 + tp] = d3;
                     }
                 }
-                if (blockIdx.x == 0 && tid == 0 && G.step) *G.step += 1;      // this iteration's Adam step (both groups)
+                if (blockIdx.x == 0 && tp == 0 && G.step) *G.step += 1;      // this iteration's Adam step (both groups)
                 SMX_LDS_BARRIER();
                 // dz2 = (dz3 W3) relu'(h2), a K = 1 product: elementwise
-                for (int idx = tid; idx < RB * c2; idx += DNTH) {
+                for (int idx = tp; idx < RB * c2; idx += DNTH) {
                     const int n = idx / c2, j = idx - n * c2;
                     float v = sm[G.oS + n] * G.cW3[j];
-                    v = (sm[G.oB + n * G.ldB + j] > 0.f) ? v : 0.f;
-                    sm[G.oA + n * G.ldA + j] = v;
-                    if (n < nrows) G.dz2[(size_t)(row0 + n) * c2 + j] = v;
+                    if constexpr (LN) {              // d/d(LayerNorm 2's output): its backward rule follows below
+                        sm[Q->oD + n * Q->ldD + j] = v;
+                        if (n < nrows) Q->dn2[(size_t)(row0 + n) * c2 + j] = v;
+                    } else {
+                        v = (sm[G.oB + n * G.ldB + j] > 0.f) ? v : 0.f;
+                        sm[G.oA + n * G.ldA + j] = v;
+                        if (n < nrows) G.dz2[(size_t)(row0 + n) * c2 + j] = v;
+                    }
                 }
                 SMX_LDS_BARRIER();
             }
@@ -322,8 +458,8 @@ __global__ __launch_bounds__(DNTH) void ddpg_rows4_kernel(RArgs G, Prog P) {
             if (post == P_TC_CAT || post == P_TC2_CAT) {
                 // [h1' | mu'(s')] for the first target critic; the second sees the action under the clipped noise:
                 // min(max(mu' + noise, -1), 1), an fp32 add then the clamp (ddpg.py:266-283 adds it after Q1' was formed)
-                if (tid < RB * A) {
-                    const int n = tid / A, j = tid - n * A;
+                if (tp < RB * A) {
+                    const int n = tp / A, j = tp - n * A;
                     float v = sm[G.oO + n * LDO + j];
                     if (post == P_TC2_CAT && G.noise) {
                         const float nz = (n < nrows) ? G.noise[(size_t)(row0 + n) * A + j] : 0.f;
@@ -334,8 +470,8 @@ __global__ __launch_bounds__(DNTH) void ddpg_rows4_kernel(RArgs G, Prog P) {
                 SMX_LDS_BARRIER();
             } else if (post == P_C_CAT || post == P_C2_CAT) {      // [h1 | a] and its row-major copy, per critic
                 float* xc = post == P_C_CAT ? G.xcat : G.xcat2;
-                if (tid < RB * A) {
-                    const int n = tid / A, j = tid - n * A;
+                if (tp < RB * A) {
+                    const int n = tp / A, j = tp - n * A;
                     const float v = (n < nrows) ? G.actions[(size_t)(row0 + n) * A + j] : 0.f;
                     sm[G.oC + n * G.ldC + c1 + j] = v;
                     if (n < nrows) xc[(size_t)(row0 + n) * ldc + c1 + j] = v;
@@ -345,35 +481,35 @@ __global__ __launch_bounds__(DNTH) void ddpg_rows4_kernel(RArgs G, Prog P) {
                 // first critic: y = min(y1, y2) of the two targets, each formed as the one-critic rule forms it (r + t is
                 // monotone in Q': the same value as the Bellman target of min(Q1', Q2')); y stays in LDS for the second
                 const bool first = post == P_LOSS;
-                if (tid < RB) {
-                    const float q = sm[G.oO + tid * LDO];
+                if (tp < RB) {
+                    const float q = sm[G.oO + tp * LDO];
                     float yy;
                     if (first) {
-                        const float qn1 = sm[G.oO2 + tid * LDO], qn2 = sm[G.oO3 + tid * LDO];
+                        const float qn1 = sm[G.oO2 + tp * LDO], qn2 = sm[G.oO3 + tp * LDO];
                         const float t1 = (G.gamma_n * qn1) * (1.0f - dn), t2 = (G.gamma_n * qn2) * (1.0f - dn);
                         const float y1 = rew + t1, y2 = rew + t2;
                         yy = fminf(y1, y2);
-                        sm[G.oY + tid] = yy;
-                        if (tid < nrows) {
-                            G.q_next[row0 + tid] = qn1;
-                            G.q_next2[row0 + tid] = fminf(qn1, qn2);
-                            G.y[row0 + tid] = yy;
+                        sm[G.oY + tp] = yy;
+                        if (tp < nrows) {
+                            G.q_next[row0 + tp] = qn1;
+                            G.q_next2[row0 + tp] = fminf(qn1, qn2);
+                            G.y[row0 + tp] = yy;
                         }
                     } else {
-                        yy = sm[G.oY + tid];
+                        yy = sm[G.oY + tp];
                     }
                     const float d3 = (2.0f * (q - yy)) / (float)G.rows;
-                    sm[G.oS + tid] = (tid < nrows) ? d3 : 0.f;
-                    if (tid < nrows) {
-                        (first ? G.q : G.q2)[row0 + tid] = q;
-                        (first ? G.dz3 : G.dz3_2)[row0 + tid] = d3;
+                    sm[G.oS + tp] = (tp < nrows) ? d3 : 0.f;
+                    if (tp < nrows) {
+                        (first ? G.q : G.q2)[row0 + tp] = q;
+                        (first ? G.dz3 : G.dz3_2)[row0 + tp] = d3;
                     }
                 }
-                if (first && blockIdx.x == 0 && tid == 0 && G.step) *G.step += 1;      // ONE Adam step count for all groups
+                if (first && blockIdx.x == 0 && tp == 0 && G.step) *G.step += 1;      // ONE Adam step count for all groups
                 SMX_LDS_BARRIER();
                 const float* W3 = first ? G.cW3 : G.c2W3;
                 float* dz2 = first ? G.dz2 : G.dz2_2;
-                for (int idx = tid; idx < RB * c2; idx += DNTH) {
+                for (int idx = tp; idx < RB * c2; idx += DNTH) {
                     const int n = idx / c2, j = idx - n * c2;
                     float v = sm[G.oS + n] * W3[j];
                     v = (sm[G.oB + n * G.ldB + j] > 0.f) ? v : 0.f;
@@ -384,27 +520,31 @@ __global__ __launch_bounds__(DNTH) void ddpg_rows4_kernel(RArgs G, Prog P) {
             }
         } else {
             if (post == P_A_CAT) {
-                if (tid < RB * A) {
-                    const int n = tid / A, j = tid - n * A;
+                if (tp < RB * A) {
+                    const int n = tp / A, j = tp - n * A;
                     sm[G.oC + n * G.ldC + c1 + j] = sm[G.oO + n * LDO + j];
                 }
                 SMX_LDS_BARRIER();
             } else if (post == P_A_DQ) {
                 // the masks of the actor's backward pass (its forward pass ran in the critic phase): h1a -> the concat
                 // tile, whose layer-2 product is done; h2a follows once dz2 has read the critic's ReLU mask
-                stage_rows(G.h1a, G.H1, G.H1, row0, nrows, G.oC, G.ldC);
+                if constexpr (!LN) stage_rows(G.h1a, G.H1, G.H1, row0, nrows, G.oC, G.ldC);
                 const float dq = -1.0f / (float)G.rows;            // d(-mean Q)/d(h2) = (-1/rows) W3 relu'(h2)
-                for (int idx = tid; idx < RB * c2; idx += DNTH) {
+                for (int idx = tp; idx < RB * c2; idx += DNTH) {
                     const int n = idx / c2, j = idx - n * c2;
                     float v = dq * G.cW3[j];
-                    v = (n < nrows && sm[G.oB + n * G.ldB + j] > 0.f) ? v : 0.f;
-                    sm[G.oA + n * G.ldA + j] = v;
+                    if constexpr (LN) {              // d/d(LayerNorm 2's output) of the critic, as in the critic chain
+                        sm[Q->oD + n * Q->ldD + j] = (n < nrows) ? v : 0.f;
+                    } else {
+                        v = (n < nrows && sm[G.oB + n * G.ldB + j] > 0.f) ? v : 0.f;
+                        sm[G.oA + n * G.ldA + j] = v;
+                    }
                 }
                 SMX_LDS_BARRIER();
-                stage_rows(G.h2a, G.H2, G.H2, row0, nrows, G.oB, G.ldB);
+                if constexpr (!LN) stage_rows(G.h2a, G.H2, G.H2, row0, nrows, G.oB, G.ldB);
             } else if (post == P_A_TANH) {     // through tanh: the action gradient times 1 - a^2
-                if (tid < RB * A) {
-                    const int n = tid / A, j = tid - n * A;
+                if (tp < RB * A) {
+                    const int n = tp / A, j = tp - n * A;
                     const float a = sm[G.oO + n * LDO + j];
                     const float v = sm[G.oO2 + n * LDO + j] * (1.0f - a * a);
                     sm[G.oZ + n * LDK4 + j] = v;
@@ -413,8 +553,38 @@ __global__ __launch_bounds__(DNTH) void ddpg_rows4_kernel(RArgs G, Prog P) {
                 SMX_LDS_BARRIER();
             }
         }
+        if constexpr (LN) {
+            const LnStep& T = ln_late(Q, si);
+            if (T.kind == LN_BWD) {
+                ln_bwd_rows(sm + T.d_off, T.ldd, sm + T.p_off, T.ldp, sm + Q->oM + 2 * RB * T.st, T.F, T.gamma,
+                            T.t_off >= 0 ? sm + T.t_off : nullptr, T.ldt, T.n, T.ldn, row0, nrows, wv, lane);
+                SMX_LDS_BARRIER();
+                if (PHASE == 1 && post == P_A_DQ) {
+                    // the actor's backward pass (its forward pass ran in the critic phase): its pre-LayerNorm rows and
+                    // statistics into the tiles and slots the critic's LayerNorms are done with (the barriers of the next
+                    // step stand between this and the rules that read them)
+                    stage_rows(Q->a1, G.H1, G.H1, row0, nrows, Q->oP1, Q->ldP1);
+                    stage_rows(Q->a2, G.H2, G.H2, row0, nrows, Q->oP2, Q->ldP2);
+                    if (tp < 4 * RB) {
+                        const int w = tp >> 2, n = tp & 3;       // (am1, ar1, am2, ar2) -> slots 2, 3
+                        const float* src = w == 0 ? Q->am1 : w == 1 ? Q->ar1 : w == 2 ? Q->am2 : Q->ar2;
+                        sm[Q->oM + 4 * RB + RB * w + n] = (n < nrows) ? src[row0 + n] : 0.f;
+                    }
+                }
+            }
+        }
         TSTAMP(si + 1);
     }
+}
+
+template <int PHASE>
+__global__ __launch_bounds__(DNTH) void ddpg_rows4_kernel(RArgs G, Prog P) {
+    ddpg_rows4_chain<PHASE, false>(G, P, nullptr);
+}
+
+template <int PHASE>
+__global__ __launch_bounds__(DNTH) void ddpg_rows4_ln_kernel(RArgs G, Prog P, LnProg Q) {
+    ddpg_rows4_chain<PHASE, true>(G, P, &Q);
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -569,6 +739,11 @@ struct WMat {
     int ldz, ldx, tiles_n, tile0; // tile0: first workgroup of this matrix
     long boff;                    // the bias [M] inside the group's buffer
 };
+struct WLn {                      // dgamma = sum_rows dn xhat, dbeta = sum_rows dn of one LayerNorm
+    const float *dn, *pre, *mean, *rstd;      // [rows][lddn], [rows][ldp] (in front of the LayerNorm), [rows] x 2
+    int lddn, ldp, F, blk0;       // blk0: the LayerNorm's first workgroup among the ln_blocks
+    long goff, boff;              // gamma [F], beta [F] inside the group's buffer
+};
 struct WUArgs {
     UArgs U;
     WMat w[3];
@@ -581,6 +756,9 @@ struct WUArgs {
     const float *s_q, *s_y, *s_rewards, *s_actions, *s_q_actor;
     int s_A, tiles;
     long long* tbuf;              // SMX_DDPG_TIMING builds
+    // LayerNorm: the group's two gain / bias pairs as ln_blocks further workgroups behind the tiles (0: none)
+    WLn ln[2];
+    int ln_blocks;
 };
 #ifdef SMX_DDPG_TIMING
 #define WSTAMP(i) do { if (G.tbuf && threadIdx.x == 0) G.tbuf[(size_t)blockIdx.x * 128 + (i)] = (long long)__builtin_readcyclecounter(); } while (0)
@@ -614,6 +792,81 @@ __device__ __forceinline__ void ddpg_step_element(const UArgs& U, long i, float 
 
 constexpr int WNW = 8;            // waves per tile: wave w takes the w-th eighth of the rows, the WHOLE 32 x 32 tile
 constexpr int WUB = 16;           // steps (of four rows) a wave requests at once: 64 rows, 64 loads in flight
+constexpr int LNC = 16;           // columns of a LayerNorm's gain and bias per workgroup
+constexpr int LUB = 8;            // steps (of four rows) one of its waves requests at once
+
+// A LayerNorm's parameter gradients and their step: a workgroup owns LNC columns; wave w sums the w-th eighth of the rows
+// (the tiles' qrows split), lane (i, g) the rows k + g of column i, four rows a step and LUB steps requested at once; the
+// four row phases meet by meet_kq1, the eight waves through LDS in wave order (no atomics: a fixed order).  xhat is formed
+// from the pre-LayerNorm buffer, mean and rstd as layernorm_bwd_kernel forms it.  Threads 0 .. 2 LNC - 1 then step
+// gamma's and beta's elements.
+__device__ __forceinline__ void ddpg_ln_pgrad_block(const WUArgs& G, int b, float* part, float* coef, int* upd_s) {
+    const UArgs& U = G.U;
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int i = lane & 15, g = lane >> 4;
+    const WLn W = G.ln[b >= G.ln[1].blk0 ? 1 : 0];
+    const int col = LNC * (b - W.blk0) + i;
+    const bool ok = col < W.F;
+    const int rows = G.rows;
+    const int qrows = ((rows + 4 * WNW - 1) / (4 * WNW)) << 2;
+    const int k_lo = wv * qrows;
+    int k_hi = k_lo + qrows;
+    k_hi = k_hi < rows ? k_hi : rows;
+    // the element this thread steps: which = 0 gamma, 1 beta
+    const int which = tid >> 4, ci = LNC * (b - W.blk0) + (tid & 15);
+    const bool eok = tid < 2 * LNC && ci < W.F;
+    const long ei = eok ? (which ? W.boff : W.goff) + ci : W.goff;
+    const float ep = U.theta[ei], em = U.m[ei], ev = U.v[ei], et = U.target ? U.target[ei] : 0.f;
+    if (tid == 64 * (WNW - 1)) {
+        const int st = *U.step;
+        const double bc1 = 1.0 - ipow(0.9, st), bc2 = 1.0 - ipow(0.999, st);
+        coef[0] = (float)(-((double)*U.lr / bc1));
+        coef[1] = (float)sqrt(bc2);
+        *upd_s = U.interval > 0 ? (st % U.interval == 0) : 1;
+    }
+    // addressing as the tiles': the lane's part a vector offset formed once, the step's rows a scalar offset; the
+    // descriptors end at the wave's last row, so a row past k_hi (or a column past F: OOB) loads 0
+    const unsigned kb = (unsigned)(k_hi > 0 ? k_hi : 0);
+    const rsrc_t rd = make_rsrc(W.dn, kb * (unsigned)W.lddn * 4u), rx = make_rsrc(W.pre, kb * (unsigned)W.ldp * 4u);
+    const rsrc_t rm = make_rsrc(W.mean, kb * 4u), rr = make_rsrc(W.rstd, kb * 4u);
+    const unsigned vd = ok ? ((unsigned)g * (unsigned)W.lddn + (unsigned)col) * 4u : OOB;
+    const unsigned vx = ok ? ((unsigned)g * (unsigned)W.ldp + (unsigned)col) * 4u : OOB;
+    const unsigned vs = ok ? (unsigned)g * 4u : OOB;
+#define SMX_LDL(R, v, k, sb) __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(R, v, (unsigned)(k) * (sb), 0))
+    float ag = 0.f, ab = 0.f;
+#pragma unroll 1
+    for (int k = k_lo; k < k_hi; k += 4 * LUB) {
+        float d[LUB], x[LUB], m[LUB], rs[LUB];
+#pragma unroll
+        for (int u = 0; u < LUB; ++u) {
+            d[u] = SMX_LDL(rd, vd, k + 4 * u, 4u * (unsigned)W.lddn);
+            x[u] = SMX_LDL(rx, vx, k + 4 * u, 4u * (unsigned)W.ldp);
+            m[u] = SMX_LDL(rm, vs, k + 4 * u, 4u);
+            rs[u] = SMX_LDL(rr, vs, k + 4 * u, 4u);
+        }
+#pragma unroll
+        for (int u = 0; u < LUB; ++u) {
+            const float xh = (x[u] - m[u]) * rs[u];
+            ag += d[u] * xh;
+            ab += d[u];
+        }
+    }
+#undef SMX_LDL
+    ag = meet_kq1(ag);
+    ab = meet_kq1(ab);
+    if (g == 0) { part[(wv * 2 + 0) * LNC + i] = ag; part[(wv * 2 + 1) * LNC + i] = ab; }
+    __syncthreads();
+    if (eok) {
+        float gsum = part[(0 * 2 + which) * LNC + (tid & 15)];
+#pragma unroll
+        for (int w = 1; w < WNW; ++w) gsum += part[(w * 2 + which) * LNC + (tid & 15)];      // the waves' row ranges in order
+        U.grads_out[ei] = gsum;
+        float pn, tn;
+        bool tw;
+        ddpg_step_element(U, ei, gsum, ep, em, ev, et, coef[0], coef[1], *upd_s, pn, tn, tw);
+    }
+}
 
 __global__ __launch_bounds__(64 * WNW) void ddpg_rows_wgrad_update_kernel(WUArgs G) {
     __shared__ float red[WNW][4][64][4];            // every wave's four quadrant accumulators (32 KB)
@@ -624,7 +877,11 @@ __global__ __launch_bounds__(64 * WNW) void ddpg_rows_wgrad_update_kernel(WUArgs
     const int tid = threadIdx.x, lane = tid & 63;
     const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int i = lane & 15, g = lane >> 4;
-    if ((int)blockIdx.x == G.tiles) {               // the workgroup behind the last tile: the statistics
+    if ((int)blockIdx.x >= G.tiles) {               // behind the last tile: the LayerNorms' workgroups, then the statistics
+        if ((int)blockIdx.x < G.tiles + G.ln_blocks) {
+            ddpg_ln_pgrad_block(G, (int)blockIdx.x - G.tiles, &red[0][0][0][0], coef, &upd_s);
+            return;
+        }
         float* mirror = G.stats_host ? G.stats_host + (G.stats2 ? 16 : 8) * (*G.U.step & 1) : nullptr;
         ddpg_stats_block<64 * WNW>(G.s_q, G.s_y, G.s_rewards, G.s_actions, G.s_A, G.s_A, G.s_q_actor, (long)G.rows, G.stats,
                                    mirror);
@@ -850,6 +1107,46 @@ int lds_floats(const Dims& d, RArgs* G, bool td3 = false) {
     return o;
 }
 
+// The LayerNorm chains' carve-up: the plain one with tiles A and B wide enough for either network's rows (they take
+// turns in them), then the two pre-LayerNorm tiles (layer 1's, layer 2's: kept for the backward rules beside the
+// LayerNorm outputs), the dn tile and four statistics slots of (mean [4], rstd [4])
+int lds_floats_ln(const Dims& d, RArgs* G, LnProg* Q) {
+    constexpr int RB = RBLK;
+    const int pad = 16;
+    auto mx = [](int a, int b) { return a > b ? a : b; };
+    const int ldx = r64(d.D) + pad;
+    const int wa = mx(mx(d.H1, d.c2), d.H2), wb = mx(d.H2, d.c2), wc = mx(d.c1 + d.A, d.H1);
+    const int ldA = r64(wa) + pad, ldB = r64(wb) + pad, ldC = r64(wc) + pad;
+    const int ldP1 = r64(mx(d.H1, d.c1)) + pad, ldP2 = r64(mx(d.H2, d.c2)) + pad;
+    const int ldD = r64(mx(mx(d.H1, d.H2), mx(d.c1, d.c2))) + pad;
+    int o = 0;
+    const int oX = o; o += RB * ldx;
+    const int oXn = o; o += RB * ldx;
+    const int oA = o; o += RB * ldA;
+    const int oB = o; o += RB * ldB;
+    const int oC = o; o += RB * ldC;
+    const int oO = o; o += RB * LDO;
+    const int oO2 = o; o += RB * LDO;
+    const int oO3 = o; o += RB * LDO;
+    const int oZ = o; o += RB * LDK4;
+    const int oS = o; o += 16;
+    const int oR = o; o += DNWV * 2 * 4 * 16;
+    o += 128;                     // the K loop's prefetch reads up to two chunks past a tile's last row
+    const int oP1 = o; o += RB * ldP1;
+    const int oP2 = o; o += RB * ldP2;
+    const int oD = o; o += RB * ldD;
+    const int oM = o; o += 4 * 2 * RB;
+    if (G) {
+        G->ldx = ldx; G->ldA = ldA; G->ldB = ldB; G->ldC = ldC;
+        G->oX = oX; G->oXn = oXn; G->oA = oA; G->oB = oB; G->oC = oC; G->oO = oO; G->oO2 = oO2; G->oO3 = oO3;
+        G->oZ = oZ; G->oS = oS; G->oR = oR; G->oY = o; G->total = o;
+    }
+    if (Q) {
+        Q->oP1 = oP1; Q->ldP1 = ldP1; Q->oP2 = oP2; Q->ldP2 = ldP2; Q->oD = oD; Q->ldD = ldD; Q->oM = oM;
+    }
+    return o;
+}
+
 bool dims_ok(const Dims& d, bool td3 = false) {
     return d.D > 0 && d.A > 0 && d.A <= 32 && d.H1 > 0 && d.H2 > 0 && d.c1 > 0 && d.c2 > 0 && d.D <= 2048 &&
            d.H1 % 4 == 0 && d.H2 % 4 == 0 && d.c1 % 4 == 0 && d.c2 % 4 == 0 && d.H1 <= 1024 && d.H2 <= 1024 &&
@@ -879,6 +1176,10 @@ bool offsets_ok(const Dims& d, int64_t rows) {
     return rows * widest * 4 < (1ll << 31);
 }
 
+bool dims_ok_ln(const Dims& d) {
+    return dims_ok(d) && lds_floats_ln(d, nullptr, nullptr) * (int)sizeof(float) <= MAX_LDS;
+}
+
 PMat pmat2(const smx_ddpg_rows_second& s, const Dims& d, int b) {
     PMat m;
     block_shape(d, second_as_first[b], m.M, m.K);
@@ -886,9 +1187,10 @@ PMat pmat2(const smx_ddpg_rows_second& s, const Dims& d, int b) {
     return m;
 }
 
-int fill(RArgs& G, const smx_ddpg_rows_t* a, bool td3 = false) {
+int fill(RArgs& G, const smx_ddpg_rows_t* a, bool td3 = false, LnProg* Q = nullptr) {
     SMX_REQUIRE(a && a->packed, SMX_E_NULL);
     const Dims d = dims_of(*a);
+    SMX_REQUIRE(!a->ln || (Q && !td3 && !a->second), SMX_E_UNSUPPORTED);      // LayerNorm: one critic, its own launches
     SMX_REQUIRE(a->rows > 0 && a->rows < (1 << 24), SMX_E_SHAPE);
     SMX_REQUIRE(dims_ok(d, td3), SMX_E_UNSUPPORTED);
     {
@@ -923,6 +1225,17 @@ int fill(RArgs& G, const smx_ddpg_rows_t* a, bool td3 = false) {
     G.step = a->step;
     lds_floats(d, &G, td3);
     G.tbuf = g_tbuf;
+    if (a->ln) {
+        const smx_ddpg_rows_ln* l = a->ln;
+        SMX_REQUIRE(dims_ok_ln(d), SMX_E_UNSUPPORTED);
+        SMX_REQUIRE(offsets_ok(d, a->rows), SMX_E_SHAPE);
+        const smx_ddpg_ln_net* ln[4] = {&l->actor, &l->critic, &l->target_actor, &l->target_critic};
+        for (int k = 0; k < 4; ++k) SMX_REQUIRE(ln[k]->g1 && ln[k]->b1 && ln[k]->g2 && ln[k]->b2, SMX_E_NULL);
+        SMX_REQUIRE(l->eps > 0.f, SMX_E_SHAPE);
+        memset(Q, 0, sizeof(*Q));
+        lds_floats_ln(d, &G, Q);
+        Q->eps = l->eps;
+    }
     if (td3) {
         const smx_ddpg_rows_second* s = a->second;
         SMX_REQUIRE(s && s->packed2, SMX_E_NULL);
@@ -985,6 +1298,72 @@ void actor_program(const RArgs& G, Prog& P) {
     P.s[n] = step(G.oA, G.ldA, G.aW2T, nullptr, A_MASK, -1, 0, G.dz1a, G.H1, P_NONE);
     P.s[n].mask_off = G.oC; P.s[n].ldm = G.ldC; ++n;
     P.n = n;
+}
+
+// The LayerNorm chains: the same products (13 and 6).  A hidden layer writes relu(z) to a pre-LayerNorm tile (P1 behind a
+// first layer, P2 behind a second) and the rule puts the normalised rows where the plain chain has the layer's output; a
+// backward product leaves dn in the dn tile and the rule puts the gradient at the ReLU's input where the plain chain has
+// the masked product.  With LayerNorm h2c, h1a, h2a name the LayerNorm OUTPUTS (what the weight gradients multiply).
+void ln_fwd(LnProg& Q, int si, const Step& S, const float* gamma, const float* beta, int t_off, int ldt, float* n, int ldn,
+            float* mean, float* rstd, int st) {
+    LnStep& T = Q.s[si];
+    T.kind = LN_FWD; T.F = S.M; T.gamma = gamma; T.beta = beta; T.p_off = S.out_off; T.ldp = S.ldo; T.t_off = t_off;
+    T.ldt = ldt; T.n = n; T.ldn = ldn; T.mean = mean; T.rstd = rstd; T.st = st;
+}
+void ln_bwd(LnProg& Q, int si, int F, const float* gamma, int p_off, int ldp, int t_off, int ldt, float* n, int ldn, int st) {
+    LnStep& T = Q.s[si];
+    T.kind = LN_BWD; T.F = F; T.gamma = gamma; T.p_off = p_off; T.ldp = ldp; T.d_off = Q.oD; T.ldd = Q.ldD; T.t_off = t_off;
+    T.ldt = ldt; T.n = n; T.ldn = ldn; T.st = st;
+}
+
+void critic_program_ln(const RArgs& G, const smx_ddpg_rows_ln& l, Prog& P, LnProg& Q) {
+    const int ldc = G.c1 + G.A;
+    const int P1 = Q.oP1, l1 = Q.ldP1, P2 = Q.oP2, l2 = Q.ldP2;
+    int n = 0;
+    P.s[n] = step(G.oXn, G.ldx, G.ta.W1, G.ta.b1, A_RELU, P1, l1, nullptr, 0, P_NONE);                // mu'(s')
+    ln_fwd(Q, n, P.s[n], l.target_actor.g1, l.target_actor.b1, G.oA, G.ldA, nullptr, 0, nullptr, nullptr, 0); ++n;
+    P.s[n] = step(G.oA, G.ldA, G.ta.W2, G.ta.b2, A_RELU, P2, l2, nullptr, 0, P_NONE);
+    ln_fwd(Q, n, P.s[n], l.target_actor.g2, l.target_actor.b2, G.oB, G.ldB, nullptr, 0, nullptr, nullptr, 1); ++n;
+    P.s[n++] = step(G.oB, G.ldB, G.ta.W3, G.ta.b3, A_TANH, G.oO, LDO, nullptr, 0, P_NONE);
+    P.s[n] = step(G.oXn, G.ldx, G.tc.W1, G.tc.b1, A_RELU, P1, l1, nullptr, 0, P_TC_CAT);              // Q'(s', mu'(s'))
+    ln_fwd(Q, n, P.s[n], l.target_critic.g1, l.target_critic.b1, G.oC, G.ldC, nullptr, 0, nullptr, nullptr, 0); ++n;
+    P.s[n] = step(G.oC, G.ldC, G.tc.W2, G.tc.b2, A_RELU, P2, l2, nullptr, 0, P_NONE);
+    ln_fwd(Q, n, P.s[n], l.target_critic.g2, l.target_critic.b2, G.oB, G.ldB, nullptr, 0, nullptr, nullptr, 1); ++n;
+    P.s[n++] = step(G.oB, G.ldB, G.tc.W3, G.tc.b3, A_NONE, G.oO2, LDO, nullptr, 0, P_NONE);
+    P.s[n] = step(G.oX, G.ldx, G.c.W1, G.c.b1, A_RELU, P1, l1, l.c_a1, G.c1, P_C_CAT);                // Q(s, a)
+    ln_fwd(Q, n, P.s[n], l.critic.g1, l.critic.b1, G.oC, G.ldC, G.xcat, ldc, l.cm1, l.cr1, 0); ++n;
+    P.s[n] = step(G.oC, G.ldC, G.c.W2, G.c.b2, A_RELU, P2, l2, l.c_a2, G.c2, P_NONE);
+    ln_fwd(Q, n, P.s[n], l.critic.g2, l.critic.b2, G.oB, G.ldB, G.h2c, G.c2, l.cm2, l.cr2, 1); ++n;
+    P.s[n] = step(G.oB, G.ldB, G.c.W3, G.c.b3, A_NONE, G.oO, LDO, nullptr, 0, P_LOSS);                // -> y, dz3, dn2
+    ln_bwd(Q, n, G.c2, l.critic.g2, P2, l2, G.oA, G.ldA, G.dz2, G.c2, 1); ++n;                        // -> dz2
+    P.s[n] = step(G.oA, G.ldA, G.cW2Tlo, nullptr, A_NONE, Q.oD, Q.ldD, G.dxcat, ldc, P_NONE);         // dn1
+    ln_bwd(Q, n, G.c1, l.critic.g1, P1, l1, -1, 0, l.dz1c, G.c1, 0); ++n;                             // -> dz1
+    P.s[n] = step(G.oX, G.ldx, G.a.W1, G.a.b1, A_RELU, P1, l1, l.a1, G.H1, P_NONE);                   // mu(s), kept
+    ln_fwd(Q, n, P.s[n], l.actor.g1, l.actor.b1, G.oA, G.ldA, G.h1a, G.H1, l.am1, l.ar1, 0); ++n;
+    P.s[n] = step(G.oA, G.ldA, G.a.W2, G.a.b2, A_RELU, P2, l2, l.a2, G.H2, P_NONE);
+    ln_fwd(Q, n, P.s[n], l.actor.g2, l.actor.b2, G.oB, G.ldB, G.h2a, G.H2, l.am2, l.ar2, 1); ++n;
+    P.s[n++] = step(G.oB, G.ldB, G.a.W3, G.a.b3, A_TANH, -1, 0, G.act, G.A, P_NONE);
+    P.n = n;
+    Q.dn2 = l.dn2;
+}
+static_assert(LN_STEPS >= 13, "the LayerNorm critic chain has 13 layers");
+
+void actor_program_ln(const RArgs& G, const smx_ddpg_rows_ln& l, Prog& P, LnProg& Q) {
+    const int P1 = Q.oP1, l1 = Q.ldP1, P2 = Q.oP2, l2 = Q.ldP2;
+    int n = 0;
+    P.s[n] = step(G.oX, G.ldx, G.c.W1, G.c.b1, A_RELU, P1, l1, nullptr, 0, P_A_CAT);                  // Q(s, mu(s))
+    ln_fwd(Q, n, P.s[n], l.critic.g1, l.critic.b1, G.oC, G.ldC, nullptr, 0, nullptr, nullptr, 0); ++n;
+    P.s[n] = step(G.oC, G.ldC, G.c.W2, G.c.b2, A_RELU, P2, l2, nullptr, 0, P_NONE);
+    ln_fwd(Q, n, P.s[n], l.critic.g2, l.critic.b2, G.oB, G.ldB, nullptr, 0, nullptr, nullptr, 1); ++n;
+    P.s[n] = step(G.oB, G.ldB, G.c.W3, G.c.b3, A_NONE, -1, 0, G.q_actor, 1, P_A_DQ);                  // -> dn2
+    ln_bwd(Q, n, G.c2, l.critic.g2, P2, l2, G.oA, G.ldA, nullptr, 0, 1); ++n;     // back through the critic's LayerNorm 2 only
+    P.s[n++] = step(G.oA, G.ldA, G.cW2Thi, nullptr, A_NONE, G.oO2, LDO, nullptr, 0, P_A_TANH);        // d/d(action)
+    P.s[n] = step(G.oZ, LDK4, G.aW3T, nullptr, A_NONE, Q.oD, Q.ldD, l.dn2a, G.H2, P_NONE);            // the actor's dn2, dn1
+    ln_bwd(Q, n, G.H2, l.actor.g2, P2, l2, G.oA, G.ldA, G.dz2a, G.H2, 3); ++n;                        // (a2, a1: staged)
+    P.s[n] = step(G.oA, G.ldA, G.aW2T, nullptr, A_NONE, Q.oD, Q.ldD, l.dn1a, G.H1, P_NONE);
+    ln_bwd(Q, n, G.H1, l.actor.g1, P1, l1, -1, 0, G.dz1a, G.H1, 2); ++n;
+    P.n = n;
+    Q.a1 = l.a1; Q.a2 = l.a2; Q.am1 = l.am1; Q.ar1 = l.ar1; Q.am2 = l.am2; Q.ar2 = l.ar2;
 }
 
 // TD3's critic chain (ddpg.py:266-283, 312-319): both target critics (the second at the noised action), then each
@@ -1052,6 +1431,13 @@ extern "C" int32_t smx_ddpg_rows_second_supported(int32_t D, int32_t A, int32_t 
     return rows > 0 && rows < (1 << 24) && dims_ok(d, true) && offsets_ok(d, rows) ? 1 : 0;
 }
 
+extern "C" int32_t smx_ddpg_rows_ln_supported(int32_t D, int32_t A, int32_t H1, int32_t H2, int32_t c1, int32_t c2,
+                                              int64_t rows) {
+    Dims d;
+    d.D = D; d.A = A; d.H1 = H1; d.H2 = H2; d.c1 = c1; d.c2 = c2;
+    return smx_ddpg_rows_supported_at(D, A, H1, H2, c1, c2, rows) && dims_ok_ln(d) && offsets_ok(d, rows) ? 1 : 0;
+}
+
 extern "C" int64_t smx_ddpg_rows_second_packed_floats(int32_t D, int32_t A, int32_t H1, int32_t H2, int32_t c1, int32_t c2) {
     Dims d;
     d.D = D; d.A = A; d.H1 = H1; d.H2 = H2; d.c1 = c1; d.c2 = c2;
@@ -1092,6 +1478,7 @@ extern "C" int smx_ddpg_rows_pack_f32(const smx_ddpg_rows_t* a, int32_t which, s
     SMX_REQUIRE(a && a->packed, SMX_E_NULL);
     const Dims d = dims_of(*a);
     SMX_REQUIRE(dims_ok(d), SMX_E_UNSUPPORTED);
+    SMX_REQUIRE(!(a->ln && (a->second || which == SMX_DDPG_PACK_SECOND)), SMX_E_UNSUPPORTED);
     if (which == SMX_DDPG_PACK_SECOND) return pack_second(a, d, stream);
     SMX_REQUIRE(which == SMX_DDPG_PACK_ALL || which == SMX_DDPG_PACK_CRITIC, SMX_E_SHAPE);
     const int ldc = d.c1 + d.A;
@@ -1119,13 +1506,56 @@ extern "C" int smx_ddpg_rows_pack_f32(const smx_ddpg_rows_t* a, int32_t which, s
     return SMX_OK;
 }
 
+namespace {
+int launch_critic_ln(const smx_ddpg_rows_t* a, RArgs& G, LnProg& Q, smx_stream_t stream) {
+    const smx_ddpg_rows_ln& l = *a->ln;
+    SMX_REQUIRE(l.c_a1 && l.cm1 && l.cr1 && l.c_a2 && l.cm2 && l.cr2 && l.dn2 && l.dz1c && l.a1 && l.am1 && l.ar1 && l.a2 &&
+                    l.am2 && l.ar2, SMX_E_NULL);
+    const int bytes = G.total * (int)sizeof(float);
+    static int set = 0;
+    if (set < bytes) {
+        const int e = set_lds((const void*)ddpg_rows4_ln_kernel<0>, bytes);
+        if (e) return e;
+        set = bytes;
+    }
+    Prog P;
+    memset(&P, 0, sizeof(P));
+    critic_program_ln(G, l, P, Q);
+    hipLaunchKernelGGL(ddpg_rows4_ln_kernel<0>, dim3((unsigned)((G.rows + RBLK - 1) / RBLK)), dim3(DNTH), bytes, smx_s(stream),
+                       G, P, Q);
+    SMX_LAUNCH_CHECK();
+    return SMX_OK;
+}
+
+int launch_actor_ln(const smx_ddpg_rows_t* a, RArgs& G, LnProg& Q, smx_stream_t stream) {
+    const smx_ddpg_rows_ln& l = *a->ln;
+    SMX_REQUIRE(l.a1 && l.am1 && l.ar1 && l.a2 && l.am2 && l.ar2 && l.dn2a && l.dn1a, SMX_E_NULL);
+    const int bytes = G.total * (int)sizeof(float);
+    static int set = 0;
+    if (set < bytes) {
+        const int e = set_lds((const void*)ddpg_rows4_ln_kernel<1>, bytes);
+        if (e) return e;
+        set = bytes;
+    }
+    Prog P;
+    memset(&P, 0, sizeof(P));
+    actor_program_ln(G, l, P, Q);
+    hipLaunchKernelGGL(ddpg_rows4_ln_kernel<1>, dim3((unsigned)((G.rows + RBLK - 1) / RBLK)), dim3(DNTH), bytes, smx_s(stream),
+                       G, P, Q);
+    SMX_LAUNCH_CHECK();
+    return SMX_OK;
+}
+}  // namespace
+
 extern "C" int smx_ddpg_rows_critic_f32(const smx_ddpg_rows_t* a, smx_stream_t stream) {
     RArgs G;
-    const int rc = fill(G, a);
+    LnProg Q;
+    const int rc = fill(G, a, false, &Q);
     if (rc) return rc;
     SMX_REQUIRE(a->x && a->x_next && a->actions && a->rewards && a->dones, SMX_E_NULL);
     SMX_REQUIRE(a->xcat && a->h2c && a->q && a->q_next && a->y && a->dz3 && a->dz2 && a->dxcat && a->h1a && a->h2a &&
                     a->act, SMX_E_NULL);
+    if (a->ln) return launch_critic_ln(a, G, Q, stream);
     const int bytes = G.total * (int)sizeof(float);
     static int set = 0;
     if (set < bytes) {
@@ -1167,9 +1597,11 @@ extern "C" int smx_ddpg_rows_critic_td3_f32(const smx_ddpg_rows_t* a, smx_stream
 
 extern "C" int smx_ddpg_rows_actor_f32(const smx_ddpg_rows_t* a, smx_stream_t stream) {
     RArgs G;
-    const int rc = fill(G, a);
+    LnProg Q;
+    const int rc = fill(G, a, false, &Q);
     if (rc) return rc;
     SMX_REQUIRE(a->x && a->h1a && a->h2a && a->act && a->q_actor && a->dz3a && a->dz2a && a->dz1a, SMX_E_NULL);
+    if (a->ln) return launch_actor_ln(a, G, Q, stream);
     const int bytes = G.total * (int)sizeof(float);
     static int set = 0;
     if (set < bytes) {
@@ -1257,6 +1689,7 @@ int fill_update(UArgs& U, const smx_ddpg_rows_t* a, int32_t group, const smx_ddp
 extern "C" int smx_ddpg_rows_update_f32(const smx_ddpg_rows_t* a, int32_t group, const smx_ddpg_update_t* u,
                                         smx_stream_t stream) {
     SMX_REQUIRE(a && a->packed && u, SMX_E_NULL);
+    SMX_REQUIRE(!a->ln, SMX_E_UNSUPPORTED);          // (the LayerNorm path steps with its gradients: _wgrad_update_f32)
     const Dims d = dims_of(*a);
     SMX_REQUIRE(dims_ok(d), SMX_E_UNSUPPORTED);
     UArgs U;
@@ -1273,6 +1706,9 @@ extern "C" int smx_ddpg_rows_wgrad_update_f32(const smx_ddpg_rows_t* a, int32_t 
     const Dims d = dims_of(*a);
     SMX_REQUIRE(dims_ok(d), SMX_E_UNSUPPORTED);
     SMX_REQUIRE(a->rows > 0 && a->rows < (1 << 24), SMX_E_SHAPE);
+    const smx_ddpg_rows_ln* l = a->ln;
+    SMX_REQUIRE(!l || (!a->second && group != SMX_DDPG_GROUP_CRITIC2 && dims_ok_ln(d) && offsets_ok(d, a->rows)),
+                SMX_E_UNSUPPORTED);
     WUArgs G;
     memset(&G, 0, sizeof(G));
     const int rc = fill_update(G.U, a, group, u, d);
@@ -1287,9 +1723,10 @@ extern "C" int smx_ddpg_rows_wgrad_update_f32(const smx_ddpg_rows_t* a, int32_t 
     const smx_ddpg_net_t& tnet = c2nd ? s2->target_critic2 : cr ? a->target_critic : a->target_actor;
     const int ldc = d.c1 + d.A;
     // (gradient, input) of the three layers: the buffers the chain launches wrote
-    const float* dz[3] = {c2nd ? s2->dxcat2 : cr ? a->dxcat : a->dz1a, c2nd ? s2->dz2_2 : cr ? a->dz2 : a->dz2a,
+    // (LayerNorm: the critic's dz1 is a buffer of its own, dxcat keeps dn1; h2c / h1a / h2a are the LayerNorm outputs)
+    const float* dz[3] = {c2nd ? s2->dxcat2 : cr ? (l ? l->dz1c : a->dxcat) : a->dz1a, c2nd ? s2->dz2_2 : cr ? a->dz2 : a->dz2a,
                           c2nd ? s2->dz3_2 : cr ? a->dz3 : a->dz3a};
-    const int ldz[3] = {cr ? ldc : d.H1, cr ? d.c2 : d.H2, cr ? 1 : d.A};
+    const int ldz[3] = {cr ? (l ? d.c1 : ldc) : d.H1, cr ? d.c2 : d.H2, cr ? 1 : d.A};
     const float* x[3] = {a->x, c2nd ? s2->xcat2 : cr ? a->xcat : a->h1a, c2nd ? s2->h2c2 : cr ? a->h2c : a->h2a};
     const int ldx[3] = {d.D, cr ? ldc : d.H1, cr ? d.c2 : d.H2};
     const float* b[3] = {net.b1, net.b2, net.b3};
@@ -1312,9 +1749,37 @@ extern "C" int smx_ddpg_rows_wgrad_update_f32(const smx_ddpg_rows_t* a, int32_t 
     {
         long covered = 0;
         for (int j = 0; j < 3; ++j) covered += (long)G.U.mat[j].M * G.U.mat[j].K + G.U.mat[j].M;
+        if (l) covered += 2l * ((cr ? d.c1 : d.H1) + (cr ? d.c2 : d.H2));      // ... or a LayerNorm's gain or bias
         SMX_REQUIRE(covered == u->n, SMX_E_SHAPE);
     }
     G.tiles = tiles;
+    if (l) {
+        const smx_ddpg_ln_net& p = cr ? l->critic : l->actor;
+        const smx_ddpg_ln_net& tp = cr ? l->target_critic : l->target_actor;
+        const float* gam[2] = {p.g1, p.g2};
+        const float* bet[2] = {p.b1, p.b2};
+        const float* tgam[2] = {tp.g1, tp.g2};
+        const float* tbet[2] = {tp.b1, tp.b2};
+        const float* dn[2] = {cr ? a->dxcat : l->dn1a, cr ? l->dn2 : l->dn2a};
+        const int lddn[2] = {cr ? ldc : d.H1, cr ? d.c2 : d.H2};
+        const float* pre[2] = {cr ? l->c_a1 : l->a1, cr ? l->c_a2 : l->a2};
+        const float* mean[2] = {cr ? l->cm1 : l->am1, cr ? l->cm2 : l->am2};
+        const float* rstd[2] = {cr ? l->cr1 : l->ar1, cr ? l->cr2 : l->ar2};
+        const int F[2] = {cr ? d.c1 : d.H1, cr ? d.c2 : d.H2};
+        int blocks = 0;
+        for (int k = 0; k < 2; ++k) {
+            SMX_REQUIRE(gam[k] && bet[k] && dn[k] && pre[k] && mean[k] && rstd[k], SMX_E_NULL);
+            WLn& W = G.ln[k];
+            W.dn = dn[k]; W.lddn = lddn[k]; W.pre = pre[k]; W.ldp = F[k]; W.mean = mean[k]; W.rstd = rstd[k]; W.F = F[k];
+            W.goff = gam[k] - u->theta; W.boff = bet[k] - u->theta;
+            SMX_REQUIRE(W.goff >= 0 && W.goff + F[k] <= u->n && W.boff >= 0 && W.boff + F[k] <= u->n, SMX_E_SHAPE);
+            if (u->target)
+                SMX_REQUIRE(tgam[k] && tbet[k] && tgam[k] - u->target == W.goff && tbet[k] - u->target == W.boff, SMX_E_SHAPE);
+            W.blk0 = blocks;
+            blocks += (F[k] + LNC - 1) / LNC;
+        }
+        G.ln_blocks = blocks;
+    }
     if (u->stats) {
         SMX_REQUIRE(a->q && a->y && a->rewards && a->actions && a->q_actor, SMX_E_NULL);
         G.stats = u->stats; G.s_q = a->q; G.s_y = a->y; G.s_rewards = a->rewards; G.s_actions = a->actions;
@@ -1325,7 +1790,7 @@ extern "C" int smx_ddpg_rows_wgrad_update_f32(const smx_ddpg_rows_t* a, int32_t 
             G.stats2 = s2->stats2; G.s_q2 = s2->q2;
         }
     }
-    hipLaunchKernelGGL(ddpg_rows_wgrad_update_kernel, dim3((unsigned)(tiles + (u->stats ? 1 : 0))), dim3(64 * WNW), 0,
+    hipLaunchKernelGGL(ddpg_rows_wgrad_update_kernel, dim3((unsigned)(tiles + G.ln_blocks + (u->stats ? 1 : 0))), dim3(64 * WNW), 0,
                        smx_s(stream), G);
     SMX_LAUNCH_CHECK();
     return SMX_OK;

@@ -945,44 +945,10 @@ __device__ __forceinline__ long long ring_row(const DArgs& G, int kemit, long a)
 }
 
 // LayerNorm over the F features of the block's RB rows of a hidden tile, in place (behind the barrier that ends the
-// layer; the caller barriers after it).  One wavefront owns a row, the rows dealt over the RNWV waves; lane j takes the
-// columns j + 64 c, c ascending, and the expressions are layernorm_fwd_kernel's (smx_ddpg.hip), its zero terms for the
-// columns past F left out: given the same row the result has the bits smx_layernorm_forward_f32 produces, whatever RB
-// and whichever wave.  Only columns < F are written: the tile's padding stays zero.  A lane's columns are consecutive
-// words across the wave: no bank is hit twice.  gb = gamma [F] | beta [F].
+// layer; the caller barriers after it): ln_rows of smx_ln_rows.inc.h, which the DDPG row schedule shares -- given the same
+// row the result has the bits smx_layernorm_forward_f32 produces.  gb = gamma [F] | beta [F].
 constexpr int RLN_MAXC = 10;                         // columns per lane: H1, H2 <= 640
-template <int RB>
-__device__ __forceinline__ void ln_rows(float* tile, int ld, int F, const float* gb, float eps, int wv, int lane) {
-#pragma unroll 1
-    for (int r = wv; r < RB; r += RNWV) {
-        float* xr = tile + r * ld;
-        float v[RLN_MAXC];
-        float s = 0.f;
-#pragma unroll
-        for (int c = 0; c < RLN_MAXC; ++c) {
-            if (64 * c >= F) break;                  // (wave-uniform)
-            const int j = lane + 64 * c;
-            v[c] = (j < F) ? xr[j] : 0.f;
-            s += v[c];
-        }
-        const float m = smx_wave_sum(s) / (float)F;
-        float q = 0.f;
-#pragma unroll
-        for (int c = 0; c < RLN_MAXC; ++c) {
-            if (64 * c >= F) break;
-            const int j = lane + 64 * c;
-            const float d = (j < F) ? v[c] - m : 0.f;
-            q += d * d;
-        }
-        const float rs = 1.0f / sqrtf(smx_wave_sum(q) / (float)F + eps);
-#pragma unroll
-        for (int c = 0; c < RLN_MAXC; ++c) {
-            if (64 * c >= F) break;
-            const int j = lane + 64 * c;
-            if (j < F) xr[j] = ((v[c] - m) * rs) * gb[j] + gb[F + j];
-        }
-    }
-}
+#include "smx_ln_rows.inc.h"
 
 // RG row groups of four actors per workgroup; NT feature tiles a wave carries per pass.  Every block size gives the same
 // bits (layers4).
@@ -1028,8 +994,10 @@ __global__ __launch_bounds__(RNTH) void ddpg_rollout_kernel(DdpgArgs<POP, LN> G)
         if constexpr (LN) {
             layers4<RG, NT>(net, sm, 3, SMX_ACT_TANH, wv, lane, [&](int l) {
                 if (l < 2) {
-                    ln_rows<RB>(sm + (l == 0 ? G.off_h1 : G.off_h2), l == 0 ? G.ldh1 : G.ldh2, l == 0 ? G.H1 : G.H2,
-                                gb + (l == 0 ? 0 : 2 * G.H1), G.ln.eps, wv, lane);
+                    float* tile = sm + (l == 0 ? G.off_h1 : G.off_h2);
+                    const int ld = l == 0 ? G.ldh1 : G.ldh2, F = l == 0 ? G.H1 : G.H2;
+                    const float* g = gb + (l == 0 ? 0 : 2 * G.H1);
+                    ln_rows<RB, RNWV, RLN_MAXC>(tile, ld, tile, ld, F, g, g + F, G.ln.eps, wv, lane, LnNoEmit{});
                     SMX_LDS_BARRIER();
                 }
             }, 0, G.D, PreLayer{}, sh);

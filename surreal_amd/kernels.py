@@ -22,6 +22,13 @@ def _row_stride(view, width):
     return view.stride(0) if view.shape[0] > 1 else max(view.stride(0), width)
 
 
+def ddpg_rows_ln(kernels):
+    """whether `kernels` runs a use_layernorm DDPG iteration (one critic) on the row schedule -- the ddpg_rows_ln_supported /
+    ddpg_rows_ln_attach methods below: its `ddpg_rows_ln` attribute; an object without it keeps LayerNorm learners on the
+    layer schedule"""
+    return bool(getattr(kernels, 'ddpg_rows_ln', False))
+
+
 def ddpg_rows_td3(kernels):
     """whether this kernels object runs TD3 (a second critic, clipped noise on the target action) on the row schedule --
     the ddpg_rows_second_* / ddpg_rows_critic_td3 methods below: its `ddpg_rows_td3` attribute; an object without it
@@ -815,6 +822,8 @@ class HipKernels(object):
     ddpg_ln_launch = True
     # TD3 on the row schedule (ddpg_rows_td3(), above)
     ddpg_rows_td3 = True
+    # use_layernorm on the row schedule (ddpg_rows_ln(), above)
+    ddpg_rows_ln = True
 
     def synth_ddpg_rollout_supported(self, net, ln=False):
         """the actor shapes synth_ddpg_rollout takes; ln: with a LayerNorm behind each hidden ReLU"""
@@ -1153,6 +1162,31 @@ class HipKernels(object):
 
     def ddpg_rows_critic_td3(self, args):
         L.call('smx_ddpg_rows_critic_td3_f32', ctypes.byref(args), self._st())
+
+    # use_layernorm: the four networks' gains and biases and the extra buffers ride in args.ln (smx_ddpg_rows_ln); the
+    # chain launches and the gradient-and-step launch around it honour it, the other entries refuse it
+    def ddpg_rows_ln_supported(self, D, A, H1, H2, c1, c2, rows):
+        return bool(self.lib.smx_ddpg_rows_ln_supported(D, A, H1, H2, c1, c2, int(rows)))
+
+    def ddpg_rows_ln_attach(self, args, ln_nets, eps, io_ln):
+        """attach the LayerNorms to a ddpg_rows_args block.  ln_nets: {'actor' | 'critic' | 'target_actor' | 'target_critic':
+        {'ln1.W', 'ln1.b', 'ln2.W', 'ln2.b'}} (views into the parameter buffers); io_ln: c_a1, cm1, cr1, c_a2, cm2, cr2, dn2,
+        dz1c, a1, am1, ar1, a2, am2, ar2, dn2a, dn1a.  The block's xcat[:, :c1], h2c, h1a, h2a are then the LayerNorm
+        OUTPUTS (include/surreal_amd.h).  Returns args."""
+        s = L.DdpgRowsLn()
+        for name in ('actor', 'critic', 'target_actor', 'target_critic'):
+            n = getattr(s, name)
+            for k, f in (('ln1.W', 'g1'), ('ln1.b', 'b1'), ('ln2.W', 'g2'), ('ln2.b', 'b2')):
+                setattr(n, f, ln_nets[name][k].data_ptr())
+        s.eps = float(eps)
+        for k in ('c_a1', 'cm1', 'cr1', 'c_a2', 'cm2', 'cr2', 'dn2', 'dz1c', 'a1', 'am1', 'ar1', 'a2', 'am2', 'ar2', 'dn2a',
+                  'dn1a'):
+            t = io_ln[k]
+            assert t.is_contiguous(), k
+            setattr(s, k, t.data_ptr())
+        args.ln = ctypes.pointer(s)
+        args._refs_ln = (s, ln_nets, io_ln)
+        return args
 
     def ddpg_rows_update(self, args, group, theta, grads, exp_avg, exp_avg_sq, lr, step, weight_decay, clip_value,
                          target=None, tau=0.0, interval=0, wgrad=False, stats=None, stats_host=None):

@@ -29,7 +29,10 @@ observations also runs on the row blocks when session_config.learner.ddpg_row_sc
 buffers, gradients, Adam group -- is one record (_critic_workspace): the second critic's update is the first one's code.
 
 use_layernorm (default off) runs layer by layer too, with every other switch: the variant lives in DDPGModel's passes
-(actor_forward ... actor_backward), the learner's iteration is the same.  torchx's LayerNorm semantics are unpinned (its source is absent): taken as
+(actor_forward ... actor_backward), the learner's iteration is the same.  With low-dimensional observations, one critic, one
+rank and the fused update it also runs on the row blocks when session_config.learner.ddpg_row_schedule is True (4 launches,
+a LayerNorm rule behind each hidden layer's step; opt-in).  LayerNorm with a double critic, with camera observations, on
+several ranks or with ddpg_rows_fused_update = False stays layer by layer.  torchx's LayerNorm semantics are unpinned (its source is absent): taken as
 torch.nn.LayerNorm over the features.
 """
 import gc
@@ -369,6 +372,12 @@ class DDPGLearner(Learner):
         """(D, A, H1, H2, c1, c2) when the row-block kernels take these shapes (for a batch of `rows`), else None"""
         m = self.model
         dims = (D, self.action_dim, m.actor.H1, m.actor.H2, m.c1, m.c2)
+        if self.use_layernorm:
+            # LayerNorm: one critic, low-dimensional observations, one rank, the fused update (the gains' and biases'
+            # gradients are formed by the gradient-and-step launch alone) -- everything else stays layer by layer
+            ok = (rows is not None and not self.use_double_critic and not self.is_pixel_input and self.world_size == 1
+                  and self.rows_fused_update and KN.ddpg_rows_ln(self.K) and self.K.ddpg_rows_ln_supported(*dims, rows))
+            return dims if ok and self.K.ddpg_rows_supported(*dims, rows=rows) else None
         if self.use_double_critic and not (rows is not None and KN.ddpg_rows_td3(self.K)
                                            and self.K.ddpg_rows_second_supported(*dims, rows)):
             return None              # (TD3's chain keeps y between the two losses and addresses more buffers)
@@ -385,10 +394,21 @@ class DDPGLearner(Learner):
         if getattr(ws, 'stats_slots', None) is None:      # (two blocks of 8 per slot with a second critic)
             ws.stats_slots = torch.zeros(2, 16 if self.use_double_critic else 8, pin_memory=torch.cuda.is_available())
         nets = {'actor': m.actor.views, 'critic': m.critic, 'target_actor': mt.actor.views, 'target_critic': mt.critic}
-        io = dict(x=x, x_next=xn, actions=actions, rewards=rewards, dones=done, xcat=ws.xcat, h2c=ws.h2c, q=ws.q,
-                  q_next=ws.q_next, y=ws.y, dz3=ws.dz3, dz2=ws.dz2, dxcat=ws.dxcat, h1a=ws.h1a, h2a=ws.h2a, act=ws.act,
-                  q_actor=ws.q_actor, dz3a=ws.dz3a, dz2a=ws.dz2a, dz1a=ws.dz1a, step=ws.step)
+        ln = self.use_layernorm
+        # (LayerNorm: what the weight gradients multiply are the LayerNorm outputs -- the layer schedule's c_n2, n1, n2)
+        io = dict(x=x, x_next=xn, actions=actions, rewards=rewards, dones=done, xcat=ws.xcat, h2c=ws.c_n2 if ln else ws.h2c,
+                  q=ws.q, q_next=ws.q_next, y=ws.y, dz3=ws.dz3, dz2=ws.dz2, dxcat=ws.dxcat, h1a=ws.n1 if ln else ws.h1a,
+                  h2a=ws.n2 if ln else ws.h2a, act=ws.act, q_actor=ws.q_actor, dz3a=ws.dz3a, dz2a=ws.dz2a, dz1a=ws.dz1a,
+                  step=ws.step)
         ws.rows_args = K.ddpg_rows_args(dims, nets, ws.rows_packed, io, pow(self.discount_factor, self.n_step))
+        if ln:
+            # the gains and biases (read row-major from the parameter buffers: no packed copy) and exactly the layer
+            # schedule's buffers: the workspace of DDPGModel's passes and their backward scratch, allocated once
+            ln_nets = {'actor': m.actor_ln, 'critic': m.critic, 'target_actor': mt.actor_ln, 'target_critic': mt.critic}
+            io_ln = dict(c_a1=ws.c_a1, cm1=ws.cm1, cr1=ws.cr1, c_a2=ws.c_a2, cm2=ws.cm2, cr2=ws.cr2, dn2=ws.bw.dn2,
+                         dz1c=ws.bw.dz1c, a1=ws.a1, am1=ws.am1, ar1=ws.ar1, a2=ws.a2, am2=ws.am2, ar2=ws.ar2,
+                         dn2a=ws.bw.dn2a, dn1a=ws.bw.dn1a)
+            ws.rows_args = K.ddpg_rows_ln_attach(ws.rows_args, ln_nets, m.ln_eps, io_ln)
         if self.use_double_critic:
             # TD3: the second critic's networks, its own packed buffer and its own buffers -- dz2 / dxcat too (ws.bw is
             # one critic's at a time; here both critics' data gradients exist before either weight-gradient launch)
@@ -415,7 +435,12 @@ class DDPGLearner(Learner):
         TD3 (use_double_critic, with or without action regularisation): the critic chain carries both target critics --
         the second at the noised, clamped action --, y = min of the two targets and both critics' losses and data
         gradients (smx_ddpg_rows_critic_td3_f32); the second critic's step is a third update launch between the first
-        critic's and the actor chain, which goes through the first critic only.  5 launches, no ATen arithmetic."""
+        critic's and the actor chain, which goes through the first critic only.  5 launches, no ATen arithmetic.
+        use_layernorm (one critic, one rank, the fused update: _rows_dims): the same 4 launches with a LayerNorm rule behind
+        every hidden layer's step and its backward rule behind the backward products, on the buffers of DDPGModel's
+        passes; the gains' and biases' gradients and steps are further workgroups of the group's gradient-and-step launch.
+        LayerNorm with a double critic, with camera observations, on several ranks or with ddpg_rows_fused_update = False
+        stays layer by layer (_schedule)."""
         K, m, mt, A = self.K, self.model, self.model_target, self.action_dim
         B, D = x.shape
         c1, c2, ld = m.c1, m.c2, m.c1 + A
@@ -432,6 +457,7 @@ class DDPGLearner(Learner):
         # one rank: a group's weight gradients and its step are ONE launch (value clipping needs no norm over the group);
         # several: the gradients are averaged over the ranks between them
         fuse = self.world_size == 1 and self.rows_fused_update
+        assert fuse or not self.use_layernorm
         second = ws.critics[1] if self.use_double_critic else None
         if second is not None:
             K.ddpg_rows_critic_td3(args)
@@ -580,7 +606,11 @@ class DDPGLearner(Learner):
         """which launch schedule an iteration on B rows of D inputs takes -- 'rows' (row blocks), 'levels' (dependency
         levels) or 'layers' (layer by layer: every switch).  Asked at each enqueue: level_schedule / row_schedule may be
         set after construction"""
-        if not (self.use_layernorm or self.is_pixel_input):
+        if self.use_layernorm:
+            # LayerNorm takes the rows only when asked to (ddpg_row_schedule = True) and where _rows_dims lets it: one
+            # critic, low-dimensional observations, one rank, the fused update; otherwise layer by layer as before
+            return 'rows' if self.row_schedule is True and self._rows_dims(D, B) is not None else 'layers'
+        if not self.is_pixel_input:
             if self.use_double_critic:
                 # TD3 takes the rows only when asked to (ddpg_row_schedule = True), where the kernels run it and the
                 # shapes fit; unset, it stays layer by layer as before -- and there are no levels for two critics
