@@ -933,10 +933,21 @@ int smx_ddpg_stats_f32(const float* q, const float* y, const float* rewards,
  *   smx_ddpg_rows_wgrad_update_f32  also forms dgamma = sum_rows dn xhat and dbeta = sum_rows dn of the group's two
  *                             LayerNorms (further workgroups of the launch, a fixed summation order, no atomics) and steps
  *                             them: update->n covers the dense layers and, behind them, the four LayerNorm vectors.
- * Every other entry that takes smx_ddpg_rows_t returns SMX_E_UNSUPPORTED with ln set (smx_ddpg_rows_critic_td3_f32,
- * smx_ddpg_rows_update_f32), and so does `second` together with `ln`; smx_ddpg_rows_pack_f32 packs the dense weights as
- * before.  smx_ddpg_rows_ln_supported: what smx_ddpg_rows_supported_at says, narrowed by the LDS budget with the
- * pre-LayerNorm and dn tiles kept, and every row-major buffer within 31-bit byte offsets. */
+ * smx_ddpg_rows_update_f32 returns SMX_E_UNSUPPORTED with ln set, and so does every entry given `second` together with
+ * an `ln` whose own `second` is NULL; smx_ddpg_rows_pack_f32 packs the dense weights as before.
+ * smx_ddpg_rows_ln_supported: what smx_ddpg_rows_supported_at says, narrowed by the LDS budget with the
+ * pre-LayerNorm and dn tiles kept, and every row-major buffer within 31-bit byte offsets.
+ *
+ * use_layernorm together with TD3: args->second AND args->ln->second (the second critic's and its target's gains and
+ * biases, its pre-LayerNorm activations c2_a1 / c2_a2 with mean and rstd, dn2_2, and dz1c2 -- dxcat2[:, :c1] keeps
+ * d/d(LayerNorm 1's output), xcat2[:, :c1] and h2c2 receive the LayerNorm outputs).  Then
+ *   smx_ddpg_rows_critic_td3_f32  runs TD3's chain with the LayerNorm rules behind every hidden layer and behind each
+ *                             critic's loss and W2^T product (smx_ddpg_rows_critic_f32 still refuses ln with second)
+ *   smx_ddpg_rows_actor_f32   the LayerNorm actor chain, unchanged: through the first critic only
+ *   smx_ddpg_rows_wgrad_update_f32  SMX_DDPG_GROUP_CRITIC2 as SMX_DDPG_GROUP_CRITIC: the second critic's three weight
+ *                             gradients, dgamma / dbeta of its two LayerNorms, Adam, its target, the copies in packed2
+ * smx_ddpg_rows_ln_second_supported: smx_ddpg_rows_ln_supported narrowed by the LDS budget with y kept between the two
+ * losses (and what smx_ddpg_rows_second_supported says). */
 typedef struct smx_ddpg_net {          /* nn.Linear layouts: W [out, in] row-major */
     const float *W1, *b1, *W2, *b2, *W3, *b3;
 } smx_ddpg_net_t;
@@ -950,6 +961,11 @@ struct smx_ddpg_rows_second {
 struct smx_ddpg_ln_net {               /* the two LayerNorms of a network: gain and bias behind layer 1 [H1 | c1], layer 2 [H2 | c2] */
     const float *g1, *b1, *g2, *b2;
 };
+struct smx_ddpg_rows_ln_second {       /* use_layernorm with TD3's second critic: its LayerNorms and its own row-major buffers */
+    struct smx_ddpg_ln_net critic2, target_critic2;
+    float *c2_a1, *c2m1, *c2r1, *c2_a2, *c2m2, *c2r2;          /* critic phase, out: as c_a1 ... cr2 for the second critic */
+    float *dn2_2, *dz1c2;                                      /* critic phase, out: [rows, c2], [rows, c1] */
+};
 struct smx_ddpg_rows_ln {
     struct smx_ddpg_ln_net actor, critic, target_actor, target_critic;
     float eps;
@@ -957,6 +973,7 @@ struct smx_ddpg_rows_ln {
     float *dn2, *dz1c;                                         /* critic phase, out: [rows, c2], [rows, c1] */
     float *a1, *am1, *ar1, *a2, *am2, *ar2;                    /* critic phase out, actor phase in: [rows, H1], .., [rows, H2], .. */
     float *dn2a, *dn1a;                                        /* actor phase, out: [rows, H2], [rows, H1] */
+    const struct smx_ddpg_rows_ln_second* second;              /* with args->second: the second critic's part; NULL: one critic */
 };
 typedef struct smx_ddpg_rows {
     int64_t rows;
@@ -984,6 +1001,7 @@ int32_t smx_ddpg_rows_second_supported(int32_t D, int32_t A, int32_t H1, int32_t
 int64_t smx_ddpg_rows_second_packed_floats(int32_t D, int32_t A, int32_t H1, int32_t H2, int32_t c1, int32_t c2);
 int smx_ddpg_rows_critic_td3_f32(const smx_ddpg_rows_t* args, smx_stream_t stream);
 int32_t smx_ddpg_rows_ln_supported(int32_t D, int32_t A, int32_t H1, int32_t H2, int32_t c1, int32_t c2, int64_t rows);
+int32_t smx_ddpg_rows_ln_second_supported(int32_t D, int32_t A, int32_t H1, int32_t H2, int32_t c1, int32_t c2, int64_t rows);
 
 /* One optimiser group's step of the row schedule in ONE launch (round 6): Adam exactly as smx_adam_step_dev_f32
  * (torch.optim.Adam after clip_grad_value_: ddpg.py:310-311, 332-333), then the group's target network -- soft

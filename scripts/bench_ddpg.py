@@ -3,10 +3,11 @@ BASELINE configs[2] (HalfCheetah shapes D=17, A=6, uniform replay, batch 512), d
 replay shard; and the oracle (reference ATen path) on the host CPU beside it.
 
     --td3                          use_double_critic + use_action_regularization
-    --layernorm                    use_layernorm (one critic; with --row-schedule on: the LayerNorm chains of the row schedule)
+    --layernorm                    use_layernorm (with --row-schedule on: the LayerNorm chains of the row schedule; with --td3
+                                   as well: two LayerNorm critics, on either schedule)
     --row-schedule on|off|unset    session_config.learner.ddpg_row_schedule (unset: the learner's own choice)
     --ab NAME[,NAME...]            timing rounds only, the named variants interleaved inside every round -- td3_layers, td3_rows,
-                                   ln_layers, ln_rows, plain (the default learner): --rounds rounds of --calls learn() calls each, one JSON line per
+                                   ln_layers, ln_rows, ln_td3_layers, ln_td3_rows, plain (the default learner): --rounds rounds of --calls learn() calls each, one JSON line per
                                    variant (ms per call of every round, their median, min and max) appended to --jsonl
     --tree PATH                    import surreal_amd from another checkout (the parent commit beside this one, same job)
     --label TEXT                   goes into the JSON lines
@@ -46,7 +47,8 @@ def make_learner(td3, row_schedule, layernorm=False):
 
 if opt.ab:
     variants = {'td3_layers': (True, 'off'), 'td3_rows': (True, 'on'), 'plain': (False, 'unset'),
-                'ln_layers': (False, 'off', True), 'ln_rows': (False, 'on', True)}
+                'ln_layers': (False, 'off', True), 'ln_rows': (False, 'on', True),
+                'ln_td3_layers': (True, 'off', True), 'ln_td3_rows': (True, 'on', True)}
     names = [n for n in opt.ab.split(',') if n]
     learners = {n: make_learner(*variants[n])[1] for n in names}
     batches = {n: [learners[n].preprocess(synthetic.make_ddpg_batch(B, D, A, seed=s)) for s in range(8)] for n in names}
@@ -116,7 +118,7 @@ try:
     import ddpg_oracle
     params = ddpg_oracle.make_ddpg_params(D, A, (300, 200), (400, 300), seed=3, layernorm=opt.layernorm)
     td3 = dict(use_double_critic=True, use_action_regularization=True, batch_size=B,
-               params2=ddpg_oracle.make_ddpg_params(D, A, (300, 200), (400, 300), seed=4)) if opt.td3 else {}
+               params2=ddpg_oracle.make_ddpg_params(D, A, (300, 200), (400, 300), seed=4, layernorm=opt.layernorm)) if opt.td3 else {}
     O = ddpg_oracle.OracleDDPGLearner(params, A, **td3) if hasattr(ddpg_oracle, 'OracleDDPGLearner') else None
     if O is not None:
         hb = [synthetic.make_ddpg_batch(B, D, A, seed=s) for s in range(8)]

@@ -142,11 +142,17 @@ class DdpgLnNet(Structure):
     _fields_ = [(n, c_void_p) for n in ('g1', 'b1', 'g2', 'b2')]
 
 
+class DdpgRowsLnSecond(Structure):
+    """struct smx_ddpg_rows_ln_second"""
+    _fields_ = ([(n, DdpgLnNet) for n in ('critic2', 'target_critic2')] +
+                [(n, c_void_p) for n in ('c2_a1', 'c2m1', 'c2r1', 'c2_a2', 'c2m2', 'c2r2', 'dn2_2', 'dz1c2')])
+
+
 class DdpgRowsLn(Structure):
     """struct smx_ddpg_rows_ln"""
     _fields_ = ([(n, DdpgLnNet) for n in ('actor', 'critic', 'target_actor', 'target_critic')] + [('eps', c_float)] +
                 [(n, c_void_p) for n in ('c_a1', 'cm1', 'cr1', 'c_a2', 'cm2', 'cr2', 'dn2', 'dz1c', 'a1', 'am1', 'ar1', 'a2',
-                                         'am2', 'ar2', 'dn2a', 'dn1a')])
+                                         'am2', 'ar2', 'dn2a', 'dn1a')] + [('second', POINTER(DdpgRowsLnSecond))])
 
 
 class DdpgRows(Structure):
@@ -409,6 +415,7 @@ _SIGS = {
     'smx_ddpg_rows_second_packed_floats': (c_int64, [c_int32] * 6),
     'smx_ddpg_rows_critic_td3_f32': (c_int32, [_P, _P]),
     'smx_ddpg_rows_ln_supported': (c_int32, [c_int32] * 6 + [c_int64]),
+    'smx_ddpg_rows_ln_second_supported': (c_int32, [c_int32] * 6 + [c_int64]),
     'smx_ddpg_rows_update_f32': (c_int32, [_P, c_int32, _P, _P]),
     'smx_ddpg_rows_wgrad_update_f32': (c_int32, [_P, c_int32, _P, _P]),
     'smx_ddpg_stats_f32': (c_int32, [_P, _P, _P, _P, c_int32, c_int32, _P, c_int64, _P, _P]),

@@ -36,6 +36,19 @@
 //              launch, behind the tiles and in front of the statistics workgroup; no atomics
 // The gains and biases are read row-major from the parameter buffers, as the dense biases are: no packed copy.
 //
+// use_layernorm together with TD3 is the composition, TD3's five launches (ddpg_rows4_ln_kernel<2>: the chain body with
+// PHASE == 2 and LN; td3_critic_program_ln: the 20 products, a forward rule behind each of the 12 hidden layers, a backward
+// rule behind each critic's loss and behind each critic's W2^T product -- 16 rules; only that instantiation takes the
+// 20-step rule table, LnProgT<20>):
+//
+//   ddpg_rows4_ln_kernel<2>   target actor -> target critic 1 at mu'(s') -> target critic 2 at clamp(mu'(s') + noise);
+//                             critic 1 forward, y = min(y1, y2) kept in LDS, dn2, LayerNorm-2 backward, W2^T lo, LayerNorm-1
+//                             backward; the same for critic 2 against the kept y (dn2_2, dz1c2: buffers of its own); the
+//                             actor's forward pass
+//   ddpg_rows_wgrad_update    critic 1;  critic 2 (SMX_DDPG_GROUP_CRITIC2: its three weight gradients, dgamma / dbeta of its
+//                             two LayerNorms, Adam, its target, the copies inside packed2)
+//   ddpg_rows4_ln_kernel<1>   unchanged;  ddpg_rows_wgrad_update  the actor, both statistics blocks
+//
 // Activations and gradients that the weight-gradient launches read go to HBM row-major, exactly the buffers of the
 // layer-by-layer schedule.  Products are summed in the MFMA loop's order (32-wide K chunks, k ascending per lane group),
 // not in smx_linear_f32's: results agree with the layered schedule to fp32 rounding, not bit for bit.
@@ -158,6 +171,7 @@ struct Prog {
 // has left dn in tile `d`; the rule writes the gradient at the ReLU's input to tile `t` (< 0: none) and to `n`.
 enum { LN_NONE = 0, LN_FWD = 1, LN_BWD = 2 };
 constexpr int LN_STEPS = 13;         // the LayerNorm critic chain
+constexpr int LN_STEPS_TD3 = 20;     // ... of TD3 (ddpg_rows4_ln_kernel<2> alone takes the longer table)
 constexpr int LNR_MAXC = 16;         // columns per lane: F <= 1024, as layernorm_fwd_kernel
 struct LnStep {
     const float *gamma, *beta;    // (BWD: gamma only)
@@ -169,26 +183,31 @@ struct LnStep {
     int d_off, ldd;
     int st;
 };
-struct LnProg {
-    LnStep s[LN_STEPS];
+template <int N>
+struct LnProgT {
+    LnStep s[N];
     float eps;
     float* dn2;                                       // critic chain: d/d(LayerNorm 2's output) [rows][c2]
     const float *a1, *a2, *am1, *ar1, *am2, *ar2;     // actor chain: the actor's pre-LayerNorm rows and statistics
     int oP1, ldP1, oP2, ldP2, oD, ldD, oM;            // LDS (float offsets): two pre-LayerNorm tiles, dn, statistics [4][2][4]
+    float* dn2_2;                                     // TD3's critic chain: the same for the second critic (else null)
 };
+typedef LnProgT<LN_STEPS_TD3> LnProg;                 // what the host fills; the 13-step launches take its narrow() copy
 static_assert(sizeof(RArgs) + sizeof(Prog) + sizeof(LnProg) < 4096, "all go by value in the kernel arguments");
 
 // The rule's fields are wanted BEHIND the layer's K loop: at an offset the compiler cannot see through, or it loads them
 // at the head of the step (the chain's own before the loop over the steps) and keeps two dozen scalar registers occupied
 // across the K loop, which is at the register file's limit as it is
-__device__ __forceinline__ const LnStep& ln_late(const LnProg* Q, int si) {
+template <class LP>
+__device__ __forceinline__ const LnStep& ln_late(const LP* Q, int si) {
     asm volatile("" : "+s"(si));
     return Q->s[si];
 }
-__device__ __forceinline__ const LnProg* ln_late(const LnProg* Q) {
+template <class LP>
+__device__ __forceinline__ const LP* ln_late(const LP* Q) {
     int z = 0;
     asm volatile("" : "+s"(z));
-    return (const LnProg*)((const char*)Q + z);
+    return (const LP*)((const char*)Q + z);
 }
 
 __device__ __forceinline__ int behind_here(int v) {      // the same value, formed no earlier than this point
@@ -264,9 +283,9 @@ __device__ __forceinline__ void ln_bwd_rows(const float* dn, int ldd, const floa
 
 // PHASE 0: the critic chain, 1: the actor chain, 2: the critic chain of TD3 (two critics, y = min of their targets; its
 // rules exist in that instantiation only)
-// LN: the LayerNorm variant (PHASE 0, 1), its rules behind `if constexpr (LN)`; Q is null without
-template <int PHASE, bool LN>
-__device__ __forceinline__ void ddpg_rows4_chain(const RArgs& G, const Prog& P, const LnProg* Q) {
+// LN: the LayerNorm variant, its rules behind `if constexpr (LN)`; Q is null without
+template <int PHASE, bool LN, class LP>
+__device__ __forceinline__ void ddpg_rows4_chain(const RArgs& G, const Prog& P, const LP* Q) {
     extern __shared__ float sm[];
     constexpr int RB = RBLK;
     const int tid = threadIdx.x, lane = tid & 63;
@@ -512,9 +531,14 @@ __device__ __forceinline__ void ddpg_rows4_chain(const RArgs& G, const Prog& P, 
                 for (int idx = tp; idx < RB * c2; idx += DNTH) {
                     const int n = idx / c2, j = idx - n * c2;
                     float v = sm[G.oS + n] * W3[j];
-                    v = (sm[G.oB + n * G.ldB + j] > 0.f) ? v : 0.f;
-                    sm[G.oA + n * G.ldA + j] = v;
-                    if (n < nrows) dz2[(size_t)(row0 + n) * c2 + j] = v;
+                    if constexpr (LN) {              // d/d(LayerNorm 2's output) of this critic: its backward rule follows
+                        sm[Q->oD + n * Q->ldD + j] = v;
+                        if (n < nrows) (first ? Q->dn2 : Q->dn2_2)[(size_t)(row0 + n) * c2 + j] = v;
+                    } else {
+                        v = (sm[G.oB + n * G.ldB + j] > 0.f) ? v : 0.f;
+                        sm[G.oA + n * G.ldA + j] = v;
+                        if (n < nrows) dz2[(size_t)(row0 + n) * c2 + j] = v;
+                    }
                 }
                 SMX_LDS_BARRIER();
             }
@@ -579,11 +603,12 @@ __device__ __forceinline__ void ddpg_rows4_chain(const RArgs& G, const Prog& P, 
 
 template <int PHASE>
 __global__ __launch_bounds__(DNTH) void ddpg_rows4_kernel(RArgs G, Prog P) {
-    ddpg_rows4_chain<PHASE, false>(G, P, nullptr);
+    ddpg_rows4_chain<PHASE, false>(G, P, (const LnProgT<LN_STEPS>*)nullptr);
 }
 
 template <int PHASE>
-__global__ __launch_bounds__(DNTH) void ddpg_rows4_ln_kernel(RArgs G, Prog P, LnProg Q) {
+__global__ __launch_bounds__(DNTH) void ddpg_rows4_ln_kernel(RArgs G, Prog P,
+                                                             LnProgT<PHASE == 2 ? LN_STEPS_TD3 : LN_STEPS> Q) {
     ddpg_rows4_chain<PHASE, true>(G, P, &Q);
 }
 
@@ -1110,7 +1135,7 @@ int lds_floats(const Dims& d, RArgs* G, bool td3 = false) {
 // The LayerNorm chains' carve-up: the plain one with tiles A and B wide enough for either network's rows (they take
 // turns in them), then the two pre-LayerNorm tiles (layer 1's, layer 2's: kept for the backward rules beside the
 // LayerNorm outputs), the dn tile and four statistics slots of (mean [4], rstd [4])
-int lds_floats_ln(const Dims& d, RArgs* G, LnProg* Q) {
+int lds_floats_ln(const Dims& d, RArgs* G, LnProg* Q, bool td3 = false) {
     constexpr int RB = RBLK;
     const int pad = 16;
     auto mx = [](int a, int b) { return a > b ? a : b; };
@@ -1136,10 +1161,11 @@ int lds_floats_ln(const Dims& d, RArgs* G, LnProg* Q) {
     const int oP2 = o; o += RB * ldP2;
     const int oD = o; o += RB * ldD;
     const int oM = o; o += 4 * 2 * RB;
+    const int oY = o; o += td3 ? 16 : 0;           // TD3: y between the two critics' losses
     if (G) {
         G->ldx = ldx; G->ldA = ldA; G->ldB = ldB; G->ldC = ldC;
         G->oX = oX; G->oXn = oXn; G->oA = oA; G->oB = oB; G->oC = oC; G->oO = oO; G->oO2 = oO2; G->oO3 = oO3;
-        G->oZ = oZ; G->oS = oS; G->oR = oR; G->oY = o; G->total = o;
+        G->oZ = oZ; G->oS = oS; G->oR = oR; G->oY = oY; G->total = o;
     }
     if (Q) {
         Q->oP1 = oP1; Q->ldP1 = ldP1; Q->oP2 = oP2; Q->ldP2 = ldP2; Q->oD = oD; Q->ldD = ldD; Q->oM = oM;
@@ -1176,9 +1202,12 @@ bool offsets_ok(const Dims& d, int64_t rows) {
     return rows * widest * 4 < (1ll << 31);
 }
 
-bool dims_ok_ln(const Dims& d) {
-    return dims_ok(d) && lds_floats_ln(d, nullptr, nullptr) * (int)sizeof(float) <= MAX_LDS;
+bool dims_ok_ln(const Dims& d, bool td3 = false) {
+    return dims_ok(d, td3) && lds_floats_ln(d, nullptr, nullptr, td3) * (int)sizeof(float) <= MAX_LDS;
 }
+
+// LayerNorm with a second critic: both parts present (an `ln` without its second part beside a `second` is refused)
+bool ln_second(const smx_ddpg_rows_t* a) { return a->ln && a->ln->second && a->second; }
 
 PMat pmat2(const smx_ddpg_rows_second& s, const Dims& d, int b) {
     PMat m;
@@ -1190,7 +1219,8 @@ PMat pmat2(const smx_ddpg_rows_second& s, const Dims& d, int b) {
 int fill(RArgs& G, const smx_ddpg_rows_t* a, bool td3 = false, LnProg* Q = nullptr) {
     SMX_REQUIRE(a && a->packed, SMX_E_NULL);
     const Dims d = dims_of(*a);
-    SMX_REQUIRE(!a->ln || (Q && !td3 && !a->second), SMX_E_UNSUPPORTED);      // LayerNorm: one critic, its own launches
+    // LayerNorm: its own launches; with a second critic only where its LayerNorm part came along
+    SMX_REQUIRE(!a->ln || (Q && (a->second ? ln_second(a) : !td3)), SMX_E_UNSUPPORTED);
     SMX_REQUIRE(a->rows > 0 && a->rows < (1 << 24), SMX_E_SHAPE);
     SMX_REQUIRE(dims_ok(d, td3), SMX_E_UNSUPPORTED);
     {
@@ -1227,13 +1257,15 @@ int fill(RArgs& G, const smx_ddpg_rows_t* a, bool td3 = false, LnProg* Q = nullp
     G.tbuf = g_tbuf;
     if (a->ln) {
         const smx_ddpg_rows_ln* l = a->ln;
-        SMX_REQUIRE(dims_ok_ln(d), SMX_E_UNSUPPORTED);
+        const bool two = ln_second(a);
+        SMX_REQUIRE(dims_ok_ln(d, two), SMX_E_UNSUPPORTED);
         SMX_REQUIRE(offsets_ok(d, a->rows), SMX_E_SHAPE);
-        const smx_ddpg_ln_net* ln[4] = {&l->actor, &l->critic, &l->target_actor, &l->target_critic};
-        for (int k = 0; k < 4; ++k) SMX_REQUIRE(ln[k]->g1 && ln[k]->b1 && ln[k]->g2 && ln[k]->b2, SMX_E_NULL);
+        const smx_ddpg_ln_net* ln[6] = {&l->actor, &l->critic, &l->target_actor, &l->target_critic,
+                                        two ? &l->second->critic2 : nullptr, two ? &l->second->target_critic2 : nullptr};
+        for (int k = 0; k < (two ? 6 : 4); ++k) SMX_REQUIRE(ln[k]->g1 && ln[k]->b1 && ln[k]->g2 && ln[k]->b2, SMX_E_NULL);
         SMX_REQUIRE(l->eps > 0.f, SMX_E_SHAPE);
         memset(Q, 0, sizeof(*Q));
-        lds_floats_ln(d, &G, Q);
+        lds_floats_ln(d, &G, Q, two);
         Q->eps = l->eps;
     }
     if (td3) {
@@ -1366,6 +1398,18 @@ void actor_program_ln(const RArgs& G, const smx_ddpg_rows_ln& l, Prog& P, LnProg
     Q.a1 = l.a1; Q.a2 = l.a2; Q.am1 = l.am1; Q.ar1 = l.ar1; Q.am2 = l.am2; Q.ar2 = l.ar2;
 }
 
+// the 13-step launches' copy of the host's table, field by field: a field added to LnProgT is added HERE too (the assert
+// below fails until its size is entered); dn2_2 is left null on purpose -- the 13-step chains have no second critic
+static_assert(sizeof(LnProg) - sizeof(LnStep) * LN_STEPS_TD3 == 104, "LnProgT's fields behind s[] changed: update narrow()");
+LnProgT<LN_STEPS> narrow(const LnProg& Q) {
+    LnProgT<LN_STEPS> R;
+    memset(&R, 0, sizeof(R));
+    memcpy(R.s, Q.s, sizeof(R.s));
+    R.eps = Q.eps; R.dn2 = Q.dn2; R.a1 = Q.a1; R.a2 = Q.a2; R.am1 = Q.am1; R.ar1 = Q.ar1; R.am2 = Q.am2; R.ar2 = Q.ar2;
+    R.oP1 = Q.oP1; R.ldP1 = Q.ldP1; R.oP2 = Q.oP2; R.ldP2 = Q.ldP2; R.oD = Q.oD; R.ldD = Q.ldD; R.oM = Q.oM;
+    return R;
+}
+
 // TD3's critic chain (ddpg.py:266-283, 312-319): both target critics (the second at the noised action), then each
 // critic's forward pass, loss and data gradients against y = min(y1, y2), then the actor's forward pass
 void td3_critic_program(const RArgs& G, Prog& P) {
@@ -1396,6 +1440,56 @@ void td3_critic_program(const RArgs& G, Prog& P) {
     P.n = n;
 }
 static_assert(MAX_STEPS >= 20, "the TD3 critic chain has 20 layers");
+
+// ... with LayerNorm: the same 20 products, a forward rule behind each of the 12 hidden layers (six networks), a backward
+// rule behind each critic's loss and behind its W2^T product -- 16 rules.
+// Tiles as in critic_program_ln: P1 / P2 hold the pre-LayerNorm rows of the network in flight, statistics slots 0 / 1 its
+// two LayerNorms'; each critic's backward rules run before the next network overwrites them.
+void td3_critic_program_ln(const RArgs& G, const smx_ddpg_rows_ln& l, const smx_ddpg_rows_ln_second& l2, Prog& P, LnProg& Q) {
+    const int ldc = G.c1 + G.A;
+    const int P1 = Q.oP1, l1 = Q.ldP1, P2 = Q.oP2, l2p = Q.ldP2;
+    int n = 0;
+    P.s[n] = step(G.oXn, G.ldx, G.ta.W1, G.ta.b1, A_RELU, P1, l1, nullptr, 0, P_NONE);                // mu'(s')
+    ln_fwd(Q, n, P.s[n], l.target_actor.g1, l.target_actor.b1, G.oA, G.ldA, nullptr, 0, nullptr, nullptr, 0); ++n;
+    P.s[n] = step(G.oA, G.ldA, G.ta.W2, G.ta.b2, A_RELU, P2, l2p, nullptr, 0, P_NONE);
+    ln_fwd(Q, n, P.s[n], l.target_actor.g2, l.target_actor.b2, G.oB, G.ldB, nullptr, 0, nullptr, nullptr, 1); ++n;
+    P.s[n++] = step(G.oB, G.ldB, G.ta.W3, G.ta.b3, A_TANH, G.oO, LDO, nullptr, 0, P_NONE);
+    P.s[n] = step(G.oXn, G.ldx, G.tc.W1, G.tc.b1, A_RELU, P1, l1, nullptr, 0, P_TC_CAT);              // Q1'(s', mu'(s'))
+    ln_fwd(Q, n, P.s[n], l.target_critic.g1, l.target_critic.b1, G.oC, G.ldC, nullptr, 0, nullptr, nullptr, 0); ++n;
+    P.s[n] = step(G.oC, G.ldC, G.tc.W2, G.tc.b2, A_RELU, P2, l2p, nullptr, 0, P_NONE);
+    ln_fwd(Q, n, P.s[n], l.target_critic.g2, l.target_critic.b2, G.oB, G.ldB, nullptr, 0, nullptr, nullptr, 1); ++n;
+    P.s[n++] = step(G.oB, G.ldB, G.tc.W3, G.tc.b3, A_NONE, G.oO2, LDO, nullptr, 0, P_NONE);
+    P.s[n] = step(G.oXn, G.ldx, G.tc2.W1, G.tc2.b1, A_RELU, P1, l1, nullptr, 0, P_TC2_CAT);           // Q2'(s', clamp(mu' + noise))
+    ln_fwd(Q, n, P.s[n], l2.target_critic2.g1, l2.target_critic2.b1, G.oC, G.ldC, nullptr, 0, nullptr, nullptr, 0); ++n;
+    P.s[n] = step(G.oC, G.ldC, G.tc2.W2, G.tc2.b2, A_RELU, P2, l2p, nullptr, 0, P_NONE);
+    ln_fwd(Q, n, P.s[n], l2.target_critic2.g2, l2.target_critic2.b2, G.oB, G.ldB, nullptr, 0, nullptr, nullptr, 1); ++n;
+    P.s[n++] = step(G.oB, G.ldB, G.tc2.W3, G.tc2.b3, A_NONE, G.oO3, LDO, nullptr, 0, P_NONE);
+    P.s[n] = step(G.oX, G.ldx, G.c.W1, G.c.b1, A_RELU, P1, l1, l.c_a1, G.c1, P_C_CAT);                // Q1(s, a)
+    ln_fwd(Q, n, P.s[n], l.critic.g1, l.critic.b1, G.oC, G.ldC, G.xcat, ldc, l.cm1, l.cr1, 0); ++n;
+    P.s[n] = step(G.oC, G.ldC, G.c.W2, G.c.b2, A_RELU, P2, l2p, l.c_a2, G.c2, P_NONE);
+    ln_fwd(Q, n, P.s[n], l.critic.g2, l.critic.b2, G.oB, G.ldB, G.h2c, G.c2, l.cm2, l.cr2, 1); ++n;
+    P.s[n] = step(G.oB, G.ldB, G.c.W3, G.c.b3, A_NONE, G.oO, LDO, nullptr, 0, P_LOSS);                // -> y, dz3, dn2
+    ln_bwd(Q, n, G.c2, l.critic.g2, P2, l2p, G.oA, G.ldA, G.dz2, G.c2, 1); ++n;                       // -> dz2
+    P.s[n] = step(G.oA, G.ldA, G.cW2Tlo, nullptr, A_NONE, Q.oD, Q.ldD, G.dxcat, ldc, P_NONE);         // dn1
+    ln_bwd(Q, n, G.c1, l.critic.g1, P1, l1, -1, 0, l.dz1c, G.c1, 0); ++n;                             // -> dz1
+    P.s[n] = step(G.oX, G.ldx, G.c2n.W1, G.c2n.b1, A_RELU, P1, l1, l2.c2_a1, G.c1, P_C2_CAT);         // Q2(s, a)
+    ln_fwd(Q, n, P.s[n], l2.critic2.g1, l2.critic2.b1, G.oC, G.ldC, G.xcat2, ldc, l2.c2m1, l2.c2r1, 0); ++n;
+    P.s[n] = step(G.oC, G.ldC, G.c2n.W2, G.c2n.b2, A_RELU, P2, l2p, l2.c2_a2, G.c2, P_NONE);
+    ln_fwd(Q, n, P.s[n], l2.critic2.g2, l2.critic2.b2, G.oB, G.ldB, G.h2c2, G.c2, l2.c2m2, l2.c2r2, 1); ++n;
+    P.s[n] = step(G.oB, G.ldB, G.c2n.W3, G.c2n.b3, A_NONE, G.oO, LDO, nullptr, 0, P_LOSS2);           // -> its dz3, dn2 (kept y)
+    ln_bwd(Q, n, G.c2, l2.critic2.g2, P2, l2p, G.oA, G.ldA, G.dz2_2, G.c2, 1); ++n;
+    P.s[n] = step(G.oA, G.ldA, G.c2W2Tlo, nullptr, A_NONE, Q.oD, Q.ldD, G.dxcat2, ldc, P_NONE);
+    ln_bwd(Q, n, G.c1, l2.critic2.g1, P1, l1, -1, 0, l2.dz1c2, G.c1, 0); ++n;
+    P.s[n] = step(G.oX, G.ldx, G.a.W1, G.a.b1, A_RELU, P1, l1, l.a1, G.H1, P_NONE);                   // mu(s), kept
+    ln_fwd(Q, n, P.s[n], l.actor.g1, l.actor.b1, G.oA, G.ldA, G.h1a, G.H1, l.am1, l.ar1, 0); ++n;
+    P.s[n] = step(G.oA, G.ldA, G.a.W2, G.a.b2, A_RELU, P2, l2p, l.a2, G.H2, P_NONE);
+    ln_fwd(Q, n, P.s[n], l.actor.g2, l.actor.b2, G.oB, G.ldB, G.h2a, G.H2, l.am2, l.ar2, 1); ++n;
+    P.s[n++] = step(G.oB, G.ldB, G.a.W3, G.a.b3, A_TANH, -1, 0, G.act, G.A, P_NONE);
+    P.n = n;
+    Q.dn2 = l.dn2;
+    Q.dn2_2 = l2.dn2_2;
+}
+static_assert(LN_STEPS_TD3 >= 20 && LN_STEPS_TD3 <= MAX_STEPS, "the LayerNorm TD3 critic chain has 20 layers");
 
 int set_lds(const void* fn, int bytes) {
     return (int)hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
@@ -1438,6 +1532,13 @@ extern "C" int32_t smx_ddpg_rows_ln_supported(int32_t D, int32_t A, int32_t H1, 
     return smx_ddpg_rows_supported_at(D, A, H1, H2, c1, c2, rows) && dims_ok_ln(d) && offsets_ok(d, rows) ? 1 : 0;
 }
 
+extern "C" int32_t smx_ddpg_rows_ln_second_supported(int32_t D, int32_t A, int32_t H1, int32_t H2, int32_t c1, int32_t c2,
+                                                     int64_t rows) {
+    Dims d;
+    d.D = D; d.A = A; d.H1 = H1; d.H2 = H2; d.c1 = c1; d.c2 = c2;
+    return smx_ddpg_rows_ln_supported(D, A, H1, H2, c1, c2, rows) && dims_ok_ln(d, true) ? 1 : 0;
+}
+
 extern "C" int64_t smx_ddpg_rows_second_packed_floats(int32_t D, int32_t A, int32_t H1, int32_t H2, int32_t c1, int32_t c2) {
     Dims d;
     d.D = D; d.A = A; d.H1 = H1; d.H2 = H2; d.c1 = c1; d.c2 = c2;
@@ -1478,7 +1579,7 @@ extern "C" int smx_ddpg_rows_pack_f32(const smx_ddpg_rows_t* a, int32_t which, s
     SMX_REQUIRE(a && a->packed, SMX_E_NULL);
     const Dims d = dims_of(*a);
     SMX_REQUIRE(dims_ok(d), SMX_E_UNSUPPORTED);
-    SMX_REQUIRE(!(a->ln && (a->second || which == SMX_DDPG_PACK_SECOND)), SMX_E_UNSUPPORTED);
+    SMX_REQUIRE(!a->ln || ln_second(a) || (!a->second && which != SMX_DDPG_PACK_SECOND), SMX_E_UNSUPPORTED);
     if (which == SMX_DDPG_PACK_SECOND) return pack_second(a, d, stream);
     SMX_REQUIRE(which == SMX_DDPG_PACK_ALL || which == SMX_DDPG_PACK_CRITIC, SMX_E_SHAPE);
     const int ldc = d.c1 + d.A;
@@ -1522,7 +1623,7 @@ int launch_critic_ln(const smx_ddpg_rows_t* a, RArgs& G, LnProg& Q, smx_stream_t
     memset(&P, 0, sizeof(P));
     critic_program_ln(G, l, P, Q);
     hipLaunchKernelGGL(ddpg_rows4_ln_kernel<0>, dim3((unsigned)((G.rows + RBLK - 1) / RBLK)), dim3(DNTH), bytes, smx_s(stream),
-                       G, P, Q);
+                       G, P, narrow(Q));
     SMX_LAUNCH_CHECK();
     return SMX_OK;
 }
@@ -1541,6 +1642,28 @@ int launch_actor_ln(const smx_ddpg_rows_t* a, RArgs& G, LnProg& Q, smx_stream_t 
     memset(&P, 0, sizeof(P));
     actor_program_ln(G, l, P, Q);
     hipLaunchKernelGGL(ddpg_rows4_ln_kernel<1>, dim3((unsigned)((G.rows + RBLK - 1) / RBLK)), dim3(DNTH), bytes, smx_s(stream),
+                       G, P, narrow(Q));
+    SMX_LAUNCH_CHECK();
+    return SMX_OK;
+}
+
+int launch_critic_td3_ln(const smx_ddpg_rows_t* a, RArgs& G, LnProg& Q, smx_stream_t stream) {
+    const smx_ddpg_rows_ln& l = *a->ln;
+    const smx_ddpg_rows_ln_second& l2 = *l.second;
+    SMX_REQUIRE(l.c_a1 && l.cm1 && l.cr1 && l.c_a2 && l.cm2 && l.cr2 && l.dn2 && l.dz1c && l.a1 && l.am1 && l.ar1 && l.a2 &&
+                    l.am2 && l.ar2, SMX_E_NULL);
+    SMX_REQUIRE(l2.c2_a1 && l2.c2m1 && l2.c2r1 && l2.c2_a2 && l2.c2m2 && l2.c2r2 && l2.dn2_2 && l2.dz1c2, SMX_E_NULL);
+    const int bytes = G.total * (int)sizeof(float);
+    static int set = 0;
+    if (set < bytes) {
+        const int e = set_lds((const void*)ddpg_rows4_ln_kernel<2>, bytes);
+        if (e) return e;
+        set = bytes;
+    }
+    Prog P;
+    memset(&P, 0, sizeof(P));
+    td3_critic_program_ln(G, l, l2, P, Q);
+    hipLaunchKernelGGL(ddpg_rows4_ln_kernel<2>, dim3((unsigned)((G.rows + RBLK - 1) / RBLK)), dim3(DNTH), bytes, smx_s(stream),
                        G, P, Q);
     SMX_LAUNCH_CHECK();
     return SMX_OK;
@@ -1550,6 +1673,7 @@ int launch_actor_ln(const smx_ddpg_rows_t* a, RArgs& G, LnProg& Q, smx_stream_t 
 extern "C" int smx_ddpg_rows_critic_f32(const smx_ddpg_rows_t* a, smx_stream_t stream) {
     RArgs G;
     LnProg Q;
+    SMX_REQUIRE(!(a && a->ln && a->second), SMX_E_UNSUPPORTED);      // (two LayerNorm critics: smx_ddpg_rows_critic_td3_f32)
     const int rc = fill(G, a, false, &Q);
     if (rc) return rc;
     SMX_REQUIRE(a->x && a->x_next && a->actions && a->rewards && a->dones, SMX_E_NULL);
@@ -1573,13 +1697,15 @@ extern "C" int smx_ddpg_rows_critic_f32(const smx_ddpg_rows_t* a, smx_stream_t s
 
 extern "C" int smx_ddpg_rows_critic_td3_f32(const smx_ddpg_rows_t* a, smx_stream_t stream) {
     RArgs G;
-    const int rc = fill(G, a, true);
+    LnProg Q;
+    const int rc = fill(G, a, true, &Q);
     if (rc) return rc;
     const smx_ddpg_rows_second* s = a->second;
     SMX_REQUIRE(a->x && a->x_next && a->actions && a->rewards && a->dones, SMX_E_NULL);
     SMX_REQUIRE(a->xcat && a->h2c && a->q && a->q_next && a->y && a->dz3 && a->dz2 && a->dxcat && a->h1a && a->h2a &&
                     a->act, SMX_E_NULL);
     SMX_REQUIRE(s->xcat2 && s->h2c2 && s->q2 && s->q_next2 && s->dz3_2 && s->dz2_2 && s->dxcat2, SMX_E_NULL);
+    if (a->ln) return launch_critic_td3_ln(a, G, Q, stream);
     const int bytes = G.total * (int)sizeof(float);
     static int set = 0;
     if (set < bytes) {
@@ -1707,8 +1833,10 @@ extern "C" int smx_ddpg_rows_wgrad_update_f32(const smx_ddpg_rows_t* a, int32_t 
     SMX_REQUIRE(dims_ok(d), SMX_E_UNSUPPORTED);
     SMX_REQUIRE(a->rows > 0 && a->rows < (1 << 24), SMX_E_SHAPE);
     const smx_ddpg_rows_ln* l = a->ln;
-    SMX_REQUIRE(!l || (!a->second && group != SMX_DDPG_GROUP_CRITIC2 && dims_ok_ln(d) && offsets_ok(d, a->rows)),
-                SMX_E_UNSUPPORTED);
+    const bool two = ln_second(a);
+    SMX_REQUIRE(!l || ((two || (!a->second && group != SMX_DDPG_GROUP_CRITIC2)) && dims_ok_ln(d, two) &&
+                       offsets_ok(d, a->rows)), SMX_E_UNSUPPORTED);
+    const smx_ddpg_rows_ln_second* l2 = two ? l->second : nullptr;
     WUArgs G;
     memset(&G, 0, sizeof(G));
     const int rc = fill_update(G.U, a, group, u, d);
@@ -1724,7 +1852,7 @@ extern "C" int smx_ddpg_rows_wgrad_update_f32(const smx_ddpg_rows_t* a, int32_t 
     const int ldc = d.c1 + d.A;
     // (gradient, input) of the three layers: the buffers the chain launches wrote
     // (LayerNorm: the critic's dz1 is a buffer of its own, dxcat keeps dn1; h2c / h1a / h2a are the LayerNorm outputs)
-    const float* dz[3] = {c2nd ? s2->dxcat2 : cr ? (l ? l->dz1c : a->dxcat) : a->dz1a, c2nd ? s2->dz2_2 : cr ? a->dz2 : a->dz2a,
+    const float* dz[3] = {c2nd ? (l ? l2->dz1c2 : s2->dxcat2) : cr ? (l ? l->dz1c : a->dxcat) : a->dz1a, c2nd ? s2->dz2_2 : cr ? a->dz2 : a->dz2a,
                           c2nd ? s2->dz3_2 : cr ? a->dz3 : a->dz3a};
     const int ldz[3] = {cr ? (l ? d.c1 : ldc) : d.H1, cr ? d.c2 : d.H2, cr ? 1 : d.A};
     const float* x[3] = {a->x, c2nd ? s2->xcat2 : cr ? a->xcat : a->h1a, c2nd ? s2->h2c2 : cr ? a->h2c : a->h2a};
@@ -1754,17 +1882,17 @@ extern "C" int smx_ddpg_rows_wgrad_update_f32(const smx_ddpg_rows_t* a, int32_t 
     }
     G.tiles = tiles;
     if (l) {
-        const smx_ddpg_ln_net& p = cr ? l->critic : l->actor;
-        const smx_ddpg_ln_net& tp = cr ? l->target_critic : l->target_actor;
+        const smx_ddpg_ln_net& p = c2nd ? l2->critic2 : cr ? l->critic : l->actor;
+        const smx_ddpg_ln_net& tp = c2nd ? l2->target_critic2 : cr ? l->target_critic : l->target_actor;
         const float* gam[2] = {p.g1, p.g2};
         const float* bet[2] = {p.b1, p.b2};
         const float* tgam[2] = {tp.g1, tp.g2};
         const float* tbet[2] = {tp.b1, tp.b2};
-        const float* dn[2] = {cr ? a->dxcat : l->dn1a, cr ? l->dn2 : l->dn2a};
+        const float* dn[2] = {c2nd ? s2->dxcat2 : cr ? a->dxcat : l->dn1a, c2nd ? l2->dn2_2 : cr ? l->dn2 : l->dn2a};
         const int lddn[2] = {cr ? ldc : d.H1, cr ? d.c2 : d.H2};
-        const float* pre[2] = {cr ? l->c_a1 : l->a1, cr ? l->c_a2 : l->a2};
-        const float* mean[2] = {cr ? l->cm1 : l->am1, cr ? l->cm2 : l->am2};
-        const float* rstd[2] = {cr ? l->cr1 : l->ar1, cr ? l->cr2 : l->ar2};
+        const float* pre[2] = {c2nd ? l2->c2_a1 : cr ? l->c_a1 : l->a1, c2nd ? l2->c2_a2 : cr ? l->c_a2 : l->a2};
+        const float* mean[2] = {c2nd ? l2->c2m1 : cr ? l->cm1 : l->am1, c2nd ? l2->c2m2 : cr ? l->cm2 : l->am2};
+        const float* rstd[2] = {c2nd ? l2->c2r1 : cr ? l->cr1 : l->ar1, c2nd ? l2->c2r2 : cr ? l->cr2 : l->ar2};
         const int F[2] = {cr ? d.c1 : d.H1, cr ? d.c2 : d.H2};
         int blocks = 0;
         for (int k = 0; k < 2; ++k) {

@@ -29,6 +29,13 @@ def ddpg_rows_ln(kernels):
     return bool(getattr(kernels, 'ddpg_rows_ln', False))
 
 
+def ddpg_rows_ln_td3(kernels):
+    """whether `kernels` runs a use_layernorm DDPG iteration with TD3's double critic on the row schedule -- the
+    ddpg_rows_ln_second_supported / ddpg_rows_ln_second_attach methods below: its `ddpg_rows_ln_td3` attribute; an object
+    without it (ddpg_rows_ln and ddpg_rows_td3 alone do not say so) keeps such learners on the layer-by-layer schedule"""
+    return bool(getattr(kernels, 'ddpg_rows_ln_td3', False))
+
+
 def ddpg_rows_td3(kernels):
     """whether this kernels object runs TD3 (a second critic, clipped noise on the target action) on the row schedule --
     the ddpg_rows_second_* / ddpg_rows_critic_td3 methods below: its `ddpg_rows_td3` attribute; an object without it
@@ -824,6 +831,8 @@ class HipKernels(object):
     ddpg_rows_td3 = True
     # use_layernorm on the row schedule (ddpg_rows_ln(), above)
     ddpg_rows_ln = True
+    # use_layernorm together with TD3 on the row schedule (ddpg_rows_ln_td3(), above)
+    ddpg_rows_ln_td3 = True
 
     def synth_ddpg_rollout_supported(self, net, ln=False):
         """the actor shapes synth_ddpg_rollout takes; ln: with a LayerNorm behind each hidden ReLU"""
@@ -1186,6 +1195,29 @@ class HipKernels(object):
             setattr(s, k, t.data_ptr())
         args.ln = ctypes.pointer(s)
         args._refs_ln = (s, ln_nets, io_ln)
+        return args
+
+    # use_layernorm with TD3: the second critic's LayerNorms and buffers ride in args.ln.second
+    # (smx_ddpg_rows_ln_second), beside args.second; ddpg_rows_critic_td3 then runs the LayerNorm TD3 chain
+    def ddpg_rows_ln_second_supported(self, D, A, H1, H2, c1, c2, rows):
+        return bool(self.lib.smx_ddpg_rows_ln_second_supported(D, A, H1, H2, c1, c2, int(rows)))
+
+    def ddpg_rows_ln_second_attach(self, args, ln_nets2, io_ln2):
+        """attach the second critic's LayerNorm part to a block that ddpg_rows_ln_attach and ddpg_rows_second have been
+        through.  ln_nets2: {'critic2' | 'target_critic2': {'ln1.W', 'ln1.b', 'ln2.W', 'ln2.b'}}; io_ln2: c2_a1, c2m1, c2r1,
+        c2_a2, c2m2, c2r2, dn2_2, dz1c2.  The block's xcat2[:, :c1] and h2c2 are then the LayerNorm OUTPUTS.  Returns args."""
+        assert bool(args.ln) and bool(args.second)
+        s = L.DdpgRowsLnSecond()
+        for name in ('critic2', 'target_critic2'):
+            n = getattr(s, name)
+            for k, f in (('ln1.W', 'g1'), ('ln1.b', 'b1'), ('ln2.W', 'g2'), ('ln2.b', 'b2')):
+                setattr(n, f, ln_nets2[name][k].data_ptr())
+        for k in ('c2_a1', 'c2m1', 'c2r1', 'c2_a2', 'c2m2', 'c2r2', 'dn2_2', 'dz1c2'):
+            t = io_ln2[k]
+            assert t.is_contiguous(), k
+            setattr(s, k, t.data_ptr())
+        args.ln.contents.second = ctypes.pointer(s)
+        args._refs_ln2 = (s, ln_nets2, io_ln2)
         return args
 
     def ddpg_rows_update(self, args, group, theta, grads, exp_avg, exp_avg_sq, lr, step, weight_decay, clip_value,

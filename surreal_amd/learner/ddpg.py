@@ -29,9 +29,9 @@ observations also runs on the row blocks when session_config.learner.ddpg_row_sc
 buffers, gradients, Adam group -- is one record (_critic_workspace): the second critic's update is the first one's code.
 
 use_layernorm (default off) runs layer by layer too, with every other switch: the variant lives in DDPGModel's passes
-(actor_forward ... actor_backward), the learner's iteration is the same.  With low-dimensional observations, one critic, one
+(actor_forward ... actor_backward), the learner's iteration is the same.  With low-dimensional observations, one
 rank and the fused update it also runs on the row blocks when session_config.learner.ddpg_row_schedule is True (4 launches,
-a LayerNorm rule behind each hidden layer's step; opt-in).  LayerNorm with a double critic, with camera observations, on
+5 with TD3's double critic; a LayerNorm rule behind each hidden layer's step; opt-in).  LayerNorm with camera observations, on
 several ranks or with ddpg_rows_fused_update = False stays layer by layer.  torchx's LayerNorm semantics are unpinned (its source is absent): taken as
 torch.nn.LayerNorm over the features.
 """
@@ -373,10 +373,16 @@ class DDPGLearner(Learner):
         m = self.model
         dims = (D, self.action_dim, m.actor.H1, m.actor.H2, m.c1, m.c2)
         if self.use_layernorm:
-            # LayerNorm: one critic, low-dimensional observations, one rank, the fused update (the gains' and biases'
-            # gradients are formed by the gradient-and-step launch alone) -- everything else stays layer by layer
-            ok = (rows is not None and not self.use_double_critic and not self.is_pixel_input and self.world_size == 1
+            # LayerNorm: low-dimensional observations, one rank, the fused update (the gains' and biases' gradients are
+            # formed by the gradient-and-step launch alone) -- everything else stays layer by layer
+            ok = (rows is not None and not self.is_pixel_input and self.world_size == 1
                   and self.rows_fused_update and KN.ddpg_rows_ln(self.K) and self.K.ddpg_rows_ln_supported(*dims, rows))
+            if ok and self.use_double_critic:
+                # ... with TD3's second critic where the kernels run that cell too: y kept between the two losses.  (The
+                # library's last predicate implies the TD3 one; both are asked because a kernels object -- a test
+                # double -- may answer each more loosely)
+                ok = (KN.ddpg_rows_ln_td3(self.K) and KN.ddpg_rows_td3(self.K)
+                      and self.K.ddpg_rows_second_supported(*dims, rows) and self.K.ddpg_rows_ln_second_supported(*dims, rows))
             return dims if ok and self.K.ddpg_rows_supported(*dims, rows=rows) else None
         if self.use_double_critic and not (rows is not None and KN.ddpg_rows_td3(self.K)
                                            and self.K.ddpg_rows_second_supported(*dims, rows)):
@@ -418,9 +424,18 @@ class DDPGLearner(Learner):
             ws.dz2_2 = torch.zeros(B, c2, device=self.device)
             ws.dxcat2 = torch.zeros(B, c1 + A, device=self.device)
             nets2 = {'critic2': s.model.critic, 'target_critic2': s.target.critic}
-            io2 = dict(noise=ws.s_noise if self.use_action_regularization else None, xcat2=s.w.xcat, h2c2=s.w.h2c, q2=s.q,
-                       q_next2=ws.q_next2, dz3_2=s.dz3, dz2_2=ws.dz2_2, dxcat2=ws.dxcat2, stats2=s.stats)
+            io2 = dict(noise=ws.s_noise if self.use_action_regularization else None, xcat2=s.w.xcat,
+                       h2c2=s.w.c_n2 if ln else s.w.h2c, q2=s.q, q_next2=ws.q_next2, dz3_2=s.dz3, dz2_2=ws.dz2_2,
+                       dxcat2=ws.dxcat2, stats2=s.stats)
             ws.rows_args = K.ddpg_rows_second(ws.rows_args, nets2, ws.rows_packed2, io2)
+            if ln:
+                # ... and its LayerNorms: the second critic's gains and biases in place, its forward workspace, and dn2 /
+                # dz1 of its own (as dz2_2 / dxcat2 above: both critics' backward passes precede either step)
+                ws.dn2_2 = torch.zeros(B, c2, device=self.device)
+                ws.dz1c2 = torch.zeros(B, c1, device=self.device)
+                io_ln2 = dict(c2_a1=s.w.c_a1, c2m1=s.w.cm1, c2r1=s.w.cr1, c2_a2=s.w.c_a2, c2m2=s.w.cm2, c2r2=s.w.cr2,
+                              dn2_2=ws.dn2_2, dz1c2=ws.dz1c2)
+                ws.rows_args = K.ddpg_rows_ln_second_attach(ws.rows_args, nets2, io_ln2)
         ws.rows_key = (x.data_ptr(), xn.data_ptr(), actions.data_ptr(), rewards.data_ptr(), done.data_ptr())
         return ws.rows_args
 
@@ -436,11 +451,12 @@ class DDPGLearner(Learner):
         the second at the noised, clamped action --, y = min of the two targets and both critics' losses and data
         gradients (smx_ddpg_rows_critic_td3_f32); the second critic's step is a third update launch between the first
         critic's and the actor chain, which goes through the first critic only.  5 launches, no ATen arithmetic.
-        use_layernorm (one critic, one rank, the fused update: _rows_dims): the same 4 launches with a LayerNorm rule behind
+        use_layernorm (one rank, the fused update: _rows_dims): the same 4 launches with a LayerNorm rule behind
         every hidden layer's step and its backward rule behind the backward products, on the buffers of DDPGModel's
         passes; the gains' and biases' gradients and steps are further workgroups of the group's gradient-and-step launch.
-        LayerNorm with a double critic, with camera observations, on several ranks or with ddpg_rows_fused_update = False
-        stays layer by layer (_schedule)."""
+        With a double critic it is TD3's 5 launches, the LayerNorm rules behind TD3's chain and the second critic's gains
+        and biases stepped by its own gradient-and-step launch.  LayerNorm with camera observations, on several ranks or
+        with ddpg_rows_fused_update = False stays layer by layer (_schedule)."""
         K, m, mt, A = self.K, self.model, self.model_target, self.action_dim
         B, D = x.shape
         c1, c2, ld = m.c1, m.c2, m.c1 + A
@@ -607,8 +623,8 @@ class DDPGLearner(Learner):
         levels) or 'layers' (layer by layer: every switch).  Asked at each enqueue: level_schedule / row_schedule may be
         set after construction"""
         if self.use_layernorm:
-            # LayerNorm takes the rows only when asked to (ddpg_row_schedule = True) and where _rows_dims lets it: one
-            # critic, low-dimensional observations, one rank, the fused update; otherwise layer by layer as before
+            # LayerNorm takes the rows only when asked to (ddpg_row_schedule = True) and where _rows_dims lets it:
+            # low-dimensional observations, one rank, the fused update (one critic or two); otherwise layer by layer
             return 'rows' if self.row_schedule is True and self._rows_dims(D, B) is not None else 'layers'
         if not self.is_pixel_input:
             if self.use_double_critic:
