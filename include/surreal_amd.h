@@ -589,6 +589,26 @@ int32_t smx_epoch_fwdbwd_supported(int32_t D, int32_t H1, int32_t H2, int32_t OU
 int smx_epoch_fwdbwd_f32(const smx_epoch_job_t* jobs, int32_t njobs, const struct smx_ppo_losses* loss,
                          smx_ppo_ctrl_t* ctrl, int64_t n_total, int32_t* sync_word, uint64_t* kl_slots,
                          smx_stream_t stream);
+/* Pair mode of the two calls above: every 16-row block is carried by TWO workgroups on two CUs of one XCD.  Half h takes
+ * the feature tiles t with t % 2 == h of layer 1, layer 2 and dz1 -- each CU issues half of the MFMAs and streams half of
+ * the packed weights -- and the halves hand their h1 and h2 tiles to each other through `xchg` (every element as one
+ * 8-byte device-scope word, value | hand-over count << 32, polled by its reader: no fence, no flag round trip; a wait
+ * is bounded at 0.25 s like the batch KL's, then ctrl->reserved[1] is raised).  Layer 3, the loss and W3^T dz3 are done by both halves; results that exist once per
+ * block leave from half 0.  A tile's arithmetic does not depend on which workgroup carries it: every output has the
+ * bits of the unpaired call.
+ * xchg: smx_epoch_pair_xchg_bytes(widest H1, widest H2) bytes (for every launch the device can pair), 16-byte aligned,
+ * ZERO when allocated and never written by anyone else; it may be reused by every later launch (on one stream) of any
+ * shape that fits -- the counts only grow, nothing is ever cleared.
+ * The doubled grid must be resident at once: when smx_epoch_pair_fits(row blocks of all jobs) is 0 (or xchg is too
+ * small) the launch runs unpaired, as smx_epoch_forward_f32 / smx_epoch_fwdbwd_f32. */
+int64_t smx_epoch_pair_xchg_bytes(int32_t H1, int32_t H2);
+int32_t smx_epoch_pair_fits(int64_t blocks);
+int smx_epoch_forward_pair_f32(const smx_epoch_job_t* jobs, int32_t njobs, const struct smx_ppo_losses* loss,
+                               smx_ppo_ctrl_t* ctrl, int64_t n_total, void* xchg, int64_t xchg_bytes,
+                               smx_stream_t stream);
+int smx_epoch_fwdbwd_pair_f32(const smx_epoch_job_t* jobs, int32_t njobs, const struct smx_ppo_losses* loss,
+                              smx_ppo_ctrl_t* ctrl, int64_t n_total, int32_t* sync_word, uint64_t* kl_slots,
+                              void* xchg, int64_t xchg_bytes, smx_stream_t stream);
 /* A co-tenant for the launch above (diagnostics / tests; no reference counterpart): `blocks` workgroups, each holding
  * one compute unit to itself (more than half of its LDS) for `microseconds` (<= 2 s) without doing work.  The in-launch
  * wait of smx_epoch_fwdbwd_f32 is bounded at 0.25 s: a tenant that keeps its workgroups off the device for longer makes

@@ -1,5 +1,6 @@
 """micro-benchmark of smx_epoch_fwdbwd_f32 (one launch: forward + loss + data gradients) against the two launches it
-replaces, at the benchmark shape (GPU box).  With a timing build (python scripts/build_timing_lib.py;
+replaces and against its pair mode (smx_epoch_fwdbwd_pair_f32: every row block on two workgroups), and of the two-job
+forward-only launch in both modes, at the benchmark shape (GPU box).  With a timing build (python scripts/build_timing_lib.py;
 SMX_LIB_PATH=surreal_amd/libsurreal_amd_timing.so) also the per-phase cycle counts of thread 0 of every workgroup."""
 import ctypes, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -38,6 +39,22 @@ def one():
     k[0] += 1
 
 
+xchg = K.epoch_pair_xchg(t['act'], t['cri'])
+
+
+def pair():
+    K.epoch_fwdbwd([aj, cj], loss, t['ctrl'], rows, sync[k[0]:k[0] + 1], slots[k[0]], xchg=xchg)
+    k[0] += 1
+
+
+def fwd():
+    K.epoch_forward([aj, cj], loss, t['ctrl'], rows)
+
+
+def fwd_pair():
+    K.epoch_forward([aj, cj], loss, t['ctrl'], rows, xchg=xchg)
+
+
 def graph_time(fn, n=50):
     """n calls captured in ONE hipGraph (what the learner replays): device time per call, no host in the way"""
     fn(); torch.cuda.synchronize()
@@ -58,31 +75,51 @@ def graph_time(fn, n=50):
 
 print('two launches (forward, backward): %.2f us per epoch' % graph_time(two))
 print('one launch (fwdbwd):              %.2f us per epoch' % graph_time(one))
+print('one launch, pair mode:            %.2f us per epoch' % graph_time(pair))
+print('forward only:                     %.2f us per launch' % graph_time(fwd))
+print('forward only, pair mode:          %.2f us per launch' % graph_time(fwd_pair))
 if 'timing' in os.environ.get('SMX_LIB_PATH', ''):
     lib = K.lib
     lib.smx_epoch_debug_tbuf.argtypes = [ctypes.c_void_p]
     lib.smx_epoch_debug_tbuf.restype = None
     tb = torch.zeros(512 * 32, dtype=torch.int64, device='cuda')
     lib.smx_epoch_debug_tbuf(ctypes.c_void_p(tb.data_ptr()))
-    sync.zero_(); slots.zero_(); k[0] = 0
-    for _ in range(3):
-        one()
-    torch.cuda.synchronize()
     NB = (rows + 15) // 16                     # row blocks per job (the launch: actor blocks, then critic blocks)
-    TT = tb.view(512, 32)[:2 * NB].cpu().double()
-    base = TT[:, 0].min()
     names = [(0, 12, 'job descriptor'), (12, 13, 'x + loss input loads issued'), (13, 14, 'hidden tiles cleared'),
              (14, 15, 'x -> LDS (waits for x)'), (15, 1, 'loss inputs -> LDS'), (0, 1, 'prologue'), (1, 2, 'barrier'), (2, 3, 'layer 1'), (3, 4, 'layer 2'), (4, 5, 'layer 3'),
              (5, 6, 'loss + publish barrier'), (6, 7, 'rhs tiles + dz2 products'), (7, 8, 'wait + reduce sums'),
              (8, 9, 'dz2 epilogue + dz3T + barrier'), (9, 10, 'dz1'), (10, 11, 'scalars')]
     for l, prev in ((0, 2), (1, 3), (2, 4)):
         names += [(prev, 16 + 4 * l, 'layer %d: set-up, bias loads issued' % (l + 1)), (16 + 4 * l, 17 + 4 * l, 'layer %d: products' % (l + 1)),
-                  (17 + 4 * l, 18 + 4 * l, 'layer %d: epilogue' % (l + 1)), (18 + 4 * l, 3 + l, 'layer %d: barrier' % (l + 1))]
-    for a, b, nm in names:
-        d = TT[:, b] - TT[:, a]
-        print('%-32s actor %7.0f (max %7.0f)   critic %7.0f (max %7.0f) cycles' % (
-            nm, d[:NB].mean(), d[:NB].max(), d[NB:].mean(), d[NB:].max()))
-    tot = TT[:, 11] - TT[:, 0]
-    print('in-kernel total: actor %.0f (max %.0f) critic %.0f ; last end - first start %.0f cycles; start spread %.0f' % (
-        tot[:NB].mean(), tot[:NB].max(), tot[NB:].mean(), TT[:, 11].max() - base, TT[:, 0].max() - base))
+                  (17 + 4 * l, 18 + 4 * l, 'layer %d: epilogue' % (l + 1)), (18 + 4 * l, 3 + l, 'layer %d: stores landed + barrier' % (l + 1))]
+    # pair mode: stamp 3 + l is the layer's barrier (the workgroup's own tagged words are on their way), 28 + 2 l the
+    # partner's tiles in LDS; the next layer starts there (its table rows count from the hand-over's end)
+    pair_names = list(names)
+    for l in (0, 1):
+        i = pair_names.index((3 + l, 4 + l, 'layer %d' % (l + 2)))
+        pair_names[i] = (28 + 2 * l, 4 + l, 'layer %d' % (l + 2))
+        i = pair_names.index((3 + l, 16 + 4 * (l + 1), 'layer %d: set-up, bias loads issued' % (l + 2)))
+        pair_names[i] = (28 + 2 * l, 16 + 4 * (l + 1), 'layer %d: set-up, bias loads issued' % (l + 2))
+        pair_names += [(3 + l, 28 + 2 * l, 'hand-over %d (poll partner words -> LDS, barrier)' % (l + 1))]
+
+    def table(fn, per_blk, nm_list, title):
+        sync.zero_(); slots.zero_(); k[0] = 0
+        tb.zero_()
+        for _ in range(3):
+            fn()
+        torch.cuda.synchronize()
+        TT = tb.view(512, 32)[:2 * NB * per_blk].cpu().double()
+        base = TT[:, 0].min()
+        NA = NB * per_blk
+        print('---- %s' % title)
+        for a, b, nm in nm_list:
+            d = TT[:, b] - TT[:, a]
+            print('%-48s actor %7.0f (max %7.0f)   critic %7.0f (max %7.0f) cycles' % (
+                nm, d[:NA].mean(), d[:NA].max(), d[NA:].mean(), d[NA:].max()))
+        tot = TT[:, 11] - TT[:, 0]
+        print('in-kernel total: actor %.0f (max %.0f) critic %.0f ; last end - first start %.0f cycles; start spread %.0f' % (
+            tot[:NA].mean(), tot[:NA].max(), tot[NA:].mean(), TT[:, 11].max() - base, TT[:, 0].max() - base))
+
+    table(one, 1, names, 'epoch_fb_kernel, one workgroup per row block')
+    table(pair, 2, pair_names, 'epoch_fb_pair_kernel, two workgroups per row block (both halves of every block)')
     lib.smx_epoch_debug_tbuf(None)

@@ -23,6 +23,15 @@
 //                      16 rows per workgroup, two workgroups per row block splitting the dz1
 //                      feature tiles (the dz2 product is cheap and recomputed by both).
 //
+//   epoch_fb_kernel    what the learner runs per epoch: epoch_fwd_kernel's forward + loss and the data gradients of
+//                      the same rows in ONE launch (the batch KL travels through 8-byte device-scope slots).
+//   epoch_*_pair_kernel  the same two kernels with every row block on TWO workgroups (two CUs of one XCD): the feature
+//                      tiles of layer 1, layer 2 and dz1 are dealt between the halves, h1 and h2 are handed over as
+//                      tagged 8-byte device-scope words (see epoch_fwd_body).  Measured at the benchmark shape
+//                      (profiles/epoch_pair_split_*): 35.6 -> 33.7 us per forward + backward launch, 23.8 -> 21.7 us
+//                      per forward-only launch, bit-identical outputs; each hand-over costs 2.7 - 3.8 k cycles (two
+//                      trips through the memory side) of the 5 k it saves.
+//
 // What shaped the code (all measured, scripts/bench_epoch.py + scripts/micro/): guards are out-of-range
 // buffer offsets, never branches (a load under a lane mask is waited for at the end of the masked
 // region -- twenty bias words one after the other cost 3000 cycles per layer); nothing conditional
@@ -106,6 +115,13 @@ struct EArgs {
     int fsplit;
     int xsplit;        // forward kernels, two jobs of xsplit row blocks each: job 0 on XCDs 0-3, job 1 on XCDs 4-7 (0: as dispatched)
     long long* tbuf;   // SMX_EPOCH_TIMING builds: per-workgroup phase timestamps (else null)
+    // pair mode (epoch_fwd_pair_kernel / epoch_fb_pair_kernel): a row block is carried by TWO workgroups
+    int nblocks;       // ... row blocks of all jobs (the grid is 2 x nblocks rounded up to whole XCD rounds)
+    unsigned* xflags;  // ... [row block][half][hand-over]: the hand-overs that workgroup has published, ever (its own
+                       //     counter across launches, the tag of its words: nobody else reads it)
+    unsigned long long* xbuf;   // ... [row block][half][xhalf words]: the tiles it hands over, [h1 tiles | h2 tiles],
+                       //     a word = value | hand-over count << 32
+    int xoff2, xhalf;  // ... words: where the h2 tiles start / one workgroup's share (the same in every launch)
 };
 
 // Consecutive workgroup ids go round-robin over the 8 XCDs, each with its own L2.  With the actor's row blocks first and the
@@ -181,12 +197,37 @@ __device__ __forceinline__ void fb_reduce_partials(const float* __restrict__ par
 
 // Forward of up to four jobs' row blocks (FB = false: epoch_fwd_kernel), or forward + loss + data gradients of the
 // same rows in ONE launch (FB = true: epoch_fb_kernel, see there).
-template <bool FB>
+//
+// PAIR: the row block is carried by two workgroups on two CUs, half 0 and half 1.  The three big products (layer 1,
+// layer 2, dz1) are bounded by ONE CU's matrix pipes and by the rate at which one CU receives packed weights; half h
+// takes the feature tiles t with t % 2 == h of each of them (a tile's arithmetic does not depend on who carries it),
+// so each CU issues and streams half.  After layer 1 and after layer 2 the halves hand their tiles over: a workgroup
+// puts its tiles into its share of a per-block exchange buffer and fills the rest of its LDS tile from the partner's
+// share -- the kl_slots protocol, no fence and no flag round trip: every element travels as ONE 8-byte device-scope
+// word, value | tag << 32, and a reader polls the very words it needs until they carry the tag (a producer never
+// waits for its own stores).  The tag is the count of hand-overs the block's workgroups have published since the
+// buffer was allocated (zeroed), kept per workgroup in xflags: both halves of a block publish at the same points of
+// every launch, so the tag a workgroup is about to write is the tag it waits for, and whatever earlier launches (or
+// replays of a captured graph) left in the partner's share carries a smaller one.  The small products (layer 3, the loss, W3^T dz3) are done
+// by both halves from the full h2 tile; only half 0 publishes results that are per block.  Workgroup ids 8 apart
+// share an XCD (and its L2): that is where the two halves sit, but nothing here depends on it.
+template <bool FB, bool PAIR>
 __device__ __forceinline__ void epoch_fwd_body(const EArgs& G, smx_ppo_ctrl_t* __restrict__ ctrl) {
     extern __shared__ float sm[];
-    const int bid = xcd_job_order(G, (int)blockIdx.x);
-    const int ts_blk = bid;
+    int raw = (int)blockIdx.x, half = 0;
+    if constexpr (PAIR) {
+        const int xcd = raw & 7, slot = raw >> 3;
+        half = slot & 1;
+        raw = (slot >> 1) * 8 + xcd;
+        if (raw >= G.nblocks) return;                // (the grid is rounded up to whole rounds of the XCDs)
+    }
+    const int bid = xcd_job_order(G, raw);
+    const int ts_blk = PAIR ? 2 * bid + half : bid;
     (void)ts_blk;
+    // the workgroup that forms the epoch's scalars (FB)
+    const bool fin_wg = PAIR ? (raw == G.nblocks - 1 && half == 1) : (blockIdx.x == gridDim.x - 1);
+    (void)fin_wg;
+    const bool pub = half == 0;                      // results that exist once per row block leave from half 0
     TSTAMP(0);
     const EJob J = select_job(G, bid);
     const int stopv = J.stop ? __builtin_nontemporal_load(J.stop) : 0;
@@ -198,6 +239,19 @@ __device__ __forceinline__ void epoch_fwd_body(const EArgs& G, smx_ppo_ctrl_t* _
     const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int fm = lane & 15, kq = lane >> 4;
     TSTAMP(12);
+    // pair mode: this workgroup's flags and share of the exchange buffer, the partner's, and the hand-over counts so far
+    int pair_lost = 0;            // a hand-over timed out (what this thread saw; ctrl->reserved[1] collects them all)
+    unsigned* xf_mine = nullptr;
+    unsigned long long* xb_mine = nullptr;
+    const unsigned long long* xb_part = nullptr;
+    unsigned xseq[2] = {0u, 0u};
+    if constexpr (PAIR) {
+        xf_mine = G.xflags + ((size_t)bid * 2 + half) * 2;
+        xb_mine = G.xbuf + ((size_t)bid * 2 + half) * (size_t)G.xhalf;
+        xb_part = G.xbuf + ((size_t)bid * 2 + (half ^ 1)) * (size_t)G.xhalf;
+        xseq[0] = __hip_atomic_load(xf_mine, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) + 1u;
+        xseq[1] = __hip_atomic_load(xf_mine + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) + 1u;
+    }
 
     float* xs = sm;
     float* h1s = sm + G.off_h1;
@@ -319,13 +373,17 @@ __device__ __forceinline__ void epoch_fwd_body(const EArgs& G, smx_ppo_ctrl_t* _
         const rsrc_t rw = make_rsrc(Wp, (unsigned)tiles * (unsigned)C2 * 2048u);
         const rsrc_t rbias = make_rsrc(bias, (unsigned)H * 4u);
         float* stp = l == 2 ? J.out : hT;
-        const bool st_ok = stp != nullptr;
+        const bool st_ok = stp != nullptr && (l < 2 || pub);
+        // pair mode, hidden layers: this half's tiles are half, half + 2, ...; the output layer is done by both
+        const bool split = PAIR && l < 2;
+        const int tfirst = split ? 2 * wv + half : wv, tstep = split ? 2 * FNWV : FNWV;
+        unsigned long long* xb_st = split ? xb_mine + (l == 0 ? 0 : G.xoff2) : nullptr;
         const rsrc_t rst = make_rsrc(stp ? stp : Wp, l == 2 ? (unsigned)J.rows * (unsigned)J.out_ld * 4u
                                                              : (unsigned)H * (unsigned)J.ldT * 4u);
 #pragma unroll 1
-        for (int tb = 0; tb < tiles; tb += FNWV * FTG) {
-            const int t0 = tb + wv;
-            int nt = (tiles - t0 + FNWV - 1) / FNWV;
+        for (int tb = 0; tb < tiles; tb += tstep * FTG) {
+            const int t0 = tb + tfirst;
+            int nt = (tiles - t0 + tstep - 1) / tstep;
             nt = nt < 0 ? 0 : (nt > FTG ? FTG : nt);
             // the epilogue's bias words, requested in front of the main loop.  Guards are out-of-range
             // buffer offsets, never branches: a load under a lane mask makes hipcc wait for it at the
@@ -333,7 +391,7 @@ __device__ __forceinline__ void epoch_fwd_body(const EArgs& G, smx_ppo_ctrl_t* _
             float bs[FTG][4];
 #pragma unroll
             for (int g = 0; g < FTG; ++g) {
-                const int f0 = 16 * (t0 + FNWV * g) + 4 * kq;
+                const int f0 = 16 * (t0 + tstep * g) + 4 * kq;
 #pragma unroll
                 for (int r = 0; r < 4; ++r) bs[g][r] = ld4(rbias, (g < nt) ? (unsigned)(f0 + r) * 4u : OOB);
             }
@@ -341,9 +399,9 @@ __device__ __forceinline__ void epoch_fwd_body(const EArgs& G, smx_ppo_ctrl_t* _
 #pragma unroll
             for (int g = 0; g < TG; ++g) acc[g] = (f32x4){0.f, 0.f, 0.f, 0.f};
             TSTAMP(16 + 4 * l);
-            if (nt > 2) fwd_tiles<3>(acc, rw, tiles, C2, in_lds, ldi, t0, FNWV, lane);
-            else if (nt > 1) fwd_tiles<2>(acc, rw, tiles, C2, in_lds, ldi, t0, FNWV, lane);
-            else if (nt > 0) fwd_tiles<1>(acc, rw, tiles, C2, in_lds, ldi, t0, FNWV, lane);
+            if (nt > 2) fwd_tiles<3>(acc, rw, tiles, C2, in_lds, ldi, t0, tstep, lane);
+            else if (nt > 1) fwd_tiles<2>(acc, rw, tiles, C2, in_lds, ldi, t0, tstep, lane);
+            else if (nt > 0) fwd_tiles<1>(acc, rw, tiles, C2, in_lds, ldi, t0, tstep, lane);
             TSTAMP(17 + 4 * l);
             // hidden tiles: [feature][row] in HBM, lane (fm, kq) holds features f0..f0+3 of row fm;
             // the output tile: row-major.  Stores past the matrix / the batch go to out-of-range offsets.
@@ -353,7 +411,7 @@ __device__ __forceinline__ void epoch_fwd_body(const EArgs& G, smx_ppo_ctrl_t* _
 #pragma unroll
             for (int g = 0; g < FTG; ++g) {
                 if (g < nt) {                                            // wave-uniform
-                    const int f0 = 16 * (t0 + FNWV * g) + 4 * kq;    // features f0..f0+3 of data row fm
+                    const int f0 = 16 * (t0 + tstep * g) + 4 * kq;    // features f0..f0+3 of data row fm
                     float v[4];
 #pragma unroll
                     for (int r = 0; r < 4; ++r) {
@@ -370,12 +428,64 @@ __device__ __forceinline__ void epoch_fwd_body(const EArgs& G, smx_ppo_ctrl_t* _
                         __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(v[r]), rst,
                                                               ok ? srow + (unsigned)(f0 + r) * sstep : OOB, 0, 0);
                     }
+                    if constexpr (PAIR) {
+                        if (split) {      // the whole tile (padding and rows past the batch included: what LDS holds)
+                            unsigned long long* q = xb_st + ((t0 + tstep * g) >> 1) * 256 + (4 * kq) * ER + fm;     // [tile][feature][row]
+                            const unsigned long long tag = (unsigned long long)xseq[l] << 32;
+#pragma unroll
+                            for (int r = 0; r < 4; ++r)
+                                __hip_atomic_store(q + r * ER, tag | __float_as_uint(v[r]), __ATOMIC_RELAXED,
+                                                   __HIP_MEMORY_SCOPE_AGENT);
+                        }
+                    }
                 }
             }
         }
         TSTAMP(18 + 4 * l);
         SMX_LDS_BARRIER();
         TSTAMP(3 + l);
+        if constexpr (PAIR) {
+            if (split) {
+                // ---- the hand-over: the partner's tiles -> LDS as their words arrive -----------------------------
+                if (tid == 0)          // (this workgroup's count for its next launch; the partner polls the words, not this)
+                    __hip_atomic_store(xf_mine + l, xseq[l], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                TSTAMP(27 + 2 * l);
+                if constexpr (!FB) {
+                    if (l == 1 && !pub) return;       // forward only: layer 3 and the loss are half 0's
+                }
+                const int nthem = ((tiles + half) >> 1) * 256;   // words of the other half: tiles (half ^ 1), (half ^ 1) + 2, ...
+                const unsigned long long* src = xb_part + (l == 0 ? 0 : G.xoff2);
+                const long long t0w = (long long)wall_clock64();
+                for (int i0 = tid; i0 < nthem; i0 += 4 * FNTH) {
+                    unsigned long long w[4];
+                    for (;;) {
+                        bool there = true;
+#pragma unroll
+                        for (int u = 0; u < 4; ++u) {
+                            w[u] = __hip_atomic_load(src + min(i0 + FNTH * u, nthem - 1), __ATOMIC_RELAXED,
+                                                     __HIP_MEMORY_SCOPE_AGENT);
+                            there = there && (unsigned)(w[u] >> 32) == xseq[l];
+                        }
+                        if (there) break;
+                        if ((long long)wall_clock64() - t0w > 25000000LL) {      // 0.25 s (100 MHz): a lost workgroup
+                            pair_lost = 1;
+                            atomicOr(&ctrl->reserved[1], 1);
+                            break;
+                        }
+                        __builtin_amdgcn_s_sleep(1);
+                    }
+#pragma unroll
+                    for (int u = 0; u < 4; ++u) {
+                        const int i = i0 + FNTH * u;
+                        if (i < nthem)
+                            out_lds[(i & 15) * ldo + 16 * (2 * (i >> 8) + (half ^ 1)) + ((i >> 4) & 15)] =
+                                __uint_as_float((unsigned)w[u]);
+                    }
+                }
+                SMX_LDS_BARRIER();
+                TSTAMP(28 + 2 * l);
+            }
+        }
     }
 
     // ---- the job's loss on the rows it holds (four waves: the other four retire here) ---------
@@ -384,6 +494,7 @@ __device__ __forceinline__ void epoch_fwd_body(const EArgs& G, smx_ppo_ctrl_t* _
     if (J.loss == SMX_EPOCH_LOSS_POLICY) {
         const PolArgs& p = G.pl;
         // inputs staged in LDS: row stride LW, [actions | behave | ref | adv]
+        // (pair mode: half 1 has left after its second hand-over, this is half 0)
         policy_loss_body(blk, sm + G.off_loss, p.mode, outs, LDO, p.log_var, lin_s, LW, lin_s + p.A, LW,
                          lin_s + 3 * p.A, LW, lin_s + 5 * p.A, (long)J.rows, p.A, ctrl, p.g_surr, p.g_kl,
                          p.row_partials, 1.0f, false, nullptr, nullptr, 0, row0, LW);
@@ -431,6 +542,8 @@ __device__ __forceinline__ void epoch_fwd_body(const EArgs& G, smx_ppo_ctrl_t* _
     __shared__ __attribute__((aligned(16))) float S[8 + 2 * MAX_A + 8];
     float& s_kl = S[8 + 2 * MAX_A];
     int& wait_ok = *(int*)&S[8 + 2 * MAX_A + 1];
+    int& pair_bad = *(int*)&S[8 + 2 * MAX_A + 2];        // pair mode: a thread of this workgroup lost a hand-over
+    if (PAIR && tid == 0) pair_bad = 0;                  // (the loss's barriers stand between this and the writes below)
     static_assert(sizeof(S) % 16 == 0, "static LDS is a multiple of 16 bytes");
     const PolArgs& p = G.pl;
     const bool policy = J.loss == SMX_EPOCH_LOSS_POLICY;
@@ -444,7 +557,7 @@ __device__ __forceinline__ void epoch_fwd_body(const EArgs& G, smx_ppo_ctrl_t* _
     const float inv_n = 1.0f / nf;
     // was the actor's early-exit flag up when the launch started?  (its workgroups have returned then; read by the
     // workgroup that forms the epoch's scalars, long before it could raise the flag itself)
-    const int pol_stopped = (G.pol_stop && blockIdx.x == gridDim.x - 1) ? __builtin_nontemporal_load(G.pol_stop) : 0;
+    const int pol_stopped = (G.pol_stop && fin_wg) ? __builtin_nontemporal_load(G.pol_stop) : 0;
     // the output layer's transposed weights for this wave's dz2 tiles (chunk 0: K = OUT <= 32), requested BEFORE the
     // loss: the optimiser launch has just rewritten them on other XCDs, a first touch is a trip to the memory-side cache
     const int tiles2 = (J.H2 + 15) >> 4;
@@ -463,7 +576,7 @@ __device__ __forceinline__ void epoch_fwd_body(const EArgs& G, smx_ppo_ctrl_t* _
         if (lo) {
             policy_loss_body<true>(blk, sm + G.off_loss, p.mode, outs, LDO, p.log_var, lin_s, LW, lin_s + p.A, LW,
                                    lin_s + 3 * p.A, LW, lin_s + 5 * p.A, (long)J.rows, p.A, ctrl, nullptr, nullptr,
-                                   p.row_partials, 1.0f, false, nullptr, nullptr, 0, row0, LW, G.kl_slots);
+                                   p.row_partials, 1.0f, false, nullptr, nullptr, 0, row0, LW, G.kl_slots, pub);
         } else {
 #pragma unroll
             for (int i = 0; i < POLICY_LOSS_BARRIERS; ++i) SMX_LDS_BARRIER();
@@ -474,7 +587,7 @@ __device__ __forceinline__ void epoch_fwd_body(const EArgs& G, smx_ppo_ctrl_t* _
         const float v = ok ? outs[tid * LDO] : 0.f, g = ok ? vret : 0.f;
         const float d = g - v, e = v - g;
         const float dz = (2.0f * e) / nf;
-        if (ok) q.v_dz3[row0 + tid] = dz;
+        if (ok && pub) q.v_dz3[row0 + tid] = dz;
         if (tid < ER) gss[tid * LDZ] = ok ? dz : 0.f;
         const float cnt = (float)nrows;
         const float md = smx_wave_sum(ok ? d : 0.f) / cnt;
@@ -482,7 +595,7 @@ __device__ __forceinline__ void epoch_fwd_body(const EArgs& G, smx_ppo_ctrl_t* _
         const float m2d = smx_wave_sum(ok ? (d - md) * (d - md) : 0.f);
         const float m2g = smx_wave_sum(ok ? (g - mg) * (g - mg) : 0.f);
         const float sq = smx_wave_sum(ok ? e * e : 0.f);
-        if (tid == 0) {
+        if (tid == 0 && pub) {
             float* P = q.v_partials + (size_t)blk * 8;
             P[0] = cnt; P[1] = md; P[2] = m2d; P[3] = mg; P[4] = m2g; P[5] = sq; P[6] = 0.f; P[7] = 0.f;
             if (blk == 0 && q.will_update) ctrl->adam_step_critic += 1;
@@ -490,6 +603,9 @@ __device__ __forceinline__ void epoch_fwd_body(const EArgs& G, smx_ppo_ctrl_t* _
     }
     SMX_LDS_BARRIER();
     TSTAMP(6);
+    if constexpr (PAIR) {
+        if (__any(pair_lost) && lane == 0) pair_bad = 1;        // (read by thread 0 behind the next barrier)
+    }
     if (policy) {
         // right-hand side tiles from the loss's scratch, zero padded to the 32 columns the K loop reads
         const float* sc = sm + G.off_loss;
@@ -585,13 +701,17 @@ __device__ __forceinline__ void epoch_fwd_body(const EArgs& G, smx_ppo_ctrl_t* _
     };
     float c_kl = 0.f;
     bool stop_now = false;
-    if (tid == 0) wait_ok = 1;          // (thread 0 is the only writer; every wait of this workgroup ANDs into it)
+    // (thread 0 is the only writer; every later wait of this workgroup ANDs into it.  Pair mode: it starts from what
+    // ALL threads of the workgroup saw in the two hand-overs, which are behind us)
+    if (tid == 0) wait_ok = PAIR ? (pair_bad == 0) : 1;
     if (adapt) kl_coef(kl_total(), c_kl, stop_now);
     // the partial ROW (all column sums: the finalizing workgroup's input) went out with device-scope stores during the
     // loss, several microseconds ago: wavefronts 0 and 1 make sure they have completed, then the counter moves
-    if (policy && tid < 128) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    // (pair mode: all wavefronts -- a thread that lost a hand-over has raised ctrl->reserved[1], and that must have
+    // landed before the counter tells the finalizing workgroup that this block's row is there)
+    if (policy && (PAIR || tid < 128)) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     SMX_LDS_BARRIER();
-    if (policy && tid == 0) __hip_atomic_fetch_add(G.sync, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (policy && pub && tid == 0) __hip_atomic_fetch_add(G.sync, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     TSTAMP(8);
     if (!stop_now) {
         // ---- dz2 = (W3^T dz3) * relu'(h2): LDS tile (dz1's B operand) + transposed copy (weight gradients) ----
@@ -609,7 +729,7 @@ __device__ __forceinline__ void epoch_fwd_body(const EArgs& G, smx_ppo_ctrl_t* _
                     v.z = (m.z > 0.f) ? aS[g][2] + c_kl * aK[g][2] : 0.f;
                     v.w = (m.w > 0.f) ? aS[g][3] + c_kl * aK[g][3] : 0.f;
                     *(float4*)(dz2s + fm * ldh2 + f0) = v;
-                    const bool ok = fm < nrows;
+                    const bool ok = fm < nrows && (!PAIR || (t & 1) == half);      // (pair mode: the tile's owner stores it)
                     const unsigned o = ((unsigned)f0 * (unsigned)J.ldT + (unsigned)(row0 + fm)) * 4u, st = (unsigned)J.ldT * 4u;
                     __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(v.x), rout, ok && f0 < J.H2 ? o : OOB, 0, 0);
                     __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(v.y), rout, ok && f0 + 1 < J.H2 ? o + st : OOB, 0, 0);
@@ -622,7 +742,7 @@ __device__ __forceinline__ void epoch_fwd_body(const EArgs& G, smx_ppo_ctrl_t* _
             for (int idx = tid; idx < ER * A; idx += FNTH) {
                 const int a = idx / ER, n = idx - a * ER;
                 const float v = gss[n * LDZ + a] + c_kl * gks[n * LDZ + a];
-                if (n < nrows) J.dz3T[(size_t)a * J.ldT + row0 + n] = v;
+                if (n < nrows && pub) J.dz3T[(size_t)a * J.ldT + row0 + n] = v;
             }
         }
         SMX_LDS_BARRIER();
@@ -633,20 +753,22 @@ __device__ __forceinline__ void epoch_fwd_body(const EArgs& G, smx_ppo_ctrl_t* _
             const int C2h = pack_chunks(J.H2);
             const rsrc_t rw2 = make_rsrc(J.P2T, (unsigned)tiles1 * (unsigned)C2h * 2048u);
             const rsrc_t rout = make_rsrc(J.dz1T, (unsigned)J.H1 * (unsigned)J.ldT * 4u);
+            // (pair mode: this half's tiles are half, half + 2, ...)
+            const int tfirst = PAIR ? 2 * wv + half : wv, tstep = PAIR ? 2 * FNWV : FNWV;
 #pragma unroll 1
-            for (int tb = 0; tb < tiles1; tb += FNWV * FTG) {
-                const int t0 = tb + wv;
-                int nt = (tiles1 - t0 + FNWV - 1) / FNWV;
+            for (int tb = 0; tb < tiles1; tb += tstep * FTG) {
+                const int t0 = tb + tfirst;
+                int nt = (tiles1 - t0 + tstep - 1) / tstep;
                 nt = nt < 0 ? 0 : (nt > FTG ? FTG : nt);
                 f32x4 acc[TG];
 #pragma unroll
                 for (int g = 0; g < TG; ++g) acc[g] = (f32x4){0.f, 0.f, 0.f, 0.f};
-                if (nt > 2) fwd_tiles<3>(acc, rw2, tiles1, C2h, dz2s, ldh2, t0, FNWV, lane);
-                else fwd_tiles<2>(acc, rw2, tiles1, C2h, dz2s, ldh2, t0, FNWV, lane);
+                if (nt > 2) fwd_tiles<3>(acc, rw2, tiles1, C2h, dz2s, ldh2, t0, tstep, lane);
+                else fwd_tiles<2>(acc, rw2, tiles1, C2h, dz2s, ldh2, t0, tstep, lane);
 #pragma unroll
                 for (int g = 0; g < FTG; ++g) {
                     if (g < nt) {
-                        const int f0 = 16 * (t0 + FNWV * g) + 4 * kq;
+                        const int f0 = 16 * (t0 + tstep * g) + 4 * kq;
                         const float4 m = *(const float4*)(h1s + fm * ldh1 + f0);
                         const float vx = (m.x > 0.f) ? acc[g][0] : 0.f, vy = (m.y > 0.f) ? acc[g][1] : 0.f;
                         const float vz = (m.z > 0.f) ? acc[g][2] : 0.f, vw = (m.w > 0.f) ? acc[g][3] : 0.f;
@@ -663,7 +785,7 @@ __device__ __forceinline__ void epoch_fwd_body(const EArgs& G, smx_ppo_ctrl_t* _
     }
     TSTAMP(10);
     // ---- the epoch's scalars: the last workgroup of the grid, once its own rows are done -------------------
-    if (nbp > 0 && blockIdx.x == gridDim.x - 1 && pol_stopped == 0) {
+    if (nbp > 0 && fin_wg && pol_stopped == 0) {
         wait_count();
         fb_reduce_partials(p.row_partials, nbp, pstride, S, sm + G.off_loss);
         const float klsum = kl_total();                    // the KL sum every actor workgroup used: the same bits
@@ -672,7 +794,12 @@ __device__ __forceinline__ void epoch_fwd_body(const EArgs& G, smx_ppo_ctrl_t* _
         SMX_LDS_BARRIER();
         loss_and_kl_coef(p.mode, S, nf, ctrl, loss, ck);
         for (int a = tid; a < A; a += FNTH) p.dlogvar[a] = (S[8 + a] + ck * S[8 + A + a]) * inv_n;
-        if (tid == 0 && wait_ok)
+        // (pair mode: a block whose half 0 lost a hand-over has counted itself all the same, its row is garbage; the error
+        // word it raised landed before its count did -- the scalars stay unwritten, as after a wait of this workgroup)
+        bool rows_ok = true;
+        if constexpr (PAIR)
+            rows_ok = __hip_atomic_load(&ctrl->reserved[1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0;
+        if (tid == 0 && wait_ok && rows_ok)
             write_policy_scalars(S, nf, loss, ck, p.log_var, A, ctrl, p.check_stop, p.will_update, p.dlogvar_sumsq,
                                  p.stats);
     }
@@ -681,7 +808,10 @@ __device__ __forceinline__ void epoch_fwd_body(const EArgs& G, smx_ppo_ctrl_t* _
 }
 
 __global__ __launch_bounds__(FNTH) void epoch_fwd_kernel(EArgs G, smx_ppo_ctrl_t* __restrict__ ctrl) {
-    epoch_fwd_body<false>(G, ctrl);
+    epoch_fwd_body<false, false>(G, ctrl);
+}
+__global__ __launch_bounds__(FNTH) void epoch_fwd_pair_kernel(EArgs G, smx_ppo_ctrl_t* __restrict__ ctrl) {
+    epoch_fwd_body<false, true>(G, ctrl);
 }
 
 // One launch per epoch for [forward + loss + data gradients] of the row blocks of both networks: what
@@ -689,7 +819,11 @@ __global__ __launch_bounds__(FNTH) void epoch_fwd_kernel(EArgs G, smx_ppo_ctrl_t
 // see the FB part of epoch_fwd_body).  The actor workgroups of a launch must be co-resident (<= one per CU,
 // dispatched before anything that could wait on them: they are); a wait is bounded all the same.
 __global__ __launch_bounds__(FNTH) void epoch_fb_kernel(EArgs G, smx_ppo_ctrl_t* __restrict__ ctrl) {
-    epoch_fwd_body<true>(G, ctrl);
+    epoch_fwd_body<true, false>(G, ctrl);
+}
+// ... with every row block on a pair of CUs (see epoch_fwd_body): the grid is twice as large, all of it co-resident
+__global__ __launch_bounds__(FNTH) void epoch_fb_pair_kernel(EArgs G, smx_ppo_ctrl_t* __restrict__ ctrl) {
+    epoch_fwd_body<true, true>(G, ctrl);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1188,8 +1322,48 @@ static int fill_args(EArgs& G, const smx_epoch_job_t* jobs, int32_t njobs, const
     return bytes > EXCLUSIVE_LDS ? bytes : EXCLUSIVE_LDS;
 }
 
-extern "C" int smx_epoch_forward_f32(const smx_epoch_job_t* jobs, int32_t njobs, const smx_ppo_losses_t* loss,
-                                     smx_ppo_ctrl_t* ctrl, int64_t n_total, smx_stream_t stream) {
+// ---- pair mode: two workgroups per row block (see epoch_fwd_body) --------------------------------------------------
+// The exchange buffer: [PC][2][2] flag words, then [PC][2] shares of whole KB, PC = the most row blocks a paired launch
+// can have on this device.  A share holds the tiles its workgroup hands over, (tiles of H1 + 1) / 2 + (tiles of H2 + 1) / 2
+// tiles of 16 x 16 eight-byte words.  Where a workgroup's share lies depends on the buffer alone, not on the launch: the
+// tags in it (hand-overs of THAT workgroup) only ever grow.
+static int pair_half_tiles(int H) { return (((H + 15) >> 4) + 1) >> 1; }
+static int pair_cap_blocks() { return (smx_cu_count() / 2) & ~7; }
+static int64_t pair_flag_bytes() { return ((int64_t)pair_cap_blocks() * 16 + 255) & ~(int64_t)255; }
+
+extern "C" int64_t smx_epoch_pair_xchg_bytes(int32_t H1, int32_t H2) {
+    if (H1 <= 0 || H2 <= 0) return 0;
+    return pair_flag_bytes() + (int64_t)pair_cap_blocks() * 2 * (pair_half_tiles(H1) + pair_half_tiles(H2)) * 2048;
+}
+
+// The doubled grid (rounded up to whole rounds of the 8 XCDs, so that the two halves of a block are 8 ids apart) must
+// be resident at once, one workgroup per CU: every workgroup waits for its partner.
+extern "C" int32_t smx_epoch_pair_fits(int64_t blocks) {
+    return blocks > 0 && 2 * ((blocks + 7) & ~(int64_t)7) <= (int64_t)smx_cu_count();
+}
+
+// fills the pair-mode fields of G; false: the launch runs unpaired
+static bool pair_args(EArgs& G, int blocks, int njobs, void* xchg, int64_t xchg_bytes) {
+    if (!xchg || !smx_epoch_pair_fits(blocks) || ((uintptr_t)xchg & 15) != 0) return false;
+    int H1 = 0, H2 = 0;
+    for (int k = 0; k < njobs; ++k) {
+        H1 = G.j[k].H1 > H1 ? G.j[k].H1 : H1;
+        H2 = G.j[k].H2 > H2 ? G.j[k].H2 : H2;
+    }
+    const int64_t share = ((xchg_bytes - pair_flag_bytes()) / (2 * (int64_t)pair_cap_blocks())) & ~(int64_t)2047;
+    if (share < (int64_t)(pair_half_tiles(H1) + pair_half_tiles(H2)) * 2048) return false;
+    G.nblocks = blocks;
+    G.xflags = (unsigned*)xchg;
+    G.xbuf = (unsigned long long*)((char*)xchg + pair_flag_bytes());
+    G.xoff2 = pair_half_tiles(H1) * 256;
+    G.xhalf = (int)(share / 8);
+    return true;
+}
+static int pair_grid(int blocks) { return 2 * ((blocks + 7) & ~7); }
+
+static int epoch_forward_launch(const smx_epoch_job_t* jobs, int32_t njobs, const smx_ppo_losses_t* loss,
+                                smx_ppo_ctrl_t* ctrl, int64_t n_total, void* xchg, int64_t xchg_bytes,
+                                smx_stream_t stream) {
     EArgs G;
     const int lds = fill_args(G, jobs, njobs, loss, n_total, 1, KIND_FWD);
     if (lds < 0) return lds;
@@ -1205,19 +1379,35 @@ extern "C" int smx_epoch_forward_f32(const smx_epoch_job_t* jobs, int32_t njobs,
     static bool attr_set = false;
     if (!attr_set) {
         (void)hipFuncSetAttribute((const void*)epoch_fwd_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024);
+        (void)hipFuncSetAttribute((const void*)epoch_fwd_pair_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024);
         attr_set = true;
     }
-    hipLaunchKernelGGL(epoch_fwd_kernel, dim3(blocks), dim3(FNTH), lds, smx_s(stream), G, ctrl);
+    if (pair_args(G, blocks, njobs, xchg, xchg_bytes))
+        hipLaunchKernelGGL(epoch_fwd_pair_kernel, dim3(pair_grid(blocks)), dim3(FNTH), lds, smx_s(stream), G, ctrl);
+    else
+        hipLaunchKernelGGL(epoch_fwd_kernel, dim3(blocks), dim3(FNTH), lds, smx_s(stream), G, ctrl);
     SMX_LAUNCH_CHECK();
     return SMX_OK;
+}
+
+extern "C" int smx_epoch_forward_f32(const smx_epoch_job_t* jobs, int32_t njobs, const smx_ppo_losses_t* loss,
+                                     smx_ppo_ctrl_t* ctrl, int64_t n_total, smx_stream_t stream) {
+    return epoch_forward_launch(jobs, njobs, loss, ctrl, n_total, nullptr, 0, stream);
+}
+
+extern "C" int smx_epoch_forward_pair_f32(const smx_epoch_job_t* jobs, int32_t njobs, const smx_ppo_losses_t* loss,
+                                          smx_ppo_ctrl_t* ctrl, int64_t n_total, void* xchg, int64_t xchg_bytes,
+                                          smx_stream_t stream) {
+    SMX_REQUIRE(xchg && xchg_bytes > 0, SMX_E_NULL);
+    return epoch_forward_launch(jobs, njobs, loss, ctrl, n_total, xchg, xchg_bytes, stream);
 }
 
 extern "C" int smx_epoch_backward_f32(const smx_epoch_job_t* jobs, int32_t njobs, const smx_ppo_losses_t* loss,
                                       smx_ppo_ctrl_t* ctrl, int64_t n_total, smx_stream_t stream);
 
-extern "C" int smx_epoch_fwdbwd_f32(const smx_epoch_job_t* jobs, int32_t njobs, const smx_ppo_losses_t* loss,
-                                    smx_ppo_ctrl_t* ctrl, int64_t n_total, int32_t* sync_word, uint64_t* kl_slots,
-                                    smx_stream_t stream) {
+static int epoch_fwdbwd_launch(const smx_epoch_job_t* jobs, int32_t njobs, const smx_ppo_losses_t* loss,
+                               smx_ppo_ctrl_t* ctrl, int64_t n_total, int32_t* sync_word, uint64_t* kl_slots,
+                               void* xchg, int64_t xchg_bytes, smx_stream_t stream) {
     EArgs G;
     SMX_REQUIRE(loss && ctrl, SMX_E_NULL);
     const int lds = fill_args(G, jobs, njobs, loss, n_total, 1, KIND_FB);
@@ -1264,11 +1454,28 @@ extern "C" int smx_epoch_fwdbwd_f32(const smx_epoch_job_t* jobs, int32_t njobs, 
     static bool attr_set_fb = false;
     if (!attr_set_fb) {
         (void)hipFuncSetAttribute((const void*)epoch_fb_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024);
+        (void)hipFuncSetAttribute((const void*)epoch_fb_pair_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024);
         attr_set_fb = true;
     }
-    hipLaunchKernelGGL(epoch_fb_kernel, dim3(blocks), dim3(FNTH), lds, smx_s(stream), G, ctrl);
+    if (pair_args(G, blocks, njobs, xchg, xchg_bytes))
+        hipLaunchKernelGGL(epoch_fb_pair_kernel, dim3(pair_grid(blocks)), dim3(FNTH), lds, smx_s(stream), G, ctrl);
+    else
+        hipLaunchKernelGGL(epoch_fb_kernel, dim3(blocks), dim3(FNTH), lds, smx_s(stream), G, ctrl);
     SMX_LAUNCH_CHECK();
     return SMX_OK;
+}
+
+extern "C" int smx_epoch_fwdbwd_f32(const smx_epoch_job_t* jobs, int32_t njobs, const smx_ppo_losses_t* loss,
+                                    smx_ppo_ctrl_t* ctrl, int64_t n_total, int32_t* sync_word, uint64_t* kl_slots,
+                                    smx_stream_t stream) {
+    return epoch_fwdbwd_launch(jobs, njobs, loss, ctrl, n_total, sync_word, kl_slots, nullptr, 0, stream);
+}
+
+extern "C" int smx_epoch_fwdbwd_pair_f32(const smx_epoch_job_t* jobs, int32_t njobs, const smx_ppo_losses_t* loss,
+                                         smx_ppo_ctrl_t* ctrl, int64_t n_total, int32_t* sync_word, uint64_t* kl_slots,
+                                         void* xchg, int64_t xchg_bytes, smx_stream_t stream) {
+    SMX_REQUIRE(xchg && xchg_bytes > 0, SMX_E_NULL);
+    return epoch_fwdbwd_launch(jobs, njobs, loss, ctrl, n_total, sync_word, kl_slots, xchg, xchg_bytes, stream);
 }
 
 extern "C" int smx_epoch_backward_f32(const smx_epoch_job_t* jobs, int32_t njobs, const smx_ppo_losses_t* loss,

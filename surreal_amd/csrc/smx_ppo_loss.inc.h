@@ -61,7 +61,9 @@ __device__ __forceinline__ void policy_loss_body(
     const long in_row0 = 0 /* first row held by g_actions / g_behave / g_ref / adv (a staged block: row0) */,
     const int ld_adv = 1,
     unsigned long long* __restrict__ kl_slot = nullptr /* (COH) the block's KL sum | 1 << 32, ONE 8-byte device-scope
-    store as soon as it is known: value and "it is there" travel together (see epoch_fb_kernel) */) {
+    store as soon as it is known: value and "it is there" travel together (see epoch_fb_kernel) */,
+    const bool publish = true /* false: the block's sums stay in the workgroup (the second half of a row block that two
+    workgroups carry, smx_epoch.hip pair mode: its partner publishes the same bits) */) {
     const int R = LOSS_ROWS_PER_BLOCK;
     float* e_z2 = sm;              // ((a - mu)/sig)^2                    [R, A]
     float* e_zb2 = e_z2 + R * A;   // ((a - mb)/sb)^2
@@ -196,7 +198,7 @@ __device__ __forceinline__ void policy_loss_body(
         const float v3 = smx_wave_sum(one ? Lb : 0.f);
         const float v4 = smx_wave_sum(one ? isw : 0.f);
         const float v5 = smx_wave_sum(one ? klb : 0.f);
-        if (tid == 0) {
+        if (tid == 0 && publish) {
             if (COH && kl_slot)
                 __hip_atomic_store(kl_slot + blk, (unsigned long long)__float_as_uint(v2) | (1ull << 32), __ATOMIC_RELAXED,
                                    __HIP_MEMORY_SCOPE_AGENT);
@@ -237,7 +239,7 @@ __device__ __forceinline__ void policy_loss_body(
             gs += __shfl_xor(gs, off, 64);
             gk += __shfl_xor(gk, off, 64);
         }
-        if (q == 0) {
+        if (q == 0 && publish) {
             partial_store<COH>(P + 8 + a, gs);
             partial_store<COH>(P + 8 + A + a, gk);
         }

@@ -309,10 +309,25 @@ class HipKernels(object):
         a.v_will_update = int(loss.get('v_will_update', 0))
         return ctypes.byref(a)
 
-    def epoch_forward(self, jobs, loss=None, ctrl=None, n_total=0):
+    def epoch_pair_fits(self, blocks):
+        """can a launch of `blocks` row blocks run with two workgroups per block (all of them resident at once)?"""
+        return bool(self.lib.smx_epoch_pair_fits(int(blocks)))
+
+    def epoch_pair_xchg(self, *nets, device=None):
+        """the exchange buffer of pair-mode launches over `nets` (zero: its tags count hand-overs from here on; one
+        buffer serves every launch of a stream)"""
+        n = self.lib.smx_epoch_pair_xchg_bytes(max(t.H1 for t in nets), max(t.H2 for t in nets))
+        return torch.zeros(n, dtype=torch.uint8, device=device if device is not None else 'cuda')
+
+    def epoch_forward(self, jobs, loss=None, ctrl=None, n_total=0, xchg=None):
         """jobs: dicts(net, x[, h1T, h2T, out, act, loss='policy'|'value', stop]); loss: dict of the
         loss tensors (see smx_epoch_forward_f32).  One launch: 16 rows per workgroup through the three
-        layers and the job's loss."""
+        layers and the job's loss.  xchg (epoch_pair_xchg): pair mode, two workgroups per row block where the
+        doubled grid fits the device (smx_epoch_forward_pair_f32; the same bits)"""
+        if xchg is not None:
+            L.call('smx_epoch_forward_pair_f32', self._epoch_jobs(jobs), len(jobs), self._epoch_loss(loss),
+                   L.ptr(ctrl), int(n_total), L.ptr(xchg), xchg.numel(), self._st())
+            return
         L.call('smx_epoch_forward_f32', self._epoch_jobs(jobs), len(jobs), self._epoch_loss(loss),
                L.ptr(ctrl), int(n_total), self._st())
 
@@ -326,9 +341,14 @@ class HipKernels(object):
                     self.lib.smx_epoch_fwdbwd_supported(max(n.D for n in nets), max(n.H1 for n in nets),
                                                         max(n.H2 for n in nets), max(n.OUT for n in nets)))
 
-    def epoch_fwdbwd(self, jobs, loss, ctrl, n_total, sync_word, kl_slots):
+    def epoch_fwdbwd(self, jobs, loss, ctrl, n_total, sync_word, kl_slots, xchg=None):
         """epoch_forward + epoch_backward of an updating epoch in ONE launch (smx_epoch_fwdbwd_f32); sync_word: one
-        int32, kl_slots: 2 * epoch_blocks(rows) 4-byte words (8-byte aligned) per launch, zero on entry"""
+        int32, kl_slots: 2 * epoch_blocks(rows) 4-byte words (8-byte aligned) per launch, zero on entry; xchg: pair
+        mode as in epoch_forward (smx_epoch_fwdbwd_pair_f32)"""
+        if xchg is not None:
+            L.call('smx_epoch_fwdbwd_pair_f32', self._epoch_jobs(jobs), len(jobs), self._epoch_loss(loss),
+                   L.ptr(ctrl), int(n_total), L.ptr(sync_word), L.ptr(kl_slots), L.ptr(xchg), xchg.numel(), self._st())
+            return
         L.call('smx_epoch_fwdbwd_f32', self._epoch_jobs(jobs), len(jobs), self._epoch_loss(loss),
                L.ptr(ctrl), int(n_total), L.ptr(sync_word), L.ptr(kl_slots), self._st())
 

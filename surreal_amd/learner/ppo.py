@@ -41,6 +41,10 @@ from surreal_amd.learner.base import Learner, DeferredStats
 from surreal_amd.learner.dist import _SegmentedGraph, _dist_info, setup_peer_exchange
 from surreal_amd.model.ppo_net import DiagGauss, PPOModel
 
+# session_config.learner.epoch_pair_split when the session does not set it (see _ws_epochs; the measurement that
+# decides it: DESIGN.md section 3.2, profiles/epoch_pair_split_bench.jsonl)
+EPOCH_PAIR_SPLIT_DEFAULT = True
+
 
 class LinearWithMinLR(object):
     """Learning-rate schedule named by ``algo.network.anneal.lr_scheduler`` (ppo.py:121-125,
@@ -360,6 +364,14 @@ class PPOLearner(Learner):
         ws.fb = (ws.fused and self.world_size == 1 and bool(self.session_config.learner.get('fused_fwdbwd', True)) and
                  bool(self.session_config.learner.get('exclusive_device', True)) and not getattr(self, '_fb_timed_out', False) and
                  ws.n_slots > 0 and K.epoch_fwdbwd_supported(act, cri))
+        # ... with every row block of those launches (and of the learn's two forward-only launches) on a PAIR of CUs
+        # (smx_epoch_*_pair_f32: the same bits; the partners wait for each other inside the launch, so it goes where
+        # ws.fb goes).  Launches whose doubled grid does not fit the device run unpaired, the C side decides.
+        ws.xchg = None
+        if (ws.fb and bool(self.session_config.learner.get('epoch_pair_split', EPOCH_PAIR_SPLIT_DEFAULT)) and
+                hasattr(K, 'epoch_pair_xchg')):           # (a kernel set without pair mode runs the launches unpaired)
+            if K.epoch_pair_fits(K.epoch_blocks(rows)):
+                ws.xchg = K.epoch_pair_xchg(act, cri, device=self.device)
         ws.vblocks = K.epoch_blocks if ws.fused else K.value_loss_blocks     # value-loss moments per 16 / 256 rows
         ws.nblk_v = ws.vblocks(rows)
         # single rank: GAE + normalisation and the end-of-learn statistics are one launch each
@@ -731,7 +743,8 @@ class PPOLearner(Learner):
         pre = [dict(net=ref_job['net'], packed=ws.pk_ref, x=ref_job['x'], out=ref_job['out'], act=L.SMX_ACT_TANH)]
         if tail is not None:
             pre.append(dict(net=tail['net'], packed=ws.pk_critic, x=tail['x'], out=tail['out'], act=L.SMX_ACT_NONE))
-        K.epoch_forward(pre, None, ws.ctrl_f, n_total)
+        px = {} if ws.xchg is None else dict(xchg=ws.xchg)      # pair mode (see _ws_epochs)
+        K.epoch_forward(pre, None, ws.ctrl_f, n_total, **px)
         gae()
         aj = dict(net=m.actor, packed=ws.pk_actor, x=ws.xn, act=L.SMX_ACT_TANH, loss='policy', stop=ws.stop, h1T=ws.h1aT,
                   h2T=ws.h2aT, dz3T=ws.dz3aT, dz2T=ws.dz2aT, dz1T=ws.dz1aT, xT=ws.xnT, grads=ws.grads_a,
@@ -779,10 +792,10 @@ class PPOLearner(Learner):
             bj = ([aj] if pol_u else []) + ([cj] if val else [])         # the jobs that update in this epoch
             if ws.fb and (pol_u or not pol_f) and (pol_u or val):
                 # forward + loss + data gradients of every job of the epoch in ONE launch (smx_epoch_fwdbwd_f32)
-                K.epoch_fwdbwd(bj, loss, ws.ctrl_f, n_total, ws.sync[e:e + 1], ws.kl_slots[e])
+                K.epoch_fwdbwd(bj, loss, ws.ctrl_f, n_total, ws.sync[e:e + 1], ws.kl_slots[e], **px)
                 K.mlp3_wgrad_multi(bj)
             else:
-                K.epoch_forward(([aj] if pol_f else []) + ([cj] if val else []), loss, ws.ctrl_f, n_total)
+                K.epoch_forward(([aj] if pol_f else []) + ([cj] if val else []), loss, ws.ctrl_f, n_total, **px)
                 if pol_f and not pol_u:
                     K.epoch_backward([aj], loss, ws.ctrl_f, n_total)       # statistics + early exit only
                 if pol_u or val:
