@@ -1514,6 +1514,107 @@ int smx_synth_ppo_pixel_window_step(const struct smx_synth_ppo_pixel_window_step
                                     smx_stream_t stream);
 
 /* ---------------------------------------------------------------------------
+ * Recording the steps of n HOST-stepped environments (GymAdapter, DMControlAdapter, RobosuiteWrapper: simulators that
+ * end their episodes whenever they like) into the replays' device rings: what n of the reference's experience wrappers
+ * do per step on the host -- Python queues, deep copies, one insert per experience (surreal/env/exp_sender_wrapper.py:
+ * 72-112 and 153-264, restated as index arithmetic in surreal_amd/env/exp_sender_wrapper.py) -- as ONE launch per step
+ * for all actors.  Every actor has an episode clock OF ITS OWN, kept by the host (it sees the dones):
+ *   t [n] int32       the actor's step within its episode (>= 0)
+ *   rank [n] int32    -1: the actor closes nothing this step; else its position among this step's closing actors in
+ *                     ascending actor order: it writes row (cursor + rank) % capacity, so the rows of a step are dense and
+ *                     in the order n host wrappers stepped in actor order would have inserted them; rows = their number
+ *   t_host / rank_host  the host arrays t / rank were copied from, or NULL: checked before the launch (t < 0, rank outside
+ *                     [-1, n), closing actors != rows: SMX_E_SHAPE).  The kernels skip an actor with t < 0 and treat a
+ *                     rank outside [0, rows), or one the clock does not allow, as -1: nothing is written out of bounds.
+ *   cur_obs [n, D]    in: what each actor acted on; out: its next acting observation -- step_obs_reset[a] where
+ *                     step_dones[a] != 0 (step_obs_reset NULL: step_obs_next[a]), else step_obs_next[a]
+ *   step_*            this step's results on the device: actions [n, A], obs_next [n, D] (the terminal observation on
+ *                     done), rewards [n], dones [n] (0 / 1), obs_reset [n, D] (only the rows of done actors are read)
+ * These launches move bytes and do no arithmetic (but the n-step reward): no shape limit beyond positive sizes, 16-byte
+ * accesses for every field whose row width is a multiple of 4 floats and whose buffers are 16-byte aligned, 4-byte ones
+ * otherwise.  No atomics.  mon: the episode monitor (ep_reward NULL: none), fed episode_account(a, reward, done) by the
+ * lane that owns the actor's reward.
+ *
+ * smx_record_ppo_window_step_f32: one step of ExpSenderWrapperMultiStepMovingWindowWithInfo per actor, tau = t[a],
+ * N = n_step, adv = advance, S = ceil(N / adv); rings and tables in smx_synth_ppo_window_rollout's layout:
+ *   slot tau % N of carry_obs / carry_act / carry_rew / carry_pd <- cur_obs, step_actions, step_rewards, step_pds [n, 2A];
+ *   with h_before / c_before [n, hidden] and tau % adv == 0, slot (tau / adv) % S of carry_cells <- them
+ *   window j = tau + 1 - N closes iff j >= 0 and j % adv == 0 (that is what rank >= 0 must mean), into its row: obs
+ *     [N, D], actions [N, A], rewards [N], pds [N, 2A] in episode order, dones [N] zeros but the last = step_dones[a]
+ *     (windows never cross an episode), obs_next [D] = step_obs_next[a], cells [2, hidden] the state before step j
+ *     (cells NULL: not written).  The window's last step comes from the step's inputs, its N - 1 older ones from the
+ *     rings, so no workgroup reads what another one writes in the same launch.
+ * copy_workgroups: the workgroups per actor that move a closing window's older steps (0: sized by the bytes the step
+ * moves, window bytes x rows); <= 1024.
+ *
+ * smx_record_ddpg_nstep_step_f32: one step of ExpSenderWrapperSSARNStepBootstrap per actor, N = n_step:
+ *   slot tau % N of carry_obs / carry_act / carry_rew <- cur_obs, step_actions, step_rewards
+ *   tau >= N - 1 (what rank >= 0 must mean): transition j = tau - N + 1, in slot (tau + 1) % N, goes to its row: obs = s_j,
+ *     actions = a_j, obs_next = step_obs_next[a], dones = step_dones[a], rewards = the fp64 sum of
+ *     smx_synth_ddpg_rollout_f32 (gpow [N] = gamma ** e, fp64; the wrapper's fill-up exponents) rounded once
+ *   the last N - 1 transitions of an episode are never written (the host restarts the clock).
+ * n > capacity: SMX_E_SHAPE (every actor may close in one step). */
+struct smx_record_ppo_window_step {        /* (by tag: no typedef) */
+    int32_t n, D, A, hidden;               /* hidden: the LSTM's units (0: a policy without one) */
+    int32_t n_step, advance, rows, copy_workgroups;
+    const int32_t* t;
+    const int32_t* rank;
+    const int32_t* t_host;                 /* NULL: not checked on the host */
+    const int32_t* rank_host;
+    float* cur_obs;
+    const float* step_actions;
+    const float* step_pds;
+    const float* h_before;                 /* [n, hidden] the LSTM state the step started from, or NULL */
+    const float* c_before;
+    const float* step_obs_next;
+    const float* step_rewards;
+    const float* step_dones;
+    const float* step_obs_reset;           /* NULL: no actor is done */
+    float* carry_obs;
+    float* carry_act;
+    float* carry_rew;
+    float* carry_pd;
+    float* carry_cells;                    /* NULL without an LSTM */
+    float* obs;
+    float* obs_next;
+    float* actions;
+    float* rewards;
+    float* dones;
+    float* pds;
+    float* cells;                          /* NULL without an LSTM */
+    int64_t cursor, capacity;
+    struct smx_episode_monitor mon;        /* mon.ep_reward NULL: none (stays the last member) */
+};
+int smx_record_ppo_window_step_f32(const struct smx_record_ppo_window_step* args, smx_stream_t stream);
+
+struct smx_record_ddpg_nstep_step {        /* (by tag: no typedef) */
+    int32_t n, D, A, n_step;
+    int32_t rows, reserved;
+    const int32_t* t;
+    const int32_t* rank;
+    const int32_t* t_host;                 /* NULL: not checked on the host */
+    const int32_t* rank_host;
+    float* cur_obs;
+    const float* step_actions;
+    const float* step_obs_next;
+    const float* step_rewards;
+    const float* step_dones;
+    const float* step_obs_reset;           /* NULL: no actor is done */
+    const double* gpow;
+    float* carry_obs;
+    float* carry_act;
+    float* carry_rew;
+    float* obs;
+    float* obs_next;
+    float* actions;
+    float* rewards;
+    float* dones;
+    int64_t cursor, capacity;
+    struct smx_episode_monitor mon;        /* mon.ep_reward NULL: none (stays the last member) */
+};
+int smx_record_ddpg_nstep_step_f32(const struct smx_record_ddpg_nstep_step* args, smx_stream_t stream);
+
+/* ---------------------------------------------------------------------------
  * Data-parallel exchange between the learner ranks of one node over IPC-mapped peer buffers (xGMI loads): the
  * collectives N sharded learners need to equal the single reference learner -- the per-epoch
  * [gradients | loss partial rows] sum of surreal/learner/ppo.py:541-562 run on shards, the advantage moments

@@ -257,6 +257,27 @@ class SynthPpoPixelWindowStep(Structure):
                                                                                    ('mon', EpisodeMonitor)])
 
 
+class RecordPpoWindowStep(Structure):
+    """struct smx_record_ppo_window_step"""
+    _fields_ = ([(n, c_int32) for n in ('n', 'D', 'A', 'hidden', 'n_step', 'advance', 'rows', 'copy_workgroups')] +
+                [(n, c_void_p) for n in ('t', 'rank', 't_host', 'rank_host', 'cur_obs', 'step_actions', 'step_pds',
+                                         'h_before', 'c_before', 'step_obs_next', 'step_rewards', 'step_dones',
+                                         'step_obs_reset', 'carry_obs', 'carry_act', 'carry_rew', 'carry_pd',
+                                         'carry_cells', 'obs', 'obs_next', 'actions', 'rewards', 'dones', 'pds',
+                                         'cells')] +
+                [('cursor', c_int64), ('capacity', c_int64), ('mon', EpisodeMonitor)])
+
+
+class RecordDdpgNstepStep(Structure):
+    """struct smx_record_ddpg_nstep_step"""
+    _fields_ = ([(n, c_int32) for n in ('n', 'D', 'A', 'n_step', 'rows', 'reserved')] +
+                [(n, c_void_p) for n in ('t', 'rank', 't_host', 'rank_host', 'cur_obs', 'step_actions',
+                                         'step_obs_next', 'step_rewards', 'step_dones', 'step_obs_reset', 'gpow',
+                                         'carry_obs', 'carry_act', 'carry_rew', 'obs', 'obs_next', 'actions',
+                                         'rewards', 'dones')] +
+                [('cursor', c_int64), ('capacity', c_int64), ('mon', EpisodeMonitor)])
+
+
 SMX_DDPG_NOISE_NONE, SMX_DDPG_NOISE_GAUSSIAN, SMX_DDPG_NOISE_OU = 0, 1, 2
 SMX_PPO_PIXEL_STEP_MAX_A = 64            # the actions smx_synth_ppo_pixel_window_step takes
 
@@ -460,6 +481,8 @@ _SIGS = {
     'smx_param_noise_fill_f32': (c_int32, [POINTER(ParamNoise), c_int32, _P, _P]),
     'smx_param_noise_refresh_f32': (c_int32, [POINTER(ParamNoise), _P]),
     'smx_synth_ppo_pixel_window_step': (c_int32, [POINTER(SynthPpoPixelWindowStep), _P, c_int64, _P]),
+    'smx_record_ppo_window_step_f32': (c_int32, [POINTER(RecordPpoWindowStep), _P]),
+    'smx_record_ddpg_nstep_step_f32': (c_int32, [POINTER(RecordDdpgNstepStep), _P]),
     'smx_xchg_bytes': (c_int64, [c_int64, c_int32]),
     'smx_xchg_alloc': (c_int32, [c_int64, c_double, POINTER(c_void_p), POINTER(c_int32), _P]),
     'smx_xchg_free': (c_int32, [_P]),

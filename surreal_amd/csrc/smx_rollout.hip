@@ -928,17 +928,7 @@ __device__ __forceinline__ float explore(float mu, int noise, float e, double si
     return clip1(a);
 }
 
-// the closing transition's reward: r_j + g[e] r_{j+1} + ..., left to right in fp64 (the host wrapper's `+=` sequence),
-// exponents as ExpSenderWrapperSSARNStepBootstrap._discount_exponent (the reference's ramp-up quirk included)
-__device__ __forceinline__ float nstep_reward(const float* crew_a, const double* gpow, int N, int tau) {
-    const int j = tau - N + 1;
-    double R = (double)crew_a[j % N];
-    for (int u = j + 1; u <= tau; ++u) {
-        const int e = (u >= N - 1) ? (u - j) : (N - 1 - j);
-        R = R + gpow[e] * (double)crew_a[u % N];
-    }
-    return (float)R;
-}
+#include "smx_nstep.inc.h"                           // nstep_reward: the closing transition's reward
 
 __device__ __forceinline__ long long ring_row(const DArgs& G, int kemit, long a) {
     return (G.cursor + (long long)kemit * G.n + a) % G.capacity;

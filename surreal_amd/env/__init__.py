@@ -9,3 +9,5 @@ from .adapters import (ObsTransform, GymAdapter, RobosuiteWrapper, DMControlAdap
 from .monitor import (EpisodeMonitor, ConsoleMonitor, TrainingTensorplexMonitor,
                       EvalTensorplexMonitor, DeviceEpisodeMonitor, DeviceTrainingMonitor, DeviceNoise,
                       DeviceParamNoise)
+from .device_recorder import DeviceWindowRecorder, DeviceNStepRecorder, closing_ranks
+from .host_vec_env import HostVecEnv

@@ -10,6 +10,7 @@ There is NO fallback in the product: `HipKernels()` raises when the library or a
 """
 import ctypes
 
+import numpy as np
 import torch
 
 from surreal_amd import _lib as L
@@ -1017,6 +1018,89 @@ class HipKernels(object):
         p.mon = self._monitor_args(monitor, n)
         p.noise = self._noise_args(noise)
         L.call('smx_synth_ppo_pixel_window_step', ctypes.byref(p), L.ptr(mu), _row_stride(mu, A), self._st())
+
+    @staticmethod
+    def _record_step_args(p, r, N):
+        """checks and fills what the two record launches share: the clocks and ranks (device int32 [n], and the host
+        arrays they were copied from), cur_obs [n, D], the step's results, the cursor -> (n, D, A, tables, capacity)"""
+        n, D = r['cur_obs'].shape
+        A = r['actions'].shape[1]
+        tabs = r['tables']
+        cap = tabs['obs'].shape[0]
+        for k in ('t', 'rank'):
+            assert r[k].dtype == torch.int32 and r[k].is_contiguous() and r[k].numel() == n, k
+            h = r.get(k + '_host')
+            assert h is None or (h.dtype == np.int32 and h.flags['C_CONTIGUOUS'] and h.size == n), k
+            setattr(p, k, L.ptr(r[k]))
+            setattr(p, k + '_host', None if h is None else ctypes.c_void_p(h.ctypes.data))
+        for k, w in (('cur_obs', D), ('actions', A), ('obs_next', D), ('rewards', 1), ('dones', 1), ('obs_reset', D)):
+            x = r.get(k)
+            assert k == 'obs_reset' or x is not None, k
+            assert x is None or (x.dtype == torch.float32 and x.is_contiguous() and x.numel() == n * w), k
+        for k, x in tabs.items():
+            assert x.is_contiguous() and x.dtype == torch.float32 and x.shape[0] == cap, k
+        assert tabs['obs'].shape[1] == N * D and tabs['obs_next'].shape[1] == D and tabs['actions'].shape[1] == N * A
+        assert tabs['rewards'].shape[1] == N and tabs['dones'].shape[1] == N
+        p.n, p.D, p.A, p.n_step, p.rows = n, D, A, N, int(r['rows'])
+        p.cur_obs, p.step_actions, p.step_obs_next = L.ptr(r['cur_obs']), L.ptr(r['actions']), L.ptr(r['obs_next'])
+        p.step_rewards, p.step_dones, p.step_obs_reset = L.ptr(r['rewards']), L.ptr(r['dones']), L.ptr(r.get('obs_reset'))
+        p.cursor, p.capacity = int(r['cursor']), cap
+        return n, D, A, tabs, cap
+
+    def record_ppo_window_step(self, r, copy_workgroups=0, monitor=None):
+        """ONE step of n host-stepped actors' moving windows, every actor on its own episode clock
+        (include/surreal_amd.h smx_record_ppo_window_step_f32).  r: t / rank int32 [n] on the device (t_host / rank_host:
+        the numpy arrays they were copied from, checked before the launch), rows (the closing actors), cur_obs [n, D]
+        (in: acted on, out: the next acting observation), actions [n, A], pds [n, 2A], obs_next [n, D], rewards [n],
+        dones [n] (0 / 1), obs_reset [n, D] or None, h_before / c_before [n, Hl] or None, n_step, advance, carry {'obs',
+        'actions', 'rewards', 'pds' (, 'cells')}, tables (the FIFO's ring by replay field name), cursor"""
+        N = int(r['n_step'])
+        p = L.RecordPpoWindowStep()
+        n, D, A, tabs, cap = self._record_step_args(p, r, N)
+        carry = r['carry']
+        for k, x in carry.items():
+            assert x.is_contiguous() and x.dtype == torch.float32, k
+        assert tuple(carry['obs'].shape) == (n, N, D) and tuple(carry['actions'].shape) == (n, N, A)
+        assert tuple(carry['rewards'].shape) == (n, N) and tuple(carry['pds'].shape) == (n, N, 2 * A)
+        assert r['pds'].is_contiguous() and r['pds'].dtype == torch.float32 and r['pds'].numel() == n * 2 * A
+        assert tabs['pds'].shape[1] == N * 2 * A
+        hb, cb = r.get('h_before'), r.get('c_before')
+        Hl = 0
+        if 'cells' in carry:
+            Hl = carry['cells'].shape[-1]
+            assert tuple(carry['cells'].shape) == (n, -(-N // int(r['advance'])), 2, Hl)
+            for x in (hb, cb):
+                assert x is None or (x.is_contiguous() and x.dtype == torch.float32 and x.numel() == n * Hl)
+            assert 'cells' not in tabs or tabs['cells'].shape[1] == 2 * Hl
+        else:
+            assert hb is None and cb is None and 'cells' not in tabs
+        p.hidden, p.step_pds, p.h_before, p.c_before = Hl, L.ptr(r['pds']), L.ptr(hb), L.ptr(cb)
+        cursor = p.cursor
+        self._window_args(p, N, r['advance'], carry, tabs, cursor)
+        p.copy_workgroups = int(copy_workgroups)
+        p.mon = self._monitor_args(monitor, n)
+        L.call('smx_record_ppo_window_step_f32', ctypes.byref(p), self._st())
+
+    def record_ddpg_nstep_step(self, r, monitor=None):
+        """ONE step of n host-stepped actors' n-step transitions, every actor on its own episode clock
+        (include/surreal_amd.h smx_record_ddpg_nstep_step_f32).  r: as record_ppo_window_step without pds, cells and
+        advance; gpow [n_step] fp64 (gamma ** e), carry {'obs', 'actions', 'rewards'}, tables: the uniform replay's ring
+        (obs / obs_next [capacity, D], actions [capacity, A], rewards / dones [capacity, 1])"""
+        N = int(r['n_step'])
+        p = L.RecordDdpgNstepStep()
+        n, D, A, tabs, cap = self._record_step_args(p, r, 1)
+        carry = r['carry']
+        for k, x in carry.items():
+            assert x.is_contiguous() and x.dtype == torch.float32, k
+        assert tuple(carry['obs'].shape) == (n, N, D) and tuple(carry['actions'].shape) == (n, N, A)
+        assert tuple(carry['rewards'].shape) == (n, N)
+        assert r['gpow'].dtype == torch.float64 and r['gpow'].is_contiguous() and r['gpow'].numel() == N
+        p.n_step, p.gpow = N, L.ptr(r['gpow'])
+        p.carry_obs, p.carry_act, p.carry_rew = L.ptr(carry['obs']), L.ptr(carry['actions']), L.ptr(carry['rewards'])
+        p.obs, p.obs_next, p.actions = L.ptr(tabs['obs']), L.ptr(tabs['obs_next']), L.ptr(tabs['actions'])
+        p.rewards, p.dones = L.ptr(tabs['rewards']), L.ptr(tabs['dones'])
+        p.mon = self._monitor_args(monitor, n)
+        L.call('smx_record_ddpg_nstep_step_f32', ctypes.byref(p), self._st())
 
     def synth_env_step(self, state, init_state, actions, t, episode_len, slot, obs_roll, act_roll,
                        rew_roll, done_roll, monitor=None):
