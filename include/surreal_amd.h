@@ -1614,6 +1614,114 @@ struct smx_record_ddpg_nstep_step {        /* (by tag: no typedef) */
 };
 int smx_record_ddpg_nstep_step_f32(const struct smx_record_ddpg_nstep_step* args, smx_stream_t stream);
 
+/* The same two steps for host-stepped actors WITH A CAMERA (the reference's pixel configurations: FrameStackWrapper,
+ * surreal/env/wrapper.py:407-472, between the simulator and the experience wrappers of surreal/env/
+ * exp_sender_wrapper.py:72-112 and 153-264; ppo_configs.py / ddpg_configs.py:176-228 with pixel_input, frame_stacks 3):
+ * everything smx_record_ppo_window_step_f32 / smx_record_ddpg_nstep_step_f32 do -- rings, windows, n-step reward, cells,
+ * monitor, the t / rank / rows guards and the t_host / rank_host check -- and, in the same launch, the frames.  The
+ * simulators emit ONE raw uint8 frame per step; the stacking is done here.  F = C*H*W bytes per frame, S = frame_stacks,
+ * N = n_step, tau = t[a], Hd = hist_len >= N + S, p = hist_pos: ONE counter for all actors, which the caller advances by
+ * 1 (mod Hd) per launch, because every actor receives exactly one frame per step:
+ *   step_frame_next [n, F]   the frame after the step (the terminal frame where step_dones[a] != 0)
+ *   step_frame_reset [n, F]  the first frame of the next episode: only the rows of done actors are read; NULL: no actor
+ *                            is done (a done actor then goes on from step_frame_next, as cur_obs does from
+ *                            step_obs_next without a step_obs_reset)
+ *   history:  hist[a, (p - tau + u) mod Hd] holds the raw frame of step u of actor a's current episode, u <= tau
+ *   stacked(u)[i] = frame of step max(u - S + 1 + i, 0), 0 <= i < S                        (stack_sources)
+ *   hist[a, (p + 1) mod Hd] = step_frame_reset[a] where done, else step_frame_next[a]: the terminal frame never enters
+ *             the history
+ *   obs_pixel[a] = step_frame_reset[a] S times where done, else stacked(tau + 1) (its last frame: step_frame_next[a])
+ *   PPO, closing window j = tau + 1 - N into its row: pixel[row, u] = stacked(j + u), u < N; pixel_next[row] =
+ *             stacked(tau + 1), its last frame step_frame_next[a]: the terminal frame on done
+ *   DDPG, emitting step into its row: pixel[row] = stacked(tau - N + 1); pixel_next[row] = stacked(tau + 1)
+ * pixel is uint8 [capacity, N, S*F] (DDPG: [capacity, S*F]), pixel_next [capacity, S*F], obs_pixel [n, S*F] (what the
+ * actors act on next), hist [n, Hd, F].  The frames a launch reads from the history are those of episode steps
+ * max(tau - N - S + 2, 0) .. tau; the slot it writes is that of step tau + 1 - Hd <= tau - N - S + 1, and the step's own
+ * frames come from the inputs: no workgroup reads what another one writes in the same launch.
+ * Grid: per actor one workgroup does the low-dimensional step and stores step_frame_next wherever it goes;
+ * copy_workgroups further workgroups per actor split the other destination frames (0: sized by the bytes the step moves
+ * -- a closing PPO step has (N + 1) S - 1 destination frames more than any other; <= 1024).  16-byte accesses when
+ * F % 16 == 0 and all six frame buffers sit on 16 bytes, single bytes otherwise.  No atomics.
+ * Limits beyond those of the low-dimensional entry points (D >= 1 among them: an observation without a low-dimensional
+ * part is not taken): C, H, W, frame_stacks >= 1, hist_len >= n_step + frame_stacks, 0 <= hist_pos < hist_len
+ * (SMX_E_SHAPE); hist, pixel, pixel_next, obs_pixel, step_frame_next non-NULL (SMX_E_NULL); n <= capacity (SMX_E_SHAPE).
+ * The actors lie on the grid's x axis: no limit on n of its own. */
+struct smx_record_ppo_pixel_window_step {  /* (by tag: no typedef) */
+    int32_t n, D, A, hidden;               /* hidden: the LSTM's units (0: a policy without one) */
+    int32_t n_step, advance, rows, copy_workgroups;
+    const int32_t* t;
+    const int32_t* rank;
+    const int32_t* t_host;                 /* NULL: not checked on the host */
+    const int32_t* rank_host;
+    float* cur_obs;
+    const float* step_actions;
+    const float* step_pds;
+    const float* h_before;                 /* [n, hidden] the LSTM state the step started from, or NULL */
+    const float* c_before;
+    const float* step_obs_next;
+    const float* step_rewards;
+    const float* step_dones;
+    const float* step_obs_reset;           /* NULL: no actor is done */
+    float* carry_obs;
+    float* carry_act;
+    float* carry_rew;
+    float* carry_pd;
+    float* carry_cells;                    /* NULL without an LSTM */
+    float* obs;
+    float* obs_next;
+    float* actions;
+    float* rewards;
+    float* dones;
+    float* pds;
+    float* cells;                          /* NULL without an LSTM */
+    int64_t cursor, capacity;
+    int32_t C, H, W, frame_stacks;
+    int32_t hist_len, hist_pos;
+    const uint8_t* step_frame_next;        /* [n, F] */
+    const uint8_t* step_frame_reset;       /* [n, F], or NULL: no actor is done */
+    uint8_t* hist;                         /* [n, Hd, F] */
+    uint8_t* pixel;                        /* [capacity, N, S*F] */
+    uint8_t* pixel_next;                   /* [capacity, S*F] */
+    uint8_t* obs_pixel;                    /* [n, S*F] */
+    struct smx_episode_monitor mon;        /* mon.ep_reward NULL: none (stays the last member) */
+};
+int smx_record_ppo_pixel_window_step(const struct smx_record_ppo_pixel_window_step* args, smx_stream_t stream);
+
+struct smx_record_ddpg_pixel_nstep_step {  /* (by tag: no typedef) */
+    int32_t n, D, A, n_step;
+    int32_t rows, copy_workgroups;
+    const int32_t* t;
+    const int32_t* rank;
+    const int32_t* t_host;                 /* NULL: not checked on the host */
+    const int32_t* rank_host;
+    float* cur_obs;
+    const float* step_actions;
+    const float* step_obs_next;
+    const float* step_rewards;
+    const float* step_dones;
+    const float* step_obs_reset;           /* NULL: no actor is done */
+    const double* gpow;
+    float* carry_obs;
+    float* carry_act;
+    float* carry_rew;
+    float* obs;
+    float* obs_next;
+    float* actions;
+    float* rewards;
+    float* dones;
+    int64_t cursor, capacity;
+    int32_t C, H, W, frame_stacks;
+    int32_t hist_len, hist_pos;
+    const uint8_t* step_frame_next;        /* [n, F] */
+    const uint8_t* step_frame_reset;       /* [n, F], or NULL: no actor is done */
+    uint8_t* hist;                         /* [n, Hd, F] */
+    uint8_t* pixel;                        /* [capacity, S*F] */
+    uint8_t* pixel_next;                   /* [capacity, S*F] */
+    uint8_t* obs_pixel;                    /* [n, S*F] */
+    struct smx_episode_monitor mon;        /* mon.ep_reward NULL: none (stays the last member) */
+};
+int smx_record_ddpg_pixel_nstep_step(const struct smx_record_ddpg_pixel_nstep_step* args, smx_stream_t stream);
+
 /* ---------------------------------------------------------------------------
  * Data-parallel exchange between the learner ranks of one node over IPC-mapped peer buffers (xGMI loads): the
  * collectives N sharded learners need to equal the single reference learner -- the per-epoch

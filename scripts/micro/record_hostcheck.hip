@@ -46,6 +46,31 @@ static smx_record_ddpg_nstep_step ddpg(const std::vector<int32_t>& t, const std:
     return p;
 }
 
+// the camera of either camera argument block: 1 x 4 x 4 frames, 3 stacked, the shortest history n_step 4 allows
+template <typename Block>
+static void fill_camera(Block& p) {
+    uint8_t* frames = reinterpret_cast<uint8_t*>(4096);
+    p.C = 1; p.H = 4; p.W = 4; p.frame_stacks = 3; p.hist_len = 7; p.hist_pos = 6;
+    p.step_frame_next = frames; p.step_frame_reset = frames;
+    p.hist = frames; p.pixel = frames; p.pixel_next = frames; p.obs_pixel = frames;
+}
+
+static struct smx_record_ppo_pixel_window_step ppo_pixel(const std::vector<int32_t>& t, const std::vector<int32_t>& rank) {
+    struct smx_record_ppo_pixel_window_step p;   // (the tag: the entry point has the same name)
+    fill_shared(p, t, rank);
+    p.advance = 3; p.step_pds = fake(); p.carry_pd = fake(); p.pds = fake();
+    fill_camera(p);
+    return p;
+}
+
+static struct smx_record_ddpg_pixel_nstep_step ddpg_pixel(const std::vector<int32_t>& t, const std::vector<int32_t>& rank) {
+    struct smx_record_ddpg_pixel_nstep_step p;
+    fill_shared(p, t, rank);
+    p.gpow = reinterpret_cast<const double*>(4096);
+    fill_camera(p);
+    return p;
+}
+
 int main() {
     const std::vector<int32_t> t = {0, 3, 4, 7, 1}, rank = {-1, 0, -1, 1, -1};
     const std::vector<int32_t> t_neg = {0, 3, -1, 7, 1}, rank_big = {-1, 0, -1, 5, -1}, rank_low = {-1, 0, -2, 1, -1};
@@ -95,6 +120,44 @@ int main() {
         expect("ddpg: n > capacity", smx_record_ddpg_nstep_step_f32(&p, nullptr), SMX_E_SHAPE);
         p = ddpg(t, rank); p.n_step = 0;
         expect("ddpg: n_step 0", smx_record_ddpg_nstep_step_f32(&p, nullptr), SMX_E_SHAPE);
+    }
+    {
+        auto p = ppo_pixel(t, rank); p.hist = nullptr;
+        expect("ppo pixel: null history", smx_record_ppo_pixel_window_step(&p, nullptr), SMX_E_NULL);
+        p = ppo_pixel(t, rank); p.step_frame_next = nullptr;
+        expect("ppo pixel: null step_frame_next", smx_record_ppo_pixel_window_step(&p, nullptr), SMX_E_NULL);
+        p = ppo_pixel(t, rank); p.obs = nullptr;
+        expect("ppo pixel: null obs table", smx_record_ppo_pixel_window_step(&p, nullptr), SMX_E_NULL);
+        p = ppo_pixel(t, rank); p.hist_len = 6;
+        expect("ppo pixel: hist_len < n_step + frame_stacks", smx_record_ppo_pixel_window_step(&p, nullptr), SMX_E_SHAPE);
+        p = ppo_pixel(t, rank); p.hist_pos = 7;
+        expect("ppo pixel: hist_pos == hist_len", smx_record_ppo_pixel_window_step(&p, nullptr), SMX_E_SHAPE);
+        p = ppo_pixel(t, rank); p.hist_pos = -1;
+        expect("ppo pixel: hist_pos < 0", smx_record_ppo_pixel_window_step(&p, nullptr), SMX_E_SHAPE);
+        p = ppo_pixel(t, rank); p.capacity = 4;
+        expect("ppo pixel: n > capacity", smx_record_ppo_pixel_window_step(&p, nullptr), SMX_E_SHAPE);
+        p = ppo_pixel(t, rank); p.rows = 3;
+        expect("ppo pixel: rows != closing actors", smx_record_ppo_pixel_window_step(&p, nullptr), SMX_E_SHAPE);
+        p = ppo_pixel(t, rank); p.D = 0;
+        expect("ppo pixel: D 0 (a pixel-only observation)", smx_record_ppo_pixel_window_step(&p, nullptr), SMX_E_SHAPE);
+        p = ppo_pixel(t, rank); p.copy_workgroups = 1025;
+        expect("ppo pixel: copy_workgroups > 1024", smx_record_ppo_pixel_window_step(&p, nullptr), SMX_E_SHAPE);
+    }
+    {
+        auto p = ddpg_pixel(t, rank); p.pixel_next = nullptr;
+        expect("ddpg pixel: null pixel_next table", smx_record_ddpg_pixel_nstep_step(&p, nullptr), SMX_E_NULL);
+        p = ddpg_pixel(t, rank); p.gpow = nullptr;
+        expect("ddpg pixel: null gpow", smx_record_ddpg_pixel_nstep_step(&p, nullptr), SMX_E_NULL);
+        p = ddpg_pixel(t, rank); p.hist_len = 6;
+        expect("ddpg pixel: hist_len < n_step + frame_stacks", smx_record_ddpg_pixel_nstep_step(&p, nullptr), SMX_E_SHAPE);
+        p = ddpg_pixel(t, rank); p.hist_pos = 7;
+        expect("ddpg pixel: hist_pos == hist_len", smx_record_ddpg_pixel_nstep_step(&p, nullptr), SMX_E_SHAPE);
+        p = ddpg_pixel(t, rank); p.frame_stacks = 0;
+        expect("ddpg pixel: frame_stacks 0", smx_record_ddpg_pixel_nstep_step(&p, nullptr), SMX_E_SHAPE);
+        p = ddpg_pixel(t_neg, rank);
+        expect("ddpg pixel: t < 0", smx_record_ddpg_pixel_nstep_step(&p, nullptr), SMX_E_SHAPE);
+        p = ddpg_pixel(t, rank); p.copy_workgroups = -1;
+        expect("ddpg pixel: copy_workgroups < 0", smx_record_ddpg_pixel_nstep_step(&p, nullptr), SMX_E_SHAPE);
     }
     printf("%d unexpected\n", failures);
     return failures != 0;

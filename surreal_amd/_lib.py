@@ -278,6 +278,23 @@ class RecordDdpgNstepStep(Structure):
                 [('cursor', c_int64), ('capacity', c_int64), ('mon', EpisodeMonitor)])
 
 
+_RECORD_CAMERA = ([(n, c_int32) for n in ('C', 'H', 'W', 'frame_stacks', 'hist_len', 'hist_pos')] +
+                  [(n, c_void_p) for n in ('step_frame_next', 'step_frame_reset', 'hist', 'pixel', 'pixel_next',
+                                           'obs_pixel')])
+
+
+class RecordPpoPixelWindowStep(Structure):
+    """struct smx_record_ppo_pixel_window_step: RecordPpoWindowStep with the camera in front of `mon`"""
+    _fields_ = RecordPpoWindowStep._fields_[:-1] + _RECORD_CAMERA + [('mon', EpisodeMonitor)]
+
+
+class RecordDdpgPixelNstepStep(Structure):
+    """struct smx_record_ddpg_pixel_nstep_step: RecordDdpgNstepStep (its `reserved`: copy_workgroups) with the camera
+    in front of `mon`"""
+    _fields_ = ([(n, c_int32) for n in ('n', 'D', 'A', 'n_step', 'rows', 'copy_workgroups')] +
+                RecordDdpgNstepStep._fields_[6:-1] + _RECORD_CAMERA + [('mon', EpisodeMonitor)])
+
+
 SMX_DDPG_NOISE_NONE, SMX_DDPG_NOISE_GAUSSIAN, SMX_DDPG_NOISE_OU = 0, 1, 2
 SMX_PPO_PIXEL_STEP_MAX_A = 64            # the actions smx_synth_ppo_pixel_window_step takes
 
@@ -483,6 +500,8 @@ _SIGS = {
     'smx_synth_ppo_pixel_window_step': (c_int32, [POINTER(SynthPpoPixelWindowStep), _P, c_int64, _P]),
     'smx_record_ppo_window_step_f32': (c_int32, [POINTER(RecordPpoWindowStep), _P]),
     'smx_record_ddpg_nstep_step_f32': (c_int32, [POINTER(RecordDdpgNstepStep), _P]),
+    'smx_record_ppo_pixel_window_step': (c_int32, [POINTER(RecordPpoPixelWindowStep), _P]),
+    'smx_record_ddpg_pixel_nstep_step': (c_int32, [POINTER(RecordDdpgPixelNstepStep), _P]),
     'smx_xchg_bytes': (c_int64, [c_int64, c_int32]),
     'smx_xchg_alloc': (c_int32, [c_int64, c_double, POINTER(c_void_p), POINTER(c_int32), _P]),
     'smx_xchg_free': (c_int32, [_P]),

@@ -1,6 +1,8 @@
 // Recording the steps of host-stepped environments into the replays' device rings, one launch per step for all actors,
 // every actor on an episode clock of its own (include/surreal_amd.h: smx_record_ppo_window_step_f32,
-// smx_record_ddpg_nstep_step_f32; the rules are those of surreal_amd/env/exp_sender_wrapper.py).
+// smx_record_ddpg_nstep_step_f32; the rules are those of surreal_amd/env/exp_sender_wrapper.py), and the same two steps
+// for actors with a camera (smx_record_ppo_pixel_window_step, smx_record_ddpg_pixel_nstep_step: further down, with the
+// frames' own statement of the invariant below).
 //
 // Both kernels move bytes.  What a launch reads and what it writes never meet across threads:
 //   * element k of an actor's cur_obs row is read (the observation acted on) and then overwritten (the next one) by the
@@ -99,9 +101,8 @@ __device__ __forceinline__ const V* as(const float* p) { return reinterpret_cast
         else { using V = float; constexpr int E = 1; call; }                \
     } while (0)
 
-__global__ __launch_bounds__(REC_THREADS) void record_ppo_window_kernel(RecW G) {
-    const long a = blockIdx.x;
-    const int x = blockIdx.y, tid = threadIdx.x;
+// one actor's step of the moving windows: workgroup x of the X that share the actor (x == 0: the step itself)
+__device__ __forceinline__ void ppo_window_step(const RecW& G, long a, int x, int X, int tid) {
     const int tau = G.t[a];
     if (tau < 0) return;                                 // (refused on the host where it can see the clocks)
     const int N = G.N, D = G.D, A = G.A, adv = G.adv;
@@ -154,7 +155,7 @@ __global__ __launch_bounds__(REC_THREADS) void record_ppo_window_kernel(RecW G) 
     }
     if (!(wclose && N > 1)) return;
     // ---- the window's N - 1 older steps, out of the rings in episode order --------------------------------------------
-    const int first = x * REC_THREADS + tid, stride = G.X * REC_THREADS, j0 = j % N, U = N - 1;
+    const int first = x * REC_THREADS + tid, stride = X * REC_THREADS, j0 = j % N, U = N - 1;
     REC_BY_WIDTH(VEC_OBS, (copy_older<V>(as<V>(G.obs + row * N * D), as<V>(G.cobs + ring0 * D), D / E, U, N, j0, first,
                                          stride)));
     REC_BY_WIDTH(VEC_PD, (copy_older<V>(as<V>(G.pds + row * N * 2 * A), as<V>(G.cpd + ring0 * 2 * A), 2 * A / E, U, N, j0,
@@ -164,9 +165,13 @@ __global__ __launch_bounds__(REC_THREADS) void record_ppo_window_kernel(RecW G) 
     copy_older<float>(G.rewards + row * N, G.crew + ring0, 1, U, N, j0, first, stride);
 }
 
-__global__ __launch_bounds__(REC_DDPG_THREADS) void record_ddpg_nstep_kernel(RecD G) {
-    const long a = blockIdx.x;
-    const int tid = threadIdx.x;
+__global__ __launch_bounds__(REC_THREADS) void record_ppo_window_kernel(RecW G) {
+    ppo_window_step(G, blockIdx.x, blockIdx.y, G.X, threadIdx.x);
+}
+
+// one actor's step of the n-step transitions, by a workgroup of NT threads
+template <int NT>
+__device__ __forceinline__ void ddpg_nstep_step(const RecD& G, long a, int tid) {
     const int tau = G.t[a];
     if (tau < 0) return;
     const int N = G.N, D = G.D, A = G.A;
@@ -178,11 +183,11 @@ __global__ __launch_bounds__(REC_DDPG_THREADS) void record_ddpg_nstep_kernel(Rec
     const size_t ring0 = (size_t)a * N;
     const bool done = G.done[a] != 0.0f;
     const float* reset = (done && G.oreset) ? G.oreset + a * D : nullptr;
-    REC_BY_WIDTH(VEC_OBS, (step_obs<V, REC_DDPG_THREADS>(
+    REC_BY_WIDTH(VEC_OBS, (step_obs<V, NT>(
         as<V>(G.cur + a * D), as<V>(G.onext + a * D), as<V>(reset), as<V>(G.cobs + (ring0 + wslot) * D),
         emits ? as<V>(G.obs + row * D) : nullptr, emits ? as<V>(G.obs_next + row * D) : nullptr,
         ring_first ? as<V>((const float*)G.cobs + (ring0 + jslot) * D) : nullptr, D / E, tid)));
-    REC_BY_WIDTH(VEC_ACT, (step_row<V, REC_DDPG_THREADS>(
+    REC_BY_WIDTH(VEC_ACT, (step_row<V, NT>(
         as<V>(G.act + a * A), as<V>(G.cact + (ring0 + wslot) * A), emits ? as<V>(G.actions + row * A) : nullptr,
         ring_first ? as<V>((const float*)G.cact + (ring0 + jslot) * A) : nullptr, A / E, tid)));
     if (tid == 0) {
@@ -197,7 +202,151 @@ __global__ __launch_bounds__(REC_DDPG_THREADS) void record_ddpg_nstep_kernel(Rec
     }
 }
 
+__global__ __launch_bounds__(REC_DDPG_THREADS) void record_ddpg_nstep_kernel(RecD G) {
+    ddpg_nstep_step<REC_DDPG_THREADS>(G, blockIdx.x, threadIdx.x);
+}
+
 #undef REC_BY_WIDTH
+
+// ---- the same steps for actors with a camera -----------------------------------------------------------------------------
+// The frame rule of the synthetic camera steps (smx_rollout.hip, above struct PArgs) with the clock PER ACTOR: tau = t[a],
+// p = hist_pos (one counter for all actors: every actor receives one frame per step), Hd = hist_len >= N + S.  The frame
+// of step u of actor a's current episode sits in slot (p - tau + u) mod Hd; slot (p + 1) mod Hd takes the reset frame
+// where done, else the next frame (the terminal frame never enters the history); stacked(u) = frames
+// max(u - S + 1 + i, 0), i < S.  What a launch reads and what it writes never meet across threads here either:
+//   * the frames read from the history are those of episode steps max(tau - N - S + 2, 0) .. tau, in slots
+//     (p - tau + u) mod Hd with tau - u <= N + S - 2 < Hd - 1; the one slot written, (p + 1) mod Hd, is that of step
+//     tau + 1 - Hd <= tau - N - S + 1;
+//   * the step's own frames (next, reset) come from the inputs, which no workgroup writes;
+//   * obs_pixel and the table rows are only written, every destination unit by one thread.
+// Grid (n, 1 + X).  Workgroup (a, 0) does the low-dimensional step exactly as the kernels above do (as their one
+// workgroup), then reads step_frame_next[a] once and stores it wherever it goes: the history and the acting
+// observation's last frame (not on done), pixel_next's last frame at a closing step.  Workgroups (a, 1 .. X) split the
+// actor's other destination frames in units of U bytes (smx_frame_unit.inc.h).
+#include "smx_frame_unit.inc.h"
+
+constexpr int REC_PIXEL_THREADS = 256;
+
+struct RecP {
+    int S, Hd, pos, X;
+    long long F;                               // C H W bytes per frame
+    const unsigned char *fnext, *freset;
+    unsigned char *hist, *pix, *pix_next, *obs_pix;
+};
+
+// workgroup 0's tail: step_frame_next[a] -> the history slot of step tau + 1 and the acting observation's last frame
+// (unless the actor restarts), pixel_next's last frame of `row` at a closing step
+template <int U>
+__device__ __forceinline__ void store_next_frame(const RecP& P, long a, bool restart, bool closing, size_t row, int tid) {
+    const long long F = P.F, SF = (long long)P.S * F, nu = F / U;
+    const size_t last = (size_t)(P.S - 1) * F;
+    const unsigned char* src = P.fnext + (size_t)a * F;
+    unsigned char* d0 = restart ? nullptr : P.hist + ((size_t)a * P.Hd + (size_t)((P.pos + 1) % P.Hd)) * F;
+    unsigned char* d1 = closing ? P.pix_next + row * SF + last : nullptr;
+    unsigned char* d2 = restart ? nullptr : P.obs_pix + (size_t)a * SF + last;
+    if (!d0 && !d1) return;                          // (d2 goes with d0)
+    alignas(16) unsigned char b[U];
+    for (long long v = tid; v < nu; v += REC_PIXEL_THREADS) {
+        load_unit<U>(src + v * U, b);
+        if (d0) store_unit<U>(d0 + v * U, b);
+        if (d1) store_unit<U>(d1 + v * U, b);
+        if (d2) store_unit<U>(d2 + v * U, b);
+    }
+}
+
+// the copy workgroups (y = 1 .. X): item q < nq is one destination frame
+//   restart:  q < 1 + S: step_frame_reset[a] -> the history slot (q = 0), acting observation frame q - 1
+//   else:     q < S - 1: acting observation frame q <- history, step tau + 2 - S + q
+//   then at a closing step the kernel's npix items -- pixel(i, dst, u): destination and source step of item i -- and
+//   S - 1 items: pixel_next frame i of `row` <- step tau + 2 - S + i                              (steps < 0: step 0)
+template <int U, typename Pixel>
+__device__ __forceinline__ void copy_step_frames(const RecP& P, long a, int tau, bool restart, bool closing, size_t row,
+                                                 int npix, int y, int tid, Pixel pixel) {
+    const int S = P.S, Hd = P.Hd;
+    const long long F = P.F, SF = (long long)S * F, nu = F / U;
+    const int nfirst = restart ? 1 + S : S - 1;
+    const int nq = nfirst + (closing ? npix + S - 1 : 0);
+    unsigned char* hist_a = P.hist + (size_t)a * Hd * F;
+    const long long total = (long long)nq * nu, stride = (long long)P.X * REC_PIXEL_THREADS;
+    alignas(16) unsigned char b[U];
+    for (long long g = (long long)(y - 1) * REC_PIXEL_THREADS + tid; g < total; g += stride) {
+        const int q = (int)(g / nu);
+        const long long e = (g - (long long)q * nu) * U;
+        unsigned char* dst;
+        int u = 0;                                   // the source step (unless first: the reset frame)
+        const bool first = restart && q < nfirst;
+        if (q < nfirst) {
+            if (restart) dst = q == 0 ? hist_a + (size_t)((P.pos + 1) % Hd) * F : P.obs_pix + (size_t)a * SF + (size_t)(q - 1) * F;
+            else { dst = P.obs_pix + (size_t)a * SF + (size_t)q * F; u = tau + 2 - S + q; }
+        } else if (q < nfirst + npix) {
+            pixel(q - nfirst, dst, u);
+        } else {
+            const int i = q - nfirst - npix;
+            dst = P.pix_next + row * SF + (size_t)i * F;
+            u = tau + 2 - S + i;
+        }
+        if (first) {
+            load_unit<U>(P.freset + (size_t)a * F + e, b);
+        } else {
+            u = u < 0 ? 0 : u;
+            const int hs = (((P.pos - tau + u) % Hd) + Hd) % Hd;
+            load_unit<U>(hist_a + (size_t)hs * F + e, b);
+        }
+        store_unit<U>(dst + e, b);
+    }
+}
+
+template <int U>
+__global__ __launch_bounds__(REC_PIXEL_THREADS) void record_ppo_pixel_window_kernel(RecW G, RecP P) {
+    const long a = blockIdx.x;
+    const int y = blockIdx.y, tid = threadIdx.x;
+    const int tau = G.t[a];
+    if (tau < 0) return;
+    const int N = G.N, S = P.S;
+    const int j = tau + 1 - N;
+    const int rank = G.rank[a];
+    const bool wclose = rank >= 0 && rank < G.rows && j >= 0 && j % G.adv == 0;      // (ppo_window_step's rule)
+    const size_t row = wclose ? (size_t)((G.cursor + rank) % G.capacity) : 0;
+    const bool restart = G.done[a] != 0.0f && P.freset;
+    if (y == 0) {
+        ppo_window_step(G, a, 0, 1, tid);
+        store_next_frame<U>(P, a, restart, wclose, row, tid);
+        return;
+    }
+    // the closing window's N S items: pixel frame i of window step w <- step j + w - S + 1 + i
+    const long long F = P.F;
+    copy_step_frames<U>(P, a, tau, restart, wclose, row, N * S, y, tid, [&](int q, unsigned char*& dst, int& u) {
+        const int w = q / S, i = q - w * S;
+        dst = P.pix + (row * N + w) * (size_t)S * F + (size_t)i * F;
+        u = j + w - S + 1 + i;
+    });
+}
+
+template <int U>
+__global__ __launch_bounds__(REC_PIXEL_THREADS) void record_ddpg_pixel_nstep_kernel(RecD G, RecP P) {
+    const long a = blockIdx.x;
+    const int y = blockIdx.y, tid = threadIdx.x;
+    const int tau = G.t[a];
+    if (tau < 0) return;
+    const int N = G.N, S = P.S;
+    const int rank = G.rank[a];
+    const bool emits = rank >= 0 && rank < G.rows && tau >= N - 1;                   // (ddpg_nstep_step's rule)
+    const size_t row = emits ? (size_t)((G.cursor + rank) % G.capacity) : 0;
+    const bool restart = G.done[a] != 0.0f && P.freset;
+    if (y == 0) {
+        ddpg_nstep_step<REC_PIXEL_THREADS>(G, a, tid);
+        store_next_frame<U>(P, a, restart, emits, row, tid);
+        return;
+    }
+    // the emitted transition j's S items: pixel frame i <- step j - S + 1 + i
+    const int j = tau - N + 1;
+    const long long F = P.F;
+    copy_step_frames<U>(P, a, tau, restart, emits, row, S, y, tid, [&](int i, unsigned char*& dst, int& u) {
+        dst = P.pix + row * (size_t)S * F + (size_t)i * F;
+        u = j - S + 1 + i;
+    });
+}
+
 
 // ---- host side -------------------------------------------------------------------------------------------------------
 
@@ -241,9 +390,10 @@ int window_copy_workgroups(const smx_record_ppo_window_step& a) {
     return X < 1 ? 1 : (int)X;
 }
 
-}  // namespace
-
-extern "C" int smx_record_ppo_window_step_f32(const struct smx_record_ppo_window_step* a, smx_stream_t stream) {
+// ---- what the low-dimensional and the camera entry points of a step share: the checks (the SMX_E_* code, SMX_OK) and
+// the kernel's argument block, from either argument struct ----
+template <typename Block>
+int window_step_check(const Block* a) {
     SMX_REQUIRE(a && step_pointers(*a) && a->step_pds && a->carry_pd && a->pds, SMX_E_NULL);
     SMX_REQUIRE((a->h_before == nullptr) == (a->c_before == nullptr) && episode_pointers_ok(a->mon), SMX_E_NULL);
     // an LSTM policy's cells: the ring whenever a state comes in or a window's cells go out
@@ -252,12 +402,23 @@ extern "C" int smx_record_ppo_window_step_f32(const struct smx_record_ppo_window
     SMX_REQUIRE(!a->carry_cells || a->hidden > 0, SMX_E_SHAPE);
     SMX_REQUIRE(a->copy_workgroups >= 0 && a->copy_workgroups <= 1024 && episode_shape_ok(a->mon), SMX_E_SHAPE);
     SMX_REQUIRE(clocks_ok(a->t_host, a->rank_host, a->n, a->rows), SMX_E_SHAPE);
+    return SMX_OK;
+}
+
+template <typename Block>
+bool obs_on16(const Block* a) {
+    return a->D % 4 == 0 && on16(a->cur_obs) && on16(a->step_obs_next) && on16(a->step_obs_reset) && on16(a->carry_obs) &&
+           on16(a->obs) && on16(a->obs_next);
+}
+
+template <typename Block>
+RecW window_step_fields(const Block* a) {
     RecW G;
     memset(&G, 0, sizeof(G));
     G.n = a->n; G.D = a->D; G.A = a->A; G.Hl = a->hidden; G.N = a->n_step; G.adv = a->advance;
     G.S = (a->n_step + a->advance - 1) / a->advance;
     G.rows = a->rows;
-    G.X = a->copy_workgroups ? a->copy_workgroups : window_copy_workgroups(*a);
+    G.X = 1;
     G.t = a->t; G.rank = a->rank;
     G.cur = a->cur_obs; G.act = a->step_actions; G.pd = a->step_pds; G.hb = a->h_before; G.cb = a->c_before;
     G.onext = a->step_obs_next; G.rew = a->step_rewards; G.done = a->step_dones; G.oreset = a->step_obs_reset;
@@ -266,20 +427,22 @@ extern "C" int smx_record_ppo_window_step_f32(const struct smx_record_ppo_window
     G.pds = a->pds; G.cells = a->cells;
     G.cursor = a->cursor; G.capacity = a->capacity;
     G.mon = a->mon;
-    if (a->D % 4 == 0 && on16(a->cur_obs) && on16(a->step_obs_next) && on16(a->step_obs_reset) && on16(a->carry_obs) &&
-        on16(a->obs) && on16(a->obs_next))
-        G.vec |= VEC_OBS;
+    if (obs_on16(a)) G.vec |= VEC_OBS;
     if (a->A % 4 == 0 && on16(a->step_actions) && on16(a->carry_act) && on16(a->actions)) G.vec |= VEC_ACT;
     if (a->A % 2 == 0 && on16(a->step_pds) && on16(a->carry_pd) && on16(a->pds)) G.vec |= VEC_PD;
-    hipLaunchKernelGGL(record_ppo_window_kernel, dim3(a->n, G.X), dim3(REC_THREADS), 0, smx_s(stream), G);
-    SMX_LAUNCH_CHECK();
-    return SMX_OK;
+    return G;
 }
 
-extern "C" int smx_record_ddpg_nstep_step_f32(const struct smx_record_ddpg_nstep_step* a, smx_stream_t stream) {
+template <typename Block>
+int nstep_step_check(const Block* a) {
     SMX_REQUIRE(a && step_pointers(*a) && a->gpow && episode_pointers_ok(a->mon), SMX_E_NULL);
     SMX_REQUIRE(step_shape_ok(*a) && episode_shape_ok(a->mon), SMX_E_SHAPE);
     SMX_REQUIRE(clocks_ok(a->t_host, a->rank_host, a->n, a->rows), SMX_E_SHAPE);
+    return SMX_OK;
+}
+
+template <typename Block>
+RecD nstep_step_fields(const Block* a) {
     RecD G;
     memset(&G, 0, sizeof(G));
     G.n = a->n; G.D = a->D; G.A = a->A; G.N = a->n_step; G.rows = a->rows;
@@ -290,11 +453,95 @@ extern "C" int smx_record_ddpg_nstep_step_f32(const struct smx_record_ddpg_nstep
     G.obs = a->obs; G.obs_next = a->obs_next; G.actions = a->actions; G.rewards = a->rewards; G.dones = a->dones;
     G.cursor = a->cursor; G.capacity = a->capacity;
     G.mon = a->mon;
-    if (a->D % 4 == 0 && on16(a->cur_obs) && on16(a->step_obs_next) && on16(a->step_obs_reset) && on16(a->carry_obs) &&
-        on16(a->obs) && on16(a->obs_next))
-        G.vec |= VEC_OBS;
+    if (obs_on16(a)) G.vec |= VEC_OBS;
     if (a->A % 4 == 0 && on16(a->step_actions) && on16(a->carry_act) && on16(a->actions)) G.vec |= VEC_ACT;
+    return G;
+}
+
+// the camera of either camera argument struct: the frame buffers and the input frame, the frame, and a history long
+// enough that no launch reads the slot it writes (proof above struct RecP)
+template <typename Block>
+int camera_check(const Block* a) {
+    SMX_REQUIRE(a->hist && a->pixel && a->pixel_next && a->obs_pixel && a->step_frame_next, SMX_E_NULL);
+    SMX_REQUIRE(a->C > 0 && a->H > 0 && a->W > 0 && a->frame_stacks > 0, SMX_E_SHAPE);
+    SMX_REQUIRE(a->hist_len >= a->n_step + a->frame_stacks && a->hist_pos >= 0 && a->hist_pos < a->hist_len, SMX_E_SHAPE);
+    SMX_REQUIRE(a->copy_workgroups >= 0 && a->copy_workgroups <= 1024, SMX_E_SHAPE);
+    return SMX_OK;
+}
+
+// ... with X copy workgroups per actor: copy_workgroups, or ~32 KB each of the destination frames of the actor that
+// moves most -- one that restarts and, with rows > 0, closes: 1 + S frames and `closing` more -- and no more than 16
+// workgroups per CU over the launch's closing actors
+template <typename Block>
+RecP camera_fields(const Block* a, long long closing) {
+    RecP P;
+    memset(&P, 0, sizeof(P));
+    P.S = a->frame_stacks; P.Hd = a->hist_len; P.pos = a->hist_pos;
+    P.F = (long long)a->C * a->H * a->W;
+    P.fnext = a->step_frame_next; P.freset = a->step_frame_reset;
+    P.hist = a->hist; P.pix = a->pixel; P.pix_next = a->pixel_next; P.obs_pix = a->obs_pixel;
+    long long X = a->copy_workgroups;
+    if (X == 0) {
+        const long long frames = 1 + P.S + (a->rows > 0 ? closing : 0);
+        X = (frames * P.F + 32767) / 32768;
+        if (a->rows > 0) {
+            const long long room = 16LL * smx_cu_count() / a->rows;
+            if (X > room) X = room;
+        }
+        if (X > 64) X = 64;
+    }
+    P.X = X < 1 ? 1 : (int)X;
+    return P;
+}
+
+// a camera record kernel on the grid (n, 1 + X): K16 moves 16 bytes a lane where the frame size and every frame buffer
+// allow it, else K1 single bytes
+template <auto K16, auto K1, typename Args>
+int launch_camera(const Args& G, const RecP& P, int n, smx_stream_t stream) {
+    const bool vec = P.F % 16 == 0 && on16(P.fnext) && on16(P.freset) && on16(P.hist) && on16(P.pix) && on16(P.pix_next) &&
+                     on16(P.obs_pix);
+    hipLaunchKernelGGL(vec ? K16 : K1, dim3(n, 1 + P.X), dim3(REC_PIXEL_THREADS), 0, smx_s(stream), G, P);
+    SMX_LAUNCH_CHECK();
+    return SMX_OK;
+}
+
+}  // namespace
+
+extern "C" int smx_record_ppo_window_step_f32(const struct smx_record_ppo_window_step* a, smx_stream_t stream) {
+    const int rc = window_step_check(a);
+    if (rc != SMX_OK) return rc;
+    RecW G = window_step_fields(a);
+    G.X = a->copy_workgroups ? a->copy_workgroups : window_copy_workgroups(*a);
+    hipLaunchKernelGGL(record_ppo_window_kernel, dim3(a->n, G.X), dim3(REC_THREADS), 0, smx_s(stream), G);
+    SMX_LAUNCH_CHECK();
+    return SMX_OK;
+}
+
+extern "C" int smx_record_ddpg_nstep_step_f32(const struct smx_record_ddpg_nstep_step* a, smx_stream_t stream) {
+    const int rc = nstep_step_check(a);
+    if (rc != SMX_OK) return rc;
+    const RecD G = nstep_step_fields(a);
     hipLaunchKernelGGL(record_ddpg_nstep_kernel, dim3(a->n), dim3(REC_DDPG_THREADS), 0, smx_s(stream), G);
     SMX_LAUNCH_CHECK();
     return SMX_OK;
 }
+
+extern "C" int smx_record_ppo_pixel_window_step(const struct smx_record_ppo_pixel_window_step* a, smx_stream_t stream) {
+    int rc = window_step_check(a);
+    if (rc == SMX_OK) rc = camera_check(a);
+    if (rc != SMX_OK) return rc;
+    const RecW G = window_step_fields(a);
+    // a closing step: the window's N S stacked frames and pixel_next's S - 1 older ones
+    const RecP P = camera_fields(a, (long long)(a->n_step + 1) * a->frame_stacks - 1);
+    return launch_camera<record_ppo_pixel_window_kernel<16>, record_ppo_pixel_window_kernel<1>>(G, P, a->n, stream);
+}
+
+extern "C" int smx_record_ddpg_pixel_nstep_step(const struct smx_record_ddpg_pixel_nstep_step* a, smx_stream_t stream) {
+    int rc = nstep_step_check(a);
+    if (rc == SMX_OK) rc = camera_check(a);
+    if (rc != SMX_OK) return rc;
+    const RecD G = nstep_step_fields(a);
+    const RecP P = camera_fields(a, 2LL * a->frame_stacks - 1);
+    return launch_camera<record_ddpg_pixel_nstep_kernel<16>, record_ddpg_pixel_nstep_kernel<1>>(G, P, a->n, stream);
+}
+

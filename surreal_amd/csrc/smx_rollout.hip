@@ -1186,25 +1186,7 @@ __device__ __forceinline__ void render_unit(const PArgs& P, long long e0, int sh
     }
 }
 
-template <int U>
-__device__ __forceinline__ void store_unit(unsigned char* dst, const unsigned char* b) {
-    if constexpr (U == 16) {
-        *(uint4*)dst = *(const uint4*)b;
-    } else {
-#pragma unroll
-        for (int i = 0; i < U; ++i) dst[i] = b[i];
-    }
-}
-
-template <int U>
-__device__ __forceinline__ void load_unit(const unsigned char* src, unsigned char* b) {
-    if constexpr (U == 16) {
-        *(uint4*)b = *(const uint4*)src;
-    } else {
-#pragma unroll
-        for (int i = 0; i < U; ++i) b[i] = src[i];
-    }
-}
+#include "smx_frame_unit.inc.h"                         // store_unit / load_unit, shared with smx_record.hip
 
 // The frame half of both camera step kernels.  An actor's frames at step tau:
 struct FrameCtx {

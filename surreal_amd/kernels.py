@@ -1038,7 +1038,8 @@ class HipKernels(object):
             assert k == 'obs_reset' or x is not None, k
             assert x is None or (x.dtype == torch.float32 and x.is_contiguous() and x.numel() == n * w), k
         for k, x in tabs.items():
-            assert x.is_contiguous() and x.dtype == torch.float32 and x.shape[0] == cap, k
+            assert x.is_contiguous() and x.shape[0] == cap, k
+            assert x.dtype == (torch.uint8 if k in ('pixel', 'pixel_next') else torch.float32), k
         assert tabs['obs'].shape[1] == N * D and tabs['obs_next'].shape[1] == D and tabs['actions'].shape[1] == N * A
         assert tabs['rewards'].shape[1] == N and tabs['dones'].shape[1] == N
         p.n, p.D, p.A, p.n_step, p.rows = n, D, A, N, int(r['rows'])
@@ -1047,15 +1048,9 @@ class HipKernels(object):
         p.cursor, p.capacity = int(r['cursor']), cap
         return n, D, A, tabs, cap
 
-    def record_ppo_window_step(self, r, copy_workgroups=0, monitor=None):
-        """ONE step of n host-stepped actors' moving windows, every actor on its own episode clock
-        (include/surreal_amd.h smx_record_ppo_window_step_f32).  r: t / rank int32 [n] on the device (t_host / rank_host:
-        the numpy arrays they were copied from, checked before the launch), rows (the closing actors), cur_obs [n, D]
-        (in: acted on, out: the next acting observation), actions [n, A], pds [n, 2A], obs_next [n, D], rewards [n],
-        dones [n] (0 / 1), obs_reset [n, D] or None, h_before / c_before [n, Hl] or None, n_step, advance, carry {'obs',
-        'actions', 'rewards', 'pds' (, 'cells')}, tables (the FIFO's ring by replay field name), cursor"""
+    def _record_ppo_args(self, p, r, copy_workgroups, monitor):
+        """checks and fills a PPO record launch's argument struct `p` (either entry point) from r"""
         N = int(r['n_step'])
-        p = L.RecordPpoWindowStep()
         n, D, A, tabs, cap = self._record_step_args(p, r, N)
         carry = r['carry']
         for k, x in carry.items():
@@ -1079,15 +1074,21 @@ class HipKernels(object):
         self._window_args(p, N, r['advance'], carry, tabs, cursor)
         p.copy_workgroups = int(copy_workgroups)
         p.mon = self._monitor_args(monitor, n)
+
+    def record_ppo_window_step(self, r, copy_workgroups=0, monitor=None):
+        """ONE step of n host-stepped actors' moving windows, every actor on its own episode clock
+        (include/surreal_amd.h smx_record_ppo_window_step_f32).  r: t / rank int32 [n] on the device (t_host / rank_host:
+        the numpy arrays they were copied from, checked before the launch), rows (the closing actors), cur_obs [n, D]
+        (in: acted on, out: the next acting observation), actions [n, A], pds [n, 2A], obs_next [n, D], rewards [n],
+        dones [n] (0 / 1), obs_reset [n, D] or None, h_before / c_before [n, Hl] or None, n_step, advance, carry {'obs',
+        'actions', 'rewards', 'pds' (, 'cells')}, tables (the FIFO's ring by replay field name), cursor"""
+        p = L.RecordPpoWindowStep()
+        self._record_ppo_args(p, r, copy_workgroups, monitor)
         L.call('smx_record_ppo_window_step_f32', ctypes.byref(p), self._st())
 
-    def record_ddpg_nstep_step(self, r, monitor=None):
-        """ONE step of n host-stepped actors' n-step transitions, every actor on its own episode clock
-        (include/surreal_amd.h smx_record_ddpg_nstep_step_f32).  r: as record_ppo_window_step without pds, cells and
-        advance; gpow [n_step] fp64 (gamma ** e), carry {'obs', 'actions', 'rewards'}, tables: the uniform replay's ring
-        (obs / obs_next [capacity, D], actions [capacity, A], rewards / dones [capacity, 1])"""
+    def _record_ddpg_args(self, p, r, monitor):
+        """checks and fills a DDPG record launch's argument struct `p` (either entry point) from r"""
         N = int(r['n_step'])
-        p = L.RecordDdpgNstepStep()
         n, D, A, tabs, cap = self._record_step_args(p, r, 1)
         carry = r['carry']
         for k, x in carry.items():
@@ -1100,7 +1101,47 @@ class HipKernels(object):
         p.obs, p.obs_next, p.actions = L.ptr(tabs['obs']), L.ptr(tabs['obs_next']), L.ptr(tabs['actions'])
         p.rewards, p.dones = L.ptr(tabs['rewards']), L.ptr(tabs['dones'])
         p.mon = self._monitor_args(monitor, n)
+
+    def record_ddpg_nstep_step(self, r, monitor=None):
+        """ONE step of n host-stepped actors' n-step transitions, every actor on its own episode clock
+        (include/surreal_amd.h smx_record_ddpg_nstep_step_f32).  r: as record_ppo_window_step without pds, cells and
+        advance; gpow [n_step] fp64 (gamma ** e), carry {'obs', 'actions', 'rewards'}, tables: the uniform replay's ring
+        (obs / obs_next [capacity, D], actions [capacity, A], rewards / dones [capacity, 1])"""
+        p = L.RecordDdpgNstepStep()
+        self._record_ddpg_args(p, r, monitor)
         L.call('smx_record_ddpg_nstep_step_f32', ctypes.byref(p), self._st())
+
+    def _record_camera_args(self, p, r, frames_per_row):
+        """the camera block of a record launch: _camera_args' buffers (hist, hist_pos, obs_pixel, the 'pixel' /
+        'pixel_next' tables) and the step's frames: frames_next uint8 [n, C, H, W], frames_reset the same or None"""
+        self._camera_args(p, dict(r, state=r['cur_obs']), frames_per_row)
+        n, C, H, W = r['hist'].shape[0], p.C, p.H, p.W
+        for k in ('frames_next', 'frames_reset'):
+            x = r.get(k)
+            assert k == 'frames_reset' or x is not None, k
+            assert x is None or (x.dtype == torch.uint8 and x.is_contiguous() and x.numel() == n * C * H * W), k
+        p.step_frame_next, p.step_frame_reset = L.ptr(r['frames_next']), L.ptr(r.get('frames_reset'))
+
+    def record_ppo_pixel_window_step(self, r, copy_workgroups=0, monitor=None):
+        """record_ppo_window_step for actors with a camera, the frames in the same launch (include/surreal_amd.h
+        smx_record_ppo_pixel_window_step).  r also holds hist uint8 [n, Hd, C, H, W] (actor a's current frame in slot
+        hist_pos), hist_pos, obs_pixel uint8 [n, S*C, H, W] (receives the stacked observation of the next step),
+        frames_next / frames_reset uint8 [n, C, H, W] (frames_reset None: no actor is done) and the ring tables 'pixel'
+        [capacity, n_step * S*C*H*W] / 'pixel_next' [capacity, S*C*H*W] uint8.  copy_workgroups: the workgroups per
+        actor that move frames"""
+        p = L.RecordPpoPixelWindowStep()
+        self._record_ppo_args(p, r, copy_workgroups, monitor)
+        self._record_camera_args(p, r, int(r['n_step']))
+        L.call('smx_record_ppo_pixel_window_step', ctypes.byref(p), self._st())
+
+    def record_ddpg_pixel_nstep_step(self, r, copy_workgroups=0, monitor=None):
+        """record_ddpg_nstep_step for actors with a camera (include/surreal_amd.h smx_record_ddpg_pixel_nstep_step): r
+        as record_ppo_pixel_window_step's camera entries, tables 'pixel' / 'pixel_next' [capacity, S*C*H*W] uint8"""
+        p = L.RecordDdpgPixelNstepStep()
+        self._record_ddpg_args(p, r, monitor)
+        self._record_camera_args(p, r, 1)
+        p.copy_workgroups = int(copy_workgroups)
+        L.call('smx_record_ddpg_pixel_nstep_step', ctypes.byref(p), self._st())
 
     def synth_env_step(self, state, init_state, actions, t, episode_len, slot, obs_roll, act_roll,
                        rew_roll, done_roll, monitor=None):
