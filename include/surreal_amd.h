@@ -1382,6 +1382,58 @@ int32_t smx_synth_ddpg_population_block(int32_t n, int32_t actors_per_agent, int
  * the actor's output mu [n, A] (row stride ld_mu) from any forward pass */
 int smx_synth_ddpg_step_f32(const smx_ddpg_rollout_t* args, const float* mu, int64_t ld_mu, smx_stream_t stream);
 
+/* An episode clock PER ACTOR for the two one-launch, low-dimensional rollouts above (the shared clock of
+ * smx_synth_ppo_window_rollout_f32 / smx_synth_ddpg_rollout_f32 makes all actors end their episodes on the same step; the
+ * reference's actors are n independent processes, surreal/agent/base.py:244-271).  Actor a has an episode length
+ * L[a] >= 1 and a clock t[a] in [0, L[a]); one step: tau = t[a], done = (tau + 1 >= L[a]), t[a] = done ? 0 : tau + 1.
+ * Everything that depends on the shared tau there depends on the actor's own here: the carry-ring slots tau % N, the
+ * LSTM window-start slot, the closing rule (j = tau + 1 - N >= 0 and j % adv == 0; adv = 1 for DDPG), the reset to
+ * init_state, the OU process's x = 0 at tau == 0, dones, the monitor.  What stays on the call's step index s and the actor
+ * id: the exploration noise (eps[s, a, :] or the stream), noise_scale / sigmas, the population and its measure_step, the
+ * LSTM state (never reset at episode ends).
+ * Row order: the closing pairs (s, a) of a call are numbered s ascending, then a ascending -- the order in which n host
+ * wrappers stepped in actor order insert; pair number `off` goes to row (cursor + off) % capacity.  With all clocks
+ * equal that is the shared clock's (cursor + k n + a).  The numbering is a pure function of the clocks: with
+ * f(x) = x >= N ? (x - N) / adv + 1 : 0, m = min(s, L - t0), r = s - m the closings of an actor in its first s steps are
+ *   cnt(s) = f(t0 + m) - f(t0) + (r / L) f(L) + f(r % L)
+ * and off[s, a] = sum_a' cnt_a'(s) + #{a' < a closing at s}: no atomics, nothing read back; the host forms `rows` (the
+ * number of pairs) and the clocks after the call by the same rule.
+ *
+ * smx_actor_clock_rows_i32: row_off [steps, n] int32 <- off[s, a], -1 where (s, a) closes nothing.  ONE launch (workgroup
+ * s: a sum over the actors, then a ballot / popcount scan in actor order).  t / episode_len [n] int32 on the device;
+ * t_host / episode_len_host: the host arrays they were copied from, or NULL: checked before the launch (t outside
+ * [0, L), L < 1: SMX_E_SHAPE).  advance outside [1, n_step], n * steps >= 2^31: SMX_E_SHAPE.  An actor whose device
+ * clock is outside [0, L) closes nothing. */
+struct smx_actor_clock_rows {              /* (by tag: no typedef) */
+    int32_t n, steps;
+    int32_t n_step, advance;
+    const int32_t* t;
+    const int32_t* episode_len;
+    const int32_t* t_host;                 /* NULL: not checked on the host */
+    const int32_t* episode_len_host;
+    int32_t* row_off;                      /* [steps, n] */
+};
+int smx_actor_clock_rows_i32(const struct smx_actor_clock_rows* args, smx_stream_t stream);
+
+/* The clocks of a call and its table (smx_actor_clock_rows_i32 with the call's steps, n_step and advance -- 1 for DDPG);
+ * rows: the table's closing pairs.  The kernels write a record only where the actor's own clock closes one AND
+ * 0 <= row_off < rows: a table that does not belong to the clocks loses records, it never writes out of bounds. */
+struct smx_actor_clocks {                  /* (by tag: no typedef) */
+    const int32_t* t;                      /* [n] at the call's first step */
+    const int32_t* episode_len;            /* [n] */
+    const int32_t* row_off;                /* [steps, n] */
+    int64_t rows;
+};
+/* smx_synth_ppo_window_rollout_f32 / smx_synth_ddpg_rollout_f32 with per-actor clocks: the same argument blocks
+ * (base.roll.t / episode_len, resp. t / episode_len, are ignored), the same supported shapes, the same checks with
+ * 0 <= clocks->rows <= capacity (SMX_E_SHAPE) in place of n x closing steps <= capacity; clocks and its three pointers
+ * non-NULL (SMX_E_NULL).  The clocks are read once and stored nowhere: the host knows them.  4, 8 and 16 actors per
+ * workgroup give the same bits; an actor's records equal those of the shared-clock launch with episode_len = L[a]. */
+int smx_synth_ppo_window_rollout_clocks_f32(const struct smx_synth_ppo_window_rollout* args,
+                                            const struct smx_actor_clocks* clocks, smx_stream_t stream);
+int smx_synth_ddpg_rollout_clocks_f32(const smx_ddpg_rollout_t* args, const struct smx_ddpg_actor_variant* variant,
+                                      const struct smx_actor_clocks* clocks, smx_stream_t stream);
+
 /* Parameter-space noise of the device actors (surreal/agent/param_noise.py): a population of perturbed actors, one per
  * AGENT -- a group of consecutive actors that share one perturbation, as the actors of one reference agent process do
  * (an agent here spans at least the 4 actors of one MFMA row block, where the reference's spans one environment).  The

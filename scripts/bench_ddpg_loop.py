@@ -52,6 +52,8 @@ def main():
     ap.add_argument('--learn-iters', type=int, default=16)
     ap.add_argument('--batch', type=int, default=512)
     ap.add_argument('--episode-len', type=int, default=1000)
+    ap.add_argument('--episode-lens', type=int, nargs=2, metavar=('LO', 'HI'), default=None,
+                    help='with --calls: an episode clock per actor, actor a with episodes of LO + a %% (HI - LO + 1) steps')
     ap.add_argument('--monitor', action='store_true',
                     help='attach the on-device episode monitor: every line also carries mean_episode_return, the mean of '
                          'the last 10 polled episode returns per actor (null before an episode has finished)')
@@ -71,6 +73,8 @@ def main():
         ap.error('--param-noise measures single calls: give --calls N')
     if args.per_step and not (args.layernorm and args.calls and not args.param_noise):
         ap.error('--per-step goes with --layernorm --calls N, without --param-noise')
+    if args.episode_lens and not args.calls:
+        ap.error('--episode-lens measures single calls of the one-launch path: give --calls N')
     n, T, D, A = args.actors, args.steps, args.obs_dim, args.action_dim
     H1, H2 = args.hidden
     lc = ddpg_learner_config()
@@ -87,7 +91,11 @@ def main():
         for k, v in agent.model.actor_ln.items():
             v.copy_(torch.rand_like(v) + 0.5 if k.endswith('.W') else 0.1 * torch.randn_like(v))
     flops = 2.0 * n * T * (D * H1 + H1 * H2 + H2 * A)
-    venv = SyntheticVecEnv(n, D, A, episode_len=args.episode_len, device='cuda')
+    episode_len = args.episode_len
+    if args.episode_lens:
+        lo, hi = args.episode_lens
+        episode_len = [lo + a % (hi - lo + 1) for a in range(n)]
+    venv = SyntheticVecEnv(n, D, A, episode_len=episode_len, device='cuda')
     mon = venv.attach_monitor() if args.monitor else None
 
     def returns(line):

@@ -40,13 +40,19 @@ def _timed(fn):
     return a.elapsed_time(b)
 
 
-def bench_rollouts(reps, warmup, shapes, monitor=False, device_noise=False):
+def bench_rollouts(reps, warmup, shapes, monitor=False, device_noise=False, episode_lens=None):
+    """episode_lens (LO, HI): an episode clock per actor for ppo_rollout_into, actor a with episodes of
+    LO + a % (HI - LO + 1) steps; the table rollout next to it keeps the shared clock"""
     lines = []
     for n, T, D, A, hidden, H, (N, stride), L in shapes:
+        own = None
+        if episode_lens:
+            lo, hi = episode_lens
+            own = [lo + a % (hi - lo + 1) for a in range(n)]
         agent, cfg = PW.make_agent(D, A, N, stride, hidden=hidden, rnn_hidden=H, memory_size=n * (T // min(N, stride)
                                                                                                   + 2))
         replay = FIFOReplay(*cfg)
-        win = SyntheticVecEnv(n, D, A, episode_len=L)
+        win = SyntheticVecEnv(n, D, A, episode_len=own or L)
         tab = SyntheticVecEnv(n, D, A, episode_len=L)
         mon = win.attach_monitor() if monitor else None
         tab.start_rollout(T, info_width=2 * A)
@@ -75,9 +81,9 @@ def bench_rollouts(reps, warmup, shapes, monitor=False, device_noise=False):
                 replay.sample_batch(min(len(replay), replay.memory_size), copy=False)
         w, t = _stats(times['window']), _stats(times['rollout'])
         lines.append({'case': 'rollout', 'n': n, 'T': T, 'D': D, 'A': A, 'hidden': list(hidden), 'rnn_hidden': H,
-                      'n_step': N, 'stride': stride, 'episode_len': L, 'reps': reps, 'device_noise': device_noise,
-                      'windows_per_call': sorted(set(rows)), 'ppo_rollout_into_ms': w, 'rollout_ms': t,
-                      'ratio_median': w['median'] / t['median']})
+                      'n_step': N, 'stride': stride, 'episode_len': L, 'episode_lens': list(episode_lens or ()) or None,
+                      'reps': reps, 'device_noise': device_noise, 'windows_per_call': sorted(set(rows)),
+                      'ppo_rollout_into_ms': w, 'rollout_ms': t, 'ratio_median': w['median'] / t['median']})
         if mon is not None:
             mon.poll()
             lines[-1].update(mean_episode_return=mon.mean_reward(last=10), episodes=mon.num_episodes)
@@ -136,10 +142,14 @@ def main():
     ap.add_argument('--device-noise', action='store_true',
                     help='draw the exploration noise inside the launches from the env\'s Philox stream (attach_noise): no '
                          'eps tensor is made or read')
+    ap.add_argument('--episode-lens', type=int, nargs=2, metavar=('LO', 'HI'), default=None,
+                    help='the rollout cases with an episode clock per actor: actor a has episodes of LO + a %% (HI - LO + 1) '
+                         'steps (the loop case is not run)')
     args = ap.parse_args()
     reps, warmup = (1, 1) if args.quick else (args.reps, args.warmup)
-    lines = bench_rollouts(reps, warmup, ROLLOUTS, args.monitor, args.device_noise) + \
-        bench_loop(reps, warmup, monitor=args.monitor, device_noise=args.device_noise)
+    lines = bench_rollouts(reps, warmup, ROLLOUTS, args.monitor, args.device_noise, args.episode_lens)
+    if not args.episode_lens:
+        lines += bench_loop(reps, warmup, monitor=args.monitor, device_noise=args.device_noise)
     if args.out:
         with open(args.out, 'w') as f:
             for ln in lines:

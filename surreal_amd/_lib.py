@@ -229,6 +229,17 @@ class DdpgActorVariant(Structure):
                 ('measure_step', c_int32), ('reserved2', c_int32), ('dist', c_void_p)]
 
 
+class ActorClockRows(Structure):
+    """struct smx_actor_clock_rows"""
+    _fields_ = ([(n, c_int32) for n in ('n', 'steps', 'n_step', 'advance')] +
+                [(n, c_void_p) for n in ('t', 'episode_len', 't_host', 'episode_len_host', 'row_off')])
+
+
+class ActorClocks(Structure):
+    """struct smx_actor_clocks"""
+    _fields_ = [('t', c_void_p), ('episode_len', c_void_p), ('row_off', c_void_p), ('rows', c_int64)]
+
+
 class ParamNoise(Structure):
     """struct smx_param_noise"""
     _fields_ = [('net', POINTER(Mlp3)), ('seed', c_uint64), ('agent_base', c_int64), ('generation', c_int64),
@@ -492,6 +503,10 @@ _SIGS = {
     'smx_synth_ddpg_rollout_supported': (c_int32, [c_int32, c_int32, c_int32, c_int32, c_int32]),
     'smx_synth_ddpg_rollout_f32': (c_int32, [POINTER(DdpgRollout), POINTER(DdpgActorVariant), _P]),
     'smx_synth_ddpg_population_block': (c_int32, [c_int32, c_int32, c_int32]),
+    'smx_actor_clock_rows_i32': (c_int32, [POINTER(ActorClockRows), _P]),
+    'smx_synth_ppo_window_rollout_clocks_f32': (c_int32, [POINTER(SynthPpoWindowRollout), POINTER(ActorClocks), _P]),
+    'smx_synth_ddpg_rollout_clocks_f32': (c_int32, [POINTER(DdpgRollout), POINTER(DdpgActorVariant),
+                                                    POINTER(ActorClocks), _P]),
     'smx_synth_ddpg_step_f32': (c_int32, [POINTER(DdpgRollout), _P, c_int64, _P]),
     'smx_synth_ddpg_pixel_step': (c_int32, [POINTER(DdpgPixelStep), _P, c_int64, _P]),
     'smx_param_noise_copy_floats': (c_int64, [c_int32, c_int32, c_int32, c_int32, c_int32]),

@@ -35,6 +35,10 @@
 //                               windows' carry rings and frame history, the closing windows' fields and stacked uint8
 //                               pixel / pixel_next into the FIFO's ring (ppo_pixel_window_step_kernel).
 //
+//   smx_synth_ppo_window_rollout_clocks_f32 / smx_synth_ddpg_rollout_clocks_f32  the windowed PPO and the DDPG launch with
+//                               an episode clock PER ACTOR (struct smx_actor_clocks; the row table of smx_actor_clock.hip):
+//                               the CLK instantiations of the same kernels (ClkArgs).
+//
 // Layout: the persistent kernels (PPO, then DDPG), the step kernels (the two camera ones share their frame half:
 // frame_ctx / render_next_frame / copy_frames), then the host side: carve() and launch(), the argument fills (net_fields,
 // roll_fields, table_fields, lstm_fields, win_fields, pixel_fields), the rules the entry points share (*_ok, *_pointers),
@@ -162,6 +166,43 @@ struct PopLnArgs : PopArgs { LnTail ln; };
 template <bool POP, bool LN>
 using DdpgArgs = std::conditional_t<LN, std::conditional_t<POP, PopLnArgs, DLnArgs>, std::conditional_t<POP, PopArgs, DArgs>>;
 
+// Episode clocks per actor (struct smx_actor_clocks; the CLK instantiations of the windowed PPO kernels and of the DDPG
+// kernel, which take one of these behind their arguments).  The block's clocks live in LDS, three ints per actor row at
+// `off` (carve_clocks()): the actor's clock, its episode length, and this step's row_off word, which the row's head
+// lane requested before the layers.  Every reader sits behind a barrier of the step; one lane per actor advances the
+// clock behind the step's last barrier.  They are stored nowhere at exit: the host knows them.
+struct ClkArgs {
+    const int32_t *t, *L, *row_off;
+    long long rows;
+    int off;
+};
+struct NoClk {};
+// a CLK kernel's arguments: those of its shared-clock twin, then the clocks
+template <typename Base>
+struct WithClk : Base { ClkArgs clk; };
+template <typename Base>
+__device__ __forceinline__ ClkArgs clk_of(const WithClk<Base>& G) { return G.clk; }
+__device__ __forceinline__ NoClk clk_of(const RollBase&) { return NoClk{}; }
+
+// the ring row of a closing record from its row_off word, which the caller found in [0, rows) (rows <= capacity: one
+// wrap at most)
+__device__ __forceinline__ long long clk_row(long long cursor, long long capacity, int off) {
+    const long long r = cursor + off;
+    return r >= capacity ? r - capacity : r;
+}
+
+// actor row r's clock and episode length into the block's LDS words.  The ring slots are tau % N: a clock outside
+// [0, L) or a length < 1 (the host checks both where it makes the table) is taken as clock 0 / length 1, so that no
+// slot index is ever negative
+__device__ __forceinline__ void clk_load(const ClkArgs& C, int* clk, int r, long row0) {
+    int t = C.t[row0 + r], L = C.L[row0 + r];
+    if (L < 1) L = 1;
+    if (t < 0 || t >= L) t = 0;
+    clk[3 * r] = t;
+    clk[3 * r + 1] = L;
+    clk[3 * r + 2] = -1;
+}
+
 // ---- once per launch: clear the tiles (their padding columns and rows must read as zeros, the action tile's unused
 // columns too); k % A (an integer division per element and step otherwise) and, with the z-filter's running sums, its
 // mean | std go to the LDS tables at off_kmod and off_z
@@ -257,7 +298,8 @@ struct EnvLanes {
     // One environment step of the block's actors from the clipped actions in s_act [RB][RMAX_A] (unused columns 0),
     // the next state (the reset state when `done`) into the registers and the x tile.  The recording is the caller's:
     // p = open(a) once per actor row, rec(a, p, k, s, sn) per element (state s, next state sn), close(a, p, reward).
-    template <typename Open, typename Rec, typename Close>
+    // ROWDONE (per-actor episode clocks): the row's own p.done in place of `done`.
+    template <bool ROWDONE = false, typename Open, typename Rec, typename Close>
     __device__ __forceinline__ void step(const float* s_act, bool done, Open open, Rec rec, Close close) {
 #pragma unroll
         for (int rr = 0; rr < RPW; ++rr) {
@@ -265,6 +307,7 @@ struct EnvLanes {
             if (r < nrows) {
                 const long a = row0 + r;
                 const auto p = open(a);
+                if constexpr (ROWDONE) done = p.done;
                 float sn0 = 0.f;
 #pragma unroll
                 for (int i = 0; i < KPL; ++i) {
@@ -433,8 +476,13 @@ __device__ __forceinline__ void copy_window(int N, int first, Ld ld, St st) {
 // wrote its steps copy them into the FIFO row (cursor + k n + a) % capacity (k: the closing steps of the launch before
 // this one), with obs_next the observation after the step (the terminal one before a reset) and the window's dones 0
 // but the last (= done: a window never crosses an episode, the clock restarts at 0).
-template <int RG, int NT, bool LSTM, bool COLS, bool WIN = false, typename Args>
-__device__ __forceinline__ void ppo_rollout(Args G) {
+// CLK (WIN only; Clk = ClkArgs): an episode clock per actor.  What a step takes from the shared clock t -- wslot, wfirst,
+// wstart, wclose, done -- every reader forms for ITS actor row from the row's clock in LDS (rowclk), and a closing
+// window's FIFO row comes from the call's row_off table, (cursor + row_off[step, a]) % capacity, where the clock closes
+// one and the word lies in [0, rows).
+template <int RG, int NT, bool LSTM, bool COLS, bool WIN = false, bool CLK = false, typename Args, typename Clk = NoClk>
+__device__ __forceinline__ void ppo_rollout(Args G, Clk C = Clk{}) {
+    static_assert(!CLK || WIN, "per-actor clocks: the windowed kernels");
     constexpr int RB = 4 * RG;                       // actors per workgroup
     extern __shared__ float sm[];
     const int tid = threadIdx.x, lane = tid & 63;
@@ -453,6 +501,11 @@ __device__ __forceinline__ void ppo_rollout(Args G) {
     SMX_LDS_BARRIER();
     const long row0 = E.row0;
     const int nrows = E.nrows;
+    int* clk = nullptr;                          // (CLK) [RB][3]: clock, episode length, this step's row_off word
+    if constexpr (CLK) {
+        clk = (int*)(sm + C.off);
+        if (tid < nrows) clk_load(C, clk, tid, row0);        // (first read behind the first layer's barrier)
+    }
     if constexpr (LSTM) {
         float* cst = sm + G.off_c;
 #pragma unroll 1
@@ -512,10 +565,42 @@ __device__ __forceinline__ void ppo_rollout(Args G) {
             wstart = t % G.W.adv == 0;
             wclose = wj >= 0 && wj % G.W.adv == 0;
         }
+        const bool done = (t + 1 >= G.episode_len);
+        // what the step takes from the clock, for actor row r: the shared values, or (CLK) formed from the row's own
+        struct RowClk { int t, wslot, wfirst; bool wstart, wclose, done; };
+        auto rowclk = [&](int r) -> RowClk {
+            if constexpr (CLK) {
+                const int tr = clk[3 * r], wj = tr + 1 - G.W.N;
+                return RowClk{tr, tr % G.W.N, (tr + 1) % G.W.N, tr % G.W.adv == 0, wj >= 0 && wj % G.W.adv == 0,
+                              tr + 1 >= clk[3 * r + 1]};
+            } else {
+                (void)r;
+                return RowClk{t, wslot, wfirst, wstart, wclose, done};
+            }
+        };
+        // the FIFO row of actor a's closing window; (CLK) `off`: its row_off word, which must lie in [0, rows) -- else
+        // `closes` turns false and nothing is written
+        auto fifo_row = [&](long a, int off, bool& closes) -> long long {
+            if constexpr (CLK) {
+                (void)a;
+                closes = closes && off >= 0 && off < C.rows;
+                return closes ? clk_row(G.W.cursor, G.W.capacity, off) : 0;
+            } else if constexpr (WIN) {
+                (void)off;
+                return closes ? win_row(G.W, wbase, a) : 0;
+            } else {
+                (void)a; (void)off; (void)closes;
+                return 0;
+            }
+        };
         RSTAMP(0);
         // this step's normal draw of the lane's (row, action) pair, requested before the layers (consumed behind them)
         float ev = 0.f;
         if (noisy && hr < nrows) ev = noise_pick(G.eps, ((size_t)step * G.n + row0 + hr) * A + hj, G.nstream, row0 + hr, step, hj);
+        int hoff = -1;                               // (CLK) the pair's row_off word, requested here for the same reason
+        if constexpr (CLK) {
+            if (hr < nrows) hoff = C.row_off[(size_t)step * G.n + row0 + hr];
+        }
         // ---- the three layers (the output layer below when its weights are register-resident) -------------------
         if constexpr (LSTM) {
             const PreLayer gate{G.Pg, G.bg, 4 * G.H, G.Dp + G.H, G.off_g, G.ldg};
@@ -552,14 +637,23 @@ __device__ __forceinline__ void ppo_rollout(Args G) {
                             if constexpr (WIN) {
                                 const WinArgs& W = G.W;
                                 float* cc = W.ccell + (size_t)a * W.S * 2 * Hl + j;
-                                if (wstart) {
-                                    float* cw = cc + (size_t)((t / W.adv) % W.S) * 2 * Hl;
+                                const RowClk k = rowclk(r);
+                                if (k.wstart) {
+                                    float* cw = cc + (size_t)((k.t / W.adv) % W.S) * 2 * Hl;
                                     cw[0] = *hp;
                                     cw[Hl] = c0;
                                 }
-                                if (wclose) {
-                                    const float* cr = cc + (size_t)(((t + 1 - W.N) / W.adv) % W.S) * 2 * Hl;
-                                    float* d = W.cells + win_row(W, wbase, a) * 2 * Hl + j;
+                                bool closes = k.wclose;
+                                // ((CLK) the row_off word is read here, at closing steps only: the row's head lane
+                                // publishes its copy only behind the layers)
+                                int off = 0;
+                                if constexpr (CLK) {
+                                    if (closes) off = C.row_off[(size_t)step * G.n + a];
+                                }
+                                const long long row = fifo_row(a, off, closes);
+                                if (closes) {
+                                    const float* cr = cc + (size_t)(((k.t + 1 - W.N) / W.adv) % W.S) * 2 * Hl;
+                                    float* d = W.cells + row * 2 * Hl + j;
                                     __builtin_nontemporal_store(cr[0], d);
                                     __builtin_nontemporal_store(cr[Hl], d + Hl);
                                 }
@@ -612,7 +706,6 @@ __device__ __forceinline__ void ppo_rollout(Args G) {
             RSTAMP(3);
         }
         // ---- sampling head (smx_diaggauss_sample_f32's expressions): one (actor, action) pair per lane -------
-        const bool done = (t + 1 >= G.episode_len);
         if (hr < nrows) {
             const long a = row0 + hr;
             float mu;
@@ -646,14 +739,20 @@ __device__ __forceinline__ void ppo_rollout(Args G) {
                 const int N = W.N;
                 float* ca = W.cact + (size_t)a * N * A + hj;
                 float* cp = W.cpd + (size_t)a * N * 2 * A + hj;
-                ca[(size_t)wslot * A] = act;
-                cp[(size_t)wslot * 2 * A] = mu;
-                cp[(size_t)wslot * 2 * A + A] = sd;
-                if (wclose) {
-                    const long long row = win_row(W, wbase, a);
+                const RowClk k = rowclk(hr);
+                ca[(size_t)k.wslot * A] = act;
+                cp[(size_t)k.wslot * 2 * A] = mu;
+                cp[(size_t)k.wslot * 2 * A + A] = sd;
+                // ((CLK) the row's word for the environment lanes, which read it behind the barrier below)
+                if constexpr (CLK) {
+                    if (hj == 0) clk[3 * hr + 2] = hoff;
+                }
+                bool closes = k.wclose;
+                const long long row = fifo_row(a, hoff, closes);
+                if (closes) {
                     float* da = W.act + (row * N) * A + hj;
                     float* dp = W.pd + (row * N) * 2 * A + hj;
-                    copy_window<8, 3>(N, wfirst,
+                    copy_window<8, 3>(N, k.wfirst,
                         [&](int s, int c) { return c == 0 ? ca[(size_t)s * A] : cp[(size_t)s * 2 * A + (c - 1) * A]; },
                         [&](int u, int c, float v) {
                             if (c == 0) __builtin_nontemporal_store(v, da + (size_t)u * A);
@@ -687,27 +786,37 @@ __device__ __forceinline__ void ppo_rollout(Args G) {
             // rewards and dones into the FIFO row when one closes; its observations below
             const WinArgs& W = G.W;
             const int N = W.N;
-            struct Row { float* co; long long row; };
-            E.step(s_act, done,
-                   [&](long a) { return Row{W.cobs + ((size_t)a * N + wslot) * D, wclose ? win_row(W, wbase, a) : 0}; },
+            // (the row's slot, closing window and done travel in what open(a) returns: with CLK they are the row's own)
+            struct Row { float* co; long long row; int wslot, wfirst; bool wclose, done; };
+            auto open_row = [&](long a) {
+                const int r = (int)(a - row0);
+                const RowClk k = rowclk(r);
+                bool closes = k.wclose;
+                int off = 0;
+                if constexpr (CLK) off = clk[3 * r + 2];
+                const long long row = fifo_row(a, off, closes);
+                return Row{W.cobs + ((size_t)a * N + k.wslot) * D, row, k.wslot, k.wfirst, closes, k.done};
+            };
+            E.template step<CLK>(s_act, done, open_row,
                    [&](long, const Row& p, int k, float s, float sn) {
                        p.co[k] = s;
-                       if (wclose) __builtin_nontemporal_store(sn, &W.obs_next[p.row * D + k]);
+                       if (p.wclose) __builtin_nontemporal_store(sn, &W.obs_next[p.row * D + k]);
                    },
                    [&](long a, const Row& p, float rew) {
                        float* cr = W.crew + (size_t)a * N;
-                       cr[wslot] = rew;
-                       if (wclose) {
+                       cr[p.wslot] = rew;
+                       if (p.wclose) {
                            float* dr = W.rew + p.row * N;
                            float* dd = W.done + p.row * N;
-                           copy_window<8, 1>(N, wfirst, [&](int s, int) { return cr[s]; },
+                           const bool last = p.done;
+                           copy_window<8, 1>(N, p.wfirst, [&](int s, int) { return cr[s]; },
                                              [&](int u, int, float v) {
                                                  __builtin_nontemporal_store(v, dr + u);
-                                                 __builtin_nontemporal_store((done && u == N - 1) ? 1.0f : 0.0f, dd + u);
+                                                 __builtin_nontemporal_store((last && u == N - 1) ? 1.0f : 0.0f, dd + u);
                                              });
                        }
                    });
-            if (wclose) {
+            if (CLK || wclose) {
                 // the window's observations: every lane copies the elements it wrote, RPW rows of KPL each
                 using EL = decltype(E);
 #pragma unroll
@@ -715,9 +824,11 @@ __device__ __forceinline__ void ppo_rollout(Args G) {
                     const int r = E.erow0 + rr;
                     if (r < nrows) {
                         const long a = row0 + r;
+                        const Row p = open_row(a);
+                        if (!p.wclose) continue;
                         const float* co = W.cobs + (size_t)a * N * D;
-                        float* dst = W.obs + win_row(W, wbase, a) * N * D;
-                        copy_window<32 / EL::KPL, EL::KPL>(N, wfirst,
+                        float* dst = W.obs + p.row * N * D;
+                        copy_window<32 / EL::KPL, EL::KPL>(N, p.wfirst,
                             [&](int s, int i) { const int k = E.kel(i); return k < D ? co[(size_t)s * D + k] : 0.f; },
                             [&](int u, int i, float v) {
                                 const int k = E.kel(i);
@@ -726,13 +837,20 @@ __device__ __forceinline__ void ppo_rollout(Args G) {
                     }
                 }
             }
-            if (wclose) {
+            if (!CLK && wclose) {
                 wbase += G.n;
                 wbase = wbase >= G.W.capacity ? wbase - G.W.capacity : wbase;
             }
         }
         t = done ? 0 : t + 1;
         SMX_LDS_BARRIER();
+        if constexpr (CLK) {
+            // every reader of the step's clocks is behind the barrier above; the next ones follow a layer's barrier
+            if (tid < nrows) {
+                const int tr = clk[3 * tid];
+                clk[3 * tid] = (tr + 1 >= clk[3 * tid + 1]) ? 0 : tr + 1;
+            }
+        }
         RSTAMP(5);
     }
     RWALL(14); RCYC(15);
@@ -773,6 +891,17 @@ __global__ __launch_bounds__(RNTH) void ppo_window_kernel(RollArgsW G) {
 template <int RG>
 __global__ __launch_bounds__(RNTH) void lstm_window_kernel(LArgsW G) {
     ppo_rollout<RG, RG == 4 ? 2 : 3, true, RG < 4, true>(G);
+}
+
+// The same two with an episode clock per actor (smx_synth_ppo_window_rollout_clocks_f32)
+template <int RG>
+__global__ __launch_bounds__(RNTH) void ppo_window_clk_kernel(WithClk<RollArgsW> G) {
+    ppo_rollout<RG, RG == 4 ? 2 : 3, false, RG < 4, true, true>((RollArgsW)G, G.clk);
+}
+
+template <int RG>
+__global__ __launch_bounds__(RNTH) void lstm_window_clk_kernel(WithClk<LArgsW> G) {
+    ppo_rollout<RG, RG == 4 ? 2 : 3, true, RG < 4, true, true>((LArgsW)G, G.clk);
 }
 
 constexpr int RTG = 3;            // feature tiles a wave carries per pass (register budget of two waves per SIMD)
@@ -950,9 +1079,14 @@ constexpr int RLN_MAXC = 10;                         // columns per lane: H1, H2
 // barrier of each hidden layer and a barrier of its own behind it.  The gains and biases the workgroup's layers use --
 // the clean actor's, or (POP) its agent's perturbed ones -- are copied to LDS once; the clean actor of a measuring step
 // reads its own from memory.
-template <int RG, int NT, bool POP = false, bool LN = false>
-__global__ __launch_bounds__(RNTH) void ddpg_rollout_kernel(DdpgArgs<POP, LN> G) {
+// CLK (the arguments then end with the clocks): an episode clock per actor, as in ppo_rollout -- tau, emit, slot, jslot
+// and done are the actor row's own, a closing transition's ring row comes from the call's row_off table.
+template <bool POP, bool LN, bool CLK>
+using DdpgKernelArgs = std::conditional_t<CLK, WithClk<DdpgArgs<POP, LN>>, DdpgArgs<POP, LN>>;
+template <int RG, int NT, bool POP = false, bool LN = false, bool CLK = false>
+__global__ __launch_bounds__(RNTH) void ddpg_rollout_kernel(DdpgKernelArgs<POP, LN, CLK> G) {
     constexpr int RB = 4 * RG;                       // actors per workgroup
+    const auto C = clk_of(G);
     extern __shared__ float sm[];
     const int tid = threadIdx.x, lane = tid & 63;
     const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -972,6 +1106,11 @@ __global__ __launch_bounds__(RNTH) void ddpg_rollout_kernel(DdpgArgs<POP, LN> G)
     if (head) {
         if (G.noise != SMX_DDPG_NOISE_NONE) sig = G.sigmas[ha];
         if (G.noise == SMX_DDPG_NOISE_OU) x = G.ou[ha * A + hj];
+    }
+    int* clk = nullptr;                              // (CLK) [RB][3]: clock, episode length, this step's row_off word
+    if constexpr (CLK) {
+        clk = (int*)(sm + C.off);
+        if (tid < E.nrows) clk_load(C, clk, tid, E.row0);
     }
     SMX_LDS_BARRIER();
 
@@ -1011,6 +1150,10 @@ __global__ __launch_bounds__(RNTH) void ddpg_rollout_kernel(DdpgArgs<POP, LN> G)
     for (int step = 0; step < G.steps; ++step) {
         float ev = 0.f;                              // this step's draw, requested before the layers
         if (noisy && head) ev = noise_pick(G.eps, ((size_t)step * G.n + ha) * A + hj, G.nstream, ha, step, hj);
+        int hoff = -1;                               // (CLK) the pair's row_off word, requested here for the same reason
+        if constexpr (CLK) {
+            if (head) hoff = C.row_off[(size_t)step * G.n + ha];
+        }
         bool measure = false;
         float clean = 0.f;
         if constexpr (POP) {
@@ -1042,37 +1185,70 @@ __global__ __launch_bounds__(RNTH) void ddpg_rollout_kernel(DdpgArgs<POP, LN> G)
         const bool emit = tau >= N - 1;
         const int slot = tau % N, jslot = (tau + 1) % N;   // (transition j = tau - N + 1 sits in slot j % N)
         const bool done = (tau + 1 >= G.episode_len);
+        // what the step takes from the clock, for actor row r: the shared values, or (CLK) formed from the row's own; a
+        // closing transition's ring row from `off`, the row_off word, which must lie in [0, rows) -- else nothing closes
+        struct Row { long long row; float* co; int tau, slot, jslot; bool emit, done; };
+        auto open_row = [&](long a, int off) {
+            float* co = G.cobs + (size_t)a * N * D;
+            if constexpr (CLK) {
+                const int r = (int)(a - E.row0), tr = clk[3 * r];
+                const bool closes = tr >= N - 1 && off >= 0 && off < C.rows;
+                return Row{closes ? clk_row(G.cursor, G.capacity, off) : 0, co, tr, tr % N, (tr + 1) % N, closes,
+                           tr + 1 >= clk[3 * r + 1]};
+            } else {
+                (void)off;
+                return Row{emit ? ring_row(G, kemit, a) : 0, co, tau, slot, jslot, emit, done};
+            }
+        };
         // ---- exploration: one (actor, action) pair per lane ------------------------------------------------------
         if (head) {
-            const float a = explore(outs[hr * RLDO + hj], G.noise, ev, sig, G.theta, G.dt, G.root_dt, tau, x);
-            s_act[hr * RMAX_A + hj] = a;
+            // (two bodies that differ only in where the clock's values come from: written on open_row alone, the
+            // shared-clock 8-actor kernel spills 36 bytes of scratch that it does not need with its own expressions)
             float* ca = G.cact + (size_t)ha * N * A + hj;
-            ca[(size_t)slot * A] = a;
-            if (emit) G.act[ring_row(G, kemit, ha) * A + hj] = ca[(size_t)jslot * A];
+            if constexpr (CLK) {
+                const Row p = open_row(ha, hoff);
+                const float a = explore(outs[hr * RLDO + hj], G.noise, ev, sig, G.theta, G.dt, G.root_dt, p.tau, x);
+                s_act[hr * RMAX_A + hj] = a;
+                ca[(size_t)p.slot * A] = a;
+                if (p.emit) G.act[p.row * A + hj] = ca[(size_t)p.jslot * A];
+                // (the row's word for the environment lanes, which read it behind the barrier below)
+                if (hj == 0) clk[3 * hr + 2] = hoff;
+            } else {
+                const float a = explore(outs[hr * RLDO + hj], G.noise, ev, sig, G.theta, G.dt, G.root_dt, tau, x);
+                s_act[hr * RMAX_A + hj] = a;
+                ca[(size_t)slot * A] = a;
+                if (emit) G.act[ring_row(G, kemit, ha) * A + hj] = ca[(size_t)jslot * A];
+            }
         }
         SMX_LDS_BARRIER();
         // ---- environment step (smx_synth_env_step_f32's expressions), n-step record, next x tile -------------------
-        struct Row { long long row; float* co; };
-        E.step(s_act, done,
-               [&](long a) { return Row{emit ? ring_row(G, kemit, a) : 0, G.cobs + (size_t)a * N * D}; },
+        E.template step<CLK>(s_act, done,
+               [&](long a) { return open_row(a, CLK ? clk[3 * (a - E.row0) + 2] : 0); },
                [&](long, const Row& p, int k, float s, float sn) {
-                   p.co[(size_t)slot * D + k] = s;
-                   if (emit) {
-                       G.obs[p.row * D + k] = p.co[(size_t)jslot * D + k];
+                   p.co[(size_t)p.slot * D + k] = s;
+                   if (p.emit) {
+                       G.obs[p.row * D + k] = p.co[(size_t)p.jslot * D + k];
                        G.obs_next[p.row * D + k] = sn;
                    }
                },
                [&](long a, const Row& p, float rew) {
                    float* cr = G.crew + (size_t)a * N;
-                   cr[slot] = rew;
-                   if (emit) {
-                       G.rew[p.row] = nstep_reward(cr, G.gpow, N, tau);
-                       G.done[p.row] = done ? 1.0f : 0.0f;
+                   cr[p.slot] = rew;
+                   if (p.emit) {
+                       G.rew[p.row] = nstep_reward(cr, G.gpow, N, p.tau);
+                       G.done[p.row] = p.done ? 1.0f : 0.0f;
                    }
                });
         if (emit) ++kemit;
         tau = done ? 0 : tau + 1;
         SMX_LDS_BARRIER();
+        if constexpr (CLK) {
+            // every reader of the step's clocks is behind the barrier above; the next ones follow a layer's barrier
+            if (tid < E.nrows) {
+                const int tr = clk[3 * tid];
+                clk[3 * tid] = (tr + 1 >= clk[3 * tid + 1]) ? 0 : tr + 1;
+            }
+        }
     }
     // ---- the states the actors and their noise processes are left in ------------------------------------------------
     E.store();
@@ -1479,6 +1655,13 @@ int carve_episodes(RollBase& G, int rb, int lds) {
     return G.off_ep * (int)sizeof(float) + rb * 12;
 }
 
+// With per-actor clocks the block's [rb][3] ints (ClkArgs) follow the layout of `lds` bytes -> the bytes with them
+constexpr int ROLL_CLK_LDS = 16 * 12;            // (what 16 actors add: launch()'s dynamic-LDS limit has it)
+int carve_clocks(ClkArgs& C, int rb, int lds) {
+    C.off = (lds + 3) / (int)sizeof(float);
+    return C.off * (int)sizeof(float) + rb * 12;
+}
+
 // ---- LSTM stem ---------------------------------------------------------------------------------------------------
 
 __host__ __device__ inline int lstm_dp(int D) { return (D + 3) & ~3; }
@@ -1541,13 +1724,20 @@ int pick_population_block(int forced, int n, int apa) {
 
 // one workgroup of RNTH lanes per rb actors, with LDS for one workgroup per CU; each kernel's dynamic-LDS limit is raised
 // at its first launch
+// (arguments that end with clocks, WithClk: their LDS follows the episodes')
+template <typename Args>
+constexpr bool has_clocks = false;
+template <typename Base>
+constexpr bool has_clocks<WithClk<Base>> = true;
+
 template <auto K, typename Args>
 int launch(const Args& G, int rb, int lds, smx_stream_t stream) {
     static const hipError_t attr = hipFuncSetAttribute((const void*)K, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                       ROLL_MAX_LDS + ROLL_EP_LDS);
+                                                       ROLL_MAX_LDS + ROLL_EP_LDS + (has_clocks<Args> ? ROLL_CLK_LDS : 0));
     (void)attr;
     Args A = G;
     lds = carve_episodes(A, rb, lds);
+    if constexpr (has_clocks<Args>) lds = carve_clocks(A.clk, rb, lds);
     if (lds < ROLL_EXCLUSIVE_LDS) lds = ROLL_EXCLUSIVE_LDS;
     hipLaunchKernelGGL(K, dim3((A.n + rb - 1) / rb), dim3(RNTH), lds, smx_s(stream), A);
     SMX_LAUNCH_CHECK();
@@ -1560,6 +1750,23 @@ int launch(const Args& G, int rb, int lds, smx_stream_t stream) {
     if (rb == 4) return launch<K4>(G, rb, lds, stream);
     if (rb == 8) return launch<K8>(G, rb, lds, stream);
     return launch<K16>(G, rb, lds, stream);
+}
+
+// a CLK kernel's arguments from its shared-clock twin's and the clocks
+template <typename Base>
+WithClk<Base> with_clocks(const Base& G, const ClkArgs& C) {
+    WithClk<Base> X;
+    static_cast<Base&>(X) = G;
+    X.clk = C;
+    return X;
+}
+
+// what both clocked entry points ask of the clocks -> the kernels' copy (its LDS offset: launch())
+int clock_args(const smx_actor_clocks* c, long long capacity, ClkArgs& C) {
+    SMX_REQUIRE(c && c->t && c->episode_len && c->row_off, SMX_E_NULL);
+    SMX_REQUIRE(c->rows >= 0 && c->rows <= capacity, SMX_E_SHAPE);
+    C.t = c->t; C.L = c->episode_len; C.row_off = c->row_off; C.rows = c->rows; C.off = 0;
+    return SMX_OK;
 }
 
 // the fields both DDPG entry points take from the argument block
@@ -1803,7 +2010,9 @@ extern "C" int32_t smx_synth_ppo_window_rollout_supported(int32_t D, int32_t H, 
     return smx_synth_lstm_rollout_supported(D, H, H1, H2, A);
 }
 
-extern "C" int smx_synth_ppo_window_rollout_f32(const smx_synth_ppo_window_rollout* args, smx_stream_t stream) {
+// both windowed entry points; clocks: null (the shared clock of base.roll) or the actors' own
+static int ppo_window_rollout(const smx_synth_ppo_window_rollout* args, const smx_actor_clocks* clocks, bool clocked,
+                              smx_stream_t stream) {
     SMX_REQUIRE(args, SMX_E_NULL);
     const smx_synth_lstm_rollout& b = args->base;
     const smx_synth_rollout_t* a = &b.roll;
@@ -1815,13 +2024,21 @@ extern "C" int smx_synth_ppo_window_rollout_f32(const smx_synth_ppo_window_rollo
     SMX_REQUIRE(!lstm || lstm_shape_ok(n, *b.lstm, b.hidden), SMX_E_SHAPE);
     SMX_REQUIRE(smx_synth_ppo_window_rollout_supported(lstm ? b.lstm->D : n.D, lstm ? b.lstm->H : 0, n.H1, n.H2, n.OUT),
                 SMX_E_UNSUPPORTED);
-    SMX_REQUIRE(a->n > 0 && a->steps > 0 && a->episode_len > 0 && a->t >= 0 && a->t < a->episode_len, SMX_E_SHAPE);
+    SMX_REQUIRE(a->n > 0 && a->steps > 0, SMX_E_SHAPE);
+    SMX_REQUIRE(clocked || (a->episode_len > 0 && a->t >= 0 && a->t < a->episode_len), SMX_E_SHAPE);
     SMX_REQUIRE(block_ok(a->actors_per_workgroup) && window_shape_ok(*args) && episode_shape_ok(a->mon), SMX_E_SHAPE);
     SMX_REQUIRE(noise_shape_ok(a->noise, a->n), SMX_E_SHAPE);
-    // two workgroups must never write the same FIFO row: all n m rows of the call are distinct
-    const long long m = closing_steps(a->t, a->steps, a->episode_len,
-                                      [&](int t) { return window_closes(t, args->n_step, args->advance); });
-    SMX_REQUIRE((long long)a->n * m <= args->capacity, SMX_E_SHAPE);
+    ClkArgs C = {};
+    if (clocked) {
+        // (the table numbers the call's closing pairs: rows <= capacity keeps them distinct)
+        const int rc = clock_args(clocks, args->capacity, C);
+        if (rc != SMX_OK) return rc;
+    } else {
+        // two workgroups must never write the same FIFO row: all n m rows of the call are distinct
+        const long long m = closing_steps(a->t, a->steps, a->episode_len,
+                                          [&](int t) { return window_closes(t, args->n_step, args->advance); });
+        SMX_REQUIRE((long long)a->n * m <= args->capacity, SMX_E_SHAPE);
+    }
     SMX_REQUIRE(aligned_ok(a->packed, n.b1, lstm ? b.lstm_packed : nullptr), SMX_E_ALIGN);
     const int rb = pick_block(a->actors_per_workgroup, a->n);
     if (!lstm) {
@@ -1830,6 +2047,9 @@ extern "C" int smx_synth_ppo_window_rollout_f32(const smx_synth_ppo_window_rollo
         roll_fields(a, n.D, G);
         G.W = win_fields(*args);
         const int lds = carve(G, rb, /*mma16=*/false, /*split_out=*/true, /*ztables=*/true, G.D);
+        if (clocked)
+            return launch<ppo_window_clk_kernel<1>, ppo_window_clk_kernel<2>, ppo_window_clk_kernel<4>>(
+                with_clocks(G, C), rb, lds, stream);
         return launch<ppo_window_kernel<1>, ppo_window_kernel<2>, ppo_window_kernel<4>>(G, rb, lds, stream);
     }
     LArgsW G;
@@ -1838,7 +2058,19 @@ extern "C" int smx_synth_ppo_window_rollout_f32(const smx_synth_ppo_window_rollo
     lstm_fields(b, G);
     G.W = win_fields(*args);
     const int lds = carve_lstm(G, rb);
+    if (clocked)
+        return launch<lstm_window_clk_kernel<1>, lstm_window_clk_kernel<2>, lstm_window_clk_kernel<4>>(
+            with_clocks(G, C), rb, lds, stream);
     return launch<lstm_window_kernel<1>, lstm_window_kernel<2>, lstm_window_kernel<4>>(G, rb, lds, stream);
+}
+
+extern "C" int smx_synth_ppo_window_rollout_f32(const smx_synth_ppo_window_rollout* args, smx_stream_t stream) {
+    return ppo_window_rollout(args, nullptr, false, stream);
+}
+
+extern "C" int smx_synth_ppo_window_rollout_clocks_f32(const smx_synth_ppo_window_rollout* args,
+                                                       const smx_actor_clocks* clocks, smx_stream_t stream) {
+    return ppo_window_rollout(args, clocks, true, stream);
 }
 
 extern "C" int32_t smx_synth_ddpg_rollout_supported(int32_t D, int32_t H1, int32_t H2, int32_t A, int32_t ln) {
@@ -1856,7 +2088,7 @@ extern "C" int32_t smx_synth_ddpg_population_block(int32_t n, int32_t actors_per
 }
 
 // what the persistent DDPG launch asks of the block and takes from it, whatever the actor
-static int persistent_ddpg_args(const smx_ddpg_rollout_t* a, DArgs& G) {
+static int persistent_ddpg_args(const smx_ddpg_rollout_t* a, DArgs& G, bool clocked) {
     SMX_REQUIRE(a && a->net && a->packed, SMX_E_NULL);
     const smx_mlp3_t& net = *a->net;
     SMX_REQUIRE(smx_synth_ddpg_rollout_supported(net.D, net.H1, net.H2, net.OUT, 0), SMX_E_UNSUPPORTED);
@@ -1865,9 +2097,11 @@ static int persistent_ddpg_args(const smx_ddpg_rollout_t* a, DArgs& G) {
     SMX_REQUIRE(aligned_ok(a->packed, net.b1, nullptr), SMX_E_ALIGN);
     const int rc = common_args(a, G);
     if (rc != SMX_OK) return rc;
-    // two workgroups must never write the same ring row: all n m rows of the call are distinct
-    const long long m = closing_steps(a->t, a->steps, a->episode_len, [&](int t) { return t >= a->n_step - 1; });
-    SMX_REQUIRE((long long)a->n * m <= a->capacity, SMX_E_SHAPE);
+    if (!clocked) {
+        // two workgroups must never write the same ring row: all n m rows of the call are distinct
+        const long long m = closing_steps(a->t, a->steps, a->episode_len, [&](int t) { return t >= a->n_step - 1; });
+        SMX_REQUIRE((long long)a->n * m <= a->capacity, SMX_E_SHAPE);
+    }
     net_fields(net, a->packed, G);
     return SMX_OK;
 }
@@ -1897,13 +2131,28 @@ static int ln_args(const smx_mlp3_t& net, const smx_ddpg_actor_variant& v, LnTai
     return SMX_OK;
 }
 
-// the launch for one of the four actors: the block's checks, then the population's, then the LayerNorm's
+// the launch for one of the four actors: the block's checks, then the population's, then the LayerNorm's; clocked: with
+// the actors' own clocks (checked behind the block: the table numbers the call's closing pairs, rows <= capacity
+// keeps them distinct), the block's t / episode_len ignored
 template <bool POP, bool LN>
-static int ddpg_rollout(const smx_ddpg_rollout_t* a, const smx_ddpg_actor_variant& v, smx_stream_t stream) {
+static int ddpg_rollout_launch(const smx_ddpg_rollout_t* a, const smx_ddpg_actor_variant& v, const smx_actor_clocks* clocks,
+                               bool clocked, smx_stream_t stream) {
     DdpgArgs<POP, LN> G;
     memset(&G, 0, sizeof(G));
-    int rc = persistent_ddpg_args(a, G);
+    smx_ddpg_rollout_t own;
+    if (clocked && a) {
+        own = *a;
+        own.t = 0;
+        own.episode_len = 1;
+        a = &own;
+    }
+    int rc = persistent_ddpg_args(a, G, clocked);
     if (rc != SMX_OK) return rc;
+    ClkArgs C = {};
+    if (clocked) {
+        rc = clock_args(clocks, a->capacity, C);
+        if (rc != SMX_OK) return rc;
+    }
     const smx_mlp3_t& net = *a->net;
     int rb = POP ? 0 : pick_block(a->actors_per_workgroup, a->n);
     if constexpr (POP) {
@@ -1927,16 +2176,33 @@ static int ddpg_rollout(const smx_ddpg_rollout_t* a, const smx_ddpg_actor_varian
         net_fields(copy0, v.packed_pop, G.popnet);
     }
     if constexpr (LN) lds = carve_ln(G, G.ln, lds);
+    if (clocked)
+        return launch<ddpg_rollout_kernel<1, 3, POP, LN, true>, ddpg_rollout_kernel<2, 3, POP, LN, true>,
+                      ddpg_rollout_kernel<4, 2, POP, LN, true>>(with_clocks(G, C), rb, lds, stream);
     return launch<ddpg_rollout_kernel<1, 3, POP, LN>, ddpg_rollout_kernel<2, 3, POP, LN>,
                   ddpg_rollout_kernel<4, 2, POP, LN>>(G, rb, lds, stream);
 }
 
-extern "C" int smx_synth_ddpg_rollout_f32(const smx_ddpg_rollout_t* a, const struct smx_ddpg_actor_variant* variant,
-                                          smx_stream_t stream) {
+// both DDPG entry points: the actor variant picks the instantiation
+static int ddpg_rollout_variant(const smx_ddpg_rollout_t* a, const smx_ddpg_actor_variant* variant,
+                                const smx_actor_clocks* clocks, bool clocked, smx_stream_t stream) {
     static const smx_ddpg_actor_variant plain = {};
     const smx_ddpg_actor_variant& v = variant ? *variant : plain;
-    if (v.packed_pop) return v.ln ? ddpg_rollout<true, true>(a, v, stream) : ddpg_rollout<true, false>(a, v, stream);
-    return v.ln ? ddpg_rollout<false, true>(a, v, stream) : ddpg_rollout<false, false>(a, v, stream);
+    if (v.packed_pop)
+        return v.ln ? ddpg_rollout_launch<true, true>(a, v, clocks, clocked, stream)
+                    : ddpg_rollout_launch<true, false>(a, v, clocks, clocked, stream);
+    return v.ln ? ddpg_rollout_launch<false, true>(a, v, clocks, clocked, stream)
+                : ddpg_rollout_launch<false, false>(a, v, clocks, clocked, stream);
+}
+
+extern "C" int smx_synth_ddpg_rollout_f32(const smx_ddpg_rollout_t* a, const struct smx_ddpg_actor_variant* variant,
+                                          smx_stream_t stream) {
+    return ddpg_rollout_variant(a, variant, nullptr, false, stream);
+}
+
+extern "C" int smx_synth_ddpg_rollout_clocks_f32(const smx_ddpg_rollout_t* a, const struct smx_ddpg_actor_variant* variant,
+                                                 const struct smx_actor_clocks* clocks, smx_stream_t stream) {
+    return ddpg_rollout_variant(a, variant, clocks, true, stream);
 }
 
 extern "C" int smx_synth_ddpg_step_f32(const smx_ddpg_rollout_t* a, const float* mu, int64_t ld_mu, smx_stream_t stream) {

@@ -26,6 +26,7 @@ import torch
 
 from surreal_amd import kernels as KN
 from surreal_amd import _lib as L
+from . import actor_clocks as AC
 from .base import Env
 
 
@@ -92,17 +93,29 @@ class SyntheticVecEnv(object):
         """pixel = (C, H, W): every actor also has a camera (SyntheticEnv's frame: a pattern shifted by the step
         count and the first state component), rendered on the device; frame_stacks = n: the policy observes the
         last n frames on the channel axis (FrameStackWrapper's rule, surreal/env/wrapper.py:407-472) -- the rollout
-        stores ONE raw uint8 frame per step and the stacking is a gather (smx_frame_stack_u8)."""
+        stores ONE raw uint8 frame per step and the stacking is a gather (smx_frame_stack_u8).
+        episode_len: an int -- all actors share one episode clock -- or a sequence of n ints (also when they are all
+        equal): every actor has an episode length and a clock of its own (per_actor_clocks; env/actor_clocks.py), which
+        the one-launch low-dimensional ppo_rollout_into / ddpg_rollout_into take and every other stepping call refuses."""
         self.K = kernels or KN.default_kernels()
         self.device = device or KN.default_device()
-        self.n, self.D, self.A, self.episode_len = n_actors, obs_dim, action_dim, episode_len
+        self.n, self.D, self.A = n_actors, obs_dim, action_dim
+        self.per_actor_clocks = not isinstance(episode_len, (int, np.integer))
+        if self.per_actor_clocks:
+            lens = np.asarray(list(episode_len))
+            if lens.shape != (n_actors,) or lens.dtype.kind not in 'iu' or (lens < 1).any() or (lens >= 2 ** 31).any():
+                raise ValueError('SyntheticVecEnv: episode_len must be an int or %d ints >= 1, got %r'
+                                 % (n_actors, episode_len))
+            episode_len = np.ascontiguousarray(lens, dtype=np.int32)
+            self._clk = {}            # the device copies: 'L', 't' int32 [n], the [T, n] row tables by T
+        self.episode_len = episode_len
         self.pixel = tuple(pixel) if pixel is not None else None
         self.frame_stacks = int(frame_stacks) if pixel is not None else 1
         seeds = list(range(n_actors)) if seeds is None else list(seeds)
         init = np.stack([np.random.RandomState(s).randn(obs_dim).astype(np.float32) for s in seeds])
         self.init_state = torch.as_tensor(init).to(self.device)
         self.state = self.init_state.clone()
-        self.t = 0
+        self.t = self._clock_zero()
         self.rolls = None
         self.persistent = True        # rollout(): the one-launch kernel where the policy's shapes allow it
         self._ddpg = {}               # ddpg_rollout_into(): the open n-step transitions and OU states of the actors
@@ -110,6 +123,57 @@ class SyntheticVecEnv(object):
         self.monitor = None           # attach_monitor(): the actors' episode returns, kept by the step launches
         self.noise = None             # attach_noise(): the exploration noise as a per-actor stream, drawn by the launches
         self.param_noise = None       # attach_param_noise(): per-agent parameter-space noise for ddpg_rollout_into
+
+    def _clock_zero(self):
+        """the clock(s) right after a reset: an int, or with per-actor clocks int32 [n]"""
+        return np.zeros(self.n, dtype=np.int32) if self.per_actor_clocks else 0
+
+    @property
+    def clocks(self):
+        """every actor's step within its episode, np.int32 [n] (a copy)"""
+        return np.array(np.broadcast_to(self.t, (self.n,)), dtype=np.int32)
+
+    @property
+    def episode_lens(self):
+        """every actor's episode length, np.int32 [n] (a copy)"""
+        return np.array(np.broadcast_to(self.episode_len, (self.n,)), dtype=np.int32)
+
+    def _shared_clock_only(self, who):
+        """`who` steps all actors on one clock: refused on an env whose actors have their own"""
+        if self.per_actor_clocks:
+            raise NotImplementedError('%s: per-actor episode clocks: the one-launch low-dimensional ppo_rollout_into / '
+                                      'ddpg_rollout_into only' % who)
+
+    def _clock_args(self, T, n_step, advance, rows):
+        """the `clocks` keyword of a per-actor launch over the next T steps: the clocks as they are now and the episode
+        lengths on the device, and the call's row table (one launch, K.actor_clock_rows; the buffers are reused: L once,
+        t and the [T, n] table per call).  The clocks go up without a synchronisation, as the recorders' steps do
+        (device_recorder._StagingSet): through one of two pinned host buffers, copied asynchronously on the stream; an
+        event says when a buffer's copy has read it, and is waited for only before that buffer is written again, two
+        calls later"""
+        c, dev = self._clk, self.device
+        if 'L' not in c:
+            cuda = torch.device(dev).type == 'cuda'
+            c['L'] = torch.from_numpy(self.episode_len).to(dev)
+            c['t'] = torch.zeros(self.n, dtype=torch.int32, device=dev)
+            c['stage'] = [[torch.zeros(self.n, dtype=torch.int32, pin_memory=cuda),
+                           torch.cuda.Event() if cuda else None, False] for _ in range(2)]
+            c['turn'] = 0
+        if T not in c:
+            c[T] = torch.empty(T, self.n, dtype=torch.int32, device=dev)
+        stage = c['stage'][c['turn']]
+        c['turn'] = 1 - c['turn']
+        host, event, in_flight = stage
+        if in_flight and event is not None:
+            event.synchronize()                  # (the copy of two calls ago: long done)
+        t_host = host.numpy()
+        t_host[:] = self.t
+        c['t'].copy_(host, non_blocking=True)
+        if event is not None:
+            event.record()
+        stage[2] = True
+        self.K.actor_clock_rows(c['t'], c['L'], T, n_step, advance, c[T], t_host=t_host, episode_len_host=self.episode_len)
+        return {'clocks': dict(t=c['t'], episode_len=c['L'], row_off=c[T], rows=rows)}
 
     def attach_monitor(self, capacity=16):
         """-> a DeviceEpisodeMonitor (env/monitor.py) that every stepping launch from now on feeds: per actor the open
@@ -182,7 +246,7 @@ class SyntheticVecEnv(object):
 
     def reset(self):
         self.state.copy_(self.init_state)
-        self.t = 0
+        self.t = self._clock_zero()
         if self.monitor is not None:
             self.monitor.clear_open()         # (EpisodeMonitor._reset: an unfinished episode is dropped)
         for k in ('carry_obs', 'carry_act', 'carry_rew', 'ou', 'hist'):
@@ -284,6 +348,7 @@ class SyntheticVecEnv(object):
         row unused) so that one env-step launch records all fields.  A rollout is one episode
         segment: it starts right after a reset and T <= episode_len, so `done` can only be set
         on the last recorded step and windows never straddle an episode boundary."""
+        self._shared_clock_only('start_rollout')
         assert self.t == 0 and T <= self.episode_len, 'rollouts start at an episode boundary'
         f = lambda *s: torch.zeros(*s, device=self.device, dtype=torch.float32)  # noqa: E731
         self.T = T
@@ -311,6 +376,7 @@ class SyntheticVecEnv(object):
 
     def step(self, actions, pds=None):
         """actions [n, A] on the device -> next observation [n, D] (the state tensor)"""
+        self._shared_clock_only('step')
         r = self.rolls
         if r is not None and self.slot < self.T:
             self.K.synth_env_step(self.state, self.init_state, actions, self.t, self.episode_len,
@@ -340,6 +406,7 @@ class SyntheticVecEnv(object):
         eps: [T, n, A] standard-normal draws (default: drawn here in one launch; None-eps agents in
         a deterministic mode ignore it).  actors_per_workgroup: 4 | 8 | 16 forces the one-launch kernel's block (0:
         automatic; 4 and 8 give the same bits, 16 sums the layers in another order)."""
+        self._shared_clock_only('rollout')
         T, n, K = self.T, self.n, self.K
         assert self.slot == 0 and 'pds' in self.rolls, 'start_rollout(T, info_width=2 * A) first'
         eps, ns = self._draws(agent, eps, T)
@@ -440,6 +507,7 @@ class SyntheticVecEnv(object):
         learner will read them.  Starts at an episode boundary (reset() first), like start_rollout().  An LSTM-stem
         policy (window_shapes(T, agent)) also gets `out['cells']` [n, 2, 1, Hl]: the state at the window's first step.
         actors_per_workgroup: as in rollout()."""
+        self._shared_clock_only('rollout_into')
         K, n = self.K, self.n
         T = out['obs'].shape[1]
         assert self.t == 0 and T <= self.episode_len and self.can_rollout_into(agent)
@@ -465,6 +533,9 @@ class SyntheticVecEnv(object):
         refusal = self._camera_refusal('ppo_rollout_into', agent, bool(m.if_pixel))
         if refusal is not None:
             return refusal
+        if m.if_pixel and self.per_actor_clocks:
+            return NotImplementedError, ('ppo_rollout_into with a camera: per-actor episode clocks: the one-launch '
+                                         'low-dimensional ppo_rollout_into / ddpg_rollout_into only')
         if agent.rnn_config.if_rnn_policy and agent.rnn_config.rnn_layer != 1:
             return NotImplementedError, ('ppo_rollout_into: rnn_layer %d; the windowed rollout runs one LSTM layer'
                                          % agent.rnn_config.rnn_layer)
@@ -504,7 +575,11 @@ class SyntheticVecEnv(object):
         the stacked frames (PPOModel.perception_into), one LSTM step, the actor, and ONE launch
         (smx_synth_ppo_pixel_window_step) that samples, steps, keeps the carry rings and a history of n_step + S raw
         frames per actor, and writes the closing windows with their uint8 'pixel' [n_step, S*C, H, W] / 'pixel_next'
-        [1, S*C, H, W] into the ring.  The history carries from call to call like the open windows."""
+        [1, S*C, H, W] into the ring.  The history carries from call to call like the open windows.
+        With per-actor episode clocks (low-dimensional only): TWO launches -- the call's row table from the clocks
+        (smx_actor_clock_rows_i32), then smx_synth_ppo_window_rollout_clocks_f32; every actor's windows follow its own
+        clock and go to the ring in the order n host wrappers stepped in actor order insert them (step by step, actor by
+        actor).  The count and the clocks after the call are formed here (env/actor_clocks.py): nothing is read back."""
         refusal = self._ppo_window_refusal(agent)
         if refusal is not None:
             raise refusal[0](refusal[1])
@@ -520,21 +595,28 @@ class SyntheticVecEnv(object):
         camera = bool(m.if_pixel)
         c = self._ppo
         key = (N, adv, D, A, Hl) + ((self.pixel, self.frame_stacks) if camera else ())
-        if c.get('key') != key or c.get('t') != self.t:
-            if self.t != 0:
-                raise ValueError('ppo_rollout_into: the open windows of clock %d are not held (the environments were '
+        if c.get('key') != key or c.get('t') is None or not np.array_equal(c['t'], self.t):
+            if np.any(self.t != 0):
+                raise ValueError('ppo_rollout_into: the open windows of clock %s are not held (the environments were '
                                  'stepped outside ppo_rollout_into, or n_step / stride changed); reset() first' % self.t)
             f = lambda *s: torch.zeros(*s, device=self.device)  # noqa: E731
             c.clear()
             c.update(key=key, carry={'obs': f(n, N, D), 'actions': f(n, N, A), 'rewards': f(n, N), 'pds': f(n, N, 2 * A)})
             if rnn:
                 c['carry']['cells'] = f(n, -(-N // adv), 2, Hl)
-        # the closing steps of this call (the clock is shared by all actors): n windows each
-        closing, t = self._closing_steps(T, lambda t: t + 1 - N >= 0 and (t + 1 - N) % adv == 0)
-        rows = n * closing
-        if rows > replay.memory_size + 3:
-            raise ValueError('ppo_rollout_into: %d actors x %d closing steps = %d windows exceed the FIFO capacity %d '
-                             '(two of them would share a row)' % (n, closing, rows, replay.memory_size + 3))
+        if self.per_actor_clocks:
+            # every actor closes its own windows: their number and the clocks after the call in closed form
+            rows, t = int(AC.closings(self.t, self.episode_len, T, N, adv).sum()), AC.after(self.t, self.episode_len, T)
+            if rows > replay.memory_size + 3:
+                raise ValueError('ppo_rollout_into: the %d windows %d actors close in %d steps exceed the FIFO capacity '
+                                 '%d (two of them would share a row)' % (rows, n, T, replay.memory_size + 3))
+        else:
+            # the closing steps of this call (the clock is shared by all actors): n windows each
+            closing, t = self._closing_steps(T, lambda t: t + 1 - N >= 0 and (t + 1 - N) % adv == 0)
+            rows = n * closing
+            if rows > replay.memory_size + 3:
+                raise ValueError('ppo_rollout_into: %d actors x %d closing steps = %d windows exceed the FIFO capacity '
+                                 '%d (two of them would share a row)' % (n, closing, rows, replay.memory_size + 3))
         shapes = {'obs': (N, D), 'obs_next': (1, D), 'actions': (N, A), 'rewards': (N,), 'dones': (N,),
                   'pds': (N, 2 * A)}
         if rnn:
@@ -564,9 +646,12 @@ class SyntheticVecEnv(object):
             cells = self._cell_outputs(Hl)
             if held is not None and held[0].shape[1] == n:
                 cells.update(h0=held[0].contiguous(), c0=held[1].contiguous())
-        K.synth_ppo_window_rollout(m, pk, lpk, self.state, self.init_state, noise, eps, self.t, self.episode_len, T, N,
+        clk, clock = {}, (self.t, self.episode_len)
+        if self.per_actor_clocks:
+            clk, clock = self._clock_args(T, N, adv, rows), (0, 1)       # (the shared clock's arguments are ignored)
+        K.synth_ppo_window_rollout(m, pk, lpk, self.state, self.init_state, noise, eps, clock[0], clock[1], T, N,
                                    adv, c['carry'], tables, cursor, zf, actors_per_workgroup=actors_per_workgroup, **cells,
-                                   **self._mon(T), **self._noi(T, ns))
+                                   **self._mon(T), **self._noi(T, ns), **clk)
         if rnn:
             self._hand_cells(agent, cells)
         replay.commit_ring(rows)
@@ -668,11 +753,12 @@ class SyntheticVecEnv(object):
                           "on the host; use 'normal' parameter noise, none, or attach_param_noise")
         if camera and reference:
             return refuse(ValueError, 'reference=True has no camera path (no two-launch reference there)')
-        if camera:
-            return 'camera', None
-        if supported and not reference:
-            return 'launch', None
-        return ('two_launch' if reference and not ln else 'steps'), None
+        route = 'camera' if camera else 'launch' if supported and not reference else \
+            'two_launch' if reference and not ln else 'steps'
+        if self.per_actor_clocks and route != 'launch':
+            return refuse(NotImplementedError, "the '%s' route: per-actor episode clocks: the one-launch "
+                          'low-dimensional ppo_rollout_into / ddpg_rollout_into only' % route)
+        return route, None
 
     def ddpg_rollout_into(self, agent, replay, T, eps=None, sigmas=None, actors_per_workgroup=0, reference=False):
         """T steps of all actors under DDPGAgent `agent` (act: actor -> clip -> exploration noise -> clip,
@@ -694,7 +780,9 @@ class SyntheticVecEnv(object):
         stacked frames, the actor, and ONE launch (smx_synth_ddpg_pixel_step) that also renders the step's frame into
         a history of n_step + S raw frames per actor, writes the closing transitions' uint8 'pixel' / 'pixel_next'
         [S*C, H, W] into the ring and the stacked observation of the next step.  The history carries from call to call
-        like the open transitions."""
+        like the open transitions.
+        With per-actor episode clocks (the ONE-launch route only): the call's row table from the clocks
+        (smx_actor_clock_rows_i32), then smx_synth_ddpg_rollout_clocks_f32 -- as in ppo_rollout_into."""
         route, refusal = self._ddpg_route(agent, reference)
         if refusal is not None:
             raise refusal[0](refusal[1])
@@ -706,12 +794,20 @@ class SyntheticVecEnv(object):
             dtypes = {'pixel': torch.uint8, 'pixel_next': torch.uint8}
         algo = agent.learner_config.algo
         N, gamma = int(algo.n_step), algo.gamma
-        # the closing steps of this call (the clock is shared by all actors): n of them per closing step
-        m, t = self._closing_steps(T, lambda t: t >= N - 1)
-        rows = n * m
-        if rows > replay.memory_size:
-            raise ValueError('ddpg_rollout_into: %d actors x %d closing steps = %d transitions exceed the replay '
-                             'capacity %d (two of them would share a row)' % (n, m, rows, replay.memory_size))
+        T = int(T)
+        if self.per_actor_clocks:
+            # every actor closes its own transitions: their number and the clocks after the call in closed form
+            rows, t = int(AC.closings(self.t, self.episode_len, T, N, 1).sum()), AC.after(self.t, self.episode_len, T)
+            if rows > replay.memory_size:
+                raise ValueError('ddpg_rollout_into: the %d transitions %d actors close in %d steps exceed the replay '
+                                 'capacity %d (two of them would share a row)' % (rows, n, T, replay.memory_size))
+        else:
+            # the closing steps of this call (the clock is shared by all actors): n of them per closing step
+            m, t = self._closing_steps(T, lambda t: t >= N - 1)
+            rows = n * m
+            if rows > replay.memory_size:
+                raise ValueError('ddpg_rollout_into: %d actors x %d closing steps = %d transitions exceed the replay '
+                                 'capacity %d (two of them would share a row)' % (n, m, rows, replay.memory_size))
         tables, cursor, cap = replay.reserve_ring(rows, shapes, dtypes)
         d = self._ddpg
         if d.get('n_step') != N:
@@ -731,7 +827,8 @@ class SyntheticVecEnv(object):
             assert eps is None or tuple(eps.shape) == (T, n, A)
             assert sigmas.dtype == torch.float64 and sigmas.numel() == n
             sigmas = sigmas.contiguous()
-        r = dict(state=self.state, init_state=self.init_state, t=self.t, episode_len=self.episode_len, n_step=N,
+        shared = (0, 1) if self.per_actor_clocks else (self.t, self.episode_len)       # (ignored with per-actor clocks)
+        r = dict(state=self.state, init_state=self.init_state, t=shared[0], episode_len=shared[1], n_step=N,
                  noise_type=noise, eps=eps, sigmas=None if deterministic else sigmas,
                  theta=agent.theta, dt=agent.dt, root_dt=float(np.sqrt(agent.dt)), gpow=d['gpow'], ou=d['ou'],
                  carry_obs=d['carry_obs'], carry_act=d['carry_act'], carry_rew=d['carry_rew'], tables=tables,
@@ -747,6 +844,8 @@ class SyntheticVecEnv(object):
             variant = dict(ln=model.actor_ln_flat, ln_eps=model.ln_eps) if model.use_layernorm else {}    # (plain: none)
             if pn is not None:
                 variant.update(pn=pn, measure_step=pn.measure_step(T))
+            if self.per_actor_clocks:
+                variant.update(self._clock_args(T, N, 1, rows))
             K.synth_ddpg_rollout(actor, d['pk'], r, T, actors_per_workgroup, **variant, **self._mon(T),
                                  **self._noi(T, ns))
             if pn is not None:
@@ -823,6 +922,7 @@ class SyntheticVecEnv(object):
         """the same rollout with TWO launches per step out of the kernels the persistent one is built from: the
         row-block forward (smx_epoch_forward_f32: the means) and the head + step launch.  Bit-identical to
         ``rollout`` on the persistent kernel -- the parity test's reference; not used by the product loop."""
+        self._shared_clock_only('rollout_reference')
         T, n, K = self.T, self.n, self.K
         actor = agent.model.actor
         noise = agent.batch_noise(n).view(-1)
@@ -865,6 +965,7 @@ class SyntheticVecEnv(object):
         same index arithmetic as the host wrapper (env/exp_sender_wrapper.py): window w = steps
         [w * advance, w * advance + n_step), W = windows_per_episode(T, n_step, stride) per actor"""
         from surreal_amd.env.exp_sender_wrapper import window_advance, windows_per_episode
+        self._shared_clock_only('emit_windows')
         T = self.T
         assert self.slot == T, 'rollout not complete'
         W = windows_per_episode(T, n_step, stride)

@@ -828,14 +828,16 @@ class HipKernels(object):
     def synth_ppo_window_rollout(self, model, packed, lstm_packed, state, init_state, noise_scale, eps, t, episode_len,
                                  steps, n_step, advance, carry, tables, cursor, zfilter, hN=None, cN=None, h0=None,
                                  c0=None, h_before=None, c_before=None, actors_per_workgroup=0, monitor=None,
-                                 noise=None):
+                                 noise=None, clocks=None):
         """`steps` steps of synth_rollout (model.rnn None) / synth_lstm_rollout recorded as moving windows of n_step
         steps, `advance` apart, straight into a FIFO ring, ONE launch (smx_synth_ppo_window_rollout_f32).
         carry: the open windows {'obs' [n, n_step, D], 'actions' [n, n_step, A], 'rewards' [n, n_step], 'pds'
         [n, n_step, 2A], 'cells' [n, ceil(n_step / advance), 2, Hl] (LSTM)}; tables: the ring by replay field name
         ('obs' [capacity, n_step * D], 'obs_next', 'actions', 'rewards', 'dones', 'pds', 'cells' (LSTM)); the k-th
         closing step writes actor a to row (cursor + k n + a) % capacity.  h0 / c0 (None: zeros), hN / cN (LSTM),
-        h_before / c_before: [n, Hl] contiguous, Hl = model.rnn_hidden_logical"""
+        h_before / c_before: [n, Hl] contiguous, Hl = model.rnn_hidden_logical.
+        clocks: an episode clock per actor (_clock_args; smx_synth_ppo_window_rollout_clocks_f32) -- t / episode_len
+        are then ignored and the closing windows go to the rows of clocks['row_off'] (actor_clock_rows)"""
         p = L.SynthPpoWindowRollout()
         self._roll_args(p.base.roll, model.actor, packed, L.SMX_ACT_TANH, state, init_state, model.log_var, noise_scale,
                         eps, t, episode_len, steps, zfilter, actors_per_workgroup, monitor=monitor, noise=noise)
@@ -844,7 +846,42 @@ class HipKernels(object):
         for k, x in list(carry.items()) + list(tables.items()):
             assert x.is_contiguous() and x.dtype == torch.float32, k
         self._window_args(p, n_step, advance, carry, tables, cursor)
+        if clocks is not None:
+            c = self._clock_args(clocks, state.shape[0], steps)
+            L.call('smx_synth_ppo_window_rollout_clocks_f32', ctypes.byref(p), ctypes.byref(c), self._st())
+            return
         L.call('smx_synth_ppo_window_rollout_f32', ctypes.byref(p), self._st())
+
+    def actor_clock_rows(self, t, episode_len, steps, n_step, advance, row_off, t_host=None, episode_len_host=None):
+        """row_off [steps, n] int32 <- where every closing (step, actor) pair of a call of `steps` steps goes, counted
+        from the ring's cursor in (step, actor) order, -1 where the pair closes nothing (smx_actor_clock_rows_i32): actor
+        a starts at clock t[a] of episodes of episode_len[a] steps (int32 [n] on the device) and closes a record at
+        clock tau iff j = tau + 1 - n_step >= 0 and j % advance == 0 (DDPG: advance 1).  t_host / episode_len_host: the
+        numpy int32 arrays they were copied from, checked before the launch"""
+        n = t.numel()
+        for x in (t, episode_len, row_off):
+            assert x.dtype == torch.int32 and x.is_contiguous()
+        assert episode_len.numel() == n and tuple(row_off.shape) == (steps, n)
+        p = L.ActorClockRows()
+        p.n, p.steps, p.n_step, p.advance = n, int(steps), int(n_step), int(advance)
+        p.t, p.episode_len, p.row_off = L.ptr(t), L.ptr(episode_len), L.ptr(row_off)
+        for name, h in (('t_host', t_host), ('episode_len_host', episode_len_host)):
+            if h is not None:
+                assert h.dtype == np.int32 and h.flags['C_CONTIGUOUS'] and h.size == n
+                setattr(p, name, h.ctypes.data)
+        L.call('smx_actor_clock_rows_i32', ctypes.byref(p), self._st())
+
+    @staticmethod
+    def _clock_args(clocks, n, steps):
+        """struct smx_actor_clocks from {'t', 'episode_len' int32 [n], 'row_off' int32 [steps, n], 'rows'}"""
+        c = L.ActorClocks()
+        for k in ('t', 'episode_len', 'row_off'):
+            assert clocks[k].dtype == torch.int32 and clocks[k].is_contiguous(), k
+        assert clocks['t'].numel() == n == clocks['episode_len'].numel()
+        assert tuple(clocks['row_off'].shape) == (steps, n)
+        c.t, c.episode_len, c.row_off = L.ptr(clocks['t']), L.ptr(clocks['episode_len']), L.ptr(clocks['row_off'])
+        c.rows = int(clocks['rows'])
+        return c
 
     # a LayerNorm actor runs in the one-launch DDPG rollout and under the parameter noise (ddpg_ln_launch(), above)
     ddpg_ln_launch = True
@@ -901,14 +938,16 @@ class HipKernels(object):
         return L.ptr(pn.pop), pn.pop.shape[1], L.ptr(pn.dist)
 
     def synth_ddpg_rollout(self, net, packed, r, steps, actors_per_workgroup=0, monitor=None, noise=None, ln=None,
-                           ln_eps=0.0, pn=None, measure_step=-1):
+                           ln_eps=0.0, pn=None, measure_step=-1, clocks=None):
         """`steps` DDPG acting + environment steps of all actors with their n-step transitions written into the ring
         tables, ONE launch (smx_synth_ddpg_rollout_f32, csrc/smx_rollout.hip).  packed: epoch_pack of the actor `net`;
         r: see _ddpg_args (eps [steps, n, A]).
         ln, ln_eps: a LayerNorm (gains and biases, eps) behind each hidden ReLU of `net`.
         pn: every agent of `pn` (pn.actors_per_agent consecutive actors) acts from its own copy in pn.pop
         (param_noise_refresh's, for the same ln); net / packed / ln are the clean actor, evaluated at step measure_step
-        (-1: never) for pn.dist"""
+        (-1: never) for pn.dist.
+        clocks: an episode clock per actor (_clock_args; smx_synth_ddpg_rollout_clocks_f32) -- r['t'] / r['episode_len']
+        are then ignored and the closing transitions go to the rows of clocks['row_off'] (actor_clock_rows, advance 1)"""
         if r['eps'] is not None:
             assert r['eps'].is_contiguous() and tuple(r['eps'].shape) == (steps, r['state'].shape[0], net.OUT)
         p = self._ddpg_args(r, steps, net, packed, actors_per_workgroup, monitor, noise)
@@ -917,6 +956,10 @@ class HipKernels(object):
         if pn is not None:
             v.packed_pop, v.packed_stride, v.dist = self._population_ptrs(pn)
             v.actors_per_agent, v.agents, v.measure_step = int(pn.actors_per_agent), int(pn.agents), int(measure_step)
+        if clocks is not None:
+            c = self._clock_args(clocks, r['state'].shape[0], steps)
+            L.call('smx_synth_ddpg_rollout_clocks_f32', ctypes.byref(p), ctypes.byref(v), ctypes.byref(c), self._st())
+            return
         L.call('smx_synth_ddpg_rollout_f32', ctypes.byref(p), ctypes.byref(v), self._st())
 
     def synth_ddpg_population_block(self, n, actors_per_agent, forced=0):
