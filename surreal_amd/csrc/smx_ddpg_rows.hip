@@ -18,7 +18,7 @@
 //
 //   ddpg_rows4_kernel<2>      target actor -> both target critics (the second at the noised, clamped action);  y = min of
 //                             the two Bellman targets;  each critic's Q(s, a), dLoss/dQ against that y and data gradients;
-//                             the actor's forward pass (20 layers; td3_critic_program)
+//                             the actor's forward pass (20 layers; td3_critic_chain)
 //   ddpg_rows_wgrad_update    critic 1;  ddpg_rows_wgrad_update  critic 2 (its blocks live in a packed buffer of their own)
 //   ddpg_rows4_kernel<1>      unchanged: the actor goes through critic 1 only
 //   ddpg_rows_wgrad_update    the actor;  [statistics: a second block for (q2, y) by the same workgroup]
@@ -37,7 +37,7 @@
 // The gains and biases are read row-major from the parameter buffers, as the dense biases are: no packed copy.
 //
 // use_layernorm together with TD3 is the composition, TD3's five launches (ddpg_rows4_ln_kernel<2>: the chain body with
-// PHASE == 2 and LN; td3_critic_program_ln: the 20 products, a forward rule behind each of the 12 hidden layers, a backward
+// PHASE == 2 and LN; td3_critic_chain: the 20 products, a forward rule behind each of the 12 hidden layers, a backward
 // rule behind each critic's loss and behind each critic's W2^T product -- 16 rules; only that instantiation takes the
 // 20-step rule table, LnProgT<20>):
 //
@@ -183,14 +183,17 @@ struct LnStep {
     int d_off, ldd;
     int st;
 };
-template <int N>
-struct LnProgT {
-    LnStep s[N];
+struct LnTail {                                       // what a chain's rules share, behind either table
     float eps;
     float* dn2;                                       // critic chain: d/d(LayerNorm 2's output) [rows][c2]
     const float *a1, *a2, *am1, *ar1, *am2, *ar2;     // actor chain: the actor's pre-LayerNorm rows and statistics
     int oP1, ldP1, oP2, ldP2, oD, ldD, oM;            // LDS (float offsets): two pre-LayerNorm tiles, dn, statistics [4][2][4]
     float* dn2_2;                                     // TD3's critic chain: the same for the second critic (else null)
+};
+template <int N>
+struct LnProgT {
+    LnStep s[N];
+    LnTail t;
 };
 typedef LnProgT<LN_STEPS_TD3> LnProg;                 // what the host fills; the 13-step launches take its narrow() copy
 static_assert(sizeof(RArgs) + sizeof(Prog) + sizeof(LnProg) < 4096, "all go by value in the kernel arguments");
@@ -420,8 +423,8 @@ __device__ __forceinline__ void ddpg_rows4_chain(const RArgs& G, const Prog& P, 
             // Linear -> ReLU -> LayerNorm: the rows the layer has just finished, normalised from the pre-LayerNorm tile
             const LnStep& T = ln_late(Q, si);
             if (T.kind == LN_FWD) {
-                const LnEmitRows emit = {T.n, T.ldn, T.mean, T.rstd, sm + Q->oM + 2 * RB * T.st, row0, nrows, lane};
-                ln_rows<RB, DNWV, LNR_MAXC>(sm + T.p_off, T.ldp, sm + T.t_off, T.ldt, T.F, T.gamma, T.beta, Q->eps, wv, lane,
+                const LnEmitRows emit = {T.n, T.ldn, T.mean, T.rstd, sm + Q->t.oM + 2 * RB * T.st, row0, nrows, lane};
+                ln_rows<RB, DNWV, LNR_MAXC>(sm + T.p_off, T.ldp, sm + T.t_off, T.ldt, T.F, T.gamma, T.beta, Q->t.eps, wv, lane,
                                             emit);
                 SMX_LDS_BARRIER();
             }
@@ -463,8 +466,8 @@ __device__ __forceinline__ void ddpg_rows4_chain(const RArgs& G, const Prog& P, 
                     const int n = idx / c2, j = idx - n * c2;
                     float v = sm[G.oS + n] * G.cW3[j];
                     if constexpr (LN) {              // d/d(LayerNorm 2's output): its backward rule follows below
-                        sm[Q->oD + n * Q->ldD + j] = v;
-                        if (n < nrows) Q->dn2[(size_t)(row0 + n) * c2 + j] = v;
+                        sm[Q->t.oD + n * Q->t.ldD + j] = v;
+                        if (n < nrows) Q->t.dn2[(size_t)(row0 + n) * c2 + j] = v;
                     } else {
                         v = (sm[G.oB + n * G.ldB + j] > 0.f) ? v : 0.f;
                         sm[G.oA + n * G.ldA + j] = v;
@@ -532,8 +535,8 @@ __device__ __forceinline__ void ddpg_rows4_chain(const RArgs& G, const Prog& P, 
                     const int n = idx / c2, j = idx - n * c2;
                     float v = sm[G.oS + n] * W3[j];
                     if constexpr (LN) {              // d/d(LayerNorm 2's output) of this critic: its backward rule follows
-                        sm[Q->oD + n * Q->ldD + j] = v;
-                        if (n < nrows) (first ? Q->dn2 : Q->dn2_2)[(size_t)(row0 + n) * c2 + j] = v;
+                        sm[Q->t.oD + n * Q->t.ldD + j] = v;
+                        if (n < nrows) (first ? Q->t.dn2 : Q->t.dn2_2)[(size_t)(row0 + n) * c2 + j] = v;
                     } else {
                         v = (sm[G.oB + n * G.ldB + j] > 0.f) ? v : 0.f;
                         sm[G.oA + n * G.ldA + j] = v;
@@ -558,7 +561,7 @@ __device__ __forceinline__ void ddpg_rows4_chain(const RArgs& G, const Prog& P, 
                     const int n = idx / c2, j = idx - n * c2;
                     float v = dq * G.cW3[j];
                     if constexpr (LN) {              // d/d(LayerNorm 2's output) of the critic, as in the critic chain
-                        sm[Q->oD + n * Q->ldD + j] = (n < nrows) ? v : 0.f;
+                        sm[Q->t.oD + n * Q->t.ldD + j] = (n < nrows) ? v : 0.f;
                     } else {
                         v = (n < nrows && sm[G.oB + n * G.ldB + j] > 0.f) ? v : 0.f;
                         sm[G.oA + n * G.ldA + j] = v;
@@ -580,19 +583,19 @@ __device__ __forceinline__ void ddpg_rows4_chain(const RArgs& G, const Prog& P, 
         if constexpr (LN) {
             const LnStep& T = ln_late(Q, si);
             if (T.kind == LN_BWD) {
-                ln_bwd_rows(sm + T.d_off, T.ldd, sm + T.p_off, T.ldp, sm + Q->oM + 2 * RB * T.st, T.F, T.gamma,
+                ln_bwd_rows(sm + T.d_off, T.ldd, sm + T.p_off, T.ldp, sm + Q->t.oM + 2 * RB * T.st, T.F, T.gamma,
                             T.t_off >= 0 ? sm + T.t_off : nullptr, T.ldt, T.n, T.ldn, row0, nrows, wv, lane);
                 SMX_LDS_BARRIER();
                 if (PHASE == 1 && post == P_A_DQ) {
                     // the actor's backward pass (its forward pass ran in the critic phase): its pre-LayerNorm rows and
                     // statistics into the tiles and slots the critic's LayerNorms are done with (the barriers of the next
                     // step stand between this and the rules that read them)
-                    stage_rows(Q->a1, G.H1, G.H1, row0, nrows, Q->oP1, Q->ldP1);
-                    stage_rows(Q->a2, G.H2, G.H2, row0, nrows, Q->oP2, Q->ldP2);
+                    stage_rows(Q->t.a1, G.H1, G.H1, row0, nrows, Q->t.oP1, Q->t.ldP1);
+                    stage_rows(Q->t.a2, G.H2, G.H2, row0, nrows, Q->t.oP2, Q->t.ldP2);
                     if (tp < 4 * RB) {
                         const int w = tp >> 2, n = tp & 3;       // (am1, ar1, am2, ar2) -> slots 2, 3
-                        const float* src = w == 0 ? Q->am1 : w == 1 ? Q->ar1 : w == 2 ? Q->am2 : Q->ar2;
-                        sm[Q->oM + 4 * RB + RB * w + n] = (n < nrows) ? src[row0 + n] : 0.f;
+                        const float* src = w == 0 ? Q->t.am1 : w == 1 ? Q->t.ar1 : w == 2 ? Q->t.am2 : Q->t.ar2;
+                        sm[Q->t.oM + 4 * RB + RB * w + n] = (n < nrows) ? src[row0 + n] : 0.f;
                     }
                 }
             }
@@ -1076,40 +1079,58 @@ void block_shape(const Dims& d, int b, int& M, int& K) {
         default: M = d.A; K = d.c2; break;       // B_CW2THI
     }
 }
-long block_base(const Dims& d, int b) {          // in 16-byte words
-    long o = 0;
-    for (int k = 0; k < b; ++k) {
-        int M, K;
-        block_shape(d, k, M, K);
-        o += pack_words(M, K);
-    }
-    return o;
-}
 
 // the second critic's blocks (TD3) live in a buffer of their own, so the sixteen above stay where they are.  No W2^T hi:
 // nothing differentiates the second critic with respect to the action
 enum { B2_CW1, B2_CW2, B2_CW3, B2_CW2TLO, B2_TCW1, B2_TCW2, B2_TCW3, B2_COUNT };
-const int second_as_first[B2_COUNT] = {B_CW1, B_CW2, B_CW3, B_CW2TLO, B_TCW1, B_TCW2, B_TCW3};      // (same shapes)
 
-long block2_base(const Dims& d, int b) {         // in 16-byte words
-    long o = 0;
-    for (int k = 0; k < b; ++k) {
-        int M, K;
-        block_shape(d, second_as_first[k], M, K);
-        o += pack_words(M, K);
+// A packed buffer: its blocks in order, each with the shape of one of the sixteen
+struct Layout {
+    const int* as_first;          // block b has the shape of block as_first[b] of the first buffer
+    int count;
+    void shape(const Dims& d, int b, int& M, int& K) const { block_shape(d, as_first[b], M, K); }
+    long base(const Dims& d, int b) const {      // in 16-byte words; b == count: the buffer's size
+        long o = 0;
+        for (int k = 0; k < b; ++k) {
+            int M, K;
+            shape(d, k, M, K);
+            o += pack_words(M, K);
+        }
+        return o;
     }
-    return o;
-}
+    PMat pmat(const Dims& d, const float* packed, int b) const {
+        PMat m;
+        shape(d, b, m.M, m.K);
+        m.P = packed + 4 * base(d, b);
+        return m;
+    }
+};
+const int first_as_first[B_COUNT] = {B_AW1, B_AW2, B_AW3, B_AW3T, B_AW2T, B_CW1, B_CW2, B_CW3, B_CW2TLO, B_CW2THI,
+                                     B_TAW1, B_TAW2, B_TAW3, B_TCW1, B_TCW2, B_TCW3};
+const int second_as_first[B2_COUNT] = {B_CW1, B_CW2, B_CW3, B_CW2TLO, B_TCW1, B_TCW2, B_TCW3};      // (same shapes)
+const Layout L_FIRST = {first_as_first, B_COUNT}, L_SECOND = {second_as_first, B2_COUNT};
+// W1, W2, W3 of the networks: actor, critic, their targets in `packed`; the second critic and its target in `packed2`
+const int NET_W[4][3] = {{B_AW1, B_AW2, B_AW3}, {B_CW1, B_CW2, B_CW3}, {B_TAW1, B_TAW2, B_TAW3}, {B_TCW1, B_TCW2, B_TCW3}};
+const int NET2_W[2][3] = {{B2_CW1, B2_CW2, B2_CW3}, {B2_TCW1, B2_TCW2, B2_TCW3}};
 
 long long* g_tbuf = nullptr;
 
-int lds_floats(const Dims& d, RArgs* G, bool td3 = false) {
+inline int imax(int a, int b) { return a > b ? a : b; }
+
+// The chains' LDS carve-up (float offsets, into G and Q where given) -> its size.  With LayerNorm tile A is wide enough
+// for either network's rows (the networks take turns in tiles A and B), and behind the plain regions come the two
+// pre-LayerNorm tiles (layer 1's, layer 2's: kept for the backward rules beside the LayerNorm outputs), the dn tile and
+// four statistics slots of (mean [4], rstd [4]).  TD3's y, kept between the two critics' losses, sits in front of the
+// prefetch pad in the plain carve and at the very end in the LayerNorm one.
+int lds_floats(const Dims& d, bool td3, bool ln, RArgs* G = nullptr, LnProg* Q = nullptr) {
     constexpr int RB = RBLK;
     const int pad = 16;             // row strides = 16 mod 64: the 16 (row, kq) readers of the 4-row loop on distinct banks
     const int ldx = r64(d.D) + pad;
-    const int wa = d.H1 > d.c2 ? d.H1 : d.c2, wb = d.H2 > d.c2 ? d.H2 : d.c2;
-    const int wc = d.c1 + d.A > d.H1 ? d.c1 + d.A : d.H1;
+    const int wa = imax(imax(d.H1, d.c2), ln ? d.H2 : 0), wb = imax(d.H2, d.c2), wc = imax(d.c1 + d.A, d.H1);
     const int ldA = r64(wa) + pad, ldB = r64(wb) + pad, ldC = r64(wc) + pad;
+    const int ldP1 = r64(imax(d.H1, d.c1)) + pad, ldP2 = r64(imax(d.H2, d.c2)) + pad;
+    const int ldD = r64(imax(imax(d.H1, d.H2), imax(d.c1, d.c2))) + pad;
+    const int ny = td3 ? 16 : 0;
     int o = 0;
     const int oX = o; o += RB * ldx;
     const int oXn = o; o += RB * ldx;
@@ -1122,98 +1143,58 @@ int lds_floats(const Dims& d, RArgs* G, bool td3 = false) {
     const int oZ = o; o += RB * LDK4;
     const int oS = o; o += 16;
     const int oR = o; o += DNWV * 2 * 4 * 16;      // the split-K layers' partial sums
-    const int oY = o; o += td3 ? 16 : 0;           // TD3: y between the two critics' losses
+    int oY = o; o += ln ? 0 : ny;
     o += 128;                     // the K loop's prefetch reads up to two chunks past a tile's last row
-    if (G) {
-        G->ldx = ldx; G->ldA = ldA; G->ldB = ldB; G->ldC = ldC;
-        G->oX = oX; G->oXn = oXn; G->oA = oA; G->oB = oB; G->oC = oC; G->oO = oO; G->oO2 = oO2; G->oO3 = oO3;
-        G->oZ = oZ; G->oS = oS; G->oR = oR; G->oY = oY; G->total = o;
+    int oP1 = 0, oP2 = 0, oD = 0, oM = 0;
+    if (ln) {
+        oP1 = o; o += RB * ldP1;
+        oP2 = o; o += RB * ldP2;
+        oD = o; o += RB * ldD;
+        oM = o; o += 4 * 2 * RB;
+        oY = o; o += ny;
     }
-    return o;
-}
-
-// The LayerNorm chains' carve-up: the plain one with tiles A and B wide enough for either network's rows (they take
-// turns in them), then the two pre-LayerNorm tiles (layer 1's, layer 2's: kept for the backward rules beside the
-// LayerNorm outputs), the dn tile and four statistics slots of (mean [4], rstd [4])
-int lds_floats_ln(const Dims& d, RArgs* G, LnProg* Q, bool td3 = false) {
-    constexpr int RB = RBLK;
-    const int pad = 16;
-    auto mx = [](int a, int b) { return a > b ? a : b; };
-    const int ldx = r64(d.D) + pad;
-    const int wa = mx(mx(d.H1, d.c2), d.H2), wb = mx(d.H2, d.c2), wc = mx(d.c1 + d.A, d.H1);
-    const int ldA = r64(wa) + pad, ldB = r64(wb) + pad, ldC = r64(wc) + pad;
-    const int ldP1 = r64(mx(d.H1, d.c1)) + pad, ldP2 = r64(mx(d.H2, d.c2)) + pad;
-    const int ldD = r64(mx(mx(d.H1, d.H2), mx(d.c1, d.c2))) + pad;
-    int o = 0;
-    const int oX = o; o += RB * ldx;
-    const int oXn = o; o += RB * ldx;
-    const int oA = o; o += RB * ldA;
-    const int oB = o; o += RB * ldB;
-    const int oC = o; o += RB * ldC;
-    const int oO = o; o += RB * LDO;
-    const int oO2 = o; o += RB * LDO;
-    const int oO3 = o; o += RB * LDO;
-    const int oZ = o; o += RB * LDK4;
-    const int oS = o; o += 16;
-    const int oR = o; o += DNWV * 2 * 4 * 16;
-    o += 128;                     // the K loop's prefetch reads up to two chunks past a tile's last row
-    const int oP1 = o; o += RB * ldP1;
-    const int oP2 = o; o += RB * ldP2;
-    const int oD = o; o += RB * ldD;
-    const int oM = o; o += 4 * 2 * RB;
-    const int oY = o; o += td3 ? 16 : 0;           // TD3: y between the two critics' losses
     if (G) {
         G->ldx = ldx; G->ldA = ldA; G->ldB = ldB; G->ldC = ldC;
         G->oX = oX; G->oXn = oXn; G->oA = oA; G->oB = oB; G->oC = oC; G->oO = oO; G->oO2 = oO2; G->oO3 = oO3;
         G->oZ = oZ; G->oS = oS; G->oR = oR; G->oY = oY; G->total = o;
     }
     if (Q) {
-        Q->oP1 = oP1; Q->ldP1 = ldP1; Q->oP2 = oP2; Q->ldP2 = ldP2; Q->oD = oD; Q->ldD = ldD; Q->oM = oM;
+        Q->t.oP1 = oP1; Q->t.ldP1 = ldP1; Q->t.oP2 = oP2; Q->t.ldP2 = ldP2; Q->t.oD = oD; Q->t.ldD = ldD; Q->t.oM = oM;
     }
     return o;
 }
 
+// (a LayerNorm shape must fit the plain carve as well: dims_ok_ln adds its own to dims_ok's)
 bool dims_ok(const Dims& d, bool td3 = false) {
     return d.D > 0 && d.A > 0 && d.A <= 32 && d.H1 > 0 && d.H2 > 0 && d.c1 > 0 && d.c2 > 0 && d.D <= 2048 &&
            d.H1 % 4 == 0 && d.H2 % 4 == 0 && d.c1 % 4 == 0 && d.c2 % 4 == 0 && d.H1 <= 1024 && d.H2 <= 1024 &&
-           d.c1 <= 1024 && d.c2 <= 1024 && lds_floats(d, nullptr, td3) * (int)sizeof(float) <= MAX_LDS;
+           d.c1 <= 1024 && d.c2 <= 1024 && lds_floats(d, td3, false) * (int)sizeof(float) <= MAX_LDS;
 }
-
-Dims dims_of(const smx_ddpg_rows_t& a) {
-    Dims d;
-    d.D = a.D; d.A = a.A; d.H1 = a.H1; d.H2 = a.H2; d.c1 = a.c1; d.c2 = a.c2;
-    return d;
-}
-
-PMat pmat(const smx_ddpg_rows_t& a, const Dims& d, int b) {
-    PMat m;
-    block_shape(d, b, m.M, m.K);
-    m.P = a.packed + 4 * block_base(d, b);
-    return m;
-}
-
-// every row-major output is addressed through a buffer descriptor: 31-bit byte offsets
-bool offsets_ok(const Dims& d, int64_t rows) {
-    int widest = d.c1 + d.A;
-    widest = d.H1 > widest ? d.H1 : widest;
-    widest = d.c2 > widest ? d.c2 : widest;
-    widest = d.H2 > widest ? d.H2 : widest;
-    widest = d.D > widest ? d.D : widest;
-    return rows * widest * 4 < (1ll << 31);
-}
-
 bool dims_ok_ln(const Dims& d, bool td3 = false) {
-    return dims_ok(d, td3) && lds_floats_ln(d, nullptr, nullptr, td3) * (int)sizeof(float) <= MAX_LDS;
+    return dims_ok(d, td3) && lds_floats(d, td3, true) * (int)sizeof(float) <= MAX_LDS;
+}
+
+Dims dims_of(const smx_ddpg_rows_t& a) { return Dims{a.D, a.A, a.H1, a.H2, a.c1, a.c2}; }
+
+bool rows_ok(int64_t rows) { return rows > 0 && rows < (1 << 24); }
+
+// Every row-major output is addressed through a buffer descriptor: 31-bit byte offsets into the widest of them.  The
+// observations count only `with_input`: the chains stage x and x_next with size_t indices (stage_rows), not through a
+// descriptor, so the plain chains need no bound on D; the TD3 and LayerNorm paths have bounded it since they came, and
+// the shapes they accept stay as they are.
+bool offsets_ok(const Dims& d, int64_t rows, bool with_input) {
+    const int widest = imax(imax(imax(d.c1 + d.A, d.H1), imax(d.c2, d.H2)), with_input ? d.D : 0);
+    return rows * widest * 4 < (1ll << 31);
 }
 
 // LayerNorm with a second critic: both parts present (an `ln` without its second part beside a `second` is refused)
 bool ln_second(const smx_ddpg_rows_t* a) { return a->ln && a->ln->second && a->second; }
 
-PMat pmat2(const smx_ddpg_rows_second& s, const Dims& d, int b) {
-    PMat m;
-    block_shape(d, second_as_first[b], m.M, m.K);
-    m.P = s.packed2 + 4 * block2_base(d, b);
-    return m;
+bool net_present(const smx_ddpg_net_t& n) { return n.W1 && n.b1 && n.W2 && n.b2 && n.W3 && n.b3; }
+
+void set_net(RNet& r, const smx_ddpg_net_t& n, const Layout& L, const Dims& d, const float* packed, const int w[3]) {
+    r.b1 = n.b1; r.b2 = n.b2; r.b3 = n.b3;
+    r.W1 = L.pmat(d, packed, w[0]); r.W2 = L.pmat(d, packed, w[1]); r.W3 = L.pmat(d, packed, w[2]);
 }
 
 int fill(RArgs& G, const smx_ddpg_rows_t* a, bool td3 = false, LnProg* Q = nullptr) {
@@ -1221,31 +1202,18 @@ int fill(RArgs& G, const smx_ddpg_rows_t* a, bool td3 = false, LnProg* Q = nullp
     const Dims d = dims_of(*a);
     // LayerNorm: its own launches; with a second critic only where its LayerNorm part came along
     SMX_REQUIRE(!a->ln || (Q && (a->second ? ln_second(a) : !td3)), SMX_E_UNSUPPORTED);
-    SMX_REQUIRE(a->rows > 0 && a->rows < (1 << 24), SMX_E_SHAPE);
+    SMX_REQUIRE(rows_ok(a->rows), SMX_E_SHAPE);
     SMX_REQUIRE(dims_ok(d, td3), SMX_E_UNSUPPORTED);
-    {
-        int widest = d.c1 + d.A;
-        widest = d.H1 > widest ? d.H1 : widest;
-        widest = d.c2 > widest ? d.c2 : widest;
-        widest = d.H2 > widest ? d.H2 : widest;
-        SMX_REQUIRE((int64_t)a->rows * widest * 4 < (1ll << 31), SMX_E_SHAPE);
-    }
+    SMX_REQUIRE(offsets_ok(d, a->rows, false), SMX_E_SHAPE);
     SMX_REQUIRE(((uintptr_t)a->packed & 15) == 0, SMX_E_ALIGN);
     const smx_ddpg_net_t* nets[4] = {&a->actor, &a->critic, &a->target_actor, &a->target_critic};
-    for (int k = 0; k < 4; ++k)
-        SMX_REQUIRE(nets[k]->W1 && nets[k]->b1 && nets[k]->W2 && nets[k]->b2 && nets[k]->W3 && nets[k]->b3, SMX_E_NULL);
+    for (int k = 0; k < 4; ++k) SMX_REQUIRE(net_present(*nets[k]), SMX_E_NULL);
     memset(&G, 0, sizeof(G));
     G.rows = (int)a->rows; G.D = d.D; G.A = d.A; G.H1 = d.H1; G.H2 = d.H2; G.c1 = d.c1; G.c2 = d.c2;
     RNet* rn[4] = {&G.a, &G.c, &G.ta, &G.tc};
-    const int w1[4] = {B_AW1, B_CW1, B_TAW1, B_TCW1};
-    for (int k = 0; k < 4; ++k) {
-        rn[k]->b1 = nets[k]->b1; rn[k]->b2 = nets[k]->b2; rn[k]->b3 = nets[k]->b3;
-        rn[k]->W1 = pmat(*a, d, w1[k]);
-        rn[k]->W2 = pmat(*a, d, w1[k] == B_AW1 ? B_AW2 : (w1[k] == B_CW1 ? B_CW2 : w1[k] + 1));
-        rn[k]->W3 = pmat(*a, d, w1[k] == B_AW1 ? B_AW3 : (w1[k] == B_CW1 ? B_CW3 : w1[k] + 2));
-    }
-    G.cW2Tlo = pmat(*a, d, B_CW2TLO); G.cW2Thi = pmat(*a, d, B_CW2THI);
-    G.aW3T = pmat(*a, d, B_AW3T); G.aW2T = pmat(*a, d, B_AW2T);
+    for (int k = 0; k < 4; ++k) set_net(*rn[k], *nets[k], L_FIRST, d, a->packed, NET_W[k]);
+    G.cW2Tlo = L_FIRST.pmat(d, a->packed, B_CW2TLO); G.cW2Thi = L_FIRST.pmat(d, a->packed, B_CW2THI);
+    G.aW3T = L_FIRST.pmat(d, a->packed, B_AW3T); G.aW2T = L_FIRST.pmat(d, a->packed, B_AW2T);
     G.cW3 = a->critic.W3;
     G.x = a->x; G.xn = a->x_next; G.actions = a->actions; G.rewards = a->rewards; G.dones = a->dones;
     G.gamma_n = a->gamma_n;
@@ -1253,35 +1221,33 @@ int fill(RArgs& G, const smx_ddpg_rows_t* a, bool td3 = false, LnProg* Q = nullp
     G.dxcat = a->dxcat; G.h1a = a->h1a; G.h2a = a->h2a; G.act = a->act;
     G.q_actor = a->q_actor; G.dz3a = a->dz3a; G.dz2a = a->dz2a; G.dz1a = a->dz1a;
     G.step = a->step;
-    lds_floats(d, &G, td3);
+    lds_floats(d, td3, false, &G);
     G.tbuf = g_tbuf;
     if (a->ln) {
         const smx_ddpg_rows_ln* l = a->ln;
         const bool two = ln_second(a);
         SMX_REQUIRE(dims_ok_ln(d, two), SMX_E_UNSUPPORTED);
-        SMX_REQUIRE(offsets_ok(d, a->rows), SMX_E_SHAPE);
+        SMX_REQUIRE(offsets_ok(d, a->rows, true), SMX_E_SHAPE);
         const smx_ddpg_ln_net* ln[6] = {&l->actor, &l->critic, &l->target_actor, &l->target_critic,
                                         two ? &l->second->critic2 : nullptr, two ? &l->second->target_critic2 : nullptr};
         for (int k = 0; k < (two ? 6 : 4); ++k) SMX_REQUIRE(ln[k]->g1 && ln[k]->b1 && ln[k]->g2 && ln[k]->b2, SMX_E_NULL);
         SMX_REQUIRE(l->eps > 0.f, SMX_E_SHAPE);
         memset(Q, 0, sizeof(*Q));
-        lds_floats_ln(d, &G, Q, two);
-        Q->eps = l->eps;
+        lds_floats(d, two, true, &G, Q);
+        Q->t.eps = l->eps;
     }
     if (td3) {
         const smx_ddpg_rows_second* s = a->second;
         SMX_REQUIRE(s && s->packed2, SMX_E_NULL);
         SMX_REQUIRE(((uintptr_t)s->packed2 & 15) == 0, SMX_E_ALIGN);
-        SMX_REQUIRE(offsets_ok(d, a->rows), SMX_E_SHAPE);
+        SMX_REQUIRE(offsets_ok(d, a->rows, true), SMX_E_SHAPE);
         const smx_ddpg_net_t* n2[2] = {&s->critic2, &s->target_critic2};
         RNet* r2[2] = {&G.c2n, &G.tc2};
-        const int w1b[2] = {B2_CW1, B2_TCW1};
         for (int k = 0; k < 2; ++k) {
-            SMX_REQUIRE(n2[k]->W1 && n2[k]->b1 && n2[k]->W2 && n2[k]->b2 && n2[k]->W3 && n2[k]->b3, SMX_E_NULL);
-            r2[k]->b1 = n2[k]->b1; r2[k]->b2 = n2[k]->b2; r2[k]->b3 = n2[k]->b3;
-            r2[k]->W1 = pmat2(*s, d, w1b[k]); r2[k]->W2 = pmat2(*s, d, w1b[k] + 1); r2[k]->W3 = pmat2(*s, d, w1b[k] + 2);
+            SMX_REQUIRE(net_present(*n2[k]), SMX_E_NULL);
+            set_net(*r2[k], *n2[k], L_SECOND, d, s->packed2, NET2_W[k]);
         }
-        G.c2W2Tlo = pmat2(*s, d, B2_CW2TLO);
+        G.c2W2Tlo = L_SECOND.pmat(d, s->packed2, B2_CW2TLO);
         G.c2W3 = s->critic2.W3;
         G.noise = s->noise;
         G.xcat2 = s->xcat2; G.h2c2 = s->h2c2; G.q2 = s->q2; G.q_next2 = s->q_next2; G.dz3_2 = s->dz3_2;
@@ -1298,44 +1264,6 @@ Step step(int in_off, int ldi, const PMat& W, const float* bias, int act, int ou
     return S;
 }
 
-// the two chains, step for step
-void critic_program(const RArgs& G, Prog& P) {
-    const int ldc = G.c1 + G.A;
-    int n = 0;
-    P.s[n++] = step(G.oXn, G.ldx, G.ta.W1, G.ta.b1, A_RELU, G.oA, G.ldA, nullptr, 0, P_NONE);         // mu'(s')
-    P.s[n++] = step(G.oA, G.ldA, G.ta.W2, G.ta.b2, A_RELU, G.oB, G.ldB, nullptr, 0, P_NONE);
-    P.s[n++] = step(G.oB, G.ldB, G.ta.W3, G.ta.b3, A_TANH, G.oO, LDO, nullptr, 0, P_NONE);
-    P.s[n++] = step(G.oXn, G.ldx, G.tc.W1, G.tc.b1, A_RELU, G.oC, G.ldC, nullptr, 0, P_TC_CAT);       // Q'(s', mu'(s'))
-    P.s[n++] = step(G.oC, G.ldC, G.tc.W2, G.tc.b2, A_RELU, G.oB, G.ldB, nullptr, 0, P_NONE);
-    P.s[n++] = step(G.oB, G.ldB, G.tc.W3, G.tc.b3, A_NONE, G.oO2, LDO, nullptr, 0, P_NONE);
-    P.s[n++] = step(G.oX, G.ldx, G.c.W1, G.c.b1, A_RELU, G.oC, G.ldC, G.xcat, ldc, P_C_CAT);          // Q(s, a)
-    P.s[n++] = step(G.oC, G.ldC, G.c.W2, G.c.b2, A_RELU, G.oB, G.ldB, G.h2c, G.c2, P_NONE);
-    P.s[n++] = step(G.oB, G.ldB, G.c.W3, G.c.b3, A_NONE, G.oO, LDO, nullptr, 0, P_LOSS);              // -> y, dz3, dz2
-    P.s[n] = step(G.oA, G.ldA, G.cW2Tlo, nullptr, A_MASK, -1, 0, G.dxcat, ldc, P_NONE);               // dz1
-    P.s[n].mask_off = G.oC; P.s[n].ldm = G.ldC; ++n;
-    P.s[n++] = step(G.oX, G.ldx, G.a.W1, G.a.b1, A_RELU, G.oA, G.ldA, G.h1a, G.H1, P_NONE);           // mu(s), kept
-    P.s[n++] = step(G.oA, G.ldA, G.a.W2, G.a.b2, A_RELU, G.oB, G.ldB, G.h2a, G.H2, P_NONE);
-    P.s[n++] = step(G.oB, G.ldB, G.a.W3, G.a.b3, A_TANH, -1, 0, G.act, G.A, P_NONE);
-    P.n = n;
-}
-
-void actor_program(const RArgs& G, Prog& P) {
-    int n = 0;
-    P.s[n++] = step(G.oX, G.ldx, G.c.W1, G.c.b1, A_RELU, G.oC, G.ldC, nullptr, 0, P_A_CAT);           // Q(s, mu(s))
-    P.s[n++] = step(G.oC, G.ldC, G.c.W2, G.c.b2, A_RELU, G.oB, G.ldB, nullptr, 0, P_NONE);
-    P.s[n++] = step(G.oB, G.ldB, G.c.W3, G.c.b3, A_NONE, -1, 0, G.q_actor, 1, P_A_DQ);                // -> masks, dz2
-    P.s[n++] = step(G.oA, G.ldA, G.cW2Thi, nullptr, A_NONE, G.oO2, LDO, nullptr, 0, P_A_TANH);        // d/d(action)
-    P.s[n] = step(G.oZ, LDK4, G.aW3T, nullptr, A_MASK, G.oA, G.ldA, G.dz2a, G.H2, P_NONE);            // the actor's dz2, dz1
-    P.s[n].mask_off = G.oB; P.s[n].ldm = G.ldB; ++n;
-    P.s[n] = step(G.oA, G.ldA, G.aW2T, nullptr, A_MASK, -1, 0, G.dz1a, G.H1, P_NONE);
-    P.s[n].mask_off = G.oC; P.s[n].ldm = G.ldC; ++n;
-    P.n = n;
-}
-
-// The LayerNorm chains: the same products (13 and 6).  A hidden layer writes relu(z) to a pre-LayerNorm tile (P1 behind a
-// first layer, P2 behind a second) and the rule puts the normalised rows where the plain chain has the layer's output; a
-// backward product leaves dn in the dn tile and the rule puts the gradient at the ReLU's input where the plain chain has
-// the masked product.  With LayerNorm h2c, h1a, h2a name the LayerNorm OUTPUTS (what the weight gradients multiply).
 void ln_fwd(LnProg& Q, int si, const Step& S, const float* gamma, const float* beta, int t_off, int ldt, float* n, int ldn,
             float* mean, float* rstd, int st) {
     LnStep& T = Q.s[si];
@@ -1344,155 +1272,227 @@ void ln_fwd(LnProg& Q, int si, const Step& S, const float* gamma, const float* b
 }
 void ln_bwd(LnProg& Q, int si, int F, const float* gamma, int p_off, int ldp, int t_off, int ldt, float* n, int ldn, int st) {
     LnStep& T = Q.s[si];
-    T.kind = LN_BWD; T.F = F; T.gamma = gamma; T.p_off = p_off; T.ldp = ldp; T.d_off = Q.oD; T.ldd = Q.ldD; T.t_off = t_off;
+    T.kind = LN_BWD; T.F = F; T.gamma = gamma; T.p_off = p_off; T.ldp = ldp; T.d_off = Q.t.oD; T.ldd = Q.t.ldD; T.t_off = t_off;
     T.ldt = ldt; T.n = n; T.ldn = ldn; T.st = st;
 }
 
-void critic_program_ln(const RArgs& G, const smx_ddpg_rows_ln& l, Prog& P, LnProg& Q) {
-    const int ldc = G.c1 + G.A;
-    const int P1 = Q.oP1, l1 = Q.ldP1, P2 = Q.oP2, l2 = Q.ldP2;
-    int n = 0;
-    P.s[n] = step(G.oXn, G.ldx, G.ta.W1, G.ta.b1, A_RELU, P1, l1, nullptr, 0, P_NONE);                // mu'(s')
-    ln_fwd(Q, n, P.s[n], l.target_actor.g1, l.target_actor.b1, G.oA, G.ldA, nullptr, 0, nullptr, nullptr, 0); ++n;
-    P.s[n] = step(G.oA, G.ldA, G.ta.W2, G.ta.b2, A_RELU, P2, l2, nullptr, 0, P_NONE);
-    ln_fwd(Q, n, P.s[n], l.target_actor.g2, l.target_actor.b2, G.oB, G.ldB, nullptr, 0, nullptr, nullptr, 1); ++n;
-    P.s[n++] = step(G.oB, G.ldB, G.ta.W3, G.ta.b3, A_TANH, G.oO, LDO, nullptr, 0, P_NONE);
-    P.s[n] = step(G.oXn, G.ldx, G.tc.W1, G.tc.b1, A_RELU, P1, l1, nullptr, 0, P_TC_CAT);              // Q'(s', mu'(s'))
-    ln_fwd(Q, n, P.s[n], l.target_critic.g1, l.target_critic.b1, G.oC, G.ldC, nullptr, 0, nullptr, nullptr, 0); ++n;
-    P.s[n] = step(G.oC, G.ldC, G.tc.W2, G.tc.b2, A_RELU, P2, l2, nullptr, 0, P_NONE);
-    ln_fwd(Q, n, P.s[n], l.target_critic.g2, l.target_critic.b2, G.oB, G.ldB, nullptr, 0, nullptr, nullptr, 1); ++n;
-    P.s[n++] = step(G.oB, G.ldB, G.tc.W3, G.tc.b3, A_NONE, G.oO2, LDO, nullptr, 0, P_NONE);
-    P.s[n] = step(G.oX, G.ldx, G.c.W1, G.c.b1, A_RELU, P1, l1, l.c_a1, G.c1, P_C_CAT);                // Q(s, a)
-    ln_fwd(Q, n, P.s[n], l.critic.g1, l.critic.b1, G.oC, G.ldC, G.xcat, ldc, l.cm1, l.cr1, 0); ++n;
-    P.s[n] = step(G.oC, G.ldC, G.c.W2, G.c.b2, A_RELU, P2, l2, l.c_a2, G.c2, P_NONE);
-    ln_fwd(Q, n, P.s[n], l.critic.g2, l.critic.b2, G.oB, G.ldB, G.h2c, G.c2, l.cm2, l.cr2, 1); ++n;
-    P.s[n] = step(G.oB, G.ldB, G.c.W3, G.c.b3, A_NONE, G.oO, LDO, nullptr, 0, P_LOSS);                // -> y, dz3, dn2
-    ln_bwd(Q, n, G.c2, l.critic.g2, P2, l2, G.oA, G.ldA, G.dz2, G.c2, 1); ++n;                        // -> dz2
-    P.s[n] = step(G.oA, G.ldA, G.cW2Tlo, nullptr, A_NONE, Q.oD, Q.ldD, G.dxcat, ldc, P_NONE);         // dn1
-    ln_bwd(Q, n, G.c1, l.critic.g1, P1, l1, -1, 0, l.dz1c, G.c1, 0); ++n;                             // -> dz1
-    P.s[n] = step(G.oX, G.ldx, G.a.W1, G.a.b1, A_RELU, P1, l1, l.a1, G.H1, P_NONE);                   // mu(s), kept
-    ln_fwd(Q, n, P.s[n], l.actor.g1, l.actor.b1, G.oA, G.ldA, G.h1a, G.H1, l.am1, l.ar1, 0); ++n;
-    P.s[n] = step(G.oA, G.ldA, G.a.W2, G.a.b2, A_RELU, P2, l2, l.a2, G.H2, P_NONE);
-    ln_fwd(Q, n, P.s[n], l.actor.g2, l.actor.b2, G.oB, G.ldB, G.h2a, G.H2, l.am2, l.ar2, 1); ++n;
-    P.s[n++] = step(G.oB, G.ldB, G.a.W3, G.a.b3, A_TANH, -1, 0, G.act, G.A, P_NONE);
-    P.n = n;
-    Q.dn2 = l.dn2;
-}
-static_assert(LN_STEPS >= 13, "the LayerNorm critic chain has 13 layers");
+// ---------------------------------------------------------------------------------------------------------------
+// The chains, written as segments.  A segment emits its plain steps and, where the chain has LayerNorm (Q set), the
+// rule behind each; what differs between the two forms is stated in the segment, once:
+//  * a hidden layer writes relu(z) to a pre-LayerNorm tile (P1 behind a first layer, P2 behind a second) and to HBM with
+//    the layer's own width as stride; the rule puts the normalised rows where the plain chain has the layer's output.
+//    So with LayerNorm xcat, h2c, h1a, h2a name the LayerNorm OUTPUTS (what the weight gradients multiply)
+//  * a backward product leaves dn in the dn tile, unmasked; the rule (the x > 0 mask folded in) puts the gradient at the
+//    ReLU's input where the plain chain has the masked product
+// P1 / P2 hold the pre-LayerNorm rows of the network in flight, statistics slots 0 / 1 its two LayerNorms'.
+// ---------------------------------------------------------------------------------------------------------------
+struct Keep {                     // what a hidden layer leaves in HBM ({}: nothing)
+    float* h = nullptr;           // its output [rows][ldh] -- the LayerNorm's where there is one
+    int ldh = 0;
+    float *pre = nullptr, *mean = nullptr, *rstd = nullptr;       // LayerNorm: relu(z) [rows][F], the rows' statistics
+};
+const smx_ddpg_rows_ln NO_LN = {};                // what the plain chains read the LayerNorm fields from: all null
+const smx_ddpg_rows_ln_second NO_LN2 = {};
 
-void actor_program_ln(const RArgs& G, const smx_ddpg_rows_ln& l, Prog& P, LnProg& Q) {
-    const int P1 = Q.oP1, l1 = Q.ldP1, P2 = Q.oP2, l2 = Q.ldP2;
-    int n = 0;
-    P.s[n] = step(G.oX, G.ldx, G.c.W1, G.c.b1, A_RELU, P1, l1, nullptr, 0, P_A_CAT);                  // Q(s, mu(s))
-    ln_fwd(Q, n, P.s[n], l.critic.g1, l.critic.b1, G.oC, G.ldC, nullptr, 0, nullptr, nullptr, 0); ++n;
-    P.s[n] = step(G.oC, G.ldC, G.c.W2, G.c.b2, A_RELU, P2, l2, nullptr, 0, P_NONE);
-    ln_fwd(Q, n, P.s[n], l.critic.g2, l.critic.b2, G.oB, G.ldB, nullptr, 0, nullptr, nullptr, 1); ++n;
-    P.s[n] = step(G.oB, G.ldB, G.c.W3, G.c.b3, A_NONE, -1, 0, G.q_actor, 1, P_A_DQ);                  // -> dn2
-    ln_bwd(Q, n, G.c2, l.critic.g2, P2, l2, G.oA, G.ldA, nullptr, 0, 1); ++n;     // back through the critic's LayerNorm 2 only
-    P.s[n++] = step(G.oA, G.ldA, G.cW2Thi, nullptr, A_NONE, G.oO2, LDO, nullptr, 0, P_A_TANH);        // d/d(action)
-    P.s[n] = step(G.oZ, LDK4, G.aW3T, nullptr, A_NONE, Q.oD, Q.ldD, l.dn2a, G.H2, P_NONE);            // the actor's dn2, dn1
-    ln_bwd(Q, n, G.H2, l.actor.g2, P2, l2, G.oA, G.ldA, G.dz2a, G.H2, 3); ++n;                        // (a2, a1: staged)
-    P.s[n] = step(G.oA, G.ldA, G.aW2T, nullptr, A_NONE, Q.oD, Q.ldD, l.dn1a, G.H1, P_NONE);
-    ln_bwd(Q, n, G.H1, l.actor.g1, P1, l1, -1, 0, G.dz1a, G.H1, 2); ++n;
-    P.n = n;
-    Q.a1 = l.a1; Q.a2 = l.a2; Q.am1 = l.am1; Q.ar1 = l.ar1; Q.am2 = l.am2; Q.ar2 = l.ar2;
+struct Chain {
+    const RArgs& G;
+    Prog& P;
+    LnProg* Q;                    // null: no LayerNorm
+    int n;
+
+    const Step& emit(const Step& S) {
+        P.s[n] = S;
+        P.n = n + 1;
+        return P.s[n++];
+    }
+    int pre_off(int level) const { return level == 1 ? Q->t.oP1 : Q->t.oP2; }
+    int pre_ld(int level) const { return level == 1 ? Q->t.ldP1 : Q->t.ldP2; }
+
+    // hidden layer `level` of a network: relu(W in + b) -> tile (t, ldt) and k
+    void hidden(int level, int in, int ldi, const PMat& W, const float* b, const float* gamma, const float* beta, int t, int ldt,
+                int post, const Keep& k) {
+        if (!Q) {
+            emit(step(in, ldi, W, b, A_RELU, t, ldt, k.h, k.ldh, post));
+            return;
+        }
+        const Step& S = emit(step(in, ldi, W, b, A_RELU, pre_off(level), pre_ld(level), k.pre, k.pre ? W.M : 0, post));
+        ln_fwd(*Q, n - 1, S, gamma, beta, t, ldt, k.h, k.ldh, k.mean, k.rstd, level - 1);
+    }
+    // a network's two hidden layers from the observations at `in`: layer 1 (and its `post`) -> tile (t1, ldt1), layer 2 -> B
+    void hidden2(const RNet& N, const smx_ddpg_ln_net& ln, int in, int t1, int ldt1, int post1, const Keep& k1, const Keep& k2) {
+        hidden(1, in, G.ldx, N.W1, N.b1, ln.g1, ln.b1, t1, ldt1, post1, k1);
+        hidden(2, t1, ldt1, N.W2, N.b2, ln.g2, ln.b2, G.oB, G.ldB, P_NONE, k2);
+    }
+    // ... and its output layer -> tile `out` (< 0: none) and HBM g
+    void forward(const RNet& N, const smx_ddpg_ln_net& ln, int in, int t1, int ldt1, int post1, const Keep& k1, const Keep& k2,
+                 int act3, int out, int ldo, float* g = nullptr, int ldg = 0) {
+        hidden2(N, ln, in, t1, ldt1, post1, k1, k2);
+        emit(step(G.oB, G.ldB, N.W3, N.b3, act3, out, ldo, g, ldg, P_NONE));
+    }
+    // the LayerNorm-2 backward rule behind a critic's output layer, whose `post` has left dn2 in the dn tile: -> tile A, dz2
+    void back_ln2(const float* gamma2, float* dz2) {
+        if (Q) ln_bwd(*Q, n - 1, G.c2, gamma2, pre_off(2), pre_ld(2), G.oA, G.ldA, dz2, dz2 ? G.c2 : 0, 1);
+    }
+    // A backward product, W^T times the tile at `in`, through hidden layer `level`: plain, masked by the layer's output
+    // tile (m, ldm) -> tile (t, ldt; < 0: none) and HBM dz; LayerNorm, unmasked -> the dn tile and HBM dn (the same
+    // stride ldg), then the rule with the statistics of slot st -> tile t and HBM dzn
+    void back(int level, int in, int ldi, const PMat& WT, const float* gamma, int m, int ldm, int t, int ldt, float* dz, int ldg,
+              float* dn, float* dzn, int st) {
+        if (!Q) {
+            Step S = step(in, ldi, WT, nullptr, A_MASK, t, ldt, dz, ldg, P_NONE);
+            S.mask_off = m; S.ldm = ldm;
+            emit(S);
+            return;
+        }
+        emit(step(in, ldi, WT, nullptr, A_NONE, Q->t.oD, Q->t.ldD, dn, ldg, P_NONE));
+        ln_bwd(*Q, n - 1, WT.M, gamma, pre_off(level), pre_ld(level), t, ldt, dzn, WT.M, st);
+    }
+};
+
+void target_actor(Chain& C, const smx_ddpg_rows_ln& l) {                                    // mu'(s') -> tile O
+    C.forward(C.G.ta, l.target_actor, C.G.oXn, C.G.oA, C.G.ldA, P_NONE, {}, {}, A_TANH, C.G.oO, LDO);
+}
+// Q'(s', .) at the action `cat` puts beside layer 1's output (P_TC_CAT: mu'; P_TC2_CAT: clamp(mu' + noise)) -> tile `out`
+void target_critic(Chain& C, const RNet& N, const smx_ddpg_ln_net& ln, int cat, int out) {
+    C.forward(N, ln, C.G.oXn, C.G.oC, C.G.ldC, cat, {}, {}, A_NONE, out, LDO);
+}
+// A critic at (s, a), kept; its loss (P_LOSS: y, dz3 and dz2 -- LayerNorm: dn2; P_LOSS2: against the kept y) and the
+// W2^T-lo product: dz1 (LayerNorm: dn1 into dxcat, dz1 into a buffer of its own).  Its backward rules run before the next
+// network overwrites the pre-LayerNorm tiles and the statistics.
+void critic_sa(Chain& C, const RNet& N, const smx_ddpg_ln_net& ln, const PMat& W2Tlo, int cat, int loss, const Keep& k1,
+               const Keep& k2, float* dz2, float* dxcat, float* dz1c) {
+    const RArgs& G = C.G;
+    C.hidden2(N, ln, G.oX, G.oC, G.ldC, cat, k1, k2);
+    C.emit(step(G.oB, G.ldB, N.W3, N.b3, A_NONE, G.oO, LDO, nullptr, 0, loss));
+    C.back_ln2(ln.g2, dz2);
+    C.back(1, G.oA, G.ldA, W2Tlo, ln.g1, G.oC, G.ldC, -1, 0, dxcat, G.c1 + G.A, dxcat, dz1c, 0);
+}
+void first_critic(Chain& C, const smx_ddpg_rows_ln& l) {
+    const RArgs& G = C.G;
+    critic_sa(C, G.c, l.critic, G.cW2Tlo, P_C_CAT, P_LOSS, {G.xcat, G.c1 + G.A, l.c_a1, l.cm1, l.cr1},
+              {G.h2c, G.c2, l.c_a2, l.cm2, l.cr2}, G.dz2, G.dxcat, l.dz1c);
+}
+void second_critic(Chain& C, const smx_ddpg_rows_ln_second& l2) {
+    const RArgs& G = C.G;
+    critic_sa(C, G.c2n, l2.critic2, G.c2W2Tlo, P_C2_CAT, P_LOSS2, {G.xcat2, G.c1 + G.A, l2.c2_a1, l2.c2m1, l2.c2r1},
+              {G.h2c2, G.c2, l2.c2_a2, l2.c2m2, l2.c2r2}, G.dz2_2, G.dxcat2, l2.dz1c2);
+}
+void actor_kept(Chain& C, const smx_ddpg_rows_ln& l) {                                      // mu(s), kept for ITS update
+    const RArgs& G = C.G;
+    C.forward(G.a, l.actor, G.oX, G.oA, G.ldA, P_NONE, {G.h1a, G.H1, l.a1, l.am1, l.ar1}, {G.h2a, G.H2, l.a2, l.am2, l.ar2},
+              A_TANH, -1, 0, G.act, G.A);
+}
+// The actor phase behind Q(s, mu(s))'s hidden layers: q and the masks (P_A_DQ: dz2 -- LayerNorm: dn2, back through the
+// critic's LayerNorm 2 only, nothing to HBM), d/d(action) with tanh', the actor's dz2 and dz1.  With LayerNorm the kernel
+// stages the actor's pre-LayerNorm rows and statistics (a2, a1: slots 3, 2) from HBM for the two rules.
+void actor_tail(Chain& C, const smx_ddpg_rows_ln& l) {
+    const RArgs& G = C.G;
+    C.emit(step(G.oB, G.ldB, G.c.W3, G.c.b3, A_NONE, -1, 0, G.q_actor, 1, P_A_DQ));
+    C.back_ln2(l.critic.g2, nullptr);
+    C.emit(step(G.oA, G.ldA, G.cW2Thi, nullptr, A_NONE, G.oO2, LDO, nullptr, 0, P_A_TANH));
+    C.back(2, G.oZ, LDK4, G.aW3T, l.actor.g2, G.oB, G.ldB, G.oA, G.ldA, G.dz2a, G.H2, l.dn2a, G.dz2a, 3);
+    C.back(1, G.oA, G.ldA, G.aW2T, l.actor.g1, G.oC, G.ldC, -1, 0, G.dz1a, G.H1, l.dn1a, G.dz1a, 2);
 }
 
-// the 13-step launches' copy of the host's table, field by field: a field added to LnProgT is added HERE too (the assert
-// below fails until its size is entered); dn2_2 is left null on purpose -- the 13-step chains have no second critic
-static_assert(sizeof(LnProg) - sizeof(LnStep) * LN_STEPS_TD3 == 104, "LnProgT's fields behind s[] changed: update narrow()");
+// the three chains (l, l2: NO_LN, NO_LN2 without LayerNorm)
+void critic_chain(Chain& C, const smx_ddpg_rows_ln& l) {
+    target_actor(C, l);
+    target_critic(C, C.G.tc, l.target_critic, P_TC_CAT, C.G.oO2);
+    first_critic(C, l);
+    actor_kept(C, l);
+    if (C.Q) C.Q->t.dn2 = l.dn2;
+}
+static_assert(LN_STEPS >= 13, "the critic chain has 13 layers");
+
+void actor_chain(Chain& C, const smx_ddpg_rows_ln& l) {
+    C.hidden2(C.G.c, l.critic, C.G.oX, C.G.oC, C.G.ldC, P_A_CAT, {}, {});                   // Q(s, mu(s))
+    actor_tail(C, l);
+    if (C.Q) {
+        LnProg& Q = *C.Q;
+        Q.t.a1 = l.a1; Q.t.a2 = l.a2; Q.t.am1 = l.am1; Q.t.ar1 = l.ar1; Q.t.am2 = l.am2; Q.t.ar2 = l.ar2;
+    }
+}
+
+// TD3's critic chain (ddpg.py:266-283, 312-319): both target critics (the second at the noised action), then each
+// critic's forward pass, loss and data gradients against y = min(y1, y2), then the actor's forward pass.  With LayerNorm:
+// the same 20 products, a forward rule behind each of the 12 hidden layers, a backward rule behind each critic's loss and
+// behind its W2^T product -- 16 rules
+void td3_critic_chain(Chain& C, const smx_ddpg_rows_ln& l, const smx_ddpg_rows_ln_second& l2) {
+    target_actor(C, l);
+    target_critic(C, C.G.tc, l.target_critic, P_TC_CAT, C.G.oO2);
+    target_critic(C, C.G.tc2, l2.target_critic2, P_TC2_CAT, C.G.oO3);
+    first_critic(C, l);
+    second_critic(C, l2);
+    actor_kept(C, l);
+    if (C.Q) {
+        C.Q->t.dn2 = l.dn2;
+        C.Q->t.dn2_2 = l2.dn2_2;
+    }
+}
+static_assert(MAX_STEPS >= 20 && LN_STEPS_TD3 >= 20 && LN_STEPS_TD3 <= MAX_STEPS, "the TD3 critic chain has 20 layers");
+
+// the 13-step launches' copy of the host's table (its dn2_2 is null: the 13-step chains have no second critic)
 LnProgT<LN_STEPS> narrow(const LnProg& Q) {
     LnProgT<LN_STEPS> R;
     memset(&R, 0, sizeof(R));
     memcpy(R.s, Q.s, sizeof(R.s));
-    R.eps = Q.eps; R.dn2 = Q.dn2; R.a1 = Q.a1; R.a2 = Q.a2; R.am1 = Q.am1; R.ar1 = Q.ar1; R.am2 = Q.am2; R.ar2 = Q.ar2;
-    R.oP1 = Q.oP1; R.ldP1 = Q.ldP1; R.oP2 = Q.oP2; R.ldP2 = Q.ldP2; R.oD = Q.oD; R.ldD = Q.ldD; R.oM = Q.oM;
+    R.t = Q.t;
     return R;
 }
 
-// TD3's critic chain (ddpg.py:266-283, 312-319): both target critics (the second at the noised action), then each
-// critic's forward pass, loss and data gradients against y = min(y1, y2), then the actor's forward pass
-void td3_critic_program(const RArgs& G, Prog& P) {
-    const int ldc = G.c1 + G.A;
-    int n = 0;
-    P.s[n++] = step(G.oXn, G.ldx, G.ta.W1, G.ta.b1, A_RELU, G.oA, G.ldA, nullptr, 0, P_NONE);         // mu'(s')
-    P.s[n++] = step(G.oA, G.ldA, G.ta.W2, G.ta.b2, A_RELU, G.oB, G.ldB, nullptr, 0, P_NONE);
-    P.s[n++] = step(G.oB, G.ldB, G.ta.W3, G.ta.b3, A_TANH, G.oO, LDO, nullptr, 0, P_NONE);
-    P.s[n++] = step(G.oXn, G.ldx, G.tc.W1, G.tc.b1, A_RELU, G.oC, G.ldC, nullptr, 0, P_TC_CAT);       // Q1'(s', mu'(s'))
-    P.s[n++] = step(G.oC, G.ldC, G.tc.W2, G.tc.b2, A_RELU, G.oB, G.ldB, nullptr, 0, P_NONE);
-    P.s[n++] = step(G.oB, G.ldB, G.tc.W3, G.tc.b3, A_NONE, G.oO2, LDO, nullptr, 0, P_NONE);
-    P.s[n++] = step(G.oXn, G.ldx, G.tc2.W1, G.tc2.b1, A_RELU, G.oC, G.ldC, nullptr, 0, P_TC2_CAT);    // Q2'(s', clamp(mu' + noise))
-    P.s[n++] = step(G.oC, G.ldC, G.tc2.W2, G.tc2.b2, A_RELU, G.oB, G.ldB, nullptr, 0, P_NONE);
-    P.s[n++] = step(G.oB, G.ldB, G.tc2.W3, G.tc2.b3, A_NONE, G.oO3, LDO, nullptr, 0, P_NONE);
-    P.s[n++] = step(G.oX, G.ldx, G.c.W1, G.c.b1, A_RELU, G.oC, G.ldC, G.xcat, ldc, P_C_CAT);          // Q1(s, a)
-    P.s[n++] = step(G.oC, G.ldC, G.c.W2, G.c.b2, A_RELU, G.oB, G.ldB, G.h2c, G.c2, P_NONE);
-    P.s[n++] = step(G.oB, G.ldB, G.c.W3, G.c.b3, A_NONE, G.oO, LDO, nullptr, 0, P_LOSS);              // -> y, dz3, dz2
-    P.s[n] = step(G.oA, G.ldA, G.cW2Tlo, nullptr, A_MASK, -1, 0, G.dxcat, ldc, P_NONE);               // dz1
-    P.s[n].mask_off = G.oC; P.s[n].ldm = G.ldC; ++n;
-    P.s[n++] = step(G.oX, G.ldx, G.c2n.W1, G.c2n.b1, A_RELU, G.oC, G.ldC, G.xcat2, ldc, P_C2_CAT);    // Q2(s, a)
-    P.s[n++] = step(G.oC, G.ldC, G.c2n.W2, G.c2n.b2, A_RELU, G.oB, G.ldB, G.h2c2, G.c2, P_NONE);
-    P.s[n++] = step(G.oB, G.ldB, G.c2n.W3, G.c2n.b3, A_NONE, G.oO, LDO, nullptr, 0, P_LOSS2);         // -> its dz3, dz2 (kept y)
-    P.s[n] = step(G.oA, G.ldA, G.c2W2Tlo, nullptr, A_MASK, -1, 0, G.dxcat2, ldc, P_NONE);
-    P.s[n].mask_off = G.oC; P.s[n].ldm = G.ldC; ++n;
-    P.s[n++] = step(G.oX, G.ldx, G.a.W1, G.a.b1, A_RELU, G.oA, G.ldA, G.h1a, G.H1, P_NONE);           // mu(s), kept
-    P.s[n++] = step(G.oA, G.ldA, G.a.W2, G.a.b2, A_RELU, G.oB, G.ldB, G.h2a, G.H2, P_NONE);
-    P.s[n++] = step(G.oB, G.ldB, G.a.W3, G.a.b3, A_TANH, -1, 0, G.act, G.A, P_NONE);
-    P.n = n;
+// One chain launch, K(G, P) or K(G, P, Q).  A kernel's LDS limit is an attribute of the function, so the high-water mark
+// of what has been asked for is one static per kernel: per instantiation of this template.
+template <auto K, class... LQ>
+int launch_chain(const RArgs& G, const Prog& P, smx_stream_t stream, const LQ&... Q) {
+    const int bytes = G.total * (int)sizeof(float);
+    static int set = 0;
+    if (set < bytes) {
+        const int e = (int)hipFuncSetAttribute((const void*)K, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+        if (e) return e;
+        set = bytes;
+    }
+    hipLaunchKernelGGL(K, dim3((unsigned)((G.rows + RBLK - 1) / RBLK)), dim3(DNTH), bytes, smx_s(stream), G, P, Q...);
+    SMX_LAUNCH_CHECK();
+    return SMX_OK;
 }
-static_assert(MAX_STEPS >= 20, "the TD3 critic chain has 20 layers");
 
-// ... with LayerNorm: the same 20 products, a forward rule behind each of the 12 hidden layers (six networks), a backward
-// rule behind each critic's loss and behind its W2^T product -- 16 rules.
-// Tiles as in critic_program_ln: P1 / P2 hold the pre-LayerNorm rows of the network in flight, statistics slots 0 / 1 its
-// two LayerNorms'; each critic's backward rules run before the next network overwrites them.
-void td3_critic_program_ln(const RArgs& G, const smx_ddpg_rows_ln& l, const smx_ddpg_rows_ln_second& l2, Prog& P, LnProg& Q) {
-    const int ldc = G.c1 + G.A;
-    const int P1 = Q.oP1, l1 = Q.ldP1, P2 = Q.oP2, l2p = Q.ldP2;
-    int n = 0;
-    P.s[n] = step(G.oXn, G.ldx, G.ta.W1, G.ta.b1, A_RELU, P1, l1, nullptr, 0, P_NONE);                // mu'(s')
-    ln_fwd(Q, n, P.s[n], l.target_actor.g1, l.target_actor.b1, G.oA, G.ldA, nullptr, 0, nullptr, nullptr, 0); ++n;
-    P.s[n] = step(G.oA, G.ldA, G.ta.W2, G.ta.b2, A_RELU, P2, l2p, nullptr, 0, P_NONE);
-    ln_fwd(Q, n, P.s[n], l.target_actor.g2, l.target_actor.b2, G.oB, G.ldB, nullptr, 0, nullptr, nullptr, 1); ++n;
-    P.s[n++] = step(G.oB, G.ldB, G.ta.W3, G.ta.b3, A_TANH, G.oO, LDO, nullptr, 0, P_NONE);
-    P.s[n] = step(G.oXn, G.ldx, G.tc.W1, G.tc.b1, A_RELU, P1, l1, nullptr, 0, P_TC_CAT);              // Q1'(s', mu'(s'))
-    ln_fwd(Q, n, P.s[n], l.target_critic.g1, l.target_critic.b1, G.oC, G.ldC, nullptr, 0, nullptr, nullptr, 0); ++n;
-    P.s[n] = step(G.oC, G.ldC, G.tc.W2, G.tc.b2, A_RELU, P2, l2p, nullptr, 0, P_NONE);
-    ln_fwd(Q, n, P.s[n], l.target_critic.g2, l.target_critic.b2, G.oB, G.ldB, nullptr, 0, nullptr, nullptr, 1); ++n;
-    P.s[n++] = step(G.oB, G.ldB, G.tc.W3, G.tc.b3, A_NONE, G.oO2, LDO, nullptr, 0, P_NONE);
-    P.s[n] = step(G.oXn, G.ldx, G.tc2.W1, G.tc2.b1, A_RELU, P1, l1, nullptr, 0, P_TC2_CAT);           // Q2'(s', clamp(mu' + noise))
-    ln_fwd(Q, n, P.s[n], l2.target_critic2.g1, l2.target_critic2.b1, G.oC, G.ldC, nullptr, 0, nullptr, nullptr, 0); ++n;
-    P.s[n] = step(G.oC, G.ldC, G.tc2.W2, G.tc2.b2, A_RELU, P2, l2p, nullptr, 0, P_NONE);
-    ln_fwd(Q, n, P.s[n], l2.target_critic2.g2, l2.target_critic2.b2, G.oB, G.ldB, nullptr, 0, nullptr, nullptr, 1); ++n;
-    P.s[n++] = step(G.oB, G.ldB, G.tc2.W3, G.tc2.b3, A_NONE, G.oO3, LDO, nullptr, 0, P_NONE);
-    P.s[n] = step(G.oX, G.ldx, G.c.W1, G.c.b1, A_RELU, P1, l1, l.c_a1, G.c1, P_C_CAT);                // Q1(s, a)
-    ln_fwd(Q, n, P.s[n], l.critic.g1, l.critic.b1, G.oC, G.ldC, G.xcat, ldc, l.cm1, l.cr1, 0); ++n;
-    P.s[n] = step(G.oC, G.ldC, G.c.W2, G.c.b2, A_RELU, P2, l2p, l.c_a2, G.c2, P_NONE);
-    ln_fwd(Q, n, P.s[n], l.critic.g2, l.critic.b2, G.oB, G.ldB, G.h2c, G.c2, l.cm2, l.cr2, 1); ++n;
-    P.s[n] = step(G.oB, G.ldB, G.c.W3, G.c.b3, A_NONE, G.oO, LDO, nullptr, 0, P_LOSS);                // -> y, dz3, dn2
-    ln_bwd(Q, n, G.c2, l.critic.g2, P2, l2p, G.oA, G.ldA, G.dz2, G.c2, 1); ++n;                       // -> dz2
-    P.s[n] = step(G.oA, G.ldA, G.cW2Tlo, nullptr, A_NONE, Q.oD, Q.ldD, G.dxcat, ldc, P_NONE);         // dn1
-    ln_bwd(Q, n, G.c1, l.critic.g1, P1, l1, -1, 0, l.dz1c, G.c1, 0); ++n;                             // -> dz1
-    P.s[n] = step(G.oX, G.ldx, G.c2n.W1, G.c2n.b1, A_RELU, P1, l1, l2.c2_a1, G.c1, P_C2_CAT);         // Q2(s, a)
-    ln_fwd(Q, n, P.s[n], l2.critic2.g1, l2.critic2.b1, G.oC, G.ldC, G.xcat2, ldc, l2.c2m1, l2.c2r1, 0); ++n;
-    P.s[n] = step(G.oC, G.ldC, G.c2n.W2, G.c2n.b2, A_RELU, P2, l2p, l2.c2_a2, G.c2, P_NONE);
-    ln_fwd(Q, n, P.s[n], l2.critic2.g2, l2.critic2.b2, G.oB, G.ldB, G.h2c2, G.c2, l2.c2m2, l2.c2r2, 1); ++n;
-    P.s[n] = step(G.oB, G.ldB, G.c2n.W3, G.c2n.b3, A_NONE, G.oO, LDO, nullptr, 0, P_LOSS2);           // -> its dz3, dn2 (kept y)
-    ln_bwd(Q, n, G.c2, l2.critic2.g2, P2, l2p, G.oA, G.ldA, G.dz2_2, G.c2, 1); ++n;
-    P.s[n] = step(G.oA, G.ldA, G.c2W2Tlo, nullptr, A_NONE, Q.oD, Q.ldD, G.dxcat2, ldc, P_NONE);
-    ln_bwd(Q, n, G.c1, l2.critic2.g1, P1, l1, -1, 0, l2.dz1c2, G.c1, 0); ++n;
-    P.s[n] = step(G.oX, G.ldx, G.a.W1, G.a.b1, A_RELU, P1, l1, l.a1, G.H1, P_NONE);                   // mu(s), kept
-    ln_fwd(Q, n, P.s[n], l.actor.g1, l.actor.b1, G.oA, G.ldA, G.h1a, G.H1, l.am1, l.ar1, 0); ++n;
-    P.s[n] = step(G.oA, G.ldA, G.a.W2, G.a.b2, A_RELU, P2, l2p, l.a2, G.H2, P_NONE);
-    ln_fwd(Q, n, P.s[n], l.actor.g2, l.actor.b2, G.oB, G.ldB, G.h2a, G.H2, l.am2, l.ar2, 1); ++n;
-    P.s[n++] = step(G.oB, G.ldB, G.a.W3, G.a.b3, A_TANH, -1, 0, G.act, G.A, P_NONE);
-    P.n = n;
-    Q.dn2 = l.dn2;
-    Q.dn2_2 = l2.dn2_2;
+// The LayerNorm chains' launches by phase (0: critic, 1: actor, 2: TD3's critic).  Only TD3's kernel takes the 20-step rule
+// table; the other two take its narrow() copy
+int launch_chain_ln(int phase, const RArgs& G, const Prog& P, const LnProg& Q, smx_stream_t stream) {
+    switch (phase) {
+        case 0: return launch_chain<ddpg_rows4_ln_kernel<0>>(G, P, stream, narrow(Q));
+        case 1: return launch_chain<ddpg_rows4_ln_kernel<1>>(G, P, stream, narrow(Q));
+        default: return launch_chain<ddpg_rows4_ln_kernel<2>>(G, P, stream, Q);
+    }
 }
-static_assert(LN_STEPS_TD3 >= 20 && LN_STEPS_TD3 <= MAX_STEPS, "the LayerNorm TD3 critic chain has 20 layers");
 
-int set_lds(const void* fn, int bytes) {
-    return (int)hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+// the buffers the critic chains read and write; those they write with LayerNorm
+bool critic_io(const smx_ddpg_rows_t* a) {
+    return a->x && a->x_next && a->actions && a->rewards && a->dones && a->xcat && a->h2c && a->q && a->q_next && a->y &&
+           a->dz3 && a->dz2 && a->dxcat && a->h1a && a->h2a && a->act;
+}
+bool critic_io_ln(const smx_ddpg_rows_ln& l) {
+    return l.c_a1 && l.cm1 && l.cr1 && l.c_a2 && l.cm2 && l.cr2 && l.dn2 && l.dz1c && l.a1 && l.am1 && l.ar1 && l.a2 && l.am2 &&
+           l.ar2;
+}
+
+int launch_pack(const float* const* src, const int* ld, const int* tr, int first, int last, const Layout& L, const Dims& d,
+                float* packed, smx_stream_t stream) {
+    PArgs P;
+    memset(&P, 0, sizeof(P));
+    P.packed = packed;
+    P.count = last - first;
+    for (int b = first; b < last; ++b) {
+        SMX_REQUIRE(src[b], SMX_E_NULL);
+        PItem& it = P.it[b - first];
+        it.src = src[b]; it.ld = ld[b]; it.tr = tr[b];
+        L.shape(d, b, it.M, it.K);
+        it.base = L.base(d, b);
+    }
+    P.total = L.base(d, last) - L.base(d, first);
+    hipLaunchKernelGGL(ddpg_pack_kernel, dim3((unsigned)((P.total + 255) / 256)), dim3(256), 0, smx_s(stream), P);
+    SMX_LAUNCH_CHECK();
+    return SMX_OK;
 }
 
 }  // namespace
@@ -1500,175 +1500,68 @@ int set_lds(const void* fn, int bytes) {
 extern "C" void smx_ddpg_rows_debug_tbuf(void* p) { g_tbuf = (long long*)p; }
 
 extern "C" int32_t smx_ddpg_rows_supported(int32_t D, int32_t A, int32_t H1, int32_t H2, int32_t c1, int32_t c2) {
-    Dims d;
-    d.D = D; d.A = A; d.H1 = H1; d.H2 = H2; d.c1 = c1; d.c2 = c2;
-    return dims_ok(d) ? 1 : 0;
+    return dims_ok(Dims{D, A, H1, H2, c1, c2}) ? 1 : 0;
 }
 
 extern "C" int32_t smx_ddpg_rows_supported_at(int32_t D, int32_t A, int32_t H1, int32_t H2, int32_t c1, int32_t c2,
                                               int64_t rows) {
-    Dims d;
-    d.D = D; d.A = A; d.H1 = H1; d.H2 = H2; d.c1 = c1; d.c2 = c2;
-    return rows > 0 && rows < (1 << 24) && dims_ok(d) ? 1 : 0;
+    return rows_ok(rows) && dims_ok(Dims{D, A, H1, H2, c1, c2}) ? 1 : 0;
 }
 
 extern "C" int64_t smx_ddpg_rows_packed_floats(int32_t D, int32_t A, int32_t H1, int32_t H2, int32_t c1, int32_t c2) {
-    Dims d;
-    d.D = D; d.A = A; d.H1 = H1; d.H2 = H2; d.c1 = c1; d.c2 = c2;
-    return dims_ok(d) ? 4 * block_base(d, B_COUNT) : 0;
+    const Dims d{D, A, H1, H2, c1, c2};
+    return dims_ok(d) ? 4 * L_FIRST.base(d, B_COUNT) : 0;
 }
 
 extern "C" int32_t smx_ddpg_rows_second_supported(int32_t D, int32_t A, int32_t H1, int32_t H2, int32_t c1, int32_t c2,
                                                   int64_t rows) {
-    Dims d;
-    d.D = D; d.A = A; d.H1 = H1; d.H2 = H2; d.c1 = c1; d.c2 = c2;
-    return rows > 0 && rows < (1 << 24) && dims_ok(d, true) && offsets_ok(d, rows) ? 1 : 0;
+    const Dims d{D, A, H1, H2, c1, c2};
+    return rows_ok(rows) && dims_ok(d, true) && offsets_ok(d, rows, true) ? 1 : 0;
 }
 
 extern "C" int32_t smx_ddpg_rows_ln_supported(int32_t D, int32_t A, int32_t H1, int32_t H2, int32_t c1, int32_t c2,
                                               int64_t rows) {
-    Dims d;
-    d.D = D; d.A = A; d.H1 = H1; d.H2 = H2; d.c1 = c1; d.c2 = c2;
-    return smx_ddpg_rows_supported_at(D, A, H1, H2, c1, c2, rows) && dims_ok_ln(d) && offsets_ok(d, rows) ? 1 : 0;
+    const Dims d{D, A, H1, H2, c1, c2};
+    return rows_ok(rows) && dims_ok_ln(d) && offsets_ok(d, rows, true) ? 1 : 0;
 }
 
 extern "C" int32_t smx_ddpg_rows_ln_second_supported(int32_t D, int32_t A, int32_t H1, int32_t H2, int32_t c1, int32_t c2,
                                                      int64_t rows) {
-    Dims d;
-    d.D = D; d.A = A; d.H1 = H1; d.H2 = H2; d.c1 = c1; d.c2 = c2;
-    return smx_ddpg_rows_ln_supported(D, A, H1, H2, c1, c2, rows) && dims_ok_ln(d, true) ? 1 : 0;
+    return smx_ddpg_rows_ln_supported(D, A, H1, H2, c1, c2, rows) && dims_ok_ln(Dims{D, A, H1, H2, c1, c2}, true) ? 1 : 0;
 }
 
 extern "C" int64_t smx_ddpg_rows_second_packed_floats(int32_t D, int32_t A, int32_t H1, int32_t H2, int32_t c1, int32_t c2) {
-    Dims d;
-    d.D = D; d.A = A; d.H1 = H1; d.H2 = H2; d.c1 = c1; d.c2 = c2;
-    return dims_ok(d, true) ? 4 * block2_base(d, B2_COUNT) : 0;
+    const Dims d{D, A, H1, H2, c1, c2};
+    return dims_ok(d, true) ? 4 * L_SECOND.base(d, B2_COUNT) : 0;
 }
-
-namespace {
-// the second critic's seven blocks into ITS packed buffer
-int pack_second(const smx_ddpg_rows_t* a, const Dims& d, smx_stream_t stream) {
-    const smx_ddpg_rows_second* s = a->second;
-    SMX_REQUIRE(s && s->packed2, SMX_E_NULL);
-    SMX_REQUIRE(dims_ok(d, true), SMX_E_UNSUPPORTED);
-    SMX_REQUIRE(((uintptr_t)s->packed2 & 15) == 0, SMX_E_ALIGN);
-    const int ldc = d.c1 + d.A;
-    const float* src[B2_COUNT] = {s->critic2.W1, s->critic2.W2, s->critic2.W3, s->critic2.W2,
-                                  s->target_critic2.W1, s->target_critic2.W2, s->target_critic2.W3};
-    const int ld[B2_COUNT] = {d.D, ldc, d.c2, ldc, d.D, ldc, d.c2};
-    const int tr[B2_COUNT] = {0, 0, 0, 1, 0, 0, 0};
-    PArgs P;
-    memset(&P, 0, sizeof(P));
-    P.packed = s->packed2;
-    P.count = B2_COUNT;
-    for (int b = 0; b < B2_COUNT; ++b) {
-        SMX_REQUIRE(src[b], SMX_E_NULL);
-        PItem& it = P.it[b];
-        it.src = src[b]; it.ld = ld[b]; it.tr = tr[b];
-        block_shape(d, second_as_first[b], it.M, it.K);
-        it.base = block2_base(d, b);
-    }
-    P.total = block2_base(d, B2_COUNT);
-    hipLaunchKernelGGL(ddpg_pack_kernel, dim3((unsigned)((P.total + 255) / 256)), dim3(256), 0, smx_s(stream), P);
-    SMX_LAUNCH_CHECK();
-    return SMX_OK;
-}
-}  // namespace
 
 extern "C" int smx_ddpg_rows_pack_f32(const smx_ddpg_rows_t* a, int32_t which, smx_stream_t stream) {
     SMX_REQUIRE(a && a->packed, SMX_E_NULL);
     const Dims d = dims_of(*a);
     SMX_REQUIRE(dims_ok(d), SMX_E_UNSUPPORTED);
     SMX_REQUIRE(!a->ln || ln_second(a) || (!a->second && which != SMX_DDPG_PACK_SECOND), SMX_E_UNSUPPORTED);
-    if (which == SMX_DDPG_PACK_SECOND) return pack_second(a, d, stream);
-    SMX_REQUIRE(which == SMX_DDPG_PACK_ALL || which == SMX_DDPG_PACK_CRITIC, SMX_E_SHAPE);
     const int ldc = d.c1 + d.A;
+    if (which == SMX_DDPG_PACK_SECOND) {             // the second critic's seven blocks into ITS packed buffer
+        const smx_ddpg_rows_second* s = a->second;
+        SMX_REQUIRE(s && s->packed2, SMX_E_NULL);
+        SMX_REQUIRE(dims_ok(d, true), SMX_E_UNSUPPORTED);
+        SMX_REQUIRE(((uintptr_t)s->packed2 & 15) == 0, SMX_E_ALIGN);
+        const float* src[B2_COUNT] = {s->critic2.W1, s->critic2.W2, s->critic2.W3, s->critic2.W2,
+                                      s->target_critic2.W1, s->target_critic2.W2, s->target_critic2.W3};
+        const int ld[B2_COUNT] = {d.D, ldc, d.c2, ldc, d.D, ldc, d.c2};
+        const int tr[B2_COUNT] = {0, 0, 0, 1, 0, 0, 0};
+        return launch_pack(src, ld, tr, 0, B2_COUNT, L_SECOND, d, s->packed2, stream);
+    }
+    SMX_REQUIRE(which == SMX_DDPG_PACK_ALL || which == SMX_DDPG_PACK_CRITIC, SMX_E_SHAPE);
     const float* src[B_COUNT] = {a->actor.W1, a->actor.W2, a->actor.W3, a->actor.W3, a->actor.W2,
-                                 a->critic.W1, a->critic.W2, a->critic.W3, a->critic.W2, a->critic.W2 + d.c1,
+                                 a->critic.W1, a->critic.W2, a->critic.W3, a->critic.W2, a->critic.W2 ? a->critic.W2 + d.c1 : nullptr,
                                  a->target_actor.W1, a->target_actor.W2, a->target_actor.W3,
                                  a->target_critic.W1, a->target_critic.W2, a->target_critic.W3};
     const int ld[B_COUNT] = {d.D, d.H1, d.H2, d.H2, d.H1, d.D, ldc, d.c2, ldc, ldc, d.D, d.H1, d.H2, d.D, ldc, d.c2};
     const int tr[B_COUNT] = {0, 0, 0, 1, 1, 0, 0, 0, 1, 1, 0, 0, 0, 0, 0, 0};
-    const int b0 = which == SMX_DDPG_PACK_CRITIC ? B_CW1 : 0, b1 = which == SMX_DDPG_PACK_CRITIC ? B_CW2THI + 1 : B_COUNT;
-    PArgs P;
-    memset(&P, 0, sizeof(P));
-    P.packed = a->packed;
-    P.count = b1 - b0;
-    for (int b = b0; b < b1; ++b) {
-        SMX_REQUIRE(src[b], SMX_E_NULL);
-        PItem& it = P.it[b - b0];
-        it.src = src[b]; it.ld = ld[b]; it.tr = tr[b];
-        block_shape(d, b, it.M, it.K);
-        it.base = block_base(d, b);
-    }
-    P.total = block_base(d, b1) - block_base(d, b0);
-    hipLaunchKernelGGL(ddpg_pack_kernel, dim3((unsigned)((P.total + 255) / 256)), dim3(256), 0, smx_s(stream), P);
-    SMX_LAUNCH_CHECK();
-    return SMX_OK;
+    const bool cr = which == SMX_DDPG_PACK_CRITIC;
+    return launch_pack(src, ld, tr, cr ? B_CW1 : 0, cr ? B_CW2THI + 1 : B_COUNT, L_FIRST, d, a->packed, stream);
 }
-
-namespace {
-int launch_critic_ln(const smx_ddpg_rows_t* a, RArgs& G, LnProg& Q, smx_stream_t stream) {
-    const smx_ddpg_rows_ln& l = *a->ln;
-    SMX_REQUIRE(l.c_a1 && l.cm1 && l.cr1 && l.c_a2 && l.cm2 && l.cr2 && l.dn2 && l.dz1c && l.a1 && l.am1 && l.ar1 && l.a2 &&
-                    l.am2 && l.ar2, SMX_E_NULL);
-    const int bytes = G.total * (int)sizeof(float);
-    static int set = 0;
-    if (set < bytes) {
-        const int e = set_lds((const void*)ddpg_rows4_ln_kernel<0>, bytes);
-        if (e) return e;
-        set = bytes;
-    }
-    Prog P;
-    memset(&P, 0, sizeof(P));
-    critic_program_ln(G, l, P, Q);
-    hipLaunchKernelGGL(ddpg_rows4_ln_kernel<0>, dim3((unsigned)((G.rows + RBLK - 1) / RBLK)), dim3(DNTH), bytes, smx_s(stream),
-                       G, P, narrow(Q));
-    SMX_LAUNCH_CHECK();
-    return SMX_OK;
-}
-
-int launch_actor_ln(const smx_ddpg_rows_t* a, RArgs& G, LnProg& Q, smx_stream_t stream) {
-    const smx_ddpg_rows_ln& l = *a->ln;
-    SMX_REQUIRE(l.a1 && l.am1 && l.ar1 && l.a2 && l.am2 && l.ar2 && l.dn2a && l.dn1a, SMX_E_NULL);
-    const int bytes = G.total * (int)sizeof(float);
-    static int set = 0;
-    if (set < bytes) {
-        const int e = set_lds((const void*)ddpg_rows4_ln_kernel<1>, bytes);
-        if (e) return e;
-        set = bytes;
-    }
-    Prog P;
-    memset(&P, 0, sizeof(P));
-    actor_program_ln(G, l, P, Q);
-    hipLaunchKernelGGL(ddpg_rows4_ln_kernel<1>, dim3((unsigned)((G.rows + RBLK - 1) / RBLK)), dim3(DNTH), bytes, smx_s(stream),
-                       G, P, narrow(Q));
-    SMX_LAUNCH_CHECK();
-    return SMX_OK;
-}
-
-int launch_critic_td3_ln(const smx_ddpg_rows_t* a, RArgs& G, LnProg& Q, smx_stream_t stream) {
-    const smx_ddpg_rows_ln& l = *a->ln;
-    const smx_ddpg_rows_ln_second& l2 = *l.second;
-    SMX_REQUIRE(l.c_a1 && l.cm1 && l.cr1 && l.c_a2 && l.cm2 && l.cr2 && l.dn2 && l.dz1c && l.a1 && l.am1 && l.ar1 && l.a2 &&
-                    l.am2 && l.ar2, SMX_E_NULL);
-    SMX_REQUIRE(l2.c2_a1 && l2.c2m1 && l2.c2r1 && l2.c2_a2 && l2.c2m2 && l2.c2r2 && l2.dn2_2 && l2.dz1c2, SMX_E_NULL);
-    const int bytes = G.total * (int)sizeof(float);
-    static int set = 0;
-    if (set < bytes) {
-        const int e = set_lds((const void*)ddpg_rows4_ln_kernel<2>, bytes);
-        if (e) return e;
-        set = bytes;
-    }
-    Prog P;
-    memset(&P, 0, sizeof(P));
-    td3_critic_program_ln(G, l, l2, P, Q);
-    hipLaunchKernelGGL(ddpg_rows4_ln_kernel<2>, dim3((unsigned)((G.rows + RBLK - 1) / RBLK)), dim3(DNTH), bytes, smx_s(stream),
-                       G, P, Q);
-    SMX_LAUNCH_CHECK();
-    return SMX_OK;
-}
-}  // namespace
 
 extern "C" int smx_ddpg_rows_critic_f32(const smx_ddpg_rows_t* a, smx_stream_t stream) {
     RArgs G;
@@ -1676,23 +1569,13 @@ extern "C" int smx_ddpg_rows_critic_f32(const smx_ddpg_rows_t* a, smx_stream_t s
     SMX_REQUIRE(!(a && a->ln && a->second), SMX_E_UNSUPPORTED);      // (two LayerNorm critics: smx_ddpg_rows_critic_td3_f32)
     const int rc = fill(G, a, false, &Q);
     if (rc) return rc;
-    SMX_REQUIRE(a->x && a->x_next && a->actions && a->rewards && a->dones, SMX_E_NULL);
-    SMX_REQUIRE(a->xcat && a->h2c && a->q && a->q_next && a->y && a->dz3 && a->dz2 && a->dxcat && a->h1a && a->h2a &&
-                    a->act, SMX_E_NULL);
-    if (a->ln) return launch_critic_ln(a, G, Q, stream);
-    const int bytes = G.total * (int)sizeof(float);
-    static int set = 0;
-    if (set < bytes) {
-        const int e = set_lds((const void*)ddpg_rows4_kernel<0>, bytes);
-        if (e) return e;
-        set = bytes;
-    }
+    SMX_REQUIRE(critic_io(a), SMX_E_NULL);
+    SMX_REQUIRE(!a->ln || critic_io_ln(*a->ln), SMX_E_NULL);
     Prog P;
     memset(&P, 0, sizeof(P));
-    critic_program(G, P);
-    hipLaunchKernelGGL(ddpg_rows4_kernel<0>, dim3((unsigned)((G.rows + RBLK - 1) / RBLK)), dim3(DNTH), bytes, smx_s(stream), G, P);
-    SMX_LAUNCH_CHECK();
-    return SMX_OK;
+    Chain C{G, P, a->ln ? &Q : nullptr, 0};
+    critic_chain(C, a->ln ? *a->ln : NO_LN);
+    return a->ln ? launch_chain_ln(0, G, P, Q, stream) : launch_chain<ddpg_rows4_kernel<0>>(G, P, stream);
 }
 
 extern "C" int smx_ddpg_rows_critic_td3_f32(const smx_ddpg_rows_t* a, smx_stream_t stream) {
@@ -1701,24 +1584,17 @@ extern "C" int smx_ddpg_rows_critic_td3_f32(const smx_ddpg_rows_t* a, smx_stream
     const int rc = fill(G, a, true, &Q);
     if (rc) return rc;
     const smx_ddpg_rows_second* s = a->second;
-    SMX_REQUIRE(a->x && a->x_next && a->actions && a->rewards && a->dones, SMX_E_NULL);
-    SMX_REQUIRE(a->xcat && a->h2c && a->q && a->q_next && a->y && a->dz3 && a->dz2 && a->dxcat && a->h1a && a->h2a &&
-                    a->act, SMX_E_NULL);
+    SMX_REQUIRE(critic_io(a), SMX_E_NULL);
     SMX_REQUIRE(s->xcat2 && s->h2c2 && s->q2 && s->q_next2 && s->dz3_2 && s->dz2_2 && s->dxcat2, SMX_E_NULL);
-    if (a->ln) return launch_critic_td3_ln(a, G, Q, stream);
-    const int bytes = G.total * (int)sizeof(float);
-    static int set = 0;
-    if (set < bytes) {
-        const int e = set_lds((const void*)ddpg_rows4_kernel<2>, bytes);
-        if (e) return e;
-        set = bytes;
-    }
+    const smx_ddpg_rows_ln_second* l2 = a->ln ? a->ln->second : nullptr;     // (fill: there beside `second`)
+    SMX_REQUIRE(!a->ln || critic_io_ln(*a->ln), SMX_E_NULL);
+    SMX_REQUIRE(!l2 || (l2->c2_a1 && l2->c2m1 && l2->c2r1 && l2->c2_a2 && l2->c2m2 && l2->c2r2 && l2->dn2_2 && l2->dz1c2),
+                SMX_E_NULL);
     Prog P;
     memset(&P, 0, sizeof(P));
-    td3_critic_program(G, P);
-    hipLaunchKernelGGL(ddpg_rows4_kernel<2>, dim3((unsigned)((G.rows + RBLK - 1) / RBLK)), dim3(DNTH), bytes, smx_s(stream), G, P);
-    SMX_LAUNCH_CHECK();
-    return SMX_OK;
+    Chain C{G, P, a->ln ? &Q : nullptr, 0};
+    td3_critic_chain(C, a->ln ? *a->ln : NO_LN, l2 ? *l2 : NO_LN2);
+    return a->ln ? launch_chain_ln(2, G, P, Q, stream) : launch_chain<ddpg_rows4_kernel<2>>(G, P, stream);
 }
 
 extern "C" int smx_ddpg_rows_actor_f32(const smx_ddpg_rows_t* a, smx_stream_t stream) {
@@ -1727,89 +1603,82 @@ extern "C" int smx_ddpg_rows_actor_f32(const smx_ddpg_rows_t* a, smx_stream_t st
     const int rc = fill(G, a, false, &Q);
     if (rc) return rc;
     SMX_REQUIRE(a->x && a->h1a && a->h2a && a->act && a->q_actor && a->dz3a && a->dz2a && a->dz1a, SMX_E_NULL);
-    if (a->ln) return launch_actor_ln(a, G, Q, stream);
-    const int bytes = G.total * (int)sizeof(float);
-    static int set = 0;
-    if (set < bytes) {
-        const int e = set_lds((const void*)ddpg_rows4_kernel<1>, bytes);
-        if (e) return e;
-        set = bytes;
-    }
+    const smx_ddpg_rows_ln* l = a->ln;
+    SMX_REQUIRE(!l || (l->a1 && l->am1 && l->ar1 && l->a2 && l->am2 && l->ar2 && l->dn2a && l->dn1a), SMX_E_NULL);
     Prog P;
     memset(&P, 0, sizeof(P));
-    actor_program(G, P);
-    hipLaunchKernelGGL(ddpg_rows4_kernel<1>, dim3((unsigned)((G.rows + RBLK - 1) / RBLK)), dim3(DNTH), bytes, smx_s(stream), G, P);
-    SMX_LAUNCH_CHECK();
-    return SMX_OK;
+    Chain C{G, P, l ? &Q : nullptr, 0};
+    actor_chain(C, l ? *l : NO_LN);
+    return l ? launch_chain_ln(1, G, P, Q, stream) : launch_chain<ddpg_rows4_kernel<1>>(G, P, stream);
 }
 
 namespace {
+// An optimiser group's side of the packed buffers: its network and target, the buffer and its layout, the blocks of W1, W2,
+// W3, of the target's, and of the transposed copies (< 0: none; columns < split -> t0, the rest -> t1)
+struct UGroup {
+    const smx_ddpg_net_t *net, *tnet;
+    float* packed;
+    const Layout* L;
+    int w[3], tw[3], t0[3], t1[3];
+    bool split_w2;                // a critic's W2: the columns of layer 1's output apart from the action's
+};
+
 int fill_update(UArgs& U, const smx_ddpg_rows_t* a, int32_t group, const smx_ddpg_update_t* u, const Dims& d) {
     SMX_REQUIRE(u->theta && u->grads && u->exp_avg && u->exp_avg_sq && u->lr && u->step, SMX_E_NULL);
     SMX_REQUIRE(group == SMX_DDPG_GROUP_ACTOR || group == SMX_DDPG_GROUP_CRITIC || group == SMX_DDPG_GROUP_CRITIC2,
                 SMX_E_SHAPE);
     SMX_REQUIRE(u->n > 0 && u->interval >= 0 && (u->target == nullptr || u->interval > 0 || u->tau > 0.f), SMX_E_SHAPE);
+    const smx_ddpg_rows_second* s = a->second;
     if (group == SMX_DDPG_GROUP_CRITIC2) {
-        // the second critic: its own networks and packed buffer, the first critic's shapes; W2^T's low block only
-        const smx_ddpg_rows_second* s = a->second;
         SMX_REQUIRE(s && s->packed2, SMX_E_NULL);
         SMX_REQUIRE(dims_ok(d, true), SMX_E_UNSUPPORTED);
-        SMX_REQUIRE(s->critic2.W1 && s->critic2.W2 && s->critic2.W3, SMX_E_NULL);
-        memset(&U, 0, sizeof(U));
-        U.theta = u->theta; U.grads = u->grads; U.m = u->exp_avg; U.v = u->exp_avg_sq; U.target = u->target;
-        U.packed = s->packed2; U.n = u->n; U.lr = u->lr; U.step = u->step; U.wd = u->weight_decay;
-        U.clip_value = u->clip_value; U.tau = u->tau; U.interval = u->interval;
-        const float* W[3] = {s->critic2.W1, s->critic2.W2, s->critic2.W3};
-        const float* TW[3] = {s->target_critic2.W1, s->target_critic2.W2, s->target_critic2.W3};
-        for (int j = 0; j < 3; ++j) {
-            UMat& X = U.mat[j];
-            block_shape(d, second_as_first[B2_CW1 + j], X.M, X.K);
-            X.off = W[j] - u->theta;
-            SMX_REQUIRE(X.off >= 0 && X.off + (long)X.M * X.K <= u->n, SMX_E_SHAPE);
-            if (u->target) SMX_REQUIRE(TW[j] && TW[j] - u->target == X.off, SMX_E_SHAPE);
-            X.base = 4 * block2_base(d, B2_CW1 + j);
-            X.base_tgt = 4 * block2_base(d, B2_TCW1 + j);
-            X.base_t0 = X.base_t1 = -1;
-            X.split = X.K;
-        }
-        U.mat[1].base_t0 = 4 * block2_base(d, B2_CW2TLO);
-        U.mat[1].split = d.c1;
-        return SMX_OK;
     }
-    const bool cr = group == SMX_DDPG_GROUP_CRITIC;
-    const smx_ddpg_net_t& net = cr ? a->critic : a->actor;
-    const smx_ddpg_net_t& tnet = cr ? a->target_critic : a->target_actor;
-    SMX_REQUIRE(net.W1 && net.W2 && net.W3, SMX_E_NULL);
+    // the second critic: its own networks and packed buffer, the first critic's shapes; W2^T's low block only
+    const UGroup g =
+        group == SMX_DDPG_GROUP_CRITIC2
+            ? UGroup{&s->critic2, &s->target_critic2, s->packed2, &L_SECOND, {B2_CW1, B2_CW2, B2_CW3},
+                     {B2_TCW1, B2_TCW2, B2_TCW3}, {-1, B2_CW2TLO, -1}, {-1, -1, -1}, true}
+        : group == SMX_DDPG_GROUP_CRITIC
+            ? UGroup{&a->critic, &a->target_critic, a->packed, &L_FIRST, {B_CW1, B_CW2, B_CW3}, {B_TCW1, B_TCW2, B_TCW3},
+                     {-1, B_CW2TLO, -1}, {-1, B_CW2THI, -1}, true}
+            : UGroup{&a->actor, &a->target_actor, a->packed, &L_FIRST, {B_AW1, B_AW2, B_AW3}, {B_TAW1, B_TAW2, B_TAW3},
+                     {-1, B_AW2T, B_AW3T}, {-1, -1, -1}, false};
+    SMX_REQUIRE(g.net->W1 && g.net->W2 && g.net->W3, SMX_E_NULL);
     memset(&U, 0, sizeof(U));
     U.theta = u->theta; U.grads = u->grads; U.m = u->exp_avg; U.v = u->exp_avg_sq; U.target = u->target;
-    U.packed = a->packed; U.n = u->n; U.lr = u->lr; U.step = u->step; U.wd = u->weight_decay;
+    U.packed = g.packed; U.n = u->n; U.lr = u->lr; U.step = u->step; U.wd = u->weight_decay;
     U.clip_value = u->clip_value; U.tau = u->tau; U.interval = u->interval;
-    const float* W[3] = {net.W1, net.W2, net.W3};
-    const float* TW[3] = {tnet.W1, tnet.W2, tnet.W3};
-    const int blk[3] = {cr ? B_CW1 : B_AW1, cr ? B_CW2 : B_AW2, cr ? B_CW3 : B_AW3};
-    const int tblk[3] = {cr ? B_TCW1 : B_TAW1, cr ? B_TCW2 : B_TAW2, cr ? B_TCW3 : B_TAW3};
+    const float* W[3] = {g.net->W1, g.net->W2, g.net->W3};
+    const float* TW[3] = {g.tnet->W1, g.tnet->W2, g.tnet->W3};
     for (int j = 0; j < 3; ++j) {
         UMat& X = U.mat[j];
-        block_shape(d, blk[j], X.M, X.K);
+        g.L->shape(d, g.w[j], X.M, X.K);
         X.off = W[j] - u->theta;
         // the matrices lie inside the group's buffer, the target's at the same offsets inside the target's
         SMX_REQUIRE(X.off >= 0 && X.off + (long)X.M * X.K <= u->n, SMX_E_SHAPE);
         if (u->target) SMX_REQUIRE(TW[j] && TW[j] - u->target == X.off, SMX_E_SHAPE);
-        X.base = 4 * block_base(d, blk[j]);
-        X.base_tgt = 4 * block_base(d, tblk[j]);
-        X.base_t0 = X.base_t1 = -1;
-        X.split = X.K;
-    }
-    if (cr) {
-        U.mat[1].base_t0 = 4 * block_base(d, B_CW2TLO);
-        U.mat[1].base_t1 = 4 * block_base(d, B_CW2THI);
-        U.mat[1].split = d.c1;
-    } else {
-        U.mat[1].base_t0 = 4 * block_base(d, B_AW2T);
-        U.mat[2].base_t0 = 4 * block_base(d, B_AW3T);
+        X.base = 4 * g.L->base(d, g.w[j]);
+        X.base_tgt = 4 * g.L->base(d, g.tw[j]);
+        X.base_t0 = g.t0[j] < 0 ? -1 : 4 * g.L->base(d, g.t0[j]);
+        X.base_t1 = g.t1[j] < 0 ? -1 : 4 * g.L->base(d, g.t1[j]);
+        X.split = g.split_w2 && j == 1 ? d.c1 : X.K;
     }
     return SMX_OK;
 }
+
+// What a group's gradient-and-step launch reads: (gradient, input) of the three layers -- the buffers the chain launches
+// wrote -- and the networks; with LayerNorm (dn, pre-LayerNorm rows, statistics) of the two LayerNorms and their parameters.
+// LayerNorm: a critic's dz1 is a buffer of its own, dxcat keeps dn1; xcat / h2c / h1a / h2a are the LayerNorm outputs
+struct WIo {
+    const float* dz[3];
+    int ldz[3];
+    const float* x[3];
+    int ldx[3];
+    const smx_ddpg_net_t *net, *tnet;
+    const float *dn[2], *pre[2], *mean[2], *rstd[2];
+    int F[2], lddn[2];
+    const smx_ddpg_ln_net *p, *tp;
+};
 }  // namespace
 
 extern "C" int smx_ddpg_rows_update_f32(const smx_ddpg_rows_t* a, int32_t group, const smx_ddpg_update_t* u,
@@ -1831,12 +1700,11 @@ extern "C" int smx_ddpg_rows_wgrad_update_f32(const smx_ddpg_rows_t* a, int32_t 
     SMX_REQUIRE(a && a->packed && u, SMX_E_NULL);
     const Dims d = dims_of(*a);
     SMX_REQUIRE(dims_ok(d), SMX_E_UNSUPPORTED);
-    SMX_REQUIRE(a->rows > 0 && a->rows < (1 << 24), SMX_E_SHAPE);
-    const smx_ddpg_rows_ln* l = a->ln;
+    SMX_REQUIRE(rows_ok(a->rows), SMX_E_SHAPE);
+    const bool ln = a->ln != nullptr;
     const bool two = ln_second(a);
-    SMX_REQUIRE(!l || ((two || (!a->second && group != SMX_DDPG_GROUP_CRITIC2)) && dims_ok_ln(d, two) &&
-                       offsets_ok(d, a->rows)), SMX_E_UNSUPPORTED);
-    const smx_ddpg_rows_ln_second* l2 = two ? l->second : nullptr;
+    SMX_REQUIRE(!ln || ((two || (!a->second && group != SMX_DDPG_GROUP_CRITIC2)) && dims_ok_ln(d, two) &&
+                        offsets_ok(d, a->rows, true)), SMX_E_UNSUPPORTED);
     WUArgs G;
     memset(&G, 0, sizeof(G));
     const int rc = fill_update(G.U, a, group, u, d);
@@ -1844,31 +1712,42 @@ extern "C" int smx_ddpg_rows_wgrad_update_f32(const smx_ddpg_rows_t* a, int32_t 
     G.U.grads_out = const_cast<float*>(u->grads);
     G.rows = (int)a->rows;
     G.tbuf = g_tbuf;
-    const bool c2nd = group == SMX_DDPG_GROUP_CRITIC2;
-    const bool cr = group == SMX_DDPG_GROUP_CRITIC || c2nd;
     const smx_ddpg_rows_second* s2 = a->second;                      // (fill_update has checked it for the second critic)
-    const smx_ddpg_net_t& net = c2nd ? s2->critic2 : cr ? a->critic : a->actor;
-    const smx_ddpg_net_t& tnet = c2nd ? s2->target_critic2 : cr ? a->target_critic : a->target_actor;
+    const smx_ddpg_rows_ln& l = ln ? *a->ln : NO_LN;
+    const smx_ddpg_rows_ln_second& l2 = two ? *a->ln->second : NO_LN2;
     const int ldc = d.c1 + d.A;
-    // (gradient, input) of the three layers: the buffers the chain launches wrote
-    // (LayerNorm: the critic's dz1 is a buffer of its own, dxcat keeps dn1; h2c / h1a / h2a are the LayerNorm outputs)
-    const float* dz[3] = {c2nd ? (l ? l2->dz1c2 : s2->dxcat2) : cr ? (l ? l->dz1c : a->dxcat) : a->dz1a, c2nd ? s2->dz2_2 : cr ? a->dz2 : a->dz2a,
-                          c2nd ? s2->dz3_2 : cr ? a->dz3 : a->dz3a};
-    const int ldz[3] = {cr ? (l ? d.c1 : ldc) : d.H1, cr ? d.c2 : d.H2, cr ? 1 : d.A};
-    const float* x[3] = {a->x, c2nd ? s2->xcat2 : cr ? a->xcat : a->h1a, c2nd ? s2->h2c2 : cr ? a->h2c : a->h2a};
-    const int ldx[3] = {d.D, cr ? ldc : d.H1, cr ? d.c2 : d.H2};
-    const float* b[3] = {net.b1, net.b2, net.b3};
-    const float* tb[3] = {tnet.b1, tnet.b2, tnet.b3};
+    WIo io;
+    switch (group) {
+        case SMX_DDPG_GROUP_CRITIC2:
+            io = {{ln ? l2.dz1c2 : s2->dxcat2, s2->dz2_2, s2->dz3_2}, {ln ? d.c1 : ldc, d.c2, 1},
+                  {a->x, s2->xcat2, s2->h2c2}, {d.D, ldc, d.c2}, &s2->critic2, &s2->target_critic2,
+                  {s2->dxcat2, l2.dn2_2}, {l2.c2_a1, l2.c2_a2}, {l2.c2m1, l2.c2m2}, {l2.c2r1, l2.c2r2}, {d.c1, d.c2}, {ldc, d.c2},
+                  &l2.critic2, &l2.target_critic2};
+            break;
+        case SMX_DDPG_GROUP_CRITIC:
+            io = {{ln ? l.dz1c : a->dxcat, a->dz2, a->dz3}, {ln ? d.c1 : ldc, d.c2, 1},
+                  {a->x, a->xcat, a->h2c}, {d.D, ldc, d.c2}, &a->critic, &a->target_critic,
+                  {a->dxcat, l.dn2}, {l.c_a1, l.c_a2}, {l.cm1, l.cm2}, {l.cr1, l.cr2}, {d.c1, d.c2}, {ldc, d.c2},
+                  &l.critic, &l.target_critic};
+            break;
+        default:
+            io = {{a->dz1a, a->dz2a, a->dz3a}, {d.H1, d.H2, d.A},
+                  {a->x, a->h1a, a->h2a}, {d.D, d.H1, d.H2}, &a->actor, &a->target_actor,
+                  {l.dn1a, l.dn2a}, {l.a1, l.a2}, {l.am1, l.am2}, {l.ar1, l.ar2}, {d.H1, d.H2}, {d.H1, d.H2},
+                  &l.actor, &l.target_actor};
+    }
+    const float* b[3] = {io.net->b1, io.net->b2, io.net->b3};
+    const float* tb[3] = {io.tnet->b1, io.tnet->b2, io.tnet->b3};
     int tiles = 0;
     for (int j = 0; j < 3; ++j) {
-        SMX_REQUIRE(dz[j] && x[j] && b[j], SMX_E_NULL);
+        SMX_REQUIRE(io.dz[j] && io.x[j] && b[j], SMX_E_NULL);
         WMat& W = G.w[j];
         const UMat& X = G.U.mat[j];
-        W.dz = dz[j]; W.ldz = ldz[j]; W.x = x[j]; W.ldx = ldx[j];
+        W.dz = io.dz[j]; W.ldz = io.ldz[j]; W.x = io.x[j]; W.ldx = io.ldx[j];
         W.boff = b[j] - u->theta;
         SMX_REQUIRE(W.boff >= 0 && W.boff + X.M <= u->n, SMX_E_SHAPE);
         if (u->target) SMX_REQUIRE(tb[j] && tb[j] - u->target == W.boff, SMX_E_SHAPE);
-        SMX_REQUIRE((int64_t)a->rows * (ldz[j] > ldx[j] ? ldz[j] : ldx[j]) * 4 < (1ll << 31), SMX_E_SHAPE);
+        SMX_REQUIRE((int64_t)a->rows * imax(io.ldz[j], io.ldx[j]) * 4 < (1ll << 31), SMX_E_SHAPE);
         W.tiles_n = (X.K + 31) / 32;
         W.tile0 = tiles;
         tiles += ((X.M + 31) / 32) * W.tiles_n;
@@ -1877,34 +1756,27 @@ extern "C" int smx_ddpg_rows_wgrad_update_f32(const smx_ddpg_rows_t* a, int32_t 
     {
         long covered = 0;
         for (int j = 0; j < 3; ++j) covered += (long)G.U.mat[j].M * G.U.mat[j].K + G.U.mat[j].M;
-        if (l) covered += 2l * ((cr ? d.c1 : d.H1) + (cr ? d.c2 : d.H2));      // ... or a LayerNorm's gain or bias
+        if (ln) covered += 2l * (io.F[0] + io.F[1]);                 // ... or a LayerNorm's gain or bias
         SMX_REQUIRE(covered == u->n, SMX_E_SHAPE);
     }
     G.tiles = tiles;
-    if (l) {
-        const smx_ddpg_ln_net& p = c2nd ? l2->critic2 : cr ? l->critic : l->actor;
-        const smx_ddpg_ln_net& tp = c2nd ? l2->target_critic2 : cr ? l->target_critic : l->target_actor;
-        const float* gam[2] = {p.g1, p.g2};
-        const float* bet[2] = {p.b1, p.b2};
-        const float* tgam[2] = {tp.g1, tp.g2};
-        const float* tbet[2] = {tp.b1, tp.b2};
-        const float* dn[2] = {c2nd ? s2->dxcat2 : cr ? a->dxcat : l->dn1a, c2nd ? l2->dn2_2 : cr ? l->dn2 : l->dn2a};
-        const int lddn[2] = {cr ? ldc : d.H1, cr ? d.c2 : d.H2};
-        const float* pre[2] = {c2nd ? l2->c2_a1 : cr ? l->c_a1 : l->a1, c2nd ? l2->c2_a2 : cr ? l->c_a2 : l->a2};
-        const float* mean[2] = {c2nd ? l2->c2m1 : cr ? l->cm1 : l->am1, c2nd ? l2->c2m2 : cr ? l->cm2 : l->am2};
-        const float* rstd[2] = {c2nd ? l2->c2r1 : cr ? l->cr1 : l->ar1, c2nd ? l2->c2r2 : cr ? l->cr2 : l->ar2};
-        const int F[2] = {cr ? d.c1 : d.H1, cr ? d.c2 : d.H2};
+    if (ln) {
+        const float* gam[2] = {io.p->g1, io.p->g2};
+        const float* bet[2] = {io.p->b1, io.p->b2};
+        const float* tgam[2] = {io.tp->g1, io.tp->g2};
+        const float* tbet[2] = {io.tp->b1, io.tp->b2};
         int blocks = 0;
         for (int k = 0; k < 2; ++k) {
-            SMX_REQUIRE(gam[k] && bet[k] && dn[k] && pre[k] && mean[k] && rstd[k], SMX_E_NULL);
+            const int F = io.F[k];
+            SMX_REQUIRE(gam[k] && bet[k] && io.dn[k] && io.pre[k] && io.mean[k] && io.rstd[k], SMX_E_NULL);
             WLn& W = G.ln[k];
-            W.dn = dn[k]; W.lddn = lddn[k]; W.pre = pre[k]; W.ldp = F[k]; W.mean = mean[k]; W.rstd = rstd[k]; W.F = F[k];
+            W.dn = io.dn[k]; W.lddn = io.lddn[k]; W.pre = io.pre[k]; W.ldp = F; W.mean = io.mean[k]; W.rstd = io.rstd[k]; W.F = F;
             W.goff = gam[k] - u->theta; W.boff = bet[k] - u->theta;
-            SMX_REQUIRE(W.goff >= 0 && W.goff + F[k] <= u->n && W.boff >= 0 && W.boff + F[k] <= u->n, SMX_E_SHAPE);
+            SMX_REQUIRE(W.goff >= 0 && W.goff + F <= u->n && W.boff >= 0 && W.boff + F <= u->n, SMX_E_SHAPE);
             if (u->target)
                 SMX_REQUIRE(tgam[k] && tbet[k] && tgam[k] - u->target == W.goff && tbet[k] - u->target == W.boff, SMX_E_SHAPE);
             W.blk0 = blocks;
-            blocks += (F[k] + LNC - 1) / LNC;
+            blocks += (F + LNC - 1) / LNC;
         }
         G.ln_blocks = blocks;
     }
