@@ -1504,6 +1504,65 @@ struct smx_ddpg_pixel_step {           /* (by tag: no typedef) */
 int smx_synth_ddpg_pixel_step(const struct smx_ddpg_pixel_step* args, const float* mu, int64_t ld_mu,
                               smx_stream_t stream);
 
+/* The frame-pool layout of the camera replay: every raw frame is stored ONCE.  The reference's pixel DDPG configuration
+ * ships frame_stack_concatenate_on_env: False (surreal/main/ddpg_configs.py:119-122: the agent sends the stack as a list
+ * of frames "so that identical frames aren't duplicated in memory", the learner joins them, surreal/learner/ddpg.py:
+ * 430-440); the stacked tables above hold each frame up to 2 S times.  Per replay:
+ *   pool        uint8 [n, P, F]: actor a's frame with counter i (int64, monotone per actor) in slot i mod P;
+ *   an environment step writes ONE frame, the observation after the step, at counter f + 1; a terminal step two: the
+ *   terminal frame at f + 1 and the new episode's first frame at f + 2.  The frame of episode step u has counter
+ *   first + u, `first` the counter of the episode's reset frame;
+ *   a ring row carries, in place of pixel / pixel_next, frame_next (the counter of pixel_next's newest frame),
+ *   frame_first (its episode's `first`) and frame_actor (int32: whose pool) -- [capacity] each;
+ *   stack(top)[i] = frame max(top - S + 1 + i, frame_first), 0 <= i < S   (FrameStackWrapper, surreal/env/wrapper.py:
+ *   407-453: a reset fills the history with the first frame; smx_frame_stack_u8's rule), pixel_next = stack(frame_next),
+ *   pixel = stack(frame_next - n_step);
+ *   a row is live while its oldest frame max(frame_first, frame_next - n_step - S + 1) >= f_now - P + 1; the host keeps
+ *   the number of live rows (the newest ones of the ring) and samples among them only.
+ *
+ * smx_synth_ddpg_pixel_pool_step: smx_synth_ddpg_pixel_step in this layout (the shared episode clock; base as there, the
+ * same step, monitor and noise stream).  frame = f, the counter of the current step's frame, episode_first = first; the
+ * launch renders frame f + 1 once into the pool (on a terminal step also the new episode's first frame, counter f + 2),
+ * writes obs_pixel [n, S*F] -- the stacked observation of the next step, its older frames out of the pool -- and at a
+ * closing step (tau >= n_step - 1) frame_next = f + 1, frame_first = first, frame_actor = a of row (base.cursor + a) %
+ * capacity.  The caller's next call passes f + 1 (terminal: f + 2, episode_first = f + 2).  pool_len < n_step + S + 1,
+ * episode_first < 0 or > frame: SMX_E_SHAPE; the counter columns off their element size: SMX_E_ALIGN. */
+struct smx_ddpg_pixel_pool_step {      /* (by tag: no typedef) */
+    smx_ddpg_rollout_t base;           /* steps, net, packed, actors_per_workgroup: ignored */
+    int32_t C, H, W, frame_stacks;
+    int64_t pool_len;                  /* P */
+    int64_t frame, episode_first;
+    uint8_t* pool;
+    uint8_t* obs_pixel;
+    int64_t* frame_next;
+    int64_t* frame_first;
+    int32_t* frame_actor;
+};
+int smx_synth_ddpg_pixel_pool_step(const struct smx_ddpg_pixel_pool_step* args, const float* mu, int64_t ld_mu,
+                                   smx_stream_t stream);
+
+/* A whole uniform sample of a frame-pool replay in ONE launch (UniformReplay.sample, surreal/replay/uniform_replay.py:
+ * 36-47, with the learner's frame join, surreal/learner/ddpg.py:430-440): smx_uniform_gather_multi over `jobs` (1..8
+ * field tables) and, for the same rows, pixel / pixel_next [rows, S*F] built from the pool by the stack rule above,
+ * straight into the caller's buffers.  Row i is idx[i], or (idx NULL) (base + u) % capacity with u = the i-th draw of
+ * smx_uniform_indices(len, seed, offset): base = (cursor - live) mod capacity and len = live make that a draw among the
+ * live rows.  idx_out as in smx_uniform_gather_multi.  Frames move in 16-byte units where F and the buffers allow, else in
+ * 4- or single-byte ones.  pool_len < n_step + S + 1, base outside [0, capacity): SMX_E_SHAPE. */
+struct smx_gather_pool {               /* (by tag: no typedef) */
+    const uint8_t* pool;               /* [actors, pool_len, frame_bytes] */
+    int64_t pool_len, frame_bytes;
+    int32_t actors, frame_stacks, n_step, reserved;
+    const int64_t* frame_next;         /* [capacity] */
+    const int64_t* frame_first;
+    const int32_t* frame_actor;
+    uint8_t* pixel;                    /* [rows, S*F] out */
+    uint8_t* pixel_next;
+    int64_t base;
+};
+int smx_uniform_gather_pool(const smx_gather_job_t* jobs, int32_t njobs, const struct smx_gather_pool* pool,
+                            int64_t capacity, int64_t rows, const int64_t* idx, int64_t len, uint64_t seed,
+                            uint64_t offset, int64_t* idx_out, smx_stream_t stream);
+
 /* ONE step of PPO's moving windows for actors with a camera (the reference's pixel PPO configuration: FrameStackWrapper,
  * surreal/env/wrapper.py:407-472, in front of the CNN stem; PPOAgent.act, surreal/agent/ppo_agent.py:106-154; the
  * windows of ExpSenderWrapperMultiStepMovingWindowWithInfo, surreal/env/exp_sender_wrapper.py:153-264), given the
@@ -1773,6 +1832,57 @@ struct smx_record_ddpg_pixel_nstep_step {  /* (by tag: no typedef) */
     struct smx_episode_monitor mon;        /* mon.ep_reward NULL: none (stays the last member) */
 };
 int smx_record_ddpg_pixel_nstep_step(const struct smx_record_ddpg_pixel_nstep_step* args, smx_stream_t stream);
+
+/* smx_record_ddpg_pixel_nstep_step in the frame-pool layout (above smx_synth_ddpg_pixel_pool_step; the reference's
+ * frame_stack_concatenate_on_env: False, surreal/main/ddpg_configs.py:119-122, with the n-step wrapper of
+ * surreal/env/exp_sender_wrapper.py:72-112): the low-dimensional step, rings, n-step reward, monitor and the t / rank /
+ * rows guards exactly as smx_record_ddpg_nstep_step_f32, the rows where it puts them; the frames once, in the pool.  A
+ * terminal step brings two frames, so every actor has counters of its own: counters_in int64 [2, n] = f | first before the
+ * step (f: the counter of the actor's current frame, first: of its episode's reset frame), counters_out [2, n] after it
+ * (another buffer: the caller swaps the two per launch).  With restart = step_dones[a] != 0 and step_frame_reset given:
+ *   pool[a, (f + 1) mod P] = step_frame_next[a];  restart: pool[a, (f + 2) mod P] = step_frame_reset[a]
+ *   obs_pixel[a] = stack(f + 1) over `first`;     restart: step_frame_reset[a] S times
+ *   counters_out = (f + 1, first);                restart: (f + 2, f + 2)
+ *   a closing actor's row: frame_next = f + 1, frame_first = first, frame_actor = a.
+ * pool_len < n_step + S + 1, counters_in == counters_out: SMX_E_SHAPE; the counter arrays off their element size:
+ * SMX_E_ALIGN. */
+struct smx_record_ddpg_pixel_pool_nstep_step {  /* (by tag: no typedef) */
+    int32_t n, D, A, n_step;
+    int32_t rows, copy_workgroups;
+    const int32_t* t;
+    const int32_t* rank;
+    const int32_t* t_host;                 /* NULL: not checked on the host */
+    const int32_t* rank_host;
+    float* cur_obs;
+    const float* step_actions;
+    const float* step_obs_next;
+    const float* step_rewards;
+    const float* step_dones;
+    const float* step_obs_reset;           /* NULL: no actor is done */
+    const double* gpow;
+    float* carry_obs;
+    float* carry_act;
+    float* carry_rew;
+    float* obs;
+    float* obs_next;
+    float* actions;
+    float* rewards;
+    float* dones;
+    int64_t cursor, capacity;
+    int32_t C, H, W, frame_stacks;
+    int64_t pool_len;                      /* P */
+    const uint8_t* step_frame_next;        /* [n, F] */
+    const uint8_t* step_frame_reset;       /* [n, F], or NULL: no actor is done */
+    uint8_t* pool;                         /* [n, P, F] */
+    uint8_t* obs_pixel;                    /* [n, S*F] */
+    const int64_t* counters_in;            /* [2, n] */
+    int64_t* counters_out;                 /* [2, n] */
+    int64_t* frame_next;                   /* [capacity] */
+    int64_t* frame_first;
+    int32_t* frame_actor;
+    struct smx_episode_monitor mon;        /* mon.ep_reward NULL: none (stays the last member) */
+};
+int smx_record_ddpg_pixel_pool_nstep_step(const struct smx_record_ddpg_pixel_pool_nstep_step* args, smx_stream_t stream);
 
 /* ---------------------------------------------------------------------------
  * Data-parallel exchange between the learner ranks of one node over IPC-mapped peer buffers (xGMI loads): the

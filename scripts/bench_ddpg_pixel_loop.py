@@ -42,6 +42,14 @@ def step_bytes(n, D, A, C, H, W, S, emit=True):
     return n * (writes + reads + low)
 
 
+def pool_step_bytes(n, D, A, C, H, W, S):
+    """bytes smx_synth_ddpg_pixel_pool_step moves in a non-final step (--frame-pool): the new frame into the pool and the
+    next observation, the observation's older frames out of the pool, two counters and the actor a row"""
+    F = C * H * W
+    low = 4 * (2 * D + 2 * A + 2 + 3 * D + 3 * A + 3) + 8 * A + 4 * A * 2
+    return n * ((1 + S) * F + (S - 1) * F + 20 + low)
+
+
 def kernel_split(path, T_total):
     """the --stats CSV -> per-step microseconds of perception, actor and the new launch"""
     groups = collections.OrderedDict((('pixel_step', 0.0), ('actor', 0.0), ('perception', 0.0), ('other', 0.0)))
@@ -52,7 +60,7 @@ def kernel_split(path, T_total):
             # the actor's three layers (smx_mlp3_forward_f32) are the gemm32_kernel<true> launches; the stem's fc layer
             # writes a strided view of the perception output (gemm32_kernel<false>), and the low-dimensional columns
             # are one torch copy (elementwise_kernel)
-            if 'ddpg_pixel_step_kernel' in name:
+            if 'ddpg_pixel_step_kernel' in name or 'ddpg_pixel_pool_step_kernel' in name:
                 g = 'pixel_step'
             elif 'gemm32_kernel<true>' in name:
                 g = 'actor'
@@ -79,6 +87,8 @@ def main():
     ap.add_argument('--trace', action='store_true')
     ap.add_argument('--trace-rollouts', type=int, default=2)
     ap.add_argument('--stats', default=None, help='rocprofv3 kernel-stats CSV of a --trace run')
+    ap.add_argument('--frame-pool', action='store_true',
+                    help='replay.device_frame_pool: every frame once in a pool, two counters a row')
     args = ap.parse_args()
     n, T = args.actors, args.steps
     D, A, (C, H, W), S, N = 17, 6, (3, 84, 84), 3, 3
@@ -87,7 +97,7 @@ def main():
              'actor': [300, 200], 'critic': [400, 300], 'A': A, 'conv_spec': [[16, 32], [8, 4], [4, 2], 200]}
     if args.stats:
         T_total = T * (args.trace_rollouts + 1)
-        by = step_bytes(n, D, A, C, H, W, S)
+        by = (pool_step_bytes if args.frame_pool else step_bytes)(n, D, A, C, H, W, S)
         split = kernel_split(args.stats, T_total)
         us = split['pixel_step']['us_per_step']
         print(json.dumps({'what': 'ddpg_pixel_kernel_split', **shape, 'rollouts_traced': args.trace_rollouts + 1,
@@ -105,6 +115,8 @@ def main():
     lc.algo.exploration.noise_type = 'ou_noise'
     lc.replay.memory_size = args.capacity
     lc.replay.batch_size = args.batch
+    if args.frame_pool:
+        lc.replay.device_frame_pool = True
     ec = ddpg_env_config(D, A, num_agents=n, pixel=(S * C, H, W))
     ec.frame_stacks = S
     sc = ddpg_session_config()
@@ -112,8 +124,12 @@ def main():
     venv = SyntheticVecEnv(n, D, A, episode_len=1000, device='cuda', pixel=(C, H, W), frame_stacks=S)
     eps = torch.randn(T, n, A, device='cuda')
     replay = UniformReplay(lc, ec, sc)
-    row_bytes = 2 * S * F + 4 * (2 * D + A + 2)
-    ring = {'capacity_rows': args.capacity, 'row_bytes': row_bytes, 'ring_gb': args.capacity * row_bytes / 1e9}
+    row_bytes = (20 if args.frame_pool else 2 * S * F) + 4 * (2 * D + A + 2)
+    ring = {'capacity_rows': args.capacity, 'row_bytes': row_bytes, 'ring_gb': args.capacity * row_bytes / 1e9,
+            'frame_pool': bool(args.frame_pool)}
+    if args.frame_pool:
+        from surreal_amd.replay.frame_pool import default_pool_steps
+        ring['pool_gb'] = default_pool_steps(args.capacity, n, N, S) * n * F / 1e9
     venv.ddpg_rollout_into(agent, replay, T, eps=eps)                  # warm-up (tables, workspaces, code)
     torch.cuda.synchronize()
     if args.trace:
@@ -136,7 +152,7 @@ def main():
     print(json.dumps({'what': 'ddpg_pixel_rollout', **shape, **ring, 'reps': args.reps, 'ms_median': round(med, 3),
                       'ms_min': round(min(times), 3), 'ms_max': round(max(times), 3),
                       'env_steps_per_s': n * T / (med * 1e-3), 'pixel_step_bytes_per_step':
-                      step_bytes(n, D, A, C, H, W, S)}), flush=True)
+                      (pool_step_bytes if args.frame_pool else step_bytes)(n, D, A, C, H, W, S)}), flush=True)
 
     # ---- 2. the loop: rollout chunk -> learn iterations from the ring ----------------------------------------------
     learner = DDPGLearner(lc, ec, sc)

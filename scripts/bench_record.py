@@ -42,6 +42,7 @@ DDPG_N, GAMMA = 3, 0.99
 LENGTHS = [100, 140, 180, 220]           # episode lengths, every actor from another rotation: the clocks diverge
 HBM_COPY_BYTES_PER_S = 6.3e12            # the achievable copy rate DESIGN.md 3.8 quotes
 CAMERA = None                            # ((C, H, W), frame_stacks) with --pixel
+FRAME_POOL = False                       # --frame-pool
 
 
 class PlaybackEnv(Env):
@@ -192,12 +193,16 @@ class RecordPath(object):
                                self.obs_reset[s % self.RING], **frames)
 
 
-def _replay(algo, n):
+def _replay(algo, n, frame_pool=False):
+    """frame_pool: the DDPG camera replay in the frame-pool layout (what record() writes into; insert_batch of stacked rows
+    has no meaning there, so the host paths keep the stacked one)"""
     if algo == 'ppo':
         lc, ec, sc = PW.configs(D, A, *WINDOW, hidden=(300, 200), memory_size=4 * n)
         return FIFOReplay(lc, ec, sc), lc, sc
     lc, ec, sc = DC.configs(D, A, n, hidden=(300, 200), n_step=DDPG_N, gamma=GAMMA, memory_size=(16 if CAMERA else 64) * n,
                             folder='surreal_amd_bench_record')
+    if frame_pool and CAMERA:
+        lc.replay.device_frame_pool = True
     return UniformReplay(lc, ec, sc), lc, sc
 
 
@@ -217,6 +222,11 @@ def moved_bytes(algo, rows, n=0):
     and ring slot, a few KB per actor, not counted); with a camera also the closing experiences' stacked frames and, for
     each of the n actors, the new frame into the history and the acting observation"""
     per = WINDOW[0] * (D + 3 * A + 2) * 4 + D * 4 if algo == 'ppo' else (2 * D + A + 2) * 4
+    if CAMERA and FRAME_POOL and algo == 'ddpg':
+        # (a row gains two counters and its actor; per actor the input frame read once and stored twice, the
+        # observation's S - 1 older frames out of the pool)
+        (C, H, W), S = CAMERA
+        return 2 * per * rows + 20 * rows + n * (1 + 2 * S) * C * H * W
     if CAMERA:
         (C, H, W), S = CAMERA
         per += ((WINDOW[0] + 1) if algo == 'ppo' else 2) * S * C * H * W
@@ -230,7 +240,7 @@ def bench(algo, n, rounds, steps, warmup):
     for name, device_insert in (('host_insert_batch', True),) + ((() if CAMERA else (('host_insert', False),))):
         replay, lc, sc = _replay(algo, n)
         paths[name] = HostPath(algo, n, replay, lc, sc, device_insert).step
-    paths['record'] = RecordPath(algo, n, _replay(algo, n)[0], warmup + rounds * steps).step
+    paths['record'] = RecordPath(algo, n, _replay(algo, n, FRAME_POOL)[0], warmup + rounds * steps).step
     for name, step in paths.items():
         _timed_steps(step, warmup)
     times = {k: [] for k in paths}
@@ -246,7 +256,8 @@ def bench(algo, n, rounds, steps, warmup):
     med = {k: statistics.median(v) for k, v in times.items()}
     line = {'case': algo, 'n': n, 'D': D, 'A': A, 'n_step': WINDOW[0] if algo == 'ppo' else DDPG_N,
             'stride': WINDOW[1] if algo == 'ppo' else None, 'pixel': CAMERA[0] if CAMERA else None,
-            'frame_stacks': CAMERA[1] if CAMERA else None, 'rounds': rounds, 'steps_per_round': steps,
+            'frame_stacks': CAMERA[1] if CAMERA else None, 'frame_pool': bool(FRAME_POOL and CAMERA and algo == 'ddpg'),
+            'rounds': rounds, 'steps_per_round': steps,
             'experiences_per_step': rows['record'] / (rounds * steps),
             'step_ms_median': med, 'step_ms_round_medians': medians,
             'step_ms_max': {k: max(v) for k, v in times.items()},
@@ -262,7 +273,7 @@ def profile(n, steps=40, warmup=5):
     the kernel's average time over bytes_per_launch is the launch's bytes per second"""
     lines = []
     for algo in ('ppo', 'ddpg'):
-        path = RecordPath(algo, n, _replay(algo, n)[0], warmup + steps)
+        path = RecordPath(algo, n, _replay(algo, n, FRAME_POOL)[0], warmup + steps)
         ms, rows = _timed_steps(lambda: path.step(all_closing=True), warmup + steps)
         assert rows == n * (warmup + steps)
         b = moved_bytes(algo, n, n)
@@ -285,8 +296,11 @@ def main():
     ap.add_argument('--pixel', type=int, nargs=3, metavar=('C', 'H', 'W'), default=None,
                     help='the environments also emit one raw uint8 frame per step')
     ap.add_argument('--frame-stacks', type=int, default=3)
+    ap.add_argument('--frame-pool', action='store_true',
+                    help='with --pixel: DDPG\'s record() writes into a frame-pool replay (replay.device_frame_pool)')
     args = ap.parse_args()
-    global CAMERA
+    global CAMERA, FRAME_POOL
+    FRAME_POOL = bool(args.frame_pool)
     if args.pixel:
         CAMERA = (tuple(args.pixel), args.frame_stacks)
     if not torch.cuda.is_available():

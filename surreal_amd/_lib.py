@@ -255,6 +255,21 @@ class DdpgPixelStep(Structure):
                 ('pixel_next', c_void_p), ('obs_pixel', c_void_p)]
 
 
+class DdpgPixelPoolStep(Structure):
+    """struct smx_ddpg_pixel_pool_step"""
+    _fields_ = [('base', DdpgRollout), ('C', c_int32), ('H', c_int32), ('W', c_int32), ('frame_stacks', c_int32),
+                ('pool_len', c_int64), ('frame', c_int64), ('episode_first', c_int64), ('pool', c_void_p),
+                ('obs_pixel', c_void_p), ('frame_next', c_void_p), ('frame_first', c_void_p), ('frame_actor', c_void_p)]
+
+
+class GatherPool(Structure):
+    """struct smx_gather_pool"""
+    _fields_ = [('pool', c_void_p), ('pool_len', c_int64), ('frame_bytes', c_int64), ('actors', c_int32),
+                ('frame_stacks', c_int32), ('n_step', c_int32), ('reserved', c_int32), ('frame_next', c_void_p),
+                ('frame_first', c_void_p), ('frame_actor', c_void_p), ('pixel', c_void_p), ('pixel_next', c_void_p),
+                ('base', c_int64)]
+
+
 class SynthPpoPixelWindowStep(Structure):
     """struct smx_synth_ppo_pixel_window_step"""
     _fields_ = ([(n, c_int32) for n in ('n', 'D', 'A', 'hidden', 't', 'episode_len', 'n_step', 'advance')] +
@@ -304,6 +319,17 @@ class RecordDdpgPixelNstepStep(Structure):
     in front of `mon`"""
     _fields_ = ([(n, c_int32) for n in ('n', 'D', 'A', 'n_step', 'rows', 'copy_workgroups')] +
                 RecordDdpgNstepStep._fields_[6:-1] + _RECORD_CAMERA + [('mon', EpisodeMonitor)])
+
+
+class RecordDdpgPixelPoolNstepStep(Structure):
+    """struct smx_record_ddpg_pixel_pool_nstep_step: RecordDdpgPixelNstepStep's head with the frame pool in front of
+    `mon`"""
+    _fields_ = ([(n, c_int32) for n in ('n', 'D', 'A', 'n_step', 'rows', 'copy_workgroups')] +
+                RecordDdpgNstepStep._fields_[6:-1] +
+                [(n, c_int32) for n in ('C', 'H', 'W', 'frame_stacks')] + [('pool_len', c_int64)] +
+                [(n, c_void_p) for n in ('step_frame_next', 'step_frame_reset', 'pool', 'obs_pixel', 'counters_in',
+                                         'counters_out', 'frame_next', 'frame_first', 'frame_actor')] +
+                [('mon', EpisodeMonitor)])
 
 
 SMX_DDPG_NOISE_NONE, SMX_DDPG_NOISE_GAUSSIAN, SMX_DDPG_NOISE_OU = 0, 1, 2
@@ -445,6 +471,8 @@ _SIGS = {
     'smx_uniform_indices': (c_int32, [_P, c_int64, c_int64, c_uint64, c_uint64, _P]),
     'smx_uniform_gather_multi': (c_int32, [POINTER(GatherJob), c_int32, c_int64, c_int64, _P, c_int64, c_uint64, c_uint64,
                                            _P, _P]),
+    'smx_uniform_gather_pool': (c_int32, [POINTER(GatherJob), c_int32, POINTER(GatherPool), c_int64, c_int64, _P, c_int64,
+                                          c_uint64, c_uint64, _P, _P]),
     'smx_window_emit_f32': (c_int32, [_P, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32,
                                       c_int32, _P, _P]),
     'smx_synth_act_env_step_f32': (c_int32, [POINTER(SynthActStep), _P]),
@@ -509,6 +537,7 @@ _SIGS = {
                                                     POINTER(ActorClocks), _P]),
     'smx_synth_ddpg_step_f32': (c_int32, [POINTER(DdpgRollout), _P, c_int64, _P]),
     'smx_synth_ddpg_pixel_step': (c_int32, [POINTER(DdpgPixelStep), _P, c_int64, _P]),
+    'smx_synth_ddpg_pixel_pool_step': (c_int32, [POINTER(DdpgPixelPoolStep), _P, c_int64, _P]),
     'smx_param_noise_copy_floats': (c_int64, [c_int32, c_int32, c_int32, c_int32, c_int32]),
     'smx_param_noise_fill_f32': (c_int32, [POINTER(ParamNoise), c_int32, _P, _P]),
     'smx_param_noise_refresh_f32': (c_int32, [POINTER(ParamNoise), _P]),
@@ -517,6 +546,7 @@ _SIGS = {
     'smx_record_ddpg_nstep_step_f32': (c_int32, [POINTER(RecordDdpgNstepStep), _P]),
     'smx_record_ppo_pixel_window_step': (c_int32, [POINTER(RecordPpoPixelWindowStep), _P]),
     'smx_record_ddpg_pixel_nstep_step': (c_int32, [POINTER(RecordDdpgPixelNstepStep), _P]),
+    'smx_record_ddpg_pixel_pool_nstep_step': (c_int32, [POINTER(RecordDdpgPixelPoolNstepStep), _P]),
     'smx_xchg_bytes': (c_int64, [c_int64, c_int32]),
     'smx_xchg_alloc': (c_int32, [c_int64, c_double, POINTER(c_void_p), POINTER(c_int32), _P]),
     'smx_xchg_free': (c_int32, [_P]),

@@ -347,6 +347,79 @@ __global__ __launch_bounds__(REC_PIXEL_THREADS) void record_ddpg_pixel_nstep_ker
     });
 }
 
+// ---- DDPG with a camera, frame-pool layout (include/surreal_amd.h, above smx_synth_ddpg_pixel_pool_step) ------------------
+// Every frame once in a per-actor pool of Pl slots, counter i in slot i mod Pl; a terminal step brings two frames (the
+// terminal one, the reset one), so the counters are the actors' own: f = cin[a], first = cin[n + a] before the step,
+// cout[...] after it -- two buffers, because the copy workgroups read what workgroup (a, 0) moves on.  Workgroup (a, 0):
+// the low-dimensional step, the row's counters at a closing step, step_frame_next[a] -> the pool at f + 1 and (unless the
+// actor restarts) the acting observation's last frame.  Workgroups (a, 1 .. X): the observation's older frames out of the
+// pool (counters max(f + 2 - S + q, first)), or on a restart step_frame_reset[a] -> the pool at f + 2 and S times into the
+// observation.  Read: f + 2 - S .. f; written: f + 1, f + 2 -- S + 1 consecutive counters, distinct slots as Pl >= S + 2.
+struct RecPool {
+    int S, X;
+    long long F, Pl;
+    const unsigned char *fnext, *freset;
+    unsigned char *pool, *obs_pix;
+    const int64_t* cin;
+    int64_t *cout, *frame_next, *frame_first;
+    int* frame_actor;
+};
+
+template <int U>
+__global__ __launch_bounds__(REC_PIXEL_THREADS) void record_ddpg_pixel_pool_nstep_kernel(RecD G, RecPool P) {
+    const long a = blockIdx.x;
+    const int y = blockIdx.y, tid = threadIdx.x;
+    const int tau = G.t[a];
+    if (tau < 0) return;
+    const int N = G.N, S = P.S;
+    const int rank = G.rank[a];
+    const bool emits = rank >= 0 && rank < G.rows && tau >= N - 1;                   // (ddpg_nstep_step's rule)
+    const size_t row = emits ? (size_t)((G.cursor + rank) % G.capacity) : 0;
+    const bool restart = G.done[a] != 0.0f && P.freset;
+    const long long f = P.cin[a], first = P.cin[G.n + a];
+    const long long F = P.F, nu = F / U;
+    unsigned char* pool_a = P.pool + (size_t)a * P.Pl * F;
+    unsigned char* obs_a = P.obs_pix + (size_t)a * S * F;
+    auto slot = [&](long long c) { return pool_a + (size_t)(((c % P.Pl) + P.Pl) % P.Pl) * F; };
+    alignas(16) unsigned char b[U];
+    if (y == 0) {
+        ddpg_nstep_step<REC_PIXEL_THREADS>(G, a, tid);
+        if (tid == 0) {
+            if (emits) {
+                P.frame_next[row] = f + 1;
+                P.frame_first[row] = first;
+                P.frame_actor[row] = (int)a;
+            }
+            P.cout[a] = f + (restart ? 2 : 1);
+            P.cout[G.n + a] = restart ? f + 2 : first;
+        }
+        const unsigned char* src = P.fnext + (size_t)a * F;
+        unsigned char* d0 = slot(f + 1);
+        unsigned char* d1 = restart ? nullptr : obs_a + (size_t)(S - 1) * F;
+        for (long long v = tid; v < nu; v += REC_PIXEL_THREADS) {
+            load_unit<U>(src + v * U, b);
+            store_unit<U>(d0 + v * U, b);
+            if (d1) store_unit<U>(d1 + v * U, b);
+        }
+        return;
+    }
+    const int nq = restart ? 1 + S : S - 1;
+    const long long total = (long long)nq * nu, stride = (long long)P.X * REC_PIXEL_THREADS;
+    for (long long g = (long long)(y - 1) * REC_PIXEL_THREADS + tid; g < total; g += stride) {
+        const int q = (int)(g / nu);
+        const long long e = (g - (long long)q * nu) * U;
+        unsigned char* dst;
+        if (restart) {
+            dst = q == 0 ? slot(f + 2) : obs_a + (size_t)(q - 1) * F;
+            load_unit<U>(P.freset + (size_t)a * F + e, b);
+        } else {
+            dst = obs_a + (size_t)q * F;
+            const long long c = f + 2 - S + q;
+            load_unit<U>(slot(c < first ? first : c) + e, b);
+        }
+        store_unit<U>(dst + e, b);
+    }
+}
 
 // ---- host side -------------------------------------------------------------------------------------------------------
 
@@ -534,6 +607,34 @@ extern "C" int smx_record_ppo_pixel_window_step(const struct smx_record_ppo_pixe
     // a closing step: the window's N S stacked frames and pixel_next's S - 1 older ones
     const RecP P = camera_fields(a, (long long)(a->n_step + 1) * a->frame_stacks - 1);
     return launch_camera<record_ppo_pixel_window_kernel<16>, record_ppo_pixel_window_kernel<1>>(G, P, a->n, stream);
+}
+
+extern "C" int smx_record_ddpg_pixel_pool_nstep_step(const struct smx_record_ddpg_pixel_pool_nstep_step* a,
+                                                     smx_stream_t stream) {
+    const int rc = nstep_step_check(a);
+    if (rc != SMX_OK) return rc;
+    SMX_REQUIRE(a->pool && a->obs_pixel && a->step_frame_next && a->counters_in && a->counters_out && a->frame_next &&
+                a->frame_first && a->frame_actor, SMX_E_NULL);
+    SMX_REQUIRE(a->C > 0 && a->H > 0 && a->W > 0 && a->frame_stacks > 0, SMX_E_SHAPE);
+    SMX_REQUIRE(a->pool_len >= (int64_t)a->n_step + a->frame_stacks + 1 && a->counters_in != a->counters_out, SMX_E_SHAPE);
+    SMX_REQUIRE(a->copy_workgroups >= 0 && a->copy_workgroups <= 1024, SMX_E_SHAPE);
+    SMX_REQUIRE((((uintptr_t)a->counters_in | (uintptr_t)a->counters_out | (uintptr_t)a->frame_next |
+                  (uintptr_t)a->frame_first) & 7) == 0 && ((uintptr_t)a->frame_actor & 3) == 0, SMX_E_ALIGN);
+    const RecD G = nstep_step_fields(a);
+    RecPool P;
+    memset(&P, 0, sizeof(P));
+    P.S = a->frame_stacks; P.F = (long long)a->C * a->H * a->W; P.Pl = a->pool_len;
+    P.fnext = a->step_frame_next; P.freset = a->step_frame_reset; P.pool = a->pool; P.obs_pix = a->obs_pixel;
+    P.cin = a->counters_in; P.cout = a->counters_out;
+    P.frame_next = a->frame_next; P.frame_first = a->frame_first; P.frame_actor = a->frame_actor;
+    // (the copy workgroups: ~32 KB each of the 1 + S frames of an actor that restarts)
+    long long X = a->copy_workgroups ? a->copy_workgroups : ((1LL + P.S) * P.F + 32767) / 32768;
+    P.X = (int)(X < 1 ? 1 : (X > 64 && !a->copy_workgroups ? 64 : X));
+    const bool vec = P.F % 16 == 0 && on16(P.fnext) && on16(P.freset) && on16(P.pool) && on16(P.obs_pix);
+    hipLaunchKernelGGL(vec ? record_ddpg_pixel_pool_nstep_kernel<16> : record_ddpg_pixel_pool_nstep_kernel<1>,
+                       dim3(a->n, 1 + P.X), dim3(REC_PIXEL_THREADS), 0, smx_s(stream), G, P);
+    SMX_LAUNCH_CHECK();
+    return SMX_OK;
 }
 
 extern "C" int smx_record_ddpg_pixel_nstep_step(const struct smx_record_ddpg_pixel_nstep_step* a, smx_stream_t stream) {

@@ -169,6 +169,64 @@ __global__ __launch_bounds__(256) void uniform_gather_multi_kernel(GatherJobs J,
                          [](long i) { return i; }, wave, nwaves);
 }
 
+// The same sample of a frame-pool replay: parts 0 .. J.n - 1 of the grid gather the field tables as above, two more
+// build pixel (part J.n) and pixel_next (J.n + 1) for the same rows out of the pool -- item i = (sample row i / S, stack
+// position i % S) is one frame of F bytes, moved like a table row: from slot c mod P of the row's actor, c = max(top - S
+// + 1 + i % S, frame_first), top = frame_next (pixel: - n_step).  A drawn row is (base + u) % capacity.
+struct PoolJobs {
+    GatherJobs J;
+    unsigned char* pix[2];
+    int pgran;
+    int pblock0[3];         // first workgroup of the two pool parts, [2] = grid size
+    const unsigned char* pool;
+    long P, F;
+    int actors, S, N;
+    const int64_t *frame_next, *frame_first;
+    const int* frame_actor;
+    long base;
+};
+__global__ __launch_bounds__(256) void uniform_gather_pool_kernel(PoolJobs Q, long capacity, long rows,
+                                                                  const int64_t* __restrict__ idx, uint64_t len,
+                                                                  uint64_t seed, uint64_t offset,
+                                                                  int64_t* __restrict__ idx_out) {
+    const GatherJobs& J = Q.J;
+    auto ring = [=](long i) {
+        long r = idx ? (long)idx[i] : (Q.base + philox_index(offset + (uint64_t)i, len, seed)) % capacity;
+        return r < 0 ? 0 : (r >= capacity ? capacity - 1 : r);
+    };
+    if ((int)blockIdx.x >= Q.pblock0[0]) {
+        const int part = (int)blockIdx.x >= Q.pblock0[1] ? 1 : 0;
+        const long wave = ((long)((int)blockIdx.x - Q.pblock0[part]) * blockDim.x + threadIdx.x) >> 6;
+        const long nwaves = ((long)(Q.pblock0[part + 1] - Q.pblock0[part]) * blockDim.x) >> 6;
+        const int S = Q.S;
+        copy_rows_bytes_part(Q.pool, Q.pix[part], rows * S, Q.F, Q.pgran,
+                             [=](long i) {
+                                 const long r = ring(i / S);
+                                 const int k = (int)(i % S);
+                                 const long top = (long)Q.frame_next[r] - (part == 0 ? Q.N : 0);
+                                 const long lo = (long)Q.frame_first[r];
+                                 long c = top - S + 1 + k;
+                                 c = c < lo ? lo : c;
+                                 int a = Q.frame_actor[r];
+                                 a = a < 0 ? 0 : (a >= Q.actors ? Q.actors - 1 : a);
+                                 return (long)a * Q.P + ((c % Q.P) + Q.P) % Q.P;
+                             },
+                             [](long i) { return i; }, wave, nwaves);
+        return;
+    }
+    int j = 0;
+#pragma unroll
+    for (int k = 1; k < 8; ++k) j += (k < J.n && (int)blockIdx.x >= J.block0[k]) ? 1 : 0;
+    const long wave = ((long)((int)blockIdx.x - J.block0[j]) * blockDim.x + threadIdx.x) >> 6;
+    const long nwaves = ((long)(J.block0[j + 1] - J.block0[j]) * blockDim.x) >> 6;
+    if (idx_out && j == 0)
+        for (long i = (long)((int)blockIdx.x - J.block0[0]) * blockDim.x + threadIdx.x; i < rows;
+             i += (long)(J.block0[1] - J.block0[0]) * blockDim.x)
+            idx_out[i] = idx ? idx[i] : (int64_t)((Q.base + philox_index(offset + (uint64_t)i, len, seed)) % capacity);
+    copy_rows_bytes_part(J.table[j], J.dst[j], rows, J.row_bytes[j], J.gran[j], ring, [](long i) { return i; }, wave,
+                         nwaves);
+}
+
 __global__ __launch_bounds__(256) void window_emit_kernel(const float* __restrict__ src, int actors,
                                                           int T, int width, int start, int n_step,
                                                           int stride, int W, float* __restrict__ dst,
@@ -459,6 +517,23 @@ inline int byte_gran(const void* a, const void* b, long row_bytes) {
     return (u & 15) == 0 ? 16 : ((u & 3) == 0 ? 4 : 1);
 }
 
+// the field tables of a one-launch sample -> J, their workgroups counted from `base` on
+int gather_jobs(const smx_gather_job_t* jobs, int njobs, int64_t rows, GatherJobs& J, int& base) {
+    J.n = njobs;
+    for (int k = 0; k < njobs; ++k) {
+        SMX_REQUIRE(jobs[k].table && jobs[k].dst, SMX_E_NULL);
+        SMX_REQUIRE(jobs[k].row_bytes > 0, SMX_E_SHAPE);
+        J.table[k] = (const unsigned char*)jobs[k].table;
+        J.dst[k] = (unsigned char*)jobs[k].dst;
+        J.row_bytes[k] = (long)jobs[k].row_bytes;
+        J.gran[k] = byte_gran(jobs[k].table, jobs[k].dst, (long)jobs[k].row_bytes);
+        J.block0[k] = base;
+        base += (int)row_blocks_bytes((long)rows, (long)jobs[k].row_bytes);
+    }
+    for (int k = njobs; k <= 8; ++k) J.block0[k] = base;
+    return SMX_OK;
+}
+
 }  // namespace
 
 extern "C" int smx_ring_insert_f32(float* table, int64_t capacity, int32_t width, int64_t cursor,
@@ -520,20 +595,45 @@ extern "C" int smx_uniform_gather_multi(const smx_gather_job_t* jobs, int32_t nj
     SMX_REQUIRE(jobs, SMX_E_NULL);
     SMX_REQUIRE(njobs >= 1 && njobs <= 8 && capacity > 0 && rows > 0 && (idx || (len > 0 && len <= capacity)), SMX_E_SHAPE);
     GatherJobs J;
-    J.n = njobs;
     int base = 0;
-    for (int k = 0; k < njobs; ++k) {
-        SMX_REQUIRE(jobs[k].table && jobs[k].dst, SMX_E_NULL);
-        SMX_REQUIRE(jobs[k].row_bytes > 0, SMX_E_SHAPE);
-        J.table[k] = (const unsigned char*)jobs[k].table;
-        J.dst[k] = (unsigned char*)jobs[k].dst;
-        J.row_bytes[k] = (long)jobs[k].row_bytes;
-        J.gran[k] = byte_gran(jobs[k].table, jobs[k].dst, (long)jobs[k].row_bytes);
-        J.block0[k] = base;
-        base += (int)row_blocks_bytes((long)rows, (long)jobs[k].row_bytes);
-    }
-    for (int k = njobs; k <= 8; ++k) J.block0[k] = base;
+    const int rc = gather_jobs(jobs, njobs, rows, J, base);
+    if (rc != SMX_OK) return rc;
     hipLaunchKernelGGL(uniform_gather_multi_kernel, dim3((unsigned)base), dim3(256), 0, smx_s(stream), J, (long)capacity,
+                       (long)rows, idx, (uint64_t)len, seed, offset, idx_out);
+    SMX_LAUNCH_CHECK();
+    return SMX_OK;
+}
+
+extern "C" int smx_uniform_gather_pool(const smx_gather_job_t* jobs, int32_t njobs, const struct smx_gather_pool* pool,
+                                       int64_t capacity, int64_t rows, const int64_t* idx, int64_t len, uint64_t seed,
+                                       uint64_t offset, int64_t* idx_out, smx_stream_t stream) {
+    SMX_REQUIRE(jobs && pool, SMX_E_NULL);
+    SMX_REQUIRE(pool->pool && pool->frame_next && pool->frame_first && pool->frame_actor && pool->pixel && pool->pixel_next,
+                SMX_E_NULL);
+    SMX_REQUIRE(njobs >= 1 && njobs <= 8 && capacity > 0 && rows > 0 && (idx || (len > 0 && len <= capacity)), SMX_E_SHAPE);
+    const int S = pool->frame_stacks;
+    SMX_REQUIRE(pool->actors > 0 && S > 0 && pool->n_step > 0 && pool->frame_bytes > 0, SMX_E_SHAPE);
+    SMX_REQUIRE(pool->pool_len >= (int64_t)pool->n_step + S + 1 && pool->base >= 0 && pool->base < capacity, SMX_E_SHAPE);
+    SMX_REQUIRE((((uintptr_t)pool->frame_next | (uintptr_t)pool->frame_first) & 7) == 0 &&
+                ((uintptr_t)pool->frame_actor & 3) == 0, SMX_E_ALIGN);
+    PoolJobs Q;
+    int base = 0;
+    const int rc = gather_jobs(jobs, njobs, rows, Q.J, base);
+    if (rc != SMX_OK) return rc;
+    Q.pix[0] = pool->pixel; Q.pix[1] = pool->pixel_next;
+    Q.pool = pool->pool; Q.P = (long)pool->pool_len; Q.F = (long)pool->frame_bytes;
+    Q.actors = pool->actors; Q.S = S; Q.N = pool->n_step;
+    Q.frame_next = pool->frame_next; Q.frame_first = pool->frame_first; Q.frame_actor = pool->frame_actor;
+    Q.base = (long)pool->base;
+    // one unit for both parts: 16 bytes where the frame size, the pool and both destinations allow (4, else 1)
+    const int g0 = byte_gran(pool->pool, pool->pixel, Q.F), g1 = byte_gran(pool->pool, pool->pixel_next, Q.F);
+    Q.pgran = g0 < g1 ? g0 : g1;
+    for (int part = 0; part < 2; ++part) {
+        Q.pblock0[part] = base;
+        base += (int)row_blocks_bytes((long)rows * S, Q.F);
+    }
+    Q.pblock0[2] = base;
+    hipLaunchKernelGGL(uniform_gather_pool_kernel, dim3((unsigned)base), dim3(256), 0, smx_s(stream), Q, (long)capacity,
                        (long)rows, idx, (uint64_t)len, seed, offset, idx_out);
     SMX_LAUNCH_CHECK();
     return SMX_OK;

@@ -1474,6 +1474,86 @@ __global__ __launch_bounds__(256) void ddpg_pixel_step_kernel(DArgs G, PArgs P, 
     });
 }
 
+// ---- DDPG with a camera, frame-pool layout: every frame stored once --------------------------------------------------
+// Per actor a pool of P.hist_len = Pl raw frames (PArgs' hist), the frame with counter i in slot i mod Pl.  f = the
+// counter of the current step's frame, first = that of the episode's reset frame: the frame of episode step u has counter
+// first + u, and the stacked observation under a newest counter `top` is frames max(top - S + 1 + i, first), i < S
+// (stack_sources' rule, counters for steps).  A ring row holds two counters where the stacked layout holds 2 S frames.
+//
+// Grid (1 + X, n).  Workgroup (0, a) runs the step of actor a, renders frame f + 1 from the next state -- the terminal
+// one on done -- once into the pool and (not on done) the last frame of the next acting observation; at a closing step it
+// writes the row's frame_next = f + 1, frame_first = first and its actor.  Workgroups (1 .. X, a) build the rest of the
+// acting observation: its older frames out of the pool (counters f + 2 - S .. f), or on done the new episode's first
+// frame (counter f + 2, rendered from init_state) into the pool and S times into the observation.  The counters read,
+// f + 2 - S .. f, and the two written, f + 1 and f + 2, are S + 1 consecutive ones: distinct slots with Pl >= S + 2.
+struct PoolArgs {
+    long long f, first;
+    int64_t *frame_next, *frame_first;
+    int* frame_actor;
+};
+
+__device__ __forceinline__ unsigned char* pool_slot(const PArgs& P, long a, long long counter) {
+    const long long Pl = P.hist_len;
+    return P.hist + ((size_t)a * Pl + (size_t)(((counter % Pl) + Pl) % Pl)) * P.F;
+}
+
+template <int U>
+__global__ __launch_bounds__(256) void ddpg_pixel_pool_step_kernel(DArgs G, PArgs P, PoolArgs Q, const float* mu,
+                                                                   long long ld_mu) {
+    __shared__ float s_act[SA_MAX];
+    __shared__ float s_sn0;
+    const int tid = threadIdx.x, lane = tid & 63;
+    const long a = blockIdx.y;
+    const int S = P.S, tau = G.t0;
+    const bool emit = tau >= G.N - 1, done = tau + 1 >= G.episode_len;
+    const long long row = emit ? ring_row(G, 0, a) : 0;
+    const long long F = P.F, nu = F / U;
+    unsigned char* obs_a = P.obs_pix + (size_t)a * S * F;
+    alignas(16) unsigned char b[U];
+    if (blockIdx.x == 0) {
+        if (tid < 64 && lane < G.A) ddpg_step_act(G, mu, ld_mu, a, lane, row, s_act);
+        __syncthreads();
+        if (tid < 64) {
+            const float sn0 = ddpg_step_env(G, a, lane, row, s_act);
+            if (lane == 0) s_sn0 = sn0;
+        }
+        if (emit && tid == 64) {
+            Q.frame_next[row] = Q.f + 1;
+            Q.frame_first[row] = Q.first;
+            Q.frame_actor[row] = (int)a;
+        }
+        __syncthreads();
+        const int shift = synth_frame_shift(tau + 1, s_sn0);
+        unsigned char* d0 = pool_slot(P, a, Q.f + 1);
+        unsigned char* d1 = done ? nullptr : obs_a + (size_t)(S - 1) * F;
+        for (long long v = tid; v < nu; v += 256) {
+            render_unit<U>(P, v * U, shift, b);
+            store_unit<U>(d0 + v * U, b);
+            if (d1) store_unit<U>(d1 + v * U, b);
+        }
+        return;
+    }
+    // item q: done: the new episode's first frame -> the pool (q = 0), observation frame q - 1; else observation frame q
+    // <- counter max(f + 2 - S + q, first)
+    const int nq = done ? 1 + S : S - 1;
+    const int shift0 = synth_frame_shift(0, G.init_state[(size_t)a * G.D]);
+    const long long total = (long long)nq * nu, stride = (long long)P.X * 256;
+    for (long long g = (long long)(blockIdx.x - 1) * 256 + tid; g < total; g += stride) {
+        const int q = (int)(g / nu);
+        const long long e = (g - (long long)q * nu) * U;
+        unsigned char* dst;
+        if (done) {
+            dst = q == 0 ? pool_slot(P, a, Q.f + 2) : obs_a + (size_t)(q - 1) * F;
+            render_unit<U>(P, e, shift0, b);
+        } else {
+            dst = obs_a + (size_t)q * F;
+            const long long c = Q.f + 2 - S + q;
+            load_unit<U>(pool_slot(P, a, c < Q.first ? Q.first : c) + e, b);
+        }
+        store_unit<U>(dst + e, b);
+    }
+}
+
 // ---- PPO with a camera: one step of the moving windows plus the frames ---------------------------------------------
 // The record launch of the per-step camera path (the CNN perception, the LSTM step and the actor's layers run between
 // two of them): the sampling head, the environment step, WinArgs' carry rings and -- at a closing step -- the window
@@ -2230,6 +2310,41 @@ extern "C" int smx_synth_ddpg_pixel_step(const struct smx_ddpg_pixel_step* args,
     // (the copy workgroups: sized for the at most 3 S frames of a closing step; one frame's units each at least)
     const PArgs P = pixel_fields(*args, 3LL * args->frame_stacks);
     return launch_pixel<ddpg_pixel_step_kernel<16>, ddpg_pixel_step_kernel<1>>(G, P, a->n, mu, ld_mu, stream);
+}
+
+extern "C" int smx_synth_ddpg_pixel_pool_step(const struct smx_ddpg_pixel_pool_step* args, const float* mu, int64_t ld_mu,
+                                              smx_stream_t stream) {
+    SMX_REQUIRE(args && mu && args->pool && args->obs_pixel && args->frame_next && args->frame_first && args->frame_actor,
+                SMX_E_NULL);
+    const smx_ddpg_rollout_t* a = &args->base;
+    DArgs G;
+    const int rc = common_args(a, G);
+    if (rc != SMX_OK) return rc;
+    SMX_REQUIRE(step_shape_ok(a->n, a->A, ld_mu, a->capacity) && a->n <= 65535, SMX_E_SHAPE);
+    const int S = args->frame_stacks;
+    SMX_REQUIRE(args->C > 0 && args->H > 0 && args->W > 0 && S > 0 && args->pool_len <= 0x7fffffffLL, SMX_E_SHAPE);
+    // a pool that holds every frame a live row can name and the two this launch writes
+    SMX_REQUIRE(args->pool_len >= (int64_t)a->n_step + S + 1, SMX_E_SHAPE);
+    SMX_REQUIRE(args->episode_first >= 0 && args->frame >= args->episode_first, SMX_E_SHAPE);
+    SMX_REQUIRE((((uintptr_t)args->frame_next | (uintptr_t)args->frame_first) & 7) == 0 &&
+                ((uintptr_t)args->frame_actor & 3) == 0, SMX_E_ALIGN);
+    G.steps = 1;
+    PArgs P;
+    memset(&P, 0, sizeof(P));
+    P.C = args->C; P.H = args->H; P.W = args->W; P.S = S; P.hist_len = (int)args->pool_len;
+    P.F = (long long)args->C * args->H * args->W;
+    P.hist = args->pool; P.obs_pix = args->obs_pixel;
+    // (the copy workgroups: the at most 1 + S frames of a terminal step, ~32 KB each)
+    const long long X = ((1LL + S) * P.F + 32767) / 32768;
+    P.X = (int)(X < 1 ? 1 : (X > 64 ? 64 : X));
+    PoolArgs Q;
+    Q.f = args->frame; Q.first = args->episode_first;
+    Q.frame_next = args->frame_next; Q.frame_first = args->frame_first; Q.frame_actor = args->frame_actor;
+    const bool vec = P.F % 16 == 0 && (((uintptr_t)P.hist | (uintptr_t)P.obs_pix) & 15) == 0;
+    hipLaunchKernelGGL(vec ? ddpg_pixel_pool_step_kernel<16> : ddpg_pixel_pool_step_kernel<1>, dim3(1 + P.X, a->n),
+                       dim3(256), 0, smx_s(stream), G, P, Q, mu, (long long)ld_mu);
+    SMX_LAUNCH_CHECK();
+    return SMX_OK;
 }
 
 extern "C" int smx_synth_ppo_pixel_window_step(const struct smx_synth_ppo_pixel_window_step* args, const float* mu,

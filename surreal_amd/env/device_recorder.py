@@ -114,6 +114,11 @@ class _DeviceRecorder(object):
             self.hist_pos = 0
         self._sets = [_StagingSet(self.n, self.D, self.device, self.F) for _ in range(2)]
         self._next = 0
+        # a frame-pool replay (replay.device_frame_pool): the actors whose current frame (hist's slot hist_pos: begin,
+        # reset) has yet to enter the pool, and those whose episode restarted on the frame they have
+        self._pool = None
+        self._prime = np.zeros(self.n, dtype=bool)
+        self._refirst = np.zeros(self.n, dtype=bool)
 
     @property
     def observation(self):
@@ -164,6 +169,7 @@ class _DeviceRecorder(object):
             self.hist_pos = 0
             self.hist[:, 0].copy_(f)
             self.obs_pixel.copy_(f.repeat(1, self.frame_stacks, 1, 1))
+            self._prime[:] = True
         self.cur_obs.copy_(self._device_rows(obs, self.D))
         self.t[:] = 0
 
@@ -179,6 +185,11 @@ class _DeviceRecorder(object):
         rows = self._device_rows(obs, self.D) if obs is not None else None
         f = self._device_frames(frames) if frames is not None else None
         self.t[mask] = 0
+        if self.pixel is not None:
+            if f is not None:
+                self._prime |= mask
+            else:
+                self._refirst |= mask
         if obs is not None:
             m = torch.as_tensor(mask).to(self.device)
             self.cur_obs.copy_(torch.where(m.view(-1, 1), rows, self.cur_obs))
@@ -322,6 +333,50 @@ class _DeviceRecorder(object):
     def _advance(self, dones):
         self.t = np.where(dones, 0, self.t + 1).astype(np.int32)
 
+    # ---- the frame-pool layout (replay/frame_pool.py) -------------------------------------------------------------
+    def _pool_reserve(self, replay, dones, rank_host, rows, shapes):
+        """one DDPG step into a frame-pool replay, before its launch: the actors' counters f (newest frame) and first
+        (the episode's reset frame) on the host and -- two buffers [2, n], swapped per launch -- on the device; the
+        step's plan for the replay's ledger (reserve_frame_pool retires what the step overwrites); the frames begin() /
+        reset() left in hist's current slot enter the pool first -> reserve_frame_pool's handle with the launch's
+        counters_in / counters_out"""
+        from surreal_amd.replay.frame_pool import oldest_frame
+        n, N, S = self.n, self.n_step, self.frame_stacks
+        if n > replay.memory_size:
+            raise ValueError('record: %d actors exceed the replay ring of %d rows (all of them may close in one step)'
+                             % (n, replay.memory_size))
+        pl = self._pool
+        if pl is None or pl['replay'] is not replay:
+            start = replay.frame_pool['counter'].copy() if replay.frame_pool is not None else np.full(n, -1, np.int64)
+            pl = self._pool = dict(replay=replay, f=start, first=start.copy(), side=0,
+                                   dev=[torch.zeros(2, n, dtype=torch.int64, device=self.device) for _ in range(2)])
+            self._prime[:] = True
+        f, first = pl['f'], pl['first']
+        steps, prime = [], self._prime.copy()
+        moved = prime.any() or self._refirst.any()
+        if moved:
+            f[prime] += 1
+            first[prime | self._refirst] = f[prime | self._refirst]
+            steps.append((0, f.copy(), f.copy()))
+            self._prime[:] = False
+            self._refirst[:] = False
+        closes = np.asarray(rank_host) >= 0
+        oldest = np.where(closes, oldest_frame(f + 1, first, N, S), np.iinfo(np.int64).max)
+        after = f + np.where(dones, 2, 1)
+        steps.append((rows, after, oldest))
+        h = replay.reserve_frame_pool(steps, shapes, n, self.pixel, S, N)
+        if moved:
+            C, H, W = self.pixel
+            idx = torch.as_tensor(np.flatnonzero(prime)).to(self.device)
+            slots = torch.as_tensor(f[prime] % h['pool'].shape[1]).to(self.device)
+            h['pool'].view(n, -1, C, H, W)[idx, slots] = self.hist[idx, self.hist_pos]
+            pl['dev'][pl['side']].copy_(torch.as_tensor(np.stack([f, first])))
+        h.update(counters_in=pl['dev'][pl['side']], counters_out=pl['dev'][pl['side'] ^ 1], frame_shape=self.pixel)
+        pl['side'] ^= 1
+        pl['first'] = np.where(dones, f + 2, first)
+        pl['f'] = after
+        return h
+
 
 class DeviceWindowRecorder(_DeviceRecorder):
     """PPO's moving windows (ExpSenderWrapperMultiStepMovingWindowWithInfo) of n host-stepped actors, written into the
@@ -399,7 +454,9 @@ class DeviceNStepRecorder(_DeviceRecorder):
     """DDPG's n-step transitions (ExpSenderWrapperSSARNStepBootstrap, its fill-up discount exponents included) of n
     host-stepped actors, written into the uniform replay's device ring in SyntheticVecEnv.ddpg_rollout_into's layout: obs /
     obs_next [D], actions [A], rewards, dones.  The reward is the wrapper's fp64 sum in step order, rounded once.  With
-    pixel=(C, H, W), frame_stacks=S (see DeviceWindowRecorder) also uint8 pixel / pixel_next [S*C, H, W]."""
+    pixel=(C, H, W), frame_stacks=S (see DeviceWindowRecorder) also uint8 pixel / pixel_next [S*C, H, W] -- or, into a
+    frame-pool replay (replay.device_frame_pool), every frame once in the replay's pool and two counters a row
+    (smx_record_ddpg_pixel_pool_nstep_step): begin / record / observation / reset are the same calls."""
 
     def __init__(self, n, D, A, n_step, gamma, kernels=None, device=None, pixel=None, frame_stacks=1):
         super().__init__(n, D, A, n_step, kernels, device, pixel, frame_stacks)
@@ -420,6 +477,16 @@ class DeviceNStepRecorder(_DeviceRecorder):
         """one step of all actors -> the number of transitions written (arguments as DeviceWindowRecorder.record)"""
         actions = self._step_rows(actions, self.A, 'actions')
         dones, rows, dev, t_host, rank_host = self._stage(rewards, dones, obs_next, obs_reset, frames_next, frames_reset)
+        if self.pixel is not None and getattr(replay, 'frame_pool_on', False):
+            # the frame-pool layout: every frame once in the replay's pool, which is the frame history as well
+            low = {k: v for k, v in self.shapes.items() if k not in ('pixel', 'pixel_next')}
+            h = self._pool_reserve(replay, dones, rank_host, rows, low)
+            r = dict(h, t_host=t_host, rank_host=rank_host, rows=rows, cur_obs=self.cur_obs, actions=actions,
+                     n_step=self.n_step, gpow=self.gpow, carry=self.carry, obs_pixel=self.obs_pixel, **dev)
+            self.K.record_ddpg_pixel_pool_nstep_step(r, copy_workgroups=copy_workgroups, monitor=monitor)
+            replay.commit_frame_pool(rows, self._pool['f'])
+            self._moved(dones, monitor)
+            return rows
         tables, cursor = self._ring(replay, rows, self.shapes)
         r = dict(dev, t_host=t_host, rank_host=rank_host, rows=rows, cur_obs=self.cur_obs, actions=actions,
                  n_step=self.n_step, gpow=self.gpow, carry=self.carry, tables=tables, cursor=cursor)

@@ -253,6 +253,7 @@ class SyntheticVecEnv(object):
             if self._ddpg.get(k) is not None:
                 self._ddpg[k].zero_()
         self._ddpg['hist_pos'] = None         # (a camera's frame history is primed again at the next call)
+        self._ddpg['pool_replay'] = None      # (so is its place in a replay's frame pool)
         self._ppo = {}                        # (the open windows: a new episode has none)
         return self.state
 
@@ -780,7 +781,9 @@ class SyntheticVecEnv(object):
         stacked frames, the actor, and ONE launch (smx_synth_ddpg_pixel_step) that also renders the step's frame into
         a history of n_step + S raw frames per actor, writes the closing transitions' uint8 'pixel' / 'pixel_next'
         [S*C, H, W] into the ring and the stacked observation of the next step.  The history carries from call to call
-        like the open transitions.
+        like the open transitions.  Into a frame-pool replay (replay.device_frame_pool; replay/frame_pool.py) the launch
+        is smx_synth_ddpg_pixel_pool_step: the step's frame goes ONCE into the replay's pool, which is the history as
+        well, and the closing rows carry two counters in place of the stacked frames; such a call may go round the ring.
         With per-actor episode clocks (the ONE-launch route only): the call's row table from the clocks
         (smx_actor_clock_rows_i32), then smx_synth_ddpg_rollout_clocks_f32 -- as in ppo_rollout_into."""
         route, refusal = self._ddpg_route(agent, reference)
@@ -788,7 +791,10 @@ class SyntheticVecEnv(object):
             raise refusal[0](refusal[1])
         K, n, A, pn = self.K, self.n, self.A, self.param_noise
         shapes, dtypes = {'obs': (self.D,), 'obs_next': (self.D,), 'actions': (A,), 'rewards': (), 'dones': ()}, None
-        if route == 'camera':
+        # (a frame-pool replay, replay.device_frame_pool: the camera rows are counters into its pool, which is this
+        # route's frame history as well)
+        pool = route == 'camera' and bool(getattr(replay, 'frame_pool_on', False))
+        if route == 'camera' and not pool:
             (C, H, W), S = self.pixel, self.frame_stacks
             shapes.update(pixel=(S * C, H, W), pixel_next=(S * C, H, W))
             dtypes = {'pixel': torch.uint8, 'pixel_next': torch.uint8}
@@ -805,10 +811,16 @@ class SyntheticVecEnv(object):
             # the closing steps of this call (the clock is shared by all actors): n of them per closing step
             m, t = self._closing_steps(T, lambda t: t >= N - 1)
             rows = n * m
-            if rows > replay.memory_size:
+            # (the frame-pool route is a launch per step, n rows each: a call may go round the ring)
+            if rows > replay.memory_size and not (pool and n <= replay.memory_size):
                 raise ValueError('ddpg_rollout_into: %d actors x %d closing steps = %d transitions exceed the replay '
                                  'capacity %d (two of them would share a row)' % (n, m, rows, replay.memory_size))
-        tables, cursor, cap = replay.reserve_ring(rows, shapes, dtypes)
+        if pool:
+            plan = self._frame_pool_plan(replay, T, N)
+            handle = replay.reserve_frame_pool(plan['steps'], shapes, n, self.pixel, self.frame_stacks, N)
+            tables, cursor, cap = handle['tables'], handle['cursor'], handle['capacity']
+        else:
+            tables, cursor, cap = replay.reserve_ring(rows, shapes, dtypes)
         d = self._ddpg
         if d.get('n_step') != N:
             f = lambda *s: torch.zeros(*s, device=self.device)  # noqa: E731
@@ -838,6 +850,10 @@ class SyntheticVecEnv(object):
             if d.get('pk') is None or d['pk'].numel() != K.epoch_packed_numel(actor):
                 d['pk'] = torch.zeros(K.epoch_packed_numel(actor), device=self.device)
             K.epoch_pack([(actor, d['pk'])])        # (the agent's parameters only change between rollouts)
+        if pool:
+            self._ddpg_pixel_steps(agent, r, T, N, cap, eps, ns, pool=(replay, handle, plan))
+            replay.commit_frame_pool(rows, plan['frames'][-1][0])
+            return rows
         if route == 'camera':
             self._ddpg_pixel_steps(agent, r, T, N, cap, eps, ns)
         elif route == 'launch':
@@ -870,28 +886,75 @@ class SyntheticVecEnv(object):
         replay.commit_ring(rows)
         return rows
 
-    def _ddpg_pixel_steps(self, agent, r, T, N, cap, eps, ns=False):
+    def _frame_pool_plan(self, replay, T, N):
+        """the next T steps of the shared clock in a replay's frame pool -> {'frames': [(f, first)] before each step and
+        after the last: the counter of the current frame and of the episode's reset frame; 'steps': what
+        reserve_frame_pool takes; 'prime': whether the current frame must be written first (first use of this replay,
+        after reset())}.  A step writes the frame f + 1, a terminal one also the new episode's first, f + 2"""
+        from surreal_amd.replay.frame_pool import oldest_frame
+        d, S, fp = self._ddpg, self.frame_stacks, replay.frame_pool
+        f = int(fp['counter'][0]) if fp is not None else -1
+        prime = d.get('pool_replay') is not replay
+        steps, frames = [], []
+        if prime:
+            f += 1                               # (the current frame: the oldest one any stack of this episode reaches)
+            steps.append((0, f, f))
+        first = f if prime else d['pool_first']
+        for tau in self._clock_walk(T)[:-1]:
+            frames.append((f, first))
+            done = tau + 1 >= self.episode_len
+            oldest = int(oldest_frame(f + 1, first, N, S))
+            f += 2 if done else 1
+            steps.append((self.n if tau >= N - 1 else 0, f, oldest))
+            first = f if done else first
+        frames.append((f, first))
+        return dict(frames=frames, steps=steps, prime=prime)
+
+    def _ddpg_pixel_steps(self, agent, r, T, N, cap, eps, ns=False, pool=None):
         """ddpg_rollout_into's camera path: per step perception -> actor -> smx_synth_ddpg_pixel_step.  The history
         (hist [n, N + S, C, H, W], the current step's frame in slot hist_pos) is primed on first use and after reset():
-        the current frame in every slot, the actors' first observation that frame S times (N + S + 1 launches, once)"""
+        the current frame in every slot, the actors' first observation that frame S times (N + S + 1 launches, once).
+        pool = (replay, reserve_frame_pool's handle, _frame_pool_plan's plan): the frame-pool layout
+        (smx_synth_ddpg_pixel_pool_step) -- the history is the replay's pool, primed with the current frame alone"""
         from surreal_amd.model.cnn_stem import CnnStem
         K, n, d, model = self.K, self.n, self._ddpg, agent.model
-        Hd = N + self.frame_stacks
-        self._frame_history(d, Hd)
+        if pool is None:
+            Hd = N + self.frame_stacks
+            d['pool_replay'] = None
+            self._frame_history(d, Hd)
+        else:
+            replay, handle, plan = pool
+            (C, H, W), S = self.pixel, self.frame_stacks
+            if d.get('obs_pixel') is None or tuple(d['obs_pixel'].shape) != (n, S * C, H, W):
+                d['obs_pixel'] = torch.zeros((n, S * C, H, W), device=self.device, dtype=torch.uint8)
+            if plan['prime']:
+                f0 = plan['frames'][0][0]
+                slot = handle['pool'].view(n, -1, C, H, W)[:, f0 % handle['pool'].shape[1]]
+                K.synth_frames(self.state[:, 0], self.t, slot)
+                d['obs_pixel'].copy_(slot.repeat(1, S, 1, 1))
+                d['pool_replay'], d['pool_first'], d['hist_pos'] = replay, f0, None
+            r.update({k: handle[k] for k in ('pool', 'frame_next', 'frame_first', 'frame_actor')},
+                     frame_shape=self.pixel)
         p = model.cnn
         key = (n, model.input_dim, p.C, p.H, p.W, p.c1, p.c2, p.feat)
         if d.get('perc_key') != key:        # the perception's workspace, cached across steps and calls
             d['perc_key'] = key
             d['cnn_ws'] = CnnStem.workspace(model.cnn, n, self.device, backward=False)
             d['x'] = torch.empty(n, model.input_dim, device=self.device)
-        r.update(hist=d['hist'], obs_pixel=d['obs_pixel'])
+        r.update(obs_pixel=d['obs_pixel'], **({} if pool else dict(hist=d['hist'])))
         for s in range(T):
             model.perception_into(d['obs_pixel'], self.state, d['cnn_ws'], d['x'])
             mu = model.forward_actor(d['x'])
-            r['t'], r['hist_pos'] = self.t, d['hist_pos']
+            r['t'] = self.t
             r['eps'] = None if eps is None else eps[s]
-            K.synth_ddpg_pixel_step(r, mu, **self._mon(1), **self._noi(1, ns))
-            d['hist_pos'] = (d['hist_pos'] + 1) % Hd
+            if pool:
+                r['frame'], r['episode_first'] = plan['frames'][s]
+                K.synth_ddpg_pixel_pool_step(r, mu, **self._mon(1), **self._noi(1, ns))
+                d['pool_first'] = plan['frames'][s + 1][1]
+            else:
+                r['hist_pos'] = d['hist_pos']
+                K.synth_ddpg_pixel_step(r, mu, **self._mon(1), **self._noi(1, ns))
+                d['hist_pos'] = (d['hist_pos'] + 1) % Hd
             if self.t >= N - 1:
                 r['cursor'] = (r['cursor'] + n) % cap
             self._advance()

@@ -593,6 +593,34 @@ class HipKernels(object):
         L.call('smx_uniform_gather_multi', arr, len(tables), cap, rows, L.ptr(idx), int(length), int(seed), int(offset),
                L.ptr(idx_out), self._st())
 
+    def uniform_gather_pool(self, tables, outs, pool, pixel, pixel_next, length, seed, offset, base, idx=None,
+                            idx_out=None):
+        """uniform_gather_multi for a frame-pool replay, ONE launch (smx_uniform_gather_pool): the field tables as there,
+        and for the same rows pixel / pixel_next uint8 [rows, S*F] built from the pool.  pool: the replay's frame pool
+        (UniformReplay.frame_pool): 'pool' uint8 [n, P, F], 'frame_next' / 'frame_first' int64 [capacity],
+        'frame_actor' int32 [capacity], 'frame_stacks', 'n_step'.  A drawn row is (base + u) % capacity, u the draw of
+        uniform_indices(length, seed, offset)"""
+        arr = (L.GatherJob * len(tables))()
+        cap, rows = tables[0].shape[0], outs[0].shape[0]
+        for k, (t, o) in enumerate(zip(tables, outs)):
+            assert t.dtype == o.dtype and o.is_contiguous() and t.shape[0] == cap and o.shape[0] == rows
+            arr[k].table, arr[k].dst, arr[k].row_bytes = L.ptr(t), L.ptr(o), t.shape[1] * t.element_size()
+        fp, S = pool['pool'], int(pool['frame_stacks'])
+        n, P, F = fp.shape
+        assert fp.dtype == torch.uint8 and fp.is_contiguous()
+        for k, dt in (('frame_next', torch.int64), ('frame_first', torch.int64), ('frame_actor', torch.int32)):
+            assert pool[k].dtype == dt and pool[k].is_contiguous() and pool[k].numel() == cap, k
+        for o in (pixel, pixel_next):
+            assert o.dtype == torch.uint8 and o.is_contiguous() and o.numel() == rows * S * F
+        q = L.GatherPool()
+        q.pool, q.pool_len, q.frame_bytes = L.ptr(fp), P, F
+        q.actors, q.frame_stacks, q.n_step = n, S, int(pool['n_step'])
+        q.frame_next, q.frame_first, q.frame_actor = (L.ptr(pool[k]) for k in ('frame_next', 'frame_first',
+                                                                               'frame_actor'))
+        q.pixel, q.pixel_next, q.base = L.ptr(pixel), L.ptr(pixel_next), int(base)
+        L.call('smx_uniform_gather_pool', arr, len(tables), ctypes.byref(q), cap, rows, L.ptr(idx), int(length),
+               int(seed), int(offset), L.ptr(idx_out), self._st())
+
     def philox4x32_10(self, ctr_key, out):
         """ctr_key [n, 6] int32 (bit patterns of uint32) -> out [n, 4] int32: the sampler's generator by itself"""
         L.call('smx_philox4x32_10', L.ptr(ctr_key), ctr_key.shape[0], L.ptr(out), self._st())
@@ -1018,6 +1046,31 @@ class HipKernels(object):
         p.base = self._ddpg_args(r, 1, monitor=monitor, noise=noise)
         L.call('smx_synth_ddpg_pixel_step', ctypes.byref(p), L.ptr(mu), _row_stride(mu, mu.shape[1]), self._st())
 
+    def synth_ddpg_pixel_pool_step(self, r, mu, monitor=None, noise=None):
+        """synth_ddpg_pixel_step in the frame-pool layout (include/surreal_amd.h smx_synth_ddpg_pixel_pool_step): r holds,
+        in place of hist / hist_pos, pool uint8 [n, P, F] with frame (the counter of the current step's frame) and
+        episode_first (that of the episode's reset frame), and the ring's counter columns frame_next / frame_first int64
+        [capacity], frame_actor int32 [capacity]; obs_pixel uint8 [n, S*C, H, W] as there.  The ring tables hold no
+        'pixel' / 'pixel_next'"""
+        pool, obs = r['pool'], r['obs_pixel']
+        n, P, F = pool.shape
+        C, H, W = r['frame_shape']
+        S = obs.shape[1] // C
+        cap = r['tables']['obs'].shape[0]
+        assert C * H * W == F and tuple(obs.shape) == (n, S * C, H, W) and r['state'].shape[0] == n
+        for k in (pool, obs):
+            assert k.dtype == torch.uint8 and k.is_contiguous()
+        for k, dt in (('frame_next', torch.int64), ('frame_first', torch.int64), ('frame_actor', torch.int32)):
+            assert r[k].dtype == dt and r[k].is_contiguous() and r[k].numel() == cap, k
+        p = L.DdpgPixelPoolStep()
+        p.base = self._ddpg_args(r, 1, monitor=monitor, noise=noise)
+        p.C, p.H, p.W, p.frame_stacks = C, H, W, S
+        p.pool_len, p.frame, p.episode_first = P, int(r['frame']), int(r['episode_first'])
+        p.pool, p.obs_pixel = L.ptr(pool), L.ptr(obs)
+        p.frame_next, p.frame_first, p.frame_actor = L.ptr(r['frame_next']), L.ptr(r['frame_first']), \
+            L.ptr(r['frame_actor'])
+        L.call('smx_synth_ddpg_pixel_pool_step', ctypes.byref(p), L.ptr(mu), _row_stride(mu, mu.shape[1]), self._st())
+
     @staticmethod
     def synth_ppo_pixel_window_step_supported(A):
         """the actions smx_synth_ppo_pixel_window_step takes (one thread each, A <= SMX_PPO_PIXEL_STEP_MAX_A)"""
@@ -1185,6 +1238,37 @@ class HipKernels(object):
         self._record_camera_args(p, r, 1)
         p.copy_workgroups = int(copy_workgroups)
         L.call('smx_record_ddpg_pixel_nstep_step', ctypes.byref(p), self._st())
+
+    def record_ddpg_pixel_pool_nstep_step(self, r, copy_workgroups=0, monitor=None):
+        """record_ddpg_pixel_nstep_step in the frame-pool layout (include/surreal_amd.h
+        smx_record_ddpg_pixel_pool_nstep_step): r holds, in place of hist / hist_pos and the 'pixel' / 'pixel_next'
+        tables, pool uint8 [n, P, F], counters_in / counters_out int64 [2, n] (f | first before and after the step: two
+        buffers) and the ring's frame_next / frame_first int64 [capacity], frame_actor int32 [capacity]"""
+        p = L.RecordDdpgPixelPoolNstepStep()
+        self._record_ddpg_args(p, r, monitor)
+        pool, obs = r['pool'], r['obs_pixel']
+        n, P, F = pool.shape
+        C, H, W = r['frame_shape']
+        S = obs.shape[1] // C
+        cap = r['tables']['obs'].shape[0]
+        assert C * H * W == F and tuple(obs.shape) == (n, S * C, H, W) and r['cur_obs'].shape[0] == n
+        for x in (pool, obs):
+            assert x.dtype == torch.uint8 and x.is_contiguous()
+        for k, dt in (('frame_next', torch.int64), ('frame_first', torch.int64), ('frame_actor', torch.int32)):
+            assert r[k].dtype == dt and r[k].is_contiguous() and r[k].numel() == cap, k
+        for k in ('counters_in', 'counters_out'):
+            assert r[k].dtype == torch.int64 and r[k].is_contiguous() and r[k].numel() == 2 * n, k
+        for k in ('frames_next', 'frames_reset'):
+            x = r.get(k)
+            assert k == 'frames_reset' or x is not None, k
+            assert x is None or (x.dtype == torch.uint8 and x.is_contiguous() and x.numel() == n * F), k
+        p.C, p.H, p.W, p.frame_stacks, p.pool_len, p.copy_workgroups = C, H, W, S, P, int(copy_workgroups)
+        p.step_frame_next, p.step_frame_reset = L.ptr(r['frames_next']), L.ptr(r.get('frames_reset'))
+        p.pool, p.obs_pixel = L.ptr(pool), L.ptr(obs)
+        p.counters_in, p.counters_out = L.ptr(r['counters_in']), L.ptr(r['counters_out'])
+        p.frame_next, p.frame_first, p.frame_actor = L.ptr(r['frame_next']), L.ptr(r['frame_first']), \
+            L.ptr(r['frame_actor'])
+        L.call('smx_record_ddpg_pixel_pool_nstep_step', ctypes.byref(p), self._st())
 
     def synth_env_step(self, state, init_state, actions, t, episode_len, slot, obs_roll, act_roll,
                        rew_roll, done_roll, monitor=None):
