@@ -1434,6 +1434,30 @@ int smx_synth_ppo_window_rollout_clocks_f32(const struct smx_synth_ppo_window_ro
 int smx_synth_ddpg_rollout_clocks_f32(const smx_ddpg_rollout_t* args, const struct smx_ddpg_actor_variant* variant,
                                       const struct smx_actor_clocks* clocks, smx_stream_t stream);
 
+/* The dynamics of the synthetic environment, by task.  SMX_TASK_DRIFT: smx_synth_env_step_f32's (every element decays on
+ * its own; a workload).  SMX_TASK_REACH (surreal_amd/env/tasks.py holds the one definition): A point masses are steered to
+ * A goals, D = 3 A, the state row is [p (A) | v (A) | g (A)]; fp32, no contraction, each product rounded before the sum:
+ *   a = clip(action, -1, 1);  v'[j] = clamp((0.9f v[j]) + (0.2f a[j]), -1, 1);  p'[j] = clamp(p[j] + (0.1f v'[j]), -10, 10);
+ *   g'[j] = g[j];  d[j] = p'[j] - g[j];  reward = (float)(-(sum_j d[j]^2 + 0.01 sum_j a[j]^2)), both sums in fp64, j
+ *   ascending, one term at a time;  done and the reset as in smx_synth_env_step_f32.
+ * smx_synth_task_supported: 1 where the task entry points below take (task, D, A) -- DRIFT: D, A > 0; REACH: D == 3 A
+ * and A <= 21 (a row's elements sit in one wavefront) -- else 0 (an unknown task too).
+ * The three entry points take the arguments of smx_synth_env_step_f32, smx_synth_ppo_window_rollout_f32 and
+ * smx_synth_ddpg_rollout_f32 (the plain actor: no variant) and a task.  With SMX_TASK_DRIFT each forwards to that entry
+ * point.  What smx_synth_task_supported refuses returns SMX_E_UNSUPPORTED before any launch; every other check is the
+ * forwarded entry point's.  4, 8 and 16 actors per workgroup give the same bits. */
+#define SMX_TASK_DRIFT 0
+#define SMX_TASK_REACH 1
+int32_t smx_synth_task_supported(int32_t task, int32_t D, int32_t A);
+int smx_synth_task_env_step_f32(float* state, const float* init_state, const float* actions,
+                                int32_t n, int32_t D, int32_t A, int32_t t, int32_t episode_len,
+                                int32_t slot, int32_t T, float* obs_roll, float* act_roll,
+                                float* rew_roll, float* done_roll, const struct smx_episode_monitor* mon,
+                                int32_t task, smx_stream_t stream);
+int smx_synth_ppo_window_rollout_task_f32(const struct smx_synth_ppo_window_rollout* args, int32_t task,
+                                          smx_stream_t stream);
+int smx_synth_ddpg_rollout_task_f32(const smx_ddpg_rollout_t* args, int32_t task, smx_stream_t stream);
+
 /* Parameter-space noise of the device actors (surreal/agent/param_noise.py): a population of perturbed actors, one per
  * AGENT -- a group of consecutive actors that share one perturbation, as the actors of one reference agent process do
  * (an agent here spans at least the 4 actors of one MFMA row block, where the reference's spans one environment).  The

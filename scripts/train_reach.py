@@ -1,0 +1,205 @@
+"""The on-device loop on a task a policy can learn: `reach` (surreal_amd/env/tasks.py).
+
+    python scripts/train_reach.py --algo ppo|ddpg [--actors N --J J --episode-len L --iters K --seed S --out FILE]
+
+Per iteration: one rollout chunk of all actors inside one launch (ppo_rollout_into / ddpg_rollout_into on a
+SyntheticVecEnv(task='reach') with a DeviceEpisodeMonitor and an exploration noise stream attached) -> the replay's device
+ring -> learn -> the parameters back to the agent (publish + fetch).  Every --eval-every iterations the deterministic
+policy (an agent in mode 'eval_deterministic') is run from the reset states of the same seeds with step(), one episode.
+
+Prints first the zero-action return and the PD controller's return on the same seeds, from the host env; then one JSON
+line per evaluation: env steps, learner iterations, the training return from the monitor, the evaluation return, the share
+of the zero -> PD gap the evaluation return closes, wall time."""
+import argparse
+import json
+import os
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
+
+from surreal_amd.env import tasks as TK  # noqa: E402
+from surreal_amd.env.synthetic_env import SyntheticEnv, SyntheticVecEnv  # noqa: E402
+
+HIDDEN = [32, 32]
+DEFAULT_ITERS = {'ppo': 60, 'ddpg': 60}
+
+
+def host_return(J, episode_len, seeds, controller):
+    """the mean episode return of controller(state) -> action from each seed's reset state, on the host env"""
+    total = []
+    for seed in seeds:
+        env = SyntheticEnv(3 * J, J, episode_len=episode_len, seed=seed, task='reach')
+        env._reset()
+        ret, done = 0.0, False
+        while not done:
+            _, r, done, _ = env._step(controller(env.state))
+            ret += r
+        total.append(ret)
+    return float(np.mean(total))
+
+
+def baselines(J, episode_len, seeds):
+    return {'zero_action_return': host_return(J, episode_len, seeds, lambda s: np.zeros(J, np.float32)),
+            'pd_return': host_return(J, episode_len, seeds, TK.reach_pd_action)}
+
+
+def ppo_configs(D, A, n, folder):
+    from surreal_amd.main.ppo_configs import ppo_learner_config, ppo_env_config, ppo_session_config
+    lc = ppo_learner_config()
+    lc.model.actor_fc_hidden_sizes = lc.model.critic_fc_hidden_sizes = list(HIDDEN)
+    lc.algo.rnn.if_rnn_policy = False
+    lc.algo.n_step, lc.algo.stride = 10, 10
+    lc.algo.gamma = 0.95
+    lc.algo.ppo_mode = 'clip'
+    lc.algo.network.lr_actor, lc.algo.network.lr_critic = 3e-3, 3e-3
+    lc.algo.network.anneal.min_lr = 3e-3
+    lc.algo.consts.init_log_sig = -0.5
+    lc.replay.batch_size = 64
+    lc.replay.memory_size = 8 * n
+    lc.replay.sampling_start_size = 64
+    lc.parameter_publish.exp_interval = 64
+    return lc, ppo_env_config(D, A), ppo_session_config(folder)
+
+
+def ddpg_configs(D, A, n, folder):
+    from surreal_amd.main.ddpg_configs import ddpg_learner_config, ddpg_env_config, ddpg_session_config
+    lc = ddpg_learner_config()
+    lc.model.actor_fc_hidden_sizes = lc.model.critic_fc_hidden_sizes = list(HIDDEN)
+    # (a step's reward reaches -10 and more: a critic that learns fast and a slow actor; with the critic at the default
+    # 1e-3 the actor saturated at a clip before the critic meant anything)
+    lc.algo.n_step, lc.algo.gamma = 3, 0.95
+    lc.algo.network.lr_actor, lc.algo.network.lr_critic = 1e-4, 1e-2
+    lc.algo.network.target_update = {'type': 'soft', 'tau': 0.01}
+    lc.algo.exploration.noise_type, lc.algo.exploration.max_sigma = 'normal', 1.0
+    lc.replay.batch_size = 256
+    lc.replay.memory_size = 64 * 1024
+    return lc, ddpg_env_config(D, A, num_agents=n), ddpg_session_config(folder)
+
+
+class Loop(object):
+    """the loop of one algorithm: the training env, agent, learner and replay, and the evaluation pair"""
+
+    def __init__(self, algo, actors, J, episode_len, seed, device=None, folder='/tmp/surreal_amd_reach'):
+        torch.manual_seed(seed)
+        self.algo, self.n, self.J, self.L = algo, actors, J, episode_len
+        D, A = 3 * J, J
+        kw = dict(device=device) if device is not None else {}
+        if algo == 'ppo':
+            from surreal_amd.agent import PPOAgent as Agent
+            from surreal_amd.learner import PPOLearner as Learner
+            from surreal_amd.replay import FIFOReplay as Replay
+            cfg = ppo_configs(D, A, actors, folder)
+        else:
+            from surreal_amd.agent import DDPGAgent as Agent
+            from surreal_amd.learner.ddpg import DDPGLearner as Learner
+            from surreal_amd.replay import UniformReplay as Replay
+            cfg = ddpg_configs(D, A, actors, folder)
+        self.lc = cfg[0]
+        self.learner = Learner(*cfg)
+        self.replay = Replay(*cfg)
+        self.agent = Agent(*cfg, agent_id=0, agent_mode='training')
+        self.eval_agent = Agent(*cfg, agent_id=1, agent_mode='eval_deterministic')
+        for ag in (self.agent, self.eval_agent):
+            ag.attach_learner(self.learner)
+            ag.fetch_parameter()
+        seeds = list(range(actors))
+        self.venv = SyntheticVecEnv(actors, D, A, episode_len=episode_len, seeds=seeds, task='reach', **kw)
+        self.monitor = self.venv.attach_monitor(capacity=8)
+        self.venv.attach_noise(seed=seed + 1)
+        self.eval_env = SyntheticVecEnv(actors, D, A, episode_len=episode_len, seeds=seeds, task='reach', **kw)
+        self.eval_monitor = self.eval_env.attach_monitor(capacity=2)
+        self.env_steps = self.learns = 0
+        self.T = episode_len                       # a chunk: one episode of every actor
+
+    def iterate(self):
+        """one chunk -> replay -> learn -> parameters to the agent"""
+        lc, B = self.lc, self.lc.replay.batch_size
+        if self.algo == 'ppo':
+            self.venv.ppo_rollout_into(self.agent, self.replay, self.T)
+            while len(self.replay) >= B:
+                self.learner.learn(self.venv.to_batch(self.replay.sample_batch(B, copy=False)))
+                self.learns += 1
+        else:
+            self.venv.ddpg_rollout_into(self.agent, self.replay, self.T)
+            if len(self.replay) >= 4 * B:
+                stage = self.learner.staging_fields(B)
+                for _ in range(self.T):
+                    f = self.replay.sample_batch(B, out=stage)
+                    self.learner.learn({'obs': {'low_dim': {'flat_inputs': f['obs']}},
+                                        'obs_next': {'low_dim': {'flat_inputs': f['obs_next']}}, 'actions': f['actions'],
+                                        'rewards': f['rewards'].view(B, 1), 'dones': f['dones'].view(B, 1)})
+                    self.learns += 1
+        self.env_steps += self.n * self.T
+        self.learner.publish_parameter(self.learns, message='chunk')
+        self.agent.fetch_parameter()
+
+    def training_return(self):
+        self.monitor.poll()
+        return self.monitor.mean_reward(last=1)
+
+    def evaluate(self):
+        """the deterministic policy's mean episode return over the reset states of all actors (one episode, step())"""
+        ag, env = self.eval_agent, self.eval_env
+        ag.fetch_parameter()
+        env.reset()
+        for _ in range(self.L):
+            if self.algo == 'ppo':
+                actions, _ = ag.act_batch(env.state, eps=None)
+            else:
+                actions = ag.model.forward_actor(env.state)
+            env.step(actions)
+        polled = self.eval_monitor.poll()
+        assert len(polled) == self.n and all(steps == self.L for _, _, steps in polled)
+        return float(np.mean([r for _, r, _ in polled]))
+
+
+def train(algo, actors=64, J=2, episode_len=50, iters=None, seed=0, eval_every=10, device=None, log=print):
+    """-> (the baselines, the curve: one dict per evaluation)"""
+    iters = DEFAULT_ITERS[algo] if iters is None else iters
+    base = dict(baselines(J, episode_len, range(actors)), algo=algo, actors=actors, J=J, episode_len=episode_len,
+                iters=iters, seed=seed)
+    log(json.dumps(base))
+    loop = Loop(algo, actors, J, episode_len, seed, device)
+    gap = base['pd_return'] - base['zero_action_return']
+    curve, t0 = [], time.time()
+    for it in range(iters + 1):
+        if it % eval_every == 0 or it == iters:
+            ev = loop.evaluate()
+            curve.append({'algo': algo, 'iteration': it, 'env_steps': loop.env_steps, 'learner_iterations': loop.learns,
+                          'training_return': loop.training_return(), 'eval_return': ev,
+                          'gap_closed': (ev - base['zero_action_return']) / gap, 'wall_s': round(time.time() - t0, 3)})
+            log(json.dumps(curve[-1]))
+        if it < iters:
+            loop.iterate()
+    return base, curve
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument('--algo', choices=['ppo', 'ddpg'], required=True)
+    ap.add_argument('--actors', type=int, default=64)
+    ap.add_argument('--J', type=int, default=2)
+    ap.add_argument('--episode-len', type=int, default=50)
+    ap.add_argument('--iters', type=int, default=None)
+    ap.add_argument('--seed', type=int, default=0)
+    ap.add_argument('--eval-every', type=int, default=10)
+    ap.add_argument('--out', default=None, help='append the lines to this file too')
+    args = ap.parse_args()
+    lines = []
+
+    def log(s):
+        print(s, flush=True)
+        lines.append(s)
+    train(args.algo, args.actors, args.J, args.episode_len, args.iters, args.seed, args.eval_every, log=log)
+    if args.out:
+        with open(args.out, 'a') as f:
+            f.write('\n'.join(lines) + '\n')
+
+
+if __name__ == '__main__':
+    main()

@@ -333,6 +333,7 @@ class RecordDdpgPixelPoolNstepStep(Structure):
 
 
 SMX_DDPG_NOISE_NONE, SMX_DDPG_NOISE_GAUSSIAN, SMX_DDPG_NOISE_OU = 0, 1, 2
+SMX_TASK_DRIFT, SMX_TASK_REACH = 0, 1      # the synthetic environment's dynamics (include/surreal_amd.h)
 SMX_PPO_PIXEL_STEP_MAX_A = 64            # the actions smx_synth_ppo_pixel_window_step takes
 
 
@@ -535,6 +536,11 @@ _SIGS = {
     'smx_synth_ppo_window_rollout_clocks_f32': (c_int32, [POINTER(SynthPpoWindowRollout), POINTER(ActorClocks), _P]),
     'smx_synth_ddpg_rollout_clocks_f32': (c_int32, [POINTER(DdpgRollout), POINTER(DdpgActorVariant),
                                                     POINTER(ActorClocks), _P]),
+    'smx_synth_task_supported': (c_int32, [c_int32, c_int32, c_int32]),
+    'smx_synth_task_env_step_f32': (c_int32, [_P, _P, _P, c_int32, c_int32, c_int32, c_int32, c_int32,
+                                              c_int32, c_int32, _P, _P, _P, _P, POINTER(EpisodeMonitor), c_int32, _P]),
+    'smx_synth_ppo_window_rollout_task_f32': (c_int32, [POINTER(SynthPpoWindowRollout), c_int32, _P]),
+    'smx_synth_ddpg_rollout_task_f32': (c_int32, [POINTER(DdpgRollout), c_int32, _P]),
     'smx_synth_ddpg_step_f32': (c_int32, [POINTER(DdpgRollout), _P, c_int64, _P]),
     'smx_synth_ddpg_pixel_step': (c_int32, [POINTER(DdpgPixelStep), _P, c_int64, _P]),
     'smx_synth_ddpg_pixel_pool_step': (c_int32, [POINTER(DdpgPixelPoolStep), _P, c_int64, _P]),

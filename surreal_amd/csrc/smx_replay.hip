@@ -359,6 +359,48 @@ __global__ __launch_bounds__(256) void synth_env_step_kernel(
     state[i] = done ? init_state[i] : sn;
 }
 
+// The same launch on SMX_TASK_REACH (reach_* of smx_synth_env.inc.h): an actor's elements are coupled, so ONE thread
+// steps the whole row of actor a, mass by mass -- every value it reads it reads before it writes it, no two threads
+// touch the same row.  (The device's own one-step reference and the evaluation's step: not a hot path.)
+__global__ __launch_bounds__(256) void reach_env_step_kernel(
+    float* __restrict__ state, const float* __restrict__ init_state,
+    const float* __restrict__ actions, int n, int D, int A, int t, int episode_len, int slot, int T,
+    float* __restrict__ obs_roll, float* __restrict__ act_roll, float* __restrict__ rew_roll,
+    float* __restrict__ done_roll, smx_episode_monitor mon) {
+    const long a = (long)blockIdx.x * 256 + threadIdx.x;
+    if (a >= n) return;
+    const bool done = (t + 1 >= episode_len);
+    float* s = state + a * D;
+    const float* s0 = init_state + a * D;
+    float* orow = obs_roll ? obs_roll + (a * T + slot) * D : nullptr;
+    const bool onext = orow && slot + 1 < T;         // the observation AFTER this step (synth_env_step_kernel)
+    double sd = 0.0, sa = 0.0;
+    for (int j = 0; j < A; ++j) {
+        const float ac = fminf(fmaxf(actions[a * A + j], -1.0f), 1.0f);
+        const float p = s[j], v = s[A + j], g = s[2 * A + j];
+        const float vn = reach_next_v(v, ac);
+        const float pn = reach_next_p(p, vn);
+        const float d = pn - g;
+        sd += (double)d * (double)d;
+        if (orow) {
+            orow[j] = p; orow[A + j] = v; orow[2 * A + j] = g;
+            if (onext) { orow[D + j] = pn; orow[D + A + j] = vn; orow[D + 2 * A + j] = g; }
+        }
+        if (act_roll) act_roll[(a * T + slot) * A + j] = ac;
+        s[j] = done ? s0[j] : pn;
+        s[A + j] = done ? s0[A + j] : vn;
+        s[2 * A + j] = done ? s0[2 * A + j] : g;
+    }
+    for (int j = 0; j < A; ++j) {
+        const float ac = fminf(fmaxf(actions[a * A + j], -1.0f), 1.0f);
+        sa += (double)ac * (double)ac;
+    }
+    const float rew = reach_reward(sd, sa);
+    if (rew_roll) rew_roll[a * T + slot] = rew;
+    if (done_roll) done_roll[a * T + slot] = done ? 1.0f : 0.0f;
+    if (mon.ep_reward) episode_account(mon, a, rew, done);
+}
+
 // The acting head, the environment step and the next observation's z-filter in one launch -- the
 // glue between two policy forwards of a device-resident rollout (sampling head as
 // smx_diaggauss_sample_f32, dynamics as synth_env_step_kernel, filter as
@@ -763,6 +805,28 @@ extern "C" int smx_synth_env_step_f32(float* state, const float* init_state, con
     hipLaunchKernelGGL(synth_env_step_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0,
                        smx_s(stream), state, init_state, actions, n, D, A, t, episode_len, slot, T,
                        obs_roll, act_roll, rew_roll, done_roll, M);
+    SMX_LAUNCH_CHECK();
+    return SMX_OK;
+}
+
+extern "C" int smx_synth_task_env_step_f32(float* state, const float* init_state, const float* actions,
+                                           int32_t n, int32_t D, int32_t A, int32_t t,
+                                           int32_t episode_len, int32_t slot, int32_t T, float* obs_roll,
+                                           float* act_roll, float* rew_roll, float* done_roll,
+                                           const struct smx_episode_monitor* mon, int32_t task, smx_stream_t stream) {
+    if (task == SMX_TASK_DRIFT)
+        return smx_synth_env_step_f32(state, init_state, actions, n, D, A, t, episode_len, slot, T, obs_roll, act_roll,
+                                      rew_roll, done_roll, mon, stream);
+    SMX_REQUIRE(task == SMX_TASK_REACH && synth_task_ok(task, D, A), SMX_E_UNSUPPORTED);
+    SMX_REQUIRE(state && init_state && actions, SMX_E_NULL);
+    SMX_REQUIRE(n > 0 && T > 0 && slot >= 0 && slot < T && episode_len > 0, SMX_E_SHAPE);
+    smx_episode_monitor M;
+    memset(&M, 0, sizeof(M));
+    if (mon) M = *mon;
+    SMX_REQUIRE(episode_pointers_ok(M), SMX_E_NULL);
+    SMX_REQUIRE(episode_shape_ok(M), SMX_E_SHAPE);
+    hipLaunchKernelGGL(reach_env_step_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, smx_s(stream), state,
+                       init_state, actions, n, D, A, t, episode_len, slot, T, obs_roll, act_roll, rew_roll, done_roll, M);
     SMX_LAUNCH_CHECK();
     return SMX_OK;
 }

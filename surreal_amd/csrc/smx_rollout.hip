@@ -39,6 +39,10 @@
 //                               an episode clock PER ACTOR (struct smx_actor_clocks; the row table of smx_actor_clock.hip):
 //                               the CLK instantiations of the same kernels (ClkArgs).
 //
+//   smx_synth_ppo_window_rollout_task_f32 / smx_synth_ddpg_rollout_task_f32  the windowed PPO launch (plain MLP or LSTM stem)
+//                               and the plain DDPG launch on another task's dynamics (SMX_TASK_REACH: EnvLanes::step_reach;
+//                               ppo_window_task_kernel, lstm_window_task_kernel, ddpg_rollout_kernel<..., TASK>).
+//
 // Layout: the persistent kernels (PPO, then DDPG), the step kernels (the two camera ones share their frame half:
 // frame_ctx / render_next_frame / copy_frames), then the host side: carve() and launch(), the argument fills (net_fields,
 // roll_fields, table_fields, lstm_fields, win_fields, pixel_fields), the rules the entry points share (*_ok, *_pointers),
@@ -222,7 +226,8 @@ __device__ __forceinline__ void clear_tiles(const RollBase& G, float* sm, int ti
 // them and keeps their raw state in registers for the whole rollout (RB = 16: two rows a wave, k = lane + 64 i).
 // COLS: the elements' action column and drift in registers too (else read from kmod and formed every step, where the
 // registers are short).
-template <int RB, bool COLS = true>
+// TASK: the dynamics (SMX_TASK_*; step() and step_reach()).
+template <int RB, bool COLS = true, int TASK = SMX_TASK_DRIFT>
 struct EnvLanes {
     static constexpr int WPR = RB < RNWV ? RNWV / RB : 1;   // wavefronts per actor row
     static constexpr int RPW = RB > RNWV ? RB / RNWV : 1;   // actor rows per wavefront
@@ -301,6 +306,10 @@ struct EnvLanes {
     // ROWDONE (per-actor episode clocks): the row's own p.done in place of `done`.
     template <bool ROWDONE = false, typename Open, typename Rec, typename Close>
     __device__ __forceinline__ void step(const float* s_act, bool done, Open open, Rec rec, Close close) {
+        if constexpr (TASK == SMX_TASK_REACH) {
+            step_reach<ROWDONE>(s_act, done, open, rec, close);
+            return;
+        }
 #pragma unroll
         for (int rr = 0; rr < RPW; ++rr) {
             const int r = erow0 + rr;                   // wave-uniform
@@ -333,6 +342,58 @@ struct EnvLanes {
 #pragma unroll
                     for (int j = 0; j < RMAX_A; ++j) q += (double)av[j] * (double)av[j];
                     const float rew = synth_reward(q, sn0);
+                    close(a, p, rew);
+                    if (mon.ep_reward) episode_step(mon, a, ep_reward[r], ep_steps[r], rew, done);
+                }
+            }
+        }
+    }
+    // The same step of SMX_TASK_REACH (reach_* of smx_synth_env.inc.h; D = 3 A <= 63, checked by the entry points).  A
+    // row's elements are coupled, and all of them sit in the 64 lanes of the row's first wave (kel(0), part == 0) at
+    // every block size: lane j < A holds p[j], lane A + j holds v[j], lane 2 A + j holds g[j].  So wave shuffles carry
+    // what an element needs from another -- v'[j] and g[j] to lane j -- and the d[j] and a[j] to the fp64 sums, j
+    // ascending (every lane of the wave forms them, the owner uses them): no LDS, no barrier.  The shuffles run in
+    // wave-uniform control flow; a source lane past the row (k >= D) is read by lanes whose value is not used.
+    template <bool ROWDONE, typename Open, typename Rec, typename Close>
+    __device__ __forceinline__ void step_reach(const float* s_act, bool done, Open open, Rec rec, Close close) {
+        if (part != 0) return;                          // (wave-uniform: these waves own k >= 64 > D)
+        const int k = lane;                             // kel(0)
+        const int J = D / 3;
+        const int kind = k >= 2 * J ? 2 : (k >= J ? 1 : 0);
+        const int j = k - kind * J;
+        const bool live = k < D;
+#pragma unroll
+        for (int rr = 0; rr < RPW; ++rr) {
+            const int r = erow0 + rr;                   // wave-uniform
+            if (r < nrows) {
+                const long a = row0 + r;
+                const auto p = open(a);
+                if constexpr (ROWDONE) done = p.done;
+                const float s = st[rr][0];
+                const float ac = live ? s_act[r * RMAX_A + j] : 0.f;
+                const float vc = reach_next_v(s, ac);               // lane A + j: v'[j]
+                const float vn = __shfl(vc, k + J);                 // lane j: v'[j]
+                const float pc = reach_next_p(s, vn);               // lane j: p'[j]
+                const float gj = __shfl(s, k + 2 * J);              // lane j: g[j]
+                const float d = kind == 0 ? pc - gj : 0.f;
+                const float sn = kind == 0 ? pc : (kind == 1 ? vc : s);
+                if (live) {
+                    rec(a, p, k, s, sn);
+                    const float next = done ? init_state[a * D + k] : sn;
+                    st[rr][0] = next;
+                    put_x(r, k, next);
+                }
+                double sd = 0.0, sa = 0.0;
+                for (int jj = 0; jj < J; ++jj) {
+                    const double dj = (double)__shfl(d, jj);
+                    sd += dj * dj;
+                }
+                for (int jj = 0; jj < J; ++jj) {
+                    const double aj = (double)__shfl(ac, jj);
+                    sa += aj * aj;
+                }
+                if (owner()) {
+                    const float rew = reach_reward(sd, sa);
                     close(a, p, rew);
                     if (mon.ep_reward) episode_step(mon, a, ep_reward[r], ep_steps[r], rew, done);
                 }
@@ -480,9 +541,12 @@ __device__ __forceinline__ void copy_window(int N, int first, Ld ld, St st) {
 // wstart, wclose, done -- every reader forms for ITS actor row from the row's clock in LDS (rowclk), and a closing
 // window's FIFO row comes from the call's row_off table, (cursor + row_off[step, a]) % capacity, where the clock closes
 // one and the word lies in [0, rows).
-template <int RG, int NT, bool LSTM, bool COLS, bool WIN = false, bool CLK = false, typename Args, typename Clk = NoClk>
+// TASK (WIN without CLK only): the environment's dynamics, EnvLanes' TASK.
+template <int RG, int NT, bool LSTM, bool COLS, bool WIN = false, bool CLK = false, int TASK = SMX_TASK_DRIFT, typename Args,
+          typename Clk = NoClk>
 __device__ __forceinline__ void ppo_rollout(Args G, Clk C = Clk{}) {
     static_assert(!CLK || WIN, "per-actor clocks: the windowed kernels");
+    static_assert(TASK == SMX_TASK_DRIFT || (WIN && !CLK), "tasks: the windowed kernels on the shared clock");
     constexpr int RB = 4 * RG;                       // actors per workgroup
     extern __shared__ float sm[];
     const int tid = threadIdx.x, lane = tid & 63;
@@ -495,7 +559,7 @@ __device__ __forceinline__ void ppo_rollout(Args G, Clk C = Clk{}) {
     const int ldh2 = G.ldh2;
 
     clear_tiles(G, sm, tid, G.zsum, G.zsumsq, G.zcount, G.zeps);
-    EnvLanes<RB, COLS> E(G, sm, G.zsum ? sm + G.off_z : nullptr, wv, lane);
+    EnvLanes<RB, COLS, TASK> E(G, sm, G.zsum ? sm + G.off_z : nullptr, wv, lane);
     SMX_LDS_BARRIER();
     E.start();
     SMX_LDS_BARRIER();
@@ -893,6 +957,17 @@ __global__ __launch_bounds__(RNTH) void lstm_window_kernel(LArgsW G) {
     ppo_rollout<RG, RG == 4 ? 2 : 3, true, RG < 4, true>(G);
 }
 
+// The same two on another task's dynamics (smx_synth_ppo_window_rollout_task_f32)
+template <int RG, int TASK>
+__global__ __launch_bounds__(RNTH) void ppo_window_task_kernel(RollArgsW G) {
+    ppo_rollout<RG, RG == 4 ? 2 : 3, false, RG < 4, true, false, TASK>(G);
+}
+
+template <int RG, int TASK>
+__global__ __launch_bounds__(RNTH) void lstm_window_task_kernel(LArgsW G) {
+    ppo_rollout<RG, RG == 4 ? 2 : 3, true, RG < 4, true, false, TASK>(G);
+}
+
 // The same two with an episode clock per actor (smx_synth_ppo_window_rollout_clocks_f32)
 template <int RG>
 __global__ __launch_bounds__(RNTH) void ppo_window_clk_kernel(WithClk<RollArgsW> G) {
@@ -1083,8 +1158,12 @@ constexpr int RLN_MAXC = 10;                         // columns per lane: H1, H2
 // and done are the actor row's own, a closing transition's ring row comes from the call's row_off table.
 template <bool POP, bool LN, bool CLK>
 using DdpgKernelArgs = std::conditional_t<CLK, WithClk<DdpgArgs<POP, LN>>, DdpgArgs<POP, LN>>;
-template <int RG, int NT, bool POP = false, bool LN = false, bool CLK = false>
+// TASK (the plain actor on the shared clock only; smx_synth_ddpg_rollout_task_f32): the environment's dynamics, EnvLanes'
+// TASK.  (A template parameter of the kernel itself: with the body moved into a function that two kernels call, every
+// existing instantiation compiled to other code -- its arguments no longer read as kernel arguments.)
+template <int RG, int NT, bool POP = false, bool LN = false, bool CLK = false, int TASK = SMX_TASK_DRIFT>
 __global__ __launch_bounds__(RNTH) void ddpg_rollout_kernel(DdpgKernelArgs<POP, LN, CLK> G) {
+    static_assert(TASK == SMX_TASK_DRIFT || !(POP || LN || CLK), "tasks: the plain actor on the shared clock");
     constexpr int RB = 4 * RG;                       // actors per workgroup
     const auto C = clk_of(G);
     extern __shared__ float sm[];
@@ -1095,7 +1174,7 @@ __global__ __launch_bounds__(RNTH) void ddpg_rollout_kernel(DdpgKernelArgs<POP, 
     float* s_act = sm + G.off_act;                   // [RB][RMAX_A] the actions of this step (unused columns stay 0)
 
     clear_tiles(G, sm, tid, nullptr, nullptr, nullptr, 0.f);
-    EnvLanes<RB> E(G, sm, nullptr, wv, lane);
+    EnvLanes<RB, true, TASK> E(G, sm, nullptr, wv, lane);
     SMX_LDS_BARRIER();
     E.start();
     // the head's (actor, action) pair of this lane: its sigma and OU state for the whole rollout
@@ -2091,8 +2170,9 @@ extern "C" int32_t smx_synth_ppo_window_rollout_supported(int32_t D, int32_t H, 
 }
 
 // both windowed entry points; clocks: null (the shared clock of base.roll) or the actors' own
+// task: SMX_TASK_DRIFT, or (shared clock only) a task smx_synth_task_supported takes
 static int ppo_window_rollout(const smx_synth_ppo_window_rollout* args, const smx_actor_clocks* clocks, bool clocked,
-                              smx_stream_t stream) {
+                              int task, smx_stream_t stream) {
     SMX_REQUIRE(args, SMX_E_NULL);
     const smx_synth_lstm_rollout& b = args->base;
     const smx_synth_rollout_t* a = &b.roll;
@@ -2103,6 +2183,8 @@ static int ppo_window_rollout(const smx_synth_ppo_window_rollout* args, const sm
     const smx_mlp3_t& n = *a->net;
     SMX_REQUIRE(!lstm || lstm_shape_ok(n, *b.lstm, b.hidden), SMX_E_SHAPE);
     SMX_REQUIRE(smx_synth_ppo_window_rollout_supported(lstm ? b.lstm->D : n.D, lstm ? b.lstm->H : 0, n.H1, n.H2, n.OUT),
+                SMX_E_UNSUPPORTED);
+    SMX_REQUIRE(synth_task_ok(task, lstm ? b.lstm->D : n.D, n.OUT) && !(clocked && task != SMX_TASK_DRIFT),
                 SMX_E_UNSUPPORTED);
     SMX_REQUIRE(a->n > 0 && a->steps > 0, SMX_E_SHAPE);
     SMX_REQUIRE(clocked || (a->episode_len > 0 && a->t >= 0 && a->t < a->episode_len), SMX_E_SHAPE);
@@ -2130,6 +2212,9 @@ static int ppo_window_rollout(const smx_synth_ppo_window_rollout* args, const sm
         if (clocked)
             return launch<ppo_window_clk_kernel<1>, ppo_window_clk_kernel<2>, ppo_window_clk_kernel<4>>(
                 with_clocks(G, C), rb, lds, stream);
+        if (task == SMX_TASK_REACH)
+            return launch<ppo_window_task_kernel<1, SMX_TASK_REACH>, ppo_window_task_kernel<2, SMX_TASK_REACH>,
+                          ppo_window_task_kernel<4, SMX_TASK_REACH>>(G, rb, lds, stream);
         return launch<ppo_window_kernel<1>, ppo_window_kernel<2>, ppo_window_kernel<4>>(G, rb, lds, stream);
     }
     LArgsW G;
@@ -2141,16 +2226,28 @@ static int ppo_window_rollout(const smx_synth_ppo_window_rollout* args, const sm
     if (clocked)
         return launch<lstm_window_clk_kernel<1>, lstm_window_clk_kernel<2>, lstm_window_clk_kernel<4>>(
             with_clocks(G, C), rb, lds, stream);
+    if (task == SMX_TASK_REACH)
+        return launch<lstm_window_task_kernel<1, SMX_TASK_REACH>, lstm_window_task_kernel<2, SMX_TASK_REACH>,
+                      lstm_window_task_kernel<4, SMX_TASK_REACH>>(G, rb, lds, stream);
     return launch<lstm_window_kernel<1>, lstm_window_kernel<2>, lstm_window_kernel<4>>(G, rb, lds, stream);
 }
 
 extern "C" int smx_synth_ppo_window_rollout_f32(const smx_synth_ppo_window_rollout* args, smx_stream_t stream) {
-    return ppo_window_rollout(args, nullptr, false, stream);
+    return ppo_window_rollout(args, nullptr, false, SMX_TASK_DRIFT, stream);
+}
+
+extern "C" int32_t smx_synth_task_supported(int32_t task, int32_t D, int32_t A) { return synth_task_ok(task, D, A); }
+
+extern "C" int smx_synth_ppo_window_rollout_task_f32(const smx_synth_ppo_window_rollout* args, int32_t task,
+                                                     smx_stream_t stream) {
+    if (task == SMX_TASK_DRIFT) return smx_synth_ppo_window_rollout_f32(args, stream);
+    SMX_REQUIRE(task == SMX_TASK_REACH, SMX_E_UNSUPPORTED);
+    return ppo_window_rollout(args, nullptr, false, task, stream);
 }
 
 extern "C" int smx_synth_ppo_window_rollout_clocks_f32(const smx_synth_ppo_window_rollout* args,
                                                        const smx_actor_clocks* clocks, smx_stream_t stream) {
-    return ppo_window_rollout(args, clocks, true, stream);
+    return ppo_window_rollout(args, clocks, true, SMX_TASK_DRIFT, stream);
 }
 
 extern "C" int32_t smx_synth_ddpg_rollout_supported(int32_t D, int32_t H1, int32_t H2, int32_t A, int32_t ln) {
@@ -2213,10 +2310,11 @@ static int ln_args(const smx_mlp3_t& net, const smx_ddpg_actor_variant& v, LnTai
 
 // the launch for one of the four actors: the block's checks, then the population's, then the LayerNorm's; clocked: with
 // the actors' own clocks (checked behind the block: the table numbers the call's closing pairs, rows <= capacity
-// keeps them distinct), the block's t / episode_len ignored
+// keeps them distinct), the block's t / episode_len ignored; task: SMX_TASK_DRIFT, or (the plain actor on the shared clock
+// only) a task smx_synth_task_supported takes
 template <bool POP, bool LN>
 static int ddpg_rollout_launch(const smx_ddpg_rollout_t* a, const smx_ddpg_actor_variant& v, const smx_actor_clocks* clocks,
-                               bool clocked, smx_stream_t stream) {
+                               bool clocked, smx_stream_t stream, int task = SMX_TASK_DRIFT) {
     DdpgArgs<POP, LN> G;
     memset(&G, 0, sizeof(G));
     smx_ddpg_rollout_t own;
@@ -2228,6 +2326,7 @@ static int ddpg_rollout_launch(const smx_ddpg_rollout_t* a, const smx_ddpg_actor
     }
     int rc = persistent_ddpg_args(a, G, clocked);
     if (rc != SMX_OK) return rc;
+    SMX_REQUIRE(synth_task_ok(task, a->D, a->A) && !((POP || LN || clocked) && task != SMX_TASK_DRIFT), SMX_E_UNSUPPORTED);
     ClkArgs C = {};
     if (clocked) {
         rc = clock_args(clocks, a->capacity, C);
@@ -2259,6 +2358,12 @@ static int ddpg_rollout_launch(const smx_ddpg_rollout_t* a, const smx_ddpg_actor
     if (clocked)
         return launch<ddpg_rollout_kernel<1, 3, POP, LN, true>, ddpg_rollout_kernel<2, 3, POP, LN, true>,
                       ddpg_rollout_kernel<4, 2, POP, LN, true>>(with_clocks(G, C), rb, lds, stream);
+    if constexpr (!POP && !LN) {
+        if (task == SMX_TASK_REACH)
+            return launch<ddpg_rollout_kernel<1, 3, false, false, false, SMX_TASK_REACH>,
+                          ddpg_rollout_kernel<2, 3, false, false, false, SMX_TASK_REACH>,
+                          ddpg_rollout_kernel<4, 2, false, false, false, SMX_TASK_REACH>>(G, rb, lds, stream);
+    }
     return launch<ddpg_rollout_kernel<1, 3, POP, LN>, ddpg_rollout_kernel<2, 3, POP, LN>,
                   ddpg_rollout_kernel<4, 2, POP, LN>>(G, rb, lds, stream);
 }
@@ -2278,6 +2383,13 @@ static int ddpg_rollout_variant(const smx_ddpg_rollout_t* a, const smx_ddpg_acto
 extern "C" int smx_synth_ddpg_rollout_f32(const smx_ddpg_rollout_t* a, const struct smx_ddpg_actor_variant* variant,
                                           smx_stream_t stream) {
     return ddpg_rollout_variant(a, variant, nullptr, false, stream);
+}
+
+extern "C" int smx_synth_ddpg_rollout_task_f32(const smx_ddpg_rollout_t* a, int32_t task, smx_stream_t stream) {
+    if (task == SMX_TASK_DRIFT) return smx_synth_ddpg_rollout_f32(a, nullptr, stream);
+    SMX_REQUIRE(task == SMX_TASK_REACH, SMX_E_UNSUPPORTED);
+    static const smx_ddpg_actor_variant plain = {};
+    return ddpg_rollout_launch<false, false>(a, plain, nullptr, false, stream, task);
 }
 
 extern "C" int smx_synth_ddpg_rollout_clocks_f32(const smx_ddpg_rollout_t* a, const struct smx_ddpg_actor_variant* variant,

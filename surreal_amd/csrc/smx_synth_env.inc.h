@@ -15,6 +15,31 @@ __device__ __forceinline__ float synth_next(float s, float ac, float drift) {
 // the step's reward from q = sum_j a_j^2 (fp64, j ascending) and element 0 of the next state
 __device__ __forceinline__ float synth_reward(double q, float sn0) { return (float)(-0.1 * q + 0.05 * (double)sn0); }
 
+// ---- the `reach` task (SMX_TASK_REACH; surreal_amd/env/tasks.py holds the definition): A point masses, the state row
+// [p (A) | v (A) | g (A)].  The same rule: fp32, no contraction, each product rounded before the sum.
+constexpr int REACH_MAX_A = 21;                      // D = 3 A <= 63: a row's elements sit in one wavefront
+
+// what the task entry points take (smx_synth_task_supported)
+inline bool synth_task_ok(int task, int D, int A) {
+    if (task == SMX_TASK_DRIFT) return D > 0 && A > 0;
+    return task == SMX_TASK_REACH && A > 0 && A <= REACH_MAX_A && D == 3 * A;
+}
+
+// mass j's next velocity from its velocity v and its (clipped) action ac
+__device__ __forceinline__ float reach_next_v(float v, float ac) {
+    const float vn = (0.9f * v) + (0.2f * ac);
+    return fminf(fmaxf(vn, -1.0f), 1.0f);
+}
+
+// its next position from its position p and its NEXT velocity vn
+__device__ __forceinline__ float reach_next_p(float p, float vn) {
+    const float pn = p + (0.1f * vn);
+    return fminf(fmaxf(pn, -10.0f), 10.0f);
+}
+
+// the step's reward from sd = sum_j d_j^2, d_j = p'_j - g_j in fp32, and sa = sum_j a_j^2 (both fp64, j ascending)
+__device__ __forceinline__ float reach_reward(double sd, double sa) { return (float)(-(sd + 0.01 * sa)); }
+
 // the synthetic camera (SyntheticEnv._frame): a frame's shift from its step count t and the first state component s0
 // (in double, as the host's 100 * abs(float(s0))), and byte (c, y, x) of that frame.  Every kernel that renders a frame
 // (smx_replay.hip's synth_frame_kernel, smx_rollout.hip's DDPG pixel step) evaluates these two.

@@ -17,6 +17,9 @@ Dynamics (all fp32, no fused multiply-add):
     s'[k]  = clamp(0.9*s[k] + 0.5*a[k % A] + 0.01*((37k) % 17 - 8), -10, 10)
     reward = -0.1 * sum_j a[j]^2 + 0.05 * s'[0]      (accumulated in fp64, rounded once)
     done   = (t + 1 >= episode_len)
+
+These are the dynamics of task 'drift', the default: a workload, not a task.  task='reach' (tasks.py) is one a policy can
+learn, defined the same way -- once, in fp32 without fused multiply-add -- and run by both classes.
 """
 import collections
 import types
@@ -27,6 +30,7 @@ import torch
 from surreal_amd import kernels as KN
 from surreal_amd import _lib as L
 from . import actor_clocks as AC
+from . import tasks as TK
 from .base import Env
 
 
@@ -36,9 +40,12 @@ def _drift(D):
 
 
 class SyntheticEnv(Env):
-    def __init__(self, obs_dim, action_dim, episode_len=200, seed=0, pixel=None):
+    def __init__(self, obs_dim, action_dim, episode_len=200, seed=0, pixel=None, task='drift'):
         """pixel = (C, H, W): also emit a uint8 camera frame obs['pixel']['camera0'] (a fixed
-        pattern shifted by the step count and the first state component)"""
+        pattern shifted by the step count and the first state component).
+        task: 'drift' (the dynamics above) or 'reach' (env/tasks.py: obs_dim == 3 * action_dim, no camera)"""
+        TK.check_task('SyntheticEnv', task, obs_dim, action_dim, pixel)
+        self.task = task
         self.D, self.A, self.episode_len = obs_dim, action_dim, episode_len
         self.pixel = tuple(pixel) if pixel is not None else None
         self.rs = np.random.RandomState(seed)
@@ -74,6 +81,12 @@ class SyntheticEnv(Env):
         return self._obs(), {}
 
     def _step(self, action):
+        if self.task == 'reach':
+            sn, reward = TK.reach_step(self.state, np.asarray(action, dtype=np.float32).reshape(-1))
+            done = (self.t + 1 >= self.episode_len)
+            self.t += 1
+            self.state = sn
+            return self._obs(), float(reward), done, {}
         a = np.clip(np.asarray(action, dtype=np.float32).reshape(-1), -1.0, 1.0).astype(np.float32)
         k = np.arange(self.D)
         sn = (np.float32(0.9) * self.state + np.float32(0.5) * a[k % self.A]).astype(np.float32)
@@ -89,14 +102,19 @@ class SyntheticVecEnv(object):
     """n actors on one GPU; rollouts of T steps recorded on the device"""
 
     def __init__(self, n_actors, obs_dim, action_dim, episode_len=200, seeds=None, device=None,
-                 kernels=None, pixel=None, frame_stacks=1):
-        """pixel = (C, H, W): every actor also has a camera (SyntheticEnv's frame: a pattern shifted by the step
+                 kernels=None, pixel=None, frame_stacks=1, task='drift'):
+        """task: 'drift' or 'reach' (env/tasks.py; SyntheticEnv's rules: obs_dim == 3 * action_dim, no camera): a task
+        env is stepped by step(), ppo_rollout_into and ddpg_rollout_into's one-launch route; every other stepping call
+        and route refuses it (_drift_only).
+        pixel = (C, H, W): every actor also has a camera (SyntheticEnv's frame: a pattern shifted by the step
         count and the first state component), rendered on the device; frame_stacks = n: the policy observes the
         last n frames on the channel axis (FrameStackWrapper's rule, surreal/env/wrapper.py:407-472) -- the rollout
         stores ONE raw uint8 frame per step and the stacking is a gather (smx_frame_stack_u8).
         episode_len: an int -- all actors share one episode clock -- or a sequence of n ints (also when they are all
         equal): every actor has an episode length and a clock of its own (per_actor_clocks; env/actor_clocks.py), which
         the one-launch low-dimensional ppo_rollout_into / ddpg_rollout_into take and every other stepping call refuses."""
+        TK.check_task('SyntheticVecEnv', task, obs_dim, action_dim, pixel)
+        self.task = task
         self.K = kernels or KN.default_kernels()
         self.device = device or KN.default_device()
         self.n, self.D, self.A = n_actors, obs_dim, action_dim
@@ -143,6 +161,30 @@ class SyntheticVecEnv(object):
         if self.per_actor_clocks:
             raise NotImplementedError('%s: per-actor episode clocks: the one-launch low-dimensional ppo_rollout_into / '
                                       'ddpg_rollout_into only' % who)
+
+    def _drift_only(self, who, what=None, throw=True):
+        """`who` (its variant `what`) steps the 'drift' dynamics only: refused on a task env -- raised here, or
+        (throw=False) returned as (exception class, message) for the callers that collect their refusals; None on a
+        'drift' env"""
+        if self.task == 'drift':
+            return None
+        refusal = (NotImplementedError,
+                   "%s%s: task %r is stepped by step(), ppo_rollout_into (a plain-MLP or one-layer LSTM policy the "
+                   "one-launch kernel takes) and ddpg_rollout_into's 'launch' route (a plain actor, no parameter noise), on "
+                   "one shared clock, only" % (who, ' with ' + what if what else '', self.task))
+        if throw:
+            raise refusal[0](refusal[1])
+        return refusal
+
+    def _task_kw(self, who):
+        """the keyword a launch that takes tasks gets on a task env (none on 'drift': kernels objects that know no tasks
+        are called as before); the shapes the device's task entry points refuse are refused here"""
+        if self.task == 'drift':
+            return {}
+        if not self.K.synth_task_supported(self.task, self.D, self.A):
+            raise ValueError('%s: task %r with %d actions; the device runs action_dim <= %d (smx_synth_task_supported)'
+                             % (who, self.task, self.A, TK.REACH_MAX_A))
+        return {'task': self.task}
 
     def _clock_args(self, T, n_step, advance, rows):
         """the `clocks` keyword of a per-actor launch over the next T steps: the clocks as they are now and the episode
@@ -350,6 +392,7 @@ class SyntheticVecEnv(object):
         segment: it starts right after a reset and T <= episode_len, so `done` can only be set
         on the last recorded step and windows never straddle an episode boundary."""
         self._shared_clock_only('start_rollout')
+        self._drift_only('start_rollout')
         assert self.t == 0 and T <= self.episode_len, 'rollouts start at an episode boundary'
         f = lambda *s: torch.zeros(*s, device=self.device, dtype=torch.float32)  # noqa: E731
         self.T = T
@@ -378,11 +421,12 @@ class SyntheticVecEnv(object):
     def step(self, actions, pds=None):
         """actions [n, A] on the device -> next observation [n, D] (the state tensor)"""
         self._shared_clock_only('step')
+        task = self._task_kw('step')
         r = self.rolls
         if r is not None and self.slot < self.T:
             self.K.synth_env_step(self.state, self.init_state, actions, self.t, self.episode_len,
                                   self.slot, r['obs'], r['actions'], r['rewards'], r['dones'], **self._mon(1),
-                                  **self._noi(1))
+                                  **self._noi(1), **task)
             if pds is not None and pds.data_ptr() != r['pds'][:, self.slot].data_ptr():
                 r['pds'][:, self.slot] = pds         # (an agent may have written the slot in place)
             self.slot += 1
@@ -392,7 +436,7 @@ class SyntheticVecEnv(object):
                 self.K.synth_frames(r['obs'][:, self.slot, 0], self.t + 1, self.frames[:, self.slot])
         else:
             self.K.synth_env_step(self.state, self.init_state, actions, self.t, self.episode_len, 0,
-                                  None, None, None, None, **self._mon(1), **self._noi(1))
+                                  None, None, None, None, **self._mon(1), **self._noi(1), **task)
         self._advance()
         return self.state
 
@@ -408,6 +452,7 @@ class SyntheticVecEnv(object):
         a deterministic mode ignore it).  actors_per_workgroup: 4 | 8 | 16 forces the one-launch kernel's block (0:
         automatic; 4 and 8 give the same bits, 16 sums the layers in another order)."""
         self._shared_clock_only('rollout')
+        self._drift_only('rollout')
         T, n, K = self.T, self.n, self.K
         assert self.slot == 0 and 'pds' in self.rolls, 'start_rollout(T, info_width=2 * A) first'
         eps, ns = self._draws(agent, eps, T)
@@ -509,6 +554,7 @@ class SyntheticVecEnv(object):
         policy (window_shapes(T, agent)) also gets `out['cells']` [n, 2, 1, Hl]: the state at the window's first step.
         actors_per_workgroup: as in rollout()."""
         self._shared_clock_only('rollout_into')
+        self._drift_only('rollout_into')
         K, n = self.K, self.n
         T = out['obs'].shape[1]
         assert self.t == 0 and T <= self.episode_len and self.can_rollout_into(agent)
@@ -531,6 +577,12 @@ class SyntheticVecEnv(object):
     def _ppo_window_refusal(self, agent):
         """why ppo_rollout_into cannot take `agent` -> (exception class, message), or None"""
         m = agent.model
+        if self.task != 'drift':
+            what = ('a camera agent' if m.if_pixel else 'per-actor episode clocks' if self.per_actor_clocks else
+                    'rnn_layer %d' % agent.rnn_config.rnn_layer
+                    if agent.rnn_config.if_rnn_policy and agent.rnn_config.rnn_layer != 1 else None)
+            if what is not None:
+                return self._drift_only('ppo_rollout_into', what, throw=False)
         refusal = self._camera_refusal('ppo_rollout_into', agent, bool(m.if_pixel))
         if refusal is not None:
             return refusal
@@ -584,6 +636,7 @@ class SyntheticVecEnv(object):
         refusal = self._ppo_window_refusal(agent)
         if refusal is not None:
             raise refusal[0](refusal[1])
+        task = self._task_kw('ppo_rollout_into')
         T = int(T)
         if T < 1:
             raise ValueError('ppo_rollout_into: T must be positive, got %d' % T)
@@ -652,7 +705,7 @@ class SyntheticVecEnv(object):
             clk, clock = self._clock_args(T, N, adv, rows), (0, 1)       # (the shared clock's arguments are ignored)
         K.synth_ppo_window_rollout(m, pk, lpk, self.state, self.init_state, noise, eps, clock[0], clock[1], T, N,
                                    adv, c['carry'], tables, cursor, zf, actors_per_workgroup=actors_per_workgroup, **cells,
-                                   **self._mon(T), **self._noi(T, ns), **clk)
+                                   **self._mon(T), **self._noi(T, ns), **clk, **task)
         if rnn:
             self._hand_cells(agent, cells)
         replay.commit_ring(rows)
@@ -731,6 +784,15 @@ class SyntheticVecEnv(object):
         one (kernels.ddpg_ln_launch); else it stays on the per-step path, refused under a parameter noise."""
         K, model, pn = self.K, agent.model, self.param_noise
         camera = model.is_pixel_input
+        if self.task != 'drift':
+            what = ('a camera agent' if camera else 'a LayerNorm actor' if model.use_layernorm else
+                    'an attached parameter noise' if pn is not None else
+                    'per-actor episode clocks' if self.per_actor_clocks else
+                    "reference=True (the 'two_launch' route)" if reference else
+                    "an actor shape the one-launch rollout does not take (the 'steps' route)"
+                    if not K.synth_ddpg_rollout_supported(model.actor) else None)
+            if what is not None:
+                return None, self._drift_only('ddpg_rollout_into', what, throw=False)
         refusal = self._camera_refusal('ddpg_rollout_into', agent, camera)
         if refusal is not None:
             return None, refusal
@@ -790,6 +852,7 @@ class SyntheticVecEnv(object):
         if refusal is not None:
             raise refusal[0](refusal[1])
         K, n, A, pn = self.K, self.n, self.A, self.param_noise
+        task = self._task_kw('ddpg_rollout_into')
         shapes, dtypes = {'obs': (self.D,), 'obs_next': (self.D,), 'actions': (A,), 'rewards': (), 'dones': ()}, None
         # (a frame-pool replay, replay.device_frame_pool: the camera rows are counters into its pool, which is this
         # route's frame history as well)
@@ -863,7 +926,7 @@ class SyntheticVecEnv(object):
             if self.per_actor_clocks:
                 variant.update(self._clock_args(T, N, 1, rows))
             K.synth_ddpg_rollout(actor, d['pk'], r, T, actors_per_workgroup, **variant, **self._mon(T),
-                                 **self._noi(T, ns))
+                                 **self._noi(T, ns), **task)
             if pn is not None:
                 pn.acts += T
             self.t = t
@@ -986,6 +1049,7 @@ class SyntheticVecEnv(object):
         row-block forward (smx_epoch_forward_f32: the means) and the head + step launch.  Bit-identical to
         ``rollout`` on the persistent kernel -- the parity test's reference; not used by the product loop."""
         self._shared_clock_only('rollout_reference')
+        self._drift_only('rollout_reference')
         T, n, K = self.T, self.n, self.K
         actor = agent.model.actor
         noise = agent.batch_noise(n).view(-1)
@@ -1029,6 +1093,7 @@ class SyntheticVecEnv(object):
         [w * advance, w * advance + n_step), W = windows_per_episode(T, n_step, stride) per actor"""
         from surreal_amd.env.exp_sender_wrapper import window_advance, windows_per_episode
         self._shared_clock_only('emit_windows')
+        self._drift_only('emit_windows')
         T = self.T
         assert self.slot == T, 'rollout not complete'
         W = windows_per_episode(T, n_step, stride)

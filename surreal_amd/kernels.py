@@ -856,7 +856,7 @@ class HipKernels(object):
     def synth_ppo_window_rollout(self, model, packed, lstm_packed, state, init_state, noise_scale, eps, t, episode_len,
                                  steps, n_step, advance, carry, tables, cursor, zfilter, hN=None, cN=None, h0=None,
                                  c0=None, h_before=None, c_before=None, actors_per_workgroup=0, monitor=None,
-                                 noise=None, clocks=None):
+                                 noise=None, clocks=None, task='drift'):
         """`steps` steps of synth_rollout (model.rnn None) / synth_lstm_rollout recorded as moving windows of n_step
         steps, `advance` apart, straight into a FIFO ring, ONE launch (smx_synth_ppo_window_rollout_f32).
         carry: the open windows {'obs' [n, n_step, D], 'actions' [n, n_step, A], 'rewards' [n, n_step], 'pds'
@@ -865,7 +865,8 @@ class HipKernels(object):
         closing step writes actor a to row (cursor + k n + a) % capacity.  h0 / c0 (None: zeros), hN / cN (LSTM),
         h_before / c_before: [n, Hl] contiguous, Hl = model.rnn_hidden_logical.
         clocks: an episode clock per actor (_clock_args; smx_synth_ppo_window_rollout_clocks_f32) -- t / episode_len
-        are then ignored and the closing windows go to the rows of clocks['row_off'] (actor_clock_rows)"""
+        are then ignored and the closing windows go to the rows of clocks['row_off'] (actor_clock_rows).
+        task: the environment's dynamics (env/tasks.py; smx_synth_ppo_window_rollout_task_f32; the shared clock only)"""
         p = L.SynthPpoWindowRollout()
         self._roll_args(p.base.roll, model.actor, packed, L.SMX_ACT_TANH, state, init_state, model.log_var, noise_scale,
                         eps, t, episode_len, steps, zfilter, actors_per_workgroup, monitor=monitor, noise=noise)
@@ -874,11 +875,27 @@ class HipKernels(object):
         for k, x in list(carry.items()) + list(tables.items()):
             assert x.is_contiguous() and x.dtype == torch.float32, k
         self._window_args(p, n_step, advance, carry, tables, cursor)
+        if task != 'drift':
+            assert clocks is None, 'a task env has one shared clock'
+            L.call('smx_synth_ppo_window_rollout_task_f32', ctypes.byref(p), self._task_id(task), self._st())
+            return
         if clocks is not None:
             c = self._clock_args(clocks, state.shape[0], steps)
             L.call('smx_synth_ppo_window_rollout_clocks_f32', ctypes.byref(p), ctypes.byref(c), self._st())
             return
         L.call('smx_synth_ppo_window_rollout_f32', ctypes.byref(p), self._st())
+
+    @staticmethod
+    def _task_id(task):
+        """SMX_TASK_* of a task's name (env/tasks.py)"""
+        from surreal_amd.env.tasks import TASK_IDS
+        return int(TASK_IDS[task])
+
+    def synth_task_supported(self, task, D, A):
+        """the (task, observation width, action width) the task entry points take (smx_synth_task_supported); task: a
+        name of env/tasks.py or a raw SMX_TASK_* id"""
+        tid = self._task_id(task) if isinstance(task, str) else int(task)
+        return bool(self.lib.smx_synth_task_supported(tid, int(D), int(A)))
 
     def actor_clock_rows(self, t, episode_len, steps, n_step, advance, row_off, t_host=None, episode_len_host=None):
         """row_off [steps, n] int32 <- where every closing (step, actor) pair of a call of `steps` steps goes, counted
@@ -966,7 +983,7 @@ class HipKernels(object):
         return L.ptr(pn.pop), pn.pop.shape[1], L.ptr(pn.dist)
 
     def synth_ddpg_rollout(self, net, packed, r, steps, actors_per_workgroup=0, monitor=None, noise=None, ln=None,
-                           ln_eps=0.0, pn=None, measure_step=-1, clocks=None):
+                           ln_eps=0.0, pn=None, measure_step=-1, clocks=None, task='drift'):
         """`steps` DDPG acting + environment steps of all actors with their n-step transitions written into the ring
         tables, ONE launch (smx_synth_ddpg_rollout_f32, csrc/smx_rollout.hip).  packed: epoch_pack of the actor `net`;
         r: see _ddpg_args (eps [steps, n, A]).
@@ -975,10 +992,16 @@ class HipKernels(object):
         (param_noise_refresh's, for the same ln); net / packed / ln are the clean actor, evaluated at step measure_step
         (-1: never) for pn.dist.
         clocks: an episode clock per actor (_clock_args; smx_synth_ddpg_rollout_clocks_f32) -- r['t'] / r['episode_len']
-        are then ignored and the closing transitions go to the rows of clocks['row_off'] (actor_clock_rows, advance 1)"""
+        are then ignored and the closing transitions go to the rows of clocks['row_off'] (actor_clock_rows, advance 1).
+        task: the environment's dynamics (env/tasks.py; smx_synth_ddpg_rollout_task_f32: the plain actor on the shared
+        clock only)"""
         if r['eps'] is not None:
             assert r['eps'].is_contiguous() and tuple(r['eps'].shape) == (steps, r['state'].shape[0], net.OUT)
         p = self._ddpg_args(r, steps, net, packed, actors_per_workgroup, monitor, noise)
+        if task != 'drift':
+            assert ln is None and pn is None and clocks is None, 'a task env runs the plain actor on one shared clock'
+            L.call('smx_synth_ddpg_rollout_task_f32', ctypes.byref(p), self._task_id(task), self._st())
+            return
         v = L.DdpgActorVariant()
         v.ln, v.ln_eps = self._ln_ptr(net, ln), float(ln_eps)
         if pn is not None:
@@ -1271,14 +1294,20 @@ class HipKernels(object):
         L.call('smx_record_ddpg_pixel_pool_nstep_step', ctypes.byref(p), self._st())
 
     def synth_env_step(self, state, init_state, actions, t, episode_len, slot, obs_roll, act_roll,
-                       rew_roll, done_roll, monitor=None):
+                       rew_roll, done_roll, monitor=None, task='drift'):
+        """one environment step of all actors on given actions [n, A]; task: the dynamics (env/tasks.py;
+        smx_synth_task_env_step_f32)"""
         n, D = state.shape
         A = actions.shape[1]
         T = obs_roll.shape[1] if obs_roll is not None else 1
-        L.call('smx_synth_env_step_f32', L.ptr(state), L.ptr(init_state), L.ptr(actions), n, D, A,
-               int(t), int(episode_len), int(slot), T, L.ptr(obs_roll), L.ptr(act_roll),
-               L.ptr(rew_roll), L.ptr(done_roll),
-               None if monitor is None else ctypes.byref(self._monitor_args(monitor, n)), self._st())
+        args = (L.ptr(state), L.ptr(init_state), L.ptr(actions), n, D, A,
+                int(t), int(episode_len), int(slot), T, L.ptr(obs_roll), L.ptr(act_roll),
+                L.ptr(rew_roll), L.ptr(done_roll),
+                None if monitor is None else ctypes.byref(self._monitor_args(monitor, n)))
+        if task != 'drift':
+            L.call('smx_synth_task_env_step_f32', *args, self._task_id(task), self._st())
+            return
+        L.call('smx_synth_env_step_f32', *args, self._st())
 
 
     # ---- generic dense layer + DDPG pieces ---------------------------------------------------
