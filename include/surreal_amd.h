@@ -1458,6 +1458,41 @@ int smx_synth_ppo_window_rollout_task_f32(const struct smx_synth_ppo_window_roll
                                           smx_stream_t stream);
 int smx_synth_ddpg_rollout_task_f32(const smx_ddpg_rollout_t* args, int32_t task, smx_stream_t stream);
 
+/* The episodes of SMX_TASK_REACH as a counter-based stream: element k < 3 A of the row [p | v | g] that (seed, global actor
+ * id g, episode index e) begins with is a pure function of the four, formed inside the launch that steps over the episode's
+ * end (csrc/smx_philox.inc.h has the expressions; surreal_amd/env/tasks.py the one definition):
+ *   x[0..3] = Philox4x32-10(counter = (g, low32(e), high32(e), 0x52530000 | (k >> 2)), key = (low32(seed), high32(seed)))
+ *   u = (float)(x[k & 3] >> 8) * 2^-23 - 1       (a 24-bit integer, scaled, minus one: exact in fp32; u in [-1, 1))
+ *   a position (k < A) or a goal (k >= 2 A) is u; a velocity is +0.
+ * The fourth counter word keeps these blocks apart from the exploration stream's (j >> 2 < 16) and the parameter noise's
+ * (0x504E0001).  `episode` is the index of the NEXT episode to begin: the i-th episode end of a call (i from 0; the
+ * actors share one clock, so they share the index) draws episode + i for every actor, and the caller adds the call's
+ * episode ends afterwards -- nothing is written back.  An actor's reset states depend on its global id and the episode
+ * index only: not on n, on the steps of a call, on how a run is cut into calls or on how the actors are split over launches.
+ * smx_reset_fill_f32: out [n, D] <- the rows of episode resets->episode (enabled is not read); task must be one with a
+ * reset distribution (SMX_TASK_REACH with D == 3 A', A' <= 21: else SMX_E_UNSUPPORTED).
+ * The three *_resets_f32 entry points take what the *_task_f32 ones take and a stream.  resets NULL or !resets->enabled:
+ * exactly the task entry point (init_state is read at an episode end).  Enabled: init_state is not read (it may be any
+ * non-NULL pointer).  Before any launch: an enabled stream on SMX_TASK_DRIFT is SMX_E_UNSUPPORTED; actor_base < 0,
+ * actor_base + n > 2^32 or episode < 0 is SMX_E_SHAPE; every other check is the task entry point's. */
+struct smx_reset_stream {                  /* (by tag: no typedef) */
+    uint64_t seed;
+    int64_t actor_base;                    /* global id of local actor 0 */
+    int64_t episode;                       /* index of the next episode to begin */
+    int32_t enabled, reserved;
+};
+int smx_reset_fill_f32(const struct smx_reset_stream* resets, int32_t task, int32_t n, int32_t D, float* out,
+                       smx_stream_t stream);
+int smx_synth_task_env_step_resets_f32(float* state, const float* init_state, const float* actions,
+                                       int32_t n, int32_t D, int32_t A, int32_t t, int32_t episode_len,
+                                       int32_t slot, int32_t T, float* obs_roll, float* act_roll,
+                                       float* rew_roll, float* done_roll, const struct smx_episode_monitor* mon,
+                                       int32_t task, const struct smx_reset_stream* resets, smx_stream_t stream);
+int smx_synth_ppo_window_rollout_resets_f32(const struct smx_synth_ppo_window_rollout* args, int32_t task,
+                                            const struct smx_reset_stream* resets, smx_stream_t stream);
+int smx_synth_ddpg_rollout_resets_f32(const smx_ddpg_rollout_t* args, int32_t task,
+                                      const struct smx_reset_stream* resets, smx_stream_t stream);
+
 /* Parameter-space noise of the device actors (surreal/agent/param_noise.py): a population of perturbed actors, one per
  * AGENT -- a group of consecutive actors that share one perturbation, as the actors of one reference agent process do
  * (an agent here spans at least the 4 actors of one MFMA row block, where the reference's spans one environment).  The

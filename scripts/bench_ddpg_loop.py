@@ -68,6 +68,11 @@ def main():
     ap.add_argument('--per-step', action='store_true', help='with --layernorm --calls: the per-step path (reference=True)')
     ap.add_argument('--calls', type=int, default=0, help='time this many single rollout calls, print their median and stop')
     ap.add_argument('--label', default='', help='copied into the --calls line')
+    ap.add_argument('--task', default=None, choices=['drift', 'reach'],
+                    help="with --calls: the environment's dynamics at obs-dim 3 x action-dim (reach's shape; --obs-dim is "
+                         'ignored), the plain actor on the one-launch route')
+    ap.add_argument('--random-resets', action='store_true',
+                    help='with --task reach: draw every episode inside the launch from a reset stream (attach_resets)')
     args = ap.parse_args()
     if args.param_noise and not args.calls:
         ap.error('--param-noise measures single calls: give --calls N')
@@ -75,6 +80,12 @@ def main():
         ap.error('--per-step goes with --layernorm --calls N, without --param-noise')
     if args.episode_lens and not args.calls:
         ap.error('--episode-lens measures single calls of the one-launch path: give --calls N')
+    if args.task and not args.calls:
+        ap.error('--task measures single calls of the one-launch path: give --calls N')
+    if args.random_resets and args.task != 'reach':
+        ap.error('--random-resets goes with --task reach')
+    if args.task:
+        args.obs_dim = 3 * args.action_dim
     n, T, D, A = args.actors, args.steps, args.obs_dim, args.action_dim
     H1, H2 = args.hidden
     lc = ddpg_learner_config()
@@ -95,7 +106,11 @@ def main():
     if args.episode_lens:
         lo, hi = args.episode_lens
         episode_len = [lo + a % (hi - lo + 1) for a in range(n)]
-    venv = SyntheticVecEnv(n, D, A, episode_len=episode_len, device='cuda')
+    task = {'task': args.task} if args.task == 'reach' else {}       # ('drift': no keyword, as before there were tasks)
+    venv = SyntheticVecEnv(n, D, A, episode_len=episode_len, device='cuda', **task)
+    if args.random_resets:
+        venv.attach_resets(seed=3)
+        venv.reset()
     mon = venv.attach_monitor() if args.monitor else None
 
     def returns(line):
@@ -209,6 +224,8 @@ def single_calls(args, agent, venv, replay, eps):
         call()
     ms = timed(call, args.calls)
     line = {'what': 'ddpg_rollout_calls', 'label': args.label, 'actors': n, 'steps': T, 'calls': args.calls,
+            'task': args.task, 'random_resets': args.random_resets, 'shape': [args.obs_dim] + args.hidden + [args.action_dim],
+            'episode_len': args.episode_len,
             'layernorm': args.layernorm, 'per_step': args.per_step, 'param_noise': bool(pn), 'actors_per_agent': args.actors_per_agent if pn else None,
             'agents': pn.agents if pn else None, 'median_ms': round(ms[len(ms) // 2], 4),
             'fastest_tenth_ms': round(ms[len(ms) // 10], 4), 'slowest_ms': round(ms[-1], 4),

@@ -4,7 +4,12 @@ tables, no windows), timed alternately in one process with device events after w
 configs[1]'s shape (64 actors, 128-step chunks of 1000-step episodes, the reference-default algo config): chunk ->
 ppo_rollout_into -> FIFOReplay.sample_batch(copy=False) -> PPOLearner.learn per batch.
 One JSON line per case: median / min / max over the repetitions.
-    python scripts/bench_ppo_window_loop.py [--reps 7] [--warmup 2] [--out FILE] [--quick]"""
+    python scripts/bench_ppo_window_loop.py [--reps 7] [--warmup 2] [--out FILE] [--quick]
+--task drift|reach [--random-resets] --calls N: instead, N single ppo_rollout_into calls (plain MLP 300 / 200, windows of 25
+steps 20 apart) on that task's dynamics at obs-dim 3 x action-dim, each between its own pair of events; one JSON line
+with their median.
+    python scripts/bench_ppo_window_loop.py --task reach --random-resets --calls 60 --actors 1024 --steps 128 \
+        --action-dim 6 --episode-len 16"""
 import argparse
 import json
 import os
@@ -130,6 +135,36 @@ def bench_loop(reps, warmup, n=64, T=128, L=1000, D=17, A=6, monitor=False, devi
     return [line]
 
 
+def bench_task_calls(args):
+    """--task: single calls of the one-launch windowed rollout on a task's dynamics"""
+    n, T, A, L = args.actors, args.steps, args.action_dim, args.episode_len
+    D, N, stride = 3 * A, 25, 20
+    if L < N:                                       # (a window never crosses an episode end)
+        N, stride = min(N, L), min(stride, L)
+    agent, cfg = PW.make_agent(D, A, N, stride, hidden=(300, 200), rnn_hidden=None, memory_size=n * (T // min(N, stride) + 2))
+    replay = FIFOReplay(*cfg)
+    task = {'task': args.task} if args.task == 'reach' else {}       # ('drift': no keyword, as before there were tasks)
+    venv = SyntheticVecEnv(n, D, A, episode_len=L, **task)
+    venv.attach_noise(seed=1)
+    if args.random_resets:
+        venv.attach_resets(seed=3)
+        venv.reset()
+
+    def call():
+        venv.ppo_rollout_into(agent, replay, T)
+        while len(replay):                          # (the learner's pops: views, no launch)
+            replay.sample_batch(min(len(replay), replay.memory_size), copy=False)
+    for _ in range(3):
+        call()
+    ms = sorted(_timed(call) for _ in range(args.calls))
+    line = {'what': 'ppo_window_rollout_calls', 'label': args.label, 'task': args.task, 'random_resets': args.random_resets,
+            'actors': n, 'steps': T, 'shape': [D, 300, 200, A], 'n_step': N, 'stride': stride, 'episode_len': L,
+            'calls': args.calls, 'median_ms': round(ms[len(ms) // 2], 4), 'fastest_tenth_ms': round(ms[len(ms) // 10], 4),
+            'slowest_ms': round(ms[-1], 4), 'env_steps_per_s': n * T / (ms[len(ms) // 2] / 1e3)}
+    print(json.dumps(line), flush=True)
+    return [line]
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--reps', type=int, default=7)
@@ -145,7 +180,24 @@ def main():
     ap.add_argument('--episode-lens', type=int, nargs=2, metavar=('LO', 'HI'), default=None,
                     help='the rollout cases with an episode clock per actor: actor a has episodes of LO + a %% (HI - LO + 1) '
                          'steps (the loop case is not run)')
+    ap.add_argument('--task', default=None, choices=['drift', 'reach'], help='single calls on this task (see the top)')
+    ap.add_argument('--random-resets', action='store_true', help='with --task reach: episodes drawn from a reset stream')
+    ap.add_argument('--calls', type=int, default=60)
+    ap.add_argument('--actors', type=int, default=1024)
+    ap.add_argument('--steps', type=int, default=128)
+    ap.add_argument('--action-dim', type=int, default=6)
+    ap.add_argument('--episode-len', type=int, default=16)
+    ap.add_argument('--label', default='', help='copied into the --task line')
     args = ap.parse_args()
+    if args.random_resets and args.task != 'reach':
+        ap.error('--random-resets goes with --task reach')
+    if args.task:
+        lines = bench_task_calls(args)
+        if args.out:
+            with open(args.out, 'a') as f:
+                for ln in lines:
+                    f.write(json.dumps(ln) + '\n')
+        return
     reps, warmup = (1, 1) if args.quick else (args.reps, args.warmup)
     lines = bench_rollouts(reps, warmup, ROLLOUTS, args.monitor, args.device_noise, args.episode_lens)
     if not args.episode_lens:

@@ -1,6 +1,7 @@
 """The on-device loop on a task a policy can learn: `reach` (surreal_amd/env/tasks.py).
 
     python scripts/train_reach.py --algo ppo|ddpg [--actors N --J J --episode-len L --iters K --seed S --out FILE]
+                                  [--random-resets [--heldout-episodes E]] [--eval-heldout]
 
 Per iteration: one rollout chunk of all actors inside one launch (ppo_rollout_into / ddpg_rollout_into on a
 SyntheticVecEnv(task='reach') with a DeviceEpisodeMonitor and an exploration noise stream attached) -> the replay's device
@@ -9,7 +10,15 @@ policy (an agent in mode 'eval_deterministic') is run from the reset states of t
 
 Prints first the zero-action return and the PD controller's return on the same seeds, from the host env; then one JSON
 line per evaluation: env steps, learner iterations, the training return from the monitor, the evaluation return, the share
-of the zero -> PD gap the evaluation return closes, wall time."""
+of the zero -> PD gap the evaluation return closes, wall time.
+
+--random-resets: every training episode begins with a new start and goal, drawn on the device from a reset stream
+(SyntheticVecEnv.attach_resets, seed S + 2).  The evaluation env is attached to a stream with a DIFFERENT seed (S + 3)
+whose episode index is set back to 0 before each evaluation, so every evaluation sees the same E held-out episodes per
+actor (default 4), none of which training ever drew; the zero-action and PD returns come from the host env
+(SyntheticEnv(resets=...)) on those same episodes.
+--eval-heldout (without --random-resets): train the old way, from the 64 fixed reset states, but evaluate on the held-out
+episodes -- the measurement that shows what random resets buy."""
 import argparse
 import json
 import os
@@ -48,6 +57,27 @@ def baselines(J, episode_len, seeds):
             'pd_return': host_return(J, episode_len, seeds, TK.reach_pd_action)}
 
 
+def heldout_return(J, episode_len, actors, seed, episodes, controller):
+    """the mean episode return of controller(state) -> action over episodes 0 .. episodes - 1 of every actor of the
+    reset stream `seed`, on the host env"""
+    total = []
+    for g in range(actors):
+        env = SyntheticEnv(3 * J, J, episode_len=episode_len, task='reach', resets=(seed, g))
+        for _ in range(episodes):
+            env._reset()
+            ret, done = 0.0, False
+            while not done:
+                _, r, done, _ = env._step(controller(env.state))
+                ret += r
+            total.append(ret)
+    return float(np.mean(total))
+
+
+def heldout_baselines(J, episode_len, actors, seed, episodes):
+    return {'zero_action_return': heldout_return(J, episode_len, actors, seed, episodes, lambda s: np.zeros(J, np.float32)),
+            'pd_return': heldout_return(J, episode_len, actors, seed, episodes, TK.reach_pd_action)}
+
+
 def ppo_configs(D, A, n, folder):
     from surreal_amd.main.ppo_configs import ppo_learner_config, ppo_env_config, ppo_session_config
     lc = ppo_learner_config()
@@ -84,7 +114,10 @@ def ddpg_configs(D, A, n, folder):
 class Loop(object):
     """the loop of one algorithm: the training env, agent, learner and replay, and the evaluation pair"""
 
-    def __init__(self, algo, actors, J, episode_len, seed, device=None, folder='/tmp/surreal_amd_reach'):
+    def __init__(self, algo, actors, J, episode_len, seed, device=None, folder='/tmp/surreal_amd_reach',
+                 random_resets=False, heldout=0):
+        """random_resets: the training env draws its episodes (reset stream seed + 2); heldout = E > 0: the evaluation
+        runs E episodes per actor of the stream seed + 3, the same ones every time"""
         torch.manual_seed(seed)
         self.algo, self.n, self.J, self.L = algo, actors, J, episode_len
         D, A = 3 * J, J
@@ -112,7 +145,13 @@ class Loop(object):
         self.monitor = self.venv.attach_monitor(capacity=8)
         self.venv.attach_noise(seed=seed + 1)
         self.eval_env = SyntheticVecEnv(actors, D, A, episode_len=episode_len, seeds=seeds, task='reach', **kw)
-        self.eval_monitor = self.eval_env.attach_monitor(capacity=2)
+        self.heldout = int(heldout)
+        self.eval_monitor = self.eval_env.attach_monitor(capacity=max(2, self.heldout))
+        if random_resets:
+            self.venv.attach_resets(seed + 2)
+            self.venv.reset()
+        if self.heldout:
+            self.eval_env.attach_resets(seed + 3)
         self.env_steps = self.learns = 0
         self.T = episode_len                       # a chunk: one episode of every actor
 
@@ -146,6 +185,8 @@ class Loop(object):
         """the deterministic policy's mean episode return over the reset states of all actors (one episode, step())"""
         ag, env = self.eval_agent, self.eval_env
         ag.fetch_parameter()
+        if self.heldout:
+            return self._evaluate_heldout()
         env.reset()
         for _ in range(self.L):
             if self.algo == 'ppo':
@@ -157,14 +198,38 @@ class Loop(object):
         assert len(polled) == self.n and all(steps == self.L for _, _, steps in polled)
         return float(np.mean([r for _, r, _ in polled]))
 
+    def _evaluate_heldout(self):
+        """the same over the held-out episodes 0 .. E - 1 of every actor: the stream's index goes back to 0, reset()
+        begins episode 0 and the closing steps draw the next ones inside their launches"""
+        ag, env, E = self.eval_agent, self.eval_env, self.heldout
+        env.resets.episode = 0
+        env.reset()
+        for _ in range(E * self.L):
+            if self.algo == 'ppo':
+                actions, _ = ag.act_batch(env.state, eps=None)
+            else:
+                actions = ag.model.forward_actor(env.state)
+            env.step(actions)
+        polled = self.eval_monitor.poll()
+        assert len(polled) == E * self.n and all(steps == self.L for _, _, steps in polled)
+        assert env.resets.episode == E + 1
+        return float(np.mean([r for _, r, _ in polled]))
 
-def train(algo, actors=64, J=2, episode_len=50, iters=None, seed=0, eval_every=10, device=None, log=print):
-    """-> (the baselines, the curve: one dict per evaluation)"""
+
+def train(algo, actors=64, J=2, episode_len=50, iters=None, seed=0, eval_every=10, device=None, log=print,
+          random_resets=False, heldout_episodes=4, eval_heldout=False):
+    """-> (the baselines, the curve: one dict per evaluation).  random_resets / eval_heldout: the module docstring's"""
     iters = DEFAULT_ITERS[algo] if iters is None else iters
-    base = dict(baselines(J, episode_len, range(actors)), algo=algo, actors=actors, J=J, episode_len=episode_len,
-                iters=iters, seed=seed)
+    heldout = int(heldout_episodes) if (random_resets or eval_heldout) else 0
+    if heldout:
+        base = dict(heldout_baselines(J, episode_len, actors, seed + 3, heldout), algo=algo, actors=actors, J=J,
+                    episode_len=episode_len, iters=iters, seed=seed, random_resets=bool(random_resets),
+                    heldout_episodes=heldout)
+    else:
+        base = dict(baselines(J, episode_len, range(actors)), algo=algo, actors=actors, J=J, episode_len=episode_len,
+                    iters=iters, seed=seed)
     log(json.dumps(base))
-    loop = Loop(algo, actors, J, episode_len, seed, device)
+    loop = Loop(algo, actors, J, episode_len, seed, device, random_resets=random_resets, heldout=heldout)
     gap = base['pd_return'] - base['zero_action_return']
     curve, t0 = [], time.time()
     for it in range(iters + 1):
@@ -189,13 +254,18 @@ def main():
     ap.add_argument('--seed', type=int, default=0)
     ap.add_argument('--eval-every', type=int, default=10)
     ap.add_argument('--out', default=None, help='append the lines to this file too')
+    ap.add_argument('--random-resets', action='store_true', help='draw every training episode from a reset stream; '
+                    'evaluate on held-out episodes of another stream')
+    ap.add_argument('--heldout-episodes', type=int, default=4, help='held-out episodes per actor of an evaluation')
+    ap.add_argument('--eval-heldout', action='store_true', help='fixed resets in training, held-out episodes in evaluation')
     args = ap.parse_args()
     lines = []
 
     def log(s):
         print(s, flush=True)
         lines.append(s)
-    train(args.algo, args.actors, args.J, args.episode_len, args.iters, args.seed, args.eval_every, log=log)
+    train(args.algo, args.actors, args.J, args.episode_len, args.iters, args.seed, args.eval_every, log=log,
+          random_resets=args.random_resets, heldout_episodes=args.heldout_episodes, eval_heldout=args.eval_heldout)
     if args.out:
         with open(args.out, 'a') as f:
             f.write('\n'.join(lines) + '\n')

@@ -183,6 +183,12 @@ class NoiseStream(Structure):
                 ('reserved', c_int32)]
 
 
+class ResetStream(Structure):
+    """struct smx_reset_stream"""
+    _fields_ = [('seed', c_uint64), ('actor_base', c_int64), ('episode', c_int64), ('enabled', c_int32),
+                ('reserved', c_int32)]
+
+
 class SynthRollout(Structure):
     """smx_synth_rollout_t"""
     _fields_ = [('net', POINTER(Mlp3)), ('packed', c_void_p), ('out_act', c_int32), ('n', c_int32),
@@ -541,6 +547,13 @@ _SIGS = {
                                               c_int32, c_int32, _P, _P, _P, _P, POINTER(EpisodeMonitor), c_int32, _P]),
     'smx_synth_ppo_window_rollout_task_f32': (c_int32, [POINTER(SynthPpoWindowRollout), c_int32, _P]),
     'smx_synth_ddpg_rollout_task_f32': (c_int32, [POINTER(DdpgRollout), c_int32, _P]),
+    'smx_reset_fill_f32': (c_int32, [POINTER(ResetStream), c_int32, c_int32, c_int32, _P, _P]),
+    'smx_synth_task_env_step_resets_f32': (c_int32, [_P, _P, _P, c_int32, c_int32, c_int32, c_int32, c_int32,
+                                                     c_int32, c_int32, _P, _P, _P, _P, POINTER(EpisodeMonitor), c_int32,
+                                                     POINTER(ResetStream), _P]),
+    'smx_synth_ppo_window_rollout_resets_f32': (c_int32, [POINTER(SynthPpoWindowRollout), c_int32, POINTER(ResetStream),
+                                                          _P]),
+    'smx_synth_ddpg_rollout_resets_f32': (c_int32, [POINTER(DdpgRollout), c_int32, POINTER(ResetStream), _P]),
     'smx_synth_ddpg_step_f32': (c_int32, [POINTER(DdpgRollout), _P, c_int64, _P]),
     'smx_synth_ddpg_pixel_step': (c_int32, [POINTER(DdpgPixelStep), _P, c_int64, _P]),
     'smx_synth_ddpg_pixel_pool_step': (c_int32, [POINTER(DdpgPixelPoolStep), _P, c_int64, _P]),

@@ -82,3 +82,33 @@ __device__ __forceinline__ float param_noise_normal(uint64_t seed, uint32_t g, u
     philox4x32_10(c, (uint32_t)seed, (uint32_t)(seed >> 32));
     return philox_normal(c, (int)(i & 3u));
 }
+
+// ---- the reset stream (struct smx_reset_stream, include/surreal_amd.h; surreal_amd/env/tasks.py holds the definition) --
+// Element k < 3 J of the `reach` row [p | v | g] that (seed, global actor id g < 2^32, episode e) begins with: a pure
+// function of the four.
+//   x[0..3] = philox4x32_10(counter = (g, low32(e), high32(e), RESET_TAG | (k >> 2)), key = (low32(seed), high32(seed)))
+//   u = (float)(x[k & 3] >> 8) * 0x1p-23f - 1.0f        (24 bits, scaled, minus one: every step exact in fp32; [-1, 1))
+//   a position (k < J) or a goal (k >= 2 J) is u, a velocity is +0
+// The exploration stream's fourth counter word is j >> 2 < 16 and the parameter noise's PARAM_NOISE_TAG, so the three
+// never share a block, whatever the seed.  No transcendental function and no rounding: the host's integer form
+// (tasks.reach_reset_state) gives the same bits.
+constexpr uint32_t RESET_TAG = 0x52530000u;
+__device__ __forceinline__ float reset_uniform(uint64_t seed, uint32_t g, uint64_t e, int k) {
+    uint32_t c[4] = {g, (uint32_t)e, (uint32_t)(e >> 32), RESET_TAG | ((uint32_t)k >> 2)};
+    philox4x32_10(c, (uint32_t)seed, (uint32_t)(seed >> 32));
+    const uint32_t lo = (k & 1) ? c[1] : c[0], hi = (k & 1) ? c[3] : c[2];
+    const uint32_t w = (k & 2) ? hi : lo;
+    return (float)(w >> 8) * 0x1p-23f - 1.0f;
+}
+
+// element k of the row local actor a begins the call's i-th new episode with (R.episode: the index of the call's first)
+__device__ __forceinline__ float reach_reset_value(const smx_reset_stream& R, long a, int i, int k, int J) {
+    if (k >= J && k < 2 * J) return 0.0f;
+    return reset_uniform(R.seed, (uint32_t)(R.actor_base + a), (uint64_t)(R.episode + i), k);
+}
+
+// what the entry points ask of a stream over n actors: every global actor id in [0, 2^32), an episode index >= 0
+// (SMX_E_SHAPE)
+inline bool reset_shape_ok(const smx_reset_stream& R, long long n) {
+    return !R.enabled || (R.actor_base >= 0 && R.actor_base + n <= (1LL << 32) && R.episode >= 0);
+}

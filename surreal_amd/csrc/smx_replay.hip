@@ -366,10 +366,11 @@ __global__ __launch_bounds__(256) void reach_env_step_kernel(
     float* __restrict__ state, const float* __restrict__ init_state,
     const float* __restrict__ actions, int n, int D, int A, int t, int episode_len, int slot, int T,
     float* __restrict__ obs_roll, float* __restrict__ act_roll, float* __restrict__ rew_roll,
-    float* __restrict__ done_roll, smx_episode_monitor mon) {
+    float* __restrict__ done_roll, smx_episode_monitor mon, smx_reset_stream R) {
     const long a = (long)blockIdx.x * 256 + threadIdx.x;
     if (a >= n) return;
     const bool done = (t + 1 >= episode_len);
+    const bool draw = done && R.enabled;             // the reset row from the stream (reach_reset_value), not init_state
     float* s = state + a * D;
     const float* s0 = init_state + a * D;
     float* orow = obs_roll ? obs_roll + (a * T + slot) * D : nullptr;
@@ -387,9 +388,15 @@ __global__ __launch_bounds__(256) void reach_env_step_kernel(
             if (onext) { orow[D + j] = pn; orow[D + A + j] = vn; orow[D + 2 * A + j] = g; }
         }
         if (act_roll) act_roll[(a * T + slot) * A + j] = ac;
-        s[j] = done ? s0[j] : pn;
-        s[A + j] = done ? s0[A + j] : vn;
-        s[2 * A + j] = done ? s0[2 * A + j] : g;
+        if (draw) {
+            s[j] = reach_reset_value(R, a, 0, j, A);
+            s[A + j] = reach_reset_value(R, a, 0, A + j, A);
+            s[2 * A + j] = reach_reset_value(R, a, 0, 2 * A + j, A);
+        } else {
+            s[j] = done ? s0[j] : pn;
+            s[A + j] = done ? s0[A + j] : vn;
+            s[2 * A + j] = done ? s0[2 * A + j] : g;
+        }
     }
     for (int j = 0; j < A; ++j) {
         const float ac = fminf(fmaxf(actions[a * A + j], -1.0f), 1.0f);
@@ -399,6 +406,13 @@ __global__ __launch_bounds__(256) void reach_env_step_kernel(
     if (rew_roll) rew_roll[a * T + slot] = rew;
     if (done_roll) done_roll[a * T + slot] = done ? 1.0f : 0.0f;
     if (mon.ep_reward) episode_account(mon, a, rew, done);
+}
+
+// out [n, D] <- the rows the actors of a reach env begin episode R.episode with (smx_reset_fill_f32): one thread per element
+__global__ __launch_bounds__(256) void reset_fill_kernel(smx_reset_stream R, int D, long total, float* __restrict__ out) {
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= total) return;
+    out[i] = reach_reset_value(R, i / D, 0, (int)(i % D), D / 3);
 }
 
 // The acting head, the environment step and the next observation's z-filter in one launch -- the
@@ -809,11 +823,12 @@ extern "C" int smx_synth_env_step_f32(float* state, const float* init_state, con
     return SMX_OK;
 }
 
-extern "C" int smx_synth_task_env_step_f32(float* state, const float* init_state, const float* actions,
-                                           int32_t n, int32_t D, int32_t A, int32_t t,
-                                           int32_t episode_len, int32_t slot, int32_t T, float* obs_roll,
-                                           float* act_roll, float* rew_roll, float* done_roll,
-                                           const struct smx_episode_monitor* mon, int32_t task, smx_stream_t stream) {
+// the task entry point, with the reset stream or (null: none, or a disabled one) without
+static int synth_task_env_step(float* state, const float* init_state, const float* actions, int32_t n, int32_t D, int32_t A,
+                               int32_t t, int32_t episode_len, int32_t slot, int32_t T, float* obs_roll, float* act_roll,
+                               float* rew_roll, float* done_roll, const struct smx_episode_monitor* mon, int32_t task,
+                               const smx_reset_stream* resets, smx_stream_t stream) {
+    SMX_REQUIRE(!(resets && task == SMX_TASK_DRIFT), SMX_E_UNSUPPORTED);
     if (task == SMX_TASK_DRIFT)
         return smx_synth_env_step_f32(state, init_state, actions, n, D, A, t, episode_len, slot, T, obs_roll, act_roll,
                                       rew_roll, done_roll, mon, stream);
@@ -825,8 +840,45 @@ extern "C" int smx_synth_task_env_step_f32(float* state, const float* init_state
     if (mon) M = *mon;
     SMX_REQUIRE(episode_pointers_ok(M), SMX_E_NULL);
     SMX_REQUIRE(episode_shape_ok(M), SMX_E_SHAPE);
+    smx_reset_stream R;
+    memset(&R, 0, sizeof(R));
+    if (resets) R = *resets;
+    SMX_REQUIRE(reset_shape_ok(R, n), SMX_E_SHAPE);
     hipLaunchKernelGGL(reach_env_step_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, smx_s(stream), state,
-                       init_state, actions, n, D, A, t, episode_len, slot, T, obs_roll, act_roll, rew_roll, done_roll, M);
+                       init_state, actions, n, D, A, t, episode_len, slot, T, obs_roll, act_roll, rew_roll, done_roll, M, R);
+    SMX_LAUNCH_CHECK();
+    return SMX_OK;
+}
+
+extern "C" int smx_synth_task_env_step_f32(float* state, const float* init_state, const float* actions,
+                                           int32_t n, int32_t D, int32_t A, int32_t t,
+                                           int32_t episode_len, int32_t slot, int32_t T, float* obs_roll,
+                                           float* act_roll, float* rew_roll, float* done_roll,
+                                           const struct smx_episode_monitor* mon, int32_t task, smx_stream_t stream) {
+    return synth_task_env_step(state, init_state, actions, n, D, A, t, episode_len, slot, T, obs_roll, act_roll, rew_roll,
+                               done_roll, mon, task, nullptr, stream);
+}
+
+extern "C" int smx_synth_task_env_step_resets_f32(float* state, const float* init_state, const float* actions,
+                                                  int32_t n, int32_t D, int32_t A, int32_t t,
+                                                  int32_t episode_len, int32_t slot, int32_t T, float* obs_roll,
+                                                  float* act_roll, float* rew_roll, float* done_roll,
+                                                  const struct smx_episode_monitor* mon, int32_t task,
+                                                  const struct smx_reset_stream* resets, smx_stream_t stream) {
+    return synth_task_env_step(state, init_state, actions, n, D, A, t, episode_len, slot, T, obs_roll, act_roll, rew_roll,
+                               done_roll, mon, task, resets && resets->enabled ? resets : nullptr, stream);
+}
+
+extern "C" int smx_reset_fill_f32(const struct smx_reset_stream* resets, int32_t task, int32_t n, int32_t D, float* out,
+                                  smx_stream_t stream) {
+    SMX_REQUIRE(task == SMX_TASK_REACH && D % 3 == 0 && synth_task_ok(task, D, D / 3), SMX_E_UNSUPPORTED);
+    SMX_REQUIRE(resets && out, SMX_E_NULL);
+    smx_reset_stream R = *resets;
+    R.enabled = 1;
+    SMX_REQUIRE(n > 0 && reset_shape_ok(R, n), SMX_E_SHAPE);
+    const long total = (long)n * D;
+    hipLaunchKernelGGL(reset_fill_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, smx_s(stream), R, D, total,
+                       out);
     SMX_LAUNCH_CHECK();
     return SMX_OK;
 }

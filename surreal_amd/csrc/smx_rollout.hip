@@ -39,6 +39,9 @@
 //                               an episode clock PER ACTOR (struct smx_actor_clocks; the row table of smx_actor_clock.hip):
 //                               the CLK instantiations of the same kernels (ClkArgs).
 //
+//   smx_synth_ppo_window_rollout_resets_f32 / smx_synth_ddpg_rollout_resets_f32  the same two with the episodes' first rows
+//                               drawn in the launch (struct smx_reset_stream; reach_reset_value of smx_philox.inc.h).
+//
 //   smx_synth_ppo_window_rollout_task_f32 / smx_synth_ddpg_rollout_task_f32  the windowed PPO launch (plain MLP or LSTM stem)
 //                               and the plain DDPG launch on another task's dynamics (SMX_TASK_REACH: EnvLanes::step_reach;
 //                               ppo_window_task_kernel, lstm_window_task_kernel, ddpg_rollout_kernel<..., TASK>).
@@ -188,6 +191,29 @@ template <typename Base>
 __device__ __forceinline__ ClkArgs clk_of(const WithClk<Base>& G) { return G.clk; }
 __device__ __forceinline__ NoClk clk_of(const RollBase&) { return NoClk{}; }
 
+// a task kernel's arguments: those of its SMX_TASK_DRIFT twin, then the reset stream (struct smx_reset_stream; rst.enabled
+// 0: the actors restart from init_state).  What EnvLanes keeps of it (ResetLanes): where the stream lies in the argument
+// segment and the call's episode ends so far -- on the shared clock a wave-uniform count -- for SMX_TASK_REACH, nothing for
+// a task without a reset distribution.  (Held by value, the stream's seven scalars stayed live across the layers of every
+// step: 17 to 48 more SGPR spills a kernel, 2 to 3 more VGPRs, and 0.2 % on a DDPG call that draws nothing.)
+template <typename Base>
+struct WithRst : Base { smx_reset_stream rst; };
+template <int TASK>
+struct ResetLanes {};
+template <>
+struct ResetLanes<SMX_TASK_REACH> {
+    const smx_reset_stream* rst;                // in the kernel's argument segment (rst_arg): read at an episode end only
+    int ends;
+};
+// where a task kernel's arguments KArgs = WithRst<...> hold the stream (scalar loads; no registers held between episode ends)
+#pragma clang diagnostic push
+#pragma clang diagnostic ignored "-Winvalid-offsetof"       // (WithRst derives from its Base: not standard-layout, one layout here)
+template <typename KArgs>
+__device__ __forceinline__ const smx_reset_stream* rst_arg() {
+    return (const smx_reset_stream*)((const char*)__builtin_amdgcn_kernarg_segment_ptr() + __builtin_offsetof(KArgs, rst));
+}
+#pragma clang diagnostic pop
+
 // the ring row of a closing record from its row_off word, which the caller found in [0, rows) (rows <= capacity: one
 // wrap at most)
 __device__ __forceinline__ long long clk_row(long long cursor, long long capacity, int off) {
@@ -228,7 +254,7 @@ __device__ __forceinline__ void clear_tiles(const RollBase& G, float* sm, int ti
 // registers are short).
 // TASK: the dynamics (SMX_TASK_*; step() and step_reach()).
 template <int RB, bool COLS = true, int TASK = SMX_TASK_DRIFT>
-struct EnvLanes {
+struct EnvLanes : ResetLanes<TASK> {
     static constexpr int WPR = RB < RNWV ? RNWV / RB : 1;   // wavefronts per actor row
     static constexpr int RPW = RB > RNWV ? RB / RNWV : 1;   // actor rows per wavefront
     static constexpr int KPL = RKV / WPR;                   // observation elements a lane owns per row
@@ -354,6 +380,9 @@ struct EnvLanes {
     // what an element needs from another -- v'[j] and g[j] to lane j -- and the d[j] and a[j] to the fp64 sums, j
     // ascending (every lane of the wave forms them, the owner uses them): no LDS, no barrier.  The shuffles run in
     // wave-uniform control flow; a source lane past the row (k >= D) is read by lanes whose value is not used.
+    // The reset row at an episode end: with a stream (rst.enabled, uniform over the kernel) every live lane draws its
+    // element of episode rst.episode + ends itself (reach_reset_value: ten Philox rounds, no memory read), else it loads
+    // init_state's.
     template <bool ROWDONE, typename Open, typename Rec, typename Close>
     __device__ __forceinline__ void step_reach(const float* s_act, bool done, Open open, Rec rec, Close close) {
         if (part != 0) return;                          // (wave-uniform: these waves own k >= 64 > D)
@@ -379,7 +408,9 @@ struct EnvLanes {
                 const float sn = kind == 0 ? pc : (kind == 1 ? vc : s);
                 if (live) {
                     rec(a, p, k, s, sn);
-                    const float next = done ? init_state[a * D + k] : sn;
+                    float next = sn;
+                    if (done)
+                        next = this->rst->enabled ? reach_reset_value(*this->rst, a, this->ends, k, J) : init_state[a * D + k];
                     st[rr][0] = next;
                     put_x(r, k, next);
                 }
@@ -399,6 +430,7 @@ struct EnvLanes {
                 }
             }
         }
+        if (done) ++this->ends;                         // (ROWDONE: never with a task)
     }
     // the states the actors are left in
     __device__ __forceinline__ void store() const {
@@ -541,10 +573,10 @@ __device__ __forceinline__ void copy_window(int N, int first, Ld ld, St st) {
 // wstart, wclose, done -- every reader forms for ITS actor row from the row's clock in LDS (rowclk), and a closing
 // window's FIFO row comes from the call's row_off table, (cursor + row_off[step, a]) % capacity, where the clock closes
 // one and the word lies in [0, rows).
-// TASK (WIN without CLK only): the environment's dynamics, EnvLanes' TASK.
+// TASK (WIN without CLK only): the environment's dynamics, EnvLanes' TASK; S: its reset stream (SMX_TASK_REACH; rst_arg).
 template <int RG, int NT, bool LSTM, bool COLS, bool WIN = false, bool CLK = false, int TASK = SMX_TASK_DRIFT, typename Args,
           typename Clk = NoClk>
-__device__ __forceinline__ void ppo_rollout(Args G, Clk C = Clk{}) {
+__device__ __forceinline__ void ppo_rollout(Args G, Clk C = Clk{}, const smx_reset_stream* S = nullptr) {
     static_assert(!CLK || WIN, "per-actor clocks: the windowed kernels");
     static_assert(TASK == SMX_TASK_DRIFT || (WIN && !CLK), "tasks: the windowed kernels on the shared clock");
     constexpr int RB = 4 * RG;                       // actors per workgroup
@@ -560,6 +592,10 @@ __device__ __forceinline__ void ppo_rollout(Args G, Clk C = Clk{}) {
 
     clear_tiles(G, sm, tid, G.zsum, G.zsumsq, G.zcount, G.zeps);
     EnvLanes<RB, COLS, TASK> E(G, sm, G.zsum ? sm + G.off_z : nullptr, wv, lane);
+    if constexpr (TASK == SMX_TASK_REACH) {
+        E.rst = S;
+        E.ends = 0;
+    }
     SMX_LDS_BARRIER();
     E.start();
     SMX_LDS_BARRIER();
@@ -959,13 +995,13 @@ __global__ __launch_bounds__(RNTH) void lstm_window_kernel(LArgsW G) {
 
 // The same two on another task's dynamics (smx_synth_ppo_window_rollout_task_f32)
 template <int RG, int TASK>
-__global__ __launch_bounds__(RNTH) void ppo_window_task_kernel(RollArgsW G) {
-    ppo_rollout<RG, RG == 4 ? 2 : 3, false, RG < 4, true, false, TASK>(G);
+__global__ __launch_bounds__(RNTH) void ppo_window_task_kernel(WithRst<RollArgsW> G) {
+    ppo_rollout<RG, RG == 4 ? 2 : 3, false, RG < 4, true, false, TASK>((RollArgsW)G, NoClk{}, rst_arg<WithRst<RollArgsW>>());
 }
 
 template <int RG, int TASK>
-__global__ __launch_bounds__(RNTH) void lstm_window_task_kernel(LArgsW G) {
-    ppo_rollout<RG, RG == 4 ? 2 : 3, true, RG < 4, true, false, TASK>(G);
+__global__ __launch_bounds__(RNTH) void lstm_window_task_kernel(WithRst<LArgsW> G) {
+    ppo_rollout<RG, RG == 4 ? 2 : 3, true, RG < 4, true, false, TASK>((LArgsW)G, NoClk{}, rst_arg<WithRst<LArgsW>>());
 }
 
 // The same two with an episode clock per actor (smx_synth_ppo_window_rollout_clocks_f32)
@@ -1156,13 +1192,15 @@ constexpr int RLN_MAXC = 10;                         // columns per lane: H1, H2
 // reads its own from memory.
 // CLK (the arguments then end with the clocks): an episode clock per actor, as in ppo_rollout -- tau, emit, slot, jslot
 // and done are the actor row's own, a closing transition's ring row comes from the call's row_off table.
-template <bool POP, bool LN, bool CLK>
-using DdpgKernelArgs = std::conditional_t<CLK, WithClk<DdpgArgs<POP, LN>>, DdpgArgs<POP, LN>>;
+// (a task kernel's end with the reset stream)
+template <bool POP, bool LN, bool CLK, int TASK = SMX_TASK_DRIFT>
+using DdpgKernelArgs = std::conditional_t<TASK != SMX_TASK_DRIFT, WithRst<DdpgArgs<POP, LN>>,
+                                          std::conditional_t<CLK, WithClk<DdpgArgs<POP, LN>>, DdpgArgs<POP, LN>>>;
 // TASK (the plain actor on the shared clock only; smx_synth_ddpg_rollout_task_f32): the environment's dynamics, EnvLanes'
 // TASK.  (A template parameter of the kernel itself: with the body moved into a function that two kernels call, every
 // existing instantiation compiled to other code -- its arguments no longer read as kernel arguments.)
 template <int RG, int NT, bool POP = false, bool LN = false, bool CLK = false, int TASK = SMX_TASK_DRIFT>
-__global__ __launch_bounds__(RNTH) void ddpg_rollout_kernel(DdpgKernelArgs<POP, LN, CLK> G) {
+__global__ __launch_bounds__(RNTH) void ddpg_rollout_kernel(DdpgKernelArgs<POP, LN, CLK, TASK> G) {
     static_assert(TASK == SMX_TASK_DRIFT || !(POP || LN || CLK), "tasks: the plain actor on the shared clock");
     constexpr int RB = 4 * RG;                       // actors per workgroup
     const auto C = clk_of(G);
@@ -1175,6 +1213,10 @@ __global__ __launch_bounds__(RNTH) void ddpg_rollout_kernel(DdpgKernelArgs<POP, 
 
     clear_tiles(G, sm, tid, nullptr, nullptr, nullptr, 0.f);
     EnvLanes<RB, true, TASK> E(G, sm, nullptr, wv, lane);
+    if constexpr (TASK == SMX_TASK_REACH) {
+        E.rst = rst_arg<DdpgKernelArgs<POP, LN, CLK, TASK>>();
+        E.ends = 0;
+    }
     SMX_LDS_BARRIER();
     E.start();
     // the head's (actor, action) pair of this lane: its sigma and OU state for the whole rollout
@@ -1911,6 +1953,16 @@ int launch(const Args& G, int rb, int lds, smx_stream_t stream) {
     return launch<K16>(G, rb, lds, stream);
 }
 
+// a task kernel's arguments from its drift twin's and the reset stream (null: none)
+template <typename Base>
+WithRst<Base> with_resets(const Base& G, const smx_reset_stream* R) {
+    WithRst<Base> X;
+    memset(&X.rst, 0, sizeof(X.rst));
+    static_cast<Base&>(X) = G;
+    if (R) X.rst = *R;
+    return X;
+}
+
 // a CLK kernel's arguments from its shared-clock twin's and the clocks
 template <typename Base>
 WithClk<Base> with_clocks(const Base& G, const ClkArgs& C) {
@@ -2170,9 +2222,9 @@ extern "C" int32_t smx_synth_ppo_window_rollout_supported(int32_t D, int32_t H, 
 }
 
 // both windowed entry points; clocks: null (the shared clock of base.roll) or the actors' own
-// task: SMX_TASK_DRIFT, or (shared clock only) a task smx_synth_task_supported takes
+// task: SMX_TASK_DRIFT, or (shared clock only) a task smx_synth_task_supported takes; resets: its reset stream or null
 static int ppo_window_rollout(const smx_synth_ppo_window_rollout* args, const smx_actor_clocks* clocks, bool clocked,
-                              int task, smx_stream_t stream) {
+                              int task, smx_stream_t stream, const smx_reset_stream* resets = nullptr) {
     SMX_REQUIRE(args, SMX_E_NULL);
     const smx_synth_lstm_rollout& b = args->base;
     const smx_synth_rollout_t* a = &b.roll;
@@ -2190,6 +2242,7 @@ static int ppo_window_rollout(const smx_synth_ppo_window_rollout* args, const sm
     SMX_REQUIRE(clocked || (a->episode_len > 0 && a->t >= 0 && a->t < a->episode_len), SMX_E_SHAPE);
     SMX_REQUIRE(block_ok(a->actors_per_workgroup) && window_shape_ok(*args) && episode_shape_ok(a->mon), SMX_E_SHAPE);
     SMX_REQUIRE(noise_shape_ok(a->noise, a->n), SMX_E_SHAPE);
+    SMX_REQUIRE(!resets || reset_shape_ok(*resets, a->n), SMX_E_SHAPE);
     ClkArgs C = {};
     if (clocked) {
         // (the table numbers the call's closing pairs: rows <= capacity keeps them distinct)
@@ -2214,7 +2267,7 @@ static int ppo_window_rollout(const smx_synth_ppo_window_rollout* args, const sm
                 with_clocks(G, C), rb, lds, stream);
         if (task == SMX_TASK_REACH)
             return launch<ppo_window_task_kernel<1, SMX_TASK_REACH>, ppo_window_task_kernel<2, SMX_TASK_REACH>,
-                          ppo_window_task_kernel<4, SMX_TASK_REACH>>(G, rb, lds, stream);
+                          ppo_window_task_kernel<4, SMX_TASK_REACH>>(with_resets(G, resets), rb, lds, stream);
         return launch<ppo_window_kernel<1>, ppo_window_kernel<2>, ppo_window_kernel<4>>(G, rb, lds, stream);
     }
     LArgsW G;
@@ -2228,7 +2281,7 @@ static int ppo_window_rollout(const smx_synth_ppo_window_rollout* args, const sm
             with_clocks(G, C), rb, lds, stream);
     if (task == SMX_TASK_REACH)
         return launch<lstm_window_task_kernel<1, SMX_TASK_REACH>, lstm_window_task_kernel<2, SMX_TASK_REACH>,
-                      lstm_window_task_kernel<4, SMX_TASK_REACH>>(G, rb, lds, stream);
+                      lstm_window_task_kernel<4, SMX_TASK_REACH>>(with_resets(G, resets), rb, lds, stream);
     return launch<lstm_window_kernel<1>, lstm_window_kernel<2>, lstm_window_kernel<4>>(G, rb, lds, stream);
 }
 
@@ -2238,11 +2291,23 @@ extern "C" int smx_synth_ppo_window_rollout_f32(const smx_synth_ppo_window_rollo
 
 extern "C" int32_t smx_synth_task_supported(int32_t task, int32_t D, int32_t A) { return synth_task_ok(task, D, A); }
 
-extern "C" int smx_synth_ppo_window_rollout_task_f32(const smx_synth_ppo_window_rollout* args, int32_t task,
-                                                     smx_stream_t stream) {
+// the task entry point, with the reset stream or (null: none, or a disabled one) without
+static int ppo_window_rollout_task(const smx_synth_ppo_window_rollout* args, int32_t task, const smx_reset_stream* resets,
+                                   smx_stream_t stream) {
+    SMX_REQUIRE(!(resets && task == SMX_TASK_DRIFT), SMX_E_UNSUPPORTED);
     if (task == SMX_TASK_DRIFT) return smx_synth_ppo_window_rollout_f32(args, stream);
     SMX_REQUIRE(task == SMX_TASK_REACH, SMX_E_UNSUPPORTED);
-    return ppo_window_rollout(args, nullptr, false, task, stream);
+    return ppo_window_rollout(args, nullptr, false, task, stream, resets);
+}
+
+extern "C" int smx_synth_ppo_window_rollout_task_f32(const smx_synth_ppo_window_rollout* args, int32_t task,
+                                                     smx_stream_t stream) {
+    return ppo_window_rollout_task(args, task, nullptr, stream);
+}
+
+extern "C" int smx_synth_ppo_window_rollout_resets_f32(const smx_synth_ppo_window_rollout* args, int32_t task,
+                                                       const struct smx_reset_stream* resets, smx_stream_t stream) {
+    return ppo_window_rollout_task(args, task, resets && resets->enabled ? resets : nullptr, stream);
 }
 
 extern "C" int smx_synth_ppo_window_rollout_clocks_f32(const smx_synth_ppo_window_rollout* args,
@@ -2311,10 +2376,11 @@ static int ln_args(const smx_mlp3_t& net, const smx_ddpg_actor_variant& v, LnTai
 // the launch for one of the four actors: the block's checks, then the population's, then the LayerNorm's; clocked: with
 // the actors' own clocks (checked behind the block: the table numbers the call's closing pairs, rows <= capacity
 // keeps them distinct), the block's t / episode_len ignored; task: SMX_TASK_DRIFT, or (the plain actor on the shared clock
-// only) a task smx_synth_task_supported takes
+// only) a task smx_synth_task_supported takes; resets: its reset stream or null
 template <bool POP, bool LN>
 static int ddpg_rollout_launch(const smx_ddpg_rollout_t* a, const smx_ddpg_actor_variant& v, const smx_actor_clocks* clocks,
-                               bool clocked, smx_stream_t stream, int task = SMX_TASK_DRIFT) {
+                               bool clocked, smx_stream_t stream, int task = SMX_TASK_DRIFT,
+                               const smx_reset_stream* resets = nullptr) {
     DdpgArgs<POP, LN> G;
     memset(&G, 0, sizeof(G));
     smx_ddpg_rollout_t own;
@@ -2327,6 +2393,7 @@ static int ddpg_rollout_launch(const smx_ddpg_rollout_t* a, const smx_ddpg_actor
     int rc = persistent_ddpg_args(a, G, clocked);
     if (rc != SMX_OK) return rc;
     SMX_REQUIRE(synth_task_ok(task, a->D, a->A) && !((POP || LN || clocked) && task != SMX_TASK_DRIFT), SMX_E_UNSUPPORTED);
+    SMX_REQUIRE(!resets || reset_shape_ok(*resets, a->n), SMX_E_SHAPE);
     ClkArgs C = {};
     if (clocked) {
         rc = clock_args(clocks, a->capacity, C);
@@ -2362,7 +2429,8 @@ static int ddpg_rollout_launch(const smx_ddpg_rollout_t* a, const smx_ddpg_actor
         if (task == SMX_TASK_REACH)
             return launch<ddpg_rollout_kernel<1, 3, false, false, false, SMX_TASK_REACH>,
                           ddpg_rollout_kernel<2, 3, false, false, false, SMX_TASK_REACH>,
-                          ddpg_rollout_kernel<4, 2, false, false, false, SMX_TASK_REACH>>(G, rb, lds, stream);
+                          ddpg_rollout_kernel<4, 2, false, false, false, SMX_TASK_REACH>>(with_resets(G, resets), rb, lds,
+                                                                                          stream);
     }
     return launch<ddpg_rollout_kernel<1, 3, POP, LN>, ddpg_rollout_kernel<2, 3, POP, LN>,
                   ddpg_rollout_kernel<4, 2, POP, LN>>(G, rb, lds, stream);
@@ -2385,11 +2453,22 @@ extern "C" int smx_synth_ddpg_rollout_f32(const smx_ddpg_rollout_t* a, const str
     return ddpg_rollout_variant(a, variant, nullptr, false, stream);
 }
 
-extern "C" int smx_synth_ddpg_rollout_task_f32(const smx_ddpg_rollout_t* a, int32_t task, smx_stream_t stream) {
+// the task entry point, with the reset stream or (null: none, or a disabled one) without
+static int ddpg_rollout_task(const smx_ddpg_rollout_t* a, int32_t task, const smx_reset_stream* resets, smx_stream_t stream) {
+    SMX_REQUIRE(!(resets && task == SMX_TASK_DRIFT), SMX_E_UNSUPPORTED);
     if (task == SMX_TASK_DRIFT) return smx_synth_ddpg_rollout_f32(a, nullptr, stream);
     SMX_REQUIRE(task == SMX_TASK_REACH, SMX_E_UNSUPPORTED);
     static const smx_ddpg_actor_variant plain = {};
-    return ddpg_rollout_launch<false, false>(a, plain, nullptr, false, stream, task);
+    return ddpg_rollout_launch<false, false>(a, plain, nullptr, false, stream, task, resets);
+}
+
+extern "C" int smx_synth_ddpg_rollout_task_f32(const smx_ddpg_rollout_t* a, int32_t task, smx_stream_t stream) {
+    return ddpg_rollout_task(a, task, nullptr, stream);
+}
+
+extern "C" int smx_synth_ddpg_rollout_resets_f32(const smx_ddpg_rollout_t* a, int32_t task,
+                                                 const struct smx_reset_stream* resets, smx_stream_t stream) {
+    return ddpg_rollout_task(a, task, resets && resets->enabled ? resets : nullptr, stream);
 }
 
 extern "C" int smx_synth_ddpg_rollout_clocks_f32(const smx_ddpg_rollout_t* a, const struct smx_ddpg_actor_variant* variant,

@@ -300,6 +300,59 @@ class DeviceNoise(object):
         return out
 
 
+class DeviceResets(object):
+    """The episodes of a 'reach' SyntheticVecEnv as a counter-based stream (struct smx_reset_stream,
+    include/surreal_amd.h; env/tasks.py: reach_reset_state): the row [p | v | g] that actor a (global id actor_base + a)
+    begins episode e with is a pure function of (seed, actor_base + a, e), drawn inside the launch that steps over the
+    episode's end.  Made by SyntheticVecEnv.attach_resets(seed, actor_base).
+
+    episode: the index of the NEXT episode to begin -- one host integer all actors share (they are on one clock).  A
+    reset() draws it and adds one; a stepping call adds its episode ends (its i-th end draws episode + i).  Read it for
+    a checkpoint, set it to resume or to see the same episodes again."""
+
+    def __init__(self, seed, actor_base, n, D, kernels, device, task='reach'):
+        self.seed, self.actor_base, self.episode = int(seed), int(actor_base), 0
+        if not 0 <= self.seed < 1 << 64:
+            raise ValueError('DeviceResets: seed must fit 64 bits, got %r' % (seed,))
+        if self.actor_base < 0 or self.actor_base + int(n) > 1 << 32:
+            raise ValueError('DeviceResets: global actor ids %d .. %d leave [0, 2^32)'
+                             % (self.actor_base, self.actor_base + int(n) - 1))
+        self.n, self.D, self.K, self.device, self.task = int(n), int(D), kernels, device, task
+
+    def at(self, ahead=0):
+        """(seed, actor_base, the episode index `ahead` episodes from now): what a launch's `resets=` keyword takes"""
+        e = self.episode + int(ahead)
+        if e < 0:
+            raise ValueError('DeviceResets: episode %d is negative' % e)
+        return (self.seed, self.actor_base, e)
+
+    def states(self, e=None):
+        """-> [n, D] fp32 on the device: the rows the actors begin episode e (None: the next one) with
+        (smx_reset_fill_f32: the launches' own function, the same bits), without advancing the counter"""
+        import torch
+        out = torch.empty(self.n, self.D, device=self.device)
+        self.fill(out, e)
+        return out
+
+    def fill(self, out, e=None):
+        """states(e) into out [n, D]"""
+        at = self.at() if e is None else (self.seed, self.actor_base, int(e))
+        if at[2] < 0:
+            raise ValueError('DeviceResets: episode %d is negative' % at[2])
+        self.K.reset_fill(at, out, task=self.task)
+
+    def state_dict(self):
+        return {'seed': self.seed, 'actor_base': self.actor_base, 'episode': self.episode}
+
+    def load_state_dict(self, sd):
+        if int(sd['seed']) != self.seed or int(sd['actor_base']) != self.actor_base:
+            raise ValueError('DeviceResets: the checkpoint is of stream (seed %d, actor_base %d), this one of (%d, %d)'
+                             % (int(sd['seed']), int(sd['actor_base']), self.seed, self.actor_base))
+        if int(sd['episode']) < 0:
+            raise ValueError('DeviceResets: episode %d is negative' % int(sd['episode']))
+        self.episode = int(sd['episode'])
+
+
 class DeviceParamNoise(object):
     """Parameter-space noise (agent/param_noise.py: 'normal' / 'adaptive_normal') for the actors of a SyntheticVecEnv, on
     the device.  The env's n actors form n / actors_per_agent AGENTS of consecutive actors that share one perturbation,

@@ -40,12 +40,20 @@ def _drift(D):
 
 
 class SyntheticEnv(Env):
-    def __init__(self, obs_dim, action_dim, episode_len=200, seed=0, pixel=None, task='drift'):
+    def __init__(self, obs_dim, action_dim, episode_len=200, seed=0, pixel=None, task='drift', resets=None):
         """pixel = (C, H, W): also emit a uint8 camera frame obs['pixel']['camera0'] (a fixed
         pattern shifted by the step count and the first state component).
-        task: 'drift' (the dynamics above) or 'reach' (env/tasks.py: obs_dim == 3 * action_dim, no camera)"""
+        task: 'drift' (the dynamics above) or 'reach' (env/tasks.py: obs_dim == 3 * action_dim, no camera).
+        resets = (seed, actor_id), task 'reach' only: every _reset() begins a NEW episode, drawn from the reset stream
+        (tasks.reach_reset_state(seed, actor_id, self.episode, J); self.episode: the index of the next one, from 0) --
+        the host form of SyntheticVecEnv.attach_resets; init_state is not read."""
         TK.check_task('SyntheticEnv', task, obs_dim, action_dim, pixel)
         self.task = task
+        self.resets, self.episode = None, 0
+        if resets is not None:
+            if task != 'reach':
+                raise ValueError("SyntheticEnv: task %r has no reset distribution (resets=: task 'reach')" % (task,))
+            self.resets = (int(resets[0]), int(resets[1]))
         self.D, self.A, self.episode_len = obs_dim, action_dim, episode_len
         self.pixel = tuple(pixel) if pixel is not None else None
         self.rs = np.random.RandomState(seed)
@@ -76,7 +84,11 @@ class SyntheticEnv(Env):
         return obs
 
     def _reset(self):
-        self.state = self.init_state.copy()
+        if self.resets is not None:
+            self.state = TK.reach_reset_state(self.resets[0], self.resets[1], self.episode, self.A)
+            self.episode += 1
+        else:
+            self.state = self.init_state.copy()
         self.t = 0
         return self._obs(), {}
 
@@ -140,6 +152,7 @@ class SyntheticVecEnv(object):
         self._ppo = {}                # ppo_rollout_into(): the open moving windows of the actors
         self.monitor = None           # attach_monitor(): the actors' episode returns, kept by the step launches
         self.noise = None             # attach_noise(): the exploration noise as a per-actor stream, drawn by the launches
+        self.resets = None            # attach_resets(): the episodes' first states as a per-actor stream, likewise
         self.param_noise = None       # attach_param_noise(): per-agent parameter-space noise for ddpg_rollout_into
 
     def _clock_zero(self):
@@ -257,6 +270,39 @@ class SyntheticVecEnv(object):
         m, self.noise = self.noise, None
         return m
 
+    def attach_resets(self, seed, actor_base=0):
+        """-> a DeviceResets (env/monitor.py), task 'reach' only: from now on every episode begins with a row drawn from
+        the reset stream -- element k of actor a's row for episode e is tasks.reach_reset_state(seed, actor_base + a, e,
+        J)[k] (struct smx_reset_stream, include/surreal_amd.h) -- inside the launch that steps over the episode's end:
+        no host round trip, no [n, D] upload, and init_state is not read.  The episode index is one host counter all
+        actors share (DeviceResets.episode, readable and settable: the index of the NEXT episode to begin): reset()
+        draws it and adds one, step / ppo_rollout_into / ddpg_rollout_into add their calls' episode ends.  An actor's
+        episodes then depend on its global id and the index alone: not on n, T, the cut of a run into calls or the
+        split of the actors over envs (actor_base: the global id of this env's actor 0).  The state is left as it is:
+        reset() to begin episode `episode`."""
+        if self.task != 'reach':
+            raise ValueError("attach_resets: task %r has no reset distribution (task 'reach' has)" % (self.task,))
+        self._shared_clock_only('attach_resets')
+        self._task_kw('attach_resets')
+        from .monitor import DeviceResets
+        self.resets = DeviceResets(seed, actor_base, self.n, self.D, self.K, self.device, task=self.task)
+        return self.resets
+
+    def detach_resets(self):
+        """every actor restarts from its init_state again -> the stream (which keeps its counter)"""
+        m, self.resets = self.resets, None
+        return m
+
+    def _rst(self, k):
+        """the keyword a stepping launch of k steps takes when a reset stream is attached (none otherwise: kernels
+        objects that know no streams are called as before).  The stream's index moves on by the call's episode ends,
+        (t + k) // episode_len on the shared clock t: call this before the clock advances"""
+        if self.resets is None:
+            return {}
+        at = self.resets.at()
+        self.resets.episode += (int(self.t) + int(k)) // int(self.episode_len)
+        return {'resets': at}
+
     def attach_param_noise(self, agent, seed, actors_per_agent=4, agent_base=0):
         """-> a DeviceParamNoise (env/monitor.py) of DDPGAgent `agent`'s parameter-space noise ('normal' or
         'adaptive_normal': its type, sigma, alpha and target_stddev): from now on ddpg_rollout_into runs every group of
@@ -287,7 +333,11 @@ class SyntheticVecEnv(object):
         return {'noise': at} if on else {}
 
     def reset(self):
-        self.state.copy_(self.init_state)
+        if self.resets is not None:
+            self.resets.fill(self.state)      # (episode `episode` of every actor: the launches' own function)
+            self.resets.episode += 1
+        else:
+            self.state.copy_(self.init_state)
         self.t = self._clock_zero()
         if self.monitor is not None:
             self.monitor.clear_open()         # (EpisodeMonitor._reset: an unfinished episode is dropped)
@@ -426,7 +476,7 @@ class SyntheticVecEnv(object):
         if r is not None and self.slot < self.T:
             self.K.synth_env_step(self.state, self.init_state, actions, self.t, self.episode_len,
                                   self.slot, r['obs'], r['actions'], r['rewards'], r['dones'], **self._mon(1),
-                                  **self._noi(1), **task)
+                                  **self._noi(1), **task, **self._rst(1))
             if pds is not None and pds.data_ptr() != r['pds'][:, self.slot].data_ptr():
                 r['pds'][:, self.slot] = pds         # (an agent may have written the slot in place)
             self.slot += 1
@@ -436,7 +486,7 @@ class SyntheticVecEnv(object):
                 self.K.synth_frames(r['obs'][:, self.slot, 0], self.t + 1, self.frames[:, self.slot])
         else:
             self.K.synth_env_step(self.state, self.init_state, actions, self.t, self.episode_len, 0,
-                                  None, None, None, None, **self._mon(1), **self._noi(1), **task)
+                                  None, None, None, None, **self._mon(1), **self._noi(1), **task, **self._rst(1))
         self._advance()
         return self.state
 
@@ -705,7 +755,7 @@ class SyntheticVecEnv(object):
             clk, clock = self._clock_args(T, N, adv, rows), (0, 1)       # (the shared clock's arguments are ignored)
         K.synth_ppo_window_rollout(m, pk, lpk, self.state, self.init_state, noise, eps, clock[0], clock[1], T, N,
                                    adv, c['carry'], tables, cursor, zf, actors_per_workgroup=actors_per_workgroup, **cells,
-                                   **self._mon(T), **self._noi(T, ns), **clk, **task)
+                                   **self._mon(T), **self._noi(T, ns), **clk, **task, **self._rst(T))
         if rnn:
             self._hand_cells(agent, cells)
         replay.commit_ring(rows)
@@ -926,7 +976,7 @@ class SyntheticVecEnv(object):
             if self.per_actor_clocks:
                 variant.update(self._clock_args(T, N, 1, rows))
             K.synth_ddpg_rollout(actor, d['pk'], r, T, actors_per_workgroup, **variant, **self._mon(T),
-                                 **self._noi(T, ns), **task)
+                                 **self._noi(T, ns), **task, **self._rst(T))
             if pn is not None:
                 pn.acts += T
             self.t = t

@@ -684,6 +684,23 @@ class HipKernels(object):
             q.enabled = 1
         return q
 
+    @staticmethod
+    def _reset_args(resets):
+        """struct smx_reset_stream of a (seed, actor_base, episode) triple (DeviceResets.at, surreal_amd/env/monitor.py):
+        the stream a task launch draws its episodes' first rows from"""
+        q = L.ResetStream()
+        q.seed, q.actor_base, q.episode = (int(v) for v in resets)
+        q.enabled = 1
+        return q
+
+    def reset_fill(self, resets, out, task='reach'):
+        """out [n, D] fp32 contiguous <- the rows the n actors of a `task` env on the stream `resets` = (seed,
+        actor_base, episode) begin that episode with (smx_reset_fill_f32)"""
+        n, D = out.shape
+        assert out.is_contiguous() and out.dtype == torch.float32
+        L.call('smx_reset_fill_f32', ctypes.byref(self._reset_args(resets)), self._task_id(task), n, D, L.ptr(out),
+               self._st())
+
     def noise_fill(self, noise, out):
         """out [steps, n, A] fp32 contiguous <- the draws a launch on the stream `noise` = (seed, actor_base, step)
         forms for n actors over `steps` steps (smx_noise_fill_f32)"""
@@ -856,7 +873,7 @@ class HipKernels(object):
     def synth_ppo_window_rollout(self, model, packed, lstm_packed, state, init_state, noise_scale, eps, t, episode_len,
                                  steps, n_step, advance, carry, tables, cursor, zfilter, hN=None, cN=None, h0=None,
                                  c0=None, h_before=None, c_before=None, actors_per_workgroup=0, monitor=None,
-                                 noise=None, clocks=None, task='drift'):
+                                 noise=None, clocks=None, task='drift', resets=None):
         """`steps` steps of synth_rollout (model.rnn None) / synth_lstm_rollout recorded as moving windows of n_step
         steps, `advance` apart, straight into a FIFO ring, ONE launch (smx_synth_ppo_window_rollout_f32).
         carry: the open windows {'obs' [n, n_step, D], 'actions' [n, n_step, A], 'rewards' [n, n_step], 'pds'
@@ -866,7 +883,9 @@ class HipKernels(object):
         h_before / c_before: [n, Hl] contiguous, Hl = model.rnn_hidden_logical.
         clocks: an episode clock per actor (_clock_args; smx_synth_ppo_window_rollout_clocks_f32) -- t / episode_len
         are then ignored and the closing windows go to the rows of clocks['row_off'] (actor_clock_rows).
-        task: the environment's dynamics (env/tasks.py; smx_synth_ppo_window_rollout_task_f32; the shared clock only)"""
+        task: the environment's dynamics (env/tasks.py; smx_synth_ppo_window_rollout_task_f32; the shared clock only).
+        resets: a task env's reset stream (_reset_args; smx_synth_ppo_window_rollout_resets_f32) -- init_state is then not
+        read"""
         p = L.SynthPpoWindowRollout()
         self._roll_args(p.base.roll, model.actor, packed, L.SMX_ACT_TANH, state, init_state, model.log_var, noise_scale,
                         eps, t, episode_len, steps, zfilter, actors_per_workgroup, monitor=monitor, noise=noise)
@@ -875,8 +894,13 @@ class HipKernels(object):
         for k, x in list(carry.items()) + list(tables.items()):
             assert x.is_contiguous() and x.dtype == torch.float32, k
         self._window_args(p, n_step, advance, carry, tables, cursor)
+        assert resets is None or task != 'drift', "task 'drift' has no reset distribution"
         if task != 'drift':
             assert clocks is None, 'a task env has one shared clock'
+            if resets is not None:
+                L.call('smx_synth_ppo_window_rollout_resets_f32', ctypes.byref(p), self._task_id(task),
+                       ctypes.byref(self._reset_args(resets)), self._st())
+                return
             L.call('smx_synth_ppo_window_rollout_task_f32', ctypes.byref(p), self._task_id(task), self._st())
             return
         if clocks is not None:
@@ -983,7 +1007,7 @@ class HipKernels(object):
         return L.ptr(pn.pop), pn.pop.shape[1], L.ptr(pn.dist)
 
     def synth_ddpg_rollout(self, net, packed, r, steps, actors_per_workgroup=0, monitor=None, noise=None, ln=None,
-                           ln_eps=0.0, pn=None, measure_step=-1, clocks=None, task='drift'):
+                           ln_eps=0.0, pn=None, measure_step=-1, clocks=None, task='drift', resets=None):
         """`steps` DDPG acting + environment steps of all actors with their n-step transitions written into the ring
         tables, ONE launch (smx_synth_ddpg_rollout_f32, csrc/smx_rollout.hip).  packed: epoch_pack of the actor `net`;
         r: see _ddpg_args (eps [steps, n, A]).
@@ -994,12 +1018,18 @@ class HipKernels(object):
         clocks: an episode clock per actor (_clock_args; smx_synth_ddpg_rollout_clocks_f32) -- r['t'] / r['episode_len']
         are then ignored and the closing transitions go to the rows of clocks['row_off'] (actor_clock_rows, advance 1).
         task: the environment's dynamics (env/tasks.py; smx_synth_ddpg_rollout_task_f32: the plain actor on the shared
-        clock only)"""
+        clock only).  resets: a task env's reset stream (_reset_args; smx_synth_ddpg_rollout_resets_f32) -- r['init_state']
+        is then not read"""
         if r['eps'] is not None:
             assert r['eps'].is_contiguous() and tuple(r['eps'].shape) == (steps, r['state'].shape[0], net.OUT)
         p = self._ddpg_args(r, steps, net, packed, actors_per_workgroup, monitor, noise)
+        assert resets is None or task != 'drift', "task 'drift' has no reset distribution"
         if task != 'drift':
             assert ln is None and pn is None and clocks is None, 'a task env runs the plain actor on one shared clock'
+            if resets is not None:
+                L.call('smx_synth_ddpg_rollout_resets_f32', ctypes.byref(p), self._task_id(task),
+                       ctypes.byref(self._reset_args(resets)), self._st())
+                return
             L.call('smx_synth_ddpg_rollout_task_f32', ctypes.byref(p), self._task_id(task), self._st())
             return
         v = L.DdpgActorVariant()
@@ -1294,9 +1324,10 @@ class HipKernels(object):
         L.call('smx_record_ddpg_pixel_pool_nstep_step', ctypes.byref(p), self._st())
 
     def synth_env_step(self, state, init_state, actions, t, episode_len, slot, obs_roll, act_roll,
-                       rew_roll, done_roll, monitor=None, task='drift'):
+                       rew_roll, done_roll, monitor=None, task='drift', resets=None):
         """one environment step of all actors on given actions [n, A]; task: the dynamics (env/tasks.py;
-        smx_synth_task_env_step_f32)"""
+        smx_synth_task_env_step_f32); resets: a task env's reset stream (_reset_args;
+        smx_synth_task_env_step_resets_f32) -- init_state is then not read"""
         n, D = state.shape
         A = actions.shape[1]
         T = obs_roll.shape[1] if obs_roll is not None else 1
@@ -1304,7 +1335,12 @@ class HipKernels(object):
                 int(t), int(episode_len), int(slot), T, L.ptr(obs_roll), L.ptr(act_roll),
                 L.ptr(rew_roll), L.ptr(done_roll),
                 None if monitor is None else ctypes.byref(self._monitor_args(monitor, n)))
+        assert resets is None or task != 'drift', "task 'drift' has no reset distribution"
         if task != 'drift':
+            if resets is not None:
+                L.call('smx_synth_task_env_step_resets_f32', *args, self._task_id(task),
+                       ctypes.byref(self._reset_args(resets)), self._st())
+                return
             L.call('smx_synth_task_env_step_f32', *args, self._task_id(task), self._st())
             return
         L.call('smx_synth_env_step_f32', *args, self._st())
