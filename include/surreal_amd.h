@@ -1493,6 +1493,66 @@ int smx_synth_ppo_window_rollout_resets_f32(const struct smx_synth_ppo_window_ro
 int smx_synth_ddpg_rollout_resets_f32(const smx_ddpg_rollout_t* args, int32_t task,
                                       const struct smx_reset_stream* resets, smx_stream_t stream);
 
+/* Evaluation on the device: whole episodes of the policy in ONE launch, nothing recorded -- the evaluation workers of
+ * the reference (agent_mode eval_deterministic / eval_stochastic: surreal/agent/base.py:277-345 get_env, prepare_env_eval
+ * and main_eval around the per-step loop of base.py:244-271, behind surreal/env/monitor.py:164-218 EvalTensorplexMonitor)
+ * and the offline surreal/main/rollout.py:1-87, which step one host environment per process.
+ * Episode e of actor g is a pure function of (parameters, streams, g, e), so the (actor, episode) pairs are independent
+ * ROWS: row r = a * episodes + i is episode resets.episode + i (first_episode + i) of local actor a.  The launch runs
+ * n * episodes rows on workgroups of actors_per_workgroup = 4, 8 or 16 rows (0: chosen as in smx_synth_rollout_f32, from
+ * the rows) and walks every row through exactly episode_len steps:
+ *   start:  resets.enabled (SMX_TASK_REACH only): the row the reset stream draws for (seed, actor_base + a,
+ *           resets.episode + i), formed in the launch; else init_state[a] ([n, D]; with an enabled stream not read, any
+ *           non-NULL pointer).  No state buffer is read or written; an LSTM policy starts every episode from zero h, c
+ *           (PPOAgent.reset, surreal/agent/ppo_agent.py:169-178).
+ *   step:   the policy step of smx_synth_ppo_window_rollout_f32 (PPO: z-filter, [one LSTM layer,] policy MLP, act(z + b3),
+ *           clip; surreal/agent/ppo_agent.py:106-154) resp. smx_synth_ddpg_rollout_f32 with SMX_DDPG_NOISE_NONE (tanh, clip;
+ *           surreal/agent/ddpg_agent.py:155-184), then the task's dynamics -- a row's actions and rewards have the bits of
+ *           those launches, at every block size.
+ *   PPO with noise.enabled (eval_stochastic): action = clip(mean + exp(log_var) * normal(noise.seed, noise.actor_base + a,
+ *           noise.step + i * episode_len + t, j)) at step t of the row -- what a serial run of the actor's episodes on that
+ *           stream (noise.step: first_step) draws; there is no eps tensor and no noise_scale.
+ *   return: returns[a, i] ([n, episodes] fp64) = (((0.0 + r_0) + r_1) + ...) the fp32 step rewards added in fp64 in step
+ *           order by the one lane that forms them (struct smx_episode_monitor's sum), stored once after the last step.
+ * lstm NULL: a plain-MLP policy (lstm_packed, hidden unused); else net->D == lstm->H as in smx_synth_lstm_rollout_f32.
+ * Before any launch: an enabled reset stream on SMX_TASK_DRIFT, or what smx_synth_eval_supported refuses:
+ * SMX_E_UNSUPPORTED; actor_base < 0 or actor_base + n > 2^32 of an enabled stream, resets.episode < 0, n < 1, episodes < 1,
+ * episode_len < 1, n * episodes >= 2^31, episodes * episode_len >= 2^31, actors_per_workgroup not 0 | 4 | 8 | 16:
+ * SMX_E_SHAPE; a NULL required pointer (the z-filter's three: all or none): SMX_E_NULL. */
+struct smx_synth_ppo_eval {                /* (by tag: no typedef) */
+    const smx_mlp3_t* net;
+    const float* packed;                   /* smx_epoch_pack_f32 of net */
+    int32_t out_act, n;
+    const float* log_var;
+    const float* zsum;
+    const float* zsumsq;
+    const float* zcount;
+    float zeps;
+    int32_t episodes, episode_len, task;
+    int32_t actors_per_workgroup, hidden;
+    const smx_lstm_t* lstm;
+    const float* lstm_packed;              /* smx_lstm_rollout_pack_f32 of lstm */
+    const float* init_state;
+    struct smx_reset_stream resets;        /* resets.episode: first_episode */
+    struct smx_noise_stream noise;         /* noise.step: first_step */
+    double* returns;                       /* [n, episodes] */
+};
+struct smx_synth_ddpg_eval {               /* (by tag: no typedef) */
+    const smx_mlp3_t* net;                 /* the actor */
+    const float* packed;
+    int32_t n, episodes, episode_len, task;
+    int32_t actors_per_workgroup, reserved;
+    const float* init_state;
+    struct smx_reset_stream resets;
+    double* returns;
+};
+/* shapes the two take (host-side): ddpg != 0 the plain DDPG actor (H must be 0), else a PPO policy with H LSTM units (0: a
+ * plain MLP); those of smx_synth_ddpg_rollout_supported(.., 0) resp. smx_synth_ppo_window_rollout_supported that
+ * smx_synth_task_supported(task, D, A) takes too */
+int32_t smx_synth_eval_supported(int32_t ddpg, int32_t task, int32_t D, int32_t H, int32_t H1, int32_t H2, int32_t A);
+int smx_synth_ppo_eval_f32(const struct smx_synth_ppo_eval* args, smx_stream_t stream);
+int smx_synth_ddpg_eval_f32(const struct smx_synth_ddpg_eval* args, smx_stream_t stream);
+
 /* Parameter-space noise of the device actors (surreal/agent/param_noise.py): a population of perturbed actors, one per
  * AGENT -- a group of consecutive actors that share one perturbation, as the actors of one reference agent process do
  * (an agent here spans at least the 4 actors of one MFMA row block, where the reference's spans one environment).  The

@@ -1,7 +1,7 @@
 """The on-device loop on a task a policy can learn: `reach` (surreal_amd/env/tasks.py).
 
     python scripts/train_reach.py --algo ppo|ddpg [--actors N --J J --episode-len L --iters K --seed S --out FILE]
-                                  [--random-resets [--heldout-episodes E]] [--eval-heldout]
+                                  [--random-resets [--heldout-episodes E]] [--eval-heldout] [--device-eval]
 
 Per iteration: one rollout chunk of all actors inside one launch (ppo_rollout_into / ddpg_rollout_into on a
 SyntheticVecEnv(task='reach') with a DeviceEpisodeMonitor and an exploration noise stream attached) -> the replay's device
@@ -18,7 +18,12 @@ whose episode index is set back to 0 before each evaluation, so every evaluation
 actor (default 4), none of which training ever drew; the zero-action and PD returns come from the host env
 (SyntheticEnv(resets=...)) on those same episodes.
 --eval-heldout (without --random-resets): train the old way, from the 64 fixed reset states, but evaluate on the held-out
-episodes -- the measurement that shows what random resets buy."""
+episodes -- the measurement that shows what random resets buy.
+--device-eval: the evaluation return comes from ONE launch on the training env (SyntheticVecEnv.evaluate: whole episodes,
+nothing recorded, the env untouched; the held-out form with resets=(S + 3, 0); a sampling evaluation agent -- PPO's under
+env_config.stochastic_eval -- draws from a noise stream of seed S + 4); every curve line then also carries the
+per-step figure on the same parameters (eval_return_per_step) and the wall time of both.  Without the flag nothing
+changes."""
 import argparse
 import json
 import os
@@ -119,6 +124,7 @@ class Loop(object):
         """random_resets: the training env draws its episodes (reset stream seed + 2); heldout = E > 0: the evaluation
         runs E episodes per actor of the stream seed + 3, the same ones every time"""
         torch.manual_seed(seed)
+        self.seed = seed
         self.algo, self.n, self.J, self.L = algo, actors, J, episode_len
         D, A = 3 * J, J
         kw = dict(device=device) if device is not None else {}
@@ -152,7 +158,7 @@ class Loop(object):
             self.venv.reset()
         if self.heldout:
             self.eval_env.attach_resets(seed + 3)
-        self.env_steps = self.learns = 0
+        self.env_steps = self.learns = self.device_eval_steps = 0
         self.T = episode_len                       # a chunk: one episode of every actor
 
     def iterate(self):
@@ -198,6 +204,22 @@ class Loop(object):
         assert len(polled) == self.n and all(steps == self.L for _, _, steps in polled)
         return float(np.mean([r for _, r, _ in polled]))
 
+    def evaluate_device(self):
+        """the same figure from one launch on the TRAINING env (SyntheticVecEnv.evaluate): one episode from every actor's
+        reset state, or the held-out episodes 0 .. E - 1 of the stream seed + 3.  An evaluation agent that samples (the PPO
+        agent under env_config.stochastic_eval, as in evaluate(): act_batch draws there) draws from a noise stream of its
+        own, seed + 4, which moves on with every evaluation"""
+        self.eval_agent.fetch_parameter()
+        E = self.heldout or 1
+        kw = {}
+        if self.heldout:
+            kw['resets'] = (self.seed + 3, 0)
+        if self.eval_agent.agent_mode in ('eval_stochastic', 'eval_stochastic_local'):
+            kw['noise'] = (self.seed + 4, self.device_eval_steps)
+            self.device_eval_steps += E * self.L
+        returns = self.venv.evaluate(self.eval_agent, E, **kw)
+        return float(np.mean(returns.cpu().numpy()))
+
     def _evaluate_heldout(self):
         """the same over the held-out episodes 0 .. E - 1 of every actor: the stream's index goes back to 0, reset()
         begins episode 0 and the closing steps draw the next ones inside their launches"""
@@ -217,8 +239,9 @@ class Loop(object):
 
 
 def train(algo, actors=64, J=2, episode_len=50, iters=None, seed=0, eval_every=10, device=None, log=print,
-          random_resets=False, heldout_episodes=4, eval_heldout=False):
-    """-> (the baselines, the curve: one dict per evaluation).  random_resets / eval_heldout: the module docstring's"""
+          random_resets=False, heldout_episodes=4, eval_heldout=False, device_eval=False):
+    """-> (the baselines, the curve: one dict per evaluation).  random_resets / eval_heldout / device_eval: the module
+    docstring's"""
     iters = DEFAULT_ITERS[algo] if iters is None else iters
     heldout = int(heldout_episodes) if (random_resets or eval_heldout) else 0
     if heldout:
@@ -234,10 +257,20 @@ def train(algo, actors=64, J=2, episode_len=50, iters=None, seed=0, eval_every=1
     curve, t0 = [], time.time()
     for it in range(iters + 1):
         if it % eval_every == 0 or it == iters:
-            ev = loop.evaluate()
+            extra = {}
+            if device_eval:
+                t1 = time.time()
+                ev = loop.evaluate_device()
+                t2 = time.time()
+                per_step = loop.evaluate()
+                extra = {'eval_return_per_step': per_step, 'eval_device_s': round(t2 - t1, 4),
+                         'eval_per_step_s': round(time.time() - t2, 4)}
+            else:
+                ev = loop.evaluate()
             curve.append({'algo': algo, 'iteration': it, 'env_steps': loop.env_steps, 'learner_iterations': loop.learns,
                           'training_return': loop.training_return(), 'eval_return': ev,
                           'gap_closed': (ev - base['zero_action_return']) / gap, 'wall_s': round(time.time() - t0, 3)})
+            curve[-1].update(extra)
             log(json.dumps(curve[-1]))
         if it < iters:
             loop.iterate()
@@ -258,6 +291,8 @@ def main():
                     'evaluate on held-out episodes of another stream')
     ap.add_argument('--heldout-episodes', type=int, default=4, help='held-out episodes per actor of an evaluation')
     ap.add_argument('--eval-heldout', action='store_true', help='fixed resets in training, held-out episodes in evaluation')
+    ap.add_argument('--device-eval', action='store_true', help='evaluate in one launch on the training env; the curve '
+                    'lines also carry the per-step figure')
     args = ap.parse_args()
     lines = []
 
@@ -265,7 +300,8 @@ def main():
         print(s, flush=True)
         lines.append(s)
     train(args.algo, args.actors, args.J, args.episode_len, args.iters, args.seed, args.eval_every, log=log,
-          random_resets=args.random_resets, heldout_episodes=args.heldout_episodes, eval_heldout=args.eval_heldout)
+          random_resets=args.random_resets, heldout_episodes=args.heldout_episodes, eval_heldout=args.eval_heldout,
+          device_eval=args.device_eval)
     if args.out:
         with open(args.out, 'a') as f:
             f.write('\n'.join(lines) + '\n')

@@ -189,6 +189,23 @@ class ResetStream(Structure):
                 ('reserved', c_int32)]
 
 
+class SynthPpoEval(Structure):
+    """struct smx_synth_ppo_eval"""
+    _fields_ = [('net', POINTER(Mlp3)), ('packed', c_void_p), ('out_act', c_int32), ('n', c_int32),
+                ('log_var', c_void_p), ('zsum', c_void_p), ('zsumsq', c_void_p), ('zcount', c_void_p),
+                ('zeps', c_float), ('episodes', c_int32), ('episode_len', c_int32), ('task', c_int32),
+                ('actors_per_workgroup', c_int32), ('hidden', c_int32), ('lstm', POINTER(Lstm)),
+                ('lstm_packed', c_void_p), ('init_state', c_void_p), ('resets', ResetStream), ('noise', NoiseStream),
+                ('returns', c_void_p)]
+
+
+class SynthDdpgEval(Structure):
+    """struct smx_synth_ddpg_eval"""
+    _fields_ = [('net', POINTER(Mlp3)), ('packed', c_void_p), ('n', c_int32), ('episodes', c_int32),
+                ('episode_len', c_int32), ('task', c_int32), ('actors_per_workgroup', c_int32), ('reserved', c_int32),
+                ('init_state', c_void_p), ('resets', ResetStream), ('returns', c_void_p)]
+
+
 class SynthRollout(Structure):
     """smx_synth_rollout_t"""
     _fields_ = [('net', POINTER(Mlp3)), ('packed', c_void_p), ('out_act', c_int32), ('n', c_int32),
@@ -554,6 +571,9 @@ _SIGS = {
     'smx_synth_ppo_window_rollout_resets_f32': (c_int32, [POINTER(SynthPpoWindowRollout), c_int32, POINTER(ResetStream),
                                                           _P]),
     'smx_synth_ddpg_rollout_resets_f32': (c_int32, [POINTER(DdpgRollout), c_int32, POINTER(ResetStream), _P]),
+    'smx_synth_eval_supported': (c_int32, [c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32]),
+    'smx_synth_ppo_eval_f32': (c_int32, [POINTER(SynthPpoEval), _P]),
+    'smx_synth_ddpg_eval_f32': (c_int32, [POINTER(SynthDdpgEval), _P]),
     'smx_synth_ddpg_step_f32': (c_int32, [POINTER(DdpgRollout), _P, c_int64, _P]),
     'smx_synth_ddpg_pixel_step': (c_int32, [POINTER(DdpgPixelStep), _P, c_int64, _P]),
     'smx_synth_ddpg_pixel_pool_step': (c_int32, [POINTER(DdpgPixelPoolStep), _P, c_int64, _P]),

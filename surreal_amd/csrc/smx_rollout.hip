@@ -46,7 +46,11 @@
 //                               and the plain DDPG launch on another task's dynamics (SMX_TASK_REACH: EnvLanes::step_reach;
 //                               ppo_window_task_kernel, lstm_window_task_kernel, ddpg_rollout_kernel<..., TASK>).
 //
-// Layout: the persistent kernels (PPO, then DDPG), the step kernels (the two camera ones share their frame half:
+//   smx_synth_ppo_eval_f32 / smx_synth_ddpg_eval_f32  evaluation: whole episodes of the policy as independent (actor, episode)
+//                               rows of one launch, nothing recorded, the fp64 returns stored once (ppo_eval_kernel,
+//                               ddpg_eval_kernel: new kernels that share the pieces above, not the bodies).
+//
+// Layout: the persistent kernels (PPO, then DDPG, then the evaluation), the step kernels (the two camera ones share their frame half:
 // frame_ctx / render_next_frame / copy_frames), then the host side: carve() and launch(), the argument fills (net_fields,
 // roll_fields, table_fields, lstm_fields, win_fields, pixel_fields), the rules the entry points share (*_ok, *_pointers),
 // the entry points.
@@ -253,6 +257,7 @@ __device__ __forceinline__ void clear_tiles(const RollBase& G, float* sm, int ti
 // COLS: the elements' action column and drift in registers too (else read from kmod and formed every step, where the
 // registers are short).
 // TASK: the dynamics (SMX_TASK_*; step() and step_reach()).
+struct OwnStart {};
 template <int RB, bool COLS = true, int TASK = SMX_TASK_DRIFT>
 struct EnvLanes : ResetLanes<TASK> {
     static constexpr int WPR = RB < RNWV ? RNWV / RB : 1;   // wavefronts per actor row
@@ -299,6 +304,19 @@ struct EnvLanes : ResetLanes<TASK> {
                 st[rr][i] = (k < D && r < nrows) ? state[(row0 + r) * D + k] : 0.f;
             }
         }
+    }
+    // the evaluation launches (OwnStart): the block's rows begin where the caller puts them (eval_start) -- `state` is
+    // neither read nor written, there is no monitor; rows: the rows of the launch
+    __device__ __forceinline__ EnvLanes(const RollBase& G, float* sm, const float* zm_, int wv, int lane_, OwnStart)
+        : D(G.D), ldx(G.ldx), state(nullptr), init_state(G.init_state), xs(sm), zm(zm_), kmod((const int*)(sm + G.off_kmod)),
+          mon(smx_episode_monitor{}), ep_reward(nullptr), ep_steps(nullptr),
+          row0((long)blockIdx.x * RB), lane(lane_), erow0(RPW * (wv / WPR)), part(wv % WPR) {
+        nrows = G.n - (int)row0;
+        if (nrows > RB) nrows = RB;
+#pragma unroll
+        for (int i = 0; i < KPL; ++i)
+#pragma unroll
+            for (int rr = 0; rr < RPW; ++rr) st[rr][i] = 0.f;
     }
     __device__ __forceinline__ int kel(int i) const { return lane + 64 * (part + WPR * i); }
     // the lane that forms the rewards of the wave's actor rows (k == 0 lives in lane 0, i == 0 of a row's first wave)
@@ -1376,6 +1394,262 @@ __global__ __launch_bounds__(RNTH) void ddpg_rollout_kernel(DdpgKernelArgs<POP, 
     if (head && G.noise == SMX_DDPG_NOISE_OU) G.ou[ha * A + hj] = x;
 }
 
+// ---- evaluation ------------------------------------------------------------------------------------------------------
+// Whole episodes of the policy, nothing recorded (smx_synth_ppo_eval_f32 / smx_synth_ddpg_eval_f32).  Episode e of actor g
+// is a pure function of (parameters, streams, g, e), so the (actor, episode) pairs are independent ROWS: row r = a E + i
+// is episode first_episode + i of local actor a, and a launch over n actors x E episodes is n E rows on the 4-, 8- or
+// 16-row blocks of the rollouts above (RollBase.n: the rows; the tail block as there), each walked through exactly
+// episode_len steps.  A row begins where eval_start puts it -- the stream's draw, else init_state[a] -- and `state` is
+// never touched.  The policy step is the recording kernels': clear_tiles, layers4 with their NT / COLS choices, their
+// head expressions, EnvLanes::step with done = false throughout (the reset behind the final step is unobservable), so a
+// row's actions have the bits of the recording launches at every block size.  The owner lane of a row keeps its fp64
+// return in a register, 0.0 + (double)rew in step order (episode_step's sum), and stores it once at the end: no LDS
+// monitor words, no HBM traffic per step, no atomics.
+struct EvalTail {
+    int E;                                      // episodes per actor
+    smx_reset_stream rst;                       // rst.episode: first_episode (read by eval_start only)
+    double* returns;                            // [n, E] = [rows]
+};
+struct PEvalArgs : RollBase {
+    int out_act;
+    const float *log_var;
+    const float *zsum, *zsumsq, *zcount;        // z-filter running sums or null
+    float zeps;
+    const float *Pg, *bg;                       // (LSTM) the gate pass, as LArgs
+    int H, Hl, Dp, off_g, ldg, off_c;
+    EvalTail ev;
+};
+struct DEvalArgs : RollBase { EvalTail ev; };
+
+// the first rows of the block's episodes into the environment lanes' registers (before E.start())
+template <typename Lanes>
+__device__ __forceinline__ void eval_start(Lanes& E, const EvalTail& V, bool stream) {
+#pragma unroll
+    for (int rr = 0; rr < Lanes::RPW; ++rr) {
+        const int r = E.erow0 + rr;
+        if (r >= E.nrows) continue;                     // (wave-uniform)
+        const long row = E.row0 + r;
+        const long a = row / V.E;
+        const int i = (int)(row - a * V.E);
+#pragma unroll
+        for (int q = 0; q < Lanes::KPL; ++q) {
+            const int k = E.kel(q);
+            if (k < E.D) E.st[rr][q] = stream ? reach_reset_value(V.rst, a, i, k, E.D / 3) : E.init_state[a * E.D + k];
+        }
+    }
+}
+
+// what the owner lane of the wave's (at most two) rows holds: their returns
+struct EvalReturns {
+    double r0 = 0.0, r1 = 0.0;
+    template <typename Lanes>
+    __device__ __forceinline__ void add(const Lanes& E, long row, float rew) {
+        if ((int)(row - E.row0) == E.erow0) r0 = r0 + (double)rew;
+        else r1 = r1 + (double)rew;
+    }
+    template <typename Lanes>
+    __device__ __forceinline__ void store(const Lanes& E, double* returns) const {
+        static_assert(Lanes::RPW <= 2, "two rows a wave at most");
+        if (!E.owner()) return;
+        if (E.erow0 < E.nrows) returns[E.row0 + E.erow0] = r0;
+        if (Lanes::RPW > 1 && E.erow0 + 1 < E.nrows) returns[E.row0 + E.erow0 + 1] = r1;
+    }
+};
+struct EvalNoRow {};
+
+// PPO: ppo_window_kernel's / lstm_window_kernel's step (NT, COLS as there; the split output layer, the head) without a
+// record.  LSTM rows start from zero h, c (PPOAgent.reset, ppo_agent.py:169-178).  A sampling launch (nstream.enabled:
+// eval_stochastic) draws row (a, i)'s step t at normal(seed, actor_base + a, first_step + i L + t, j): what a serial run
+// of the actor's E episodes on that stream draws.
+template <int RG, int NT, bool LSTM, bool COLS, int TASK>
+__global__ __launch_bounds__(RNTH) void ppo_eval_kernel(PEvalArgs G) {
+    constexpr int RB = 4 * RG;
+    extern __shared__ float sm[];
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int fm = lane & 15, kq = lane >> 4;
+    const int A = G.A;
+    const float* h2s = sm + G.off_h2;
+    const float* outs = sm + G.off_out;
+    float* s_act = sm + G.off_act;              // [RB][RMAX_A] clipped actions
+    const int ldh2 = G.ldh2;
+
+    clear_tiles(G, sm, tid, G.zsum, G.zsumsq, G.zcount, G.zeps);
+    EnvLanes<RB, COLS, TASK> E(G, sm, G.zsum ? sm + G.off_z : nullptr, wv, lane, OwnStart{});
+    if constexpr (TASK == SMX_TASK_REACH) {
+        E.rst = nullptr;                         // (done is false at every step: never read)
+        E.ends = 0;
+        eval_start(E, G.ev, G.ev.rst.enabled != 0);
+    } else {
+        eval_start(E, G.ev, false);
+    }
+    SMX_LDS_BARRIER();
+    E.start();
+    SMX_LDS_BARRIER();
+    const long row0 = E.row0;
+    const int nrows = E.nrows;
+    if constexpr (LSTM) {
+        float* cst = sm + G.off_c;
+#pragma unroll 1
+        for (int q = tid; q < RB * G.H; q += RNTH) cst[q] = 0.f;       // (h: the tile's cleared columns)
+        SMX_LDS_BARRIER();
+    }
+    // ---- the split output layer and the head's constants: ppo_rollout's ------------------------------------------------
+    const int tiles3 = (A + 15) >> 4, C3 = pack_chunks(G.H2);
+    const bool l3res = C3 <= RNWV && tiles3 <= 2;
+    constexpr bool W3REG = RG < 4;
+    float4 w3a[2], w3b[2];
+    auto load_w3 = [&]() {
+        const rsrc_t rw3 = make_rsrc(G.P3, (unsigned)tiles3 * (unsigned)C3 * 2048u);
+#pragma unroll
+        for (int g = 0; g < 2; ++g) {
+            const unsigned o = (l3res && g < tiles3 && wv < C3)
+                ? (((unsigned)g * (unsigned)C3 + (unsigned)wv) * 512u + (unsigned)lane * 4u) * 4u : OOB;
+            w3a[g] = ld16(rw3, o);
+            w3b[g] = ld16(rw3, o == OOB ? OOB : o + 1024u);
+        }
+    };
+    if (W3REG) load_w3();
+    float* red3 = sm + G.off_red3;               // [RNWV][RB][32]: the waves' partial output sums
+    const int hr = tid / A, hj = tid - hr * A;            // RB x A <= 512 pairs
+    const float b3v = G.b3[hj];
+    const float sd0 = expf(G.log_var[hj]);
+    const bool noisy = G.nstream.enabled != 0;
+    // the pair's actor and the draw step of its episode's first step
+    long ha = 0;
+    int hk0 = 0;
+    if (hr < nrows) {
+        const long row = row0 + hr;
+        ha = row / G.ev.E;
+        hk0 = (int)(row - ha * G.ev.E) * G.episode_len;
+    }
+    EvalReturns ret;
+#pragma unroll 1
+    for (int step = 0; step < G.steps; ++step) {
+        float ev = 0.f;                              // this step's draw, requested before the layers
+        if (noisy && hr < nrows) ev = noise_draw(G.nstream, ha, hk0 + step, hj);
+        if constexpr (LSTM) {
+            const PreLayer gate{G.Pg, G.bg, 4 * G.H, G.Dp + G.H, G.off_g, G.ldg};
+            layers4<RG, NT, true>(G, sm, l3res ? 2 : 3, G.out_act, wv, lane, [&](int l) {
+                if (l >= 0) return;
+                // ---- the cell pass (smx_lstm.hip's gate functions and update order) ----
+                const float* gs = sm + G.off_g;
+                const int H = G.H, ldx = G.ldx, ldg = G.ldg, Hl = G.Hl;
+                float* cst = sm + G.off_c;
+#pragma unroll 1
+                for (int q = tid; q < RB * H; q += RNTH) {
+                    const int r = q / H, j = q - r * H;
+                    const float* g = gs + r * ldg + j;
+                    const float gi = fast_sigm(g[0]), gf = fast_sigm(g[H]), gg = fast_tanh(g[2 * H]),
+                                go = fast_sigm(g[3 * H]);
+                    float c = gf * cst[q] + gi * gg;
+                    float h = go * fast_tanh(c);
+                    if (j >= Hl) c = h = 0.f;            // (a padded unit: exactly zero whatever its weights)
+                    cst[q] = c;
+                    sm[r * ldx + G.Dp + j] = h;
+                }
+                SMX_LDS_BARRIER();
+            }, G.Dp, G.H, gate);
+        } else {
+            layers4<RG, NT>(G, sm, l3res ? 2 : 3, G.out_act, wv, lane, [](int) {}, 0, G.D);
+        }
+        if (l3res) {
+            if (!W3REG) load_w3();
+            constexpr int RC = RG < 4 ? RG : 1;
+#pragma unroll 1
+            for (int rg0 = 0; rg0 < RG; rg0 += RC) {
+                const float* bp = h2s + (lane & 3) * ldh2 + 8 * kq + 32 * (wv < C3 ? wv : 0) + 4 * rg0 * ldh2;
+                f32x4 a3[2][RC];
+#pragma unroll
+                for (int g = 0; g < 2; ++g)
+#pragma unroll
+                    for (int r = 0; r < RC; ++r) a3[g][r] = (f32x4){0.f, 0.f, 0.f, 0.f};
+                float4 x0[RC], x1[RC];
+#pragma unroll
+                for (int r = 0; r < RC; ++r) {
+                    x0[r] = *(const float4*)(bp + 4 * r * ldh2);
+                    x1[r] = *(const float4*)(bp + 4 * r * ldh2 + 4);
+                }
+#define SMX_L3(X, W, E)                                                      \
+                _Pragma("unroll") for (int g = 0; g < 2; ++g)                    \
+                    _Pragma("unroll") for (int r = 0; r < RC; ++r) a3[g][r] = MFMA4(X[r].E, W[g].E, a3[g][r]);
+                SMX_L3(x0, w3a, x) SMX_L3(x0, w3a, y) SMX_L3(x0, w3a, z) SMX_L3(x0, w3a, w)
+                SMX_L3(x1, w3b, x) SMX_L3(x1, w3b, y) SMX_L3(x1, w3b, z) SMX_L3(x1, w3b, w)
+#undef SMX_L3
+#pragma unroll
+                for (int g = 0; g < 2; ++g)
+#pragma unroll
+                    for (int r = 0; r < RC; ++r) {
+                        const float z = meet_rows(a3[g][r]);
+                        red3[(wv * RB + 4 * (rg0 + r) + kq) * 32 + 16 * g + fm] = z;
+                    }
+            }
+            SMX_LDS_BARRIER();
+        }
+        // ---- the head (ppo_rollout's expressions): one (row, action) pair per lane -------------------------------------
+        if (hr < nrows) {
+            float mu;
+            if (l3res) {
+                float p8[RNWV];
+#pragma unroll
+                for (int w = 0; w < RNWV; ++w) p8[w] = red3[(w * RB + hr) * 32 + hj];
+                float z = p8[0];
+#pragma unroll
+                for (int w = 1; w < RNWV; ++w) z += p8[w];
+                mu = act_f(z + b3v, G.out_act);
+            } else {
+                mu = outs[hr * RLDO + hj];
+            }
+            float act = noisy ? ev * sd0 + mu : mu;
+            if (act == act) act = fminf(fmaxf(act, -1.0f), 1.0f);
+            s_act[hr * RMAX_A + hj] = act;
+        }
+        SMX_LDS_BARRIER();
+        E.step(s_act, false, [](long) { return EvalNoRow{}; }, [](long, EvalNoRow, int, float, float) {},
+               [&](long row, EvalNoRow, float rew) { ret.add(E, row, rew); });
+        SMX_LDS_BARRIER();
+    }
+    ret.store(E, G.ev.returns);
+}
+
+// DDPG: ddpg_rollout_kernel's step in a deterministic agent mode (tanh, clip; SMX_DDPG_NOISE_NONE) without a record
+template <int RG, int NT, int TASK>
+__global__ __launch_bounds__(RNTH) void ddpg_eval_kernel(DEvalArgs G) {
+    constexpr int RB = 4 * RG;
+    extern __shared__ float sm[];
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int A = G.A;
+    const float* outs = sm + G.off_out;
+    float* s_act = sm + G.off_act;                   // [RB][RMAX_A] the actions of this step (unused columns stay 0)
+
+    clear_tiles(G, sm, tid, nullptr, nullptr, nullptr, 0.f);
+    EnvLanes<RB, true, TASK> E(G, sm, nullptr, wv, lane, OwnStart{});
+    if constexpr (TASK == SMX_TASK_REACH) {
+        E.rst = nullptr;                             // (done is false at every step: never read)
+        E.ends = 0;
+        eval_start(E, G.ev, G.ev.rst.enabled != 0);
+    } else {
+        eval_start(E, G.ev, false);
+    }
+    SMX_LDS_BARRIER();
+    E.start();
+    const int hr = tid / A, hj = tid - hr * A;       // RB x A <= 512 pairs
+    const bool head = hr < E.nrows;
+    SMX_LDS_BARRIER();
+    EvalReturns ret;
+#pragma unroll 1
+    for (int step = 0; step < G.steps; ++step) {
+        layers4<RG, NT>(G, sm, 3, SMX_ACT_TANH, wv, lane, [](int) {}, 0, G.D);
+        if (head) s_act[hr * RMAX_A + hj] = clip1(clip1(outs[hr * RLDO + hj]));      // (explore() without noise)
+        SMX_LDS_BARRIER();
+        E.step(s_act, false, [](long) { return EvalNoRow{}; }, [](long, EvalNoRow, int, float, float) {},
+               [&](long row, EvalNoRow, float rew) { ret.add(E, row, rew); });
+        SMX_LDS_BARRIER();
+    }
+    ret.store(E, G.ev.returns);
+}
+
 // The one-step body both step kernels share, in two phases with a barrier between them.  Phase 1, lane = action j < A
 // of actor a: exploration, the open transition's action, the closing transition's (ring row `row`); the actions go to
 // s_act_w.  Phase 2, one wavefront: the environment step, the open observation and reward, the closing transition's
@@ -1870,7 +2144,8 @@ __host__ __device__ inline int lstm_dp(int D) { return (D + 3) & ~3; }
 // The LSTM rollout's LDS: carve()'s layout with the x tile widened to [x | 0 | h], then the gate tile [RB][ldg]
 // (rewritten whole by every gate pass: not cleared) and the cells [RB H] (pair q = r H + j: written and read by thread
 // q mod RNTH alone)
-int carve_lstm(LArgs& G, int RB) {
+template <typename LstmArgs>
+int carve_lstm(LstmArgs& G, int RB) {
     G.Dp = lstm_dp(G.D);
     carve(G, RB, /*mma16=*/false, /*split_out=*/true, /*ztables=*/true, G.Dp + rr64(G.H));
     G.off_g = (G.off_kmod + G.D + 3) & ~3;
@@ -2572,4 +2847,94 @@ extern "C" int smx_synth_ppo_pixel_window_step(const struct smx_synth_ppo_pixel_
                                            ? (long long)(args->n_step + 1) * S - 1 : 0));
     if (args->copy_workgroups) P.X = args->copy_workgroups;
     return launch_pixel<ppo_pixel_window_step_kernel<16>, ppo_pixel_window_step_kernel<1>>(G, P, args->n, mu, ld_mu, stream);
+}
+
+// ---- evaluation: whole episodes in one launch, nothing recorded ---------------------------------------------------------
+
+extern "C" int32_t smx_synth_eval_supported(int32_t ddpg, int32_t task, int32_t D, int32_t H, int32_t H1, int32_t H2,
+                                            int32_t A) {
+    if (!synth_task_ok(task, D, A)) return 0;
+    if (ddpg) return H == 0 && smx_synth_ddpg_rollout_supported(D, H1, H2, A, 0);
+    if (H < 0) return 0;
+    return smx_synth_ppo_window_rollout_supported(D, H, H1, H2, A);
+}
+
+// what both evaluation entry points ask of the rows and the reset stream -> the kernels' tail
+static int eval_tail(int32_t n, int32_t episodes, int32_t episode_len, int32_t task, const smx_reset_stream& resets,
+                     double* returns, EvalTail& V) {
+    SMX_REQUIRE(!(resets.enabled && task == SMX_TASK_DRIFT), SMX_E_UNSUPPORTED);
+    SMX_REQUIRE(n > 0 && episodes >= 1 && episode_len >= 1, SMX_E_SHAPE);
+    SMX_REQUIRE((long long)n * episodes < (1LL << 31) && (long long)episodes * episode_len < (1LL << 31), SMX_E_SHAPE);
+    SMX_REQUIRE(reset_shape_ok(resets, n), SMX_E_SHAPE);
+    memset(&V, 0, sizeof(V));
+    V.E = episodes;
+    if (resets.enabled) V.rst = resets;
+    V.returns = returns;
+    return SMX_OK;
+}
+
+extern "C" int smx_synth_ppo_eval_f32(const struct smx_synth_ppo_eval* a, smx_stream_t stream) {
+    SMX_REQUIRE(a && a->net && a->packed && a->log_var && a->init_state && a->returns, SMX_E_NULL);
+    const bool lstm = a->lstm != nullptr;
+    SMX_REQUIRE(!lstm || a->lstm_packed, SMX_E_NULL);
+    SMX_REQUIRE((a->zsum == nullptr) == (a->zsumsq == nullptr) && (a->zsum == nullptr) == (a->zcount == nullptr), SMX_E_NULL);
+    const smx_mlp3_t& n = *a->net;
+    const int D = lstm ? a->lstm->D : n.D;
+    SMX_REQUIRE(!lstm || lstm_shape_ok(n, *a->lstm, a->hidden), SMX_E_SHAPE);
+    SMX_REQUIRE(smx_synth_eval_supported(0, a->task, D, lstm ? a->lstm->H : 0, n.H1, n.H2, n.OUT), SMX_E_UNSUPPORTED);
+    SMX_REQUIRE(block_ok(a->actors_per_workgroup) && noise_shape_ok(a->noise, a->n), SMX_E_SHAPE);
+    PEvalArgs G;
+    memset(&G, 0, sizeof(G));
+    const int rc = eval_tail(a->n, a->episodes, a->episode_len, a->task, a->resets, a->returns, G.ev);
+    if (rc != SMX_OK) return rc;
+    SMX_REQUIRE(aligned_ok(a->packed, n.b1, lstm ? a->lstm_packed : nullptr), SMX_E_ALIGN);
+    net_fields(n, a->packed, G);
+    G.D = D; G.A = n.OUT; G.out_act = a->out_act; G.log_var = a->log_var;
+    G.zsum = a->zsum; G.zsumsq = a->zsumsq; G.zcount = a->zcount; G.zeps = a->zeps;
+    G.init_state = a->init_state;
+    G.n = a->n * a->episodes;                        // the rows
+    G.steps = G.episode_len = a->episode_len;
+    if (a->noise.enabled) G.nstream = a->noise;
+    const int rb = pick_block(a->actors_per_workgroup, G.n);
+    const bool reach = a->task == SMX_TASK_REACH;
+    if (!lstm) {
+        const int lds = carve(G, rb, /*mma16=*/false, /*split_out=*/true, /*ztables=*/true, G.D);
+        if (reach)
+            return launch<ppo_eval_kernel<1, 3, false, true, SMX_TASK_REACH>, ppo_eval_kernel<2, 3, false, true, SMX_TASK_REACH>,
+                          ppo_eval_kernel<4, 2, false, false, SMX_TASK_REACH>>(G, rb, lds, stream);
+        return launch<ppo_eval_kernel<1, 3, false, true, SMX_TASK_DRIFT>, ppo_eval_kernel<2, 3, false, true, SMX_TASK_DRIFT>,
+                      ppo_eval_kernel<4, 2, false, false, SMX_TASK_DRIFT>>(G, rb, lds, stream);
+    }
+    G.H = a->lstm->H; G.Hl = a->hidden;
+    G.Pg = a->lstm_packed; G.bg = a->lstm_packed + pack_words(4 * G.H, lstm_dp(D) + G.H) * 4;
+    const int lds = carve_lstm(G, rb);
+    if (reach)
+        return launch<ppo_eval_kernel<1, 3, true, true, SMX_TASK_REACH>, ppo_eval_kernel<2, 3, true, true, SMX_TASK_REACH>,
+                      ppo_eval_kernel<4, 2, true, false, SMX_TASK_REACH>>(G, rb, lds, stream);
+    return launch<ppo_eval_kernel<1, 3, true, true, SMX_TASK_DRIFT>, ppo_eval_kernel<2, 3, true, true, SMX_TASK_DRIFT>,
+                  ppo_eval_kernel<4, 2, true, false, SMX_TASK_DRIFT>>(G, rb, lds, stream);
+}
+
+extern "C" int smx_synth_ddpg_eval_f32(const struct smx_synth_ddpg_eval* a, smx_stream_t stream) {
+    SMX_REQUIRE(a && a->net && a->packed && a->init_state && a->returns, SMX_E_NULL);
+    const smx_mlp3_t& n = *a->net;
+    SMX_REQUIRE(smx_synth_eval_supported(1, a->task, n.D, 0, n.H1, n.H2, n.OUT), SMX_E_UNSUPPORTED);
+    SMX_REQUIRE(block_ok(a->actors_per_workgroup), SMX_E_SHAPE);
+    DEvalArgs G;
+    memset(&G, 0, sizeof(G));
+    const int rc = eval_tail(a->n, a->episodes, a->episode_len, a->task, a->resets, a->returns, G.ev);
+    if (rc != SMX_OK) return rc;
+    SMX_REQUIRE(aligned_ok(a->packed, n.b1, nullptr), SMX_E_ALIGN);
+    net_fields(n, a->packed, G);
+    G.D = n.D; G.A = n.OUT;
+    G.init_state = a->init_state;
+    G.n = a->n * a->episodes;                        // the rows
+    G.steps = G.episode_len = a->episode_len;
+    const int rb = pick_block(a->actors_per_workgroup, G.n);
+    const int lds = carve(G, rb, /*mma16=*/false, /*split_out=*/false, /*ztables=*/false, G.D);
+    if (a->task == SMX_TASK_REACH)
+        return launch<ddpg_eval_kernel<1, 3, SMX_TASK_REACH>, ddpg_eval_kernel<2, 3, SMX_TASK_REACH>,
+                      ddpg_eval_kernel<4, 2, SMX_TASK_REACH>>(G, rb, lds, stream);
+    return launch<ddpg_eval_kernel<1, 3, SMX_TASK_DRIFT>, ddpg_eval_kernel<2, 3, SMX_TASK_DRIFT>,
+                  ddpg_eval_kernel<4, 2, SMX_TASK_DRIFT>>(G, rb, lds, stream);
 }

@@ -13,7 +13,8 @@ where a report goes and what happens after it, so they share ``_PeriodicReport``
                               eval_env_sleep seconds and fetches fresh parameters
 
 ``DeviceEpisodeMonitor`` / ``DeviceTrainingMonitor`` are the same bookkeeping and the training reports for the actors
-of a ``SyntheticVecEnv``, whose steps run on the device and never pass through a host ``Env``.
+of a ``SyntheticVecEnv``, whose steps run on the device and never pass through a host ``Env``; ``DeviceEvaluator`` is the
+evaluation worker behind ``EvalTensorplexMonitor`` for them: whole episodes in one launch (``SyntheticVecEnv.evaluate``).
 
 The tensorplex process of the reference is replaced by any object with
 ``add_scalars(dict, global_step=...)`` (default: the in-memory ScalarRecorder the learners use).
@@ -474,6 +475,81 @@ class _DeviceActorReport(TrainingTensorplexMonitor):
         self.episode_steps.append(steps)
         self._finished += 1
         self._on_episode_end()
+
+
+class _DeviceEvalReport(_TensorplexReport):
+    """EvalTensorplexMonitor's report for one actor of a DeviceEvaluator: the same period (update_schedule.eval_env),
+    mean, tags and global_step under 'eval/<id>', fed with the returns of an evaluation launch instead of wrapping an
+    env; it neither sleeps nor fetches (the evaluator fetches once per run)"""
+    group, schedule_key = 'eval', 'eval_env'
+
+    def __init__(self, owner, eval_id, session_config, separate_plots, tensorplex):
+        super().__init__(None, eval_id, session_config, separate_plots, tensorplex)
+        self._owner = owner
+        self._finished = 0
+
+    @property
+    def num_episodes(self):
+        return self._finished
+
+    def step_per_sec(self, average_episodes):
+        return self._owner.step_per_s
+
+    def feed(self, reward, steps):
+        self.episode_rewards.append(reward)
+        self.episode_steps.append(steps)
+        self._finished += 1
+        self._on_episode_end()
+
+
+class DeviceEvaluator(object):
+    """The reference's evaluation worker behind EvalTensorplexMonitor (surreal/agent/base.py:277-345,
+    surreal/env/monitor.py:164-218) for the n actors of a SyntheticVecEnv: run() fetches the agent's parameters, runs
+    `episodes` whole episodes of every actor in ONE launch (SyntheticVecEnv.evaluate: nothing recorded, the env's state
+    untouched), copies the [n, episodes] returns to the host once and feeds actor i's -- each round(x, 6), as
+    EpisodeMonitor reports an episode -- to a report under 'eval/<eval_id_base + i>': every eval_env-th episode of an
+    actor, 'reward' (':reward' with separate_plots; the mean of its last eval_env returns) and 'step_per_s' with
+    global_step = that actor's episode count.  No sleep between reports: a run is one launch.
+    resets: evaluate()'s -- None, or (seed, first_episode[, actor_base]): the same held-out episodes every run.
+    noise (an 'eval_stochastic' PPO agent): evaluate()'s (seed, first_step[, actor_base]); every run moves first_step on
+    by its episodes * episode_len steps.  tensorplex None: one ScalarRecorder per actor (reports[i].tensorplex), else
+    the one object all share.
+    step_per_s: the environment steps of one actor per second of the last run()'s wall time."""
+
+    def __init__(self, env, agent, session_config, episodes, resets=None, eval_id_base=0, tensorplex=None,
+                 separate_plots=False, noise=None):
+        if int(episodes) < 1:
+            raise ValueError('DeviceEvaluator: episodes must be positive, got %r' % (episodes,))
+        self.env, self.agent, self.episodes = env, agent, int(episodes)
+        self.resets = None if resets is None else tuple(int(v) for v in resets)
+        self.noise = None if noise is None else [int(v) for v in noise]
+        self.reports = [_DeviceEvalReport(self, int(eval_id_base) + i, session_config, separate_plots, tensorplex)
+                        for i in range(env.n)]
+        self.step_per_s = 0.0
+        self.runs = 0
+        self._out = None
+
+    def run(self):
+        """-> the returns of this run, np.float64 [n, episodes]"""
+        self.agent.fetch_parameter()
+        E, steps = self.episodes, int(self.env.episode_len)
+        t0 = time.time()
+        kw = {} if self.noise is None else {'noise': tuple(self.noise)}
+        self._out = self.env.evaluate(self.agent, E, resets=self.resets, out=self._out, **kw)
+        host = self._out.cpu().numpy()                 # (the one device -> host copy; it waits for the launch)
+        if self.noise is not None:
+            self.noise[1] += E * steps
+        self.step_per_s = E * steps / (time.time() - t0 + 1e-7)
+        self.runs += 1
+        for i, report in enumerate(self.reports):
+            for e in range(E):
+                report.feed(round(float(host[i, e]), 6), steps)
+        return host
+
+    def mean_return(self):
+        """the mean over the last run's returns of every actor (None before the first run)"""
+        xs = [r for report in self.reports for r in report.episode_rewards[-self.episodes:]]
+        return _mean(xs) if xs else None
 
 
 class DeviceTrainingMonitor(object):

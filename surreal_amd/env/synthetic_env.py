@@ -999,6 +999,116 @@ class SyntheticVecEnv(object):
         replay.commit_ring(rows)
         return rows
 
+    def _eval_refusal(self, agent):
+        """why the evaluation launch cannot take `agent`'s policy on this env -> (exception class, message), or None"""
+        m = agent.model
+        ppo = hasattr(agent, 'rnn_config')
+        camera = bool(m.if_pixel if ppo else m.is_pixel_input)
+        only = ('the evaluation launch runs a plain-MLP or one-layer LSTM PPO policy or a plain DDPG actor on '
+                'low-dimensional observations, on one shared clock, only')
+        what = ('a camera env' if self.pixel is not None else 'a camera agent' if camera else
+                'per-actor episode clocks' if self.per_actor_clocks else
+                'rnn_layer %d' % agent.rnn_config.rnn_layer
+                if ppo and agent.rnn_config.if_rnn_policy and agent.rnn_config.rnn_layer != 1 else
+                'a LayerNorm actor' if not ppo and m.use_layernorm else
+                'an attached parameter noise' if not ppo and self.param_noise is not None else None)
+        if what is not None:
+            return NotImplementedError, 'evaluate with %s: %s' % (what, only)
+        if getattr(self.K, 'synth_ppo_eval' if ppo else 'synth_ddpg_eval', None) is None:
+            return NotImplementedError, 'evaluate: the kernels object has no %s' % ('synth_ppo_eval' if ppo else
+                                                                                    'synth_ddpg_eval')
+        if not (self.K.synth_eval_supported(self.task, model=m) if ppo else
+                self.K.synth_eval_supported(self.task, actor=m.actor)):
+            return NotImplementedError, ('evaluate: shapes the evaluation launch refuses (A <= 32, hidden sizes multiples '
+                                         'of 4 up to 640, D <= 512, LSTM units up to 128; task %r: action_dim <= %d; '
+                                         'smx_synth_eval_supported)' % (self.task, TK.REACH_MAX_A))
+        return None
+
+    def can_evaluate(self, agent):
+        """evaluate() takes `agent`'s policy: a plain-MLP or one-layer LSTM PPO policy, or a plain DDPG actor (no
+        LayerNorm, no attached parameter noise), on low-dimensional observations, whose shapes the launch takes, on an
+        env with one shared clock and no camera"""
+        return self._eval_refusal(agent) is None
+
+    @staticmethod
+    def _eval_stream(who, what, value, n):
+        """(seed, counter[, actor_base]) of evaluate()'s resets= / noise= -> the launches' (seed, actor_base, counter)"""
+        v = tuple(int(x) for x in value)
+        if len(v) not in (2, 3):
+            raise ValueError('%s: %s must be (seed, %s[, actor_base]), got %r' % (who, what[0], what[1], value))
+        seed, first, base = v[0], v[1], (v[2] if len(v) == 3 else 0)
+        if not 0 <= seed < 1 << 64:
+            raise ValueError('%s: the seed of %s must fit 64 bits, got %r' % (who, what[0], seed))
+        if first < 0:
+            raise ValueError('%s: %s %d is negative' % (who, what[1], first))
+        if base < 0 or base + n > 1 << 32:
+            raise ValueError('%s: global actor ids %d .. %d leave [0, 2^32)' % (who, base, base + n - 1))
+        return (seed, base, first)
+
+    def evaluate(self, agent, episodes=1, resets=None, noise=None, out=None, actors_per_workgroup=0):
+        """`episodes` whole episodes of every actor under `agent`'s policy in ONE launch, nothing recorded -> their
+        returns, torch.float64 [n, episodes] on the device (`out`, or a new tensor); no synchronisation.  The device form
+        of the reference's evaluation workers (agent_mode eval_deterministic / eval_stochastic, surreal/agent/base.py:
+        277-345) and of surreal/main/rollout.py (smx_synth_ppo_eval_f32 / smx_synth_ddpg_eval_f32).
+        The (actor, episode) pairs are independent rows of the launch: n * episodes rows walk episode_len steps each.
+        resets: None -- every episode begins at init_state[a] -- or (seed, first_episode[, actor_base]), task 'reach'
+        only: episode i of actor a begins with tasks.reach_reset_state(seed, actor_base + a, first_episode + i, J),
+        drawn inside the launch.
+        The mode is the agent's: 'eval_deterministic[_local]' acts on the policy's mean (noise must be None);
+        'eval_stochastic[_local]', PPO only, samples -- noise = (seed, first_step[, actor_base]) is required, and step t
+        of episode i of actor a draws normal(seed, actor_base + a, first_step + i * episode_len + t, j): what a serial
+        run of the actor's episodes on that noise stream draws; 'training': ValueError.  An LSTM policy starts every
+        episode from the zero state.
+        Pure: neither state, the clock, the attached streams' counters, the monitor, the open windows and transitions,
+        agent._batch_cells nor any replay is read or written -- it can be called on the training env between chunks.
+        actors_per_workgroup: 4 | 8 | 16 forces the kernel's block of rows (0: automatic; every size gives the same bits)."""
+        refusal = self._eval_refusal(agent)
+        if refusal is not None:
+            raise refusal[0](refusal[1])
+        ppo = hasattr(agent, 'rnn_config')
+        mode = agent.agent_mode
+        if mode not in ('eval_deterministic', 'eval_deterministic_local', 'eval_stochastic', 'eval_stochastic_local'):
+            raise ValueError('evaluate: agent_mode %r; an evaluation agent (eval_deterministic[_local] / '
+                             'eval_stochastic[_local])' % (mode,))
+        stochastic = mode in ('eval_stochastic', 'eval_stochastic_local')
+        if stochastic and not ppo:
+            raise NotImplementedError('evaluate with a DDPG agent in %r: the evaluation launch runs a DDPG actor without '
+                                      'exploration noise (eval_deterministic[_local]), only' % (mode,))
+        if stochastic and noise is None:
+            raise ValueError('evaluate: agent_mode %r samples: noise=(seed, first_step[, actor_base]) is required' % (mode,))
+        if not stochastic and noise is not None:
+            raise ValueError('evaluate: agent_mode %r draws nothing: noise must be None' % (mode,))
+        E, n = int(episodes), self.n
+        if E < 1:
+            raise ValueError('evaluate: episodes must be positive, got %r' % (episodes,))
+        if resets is not None:
+            if self.task != 'reach':
+                raise ValueError("evaluate: task %r has no reset distribution (resets=: task 'reach')" % (self.task,))
+            resets = self._eval_stream('evaluate', ('resets', 'first_episode'), resets, n)
+        if noise is not None:
+            noise = self._eval_stream('evaluate', ('noise', 'first_step'), noise, n)
+        L_ = int(self.episode_len)
+        if n * E >= 1 << 31 or E * L_ >= 1 << 31:
+            raise ValueError('evaluate: %d actors x %d episodes x %d steps: n * episodes and episodes * episode_len must '
+                             'stay below 2^31' % (n, E, L_))
+        if out is None:
+            out = torch.empty(n, E, dtype=torch.float64, device=self.device)
+        elif out.dtype != torch.float64 or tuple(out.shape) != (n, E) or not out.is_contiguous():
+            raise ValueError('evaluate: out must be a contiguous torch.float64 [%d, %d] tensor' % (n, E))
+        m = agent.model
+        kw = dict(task=self.task, resets=resets, actors_per_workgroup=actors_per_workgroup)
+        # (packed copies of its own: the rollouts' stay as they are)
+        pk = self._packed('_epk', self.K.epoch_packed_numel(m.actor), lambda b: self.K.epoch_pack([(m.actor, b)]))
+        if not ppo:
+            self.K.synth_ddpg_eval(m.actor, pk, self.init_state, E, L_, out, **kw)
+            return out
+        lpk = None
+        if agent.rnn_config.if_rnn_policy:
+            lpk = self._packed('_elpk', self.K.lstm_rollout_packed_numel(m.rnn), lambda b: self.K.lstm_rollout_pack(m.rnn, b))
+        self.K.synth_ppo_eval(m, pk, lpk, self.init_state, E, L_, out, zfilter=m.z_filter if agent.use_z_filter else None,
+                              noise=noise, **kw)
+        return out
+
     def _frame_pool_plan(self, replay, T, N):
         """the next T steps of the shared clock in a replay's frame pool -> {'frames': [(f, first)] before each step and
         after the last: the counter of the current frame and of the episode's reset frame; 'steps': what

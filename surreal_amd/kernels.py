@@ -921,6 +921,69 @@ class HipKernels(object):
         tid = self._task_id(task) if isinstance(task, str) else int(task)
         return bool(self.lib.smx_synth_task_supported(tid, int(D), int(A)))
 
+    def synth_eval_supported(self, task, model=None, actor=None):
+        """the policies the evaluation launches take on `task` (smx_synth_eval_supported): model, a PPOModel with a
+        plain-MLP or one-layer LSTM policy on low-dimensional observations; or actor, a plain DDPG actor's Mlp3Params"""
+        tid = self._task_id(task)
+        if actor is not None:
+            return bool(self.lib.smx_synth_eval_supported(1, tid, actor.D, 0, actor.H1, actor.H2, actor.OUT))
+        if model.if_pixel or (model.if_rnn and model.rnn_layers != 1):
+            return False
+        a = model.actor
+        if not model.if_rnn:
+            return bool(self.lib.smx_synth_eval_supported(0, tid, a.D, 0, a.H1, a.H2, a.OUT))
+        r = model.rnn
+        return a.D == r.H and bool(self.lib.smx_synth_eval_supported(0, tid, r.D, r.H, a.H1, a.H2, a.OUT))
+
+    @staticmethod
+    def _eval_returns(returns, n, episodes):
+        assert returns.dtype == torch.float64 and returns.is_contiguous() and tuple(returns.shape) == (n, episodes)
+        return L.ptr(returns)
+
+    def synth_ppo_eval(self, model, packed, lstm_packed, init_state, episodes, episode_len, returns, zfilter=None,
+                       task='drift', resets=None, noise=None, actors_per_workgroup=0, out_act=L.SMX_ACT_TANH):
+        """`episodes` whole episodes of every actor under PPOModel `model`'s policy, ONE launch, nothing recorded
+        (smx_synth_ppo_eval_f32): returns [n, episodes] fp64 <- the episodes' returns.  packed: epoch_pack of model.actor,
+        lstm_packed: lstm_rollout_pack of model.rnn (None: a plain MLP); init_state [n, D]; resets: (seed, actor_base,
+        first_episode) of the reset stream the episodes begin from, or None: every episode begins at init_state[a];
+        noise: (seed, actor_base, first_step) -- the policy samples (eval_stochastic) -- or None: it acts on its mean;
+        out_act: the output layer's activation (PPOModel's is tanh)"""
+        n = init_state.shape[0]
+        assert init_state.is_contiguous() and init_state.dtype == torch.float32
+        p = L.SynthPpoEval()
+        a = model.actor
+        p.net, p.packed, p.out_act, p.n = ctypes.pointer(a.desc), L.ptr(packed), int(out_act), n
+        p.log_var = L.ptr(model.log_var)
+        if zfilter is not None:
+            p.zsum, p.zsumsq, p.zcount = L.ptr(zfilter.running_sum), L.ptr(zfilter.running_sumsq), L.ptr(zfilter.count)
+            p.zeps = float(zfilter.eps)
+        p.episodes, p.episode_len, p.task = int(episodes), int(episode_len), self._task_id(task)
+        p.actors_per_workgroup = int(actors_per_workgroup)
+        if model.if_rnn:
+            p.lstm, p.lstm_packed, p.hidden = ctypes.pointer(model.rnn.desc), L.ptr(lstm_packed), \
+                model.rnn_hidden_logical
+        p.init_state = L.ptr(init_state)
+        if resets is not None:
+            p.resets = self._reset_args(resets)
+        p.noise = self._noise_args(noise)
+        p.returns = self._eval_returns(returns, n, int(episodes))
+        L.call('smx_synth_ppo_eval_f32', ctypes.byref(p), self._st())
+
+    def synth_ddpg_eval(self, net, packed, init_state, episodes, episode_len, returns, task='drift', resets=None,
+                        actors_per_workgroup=0):
+        """the same for a plain DDPG actor `net` in a deterministic agent mode (smx_synth_ddpg_eval_f32)"""
+        n = init_state.shape[0]
+        assert init_state.is_contiguous() and init_state.dtype == torch.float32
+        p = L.SynthDdpgEval()
+        p.net, p.packed, p.n = ctypes.pointer(net.desc), L.ptr(packed), n
+        p.episodes, p.episode_len, p.task = int(episodes), int(episode_len), self._task_id(task)
+        p.actors_per_workgroup = int(actors_per_workgroup)
+        p.init_state = L.ptr(init_state)
+        if resets is not None:
+            p.resets = self._reset_args(resets)
+        p.returns = self._eval_returns(returns, n, int(episodes))
+        L.call('smx_synth_ddpg_eval_f32', ctypes.byref(p), self._st())
+
     def actor_clock_rows(self, t, episode_len, steps, n_step, advance, row_off, t_host=None, episode_len_host=None):
         """row_off [steps, n] int32 <- where every closing (step, actor) pair of a call of `steps` steps goes, counted
         from the ring's cursor in (step, actor) order, -1 where the pair closes nothing (smx_actor_clock_rows_i32): actor
