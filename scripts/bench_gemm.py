@@ -1,12 +1,13 @@
-"""micro-benchmark of the layer GEMM kernel (GPU box): time vs K and vs tile count"""
+"""micro-benchmark of the layer GEMM kernel (GPU box): time vs K and vs tile count; argv[1]: launches per timing (50)"""
 import sys, os
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import torch
 from surreal_amd.kernels import HipKernels
 K = HipKernels()
+ITERS = int(sys.argv[1]) if len(sys.argv) > 1 else 50
 
-def timeit(fn, n=50):
+def timeit(fn, n=ITERS):
     for _ in range(5): fn()
     torch.cuda.synchronize()
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)

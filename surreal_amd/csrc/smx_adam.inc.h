@@ -1,6 +1,5 @@
-// clip_grad_norm_ + torch.optim.Adam's single-tensor step, shared by the optimiser launch (smx_ppo.hip:
-// clip_adam_kernel) and by the weight-gradient launch that steps its own tiles (smx_gemm.hip: gemm32_adam_kernel) --
-// one source, so that both form the same bits.  Included inside an anonymous namespace, after smx_epoch_pack.inc.h.
+// clip_grad_norm_ + torch.optim.Adam's single-tensor step for the optimiser launch (smx_ppo.hip: clip_adam_kernel).
+// Included inside an anonymous namespace, after smx_epoch_pack.inc.h.
 //   torch/nn/utils/clip_grad.py: clip_coef = max_norm / (total_norm + 1e-6), clamped to <= 1, always multiplied in
 //   (a NaN or inf gradient makes the norm NaN / inf and the step NaN, as in torch)
 //   torch/optim/adam.py _single_tensor_adam (the reference's optimisers: surreal/learner/ppo.py:120-135)

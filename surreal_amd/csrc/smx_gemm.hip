@@ -15,9 +15,6 @@
 
 namespace {
 
-#include "smx_epoch_pack.inc.h"
-#include "smx_adam.inc.h"
-
 struct GemmProb {
     const float* A;
     const float* B;
@@ -30,7 +27,8 @@ struct GemmProb {
     int ldct;
     int lda, ldb, ldc, M, N, K;
     int a_kc, b_kc, act;
-    int tiles_m, tiles_n, tile_base, a_mode, b_mode;   // 0 kc-vec, 1 kc-scalar, 2 k-strided
+    int tiles_m, tiles_n, tile_base;   // in tiles of the kernel that takes the batch: written by plan_batch() alone
+    int a_mode, b_mode;                // 0 kc-vec, 1 kc-scalar, 2 k-strided
     unsigned a_bytes, b_bytes;   // extent of each operand for the buffer descriptors (< 2 GiB)
     const int* stop;     // device flag: non-zero -> this problem is skipped
     // split-K (weight gradients over many rows): `splits` workgroups share an output tile, each
@@ -70,11 +68,10 @@ __device__ __forceinline__ TileBases load_tile_bases(const GemmBatch& G) {
 }
 
 // batch 2: the whole descriptor of the problem that owns tile `bid`
-__device__ __forceinline__ GemmProb select_problem(const GemmBatch& G, const TileBases& t, int bid, int* pi_out = nullptr) {
+__device__ __forceinline__ GemmProb select_problem(const GemmBatch& G, const TileBases& t, int bid) {
     int pi = 0;
 #pragma unroll
     for (int k = 1; k < MAX_PROBS; ++k) pi += (k < t.n && bid >= t.tb[k]) ? 1 : 0;   // tile_base ascends
-    if (pi_out) *pi_out = pi;
     GemmProb P = G.p[pi];
     asm volatile("" :: "s"(P.A), "s"(P.B), "s"(P.bias), "s"(P.mask), "s"(P.C), "s"(P.dbias), "s"(P.sumsq),
                  "s"(P.CT), "s"(P.stop), "s"(P.c_split), "s"(P.ldct), "s"(P.lda), "s"(P.ldb), "s"(P.ldc),
@@ -188,6 +185,26 @@ struct KRange {          // the K range this workgroup sums (the whole K unless 
     int K;
 };
 
+// split-K (weight gradients over 10^4 - 10^5 rows): `splits` consecutive workgroups share an output tile, each sums its
+// own K chunk into its own slice of C (and of dbias).  `tile` comes in as the workgroup's index inside the problem and
+// leaves as its output tile, `sp` as its chunk.
+__device__ __forceinline__ KRange k_range(const GemmProb& P, int& tile, int& sp) {
+    KRange R;
+    R.A = P.A; R.B = P.B; R.a_bytes = P.a_bytes; R.b_bytes = P.b_bytes; R.K = P.K;
+    sp = 0;
+    if (P.splits > 1) {
+        sp = tile % P.splits;
+        tile /= P.splits;
+        const int k0 = sp * P.k_chunk;
+        R.K = min(P.k_chunk, P.K - k0);
+        R.A = P.A + (P.a_kc ? (size_t)k0 : (size_t)k0 * P.lda);
+        R.B = P.B + (P.b_kc ? (size_t)k0 : (size_t)k0 * P.ldb);
+        R.a_bytes = 4u * (P.a_kc ? (unsigned)(P.M - 1) * P.lda + R.K : (unsigned)(R.K - 1) * P.lda + P.M);
+        R.b_bytes = 4u * (P.b_kc ? (unsigned)(P.N - 1) * P.ldb + R.K : (unsigned)(R.K - 1) * P.ldb + P.N);
+    }
+    return R;
+}
+
 // `wv` / NW: this wave takes super-blocks wv, wv + NW, ... (NW = 4: the waves of a workgroup split K;
 // NW = 1: the wave walks all of K by itself)
 template <int AM, int BM, int NW = 4>
@@ -222,6 +239,23 @@ __device__ __forceinline__ void mainloop(const GemmProb& P, const KRange& R, int
         if (sb + 2 * NW < nsb) mma_sb(acc, asum, f2);
         __builtin_amdgcn_sched_barrier(0);
         load_sb<AM, BM>(f2, O, (sb + 5 * NW) * 32 + kofs);
+    }
+}
+
+// the problem's operand-mode pair (workgroup-uniform) -> its mainloop instantiation
+template <int NW>
+__device__ __forceinline__ void mainloop_modes(const GemmProb& P, const KRange& R, int m0, int n0, int i, int kh, int wv,
+                                               f32x16& acc, float& asum) {
+    switch (P.a_mode * 3 + P.b_mode) {
+        case 0: mainloop<0, 0, NW>(P, R, m0, n0, i, kh, wv, acc, asum); break;
+        case 1: mainloop<0, 1, NW>(P, R, m0, n0, i, kh, wv, acc, asum); break;
+        case 2: mainloop<0, 2, NW>(P, R, m0, n0, i, kh, wv, acc, asum); break;
+        case 3: mainloop<1, 0, NW>(P, R, m0, n0, i, kh, wv, acc, asum); break;
+        case 4: mainloop<1, 1, NW>(P, R, m0, n0, i, kh, wv, acc, asum); break;
+        case 5: mainloop<1, 2, NW>(P, R, m0, n0, i, kh, wv, acc, asum); break;
+        case 6: mainloop<2, 0, NW>(P, R, m0, n0, i, kh, wv, acc, asum); break;
+        case 7: mainloop<2, 1, NW>(P, R, m0, n0, i, kh, wv, acc, asum); break;
+        default: mainloop<2, 2, NW>(P, R, m0, n0, i, kh, wv, acc, asum); break;
     }
 }
 
@@ -318,6 +352,8 @@ __device__ __forceinline__ void mainloop_co(const GemmProb& P, const KRange& R, 
 
 // ALL_VEC: every problem of the batch is mode (0, 0) -- the host picks this instantiation, which
 // fits 3 workgroups per CU (<= 168 VGPRs); the general one carries the scalar-load variants.
+// (body and kernel stay two functions: written as one, the compiler allots both instantiations two SGPRs fewer and a
+// different prologue -- the split keeps the kernels' resource figures where they were measured)
 template <bool ALL_VEC>
 __device__ __forceinline__ void gemm32_body(const GemmBatch& G) {
     __shared__ float red[4][32 * 33];
@@ -328,7 +364,9 @@ __device__ __forceinline__ void gemm32_body(const GemmBatch& G) {
     // XCD-aware order: consecutive workgroup ids land on the 8 XCDs round-robin, each with its own
     // L2.  Give XCD x the x-th contiguous eighth of the tile list (tiles are row-major in M, so
     // that is a band of A rows and all of B) instead of every 8th tile -- otherwise all eight L2s
-    // pull every operand of the launch across the fabric.
+    // pull every operand of the launch across the fabric.  (The same permutation as gemm_tile_kernel's, and
+    // deliberately not one helper: in that kernel's branch-free form this prologue measured 0.12 - 0.19 us per launch
+    // slower on the coalesced instantiation, 1 - 2 % of these short launches.)
     const TileBases TB = load_tile_bases(G);
     int bid = blockIdx.x;
     {
@@ -336,23 +374,10 @@ __device__ __forceinline__ void gemm32_body(const GemmBatch& G) {
         const int xcd = bid & 7, slot = bid >> 3;
         bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + slot;
     }
-    int pi = 0;
-    const GemmProb P = select_problem(G, TB, bid, &pi);
+    const GemmProb P = select_problem(G, TB, bid);
     const int stopv = stop_load(P);
-    int tile = bid - P.tile_base;
-    int sp = 0;
-    KRange R;
-    R.A = P.A; R.B = P.B; R.a_bytes = P.a_bytes; R.b_bytes = P.b_bytes; R.K = P.K;
-    if (P.splits > 1) {
-        sp = tile % P.splits;
-        tile /= P.splits;
-        const int k0 = sp * P.k_chunk;
-        R.K = min(P.k_chunk, P.K - k0);
-        R.A = P.A + (P.a_kc ? (size_t)k0 : (size_t)k0 * P.lda);
-        R.B = P.B + (P.b_kc ? (size_t)k0 : (size_t)k0 * P.ldb);
-        R.a_bytes = 4u * (P.a_kc ? (unsigned)(P.M - 1) * P.lda + R.K : (unsigned)(R.K - 1) * P.lda + P.M);
-        R.b_bytes = 4u * (P.b_kc ? (unsigned)(P.N - 1) * P.ldb + R.K : (unsigned)(R.K - 1) * P.ldb + P.N);
-    }
+    int tile = bid - P.tile_base, sp;
+    const KRange R = k_range(P, tile, sp);
     const int tm = tile / P.tiles_n, tn = tile - tm * P.tiles_n;
     const int m0 = tm * 32, n0 = tn * 32;
 
@@ -389,17 +414,7 @@ __device__ __forceinline__ void gemm32_body(const GemmBatch& G) {
     float asum = 0.f;
 
     if (ALL_VEC) mainloop_co(P, R, m0, n0, lane, wv, stage, acc, asum);
-    else switch (P.a_mode * 3 + P.b_mode) {   // workgroup-uniform
-        case 0: mainloop<0, 0>(P, R, m0, n0, i, kh, wv, acc, asum); break;
-        case 1: mainloop<0, 1>(P, R, m0, n0, i, kh, wv, acc, asum); break;
-        case 2: mainloop<0, 2>(P, R, m0, n0, i, kh, wv, acc, asum); break;
-        case 3: mainloop<1, 0>(P, R, m0, n0, i, kh, wv, acc, asum); break;
-        case 4: mainloop<1, 1>(P, R, m0, n0, i, kh, wv, acc, asum); break;
-        case 5: mainloop<1, 2>(P, R, m0, n0, i, kh, wv, acc, asum); break;
-        case 6: mainloop<2, 0>(P, R, m0, n0, i, kh, wv, acc, asum); break;
-        case 7: mainloop<2, 1>(P, R, m0, n0, i, kh, wv, acc, asum); break;
-        default: mainloop<2, 2>(P, R, m0, n0, i, kh, wv, acc, asum); break;
-    }
+    else mainloop_modes<4>(P, R, m0, n0, i, kh, wv, acc, asum);
 
     if (stop_taken(stopv)) return;
     // ---- combine the 4 K-partials through LDS (fixed order => deterministic) -------------
@@ -464,23 +479,13 @@ __global__ __launch_bounds__(256, 2) void gemm_rows_kernel(GemmBatch G) {
     const int i = lane & 31, kh = lane >> 5;
     const int m0 = (tm * 4 + wv) * 32, n0 = tn * 32;
     if (m0 >= P.M) return;
-    KRange R;
+    KRange R;                                                  // (never split: plan_batch)
     R.A = P.A; R.B = P.B; R.a_bytes = P.a_bytes; R.b_bytes = P.b_bytes; R.K = P.K;
     f32x16 acc;
 #pragma unroll
     for (int s = 0; s < 16; ++s) acc[s] = 0.f;
     float asum = 0.f;
-    switch (P.a_mode * 3 + P.b_mode) {
-        case 0: mainloop<0, 0, 1>(P, R, m0, n0, i, kh, 0, acc, asum); break;
-        case 1: mainloop<0, 1, 1>(P, R, m0, n0, i, kh, 0, acc, asum); break;
-        case 2: mainloop<0, 2, 1>(P, R, m0, n0, i, kh, 0, acc, asum); break;
-        case 3: mainloop<1, 0, 1>(P, R, m0, n0, i, kh, 0, acc, asum); break;
-        case 4: mainloop<1, 1, 1>(P, R, m0, n0, i, kh, 0, acc, asum); break;
-        case 5: mainloop<1, 2, 1>(P, R, m0, n0, i, kh, 0, acc, asum); break;
-        case 6: mainloop<2, 0, 1>(P, R, m0, n0, i, kh, 0, acc, asum); break;
-        case 7: mainloop<2, 1, 1>(P, R, m0, n0, i, kh, 0, acc, asum); break;
-        default: mainloop<2, 2, 1>(P, R, m0, n0, i, kh, 0, acc, asum); break;
-    }
+    mainloop_modes<1>(P, R, m0, n0, i, kh, 0, acc, asum);
     if (stop_taken(stopv)) return;
     // C fragment: lane holds column n0 + i, reg s holds row (s&3) + 8(s>>2) + 4kh -> each store
     // instruction writes two rows of 32 consecutive floats
@@ -571,22 +576,8 @@ __global__ __launch_bounds__(256, 2) void gemm_tile_kernel(GemmBatch G) {
     const int bid = xcd * per + (xcd < rem ? xcd : rem) + idx;
     const GemmProb P = select_problem(G, TB, bid);
     const int stopv = stop_load(P);
-    int tile = bid - P.tile_base;
-    // split-K (weight gradients over 10^4 - 10^5 rows): `splits` workgroups share an output tile, each sums its own K
-    // chunk into its own slice of C (and of dbias), as in gemm32_kernel
-    int sp = 0;
-    KRange R;
-    R.A = P.A; R.B = P.B; R.a_bytes = P.a_bytes; R.b_bytes = P.b_bytes; R.K = P.K;
-    if (P.splits > 1) {
-        sp = tile % P.splits;
-        tile /= P.splits;
-        const int k0 = sp * P.k_chunk;
-        R.K = min(P.k_chunk, P.K - k0);
-        R.A = P.A + (P.a_kc ? (size_t)k0 : (size_t)k0 * P.lda);
-        R.B = P.B + (P.b_kc ? (size_t)k0 : (size_t)k0 * P.ldb);
-        R.a_bytes = 4u * (P.a_kc ? (unsigned)(P.M - 1) * P.lda + R.K : (unsigned)(R.K - 1) * P.lda + P.M);
-        R.b_bytes = 4u * (P.b_kc ? (unsigned)(P.N - 1) * P.ldb + R.K : (unsigned)(R.K - 1) * P.ldb + P.N);
-    }
+    int tile = bid - P.tile_base, sp;
+    const KRange R = k_range(P, tile, sp);
     const int tm = tile / P.tiles_n, tn = tile - tm * P.tiles_n;
     const int tid = threadIdx.x, lane = tid & 63;
     const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -694,21 +685,62 @@ inline unsigned long long operand_bytes(int ld, int kc, int nrows, int K) {
               : 4ull * ((unsigned long long)(K - 1) * ld + nrows);
 }
 
-inline void fill_prob(GemmProb& P, const float* A, int lda, int a_kc, const float* B, int ldb,
-                      int b_kc, const float* bias, const float* mask, float* C, int ldc, int M,
-                      int N, int K, int act, float* dbias, float* sumsq, int tile_base,
-                      const int* stop = nullptr, float* CT = nullptr, int ldct = 0) {
-    P.A = A; P.B = B; P.bias = bias; P.mask = mask; P.C = C; P.dbias = dbias; P.sumsq = sumsq;
-    P.CT = CT; P.ldct = ldct;
-    P.stop = stop;
+// C[M, N] = A . B^T over K, plain: the geometry alone.  Callers set what else they need by name: bias, mask, act, dbias,
+// sumsq, stop, CT / ldct, and the split with split_prob().
+inline GemmProb gemm_prob(const float* A, int lda, int a_kc, const float* B, int ldb, int b_kc, float* C, int ldc, int M,
+                          int N, int K) {
+    GemmProb P;
+    memset(&P, 0, sizeof(P));
+    P.A = A; P.B = B; P.C = C;
     P.lda = lda; P.ldb = ldb; P.ldc = ldc; P.M = M; P.N = N; P.K = K;
-    P.a_kc = a_kc; P.b_kc = b_kc; P.act = act;
-    P.tiles_m = (M + 31) / 32; P.tiles_n = (N + 31) / 32; P.tile_base = tile_base;
-    P.splits = 1; P.k_chunk = K; P.c_split = 0;
+    P.a_kc = a_kc; P.b_kc = b_kc; P.act = SMX_ACT_NONE;
+    P.splits = 1; P.k_chunk = K;
     P.a_mode = !a_kc ? 2 : ((lda % 4 == 0 && K % 4 == 0 && ((uintptr_t)A & 15) == 0) ? 0 : 1);
     P.b_mode = !b_kc ? 2 : ((ldb % 4 == 0 && K % 4 == 0 && ((uintptr_t)B & 15) == 0) ? 0 : 1);
     P.a_bytes = (unsigned)operand_bytes(lda, a_kc, M, K);
     P.b_bytes = (unsigned)operand_bytes(ldb, b_kc, N, K);
+    return P;
+}
+
+// a weight gradient dW[M, N] = dZ^T . X with db = column sums of dZ (the arguments of smx_linear_wgrad_f32): both
+// operands K-strided, K = rows
+inline GemmProb wgrad_prob(const float* dZ, int ldz, const float* X, int ldx, float* dW, int ldw, float* db, int M, int N,
+                           int rows) {
+    GemmProb P = gemm_prob(dZ, ldz, 0, X, ldx, 0, dW, ldw, M, N, rows);
+    P.dbias = db;
+    return P;
+}
+
+inline int tiles32(int M, int N) { return ((M + 31) / 32) * ((N + 31) / 32); }
+
+// The one split-K rule: `rows` cut into S chunks of a multiple of 32 rows, then chunks dropped until the last one is
+// non-empty -> the chunk length and the chunks left.
+struct SplitK {
+    int k_chunk, splits;
+};
+inline SplitK split_k(int rows, int S) {
+    SplitK s;
+    s.k_chunk = ((rows + S - 1) / S + 31) & ~31;
+    s.splits = S;
+    while ((long)(s.splits - 1) * s.k_chunk >= rows) --s.splits;
+    return s;
+}
+// ... on a problem whose C is the [splits][M][N] partials and whose dbias the [splits][M] partial sums
+inline void split_prob(GemmProb& P, const SplitK& s) {
+    P.splits = s.splits;
+    P.k_chunk = s.k_chunk;
+    P.c_split = (long)P.M * P.N;
+}
+// ... and on a problem of smx_wgrad.hip (a column group of dW when b_col0 > 0: Cpart and B point at its first column)
+inline WgradProb wgrad_rows_prob(const float* dZ, int ldz, const float* X, int ldx, float* Cpart, float* bpart, int M,
+                                 int N, int ldc, int b_col0, int rows, const SplitK& s) {
+    WgradProb P;
+    memset(&P, 0, sizeof(P));
+    P.A = dZ; P.B = X; P.Cpart = Cpart; P.bpart = bpart;
+    P.M = M; P.N = N; P.lda = ldz; P.ldb = ldx; P.rows = rows;
+    P.ldc = ldc; P.c_split = (long)M * ldc; P.b_col0 = b_col0;
+    P.splits = s.splits; P.k_chunk = s.k_chunk;
+    return P;
 }
 
 // every operand must fit a 31-bit byte offset (buffer descriptor addressing)
@@ -718,145 +750,129 @@ inline bool prob_ok(const GemmProb& P) {
            operand_bytes(P.ldb, P.b_kc, P.N, Kc) < (1ull << 31);
 }
 
+// ---------------------------------------------------------------------------
+// The planner: which kernel takes a batch, and how its tiles are numbered.  tests/dense_cases.py::launch_batch states
+// the same rule in Python; scripts/check_gemm_plan.py compares the two case by case on the host.
+// ---------------------------------------------------------------------------
+enum GemmKernel { GEMM_TILE, GEMM_ROWS, GEMM32_CO, GEMM32 };
+
+struct GemmPlan {
+    GemmKernel kernel;
+    int am, bm;          // GEMM_TILE: the instantiation's operand storage
+    int grid;            // workgroups (plan_batch)
+};
+
+// the tile kernel's storage of an operand: 0 K-contiguous (mode 0: fully aligned), 2 K-strided with ld % 4 == 0 and an
+// aligned base, -1 neither
+inline int tile_mode_of(const float* X, int ld, int kc, int mode) {
+    if (kc) return mode == 0 ? 0 : -1;
+    return (ld % 4 == 0 && ((uintptr_t)X & 15) == 0) ? 2 : -1;
+}
+
 // gemm_tile_kernel: eligible when every problem of the batch has the same operand storage out of {K-contiguous aligned,
-// K-strided with ld % 4 == 0 and an aligned base}, N >= 64 and K >= 32.
-template <int AM, int BM, int TM, int TN>
-inline int launch_tile_variant(GemmBatch& G, hipStream_t st) {
-    int base = 0;
-    for (int k = 0; k < G.n; ++k) {
-        G.p[k].tiles_m = (G.p[k].M + 64 * TM - 1) / (64 * TM);
-        G.p[k].tiles_n = (G.p[k].N + 64 * TN - 1) / (64 * TN);
-        G.p[k].tile_base = base;
-        base += G.p[k].tiles_m * G.p[k].tiles_n * G.p[k].splits;
-    }
-    const size_t lds = 2 * sizeof(float) * (size_t)(TileStage<AM, 64 * TM>::LDS_FLOATS + TileStage<BM, 64 * TN>::LDS_FLOATS);
-    auto kern = gemm_tile_kernel<AM, BM, TM, TN>;
-    static bool attr_done = false;                        // per instantiation
-    if (!attr_done) {
-        const hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return (int)e;
-        attr_done = true;
-    }
-    hipLaunchKernelGGL(kern, dim3(base), dim3(256), lds, st, G);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? SMX_OK : (int)e;
-}
-
-// Tile shape: 64 x 64 (TM = TN = 1, 32 x 32 per wavefront).  Measured on the stems' shapes (scripts/bench_gemm_tile.py):
-// 7168 x 256 x 2592: 85 TFLOP/s against 81 (128 x 64) and 48 (128 x 128); 7168 x 2592 x 256: 75 / 54 / 52; 131072 x 300 x
-// 100: 57 / 48 / 42 -- with one K block of look-ahead the bigger tiles' 2 - 3 workgroups per CU cannot cover a workgroup's
-// load -> LDS -> barrier bubble, the small tile's 6 - 7 can.  (gemm_rows_kernel on the same three: 59 / 47 / 35.)
-template <int AM, int BM>
-inline int launch_tile_modes(GemmBatch& G, hipStream_t st) {
-    return launch_tile_variant<AM, BM, 1, 1>(G, st);
-}
-
-inline bool tile_mode_of(const float* X, int ld, int kc, int mode, int& out) {
-    if (kc) { out = 0; return mode == 0; }
-    out = 2;
-    return ld % 4 == 0 && ((uintptr_t)X & 15) == 0;
-}
-
-// -> true when the batch was taken (rc = the launch's result)
-inline bool launch_tiles(GemmBatch& G, hipStream_t st, int& rc) {
+// K-strided with ld % 4 == 0 and an aligned base}, N >= 64 and K >= 32 (and no sum-of-squares output).
+inline bool tiles_take(const GemmBatch& G, int& am, int& bm) {
     // the library's one environment read: tests/test_gpu_kernels.py::test_linear_tile_kernel_* runs the same problems on
     // gemm_rows_kernel in a child process to pin the two kernels to the same bits
     static const bool off = getenv("SMX_GEMM_ROWS_ONLY") != nullptr;
     if (off) return false;
-    int am = -1, bm = -1;
     for (int k = 0; k < G.n; ++k) {
         const GemmProb& P = G.p[k];
-        int a, b;
-        if (!tile_mode_of(P.A, P.lda, P.a_kc, P.a_mode, a) || !tile_mode_of(P.B, P.ldb, P.b_kc, P.b_mode, b)) return false;
+        const int a = tile_mode_of(P.A, P.lda, P.a_kc, P.a_mode), b = tile_mode_of(P.B, P.ldb, P.b_kc, P.b_mode);
+        if (a < 0 || b < 0) return false;
         if (P.N < 64 || (P.splits > 1 ? P.k_chunk : P.K) < 32 || P.sumsq) return false;
         if (k && (a != am || b != bm)) return false;
         am = a; bm = b;
     }
-    if (am == 0 && bm == 0) rc = launch_tile_modes<0, 0>(G, st);
-    else if (am == 0 && bm == 2) rc = launch_tile_modes<0, 2>(G, st);
-    else if (am == 2 && bm == 0) rc = launch_tile_modes<2, 0>(G, st);
-    else rc = launch_tile_modes<2, 2>(G, st);
     return true;
 }
 
-// would launch_batch() hand this weight-gradient batch to the 64 x 64 tile kernel (below: `wide && wgs >= 512` and the
-// tile kernel's operand rules)?  Callers that MERGE batches ask first: a merge must not move a problem to another kernel
-// (another summation order).
-inline bool wgrad_batch_takes_tiles(const GemmBatch& G) {
-    static const bool off = getenv("SMX_GEMM_ROWS_ONLY") != nullptr;     // (as in launch_tiles)
-    if (off) return false;
-    bool wide = true;
-    long wgs = 0;
-    int am = -1, bm = -1;
+inline GemmPlan choose_kernel(const GemmBatch& G) {
+    bool rows_variant = true, wide = true, all_vec = true;
+    long wgs = 0;                                         // 64 x 64 tiles
     for (int k = 0; k < G.n; ++k) {
         const GemmProb& P = G.p[k];
+        // many rows and a plain epilogue (M >= 2048: the stem passes over B*T or frames*pixels rows)
+        rows_variant = rows_variant && P.M >= 2048 && !P.dbias && !P.sumsq && P.splits == 1;
+        // weight gradients over many rows (M x N = the weight's shape, K = rows >= 2048, split or not): 64 x 64 tiles read
+        // each operand word for 64 outputs instead of 32 -- at 10^5 rows the 32 x 32 kernel is bound by L2 -> CU traffic
         wide = wide && P.K >= 2048 && P.M >= 48 && !P.sumsq;
         wgs += (long)((P.M + 63) / 64) * ((P.N + 63) / 64) * P.splits;
-        int a, b;
-        if (!tile_mode_of(P.A, P.lda, P.a_kc, P.a_mode, a) || !tile_mode_of(P.B, P.ldb, P.b_kc, P.b_mode, b)) return false;
-        if (P.N < 64 || (P.splits > 1 ? P.k_chunk : P.K) < 32 || P.sumsq) return false;
-        if (k && (a != am || b != bm)) return false;
-        am = a; bm = b;
+        all_vec = all_vec && P.a_mode == 0 && P.b_mode == 0;
     }
-    return wide && wgs >= 512;
+    GemmPlan p = {GEMM32, 0, 0, 0};
+    // `wgs >= 512`: the wide batches go to the tile kernel when there are enough workgroups: one alone on its CU runs a K
+    // block in 2400 cycles (1090 of MFMA issue); below ~2 workgroups per CU the 32 x 32 kernel's four-way K split inside
+    // the workgroup is faster (measured: 7936 rows, dW_hh 98 workgroups 36 us against 20 us; 127 k rows, 896: 0.19 against
+    // 0.38 ms)
+    if ((rows_variant || (wide && wgs >= 512)) && tiles_take(G, p.am, p.bm)) p.kernel = GEMM_TILE;
+    else if (rows_variant) p.kernel = GEMM_ROWS;
+    else p.kernel = all_vec ? GEMM32_CO : GEMM32;
+    return p;
 }
-// problems of `src` appended to `dst` (tile bases renumbered)
-inline void batch_append(GemmBatch& dst, const GemmBatch& src) {
-    int base = 0;
-    if (dst.n) {
-        const GemmProb& L = dst.p[dst.n - 1];
-        base = L.tile_base + L.tiles_m * L.tiles_n * L.splits;
+
+// would launch_batch() hand this weight-gradient batch to the 64 x 64 tile kernel?  Callers that MERGE batches ask first:
+// a merge must not move a problem to another kernel (another summation order).
+inline bool wgrad_batch_takes_tiles(const GemmBatch& G) { return choose_kernel(G).kernel == GEMM_TILE; }
+
+// validate, choose, and number the tiles in the chosen kernel's tile shape -> SMX_OK and the plan
+inline int plan_batch(GemmBatch& G, GemmPlan& plan) {
+    for (int k = 0; k < G.n; ++k)
+        if (!prob_ok(G.p[k])) return SMX_E_SHAPE;
+    plan = choose_kernel(G);
+    // Tile kernel: 64 x 64 (TM = TN = 1, 32 x 32 per wavefront).  Measured on the stems' shapes (scripts/bench_gemm_tile.py):
+    // 7168 x 256 x 2592: 85 TFLOP/s against 81 (128 x 64) and 48 (128 x 128); 7168 x 2592 x 256: 75 / 54 / 52; 131072 x
+    // 300 x 100: 57 / 48 / 42 -- with one K block of look-ahead the bigger tiles' 2 - 3 workgroups per CU cannot cover a
+    // workgroup's load -> LDS -> barrier bubble, the small tile's 6 - 7 can.  (gemm_rows_kernel on the same three:
+    // 59 / 47 / 35.)  Rows kernel: 128 x 32, a 32 x 32 tile per wavefront.
+    const int tm = plan.kernel == GEMM_TILE ? 64 : plan.kernel == GEMM_ROWS ? 128 : 32;
+    const int tn = plan.kernel == GEMM_TILE ? 64 : 32;
+    plan.grid = 0;
+    for (int k = 0; k < G.n; ++k) {
+        GemmProb& P = G.p[k];
+        P.tiles_m = (P.M + tm - 1) / tm;
+        P.tiles_n = (P.N + tn - 1) / tn;
+        P.tile_base = plan.grid;
+        plan.grid += P.tiles_m * P.tiles_n * P.splits;
     }
-    for (int k = 0; k < src.n; ++k) {
-        GemmProb& P = dst.p[dst.n++];
-        P = src.p[k];
-        P.tile_base = base;
-        base += P.tiles_m * P.tiles_n * P.splits;
+    return SMX_OK;
+}
+
+typedef void (*GemmKernelFn)(GemmBatch);
+
+// the tile kernel's instantiation and its dynamic LDS (raised above the default once per instantiation)
+template <int AM, int BM>
+inline int tile_kernel(GemmKernelFn& fn, size_t& lds) {
+    fn = gemm_tile_kernel<AM, BM, 1, 1>;
+    lds = 2 * sizeof(float) * (size_t)(TileStage<AM, 64>::LDS_FLOATS + TileStage<BM, 64>::LDS_FLOATS);
+    static bool attr_done = false;                        // per instantiation
+    if (!attr_done) {
+        const hipError_t e = hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        if (e != hipSuccess) return (int)e;
+        attr_done = true;
     }
+    return SMX_OK;
 }
 
 inline int launch_batch(GemmBatch& G, hipStream_t st) {
-    for (int k = 0; k < G.n; ++k)
-        if (!prob_ok(G.p[k])) return SMX_E_SHAPE;
-    bool rows_variant = true;
-    int rc_tiles = SMX_OK;
-    for (int k = 0; k < G.n; ++k)
-        rows_variant = rows_variant && G.p[k].M >= 2048 && !G.p[k].dbias && !G.p[k].sumsq &&
-                       G.p[k].splits == 1;
-    if (rows_variant && launch_tiles(G, st, rc_tiles)) return rc_tiles;
-    // weight gradients over many rows (M x N = the weight's shape, K = rows >= 2048, split or not): 64 x 64 tiles read
-    // each operand word for 64 outputs instead of 32 -- at 10^5 rows the 32 x 32 kernel is bound by L2 -> CU traffic
-    {
-        bool wide = true;
-        long wgs = 0;
-        for (int k = 0; k < G.n; ++k) {
-            wide = wide && G.p[k].K >= 2048 && G.p[k].M >= 48 && !G.p[k].sumsq;
-            wgs += (long)((G.p[k].M + 63) / 64) * ((G.p[k].N + 63) / 64) * G.p[k].splits;
-        }
-        // ... when there are enough of them: a workgroup alone on its CU runs a K block in 2400 cycles (1090 of MFMA
-        // issue); below ~2 workgroups per CU the 32 x 32 kernel's four-way K split inside the workgroup is faster
-        // (measured: 7936 rows, dW_hh 98 workgroups 36 us against 20 us; 127 k rows, 896: 0.19 against 0.38 ms)
-        if (wide && wgs >= 512 && launch_tiles(G, st, rc_tiles)) return rc_tiles;
+    GemmPlan plan;
+    int rc = plan_batch(G, plan);
+    if (rc) return rc;
+    GemmKernelFn fn = nullptr;
+    size_t lds = 0;
+    switch (plan.kernel) {
+        case GEMM_TILE:
+            rc = plan.am == 0 ? (plan.bm == 0 ? tile_kernel<0, 0>(fn, lds) : tile_kernel<0, 2>(fn, lds))
+                              : (plan.bm == 0 ? tile_kernel<2, 0>(fn, lds) : tile_kernel<2, 2>(fn, lds));
+            if (rc) return rc;
+            break;
+        case GEMM_ROWS: fn = gemm_rows_kernel; break;
+        case GEMM32_CO: fn = gemm32_kernel<true>; break;
+        case GEMM32: fn = gemm32_kernel<false>; break;
     }
-    if (rows_variant) {
-        int base = 0;
-        for (int k = 0; k < G.n; ++k) {
-            G.p[k].tiles_m = (G.p[k].M + 127) / 128;        // 128-row workgroup tiles
-            G.p[k].tile_base = base;
-            base += G.p[k].tiles_m * G.p[k].tiles_n;
-        }
-        hipLaunchKernelGGL(gemm_rows_kernel, dim3(base), dim3(256), 0, st, G);
-        hipError_t e = hipGetLastError();
-        return e == hipSuccess ? SMX_OK : (int)e;
-    }
-    const GemmProb& L = G.p[G.n - 1];
-    const int blocks = L.tile_base + L.tiles_m * L.tiles_n * L.splits;
-    bool all_vec = true;
-    for (int k = 0; k < G.n; ++k) all_vec = all_vec && G.p[k].a_mode == 0 && G.p[k].b_mode == 0;
-    if (all_vec) hipLaunchKernelGGL(gemm32_kernel<true>, dim3(blocks), dim3(256), 0, st, G);
-    else hipLaunchKernelGGL(gemm32_kernel<false>, dim3(blocks), dim3(256), 0, st, G);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? SMX_OK : (int)e;
+    hipLaunchKernelGGL(fn, dim3(plan.grid), dim3(256), lds, st, G);
+    SMX_LAUNCH_CHECK();
+    return SMX_OK;
 }
 
 }  // namespace
@@ -878,14 +894,14 @@ extern "C" int smx_linear_f32(const float* A, int32_t lda, int32_t a_kcontig, co
     SMX_REQUIRE(parts <= MAX_PROBS, SMX_E_UNSUPPORTED);
     const int rows_per = parts == 1 ? M : ((((M + parts - 1) / parts) + 127) & ~127);
     G.n = 0;
-    int base = 0;
     for (int m_off = 0; m_off < M; m_off += rows_per) {
         const int Mp = M - m_off < rows_per ? M - m_off : rows_per;
         GemmProb& P = G.p[G.n++];
-        fill_prob(P, A + (size_t)m_off * lda, lda, a_kcontig, B, ldb, b_kcontig, bias,
-                  relu_mask ? relu_mask + (size_t)m_off * ldc : nullptr, C + (size_t)m_off * ldc, ldc, Mp,
-                  N, K, act, nullptr, nullptr, base, stop_flag);
-        base += P.tiles_m * P.tiles_n;
+        P = gemm_prob(A + (size_t)m_off * lda, lda, a_kcontig, B, ldb, b_kcontig, C + (size_t)m_off * ldc, ldc, Mp, N, K);
+        P.bias = bias;
+        P.mask = relu_mask ? relu_mask + (size_t)m_off * ldc : nullptr;
+        P.act = act;
+        P.stop = stop_flag;
     }
     return launch_batch(G, smx_s(stream));
 }
@@ -899,21 +915,22 @@ extern "C" int smx_linear_multi_f32(const smx_linear_job_t* jobs, int32_t njobs,
     SMX_REQUIRE(njobs >= 1 && njobs <= MAX_PROBS, SMX_E_SHAPE);
     GemmBatch G;
     G.n = njobs;
-    int base = 0;
     for (int k = 0; k < njobs; ++k) {
         const smx_linear_job_t& j = jobs[k];
+        GemmProb& P = G.p[k];
         SMX_REQUIRE(j.A && j.B && j.C, SMX_E_NULL);
         SMX_REQUIRE(j.M > 0 && j.N > 0 && j.K > 0 && j.lda > 0 && j.ldb > 0 && j.ldc >= j.N, SMX_E_SHAPE);
         if (j.kind == 1) {
             SMX_REQUIRE(j.lda >= j.M && j.ldb >= j.N, SMX_E_SHAPE);
-            fill_prob(G.p[k], j.A, j.lda, 0, j.B, j.ldb, 0, nullptr, nullptr, j.C, j.ldc, j.M, j.N, j.K, SMX_ACT_NONE,
-                      j.dbias, nullptr, base, j.stop_flag);
+            P = wgrad_prob(j.A, j.lda, j.B, j.ldb, j.C, j.ldc, j.dbias, j.M, j.N, j.K);
         } else {
             SMX_REQUIRE(j.kind == 0, SMX_E_UNSUPPORTED);
-            fill_prob(G.p[k], j.A, j.lda, j.a_kcontig, j.B, j.ldb, j.b_kcontig, j.bias, j.relu_mask, j.C, j.ldc, j.M, j.N,
-                      j.K, j.act, nullptr, nullptr, base, j.stop_flag);
+            P = gemm_prob(j.A, j.lda, j.a_kcontig, j.B, j.ldb, j.b_kcontig, j.C, j.ldc, j.M, j.N, j.K);
+            P.bias = j.bias;
+            P.mask = j.relu_mask;
+            P.act = j.act;
         }
-        base += G.p[k].tiles_m * G.p[k].tiles_n;
+        P.stop = j.stop_flag;
     }
     return launch_batch(G, smx_s(stream));
 }
@@ -926,8 +943,7 @@ extern "C" int smx_linear_wgrad_f32(const float* dZ, int32_t ldz, const float* X
     SMX_REQUIRE(M > 0 && N > 0 && rows > 0 && ldz >= M && ldx >= N && ldw >= N, SMX_E_SHAPE);
     GemmBatch G;
     G.n = 1;
-    fill_prob(G.p[0], dZ, ldz, 0, X, ldx, 0, nullptr, nullptr, dW, ldw, M, N, rows, SMX_ACT_NONE, db,
-              nullptr, 0);
+    G.p[0] = wgrad_prob(dZ, ldz, X, ldx, dW, ldw, db, M, N, rows);
     return launch_batch(G, smx_s(stream));
 }
 
@@ -1032,14 +1048,14 @@ inline int splitk_reduce_launch(float* part, float* dbpart, int splits, int M, i
         L.total = db ? (int)total : M * N;
         hipLaunchKernelGGL(segmented_reduce_kernel, dim3((unsigned)((L.total + 15) / 16)), dim3(256), 0, st, L, splits,
                            (const int*)nullptr);
-        hipError_t e = hipGetLastError();
-        return e == hipSuccess ? SMX_OK : (int)e;
+        SMX_LAUNCH_CHECK();
+        return SMX_OK;
     }
     long blocks = (total + 255) / 256;
     if (blocks > 1024) blocks = 1024;
     hipLaunchKernelGGL(splitk_reduce_kernel, dim3((unsigned)blocks), dim3(256), 0, st, part, dbpart, splits, M, N, dW, ldw, db);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? SMX_OK : (int)e;
+    SMX_LAUNCH_CHECK();
+    return SMX_OK;
 }
 
 }  // namespace
@@ -1058,17 +1074,9 @@ extern "C" int smx_linear_wgrad_splitk_f32(const float* dZ, int32_t ldz, const f
     const int S = pick_splits(M, N, rows);
     if (S <= 1 || !ws || ws_floats < (int64_t)S * ((int64_t)M * N + M))
         return smx_linear_wgrad_f32(dZ, ldz, X, ldx, dW, ldw, db, M, N, rows, stream);
-    GemmBatch G;
-    G.n = 1;
     float* part = ws;
-    float* dbpart = ws + (size_t)S * M * N;
-    fill_prob(G.p[0], dZ, ldz, 0, X, ldx, 0, nullptr, nullptr, part, N, M, N, rows, SMX_ACT_NONE,
-              dbpart, nullptr, 0);
-    G.p[0].splits = S;
-    G.p[0].k_chunk = ((rows + S - 1) / S + 31) & ~31;
-    G.p[0].c_split = (long)M * N;
-    // every chunk must be non-empty
-    while ((long)(G.p[0].splits - 1) * G.p[0].k_chunk >= rows) --G.p[0].splits;
+    float* dbpart = ws + (size_t)S * M * N;               // laid out by the S asked for; `sk.splits` chunks are written
+    const SplitK sk = split_k(rows, S);
     if (smx_wgrad_rows_eligible(dZ, ldz, X, ldx, M, N, rows)) {
         // the whole dW in one workgroup's registers, every operand row read once (smx_wgrad.hip)
         // (a dW wider than one workgroup's registers -- the LSTM's dW_ih at 376 inputs: 400 x 376 -- goes as column groups,
@@ -1078,20 +1086,21 @@ extern "C" int smx_linear_wgrad_splitk_f32(const float* dZ, int32_t ldz, const f
         Gd.n = smx_wgrad_rows_groups(M, N, &gw);
         Gd.stop = nullptr;
         for (int gi = 0; gi < Gd.n; ++gi) {
-            WgradProb& P = Gd.p[gi];
             const int c0 = gi * gw;
-            P.A = dZ; P.B = X + c0; P.Cpart = part + c0; P.bpart = gi == 0 ? dbpart : nullptr;
-            P.M = M; P.N = (N - c0 < gw) ? N - c0 : gw; P.lda = ldz; P.ldb = ldx; P.rows = rows;
-            P.ldc = N; P.c_split = (long)M * N; P.b_col0 = c0;
-            P.splits = G.p[0].splits; P.k_chunk = G.p[0].k_chunk;
+            Gd.p[gi] = wgrad_rows_prob(dZ, ldz, X + c0, ldx, part + c0, gi == 0 ? dbpart : nullptr, M,
+                                       (N - c0 < gw) ? N - c0 : gw, N, c0, rows, sk);
         }
         const int rc = smx_wgrad_rows_launch(Gd, smx_s(stream));
         if (rc) return rc;
     } else {
+        GemmBatch G;
+        G.n = 1;
+        G.p[0] = wgrad_prob(dZ, ldz, X, ldx, part, N, dbpart, M, N, rows);
+        split_prob(G.p[0], sk);
         const int rc = launch_batch(G, smx_s(stream));
         if (rc) return rc;
     }
-    return splitk_reduce_launch(part, dbpart, G.p[0].splits, M, N, dW, ldw, db, smx_s(stream));
+    return splitk_reduce_launch(part, dbpart, sk.splits, M, N, dW, ldw, db, smx_s(stream));
 }
 
 extern "C" int smx_linear_wgrad_splitk_pair_f32(const float* dZ, int32_t ldz, int32_t M, int32_t rows, const float* X1,
@@ -1110,21 +1119,14 @@ extern "C" int smx_linear_wgrad_splitk_pair_f32(const float* dZ, int32_t ldz, in
     if (pair) {
         const float* X[2] = {X1, X2};
         const int ldx[2] = {ldx1, ldx2}, N[2] = {N1, N2}, S[2] = {S1, S2};
-        G.n = 0;
-        int base = 0;
+        G.n = 2;
         for (int k = 0; k < 2; ++k) {
-            GemmProb& P = G.p[G.n++];
-            fill_prob(P, dZ, ldz, 0, X[k], ldx[k], 0, nullptr, nullptr, part[k], N[k], M, N[k], rows, SMX_ACT_NONE,
-                      part[k] + (size_t)S[k] * M * N[k], nullptr, base);
-            P.splits = S[k];
-            P.k_chunk = ((rows + S[k] - 1) / S[k] + 31) & ~31;
-            P.c_split = (long)M * N[k];
-            while ((long)(P.splits - 1) * P.k_chunk >= rows) --P.splits;      // every chunk non-empty
-            base += P.tiles_m * P.tiles_n * P.splits;
+            G.p[k] = wgrad_prob(dZ, ldz, X[k], ldx[k], part[k], N[k], part[k] + (size_t)S[k] * M * N[k], M, N[k], rows);
+            split_prob(G.p[k], split_k(rows, S[k]));
         }
         G1.n = G2.n = 1;
         G1.p[0] = G.p[0];
-        G2.p[0] = G.p[1]; G2.p[0].tile_base = 0;
+        G2.p[0] = G.p[1];
         // each problem must stay on the kernel it has alone (the 32 x 32 one)
         pair = !wgrad_batch_takes_tiles(G1) && !wgrad_batch_takes_tiles(G2) && !wgrad_batch_takes_tiles(G);
     }
@@ -1163,22 +1165,23 @@ extern "C" int smx_mlp3_forward_multi_f32(const smx_mlp3_job_t* jobs, int32_t nj
     for (int layer = 0; layer < 3; ++layer) {
         GemmBatch G;
         G.n = njobs;
-        int base = 0;
         for (int j = 0; j < njobs; ++j) {
             const smx_mlp3_job_t& J = jobs[j];
             const smx_mlp3_t* n = J.net;
             const int R = (int)J.rows;
-            if (layer == 0)
-                fill_prob(G.p[j], J.x, n->D, 1, n->W1, n->D, 1, n->b1, nullptr, J.h1, n->H1, R, n->H1,
-                          n->D, SMX_ACT_RELU, nullptr, nullptr, base, J.stop_flag, J.h1T, (int)(J.ldT ? J.ldT : R));
-            else if (layer == 1)
-                fill_prob(G.p[j], J.h1, n->H1, 1, n->W2, n->H1, 1, n->b2, nullptr, J.h2, n->H2, R,
-                          n->H2, n->H1, SMX_ACT_RELU, nullptr, nullptr, base, J.stop_flag, J.h2T, (int)(J.ldT ? J.ldT : R));
-            else
-                fill_prob(G.p[j], J.h2, n->H2, 1, n->W3, n->H2, 1, n->b3, nullptr, J.out,
-                          J.out_ld ? J.out_ld : n->OUT, R, n->OUT, n->H2, J.out_act, nullptr, nullptr,
-                          base, J.stop_flag);
-            base += G.p[j].tiles_m * G.p[j].tiles_n;
+            GemmProb& P = G.p[j];
+            if (layer == 0) {
+                P = gemm_prob(J.x, n->D, 1, n->W1, n->D, 1, J.h1, n->H1, R, n->H1, n->D);
+                P.bias = n->b1; P.act = SMX_ACT_RELU; P.CT = J.h1T;
+            } else if (layer == 1) {
+                P = gemm_prob(J.h1, n->H1, 1, n->W2, n->H1, 1, J.h2, n->H2, R, n->H2, n->H1);
+                P.bias = n->b2; P.act = SMX_ACT_RELU; P.CT = J.h2T;
+            } else {
+                P = gemm_prob(J.h2, n->H2, 1, n->W3, n->H2, 1, J.out, J.out_ld ? J.out_ld : n->OUT, R, n->OUT, n->H2);
+                P.bias = n->b3; P.act = J.out_act;
+            }
+            P.ldct = P.CT ? (int)(J.ldT ? J.ldT : R) : 0;
+            P.stop = J.stop_flag;
         }
         const int rc = launch_batch(G, smx_s(stream));
         if (rc) return rc;
@@ -1198,14 +1201,12 @@ extern "C" int smx_mlp3_forward_f32(const smx_mlp3_t* net, const float* x, int64
 }
 
 extern "C" int32_t smx_mlp3_backward_partials(int32_t D, int32_t H1, int32_t H2, int32_t OUT) {
-    auto t = [](int a) { return (a + 31) / 32; };
-    return t(H1) * t(D) + t(H2) * t(H1) + t(OUT) * t(H2);
+    return tiles32(H1, D) + tiles32(H2, H1) + tiles32(OUT, H2);
 }
 
 // dW_l = dz_l^T . input_l , db_l = column sums of dz_l : 3 problems per job, one launch
 static void build_wgrads(GemmBatch& G, const smx_mlp3_job_t* jobs, int32_t njobs) {
     G.n = 3 * njobs;
-    int base = 0;
     for (int j = 0; j < njobs; ++j) {
         const smx_mlp3_job_t& J = jobs[j];
         const smx_mlp3_t* n = J.net;
@@ -1216,8 +1217,7 @@ static void build_wgrads(GemmBatch& G, const smx_mlp3_job_t* jobs, int32_t njobs
         float* gb2 = gW2 + (size_t)H2 * H1;
         float* gW3 = gb2 + H2;
         float* gb3 = gW3 + (size_t)O * H2;
-        float* sq = J.sumsq_partials;
-        const int job_base = base;
+        float* sq = J.sumsq_partials;                   // one per 32 x 32 tile, the job's three layers in a row
         // with the transposed copies ([features, rows], written by the producing GEMMs' epilogues)
         // both operands of dW = dz^T . input are K-contiguous: 16-byte fragment loads, 4 MFMA steps
         // per load, instead of one 4-byte load per operand per step
@@ -1225,15 +1225,16 @@ static void build_wgrads(GemmBatch& G, const smx_mlp3_job_t* jobs, int32_t njobs
         const int LT = (int)(J.ldT ? J.ldT : R);
         const float *a1 = kc ? J.dz1T : J.dz1, *a2 = kc ? J.dz2T : J.dz2, *a3 = kc ? J.dz3T : J.dz3;
         const float *b1 = kc ? J.xT : J.x, *b2 = kc ? J.h1T : J.h1, *b3 = kc ? J.h2T : J.h2;
-        fill_prob(G.p[3 * j + 0], a1, kc ? LT : H1, kc, b1, kc ? LT : D, kc, nullptr, nullptr, gW1, D, H1,
-                  D, R, SMX_ACT_NONE, gb1, sq, base, J.stop_flag);
-        base += G.p[3 * j + 0].tiles_m * G.p[3 * j + 0].tiles_n;
-        fill_prob(G.p[3 * j + 1], a2, kc ? LT : H2, kc, b2, kc ? LT : H1, kc, nullptr, nullptr, gW2, H1,
-                  H2, H1, R, SMX_ACT_NONE, gb2, sq ? sq + (base - job_base) : nullptr, base, J.stop_flag);
-        base += G.p[3 * j + 1].tiles_m * G.p[3 * j + 1].tiles_n;
-        fill_prob(G.p[3 * j + 2], a3, kc ? LT : O, kc, b3, kc ? LT : H2, kc, nullptr, nullptr, gW3, H2, O,
-                  H2, R, SMX_ACT_NONE, gb3, sq ? sq + (base - job_base) : nullptr, base, J.stop_flag);
-        base += G.p[3 * j + 2].tiles_m * G.p[3 * j + 2].tiles_n;
+        GemmProb* P = &G.p[3 * j];
+        P[0] = gemm_prob(a1, kc ? LT : H1, kc, b1, kc ? LT : D, kc, gW1, D, H1, D, R);
+        P[1] = gemm_prob(a2, kc ? LT : H2, kc, b2, kc ? LT : H1, kc, gW2, H1, H2, H1, R);
+        P[2] = gemm_prob(a3, kc ? LT : O, kc, b3, kc ? LT : H2, kc, gW3, H2, O, H2, R);
+        P[0].dbias = gb1; P[1].dbias = gb2; P[2].dbias = gb3;
+        for (int l = 0; l < 3; ++l) {
+            P[l].stop = J.stop_flag;
+            P[l].sumsq = sq;
+            if (sq) sq += tiles32(P[l].M, P[l].N);
+        }
     }
 }
 
@@ -1241,6 +1242,17 @@ static int launch_wgrads(const smx_mlp3_job_t* jobs, int32_t njobs, smx_stream_t
     GemmBatch G;
     build_wgrads(G, jobs, njobs);
     return launch_batch(G, smx_s(stream));
+}
+
+// the data gradients, one problem per stage: 0: dz2 = (dz3 . W3) * relu'(h2)   [R, H2], K = OUT ;
+// 1: dz1 = (dz2 . W2) * relu'(h1)   [R, H1], K = H2
+static GemmProb dgrad_prob(const smx_mlp3_t* n, int stage, const float* dz3, const float* h2, float* dz2, const float* h1,
+                           float* dz1, int R, const int32_t* stop_flag) {
+    GemmProb P = stage == 0 ? gemm_prob(dz3, n->OUT, 1, n->W3, n->H2, 0, dz2, n->H2, R, n->H2, n->OUT)
+                            : gemm_prob(dz2, n->H2, 1, n->W2, n->H1, 0, dz1, n->H1, R, n->H1, n->H2);
+    P.mask = stage == 0 ? h2 : h1;
+    P.stop = stop_flag;
+    return P;
 }
 
 extern "C" int smx_mlp3_backward_multi_f32(const smx_mlp3_job_t* jobs, int32_t njobs,
@@ -1252,22 +1264,14 @@ extern "C" int smx_mlp3_backward_multi_f32(const smx_mlp3_job_t* jobs, int32_t n
         SMX_REQUIRE(J.net && J.x && J.h1 && J.h2 && J.dz3 && J.dz2 && J.dz1 && J.grads, SMX_E_NULL);
         SMX_REQUIRE(J.rows > 0 && J.rows < (1 << 30), SMX_E_SHAPE);
     }
-    // dz2 = (dz3 . W3) * relu'(h2)   [R, H2], K = OUT ;  dz1 = (dz2 . W2) * relu'(h1)   [R, H1], K = H2
     for (int stage = 0; stage < 2; ++stage) {
         GemmBatch G;
         G.n = njobs;
-        int base = 0;
         for (int j = 0; j < njobs; ++j) {
             const smx_mlp3_job_t& J = jobs[j];
-            const smx_mlp3_t* n = J.net;
-            const int R = (int)J.rows;
-            if (stage == 0)
-                fill_prob(G.p[j], J.dz3, n->OUT, 1, n->W3, n->H2, 0, nullptr, J.h2, J.dz2, n->H2, R,
-                          n->H2, n->OUT, SMX_ACT_NONE, nullptr, nullptr, base, J.stop_flag, J.dz2T, (int)(J.ldT ? J.ldT : R));
-            else
-                fill_prob(G.p[j], J.dz2, n->H2, 1, n->W2, n->H1, 0, nullptr, J.h1, J.dz1, n->H1, R,
-                          n->H1, n->H2, SMX_ACT_NONE, nullptr, nullptr, base, J.stop_flag, J.dz1T, (int)(J.ldT ? J.ldT : R));
-            base += G.p[j].tiles_m * G.p[j].tiles_n;
+            G.p[j] = dgrad_prob(J.net, stage, J.dz3, J.h2, J.dz2, J.h1, J.dz1, (int)J.rows, J.stop_flag);
+            G.p[j].CT = stage == 0 ? J.dz2T : J.dz1T;
+            G.p[j].ldct = (int)(J.ldT ? J.ldT : J.rows);
         }
         const int rc = launch_batch(G, smx_s(stream));
         if (rc) return rc;
@@ -1338,11 +1342,11 @@ extern "C" int64_t smx_mlp3_backward_ws_floats(int32_t D, int32_t H1, int32_t H2
 
 // the weight-gradient half of the many-row backward: split-K partials in the workspace + one segmented reduce
 static int mlp3_wgrads_splitk(const smx_mlp3_t* net, const float* x, const float* h1, const float* h2, const float* dz3,
-                              const int R, const float* dz2, const float* dz1, float* grads, float* ws, int S,
+                              const int R, const float* dz2, const float* dz1, float* grads, float* ws, int S_asked,
                               const int32_t* stop_flag, smx_stream_t stream) {
     const int D = net->D, H1 = net->H1, H2 = net->H2, O = net->OUT;
-    int k_chunk = ((R + S - 1) / S + 31) & ~31;
-    while ((long)(S - 1) * k_chunk >= R) --S;                 // every chunk non-empty
+    const SplitK sk = split_k(R, S_asked);
+    const int S = sk.splits;                                  // the workspace is laid out by the chunks LEFT
     const float* dz[3] = {dz1, dz2, dz3};
     const float* in[3] = {x, h1, h2};
     const int Ms[3] = {H1, H2, O}, Ns[3] = {D, H1, H2};
@@ -1358,7 +1362,7 @@ static int mlp3_wgrads_splitk(const smx_mlp3_t* net, const float* x, const float
     Gd.stop = (const int*)stop_flag;
     RedSegs L;
     L.n = 6;
-    int base_w = 0, base_r = 0, ebase = 0;
+    int ebase = 0;
     for (int l = 0; l < 3; ++l) {
         const int M = Ms[l], N = Ns[l];
         float* wpart = wsp;
@@ -1366,22 +1370,14 @@ static int mlp3_wgrads_splitk(const smx_mlp3_t* net, const float* x, const float
         wsp = bpart + (size_t)S * M;
         int gw;
         if (smx_wgrad_rows_eligible(dz[l], M, in[l], N, M, N, R) && smx_wgrad_rows_groups(M, N, &gw) == 1) {
-            WgradProb& P = Gd.p[Gd.n++];
-            P.A = dz[l]; P.B = in[l]; P.Cpart = wpart; P.bpart = bpart;
-            P.M = M; P.N = N; P.lda = M; P.ldb = N; P.rows = R;
-            P.ldc = N; P.c_split = (long)M * N; P.b_col0 = 0;
-            P.splits = S; P.k_chunk = k_chunk;
+            Gd.p[Gd.n++] = wgrad_rows_prob(dz[l], M, in[l], N, wpart, bpart, M, N, N, 0, R, sk);
         } else {
             const bool wide = M >= 48 && N >= 64 && M % 4 == 0 && N % 4 == 0;
             GemmBatch& G = wide ? Gw : Gr;
-            int& base = wide ? base_w : base_r;
             GemmProb& P = G.p[G.n++];
-            fill_prob(P, dz[l], M, 0, in[l], N, 0, nullptr, nullptr, wpart, N, M, N, R, SMX_ACT_NONE, bpart, nullptr, base,
-                      stop_flag);
-            P.splits = S;
-            P.k_chunk = k_chunk;
-            P.c_split = (long)M * N;
-            base += P.tiles_m * P.tiles_n * S;
+            P = wgrad_prob(dz[l], M, in[l], N, wpart, N, bpart, M, N, R);
+            P.stop = stop_flag;
+            split_prob(P, sk);
         }
         L.g[2 * l] = RedSeg{wpart, gdst, ebase, M * N};
         ebase += M * N;
@@ -1398,7 +1394,7 @@ static int mlp3_wgrads_splitk(const smx_mlp3_t* net, const float* x, const float
     // both on the 32 x 32 kernel (the wide layers' batch below the tile kernel's break-even: B*E ~ 10^4 rows): ONE launch --
     // the output layer's 12 us launch ran behind the hidden layers' instead of beside them
     if (Gw.n && Gr.n && Gw.n + Gr.n <= MAX_PROBS && !wgrad_batch_takes_tiles(Gw)) {
-        batch_append(Gw, Gr);
+        for (int k = 0; k < Gr.n; ++k) Gw.p[Gw.n++] = Gr.p[k];
         Gr.n = 0;
     }
     for (GemmBatch* G : {&Gw, &Gr}) {
@@ -1421,17 +1417,11 @@ extern "C" int smx_mlp3_backward_splitk_f32(const smx_mlp3_t* net, const float* 
     int S = mlp3_splits(net, rows);
     if (S <= 1 || !ws || ws_floats < (int64_t)S * mlp3_numel(net))
         return smx_mlp3_backward_f32(net, x, h1, h2, dz3, rows, dz2, dz1, grads, nullptr, stop_flag, stream);
-    const int R = (int)rows, H1 = net->H1, H2 = net->H2, O = net->OUT;
-    // dz2 = (dz3 . W3) * relu'(h2), dz1 = (dz2 . W2) * relu'(h1): as smx_mlp3_backward_multi_f32
+    const int R = (int)rows;
     for (int stage = 0; stage < 2; ++stage) {
         GemmBatch G;
         G.n = 1;
-        if (stage == 0)
-            fill_prob(G.p[0], dz3, O, 1, net->W3, H2, 0, nullptr, h2, dz2, H2, R, H2, O, SMX_ACT_NONE, nullptr, nullptr, 0,
-                      stop_flag);
-        else
-            fill_prob(G.p[0], dz2, H2, 1, net->W2, H1, 0, nullptr, h1, dz1, H1, R, H1, H2, SMX_ACT_NONE, nullptr, nullptr,
-                      0, stop_flag);
+        G.p[0] = dgrad_prob(net, stage, dz3, h2, dz2, h1, dz1, R, stop_flag);
         const int rc = launch_batch(G, smx_s(stream));
         if (rc) return rc;
     }

@@ -14,9 +14,10 @@ extent + pad, a few floats behind, everything outside the logical extent NaN (op
 of the sentinel -7777 whose logical [M, N] region is pre-filled with NaN: after the call the logical region must equal the
 reference (an unwritten tile shows as NaN) and every other element must still be the sentinel.
 
-Dispatch.  expected_path() / launch_batch() / wgrad_plan() restate fill_prob, tile_mode_of, launch_tiles, launch_batch and
-pick_splits.  The kernel choice is confirmed by a kernel trace (profiles/dense_paths_kernel_stats.csv); the operand-mode
-pair inside gemm32_kernel<false> and gemm_rows_kernel rests on the restated fill_prob rule.
+Dispatch.  expected_path() / launch_batch() / wgrad_plan() restate gemm_prob, tile_mode_of, tiles_take, choose_kernel /
+plan_batch, split_k and pick_splits.  The kernel choice is confirmed by a kernel trace
+(profiles/dense_paths_kernel_stats.csv); the operand-mode pair inside gemm32_kernel<false> and gemm_rows_kernel rests on
+the restated gemm_prob rule.
 """
 import collections
 import zlib
@@ -42,7 +43,7 @@ def ld_of(kc, rows, K, pad):
 
 
 def mode_of(kc, ld, K, off):
-    """fill_prob: 0 K-contiguous and fully aligned, 1 K-contiguous otherwise, 2 K-strided (buffers are 16-byte aligned,
+    """gemm_prob: 0 K-contiguous and fully aligned, 1 K-contiguous otherwise, 2 K-strided (buffers are 16-byte aligned,
     so the base is aligned when `off` is a multiple of 4 floats)"""
     if not kc:
         return 2
@@ -74,7 +75,7 @@ def tile_mode_of(kc, ld, off, mode):
 
 
 def tiles_take(probs):
-    """launch_tiles: every problem tile-eligible with the same storage -> the instantiation's (AM, BM), else None"""
+    """tiles_take: every problem tile-eligible with the same storage -> the instantiation's (AM, BM), else None"""
     first = None
     for p in probs:
         am, bm = prob_modes(p)
