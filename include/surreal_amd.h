@@ -1060,6 +1060,10 @@ int smx_ddpg_rows_wgrad_update_f32(const smx_ddpg_rows_t* args, int32_t group, c
  * front of the actor / critic MLPs; forward at :277-279, :307-309, single step at :338-349).
  * torch.nn.LSTM layouts: W_ih [4H, D], W_hh [4H, H], b_ih [4H], b_hh [4H], gate order i, f, g, o.
  * H must be a multiple of 4 and <= 384; B*T*4H < 2^31.
+ * Alignment: W_hh must be 16-byte aligned (the kernels read its rows four floats at a time; with H % 4 == 0 every row
+ * then is) -- inside a flat [W_ih | W_hh | b_ih | b_hh] vector that is a 16-byte aligned W_ih, since 4 H D is a multiple
+ * of 4 floats.  smx_lstm_forward_f32 refuses anything else (SMX_E_UNSUPPORTED).  W_ih, b_ih, b_hh, x, h0, c0 and every
+ * output need only float alignment.
  * ------------------------------------------------------------------------------------------- */
 typedef struct smx_lstm {
     const float* W_ih;
@@ -1085,7 +1089,9 @@ int smx_lstm_forward_f32(const smx_lstm_t* net, const float* x, int64_t B, int32
  * (h0, c0 are constants: ppo.py:511-515 detaches them).  dgates [B, T, 4H] is workspace (it may
  * alias `gates`).  grads receives dW_ih, dW_hh, db_ih, db_hh (overwritten, not accumulated).
  * ws / ws_floats: optional split-K workspace for the two weight-gradient GEMMs over B*T rows
- * (smx_lstm_backward_ws_floats; NULL = unsplit). */
+ * (smx_lstm_backward_ws_floats; NULL = unsplit).  A non-zero *stop_flag skips the whole call, the weight-gradient
+ * launches included: dgates, grads and ws are left as they are (like smx_lstm_forward_f32 and every other call that
+ * takes the flag). */
 int64_t smx_lstm_backward_ws_floats(int32_t D, int32_t H, int64_t B, int32_t T);
 int smx_lstm_backward_f32(const smx_lstm_t* net, const float* x, int64_t B, int32_t T,
                           const float* c0, const float* gates, const float* cs,

@@ -936,15 +936,22 @@ extern "C" int smx_linear_multi_f32(const smx_linear_job_t* jobs, int32_t njobs,
 }
 
 // dW[M,N] = dZ^T . X (dZ [rows, >=M] stride ldz, X [rows, >=N] stride ldx), db[M] = column sums of dZ
-extern "C" int smx_linear_wgrad_f32(const float* dZ, int32_t ldz, const float* X, int32_t ldx,
-                                    float* dW, int32_t ldw, float* db, int32_t M, int32_t N,
-                                    int32_t rows, smx_stream_t stream) {
+// (`stop`: a device flag, non-zero -> nothing is written; the C entry points below pass none)
+static int linear_wgrad_stop(const float* dZ, int32_t ldz, const float* X, int32_t ldx, float* dW, int32_t ldw, float* db,
+                             int32_t M, int32_t N, int32_t rows, const int32_t* stop, smx_stream_t stream) {
     SMX_REQUIRE(dZ && X && dW, SMX_E_NULL);
     SMX_REQUIRE(M > 0 && N > 0 && rows > 0 && ldz >= M && ldx >= N && ldw >= N, SMX_E_SHAPE);
     GemmBatch G;
     G.n = 1;
     G.p[0] = wgrad_prob(dZ, ldz, X, ldx, dW, ldw, db, M, N, rows);
+    G.p[0].stop = stop;
     return launch_batch(G, smx_s(stream));
+}
+
+extern "C" int smx_linear_wgrad_f32(const float* dZ, int32_t ldz, const float* X, int32_t ldx,
+                                    float* dW, int32_t ldw, float* db, int32_t M, int32_t N,
+                                    int32_t rows, smx_stream_t stream) {
+    return linear_wgrad_stop(dZ, ldz, X, ldx, dW, ldw, db, M, N, rows, nullptr, stream);
 }
 
 // ---------------------------------------------------------------------------
@@ -1003,7 +1010,8 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(const float* __restr
                                                             const float* __restrict__ dbpart,
                                                             int splits, int M, int N,
                                                             float* __restrict__ dW, int ldw,
-                                                            float* __restrict__ db) {
+                                                            float* __restrict__ db, const int* __restrict__ stop) {
+    if (stop && *stop) return;
     const long total = (long)M * N;
     for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total + M; i += (long)gridDim.x * 256) {
         if (i < total) {
@@ -1036,7 +1044,7 @@ inline int pick_splits(int M, int N, int rows) {
 
 // the second launch of a split-K weight gradient: the chunks' partial tiles added in chunk order
 inline int splitk_reduce_launch(float* part, float* dbpart, int splits, int M, int N, float* dW, int ldw, float* db,
-                                hipStream_t st) {
+                                hipStream_t st, const int* stop = nullptr) {
     const long total = (long)M * N + M;
     if (ldw == N && splits > 32) {
         // many chunks: 16 slices of the split index per element in parallel, combined in slice order (one thread per
@@ -1046,14 +1054,14 @@ inline int splitk_reduce_launch(float* part, float* dbpart, int splits, int M, i
         L.g[0] = RedSeg{part, dW, 0, M * N};
         L.g[1] = RedSeg{dbpart, db, M * N, M};
         L.total = db ? (int)total : M * N;
-        hipLaunchKernelGGL(segmented_reduce_kernel, dim3((unsigned)((L.total + 15) / 16)), dim3(256), 0, st, L, splits,
-                           (const int*)nullptr);
+        hipLaunchKernelGGL(segmented_reduce_kernel, dim3((unsigned)((L.total + 15) / 16)), dim3(256), 0, st, L, splits, stop);
         SMX_LAUNCH_CHECK();
         return SMX_OK;
     }
     long blocks = (total + 255) / 256;
     if (blocks > 1024) blocks = 1024;
-    hipLaunchKernelGGL(splitk_reduce_kernel, dim3((unsigned)blocks), dim3(256), 0, st, part, dbpart, splits, M, N, dW, ldw, db);
+    hipLaunchKernelGGL(splitk_reduce_kernel, dim3((unsigned)blocks), dim3(256), 0, st, part, dbpart, splits, M, N, dW, ldw, db,
+                       stop);
     SMX_LAUNCH_CHECK();
     return SMX_OK;
 }
@@ -1065,15 +1073,14 @@ extern "C" int64_t smx_linear_wgrad_ws_floats(int32_t M, int32_t N, int32_t rows
     return s > 1 ? (int64_t)s * ((int64_t)M * N + M) : 0;
 }
 
-extern "C" int smx_linear_wgrad_splitk_f32(const float* dZ, int32_t ldz, const float* X,
-                                           int32_t ldx, float* dW, int32_t ldw, float* db,
-                                           int32_t M, int32_t N, int32_t rows, float* ws,
-                                           int64_t ws_floats, smx_stream_t stream) {
+static int linear_wgrad_splitk_stop(const float* dZ, int32_t ldz, const float* X, int32_t ldx, float* dW, int32_t ldw,
+                                    float* db, int32_t M, int32_t N, int32_t rows, float* ws, int64_t ws_floats,
+                                    const int32_t* stop, smx_stream_t stream) {
     SMX_REQUIRE(dZ && X && dW, SMX_E_NULL);
     SMX_REQUIRE(M > 0 && N > 0 && rows > 0 && ldz >= M && ldx >= N && ldw >= N, SMX_E_SHAPE);
     const int S = pick_splits(M, N, rows);
     if (S <= 1 || !ws || ws_floats < (int64_t)S * ((int64_t)M * N + M))
-        return smx_linear_wgrad_f32(dZ, ldz, X, ldx, dW, ldw, db, M, N, rows, stream);
+        return linear_wgrad_stop(dZ, ldz, X, ldx, dW, ldw, db, M, N, rows, stop, stream);
     float* part = ws;
     float* dbpart = ws + (size_t)S * M * N;               // laid out by the S asked for; `sk.splits` chunks are written
     const SplitK sk = split_k(rows, S);
@@ -1084,7 +1091,7 @@ extern "C" int smx_linear_wgrad_splitk_f32(const float* dZ, int32_t ldz, const f
         WgradBatch Gd;
         int gw = N;
         Gd.n = smx_wgrad_rows_groups(M, N, &gw);
-        Gd.stop = nullptr;
+        Gd.stop = (const int*)stop;
         for (int gi = 0; gi < Gd.n; ++gi) {
             const int c0 = gi * gw;
             Gd.p[gi] = wgrad_rows_prob(dZ, ldz, X + c0, ldx, part + c0, gi == 0 ? dbpart : nullptr, M,
@@ -1096,17 +1103,27 @@ extern "C" int smx_linear_wgrad_splitk_f32(const float* dZ, int32_t ldz, const f
         GemmBatch G;
         G.n = 1;
         G.p[0] = wgrad_prob(dZ, ldz, X, ldx, part, N, dbpart, M, N, rows);
+        G.p[0].stop = stop;
         split_prob(G.p[0], sk);
         const int rc = launch_batch(G, smx_s(stream));
         if (rc) return rc;
     }
-    return splitk_reduce_launch(part, dbpart, sk.splits, M, N, dW, ldw, db, smx_s(stream));
+    return splitk_reduce_launch(part, dbpart, sk.splits, M, N, dW, ldw, db, smx_s(stream), (const int*)stop);
 }
 
-extern "C" int smx_linear_wgrad_splitk_pair_f32(const float* dZ, int32_t ldz, int32_t M, int32_t rows, const float* X1,
-                                                int32_t ldx1, float* dW1, float* db1, int32_t N1, const float* X2,
-                                                int32_t ldx2, float* dW2, float* db2, int32_t N2, float* ws,
-                                                int64_t ws_floats, smx_stream_t stream) {
+extern "C" int smx_linear_wgrad_splitk_f32(const float* dZ, int32_t ldz, const float* X,
+                                           int32_t ldx, float* dW, int32_t ldw, float* db,
+                                           int32_t M, int32_t N, int32_t rows, float* ws,
+                                           int64_t ws_floats, smx_stream_t stream) {
+    return linear_wgrad_splitk_stop(dZ, ldz, X, ldx, dW, ldw, db, M, N, rows, ws, ws_floats, nullptr, stream);
+}
+
+// smx_linear_wgrad_splitk_pair_f32 with a device stop flag on every launch (non-zero -> dW1, db1, dW2, db2 and the workspace
+// are left as they are): what smx_lstm_backward_f32 calls (smx_wgrad.h)
+int smx_linear_wgrad_splitk_pair_stop(const float* dZ, int32_t ldz, int32_t M, int32_t rows, const float* X1, int32_t ldx1,
+                                      float* dW1, float* db1, int32_t N1, const float* X2, int32_t ldx2, float* dW2,
+                                      float* db2, int32_t N2, float* ws, int64_t ws_floats, const int32_t* stop,
+                                      smx_stream_t stream) {
     SMX_REQUIRE(dZ && X1 && dW1 && X2 && dW2, SMX_E_NULL);
     SMX_REQUIRE(M > 0 && N1 > 0 && N2 > 0 && rows > 0 && ldz >= M && ldx1 >= N1 && ldx2 >= N2, SMX_E_SHAPE);
     const int S1 = pick_splits(M, N1, rows), S2 = pick_splits(M, N2, rows);
@@ -1122,6 +1139,7 @@ extern "C" int smx_linear_wgrad_splitk_pair_f32(const float* dZ, int32_t ldz, in
         G.n = 2;
         for (int k = 0; k < 2; ++k) {
             G.p[k] = wgrad_prob(dZ, ldz, X[k], ldx[k], part[k], N[k], part[k] + (size_t)S[k] * M * N[k], M, N[k], rows);
+            G.p[k].stop = stop;
             split_prob(G.p[k], split_k(rows, S[k]));
         }
         G1.n = G2.n = 1;
@@ -1131,15 +1149,25 @@ extern "C" int smx_linear_wgrad_splitk_pair_f32(const float* dZ, int32_t ldz, in
         pair = !wgrad_batch_takes_tiles(G1) && !wgrad_batch_takes_tiles(G2) && !wgrad_batch_takes_tiles(G);
     }
     if (!pair) {
-        const int rc = smx_linear_wgrad_splitk_f32(dZ, ldz, X1, ldx1, dW1, N1, db1, M, N1, rows, ws, ws_floats, stream);
+        const int rc = linear_wgrad_splitk_stop(dZ, ldz, X1, ldx1, dW1, N1, db1, M, N1, rows, ws, ws_floats, stop, stream);
         if (rc) return rc;
-        return smx_linear_wgrad_splitk_f32(dZ, ldz, X2, ldx2, dW2, N2, db2, M, N2, rows, ws, ws_floats, stream);
+        return linear_wgrad_splitk_stop(dZ, ldz, X2, ldx2, dW2, N2, db2, M, N2, rows, ws, ws_floats, stop, stream);
     }
     int rc = launch_batch(G, smx_s(stream));
     if (rc) return rc;
-    rc = splitk_reduce_launch(part[0], part[0] + (size_t)S1 * M * N1, G.p[0].splits, M, N1, dW1, N1, db1, smx_s(stream));
+    rc = splitk_reduce_launch(part[0], part[0] + (size_t)S1 * M * N1, G.p[0].splits, M, N1, dW1, N1, db1, smx_s(stream),
+                              (const int*)stop);
     if (rc) return rc;
-    return splitk_reduce_launch(part[1], part[1] + (size_t)S2 * M * N2, G.p[1].splits, M, N2, dW2, N2, db2, smx_s(stream));
+    return splitk_reduce_launch(part[1], part[1] + (size_t)S2 * M * N2, G.p[1].splits, M, N2, dW2, N2, db2, smx_s(stream),
+                                (const int*)stop);
+}
+
+extern "C" int smx_linear_wgrad_splitk_pair_f32(const float* dZ, int32_t ldz, int32_t M, int32_t rows, const float* X1,
+                                                int32_t ldx1, float* dW1, float* db1, int32_t N1, const float* X2,
+                                                int32_t ldx2, float* dW2, float* db2, int32_t N2, float* ws,
+                                                int64_t ws_floats, smx_stream_t stream) {
+    return smx_linear_wgrad_splitk_pair_stop(dZ, ldz, M, rows, X1, ldx1, dW1, db1, N1, X2, ldx2, dW2, db2, N2, ws, ws_floats,
+                                             nullptr, stream);
 }
 
 // ---------------------------------------------------------------------------

@@ -18,6 +18,7 @@
 // Backward is the mirror image (t = T-1 .. 0, dh_rec = dgates_t . W_hh), followed by the
 // weight-gradient GEMMs over all B*T rows (split-K).
 #include "smx_common.h"
+#include "smx_wgrad.h"
 
 namespace {
 
@@ -980,6 +981,8 @@ extern "C" int smx_lstm_forward_f32(const smx_lstm_t* net, const float* x, int64
     const int H = net->H, D = net->D;
     SMX_REQUIRE(B > 0 && T > 0 && H > 0 && D > 0 && B * T * 4 * H < (1ll << 31), SMX_E_SHAPE);
     SMX_REQUIRE(H % 4 == 0 && H <= 16 * KG_MAX, SMX_E_UNSUPPORTED);
+    // lstm_fwdm_kernel and lstm_fwd_kernel read W_hh rows as float4 (one contract for every family)
+    SMX_REQUIRE(reinterpret_cast<uintptr_t>(net->W_hh) % 16 == 0, SMX_E_UNSUPPORTED);
     const LstmPlan p = lstm_plan(B, D, H);
     if (!p.fold) {
         int rc = smx_linear_f32(x, D, 1, net->W_ih, D, 1, net->b_ih, gates, 4 * H, (int32_t)(B * T),
@@ -1060,9 +1063,10 @@ extern "C" int smx_lstm_backward_f32(const smx_lstm_t* net, const float* x, int6
     float* gbhh = gbih + 4 * H;
     const int32_t rows = (int32_t)(B * T);
     // both gradients read the same dgates: ONE split-K launch where both are on the 32 x 32 kernel (B*T ~ 10^4 rows; the
-    // call falls back to two launches by itself when one of them has a kernel of its own at these shapes)
-    return smx_linear_wgrad_splitk_pair_f32(dgates, 4 * H, 4 * H, rows, x, D, gWih, gbih, D, hprev, H, gWhh, gbhh, H, ws,
-                                            ws_floats, stream);
+    // call falls back to two launches by itself when one of them has a kernel of its own at these shapes).  The stop flag
+    // goes with every one of them: a stopped call leaves grads (and ws) alone, as the recurrence left dgates
+    return smx_linear_wgrad_splitk_pair_stop(dgates, 4 * H, 4 * H, rows, x, D, gWih, gbih, D, hprev, H, gWhh, gbhh, H, ws,
+                                             ws_floats, stop_flag, stream);
 }
 
 extern "C" int64_t smx_lstm_backward_ws_floats(int32_t D, int32_t H, int64_t B, int32_t T) {

@@ -33,3 +33,10 @@ __attribute__((visibility("hidden"))) bool smx_wgrad_rows_plan(int M, int N, int
 // a dW too wide for one workgroup's registers: N cut into `groups` column groups of `width` columns (the last one narrower),
 // each a problem of its own that re-reads dZ; 0 when no cut fits
 __attribute__((visibility("hidden"))) int smx_wgrad_rows_groups(int M, int N, int* width);
+
+// smx_gemm.hip: smx_linear_wgrad_splitk_pair_f32 with a device stop flag on every launch it makes (non-zero -> the four
+// outputs and the workspace are left as they are; null -> the C entry point)
+__attribute__((visibility("hidden"))) int smx_linear_wgrad_splitk_pair_stop(
+    const float* dZ, int32_t ldz, int32_t M, int32_t rows, const float* X1, int32_t ldx1, float* dW1, float* db1, int32_t N1,
+    const float* X2, int32_t ldx2, float* dW2, float* db2, int32_t N2, float* ws, int64_t ws_floats, const int32_t* stop,
+    smx_stream_t stream);
