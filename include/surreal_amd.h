@@ -1559,6 +1559,54 @@ int32_t smx_synth_eval_supported(int32_t ddpg, int32_t task, int32_t D, int32_t 
 int smx_synth_ppo_eval_f32(const struct smx_synth_ppo_eval* args, smx_stream_t stream);
 int smx_synth_ddpg_eval_f32(const struct smx_synth_ddpg_eval* args, smx_stream_t stream);
 
+/* Several parameter sets of one policy architecture -- a learning curve's snapshots, an actor and its target, the
+ * perturbed actors of a parameter-noise population -- evaluated in ONE launch on the same episodes.
+ *
+ * A SNAPSHOT is one policy's parameters as one contiguous blob of smx_eval_snapshot_floats floats (a multiple of 64; every
+ * block on 16 bytes, the padding between and behind the blocks zero), D the observation's width (the LSTM's input width
+ * where H > 0 units stand in front of the actor):
+ *   DDPG (ddpg != 0, H == 0, zfilter == 0):  [smx_epoch_pack_f32's layout of the actor | b1 | b2 | b3] -- by definition
+ *       smx_param_noise_copy_floats(D, H1, H2, A, 0) floats in that order: a plain-actor population is an array of snapshots;
+ *   PPO:  the same four, then log_var [A]; with zfilter != 0 zsum [D] | zsumsq [D] | zcount [1]; with H > 0
+ *       smx_lstm_rollout_pack_f32's layout of the LSTM (its gate biases included).
+ * 0: a shape smx_synth_eval_supported refuses on every task, a DDPG actor with a z-filter, zfilter not 0 | 1. */
+int64_t smx_eval_snapshot_floats(int32_t ddpg, int32_t D, int32_t H, int32_t H1, int32_t H2, int32_t A, int32_t zfilter);
+struct smx_eval_snapshot_src {             /* (by tag: no typedef) what names a policy in the evaluation argument blocks */
+    const smx_mlp3_t* net;                 /* the actor (with lstm: net->D == lstm->H) */
+    const float* log_var;                  /* PPO [A]; not read with ddpg != 0 */
+    const float* zsum;                     /* the z-filter's three, or none */
+    const float* zsumsq;
+    const float* zcount;
+    const smx_lstm_t* lstm;                /* NULL: no LSTM stem */
+    int32_t ddpg, reserved;
+};
+/* blob (16-byte aligned) <- the snapshot of the live parameters behind src: no host synchronisation, at most three
+ * launches (smx_epoch_pack_f32 and smx_lstm_rollout_pack_f32 into the blob, one copy kernel for the small arrays and the
+ * padding).  Writes exactly smx_eval_snapshot_floats floats.  A NULL pointer (the z-filter's three: all or none):
+ * SMX_E_NULL; net->D != lstm->H: SMX_E_SHAPE; a policy whose snapshot has 0 floats: SMX_E_UNSUPPORTED; blob: SMX_E_ALIGN. */
+int smx_eval_snapshot_store_f32(const struct smx_eval_snapshot_src* src, float* blob, smx_stream_t stream);
+
+/* The launches.  args: the shapes (net, lstm, hidden, out_act, zeps), n, episodes, episode_len, task,
+ * actors_per_workgroup, init_state and the streams, as above -- its parameter pointers (packed, log_var, zsum, zsumsq,
+ * zcount, lstm_packed, the arrays behind net and lstm) are NOT read: set s reads its parameters from blobs + s * stride.
+ * args->returns is [sets, n, episodes] fp64.  ONE launch of sets x ceil(n episodes / block) workgroups: every workgroup
+ * belongs to one set, every set has its own tail block; actors_per_workgroup 0 chooses the block from the sets * n *
+ * episodes rows as smx_synth_rollout_f32 does from its rows.  returns[s] has the bits smx_synth_*_eval_f32 leaves for a
+ * policy holding set s's parameters, at every block size: row (a, i) of every set starts, draws and sums alike.
+ * Before any launch: a NULL sets or blobs: SMX_E_NULL; sets < 1, sets > 65535, sets * n * episodes >= 2^31, stride <
+ * smx_eval_snapshot_floats(.., zfilter) or no multiple of 4, zfilter not 0 | 1 (DDPG: not 0): SMX_E_SHAPE; blobs not on
+ * 16 bytes: SMX_E_ALIGN; and what smx_synth_*_eval_f32 refuses, with its codes (the pointers that are not read apart). */
+struct smx_eval_sets {                     /* (by tag: no typedef) */
+    const float* blobs;                    /* [sets, stride] */
+    int64_t stride;                        /* floats from one snapshot to the next */
+    int32_t sets;
+    int32_t zfilter;                       /* != 0: the snapshots hold a z-filter's sums, and the policy filters */
+};
+int smx_synth_ppo_eval_sets_f32(const struct smx_synth_ppo_eval* args, const struct smx_eval_sets* sets,
+                                smx_stream_t stream);
+int smx_synth_ddpg_eval_sets_f32(const struct smx_synth_ddpg_eval* args, const struct smx_eval_sets* sets,
+                                 smx_stream_t stream);
+
 /* Parameter-space noise of the device actors (surreal/agent/param_noise.py): a population of perturbed actors, one per
  * AGENT -- a group of consecutive actors that share one perturbation, as the actors of one reference agent process do
  * (an agent here spans at least the 4 actors of one MFMA row block, where the reference's spans one environment).  The

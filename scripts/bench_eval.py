@@ -13,7 +13,11 @@ configurations, algorithms and variants; one JSON line per (configuration, algor
 `calls` calls, then one line per (configuration, algorithm, variant) with the rounds' medians and their range.
 
     python scripts/bench_eval.py [--rounds 5] [--calls 60] [--configs small,big1,big4] [--algos ppo,ddpg]
-                                 [--variants per_step,rollout,evaluate] [--out FILE]"""
+                                 [--variants per_step,rollout,evaluate] [--out FILE]
+
+--sets K[,K..]: several parameter sets on the same episodes (DeviceEvalSnapshots) -- per (configuration, algorithm, K) the
+host time of `sequential`, K evaluate calls and one copy of the [K, n, E] returns, against `sets`, the one K-set launch and
+one copy; the same rounds, calls and lines (`sets_rounds`), after a line that says the two leave the same bits."""
 import argparse
 import json
 import os
@@ -95,6 +99,69 @@ def workloads(algo, n, E, L, hidden, J):
     return {'per_step': per_step, 'rollout': rollout, 'evaluate': evaluate}
 
 
+def set_workloads(algo, K, n, E, L, hidden, J):
+    """--sets: K parameter sets of one architecture on the same held-out episodes -> {variant: a function that runs one
+    evaluation of all K and returns the [K n E] returns on the host}: `sequential`, K SyntheticVecEnv.evaluate calls into
+    the rows of one tensor and one device -> host copy; `sets`, DeviceEvalSnapshots.evaluate: one launch, one copy"""
+    D, A = 3 * J, J
+    TR.HIDDEN = list(hidden)
+    if algo == 'ppo':
+        from surreal_amd.agent import PPOAgent as Agent
+        cfg = TR.ppo_configs(D, A, n, '/tmp/surreal_amd_bench_eval')
+    else:
+        from surreal_amd.agent import DDPGAgent as Agent
+        cfg = TR.ddpg_configs(D, A, n, '/tmp/surreal_amd_bench_eval')
+    agents = []
+    for k in range(K):
+        torch.manual_seed(SEED + k)
+        agents.append(Agent(*cfg, agent_id=1 + k, agent_mode='eval_deterministic_local'))
+    venv = SyntheticVecEnv(n, D, A, episode_len=L, seeds=list(range(n)), task='reach')
+    out = torch.empty(K, n, E, dtype=torch.float64, device=venv.device)
+    snaps = venv.eval_snapshots(agents[0], K)
+    for k, ag in enumerate(agents):
+        snaps.store(k, ag)
+
+    def sequential():
+        for k, ag in enumerate(agents):
+            venv.evaluate(ag, E, resets=(SEED, 0), out=out[k])
+        return out.cpu().numpy().reshape(-1)
+
+    def sets():
+        return snaps.evaluate(E, resets=(SEED, 0), out=out).cpu().numpy().reshape(-1)
+    return {'sequential': sequential, 'sets': sets}
+
+
+def main_sets(args):
+    """--sets K[,K..]: per (configuration, algorithm, K) the two variants of set_workloads, the protocol of the other
+    mode (interleaved rounds, the median of `calls` calls a round, the rounds' range); the two must agree bit for bit"""
+    ks = [int(k) for k in args.sets.split(',')]
+    work = {(c, a, K): set_workloads(a, K, **CONFIGS[c])
+            for c in args.configs.split(',') for a in args.algos.split(',') for K in ks}
+    lines = []
+
+    def emit(d):
+        lines.append(d)
+        print(json.dumps(d), flush=True)
+    for (c, a, K), w in work.items():
+        got = {v: [f() for _ in range(3)][-1] for v, f in w.items()}
+        emit({'what': 'sets_agreement', 'config': c, 'algo': a, 'sets': K, **CONFIGS[c],
+              'same_bits': bool(np.array_equal(got['sequential'].view(np.uint64), got['sets'].view(np.uint64)))})
+    rounds = {}
+    for r in range(args.rounds):
+        for (c, a, K), w in work.items():
+            for v, f in w.items():
+                ms = [timed(f) for _ in range(args.calls)]
+                rounds.setdefault((c, a, K, v), []).append(statistics.median(ms))
+    for (c, a, K, v), m in rounds.items():
+        emit({'what': 'sets_rounds', 'config': c, 'algo': a, 'sets': K, 'variant': v, 'calls': args.calls, **CONFIGS[c],
+              'round_medians_ms': [round(x, 4) for x in m], 'min_ms': round(min(m), 4),
+              'median_of_rounds_ms': round(statistics.median(m), 4), 'max_ms': round(max(m), 4)})
+    if args.out:
+        with open(args.out, 'w') as f:
+            for ln in lines:
+                f.write(json.dumps(ln) + '\n')
+
+
 def timed(fn):
     torch.cuda.synchronize()
     t0 = time.perf_counter()
@@ -110,7 +177,10 @@ def main():
     ap.add_argument('--algos', default='ppo,ddpg')
     ap.add_argument('--variants', default='per_step,rollout,evaluate')
     ap.add_argument('--out', default=None)
+    ap.add_argument('--sets', default=None, help='K[,K..]: time K sequential evaluate calls against one K-set launch')
     args = ap.parse_args()
+    if args.sets:
+        return main_sets(args)
     variants = args.variants.split(',')
     work = {(c, a): workloads(a, **CONFIGS[c]) for c in args.configs.split(',') for a in args.algos.split(',')}
     lines = []

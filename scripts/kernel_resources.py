@@ -31,8 +31,14 @@ def demangle(names):
         return list(names)
     out = subprocess.run([filt] + list(names), check=True, capture_output=True, text=True).stdout
     # (ddpg_rollout_kernel's argument type is a nest of std::conditional_t: written (...))
-    return [re.sub(r'(ddpg_rollout_kernel<[^>]*>)\(.*\)$', r'\1(...)', s.replace('(anonymous namespace)::', ''))
-            for s in out.splitlines()]
+    # (the evaluation kernels' last template argument, SETS, came with the multi-set launches: a single-set
+    # instantiation <.., false> keeps the name it had without it, so that it meets its row of the parent commit; the
+    # SETS ones take a WithSets<...> argument: written (...))
+    names = [re.sub(r'(ddpg_rollout_kernel<[^>]*>)\(.*\)$', r'\1(...)', s.replace('(anonymous namespace)::', ''))
+             for s in out.splitlines()]
+    names = [re.sub(r'((?:ppo|ddpg)_eval_kernel<[^>]*), false>', r'\1>', s) for s in names]
+    names = [re.sub(r'std::conditional<false, WithSets<(\w+)>, \1>::type', r'\1', s) for s in names]
+    return [re.sub(r'((?:ppo|ddpg)_eval_kernel<[^>]*, true>)\(.*\)$', r'\1(...)', s) for s in names]
 
 
 def remarks(path):

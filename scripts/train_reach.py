@@ -2,6 +2,7 @@
 
     python scripts/train_reach.py --algo ppo|ddpg [--actors N --J J --episode-len L --iters K --seed S --out FILE]
                                   [--random-resets [--heldout-episodes E]] [--eval-heldout] [--device-eval]
+                                  [--snapshot-curve]
 
 Per iteration: one rollout chunk of all actors inside one launch (ppo_rollout_into / ddpg_rollout_into on a
 SyntheticVecEnv(task='reach') with a DeviceEpisodeMonitor and an exploration noise stream attached) -> the replay's device
@@ -23,7 +24,14 @@ episodes -- the measurement that shows what random resets buy.
 nothing recorded, the env untouched; the held-out form with resets=(S + 3, 0); a sampling evaluation agent -- PPO's under
 env_config.stochastic_eval -- draws from a noise stream of seed S + 4); every curve line then also carries the
 per-step figure on the same parameters (eval_return_per_step) and the wall time of both.  Without the flag nothing
-changes."""
+changes.
+--snapshot-curve: at every evaluation point the evaluation agent's parameters go into a slot of a DeviceEvalSnapshots on
+the training env (one asynchronous store); after training ALL of them are evaluated in ONE launch on the evaluation's
+episodes -- the held-out ones (resets=(S + 3, 0), --heldout-episodes per actor) where the evaluation is held out, else one
+episode from every actor's reset state; a sampling PPO agent draws from ONE fixed noise stream (S + 4, first_step 0) for
+all snapshots, so the points are paired -- and one last line {"kind": "snapshot_curve", ...} carries the mean return per
+point.  With --device-eval and a deterministic evaluation agent every point must have the bits of the per-point device
+evaluation made during training (asserted; "bits_match": true).  Without the flag every line is unchanged."""
 import argparse
 import json
 import os
@@ -218,7 +226,18 @@ class Loop(object):
             kw['noise'] = (self.seed + 4, self.device_eval_steps)
             self.device_eval_steps += E * self.L
         returns = self.venv.evaluate(self.eval_agent, E, **kw)
+        self.last_device_returns = returns           # (kept on the device: --snapshot-curve compares bits with it)
         return float(np.mean(returns.cpu().numpy()))
+
+    def snapshot_curve_args(self):
+        """(episodes, evaluate()'s keywords) of the one launch over all snapshots: the evaluation's own episodes; a
+        sampling agent's draws from one fixed stream position for every snapshot"""
+        kw = {}
+        if self.heldout:
+            kw['resets'] = (self.seed + 3, 0)
+        if self.eval_agent.agent_mode in ('eval_stochastic', 'eval_stochastic_local'):
+            kw['noise'] = (self.seed + 4, 0)
+        return self.heldout or 1, kw
 
     def _evaluate_heldout(self):
         """the same over the held-out episodes 0 .. E - 1 of every actor: the stream's index goes back to 0, reset()
@@ -239,7 +258,7 @@ class Loop(object):
 
 
 def train(algo, actors=64, J=2, episode_len=50, iters=None, seed=0, eval_every=10, device=None, log=print,
-          random_resets=False, heldout_episodes=4, eval_heldout=False, device_eval=False):
+          random_resets=False, heldout_episodes=4, eval_heldout=False, device_eval=False, snapshot_curve=False):
     """-> (the baselines, the curve: one dict per evaluation).  random_resets / eval_heldout / device_eval: the module
     docstring's"""
     iters = DEFAULT_ITERS[algo] if iters is None else iters
@@ -255,6 +274,9 @@ def train(algo, actors=64, J=2, episode_len=50, iters=None, seed=0, eval_every=1
     loop = Loop(algo, actors, J, episode_len, seed, device, random_resets=random_resets, heldout=heldout)
     gap = base['pd_return'] - base['zero_action_return']
     curve, t0 = [], time.time()
+    points = [it for it in range(iters + 1) if it % eval_every == 0 or it == iters]
+    snaps = loop.venv.eval_snapshots(loop.eval_agent, len(points)) if snapshot_curve else None
+    per_point = []                                   # (--device-eval: the per-point launches' returns, on the device)
     for it in range(iters + 1):
         if it % eval_every == 0 or it == iters:
             extra = {}
@@ -272,8 +294,26 @@ def train(algo, actors=64, J=2, episode_len=50, iters=None, seed=0, eval_every=1
                           'gap_closed': (ev - base['zero_action_return']) / gap, 'wall_s': round(time.time() - t0, 3)})
             curve[-1].update(extra)
             log(json.dumps(curve[-1]))
+            if snaps is not None:
+                snaps.store(len(curve) - 1)          # (both evaluations fetched: the parameters they ran)
+                if device_eval:
+                    per_point.append(loop.last_device_returns)
         if it < iters:
             loop.iterate()
+    if snaps is not None:
+        E, kw = loop.snapshot_curve_args()
+        t1 = time.time()
+        returns = snaps.evaluate(E, **kw)            # [points, n, E]: ONE launch
+        means = returns.mean(dim=(1, 2)).cpu().numpy()
+        line = {'kind': 'snapshot_curve', 'algo': algo, 'points': len(points), 'iterations': points, 'episodes': E,
+                'mean_return': [float(v) for v in means], 'wall_s': round(time.time() - t1, 4), 'bits_match': None}
+        if device_eval and 'noise' not in kw:
+            for k, want in enumerate(per_point):
+                assert torch.equal(returns[k].view(torch.int64), want.view(torch.int64)), \
+                    'snapshot %d (iteration %d) does not have the bits of its per-point evaluation' % (k, points[k])
+            line['bits_match'] = True
+        log(json.dumps(line))
+        curve.append(line)
     return base, curve
 
 
@@ -293,6 +333,8 @@ def main():
     ap.add_argument('--eval-heldout', action='store_true', help='fixed resets in training, held-out episodes in evaluation')
     ap.add_argument('--device-eval', action='store_true', help='evaluate in one launch on the training env; the curve '
                     'lines also carry the per-step figure')
+    ap.add_argument('--snapshot-curve', action='store_true', help='store a parameter snapshot at every evaluation point '
+                    'and evaluate all of them in one launch after training')
     args = ap.parse_args()
     lines = []
 
@@ -301,7 +343,7 @@ def main():
         lines.append(s)
     train(args.algo, args.actors, args.J, args.episode_len, args.iters, args.seed, args.eval_every, log=log,
           random_resets=args.random_resets, heldout_episodes=args.heldout_episodes, eval_heldout=args.eval_heldout,
-          device_eval=args.device_eval)
+          device_eval=args.device_eval, snapshot_curve=args.snapshot_curve)
     if args.out:
         with open(args.out, 'a') as f:
             f.write('\n'.join(lines) + '\n')

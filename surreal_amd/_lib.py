@@ -206,6 +206,17 @@ class SynthDdpgEval(Structure):
                 ('init_state', c_void_p), ('resets', ResetStream), ('returns', c_void_p)]
 
 
+class EvalSnapshotSrc(Structure):
+    """struct smx_eval_snapshot_src"""
+    _fields_ = [('net', POINTER(Mlp3)), ('log_var', c_void_p), ('zsum', c_void_p), ('zsumsq', c_void_p),
+                ('zcount', c_void_p), ('lstm', POINTER(Lstm)), ('ddpg', c_int32), ('reserved', c_int32)]
+
+
+class EvalSets(Structure):
+    """struct smx_eval_sets"""
+    _fields_ = [('blobs', c_void_p), ('stride', c_int64), ('sets', c_int32), ('zfilter', c_int32)]
+
+
 class SynthRollout(Structure):
     """smx_synth_rollout_t"""
     _fields_ = [('net', POINTER(Mlp3)), ('packed', c_void_p), ('out_act', c_int32), ('n', c_int32),
@@ -574,6 +585,10 @@ _SIGS = {
     'smx_synth_eval_supported': (c_int32, [c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32]),
     'smx_synth_ppo_eval_f32': (c_int32, [POINTER(SynthPpoEval), _P]),
     'smx_synth_ddpg_eval_f32': (c_int32, [POINTER(SynthDdpgEval), _P]),
+    'smx_eval_snapshot_floats': (c_int64, [c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32]),
+    'smx_eval_snapshot_store_f32': (c_int32, [POINTER(EvalSnapshotSrc), _P, _P]),
+    'smx_synth_ppo_eval_sets_f32': (c_int32, [POINTER(SynthPpoEval), POINTER(EvalSets), _P]),
+    'smx_synth_ddpg_eval_sets_f32': (c_int32, [POINTER(SynthDdpgEval), POINTER(EvalSets), _P]),
     'smx_synth_ddpg_step_f32': (c_int32, [POINTER(DdpgRollout), _P, c_int64, _P]),
     'smx_synth_ddpg_pixel_step': (c_int32, [POINTER(DdpgPixelStep), _P, c_int64, _P]),
     'smx_synth_ddpg_pixel_pool_step': (c_int32, [POINTER(DdpgPixelPoolStep), _P, c_int64, _P]),

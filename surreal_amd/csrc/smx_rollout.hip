@@ -50,6 +50,11 @@
 //                               rows of one launch, nothing recorded, the fp64 returns stored once (ppo_eval_kernel,
 //                               ddpg_eval_kernel: new kernels that share the pieces above, not the bodies).
 //
+//   smx_synth_ppo_eval_sets_f32 / smx_synth_ddpg_eval_sets_f32  the same for several parameter SNAPSHOTS on the same episodes
+//                               in one launch (the SETS instantiations of the two evaluation kernels on a grid (blocks, sets):
+//                               the same bodies, the set's shift applied once at entry); smx_eval_snapshot_floats /
+//                               smx_eval_snapshot_store_f32: a snapshot's layout and its store (at the end of the file).
+//
 // Layout: the persistent kernels (PPO, then DDPG, then the evaluation), the step kernels (the two camera ones share their frame half:
 // frame_ctx / render_next_frame / copy_frames), then the host side: carve() and launch(), the argument fills (net_fields,
 // roll_fields, table_fields, lstm_fields, win_fields, pixel_fields), the rules the entry points share (*_ok, *_pointers),
@@ -1420,6 +1425,22 @@ struct PEvalArgs : RollBase {
     EvalTail ev;
 };
 struct DEvalArgs : RollBase { EvalTail ev; };
+// Several parameter sets in one launch (smx_synth_*_eval_sets_f32; the SETS instantiations): a set's twin arguments --
+// every parameter pointer into set 0's snapshot, n the rows of ONE set, returns set 0's [n, E] -- then the floats from
+// one snapshot to the next.  The grid is (blocks of one set, sets): workgroup (x, s) is block x of the single-set launch
+// with every parameter pointer moved on by s * set_stride floats and the returns by s * n.
+template <typename Base>
+struct WithSets : Base { long long set_stride; };
+template <bool SETS>
+using PEvalKernelArgs = std::conditional_t<SETS, WithSets<PEvalArgs>, PEvalArgs>;
+template <bool SETS>
+using DEvalKernelArgs = std::conditional_t<SETS, WithSets<DEvalArgs>, DEvalArgs>;
+// floats from set 0's parameters to this workgroup's set's (0 in a single-set kernel: folded away)
+template <bool SETS, typename KArgs>
+__device__ __forceinline__ size_t eval_set_shift(const KArgs& G) {
+    if constexpr (SETS) return (size_t)blockIdx.y * (size_t)G.set_stride;
+    else return 0;
+}
 
 // the first rows of the block's episodes into the environment lanes' registers (before E.start())
 template <typename Lanes>
@@ -1461,8 +1482,8 @@ struct EvalNoRow {};
 // record.  LSTM rows start from zero h, c (PPOAgent.reset, ppo_agent.py:169-178).  A sampling launch (nstream.enabled:
 // eval_stochastic) draws row (a, i)'s step t at normal(seed, actor_base + a, first_step + i L + t, j): what a serial run
 // of the actor's E episodes on that stream draws.
-template <int RG, int NT, bool LSTM, bool COLS, int TASK>
-__global__ __launch_bounds__(RNTH) void ppo_eval_kernel(PEvalArgs G) {
+template <int RG, int NT, bool LSTM, bool COLS, int TASK, bool SETS = false>
+__global__ __launch_bounds__(RNTH) void ppo_eval_kernel(PEvalKernelArgs<SETS> G) {
     constexpr int RB = 4 * RG;
     extern __shared__ float sm[];
     const int tid = threadIdx.x, lane = tid & 63;
@@ -1473,8 +1494,15 @@ __global__ __launch_bounds__(RNTH) void ppo_eval_kernel(PEvalArgs G) {
     const float* outs = sm + G.off_out;
     float* s_act = sm + G.off_act;              // [RB][RMAX_A] clipped actions
     const int ldh2 = G.ldh2;
+    // (SETS) the one shift of the workgroup's set: every parameter read below goes through it
+    const size_t shift = eval_set_shift<SETS>(G);
 
-    clear_tiles(G, sm, tid, G.zsum, G.zsumsq, G.zcount, G.zeps);
+    if constexpr (SETS) {
+        if (G.zsum) clear_tiles(G, sm, tid, G.zsum + shift, G.zsumsq + shift, G.zcount + shift, G.zeps);
+        else clear_tiles(G, sm, tid, nullptr, nullptr, nullptr, G.zeps);
+    } else {
+        clear_tiles(G, sm, tid, G.zsum, G.zsumsq, G.zcount, G.zeps);
+    }
     EnvLanes<RB, COLS, TASK> E(G, sm, G.zsum ? sm + G.off_z : nullptr, wv, lane, OwnStart{});
     if constexpr (TASK == SMX_TASK_REACH) {
         E.rst = nullptr;                         // (done is false at every step: never read)
@@ -1500,7 +1528,7 @@ __global__ __launch_bounds__(RNTH) void ppo_eval_kernel(PEvalArgs G) {
     constexpr bool W3REG = RG < 4;
     float4 w3a[2], w3b[2];
     auto load_w3 = [&]() {
-        const rsrc_t rw3 = make_rsrc(G.P3, (unsigned)tiles3 * (unsigned)C3 * 2048u);
+        const rsrc_t rw3 = make_rsrc(G.P3 + shift, (unsigned)tiles3 * (unsigned)C3 * 2048u);
 #pragma unroll
         for (int g = 0; g < 2; ++g) {
             const unsigned o = (l3res && g < tiles3 && wv < C3)
@@ -1512,8 +1540,8 @@ __global__ __launch_bounds__(RNTH) void ppo_eval_kernel(PEvalArgs G) {
     if (W3REG) load_w3();
     float* red3 = sm + G.off_red3;               // [RNWV][RB][32]: the waves' partial output sums
     const int hr = tid / A, hj = tid - hr * A;            // RB x A <= 512 pairs
-    const float b3v = G.b3[hj];
-    const float sd0 = expf(G.log_var[hj]);
+    const float b3v = (G.b3 + shift)[hj];
+    const float sd0 = expf((G.log_var + shift)[hj]);
     const bool noisy = G.nstream.enabled != 0;
     // the pair's actor and the draw step of its episode's first step
     long ha = 0;
@@ -1549,9 +1577,9 @@ __global__ __launch_bounds__(RNTH) void ppo_eval_kernel(PEvalArgs G) {
                     sm[r * ldx + G.Dp + j] = h;
                 }
                 SMX_LDS_BARRIER();
-            }, G.Dp, G.H, gate);
+            }, G.Dp, G.H, gate, shift);
         } else {
-            layers4<RG, NT>(G, sm, l3res ? 2 : 3, G.out_act, wv, lane, [](int) {}, 0, G.D);
+            layers4<RG, NT>(G, sm, l3res ? 2 : 3, G.out_act, wv, lane, [](int) {}, 0, G.D, PreLayer{}, shift);
         }
         if (l3res) {
             if (!W3REG) load_w3();
@@ -1609,12 +1637,13 @@ __global__ __launch_bounds__(RNTH) void ppo_eval_kernel(PEvalArgs G) {
                [&](long row, EvalNoRow, float rew) { ret.add(E, row, rew); });
         SMX_LDS_BARRIER();
     }
-    ret.store(E, G.ev.returns);
+    if constexpr (SETS) ret.store(E, G.ev.returns + (size_t)blockIdx.y * (size_t)G.n);
+    else ret.store(E, G.ev.returns);
 }
 
 // DDPG: ddpg_rollout_kernel's step in a deterministic agent mode (tanh, clip; SMX_DDPG_NOISE_NONE) without a record
-template <int RG, int NT, int TASK>
-__global__ __launch_bounds__(RNTH) void ddpg_eval_kernel(DEvalArgs G) {
+template <int RG, int NT, int TASK, bool SETS = false>
+__global__ __launch_bounds__(RNTH) void ddpg_eval_kernel(DEvalKernelArgs<SETS> G) {
     constexpr int RB = 4 * RG;
     extern __shared__ float sm[];
     const int tid = threadIdx.x, lane = tid & 63;
@@ -1636,18 +1665,20 @@ __global__ __launch_bounds__(RNTH) void ddpg_eval_kernel(DEvalArgs G) {
     E.start();
     const int hr = tid / A, hj = tid - hr * A;       // RB x A <= 512 pairs
     const bool head = hr < E.nrows;
+    const size_t shift = eval_set_shift<SETS>(G);    // (SETS) floats to the workgroup's set
     SMX_LDS_BARRIER();
     EvalReturns ret;
 #pragma unroll 1
     for (int step = 0; step < G.steps; ++step) {
-        layers4<RG, NT>(G, sm, 3, SMX_ACT_TANH, wv, lane, [](int) {}, 0, G.D);
+        layers4<RG, NT>(G, sm, 3, SMX_ACT_TANH, wv, lane, [](int) {}, 0, G.D, PreLayer{}, shift);
         if (head) s_act[hr * RMAX_A + hj] = clip1(clip1(outs[hr * RLDO + hj]));      // (explore() without noise)
         SMX_LDS_BARRIER();
         E.step(s_act, false, [](long) { return EvalNoRow{}; }, [](long, EvalNoRow, int, float, float) {},
                [&](long row, EvalNoRow, float rew) { ret.add(E, row, rew); });
         SMX_LDS_BARRIER();
     }
-    ret.store(E, G.ev.returns);
+    if constexpr (SETS) ret.store(E, G.ev.returns + (size_t)blockIdx.y * (size_t)G.n);
+    else ret.store(E, G.ev.returns);
 }
 
 // The one-step body both step kernels share, in two phases with a barrier between them.  Phase 1, lane = action j < A
@@ -2206,8 +2237,9 @@ constexpr bool has_clocks = false;
 template <typename Base>
 constexpr bool has_clocks<WithClk<Base>> = true;
 
+// (sets: the grid's second dimension -- the evaluation of several parameter sets, one row of workgroups a set)
 template <auto K, typename Args>
-int launch(const Args& G, int rb, int lds, smx_stream_t stream) {
+int launch(const Args& G, int rb, int lds, smx_stream_t stream, int sets = 1) {
     static const hipError_t attr = hipFuncSetAttribute((const void*)K, hipFuncAttributeMaxDynamicSharedMemorySize,
                                                        ROLL_MAX_LDS + ROLL_EP_LDS + (has_clocks<Args> ? ROLL_CLK_LDS : 0));
     (void)attr;
@@ -2215,17 +2247,17 @@ int launch(const Args& G, int rb, int lds, smx_stream_t stream) {
     lds = carve_episodes(A, rb, lds);
     if constexpr (has_clocks<Args>) lds = carve_clocks(A.clk, rb, lds);
     if (lds < ROLL_EXCLUSIVE_LDS) lds = ROLL_EXCLUSIVE_LDS;
-    hipLaunchKernelGGL(K, dim3((A.n + rb - 1) / rb), dim3(RNTH), lds, smx_s(stream), A);
+    hipLaunchKernelGGL(K, dim3((A.n + rb - 1) / rb, sets), dim3(RNTH), lds, smx_s(stream), A);
     SMX_LAUNCH_CHECK();
     return SMX_OK;
 }
 
 // the same for a block of rb = 4 | 8 | 16 actors: each has its own instantiation
 template <auto K4, auto K8, auto K16, typename Args>
-int launch(const Args& G, int rb, int lds, smx_stream_t stream) {
-    if (rb == 4) return launch<K4>(G, rb, lds, stream);
-    if (rb == 8) return launch<K8>(G, rb, lds, stream);
-    return launch<K16>(G, rb, lds, stream);
+int launch(const Args& G, int rb, int lds, smx_stream_t stream, int sets = 1) {
+    if (rb == 4) return launch<K4>(G, rb, lds, stream, sets);
+    if (rb == 8) return launch<K8>(G, rb, lds, stream, sets);
+    return launch<K16>(G, rb, lds, stream, sets);
 }
 
 // a task kernel's arguments from its drift twin's and the reset stream (null: none)
@@ -2937,4 +2969,226 @@ extern "C" int smx_synth_ddpg_eval_f32(const struct smx_synth_ddpg_eval* a, smx_
                       ddpg_eval_kernel<4, 2, SMX_TASK_REACH>>(G, rb, lds, stream);
     return launch<ddpg_eval_kernel<1, 3, SMX_TASK_DRIFT>, ddpg_eval_kernel<2, 3, SMX_TASK_DRIFT>,
                   ddpg_eval_kernel<4, 2, SMX_TASK_DRIFT>>(G, rb, lds, stream);
+}
+
+// ---- evaluation of several parameter sets in one launch ---------------------------------------------------------------------
+// A snapshot is one policy's parameters as one blob (smx_eval_snapshot_floats): [smx_epoch_pack_f32's copy of the actor |
+// b1 | b2 | b3], which is one agent's copy of a plain-actor population (pop_copy_floats); a PPO policy's goes on with
+// log_var [A], the z-filter's zsum [D] | zsumsq [D] | zcount [1] and the LSTM's gate pass (smx_lstm_rollout_pack_f32),
+// each on 16 bytes.  The offsets are floats from the blob's start; 0: the policy has no such block.
+namespace {
+
+struct SnapLayout {
+    long bias, log_var, zsum, zsumsq, zcount, lstm, lstm_n, total;
+};
+inline long up4(long x) { return (x + 3) & ~3L; }
+
+// D: the observation's width (the LSTM's input width where H > 0: the actor then reads the H units)
+SnapLayout snap_layout(bool ddpg, int D, int H, int H1, int H2, int A, bool zfilter) {
+    SnapLayout S;
+    memset(&S, 0, sizeof(S));
+    S.bias = pop_bias_off(H > 0 ? H : D, H1, H2, A);
+    long o = S.bias + H1 + H2 + A;
+    if (!ddpg) {
+        S.log_var = o = up4(o);
+        o += A;
+        if (zfilter) {
+            S.zsum = o = up4(o);
+            o += D;
+            S.zsumsq = o = up4(o);
+            o += D;
+            S.zcount = o = up4(o);
+            o += 1;
+        }
+        if (H > 0) {
+            S.lstm = o = up4(o);
+            S.lstm_n = lstm_pack_floats(D, H);
+            o += S.lstm_n;
+        }
+    }
+    S.total = (o + 63) & ~63L;
+    return S;
+}
+
+// floats of a snapshot, 0 for a policy no evaluation launch takes on any task (a DDPG actor has no z-filter)
+long snap_floats(int ddpg, int D, int H, int H1, int H2, int A, int zfilter) {
+    if ((zfilter != 0 && zfilter != 1) || (ddpg && zfilter)) return 0;
+    if (!smx_synth_eval_supported(ddpg, SMX_TASK_DRIFT, D, H, H1, H2, A) &&
+        !smx_synth_eval_supported(ddpg, SMX_TASK_REACH, D, H, H1, H2, A))
+        return 0;
+    return snap_layout(ddpg != 0, D, H, H1, H2, A, zfilter != 0).total;
+}
+
+// everything behind the packed weights but the LSTM's block: the small arrays, zeros between and behind them
+struct SnapTailArgs {
+    const float *b1, *b2, *b3, *log_var, *zsum, *zsumsq, *zcount;
+    int D, H1, H2, A;
+    SnapLayout S;
+    float* blob;
+};
+__global__ __launch_bounds__(256) void eval_snapshot_tail_kernel(SnapTailArgs P) {
+    const SnapLayout& S = P.S;
+    for (long i = S.bias + (long)blockIdx.x * 256 + threadIdx.x; i < S.total; i += (long)gridDim.x * 256) {
+        if (S.lstm_n && i >= S.lstm && i < S.lstm + S.lstm_n) continue;     // (the gate pass's pack kernel writes these)
+        const long e = i - S.bias;
+        float v = 0.f;
+        if (e < P.H1) v = P.b1[e];
+        else if (e < P.H1 + P.H2) v = P.b2[e - P.H1];
+        else if (e < P.H1 + P.H2 + P.A) v = P.b3[e - P.H1 - P.H2];
+        else if (P.log_var && i >= S.log_var && i < S.log_var + P.A) v = P.log_var[i - S.log_var];
+        else if (P.zsum && i >= S.zsum && i < S.zsum + P.D) v = P.zsum[i - S.zsum];
+        else if (P.zsum && i >= S.zsumsq && i < S.zsumsq + P.D) v = P.zsumsq[i - S.zsumsq];
+        else if (P.zsum && i == S.zcount) v = P.zcount[0];
+        P.blob[i] = v;
+    }
+}
+
+template <typename Base>
+WithSets<Base> with_sets(const Base& G, long long stride) {
+    WithSets<Base> X;
+    static_cast<Base&>(X) = G;
+    X.set_stride = stride;
+    return X;
+}
+
+// what both entry points ask of the sets (need: the floats of one snapshot; rows: n * episodes of one set)
+int sets_ok(const struct smx_eval_sets* s, long need, long long rows) {
+    SMX_REQUIRE(s->sets >= 1 && s->sets <= 65535 && (long long)s->sets * rows < (1LL << 31), SMX_E_SHAPE);
+    SMX_REQUIRE(need > 0 && s->stride >= need && s->stride % 4 == 0, SMX_E_SHAPE);
+    SMX_REQUIRE(((uintptr_t)s->blobs & 15) == 0, SMX_E_ALIGN);
+    return SMX_OK;
+}
+
+// the actor's fields from set 0's snapshot
+void snap_net_fields(const smx_mlp3_t& n, const float* blob, const SnapLayout& S, RollBase& G) {
+    smx_mlp3_t m = n;
+    m.b1 = const_cast<float*>(blob) + S.bias;
+    m.b2 = m.b1 + n.H1;
+    m.b3 = m.b2 + n.H2;
+    net_fields(m, blob, G);
+}
+
+template <bool LSTM, int TASK, typename Args>
+int ppo_eval_sets_launch(const Args& G, int rb, int lds, smx_stream_t stream, int sets) {
+    return launch<ppo_eval_kernel<1, 3, LSTM, true, TASK, true>, ppo_eval_kernel<2, 3, LSTM, true, TASK, true>,
+                  ppo_eval_kernel<4, 2, LSTM, false, TASK, true>>(G, rb, lds, stream, sets);
+}
+template <int TASK, typename Args>
+int ddpg_eval_sets_launch(const Args& G, int rb, int lds, smx_stream_t stream, int sets) {
+    return launch<ddpg_eval_kernel<1, 3, TASK, true>, ddpg_eval_kernel<2, 3, TASK, true>,
+                  ddpg_eval_kernel<4, 2, TASK, true>>(G, rb, lds, stream, sets);
+}
+
+}  // namespace
+
+extern "C" int64_t smx_eval_snapshot_floats(int32_t ddpg, int32_t D, int32_t H, int32_t H1, int32_t H2, int32_t A,
+                                            int32_t zfilter) {
+    return snap_floats(ddpg, D, H, H1, H2, A, zfilter);
+}
+
+extern "C" int smx_eval_snapshot_store_f32(const struct smx_eval_snapshot_src* src, float* blob, smx_stream_t stream) {
+    SMX_REQUIRE(src && blob && src->net, SMX_E_NULL);
+    const smx_mlp3_t& n = *src->net;
+    SMX_REQUIRE(n.W1 && n.b1 && n.W2 && n.b2 && n.W3 && n.b3 && (src->ddpg || src->log_var), SMX_E_NULL);
+    const bool zf = src->zsum != nullptr;
+    SMX_REQUIRE(zf == (src->zsumsq != nullptr) && zf == (src->zcount != nullptr), SMX_E_NULL);
+    const smx_lstm_t* l = src->lstm;
+    SMX_REQUIRE(!l || (l->W_ih && l->W_hh && l->b_ih && l->b_hh), SMX_E_NULL);
+    SMX_REQUIRE(!l || n.D == l->H, SMX_E_SHAPE);
+    const int D = l ? l->D : n.D, H = l ? l->H : 0;
+    SMX_REQUIRE(snap_floats(src->ddpg, D, H, n.H1, n.H2, n.OUT, zf) > 0, SMX_E_UNSUPPORTED);
+    SMX_REQUIRE(((uintptr_t)blob & 15) == 0, SMX_E_ALIGN);
+    const SnapLayout S = snap_layout(src->ddpg != 0, D, H, n.H1, n.H2, n.OUT, zf);
+    smx_epoch_pack_t item;
+    memset(&item, 0, sizeof(item));
+    item.net = src->net;
+    item.packed = blob;
+    int rc = smx_epoch_pack_f32(&item, 1, stream);
+    if (rc != SMX_OK) return rc;
+    if (l) {
+        rc = smx_lstm_rollout_pack_f32(l, blob + S.lstm, stream);
+        if (rc != SMX_OK) return rc;
+    }
+    SnapTailArgs P;
+    memset(&P, 0, sizeof(P));
+    P.b1 = n.b1; P.b2 = n.b2; P.b3 = n.b3;
+    if (!src->ddpg) P.log_var = src->log_var;
+    P.zsum = src->zsum; P.zsumsq = src->zsumsq; P.zcount = src->zcount;
+    P.D = D; P.H1 = n.H1; P.H2 = n.H2; P.A = n.OUT;
+    P.S = S;
+    P.blob = blob;
+    const long tail = S.total - S.bias;
+    hipLaunchKernelGGL(eval_snapshot_tail_kernel, dim3((unsigned)((tail + 255) / 256 < 64 ? (tail + 255) / 256 : 64)),
+                       dim3(256), 0, smx_s(stream), P);
+    SMX_LAUNCH_CHECK();
+    return SMX_OK;
+}
+
+extern "C" int smx_synth_ppo_eval_sets_f32(const struct smx_synth_ppo_eval* a, const struct smx_eval_sets* s,
+                                           smx_stream_t stream) {
+    SMX_REQUIRE(a && a->net && a->init_state && a->returns && s && s->blobs, SMX_E_NULL);
+    const bool lstm = a->lstm != nullptr;
+    const smx_mlp3_t& n = *a->net;
+    const int D = lstm ? a->lstm->D : n.D, H = lstm ? a->lstm->H : 0;
+    SMX_REQUIRE(!lstm || lstm_shape_ok(n, *a->lstm, a->hidden), SMX_E_SHAPE);
+    SMX_REQUIRE(smx_synth_eval_supported(0, a->task, D, H, n.H1, n.H2, n.OUT), SMX_E_UNSUPPORTED);
+    SMX_REQUIRE(block_ok(a->actors_per_workgroup) && noise_shape_ok(a->noise, a->n), SMX_E_SHAPE);
+    PEvalArgs G;
+    memset(&G, 0, sizeof(G));
+    int rc = eval_tail(a->n, a->episodes, a->episode_len, a->task, a->resets, a->returns, G.ev);
+    if (rc != SMX_OK) return rc;
+    SMX_REQUIRE(s->zfilter == 0 || s->zfilter == 1, SMX_E_SHAPE);
+    const SnapLayout S = snap_layout(false, D, H, n.H1, n.H2, n.OUT, s->zfilter != 0);
+    G.n = a->n * a->episodes;                        // the rows of one set
+    rc = sets_ok(s, S.total, G.n);
+    if (rc != SMX_OK) return rc;
+    snap_net_fields(n, s->blobs, S, G);
+    G.D = D; G.A = n.OUT; G.out_act = a->out_act; G.log_var = s->blobs + S.log_var;
+    if (s->zfilter) {
+        G.zsum = s->blobs + S.zsum; G.zsumsq = s->blobs + S.zsumsq; G.zcount = s->blobs + S.zcount;
+    }
+    G.zeps = a->zeps;
+    G.init_state = a->init_state;
+    G.steps = G.episode_len = a->episode_len;
+    if (a->noise.enabled) G.nstream = a->noise;
+    const int rb = pick_block(a->actors_per_workgroup, s->sets * G.n);
+    const bool reach = a->task == SMX_TASK_REACH;
+    if (!lstm) {
+        const int lds = carve(G, rb, /*mma16=*/false, /*split_out=*/true, /*ztables=*/true, G.D);
+        const auto X = with_sets(G, s->stride);
+        return reach ? ppo_eval_sets_launch<false, SMX_TASK_REACH>(X, rb, lds, stream, s->sets)
+                     : ppo_eval_sets_launch<false, SMX_TASK_DRIFT>(X, rb, lds, stream, s->sets);
+    }
+    G.H = H; G.Hl = a->hidden;
+    G.Pg = s->blobs + S.lstm; G.bg = G.Pg + pack_words(4 * G.H, lstm_dp(D) + G.H) * 4;
+    const int lds = carve_lstm(G, rb);
+    const auto X = with_sets(G, s->stride);
+    return reach ? ppo_eval_sets_launch<true, SMX_TASK_REACH>(X, rb, lds, stream, s->sets)
+                 : ppo_eval_sets_launch<true, SMX_TASK_DRIFT>(X, rb, lds, stream, s->sets);
+}
+
+extern "C" int smx_synth_ddpg_eval_sets_f32(const struct smx_synth_ddpg_eval* a, const struct smx_eval_sets* s,
+                                            smx_stream_t stream) {
+    SMX_REQUIRE(a && a->net && a->init_state && a->returns && s && s->blobs, SMX_E_NULL);
+    const smx_mlp3_t& n = *a->net;
+    SMX_REQUIRE(smx_synth_eval_supported(1, a->task, n.D, 0, n.H1, n.H2, n.OUT), SMX_E_UNSUPPORTED);
+    SMX_REQUIRE(block_ok(a->actors_per_workgroup), SMX_E_SHAPE);
+    DEvalArgs G;
+    memset(&G, 0, sizeof(G));
+    int rc = eval_tail(a->n, a->episodes, a->episode_len, a->task, a->resets, a->returns, G.ev);
+    if (rc != SMX_OK) return rc;
+    SMX_REQUIRE(s->zfilter == 0, SMX_E_SHAPE);       // (a DDPG actor has no z-filter)
+    const SnapLayout S = snap_layout(true, n.D, 0, n.H1, n.H2, n.OUT, false);
+    G.n = a->n * a->episodes;                        // the rows of one set
+    rc = sets_ok(s, S.total, G.n);
+    if (rc != SMX_OK) return rc;
+    snap_net_fields(n, s->blobs, S, G);
+    G.D = n.D; G.A = n.OUT;
+    G.init_state = a->init_state;
+    G.steps = G.episode_len = a->episode_len;
+    const int rb = pick_block(a->actors_per_workgroup, s->sets * G.n);
+    const int lds = carve(G, rb, /*mma16=*/false, /*split_out=*/false, /*ztables=*/false, G.D);
+    const auto X = with_sets(G, s->stride);
+    return a->task == SMX_TASK_REACH ? ddpg_eval_sets_launch<SMX_TASK_REACH>(X, rb, lds, stream, s->sets)
+                                     : ddpg_eval_sets_launch<SMX_TASK_DRIFT>(X, rb, lds, stream, s->sets);
 }

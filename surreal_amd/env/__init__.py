@@ -8,6 +8,6 @@ from .adapters import (ObsTransform, GymAdapter, RobosuiteWrapper, DMControlAdap
                        make_env, make_env_config, wrap_gym, wrap_robosuite, wrap_dm_control)
 from .monitor import (EpisodeMonitor, ConsoleMonitor, TrainingTensorplexMonitor,
                       EvalTensorplexMonitor, DeviceEpisodeMonitor, DeviceTrainingMonitor, DeviceNoise,
-                      DeviceParamNoise, DeviceEvaluator)
+                      DeviceParamNoise, DeviceEvaluator, DeviceEvalSnapshots)
 from .device_recorder import DeviceWindowRecorder, DeviceNStepRecorder, closing_ranks
 from .host_vec_env import HostVecEnv

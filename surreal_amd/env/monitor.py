@@ -552,6 +552,143 @@ class DeviceEvaluator(object):
         return _mean(xs) if xs else None
 
 
+class DeviceEvalSnapshots(object):
+    """`capacity` parameter SNAPSHOTS of one policy architecture on the device, all evaluated on the same episodes in ONE
+    launch (smx_synth_ppo_eval_sets_f32 / smx_synth_ddpg_eval_sets_f32): a learning curve's snapshots, an actor and its
+    target, the last K checkpoints.  Every set sees the same reset stream and the same noise stream, so a comparison
+    between snapshots is paired; set k's returns have the bits of env.evaluate() of an agent holding its parameters.
+    Also SyntheticVecEnv.eval_snapshots(agent, capacity).
+
+    agent: the TEMPLATE, an evaluation agent env.can_evaluate() accepts (anything else: can_evaluate's refusal, before
+    anything is allocated) -- it gives the architecture, whether a z-filter is used, and evaluate()'s mode.
+    buf: float32 [capacity, stride] on the device, slot k one snapshot (smx_eval_snapshot_floats: the packed actor, its
+    biases, a PPO policy's log_var, z-filter sums and packed LSTM); stored: which slots hold one."""
+
+    def __init__(self, env, agent, capacity, _population=None):
+        import torch
+        pn = _population
+        refusal = env._eval_refusal(agent, population=pn is not None)
+        if refusal is not None:
+            raise refusal[0](refusal[1])
+        self.ppo = hasattr(agent, 'rnn_config')
+        K = env.K
+        for name in ('eval_snapshot_floats', 'eval_snapshot_store', 'synth_ppo_eval_sets' if self.ppo else 'synth_ddpg_eval_sets'):
+            if getattr(K, name, None) is None:
+                raise NotImplementedError('DeviceEvalSnapshots: the kernels object has no %s' % name)
+        capacity = int(capacity)
+        if not 1 <= capacity <= 65535:
+            raise ValueError('DeviceEvalSnapshots: capacity must lie in [1, 65535], got %d' % capacity)
+        self.env, self.agent, self.K, self.capacity = env, agent, K, capacity
+        self.zfilter = bool(self.ppo and agent.use_z_filter)
+        self.floats = self._floats(agent)
+        if self.floats <= 0:
+            raise NotImplementedError('DeviceEvalSnapshots: smx_eval_snapshot_floats refuses the policy\'s shapes')
+        self.population = pn
+        if pn is None:
+            self.buf = torch.zeros(capacity, self.floats, device=env.device)
+            self.stored = [False] * capacity
+        else:
+            self.buf = pn.pop                        # (zero copy: refresh() rewrites the slots)
+            self.stored = [True] * capacity
+        self.stride = int(self.buf.shape[1])
+
+    @classmethod
+    def from_param_noise(cls, env, pn):
+        """a zero-copy view of a plain-actor DeviceParamNoise's population: slot p is agent p's perturbed actor as
+        pn.pop holds it (one agent's copy IS a DDPG snapshot), so evaluate() gives every perturbed actor's returns over
+        all n actors' episodes, acting without exploration noise.  The view cannot store(); pn.refresh() moves it on.
+        A LayerNorm population: NotImplementedError"""
+        if pn.ln:
+            raise NotImplementedError('DeviceEvalSnapshots.from_param_noise with a LayerNorm actor: the evaluation launch '
+                                      'runs a plain DDPG actor, only')
+        snaps = cls(env, pn.agent, pn.agents, _population=pn)
+        if int(pn.pop.shape[1]) < snaps.floats or int(pn.pop.shape[1]) % 4:
+            raise ValueError('DeviceEvalSnapshots.from_param_noise: a copy of the population has %d floats, a snapshot %d'
+                             % (int(pn.pop.shape[1]), snaps.floats))
+        return snaps
+
+    def _floats(self, agent):
+        m = agent.model
+        return self.K.eval_snapshot_floats(model=m, zfilter=self.zfilter) if self.ppo else \
+            self.K.eval_snapshot_floats(actor=m.actor)
+
+    @staticmethod
+    def _architecture(agent):
+        """what two agents must share to share snapshots"""
+        ppo = hasattr(agent, 'rnn_config')
+        m = agent.model
+        a = m.actor
+        arch = (ppo, a.D, a.H1, a.H2, a.OUT)
+        if ppo:
+            rnn = bool(agent.rnn_config.if_rnn_policy)
+            arch += (bool(agent.use_z_filter), rnn) + ((m.rnn.D, m.rnn.H, m.rnn_hidden_logical) if rnn else ())
+        return arch
+
+    def _slots(self, first, count):
+        first = int(first)
+        count = self.capacity - first if count is None else int(count)
+        if first < 0 or count < 1 or first + count > self.capacity:
+            raise ValueError('DeviceEvalSnapshots: slots [%d, %d) leave [0, %d)' % (first, first + count, self.capacity))
+        return first, count
+
+    def store(self, slot, agent=None):
+        """slot <- the agent's (None: the template's) CURRENT parameters, the z-filter's sums with them where the
+        template uses one; asynchronous, no host synchronisation (smx_eval_snapshot_store_f32).  The slot then no longer
+        depends on the agent.  An agent of another architecture or z-filter use: ValueError"""
+        if self.population is not None:
+            raise ValueError('DeviceEvalSnapshots.store: a view of a parameter-noise population holds its perturbed '
+                             'actors (refresh the noise)')
+        slot, _ = self._slots(slot, 1)
+        agent = self.agent if agent is None else agent
+        if hasattr(agent, 'rnn_config') != self.ppo or self._architecture(agent) != self._architecture(self.agent):
+            raise ValueError('DeviceEvalSnapshots.store: the agent\'s architecture %r is not the template\'s %r'
+                             % (self._architecture(agent), self._architecture(self.agent)))
+        m = agent.model
+        if self.ppo:
+            self.K.eval_snapshot_store(self.buf[slot], model=m, zfilter=m.z_filter if self.zfilter else None)
+        else:
+            self.K.eval_snapshot_store(self.buf[slot], actor=m.actor)
+        self.stored[slot] = True
+
+    def evaluate(self, episodes=1, first=0, count=None, resets=None, noise=None, out=None, actors_per_workgroup=0):
+        """`episodes` whole episodes of every actor under each of the snapshots in slots [first, first + count) (count
+        None: up to the last slot; all must have been stored, else ValueError) in ONE launch -> their returns,
+        torch.float64 [count, n, episodes] on the device (`out`, or a new tensor); no synchronisation.  The mode rule,
+        resets=, noise= and the size checks are SyntheticVecEnv.evaluate's, with the template agent's mode; it is pure in
+        the same sense"""
+        import torch
+        first, count = self._slots(first, count)
+        env = self.env
+        ppo, E, resets, noise = env._eval_check(self.agent, episodes, resets, noise, self.population is not None, count)
+        missing = [k for k in range(first, first + count) if not self.stored[k]]
+        if missing:
+            raise ValueError('DeviceEvalSnapshots.evaluate: slots %r were never stored' % (missing,))
+        n, L_ = env.n, int(env.episode_len)
+        if out is None:
+            out = torch.empty(count, n, E, dtype=torch.float64, device=env.device)
+        elif out.dtype != torch.float64 or tuple(out.shape) != (count, n, E) or not out.is_contiguous():
+            raise ValueError('evaluate: out must be a contiguous torch.float64 [%d, %d, %d] tensor' % (count, n, E))
+        blobs = self.buf[first:first + count]
+        kw = dict(task=env.task, resets=resets, actors_per_workgroup=actors_per_workgroup)
+        m = self.agent.model
+        if ppo:
+            self.K.synth_ppo_eval_sets(m, blobs, env.init_state, E, L_, out, zfilter=m.z_filter if self.zfilter else None,
+                                       noise=noise, **kw)
+        else:
+            self.K.synth_ddpg_eval_sets(m.actor, blobs, env.init_state, E, L_, out, **kw)
+        return out
+
+    def state_dict(self):
+        return {'buf': self.buf.to('cpu', copy=True), 'stored': list(self.stored)}
+
+    def load_state_dict(self, sd):
+        if tuple(sd['buf'].shape) != tuple(self.buf.shape) or len(sd['stored']) != self.capacity:
+            raise ValueError('DeviceEvalSnapshots: the checkpoint holds %r floats in %d slots, this one %r in %d'
+                             % (tuple(sd['buf'].shape), len(sd['stored']), tuple(self.buf.shape), self.capacity))
+        self.buf.copy_(sd['buf'])
+        self.stored = [bool(v) for v in sd['stored']]
+
+
 class DeviceTrainingMonitor(object):
     """What n TrainingTensorplexMonitor(agent_id=i) around n host envs would report, for the actors of a
     SyntheticVecEnv: on each poll(), for actor i and every training_env-th of its episodes, ':reward' (the mean of its

@@ -999,8 +999,9 @@ class SyntheticVecEnv(object):
         replay.commit_ring(rows)
         return rows
 
-    def _eval_refusal(self, agent):
-        """why the evaluation launch cannot take `agent`'s policy on this env -> (exception class, message), or None"""
+    def _eval_refusal(self, agent, population=False):
+        """why the evaluation launch cannot take `agent`'s policy on this env -> (exception class, message), or None
+        (population: the parameter sets are the attached noise's own perturbed actors, so the noise is no obstacle)"""
         m = agent.model
         ppo = hasattr(agent, 'rnn_config')
         camera = bool(m.if_pixel if ppo else m.is_pixel_input)
@@ -1011,7 +1012,7 @@ class SyntheticVecEnv(object):
                 'rnn_layer %d' % agent.rnn_config.rnn_layer
                 if ppo and agent.rnn_config.if_rnn_policy and agent.rnn_config.rnn_layer != 1 else
                 'a LayerNorm actor' if not ppo and m.use_layernorm else
-                'an attached parameter noise' if not ppo and self.param_noise is not None else None)
+                'an attached parameter noise' if not ppo and self.param_noise is not None and not population else None)
         if what is not None:
             return NotImplementedError, 'evaluate with %s: %s' % (what, only)
         if getattr(self.K, 'synth_ppo_eval' if ppo else 'synth_ddpg_eval', None) is None:
@@ -1062,11 +1063,36 @@ class SyntheticVecEnv(object):
         Pure: neither state, the clock, the attached streams' counters, the monitor, the open windows and transitions,
         agent._batch_cells nor any replay is read or written -- it can be called on the training env between chunks.
         actors_per_workgroup: 4 | 8 | 16 forces the kernel's block of rows (0: automatic; every size gives the same bits)."""
-        refusal = self._eval_refusal(agent)
+        ppo, E, resets, noise = self._eval_check(agent, episodes, resets, noise)
+        n, L_ = self.n, int(self.episode_len)
+        if out is None:
+            out = torch.empty(n, E, dtype=torch.float64, device=self.device)
+        elif out.dtype != torch.float64 or tuple(out.shape) != (n, E) or not out.is_contiguous():
+            raise ValueError('evaluate: out must be a contiguous torch.float64 [%d, %d] tensor' % (n, E))
+        m = agent.model
+        kw = dict(task=self.task, resets=resets, actors_per_workgroup=actors_per_workgroup)
+        # (packed copies of its own: the rollouts' stay as they are)
+        pk = self._packed('_epk', self.K.epoch_packed_numel(m.actor), lambda b: self.K.epoch_pack([(m.actor, b)]))
+        if not ppo:
+            self.K.synth_ddpg_eval(m.actor, pk, self.init_state, E, L_, out, **kw)
+            return out
+        lpk = None
+        if agent.rnn_config.if_rnn_policy:
+            lpk = self._packed('_elpk', self.K.lstm_rollout_packed_numel(m.rnn), lambda b: self.K.lstm_rollout_pack(m.rnn, b))
+        self.K.synth_ppo_eval(m, pk, lpk, self.init_state, E, L_, out, zfilter=m.z_filter if agent.use_z_filter else None,
+                              noise=noise, **kw)
+        return out
+
+    def _eval_check(self, agent, episodes, resets, noise, population=False, sets=1):
+        """evaluate()'s refusals, mode rule and checks of episodes / resets= / noise= / the sizes, before anything is
+        allocated or launched -> (ppo, episodes, resets, noise), the streams as the launches take them (seed, actor_base,
+        counter).  population: _eval_refusal's, and the agent's mode is not asked (the perturbed actors act on their
+        means); sets: the parameter sets of the launch (DeviceEvalSnapshots)"""
+        refusal = self._eval_refusal(agent, population)
         if refusal is not None:
             raise refusal[0](refusal[1])
         ppo = hasattr(agent, 'rnn_config')
-        mode = agent.agent_mode
+        mode = 'eval_deterministic' if population else agent.agent_mode
         if mode not in ('eval_deterministic', 'eval_deterministic_local', 'eval_stochastic', 'eval_stochastic_local'):
             raise ValueError('evaluate: agent_mode %r; an evaluation agent (eval_deterministic[_local] / '
                              'eval_stochastic[_local])' % (mode,))
@@ -1091,23 +1117,15 @@ class SyntheticVecEnv(object):
         if n * E >= 1 << 31 or E * L_ >= 1 << 31:
             raise ValueError('evaluate: %d actors x %d episodes x %d steps: n * episodes and episodes * episode_len must '
                              'stay below 2^31' % (n, E, L_))
-        if out is None:
-            out = torch.empty(n, E, dtype=torch.float64, device=self.device)
-        elif out.dtype != torch.float64 or tuple(out.shape) != (n, E) or not out.is_contiguous():
-            raise ValueError('evaluate: out must be a contiguous torch.float64 [%d, %d] tensor' % (n, E))
-        m = agent.model
-        kw = dict(task=self.task, resets=resets, actors_per_workgroup=actors_per_workgroup)
-        # (packed copies of its own: the rollouts' stay as they are)
-        pk = self._packed('_epk', self.K.epoch_packed_numel(m.actor), lambda b: self.K.epoch_pack([(m.actor, b)]))
-        if not ppo:
-            self.K.synth_ddpg_eval(m.actor, pk, self.init_state, E, L_, out, **kw)
-            return out
-        lpk = None
-        if agent.rnn_config.if_rnn_policy:
-            lpk = self._packed('_elpk', self.K.lstm_rollout_packed_numel(m.rnn), lambda b: self.K.lstm_rollout_pack(m.rnn, b))
-        self.K.synth_ppo_eval(m, pk, lpk, self.init_state, E, L_, out, zfilter=m.z_filter if agent.use_z_filter else None,
-                              noise=noise, **kw)
-        return out
+        if int(sets) * n * E >= 1 << 31:
+            raise ValueError('evaluate: %d sets x %d actors x %d episodes must stay below 2^31' % (sets, n, E))
+        return ppo, E, resets, noise
+
+    def eval_snapshots(self, agent, capacity):
+        """-> DeviceEvalSnapshots(self, agent, capacity): `capacity` parameter snapshots of `agent`'s architecture, all
+        evaluated on the same episodes in ONE launch"""
+        from .monitor import DeviceEvalSnapshots
+        return DeviceEvalSnapshots(self, agent, capacity)
 
     def _frame_pool_plan(self, replay, T, N):
         """the next T steps of the shared clock in a replay's frame pool -> {'frames': [(f, first)] before each step and

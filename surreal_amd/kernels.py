@@ -984,6 +984,86 @@ class HipKernels(object):
         p.returns = self._eval_returns(returns, n, int(episodes))
         L.call('smx_synth_ddpg_eval_f32', ctypes.byref(p), self._st())
 
+    # ---- several parameter sets in one evaluation launch (snapshots) ----
+    def eval_snapshot_floats(self, model=None, actor=None, zfilter=False):
+        """floats of one snapshot (smx_eval_snapshot_floats): model, a PPOModel (zfilter: its z-filter's sums are part of
+        the snapshot), or actor, a plain DDPG actor's Mlp3Params; 0: a policy no evaluation launch takes"""
+        if actor is not None:
+            return int(self.lib.smx_eval_snapshot_floats(1, actor.D, 0, actor.H1, actor.H2, actor.OUT, 0))
+        a = model.actor
+        if model.if_pixel or (model.if_rnn and (model.rnn_layers != 1 or a.D != model.rnn.H)):
+            return 0
+        D, H = (model.rnn.D, model.rnn.H) if model.if_rnn else (a.D, 0)
+        return int(self.lib.smx_eval_snapshot_floats(0, D, H, a.H1, a.H2, a.OUT, int(bool(zfilter))))
+
+    def eval_snapshot_store(self, blob, model=None, actor=None, zfilter=None):
+        """blob (float32, 16-byte aligned, eval_snapshot_floats long) <- the snapshot of the live parameters, no
+        synchronisation (smx_eval_snapshot_store_f32): model, a PPOModel, with zfilter its ZFilter or None; or actor, a
+        plain DDPG actor's Mlp3Params"""
+        s = L.EvalSnapshotSrc()
+        if actor is not None:
+            need = self.eval_snapshot_floats(actor=actor)
+            s.net, s.ddpg = ctypes.pointer(actor.desc), 1
+        else:
+            need = self.eval_snapshot_floats(model=model, zfilter=zfilter is not None)
+            s.net, s.log_var = ctypes.pointer(model.actor.desc), L.ptr(model.log_var)
+            if zfilter is not None:
+                s.zsum, s.zsumsq, s.zcount = L.ptr(zfilter.running_sum), L.ptr(zfilter.running_sumsq), L.ptr(zfilter.count)
+            if model.if_rnn:
+                s.lstm = ctypes.pointer(model.rnn.desc)
+        assert blob.dtype == torch.float32 and blob.is_contiguous() and blob.numel() >= need > 0
+        L.call('smx_eval_snapshot_store_f32', ctypes.byref(s), L.ptr(blob), self._st())
+
+    @staticmethod
+    def _eval_sets(blobs, sets, zfilter, returns, n, episodes):
+        """struct smx_eval_sets of the first `sets` rows of blobs [K, stride] (a row-strided float32 view), and the
+        check of returns [sets, n, episodes]"""
+        assert blobs.dtype == torch.float32 and blobs.dim() == 2 and blobs.stride(1) == 1 and blobs.shape[0] >= sets
+        assert returns.dtype == torch.float64 and returns.is_contiguous() and tuple(returns.shape) == (sets, n, episodes)
+        s = L.EvalSets()
+        s.blobs, s.stride = L.ptr(blobs), int(blobs.stride(0)) if blobs.shape[0] > 1 else int(blobs.shape[1])
+        s.sets, s.zfilter = int(sets), int(bool(zfilter))
+        return s
+
+    def synth_ppo_eval_sets(self, model, blobs, init_state, episodes, episode_len, returns, zfilter=None, task='drift',
+                            resets=None, noise=None, actors_per_workgroup=0, out_act=L.SMX_ACT_TANH):
+        """synth_ppo_eval for the blobs.shape[0] snapshots in the rows of blobs [sets, stride] in ONE launch
+        (smx_synth_ppo_eval_sets_f32): returns [sets, n, episodes] fp64.  model gives the shapes alone -- its parameters
+        are not read; zfilter: the ZFilter whose eps applies (the snapshots hold the sums), or None"""
+        n = init_state.shape[0]
+        assert init_state.is_contiguous() and init_state.dtype == torch.float32
+        p = L.SynthPpoEval()
+        p.net, p.out_act, p.n = ctypes.pointer(model.actor.desc), int(out_act), n
+        if zfilter is not None:
+            p.zeps = float(zfilter.eps)
+        p.episodes, p.episode_len, p.task = int(episodes), int(episode_len), self._task_id(task)
+        p.actors_per_workgroup = int(actors_per_workgroup)
+        if model.if_rnn:
+            p.lstm, p.hidden = ctypes.pointer(model.rnn.desc), model.rnn_hidden_logical
+        p.init_state = L.ptr(init_state)
+        if resets is not None:
+            p.resets = self._reset_args(resets)
+        p.noise = self._noise_args(noise)
+        s = self._eval_sets(blobs, blobs.shape[0], zfilter is not None, returns, n, int(episodes))
+        p.returns = L.ptr(returns)
+        L.call('smx_synth_ppo_eval_sets_f32', ctypes.byref(p), ctypes.byref(s), self._st())
+
+    def synth_ddpg_eval_sets(self, net, blobs, init_state, episodes, episode_len, returns, task='drift', resets=None,
+                             actors_per_workgroup=0):
+        """the same for plain DDPG actors of net's shapes (smx_synth_ddpg_eval_sets_f32)"""
+        n = init_state.shape[0]
+        assert init_state.is_contiguous() and init_state.dtype == torch.float32
+        p = L.SynthDdpgEval()
+        p.net, p.n = ctypes.pointer(net.desc), n
+        p.episodes, p.episode_len, p.task = int(episodes), int(episode_len), self._task_id(task)
+        p.actors_per_workgroup = int(actors_per_workgroup)
+        p.init_state = L.ptr(init_state)
+        if resets is not None:
+            p.resets = self._reset_args(resets)
+        s = self._eval_sets(blobs, blobs.shape[0], False, returns, n, int(episodes))
+        p.returns = L.ptr(returns)
+        L.call('smx_synth_ddpg_eval_sets_f32', ctypes.byref(p), ctypes.byref(s), self._st())
+
     def actor_clock_rows(self, t, episode_len, steps, n_step, advance, row_off, t_host=None, episode_len_host=None):
         """row_off [steps, n] int32 <- where every closing (step, actor) pair of a call of `steps` steps goes, counted
         from the ring's cursor in (step, actor) order, -1 where the pair closes nothing (smx_actor_clock_rows_i32): actor
