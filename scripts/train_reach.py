@@ -2,7 +2,7 @@
 
     python scripts/train_reach.py --algo ppo|ddpg [--actors N --J J --episode-len L --iters K --seed S --out FILE]
                                   [--random-resets [--heldout-episodes E]] [--eval-heldout] [--device-eval]
-                                  [--snapshot-curve]
+                                  [--snapshot-curve] [--save PATH [--save-every K]] [--resume PATH]
 
 Per iteration: one rollout chunk of all actors inside one launch (ppo_rollout_into / ddpg_rollout_into on a
 SyntheticVecEnv(task='reach') with a DeviceEpisodeMonitor and an exploration noise stream attached) -> the replay's device
@@ -31,7 +31,12 @@ episodes -- the held-out ones (resets=(S + 3, 0), --heldout-episodes per actor) 
 episode from every actor's reset state; a sampling PPO agent draws from ONE fixed noise stream (S + 4, first_step 0) for
 all snapshots, so the points are paired -- and one last line {"kind": "snapshot_curve", ...} carries the mean return per
 point.  With --device-eval and a deterministic evaluation agent every point must have the bits of the per-point device
-evaluation made during training (asserted; "bits_match": true).  Without the flag every line is unchanged."""
+evaluation made during training (asserted; "bits_match": true).  Without the flag every line is unchanged.
+--save PATH: the whole run -- env, both agents, replay, learner, the torch generators, the loop's counters and the
+baselines -- goes into ONE file (surreal_amd/utils/run_state.py; written atomically) after every K-th chunk (--save-every K)
+and after the last one.  --resume PATH: the run goes on from that file, with the same --algo / --actors / --J /
+--episode-len / --seed / reset flags (anything else: ValueError): from there on it prints exactly the lines the
+uninterrupted run prints, wall times apart -- the baseline line is not printed again.  Not with --snapshot-curve."""
 import argparse
 import json
 import os
@@ -191,6 +196,37 @@ class Loop(object):
         self.learner.publish_parameter(self.learns, message='chunk')
         self.agent.fetch_parameter()
 
+    def identity(self):
+        """what a saved run and the loop that goes on from it must share"""
+        return {'algo': self.algo, 'actors': self.n, 'J': self.J, 'episode_len': self.L, 'seed': self.seed,
+                'random_resets': self.venv.resets is not None, 'heldout': self.heldout}
+
+    def state_parts(self, **script):
+        """the parts of run_state.save_run: every holder's state (live tensors: save_run copies) and, under 'script',
+        the loop's own counters with whatever the caller adds"""
+        from surreal_amd.utils import run_state as RS
+        script = dict(script, identity=self.identity(), env_steps=self.env_steps, learns=self.learns,
+                      device_eval_steps=self.device_eval_steps)
+        return dict(env=self.venv.state_dict(), agent=self.agent.state_dict(), eval_agent=self.eval_agent.state_dict(),
+                    replay=self.replay.state_dict(), learner=self.learner.train_state_dict(),
+                    torch_rng=RS.torch_rng_state(), script=script)
+
+    def load_parts(self, parts):
+        """run_state.load_run's parts into this loop's objects (ValueError: a run of another shape) -> parts['script']"""
+        from surreal_amd.utils import run_state as RS
+        script = parts['script']
+        if script['identity'] != self.identity():
+            raise ValueError('the saved run is %r, this one %r' % (script['identity'], self.identity()))
+        self.learner.load_train_state_dict(parts['learner'])
+        self.replay.load_state_dict(parts['replay'])
+        self.venv.load_state_dict(parts['env'])
+        self.agent.load_state_dict(parts['agent'])
+        self.eval_agent.load_state_dict(parts['eval_agent'])
+        RS.set_torch_rng_state(parts['torch_rng'])
+        self.env_steps, self.learns = int(script['env_steps']), int(script['learns'])
+        self.device_eval_steps = int(script['device_eval_steps'])
+        return script
+
     def training_return(self):
         self.monitor.poll()
         return self.monitor.mean_reward(last=1)
@@ -258,26 +294,39 @@ class Loop(object):
 
 
 def train(algo, actors=64, J=2, episode_len=50, iters=None, seed=0, eval_every=10, device=None, log=print,
-          random_resets=False, heldout_episodes=4, eval_heldout=False, device_eval=False, snapshot_curve=False):
-    """-> (the baselines, the curve: one dict per evaluation).  random_resets / eval_heldout / device_eval: the module
-    docstring's"""
+          random_resets=False, heldout_episodes=4, eval_heldout=False, device_eval=False, snapshot_curve=False,
+          save=None, save_every=None, resume=None):
+    """-> (the baselines, the curve: one dict per evaluation).  random_resets / eval_heldout / device_eval / save /
+    save_every (in chunks) / resume: the module docstring's"""
+    from surreal_amd.utils import run_state as RS
     iters = DEFAULT_ITERS[algo] if iters is None else iters
     heldout = int(heldout_episodes) if (random_resets or eval_heldout) else 0
-    if heldout:
+    if snapshot_curve and (save or resume):
+        raise ValueError('--snapshot-curve keeps its snapshots outside the saved run: not with --save / --resume')
+    if save_every is not None and (not save or int(save_every) < 1):
+        raise ValueError('--save-every K: a positive number of chunks, with --save PATH')
+    parts = RS.load_run(resume) if resume else None
+    if parts is not None:
+        base = parts['script']['base']               # (the baselines of the saved run: not computed, not printed again)
+    elif heldout:
         base = dict(heldout_baselines(J, episode_len, actors, seed + 3, heldout), algo=algo, actors=actors, J=J,
                     episode_len=episode_len, iters=iters, seed=seed, random_resets=bool(random_resets),
                     heldout_episodes=heldout)
     else:
         base = dict(baselines(J, episode_len, range(actors)), algo=algo, actors=actors, J=J, episode_len=episode_len,
                     iters=iters, seed=seed)
-    log(json.dumps(base))
+    if parts is None:
+        log(json.dumps(base))
     loop = Loop(algo, actors, J, episode_len, seed, device, random_resets=random_resets, heldout=heldout)
+    first = int(loop.load_parts(parts)['iteration']) if parts is not None else 0
+    if first > iters:
+        raise ValueError('the saved run has done %d chunks, --iters is %d' % (first, iters))
     gap = base['pd_return'] - base['zero_action_return']
     curve, t0 = [], time.time()
     points = [it for it in range(iters + 1) if it % eval_every == 0 or it == iters]
     snaps = loop.venv.eval_snapshots(loop.eval_agent, len(points)) if snapshot_curve else None
     per_point = []                                   # (--device-eval: the per-point launches' returns, on the device)
-    for it in range(iters + 1):
+    for it in range(first, iters + 1):
         if it % eval_every == 0 or it == iters:
             extra = {}
             if device_eval:
@@ -300,6 +349,8 @@ def train(algo, actors=64, J=2, episode_len=50, iters=None, seed=0, eval_every=1
                     per_point.append(loop.last_device_returns)
         if it < iters:
             loop.iterate()
+            if save and (it + 1 == iters or (save_every is not None and (it + 1) % int(save_every) == 0)):
+                RS.save_run(save, **loop.state_parts(iteration=it + 1, base=base))
     if snaps is not None:
         E, kw = loop.snapshot_curve_args()
         t1 = time.time()
@@ -335,6 +386,10 @@ def main():
                     'lines also carry the per-step figure')
     ap.add_argument('--snapshot-curve', action='store_true', help='store a parameter snapshot at every evaluation point '
                     'and evaluate all of them in one launch after training')
+    ap.add_argument('--save', default=None, metavar='PATH', help='write the whole run into this file after the last '
+                    'chunk (and after every K-th: --save-every)')
+    ap.add_argument('--save-every', type=int, default=None, metavar='K', help='also save after every K-th chunk')
+    ap.add_argument('--resume', default=None, metavar='PATH', help='go on from a file written by --save')
     args = ap.parse_args()
     lines = []
 
@@ -343,7 +398,8 @@ def main():
         lines.append(s)
     train(args.algo, args.actors, args.J, args.episode_len, args.iters, args.seed, args.eval_every, log=log,
           random_resets=args.random_resets, heldout_episodes=args.heldout_episodes, eval_heldout=args.eval_heldout,
-          device_eval=args.device_eval, snapshot_curve=args.snapshot_curve)
+          device_eval=args.device_eval, snapshot_curve=args.snapshot_curve, save=args.save, save_every=args.save_every,
+          resume=args.resume)
     if args.out:
         with open(args.out, 'a') as f:
             f.write('\n'.join(lines) + '\n')

@@ -151,6 +151,58 @@ class Agent(object, metaclass=AutoInitializeMeta):
     def fetch_parameter_info(self):
         return None if self._published is None else self._published[1]
 
+    # ---- the agent's state (utils/run_state.py) ----------------------------------------------------------------------
+    def _camera_agent(self):
+        return bool(getattr(self.model, 'if_pixel', False) or getattr(self.model, 'is_pixel_input', False))
+
+    def _state_refusal(self, who):
+        if self._camera_agent():
+            raise NotImplementedError('%s: a camera agent (the camera envs\' state is not carried either)' % who)
+        if getattr(self, '_param_client', None) is not None:
+            raise NotImplementedError('%s: an agent that fetches through a parameter client' % who)
+
+    def state_dict(self):
+        """The agent's OWN copy of the parameters -- between the learner's publish and its fetch it lags the learner --
+        as LIVE tensors (run_state.model_tensors), and the in-process hand-off: the publish it fetched last and the
+        snapshot published last (a fetch after the resume loads what a fetch in the uninterrupted run loads, or nothing).
+        Not carried: the batch-1 act() path's host state (cells, the host action-noise process) and the counters of
+        the episode loop.  A camera agent: NotImplementedError."""
+        self._state_refusal('%s.state_dict' % type(self).__name__)
+        from surreal_amd.utils.run_state import model_tensors
+        published = None
+        if self._published is not None:
+            snap, info = self._published
+            published = {'modules': {name: dict(sd) for name, sd in snap.items()},
+                         'info': {k: info.get(k) for k in ('iteration', 'message', 'publish_seq')}}
+        return {'model': model_tensors(self.model), 'fetched': self._fetched_iteration, 'published': published}
+
+    def _check_state_dict(self, sd):
+        from surreal_amd.utils.run_state import check_tensors, model_tensors
+        who = '%s.load_state_dict' % type(self).__name__
+        self._state_refusal(who)
+        check_tensors(who, sd['model'], model_tensors(self.model))
+        if sd['published'] is not None:
+            mine = {name: m.state_dict() for name, m in self._module_dict.items()}
+            theirs = sd['published']['modules']
+            if sorted(theirs) != sorted(mine):
+                raise ValueError('%s: the published snapshot holds the modules %r, this agent %r'
+                                 % (who, sorted(theirs), sorted(mine)))
+            for name in mine:
+                check_tensors('%s (the published %r)' % (who, name), theirs[name], dict(mine[name]))
+
+    def load_state_dict(self, sd):
+        """state_dict()'s, back: the parameters in place.  ValueError before anything is written when the model's
+        buffers or the published snapshot's entries differ in name, shape or dtype"""
+        from surreal_amd.utils.run_state import load_tensors, model_tensors
+        self._check_state_dict(sd)
+        load_tensors(sd['model'], model_tensors(self.model))
+        self._fetched_iteration = sd['fetched']
+        self._published = None
+        if sd['published'] is not None:
+            snap = {name: {k: (v.to(self.device, copy=True) if hasattr(v, 'to') else v) for k, v in m.items()}
+                    for name, m in sd['published']['modules'].items()}
+            self._published = (snap, dict(sd['published']['info'], time=time.time(), _snapshot=snap))
+
     # ---- hooks (agent/base.py:182-222) -----------------------------------------------------------
     def pre_action(self, obs):
         if self.agent_mode == 'training':

@@ -141,6 +141,15 @@ class DDPGAgent(Agent):
     def module_dict(self, model=None):
         return {'ddpg': self.model if model is None else model}
 
+    def _state_refusal(self, who):
+        """state_dict() / load_state_dict() (Agent): also refused while the parameter-space noise is made on the host --
+        it draws from numpy's global stream at every fetch, which no file of this package carries; on the device
+        (SyntheticVecEnv.attach_param_noise) it is the env's state"""
+        super()._state_refusal(who)
+        if self.param_noise and not self.device_param_noise:
+            raise NotImplementedError('%s: host parameter-space noise (numpy\'s global stream); attach_param_noise makes '
+                                      'it on the device' % who)
+
     def pre_episode(self):                                # ddpg_agent.py:205-208
         super().pre_episode()
         if self.agent_mode not in ['eval_deterministic', 'eval_deterministic_local']:

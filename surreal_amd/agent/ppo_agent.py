@@ -187,6 +187,24 @@ class PPOAgent(Agent):
         keep = (~mask).to(torch.float32).view(1, -1, 1)
         self._batch_cells = (self._batch_cells[0] * keep, self._batch_cells[1] * keep)
 
+    def state_dict(self):
+        """Agent.state_dict, and for an LSTM policy the held batch cells (_batch_cells: the (h, c) every actor goes on
+        from, None before the first step)"""
+        sd = super().state_dict()
+        sd['batch_cells'] = None if self._batch_cells is None else list(self._batch_cells)
+        return sd
+
+    def load_state_dict(self, sd):
+        cells = sd['batch_cells']
+        if cells is not None:
+            ok = self.rnn_config.if_rnn_policy and len(cells) == 2 and all(
+                c.dim() == 3 and tuple(c.shape[::2]) == (self.rnn_config.rnn_layer, self.rnn_config.rnn_hidden)
+                for c in cells)
+            if not ok:
+                raise ValueError('PPOAgent.load_state_dict: the saved batch cells do not fit this policy')
+        super().load_state_dict(sd)
+        self._batch_cells = None if cells is None else tuple(c.to(self.device, copy=True) for c in cells)
+
     def set_experience_sink(self, sink):
         """where windowed experiences go: normally ``replay._insert_wrapper``"""
         self.sink = sink

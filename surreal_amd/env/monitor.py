@@ -268,6 +268,28 @@ class DeviceEpisodeMonitor(object):
         xs = [r for per_actor in self.episode_rewards for r in per_actor[-int(last):]]
         return _mean(xs) if xs else None
 
+    def state_dict(self):
+        """the device words (the one LIVE buffer: open episodes, counts and rings) and what poll() keeps on the host"""
+        return {'n': self.n, 'capacity': self.capacity, 'buf': self._buf,
+                'episode_rewards': [list(x) for x in self.episode_rewards],
+                'episode_steps': [list(x) for x in self.episode_steps], 'counts': list(self.counts),
+                'dropped_by_actor': list(self.dropped_by_actor), 'total_steps': self.total_steps,
+                'steps_per_actor': self.steps_per_actor}
+
+    def check_state_dict(self, sd):
+        if (int(sd['n']), int(sd['capacity'])) != (self.n, self.capacity) or tuple(sd['buf'].shape) != tuple(self._buf.shape):
+            raise ValueError('DeviceEpisodeMonitor: the state is of %d actors with rings of %d, this monitor of %d with %d'
+                             % (int(sd['n']), int(sd['capacity']), self.n, self.capacity))
+
+    def load_state_dict(self, sd):
+        self.check_state_dict(sd)
+        self._buf.copy_(sd['buf'])
+        self.episode_rewards = [[float(r) for r in x] for x in sd['episode_rewards']]
+        self.episode_steps = [[int(s) for s in x] for x in sd['episode_steps']]
+        self.counts = [int(c) for c in sd['counts']]
+        self.dropped_by_actor = [int(c) for c in sd['dropped_by_actor']]
+        self.total_steps, self.steps_per_actor = int(sd['total_steps']), int(sd['steps_per_actor'])
+
 
 class DeviceNoise(object):
     """The exploration noise of a SyntheticVecEnv's actors as a counter-based stream (struct smx_noise_stream,
@@ -299,6 +321,20 @@ class DeviceNoise(object):
         out = torch.empty(int(T), self.n if n is None else int(n), self.A if A is None else int(A), device=self.device)
         self.K.noise_fill(self.at(), out)
         return out
+
+    def state_dict(self):
+        return {'seed': self.seed, 'actor_base': self.actor_base, 'step': self.step}
+
+    def check_state_dict(self, sd):
+        if int(sd['seed']) != self.seed or int(sd['actor_base']) != self.actor_base:
+            raise ValueError('DeviceNoise: the state is of stream (seed %d, actor_base %d), this one of (%d, %d)'
+                             % (int(sd['seed']), int(sd['actor_base']), self.seed, self.actor_base))
+        if int(sd['step']) < 0:
+            raise ValueError('DeviceNoise: step %d is negative' % int(sd['step']))
+
+    def load_state_dict(self, sd):
+        self.check_state_dict(sd)
+        self.step = int(sd['step'])
 
 
 class DeviceResets(object):
@@ -344,6 +380,14 @@ class DeviceResets(object):
 
     def state_dict(self):
         return {'seed': self.seed, 'actor_base': self.actor_base, 'episode': self.episode}
+
+    def check_state_dict(self, sd):
+        """load_state_dict's refusals alone: nothing is written"""
+        if int(sd['seed']) != self.seed or int(sd['actor_base']) != self.actor_base:
+            raise ValueError('DeviceResets: the checkpoint is of stream (seed %d, actor_base %d), this one of (%d, %d)'
+                             % (int(sd['seed']), int(sd['actor_base']), self.seed, self.actor_base))
+        if int(sd['episode']) < 0:
+            raise ValueError('DeviceResets: episode %d is negative' % int(sd['episode']))
 
     def load_state_dict(self, sd):
         if int(sd['seed']) != self.seed or int(sd['actor_base']) != self.actor_base:
@@ -444,6 +488,16 @@ class DeviceParamNoise(object):
     def state_dict(self):
         return {'sigma': self.sigma.cpu(), 'dist': self.dist.cpu(), 'pop': self.pop.cpu(),
                 'generation': self.generation, 'acts': self.acts}
+
+    def check_state_dict(self, sd):
+        """ValueError unless the state fits this population (agents, copy size): nothing is written"""
+        for k in ('sigma', 'dist', 'pop'):
+            have = getattr(self, k)
+            if tuple(sd[k].shape) != tuple(have.shape) or sd[k].dtype != have.dtype:
+                raise ValueError('DeviceParamNoise: the saved %s is %s %s, this population\'s %s %s'
+                                 % (k, tuple(sd[k].shape), sd[k].dtype, tuple(have.shape), have.dtype))
+        if not -1 <= int(sd['generation']) < 1 << 32 or int(sd['acts']) < 0:
+            raise ValueError('DeviceParamNoise: generation %d, acts %d' % (int(sd['generation']), int(sd['acts'])))
 
     def load_state_dict(self, sd):
         for k in ('sigma', 'dist', 'pop'):

@@ -349,6 +349,100 @@ class SyntheticVecEnv(object):
         self._ppo = {}                        # (the open windows: a new episode has none)
         return self.state
 
+    # ---- the env's state (utils/run_state.py) ----------------------------------------------------------------------
+    _ATTACHMENTS = ('noise', 'resets', 'monitor', 'param_noise')
+
+    def _state_refusal(self, who):
+        if self.pixel is not None:
+            raise NotImplementedError('%s: a camera env: its frame histories (and a replay\'s frame pool) are not carried'
+                                      % who)
+
+    def state_dict(self):
+        """What the next ppo_rollout_into / ddpg_rollout_into / step reads, as LIVE tensors (run_state.to_host / save_run
+        make the host copy): `state`; the clock `t` (an int, or int32 [n] with per-actor clocks); the open PPO windows
+        (_ppo: key, every carry tensor, t) and the open DDPG transitions and fp64 OU states (_ddpg: n_step, carry_obs /
+        carry_act / carry_rew, ou); under their own keys the states of what is attached -- 'noise', 'resets', 'monitor',
+        'param_noise', None where nothing is --; and a fingerprint: n, D, A, task, episode_len and init_state.
+        Derived, so rebuilt and not stored: the device copies of the clocks (_clk), gamma's powers and the packed
+        parameter copies (they follow the agent at every call).
+        NOT carried: the recording table of start_rollout() / rollout() / emit_windows() (rolls, slot): a recorded
+        rollout is one episode segment that starts after a reset; finish it before saving.
+        A camera env: NotImplementedError."""
+        self._state_refusal('SyntheticVecEnv.state_dict')
+        ppo = None
+        if self._ppo.get('key') is not None:
+            ppo = {'key': list(self._ppo['key']), 'carry': dict(self._ppo['carry']), 't': self._ppo.get('t')}
+        ddpg = None
+        if self._ddpg.get('n_step') is not None:
+            ddpg = {k: self._ddpg[k] for k in ('n_step', 'carry_obs', 'carry_act', 'carry_rew', 'ou')}
+        sd = {'fingerprint': {'n': self.n, 'D': self.D, 'A': self.A, 'task': self.task, 'episode_len': self.episode_len,
+                              'init_state': self.init_state},
+              'state': self.state, 't': self.t, 'ppo': ppo, 'ddpg': ddpg}
+        for k in self._ATTACHMENTS:
+            part = getattr(self, k)
+            sd[k] = None if part is None else part.state_dict()
+        return sd
+
+    def load_state_dict(self, sd):
+        """state_dict()'s, back: `state` in place, the clock, the open windows and transitions; the attachments load
+        their own.  ValueError -- before anything is written -- when the fingerprint differs (n, D, A, task,
+        episode_len, the bytes of init_state), when something is attached on one side only, or when an attachment
+        refuses its state (another stream seed, another monitor capacity, ...).  A camera env: NotImplementedError."""
+        who = 'SyntheticVecEnv.load_state_dict'
+        self._state_refusal(who)
+        fp = sd['fingerprint']
+        for k in ('n', 'D', 'A', 'task'):
+            if fp[k] != getattr(self, k):
+                raise ValueError('%s: the state is of an env with %s = %r, this one has %r' % (who, k, fp[k], getattr(self, k)))
+        is_array = lambda v: torch.is_tensor(v) or isinstance(v, np.ndarray)  # noqa: E731
+        as_np = lambda v: v.cpu().numpy() if torch.is_tensor(v) else np.asarray(v)  # noqa: E731
+        lens = fp['episode_len']
+        if is_array(lens) != self.per_actor_clocks or not np.array_equal(as_np(lens), self.episode_len):
+            raise ValueError('%s: the state is of episode_len %s, this env of %s'
+                             % (who, as_np(lens).tolist(), np.asarray(self.episode_len).tolist()))
+        init = fp['init_state']
+        if tuple(init.shape) != tuple(self.init_state.shape) or not torch.equal(init.to(self.init_state.device), self.init_state):
+            raise ValueError('%s: the state is of an env with another init_state (other seeds)' % who)
+        for k in self._ATTACHMENTS:
+            part = getattr(self, k)
+            if (part is None) != (sd.get(k) is None):
+                raise ValueError('%s: %s is attached %s' % (who, k, 'to the saved env only' if part is None else
+                                                            'to this env only'))
+            if part is not None:
+                part.check_state_dict(sd[k])
+        n = self.n
+        if tuple(sd['state'].shape) != tuple(self.state.shape):
+            raise ValueError('%s: the saved state is %s' % (who, tuple(sd['state'].shape)))
+        t = sd['t']
+        if is_array(t) != self.per_actor_clocks or (self.per_actor_clocks and tuple(t.shape) != (n,)):
+            raise ValueError('%s: the saved clock does not fit %s' % (who, 'per-actor clocks' if self.per_actor_clocks
+                                                                       else 'one shared clock'))
+        for part, names in ((sd['ppo'], None), (sd['ddpg'], ('carry_obs', 'carry_act', 'carry_rew', 'ou'))):
+            tensors = {} if part is None else part['carry'] if names is None else {k: part[k] for k in names}
+            for k, v in tensors.items():
+                if not torch.is_tensor(v) or v.shape[0] != n:
+                    raise ValueError('%s: the saved %s does not hold %d actors' % (who, k, n))
+        # ---- everything fits: write ----
+        clock = lambda v: np.array(as_np(v), dtype=np.int32) if is_array(v) else (None if v is None else int(v))  # noqa: E731
+        dev = self.device
+        self.state.copy_(sd['state'])
+        self.t = clock(t)
+        if self.per_actor_clocks:
+            self._clk = {}                       # (the device copies: made again by the next call)
+        self._ppo = {}
+        if sd['ppo'] is not None:
+            p = sd['ppo']
+            self._ppo = {'key': tuple(tuple(v) if isinstance(v, list) else v for v in p['key']),
+                         'carry': {k: v.to(dev, copy=True) for k, v in p['carry'].items()}, 't': clock(p['t'])}
+        self._ddpg = {}
+        if sd['ddpg'] is not None:
+            d = sd['ddpg']
+            self._ddpg = {'n_step': int(d['n_step']), 'hist': None}
+            self._ddpg.update({k: d[k].to(dev, copy=True) for k in ('carry_obs', 'carry_act', 'carry_rew', 'ou')})
+        for k in self._ATTACHMENTS:
+            if getattr(self, k) is not None:
+                getattr(self, k).load_state_dict(sd[k])
+
     def _clock_walk(self, k):
         """the shared clock at each of the next k steps and after them (k + 1 values): an episode ends at episode_len"""
         ts = [self.t]

@@ -654,7 +654,7 @@ class DDPGLearner(Learner):
         ws = self._workspace(B, D)
         if ws.dev_step != self.critic_step:          # restored from a checkpoint
             ws.step.fill_(self.critic_step)
-            ws.rows_versions = None
+            self.invalidate_packed()
         if ws.lr_host != (self.lr_actor, self.lr_critic):
             ws.lr_host = (self.lr_actor, self.lr_critic)
             ws.lr.copy_(torch.tensor(ws.lr_host, dtype=torch.float32))
@@ -796,6 +796,90 @@ class DDPGLearner(Learner):
 
     def checkpoint_attributes(self):
         return ['current_iteration', 'model', 'model_target']
+
+    # ---- the whole training state (utils/run_state.py); the reference-format checkpoint above stays what it is ---------
+    def invalidate_packed(self):
+        """The row schedule's fragment-order weight copies (ws.rows_packed) follow the parameters through the update
+        launches alone; a write from outside is noticed only through torch's write counters (_rows_versions).  A writer
+        that does not move them -- raw pointers: a ctypes / hipMemcpy loader, a DLPack or numpy alias, a peer or IPC
+        broadcast -- MUST call this after writing model, model_target (model2, model_target2): the next iteration then
+        packs every network again.  load_train_state_dict and the checkpoint-restore path call it."""
+        if self._ws is not None:
+            self._ws.rows_versions = None
+
+    def _train_tensors(self):
+        """every device tensor that decides the next learn(), LIVE, by name: the models and targets (TD3: the second
+        critic and its target) and every Adam moment group"""
+        from surreal_amd.utils.run_state import model_tensors
+        out = {}
+        models = [('model', self.model), ('model_target', self.model_target)]
+        moments = [('actor', (self.actor_exp_avg, self.actor_exp_avg_sq)),
+                   ('critic', (self.critic_exp_avg, self.critic_exp_avg_sq)), ('perception', self.perception_moments)]
+        if self.use_double_critic:
+            models += [('model2', self.model2), ('model_target2', self.model_target2)]
+            moments += [('critic2', self.critic2_moments), ('perception2', self.perception2_moments)]
+        for name, m in models:
+            for k, v in model_tensors(m).items():
+                out['%s.%s' % (name, k)] = v
+        for name, pair in moments:
+            if pair is not None and pair[0] is not None:
+                out['%s.exp_avg' % name], out['%s.exp_avg_sq' % name] = pair
+        return out
+
+    _TRAIN_WORDS = ('current_iteration', 'current_iter', 'actor_step', 'critic_step', 'lr_actor', 'lr_critic')
+
+    def _train_state_refusal(self, who):
+        if self.world_size > 1:
+            raise NotImplementedError('%s: %d ranks; one rank only' % (who, self.world_size))
+
+    def train_state_dict(self):
+        """Everything that decides the bytes of the next learn(), as LIVE tensors (run_state.to_host / save_run make
+        the host copy): the models and their targets, TD3's second critic and its target, every Adam moment group (the
+        second critic's and the perception CNNs' included), actor_step / critic_step (the device step word ws.step is
+        derived from critic_step), the learning rates, current_iteration, the hard update's counter, the publish
+        counter, and the key of the workspace.  Not carried: the numpy global stream TD3's action regularisation draws
+        from, the scalar history.  Several ranks: NotImplementedError."""
+        self._train_state_refusal('DDPGLearner.train_state_dict')
+        words = {k: getattr(self, k) for k in self._TRAIN_WORDS}
+        words['publish_seq'] = int(getattr(self, '_publish_seq', 0))
+        if self.target_update_type == 'hard':
+            words['target_update_counter'] = int(self.target_update_counter)
+        return {'kind': 'DDPGLearner', 'tensors': self._train_tensors(), 'words': words,
+                'workspace': None if self._ws is None else list(self._ws.key)}
+
+    def load_train_state_dict(self, sd):
+        """train_state_dict()'s, back, IN PLACE (copy_ into the existing tensors: a captured hipGraph stays valid; a
+        workspace that does not exist yet is built first).  Afterwards the device step word equals critic_step -- the
+        statistics slot parity (critic_step & 1) agrees with it, both come from the one value --, the learning-rate
+        words are the saved ones and the packed row weights are invalidated.  ValueError before anything is written when
+        a tensor's name, shape or dtype differs; several ranks: NotImplementedError."""
+        from surreal_amd.utils.run_state import check_tensors, load_tensors
+        who = 'DDPGLearner.load_train_state_dict'
+        self._train_state_refusal(who)
+        if sd.get('kind') != 'DDPGLearner':
+            raise ValueError('%s: the state is of a %s' % (who, sd.get('kind')))
+        live = self._train_tensors()
+        check_tensors(who, sd['tensors'], live)
+        words = sd['words']
+        if ('target_update_counter' in words) != (self.target_update_type == 'hard'):
+            raise ValueError('%s: the state is of a %s target update, this learner\'s is %s'
+                             % (who, 'hard' if 'target_update_counter' in words else 'soft', self.target_update_type))
+        self._flush_stats()                          # (a read-back in flight belongs to the state that goes)
+        load_tensors(sd['tensors'], live)
+        for k in self._TRAIN_WORDS:
+            setattr(self, k, type(getattr(self, k))(words[k]))
+        self._publish_seq = int(words['publish_seq'])
+        if self.target_update_type == 'hard':
+            self.target_update_counter = int(words['target_update_counter'])
+        if self._ws is None and sd.get('workspace') is not None:
+            self._workspace(*(int(v) for v in sd['workspace']))
+        ws = self._ws
+        if ws is not None:
+            ws.step.fill_(self.critic_step)
+            ws.dev_step = self.critic_step
+            ws.lr_host = (self.lr_actor, self.lr_critic)
+            ws.lr.copy_(torch.tensor(ws.lr_host, dtype=torch.float32))
+        self.invalidate_packed()
 
     def _prefetcher_preprocess(self, batch):
         if not self.frame_stack_concatenate_on_env:        # ddpg.py:430-440

@@ -1528,6 +1528,93 @@ class PPOLearner(Learner):
         return ['model', 'ref_target_model', 'actor_lr_scheduler', 'critic_lr_scheduler',
                 'current_iteration']
 
+    # ---- the whole training state (utils/run_state.py); the reference-format checkpoint above stays what it is ---------
+    def _train_tensors(self):
+        """every device tensor that decides the next learn(), LIVE, by name: the model and the reference policy (their
+        z-filter sums with them), the two Adam moment groups, and -- once a workspace exists -- the two device words of
+        the optimisers' step counts and the reward filter's {count, running_sum, running_sumsq}"""
+        from surreal_amd.utils.run_state import model_tensors
+        out = {}
+        for name, m in (('model', self.model), ('ref_target_model', self.ref_target_model)):
+            for k, v in model_tensors(m).items():
+                out['%s.%s' % (name, k)] = v
+        for k in ('actor_exp_avg', 'actor_exp_avg_sq', 'critic_exp_avg', 'critic_exp_avg_sq'):
+            out[k] = getattr(self, k)
+        ws = self._ws
+        if ws is not None:
+            out['adam_steps'] = ws.ctrl_i[L.C_STEP_ACTOR:L.C_STEP_CRITIC + 1]
+            out['rf_state'] = ws.rf_state
+        return out
+
+    _TRAIN_WORDS = ('current_iteration', 'current_iter', 'global_step', 'exp_counter')
+
+    def _train_state_refusal(self, who):
+        if self.world_size > 1:
+            raise NotImplementedError('%s: %d ranks; one rank only' % (who, self.world_size))
+
+    def train_state_dict(self):
+        """Everything that decides the bytes of the next learn(), as LIVE tensors (run_state.to_host / save_run make
+        the host copy): model and ref_target_model with their z-filter sums, the Adam moments of both groups, the device
+        words of the two optimisers' step counts, the reward filter's state, the two lr schedulers, beta or clip_epsilon,
+        kl_record, exp_counter, current_iteration / global_step, the publish counter, and the key of the workspace.
+        The control words the kernels read (ws.ctrl_f: learning rates, beta, clip_epsilon) are derived from these and
+        written again by the next learn().  Several ranks: NotImplementedError."""
+        self._train_state_refusal('PPOLearner.train_state_dict')
+        words = {k: int(getattr(self, k)) for k in self._TRAIN_WORDS}
+        words['publish_seq'] = int(getattr(self, '_publish_seq', 0))
+        words['kl_record'] = [float(v) for v in self.kl_record]              # (the property waits for a read-back in flight)
+        words['beta' if self.ppo_mode == 'adapt' else 'clip_epsilon'] = float(
+            self.beta if self.ppo_mode == 'adapt' else self.clip_epsilon)
+        words['actor_lr_scheduler'] = self.actor_lr_scheduler.state_dict()
+        words['critic_lr_scheduler'] = self.critic_lr_scheduler.state_dict()
+        key = None
+        if self._ws is not None:
+            key = [v if v is None or isinstance(v, int) else str(v) for v in self._ws.key]
+        return {'kind': 'PPOLearner', 'ppo_mode': self.ppo_mode, 'tensors': self._train_tensors(), 'words': words,
+                'workspace': key}
+
+    def load_train_state_dict(self, sd):
+        """train_state_dict()'s, back, IN PLACE (copy_ into the existing tensors: the captured hipGraphs stay valid; a
+        workspace that does not exist yet is built first, from the saved key).  The control words are pushed again by
+        the next learn().  ValueError before anything is written when the mode or a tensor's name, shape or dtype
+        differs; several ranks: NotImplementedError."""
+        from surreal_amd.utils.run_state import check_tensors, load_tensors
+        who = 'PPOLearner.load_train_state_dict'
+        self._train_state_refusal(who)
+        if sd.get('kind') != 'PPOLearner' or sd.get('ppo_mode') != self.ppo_mode:
+            raise ValueError('%s: the state is of a %s in mode %r, this is a PPOLearner in mode %r'
+                             % (who, sd.get('kind'), sd.get('ppo_mode'), self.ppo_mode))
+        saved, key = sd['tensors'], sd.get('workspace')
+        device_words = ('adam_steps', 'rf_state')
+        live = self._train_tensors()
+        check_tensors(who, {k: v for k, v in saved.items() if k not in device_words},
+                      {k: v for k, v in live.items() if k not in device_words})
+        if ('adam_steps' in saved) != (key is not None):
+            raise ValueError('%s: the state holds device words without a workspace key (or the reverse)' % who)
+        self._flush_stats()                          # (a read-back in flight belongs to the state that goes)
+        if self._ws is None and key is not None:
+            dtype = key[4] if key[4] is None else getattr(torch, str(key[4]).split('.')[-1])
+            self._workspace(*(int(v) for v in key[:4]), dtype)
+            live = self._train_tensors()
+        ws = self._ws
+        if ws is not None and key is None:
+            # the state of a learner that never learned, into one that has: the words as a new workspace has them
+            ws.ctrl_i[L.C_STEP_ACTOR:L.C_STEP_CRITIC + 1].zero_()
+            ws.rf_state.copy_(torch.tensor([1e-5, 0.0, 0.0]))
+        load_tensors(saved, {k: v for k, v in live.items() if k in saved})
+        words = sd['words']
+        for k in self._TRAIN_WORDS:
+            setattr(self, k, int(words[k]))
+        self._publish_seq = int(words['publish_seq'])
+        self.kl_record = [float(v) for v in words['kl_record']]
+        if self.ppo_mode == 'adapt':
+            self.beta = float(words['beta'])
+        else:
+            self.clip_epsilon = float(words['clip_epsilon'])
+        self.actor_lr_scheduler.load_state_dict(words['actor_lr_scheduler'])
+        self.critic_lr_scheduler.load_state_dict(words['critic_lr_scheduler'])
+        self._ctrl_host = None                       # (the control words: pushed again by the next learn)
+
     def _prefetcher_preprocess(self, batch, out=None):
         return self.aggregator.aggregate(batch, out=out)
     _prefetcher_preprocess.accepts_out = True       # (LearnerDataPrefetcher: aggregate straight into pinned staging)

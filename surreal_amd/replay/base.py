@@ -124,6 +124,68 @@ class Replay(object):
             'report_interval_s': dt,
         }
 
+    # ---- the device tier's state (utils/run_state.py) ----------------------------------------------
+    _state_cursors = ()          # the subclass's cursor / count attributes, all ints
+
+    def _state_capacity(self):
+        """the rows of a device table of this replay"""
+        raise NotImplementedError
+
+    def _state_refusals(self, who):
+        if getattr(self, 'frame_pool_on', False):
+            raise NotImplementedError('%s: a frame-pool replay (replay.device_frame_pool): its pool and ledger are not '
+                                      'carried' % who)
+        if len(getattr(self, '_memory', ())):
+            raise ValueError('%s: the host tier holds %d experiences; it is not carried (the device tier only)'
+                             % (who, len(self._memory)))
+
+    def state_dict(self):
+        """the device tier: every table in full (the LIVE tensors: run_state.to_host / save_run make the host copy), the
+        cursors and counts, the cumulative counters.  NotImplementedError for a frame-pool replay, ValueError while the
+        host tier holds experiences (it is not carried)."""
+        self._state_refusals('state_dict')
+        tables = None
+        if self._tables is not None:
+            tables = {k: {'shape': list(t.shape), 'data': t.data} for k, t in self._tables.items()}
+        return {'kind': type(self).__name__, 'memory_size': int(self.memory_size), 'tables': tables,
+                'cursors': {k: int(getattr(self, k)) for k in self._state_cursors},
+                'counters': {k: int(getattr(self, k)) for k in ('cumulative_collected_count', 'cumulative_sampled_count',
+                                                                'cumulative_request_count')}}
+
+    def load_state_dict(self, sd):
+        """state_dict()'s, back.  Tables that exist are written in place (they keep their addresses: views and captured
+        graphs stay valid); a replay that has none yet reserves them through reserve_ring with the saved shapes and
+        dtypes.  ValueError -- before anything is written -- when the kind, memory_size, the fields, their shapes or
+        dtypes differ or the host tier holds experiences; NotImplementedError for a frame-pool replay."""
+        who = '%s.load_state_dict' % type(self).__name__
+        self._state_refusals(who)
+        if sd.get('kind') != type(self).__name__ or int(sd['memory_size']) != int(self.memory_size):
+            raise ValueError('%s: the state is of a %s of memory_size %s, this is a %s of %d'
+                             % (who, sd.get('kind'), sd.get('memory_size'), type(self).__name__, self.memory_size))
+        if sorted(sd['cursors']) != sorted(self._state_cursors):
+            raise ValueError('%s: the state holds the cursors %r, this replay %r'
+                             % (who, sorted(sd['cursors']), sorted(self._state_cursors)))
+        saved, cap = sd['tables'], self._state_capacity()
+        for k, t in (saved or {}).items():
+            width = int(torch.Size(t['shape']).numel())
+            if tuple(t['data'].shape) != (cap, width) or t['data'].dtype != table_dtype(t['data'].dtype):
+                raise ValueError('%s: the saved table %r is %s %s, a table of this replay has %d rows of %d'
+                                 % (who, k, tuple(t['data'].shape), t['data'].dtype, cap, width))
+        if self._tables is not None:
+            mine = {k: (t.shape, t.dtype) for k, t in self._tables.items()}
+            theirs = {k: (tuple(t['shape']), t['data'].dtype) for k, t in (saved or {}).items()}
+            if mine != theirs:
+                raise ValueError('%s: the saved fields %r do not match the replay tables %r' % (who, theirs, mine))
+        elif saved:
+            self.reserve_ring(0, {k: tuple(t['shape']) for k, t in saved.items()},
+                              {k: t['data'].dtype for k, t in saved.items()})
+        for k, t in (saved or {}).items():
+            self._tables[k].data.copy_(t['data'])
+        for k, v in sd['cursors'].items():
+            setattr(self, k, int(v))
+        for k, v in sd['counters'].items():
+            setattr(self, k, int(v))
+
     # ---- device tier helpers ---------------------------------------------------------------
     def _ensure_tables(self, capacity, fields):
         if self._tables is None:

@@ -27,6 +27,12 @@ class FIFOReplay(Replay):
         self._head = 0
         self._count = 0
 
+    # state_dict() / load_state_dict() (Replay): the tables, head and count of the device ring
+    _state_cursors = ('_head', '_count')
+
+    def _state_capacity(self):
+        return self.memory_size + 3
+
     # ---- host tier: the reference semantics ---------------------------------------------
     def insert(self, exp_tuple):
         self._memory.append(exp_tuple)

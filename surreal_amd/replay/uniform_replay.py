@@ -28,6 +28,13 @@ class UniformReplay(Replay):
         self.frame_pool_on = bool(self.learner_config.replay.get('device_frame_pool', False))
         self.frame_pool = None                   # (created by the first reserve_frame_pool)
 
+    # state_dict() / load_state_dict() (Replay): the tables, the ring cursor and length, the sampling stream's seed and
+    # its Philox draw counter -- the next sample_batch draws what the saved replay would have drawn
+    _state_cursors = ('_dev_len', '_dev_next', '_draws', 'seed')
+
+    def _state_capacity(self):
+        return self.memory_size
+
     # ---- host tier: the reference semantics ---------------------------------------------
     def insert(self, exp_dict):
         if self._next_idx >= len(self._memory):
