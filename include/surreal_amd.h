@@ -609,6 +609,22 @@ int smx_epoch_forward_pair_f32(const smx_epoch_job_t* jobs, int32_t njobs, const
 int smx_epoch_fwdbwd_pair_f32(const smx_epoch_job_t* jobs, int32_t njobs, const struct smx_ppo_losses* loss,
                               smx_ppo_ctrl_t* ctrl, int64_t n_total, int32_t* sync_word, uint64_t* kl_slots,
                               void* xchg, int64_t xchg_bytes, smx_stream_t stream);
+/* The learn's FINAL forward-only policy pass (one SMX_EPOCH_LOSS_POLICY job, loss->will_update == 0) with the launches
+ * that used to follow it folded in; every word they wrote is written with the same bits.
+ *   stats_ticket != NULL: the pass's statistics, as smx_epoch_backward_f32 forms them for will_update == 0
+ *     (loss->stats / dlogvar / dlogvar_sumsq, the KL early-exit flag), by the last policy workgroup to finish -- found by
+ *     a ticket (an atomic add and a branch, never a wait); the partial rows cross workgroups as device-scope stores and
+ *     loads and are added in smx_epoch_backward_f32's order.  A job whose stop_flag is up writes nothing, as there.
+ *   epilogue != NULL: what smx_ppo_learn_epilogue_f32 does, on extra workgroups behind the row blocks (they do not
+ *     look at the stop flag); the last of them forms out4.  512 threads play the 1024 of that launch in two passes:
+ *     every sum keeps its operands and its order.  The value finalize reads v_partials of EARLIER launches only.
+ * Both tickets: one int32 each in device memory, zero before the first call, left zero.
+ * xchg / xchg_bytes: pair mode as smx_epoch_forward_pair_f32 (NULL / 0: unpaired). */
+struct smx_learn_epilogue;
+int smx_epoch_forward_final_f32(const smx_epoch_job_t* jobs, int32_t njobs, const struct smx_ppo_losses* loss,
+                                smx_ppo_ctrl_t* ctrl, int64_t n_total, void* xchg, int64_t xchg_bytes,
+                                int32_t* stats_ticket, const struct smx_learn_epilogue* epilogue,
+                                smx_stream_t stream);
 /* A co-tenant for the launch above (diagnostics / tests; no reference counterpart): `blocks` workgroups, each holding
  * one compute unit to itself (more than half of its LDS) for `microseconds` (<= 2 s) without doing work.  The in-launch
  * wait of smx_epoch_fwdbwd_f32 is bounded at 0.25 s: a tenant that keeps its workgroups off the device for longer makes

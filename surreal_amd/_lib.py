@@ -434,6 +434,8 @@ _SIGS = {
     'smx_epoch_forward_pair_f32': (c_int32, [POINTER(EpochJob), c_int32, POINTER(PpoLosses), _P, c_int64, _P, c_int64, _P]),
     'smx_epoch_fwdbwd_pair_f32': (c_int32, [POINTER(EpochJob), c_int32, POINTER(PpoLosses), _P, c_int64, _P, _P, _P,
                                             c_int64, _P]),
+    'smx_epoch_forward_final_f32': (c_int32, [POINTER(EpochJob), c_int32, POINTER(PpoLosses), _P, c_int64, _P, c_int64,
+                                              _P, POINTER(LearnEpilogue), _P]),
     'smx_device_occupy': (c_int32, [c_int32, c_int64, _P]),
     'smx_layernorm_forward_f32': (c_int32, [_P, c_int64, c_int64, c_int32, _P, _P, c_float, _P, c_int64, _P, _P, _P]),
     'smx_layernorm_backward_ws_floats': (c_int64, [c_int64, c_int32]),

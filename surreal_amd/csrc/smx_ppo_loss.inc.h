@@ -253,6 +253,8 @@ constexpr int FIN_CH = 64;                                   // partial rows sta
 // q, q + Q, ... of every staged chunk; the Q chains of a column meet in the fixed order ((s0 + s1) + s2) + ... -- the same
 // bits on every run and in every workgroup.  (One chain per column was 7936 dependent additions at the LSTM policy's
 // 127 k rows: 197 us per launch, every workgroup of the finalize walking all of them.)
+// COH: the rows were written by other workgroups of THIS launch (partial_store<true>) -- device-scope loads, the same sums
+template <bool COH = false>
 __device__ __forceinline__ void reduce_row_partials(const float* __restrict__ partials, int nblk,
                                                     int stride, float* S, float* buf) {
     const int Q = 256 / stride;                       // stride <= 8 + 2 * MAX_A = 72: at least 3 chains
@@ -267,7 +269,12 @@ __device__ __forceinline__ void reduce_row_partials(const float* __restrict__ pa
         for (int i0 = threadIdx.x; i0 < cnt; i0 += 8 * 256) {
             float v[8];
 #pragma unroll
-            for (int u = 0; u < 8; ++u) v[u] = src[min(i0 + 256 * u, cnt - 1)];
+            for (int u = 0; u < 8; ++u) {
+                if constexpr (COH)
+                    v[u] = __hip_atomic_load(src + min(i0 + 256 * u, cnt - 1), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                else
+                    v[u] = src[min(i0 + 256 * u, cnt - 1)];
+            }
 #pragma unroll
             for (int u = 0; u < 8; ++u)
                 if (i0 + 256 * u < cnt) buf[i0 + 256 * u] = v[u];

@@ -332,6 +332,14 @@ class HipKernels(object):
         L.call('smx_epoch_forward_f32', self._epoch_jobs(jobs), len(jobs), self._epoch_loss(loss),
                L.ptr(ctrl), int(n_total), self._st())
 
+    def epoch_forward_final(self, jobs, loss, ctrl, n_total, xchg=None, stats_ticket=None, epilogue=None):
+        """the learn's final forward-only policy pass with what used to follow it in the same launch
+        (smx_epoch_forward_final_f32): stats_ticket (one int32, zero) -- the pass's statistics, epoch_backward's for
+        will_update = 0; epilogue (dict of learn_epilogue's arguments) -- the end-of-learn launch.  The same bits."""
+        epi = None if epilogue is None else ctypes.byref(self._learn_epilogue_args(**epilogue))
+        L.call('smx_epoch_forward_final_f32', self._epoch_jobs(jobs), len(jobs), self._epoch_loss(loss), L.ptr(ctrl),
+               int(n_total), L.ptr(xchg), 0 if xchg is None else xchg.numel(), L.ptr(stats_ticket), epi, self._st())
+
     def epoch_backward(self, jobs, loss, ctrl, n_total):
         """jobs: dicts(net, x, h1T, h2T, loss, dz2T, dz1T[, dz3T (policy), dz3 (value), stop])"""
         L.call('smx_epoch_backward_f32', self._epoch_jobs(jobs), len(jobs), self._epoch_loss(loss),
@@ -405,6 +413,13 @@ class HipKernels(object):
     def learn_epilogue(self, ret, ret_mom, log_var, out4, ticket, zfilter=None, x=None, count_rows=0, v_partials=None,
                        n_epochs=0, nblk=0, v_stats=None, stats_stride=0):
         """value_finalize + moments(ret) + zfilter_update(x) + final_stats in one launch (single rank)"""
+        a = self._learn_epilogue_args(ret, ret_mom, log_var, out4, ticket, zfilter, x, count_rows, v_partials, n_epochs,
+                                      nblk, v_stats, stats_stride)
+        L.call('smx_ppo_learn_epilogue_f32', ctypes.byref(a), self._st())
+
+    @staticmethod
+    def _learn_epilogue_args(ret, ret_mom, log_var, out4, ticket, zfilter=None, x=None, count_rows=0, v_partials=None,
+                             n_epochs=0, nblk=0, v_stats=None, stats_stride=0):
         a = L.LearnEpilogue()
         if zfilter is not None:
             rows, D = x.shape
@@ -417,7 +432,7 @@ class HipKernels(object):
         a.v_partials, a.n_epochs, a.nblk, a.v_stats, a.stats_stride = L.ptr(v_partials), n_epochs, nblk, L.ptr(v_stats), \
             stats_stride
         a.log_var, a.out4, a.ticket = L.ptr(log_var), L.ptr(out4), L.ptr(ticket)
-        L.call('smx_ppo_learn_epilogue_f32', ctypes.byref(a), self._st())
+        return a
 
     def moments(self, x, out):
         L.call('smx_moments_f32', L.ptr(x), x.numel(), L.ptr(out), self._st())

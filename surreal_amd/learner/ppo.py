@@ -44,6 +44,11 @@ from surreal_amd.model.ppo_net import DiagGauss, PPOModel
 # session_config.learner.epoch_pair_split when the session does not set it (see _ws_epochs; the measurement that
 # decides it: DESIGN.md section 3.2, profiles/epoch_pair_split_bench.jsonl)
 EPOCH_PAIR_SPLIT_DEFAULT = True
+# session_config.learner.fold_final_stats / fold_epilogue when the session does not set them: the final policy pass's
+# statistics launch and the end-of-learn launch ride in that pass's forward launch (see _ws_epochs; DESIGN.md section
+# 3.2, profiles/learn_folds_bench.jsonl)
+FOLD_FINAL_STATS_DEFAULT = True
+FOLD_EPILOGUE_DEFAULT = True
 
 
 class LinearWithMinLR(object):
@@ -299,7 +304,7 @@ class PPOLearner(Learner):
             ws.ctrl_i[L.C_STEP_ACTOR:L.C_STEP_CRITIC + 1].copy_(
                 self._ws.ctrl_i[L.C_STEP_ACTOR:L.C_STEP_CRITIC + 1])
         self._ctrl_host = None
-        ws.ticket = torch.zeros(2, dtype=torch.int32, device=dev)
+        ws.ticket = torch.zeros(4, dtype=torch.int32, device=dev)    # GAE, epilogue, final statistics
 
     def _ws_critic_pass(self, ws):
         """critic pass + GAE"""
@@ -376,6 +381,14 @@ class PPOLearner(Learner):
         ws.nblk_v = ws.vblocks(rows)
         # single rank: GAE + normalisation and the end-of-learn statistics are one launch each
         ws.merged_tail = ws.fused and self.world_size == 1
+        # ... and two of them ride in the final, forward-only policy pass's launch (smx_epoch_forward_final_f32: the same
+        # bits): that pass's statistics and the end-of-learn statistics -- where that launch carries the policy alone and
+        # no value epoch runs behind it (epoch_baseline <= epoch_policy).  A kernel set without that launch keeps the
+        # separate ones.
+        cfg = self.session_config.learner
+        can_fold = (ws.merged_tail and self.epoch_baseline <= self.epoch_policy and hasattr(K, 'epoch_forward_final'))
+        ws.fold_final_stats = can_fold and bool(cfg.get('fold_final_stats', FOLD_FINAL_STATS_DEFAULT))
+        ws.fold_epilogue = can_fold and bool(cfg.get('fold_epilogue', FOLD_EPILOGUE_DEFAULT))
         if ws.fused:
             assert ws.nblk_p == K.epoch_blocks(rows)
             # the weights in the forward kernel's fragment order (model, critic, reference policy)
@@ -731,11 +744,12 @@ class PPOLearner(Learner):
         if ws.nblk_p < ws.ppart_ar.shape[0]:
             ws.ppart_ar[ws.nblk_p:].zero_()
 
-    def _enqueue_fused_epochs(self, ws, actions0, behave0, ref_job, tail, gae):
+    def _enqueue_fused_epochs(self, ws, actions0, behave0, ref_job, tail, gae, epilogue=None):
         """The lock-step epochs on the row-block kernels (csrc/smx_epoch.hip): per epoch
         [forward + losses] -> [batch means, KL coefficient / early exit, data gradients] ->
         [all weight gradients] -> [clip-norm + Adam of both groups]: four dependent launches where
-        the layered schedule takes nine.  Same arithmetic contract as _enqueue_lockstep_epochs."""
+        the layered schedule takes nine.  Same arithmetic contract as _enqueue_lockstep_epochs.
+        epilogue: learn_epilogue's arguments when that launch rides in the final policy pass's (ws.fold_epilogue)."""
         K, m = self.K, self.model
         Ep, Ev = self.epoch_policy, self.epoch_baseline
         n_total = ws.n_total
@@ -794,6 +808,12 @@ class PPOLearner(Learner):
                 # forward + loss + data gradients of every job of the epoch in ONE launch (smx_epoch_fwdbwd_f32)
                 K.epoch_fwdbwd(bj, loss, ws.ctrl_f, n_total, ws.sync[e:e + 1], ws.kl_slots[e], **px)
                 K.mlp3_wgrad_multi(bj)
+            elif pol_f and not pol_u and not val and (ws.fold_final_stats or epilogue is not None):
+                # the final pass with its statistics and / or the end-of-learn launch inside (the same bits)
+                K.epoch_forward_final([aj], loss, ws.ctrl_f, n_total, stats_ticket=ws.ticket[2:3] if ws.fold_final_stats
+                                      else None, epilogue=epilogue, **px)
+                if not ws.fold_final_stats:
+                    K.epoch_backward([aj], loss, ws.ctrl_f, n_total)       # statistics + early exit only
             else:
                 K.epoch_forward(([aj] if pol_f else []) + ([cj] if val else []), loss, ws.ctrl_f, n_total, **px)
                 if pol_f and not pol_u:
@@ -946,9 +966,18 @@ class PPOLearner(Learner):
         if not fused:
             ws.xnT.copy_(ws.xn.t())
             ws.ref_pol[:, A:].copy_(torch.exp(ref.log_var).expand(ws.rows, A))
+        epilogue = None
+        if fused and ws.merged_tail:
+            # value-loss finalize, _avg_return_targ (ppo.py:571), model.z_update(obs_iter) (:578-579) and the
+            # reported means: one launch, or part of the final policy pass's
+            epilogue = dict(ret=ws.ret, ret_mom=ws.ret_mom, log_var=m.log_var.view(-1), out4=ws.fin, ticket=ws.ticket[1:2],
+                            zfilter=m.z_filter if self.use_z_filter else None, x=obs0, count_rows=B,
+                            v_partials=ws.vpart, n_epochs=self.epoch_baseline, nblk=ws.vpart.shape[1],
+                            v_stats=ws.vstats, stats_stride=L.VS_STRIDE)
         if fused:
             self._enqueue_fused_epochs(ws, actions0, behave0, ref_job, tail,
-                                       lambda: self._enqueue_gae_from_values(ws, obs, rewards, dones))
+                                       lambda: self._enqueue_gae_from_values(ws, obs, rewards, dones),
+                                       epilogue=epilogue if ws.fold_epilogue else None)
         else:
             # the reference policy and the critic's obs_next rows ride in epoch 0's forward
             # launches (four independent networks, one launch per layer); GAE follows them
@@ -961,12 +990,8 @@ class PPOLearner(Learner):
             self._enqueue_final_stats(ws)
             return
         if fused and ws.merged_tail:
-            # value-loss finalize, _avg_return_targ (ppo.py:571), model.z_update(obs_iter) (:578-579) and the
-            # reported means: one launch
-            K.learn_epilogue(ws.ret, ws.ret_mom, m.log_var.view(-1), ws.fin, ws.ticket[1:2],
-                             zfilter=m.z_filter if self.use_z_filter else None, x=obs0, count_rows=B,
-                             v_partials=ws.vpart, n_epochs=self.epoch_baseline, nblk=ws.vpart.shape[1],
-                             v_stats=ws.vstats, stats_stride=L.VS_STRIDE)
+            if not ws.fold_epilogue:
+                K.learn_epilogue(**epilogue)
             return
         self._enqueue_learn_stats(ws, obs0, B, None)
 
