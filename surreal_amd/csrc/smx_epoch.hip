@@ -33,8 +33,9 @@
 //                      trips through the memory side) of the 5 k it saves.
 //   epoch_fwd_final*_kernel  the learn's final forward-only policy pass with the two launches that followed it inside: its
 //                      last workgroup forms the pass's statistics (epoch_bwd_kernel's with nothing to update), and eight
-//                      workgroups behind the row blocks run the end-of-learn statistics (learn_epilogue_kernel,
-//                      smx_scan.hip).  Measured (profiles/learn_folds_*): 24.2 + 8.8 + 10.2 us -> 29.6 us, the same bits.
+//                      workgroups behind the row blocks run the end-of-learn statistics (the roles of
+//                      smx_learn_epilogue.inc.h, which learn_epilogue_kernel runs too).  Measured
+//                      (profiles/learn_folds_*): 24.2 + 8.8 + 10.2 us -> 29.6 us, the same bits.
 //
 // What shaped the code (all measured, scripts/bench_epoch.py + scripts/micro/): guards are out-of-range
 // buffer offsets, never branches (a load under a lane mask is waited for at the end of the masked
@@ -45,7 +46,7 @@
 // The weight gradients (sums over ALL rows) stay a GEMM launch (smx_gemm.hip), clip-norm + Adam
 // one more: 4 dependent launches per epoch instead of 9.
 #include "smx_common.h"
-#include "smx_moments.inc.h"
+#include "smx_learn_epilogue.inc.h"
 #include <string.h>
 
 // workgroup barrier for data exchanged through LDS: does NOT wait for the wave's global stores
@@ -132,17 +133,6 @@ struct EArgs {
     int epi_base;      // ... the workgroups from this one on carry the end-of-learn roles (0: none)
 };
 
-// What the workgroups behind the row blocks of the learn's final launch do (learn_epilogue_kernel's arguments, smx_scan.hip)
-struct EpiArgs {
-    const float* x; long ldx; long rows; int D;
-    float *rs, *rsq, *cnt; float count_rows;
-    const float* ret; long n_ret; float* ret_mom;
-    const float* vpartials; int n_epochs, nblk; float* vstats; int vstride;
-    const float* log_var; int A; float* out4;
-    int* ticket;
-    int nz, count;     // column blocks of the z-update / workgroups of all roles
-};
-
 // Consecutive workgroup ids go round-robin over the 8 XCDs, each with its own L2.  With the actor's row blocks first and the
 // critic's behind them, every XCD ran eight of each and pulled BOTH networks' packed weights (rewritten by the optimiser
 // launch, so every epoch's first touch is a trip to the memory side) into its L2: 2.2 MB per XCD and launch where 1.1 would do.
@@ -214,173 +204,13 @@ __device__ __forceinline__ void fb_reduce_partials(const float* __restrict__ par
     SMX_LDS_BARRIER();
 }
 
-// ---------------------------------------------------------------------------------------------------------------
-// The end-of-learn roles of learn_epilogue_kernel (smx_scan.hip) as workgroups of the learn's final forward-only
-// launch, which fills half of the device: nothing in them depends on that launch's policy pass.  Role workgroup r:
-//   r < nz         column sums of 64 observation features (the z-filter update)
-//   r == nz        moments of the return targets
-//   r > nz         value-loss finalize, 16 epochs (waves) per workgroup
-// and the last of them to finish forms the reported means (it reads the UPDATED z-filter sums).
-// learn_epilogue_kernel runs 1024 threads, these kernels 512: thread t plays the "virtual" threads t and t + 512 one
-// after the other -- virtual wave w + 8 is real wave w with the same lanes -- so every per-thread chain, every wave
-// butterfly and every fixed-order sum over the sixteen waves has the operands and the order it has there: the same
-// bits.  What the last workgroup reads from the others (the running sums and the count) travels as device-scope
-// stores and loads (no fence: see partial_store), counted by a ticket that the last one resets.
-// ---------------------------------------------------------------------------------------------------------------
-constexpr int EPI_VT = 1024 / FNTH;          // virtual threads per real thread
-
-__device__ __forceinline__ void epi_block_moments(const float* __restrict__ x, long n, float* __restrict__ out,
-                                                  double* red, double* bc) {
-    const int tid = threadIdx.x, lane = tid & 63;
-#pragma unroll
-    for (int ps = 0; ps < EPI_VT; ++ps) {
-        const int vt = tid + FNTH * ps;
-        double s = 0.0;
-        for (long i = vt; i < n; i += 1024) s += (double)__builtin_nontemporal_load(x + i);
-        s = smx_wave_sum_d(s);
-        if (lane == 0) red[vt >> 6] = s;
-    }
-    __syncthreads();
-    if (tid == 0) {
-        double t = 0.0;
-        for (int i = 0; i < 16; ++i) t += red[i];
-        *bc = t / (double)n;
-    }
-    __syncthreads();
-    const double mean = *bc;
-    double q2[EPI_VT];
-#pragma unroll
-    for (int ps = 0; ps < EPI_VT; ++ps) {
-        const int vt = tid + FNTH * ps;
-        double q = 0.0;
-        for (long i = vt; i < n; i += 1024) {
-            const double d = (double)__builtin_nontemporal_load(x + i) - mean;
-            q += d * d;
-        }
-        q2[ps] = smx_wave_sum_d(q);
-    }
-    __syncthreads();
-#pragma unroll
-    for (int ps = 0; ps < EPI_VT; ++ps)
-        if (lane == 0) red[(tid + FNTH * ps) >> 6] = q2[ps];
-    __syncthreads();
-    if (tid == 0) {
-        double t = 0.0;
-        for (int i = 0; i < 16; ++i) t += red[i];
-        out[0] = (float)n;
-        out[1] = (float)mean;
-        out[2] = (float)t;
-    }
-}
-
-__device__ __forceinline__ void epi_final_stats(const EpiArgs& P, double (*red)[4]) {
-    const int tid = threadIdx.x, lane = tid & 63;
-    const float* rsum = P.nz ? P.rs : nullptr;
-#pragma unroll
-    for (int ps = 0; ps < EPI_VT; ++ps) {
-        const int vt = tid + FNTH * ps;
-        double s0 = 0.0, s1 = 0.0, s2 = 0.0, s3 = 0.0;
-        for (int a = vt; a < P.A; a += 1024) s0 += (double)P.log_var[a];
-        if (rsum) {
-            const float cnt = __hip_atomic_load(P.cnt, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            for (int d = vt; d < P.D; d += 1024) {
-                const float m = __hip_atomic_load(rsum + d, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) / cnt;
-                const float q = __hip_atomic_load(P.rsq + d, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) / cnt;
-                s1 += (double)m;
-                s2 += (double)q;
-                s3 += (double)sqrtf(q - m * m);
-            }
-        }
-        s0 = smx_wave_sum_d(s0); s1 = smx_wave_sum_d(s1); s2 = smx_wave_sum_d(s2); s3 = smx_wave_sum_d(s3);
-        if (lane == 0) { const int w = vt >> 6; red[w][0] = s0; red[w][1] = s1; red[w][2] = s2; red[w][3] = s3; }
-    }
-    __syncthreads();
-    if (tid < 4) {
-        double t = 0.0;
-        for (int i = 0; i < 16; ++i) t += red[i][tid];
-        P.out4[tid] = (float)(t / (double)(tid == 0 ? P.A : (P.D > 0 ? P.D : 1)));
-    }
-}
-
-__device__ __forceinline__ void epi_roles(const EpiArgs& P, const int blk, float* sm) {
-    const int tid = threadIdx.x;
-    float* s1 = sm;                              // [16][64]
-    float* s2 = sm + 1024;                       // [16][64]
-    double* red = (double*)(sm + 2048);          // [16][4] (the moments use the first 16)
+// The end-of-learn roles (smx_learn_epilogue.inc.h) as workgroups of the learn's final forward-only launch, which fills
+// half of the device: nothing in them depends on that launch's policy pass.  Their scratch is the head of the launch's
+// dynamic LDS segment.
+__device__ __forceinline__ void final_roles(const EpilogueArgs& P, const int blk, float* sm) {
+    double* red = (double*)(sm + 2048);          // [16][4], behind s1 and s2
     double* bc = red + 64;
-    int* is_last = (int*)(bc + 1);
-    if (blk < P.nz) {
-        const float* x = P.x;
-        const long ldx = P.ldx, rows = P.rows;
-#pragma unroll
-        for (int ps = 0; ps < EPI_VT; ++ps) {
-            const int vt = tid + FNTH * ps;
-            const int c = vt & 63, g = vt >> 6;
-            const int col = blk * 64 + c;
-            float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f, q0 = 0.f, q1 = 0.f, q2 = 0.f, q3 = 0.f;
-            if (col < P.D) {
-                long r = g;
-                for (; r + 240 < rows; r += 256) {
-                    float v[16];
-#pragma unroll
-                    for (int i = 0; i < 16; ++i) v[i] = x[(r + 16 * i) * ldx + col];
-#pragma unroll
-                    for (int i = 0; i < 16; i += 4) {
-                        a0 += v[i]; q0 += v[i] * v[i];
-                        a1 += v[i + 1]; q1 += v[i + 1] * v[i + 1];
-                        a2 += v[i + 2]; q2 += v[i + 2] * v[i + 2];
-                        a3 += v[i + 3]; q3 += v[i + 3] * v[i + 3];
-                    }
-                }
-                for (; r + 48 < rows; r += 64) {
-                    const float v0 = x[r * ldx + col], v1 = x[(r + 16) * ldx + col];
-                    const float v2 = x[(r + 32) * ldx + col], v3 = x[(r + 48) * ldx + col];
-                    a0 += v0; q0 += v0 * v0;
-                    a1 += v1; q1 += v1 * v1;
-                    a2 += v2; q2 += v2 * v2;
-                    a3 += v3; q3 += v3 * v3;
-                }
-                for (; r < rows; r += 16) {
-                    const float v = x[r * ldx + col];
-                    a0 += v; q0 += v * v;
-                }
-            }
-            s1[g * 64 + c] = (a0 + a1) + (a2 + a3);
-            s2[g * 64 + c] = (q0 + q1) + (q2 + q3);
-        }
-        __syncthreads();
-        const int col = blk * 64 + tid;
-        if (tid < 64 && col < P.D) {             // (virtual row group 0)
-            float ta = 0.f, tq = 0.f;
-            for (int k = 0; k < 16; ++k) { ta += s1[k * 64 + tid]; tq += s2[k * 64 + tid]; }
-            __hip_atomic_store(P.rs + col, P.rs[col] + ta, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);     // z_filter.py:55
-            __hip_atomic_store(P.rsq + col, P.rsq[col] + tq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // z_filter.py:56
-        }
-        if (blk == 0 && tid == 0)
-            __hip_atomic_store(P.cnt, P.cnt[0] + P.count_rows, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // z_filter.py:57
-    } else if (blk == P.nz) {
-        epi_block_moments(P.ret, P.n_ret, P.ret_mom, red, bc);
-    } else {
-#pragma unroll
-        for (int ps = 0; ps < EPI_VT; ++ps) {
-            const int e = (blk - P.nz - 1) * 16 + ((tid + FNTH * ps) >> 6);
-            if (e < P.n_epochs)
-                value_finalize_wave(P.vpartials + (size_t)e * P.nblk * 8, P.nblk, P.vstats + (size_t)e * P.vstride,
-                                    tid & 63);
-        }
-    }
-    // the last role workgroup to get here (its ticket counts them alone: they run whether or not the policy has stopped)
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    if (tid == 0) {
-        const int t = __hip_atomic_fetch_add(P.ticket, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        const int last = t == P.count - 1;
-        if (last) __hip_atomic_store(P.ticket, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        *is_last = last;
-    }
-    __syncthreads();
-    if (*is_last == 0) return;
-    epi_final_stats(P, (double(*)[4])red);
+    learn_epilogue_roles<FNTH, true>(P, blk, sm, sm + 1024, (double(*)[4])red, bc, (int*)(bc + 1));
 }
 
 // Forward of up to four jobs' row blocks (FB = false: epoch_fwd_kernel), or forward + loss + data gradients of the
@@ -1032,19 +862,19 @@ __global__ __launch_bounds__(FNTH) void epoch_fwd_pair_kernel(EArgs G, smx_ppo_c
     epoch_fwd_body<false, true>(G, ctrl);
 }
 // The learn's final forward-only launch (smx_epoch_forward_final_f32): the policy pass, whose last workgroup also forms
-// the pass's statistics (one launch less), and behind the row blocks the end-of-learn roles (epi_roles: one launch less).
-__global__ __launch_bounds__(FNTH) void epoch_fwd_final_kernel(EArgs G, EpiArgs E, smx_ppo_ctrl_t* __restrict__ ctrl) {
+// the pass's statistics (one launch less), and behind the row blocks the end-of-learn roles (final_roles: one launch less).
+__global__ __launch_bounds__(FNTH) void epoch_fwd_final_kernel(EArgs G, EpilogueArgs E, smx_ppo_ctrl_t* __restrict__ ctrl) {
     if (G.epi_base && (int)blockIdx.x >= G.epi_base) {
         extern __shared__ float sm[];
-        epi_roles(E, (int)blockIdx.x - G.epi_base, sm);
+        final_roles(E, (int)blockIdx.x - G.epi_base, sm);
         return;
     }
     epoch_fwd_body<false, false, true>(G, ctrl);
 }
-__global__ __launch_bounds__(FNTH) void epoch_fwd_final_pair_kernel(EArgs G, EpiArgs E, smx_ppo_ctrl_t* __restrict__ ctrl) {
+__global__ __launch_bounds__(FNTH) void epoch_fwd_final_pair_kernel(EArgs G, EpilogueArgs E, smx_ppo_ctrl_t* __restrict__ ctrl) {
     if (G.epi_base && (int)blockIdx.x >= G.epi_base) {
         extern __shared__ float sm[];
-        epi_roles(E, (int)blockIdx.x - G.epi_base, sm);
+        final_roles(E, (int)blockIdx.x - G.epi_base, sm);
         return;
     }
     epoch_fwd_body<false, true, true>(G, ctrl);
@@ -1663,26 +1493,12 @@ extern "C" int smx_epoch_forward_final_f32(const smx_epoch_job_t* jobs, int32_t 
         const int need = (G.off_loss + fb_loss_floats(loss->A)) * (int)sizeof(float);
         lds = need > lds ? need : lds;
     }
-    EpiArgs P;
+    EpilogueArgs P;
     memset(&P, 0, sizeof(P));
     int n_epi = 0;
     if (epilogue) {
-        const smx_learn_epilogue_t* a = epilogue;
-        SMX_REQUIRE(a->ret && a->ret_moments && a->log_var && a->out4 && a->ticket, SMX_E_NULL);
-        SMX_REQUIRE(a->n_ret > 0 && a->A > 0, SMX_E_SHAPE);
-        SMX_REQUIRE(!a->x || (a->running_sum && a->running_sumsq && a->count && a->rows > 0 && a->D > 0 && a->ldx >= a->D),
-                    SMX_E_SHAPE);
-        SMX_REQUIRE(a->n_epochs == 0 || (a->v_partials && a->v_stats && a->nblk > 0 && a->stats_stride >= 2), SMX_E_SHAPE);
-        SMX_REQUIRE(a->n_epochs == 0 || ((uintptr_t)a->v_partials & 15) == 0, SMX_E_ALIGN);
-        P.x = a->x; P.ldx = (long)a->ldx; P.rows = (long)a->rows; P.D = a->D;
-        P.rs = a->running_sum; P.rsq = a->running_sumsq; P.cnt = a->count; P.count_rows = a->count_rows;
-        P.ret = a->ret; P.n_ret = (long)a->n_ret; P.ret_mom = a->ret_moments;
-        P.vpartials = a->v_partials; P.n_epochs = a->n_epochs; P.nblk = a->nblk; P.vstats = a->v_stats;
-        P.vstride = a->stats_stride;
-        P.log_var = a->log_var; P.A = a->A; P.out4 = a->out4; P.ticket = (int*)a->ticket;
-        P.nz = a->x ? (a->D + 63) / 64 : 0;
-        n_epi = P.nz + 1 + (a->n_epochs + 15) / 16;
-        P.count = n_epi;
+        n_epi = learn_epilogue_args(epilogue, P);
+        if (n_epi < 0) return n_epi;
     }
     SMX_REQUIRE(lds <= MAX_LDS, SMX_E_UNSUPPORTED);
     static bool attr_set_fin = false;

@@ -1,5 +1,5 @@
-// Statistics reductions shared by smx_ppo.hip (their own launches) and smx_scan.hip (the one-launch
-// learn epilogue).  Included at file scope.
+// Statistics reductions shared by smx_ppo.hip (their own launches), smx_scan.hip (GAE + normalisation) and the
+// end-of-learn roles (smx_learn_epilogue.inc.h).  Included at file scope.
 #pragma once
 
 // mergeable moments (count, mean, M2) of two disjoint sets (Chan et al.)
@@ -54,33 +54,107 @@ static __device__ __forceinline__ void value_finalize_wave(const float* __restri
     }
 }
 
+// ---------------------------------------------------------------------------------------------------------------
+// One workgroup's reductions, written for VT "virtual" threads and run by NTH real ones (VT a multiple of NTH, both of
+// 64): real thread t plays the virtual threads t, t + NTH, ... one after the other, so virtual wave w + NTH / 64 is real
+// wave w with the same lanes.  Every per-thread chain (stride VT), every wave butterfly and every fixed-order sum over
+// the VT / 64 waves has the operands and the order it has on VT real threads: the result's bits depend on VT alone.
+// With NTH == VT the pass loops have one trip.
+// ---------------------------------------------------------------------------------------------------------------
+
+// a running statistic that another workgroup of the SAME launch writes or reads travels as device-scope relaxed stores
+// and loads (COH; see partial_store, smx_ppo_loss.inc.h); across a launch boundary plain accesses do
+template <bool COH>
+static __device__ __forceinline__ float stat_load(const float* p) {
+    if constexpr (COH) return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    else return __builtin_nontemporal_load(p);
+}
+template <bool COH>
+static __device__ __forceinline__ void stat_store(float* p, float v) {
+    if constexpr (COH) __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    else *p = v;
+}
+
+// batch moments {n, mean, M2} of x[0, n) in fp64 (two passes); red: VT / 64 doubles of LDS, bc: one more.  On return
+// out[] is there for every thread of the workgroup.
+template <int VT, int NTH>
+static __device__ __forceinline__ void block_moments(const float* __restrict__ x, long n, float* __restrict__ out,
+                                                     double* red, double* bc) {
+    constexpr int PS = VT / NTH;
+    const int tid = threadIdx.x, lane = tid & 63;
+#pragma unroll
+    for (int ps = 0; ps < PS; ++ps) {
+        const int vt = tid + NTH * ps;
+        double s = 0.0;
+        for (long i = vt; i < n; i += VT) s += (double)__builtin_nontemporal_load(x + i);
+        s = smx_wave_sum_d(s);
+        if (lane == 0) red[vt >> 6] = s;
+    }
+    __syncthreads();
+    if (tid == 0) {
+        double t = 0.0;
+        for (int i = 0; i < VT / 64; ++i) t += red[i];
+        *bc = t / (double)n;
+    }
+    __syncthreads();
+    const double mean = *bc;
+    double q2[PS];
+#pragma unroll
+    for (int ps = 0; ps < PS; ++ps) {
+        double q = 0.0;
+        for (long i = tid + NTH * ps; i < n; i += VT) {
+            const double d = (double)__builtin_nontemporal_load(x + i) - mean;
+            q += d * d;
+        }
+        q2[ps] = smx_wave_sum_d(q);
+    }
+    __syncthreads();
+#pragma unroll
+    for (int ps = 0; ps < PS; ++ps)
+        if (lane == 0) red[(tid + NTH * ps) >> 6] = q2[ps];
+    __syncthreads();
+    if (tid == 0) {
+        double t = 0.0;
+        for (int i = 0; i < VT / 64; ++i) t += red[i];
+        out[0] = (float)n;
+        out[1] = (float)mean;
+        out[2] = (float)t;
+    }
+    __syncthreads();
+}
+
 // out[0] = mean(log_var); out[1..3] = mean over the D features of running_sum/count,
 // running_sumsq/count and sqrt(running_sumsq/count - (running_sum/count)^2)  (no clamp: z_filter.py:90-98);
-// one workgroup of blockDim.x threads (a multiple of 64, <= 1024); red: 16 x 4 doubles of LDS
+// red: VT / 64 x 4 doubles of LDS
+template <int VT, int NTH, bool COH>
 static __device__ __forceinline__ void final_stats_block(const float* __restrict__ log_var, int A,
                                                          const float* __restrict__ rsum,
                                                          const float* __restrict__ rsumsq,
                                                          const float* __restrict__ count, int D,
                                                          float* __restrict__ out, double (*red)[4]) {
-    double s0 = 0.0, s1 = 0.0, s2 = 0.0, s3 = 0.0;
-    for (int a = threadIdx.x; a < A; a += blockDim.x) s0 += (double)log_var[a];
-    if (rsum) {
-        const float cnt = __builtin_nontemporal_load(count);
-        for (int d = threadIdx.x; d < D; d += blockDim.x) {
-            const float m = __builtin_nontemporal_load(rsum + d) / cnt, q = __builtin_nontemporal_load(rsumsq + d) / cnt;
-            s1 += (double)m;
-            s2 += (double)q;
-            s3 += (double)sqrtf(q - m * m);
+    const int tid = threadIdx.x, lane = tid & 63;
+    __syncthreads();  // protect `red` from a previous use
+#pragma unroll
+    for (int ps = 0; ps < VT / NTH; ++ps) {
+        const int vt = tid + NTH * ps;
+        double s0 = 0.0, s1 = 0.0, s2 = 0.0, s3 = 0.0;
+        for (int a = vt; a < A; a += VT) s0 += (double)log_var[a];
+        if (rsum) {
+            const float cnt = stat_load<COH>(count);
+            for (int d = vt; d < D; d += VT) {
+                const float m = stat_load<COH>(rsum + d) / cnt, q = stat_load<COH>(rsumsq + d) / cnt;
+                s1 += (double)m;
+                s2 += (double)q;
+                s3 += (double)sqrtf(q - m * m);
+            }
         }
+        s0 = smx_wave_sum_d(s0); s1 = smx_wave_sum_d(s1); s2 = smx_wave_sum_d(s2); s3 = smx_wave_sum_d(s3);
+        if (lane == 0) { const int w = vt >> 6; red[w][0] = s0; red[w][1] = s1; red[w][2] = s2; red[w][3] = s3; }
     }
-    s0 = smx_wave_sum_d(s0); s1 = smx_wave_sum_d(s1); s2 = smx_wave_sum_d(s2); s3 = smx_wave_sum_d(s3);
-    const int w = threadIdx.x >> 6, nw = (blockDim.x + 63) >> 6;
     __syncthreads();
-    if ((threadIdx.x & 63) == 0) { red[w][0] = s0; red[w][1] = s1; red[w][2] = s2; red[w][3] = s3; }
-    __syncthreads();
-    if (threadIdx.x < 4) {
+    if (tid < 4) {
         double t = 0.0;
-        for (int i = 0; i < nw; ++i) t += red[i][threadIdx.x];
-        out[threadIdx.x] = (float)(t / (double)(threadIdx.x == 0 ? A : (D > 0 ? D : 1)));
+        for (int i = 0; i < VT / 64; ++i) t += red[i][tid];
+        out[tid] = (float)(t / (double)(tid == 0 ? A : (D > 0 ? D : 1)));
     }
 }

@@ -304,8 +304,8 @@ __global__ __launch_bounds__(256) void final_stats_kernel(const float* __restric
                                                           const float* __restrict__ rsumsq,
                                                           const float* __restrict__ count, int D,
                                                           float* __restrict__ out) {
-    __shared__ double red[16][4];
-    final_stats_block(log_var, A, rsum, rsumsq, count, D, out, red);
+    __shared__ double red[4][4];
+    final_stats_block<256, 256, false>(log_var, A, rsum, rsumsq, count, D, out, red);
 }
 
 // acting head of PPOAgent.act (ppo_agent.py:106-154, ppo_net.py:74-91): pd = [mean, exp(log_var) *

@@ -3,7 +3,7 @@
 // coalesced row loads, LDS-staged masked values, wave-shuffle reductions.
 // Reference: surreal/learner/ppo.py:387-418, surreal/model/z_filter.py:44-79.
 #include "smx_common.h"
-#include "smx_moments.inc.h"
+#include "smx_learn_epilogue.inc.h"
 
 // ---------------------------------------------------------------------------
 // One wave per sub-trajectory b.  LDS per wave: Vm[N+1] | r[N] | delta[N]
@@ -100,59 +100,6 @@ __global__ __launch_bounds__(256) void gae_kernel(
     gae_body(values, values_tail, rewards, dones, gpow, lpow, gamma, gamma_H, B, N, H, adv, ret);
 }
 
-// the LAST workgroup of a launch to get here returns true (device-scope release / acquire around a
-// ticket counter, which it resets for the next launch): the place for a launch's global epilogue
-__device__ __forceinline__ bool last_block_done(int* ticket) {
-    __shared__ int is_last;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        __threadfence();
-        const int t = atomicAdd(ticket, 1);
-        is_last = (t == (int)gridDim.x - 1);
-        if (is_last) *ticket = 0;
-        __threadfence();
-    }
-    __syncthreads();
-    return is_last != 0;
-}
-
-// batch moments {n, mean, M2} of x[0, n) in fp64 (two passes) by ONE workgroup of blockDim.x <= 1024 threads
-__device__ __forceinline__ void block_moments(const float* __restrict__ x, long n, float* __restrict__ out) {
-    __shared__ double red[16];
-    __shared__ double bc;
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, nw = (blockDim.x + 63) >> 6;
-    double s = 0.0;
-    for (long i = threadIdx.x; i < n; i += blockDim.x) s += (double)__builtin_nontemporal_load(x + i);
-    s = smx_wave_sum_d(s);
-    if (lane == 0) red[w] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double t = 0.0;
-        for (int i = 0; i < nw; ++i) t += red[i];
-        bc = t / (double)n;
-    }
-    __syncthreads();
-    const double mean = bc;
-    double q = 0.0;
-    for (long i = threadIdx.x; i < n; i += blockDim.x) {
-        const double d = (double)__builtin_nontemporal_load(x + i) - mean;
-        q += d * d;
-    }
-    q = smx_wave_sum_d(q);
-    __syncthreads();
-    if (lane == 0) red[w] = q;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double t = 0.0;
-        for (int i = 0; i < nw; ++i) t += red[i];
-        out[0] = (float)n;
-        out[1] = (float)mean;
-        out[2] = (float)t;
-        bc = t;
-    }
-    __syncthreads();
-}
-
 // GAE + (optionally) the batch normalisation of the advantages (ppo.py:402-405, 413-416) in the same
 // launch: the last workgroup to finish forms the moments and normalises in place
 __global__ __launch_bounds__(256) void gae_norm_kernel(
@@ -163,8 +110,10 @@ __global__ __launch_bounds__(256) void gae_norm_kernel(
     int* __restrict__ ticket) {
     gae_body(values, values_tail, rewards, dones, gpow, lpow, gamma, gamma_H, B, N, H, adv, ret);
     if (!last_block_done(ticket)) return;
+    __shared__ double red[4];
+    __shared__ double bc;
     const long n = (long)B * (N - H + 1);
-    block_moments(adv, n, norm_mom);
+    block_moments<256, 256>(adv, n, norm_mom, red, &bc);
     const float cnt = (float)n, mean = norm_mom[1], m2 = norm_mom[2];
     const float stdv = sqrtf(m2 / (cnt - 1.0f));             // advs.std(): unbiased
     const float den = (min_std > stdv) ? min_std : stdv;     // Python max(std, 1e-4)
@@ -484,42 +433,13 @@ extern "C" int smx_zfilter_forward_sums_f32(const float* x, int64_t ldx, int64_t
     return SMX_OK;
 }
 
-// Column sums of x and x*x: block = 64 columns x 16 row-lanes (1024 threads); each thread walks
-// rows r = g, g+16, ... (the rows of obs[:, 0, :] are N*D floats apart: latency-bound, so depth
-// comes from 16 row-lanes x 4 independent loads in flight), then a fixed-order LDS reduction.
+// Column sums of x and x*x into the running sums: one workgroup per 64 columns (smx_learn_epilogue.inc.h)
 __global__ __launch_bounds__(1024) void zupdate_kernel(const float* __restrict__ x, long ldx,
                                                        long rows, int D, float* __restrict__ rs,
                                                        float* __restrict__ rsq,
                                                        float* __restrict__ cnt, float count_rows) {
-    __shared__ float s1[16][64], s2[16][64];
-    const int c = threadIdx.x & 63, g = threadIdx.x >> 6;
-    const int col = blockIdx.x * 64 + c;
-    float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f, q0 = 0.f, q1 = 0.f, q2 = 0.f, q3 = 0.f;
-    if (col < D) {
-        long r = g;
-        for (; r + 48 < rows; r += 64) {
-            const float v0 = x[r * ldx + col], v1 = x[(r + 16) * ldx + col];
-            const float v2 = x[(r + 32) * ldx + col], v3 = x[(r + 48) * ldx + col];
-            a0 += v0; q0 += v0 * v0;
-            a1 += v1; q1 += v1 * v1;
-            a2 += v2; q2 += v2 * v2;
-            a3 += v3; q3 += v3 * v3;
-        }
-        for (; r < rows; r += 16) {
-            const float v = x[r * ldx + col];
-            a0 += v; q0 += v * v;
-        }
-    }
-    s1[g][c] = (a0 + a1) + (a2 + a3);
-    s2[g][c] = (q0 + q1) + (q2 + q3);
-    __syncthreads();
-    if (g == 0 && col < D) {
-        float ta = 0.f, tq = 0.f;
-        for (int k = 0; k < 16; ++k) { ta += s1[k][c]; tq += s2[k][c]; }
-        rs[col] += ta;    // z_filter.py:55
-        rsq[col] += tq;   // z_filter.py:56
-    }
-    if (blockIdx.x == 0 && threadIdx.x == 0) cnt[0] += count_rows;  // z_filter.py:57
+    __shared__ float s1[16 * 64], s2[16 * 64];
+    zfilter_column_sums<1024, false>(x, ldx, rows, D, blockIdx.x, rs, rsq, cnt, count_rows, s1, s2);
 }
 
 extern "C" int smx_zfilter_update_f32(const float* x, int64_t ldx, int64_t rows, int32_t D,
@@ -609,103 +529,20 @@ extern "C" int smx_zfilter_update_ws_f32(const float* x, int64_t ldx, int64_t ro
 
 
 // ---------------------------------------------------------------------------
-// What PPOLearner._optimize does after its epoch loops (ppo.py:565-584), in ONE launch instead of
-// four: the explained variance / value loss of every value epoch from their block moments, the
-// moments of the return targets, the z-filter update on the step-0 observations -- independent
-// pieces, one per group of workgroups -- and, by the last workgroup to finish, the means the learner
-// reports (they read the UPDATED z-filter sums).
-//   blocks [0, nz)            column sums of 64 observation features each (zupdate_kernel's scheme)
-//   block  nz                 moments of `ret`
-//   blocks (nz, nz + nv]      value-loss finalize, 16 epochs (waves) per block
+// The end-of-learn roles (smx_learn_epilogue.inc.h) as ONE launch of their own instead of four
 // ---------------------------------------------------------------------------
-struct EpilogueArgs {
-    const float* x; long ldx; long rows; int D;
-    float *rs, *rsq, *cnt; float count_rows;
-    const float* ret; long n_ret; float* ret_mom;
-    const float* vpartials; int n_epochs, nblk; float* vstats; int vstride;
-    const float* log_var; int A; float* out4;
-    int* ticket;
-    int nz;
-};
-
 __global__ __launch_bounds__(1024) void learn_epilogue_kernel(EpilogueArgs P) {
-    __shared__ float s1[16][64], s2[16][64];
+    __shared__ float s1[16 * 64], s2[16 * 64];
     __shared__ double red4[16][4];
-    const int blk = blockIdx.x;
-    if (blk < P.nz) {
-        const int c = threadIdx.x & 63, g = threadIdx.x >> 6;
-        const int col = blk * 64 + c;
-        float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f, q0 = 0.f, q1 = 0.f, q2 = 0.f, q3 = 0.f;
-        if (col < P.D) {
-            const float* x = P.x;
-            const long ldx = P.ldx, rows = P.rows;
-            long r = g;
-            // (sixteen loads in flight; the additions in the order of four passes of the loop below: bit-identical sums.
-            // With four in flight a thread's 64 rows were sixteen dependent round trips -- 10 of this launch's 12 us)
-            for (; r + 240 < rows; r += 256) {
-                float v[16];
-#pragma unroll
-                for (int i = 0; i < 16; ++i) v[i] = x[(r + 16 * i) * ldx + col];
-#pragma unroll
-                for (int i = 0; i < 16; i += 4) {
-                    a0 += v[i]; q0 += v[i] * v[i];
-                    a1 += v[i + 1]; q1 += v[i + 1] * v[i + 1];
-                    a2 += v[i + 2]; q2 += v[i + 2] * v[i + 2];
-                    a3 += v[i + 3]; q3 += v[i + 3] * v[i + 3];
-                }
-            }
-            for (; r + 48 < rows; r += 64) {
-                const float v0 = x[r * ldx + col], v1 = x[(r + 16) * ldx + col];
-                const float v2 = x[(r + 32) * ldx + col], v3 = x[(r + 48) * ldx + col];
-                a0 += v0; q0 += v0 * v0;
-                a1 += v1; q1 += v1 * v1;
-                a2 += v2; q2 += v2 * v2;
-                a3 += v3; q3 += v3 * v3;
-            }
-            for (; r < rows; r += 16) {
-                const float v = x[r * ldx + col];
-                a0 += v; q0 += v * v;
-            }
-        }
-        s1[g][c] = (a0 + a1) + (a2 + a3);
-        s2[g][c] = (q0 + q1) + (q2 + q3);
-        __syncthreads();
-        if (g == 0 && col < P.D) {
-            float ta = 0.f, tq = 0.f;
-            for (int k = 0; k < 16; ++k) { ta += s1[k][c]; tq += s2[k][c]; }
-            P.rs[col] += ta;    // z_filter.py:55
-            P.rsq[col] += tq;   // z_filter.py:56
-        }
-        if (blk == 0 && threadIdx.x == 0) P.cnt[0] += P.count_rows;  // z_filter.py:57
-    } else if (blk == P.nz) {
-        block_moments(P.ret, P.n_ret, P.ret_mom);
-    } else {
-        const int e = (blk - P.nz - 1) * 16 + (threadIdx.x >> 6);
-        if (e < P.n_epochs)
-            value_finalize_wave(P.vpartials + (size_t)e * P.nblk * 8, P.nblk, P.vstats + (size_t)e * P.vstride,
-                                threadIdx.x & 63);
-    }
-    if (!last_block_done(P.ticket)) return;
-    final_stats_block(P.log_var, P.A, P.nz ? P.rs : nullptr, P.rsq, P.cnt, P.D, P.out4, red4);
+    __shared__ double bc;
+    learn_epilogue_roles<1024, false>(P, blockIdx.x, s1, s2, red4, &bc, nullptr /* last_block_done has its own */);
 }
 
 extern "C" int smx_ppo_learn_epilogue_f32(const smx_learn_epilogue_t* a, smx_stream_t stream) {
-    SMX_REQUIRE(a && a->ret && a->ret_moments && a->log_var && a->out4 && a->ticket, SMX_E_NULL);
-    SMX_REQUIRE(a->n_ret > 0 && a->A > 0, SMX_E_SHAPE);
-    SMX_REQUIRE(!a->x || (a->running_sum && a->running_sumsq && a->count && a->rows > 0 && a->D > 0 && a->ldx >= a->D),
-                SMX_E_SHAPE);
-    SMX_REQUIRE(a->n_epochs == 0 || (a->v_partials && a->v_stats && a->nblk > 0 && a->stats_stride >= 2), SMX_E_SHAPE);
-    SMX_REQUIRE(a->n_epochs == 0 || ((uintptr_t)a->v_partials & 15) == 0, SMX_E_ALIGN);
     EpilogueArgs P;
-    P.x = a->x; P.ldx = (long)a->ldx; P.rows = (long)a->rows; P.D = a->D;
-    P.rs = a->running_sum; P.rsq = a->running_sumsq; P.cnt = a->count; P.count_rows = a->count_rows;
-    P.ret = a->ret; P.n_ret = (long)a->n_ret; P.ret_mom = a->ret_moments;
-    P.vpartials = a->v_partials; P.n_epochs = a->n_epochs; P.nblk = a->nblk; P.vstats = a->v_stats;
-    P.vstride = a->stats_stride;
-    P.log_var = a->log_var; P.A = a->A; P.out4 = a->out4; P.ticket = (int*)a->ticket;
-    P.nz = a->x ? (a->D + 63) / 64 : 0;
-    const int nv = (a->n_epochs + 15) / 16;
-    hipLaunchKernelGGL(learn_epilogue_kernel, dim3(P.nz + 1 + nv), dim3(1024), 0, smx_s(stream), P);
+    const int count = learn_epilogue_args(a, P);
+    if (count < 0) return count;
+    hipLaunchKernelGGL(learn_epilogue_kernel, dim3(count), dim3(1024), 0, smx_s(stream), P);
     SMX_LAUNCH_CHECK();
     return SMX_OK;
 }

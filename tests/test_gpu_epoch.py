@@ -500,3 +500,34 @@ def test_learn_epilogue_equals_the_four_launches(K, rows, D, A, Ev, nblk, use_z)
         close(d['zf'].running_sumsq, c['zf'].running_sumsq, rtol=1e-5, atol=1e-2)
         close(d['zf'].count, c['zf'].count)
     assert int(d['ticket'][0]) == 0
+
+
+# rows: each of the column walk's three loops alone (sixteen loads in flight above 240 rows, four above 48, one), every
+# hand-over between them and a partial last row lane; widths: one column block, and three with a partial last one
+@pytest.mark.parametrize('rows,D,nan', [(r, d, False) for r in (1, 16, 17, 63, 65, 241, 257, 300, 600) for d in (24, 130)] +
+                         [(300, 130, True)])
+def test_zfilter_update_and_the_epilogue_z_role_leave_the_same_words(K, rows, D, nan):
+    """zupdate_kernel is the z role of the end-of-learn launch alone (one column walk, csrc/smx_learn_epilogue.inc.h): from
+    equal running sums both leave the same running_sum, running_sumsq and count, compared as integers."""
+    import types
+    g = torch.Generator().manual_seed(11 * rows + D)
+    obs = torch.randn(rows, 2, D, generator=g) * 2 + 0.5
+    if nan:
+        obs[rows // 2, 0, D // 3] = float('nan')
+    x = obs.cuda()[:, 0, :]                         # row stride 2 * D
+    rs0, rsq0 = torch.randn(D, generator=g) * 100, torch.rand(D, generator=g) * 5000 + 2000
+    ret, log_var = torch.randn(rows, generator=g).cuda(), torch.randn(3, generator=g).cuda()
+    bits = lambda v: v.contiguous().view(torch.int32)  # noqa: E731
+    a = [rs0.cuda(), rsq0.cuda(), torch.tensor([1000.0]).cuda()]
+    zf = types.SimpleNamespace(running_sum=rs0.cuda(), running_sumsq=rsq0.cuda(), count=torch.tensor([1000.0]).cuda())
+    ret_mom, out4 = torch.zeros(3).cuda(), torch.zeros(4).cuda()
+    ticket = torch.zeros(1, dtype=torch.int32).cuda()
+    for launch in range(2):                         # twice: the sums accumulate, the ticket must come back to zero
+        K.zfilter_update(x, a[0], a[1], a[2], rows)
+        K.learn_epilogue(ret, ret_mom, log_var, out4, ticket, zfilter=zf, x=x, count_rows=rows, n_epochs=0)
+        torch.cuda.synchronize()
+        for name, u, v in zip(('running_sum', 'running_sumsq', 'count'), a, (zf.running_sum, zf.running_sumsq, zf.count)):
+            assert torch.equal(bits(u), bits(v)), (launch, name)
+        assert int(ticket[0]) == 0
+    assert bool(torch.isnan(a[0]).any()) == nan and float(a[2][0]) == 1000.0 + 2 * rows
+    assert not torch.equal(bits(a[0]), bits(rs0.cuda()))
