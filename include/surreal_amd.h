@@ -1515,6 +1515,19 @@ int smx_synth_ppo_window_rollout_resets_f32(const struct smx_synth_ppo_window_ro
 int smx_synth_ddpg_rollout_resets_f32(const smx_ddpg_rollout_t* args, int32_t task,
                                       const struct smx_reset_stream* resets, smx_stream_t stream);
 
+/* smx_synth_ddpg_rollout_f32's four actors (variant: as there; NULL or all-zero: the plain actor) on a task, with an
+ * optional reset stream: the cross product of the actor variants with the tasks, on the shared clock.
+ *   SMX_TASK_DRIFT, resets NULL or !resets->enabled: forwards to smx_synth_ddpg_rollout_f32(args, variant, stream).
+ *   SMX_TASK_DRIFT with an enabled stream, an unknown task: SMX_E_UNSUPPORTED.
+ *   SMX_TASK_REACH: every variant smx_synth_ddpg_rollout_f32 takes, the step's environment half replaced by the task's
+ *   and the episodes' first rows by the stream's, as in smx_synth_ddpg_rollout_resets_f32 -- whose bytes the plain actor
+ *   leaves.  Nothing else of a step changes: a population's measuring step, the LayerNorm's LDS copy, the episode monitor
+ *   and the noise stream are smx_synth_ddpg_rollout_f32's.
+ * The refusals are the union of those entry points', with their codes, all before any launch.  Per-actor clocks
+ * (smx_synth_ddpg_rollout_clocks_f32) run on SMX_TASK_DRIFT only.  4, 8 and 16 actors per workgroup give the same bits. */
+int smx_synth_ddpg_rollout_variant_task_f32(const smx_ddpg_rollout_t* args, const struct smx_ddpg_actor_variant* variant,
+                                            int32_t task, const struct smx_reset_stream* resets, smx_stream_t stream);
+
 /* Evaluation on the device: whole episodes of the policy in ONE launch, nothing recorded -- the evaluation workers of
  * the reference (agent_mode eval_deterministic / eval_stochastic: surreal/agent/base.py:277-345 get_env, prepare_env_eval
  * and main_eval around the per-step loop of base.py:244-271, behind surreal/env/monitor.py:164-218 EvalTensorplexMonitor)

@@ -70,7 +70,8 @@ def main():
     ap.add_argument('--label', default='', help='copied into the --calls line')
     ap.add_argument('--task', default=None, choices=['drift', 'reach'],
                     help="with --calls: the environment's dynamics at obs-dim 3 x action-dim (reach's shape; --obs-dim is "
-                         'ignored), the plain actor on the one-launch route')
+                         'ignored) on the one-launch route: the plain actor, or with --layernorm / --param-noise their '
+                         'instantiations on the task')
     ap.add_argument('--random-resets', action='store_true',
                     help='with --task reach: draw every episode inside the launch from a reset stream (attach_resets)')
     args = ap.parse_args()

@@ -3,6 +3,7 @@
     python scripts/train_reach.py --algo ppo|ddpg [--actors N --J J --episode-len L --iters K --seed S --out FILE]
                                   [--random-resets [--heldout-episodes E]] [--eval-heldout] [--device-eval]
                                   [--snapshot-curve] [--save PATH [--save-every K]] [--resume PATH]
+                                  [--layernorm] [--param-noise normal|adaptive_normal [--actors-per-agent K]]
 
 Per iteration: one rollout chunk of all actors inside one launch (ppo_rollout_into / ddpg_rollout_into on a
 SyntheticVecEnv(task='reach') with a DeviceEpisodeMonitor and an exploration noise stream attached) -> the replay's device
@@ -36,7 +37,17 @@ evaluation made during training (asserted; "bits_match": true).  Without the fla
 baselines -- goes into ONE file (surreal_amd/utils/run_state.py; written atomically) after every K-th chunk (--save-every K)
 and after the last one.  --resume PATH: the run goes on from that file, with the same --algo / --actors / --J /
 --episode-len / --seed / reset flags (anything else: ValueError): from there on it prints exactly the lines the
-uninterrupted run prints, wall times apart -- the baseline line is not printed again.  Not with --snapshot-curve."""
+uninterrupted run prints, wall times apart -- the baseline line is not printed again.  Not with --snapshot-curve.
+DDPG only: --layernorm: a LayerNorm behind each hidden ReLU of actor and critic (use_layernorm; the rollout is the
+LayerNorm instantiation of the one-launch kernel on the task).  --param-noise T: parameter-space noise of type T on the
+device (SyntheticVecEnv.attach_param_noise, seed S + 5): every --actors-per-agent K consecutive actors (default 4, a
+multiple of 4 that divides --actors) act from their own perturbed copy of the actor; where the loop hands the learner's
+parameters to the agent the noise is refreshed ('adaptive_normal': every agent's sigma adapted to its measured action
+distance first).  With a plain-actor population every evaluation point also prints {"kind": "population", ...}: the
+deterministic return of every agent's perturbed actor on the evaluation's episodes, one launch for all
+(DeviceEvalSnapshots.from_param_noise), and the agents' sigmas.  Neither option goes with --device-eval or
+--snapshot-curve (the evaluation launch runs a plain actor without an attached noise).  Without them every printed line is
+what it was."""
 import argparse
 import json
 import os
@@ -114,7 +125,7 @@ def ppo_configs(D, A, n, folder):
     return lc, ppo_env_config(D, A), ppo_session_config(folder)
 
 
-def ddpg_configs(D, A, n, folder):
+def ddpg_configs(D, A, n, folder, layernorm=False, param_noise=None):
     from surreal_amd.main.ddpg_configs import ddpg_learner_config, ddpg_env_config, ddpg_session_config
     lc = ddpg_learner_config()
     lc.model.actor_fc_hidden_sizes = lc.model.critic_fc_hidden_sizes = list(HIDDEN)
@@ -126,6 +137,8 @@ def ddpg_configs(D, A, n, folder):
     lc.algo.exploration.noise_type, lc.algo.exploration.max_sigma = 'normal', 1.0
     lc.replay.batch_size = 256
     lc.replay.memory_size = 64 * 1024
+    lc.model.use_layernorm = bool(layernorm)
+    lc.algo.exploration.param_noise_type = param_noise
     return lc, ddpg_env_config(D, A, num_agents=n), ddpg_session_config(folder)
 
 
@@ -133,9 +146,14 @@ class Loop(object):
     """the loop of one algorithm: the training env, agent, learner and replay, and the evaluation pair"""
 
     def __init__(self, algo, actors, J, episode_len, seed, device=None, folder='/tmp/surreal_amd_reach',
-                 random_resets=False, heldout=0):
+                 random_resets=False, heldout=0, layernorm=False, param_noise=None, actors_per_agent=4):
         """random_resets: the training env draws its episodes (reset stream seed + 2); heldout = E > 0: the evaluation
-        runs E episodes per actor of the stream seed + 3, the same ones every time"""
+        runs E episodes per actor of the stream seed + 3, the same ones every time; layernorm / param_noise /
+        actors_per_agent (DDPG): the module docstring's"""
+        if algo != 'ddpg' and (layernorm or param_noise):
+            raise ValueError('--layernorm / --param-noise: DDPG only')
+        if param_noise not in (None, 'normal', 'adaptive_normal'):
+            raise ValueError('--param-noise: normal or adaptive_normal, got %r' % (param_noise,))
         torch.manual_seed(seed)
         self.seed = seed
         self.algo, self.n, self.J, self.L = algo, actors, J, episode_len
@@ -150,7 +168,7 @@ class Loop(object):
             from surreal_amd.agent import DDPGAgent as Agent
             from surreal_amd.learner.ddpg import DDPGLearner as Learner
             from surreal_amd.replay import UniformReplay as Replay
-            cfg = ddpg_configs(D, A, actors, folder)
+            cfg = ddpg_configs(D, A, actors, folder, layernorm, param_noise)
         self.lc = cfg[0]
         self.learner = Learner(*cfg)
         self.replay = Replay(*cfg)
@@ -171,6 +189,10 @@ class Loop(object):
             self.venv.reset()
         if self.heldout:
             self.eval_env.attach_resets(seed + 3)
+        self.layernorm = bool(layernorm)
+        # (the parameter noise of the training agent, on the device: populations of actors_per_agent actors)
+        self.pn = self.venv.attach_param_noise(self.agent, seed + 5, actors_per_agent=actors_per_agent) \
+            if param_noise else None
         self.env_steps = self.learns = self.device_eval_steps = 0
         self.T = episode_len                       # a chunk: one episode of every actor
 
@@ -195,11 +217,31 @@ class Loop(object):
         self.env_steps += self.n * self.T
         self.learner.publish_parameter(self.learns, message='chunk')
         self.agent.fetch_parameter()
+        if self.pn is not None:
+            self.pn.refresh()                      # (the device form of on_parameter_fetched: adapt, perturb again)
 
     def identity(self):
         """what a saved run and the loop that goes on from it must share"""
-        return {'algo': self.algo, 'actors': self.n, 'J': self.J, 'episode_len': self.L, 'seed': self.seed,
-                'random_resets': self.venv.resets is not None, 'heldout': self.heldout}
+        ident = {'algo': self.algo, 'actors': self.n, 'J': self.J, 'episode_len': self.L, 'seed': self.seed,
+                 'random_resets': self.venv.resets is not None, 'heldout': self.heldout}
+        if self.layernorm:
+            ident['layernorm'] = True
+        if self.pn is not None:
+            ident.update(param_noise=self.pn.type, actors_per_agent=self.pn.actors_per_agent)
+        return ident
+
+    def population_line(self, it):
+        """a plain-actor population: the deterministic return of every agent's perturbed actor on the evaluation's
+        episodes (one launch over all agents), and the agents' sigmas; None for a LayerNorm population, which the
+        evaluation launch does not run"""
+        if self.pn is None or self.pn.ln:
+            return None
+        from surreal_amd.env.monitor import DeviceEvalSnapshots
+        E, kw = self.snapshot_curve_args()
+        returns = DeviceEvalSnapshots.from_param_noise(self.venv, self.pn).evaluate(E, **kw)      # [agents, n, E]
+        return {'kind': 'population', 'algo': self.algo, 'iteration': it, 'generation': self.pn.generation,
+                'agent_returns': [float(v) for v in returns.mean(dim=(1, 2)).cpu().numpy()],
+                'sigma': [float(v) for v in self.pn.sigma.cpu().numpy()]}
 
     def state_parts(self, **script):
         """the parts of run_state.save_run: every holder's state (live tensors: save_run copies) and, under 'script',
@@ -295,14 +337,17 @@ class Loop(object):
 
 def train(algo, actors=64, J=2, episode_len=50, iters=None, seed=0, eval_every=10, device=None, log=print,
           random_resets=False, heldout_episodes=4, eval_heldout=False, device_eval=False, snapshot_curve=False,
-          save=None, save_every=None, resume=None):
+          save=None, save_every=None, resume=None, layernorm=False, param_noise=None, actors_per_agent=4):
     """-> (the baselines, the curve: one dict per evaluation).  random_resets / eval_heldout / device_eval / save /
-    save_every (in chunks) / resume: the module docstring's"""
+    save_every (in chunks) / resume / layernorm / param_noise / actors_per_agent: the module docstring's"""
     from surreal_amd.utils import run_state as RS
     iters = DEFAULT_ITERS[algo] if iters is None else iters
     heldout = int(heldout_episodes) if (random_resets or eval_heldout) else 0
     if snapshot_curve and (save or resume):
         raise ValueError('--snapshot-curve keeps its snapshots outside the saved run: not with --save / --resume')
+    if (layernorm or param_noise) and (device_eval or snapshot_curve):
+        raise ValueError('--layernorm / --param-noise: not with --device-eval / --snapshot-curve (the evaluation launch '
+                         'runs a plain actor without an attached parameter noise)')
     if save_every is not None and (not save or int(save_every) < 1):
         raise ValueError('--save-every K: a positive number of chunks, with --save PATH')
     parts = RS.load_run(resume) if resume else None
@@ -317,7 +362,10 @@ def train(algo, actors=64, J=2, episode_len=50, iters=None, seed=0, eval_every=1
                     iters=iters, seed=seed)
     if parts is None:
         log(json.dumps(base))
-    loop = Loop(algo, actors, J, episode_len, seed, device, random_resets=random_resets, heldout=heldout)
+    variant = {}
+    if layernorm or param_noise:
+        variant = dict(layernorm=layernorm, param_noise=param_noise, actors_per_agent=actors_per_agent)
+    loop = Loop(algo, actors, J, episode_len, seed, device, random_resets=random_resets, heldout=heldout, **variant)
     first = int(loop.load_parts(parts)['iteration']) if parts is not None else 0
     if first > iters:
         raise ValueError('the saved run has done %d chunks, --iters is %d' % (first, iters))
@@ -343,6 +391,10 @@ def train(algo, actors=64, J=2, episode_len=50, iters=None, seed=0, eval_every=1
                           'gap_closed': (ev - base['zero_action_return']) / gap, 'wall_s': round(time.time() - t0, 3)})
             curve[-1].update(extra)
             log(json.dumps(curve[-1]))
+            pop = loop.population_line(it)
+            if pop is not None:
+                log(json.dumps(pop))
+                curve[-1]['population'] = pop
             if snaps is not None:
                 snaps.store(len(curve) - 1)          # (both evaluations fetched: the parameters they ran)
                 if device_eval:
@@ -390,6 +442,10 @@ def main():
                     'chunk (and after every K-th: --save-every)')
     ap.add_argument('--save-every', type=int, default=None, metavar='K', help='also save after every K-th chunk')
     ap.add_argument('--resume', default=None, metavar='PATH', help='go on from a file written by --save')
+    ap.add_argument('--layernorm', action='store_true', help='DDPG: LayerNorm actor and critic (use_layernorm)')
+    ap.add_argument('--param-noise', choices=['normal', 'adaptive_normal'], default=None,
+                    help='DDPG: parameter-space noise on the device, one perturbed actor per agent')
+    ap.add_argument('--actors-per-agent', type=int, default=4, metavar='K', help='actors that share a perturbation')
     args = ap.parse_args()
     lines = []
 
@@ -399,7 +455,8 @@ def main():
     train(args.algo, args.actors, args.J, args.episode_len, args.iters, args.seed, args.eval_every, log=log,
           random_resets=args.random_resets, heldout_episodes=args.heldout_episodes, eval_heldout=args.eval_heldout,
           device_eval=args.device_eval, snapshot_curve=args.snapshot_curve, save=args.save, save_every=args.save_every,
-          resume=args.resume)
+          resume=args.resume, layernorm=args.layernorm, param_noise=args.param_noise,
+          actors_per_agent=args.actors_per_agent)
     if args.out:
         with open(args.out, 'a') as f:
             f.write('\n'.join(lines) + '\n')

@@ -584,6 +584,8 @@ _SIGS = {
     'smx_synth_ppo_window_rollout_resets_f32': (c_int32, [POINTER(SynthPpoWindowRollout), c_int32, POINTER(ResetStream),
                                                           _P]),
     'smx_synth_ddpg_rollout_resets_f32': (c_int32, [POINTER(DdpgRollout), c_int32, POINTER(ResetStream), _P]),
+    'smx_synth_ddpg_rollout_variant_task_f32': (c_int32, [POINTER(DdpgRollout), POINTER(DdpgActorVariant), c_int32,
+                                                          POINTER(ResetStream), _P]),
     'smx_synth_eval_supported': (c_int32, [c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32]),
     'smx_synth_ppo_eval_f32': (c_int32, [POINTER(SynthPpoEval), _P]),
     'smx_synth_ddpg_eval_f32': (c_int32, [POINTER(SynthDdpgEval), _P]),

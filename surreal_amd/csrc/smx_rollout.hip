@@ -46,6 +46,9 @@
 //                               and the plain DDPG launch on another task's dynamics (SMX_TASK_REACH: EnvLanes::step_reach;
 //                               ppo_window_task_kernel, lstm_window_task_kernel, ddpg_rollout_kernel<..., TASK>).
 //
+//   smx_synth_ddpg_rollout_variant_task_f32  the DDPG launch of any of the four actors (struct smx_ddpg_actor_variant) on a
+//                               task, with or without the reset stream: ddpg_rollout_kernel<RG, NT, POP, LN, false, TASK>.
+//
 //   smx_synth_ppo_eval_f32 / smx_synth_ddpg_eval_f32  evaluation: whole episodes of the policy as independent (actor, episode)
 //                               rows of one launch, nothing recorded, the fp64 returns stored once (ppo_eval_kernel,
 //                               ddpg_eval_kernel: new kernels that share the pieces above, not the bodies).
@@ -1219,12 +1222,12 @@ constexpr int RLN_MAXC = 10;                         // columns per lane: H1, H2
 template <bool POP, bool LN, bool CLK, int TASK = SMX_TASK_DRIFT>
 using DdpgKernelArgs = std::conditional_t<TASK != SMX_TASK_DRIFT, WithRst<DdpgArgs<POP, LN>>,
                                           std::conditional_t<CLK, WithClk<DdpgArgs<POP, LN>>, DdpgArgs<POP, LN>>>;
-// TASK (the plain actor on the shared clock only; smx_synth_ddpg_rollout_task_f32): the environment's dynamics, EnvLanes'
+// TASK (any actor on the shared clock; smx_synth_ddpg_rollout_variant_task_f32): the environment's dynamics, EnvLanes'
 // TASK.  (A template parameter of the kernel itself: with the body moved into a function that two kernels call, every
 // existing instantiation compiled to other code -- its arguments no longer read as kernel arguments.)
 template <int RG, int NT, bool POP = false, bool LN = false, bool CLK = false, int TASK = SMX_TASK_DRIFT>
 __global__ __launch_bounds__(RNTH) void ddpg_rollout_kernel(DdpgKernelArgs<POP, LN, CLK, TASK> G) {
-    static_assert(TASK == SMX_TASK_DRIFT || !(POP || LN || CLK), "tasks: the plain actor on the shared clock");
+    static_assert(TASK == SMX_TASK_DRIFT || !CLK, "tasks: the shared clock");
     constexpr int RB = 4 * RG;                       // actors per workgroup
     const auto C = clk_of(G);
     extern __shared__ float sm[];
@@ -2682,8 +2685,8 @@ static int ln_args(const smx_mlp3_t& net, const smx_ddpg_actor_variant& v, LnTai
 
 // the launch for one of the four actors: the block's checks, then the population's, then the LayerNorm's; clocked: with
 // the actors' own clocks (checked behind the block: the table numbers the call's closing pairs, rows <= capacity
-// keeps them distinct), the block's t / episode_len ignored; task: SMX_TASK_DRIFT, or (the plain actor on the shared clock
-// only) a task smx_synth_task_supported takes; resets: its reset stream or null
+// keeps them distinct), the block's t / episode_len ignored; task: SMX_TASK_DRIFT, or (on the shared clock only) a task
+// smx_synth_task_supported takes; resets: its reset stream or null
 template <bool POP, bool LN>
 static int ddpg_rollout_launch(const smx_ddpg_rollout_t* a, const smx_ddpg_actor_variant& v, const smx_actor_clocks* clocks,
                                bool clocked, smx_stream_t stream, int task = SMX_TASK_DRIFT,
@@ -2699,7 +2702,7 @@ static int ddpg_rollout_launch(const smx_ddpg_rollout_t* a, const smx_ddpg_actor
     }
     int rc = persistent_ddpg_args(a, G, clocked);
     if (rc != SMX_OK) return rc;
-    SMX_REQUIRE(synth_task_ok(task, a->D, a->A) && !((POP || LN || clocked) && task != SMX_TASK_DRIFT), SMX_E_UNSUPPORTED);
+    SMX_REQUIRE(synth_task_ok(task, a->D, a->A) && !(clocked && task != SMX_TASK_DRIFT), SMX_E_UNSUPPORTED);
     SMX_REQUIRE(!resets || reset_shape_ok(*resets, a->n), SMX_E_SHAPE);
     ClkArgs C = {};
     if (clocked) {
@@ -2732,27 +2735,25 @@ static int ddpg_rollout_launch(const smx_ddpg_rollout_t* a, const smx_ddpg_actor
     if (clocked)
         return launch<ddpg_rollout_kernel<1, 3, POP, LN, true>, ddpg_rollout_kernel<2, 3, POP, LN, true>,
                       ddpg_rollout_kernel<4, 2, POP, LN, true>>(with_clocks(G, C), rb, lds, stream);
-    if constexpr (!POP && !LN) {
-        if (task == SMX_TASK_REACH)
-            return launch<ddpg_rollout_kernel<1, 3, false, false, false, SMX_TASK_REACH>,
-                          ddpg_rollout_kernel<2, 3, false, false, false, SMX_TASK_REACH>,
-                          ddpg_rollout_kernel<4, 2, false, false, false, SMX_TASK_REACH>>(with_resets(G, resets), rb, lds,
-                                                                                          stream);
-    }
+    if (task == SMX_TASK_REACH)
+        return launch<ddpg_rollout_kernel<1, 3, POP, LN, false, SMX_TASK_REACH>,
+                      ddpg_rollout_kernel<2, 3, POP, LN, false, SMX_TASK_REACH>,
+                      ddpg_rollout_kernel<4, 2, POP, LN, false, SMX_TASK_REACH>>(with_resets(G, resets), rb, lds, stream);
     return launch<ddpg_rollout_kernel<1, 3, POP, LN>, ddpg_rollout_kernel<2, 3, POP, LN>,
                   ddpg_rollout_kernel<4, 2, POP, LN>>(G, rb, lds, stream);
 }
 
-// both DDPG entry points: the actor variant picks the instantiation
+// the DDPG entry points: the actor variant picks the instantiation
 static int ddpg_rollout_variant(const smx_ddpg_rollout_t* a, const smx_ddpg_actor_variant* variant,
-                                const smx_actor_clocks* clocks, bool clocked, smx_stream_t stream) {
+                                const smx_actor_clocks* clocks, bool clocked, smx_stream_t stream,
+                                int task = SMX_TASK_DRIFT, const smx_reset_stream* resets = nullptr) {
     static const smx_ddpg_actor_variant plain = {};
     const smx_ddpg_actor_variant& v = variant ? *variant : plain;
     if (v.packed_pop)
-        return v.ln ? ddpg_rollout_launch<true, true>(a, v, clocks, clocked, stream)
-                    : ddpg_rollout_launch<true, false>(a, v, clocks, clocked, stream);
-    return v.ln ? ddpg_rollout_launch<false, true>(a, v, clocks, clocked, stream)
-                : ddpg_rollout_launch<false, false>(a, v, clocks, clocked, stream);
+        return v.ln ? ddpg_rollout_launch<true, true>(a, v, clocks, clocked, stream, task, resets)
+                    : ddpg_rollout_launch<true, false>(a, v, clocks, clocked, stream, task, resets);
+    return v.ln ? ddpg_rollout_launch<false, true>(a, v, clocks, clocked, stream, task, resets)
+                : ddpg_rollout_launch<false, false>(a, v, clocks, clocked, stream, task, resets);
 }
 
 extern "C" int smx_synth_ddpg_rollout_f32(const smx_ddpg_rollout_t* a, const struct smx_ddpg_actor_variant* variant,
@@ -2776,6 +2777,17 @@ extern "C" int smx_synth_ddpg_rollout_task_f32(const smx_ddpg_rollout_t* a, int3
 extern "C" int smx_synth_ddpg_rollout_resets_f32(const smx_ddpg_rollout_t* a, int32_t task,
                                                  const struct smx_reset_stream* resets, smx_stream_t stream) {
     return ddpg_rollout_task(a, task, resets && resets->enabled ? resets : nullptr, stream);
+}
+
+// any actor variant on a task, with the reset stream or (null, or a disabled one) without
+extern "C" int smx_synth_ddpg_rollout_variant_task_f32(const smx_ddpg_rollout_t* a,
+                                                       const struct smx_ddpg_actor_variant* variant, int32_t task,
+                                                       const struct smx_reset_stream* resets, smx_stream_t stream) {
+    if (resets && !resets->enabled) resets = nullptr;
+    SMX_REQUIRE(!(resets && task == SMX_TASK_DRIFT), SMX_E_UNSUPPORTED);
+    if (task == SMX_TASK_DRIFT) return smx_synth_ddpg_rollout_f32(a, variant, stream);
+    SMX_REQUIRE(task == SMX_TASK_REACH, SMX_E_UNSUPPORTED);
+    return ddpg_rollout_variant(a, variant, nullptr, false, stream, task, resets);
 }
 
 extern "C" int smx_synth_ddpg_rollout_clocks_f32(const smx_ddpg_rollout_t* a, const struct smx_ddpg_actor_variant* variant,

@@ -925,16 +925,21 @@ class SyntheticVecEnv(object):
         """how ddpg_rollout_into runs `agent` -> (route, refusal): 'camera' (the per-step camera path), 'launch' (ONE
         launch), 'two_launch' (the persistent kernel's two-launch reference) or 'steps' (forward_actor and a step launch
         per step); refusal (exception class, message) or None.  A LayerNorm actor takes the launch where the kernels run
-        one (kernels.ddpg_ln_launch); else it stays on the per-step path, refused under a parameter noise."""
+        one (kernels.ddpg_ln_launch); else it stays on the per-step path, refused under a parameter noise.  On a task
+        env only the 'launch' route runs: the plain actor, and a LayerNorm actor or an attached parameter noise where the
+        kernels run them there (kernels.ddpg_variant_task_launch)."""
         K, model, pn = self.K, agent.model, self.param_noise
         camera = model.is_pixel_input
         if self.task != 'drift':
-            what = ('a camera agent' if camera else 'a LayerNorm actor' if model.use_layernorm else
-                    'an attached parameter noise' if pn is not None else
+            ln = not camera and bool(model.use_layernorm)
+            variants = not camera and KN.ddpg_variant_task_launch(K) and (not ln or KN.ddpg_ln_launch(K))
+            what = ('a camera agent' if camera else 'a LayerNorm actor' if ln and not variants else
+                    'an attached parameter noise' if pn is not None and not variants else
                     'per-actor episode clocks' if self.per_actor_clocks else
                     "reference=True (the 'two_launch' route)" if reference else
                     "an actor shape the one-launch rollout does not take (the 'steps' route)"
-                    if not K.synth_ddpg_rollout_supported(model.actor) else None)
+                    if not K.synth_ddpg_rollout_supported(model.actor, **(dict(ln=True) if ln and variants else {}))
+                    else None)
             if what is not None:
                 return None, self._drift_only('ddpg_rollout_into', what, throw=False)
         refusal = self._camera_refusal('ddpg_rollout_into', agent, camera)
@@ -991,7 +996,10 @@ class SyntheticVecEnv(object):
         is smx_synth_ddpg_pixel_pool_step: the step's frame goes ONCE into the replay's pool, which is the history as
         well, and the closing rows carry two counters in place of the stacked frames; such a call may go round the ring.
         With per-actor episode clocks (the ONE-launch route only): the call's row table from the clocks
-        (smx_actor_clock_rows_i32), then smx_synth_ddpg_rollout_clocks_f32 -- as in ppo_rollout_into."""
+        (smx_actor_clock_rows_i32), then smx_synth_ddpg_rollout_clocks_f32 -- as in ppo_rollout_into.
+        On a task env (the ONE-launch route on the shared clock only): the plain actor (smx_synth_ddpg_rollout_task_f32 /
+        _resets_f32) and, where the kernels run them there (kernels.ddpg_variant_task_launch), a LayerNorm actor and an
+        attached parameter noise (smx_synth_ddpg_rollout_variant_task_f32) -- variant, task and reset stream in one call."""
         route, refusal = self._ddpg_route(agent, reference)
         if refusal is not None:
             raise refusal[0](refusal[1])

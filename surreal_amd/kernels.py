@@ -51,6 +51,13 @@ def ddpg_ln_launch(kernels):
     return bool(getattr(kernels, 'ddpg_ln_launch', False))
 
 
+def ddpg_variant_task_launch(kernels):
+    """whether `kernels` runs a LayerNorm actor and a parameter-noise population in the one-launch DDPG rollout on a task
+    env (the ln / pn arguments of synth_ddpg_rollout together with task and resets): its `ddpg_variant_task_launch`
+    attribute; an object without one runs the plain actor there.  A property of the kernels object alone."""
+    return bool(getattr(kernels, 'ddpg_variant_task_launch', False))
+
+
 class HipKernels(object):
     name = 'hip'
 
@@ -1112,6 +1119,8 @@ class HipKernels(object):
 
     # a LayerNorm actor runs in the one-launch DDPG rollout and under the parameter noise (ddpg_ln_launch(), above)
     ddpg_ln_launch = True
+    # both of them on a task env too (ddpg_variant_task_launch(), above)
+    ddpg_variant_task_launch = True
     # TD3 on the row schedule (ddpg_rows_td3(), above)
     ddpg_rows_td3 = True
     # use_layernorm on the row schedule (ddpg_rows_ln(), above)
@@ -1164,6 +1173,16 @@ class HipKernels(object):
         assert pn.pop.shape[0] == int(pn.agents) == pn.dist.numel() and pn.dist.is_contiguous()
         return L.ptr(pn.pop), pn.pop.shape[1], L.ptr(pn.dist)
 
+    @classmethod
+    def _variant_args(cls, net, ln, ln_eps, pn, measure_step):
+        """struct smx_ddpg_actor_variant of synth_ddpg_rollout's ln / ln_eps / pn / measure_step"""
+        v = L.DdpgActorVariant()
+        v.ln, v.ln_eps = cls._ln_ptr(net, ln), float(ln_eps)
+        if pn is not None:
+            v.packed_pop, v.packed_stride, v.dist = cls._population_ptrs(pn)
+            v.actors_per_agent, v.agents, v.measure_step = int(pn.actors_per_agent), int(pn.agents), int(measure_step)
+        return v
+
     def synth_ddpg_rollout(self, net, packed, r, steps, actors_per_workgroup=0, monitor=None, noise=None, ln=None,
                            ln_eps=0.0, pn=None, measure_step=-1, clocks=None, task='drift', resets=None):
         """`steps` DDPG acting + environment steps of all actors with their n-step transitions written into the ring
@@ -1175,26 +1194,28 @@ class HipKernels(object):
         (-1: never) for pn.dist.
         clocks: an episode clock per actor (_clock_args; smx_synth_ddpg_rollout_clocks_f32) -- r['t'] / r['episode_len']
         are then ignored and the closing transitions go to the rows of clocks['row_off'] (actor_clock_rows, advance 1).
-        task: the environment's dynamics (env/tasks.py; smx_synth_ddpg_rollout_task_f32: the plain actor on the shared
-        clock only).  resets: a task env's reset stream (_reset_args; smx_synth_ddpg_rollout_resets_f32) -- r['init_state']
-        is then not read"""
+        task: the environment's dynamics (env/tasks.py; smx_synth_ddpg_rollout_task_f32, with ln or pn
+        smx_synth_ddpg_rollout_variant_task_f32: the shared clock only).  resets: a task env's reset stream (_reset_args;
+        smx_synth_ddpg_rollout_resets_f32) -- r['init_state'] is then not read"""
         if r['eps'] is not None:
             assert r['eps'].is_contiguous() and tuple(r['eps'].shape) == (steps, r['state'].shape[0], net.OUT)
         p = self._ddpg_args(r, steps, net, packed, actors_per_workgroup, monitor, noise)
         assert resets is None or task != 'drift', "task 'drift' has no reset distribution"
         if task != 'drift':
-            assert ln is None and pn is None and clocks is None, 'a task env runs the plain actor on one shared clock'
+            assert clocks is None, 'a task env runs on one shared clock'
+            if ln is not None or pn is not None:
+                # the actor variants on a task (smx_synth_ddpg_rollout_variant_task_f32)
+                v = self._variant_args(net, ln, ln_eps, pn, measure_step)
+                L.call('smx_synth_ddpg_rollout_variant_task_f32', ctypes.byref(p), ctypes.byref(v), self._task_id(task),
+                       ctypes.byref(self._reset_args(resets)) if resets is not None else None, self._st())
+                return
             if resets is not None:
                 L.call('smx_synth_ddpg_rollout_resets_f32', ctypes.byref(p), self._task_id(task),
                        ctypes.byref(self._reset_args(resets)), self._st())
                 return
             L.call('smx_synth_ddpg_rollout_task_f32', ctypes.byref(p), self._task_id(task), self._st())
             return
-        v = L.DdpgActorVariant()
-        v.ln, v.ln_eps = self._ln_ptr(net, ln), float(ln_eps)
-        if pn is not None:
-            v.packed_pop, v.packed_stride, v.dist = self._population_ptrs(pn)
-            v.actors_per_agent, v.agents, v.measure_step = int(pn.actors_per_agent), int(pn.agents), int(measure_step)
+        v = self._variant_args(net, ln, ln_eps, pn, measure_step)
         if clocks is not None:
             c = self._clock_args(clocks, r['state'].shape[0], steps)
             L.call('smx_synth_ddpg_rollout_clocks_f32', ctypes.byref(p), ctypes.byref(v), ctypes.byref(c), self._st())
