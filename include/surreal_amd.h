@@ -1462,14 +1462,24 @@ int smx_synth_ddpg_rollout_clocks_f32(const smx_ddpg_rollout_t* args, const stru
  *   a = clip(action, -1, 1);  v'[j] = clamp((0.9f v[j]) + (0.2f a[j]), -1, 1);  p'[j] = clamp(p[j] + (0.1f v'[j]), -10, 10);
  *   g'[j] = g[j];  d[j] = p'[j] - g[j];  reward = (float)(-(sum_j d[j]^2 + 0.01 sum_j a[j]^2)), both sums in fp64, j
  *   ascending, one term at a time;  done and the reset as in smx_synth_env_step_f32.
+ * SMX_TASK_ARM (the same file): a planar arm of A links of length w = 2^-ceil(log2 A), D = 2 A + 2, the state row is
+ * [theta (A) | omega (A) | g (2)] -- each link's absolute orientation, its angular velocity, the fingertip's goal; the rule:
+ *   a = clip(action, -1, 1);  omega'[j] = clamp((0.9f omega[j]) + (0.4f a[j]), -1, 1);
+ *   theta'[j] = clamp(theta[j] + (0.2f omega'[j]), -3.1415927f, 3.1415927f)  (joint limits, no wrap);  g' = g;
+ *   s[j], c[j] = theta'[j] P_S(theta'[j]^2), P_C(theta'[j]^2): the Taylor polynomials of sine and cosine with the fp32
+ *   coefficients (float)((-1)^k / (2k+1)!), k <= 8, and (float)((-1)^k / (2k)!), k <= 9, by Horner, each operation rounded
+ *   (the polynomials are the definition: no library function);
+ *   dx = (sum_j c[j]) w - g[0];  dy = (sum_j s[j]) w - g[1];  reward = (float)(-((dx dx + dy dy) + 0.01 sum_j a[j]^2)),
+ *   the three sums and what follows them in fp64, j ascending, one term at a time.
  * smx_synth_task_supported: 1 where the task entry points below take (task, D, A) -- DRIFT: D, A > 0; REACH: D == 3 A
- * and A <= 21 (a row's elements sit in one wavefront) -- else 0 (an unknown task too).
+ * and A <= 21; ARM: D == 2 A + 2 and A <= 30 (a row's elements sit in one wavefront) -- else 0 (an unknown task too).
  * The three entry points take the arguments of smx_synth_env_step_f32, smx_synth_ppo_window_rollout_f32 and
  * smx_synth_ddpg_rollout_f32 (the plain actor: no variant) and a task.  With SMX_TASK_DRIFT each forwards to that entry
  * point.  What smx_synth_task_supported refuses returns SMX_E_UNSUPPORTED before any launch; every other check is the
  * forwarded entry point's.  4, 8 and 16 actors per workgroup give the same bits. */
 #define SMX_TASK_DRIFT 0
 #define SMX_TASK_REACH 1
+#define SMX_TASK_ARM 2
 int32_t smx_synth_task_supported(int32_t task, int32_t D, int32_t A);
 int smx_synth_task_env_step_f32(float* state, const float* init_state, const float* actions,
                                 int32_t n, int32_t D, int32_t A, int32_t t, int32_t episode_len,
@@ -1486,13 +1496,16 @@ int smx_synth_ddpg_rollout_task_f32(const smx_ddpg_rollout_t* args, int32_t task
  *   x[0..3] = Philox4x32-10(counter = (g, low32(e), high32(e), 0x52530000 | (k >> 2)), key = (low32(seed), high32(seed)))
  *   u = (float)(x[k & 3] >> 8) * 2^-23 - 1       (a 24-bit integer, scaled, minus one: exact in fp32; u in [-1, 1))
  *   a position (k < A) or a goal (k >= 2 A) is u; a velocity is +0.
+ * SMX_TASK_ARM draws its row [theta | omega | g], k < 2 A + 2, from the same blocks: an orientation (k < A) is u, an
+ * angular velocity +0, a goal coordinate (k >= 2 A) 0.25f * u.
  * The fourth counter word keeps these blocks apart from the exploration stream's (j >> 2 < 16) and the parameter noise's
  * (0x504E0001).  `episode` is the index of the NEXT episode to begin: the i-th episode end of a call (i from 0; the
  * actors share one clock, so they share the index) draws episode + i for every actor, and the caller adds the call's
  * episode ends afterwards -- nothing is written back.  An actor's reset states depend on its global id and the episode
  * index only: not on n, on the steps of a call, on how a run is cut into calls or on how the actors are split over launches.
  * smx_reset_fill_f32: out [n, D] <- the rows of episode resets->episode (enabled is not read); task must be one with a
- * reset distribution (SMX_TASK_REACH with D == 3 A', A' <= 21: else SMX_E_UNSUPPORTED).
+ * reset distribution (SMX_TASK_REACH with D == 3 A', A' <= 21, or SMX_TASK_ARM with D == 2 A' + 2, A' <= 30: else
+ * SMX_E_UNSUPPORTED).
  * The three *_resets_f32 entry points take what the *_task_f32 ones take and a stream.  resets NULL or !resets->enabled:
  * exactly the task entry point (init_state is read at an episode end).  Enabled: init_state is not read (it may be any
  * non-NULL pointer).  Before any launch: an enabled stream on SMX_TASK_DRIFT is SMX_E_UNSUPPORTED; actor_base < 0,
@@ -1519,7 +1532,7 @@ int smx_synth_ddpg_rollout_resets_f32(const smx_ddpg_rollout_t* args, int32_t ta
  * optional reset stream: the cross product of the actor variants with the tasks, on the shared clock.
  *   SMX_TASK_DRIFT, resets NULL or !resets->enabled: forwards to smx_synth_ddpg_rollout_f32(args, variant, stream).
  *   SMX_TASK_DRIFT with an enabled stream, an unknown task: SMX_E_UNSUPPORTED.
- *   SMX_TASK_REACH: every variant smx_synth_ddpg_rollout_f32 takes, the step's environment half replaced by the task's
+ *   SMX_TASK_REACH, SMX_TASK_ARM: every variant smx_synth_ddpg_rollout_f32 takes, the step's environment half replaced by the task's
  *   and the episodes' first rows by the stream's, as in smx_synth_ddpg_rollout_resets_f32 -- whose bytes the plain actor
  *   leaves.  Nothing else of a step changes: a population's measuring step, the LayerNorm's LDS copy, the episode monitor
  *   and the noise stream are smx_synth_ddpg_rollout_f32's.
@@ -1536,7 +1549,7 @@ int smx_synth_ddpg_rollout_variant_task_f32(const smx_ddpg_rollout_t* args, cons
  * ROWS: row r = a * episodes + i is episode resets.episode + i (first_episode + i) of local actor a.  The launch runs
  * n * episodes rows on workgroups of actors_per_workgroup = 4, 8 or 16 rows (0: chosen as in smx_synth_rollout_f32, from
  * the rows) and walks every row through exactly episode_len steps:
- *   start:  resets.enabled (SMX_TASK_REACH only): the row the reset stream draws for (seed, actor_base + a,
+ *   start:  resets.enabled (SMX_TASK_REACH, SMX_TASK_ARM): the row the reset stream draws for (seed, actor_base + a,
  *           resets.episode + i), formed in the launch; else init_state[a] ([n, D]; with an enabled stream not read, any
  *           non-NULL pointer).  No state buffer is read or written; an LSTM policy starts every episode from zero h, c
  *           (PPOAgent.reset, surreal/agent/ppo_agent.py:169-178).

@@ -68,12 +68,13 @@ def main():
     ap.add_argument('--per-step', action='store_true', help='with --layernorm --calls: the per-step path (reference=True)')
     ap.add_argument('--calls', type=int, default=0, help='time this many single rollout calls, print their median and stop')
     ap.add_argument('--label', default='', help='copied into the --calls line')
-    ap.add_argument('--task', default=None, choices=['drift', 'reach'],
+    ap.add_argument('--task', default=None, choices=['drift', 'reach', 'arm'],
                     help="with --calls: the environment's dynamics at obs-dim 3 x action-dim (reach's shape; --obs-dim is "
-                         'ignored) on the one-launch route: the plain actor, or with --layernorm / --param-noise their '
-                         'instantiations on the task')
+                         'ignored; arm: at its own 2 x action-dim + 2) on the one-launch route: the plain actor, or with '
+                         '--layernorm / --param-noise their instantiations on the task')
+    ap.add_argument('--arm-shape', action='store_true', help="with --task drift: arm's obs-dim, 2 x action-dim + 2")
     ap.add_argument('--random-resets', action='store_true',
-                    help='with --task reach: draw every episode inside the launch from a reset stream (attach_resets)')
+                    help='with --task reach | arm: draw every episode inside the launch from a reset stream (attach_resets)')
     args = ap.parse_args()
     if args.param_noise and not args.calls:
         ap.error('--param-noise measures single calls: give --calls N')
@@ -83,10 +84,10 @@ def main():
         ap.error('--episode-lens measures single calls of the one-launch path: give --calls N')
     if args.task and not args.calls:
         ap.error('--task measures single calls of the one-launch path: give --calls N')
-    if args.random_resets and args.task != 'reach':
+    if args.random_resets and args.task not in ('reach', 'arm'):
         ap.error('--random-resets goes with --task reach')
     if args.task:
-        args.obs_dim = 3 * args.action_dim
+        args.obs_dim = 2 * args.action_dim + 2 if args.task == 'arm' or args.arm_shape else 3 * args.action_dim
     n, T, D, A = args.actors, args.steps, args.obs_dim, args.action_dim
     H1, H2 = args.hidden
     lc = ddpg_learner_config()
@@ -107,7 +108,7 @@ def main():
     if args.episode_lens:
         lo, hi = args.episode_lens
         episode_len = [lo + a % (hi - lo + 1) for a in range(n)]
-    task = {'task': args.task} if args.task == 'reach' else {}       # ('drift': no keyword, as before there were tasks)
+    task = {'task': args.task} if args.task in ('reach', 'arm') else {}  # ('drift': no keyword, as before there were tasks)
     venv = SyntheticVecEnv(n, D, A, episode_len=episode_len, device='cuda', **task)
     if args.random_resets:
         venv.attach_resets(seed=3)

@@ -138,12 +138,12 @@ def bench_loop(reps, warmup, n=64, T=128, L=1000, D=17, A=6, monitor=False, devi
 def bench_task_calls(args):
     """--task: single calls of the one-launch windowed rollout on a task's dynamics"""
     n, T, A, L = args.actors, args.steps, args.action_dim, args.episode_len
-    D, N, stride = 3 * A, 25, 20
+    D, N, stride = (2 * A + 2 if args.task == 'arm' or args.arm_shape else 3 * A), 25, 20
     if L < N:                                       # (a window never crosses an episode end)
         N, stride = min(N, L), min(stride, L)
     agent, cfg = PW.make_agent(D, A, N, stride, hidden=(300, 200), rnn_hidden=None, memory_size=n * (T // min(N, stride) + 2))
     replay = FIFOReplay(*cfg)
-    task = {'task': args.task} if args.task == 'reach' else {}       # ('drift': no keyword, as before there were tasks)
+    task = {'task': args.task} if args.task in ('reach', 'arm') else {}  # ('drift': no keyword, as before there were tasks)
     venv = SyntheticVecEnv(n, D, A, episode_len=L, **task)
     venv.attach_noise(seed=1)
     if args.random_resets:
@@ -180,8 +180,10 @@ def main():
     ap.add_argument('--episode-lens', type=int, nargs=2, metavar=('LO', 'HI'), default=None,
                     help='the rollout cases with an episode clock per actor: actor a has episodes of LO + a %% (HI - LO + 1) '
                          'steps (the loop case is not run)')
-    ap.add_argument('--task', default=None, choices=['drift', 'reach'], help='single calls on this task (see the top)')
-    ap.add_argument('--random-resets', action='store_true', help='with --task reach: episodes drawn from a reset stream')
+    ap.add_argument('--task', default=None, choices=['drift', 'reach', 'arm'],
+                    help='single calls on this task (see the top; arm: at obs-dim 2 x action-dim + 2)')
+    ap.add_argument('--arm-shape', action='store_true', help="with --task drift: arm's obs-dim, 2 x action-dim + 2")
+    ap.add_argument('--random-resets', action='store_true', help='with --task reach | arm: episodes drawn from a reset stream')
     ap.add_argument('--calls', type=int, default=60)
     ap.add_argument('--actors', type=int, default=1024)
     ap.add_argument('--steps', type=int, default=128)
@@ -189,7 +191,7 @@ def main():
     ap.add_argument('--episode-len', type=int, default=16)
     ap.add_argument('--label', default='', help='copied into the --task line')
     args = ap.parse_args()
-    if args.random_resets and args.task != 'reach':
+    if args.random_resets and args.task not in ('reach', 'arm'):
         ap.error('--random-resets goes with --task reach')
     if args.task:
         lines = bench_task_calls(args)

@@ -1,6 +1,7 @@
-"""The on-device loop on a task a policy can learn: `reach` (surreal_amd/env/tasks.py).
+"""The on-device loop on a task a policy can learn: `reach`, or with --task arm `arm` (surreal_amd/env/tasks.py).
 
-    python scripts/train_reach.py --algo ppo|ddpg [--actors N --J J --episode-len L --iters K --seed S --out FILE]
+    python scripts/train_reach.py --algo ppo|ddpg [--task reach|arm] [--actors N --J J --episode-len L --iters K --seed S
+                                  --out FILE]
                                   [--random-resets [--heldout-episodes E]] [--eval-heldout] [--device-eval]
                                   [--snapshot-curve] [--save PATH [--save-every K]] [--resume PATH]
                                   [--layernorm] [--param-noise normal|adaptive_normal [--actors-per-agent K]]
@@ -47,7 +48,10 @@ distance first).  With a plain-actor population every evaluation point also prin
 deterministic return of every agent's perturbed actor on the evaluation's episodes, one launch for all
 (DeviceEvalSnapshots.from_param_noise), and the agents' sigmas.  Neither option goes with --device-eval or
 --snapshot-curve (the evaluation launch runs a plain actor without an attached noise).  Without them every printed line is
-what it was."""
+what it was.
+--task arm: the same loop on the planar arm of J links (D = 2 J + 2): the controller's line ("pd_return") is the
+Jacobian-transpose baseline's (tasks.arm_jt_action), every line that names the run also carries "task": "arm".  The default,
+reach, prints what it printed."""
 import argparse
 import json
 import os
@@ -67,11 +71,15 @@ HIDDEN = [32, 32]
 DEFAULT_ITERS = {'ppo': 60, 'ddpg': 60}
 
 
-def host_return(J, episode_len, seeds, controller):
+def obs_dim(task, J):
+    return {'reach': 3 * J, 'arm': 2 * J + 2}[task]
+
+
+def host_return(J, episode_len, seeds, controller, task='reach'):
     """the mean episode return of controller(state) -> action from each seed's reset state, on the host env"""
     total = []
     for seed in seeds:
-        env = SyntheticEnv(3 * J, J, episode_len=episode_len, seed=seed, task='reach')
+        env = SyntheticEnv(obs_dim(task, J), J, episode_len=episode_len, seed=seed, task=task)
         env._reset()
         ret, done = 0.0, False
         while not done:
@@ -81,17 +89,17 @@ def host_return(J, episode_len, seeds, controller):
     return float(np.mean(total))
 
 
-def baselines(J, episode_len, seeds):
-    return {'zero_action_return': host_return(J, episode_len, seeds, lambda s: np.zeros(J, np.float32)),
-            'pd_return': host_return(J, episode_len, seeds, TK.reach_pd_action)}
+def baselines(J, episode_len, seeds, task='reach'):
+    return {'zero_action_return': host_return(J, episode_len, seeds, lambda s: np.zeros(J, np.float32), task),
+            'pd_return': host_return(J, episode_len, seeds, TK.BASELINE_ACTION[task], task)}
 
 
-def heldout_return(J, episode_len, actors, seed, episodes, controller):
+def heldout_return(J, episode_len, actors, seed, episodes, controller, task='reach'):
     """the mean episode return of controller(state) -> action over episodes 0 .. episodes - 1 of every actor of the
     reset stream `seed`, on the host env"""
     total = []
     for g in range(actors):
-        env = SyntheticEnv(3 * J, J, episode_len=episode_len, task='reach', resets=(seed, g))
+        env = SyntheticEnv(obs_dim(task, J), J, episode_len=episode_len, task=task, resets=(seed, g))
         for _ in range(episodes):
             env._reset()
             ret, done = 0.0, False
@@ -102,9 +110,10 @@ def heldout_return(J, episode_len, actors, seed, episodes, controller):
     return float(np.mean(total))
 
 
-def heldout_baselines(J, episode_len, actors, seed, episodes):
-    return {'zero_action_return': heldout_return(J, episode_len, actors, seed, episodes, lambda s: np.zeros(J, np.float32)),
-            'pd_return': heldout_return(J, episode_len, actors, seed, episodes, TK.reach_pd_action)}
+def heldout_baselines(J, episode_len, actors, seed, episodes, task='reach'):
+    return {'zero_action_return': heldout_return(J, episode_len, actors, seed, episodes, lambda s: np.zeros(J, np.float32),
+                                                 task),
+            'pd_return': heldout_return(J, episode_len, actors, seed, episodes, TK.BASELINE_ACTION[task], task)}
 
 
 def ppo_configs(D, A, n, folder):
@@ -146,7 +155,7 @@ class Loop(object):
     """the loop of one algorithm: the training env, agent, learner and replay, and the evaluation pair"""
 
     def __init__(self, algo, actors, J, episode_len, seed, device=None, folder='/tmp/surreal_amd_reach',
-                 random_resets=False, heldout=0, layernorm=False, param_noise=None, actors_per_agent=4):
+                 random_resets=False, heldout=0, layernorm=False, param_noise=None, actors_per_agent=4, task='reach'):
         """random_resets: the training env draws its episodes (reset stream seed + 2); heldout = E > 0: the evaluation
         runs E episodes per actor of the stream seed + 3, the same ones every time; layernorm / param_noise /
         actors_per_agent (DDPG): the module docstring's"""
@@ -157,7 +166,8 @@ class Loop(object):
         torch.manual_seed(seed)
         self.seed = seed
         self.algo, self.n, self.J, self.L = algo, actors, J, episode_len
-        D, A = 3 * J, J
+        self.task = task
+        D, A = obs_dim(task, J), J
         kw = dict(device=device) if device is not None else {}
         if algo == 'ppo':
             from surreal_amd.agent import PPOAgent as Agent
@@ -178,10 +188,10 @@ class Loop(object):
             ag.attach_learner(self.learner)
             ag.fetch_parameter()
         seeds = list(range(actors))
-        self.venv = SyntheticVecEnv(actors, D, A, episode_len=episode_len, seeds=seeds, task='reach', **kw)
+        self.venv = SyntheticVecEnv(actors, D, A, episode_len=episode_len, seeds=seeds, task=task, **kw)
         self.monitor = self.venv.attach_monitor(capacity=8)
         self.venv.attach_noise(seed=seed + 1)
-        self.eval_env = SyntheticVecEnv(actors, D, A, episode_len=episode_len, seeds=seeds, task='reach', **kw)
+        self.eval_env = SyntheticVecEnv(actors, D, A, episode_len=episode_len, seeds=seeds, task=task, **kw)
         self.heldout = int(heldout)
         self.eval_monitor = self.eval_env.attach_monitor(capacity=max(2, self.heldout))
         if random_resets:
@@ -224,6 +234,8 @@ class Loop(object):
         """what a saved run and the loop that goes on from it must share"""
         ident = {'algo': self.algo, 'actors': self.n, 'J': self.J, 'episode_len': self.L, 'seed': self.seed,
                  'random_resets': self.venv.resets is not None, 'heldout': self.heldout}
+        if self.task != 'reach':
+            ident['task'] = self.task
         if self.layernorm:
             ident['layernorm'] = True
         if self.pn is not None:
@@ -337,9 +349,9 @@ class Loop(object):
 
 def train(algo, actors=64, J=2, episode_len=50, iters=None, seed=0, eval_every=10, device=None, log=print,
           random_resets=False, heldout_episodes=4, eval_heldout=False, device_eval=False, snapshot_curve=False,
-          save=None, save_every=None, resume=None, layernorm=False, param_noise=None, actors_per_agent=4):
+          save=None, save_every=None, resume=None, layernorm=False, param_noise=None, actors_per_agent=4, task='reach'):
     """-> (the baselines, the curve: one dict per evaluation).  random_resets / eval_heldout / device_eval / save /
-    save_every (in chunks) / resume / layernorm / param_noise / actors_per_agent: the module docstring's"""
+    save_every (in chunks) / resume / layernorm / param_noise / actors_per_agent / task: the module docstring's"""
     from surreal_amd.utils import run_state as RS
     iters = DEFAULT_ITERS[algo] if iters is None else iters
     heldout = int(heldout_episodes) if (random_resets or eval_heldout) else 0
@@ -354,17 +366,21 @@ def train(algo, actors=64, J=2, episode_len=50, iters=None, seed=0, eval_every=1
     if parts is not None:
         base = parts['script']['base']               # (the baselines of the saved run: not computed, not printed again)
     elif heldout:
-        base = dict(heldout_baselines(J, episode_len, actors, seed + 3, heldout), algo=algo, actors=actors, J=J,
+        base = dict(heldout_baselines(J, episode_len, actors, seed + 3, heldout, task), algo=algo, actors=actors, J=J,
                     episode_len=episode_len, iters=iters, seed=seed, random_resets=bool(random_resets),
                     heldout_episodes=heldout)
     else:
-        base = dict(baselines(J, episode_len, range(actors)), algo=algo, actors=actors, J=J, episode_len=episode_len,
+        base = dict(baselines(J, episode_len, range(actors), task), algo=algo, actors=actors, J=J, episode_len=episode_len,
                     iters=iters, seed=seed)
     if parts is None:
+        if task != 'reach':
+            base['task'] = task
         log(json.dumps(base))
     variant = {}
     if layernorm or param_noise:
         variant = dict(layernorm=layernorm, param_noise=param_noise, actors_per_agent=actors_per_agent)
+    if task != 'reach':
+        variant['task'] = task
     loop = Loop(algo, actors, J, episode_len, seed, device, random_resets=random_resets, heldout=heldout, **variant)
     first = int(loop.load_parts(parts)['iteration']) if parts is not None else 0
     if first > iters:
@@ -423,6 +439,7 @@ def train(algo, actors=64, J=2, episode_len=50, iters=None, seed=0, eval_every=1
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--algo', choices=['ppo', 'ddpg'], required=True)
+    ap.add_argument('--task', choices=['reach', 'arm'], default='reach', help='the task the loop trains on')
     ap.add_argument('--actors', type=int, default=64)
     ap.add_argument('--J', type=int, default=2)
     ap.add_argument('--episode-len', type=int, default=50)
@@ -456,7 +473,7 @@ def main():
           random_resets=args.random_resets, heldout_episodes=args.heldout_episodes, eval_heldout=args.eval_heldout,
           device_eval=args.device_eval, snapshot_curve=args.snapshot_curve, save=args.save, save_every=args.save_every,
           resume=args.resume, layernorm=args.layernorm, param_noise=args.param_noise,
-          actors_per_agent=args.actors_per_agent)
+          actors_per_agent=args.actors_per_agent, task=args.task)
     if args.out:
         with open(args.out, 'a') as f:
             f.write('\n'.join(lines) + '\n')

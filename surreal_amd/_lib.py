@@ -367,7 +367,7 @@ class RecordDdpgPixelPoolNstepStep(Structure):
 
 
 SMX_DDPG_NOISE_NONE, SMX_DDPG_NOISE_GAUSSIAN, SMX_DDPG_NOISE_OU = 0, 1, 2
-SMX_TASK_DRIFT, SMX_TASK_REACH = 0, 1      # the synthetic environment's dynamics (include/surreal_amd.h)
+SMX_TASK_DRIFT, SMX_TASK_REACH, SMX_TASK_ARM = 0, 1, 2      # the synthetic environment's dynamics (include/surreal_amd.h)
 SMX_PPO_PIXEL_STEP_MAX_A = 64            # the actions smx_synth_ppo_pixel_window_step takes
 
 

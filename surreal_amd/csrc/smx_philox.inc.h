@@ -107,6 +107,22 @@ __device__ __forceinline__ float reach_reset_value(const smx_reset_stream& R, lo
     return reset_uniform(R.seed, (uint32_t)(R.actor_base + a), (uint64_t)(R.episode + i), k);
 }
 
+// the same of the `arm` row [theta (J) | omega (J) | g (2)] (tasks.arm_reset_state): the same blocks and tag, word k & 3 of
+// block k >> 2 for element k; an orientation is u (in [-1, 1): well inside the joint limits), an angular
+// velocity +0, a goal coordinate 0.25f * u (exact)
+__device__ __forceinline__ float arm_reset_value(const smx_reset_stream& R, long a, int i, int k, int J) {
+    if (k >= J && k < 2 * J) return 0.0f;
+    const float u = reset_uniform(R.seed, (uint32_t)(R.actor_base + a), (uint64_t)(R.episode + i), k);
+    return k < J ? u : 0.25f * u;
+}
+
+// element k of a TASK row of D elements (a task with a reset distribution)
+template <int TASK>
+__device__ __forceinline__ float task_reset_value(const smx_reset_stream& R, long a, int i, int k, int D) {
+    if constexpr (TASK == SMX_TASK_ARM) return arm_reset_value(R, a, i, k, (D - 2) / 2);
+    else return reach_reset_value(R, a, i, k, D / 3);
+}
+
 // what the entry points ask of a stream over n actors: every global actor id in [0, 2^32), an episode index >= 0
 // (SMX_E_SHAPE)
 inline bool reset_shape_ok(const smx_reset_stream& R, long long n) {

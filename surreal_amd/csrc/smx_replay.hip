@@ -408,11 +408,74 @@ __global__ __launch_bounds__(256) void reach_env_step_kernel(
     if (mon.ep_reward) episode_account(mon, a, rew, done);
 }
 
+// The same launch on SMX_TASK_ARM (arm_* of smx_synth_env.inc.h): ONE thread steps the whole row of actor a, link by link,
+// as reach_env_step_kernel does -- the goal is read before anything is written, no two threads touch the same row.
+__global__ __launch_bounds__(256) void arm_env_step_kernel(
+    float* __restrict__ state, const float* __restrict__ init_state,
+    const float* __restrict__ actions, int n, int D, int A, int t, int episode_len, int slot, int T,
+    float* __restrict__ obs_roll, float* __restrict__ act_roll, float* __restrict__ rew_roll,
+    float* __restrict__ done_roll, smx_episode_monitor mon, smx_reset_stream R) {
+    const long a = (long)blockIdx.x * 256 + threadIdx.x;
+    if (a >= n) return;
+    const bool done = (t + 1 >= episode_len);
+    const bool draw = done && R.enabled;             // the reset row from the stream (arm_reset_value), not init_state
+    float* s = state + a * D;
+    const float* s0 = init_state + a * D;
+    float* orow = obs_roll ? obs_roll + (a * T + slot) * D : nullptr;
+    const bool onext = orow && slot + 1 < T;         // the observation AFTER this step (synth_env_step_kernel)
+    const float g0 = s[2 * A], g1 = s[2 * A + 1];
+    double sx = 0.0, sy = 0.0, sa = 0.0;
+    for (int j = 0; j < A; ++j) {
+        const float ac = fminf(fmaxf(actions[a * A + j], -1.0f), 1.0f);
+        const float th = s[j], om = s[A + j];
+        const float on = arm_next_omega(om, ac);
+        const float tn = arm_next_theta(th, on);
+        float sn, cs;
+        arm_sincos(tn, sn, cs);
+        sx += (double)cs;
+        sy += (double)sn;
+        if (orow) {
+            orow[j] = th; orow[A + j] = om;
+            if (onext) { orow[D + j] = tn; orow[D + A + j] = on; }
+        }
+        if (act_roll) act_roll[(a * T + slot) * A + j] = ac;
+        if (draw) {
+            s[j] = arm_reset_value(R, a, 0, j, A);
+            s[A + j] = arm_reset_value(R, a, 0, A + j, A);
+        } else {
+            s[j] = done ? s0[j] : tn;
+            s[A + j] = done ? s0[A + j] : on;
+        }
+    }
+    for (int i = 0; i < 2; ++i) {
+        const float g = i ? g1 : g0;
+        if (orow) {
+            orow[2 * A + i] = g;
+            if (onext) orow[D + 2 * A + i] = g;
+        }
+        s[2 * A + i] = draw ? arm_reset_value(R, a, 0, 2 * A + i, A) : (done ? s0[2 * A + i] : g);
+    }
+    for (int j = 0; j < A; ++j) {
+        const float ac = fminf(fmaxf(actions[a * A + j], -1.0f), 1.0f);
+        sa += (double)ac * (double)ac;
+    }
+    const float rew = arm_reward(sx, sy, sa, arm_link(A), g0, g1);
+    if (rew_roll) rew_roll[a * T + slot] = rew;
+    if (done_roll) done_roll[a * T + slot] = done ? 1.0f : 0.0f;
+    if (mon.ep_reward) episode_account(mon, a, rew, done);
+}
+
 // out [n, D] <- the rows the actors of a reach env begin episode R.episode with (smx_reset_fill_f32): one thread per element
 __global__ __launch_bounds__(256) void reset_fill_kernel(smx_reset_stream R, int D, long total, float* __restrict__ out) {
     const long i = (long)blockIdx.x * 256 + threadIdx.x;
     if (i >= total) return;
     out[i] = reach_reset_value(R, i / D, 0, (int)(i % D), D / 3);
+}
+// the same of an arm env (D = 2 J + 2)
+__global__ __launch_bounds__(256) void arm_reset_fill_kernel(smx_reset_stream R, int D, long total, float* __restrict__ out) {
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= total) return;
+    out[i] = arm_reset_value(R, i / D, 0, (int)(i % D), (D - 2) / 2);
 }
 
 // The acting head, the environment step and the next observation's z-filter in one launch -- the
@@ -832,7 +895,7 @@ static int synth_task_env_step(float* state, const float* init_state, const floa
     if (task == SMX_TASK_DRIFT)
         return smx_synth_env_step_f32(state, init_state, actions, n, D, A, t, episode_len, slot, T, obs_roll, act_roll,
                                       rew_roll, done_roll, mon, stream);
-    SMX_REQUIRE(task == SMX_TASK_REACH && synth_task_ok(task, D, A), SMX_E_UNSUPPORTED);
+    SMX_REQUIRE((task == SMX_TASK_REACH || task == SMX_TASK_ARM) && synth_task_ok(task, D, A), SMX_E_UNSUPPORTED);
     SMX_REQUIRE(state && init_state && actions, SMX_E_NULL);
     SMX_REQUIRE(n > 0 && T > 0 && slot >= 0 && slot < T && episode_len > 0, SMX_E_SHAPE);
     smx_episode_monitor M;
@@ -844,8 +907,9 @@ static int synth_task_env_step(float* state, const float* init_state, const floa
     memset(&R, 0, sizeof(R));
     if (resets) R = *resets;
     SMX_REQUIRE(reset_shape_ok(R, n), SMX_E_SHAPE);
-    hipLaunchKernelGGL(reach_env_step_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, smx_s(stream), state,
-                       init_state, actions, n, D, A, t, episode_len, slot, T, obs_roll, act_roll, rew_roll, done_roll, M, R);
+    hipLaunchKernelGGL(task == SMX_TASK_ARM ? arm_env_step_kernel : reach_env_step_kernel, dim3((unsigned)((n + 255) / 256)),
+                       dim3(256), 0, smx_s(stream), state, init_state, actions, n, D, A, t, episode_len, slot, T, obs_roll,
+                       act_roll, rew_roll, done_roll, M, R);
     SMX_LAUNCH_CHECK();
     return SMX_OK;
 }
@@ -871,14 +935,16 @@ extern "C" int smx_synth_task_env_step_resets_f32(float* state, const float* ini
 
 extern "C" int smx_reset_fill_f32(const struct smx_reset_stream* resets, int32_t task, int32_t n, int32_t D, float* out,
                                   smx_stream_t stream) {
-    SMX_REQUIRE(task == SMX_TASK_REACH && D % 3 == 0 && synth_task_ok(task, D, D / 3), SMX_E_UNSUPPORTED);
+    const bool arm = task == SMX_TASK_ARM;           // (a task with a reset distribution and a row of D elements)
+    SMX_REQUIRE(arm ? D >= 4 && D % 2 == 0 && synth_task_ok(task, D, (D - 2) / 2)
+                    : task == SMX_TASK_REACH && D % 3 == 0 && synth_task_ok(task, D, D / 3), SMX_E_UNSUPPORTED);
     SMX_REQUIRE(resets && out, SMX_E_NULL);
     smx_reset_stream R = *resets;
     R.enabled = 1;
     SMX_REQUIRE(n > 0 && reset_shape_ok(R, n), SMX_E_SHAPE);
     const long total = (long)n * D;
-    hipLaunchKernelGGL(reset_fill_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, smx_s(stream), R, D, total,
-                       out);
+    hipLaunchKernelGGL(arm ? arm_reset_fill_kernel : reset_fill_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0,
+                       smx_s(stream), R, D, total, out);
     SMX_LAUNCH_CHECK();
     return SMX_OK;
 }

@@ -205,7 +205,7 @@ __device__ __forceinline__ NoClk clk_of(const RollBase&) { return NoClk{}; }
 
 // a task kernel's arguments: those of its SMX_TASK_DRIFT twin, then the reset stream (struct smx_reset_stream; rst.enabled
 // 0: the actors restart from init_state).  What EnvLanes keeps of it (ResetLanes): where the stream lies in the argument
-// segment and the call's episode ends so far -- on the shared clock a wave-uniform count -- for SMX_TASK_REACH, nothing for
+// segment and the call's episode ends so far -- on the shared clock a wave-uniform count -- for SMX_TASK_REACH / _ARM, nothing for
 // a task without a reset distribution.  (Held by value, the stream's seven scalars stayed live across the layers of every
 // step: 17 to 48 more SGPR spills a kernel, 2 to 3 more VGPRs, and 0.2 % on a DDPG call that draws nothing.)
 template <typename Base>
@@ -217,6 +217,8 @@ struct ResetLanes<SMX_TASK_REACH> {
     const smx_reset_stream* rst;                // in the kernel's argument segment (rst_arg): read at an episode end only
     int ends;
 };
+template <>
+struct ResetLanes<SMX_TASK_ARM> : ResetLanes<SMX_TASK_REACH> {};
 // where a task kernel's arguments KArgs = WithRst<...> hold the stream (scalar loads; no registers held between episode ends)
 #pragma clang diagnostic push
 #pragma clang diagnostic ignored "-Winvalid-offsetof"       // (WithRst derives from its Base: not standard-layout, one layout here)
@@ -264,10 +266,11 @@ __device__ __forceinline__ void clear_tiles(const RollBase& G, float* sm, int ti
 // them and keeps their raw state in registers for the whole rollout (RB = 16: two rows a wave, k = lane + 64 i).
 // COLS: the elements' action column and drift in registers too (else read from kmod and formed every step, where the
 // registers are short).
-// TASK: the dynamics (SMX_TASK_*; step() and step_reach()).
+// TASK: the dynamics (SMX_TASK_*; step(), step_reach() and step_arm()).
 struct OwnStart {};
 template <int RB, bool COLS = true, int TASK = SMX_TASK_DRIFT>
 struct EnvLanes : ResetLanes<TASK> {
+    static constexpr int TASK_ID = TASK;
     static constexpr int WPR = RB < RNWV ? RNWV / RB : 1;   // wavefronts per actor row
     static constexpr int RPW = RB > RNWV ? RB / RNWV : 1;   // actor rows per wavefront
     static constexpr int KPL = RKV / WPR;                   // observation elements a lane owns per row
@@ -362,6 +365,10 @@ struct EnvLanes : ResetLanes<TASK> {
             step_reach<ROWDONE>(s_act, done, open, rec, close);
             return;
         }
+        if constexpr (TASK == SMX_TASK_ARM) {
+            step_arm<ROWDONE>(s_act, done, open, rec, close);
+            return;
+        }
 #pragma unroll
         for (int rr = 0; rr < RPW; ++rr) {
             const int r = erow0 + rr;                   // wave-uniform
@@ -451,6 +458,61 @@ struct EnvLanes : ResetLanes<TASK> {
                 }
                 if (owner()) {
                     const float rew = reach_reward(sd, sa);
+                    close(a, p, rew);
+                    if (mon.ep_reward) episode_step(mon, a, ep_reward[r], ep_steps[r], rew, done);
+                }
+            }
+        }
+        if (done) ++this->ends;                         // (ROWDONE: never with a task)
+    }
+    // The same step of SMX_TASK_ARM (arm_* of smx_synth_env.inc.h; D = 2 A + 2 <= 62, checked by the entry points), laid
+    // out as step_reach's: lane j < A holds theta[j], lane A + j holds omega[j], lanes 2 A and 2 A + 1 hold the goal.  One
+    // shuffle carries omega'[j] to lane j, which forms theta'[j] and its sine and cosine; every lane of the wave forms the
+    // three fp64 sums -- cosines, sines, squared actions -- over jj ascending and reads the goal by two more shuffles, the
+    // owner uses them: no LDS, no barrier, the shuffles in wave-uniform control flow.  The reset row as in step_reach
+    // (arm_reset_value).
+    template <bool ROWDONE, typename Open, typename Rec, typename Close>
+    __device__ __forceinline__ void step_arm(const float* s_act, bool done, Open open, Rec rec, Close close) {
+        if (part != 0) return;                          // (wave-uniform: these waves own k >= 64 > D)
+        const int k = lane;                             // kel(0)
+        const int J = (D - 2) / 2;
+        const int kind = k >= 2 * J ? 2 : (k >= J ? 1 : 0);
+        const int j = k - kind * J;                     // (a goal lane: 0 or 1 -- a column of the tile, its action unused)
+        const bool live = k < D;
+        const double w = arm_link(J);
+#pragma unroll
+        for (int rr = 0; rr < RPW; ++rr) {
+            const int r = erow0 + rr;                   // wave-uniform
+            if (r < nrows) {
+                const long a = row0 + r;
+                const auto p = open(a);
+                if constexpr (ROWDONE) done = p.done;
+                const float s = st[rr][0];
+                const float ac = live ? s_act[r * RMAX_A + j] : 0.f;
+                const float oc = arm_next_omega(s, ac);             // lane A + j: omega'[j]
+                const float on = __shfl(oc, k + J);                 // lane j: omega'[j]
+                const float tc = arm_next_theta(s, on);             // lane j: theta'[j]
+                float sj, cj;
+                arm_sincos(tc, sj, cj);                             // lane j: its sine and cosine
+                const float g0 = __shfl(s, 2 * J), g1 = __shfl(s, 2 * J + 1);
+                const float sn = kind == 0 ? tc : (kind == 1 ? oc : s);
+                if (live) {
+                    rec(a, p, k, s, sn);
+                    float next = sn;
+                    if (done)
+                        next = this->rst->enabled ? arm_reset_value(*this->rst, a, this->ends, k, J) : init_state[a * D + k];
+                    st[rr][0] = next;
+                    put_x(r, k, next);
+                }
+                double sx = 0.0, sy = 0.0, sa = 0.0;
+                for (int jj = 0; jj < J; ++jj) sx += (double)__shfl(cj, jj);
+                for (int jj = 0; jj < J; ++jj) sy += (double)__shfl(sj, jj);
+                for (int jj = 0; jj < J; ++jj) {
+                    const double aj = (double)__shfl(ac, jj);
+                    sa += aj * aj;
+                }
+                if (owner()) {
+                    const float rew = arm_reward(sx, sy, sa, w, g0, g1);
                     close(a, p, rew);
                     if (mon.ep_reward) episode_step(mon, a, ep_reward[r], ep_steps[r], rew, done);
                 }
@@ -618,7 +680,7 @@ __device__ __forceinline__ void ppo_rollout(Args G, Clk C = Clk{}, const smx_res
 
     clear_tiles(G, sm, tid, G.zsum, G.zsumsq, G.zcount, G.zeps);
     EnvLanes<RB, COLS, TASK> E(G, sm, G.zsum ? sm + G.off_z : nullptr, wv, lane);
-    if constexpr (TASK == SMX_TASK_REACH) {
+    if constexpr (TASK != SMX_TASK_DRIFT) {
         E.rst = S;
         E.ends = 0;
     }
@@ -1239,7 +1301,7 @@ __global__ __launch_bounds__(RNTH) void ddpg_rollout_kernel(DdpgKernelArgs<POP, 
 
     clear_tiles(G, sm, tid, nullptr, nullptr, nullptr, 0.f);
     EnvLanes<RB, true, TASK> E(G, sm, nullptr, wv, lane);
-    if constexpr (TASK == SMX_TASK_REACH) {
+    if constexpr (TASK != SMX_TASK_DRIFT) {
         E.rst = rst_arg<DdpgKernelArgs<POP, LN, CLK, TASK>>();
         E.ends = 0;
     }
@@ -1458,7 +1520,7 @@ __device__ __forceinline__ void eval_start(Lanes& E, const EvalTail& V, bool str
 #pragma unroll
         for (int q = 0; q < Lanes::KPL; ++q) {
             const int k = E.kel(q);
-            if (k < E.D) E.st[rr][q] = stream ? reach_reset_value(V.rst, a, i, k, E.D / 3) : E.init_state[a * E.D + k];
+            if (k < E.D) E.st[rr][q] = stream ? task_reset_value<Lanes::TASK_ID>(V.rst, a, i, k, E.D) : E.init_state[a * E.D + k];
         }
     }
 }
@@ -1507,7 +1569,7 @@ __global__ __launch_bounds__(RNTH) void ppo_eval_kernel(PEvalKernelArgs<SETS> G)
         clear_tiles(G, sm, tid, G.zsum, G.zsumsq, G.zcount, G.zeps);
     }
     EnvLanes<RB, COLS, TASK> E(G, sm, G.zsum ? sm + G.off_z : nullptr, wv, lane, OwnStart{});
-    if constexpr (TASK == SMX_TASK_REACH) {
+    if constexpr (TASK != SMX_TASK_DRIFT) {
         E.rst = nullptr;                         // (done is false at every step: never read)
         E.ends = 0;
         eval_start(E, G.ev, G.ev.rst.enabled != 0);
@@ -1657,7 +1719,7 @@ __global__ __launch_bounds__(RNTH) void ddpg_eval_kernel(DEvalKernelArgs<SETS> G
 
     clear_tiles(G, sm, tid, nullptr, nullptr, nullptr, 0.f);
     EnvLanes<RB, true, TASK> E(G, sm, nullptr, wv, lane, OwnStart{});
-    if constexpr (TASK == SMX_TASK_REACH) {
+    if constexpr (TASK != SMX_TASK_DRIFT) {
         E.rst = nullptr;                             // (done is false at every step: never read)
         E.ends = 0;
         eval_start(E, G.ev, G.ev.rst.enabled != 0);
@@ -2578,6 +2640,9 @@ static int ppo_window_rollout(const smx_synth_ppo_window_rollout* args, const sm
         if (task == SMX_TASK_REACH)
             return launch<ppo_window_task_kernel<1, SMX_TASK_REACH>, ppo_window_task_kernel<2, SMX_TASK_REACH>,
                           ppo_window_task_kernel<4, SMX_TASK_REACH>>(with_resets(G, resets), rb, lds, stream);
+        if (task == SMX_TASK_ARM)
+            return launch<ppo_window_task_kernel<1, SMX_TASK_ARM>, ppo_window_task_kernel<2, SMX_TASK_ARM>,
+                          ppo_window_task_kernel<4, SMX_TASK_ARM>>(with_resets(G, resets), rb, lds, stream);
         return launch<ppo_window_kernel<1>, ppo_window_kernel<2>, ppo_window_kernel<4>>(G, rb, lds, stream);
     }
     LArgsW G;
@@ -2592,6 +2657,9 @@ static int ppo_window_rollout(const smx_synth_ppo_window_rollout* args, const sm
     if (task == SMX_TASK_REACH)
         return launch<lstm_window_task_kernel<1, SMX_TASK_REACH>, lstm_window_task_kernel<2, SMX_TASK_REACH>,
                       lstm_window_task_kernel<4, SMX_TASK_REACH>>(with_resets(G, resets), rb, lds, stream);
+    if (task == SMX_TASK_ARM)
+        return launch<lstm_window_task_kernel<1, SMX_TASK_ARM>, lstm_window_task_kernel<2, SMX_TASK_ARM>,
+                      lstm_window_task_kernel<4, SMX_TASK_ARM>>(with_resets(G, resets), rb, lds, stream);
     return launch<lstm_window_kernel<1>, lstm_window_kernel<2>, lstm_window_kernel<4>>(G, rb, lds, stream);
 }
 
@@ -2606,7 +2674,7 @@ static int ppo_window_rollout_task(const smx_synth_ppo_window_rollout* args, int
                                    smx_stream_t stream) {
     SMX_REQUIRE(!(resets && task == SMX_TASK_DRIFT), SMX_E_UNSUPPORTED);
     if (task == SMX_TASK_DRIFT) return smx_synth_ppo_window_rollout_f32(args, stream);
-    SMX_REQUIRE(task == SMX_TASK_REACH, SMX_E_UNSUPPORTED);
+    SMX_REQUIRE(task == SMX_TASK_REACH || task == SMX_TASK_ARM, SMX_E_UNSUPPORTED);
     return ppo_window_rollout(args, nullptr, false, task, stream, resets);
 }
 
@@ -2739,6 +2807,10 @@ static int ddpg_rollout_launch(const smx_ddpg_rollout_t* a, const smx_ddpg_actor
         return launch<ddpg_rollout_kernel<1, 3, POP, LN, false, SMX_TASK_REACH>,
                       ddpg_rollout_kernel<2, 3, POP, LN, false, SMX_TASK_REACH>,
                       ddpg_rollout_kernel<4, 2, POP, LN, false, SMX_TASK_REACH>>(with_resets(G, resets), rb, lds, stream);
+    if (task == SMX_TASK_ARM)
+        return launch<ddpg_rollout_kernel<1, 3, POP, LN, false, SMX_TASK_ARM>,
+                      ddpg_rollout_kernel<2, 3, POP, LN, false, SMX_TASK_ARM>,
+                      ddpg_rollout_kernel<4, 2, POP, LN, false, SMX_TASK_ARM>>(with_resets(G, resets), rb, lds, stream);
     return launch<ddpg_rollout_kernel<1, 3, POP, LN>, ddpg_rollout_kernel<2, 3, POP, LN>,
                   ddpg_rollout_kernel<4, 2, POP, LN>>(G, rb, lds, stream);
 }
@@ -2765,7 +2837,7 @@ extern "C" int smx_synth_ddpg_rollout_f32(const smx_ddpg_rollout_t* a, const str
 static int ddpg_rollout_task(const smx_ddpg_rollout_t* a, int32_t task, const smx_reset_stream* resets, smx_stream_t stream) {
     SMX_REQUIRE(!(resets && task == SMX_TASK_DRIFT), SMX_E_UNSUPPORTED);
     if (task == SMX_TASK_DRIFT) return smx_synth_ddpg_rollout_f32(a, nullptr, stream);
-    SMX_REQUIRE(task == SMX_TASK_REACH, SMX_E_UNSUPPORTED);
+    SMX_REQUIRE(task == SMX_TASK_REACH || task == SMX_TASK_ARM, SMX_E_UNSUPPORTED);
     static const smx_ddpg_actor_variant plain = {};
     return ddpg_rollout_launch<false, false>(a, plain, nullptr, false, stream, task, resets);
 }
@@ -2786,7 +2858,7 @@ extern "C" int smx_synth_ddpg_rollout_variant_task_f32(const smx_ddpg_rollout_t*
     if (resets && !resets->enabled) resets = nullptr;
     SMX_REQUIRE(!(resets && task == SMX_TASK_DRIFT), SMX_E_UNSUPPORTED);
     if (task == SMX_TASK_DRIFT) return smx_synth_ddpg_rollout_f32(a, variant, stream);
-    SMX_REQUIRE(task == SMX_TASK_REACH, SMX_E_UNSUPPORTED);
+    SMX_REQUIRE(task == SMX_TASK_REACH || task == SMX_TASK_ARM, SMX_E_UNSUPPORTED);
     return ddpg_rollout_variant(a, variant, nullptr, false, stream, task, resets);
 }
 
@@ -2940,9 +3012,12 @@ extern "C" int smx_synth_ppo_eval_f32(const struct smx_synth_ppo_eval* a, smx_st
     G.steps = G.episode_len = a->episode_len;
     if (a->noise.enabled) G.nstream = a->noise;
     const int rb = pick_block(a->actors_per_workgroup, G.n);
-    const bool reach = a->task == SMX_TASK_REACH;
+    const bool reach = a->task == SMX_TASK_REACH, arm = a->task == SMX_TASK_ARM;
     if (!lstm) {
         const int lds = carve(G, rb, /*mma16=*/false, /*split_out=*/true, /*ztables=*/true, G.D);
+        if (arm)
+            return launch<ppo_eval_kernel<1, 3, false, true, SMX_TASK_ARM>, ppo_eval_kernel<2, 3, false, true, SMX_TASK_ARM>,
+                          ppo_eval_kernel<4, 2, false, false, SMX_TASK_ARM>>(G, rb, lds, stream);
         if (reach)
             return launch<ppo_eval_kernel<1, 3, false, true, SMX_TASK_REACH>, ppo_eval_kernel<2, 3, false, true, SMX_TASK_REACH>,
                           ppo_eval_kernel<4, 2, false, false, SMX_TASK_REACH>>(G, rb, lds, stream);
@@ -2952,6 +3027,9 @@ extern "C" int smx_synth_ppo_eval_f32(const struct smx_synth_ppo_eval* a, smx_st
     G.H = a->lstm->H; G.Hl = a->hidden;
     G.Pg = a->lstm_packed; G.bg = a->lstm_packed + pack_words(4 * G.H, lstm_dp(D) + G.H) * 4;
     const int lds = carve_lstm(G, rb);
+    if (arm)
+        return launch<ppo_eval_kernel<1, 3, true, true, SMX_TASK_ARM>, ppo_eval_kernel<2, 3, true, true, SMX_TASK_ARM>,
+                      ppo_eval_kernel<4, 2, true, false, SMX_TASK_ARM>>(G, rb, lds, stream);
     if (reach)
         return launch<ppo_eval_kernel<1, 3, true, true, SMX_TASK_REACH>, ppo_eval_kernel<2, 3, true, true, SMX_TASK_REACH>,
                       ppo_eval_kernel<4, 2, true, false, SMX_TASK_REACH>>(G, rb, lds, stream);
@@ -2976,6 +3054,9 @@ extern "C" int smx_synth_ddpg_eval_f32(const struct smx_synth_ddpg_eval* a, smx_
     G.steps = G.episode_len = a->episode_len;
     const int rb = pick_block(a->actors_per_workgroup, G.n);
     const int lds = carve(G, rb, /*mma16=*/false, /*split_out=*/false, /*ztables=*/false, G.D);
+    if (a->task == SMX_TASK_ARM)
+        return launch<ddpg_eval_kernel<1, 3, SMX_TASK_ARM>, ddpg_eval_kernel<2, 3, SMX_TASK_ARM>,
+                      ddpg_eval_kernel<4, 2, SMX_TASK_ARM>>(G, rb, lds, stream);
     if (a->task == SMX_TASK_REACH)
         return launch<ddpg_eval_kernel<1, 3, SMX_TASK_REACH>, ddpg_eval_kernel<2, 3, SMX_TASK_REACH>,
                       ddpg_eval_kernel<4, 2, SMX_TASK_REACH>>(G, rb, lds, stream);
@@ -3168,6 +3249,7 @@ extern "C" int smx_synth_ppo_eval_sets_f32(const struct smx_synth_ppo_eval* a, c
     if (!lstm) {
         const int lds = carve(G, rb, /*mma16=*/false, /*split_out=*/true, /*ztables=*/true, G.D);
         const auto X = with_sets(G, s->stride);
+        if (a->task == SMX_TASK_ARM) return ppo_eval_sets_launch<false, SMX_TASK_ARM>(X, rb, lds, stream, s->sets);
         return reach ? ppo_eval_sets_launch<false, SMX_TASK_REACH>(X, rb, lds, stream, s->sets)
                      : ppo_eval_sets_launch<false, SMX_TASK_DRIFT>(X, rb, lds, stream, s->sets);
     }
@@ -3175,6 +3257,7 @@ extern "C" int smx_synth_ppo_eval_sets_f32(const struct smx_synth_ppo_eval* a, c
     G.Pg = s->blobs + S.lstm; G.bg = G.Pg + pack_words(4 * G.H, lstm_dp(D) + G.H) * 4;
     const int lds = carve_lstm(G, rb);
     const auto X = with_sets(G, s->stride);
+    if (a->task == SMX_TASK_ARM) return ppo_eval_sets_launch<true, SMX_TASK_ARM>(X, rb, lds, stream, s->sets);
     return reach ? ppo_eval_sets_launch<true, SMX_TASK_REACH>(X, rb, lds, stream, s->sets)
                  : ppo_eval_sets_launch<true, SMX_TASK_DRIFT>(X, rb, lds, stream, s->sets);
 }
@@ -3201,6 +3284,7 @@ extern "C" int smx_synth_ddpg_eval_sets_f32(const struct smx_synth_ddpg_eval* a,
     const int rb = pick_block(a->actors_per_workgroup, s->sets * G.n);
     const int lds = carve(G, rb, /*mma16=*/false, /*split_out=*/false, /*ztables=*/false, G.D);
     const auto X = with_sets(G, s->stride);
+    if (a->task == SMX_TASK_ARM) return ddpg_eval_sets_launch<SMX_TASK_ARM>(X, rb, lds, stream, s->sets);
     return a->task == SMX_TASK_REACH ? ddpg_eval_sets_launch<SMX_TASK_REACH>(X, rb, lds, stream, s->sets)
                                      : ddpg_eval_sets_launch<SMX_TASK_DRIFT>(X, rb, lds, stream, s->sets);
 }

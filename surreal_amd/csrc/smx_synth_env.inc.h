@@ -18,10 +18,12 @@ __device__ __forceinline__ float synth_reward(double q, float sn0) { return (flo
 // ---- the `reach` task (SMX_TASK_REACH; surreal_amd/env/tasks.py holds the definition): A point masses, the state row
 // [p (A) | v (A) | g (A)].  The same rule: fp32, no contraction, each product rounded before the sum.
 constexpr int REACH_MAX_A = 21;                      // D = 3 A <= 63: a row's elements sit in one wavefront
+constexpr int ARM_MAX_A = 30;                        // (SMX_TASK_ARM, below) D = 2 A + 2 <= 62: likewise
 
 // what the task entry points take (smx_synth_task_supported)
 inline bool synth_task_ok(int task, int D, int A) {
     if (task == SMX_TASK_DRIFT) return D > 0 && A > 0;
+    if (task == SMX_TASK_ARM) return A > 0 && A <= ARM_MAX_A && D == 2 * A + 2;
     return task == SMX_TASK_REACH && A > 0 && A <= REACH_MAX_A && D == 3 * A;
 }
 
@@ -39,6 +41,54 @@ __device__ __forceinline__ float reach_next_p(float p, float vn) {
 
 // the step's reward from sd = sum_j d_j^2, d_j = p'_j - g_j in fp32, and sa = sum_j a_j^2 (both fp64, j ascending)
 __device__ __forceinline__ float reach_reward(double sd, double sa) { return (float)(-(sd + 0.01 * sa)); }
+
+// ---- the `arm` task (SMX_TASK_ARM; surreal_amd/env/tasks.py holds the definition): a planar arm of A links of length w =
+// 2^-ceil(log2 A), the state row [theta (A) | omega (A) | g (2)] -- each link's absolute orientation, its angular velocity,
+// the fingertip's goal.  The same rule: fp32, no contraction, each product rounded before the sum.
+// link j's next angular velocity from its angular velocity om and its (clipped) action ac
+__device__ __forceinline__ float arm_next_omega(float om, float ac) {
+    const float on = (0.9f * om) + (0.4f * ac);
+    return fminf(fmaxf(on, -1.0f), 1.0f);
+}
+
+// its next orientation from its orientation th and its NEXT angular velocity on: joint limits at +-(float)pi, no wrap
+__device__ __forceinline__ float arm_next_theta(float th, float on) {
+    const float tn = th + (0.2f * on);
+    return fminf(fmaxf(tn, -3.1415927f), 3.1415927f);
+}
+
+// the task's sine and cosine of th in [-pi, pi]: the Taylor polynomials in th^2, c_k = (float)((-1)^k / (2k+1)!), k = 0..8,
+// and (float)((-1)^k / (2k)!), k = 0..9, by Horner from the highest, acc = (acc * x2) + c_k with every operation rounded.
+// The polynomials are the definition (within 1e-6 of the functions): no library call, the host's bits.
+__device__ __forceinline__ void arm_sincos(float th, float& sn, float& cs) {
+    constexpr float S[9] = {0x1p+0f, -0x1.555556p-3f, 0x1.111112p-7f, -0x1.a01a02p-13f, 0x1.71de3ap-19f, -0x1.ae6456p-26f,
+                            0x1.612462p-33f, -0x1.ae7f3ep-41f, 0x1.952c78p-49f};
+    constexpr float C[10] = {0x1p+0f, -0x1p-1f, 0x1.555556p-5f, -0x1.6c16c2p-10f, 0x1.a01a02p-16f, -0x1.27e4fcp-22f,
+                             0x1.1eed8ep-29f, -0x1.93974ap-37f, 0x1.ae7f3ep-45f, -0x1.682786p-53f};
+    const float x2 = th * th;
+    float ps = S[8], pc = C[9];
+#pragma unroll
+    for (int k = 7; k >= 0; --k) ps = (ps * x2) + S[k];
+#pragma unroll
+    for (int k = 8; k >= 0; --k) pc = (pc * x2) + C[k];
+    sn = th * ps;
+    cs = pc;
+}
+
+// the length of each of the J links: 2^-ceil(log2 J), exact in every product
+__device__ __forceinline__ double arm_link(int J) {
+    double w = 1.0;
+    for (int m = 1; m < J; m <<= 1) w *= 0.5;
+    return w;
+}
+
+// the step's reward from sx = sum_j c_j, sy = sum_j s_j of the NEXT orientations and sa = sum_j a_j^2 (fp64, j ascending),
+// the link length w and the goal (g0, g1)
+__device__ __forceinline__ float arm_reward(double sx, double sy, double sa, double w, float g0, float g1) {
+    const double dx = sx * w - (double)g0;
+    const double dy = sy * w - (double)g1;
+    return (float)(-((dx * dx + dy * dy) + 0.01 * sa));
+}
 
 // the synthetic camera (SyntheticEnv._frame): a frame's shift from its step count t and the first state component s0
 // (in double, as the host's 100 * abs(float(s0))), and byte (c, y, x) of that frame.  Every kernel that renders a frame

@@ -338,9 +338,9 @@ class DeviceNoise(object):
 
 
 class DeviceResets(object):
-    """The episodes of a 'reach' SyntheticVecEnv as a counter-based stream (struct smx_reset_stream,
-    include/surreal_amd.h; env/tasks.py: reach_reset_state): the row [p | v | g] that actor a (global id actor_base + a)
-    begins episode e with is a pure function of (seed, actor_base + a, e), drawn inside the launch that steps over the
+    """The episodes of a 'reach' or 'arm' SyntheticVecEnv as a counter-based stream (struct smx_reset_stream,
+    include/surreal_amd.h; env/tasks.py: reach_reset_state, arm_reset_state): the row [p | v | g] resp. [theta | omega | g]
+    that actor a (global id actor_base + a) begins episode e with is a pure function of (seed, actor_base + a, e), drawn inside the launch that steps over the
     episode's end.  Made by SyntheticVecEnv.attach_resets(seed, actor_base).
 
     episode: the index of the NEXT episode to begin -- one host integer all actors share (they are on one clock).  A

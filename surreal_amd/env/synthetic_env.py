@@ -19,7 +19,8 @@ Dynamics (all fp32, no fused multiply-add):
     done   = (t + 1 >= episode_len)
 
 These are the dynamics of task 'drift', the default: a workload, not a task.  task='reach' (tasks.py) is one a policy can
-learn, defined the same way -- once, in fp32 without fused multiply-add -- and run by both classes.
+learn, defined the same way -- once, in fp32 without fused multiply-add -- and run by both classes; task='arm' (tasks.py) is
+a second one, a planar multi-link arm with nonlinear kinematics and a reward that couples all joints.
 """
 import collections
 import types
@@ -43,15 +44,17 @@ class SyntheticEnv(Env):
     def __init__(self, obs_dim, action_dim, episode_len=200, seed=0, pixel=None, task='drift', resets=None):
         """pixel = (C, H, W): also emit a uint8 camera frame obs['pixel']['camera0'] (a fixed
         pattern shifted by the step count and the first state component).
-        task: 'drift' (the dynamics above) or 'reach' (env/tasks.py: obs_dim == 3 * action_dim, no camera).
-        resets = (seed, actor_id), task 'reach' only: every _reset() begins a NEW episode, drawn from the reset stream
-        (tasks.reach_reset_state(seed, actor_id, self.episode, J); self.episode: the index of the next one, from 0) --
+        task: 'drift' (the dynamics above), 'reach' (env/tasks.py: obs_dim == 3 * action_dim, no camera) or 'arm' (likewise:
+        obs_dim == 2 * action_dim + 2, no camera).
+        resets = (seed, actor_id), tasks 'reach' and 'arm' only: every _reset() begins a NEW episode, drawn from the reset
+        stream (tasks.reach_reset_state / arm_reset_state(seed, actor_id, self.episode, J); self.episode: the index of the
+        next one, from 0) --
         the host form of SyntheticVecEnv.attach_resets; init_state is not read."""
         TK.check_task('SyntheticEnv', task, obs_dim, action_dim, pixel)
         self.task = task
         self.resets, self.episode = None, 0
         if resets is not None:
-            if task != 'reach':
+            if task == 'drift':
                 raise ValueError("SyntheticEnv: task %r has no reset distribution (resets=: task 'reach')" % (task,))
             self.resets = (int(resets[0]), int(resets[1]))
         self.D, self.A, self.episode_len = obs_dim, action_dim, episode_len
@@ -85,7 +88,7 @@ class SyntheticEnv(Env):
 
     def _reset(self):
         if self.resets is not None:
-            self.state = TK.reach_reset_state(self.resets[0], self.resets[1], self.episode, self.A)
+            self.state = TK.RESET_STATE[self.task](self.resets[0], self.resets[1], self.episode, self.A)
             self.episode += 1
         else:
             self.state = self.init_state.copy()
@@ -93,8 +96,8 @@ class SyntheticEnv(Env):
         return self._obs(), {}
 
     def _step(self, action):
-        if self.task == 'reach':
-            sn, reward = TK.reach_step(self.state, np.asarray(action, dtype=np.float32).reshape(-1))
+        if self.task != 'drift':
+            sn, reward = TK.STEP[self.task](self.state, np.asarray(action, dtype=np.float32).reshape(-1))
             done = (self.t + 1 >= self.episode_len)
             self.t += 1
             self.state = sn
@@ -115,7 +118,8 @@ class SyntheticVecEnv(object):
 
     def __init__(self, n_actors, obs_dim, action_dim, episode_len=200, seeds=None, device=None,
                  kernels=None, pixel=None, frame_stacks=1, task='drift'):
-        """task: 'drift' or 'reach' (env/tasks.py; SyntheticEnv's rules: obs_dim == 3 * action_dim, no camera): a task
+        """task: 'drift', 'reach' or 'arm' (env/tasks.py; SyntheticEnv's rules: obs_dim == 3 * action_dim resp. 2 *
+        action_dim + 2, no camera): a task
         env is stepped by step(), ppo_rollout_into and ddpg_rollout_into's one-launch route; every other stepping call
         and route refuses it (_drift_only).
         pixel = (C, H, W): every actor also has a camera (SyntheticEnv's frame: a pattern shifted by the step
@@ -196,7 +200,7 @@ class SyntheticVecEnv(object):
             return {}
         if not self.K.synth_task_supported(self.task, self.D, self.A):
             raise ValueError('%s: task %r with %d actions; the device runs action_dim <= %d (smx_synth_task_supported)'
-                             % (who, self.task, self.A, TK.REACH_MAX_A))
+                             % (who, self.task, self.A, TK.MAX_A[self.task]))
         return {'task': self.task}
 
     def _clock_args(self, T, n_step, advance, rows):
@@ -271,16 +275,16 @@ class SyntheticVecEnv(object):
         return m
 
     def attach_resets(self, seed, actor_base=0):
-        """-> a DeviceResets (env/monitor.py), task 'reach' only: from now on every episode begins with a row drawn from
-        the reset stream -- element k of actor a's row for episode e is tasks.reach_reset_state(seed, actor_base + a, e,
-        J)[k] (struct smx_reset_stream, include/surreal_amd.h) -- inside the launch that steps over the episode's end:
+        """-> a DeviceResets (env/monitor.py), tasks 'reach' and 'arm' only: from now on every episode begins with a row drawn
+        from the reset stream -- element k of actor a's row for episode e is tasks.reach_reset_state(seed, actor_base + a,
+        e, J)[k], on 'arm' arm_reset_state's (struct smx_reset_stream, include/surreal_amd.h) -- inside the launch that steps over the episode's end:
         no host round trip, no [n, D] upload, and init_state is not read.  The episode index is one host counter all
         actors share (DeviceResets.episode, readable and settable: the index of the NEXT episode to begin): reset()
         draws it and adds one, step / ppo_rollout_into / ddpg_rollout_into add their calls' episode ends.  An actor's
         episodes then depend on its global id and the index alone: not on n, T, the cut of a run into calls or the
         split of the actors over envs (actor_base: the global id of this env's actor 0).  The state is left as it is:
         reset() to begin episode `episode`."""
-        if self.task != 'reach':
+        if self.task == 'drift':
             raise ValueError("attach_resets: task %r has no reset distribution (task 'reach' has)" % (self.task,))
         self._shared_clock_only('attach_resets')
         self._task_kw('attach_resets')
@@ -1124,7 +1128,7 @@ class SyntheticVecEnv(object):
                 self.K.synth_eval_supported(self.task, actor=m.actor)):
             return NotImplementedError, ('evaluate: shapes the evaluation launch refuses (A <= 32, hidden sizes multiples '
                                          'of 4 up to 640, D <= 512, LSTM units up to 128; task %r: action_dim <= %d; '
-                                         'smx_synth_eval_supported)' % (self.task, TK.REACH_MAX_A))
+                                         'smx_synth_eval_supported)' % (self.task, TK.MAX_A[self.task] or TK.REACH_MAX_A))
         return None
 
     def can_evaluate(self, agent):
@@ -1154,9 +1158,9 @@ class SyntheticVecEnv(object):
         of the reference's evaluation workers (agent_mode eval_deterministic / eval_stochastic, surreal/agent/base.py:
         277-345) and of surreal/main/rollout.py (smx_synth_ppo_eval_f32 / smx_synth_ddpg_eval_f32).
         The (actor, episode) pairs are independent rows of the launch: n * episodes rows walk episode_len steps each.
-        resets: None -- every episode begins at init_state[a] -- or (seed, first_episode[, actor_base]), task 'reach'
-        only: episode i of actor a begins with tasks.reach_reset_state(seed, actor_base + a, first_episode + i, J),
-        drawn inside the launch.
+        resets: None -- every episode begins at init_state[a] -- or (seed, first_episode[, actor_base]), tasks 'reach'
+        and 'arm' only: episode i of actor a begins with tasks.reach_reset_state(seed, actor_base + a, first_episode + i,
+        J), on 'arm' arm_reset_state's, drawn inside the launch.
         The mode is the agent's: 'eval_deterministic[_local]' acts on the policy's mean (noise must be None);
         'eval_stochastic[_local]', PPO only, samples -- noise = (seed, first_step[, actor_base]) is required, and step t
         of episode i of actor a draws normal(seed, actor_base + a, first_step + i * episode_len + t, j): what a serial
@@ -1210,7 +1214,7 @@ class SyntheticVecEnv(object):
         if E < 1:
             raise ValueError('evaluate: episodes must be positive, got %r' % (episodes,))
         if resets is not None:
-            if self.task != 'reach':
+            if self.task == 'drift':
                 raise ValueError("evaluate: task %r has no reset distribution (resets=: task 'reach')" % (self.task,))
             resets = self._eval_stream('evaluate', ('resets', 'first_episode'), resets, n)
         if noise is not None:

@@ -1,5 +1,6 @@
 """
-The dynamics the synthetic environments can run, by name ('drift' | 'reach'), and the one host definition of `reach`.
+The dynamics the synthetic environments can run, by name ('drift' | 'reach' | 'arm'), and the one host definition of
+`reach` and of `arm`.
 
 'drift' (synthetic_env.py's docstring) is a fixed workload: every state element decays on its own and no policy is
 meaningfully better than another.  'reach' is a task: J point masses are steered to J goals, A = J, D = 3 J, the state
@@ -18,13 +19,35 @@ bit):
              both sums in fp64, j ascending, one term at a time, rounded once
     done   = t + 1 >= episode_len (the environment's clock; on done the actor restarts from its init_state, or -- with a
              reset stream, reach_reset_state below -- from a row drawn for its next episode)
+
+'arm' is a planar arm of J links: A = J, D = 2 J + 2 (1 <= J <= 30), the state row is [theta (J) | omega (J) | g (2)] --
+each link's absolute orientation, its angular velocity, the goal of the fingertip -- and the policy observes the row
+itself.  The kinematics are nonlinear and the reward couples every joint through the fingertip.  The same rule of
+arithmetic (the device's arm_* functions restate it):
+
+    a         = clip(action, -1, 1)
+    omega'[j] = clamp((0.9f * omega[j]) + (0.4f * a[j]), -1, 1)
+    theta'[j] = clamp(theta[j] + (0.2f * omega'[j]), -PI_F, PI_F)      PI_F = 3.1415927f: joint limits, no wrap
+    x2        = theta'[j] * theta'[j]
+    s[j]      = theta'[j] * P_S(x2)     P_S, P_C: Horner from the highest coefficient, acc = (acc * x2) + c_k, each
+    c[j]      = P_C(x2)                 operation rounded; c_k = (float)((-1)^k / (2k+1)!), k = 0..8, resp.
+                                        (float)((-1)^k / (2k)!), k = 0..9.  The polynomials ARE the definition: no
+                                        library sine or cosine (within 1e-6 of them on [-pi, pi]), no division
+    g'        = g
+    w         = 2^-ceil(log2 J)         a power of two (J = 1: 1): every link has length w, the reach J w is in (0.5, 1]
+    dx        = (sum_j (double)c[j]) * w - (double)g[0]        the sums in fp64, j ascending, one term at a time
+    dy        = (sum_j (double)s[j]) * w - (double)g[1]
+    reward    = (float)(-((dx dx + dy dy) + 0.01 sum_j (double)a[j] (double)a[j]))
+    done      = the environment's clock, as for reach; with a reset stream the next episode's row is arm_reset_state's
 """
+import math
+
 import numpy as np
 
 from surreal_amd import _lib as L
 
-TASKS = ('drift', 'reach')
-TASK_IDS = {'drift': L.SMX_TASK_DRIFT, 'reach': L.SMX_TASK_REACH}
+TASKS = ('drift', 'reach', 'arm')
+TASK_IDS = {'drift': L.SMX_TASK_DRIFT, 'reach': L.SMX_TASK_REACH, 'arm': L.SMX_TASK_ARM}
 
 REACH_MAX_A = 21                             # D = 3 A <= 63: a row's elements sit in one wavefront
 REACH_V_DECAY = np.float32(0.9)
@@ -36,11 +59,34 @@ REACH_ACTION_COST = 0.01
 REACH_PD_KP = np.float32(4.0)
 REACH_PD_KD = np.float32(2.0)
 
+ARM_MAX_A = 30                               # D = 2 A + 2 <= 62: a row's elements sit in one wavefront
+ARM_W_DECAY = np.float32(0.9)
+ARM_W_GAIN = np.float32(0.4)
+ARM_DT = np.float32(0.2)
+ARM_W_MAX = np.float32(1.0)
+ARM_PI = np.float32(3.1415927)
+ARM_ACTION_COST = 0.01
+ARM_RESET_THETA = np.float32(1.0)            # theta = u: in [-1, 1), well inside the limits
+ARM_RESET_GOAL = np.float32(0.25)            # g = u / 4: |g| < 0.36 < 0.5 < J w, reachable for every J >= 2
+ARM_JT_KP = np.float32(8.0)
+ARM_JT_KD = np.float32(2.0)
+ARM_SIN_C = tuple(np.float32((-1) ** k / math.factorial(2 * k + 1)) for k in range(9))
+ARM_COS_C = tuple(np.float32((-1) ** k / math.factorial(2 * k)) for k in range(10))
+
+# the widest action a task takes on the device (None: no limit of the task's own)
+MAX_A = {'drift': None, 'reach': REACH_MAX_A, 'arm': ARM_MAX_A}
+
 
 def check_task(who, task, obs_dim, action_dim, pixel=None):
     """what both synthetic environments ask of a task and its shapes"""
     if task not in TASKS:
         raise ValueError('%s: task must be one of %r, got %r' % (who, TASKS, task))
+    if task == 'arm':
+        if obs_dim != 2 * action_dim + 2:
+            raise ValueError("%s: task 'arm' has obs_dim == 2 * action_dim + 2 (orientation | angular velocity | goal), "
+                             'got obs_dim %d, action_dim %d' % (who, obs_dim, action_dim))
+        if pixel is not None:
+            raise ValueError("%s: task 'arm' has no camera" % who)
     if task == 'reach':
         if obs_dim != 3 * action_dim:
             raise ValueError("%s: task 'reach' has obs_dim == 3 * action_dim (position | velocity | goal), got "
@@ -132,3 +178,109 @@ def reach_reset_state(seed, actor, episode, J):
     u = ((w >> np.uint32(8)).astype(np.float32) * np.float32(2.0 ** -23) - np.float32(1.0)).astype(np.float32)
     u[..., J:2 * J] = np.float32(0.0)
     return u
+
+
+# ---- `arm` (the module docstring's expressions) --------------------------------------------------------------------------
+def arm_link(J):
+    """w = 2^-ceil(log2 J): the length of each of the J links"""
+    J = int(J)
+    assert J >= 1, J
+    return 2.0 ** -((J - 1).bit_length())
+
+
+def _horner(x2, coef):
+    acc = np.full_like(x2, coef[-1])
+    for c in coef[-2::-1]:
+        acc = ((acc * x2).astype(np.float32) + c).astype(np.float32)
+    return acc
+
+
+def arm_sincos(theta):
+    """theta fp32 -> (s, c) fp32: the task's sine and cosine, the two polynomials in theta^2 (for |theta| <= PI_F)"""
+    x = np.asarray(theta, dtype=np.float32)
+    x2 = (x * x).astype(np.float32)
+    return (x * _horner(x2, ARM_SIN_C)).astype(np.float32), _horner(x2, ARM_COS_C)
+
+
+def _arm_tip(s, c, J):
+    """(x, y) fp64 of the fingertip from the links' sines and cosines [..., J]: sums j ascending, one term at a time"""
+    sx = np.zeros(s.shape[:-1], dtype=np.float64)
+    sy = np.zeros(s.shape[:-1], dtype=np.float64)
+    for j in range(J):
+        sx = sx + c[..., j].astype(np.float64)
+        sy = sy + s[..., j].astype(np.float64)
+    w = arm_link(J)
+    return sx * w, sy * w
+
+
+def arm_step(state, action):
+    """state [..., 2 J + 2] and action [..., J] -> (next_state [..., 2 J + 2] fp32, reward [...] fp32): one step of `arm`
+    (no clock and no reset -- those are the environment's)"""
+    st = np.asarray(state, dtype=np.float32)
+    a = np.clip(np.asarray(action, dtype=np.float32), -1.0, 1.0).astype(np.float32)
+    J = a.shape[-1]
+    assert st.shape[-1] == 2 * J + 2 and st.shape[:-1] == a.shape[:-1], (st.shape, a.shape)
+    th, om, g = st[..., :J], st[..., J:2 * J], st[..., 2 * J:]
+    on = ((ARM_W_DECAY * om).astype(np.float32) + (ARM_W_GAIN * a).astype(np.float32)).astype(np.float32)
+    on = np.clip(on, -ARM_W_MAX, ARM_W_MAX).astype(np.float32)
+    tn = (th + (ARM_DT * on).astype(np.float32)).astype(np.float32)
+    tn = np.clip(tn, -ARM_PI, ARM_PI).astype(np.float32)
+    s, c = arm_sincos(tn)
+    x, y = _arm_tip(s, c, J)
+    dx = x - g[..., 0].astype(np.float64)
+    dy = y - g[..., 1].astype(np.float64)
+    a64 = a.astype(np.float64)
+    sa = np.zeros(st.shape[:-1], dtype=np.float64)
+    for j in range(J):
+        sa = sa + a64[..., j] * a64[..., j]
+    reward = (-((dx * dx + dy * dy) + ARM_ACTION_COST * sa)).astype(np.float32)
+    return np.concatenate([tn, on, g], axis=-1).astype(np.float32), reward
+
+
+def arm_jt_action(state):
+    """the Jacobian-transpose baseline of `arm`: a_j = -8 (-s_j ex + c_j ey) - 2 omega_j, e = tip - g at the state's own
+    orientations (arm_step clips it); what reach_pd_action is to `reach`"""
+    st = np.asarray(state, dtype=np.float32)
+    J = (st.shape[-1] - 2) // 2
+    th, om, g = st[..., :J], st[..., J:2 * J], st[..., 2 * J:]
+    s, c = arm_sincos(th)
+    x, y = _arm_tip(s, c, J)
+    ex = (x - g[..., 0].astype(np.float64))[..., None]
+    ey = (y - g[..., 1].astype(np.float64))[..., None]
+    return (-float(ARM_JT_KP) * (-s.astype(np.float64) * ex + c.astype(np.float64) * ey)
+            - float(ARM_JT_KD) * om.astype(np.float64)).astype(np.float32)
+
+
+def _reset_uniform(who, seed, actor, episode, width):
+    """-> [..., width] fp32: u of elements k < width of the reset stream's row (the expressions above `philox4x32_10`)"""
+    seed = int(seed)
+    g = np.asarray(actor, dtype=np.int64)
+    e = np.asarray(episode, dtype=np.int64)
+    if not 0 <= seed < 1 << 64:
+        raise ValueError('%s: seed must fit 64 bits, got %r' % (who, seed))
+    if (g < 0).any() or (g >= 1 << 32).any() or (e < 0).any():
+        raise ValueError('%s: actor ids in [0, 2^32) and episodes >= 0, got %r, %r' % (who, actor, episode))
+    g, e = np.broadcast_arrays(g.astype(np.uint64), e.astype(np.uint64))
+    k = np.arange(width, dtype=np.uint64)
+    counter = np.stack(np.broadcast_arrays(g[..., None], e[..., None] & _M32, e[..., None] >> np.uint64(32),
+                                           np.uint64(RESET_TAG) | (k >> np.uint64(2))), axis=-1)
+    x = philox4x32_10(counter, np.array([seed & 0xFFFFFFFF, seed >> 32], dtype=np.uint64))
+    w = np.take_along_axis(x, (k & np.uint64(3)).astype(np.int64).reshape((1,) * g.ndim + (-1, 1)), axis=-1)[..., 0]
+    return ((w >> np.uint32(8)).astype(np.float32) * np.float32(2.0 ** -23) - np.float32(1.0)).astype(np.float32)
+
+
+def arm_reset_state(seed, actor, episode, J):
+    """-> [2 J + 2] fp32: the row [theta | omega | g] that global actor `actor` begins episode `episode` with under `seed`
+    -- reach's stream, blocks and tag (word k & 3 of block k >> 2 serves element k): theta[j] = 1.0f * u, omega[j] = +0, g[i] = 0.25f * u (exact); actor and episode may be arrays that broadcast: -> [..., 2 J + 2]"""
+    J = int(J)
+    u = _reset_uniform('arm_reset_state', seed, actor, episode, 2 * J + 2)
+    u[..., :J] = (ARM_RESET_THETA * u[..., :J]).astype(np.float32)
+    u[..., J:2 * J] = np.float32(0.0)
+    u[..., 2 * J:] = (ARM_RESET_GOAL * u[..., 2 * J:]).astype(np.float32)
+    return u
+
+
+# per task: one step, the reset stream's row (None: no reset distribution), the baseline controller
+STEP = {'reach': reach_step, 'arm': arm_step}
+RESET_STATE = {'reach': reach_reset_state, 'arm': arm_reset_state}
+BASELINE_ACTION = {'reach': reach_pd_action, 'arm': arm_jt_action}
