@@ -1509,12 +1509,35 @@ int smx_synth_ddpg_rollout_task_f32(const smx_ddpg_rollout_t* args, int32_t task
  * The three *_resets_f32 entry points take what the *_task_f32 ones take and a stream.  resets NULL or !resets->enabled:
  * exactly the task entry point (init_state is read at an episode end).  Enabled: init_state is not read (it may be any
  * non-NULL pointer).  Before any launch: an enabled stream on SMX_TASK_DRIFT is SMX_E_UNSUPPORTED; actor_base < 0,
- * actor_base + n > 2^32 or episode < 0 is SMX_E_SHAPE; every other check is the task entry point's. */
+ * actor_base + n > 2^32 or episode < 0 is SMX_E_SHAPE; every other check is the task entry point's.
+ *
+ * Per-step DISTURBANCES from the same stream make the tasks stochastic.  The word `reserved` holds the bits of an fp32 scale
+ * s, 0 <= s <= 1 (memcpy a float into it; it keeps its name, offset and size, and the zero bit pattern -- what every caller
+ * has passed so far -- means none); it is read only when `enabled`.  With s != 0, step t (0 <= t < episode_len) of the
+ * episode under way e (0 <= e < 2^32) of global actor g draws, for joint / mass j < A,
+ *   x[0..3] = Philox4x32-10(counter = (g, low32(e), t, 0x44530000 | (j >> 2)), key = (low32(seed), high32(seed)))
+ *   w[j]    = (float)(x[j & 3] >> 8) * 2^-23 - 1                  (the reset rows' exact conversion; w in [-1, 1))
+ *   REACH:  v'[j]     = clamp(((0.9f v[j]) + (0.2f a[j])) + (s * w[j]), -1, 1)
+ *   ARM:    omega'[j] = clamp(((0.9f omega[j]) + (0.4f a[j])) + (s * w[j]), -1, 1)
+ * in fp32 without contraction, the product rounded before the sum; everything downstream of v' / omega' is unchanged.  With
+ * s == 0 the term is NOT added: such a stream leaves the bytes it left, signed zeros included.  The tag 0x4453.... keeps
+ * these blocks apart from the reset rows' (0x5253....), the exploration stream's and the parameter noise's.  The draw is a
+ * pure function of (seed, g, e, t, j): not of how a run is cut into calls, of the block size or of how the actors are split
+ * over launches.  Every entry point that takes a stream honours it, in the lane that forms v'[j] / omega'[j] (ten Philox
+ * rounds a step, no memory read): smx_synth_task_env_step_resets_f32 (its `t` is the step in the episode; e = episode - 1),
+ * smx_synth_ppo_window_rollout_resets_f32 (MLP and LSTM), smx_synth_ddpg_rollout_resets_f32,
+ * smx_synth_ddpg_rollout_variant_task_f32 (all four actors) -- a recording launch is in episode e = episode - 1 + (its
+ * episode ends so far) -- and smx_synth_ppo_eval_f32, smx_synth_ddpg_eval_f32 and both *_eval_sets_f32, whose row (a, i) is
+ * in episode first_episode + i: a disturbed evaluation returns what the monitor records for that (seed, actor, episode, s).
+ * Before any launch, with s != 0 on an enabled stream: a NaN, negative or > 1 scale, or an episode under way with an index
+ * < 0 or >= 2^32 (a recording call: episode - 1 .. episode - 1 + (t + steps - 1) / episode_len; an evaluation:
+ * first_episode .. first_episode + episodes - 1; the per-step call also t outside [0, episode_len)): SMX_E_SHAPE;
+ * SMX_TASK_DRIFT: SMX_E_UNSUPPORTED, as for every enabled stream. */
 struct smx_reset_stream {                  /* (by tag: no typedef) */
     uint64_t seed;
     int64_t actor_base;                    /* global id of local actor 0 */
     int64_t episode;                       /* index of the next episode to begin */
-    int32_t enabled, reserved;
+    int32_t enabled, reserved;             /* reserved: the bits of the fp32 disturbance scale (0: none) */
 };
 int smx_reset_fill_f32(const struct smx_reset_stream* resets, int32_t task, int32_t n, int32_t D, float* out,
                        smx_stream_t stream);

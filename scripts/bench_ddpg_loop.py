@@ -75,6 +75,9 @@ def main():
     ap.add_argument('--arm-shape', action='store_true', help="with --task drift: arm's obs-dim, 2 x action-dim + 2")
     ap.add_argument('--random-resets', action='store_true',
                     help='with --task reach | arm: draw every episode inside the launch from a reset stream (attach_resets)')
+    ap.add_argument('--disturbance', type=float, default=0.0, metavar='S',
+                    help='with --random-resets: per-step disturbances of scale S in [0, 1] drawn inside the launch '
+                         '(attach_resets(disturbance=S)); 0: none')
     args = ap.parse_args()
     if args.param_noise and not args.calls:
         ap.error('--param-noise measures single calls: give --calls N')
@@ -86,6 +89,8 @@ def main():
         ap.error('--task measures single calls of the one-launch path: give --calls N')
     if args.random_resets and args.task not in ('reach', 'arm'):
         ap.error('--random-resets goes with --task reach')
+    if args.disturbance and not args.random_resets:
+        ap.error('--disturbance is drawn from the reset stream: give --random-resets')
     if args.task:
         args.obs_dim = 2 * args.action_dim + 2 if args.task == 'arm' or args.arm_shape else 3 * args.action_dim
     n, T, D, A = args.actors, args.steps, args.obs_dim, args.action_dim
@@ -111,7 +116,7 @@ def main():
     task = {'task': args.task} if args.task in ('reach', 'arm') else {}  # ('drift': no keyword, as before there were tasks)
     venv = SyntheticVecEnv(n, D, A, episode_len=episode_len, device='cuda', **task)
     if args.random_resets:
-        venv.attach_resets(seed=3)
+        venv.attach_resets(seed=3, disturbance=args.disturbance)
         venv.reset()
     mon = venv.attach_monitor() if args.monitor else None
 
@@ -226,7 +231,7 @@ def single_calls(args, agent, venv, replay, eps):
         call()
     ms = timed(call, args.calls)
     line = {'what': 'ddpg_rollout_calls', 'label': args.label, 'actors': n, 'steps': T, 'calls': args.calls,
-            'task': args.task, 'random_resets': args.random_resets, 'shape': [args.obs_dim] + args.hidden + [args.action_dim],
+            'task': args.task, 'random_resets': args.random_resets, 'disturbance': args.disturbance, 'shape': [args.obs_dim] + args.hidden + [args.action_dim],
             'episode_len': args.episode_len,
             'layernorm': args.layernorm, 'per_step': args.per_step, 'param_noise': bool(pn), 'actors_per_agent': args.actors_per_agent if pn else None,
             'agents': pn.agents if pn else None, 'median_ms': round(ms[len(ms) // 2], 4),

@@ -147,7 +147,7 @@ def bench_task_calls(args):
     venv = SyntheticVecEnv(n, D, A, episode_len=L, **task)
     venv.attach_noise(seed=1)
     if args.random_resets:
-        venv.attach_resets(seed=3)
+        venv.attach_resets(seed=3, disturbance=args.disturbance)
         venv.reset()
 
     def call():
@@ -157,7 +157,7 @@ def bench_task_calls(args):
     for _ in range(3):
         call()
     ms = sorted(_timed(call) for _ in range(args.calls))
-    line = {'what': 'ppo_window_rollout_calls', 'label': args.label, 'task': args.task, 'random_resets': args.random_resets,
+    line = {'what': 'ppo_window_rollout_calls', 'label': args.label, 'task': args.task, 'random_resets': args.random_resets, 'disturbance': args.disturbance,
             'actors': n, 'steps': T, 'shape': [D, 300, 200, A], 'n_step': N, 'stride': stride, 'episode_len': L,
             'calls': args.calls, 'median_ms': round(ms[len(ms) // 2], 4), 'fastest_tenth_ms': round(ms[len(ms) // 10], 4),
             'slowest_ms': round(ms[-1], 4), 'env_steps_per_s': n * T / (ms[len(ms) // 2] / 1e3)}
@@ -190,9 +190,14 @@ def main():
     ap.add_argument('--action-dim', type=int, default=6)
     ap.add_argument('--episode-len', type=int, default=16)
     ap.add_argument('--label', default='', help='copied into the --task line')
+    ap.add_argument('--disturbance', type=float, default=0.0, metavar='S',
+                    help='with --random-resets: per-step disturbances of scale S in [0, 1] drawn inside the launch '
+                         '(attach_resets(disturbance=S)); 0: none')
     args = ap.parse_args()
     if args.random_resets and args.task not in ('reach', 'arm'):
         ap.error('--random-resets goes with --task reach')
+    if args.disturbance and not args.random_resets:
+        ap.error('--disturbance is drawn from the reset stream: give --random-resets')
     if args.task:
         lines = bench_task_calls(args)
         if args.out:

@@ -5,6 +5,7 @@
                                   [--random-resets [--heldout-episodes E]] [--eval-heldout] [--device-eval]
                                   [--snapshot-curve] [--save PATH [--save-every K]] [--resume PATH]
                                   [--layernorm] [--param-noise normal|adaptive_normal [--actors-per-agent K]]
+                                  [--disturbance [S]]
 
 Per iteration: one rollout chunk of all actors inside one launch (ppo_rollout_into / ddpg_rollout_into on a
 SyntheticVecEnv(task='reach') with a DeviceEpisodeMonitor and an exploration noise stream attached) -> the replay's device
@@ -51,7 +52,13 @@ deterministic return of every agent's perturbed actor on the evaluation's episod
 what it was.
 --task arm: the same loop on the planar arm of J links (D = 2 J + 2): the controller's line ("pd_return") is the
 Jacobian-transpose baseline's (tasks.arm_jt_action), every line that names the run also carries "task": "arm".  The default,
-reach, prints what it printed."""
+reach, prints what it printed.
+--disturbance [S] (needs --random-resets; S alone: DEFAULT_DISTURBANCE): the task is stochastic -- every step of every
+training episode adds S * w to the sum that becomes the next velocity, w drawn on the device from the reset stream's Philox
+(SyntheticVecEnv.attach_resets(disturbance=S); tasks.disturbance) -- and the held-out evaluation runs under the same scale
+on its own stream (seed S + 3): the zero action's and the controller's returns come from the host env
+(SyntheticEnv(resets=, disturbance=)) on those same disturbed episodes.  Every line that names the run carries
+"disturbance": S.  Without the flag every printed line is what it was."""
 import argparse
 import json
 import os
@@ -68,6 +75,10 @@ from surreal_amd.env import tasks as TK  # noqa: E402
 from surreal_amd.env.synthetic_env import SyntheticEnv, SyntheticVecEnv  # noqa: E402
 
 HIDDEN = [32, 32]
+# --disturbance without a value.  Chosen on the host env and the CPU double before any training run (J = 2, episodes of 50,
+# 64 actors x 4 held-out episodes, seed 0; profiles/task_disturbance_learning.jsonl has the table): large enough that the
+# zero action's held-out return moves visibly, small enough that the baseline controller still solves the task
+DEFAULT_DISTURBANCE = 0.25
 DEFAULT_ITERS = {'ppo': 60, 'ddpg': 60}
 
 
@@ -94,12 +105,13 @@ def baselines(J, episode_len, seeds, task='reach'):
             'pd_return': host_return(J, episode_len, seeds, TK.BASELINE_ACTION[task], task)}
 
 
-def heldout_return(J, episode_len, actors, seed, episodes, controller, task='reach'):
+def heldout_return(J, episode_len, actors, seed, episodes, controller, task='reach', disturbance=0.0):
     """the mean episode return of controller(state) -> action over episodes 0 .. episodes - 1 of every actor of the
-    reset stream `seed`, on the host env"""
+    reset stream `seed` (under its disturbance), on the host env"""
     total = []
     for g in range(actors):
-        env = SyntheticEnv(obs_dim(task, J), J, episode_len=episode_len, task=task, resets=(seed, g))
+        env = SyntheticEnv(obs_dim(task, J), J, episode_len=episode_len, task=task, resets=(seed, g),
+                           disturbance=disturbance)
         for _ in range(episodes):
             env._reset()
             ret, done = 0.0, False
@@ -110,10 +122,10 @@ def heldout_return(J, episode_len, actors, seed, episodes, controller, task='rea
     return float(np.mean(total))
 
 
-def heldout_baselines(J, episode_len, actors, seed, episodes, task='reach'):
+def heldout_baselines(J, episode_len, actors, seed, episodes, task='reach', disturbance=0.0):
     return {'zero_action_return': heldout_return(J, episode_len, actors, seed, episodes, lambda s: np.zeros(J, np.float32),
-                                                 task),
-            'pd_return': heldout_return(J, episode_len, actors, seed, episodes, TK.BASELINE_ACTION[task], task)}
+                                                 task, disturbance),
+            'pd_return': heldout_return(J, episode_len, actors, seed, episodes, TK.BASELINE_ACTION[task], task, disturbance)}
 
 
 def ppo_configs(D, A, n, folder):
@@ -155,10 +167,14 @@ class Loop(object):
     """the loop of one algorithm: the training env, agent, learner and replay, and the evaluation pair"""
 
     def __init__(self, algo, actors, J, episode_len, seed, device=None, folder='/tmp/surreal_amd_reach',
-                 random_resets=False, heldout=0, layernorm=False, param_noise=None, actors_per_agent=4, task='reach'):
+                 random_resets=False, heldout=0, layernorm=False, param_noise=None, actors_per_agent=4, task='reach',
+                 disturbance=0.0):
         """random_resets: the training env draws its episodes (reset stream seed + 2); heldout = E > 0: the evaluation
         runs E episodes per actor of the stream seed + 3, the same ones every time; layernorm / param_noise /
-        actors_per_agent (DDPG): the module docstring's"""
+        actors_per_agent (DDPG): the module docstring's; disturbance: the scale on both streams (needs both)"""
+        self.disturbance = float(TK.check_disturbance('--disturbance', disturbance))
+        if self.disturbance != 0 and not (random_resets and heldout):
+            raise ValueError('--disturbance: the draws come from the reset streams: with --random-resets only')
         if algo != 'ddpg' and (layernorm or param_noise):
             raise ValueError('--layernorm / --param-noise: DDPG only')
         if param_noise not in (None, 'normal', 'adaptive_normal'):
@@ -195,10 +211,10 @@ class Loop(object):
         self.heldout = int(heldout)
         self.eval_monitor = self.eval_env.attach_monitor(capacity=max(2, self.heldout))
         if random_resets:
-            self.venv.attach_resets(seed + 2)
+            self.venv.attach_resets(seed + 2, disturbance=self.disturbance)
             self.venv.reset()
         if self.heldout:
-            self.eval_env.attach_resets(seed + 3)
+            self.eval_env.attach_resets(seed + 3, disturbance=self.disturbance)
         self.layernorm = bool(layernorm)
         # (the parameter noise of the training agent, on the device: populations of actors_per_agent actors)
         self.pn = self.venv.attach_param_noise(self.agent, seed + 5, actors_per_agent=actors_per_agent) \
@@ -236,6 +252,8 @@ class Loop(object):
                  'random_resets': self.venv.resets is not None, 'heldout': self.heldout}
         if self.task != 'reach':
             ident['task'] = self.task
+        if self.disturbance != 0:
+            ident['disturbance'] = self.disturbance
         if self.layernorm:
             ident['layernorm'] = True
         if self.pn is not None:
@@ -312,6 +330,8 @@ class Loop(object):
         kw = {}
         if self.heldout:
             kw['resets'] = (self.seed + 3, 0)
+            if self.disturbance != 0:
+                kw['disturbance'] = self.disturbance
         if self.eval_agent.agent_mode in ('eval_stochastic', 'eval_stochastic_local'):
             kw['noise'] = (self.seed + 4, self.device_eval_steps)
             self.device_eval_steps += E * self.L
@@ -325,6 +345,8 @@ class Loop(object):
         kw = {}
         if self.heldout:
             kw['resets'] = (self.seed + 3, 0)
+            if self.disturbance != 0:
+                kw['disturbance'] = self.disturbance
         if self.eval_agent.agent_mode in ('eval_stochastic', 'eval_stochastic_local'):
             kw['noise'] = (self.seed + 4, 0)
         return self.heldout or 1, kw
@@ -349,12 +371,16 @@ class Loop(object):
 
 def train(algo, actors=64, J=2, episode_len=50, iters=None, seed=0, eval_every=10, device=None, log=print,
           random_resets=False, heldout_episodes=4, eval_heldout=False, device_eval=False, snapshot_curve=False,
-          save=None, save_every=None, resume=None, layernorm=False, param_noise=None, actors_per_agent=4, task='reach'):
+          save=None, save_every=None, resume=None, layernorm=False, param_noise=None, actors_per_agent=4, task='reach',
+          disturbance=0.0):
     """-> (the baselines, the curve: one dict per evaluation).  random_resets / eval_heldout / device_eval / save /
     save_every (in chunks) / resume / layernorm / param_noise / actors_per_agent / task: the module docstring's"""
     from surreal_amd.utils import run_state as RS
     iters = DEFAULT_ITERS[algo] if iters is None else iters
     heldout = int(heldout_episodes) if (random_resets or eval_heldout) else 0
+    disturbance = float(TK.check_disturbance('--disturbance', disturbance))
+    if disturbance != 0 and not random_resets:
+        raise ValueError('--disturbance: the draws come from the reset streams: with --random-resets only')
     if snapshot_curve and (save or resume):
         raise ValueError('--snapshot-curve keeps its snapshots outside the saved run: not with --save / --resume')
     if (layernorm or param_noise) and (device_eval or snapshot_curve):
@@ -366,9 +392,11 @@ def train(algo, actors=64, J=2, episode_len=50, iters=None, seed=0, eval_every=1
     if parts is not None:
         base = parts['script']['base']               # (the baselines of the saved run: not computed, not printed again)
     elif heldout:
-        base = dict(heldout_baselines(J, episode_len, actors, seed + 3, heldout, task), algo=algo, actors=actors, J=J,
-                    episode_len=episode_len, iters=iters, seed=seed, random_resets=bool(random_resets),
+        base = dict(heldout_baselines(J, episode_len, actors, seed + 3, heldout, task, disturbance), algo=algo,
+                    actors=actors, J=J, episode_len=episode_len, iters=iters, seed=seed, random_resets=bool(random_resets),
                     heldout_episodes=heldout)
+        if disturbance != 0:
+            base['disturbance'] = disturbance
     else:
         base = dict(baselines(J, episode_len, range(actors), task), algo=algo, actors=actors, J=J, episode_len=episode_len,
                     iters=iters, seed=seed)
@@ -381,6 +409,8 @@ def train(algo, actors=64, J=2, episode_len=50, iters=None, seed=0, eval_every=1
         variant = dict(layernorm=layernorm, param_noise=param_noise, actors_per_agent=actors_per_agent)
     if task != 'reach':
         variant['task'] = task
+    if disturbance != 0:
+        variant['disturbance'] = disturbance
     loop = Loop(algo, actors, J, episode_len, seed, device, random_resets=random_resets, heldout=heldout, **variant)
     first = int(loop.load_parts(parts)['iteration']) if parts is not None else 0
     if first > iters:
@@ -463,6 +493,9 @@ def main():
     ap.add_argument('--param-noise', choices=['normal', 'adaptive_normal'], default=None,
                     help='DDPG: parameter-space noise on the device, one perturbed actor per agent')
     ap.add_argument('--actors-per-agent', type=int, default=4, metavar='K', help='actors that share a perturbation')
+    ap.add_argument('--disturbance', type=float, nargs='?', const=DEFAULT_DISTURBANCE, default=0.0, metavar='S',
+                    help='per-step disturbances of scale S in [0, 1] on the training and the held-out episodes '
+                    '(needs --random-resets; without a value: %g)' % DEFAULT_DISTURBANCE)
     args = ap.parse_args()
     lines = []
 
@@ -473,7 +506,7 @@ def main():
           random_resets=args.random_resets, heldout_episodes=args.heldout_episodes, eval_heldout=args.eval_heldout,
           device_eval=args.device_eval, snapshot_curve=args.snapshot_curve, save=args.save, save_every=args.save_every,
           resume=args.resume, layernorm=args.layernorm, param_noise=args.param_noise,
-          actors_per_agent=args.actors_per_agent, task=args.task)
+          actors_per_agent=args.actors_per_agent, task=args.task, disturbance=args.disturbance)
     if args.out:
         with open(args.out, 'a') as f:
             f.write('\n'.join(lines) + '\n')

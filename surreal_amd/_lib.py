@@ -184,9 +184,18 @@ class NoiseStream(Structure):
 
 
 class ResetStream(Structure):
-    """struct smx_reset_stream"""
+    """struct smx_reset_stream; `reserved` holds the bits of the fp32 disturbance scale (zero bits: none), read and set
+    as a number through `disturbance`"""
     _fields_ = [('seed', c_uint64), ('actor_base', c_int64), ('episode', c_int64), ('enabled', c_int32),
                 ('reserved', c_int32)]
+
+    @property
+    def disturbance(self):
+        return ctypes.c_float.from_buffer_copy(c_int32(self.reserved)).value
+
+    @disturbance.setter
+    def disturbance(self, scale):
+        self.reserved = c_int32.from_buffer_copy(ctypes.c_float(scale)).value
 
 
 class SynthPpoEval(Structure):

@@ -128,3 +128,40 @@ __device__ __forceinline__ float task_reset_value(const smx_reset_stream& R, lon
 inline bool reset_shape_ok(const smx_reset_stream& R, long long n) {
     return !R.enabled || (R.actor_base >= 0 && R.actor_base + n <= (1LL << 32) && R.episode >= 0);
 }
+
+// ---- the per-step disturbance of a task (struct smx_reset_stream's `reserved` word: the bits of the fp32 scale s, 0 <= s
+// <= 1, zero bits: none; surreal_amd/env/tasks.py holds the definition) -------------------------------------------------------
+// The draw of (seed, global actor id g, the episode under way e < 2^32, the step t within it, joint / mass j): a pure
+// function of the five, through the reset stream's exact conversion.
+//   x[0..3] = philox4x32_10(counter = (g, low32(e), t, DISTURB_TAG | (j >> 2)), key = (low32(seed), high32(seed)))
+//   w[j]    = (float)(x[j & 3] >> 8) * 0x1p-23f - 1.0f                                                  (in [-1, 1))
+// and the task adds s * w[j] (rounded) to the sum that becomes v'[j] / omega'[j], before the clamp (reach_next_v,
+// arm_next_omega of smx_synth_env.inc.h).  The tag keeps these blocks apart from the reset blocks (RESET_TAG), the
+// exploration stream's (fourth word < 16) and the parameter noise's (PARAM_NOISE_TAG), whatever the seed.
+constexpr uint32_t DISTURB_TAG = 0x44530000u;
+__device__ __forceinline__ float disturbance_uniform(uint64_t seed, uint32_t g, uint32_t e, uint32_t t, int j) {
+    uint32_t c[4] = {g, e, t, DISTURB_TAG | ((uint32_t)j >> 2)};
+    philox4x32_10(c, (uint32_t)seed, (uint32_t)(seed >> 32));
+    const uint32_t lo = (j & 1) ? c[1] : c[0], hi = (j & 1) ? c[3] : c[2];
+    const uint32_t w = (j & 2) ? hi : lo;
+    return (float)(w >> 8) * 0x1p-23f - 1.0f;
+}
+
+// the stream's scale (read only when enabled; 0: no disturbance, and the tasks add nothing)
+__host__ __device__ inline float reset_disturbance(const smx_reset_stream& R) {
+    return R.enabled ? __builtin_bit_cast(float, R.reserved) : 0.0f;
+}
+
+// what the entry points ask of a disturbed stream whose launch has the episodes first .. first + more under way: a scale in [0, 1]
+// (a NaN fails) and every such index in [0, 2^32) (SMX_E_SHAPE).  A recording launch from clock t over `steps` steps has
+// episode - 1 .. episode - 1 + (t + steps - 1) / episode_len under way, an evaluation episode .. episode + episodes - 1.
+inline bool disturbance_shape_ok(const smx_reset_stream& R, long long first, long long more) {
+    if (!R.enabled || R.reserved == 0) return true;
+    const float s = reset_disturbance(R);
+    return s >= 0.0f && s <= 1.0f && first >= 0 && first < (1LL << 32) && first + more < (1LL << 32);
+}
+inline bool disturbance_rollout_ok(const smx_reset_stream& R, long long t, long long steps, long long episode_len) {
+    if (!R.enabled || R.reserved == 0) return true;                 // (nothing is asked, and nothing divided, without a scale)
+    if (episode_len < 1 || t < 0 || steps < 1) return false;
+    return disturbance_shape_ok(R, R.episode - 1, (t + steps - 1) / episode_len);
+}

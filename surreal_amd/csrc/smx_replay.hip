@@ -371,6 +371,7 @@ __global__ __launch_bounds__(256) void reach_env_step_kernel(
     if (a >= n) return;
     const bool done = (t + 1 >= episode_len);
     const bool draw = done && R.enabled;             // the reset row from the stream (reach_reset_value), not init_state
+    const float dsc = reset_disturbance(R);          // 0: no disturbance; else step t of episode R.episode - 1 draws w[j]
     float* s = state + a * D;
     const float* s0 = init_state + a * D;
     float* orow = obs_roll ? obs_roll + (a * T + slot) * D : nullptr;
@@ -379,7 +380,10 @@ __global__ __launch_bounds__(256) void reach_env_step_kernel(
     for (int j = 0; j < A; ++j) {
         const float ac = fminf(fmaxf(actions[a * A + j], -1.0f), 1.0f);
         const float p = s[j], v = s[A + j], g = s[2 * A + j];
-        const float vn = reach_next_v(v, ac);
+        float sw = 0.f;
+        if (dsc != 0.0f)
+            sw = dsc * disturbance_uniform(R.seed, (uint32_t)(R.actor_base + a), (uint32_t)(R.episode - 1), (uint32_t)t, j);
+        const float vn = reach_next_v(v, ac, dsc != 0.0f, sw);
         const float pn = reach_next_p(p, vn);
         const float d = pn - g;
         sd += (double)d * (double)d;
@@ -419,6 +423,7 @@ __global__ __launch_bounds__(256) void arm_env_step_kernel(
     if (a >= n) return;
     const bool done = (t + 1 >= episode_len);
     const bool draw = done && R.enabled;             // the reset row from the stream (arm_reset_value), not init_state
+    const float dsc = reset_disturbance(R);          // 0: no disturbance; else step t of episode R.episode - 1 draws w[j]
     float* s = state + a * D;
     const float* s0 = init_state + a * D;
     float* orow = obs_roll ? obs_roll + (a * T + slot) * D : nullptr;
@@ -428,7 +433,10 @@ __global__ __launch_bounds__(256) void arm_env_step_kernel(
     for (int j = 0; j < A; ++j) {
         const float ac = fminf(fmaxf(actions[a * A + j], -1.0f), 1.0f);
         const float th = s[j], om = s[A + j];
-        const float on = arm_next_omega(om, ac);
+        float sw = 0.f;
+        if (dsc != 0.0f)
+            sw = dsc * disturbance_uniform(R.seed, (uint32_t)(R.actor_base + a), (uint32_t)(R.episode - 1), (uint32_t)t, j);
+        const float on = arm_next_omega(om, ac, dsc != 0.0f, sw);
         const float tn = arm_next_theta(th, on);
         float sn, cs;
         arm_sincos(tn, sn, cs);
@@ -907,6 +915,8 @@ static int synth_task_env_step(float* state, const float* init_state, const floa
     memset(&R, 0, sizeof(R));
     if (resets) R = *resets;
     SMX_REQUIRE(reset_shape_ok(R, n), SMX_E_SHAPE);
+    // (a disturbed step: its episode R.episode - 1 and its step t within it are counter words)
+    SMX_REQUIRE(disturbance_rollout_ok(R, 0, 1, 1) && (reset_disturbance(R) == 0.0f || (t >= 0 && t < episode_len)), SMX_E_SHAPE);
     hipLaunchKernelGGL(task == SMX_TASK_ARM ? arm_env_step_kernel : reach_env_step_kernel, dim3((unsigned)((n + 255) / 256)),
                        dim3(256), 0, smx_s(stream), state, init_state, actions, n, D, A, t, episode_len, slot, T, obs_roll,
                        act_roll, rew_roll, done_roll, M, R);

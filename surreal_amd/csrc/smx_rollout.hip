@@ -214,8 +214,35 @@ template <int TASK>
 struct ResetLanes {};
 template <>
 struct ResetLanes<SMX_TASK_REACH> {
-    const smx_reset_stream* rst;                // in the kernel's argument segment (rst_arg): read at an episode end only
-    int ends;
+    const smx_reset_stream* rst;                // in the kernel's argument segment (rst_arg): read at an episode end, and
+    int ends;                                   // by a disturbed step for the draw's counter and key words
+    int tstep;                                  // the step within the episode under way (the disturbance's counter word)
+    int evalE;                                  // an evaluation launch's episodes per actor (row = a E + i), else 0
+    float dsc;                                  // the stream's scale, read once (one scalar; 0: the steps are undisturbed)
+    __device__ __forceinline__ float scale() const { return dsc; }
+    // w[j] of row a's step: a recording launch's row is local actor a in episode rst.episode - 1 + ends, an evaluation's
+    // row a = a' E + i is actor a' in episode rst.episode + i (rows < 2^31: an int division, only where the scale is on)
+    __device__ __forceinline__ float draw(long a, int j) const {
+        uint32_t g = (uint32_t)rst->actor_base, e = (uint32_t)rst->episode;
+        if (evalE) {
+            const int q = (int)a / evalE;
+            g += (uint32_t)q;
+            e += (uint32_t)((int)a - q * evalE);
+        } else {
+            g += (uint32_t)a;
+            e += (uint32_t)(ends - 1);
+        }
+        return disturbance_uniform(rst->seed, g, e, (uint32_t)tstep, j);
+    }
+    // the clock behind a step
+    __device__ __forceinline__ void tick(bool done) {
+        tstep = done ? 0 : tstep + 1;
+        if (done) ++ends;
+    }
+    __device__ __forceinline__ void begin(const smx_reset_stream* S, int t0, int E = 0) {
+        rst = S; ends = 0; tstep = t0; evalE = E;
+        dsc = reset_disturbance(*S);
+    }
 };
 template <>
 struct ResetLanes<SMX_TASK_ARM> : ResetLanes<SMX_TASK_REACH> {};
@@ -416,6 +443,10 @@ struct EnvLanes : ResetLanes<TASK> {
     // The reset row at an episode end: with a stream (rst.enabled, uniform over the kernel) every live lane draws its
     // element of episode rst.episode + ends itself (reach_reset_value: ten Philox rounds, no memory read), else it loads
     // init_state's.
+    // The per-step disturbance (a stream with a scale != 0; ResetLanes::dsc, uniform over the launch): lane A + j, which
+    // forms v'[j], draws s * w[j] of step tstep of the episode under way (ResetLanes::draw: ten more rounds, no memory
+    // read) ahead of the step's dependent chain; with dsc == 0 nothing is drawn and nothing is added.  tick(done) behind
+    // the step moves the clock of the draws on: tstep + 1, or 0 and one more episode end (what `++ends` did alone).
     template <bool ROWDONE, typename Open, typename Rec, typename Close>
     __device__ __forceinline__ void step_reach(const float* s_act, bool done, Open open, Rec rec, Close close) {
         if (part != 0) return;                          // (wave-uniform: these waves own k >= 64 > D)
@@ -424,6 +455,16 @@ struct EnvLanes : ResetLanes<TASK> {
         const int kind = k >= 2 * J ? 2 : (k >= J ? 1 : 0);
         const int j = k - kind * J;
         const bool live = k < D;
+        const float dsc = this->scale();                // (wave-uniform) the disturbance's scale, 0: none
+        // lane A + j: s * w[j] of the wave's rows (ten Philox rounds, no memory), drawn ahead of the step's dependent chain
+        // so that an undisturbed step keeps that chain in one piece
+        float sw[RPW];
+#pragma unroll
+        for (int rr = 0; rr < RPW; ++rr) sw[rr] = 0.f;
+        if (dsc != 0.0f) {
+#pragma unroll
+            for (int rr = 0; rr < RPW; ++rr) sw[rr] = dsc * this->draw(row0 + erow0 + rr, j);
+        }
 #pragma unroll
         for (int rr = 0; rr < RPW; ++rr) {
             const int r = erow0 + rr;                   // wave-uniform
@@ -433,7 +474,7 @@ struct EnvLanes : ResetLanes<TASK> {
                 if constexpr (ROWDONE) done = p.done;
                 const float s = st[rr][0];
                 const float ac = live ? s_act[r * RMAX_A + j] : 0.f;
-                const float vc = reach_next_v(s, ac);               // lane A + j: v'[j]
+                const float vc = reach_next_v(s, ac, dsc != 0.0f, sw[rr]);  // lane A + j: v'[j]
                 const float vn = __shfl(vc, k + J);                 // lane j: v'[j]
                 const float pc = reach_next_p(s, vn);               // lane j: p'[j]
                 const float gj = __shfl(s, k + 2 * J);              // lane j: g[j]
@@ -463,7 +504,7 @@ struct EnvLanes : ResetLanes<TASK> {
                 }
             }
         }
-        if (done) ++this->ends;                         // (ROWDONE: never with a task)
+        this->tick(done);                               // (ROWDONE: never with a task)
     }
     // The same step of SMX_TASK_ARM (arm_* of smx_synth_env.inc.h; D = 2 A + 2 <= 62, checked by the entry points), laid
     // out as step_reach's: lane j < A holds theta[j], lane A + j holds omega[j], lanes 2 A and 2 A + 1 hold the goal.  One
@@ -480,6 +521,14 @@ struct EnvLanes : ResetLanes<TASK> {
         const int j = k - kind * J;                     // (a goal lane: 0 or 1 -- a column of the tile, its action unused)
         const bool live = k < D;
         const double w = arm_link(J);
+        const float dsc = this->scale();                // (wave-uniform) the disturbance's scale, 0: none
+        float sw[RPW];                                  // lane A + j: s * w[j] of the wave's rows, as in step_reach
+#pragma unroll
+        for (int rr = 0; rr < RPW; ++rr) sw[rr] = 0.f;
+        if (dsc != 0.0f) {
+#pragma unroll
+            for (int rr = 0; rr < RPW; ++rr) sw[rr] = dsc * this->draw(row0 + erow0 + rr, j);
+        }
 #pragma unroll
         for (int rr = 0; rr < RPW; ++rr) {
             const int r = erow0 + rr;                   // wave-uniform
@@ -489,7 +538,7 @@ struct EnvLanes : ResetLanes<TASK> {
                 if constexpr (ROWDONE) done = p.done;
                 const float s = st[rr][0];
                 const float ac = live ? s_act[r * RMAX_A + j] : 0.f;
-                const float oc = arm_next_omega(s, ac);             // lane A + j: omega'[j]
+                const float oc = arm_next_omega(s, ac, dsc != 0.0f, sw[rr]);    // lane A + j: omega'[j]
                 const float on = __shfl(oc, k + J);                 // lane j: omega'[j]
                 const float tc = arm_next_theta(s, on);             // lane j: theta'[j]
                 float sj, cj;
@@ -518,7 +567,7 @@ struct EnvLanes : ResetLanes<TASK> {
                 }
             }
         }
-        if (done) ++this->ends;                         // (ROWDONE: never with a task)
+        this->tick(done);                               // (ROWDONE: never with a task)
     }
     // the states the actors are left in
     __device__ __forceinline__ void store() const {
@@ -680,10 +729,7 @@ __device__ __forceinline__ void ppo_rollout(Args G, Clk C = Clk{}, const smx_res
 
     clear_tiles(G, sm, tid, G.zsum, G.zsumsq, G.zcount, G.zeps);
     EnvLanes<RB, COLS, TASK> E(G, sm, G.zsum ? sm + G.off_z : nullptr, wv, lane);
-    if constexpr (TASK != SMX_TASK_DRIFT) {
-        E.rst = S;
-        E.ends = 0;
-    }
+    if constexpr (TASK != SMX_TASK_DRIFT) E.begin(S, G.t0);
     SMX_LDS_BARRIER();
     E.start();
     SMX_LDS_BARRIER();
@@ -1301,10 +1347,7 @@ __global__ __launch_bounds__(RNTH) void ddpg_rollout_kernel(DdpgKernelArgs<POP, 
 
     clear_tiles(G, sm, tid, nullptr, nullptr, nullptr, 0.f);
     EnvLanes<RB, true, TASK> E(G, sm, nullptr, wv, lane);
-    if constexpr (TASK != SMX_TASK_DRIFT) {
-        E.rst = rst_arg<DdpgKernelArgs<POP, LN, CLK, TASK>>();
-        E.ends = 0;
-    }
+    if constexpr (TASK != SMX_TASK_DRIFT) E.begin(rst_arg<DdpgKernelArgs<POP, LN, CLK, TASK>>(), G.t0);
     SMX_LDS_BARRIER();
     E.start();
     // the head's (actor, action) pair of this lane: its sigma and OU state for the whole rollout
@@ -1507,6 +1550,16 @@ __device__ __forceinline__ size_t eval_set_shift(const KArgs& G) {
     else return 0;
 }
 
+// where an evaluation kernel's arguments hold the stream (rst_arg's scalar loads: a step reads its disturbance there)
+#pragma clang diagnostic push
+#pragma clang diagnostic ignored "-Winvalid-offsetof"
+template <typename KArgs>
+__device__ __forceinline__ const smx_reset_stream* eval_rst_arg() {
+    return (const smx_reset_stream*)((const char*)__builtin_amdgcn_kernarg_segment_ptr() + __builtin_offsetof(KArgs, ev) +
+                                     __builtin_offsetof(EvalTail, rst));
+}
+#pragma clang diagnostic pop
+
 // the first rows of the block's episodes into the environment lanes' registers (before E.start())
 template <typename Lanes>
 __device__ __forceinline__ void eval_start(Lanes& E, const EvalTail& V, bool stream) {
@@ -1570,8 +1623,7 @@ __global__ __launch_bounds__(RNTH) void ppo_eval_kernel(PEvalKernelArgs<SETS> G)
     }
     EnvLanes<RB, COLS, TASK> E(G, sm, G.zsum ? sm + G.off_z : nullptr, wv, lane, OwnStart{});
     if constexpr (TASK != SMX_TASK_DRIFT) {
-        E.rst = nullptr;                         // (done is false at every step: never read)
-        E.ends = 0;
+        E.begin(eval_rst_arg<PEvalKernelArgs<SETS>>(), 0, G.ev.E);      // (done is false at every step)
         eval_start(E, G.ev, G.ev.rst.enabled != 0);
     } else {
         eval_start(E, G.ev, false);
@@ -1720,8 +1772,7 @@ __global__ __launch_bounds__(RNTH) void ddpg_eval_kernel(DEvalKernelArgs<SETS> G
     clear_tiles(G, sm, tid, nullptr, nullptr, nullptr, 0.f);
     EnvLanes<RB, true, TASK> E(G, sm, nullptr, wv, lane, OwnStart{});
     if constexpr (TASK != SMX_TASK_DRIFT) {
-        E.rst = nullptr;                             // (done is false at every step: never read)
-        E.ends = 0;
+        E.begin(eval_rst_arg<DEvalKernelArgs<SETS>>(), 0, G.ev.E);      // (done is false at every step)
         eval_start(E, G.ev, G.ev.rst.enabled != 0);
     } else {
         eval_start(E, G.ev, false);
@@ -2615,6 +2666,7 @@ static int ppo_window_rollout(const smx_synth_ppo_window_rollout* args, const sm
     SMX_REQUIRE(block_ok(a->actors_per_workgroup) && window_shape_ok(*args) && episode_shape_ok(a->mon), SMX_E_SHAPE);
     SMX_REQUIRE(noise_shape_ok(a->noise, a->n), SMX_E_SHAPE);
     SMX_REQUIRE(!resets || reset_shape_ok(*resets, a->n), SMX_E_SHAPE);
+    SMX_REQUIRE(!resets || disturbance_rollout_ok(*resets, a->t, a->steps, a->episode_len), SMX_E_SHAPE);
     ClkArgs C = {};
     if (clocked) {
         // (the table numbers the call's closing pairs: rows <= capacity keeps them distinct)
@@ -2772,6 +2824,7 @@ static int ddpg_rollout_launch(const smx_ddpg_rollout_t* a, const smx_ddpg_actor
     if (rc != SMX_OK) return rc;
     SMX_REQUIRE(synth_task_ok(task, a->D, a->A) && !(clocked && task != SMX_TASK_DRIFT), SMX_E_UNSUPPORTED);
     SMX_REQUIRE(!resets || reset_shape_ok(*resets, a->n), SMX_E_SHAPE);
+    SMX_REQUIRE(!resets || disturbance_rollout_ok(*resets, a->t, a->steps, a->episode_len), SMX_E_SHAPE);
     ClkArgs C = {};
     if (clocked) {
         rc = clock_args(clocks, a->capacity, C);
@@ -2981,7 +3034,7 @@ static int eval_tail(int32_t n, int32_t episodes, int32_t episode_len, int32_t t
     SMX_REQUIRE(!(resets.enabled && task == SMX_TASK_DRIFT), SMX_E_UNSUPPORTED);
     SMX_REQUIRE(n > 0 && episodes >= 1 && episode_len >= 1, SMX_E_SHAPE);
     SMX_REQUIRE((long long)n * episodes < (1LL << 31) && (long long)episodes * episode_len < (1LL << 31), SMX_E_SHAPE);
-    SMX_REQUIRE(reset_shape_ok(resets, n), SMX_E_SHAPE);
+    SMX_REQUIRE(reset_shape_ok(resets, n) && disturbance_shape_ok(resets, resets.episode, episodes - 1), SMX_E_SHAPE);
     memset(&V, 0, sizeof(V));
     V.E = episodes;
     if (resets.enabled) V.rst = resets;

@@ -27,9 +27,12 @@ inline bool synth_task_ok(int task, int D, int A) {
     return task == SMX_TASK_REACH && A > 0 && A <= REACH_MAX_A && D == 3 * A;
 }
 
-// mass j's next velocity from its velocity v and its (clipped) action ac
-__device__ __forceinline__ float reach_next_v(float v, float ac) {
-    const float vn = (0.9f * v) + (0.2f * ac);
+// mass j's next velocity from its velocity v and its (clipped) action ac; disturbed (a stream with a scale s != 0;
+// uniform over the launch): the step's draw sw = s * w[j] (disturbance_uniform of smx_philox.inc.h; the product rounded)
+// joins the sum before the clamp -- and is NOT added otherwise: an undisturbed step keeps its bytes, a -0 included
+__device__ __forceinline__ float reach_next_v(float v, float ac, bool disturbed = false, float sw = 0.f) {
+    float vn = (0.9f * v) + (0.2f * ac);
+    if (disturbed) vn = vn + sw;
     return fminf(fmaxf(vn, -1.0f), 1.0f);
 }
 
@@ -45,9 +48,10 @@ __device__ __forceinline__ float reach_reward(double sd, double sa) { return (fl
 // ---- the `arm` task (SMX_TASK_ARM; surreal_amd/env/tasks.py holds the definition): a planar arm of A links of length w =
 // 2^-ceil(log2 A), the state row [theta (A) | omega (A) | g (2)] -- each link's absolute orientation, its angular velocity,
 // the fingertip's goal.  The same rule: fp32, no contraction, each product rounded before the sum.
-// link j's next angular velocity from its angular velocity om and its (clipped) action ac
-__device__ __forceinline__ float arm_next_omega(float om, float ac) {
-    const float on = (0.9f * om) + (0.4f * ac);
+// link j's next angular velocity from its angular velocity om and its (clipped) action ac; disturbed, sw: as reach_next_v's
+__device__ __forceinline__ float arm_next_omega(float om, float ac, bool disturbed = false, float sw = 0.f) {
+    float on = (0.9f * om) + (0.4f * ac);
+    if (disturbed) on = on + sw;
     return fminf(fmaxf(on, -1.0f), 1.0f);
 }
 

@@ -343,11 +343,16 @@ class DeviceResets(object):
     that actor a (global id actor_base + a) begins episode e with is a pure function of (seed, actor_base + a, e), drawn inside the launch that steps over the
     episode's end.  Made by SyntheticVecEnv.attach_resets(seed, actor_base).
 
+    disturbance: the scale s in [0, 1] of the per-step disturbance every launch on the stream applies (env/tasks.py:
+    disturbance; 0: none, and at() is the triple it was).
+
     episode: the index of the NEXT episode to begin -- one host integer all actors share (they are on one clock).  A
     reset() draws it and adds one; a stepping call adds its episode ends (its i-th end draws episode + i).  Read it for
     a checkpoint, set it to resume or to see the same episodes again."""
 
-    def __init__(self, seed, actor_base, n, D, kernels, device, task='reach'):
+    def __init__(self, seed, actor_base, n, D, kernels, device, task='reach', disturbance=0.0):
+        from .tasks import check_disturbance
+        self.disturbance = float(check_disturbance('DeviceResets', disturbance))     # (the fp32 value the launches get)
         self.seed, self.actor_base, self.episode = int(seed), int(actor_base), 0
         if not 0 <= self.seed < 1 << 64:
             raise ValueError('DeviceResets: seed must fit 64 bits, got %r' % (seed,))
@@ -357,10 +362,13 @@ class DeviceResets(object):
         self.n, self.D, self.K, self.device, self.task = int(n), int(D), kernels, device, task
 
     def at(self, ahead=0):
-        """(seed, actor_base, the episode index `ahead` episodes from now): what a launch's `resets=` keyword takes"""
+        """(seed, actor_base, the episode index `ahead` episodes from now) -- with a disturbance (seed, actor_base, index,
+        scale) --: what a launch's `resets=` keyword takes"""
         e = self.episode + int(ahead)
         if e < 0:
             raise ValueError('DeviceResets: episode %d is negative' % e)
+        if self.disturbance != 0:
+            return (self.seed, self.actor_base, e, self.disturbance)
         return (self.seed, self.actor_base, e)
 
     def states(self, e=None):
@@ -379,10 +387,20 @@ class DeviceResets(object):
         self.K.reset_fill(at, out, task=self.task)
 
     def state_dict(self):
-        return {'seed': self.seed, 'actor_base': self.actor_base, 'episode': self.episode}
+        sd = {'seed': self.seed, 'actor_base': self.actor_base, 'episode': self.episode}
+        if self.disturbance != 0:
+            sd['disturbance'] = self.disturbance       # (an undisturbed stream keeps the keys it had)
+        return sd
+
+    def _same_disturbance(self, sd):
+        """a checkpoint of another scale is refused (no key: scale 0)"""
+        if float(sd.get('disturbance', 0.0)) != self.disturbance:
+            raise ValueError('DeviceResets: the checkpoint is of a stream with disturbance %r, this one has %r'
+                             % (float(sd.get('disturbance', 0.0)), self.disturbance))
 
     def check_state_dict(self, sd):
         """load_state_dict's refusals alone: nothing is written"""
+        self._same_disturbance(sd)
         if int(sd['seed']) != self.seed or int(sd['actor_base']) != self.actor_base:
             raise ValueError('DeviceResets: the checkpoint is of stream (seed %d, actor_base %d), this one of (%d, %d)'
                              % (int(sd['seed']), int(sd['actor_base']), self.seed, self.actor_base))
@@ -390,11 +408,7 @@ class DeviceResets(object):
             raise ValueError('DeviceResets: episode %d is negative' % int(sd['episode']))
 
     def load_state_dict(self, sd):
-        if int(sd['seed']) != self.seed or int(sd['actor_base']) != self.actor_base:
-            raise ValueError('DeviceResets: the checkpoint is of stream (seed %d, actor_base %d), this one of (%d, %d)'
-                             % (int(sd['seed']), int(sd['actor_base']), self.seed, self.actor_base))
-        if int(sd['episode']) < 0:
-            raise ValueError('DeviceResets: episode %d is negative' % int(sd['episode']))
+        self.check_state_dict(sd)
         self.episode = int(sd['episode'])
 
 
@@ -564,17 +578,19 @@ class DeviceEvaluator(object):
     EpisodeMonitor reports an episode -- to a report under 'eval/<eval_id_base + i>': every eval_env-th episode of an
     actor, 'reward' (':reward' with separate_plots; the mean of its last eval_env returns) and 'step_per_s' with
     global_step = that actor's episode count.  No sleep between reports: a run is one launch.
-    resets: evaluate()'s -- None, or (seed, first_episode[, actor_base]): the same held-out episodes every run.
+    resets: evaluate()'s -- None, or (seed, first_episode[, actor_base]): the same held-out episodes every run;
+    disturbance: evaluate()'s scale on them.
     noise (an 'eval_stochastic' PPO agent): evaluate()'s (seed, first_step[, actor_base]); every run moves first_step on
     by its episodes * episode_len steps.  tensorplex None: one ScalarRecorder per actor (reports[i].tensorplex), else
     the one object all share.
     step_per_s: the environment steps of one actor per second of the last run()'s wall time."""
 
     def __init__(self, env, agent, session_config, episodes, resets=None, eval_id_base=0, tensorplex=None,
-                 separate_plots=False, noise=None):
+                 separate_plots=False, noise=None, disturbance=None):
         if int(episodes) < 1:
             raise ValueError('DeviceEvaluator: episodes must be positive, got %r' % (episodes,))
         self.env, self.agent, self.episodes = env, agent, int(episodes)
+        self.disturbance = disturbance                 # (evaluate()'s: the held-out episodes' scale, None: undisturbed)
         self.resets = None if resets is None else tuple(int(v) for v in resets)
         self.noise = None if noise is None else [int(v) for v in noise]
         self.reports = [_DeviceEvalReport(self, int(eval_id_base) + i, session_config, separate_plots, tensorplex)
@@ -589,6 +605,8 @@ class DeviceEvaluator(object):
         E, steps = self.episodes, int(self.env.episode_len)
         t0 = time.time()
         kw = {} if self.noise is None else {'noise': tuple(self.noise)}
+        if self.disturbance is not None:
+            kw['disturbance'] = self.disturbance
         self._out = self.env.evaluate(self.agent, E, resets=self.resets, out=self._out, **kw)
         host = self._out.cpu().numpy()                 # (the one device -> host copy; it waits for the launch)
         if self.noise is not None:
@@ -704,16 +722,18 @@ class DeviceEvalSnapshots(object):
             self.K.eval_snapshot_store(self.buf[slot], actor=m.actor)
         self.stored[slot] = True
 
-    def evaluate(self, episodes=1, first=0, count=None, resets=None, noise=None, out=None, actors_per_workgroup=0):
+    def evaluate(self, episodes=1, first=0, count=None, resets=None, noise=None, out=None, actors_per_workgroup=0,
+                 disturbance=None):
         """`episodes` whole episodes of every actor under each of the snapshots in slots [first, first + count) (count
         None: up to the last slot; all must have been stored, else ValueError) in ONE launch -> their returns,
         torch.float64 [count, n, episodes] on the device (`out`, or a new tensor); no synchronisation.  The mode rule,
-        resets=, noise= and the size checks are SyntheticVecEnv.evaluate's, with the template agent's mode; it is pure in
-        the same sense"""
+        resets=, noise=, disturbance= and the size checks are SyntheticVecEnv.evaluate's, with the template agent's mode;
+        it is pure in the same sense"""
         import torch
         first, count = self._slots(first, count)
         env = self.env
-        ppo, E, resets, noise = env._eval_check(self.agent, episodes, resets, noise, self.population is not None, count)
+        ppo, E, resets, noise = env._eval_check(self.agent, episodes, resets, noise, self.population is not None, count,
+                                                disturbance=disturbance)
         missing = [k for k in range(first, first + count) if not self.stored[k]]
         if missing:
             raise ValueError('DeviceEvalSnapshots.evaluate: slots %r were never stored' % (missing,))

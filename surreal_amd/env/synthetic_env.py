@@ -41,7 +41,8 @@ def _drift(D):
 
 
 class SyntheticEnv(Env):
-    def __init__(self, obs_dim, action_dim, episode_len=200, seed=0, pixel=None, task='drift', resets=None):
+    def __init__(self, obs_dim, action_dim, episode_len=200, seed=0, pixel=None, task='drift', resets=None,
+                 disturbance=0.0):
         """pixel = (C, H, W): also emit a uint8 camera frame obs['pixel']['camera0'] (a fixed
         pattern shifted by the step count and the first state component).
         task: 'drift' (the dynamics above), 'reach' (env/tasks.py: obs_dim == 3 * action_dim, no camera) or 'arm' (likewise:
@@ -49,10 +50,18 @@ class SyntheticEnv(Env):
         resets = (seed, actor_id), tasks 'reach' and 'arm' only: every _reset() begins a NEW episode, drawn from the reset
         stream (tasks.reach_reset_state / arm_reset_state(seed, actor_id, self.episode, J); self.episode: the index of the
         next one, from 0) --
-        the host form of SyntheticVecEnv.attach_resets; init_state is not read."""
+        the host form of SyntheticVecEnv.attach_resets; init_state is not read.
+        disturbance = s in [0, 1], with resets= only: step t of the episode under way (self.episode - 1) adds s *
+        tasks.disturbance(seed, actor_id, self.episode - 1, t, J) (env/tasks.py); the env is stepped from a reset()."""
         TK.check_task('SyntheticEnv', task, obs_dim, action_dim, pixel)
         self.task = task
         self.resets, self.episode = None, 0
+        self.disturbance = float(TK.check_disturbance('SyntheticEnv', disturbance))
+        self._draws = None
+        if self.disturbance != 0 and task == 'drift':
+            raise ValueError("SyntheticEnv: task %r takes no disturbance (tasks 'reach' and 'arm' do)" % (task,))
+        if self.disturbance != 0 and resets is None:
+            raise ValueError('SyntheticEnv: a disturbance is drawn from the reset stream: resets=(seed, actor_id) is required')
         if resets is not None:
             if task == 'drift':
                 raise ValueError("SyntheticEnv: task %r has no reset distribution (resets=: task 'reach')" % (task,))
@@ -97,7 +106,17 @@ class SyntheticEnv(Env):
 
     def _step(self, action):
         if self.task != 'drift':
-            sn, reward = TK.STEP[self.task](self.state, np.asarray(action, dtype=np.float32).reshape(-1))
+            kw = {}
+            if self.disturbance != 0:
+                if self.episode < 1:
+                    raise ValueError('SyntheticEnv: a disturbed env is stepped from a reset(): the episode under way has '
+                                     'no index yet')
+                if self._draws is None or self._draws[0] != self.episode - 1:
+                    # (the draws of the episode's steps at once: the same numbers, one Philox call an episode)
+                    self._draws = (self.episode - 1, TK.disturbance(self.resets[0], self.resets[1], self.episode - 1,
+                                                                    np.arange(self.episode_len), self.A))
+                kw = dict(w=self._draws[1][self.t], scale=self.disturbance)
+            sn, reward = TK.STEP[self.task](self.state, np.asarray(action, dtype=np.float32).reshape(-1), **kw)
             done = (self.t + 1 >= self.episode_len)
             self.t += 1
             self.state = sn
@@ -203,6 +222,13 @@ class SyntheticVecEnv(object):
                              % (who, self.task, self.A, TK.MAX_A[self.task]))
         return {'task': self.task}
 
+    def _disturbed_ok(self, who):
+        """a stepping call on a disturbed env: the episode under way is DeviceResets.episode - 1, so one must have begun --
+        by reset() -- since the stream was attached (or the counter set)"""
+        if self.resets is not None and self.resets.disturbance != 0 and self.resets.episode < 1:
+            raise ValueError('%s: a disturbed env is stepped from a reset(): the episode under way has no index yet '
+                             '(DeviceResets.episode is %d, the index of the NEXT one)' % (who, self.resets.episode))
+
     def _clock_args(self, T, n_step, advance, rows):
         """the `clocks` keyword of a per-actor launch over the next T steps: the clocks as they are now and the episode
         lengths on the device, and the call's row table (one launch, K.actor_clock_rows; the buffers are reused: L once,
@@ -274,7 +300,7 @@ class SyntheticVecEnv(object):
         m, self.noise = self.noise, None
         return m
 
-    def attach_resets(self, seed, actor_base=0):
+    def attach_resets(self, seed, actor_base=0, disturbance=0.0):
         """-> a DeviceResets (env/monitor.py), tasks 'reach' and 'arm' only: from now on every episode begins with a row drawn
         from the reset stream -- element k of actor a's row for episode e is tasks.reach_reset_state(seed, actor_base + a,
         e, J)[k], on 'arm' arm_reset_state's (struct smx_reset_stream, include/surreal_amd.h) -- inside the launch that steps over the episode's end:
@@ -283,13 +309,21 @@ class SyntheticVecEnv(object):
         draws it and adds one, step / ppo_rollout_into / ddpg_rollout_into add their calls' episode ends.  An actor's
         episodes then depend on its global id and the index alone: not on n, T, the cut of a run into calls or the
         split of the actors over envs (actor_base: the global id of this env's actor 0).  The state is left as it is:
-        reset() to begin episode `episode`."""
+        reset() to begin episode `episode`.
+        disturbance = s in [0, 1] (DeviceResets.disturbance): the task becomes stochastic -- step t of episode e of actor a
+        adds s * tasks.disturbance(seed, actor_base + a, e, t, J)[j] to the sum that becomes v'[j] / omega'[j], drawn in the
+        lane that forms it; a pure function of (seed, actor, episode, step), so everything above still holds.  0: no term
+        is added, the bytes of an undisturbed stream.  A disturbed env is stepped from a reset() (the episode under way
+        is episode - 1)."""
         if self.task == 'drift':
+            if disturbance != 0:
+                raise ValueError("attach_resets: task %r takes no disturbance (tasks 'reach' and 'arm' do)" % (self.task,))
             raise ValueError("attach_resets: task %r has no reset distribution (task 'reach' has)" % (self.task,))
         self._shared_clock_only('attach_resets')
         self._task_kw('attach_resets')
         from .monitor import DeviceResets
-        self.resets = DeviceResets(seed, actor_base, self.n, self.D, self.K, self.device, task=self.task)
+        self.resets = DeviceResets(seed, actor_base, self.n, self.D, self.K, self.device, task=self.task,
+                                   disturbance=disturbance)
         return self.resets
 
     def detach_resets(self):
@@ -570,6 +604,7 @@ class SyntheticVecEnv(object):
         """actions [n, A] on the device -> next observation [n, D] (the state tensor)"""
         self._shared_clock_only('step')
         task = self._task_kw('step')
+        self._disturbed_ok('step')
         r = self.rolls
         if r is not None and self.slot < self.T:
             self.K.synth_env_step(self.state, self.init_state, actions, self.t, self.episode_len,
@@ -785,6 +820,7 @@ class SyntheticVecEnv(object):
         if refusal is not None:
             raise refusal[0](refusal[1])
         task = self._task_kw('ppo_rollout_into')
+        self._disturbed_ok('ppo_rollout_into')
         T = int(T)
         if T < 1:
             raise ValueError('ppo_rollout_into: T must be positive, got %d' % T)
@@ -1009,6 +1045,7 @@ class SyntheticVecEnv(object):
             raise refusal[0](refusal[1])
         K, n, A, pn = self.K, self.n, self.A, self.param_noise
         task = self._task_kw('ddpg_rollout_into')
+        self._disturbed_ok('ddpg_rollout_into')
         shapes, dtypes = {'obs': (self.D,), 'obs_next': (self.D,), 'actions': (A,), 'rewards': (), 'dones': ()}, None
         # (a frame-pool replay, replay.device_frame_pool: the camera rows are counters into its pool, which is this
         # route's frame history as well)
@@ -1152,7 +1189,7 @@ class SyntheticVecEnv(object):
             raise ValueError('%s: global actor ids %d .. %d leave [0, 2^32)' % (who, base, base + n - 1))
         return (seed, base, first)
 
-    def evaluate(self, agent, episodes=1, resets=None, noise=None, out=None, actors_per_workgroup=0):
+    def evaluate(self, agent, episodes=1, resets=None, noise=None, out=None, actors_per_workgroup=0, disturbance=None):
         """`episodes` whole episodes of every actor under `agent`'s policy in ONE launch, nothing recorded -> their
         returns, torch.float64 [n, episodes] on the device (`out`, or a new tensor); no synchronisation.  The device form
         of the reference's evaluation workers (agent_mode eval_deterministic / eval_stochastic, surreal/agent/base.py:
@@ -1161,6 +1198,9 @@ class SyntheticVecEnv(object):
         resets: None -- every episode begins at init_state[a] -- or (seed, first_episode[, actor_base]), tasks 'reach'
         and 'arm' only: episode i of actor a begins with tasks.reach_reset_state(seed, actor_base + a, first_episode + i,
         J), on 'arm' arm_reset_state's, drawn inside the launch.
+        disturbance: None or 0 -- undisturbed steps -- or a scale s in (0, 1], which requires resets=: step t of that
+        episode adds s * tasks.disturbance(seed, actor_base + a, first_episode + i, t, J) as a recording launch on the
+        stream does (attach_resets), so the return is the one the monitor records for that (seed, actor, episode, scale).
         The mode is the agent's: 'eval_deterministic[_local]' acts on the policy's mean (noise must be None);
         'eval_stochastic[_local]', PPO only, samples -- noise = (seed, first_step[, actor_base]) is required, and step t
         of episode i of actor a draws normal(seed, actor_base + a, first_step + i * episode_len + t, j): what a serial
@@ -1169,7 +1209,7 @@ class SyntheticVecEnv(object):
         Pure: neither state, the clock, the attached streams' counters, the monitor, the open windows and transitions,
         agent._batch_cells nor any replay is read or written -- it can be called on the training env between chunks.
         actors_per_workgroup: 4 | 8 | 16 forces the kernel's block of rows (0: automatic; every size gives the same bits)."""
-        ppo, E, resets, noise = self._eval_check(agent, episodes, resets, noise)
+        ppo, E, resets, noise = self._eval_check(agent, episodes, resets, noise, disturbance=disturbance)
         n, L_ = self.n, int(self.episode_len)
         if out is None:
             out = torch.empty(n, E, dtype=torch.float64, device=self.device)
@@ -1189,11 +1229,12 @@ class SyntheticVecEnv(object):
                               noise=noise, **kw)
         return out
 
-    def _eval_check(self, agent, episodes, resets, noise, population=False, sets=1):
+    def _eval_check(self, agent, episodes, resets, noise, population=False, sets=1, disturbance=None):
         """evaluate()'s refusals, mode rule and checks of episodes / resets= / noise= / the sizes, before anything is
         allocated or launched -> (ppo, episodes, resets, noise), the streams as the launches take them (seed, actor_base,
         counter).  population: _eval_refusal's, and the agent's mode is not asked (the perturbed actors act on their
-        means); sets: the parameter sets of the launch (DeviceEvalSnapshots)"""
+        means); sets: the parameter sets of the launch (DeviceEvalSnapshots); disturbance: evaluate()'s -- a scale != 0
+        makes resets (seed, actor_base, first_episode, scale)"""
         refusal = self._eval_refusal(agent, population)
         if refusal is not None:
             raise refusal[0](refusal[1])
@@ -1217,6 +1258,17 @@ class SyntheticVecEnv(object):
             if self.task == 'drift':
                 raise ValueError("evaluate: task %r has no reset distribution (resets=: task 'reach')" % (self.task,))
             resets = self._eval_stream('evaluate', ('resets', 'first_episode'), resets, n)
+        if disturbance is not None:
+            scale = float(TK.check_disturbance('evaluate', disturbance))
+            if scale != 0:
+                if self.task == 'drift':
+                    raise ValueError("evaluate: task %r takes no disturbance (tasks 'reach' and 'arm' do)" % (self.task,))
+                if resets is None:
+                    raise ValueError('evaluate: a disturbance is drawn from the reset stream: resets=(seed, first_episode'
+                                     '[, actor_base]) is required')
+                if resets[2] + E > 1 << 32:
+                    raise ValueError('evaluate: disturbed episodes %d .. %d leave [0, 2^32)' % (resets[2], resets[2] + E - 1))
+                resets = resets + (scale,)
         if noise is not None:
             noise = self._eval_stream('evaluate', ('noise', 'first_step'), noise, n)
         L_ = int(self.episode_len)

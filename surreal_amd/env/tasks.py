@@ -39,6 +39,15 @@ arithmetic (the device's arm_* functions restate it):
     dy        = (sum_j (double)s[j]) * w - (double)g[1]
     reward    = (float)(-((dx dx + dy dy) + 0.01 sum_j (double)a[j] (double)a[j]))
     done      = the environment's clock, as for reach; with a reset stream the next episode's row is arm_reset_state's
+
+A reset stream may carry a DISTURBANCE of scale s (fp32, 0 <= s <= 1; `disturbance` below): step t of episode e of global
+actor g then adds s * w[j] to the sum that becomes v'[j] resp. omega'[j], the product rounded before the sum, inside the
+clamp -- everything downstream of v' / omega' is unchanged:
+
+    reach:  v'[j]     = clamp(((0.9f * v[j]) + (0.2f * a[j])) + (s * w[j]), -1, 1)
+    arm:    omega'[j] = clamp(((0.9f * omega[j]) + (0.4f * a[j])) + (s * w[j]), -1, 1)
+
+With s == 0 the term is NOT added (no `+ 0`): a stream without a disturbance leaves the bytes above, signed zeros included.
 """
 import math
 
@@ -95,15 +104,31 @@ def check_task(who, task, obs_dim, action_dim, pixel=None):
             raise ValueError("%s: task 'reach' has no camera" % who)
 
 
-def reach_step(state, action):
+def _disturb(who, vn, w, scale):
+    """the sum that becomes v' / omega' with the step's disturbance: vn + (scale * w), or vn itself where scale == 0"""
+    scale = np.float32(scale)
+    if not 0.0 <= float(scale) <= 1.0:
+        raise ValueError('%s: the disturbance scale lies in [0, 1], got %r' % (who, float(scale)))
+    if scale == 0:
+        return vn
+    if w is None:
+        raise ValueError('%s: a disturbed step takes its draws w (tasks.disturbance)' % who)
+    w = np.asarray(w, dtype=np.float32)
+    assert w.shape == vn.shape, (w.shape, vn.shape)
+    return (vn + (scale * w).astype(np.float32)).astype(np.float32)
+
+
+def reach_step(state, action, w=None, scale=0.0):
     """state [..., 3 J] and action [..., J] -> (next_state [..., 3 J] fp32, reward [...] fp32): one step of `reach`
-    (the module docstring's expressions; no clock and no reset -- those are the environment's)"""
+    (the module docstring's expressions; no clock and no reset -- those are the environment's).  scale != 0: a disturbed
+    step, w [..., J] its draws (`disturbance`)"""
     s = np.asarray(state, dtype=np.float32)
     a = np.clip(np.asarray(action, dtype=np.float32), -1.0, 1.0).astype(np.float32)
     J = a.shape[-1]
     assert s.shape[-1] == 3 * J and s.shape[:-1] == a.shape[:-1], (s.shape, a.shape)
     p, v, g = s[..., :J], s[..., J:2 * J], s[..., 2 * J:]
     vn = ((REACH_V_DECAY * v).astype(np.float32) + (REACH_V_GAIN * a).astype(np.float32)).astype(np.float32)
+    vn = _disturb('reach_step', vn, w, scale)
     vn = np.clip(vn, -REACH_V_MAX, REACH_V_MAX).astype(np.float32)
     pn = (p + (REACH_DT * vn).astype(np.float32)).astype(np.float32)
     pn = np.clip(pn, -REACH_P_MAX, REACH_P_MAX).astype(np.float32)
@@ -180,6 +205,48 @@ def reach_reset_state(seed, actor, episode, J):
     return u
 
 
+# ---- the per-step disturbance (struct smx_reset_stream's scale; csrc/smx_philox.inc.h restates it) ------------------------------
+# For a seed, a global actor id g < 2^32, the episode under way e (0 <= e < 2^32), the step t within it (0 <= t < 2^32) and
+# joint / mass j < J:
+#     x[0..3] = Philox4x32-10(counter = (g, low32(e), t, 0x44530000 | (j >> 2)), key = (low32(seed), high32(seed)))
+#     w[j]    = (float)(x[j & 3] >> 8) * 0x1p-23f - 1.0f       the reset stream's exact conversion: w in [-1, 1)
+# The tag keeps these blocks apart from the reset blocks (RESET_TAG), the exploration stream's (fourth word < 16) and the
+# parameter noise's (0x504E0001).  The draw is a pure function of (seed, g, e, t, j): not of how a run is cut into calls, of
+# the block size or of how the actors are split over envs.
+DISTURB_TAG = 0x44530000
+
+
+def check_disturbance(who, scale):
+    """-> the scale as np.float32; a scale outside [0, 1] (a NaN too) is a ValueError"""
+    try:
+        s = np.float32(scale)
+    except (TypeError, ValueError):
+        raise ValueError('%s: the disturbance scale is a number in [0, 1], got %r' % (who, scale))
+    if not 0.0 <= float(s) <= 1.0:
+        raise ValueError('%s: the disturbance scale lies in [0, 1], got %r' % (who, scale))
+    return s
+
+
+def disturbance(seed, actor, episode, t, J):
+    """-> [..., J] fp32: w of step `t` of episode `episode` of global actor `actor` under `seed` (the expressions above;
+    actor, episode and t may be arrays that broadcast)"""
+    seed, J = int(seed), int(J)
+    g = np.asarray(actor, dtype=np.int64)
+    e = np.asarray(episode, dtype=np.int64)
+    t = np.asarray(t, dtype=np.int64)
+    if not 0 <= seed < 1 << 64:
+        raise ValueError('disturbance: seed must fit 64 bits, got %r' % (seed,))
+    if any((v < 0).any() or (v >= 1 << 32).any() for v in (g, e, t)):
+        raise ValueError('disturbance: actor ids, episodes and steps in [0, 2^32), got %r, %r, %r' % (actor, episode, t))
+    g, e, t = np.broadcast_arrays(g.astype(np.uint64), e.astype(np.uint64), t.astype(np.uint64))
+    j = np.arange(J, dtype=np.uint64)
+    counter = np.stack(np.broadcast_arrays(g[..., None], e[..., None], t[..., None],
+                                           np.uint64(DISTURB_TAG) | (j >> np.uint64(2))), axis=-1)
+    x = philox4x32_10(counter, np.array([seed & 0xFFFFFFFF, seed >> 32], dtype=np.uint64))     # [..., J, 4]
+    w = np.take_along_axis(x, (j & np.uint64(3)).astype(np.int64).reshape((1,) * g.ndim + (-1, 1)), axis=-1)[..., 0]
+    return ((w >> np.uint32(8)).astype(np.float32) * np.float32(2.0 ** -23) - np.float32(1.0)).astype(np.float32)
+
+
 # ---- `arm` (the module docstring's expressions) --------------------------------------------------------------------------
 def arm_link(J):
     """w = 2^-ceil(log2 J): the length of each of the J links"""
@@ -213,15 +280,17 @@ def _arm_tip(s, c, J):
     return sx * w, sy * w
 
 
-def arm_step(state, action):
+def arm_step(state, action, w=None, scale=0.0):
     """state [..., 2 J + 2] and action [..., J] -> (next_state [..., 2 J + 2] fp32, reward [...] fp32): one step of `arm`
-    (no clock and no reset -- those are the environment's)"""
+    (no clock and no reset -- those are the environment's).  scale != 0: a disturbed step, w [..., J] its draws
+    (`disturbance`)"""
     st = np.asarray(state, dtype=np.float32)
     a = np.clip(np.asarray(action, dtype=np.float32), -1.0, 1.0).astype(np.float32)
     J = a.shape[-1]
     assert st.shape[-1] == 2 * J + 2 and st.shape[:-1] == a.shape[:-1], (st.shape, a.shape)
     th, om, g = st[..., :J], st[..., J:2 * J], st[..., 2 * J:]
     on = ((ARM_W_DECAY * om).astype(np.float32) + (ARM_W_GAIN * a).astype(np.float32)).astype(np.float32)
+    on = _disturb('arm_step', on, w, scale)
     on = np.clip(on, -ARM_W_MAX, ARM_W_MAX).astype(np.float32)
     tn = (th + (ARM_DT * on).astype(np.float32)).astype(np.float32)
     tn = np.clip(tn, -ARM_PI, ARM_PI).astype(np.float32)

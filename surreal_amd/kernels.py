@@ -708,10 +708,13 @@ class HipKernels(object):
 
     @staticmethod
     def _reset_args(resets):
-        """struct smx_reset_stream of a (seed, actor_base, episode) triple (DeviceResets.at, surreal_amd/env/monitor.py):
-        the stream a task launch draws its episodes' first rows from"""
+        """struct smx_reset_stream of a (seed, actor_base, episode[, disturbance]) tuple (DeviceResets.at,
+        surreal_amd/env/monitor.py): the stream a task launch draws its episodes' first rows from, and -- with a fourth
+        element != 0, the scale -- its per-step disturbances (env/tasks.py: disturbance)"""
         q = L.ResetStream()
-        q.seed, q.actor_base, q.episode = (int(v) for v in resets)
+        q.seed, q.actor_base, q.episode = (int(v) for v in resets[:3])
+        if len(resets) > 3:
+            q.disturbance = float(resets[3])
         q.enabled = 1
         return q
 
