@@ -1038,6 +1038,23 @@ int64_t smx_ddpg_rows_second_packed_floats(int32_t D, int32_t A, int32_t H1, int
 int smx_ddpg_rows_critic_td3_f32(const smx_ddpg_rows_t* args, smx_stream_t stream);
 int32_t smx_ddpg_rows_ln_supported(int32_t D, int32_t A, int32_t H1, int32_t H2, int32_t c1, int32_t c2, int64_t rows);
 int32_t smx_ddpg_rows_ln_second_supported(int32_t D, int32_t A, int32_t H1, int32_t H2, int32_t c1, int32_t c2, int64_t rows);
+/* Delayed policy updates (TD3's third ingredient; the reference's iteration, ddpg.py:244-352, is the case d = 1): the
+ * actor and every target move once per d critic updates.  An iteration that updates the critics alone runs
+ *   smx_ddpg_rows_critic_only_f32 / smx_ddpg_rows_critic_only_td3_f32  the chains of smx_ddpg_rows_critic_f32 /
+ *                             _critic_td3_f32 WITHOUT the actor's forward pass, on the same kernels (the chain is a step
+ *                             table): target networks, y, *step += 1, each critic's loss and data gradients -- with args->ln
+ *                             the LayerNorm forms.  h1a, h2a, act (ln: a1 ... ar2) are neither required nor written.
+ * followed by the critic groups' smx_ddpg_rows_wgrad_update_f32 with target == NULL, the last of them carrying the
+ * statistics (q_actor as the last actor chain left it).  An iteration that updates the actor too runs today's launches, the
+ * actor's update with a step word of its own, and between the actor chain and that update
+ *   smx_ddpg_rows_delay_tail_f32  one workgroup: with stats, the statistics exactly as smx_ddpg_rows_wgrad_update_f32's
+ *                             extra workgroup forms them (args' q, y, rewards, actions, q_actor; second->stats2; stats_host
+ *                             slot *args->step & 1 -- the ITERATION's word, not the actor's); then *actor_step += 1.
+ *                             stats == NULL (args may be NULL then): the increment alone. */
+int smx_ddpg_rows_critic_only_f32(const smx_ddpg_rows_t* args, smx_stream_t stream);
+int smx_ddpg_rows_critic_only_td3_f32(const smx_ddpg_rows_t* args, smx_stream_t stream);
+int smx_ddpg_rows_delay_tail_f32(const smx_ddpg_rows_t* args, int32_t* actor_step, float* stats, float* stats_host,
+                                 smx_stream_t stream);
 
 /* One optimiser group's step of the row schedule in ONE launch (round 6): Adam exactly as smx_adam_step_dev_f32
  * (torch.optim.Adam after clip_grad_value_: ddpg.py:310-311, 332-333), then the group's target network -- soft

@@ -11,6 +11,10 @@ replay shard; and the oracle (reference ATen path) on the host CPU beside it.
                                    variant (ms per call of every round, their median, min and max) appended to --jsonl
     --tree PATH                    import surreal_amd from another checkout (the parent commit beside this one, same job)
     --label TEXT                   goes into the JSON lines
+    --soft-targets                 target_update soft, tau 1e-3 (the default config's is hard every 500 iterations)
+    --policy-delay D               learner_config.algo.network.policy_delay = D (D > 1 implies --soft-targets); every mean is
+                                   then taken over a multiple of D iterations, so it weighs the two kinds of iteration as
+                                   the learner runs them
 """
 import argparse, json, sys, os, time, copy
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -24,7 +28,10 @@ ap.add_argument('--calls', type=int, default=300)
 ap.add_argument('--jsonl', default='')
 ap.add_argument('--tree', default=ROOT)
 ap.add_argument('--label', default='')
+ap.add_argument('--soft-targets', action='store_true')
+ap.add_argument('--policy-delay', type=int, default=1)
 opt = ap.parse_args()
+opt.calls = -(-opt.calls // opt.policy_delay) * opt.policy_delay
 sys.path.insert(0, os.path.abspath(opt.tree)); sys.path.insert(0, os.path.join(ROOT, 'tests')); sys.path.insert(0, os.path.join(ROOT, 'oracle'))
 import numpy as np
 import torch
@@ -39,6 +46,10 @@ def make_learner(td3, row_schedule, layernorm=False):
     lc = ddpg_learner_config(); lc.replay.batch_size = B
     lc.model.use_layernorm = bool(layernorm)
     lc.algo.network.use_double_critic = lc.algo.network.use_action_regularization = bool(td3)
+    if opt.soft_targets or opt.policy_delay > 1:
+        lc.algo.network.target_update = {'type': 'soft', 'tau': 1e-3}
+    if opt.policy_delay != 1:
+        lc.algo.network.policy_delay = opt.policy_delay
     sc = ddpg_session_config()
     if row_schedule != 'unset':
         sc.learner['ddpg_row_schedule'] = row_schedule == 'on'
@@ -66,6 +77,7 @@ if opt.ab:
     for n in names:
         L = learners[n]
         rec = {'variant': n, 'label': opt.label, 'batch': B, 'D': D, 'A': A, 'calls_per_round': opt.calls, 'rounds': opt.rounds,
+               'policy_delay': opt.policy_delay, 'target_update': L.target_update_type,
                'schedule': L._schedule(B, D), 'graph': L._ws.graph is not None, 'ms_per_learn_rounds': [round(v, 5) for v in ms[n]],
                'ms_per_learn_median': round(float(np.median(ms[n])), 5), 'ms_min': round(min(ms[n]), 5), 'ms_max': round(max(ms[n]), 5)}
         line = json.dumps(rec)
@@ -79,7 +91,7 @@ lc, L = make_learner(opt.td3, opt.row_schedule, opt.layernorm)
 print('schedule: %s (td3 %s, layernorm %s, ddpg_row_schedule %s)' % (L._schedule(B, D), opt.td3, opt.layernorm, opt.row_schedule))
 batches = [L.preprocess(synthetic.make_ddpg_batch(B, D, A, seed=s)) for s in range(8)]
 for i in range(20): L.learn(batches[i % 8])
-torch.cuda.synchronize(); t0 = time.perf_counter(); n = 300
+torch.cuda.synchronize(); t0 = time.perf_counter(); n = -(-300 // opt.policy_delay) * opt.policy_delay
 for i in range(n): st = L.learn(batches[i % 8])
 torch.cuda.synchronize(); dt = (time.perf_counter() - t0) / n
 print('DDPG learn (batch resident): %.3f ms/iter  %.3g samples/s  critic_loss %.4f' % (dt * 1e3, B / dt, st['critic_loss']))

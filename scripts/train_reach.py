@@ -5,7 +5,7 @@
                                   [--random-resets [--heldout-episodes E]] [--eval-heldout] [--device-eval]
                                   [--snapshot-curve] [--save PATH [--save-every K]] [--resume PATH]
                                   [--layernorm] [--param-noise normal|adaptive_normal [--actors-per-agent K]]
-                                  [--disturbance [S]]
+                                  [--disturbance [S]] [--double-critic] [--policy-delay D]
 
 Per iteration: one rollout chunk of all actors inside one launch (ppo_rollout_into / ddpg_rollout_into on a
 SyntheticVecEnv(task='reach') with a DeviceEpisodeMonitor and an exploration noise stream attached) -> the replay's device
@@ -50,6 +50,10 @@ deterministic return of every agent's perturbed actor on the evaluation's episod
 (DeviceEvalSnapshots.from_param_noise), and the agents' sigmas.  Neither option goes with --device-eval or
 --snapshot-curve (the evaluation launch runs a plain actor without an attached noise).  Without them every printed line is
 what it was.
+--double-critic (DDPG): TD3's second critic (use_double_critic; the learner is asked for the row schedule,
+ddpg_row_schedule = True).  --policy-delay D (DDPG): the actor and the target networks move once per D learner iterations
+(learner_config.algo.network.policy_delay).  Both are named by the run's identity; without them every printed line is what
+it was.
 --task arm: the same loop on the planar arm of J links (D = 2 J + 2): the controller's line ("pd_return") is the
 Jacobian-transpose baseline's (tasks.arm_jt_action), every line that names the run also carries "task": "arm".  The default,
 reach, prints what it printed.
@@ -146,7 +150,7 @@ def ppo_configs(D, A, n, folder):
     return lc, ppo_env_config(D, A), ppo_session_config(folder)
 
 
-def ddpg_configs(D, A, n, folder, layernorm=False, param_noise=None):
+def ddpg_configs(D, A, n, folder, layernorm=False, param_noise=None, double_critic=False, policy_delay=1):
     from surreal_amd.main.ddpg_configs import ddpg_learner_config, ddpg_env_config, ddpg_session_config
     lc = ddpg_learner_config()
     lc.model.actor_fc_hidden_sizes = lc.model.critic_fc_hidden_sizes = list(HIDDEN)
@@ -160,7 +164,13 @@ def ddpg_configs(D, A, n, folder, layernorm=False, param_noise=None):
     lc.replay.memory_size = 64 * 1024
     lc.model.use_layernorm = bool(layernorm)
     lc.algo.exploration.param_noise_type = param_noise
-    return lc, ddpg_env_config(D, A, num_agents=n), ddpg_session_config(folder)
+    sc = ddpg_session_config(folder)
+    if double_critic:                # (two critics take the row schedule only when asked to)
+        lc.algo.network.use_double_critic = True
+        sc.learner.ddpg_row_schedule = True
+    if policy_delay != 1:
+        lc.algo.network.policy_delay = policy_delay
+    return lc, ddpg_env_config(D, A, num_agents=n), sc
 
 
 class Loop(object):
@@ -168,15 +178,18 @@ class Loop(object):
 
     def __init__(self, algo, actors, J, episode_len, seed, device=None, folder='/tmp/surreal_amd_reach',
                  random_resets=False, heldout=0, layernorm=False, param_noise=None, actors_per_agent=4, task='reach',
-                 disturbance=0.0):
+                 disturbance=0.0, double_critic=False, policy_delay=1):
         """random_resets: the training env draws its episodes (reset stream seed + 2); heldout = E > 0: the evaluation
         runs E episodes per actor of the stream seed + 3, the same ones every time; layernorm / param_noise /
-        actors_per_agent (DDPG): the module docstring's; disturbance: the scale on both streams (needs both)"""
+        actors_per_agent / double_critic / policy_delay (DDPG): the module docstring's; disturbance: the scale on both
+        streams (needs both)"""
         self.disturbance = float(TK.check_disturbance('--disturbance', disturbance))
         if self.disturbance != 0 and not (random_resets and heldout):
             raise ValueError('--disturbance: the draws come from the reset streams: with --random-resets only')
         if algo != 'ddpg' and (layernorm or param_noise):
             raise ValueError('--layernorm / --param-noise: DDPG only')
+        if algo != 'ddpg' and (double_critic or policy_delay != 1):
+            raise ValueError('--double-critic / --policy-delay: DDPG only')
         if param_noise not in (None, 'normal', 'adaptive_normal'):
             raise ValueError('--param-noise: normal or adaptive_normal, got %r' % (param_noise,))
         torch.manual_seed(seed)
@@ -194,7 +207,7 @@ class Loop(object):
             from surreal_amd.agent import DDPGAgent as Agent
             from surreal_amd.learner.ddpg import DDPGLearner as Learner
             from surreal_amd.replay import UniformReplay as Replay
-            cfg = ddpg_configs(D, A, actors, folder, layernorm, param_noise)
+            cfg = ddpg_configs(D, A, actors, folder, layernorm, param_noise, double_critic, policy_delay)
         self.lc = cfg[0]
         self.learner = Learner(*cfg)
         self.replay = Replay(*cfg)
@@ -216,6 +229,7 @@ class Loop(object):
         if self.heldout:
             self.eval_env.attach_resets(seed + 3, disturbance=self.disturbance)
         self.layernorm = bool(layernorm)
+        self.double_critic, self.policy_delay = bool(double_critic), policy_delay
         # (the parameter noise of the training agent, on the device: populations of actors_per_agent actors)
         self.pn = self.venv.attach_param_noise(self.agent, seed + 5, actors_per_agent=actors_per_agent) \
             if param_noise else None
@@ -258,6 +272,10 @@ class Loop(object):
             ident['layernorm'] = True
         if self.pn is not None:
             ident.update(param_noise=self.pn.type, actors_per_agent=self.pn.actors_per_agent)
+        if self.double_critic:
+            ident['double_critic'] = True
+        if self.policy_delay != 1:
+            ident['policy_delay'] = self.policy_delay
         return ident
 
     def population_line(self, it):
@@ -372,9 +390,10 @@ class Loop(object):
 def train(algo, actors=64, J=2, episode_len=50, iters=None, seed=0, eval_every=10, device=None, log=print,
           random_resets=False, heldout_episodes=4, eval_heldout=False, device_eval=False, snapshot_curve=False,
           save=None, save_every=None, resume=None, layernorm=False, param_noise=None, actors_per_agent=4, task='reach',
-          disturbance=0.0):
+          disturbance=0.0, double_critic=False, policy_delay=1):
     """-> (the baselines, the curve: one dict per evaluation).  random_resets / eval_heldout / device_eval / save /
-    save_every (in chunks) / resume / layernorm / param_noise / actors_per_agent / task: the module docstring's"""
+    save_every (in chunks) / resume / layernorm / param_noise / actors_per_agent / task / double_critic / policy_delay: the
+    module docstring's"""
     from surreal_amd.utils import run_state as RS
     iters = DEFAULT_ITERS[algo] if iters is None else iters
     heldout = int(heldout_episodes) if (random_resets or eval_heldout) else 0
@@ -403,6 +422,10 @@ def train(algo, actors=64, J=2, episode_len=50, iters=None, seed=0, eval_every=1
     if parts is None:
         if task != 'reach':
             base['task'] = task
+        if double_critic:
+            base['double_critic'] = True
+        if policy_delay != 1:
+            base['policy_delay'] = policy_delay
         log(json.dumps(base))
     variant = {}
     if layernorm or param_noise:
@@ -411,6 +434,8 @@ def train(algo, actors=64, J=2, episode_len=50, iters=None, seed=0, eval_every=1
         variant['task'] = task
     if disturbance != 0:
         variant['disturbance'] = disturbance
+    if double_critic or policy_delay != 1:
+        variant.update(double_critic=double_critic, policy_delay=policy_delay)
     loop = Loop(algo, actors, J, episode_len, seed, device, random_resets=random_resets, heldout=heldout, **variant)
     first = int(loop.load_parts(parts)['iteration']) if parts is not None else 0
     if first > iters:
@@ -496,6 +521,9 @@ def main():
     ap.add_argument('--disturbance', type=float, nargs='?', const=DEFAULT_DISTURBANCE, default=0.0, metavar='S',
                     help='per-step disturbances of scale S in [0, 1] on the training and the held-out episodes '
                     '(needs --random-resets; without a value: %g)' % DEFAULT_DISTURBANCE)
+    ap.add_argument('--double-critic', action='store_true', help="DDPG: TD3's second critic, on the row schedule")
+    ap.add_argument('--policy-delay', type=int, default=1, metavar='D',
+                    help='DDPG: the actor and the targets move once per D learner iterations')
     args = ap.parse_args()
     lines = []
 
@@ -506,7 +534,8 @@ def main():
           random_resets=args.random_resets, heldout_episodes=args.heldout_episodes, eval_heldout=args.eval_heldout,
           device_eval=args.device_eval, snapshot_curve=args.snapshot_curve, save=args.save, save_every=args.save_every,
           resume=args.resume, layernorm=args.layernorm, param_noise=args.param_noise,
-          actors_per_agent=args.actors_per_agent, task=args.task, disturbance=args.disturbance)
+          actors_per_agent=args.actors_per_agent, task=args.task, disturbance=args.disturbance,
+          double_critic=args.double_critic, policy_delay=args.policy_delay)
     if args.out:
         with open(args.out, 'a') as f:
             f.write('\n'.join(lines) + '\n')

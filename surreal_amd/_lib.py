@@ -544,6 +544,9 @@ _SIGS = {
     'smx_ddpg_rows_critic_td3_f32': (c_int32, [_P, _P]),
     'smx_ddpg_rows_ln_supported': (c_int32, [c_int32] * 6 + [c_int64]),
     'smx_ddpg_rows_ln_second_supported': (c_int32, [c_int32] * 6 + [c_int64]),
+    'smx_ddpg_rows_critic_only_f32': (c_int32, [_P, _P]),
+    'smx_ddpg_rows_critic_only_td3_f32': (c_int32, [_P, _P]),
+    'smx_ddpg_rows_delay_tail_f32': (c_int32, [_P, _P, _P, _P, _P]),
     'smx_ddpg_rows_update_f32': (c_int32, [_P, c_int32, _P, _P]),
     'smx_ddpg_rows_wgrad_update_f32': (c_int32, [_P, c_int32, _P, _P]),
     'smx_ddpg_stats_f32': (c_int32, [_P, _P, _P, _P, c_int32, c_int32, _P, c_int64, _P, _P]),

@@ -1395,11 +1395,12 @@ void actor_tail(Chain& C, const smx_ddpg_rows_ln& l) {
 }
 
 // the three chains (l, l2: NO_LN, NO_LN2 without LayerNorm)
-void critic_chain(Chain& C, const smx_ddpg_rows_ln& l) {
+// (actor false: the critic-only programs of a delayed policy update -- the same chain without its last segment)
+void critic_chain(Chain& C, const smx_ddpg_rows_ln& l, bool actor = true) {
     target_actor(C, l);
     target_critic(C, C.G.tc, l.target_critic, P_TC_CAT, C.G.oO2);
     first_critic(C, l);
-    actor_kept(C, l);
+    if (actor) actor_kept(C, l);
     if (C.Q) C.Q->t.dn2 = l.dn2;
 }
 static_assert(LN_STEPS >= 13, "the critic chain has 13 layers");
@@ -1417,13 +1418,13 @@ void actor_chain(Chain& C, const smx_ddpg_rows_ln& l) {
 // critic's forward pass, loss and data gradients against y = min(y1, y2), then the actor's forward pass.  With LayerNorm:
 // the same 20 products, a forward rule behind each of the 12 hidden layers, a backward rule behind each critic's loss and
 // behind its W2^T product -- 16 rules
-void td3_critic_chain(Chain& C, const smx_ddpg_rows_ln& l, const smx_ddpg_rows_ln_second& l2) {
+void td3_critic_chain(Chain& C, const smx_ddpg_rows_ln& l, const smx_ddpg_rows_ln_second& l2, bool actor = true) {
     target_actor(C, l);
     target_critic(C, C.G.tc, l.target_critic, P_TC_CAT, C.G.oO2);
     target_critic(C, C.G.tc2, l2.target_critic2, P_TC2_CAT, C.G.oO3);
     first_critic(C, l);
     second_critic(C, l2);
-    actor_kept(C, l);
+    if (actor) actor_kept(C, l);
     if (C.Q) {
         C.Q->t.dn2 = l.dn2;
         C.Q->t.dn2_2 = l2.dn2_2;
@@ -1466,14 +1467,15 @@ int launch_chain_ln(int phase, const RArgs& G, const Prog& P, const LnProg& Q, s
     }
 }
 
-// the buffers the critic chains read and write; those they write with LayerNorm
-bool critic_io(const smx_ddpg_rows_t* a) {
+// the buffers the critic chains read and write; those they write with LayerNorm (actor false: a critic-only program,
+// which leaves the actor's buffers alone)
+bool critic_io(const smx_ddpg_rows_t* a, bool actor = true) {
     return a->x && a->x_next && a->actions && a->rewards && a->dones && a->xcat && a->h2c && a->q && a->q_next && a->y &&
-           a->dz3 && a->dz2 && a->dxcat && a->h1a && a->h2a && a->act;
+           a->dz3 && a->dz2 && a->dxcat && (!actor || (a->h1a && a->h2a && a->act));
 }
-bool critic_io_ln(const smx_ddpg_rows_ln& l) {
-    return l.c_a1 && l.cm1 && l.cr1 && l.c_a2 && l.cm2 && l.cr2 && l.dn2 && l.dz1c && l.a1 && l.am1 && l.ar1 && l.a2 && l.am2 &&
-           l.ar2;
+bool critic_io_ln(const smx_ddpg_rows_ln& l, bool actor = true) {
+    return l.c_a1 && l.cm1 && l.cr1 && l.c_a2 && l.cm2 && l.cr2 && l.dn2 && l.dz1c &&
+           (!actor || (l.a1 && l.am1 && l.ar1 && l.a2 && l.am2 && l.ar2));
 }
 
 int launch_pack(const float* const* src, const int* ld, const int* tr, int first, int last, const Layout& L, const Dims& d,
@@ -1563,38 +1565,103 @@ extern "C" int smx_ddpg_rows_pack_f32(const smx_ddpg_rows_t* a, int32_t which, s
     return launch_pack(src, ld, tr, cr ? B_CW1 : 0, cr ? B_CW2THI + 1 : B_COUNT, L_FIRST, d, a->packed, stream);
 }
 
-extern "C" int smx_ddpg_rows_critic_f32(const smx_ddpg_rows_t* a, smx_stream_t stream) {
+namespace {
+// the one-critic critic chain's launch, with (an iteration that updates the actor) or without the actor's forward pass
+int launch_critic(const smx_ddpg_rows_t* a, bool actor, smx_stream_t stream) {
     RArgs G;
     LnProg Q;
     SMX_REQUIRE(!(a && a->ln && a->second), SMX_E_UNSUPPORTED);      // (two LayerNorm critics: smx_ddpg_rows_critic_td3_f32)
     const int rc = fill(G, a, false, &Q);
     if (rc) return rc;
-    SMX_REQUIRE(critic_io(a), SMX_E_NULL);
-    SMX_REQUIRE(!a->ln || critic_io_ln(*a->ln), SMX_E_NULL);
+    SMX_REQUIRE(critic_io(a, actor), SMX_E_NULL);
+    SMX_REQUIRE(!a->ln || critic_io_ln(*a->ln, actor), SMX_E_NULL);
     Prog P;
     memset(&P, 0, sizeof(P));
     Chain C{G, P, a->ln ? &Q : nullptr, 0};
-    critic_chain(C, a->ln ? *a->ln : NO_LN);
+    critic_chain(C, a->ln ? *a->ln : NO_LN, actor);
     return a->ln ? launch_chain_ln(0, G, P, Q, stream) : launch_chain<ddpg_rows4_kernel<0>>(G, P, stream);
 }
 
-extern "C" int smx_ddpg_rows_critic_td3_f32(const smx_ddpg_rows_t* a, smx_stream_t stream) {
+// ... and TD3's
+int launch_critic_td3(const smx_ddpg_rows_t* a, bool actor, smx_stream_t stream) {
     RArgs G;
     LnProg Q;
     const int rc = fill(G, a, true, &Q);
     if (rc) return rc;
     const smx_ddpg_rows_second* s = a->second;
-    SMX_REQUIRE(critic_io(a), SMX_E_NULL);
+    SMX_REQUIRE(critic_io(a, actor), SMX_E_NULL);
     SMX_REQUIRE(s->xcat2 && s->h2c2 && s->q2 && s->q_next2 && s->dz3_2 && s->dz2_2 && s->dxcat2, SMX_E_NULL);
     const smx_ddpg_rows_ln_second* l2 = a->ln ? a->ln->second : nullptr;     // (fill: there beside `second`)
-    SMX_REQUIRE(!a->ln || critic_io_ln(*a->ln), SMX_E_NULL);
+    SMX_REQUIRE(!a->ln || critic_io_ln(*a->ln, actor), SMX_E_NULL);
     SMX_REQUIRE(!l2 || (l2->c2_a1 && l2->c2m1 && l2->c2r1 && l2->c2_a2 && l2->c2m2 && l2->c2r2 && l2->dn2_2 && l2->dz1c2),
                 SMX_E_NULL);
     Prog P;
     memset(&P, 0, sizeof(P));
     Chain C{G, P, a->ln ? &Q : nullptr, 0};
-    td3_critic_chain(C, a->ln ? *a->ln : NO_LN, l2 ? *l2 : NO_LN2);
+    td3_critic_chain(C, a->ln ? *a->ln : NO_LN, l2 ? *l2 : NO_LN2, actor);
     return a->ln ? launch_chain_ln(2, G, P, Q, stream) : launch_chain<ddpg_rows4_kernel<2>>(G, P, stream);
+}
+
+// The tail of a delayed learner's UPDATE iteration, one workgroup between the actor chain and the actor's
+// gradient-and-step launch: the iteration's statistics as the gradient-and-step launch's extra workgroup forms them --
+// the host slot chosen by the ITERATION's step word, which the actor's launch no longer reads --, then the actor's own
+// Adam step word moves on
+struct DTail {
+    int* actor_step;
+    const int* step;
+    float *stats, *stats2, *stats_host;
+    const float *q, *y, *rewards, *actions, *q_actor, *q2;
+    int A, rows;
+};
+__global__ __launch_bounds__(64 * WNW) void ddpg_rows_delay_tail_kernel(DTail T) {
+    if (T.stats) {
+        float* mirror = T.stats_host ? T.stats_host + (T.stats2 ? 16 : 8) * (*T.step & 1) : nullptr;
+        ddpg_stats_block<64 * WNW>(T.q, T.y, T.rewards, T.actions, T.A, T.A, T.q_actor, (long)T.rows, T.stats, mirror);
+        if (T.stats2)
+            ddpg_stats_block<64 * WNW>(T.q2, T.y, T.rewards, T.actions, T.A, T.A, T.q2, (long)T.rows, T.stats2,
+                                       mirror ? mirror + 8 : nullptr);
+    }
+    if (threadIdx.x == 0) *T.actor_step += 1;
+}
+}  // namespace
+
+extern "C" int smx_ddpg_rows_critic_f32(const smx_ddpg_rows_t* a, smx_stream_t stream) {
+    return launch_critic(a, true, stream);
+}
+
+extern "C" int smx_ddpg_rows_critic_td3_f32(const smx_ddpg_rows_t* a, smx_stream_t stream) {
+    return launch_critic_td3(a, true, stream);
+}
+
+extern "C" int smx_ddpg_rows_critic_only_f32(const smx_ddpg_rows_t* a, smx_stream_t stream) {
+    return launch_critic(a, false, stream);
+}
+
+extern "C" int smx_ddpg_rows_critic_only_td3_f32(const smx_ddpg_rows_t* a, smx_stream_t stream) {
+    return launch_critic_td3(a, false, stream);
+}
+
+extern "C" int smx_ddpg_rows_delay_tail_f32(const smx_ddpg_rows_t* a, int32_t* actor_step, float* stats, float* stats_host,
+                                            smx_stream_t stream) {
+    SMX_REQUIRE(actor_step, SMX_E_NULL);
+    SMX_REQUIRE(stats || !stats_host, SMX_E_NULL);
+    DTail T;
+    memset(&T, 0, sizeof(T));
+    T.actor_step = actor_step;
+    if (stats) {
+        SMX_REQUIRE(a && a->step && a->q && a->y && a->rewards && a->actions && a->q_actor, SMX_E_NULL);
+        SMX_REQUIRE(rows_ok(a->rows), SMX_E_SHAPE);
+        T.step = a->step; T.stats = stats; T.stats_host = stats_host;
+        T.q = a->q; T.y = a->y; T.rewards = a->rewards; T.actions = a->actions; T.q_actor = a->q_actor;
+        T.A = a->A; T.rows = (int)a->rows;
+        if (a->second && a->second->stats2) {        // the second critic's block, (q2, y), as the fused launch writes it
+            SMX_REQUIRE(a->second->q2, SMX_E_NULL);
+            T.stats2 = a->second->stats2; T.q2 = a->second->q2;
+        }
+    }
+    hipLaunchKernelGGL(ddpg_rows_delay_tail_kernel, dim3(1), dim3(64 * WNW), 0, smx_s(stream), T);
+    SMX_LAUNCH_CHECK();
+    return SMX_OK;
 }
 
 extern "C" int smx_ddpg_rows_actor_f32(const smx_ddpg_rows_t* a, smx_stream_t stream) {

@@ -37,6 +37,13 @@ def ddpg_rows_ln_td3(kernels):
     return bool(getattr(kernels, 'ddpg_rows_ln_td3', False))
 
 
+def ddpg_rows_delay(kernels):
+    """whether `kernels` runs the row schedule's critic-only iterations of a delayed policy update (policy_delay > 1) -- the
+    ddpg_rows_critic_only / ddpg_rows_critic_only_td3 / ddpg_rows_delay_tail methods below: its `ddpg_rows_delay`
+    attribute; an object without it keeps a learner with policy_delay > 1 on the layer-by-layer schedule"""
+    return bool(getattr(kernels, 'ddpg_rows_delay', False))
+
+
 def ddpg_rows_td3(kernels):
     """whether this kernels object runs TD3 (a second critic, clipped noise on the target action) on the row schedule --
     the ddpg_rows_second_* / ddpg_rows_critic_td3 methods below: its `ddpg_rows_td3` attribute; an object without it
@@ -1130,6 +1137,8 @@ class HipKernels(object):
     ddpg_rows_ln = True
     # use_layernorm together with TD3 on the row schedule (ddpg_rows_ln_td3(), above)
     ddpg_rows_ln_td3 = True
+    # critic-only iterations of a delayed policy update on the row schedule (ddpg_rows_delay(), above)
+    ddpg_rows_delay = True
 
     def synth_ddpg_rollout_supported(self, net, ln=False):
         """the actor shapes synth_ddpg_rollout takes; ln: with a LayerNorm behind each hidden ReLU"""
@@ -1690,6 +1699,23 @@ class HipKernels(object):
 
     def ddpg_rows_critic_td3(self, args):
         L.call('smx_ddpg_rows_critic_td3_f32', ctypes.byref(args), self._st())
+
+    # policy_delay > 1: the critic chains without the actor's forward pass (an iteration that leaves the actor and the
+    # targets alone), and the one-workgroup launch in front of a delayed learner's actor step
+    def ddpg_rows_critic_only(self, args):
+        L.call('smx_ddpg_rows_critic_only_f32', ctypes.byref(args), self._st())
+
+    def ddpg_rows_critic_only_td3(self, args):
+        L.call('smx_ddpg_rows_critic_only_td3_f32', ctypes.byref(args), self._st())
+
+    def ddpg_rows_delay_tail(self, args, actor_step, stats=None, stats_host=None):
+        """smx_ddpg_rows_delay_tail_f32: the iteration's statistics (stats: args' q, y, rewards, actions, q_actor -> [7],
+        second block to args.second.stats2; stats_host: the pinned mirror, slot *args.step & 1), then *actor_step += 1"""
+        assert actor_step.dtype == torch.int32 and actor_step.numel() == 1
+        assert stats_host is None or (stats is not None and stats_host.is_pinned() and stats_host.numel() >= 16)
+        assert stats_host is None or not (bool(args.second) and args.second.contents.stats2) or stats_host.numel() >= 32
+        L.call('smx_ddpg_rows_delay_tail_f32', ctypes.byref(args), actor_step.data_ptr(),
+               None if stats is None else stats.data_ptr(), None if stats_host is None else stats_host.data_ptr(), self._st())
 
     # use_layernorm: the four networks' gains and biases and the extra buffers ride in args.ln (smx_ddpg_rows_ln); the
     # chain launches and the gradient-and-step launch around it honour it, the other entries refuse it

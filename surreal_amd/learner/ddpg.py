@@ -34,6 +34,15 @@ rank and the fused update it also runs on the row blocks when session_config.lea
 5 with TD3's double critic; a LayerNorm rule behind each hidden layer's step; opt-in).  LayerNorm with camera observations, on
 several ranks or with ddpg_rows_fused_update = False stays layer by layer.  torchx's LayerNorm semantics are unpinned (its source is absent): taken as
 torch.nn.LayerNorm over the features.
+
+TD3's third ingredient, delayed policy updates: learner_config.algo.network.policy_delay = d (optional, default 1 = the
+reference's iteration).  Iteration k = critic_step after its increment updates the critic(s) as always; the actor -- Adam on the
+count of ACTOR updates, k / d, a device word of its own -- and every target move when k % d == 0 only.  The host picks the
+iteration's kind from k (every rank agrees), each kind has its own captured graph, and every schedule has a critic-only form:
+the layer schedule ends after the last critic's step and the statistics, the levels lose the actor's problems and levels 11-19,
+the rows run the chain programs without the actor's forward pass and 2 launches instead of 4 (3 instead of 5 with two
+critics).  The statistics of a critic-only iteration read Q(s, mu(s)) as the last actor update left it (zeros before the first;
+the buffer is workspace scratch: not part of train_state_dict).  d > 1 needs soft target updates.
 """
 import gc
 import types
@@ -81,6 +90,9 @@ class DDPGLearner(Learner):
         net = self.learner_config.algo.network
         self.use_double_critic = net.use_double_critic
         self.use_action_regularization = net.use_action_regularization
+        # TD3's delayed policy updates: the actor and every target network move once per policy_delay critic updates
+        # (1, the default: every iteration, the reference's ddpg.py:244-352)
+        self.policy_delay = self._policy_delay(net)
         self._target_update_init()
         # data-parallel: every rank owns batch_size samples of the global batch (uniform replay shards
         # per GPU, ddpg_configs.py:89-93 / SURVEY.md 8(e)); gradients are averaged before each Adam step
@@ -140,6 +152,20 @@ class DDPGLearner(Learner):
         # ... with a group's weight gradients formed in its update launch (one rank)
         self.rows_fused_update = bool(self.session_config.learner.get('ddpg_rows_fused_update', True))
 
+    @staticmethod
+    def _policy_delay(net):
+        d = net.get('policy_delay', 1)
+        if isinstance(d, bool) or not isinstance(d, (int, np.integer)) or d < 1:
+            raise ConfigError('learner_config.algo.network.policy_delay must be an integer >= 1, got %r' % (d,))
+        if d > 1 and net.target_update.type == 'hard':
+            raise ConfigError('learner_config.algo.network.policy_delay = %d needs target_update.type = "soft": what the '
+                              'hard update\'s interval counts under a delay is not defined' % d)
+        return int(d)
+
+    def _updates_actor(self, k):
+        """whether iteration k = 1, 2, ... (critic_step after its increment) also updates the actor and the targets"""
+        return k % self.policy_delay == 0
+
     # ---- target update (ddpg.py:389-428) ----------------------------------------------------
     def _target_update_init(self):
         cfg = self.learner_config.algo.network.target_update
@@ -187,6 +213,12 @@ class DDPGLearner(Learner):
         ws.lr = torch.tensor([self.lr_actor, self.lr_critic], dtype=torch.float32, device=self.device)
         ws.lr_host = (self.lr_actor, self.lr_critic)
         ws.act, ws.q_next, ws.q_actor, ws.q_policy = f(B, A), f(B), f(B), f(B)
+        # a delayed policy update: the actor's Adam counts ITS updates in a word of its own, and the statistics of the
+        # iterations before the first actor update read Q(s, mu(s)) = 0
+        ws.astep, ws.dev_astep = None, self.actor_step
+        if self.policy_delay > 1:
+            ws.astep = torch.full((1,), self.actor_step, dtype=torch.int32, device=self.device)
+            ws.q_actor.zero_()
         if self.is_pixel_input:
             ws.dxin = f(B, m.input_dim)
             ws.cnn_sk = m._cnn_stem.splitk_workspace(m.cnn, B, self.device)
@@ -230,7 +262,7 @@ class DDPGLearner(Learner):
         ws.s_obs, ws.s_next, ws.s_act, ws.s_rew, ws.s_done = f(B, D), f(B, D), f(B, A), f(B), f(B)
         if self.use_action_regularization:
             ws.s_noise, ws.act_n = f(B, A), f(B, A)
-        ws.graph = None
+        ws.graph = ws.graph_critic = None         # the captured iteration; the critic-only one of a delayed policy update
         self._rank_weight = 1.0
         ws.xerr = torch.zeros(1, dtype=torch.int32, device=self.device) if self.device != 'cpu' else None
         if self.world_size > 1:            # a rank's share of the global batch: the means are weighted sums
@@ -279,11 +311,18 @@ class DDPGLearner(Learner):
         if self._dist.exchange is None:
             self.use_graph = False            # process-group collectives are not captured
 
-    def _enqueue_adam(self, ws, group):
+    def _enqueue_adam(self, ws, group, step=None):
         """one optimiser group's Adam step (the actor's, a critic's, a critic's perception CNN's); step count and lr are
         read on the device"""
         flat, grads, exp_avg, exp_avg_sq, lr, decay, clip = group
-        self.K.adam_step_dev(flat, grads, exp_avg, exp_avg_sq, lr, ws.step, decay, clip)
+        self.K.adam_step_dev(flat, grads, exp_avg, exp_avg_sq, lr, ws.step if step is None else step, decay, clip)
+
+    def _enqueue_actor_adam(self, ws):
+        """the actor's Adam step.  With a delayed policy update its step count is the number of ACTOR updates: the word of
+        its own moves first"""
+        if ws.astep is not None:
+            ws.astep.add_(1)
+        self._enqueue_adam(ws, ws.adam_actor, ws.astep)
 
     def _enqueue_target_update(self, ws):
         """ddpg.py:389-428"""
@@ -300,7 +339,7 @@ class DDPGLearner(Learner):
             t.mul_(self._rank_weight)
             self._dist.all_reduce(t)
 
-    def _enqueue_iteration_levels(self, ws, x, xn, actions, rewards, done):
+    def _enqueue_iteration_levels(self, ws, x, xn, actions, rewards, done, update=True):
         """One DDPG iteration (ddpg.py:244-352; low-dimensional observations, one critic, one rank) scheduled by
         DEPENDENCY LEVEL: the layers of the target actor, the target critic, the critic and the actor that do not
         depend on each other share a launch (smx_linear_multi_f32), and so do a level's weight gradients --
@@ -315,6 +354,9 @@ class DDPGLearner(Learner):
         c1, c2, ld = m.c1, m.c2, m.c1 + A
         H1, H2 = m.actor.H1, m.actor.H2
         R, T = L.SMX_ACT_RELU, L.SMX_ACT_TANH
+        # (update False -- a critic-only iteration of a delayed policy update: the actor's problems leave levels 1-3,
+        # levels 11-19 and the target update are skipped)
+        only = (lambda *problems: list(problems)) if update else (lambda *problems: [])
         # 1: first layers of all four chains (none depends on another) -- and the batch's actions into the last A columns
         # of the critic's concat buffer as a fifth problem of the launch, actions . I^T (exact for FINITE actions: one product
         # with 1, the rest with 0 -- the contract |a| <= 1 of ddpg.py:262-263, which the statistics launch checks on `actions`
@@ -324,19 +366,19 @@ class DDPGLearner(Learner):
             ws.eyeA = torch.eye(A, device=self.device)
         K.linear_multi([('linear', xn, 1, ta['W1'], 1, ta['b1'], ws.h1a_t, B, H1, D, dict(act=R)),
                         ('linear', xn, 1, tc['W1'], 1, tc['b1'], ws.xcat_t, B, c1, D, dict(act=R, ldc=ld)),
-                        ('linear', x, 1, c['W1'], 1, c['b1'], ws.xcat, B, c1, D, dict(act=R, ldc=ld)),
-                        ('linear', x, 1, a['W1'], 1, a['b1'], ws.h1a, B, H1, D, dict(act=R)),
-                        ('linear', actions, 1, ws.eyeA, 1, None, ws.xcat[:, c1:], B, A, A, dict(ldc=ld))])
+                        ('linear', x, 1, c['W1'], 1, c['b1'], ws.xcat, B, c1, D, dict(act=R, ldc=ld))]
+                       + only(('linear', x, 1, a['W1'], 1, a['b1'], ws.h1a, B, H1, D, dict(act=R)))
+                       + [('linear', actions, 1, ws.eyeA, 1, None, ws.xcat[:, c1:], B, A, A, dict(ldc=ld))])
         # 2
         K.linear_multi([('linear', ws.h1a_t, 1, ta['W2'], 1, ta['b2'], ws.h2a_t, B, H2, H1, dict(act=R)),
-                        ('linear', ws.xcat, 1, c['W2'], 1, c['b2'], ws.h2c, B, c2, ld, dict(act=R)),
-                        ('linear', ws.h1a, 1, a['W2'], 1, a['b2'], ws.h2a, B, H2, H1, dict(act=R))])
+                        ('linear', ws.xcat, 1, c['W2'], 1, c['b2'], ws.h2c, B, c2, ld, dict(act=R))]
+                       + only(('linear', ws.h1a, 1, a['W2'], 1, a['b2'], ws.h2a, B, H2, H1, dict(act=R))))
         # 3: the target policy's action lands in the target critic's concat buffer, the policy's own action in the
         # concat buffer of the actor update's critic pass
         K.linear_multi([('linear', ws.h2a_t, 1, ta['W3'], 1, ta['b3'], ws.xcat_t[:, c1:], B, A, H2, dict(act=T, ldc=ld)),
-                        ('linear', ws.h2c, 1, c['W3'], 1, c['b3'], ws.q.view(B, 1), B, 1, c2, dict(act=0)),
-                        ('linear', ws.h2a, 1, a['W3'], 1, a['b3'], ws.xcat_a[:, c1:], B, A, H2, dict(act=T, ldc=ld)),
-                        ('linear', ws.h2a, 1, a['W3'], 1, a['b3'], ws.act, B, A, H2, dict(act=T))])   # (dense copy: tanh')
+                        ('linear', ws.h2c, 1, c['W3'], 1, c['b3'], ws.q.view(B, 1), B, 1, c2, dict(act=0))]
+                       + only(('linear', ws.h2a, 1, a['W3'], 1, a['b3'], ws.xcat_a[:, c1:], B, A, H2, dict(act=T, ldc=ld)),
+                              ('linear', ws.h2a, 1, a['W3'], 1, a['b3'], ws.act, B, A, H2, dict(act=T))))   # (dense copy: tanh')
         # 4, 5: Q'(s', mu'(s'))
         K.linear(ws.xcat_t, 1, tc['W2'], 1, tc['b2'], ws.h2c_t, B, c2, ld, act=R)
         K.linear(ws.h2c_t, 1, tc['W3'], 1, tc['b3'], ws.q_next.view(B, 1), B, 1, c2, act=0)
@@ -353,6 +395,9 @@ class DDPGLearner(Learner):
         K.linear_wgrad(ws.dxcat, x, ws.gc['W1'], ws.gc['b1'], c1, D, B, ldz=ld)
         # 10
         self._enqueue_adam(ws, ws.critics[0].adam)
+        if not update:               # (the statistics on Q(s, mu(s)) as the last actor update left it)
+            K.ddpg_stats(ws.q, ws.y, rewards, actions, ws.q_actor, ws.stats)
+            return
         # 11-13: Q(s, mu(s)) through the UPDATED critic; d(-mean Q)/d(layer 2) needs only that pass's ReLU mask
         K.linear(x, 1, c['W1'], 1, c['b1'], ws.xcat_a, B, c1, D, act=R, ldc=ld)
         K.linear(ws.xcat_a, 1, c['W2'], 1, c['b2'], ws.h2c_a, B, c2, ld, act=R)
@@ -364,7 +409,7 @@ class DDPGLearner(Learner):
         K.tanh_backward(ws.dz3a, ws.act, ws.dz3a)
         # 16-18: actor backward (data gradients, weight gradients), 19: its Adam step
         K.mlp3_backward(m.actor, x, ws.h1a, ws.h2a, ws.dz3a, ws.dz2a, ws.dz1a, ws.grads_a, None)
-        self._enqueue_adam(ws, ws.adam_actor)
+        self._enqueue_actor_adam(ws)
         K.ddpg_stats(ws.q, ws.y, rewards, actions, ws.q_actor, ws.stats)
         self._enqueue_target_update(ws)
 
@@ -439,7 +484,7 @@ class DDPGLearner(Learner):
         ws.rows_key = (x.data_ptr(), xn.data_ptr(), actions.data_ptr(), rewards.data_ptr(), done.data_ptr())
         return ws.rows_args
 
-    def _enqueue_iteration_rows(self, ws, x, xn, actions, rewards, done):
+    def _enqueue_iteration_rows(self, ws, x, xn, actions, rewards, done, update=True):
         """One DDPG iteration (ddpg.py:244-352; low-dimensional observations, one critic -- TD3's two below) on ROW BLOCKS: a
         workgroup carries 4 batch rows through whole chains -- target actor -> target critic -> y, critic -> loss ->
         its data gradients, and the actor's forward pass in one launch; Q(s, mu(s)) through the updated critic -> the
@@ -456,7 +501,14 @@ class DDPGLearner(Learner):
         passes; the gains' and biases' gradients and steps are further workgroups of the group's gradient-and-step launch.
         With a double critic it is TD3's 5 launches, the LayerNorm rules behind TD3's chain and the second critic's gains
         and biases stepped by its own gradient-and-step launch.  LayerNorm with camera observations, on several ranks or
-        with ddpg_rows_fused_update = False stays layer by layer (_schedule)."""
+        with ddpg_rows_fused_update = False stays layer by layer (_schedule).
+        policy_delay > 1, a critic-only iteration (update False): the critic chain without the actor's forward pass
+        (smx_ddpg_rows_critic_only_f32 / _td3_f32: the same kernels, a shorter step table) and the critic groups'
+        gradient-and-step launches WITHOUT their target, the last of them carrying the statistics (Q(s, mu(s)) as the last
+        actor update left it) -- 2 launches, 3 with TD3; no actor chain, no actor step.  Its update iterations are the 4 / 5
+        launches with the actor's step reading the actor's own step word, and one workgroup more between the actor chain
+        and that step (smx_ddpg_rows_delay_tail_f32): the statistics -- their host slot goes by the iteration's word, which
+        the actor's launch no longer reads -- and the word's increment.  5 / 6 launches."""
         K, m, mt, A = self.K, self.model, self.model_target, self.action_dim
         B, D = x.shape
         c1, c2, ld = m.c1, m.c2, m.c1 + A
@@ -475,10 +527,14 @@ class DDPGLearner(Learner):
         fuse = self.world_size == 1 and self.rows_fused_update
         assert fuse or not self.use_layernorm
         second = ws.critics[1] if self.use_double_critic else None
+        delayed = ws.astep is not None
+        if not update:               # (a critic-only iteration: the targets stay, the last critic group reports)
+            tgt = dict(tau=0.0, interval=0)
+            last = dict(stats=ws.stats if fuse else None, stats_host=ws.stats_slots if fuse and self.lazy_stats else None)
         if second is not None:
-            K.ddpg_rows_critic_td3(args)
+            (K.ddpg_rows_critic_td3 if update else K.ddpg_rows_critic_only_td3)(args)
         else:
-            K.ddpg_rows_critic(args)
+            (K.ddpg_rows_critic if update else K.ddpg_rows_critic_only)(args)
         if not fuse:
             K.linear_multi([('wgrad', ws.dxcat, x, gc['W1'], gc['b1'], c1, D, B, dict(ldz=ld)),
                             ('wgrad', ws.dz2, ws.xcat, gc['W2'], gc['b2'], c2, ld, B, {}),
@@ -486,7 +542,8 @@ class DDPGLearner(Learner):
             self._average_over_ranks(ws.grads_c)
         K.ddpg_rows_update(args, 'critic', m.critic_flat, ws.grads_c, self.critic_exp_avg, self.critic_exp_avg_sq,
                            ws.lr[1:2], ws.step, self.critic_regularization, self.critic_gradient_clip_value,
-                           target=mt.critic_flat, wgrad=fuse, **tgt)
+                           target=mt.critic_flat if update else None, wgrad=fuse,
+                           **(tgt if update or second is not None else dict(tgt, **last)))
         if second is not None:
             g2, w2 = second.gv, second.w
             if not fuse:
@@ -496,17 +553,28 @@ class DDPGLearner(Learner):
                 self._average_over_ranks(second.grads)
             K.ddpg_rows_update(args, 'critic2', second.model.critic_flat, second.grads, self.critic2_moments[0],
                                self.critic2_moments[1], ws.lr[1:2], ws.step, self.critic_regularization,
-                               self.critic_gradient_clip_value, target=second.target.critic_flat, wgrad=fuse, **tgt)
-        K.ddpg_rows_actor(args)
-        if not fuse:
-            K.linear_multi([('wgrad', ws.dz1a, x, ga['W1'], ga['b1'], H1, D, B, {}),
-                            ('wgrad', ws.dz2a, ws.h1a, ga['W2'], ga['b2'], H2, H1, B, {}),
-                            ('wgrad', ws.dz3a, ws.h2a, ga['W3'], ga['b3'], A, H2, B, {})])
-            self._average_over_ranks(ws.grads_a)
-        K.ddpg_rows_update(args, 'actor', m.actor_flat, ws.grads_a, self.actor_exp_avg, self.actor_exp_avg_sq,
-                           ws.lr[0:1], ws.step, self.actor_regularization, self.actor_gradient_clip_value,
-                           target=mt.actor_flat, wgrad=fuse, stats=ws.stats if fuse else None,
-                           stats_host=ws.stats_slots if fuse and self.lazy_stats else None, **tgt)
+                               self.critic_gradient_clip_value, target=second.target.critic_flat if update else None,
+                               wgrad=fuse, **(tgt if update else dict(tgt, **last)))
+        if update:
+            K.ddpg_rows_actor(args)
+            if not fuse:
+                K.linear_multi([('wgrad', ws.dz1a, x, ga['W1'], ga['b1'], H1, D, B, {}),
+                                ('wgrad', ws.dz2a, ws.h1a, ga['W2'], ga['b2'], H2, H1, B, {}),
+                                ('wgrad', ws.dz3a, ws.h2a, ga['W3'], ga['b3'], A, H2, B, {})])
+                self._average_over_ranks(ws.grads_a)
+            # the statistics ride in the actor's launch -- unless the learner delays its policy updates: the actor's
+            # launch then reads the ACTOR's step word, and the workgroup in front of it reports and moves that word
+            ride = fuse and not delayed
+            if delayed and fuse:
+                K.ddpg_rows_delay_tail(args, ws.astep, stats=ws.stats,
+                                       stats_host=ws.stats_slots if self.lazy_stats else None)
+            elif delayed:
+                ws.astep.add_(1)
+            K.ddpg_rows_update(args, 'actor', m.actor_flat, ws.grads_a, self.actor_exp_avg, self.actor_exp_avg_sq,
+                               ws.lr[0:1], ws.astep if delayed else ws.step, self.actor_regularization,
+                               self.actor_gradient_clip_value, target=mt.actor_flat, wgrad=fuse,
+                               stats=ws.stats if ride else None,
+                               stats_host=ws.stats_slots if ride and self.lazy_stats else None, **tgt)
         ws.stats_zero_copy = bool(fuse and self.lazy_stats)
         if not fuse:                 # (fused: the statistics are one more workgroup of the actor's launch)
             K.ddpg_stats(ws.q, ws.y, rewards, actions, ws.q_actor, ws.stats)
@@ -552,7 +620,7 @@ class DDPGLearner(Learner):
         if self.is_pixel_input:
             self._enqueue_adam(ws, c.adam_p)
 
-    def _enqueue_iteration_layers(self, ws, x, xn, actions, rewards, done, pix=None, pix_next=None):
+    def _enqueue_iteration_layers(self, ws, x, xn, actions, rewards, done, pix=None, pix_next=None, update=True):
         """one DDPG iteration (ddpg.py:244-352) layer by layer, with every switch: camera observations (the perception CNN
         in front of both networks, trained by the critic loss, ddpg_net.py:37-88), the TD3 double critic and action
         regularisation (ddpg.py:119-147, 266-283, 312-319), several ranks -- and use_layernorm, which the model's passes
@@ -608,44 +676,51 @@ class DDPGLearner(Learner):
             K.ddpg_stats(c2.q, c2.y, rewards, actions, c2.q, c2.stats)
             self._average_over_ranks(c2.stats[:6])
         # ---- actor update through the UPDATED critic: loss = -mean Q(s, mu(s)) ----
-        m.actor_forward(x, c.w, ws.act)
-        m.critic_forward(x, ws.act, c.w, ws.q_actor)
-        K.fill(c.dz3, -1.0 / B)
-        m.actor_backward(x, c.w, ws.bw, c.dz3, ws.act, ws.ga, ws.grads_a)
-        self._average_over_ranks(ws.grads_a)
-        self._enqueue_adam(ws, ws.adam_actor)
+        # (update False -- a critic-only iteration of a delayed policy update: the iteration ends with the statistics, on
+        # Q(s, mu(s)) as the last actor update left it)
+        if update:
+            m.actor_forward(x, c.w, ws.act)
+            m.critic_forward(x, ws.act, c.w, ws.q_actor)
+            K.fill(c.dz3, -1.0 / B)
+            m.actor_backward(x, c.w, ws.bw, c.dz3, ws.act, ws.ga, ws.grads_a)
+            self._average_over_ranks(ws.grads_a)
+            self._enqueue_actor_adam(ws)
         K.ddpg_stats(ws.q_policy, c.y, rewards, actions, ws.q_actor, c.stats)
         self._average_over_ranks(c.stats[:6])       # means over the global batch (max |a| stays local)
-        self._enqueue_target_update(ws)
+        if update:
+            self._enqueue_target_update(ws)
 
     def _schedule(self, B, D):
         """which launch schedule an iteration on B rows of D inputs takes -- 'rows' (row blocks), 'levels' (dependency
         levels) or 'layers' (layer by layer: every switch).  Asked at each enqueue: level_schedule / row_schedule may be
         set after construction"""
+        # (a delayed policy update takes the rows only where the kernels run its critic-only iterations)
+        can_rows = self.policy_delay == 1 or KN.ddpg_rows_delay(self.K)
         if self.use_layernorm:
             # LayerNorm takes the rows only when asked to (ddpg_row_schedule = True) and where _rows_dims lets it:
             # low-dimensional observations, one rank, the fused update (one critic or two); otherwise layer by layer
-            return 'rows' if self.row_schedule is True and self._rows_dims(D, B) is not None else 'layers'
+            return 'rows' if self.row_schedule is True and can_rows and self._rows_dims(D, B) is not None else 'layers'
         if not self.is_pixel_input:
             if self.use_double_critic:
                 # TD3 takes the rows only when asked to (ddpg_row_schedule = True), where the kernels run it and the
                 # shapes fit; unset, it stays layer by layer as before -- and there are no levels for two critics
-                return 'rows' if self.row_schedule is True and self._rows_dims(D, B) is not None else 'layers'
+                return 'rows' if self.row_schedule is True and can_rows and self._rows_dims(D, B) is not None else 'layers'
             rows = self.row_schedule if self.row_schedule is not None else B <= 1024
-            if rows and self._rows_dims(D, B) is not None:
+            if rows and can_rows and self._rows_dims(D, B) is not None:
                 return 'rows'
             if self.level_schedule and self.world_size == 1:
                 return 'levels'
         return 'layers'
 
-    def _enqueue_iteration(self, ws, x, xn, actions, rewards, done, pix=None, pix_next=None):
-        """one DDPG iteration (ddpg.py:244-352) as a launch sequence without host round trips"""
+    def _enqueue_iteration(self, ws, x, xn, actions, rewards, done, pix=None, pix_next=None, update=True):
+        """one DDPG iteration (ddpg.py:244-352) as a launch sequence without host round trips; update False: a critic-only
+        iteration of a delayed policy update -- everything up to the critics' steps and the statistics"""
         schedule = self._schedule(*x.shape)
         if schedule == 'rows':
-            return self._enqueue_iteration_rows(ws, x, xn, actions, rewards, done)
+            return self._enqueue_iteration_rows(ws, x, xn, actions, rewards, done, update)
         if schedule == 'levels':
-            return self._enqueue_iteration_levels(ws, x, xn, actions, rewards, done)
-        return self._enqueue_iteration_layers(ws, x, xn, actions, rewards, done, pix, pix_next)
+            return self._enqueue_iteration_levels(ws, x, xn, actions, rewards, done, update)
+        return self._enqueue_iteration_layers(ws, x, xn, actions, rewards, done, pix, pix_next, update)
 
     def _optimize(self, obs, actions, rewards, obs_next, done):       # ddpg.py:244-352
         x = obs['low_dim']['flat_inputs']
@@ -655,6 +730,8 @@ class DDPGLearner(Learner):
         if ws.dev_step != self.critic_step:          # restored from a checkpoint
             ws.step.fill_(self.critic_step)
             self.invalidate_packed()
+        if ws.astep is not None and ws.dev_astep != self.actor_step:
+            ws.astep.fill_(self.actor_step)
         if ws.lr_host != (self.lr_actor, self.lr_critic):
             ws.lr_host = (self.lr_actor, self.lr_critic)
             ws.lr.copy_(torch.tensor(ws.lr_host, dtype=torch.float32))
@@ -676,29 +753,35 @@ class DDPGLearner(Learner):
             # ddpg.py:268-274: policy_noise 0.2 clipped at 0.5, from numpy's global stream
             noise = np.clip(np.random.normal(0, 0.2, size=(self.batch_size, self.action_dim)), -0.5, 0.5)
             ws.s_noise.copy_(torch.as_tensor(noise, dtype=torch.float32))
-        if self.use_graph and ws.graph is None:
+        # the iteration's kind, from its number alone (every rank agrees): with a delayed policy update a workspace holds
+        # two captured graphs, the full iteration and the critic-only one, each captured after one eager iteration of its kind
+        update = self._updates_actor(self.critic_step + 1)
+        which = 'graph' if update else 'graph_critic'
+        batch = (ws.s_obs, ws.s_next, ws.s_act, ws.s_rew, ws.s_done) + tuple(frames)
+        if self.use_graph and getattr(ws, which) is None:
             # capture after one eager iteration (lazy allocations, module load); its effects are
             # real: the capture itself executes nothing
-            self._enqueue_iteration(ws, ws.s_obs, ws.s_next, ws.s_act, ws.s_rew, ws.s_done, *frames)
+            self._enqueue_iteration(ws, *batch, update=update)
             gc.collect()
             gc.disable()               # a collection inside capture may free device memory: illegal
             try:
                 g = torch.cuda.CUDAGraph()
                 with torch.cuda.graph(g):
-                    self._enqueue_iteration(ws, ws.s_obs, ws.s_next, ws.s_act, ws.s_rew, ws.s_done, *frames)
-                ws.graph = g
+                    self._enqueue_iteration(ws, *batch, update=update)
+                setattr(ws, which, g)
             finally:
                 gc.enable()
-        elif ws.graph is not None:
+        elif getattr(ws, which) is not None:
             self._rows_refresh(ws)
-            ws.graph.replay()
+            getattr(ws, which).replay()
             if getattr(ws, 'rows_args', None) is not None:
                 ws.rows_versions = self._rows_versions()
         else:
-            self._enqueue_iteration(ws, ws.s_obs, ws.s_next, ws.s_act, ws.s_rew, ws.s_done, *frames)
+            self._enqueue_iteration(ws, *batch, update=update)
         self.critic_step += 1
-        self.actor_step += 1
-        ws.dev_step = self.critic_step
+        if update:
+            self.actor_step += 1
+        ws.dev_step, ws.dev_astep = self.critic_step, self.actor_step
         if self.target_update_type == 'hard':
             self.target_update_counter += 1
         return self._collect_stats(ws)
@@ -707,7 +790,7 @@ class DDPGLearner(Learner):
         """the staged camera frames of s and s' (again): the captured iteration read the old ones, so the graph goes"""
         ws.s_pix = torch.empty(tuple(shape), device=self.device, dtype=dtype)
         ws.s_pix_next = torch.empty(tuple(shape), device=self.device, dtype=dtype)
-        ws.graph = None
+        ws.graph = ws.graph_critic = None
 
     def staging_fields(self, batch_size):
         """the buffers the captured iteration reads its batch from, by replay field name:
@@ -844,6 +927,8 @@ class DDPGLearner(Learner):
         words['publish_seq'] = int(getattr(self, '_publish_seq', 0))
         if self.target_update_type == 'hard':
             words['target_update_counter'] = int(self.target_update_counter)
+        if self.policy_delay > 1:        # (a state without the key is of a learner that updates its policy every iteration)
+            words['policy_delay'] = int(self.policy_delay)
         return {'kind': 'DDPGLearner', 'tensors': self._train_tensors(), 'words': words,
                 'workspace': None if self._ws is None else list(self._ws.key)}
 
@@ -864,7 +949,10 @@ class DDPGLearner(Learner):
         if ('target_update_counter' in words) != (self.target_update_type == 'hard'):
             raise ValueError('%s: the state is of a %s target update, this learner\'s is %s'
                              % (who, 'hard' if 'target_update_counter' in words else 'soft', self.target_update_type))
-        self._flush_stats()                          # (a read-back in flight belongs to the state that goes)
+        if int(words.get('policy_delay', 1)) != self.policy_delay:
+            raise ValueError('%s: the state is of policy_delay = %d, this learner\'s is %d'
+                             % (who, int(words.get('policy_delay', 1)), self.policy_delay))
+        self._flush_stats()                         # (a read-back in flight belongs to the state that goes)
         load_tensors(sd['tensors'], live)
         for k in self._TRAIN_WORDS:
             setattr(self, k, type(getattr(self, k))(words[k]))
@@ -877,6 +965,9 @@ class DDPGLearner(Learner):
         if ws is not None:
             ws.step.fill_(self.critic_step)
             ws.dev_step = self.critic_step
+            if ws.astep is not None:         # the actor's own Adam step word of a delayed policy update
+                ws.astep.fill_(self.actor_step)
+            ws.dev_astep = self.actor_step
             ws.lr_host = (self.lr_actor, self.lr_critic)
             ws.lr.copy_(torch.tensor(ws.lr_host, dtype=torch.float32))
         self.invalidate_packed()

@@ -1,4 +1,8 @@
-"""Default DDPG hyper-parameters (surreal/main/ddpg_configs.py:16-98)."""
+"""Default DDPG hyper-parameters (surreal/main/ddpg_configs.py:16-98).
+
+One optional key beyond the reference's, absent from the defaults below: ``algo.network.policy_delay`` (an integer >= 1, read
+with ``.get('policy_delay', 1)``) -- TD3's delayed policy updates: every iteration updates the critic(s); the actor and every
+target network move once per ``policy_delay`` iterations (DDPGLearner).  Values above 1 need ``target_update.type = 'soft'``."""
 from surreal_amd.session import (Config, BASE_LEARNER_CONFIG, BASE_ENV_CONFIG,
                                  LOCAL_SESSION_CONFIG)
 
