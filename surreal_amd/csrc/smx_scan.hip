@@ -120,6 +120,33 @@ __global__ __launch_bounds__(256) void gae_norm_kernel(
     for (long i = threadIdx.x; i < n; i += blockDim.x) adv[i] = (__builtin_nontemporal_load(adv + i) - mean) / den;
 }
 
+// The dynamic LDS of a GAE launch -- four waves of Vm[N+1] | r[N] | delta[N] -- and the host side of asking for it: ONE
+// definition for both entry points.  `cap` is what the entry point is specified to take (160 KiB: N <= 3413; gae_norm keeps
+// to 128 KiB: N <= 2730); a shape above it is refused whatever the device has.  Above GAE_LDS_OPT_IN the kernel's
+// hipFuncAttributeMaxDynamicSharedMemorySize has to be raised first: then the request, together with the kernel's static
+// LDS (gae_norm_kernel: the moments' 40 B and the ticket's flag), is held against what the DEVICE grants one workgroup
+// (hipDeviceAttributeMaxSharedMemoryPerBlock) and refused with SMX_E_UNSUPPORTED before anything is launched where it
+// does not fit -- never a raw hipError_t from a launch that could not be placed.  None of these calls touches a stream:
+// they are legal while one is being captured, and a captured graph's replays do not repeat them.
+constexpr size_t GAE_LDS_OPT_IN = 48 * 1024;
+
+static int gae_lds(const void* kernel, size_t cap, int N, size_t* lds_out) {
+    const size_t lds = (size_t)4 * (3 * (size_t)N + 1) * sizeof(float);
+    *lds_out = lds;
+    SMX_REQUIRE(lds <= cap, SMX_E_UNSUPPORTED);
+    if (lds <= GAE_LDS_OPT_IN) return SMX_OK;
+    int dev = 0, granted = 0;
+    hipFuncAttributes fa;
+    if (hipGetDevice(&dev) != hipSuccess ||
+        hipDeviceGetAttribute(&granted, hipDeviceAttributeMaxSharedMemoryPerBlock, dev) != hipSuccess ||
+        hipFuncGetAttributes(&fa, kernel) != hipSuccess || lds + fa.sharedSizeBytes > (size_t)granted ||
+        hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {
+        (void)hipGetLastError();   // (a failed query leaves its code behind: the refusal is the whole answer)
+        return SMX_E_UNSUPPORTED;
+    }
+    return SMX_OK;
+}
+
 extern "C" int smx_windowed_gae_returns_f32(const float* values, const float* values_tail,
                                             const float* rewards,
                                             const float* dones, const float* gamma_pow,
@@ -128,13 +155,9 @@ extern "C" int smx_windowed_gae_returns_f32(const float* values, const float* va
                                             float* ret, smx_stream_t stream) {
     SMX_REQUIRE(values && rewards && dones && gamma_pow && lam_pow && adv && ret, SMX_E_NULL);
     SMX_REQUIRE(B > 0 && N > 0 && H > 0 && H <= N, SMX_E_SHAPE);
-    const size_t lds = (size_t)4 * (3 * (size_t)N + 1) * sizeof(float);
-    SMX_REQUIRE(lds <= 160 * 1024, SMX_E_UNSUPPORTED);
-    if (lds > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute((const void*)gae_kernel,
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return (int)e;
-    }
+    size_t lds;
+    const int rc = gae_lds((const void*)gae_kernel, 160 * 1024, N, &lds);
+    if (rc != SMX_OK) return rc;
     hipLaunchKernelGGL(gae_kernel, dim3((B + 3) / 4), dim3(256), lds, smx_s(stream), values,
                        values_tail, rewards, dones, gamma_pow, lam_pow, gamma, gamma_H, B, N, H, adv, ret);
     SMX_LAUNCH_CHECK();
@@ -148,13 +171,9 @@ extern "C" int smx_windowed_gae_norm_f32(const float* values, const float* value
                                          smx_stream_t stream) {
     SMX_REQUIRE(values && rewards && dones && gamma_pow && lam_pow && adv && ret && adv_moments && ticket, SMX_E_NULL);
     SMX_REQUIRE(B > 0 && N > 0 && H > 0 && H <= N, SMX_E_SHAPE);
-    const size_t lds = (size_t)4 * (3 * (size_t)N + 1) * sizeof(float);
-    SMX_REQUIRE(lds <= 128 * 1024, SMX_E_UNSUPPORTED);
-    if (lds > 48 * 1024) {
-        hipError_t e = hipFuncSetAttribute((const void*)gae_norm_kernel,
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return (int)e;
-    }
+    size_t lds;
+    const int rc = gae_lds((const void*)gae_norm_kernel, 128 * 1024, N, &lds);
+    if (rc != SMX_OK) return rc;
     hipLaunchKernelGGL(gae_norm_kernel, dim3((B + 3) / 4), dim3(256), lds, smx_s(stream), values, values_tail,
                        rewards, dones, gamma_pow, lam_pow, gamma, gamma_H, B, N, H, adv, ret, adv_moments, min_std,
                        (int*)ticket);
