@@ -690,6 +690,43 @@ __device__ __forceinline__ void copy_window(int N, int first, Ld ld, St st) {
     }
 }
 
+// ---- the policy step's pieces the recording and the evaluation kernels share ---------------------------------------------
+
+__device__ __forceinline__ float clip1(float a) {
+    if (a == a) a = fminf(fmaxf(a, -1.0f), 1.0f);          // (numpy's clip keeps a NaN)
+    return a;
+}
+
+// The sampling head (smx_diaggauss_sample_f32's expressions) on one (actor, action) pair: the clipped action from the
+// pair's mean, standard deviation and normal draw; noisy false: the policy acts on its mean.
+__device__ __forceinline__ float gauss_act(float mu, float sd, float ev, bool noisy) {
+    return clip1(noisy ? ev * sd + mu : mu);
+}
+
+// The LSTM cell pass behind the gate pass (smx_lstm.hip's gate functions and update order): thread q owns the (row, unit)
+// pairs q + RNTH i.  hook(r, j, h_before, c_before) runs between reading the pair's old state and writing its new one
+// (h_before: the tile's word, read where the hook uses it); a padded unit stays exactly zero whatever its weights.
+template <int RB, typename Args, typename Hook>
+__device__ __forceinline__ void lstm_cells(const Args& G, float* sm, int tid, Hook hook) {
+    const float* gs = sm + G.off_g;
+    const int H = G.H, ldx = G.ldx, ldg = G.ldg, Hl = G.Hl;
+    float* cst = sm + G.off_c;
+#pragma unroll 1
+    for (int q = tid; q < RB * H; q += RNTH) {
+        const int r = q / H, j = q - r * H;
+        const float* g = gs + r * ldg + j;
+        const float gi = fast_sigm(g[0]), gf = fast_sigm(g[H]), gg = fast_tanh(g[2 * H]), go = fast_sigm(g[3 * H]);
+        const float c0 = cst[q];
+        float c = gf * c0 + gi * gg;
+        float h = go * fast_tanh(c);
+        if (j >= Hl) c = h = 0.f;
+        hook(r, j, (const float&)sm[r * ldx + G.Dp + j], c0);
+        cst[q] = c;
+        sm[r * ldx + G.Dp + j] = h;
+    }
+    SMX_LDS_BARRIER();
+}
+
 // RG row groups of four actors per workgroup (round 6; smx_rows4_mma.inc.h).  1024 actors: RG = 1 -> 256 workgroups, one per
 // CU.  The host picks the smallest RG whose grid fits the chip once (more actors per workgroup = fewer passes over the
 // packed weights per actor; fewer = more CUs at work).
@@ -758,6 +795,8 @@ __device__ __forceinline__ void ppo_rollout(Args G, Clk C = Clk{}, const smx_res
     // of both tiles, keeps those 4 KB of packed weights in registers for the whole rollout (no loads at all), and the
     // eight partial sums of a (row, action) pair meet in the sampling head, added in wave order.  Shapes with more than 8
     // chunks (H2 > 256) or more than 2 tiles take the generic loop.
+    // (ppo_eval_kernel repeats the load, the chunk pass and the fold word for word: moved into functions, whether over a
+    // struct or over these locals, they compiled to other SGPR-spill counts in several recording kernels)
     const int tiles3 = (A + 15) >> 4, C3 = pack_chunks(G.H2);
     const bool l3res = C3 <= RNWV && tiles3 <= 2;
     // (16-actor blocks: the register budget has no room for them -- re-read from L2 every step, the same words)
@@ -774,7 +813,7 @@ __device__ __forceinline__ void ppo_rollout(Args G, Clk C = Clk{}, const smx_res
         }
     };
     if (W3REG) load_w3();
-    float* red3 = sm + G.off_red3;               // [RNWV][RB][32]: the waves' partial output sums
+    float* red3 = sm + G.off_red3;
     // the sampling head's per-pair constants (the same expressions, formed once instead of every step)
     const int hr = tid / A, hj = tid - hr * A;            // RB x A <= 512 pairs
     const float b3v = G.b3[hj];
@@ -841,63 +880,46 @@ __device__ __forceinline__ void ppo_rollout(Args G, Clk C = Clk{}, const smx_res
             layers4<RG, NT, true>(G, sm, l3res ? 2 : 3, G.out_act, wv, lane, [&](int l) {
                 if (l >= 0) { RSTAMP(1 + l); return; }
                 RSTAMP(6);
-                // ---- the cell pass (smx_lstm.hip's gate functions and update order); records the state BEFORE the step
-                const float* gs = sm + G.off_g;
-                const int H = G.H, ldx = G.ldx, ldg = G.ldg, Hl = G.Hl;
-                float* cst = sm + G.off_c;
-#pragma unroll 1
-                for (int q = tid; q < RB * H; q += RNTH) {
-                    const int r = q / H, j = q - r * H;
-                    {
-                        const float* g = gs + r * ldg + j;
-                        const float gi = fast_sigm(g[0]), gf = fast_sigm(g[H]), gg = fast_tanh(g[2 * H]),
-                                    go = fast_sigm(g[3 * H]);
-                        const float c0 = cst[q];
-                        float c = gf * c0 + gi * gg;
-                        float h = go * fast_tanh(c);
-                        if (j >= Hl) c = h = 0.f;            // (a padded unit: exactly zero whatever its weights)
-                        float* hp = sm + r * ldx + G.Dp + j;
-                        if (r < nrows && j < Hl) {
-                            const long a = row0 + r;
-                            if (G.cell_roll) {
-                                float* cp = G.cell_roll + ((a * R + slot) * 2) * Hl + j;
-                                __builtin_nontemporal_store(*hp, cp);
-                                __builtin_nontemporal_store(c0, cp + Hl);
+                // ---- the cell pass; the hook records the state BEFORE the step
+                lstm_cells<RB>(G, sm, tid, [&](int r, int j, const float& hb, float c0) {
+                    const int Hl = G.Hl;
+                    if (r < nrows && j < Hl) {
+                        const long a = row0 + r;
+                        if (G.cell_roll) {
+                            float* cp = G.cell_roll + ((a * R + slot) * 2) * Hl + j;
+                            __builtin_nontemporal_store(hb, cp);
+                            __builtin_nontemporal_store(c0, cp + Hl);
+                        }
+                        if (last_step && G.h_before) {
+                            G.h_before[a * Hl + j] = hb;
+                            G.c_before[a * Hl + j] = c0;
+                        }
+                        if constexpr (WIN) {
+                            const WinArgs& W = G.W;
+                            float* cc = W.ccell + (size_t)a * W.S * 2 * Hl + j;
+                            const RowClk k = rowclk(r);
+                            if (k.wstart) {
+                                float* cw = cc + (size_t)((k.t / W.adv) % W.S) * 2 * Hl;
+                                cw[0] = hb;
+                                cw[Hl] = c0;
                             }
-                            if (last_step && G.h_before) {
-                                G.h_before[a * Hl + j] = *hp;
-                                G.c_before[a * Hl + j] = c0;
+                            bool closes = k.wclose;
+                            // ((CLK) the row_off word is read here, at closing steps only: the row's head lane
+                            // publishes its copy only behind the layers)
+                            int off = 0;
+                            if constexpr (CLK) {
+                                if (closes) off = C.row_off[(size_t)step * G.n + a];
                             }
-                            if constexpr (WIN) {
-                                const WinArgs& W = G.W;
-                                float* cc = W.ccell + (size_t)a * W.S * 2 * Hl + j;
-                                const RowClk k = rowclk(r);
-                                if (k.wstart) {
-                                    float* cw = cc + (size_t)((k.t / W.adv) % W.S) * 2 * Hl;
-                                    cw[0] = *hp;
-                                    cw[Hl] = c0;
-                                }
-                                bool closes = k.wclose;
-                                // ((CLK) the row_off word is read here, at closing steps only: the row's head lane
-                                // publishes its copy only behind the layers)
-                                int off = 0;
-                                if constexpr (CLK) {
-                                    if (closes) off = C.row_off[(size_t)step * G.n + a];
-                                }
-                                const long long row = fifo_row(a, off, closes);
-                                if (closes) {
-                                    const float* cr = cc + (size_t)(((k.t + 1 - W.N) / W.adv) % W.S) * 2 * Hl;
-                                    float* d = W.cells + row * 2 * Hl + j;
-                                    __builtin_nontemporal_store(cr[0], d);
-                                    __builtin_nontemporal_store(cr[Hl], d + Hl);
-                                }
+                            const long long row = fifo_row(a, off, closes);
+                            if (closes) {
+                                const float* cr = cc + (size_t)(((k.t + 1 - W.N) / W.adv) % W.S) * 2 * Hl;
+                                float* d = W.cells + row * 2 * Hl + j;
+                                __builtin_nontemporal_store(cr[0], d);
+                                __builtin_nontemporal_store(cr[Hl], d + Hl);
                             }
                         }
-                        cst[q] = c;
-                        *hp = h;
                     }
-                }
-                SMX_LDS_BARRIER();
+                });
                 RSTAMP(7);
             }, G.Dp, G.H, gate);
         } else {
@@ -939,7 +961,7 @@ __device__ __forceinline__ void ppo_rollout(Args G, Clk C = Clk{}, const smx_res
             SMX_LDS_BARRIER();
             RSTAMP(3);
         }
-        // ---- sampling head (smx_diaggauss_sample_f32's expressions): one (actor, action) pair per lane -------
+        // ---- sampling head: one (actor, action) pair per lane ---------------------------------------------------
         if (hr < nrows) {
             const long a = row0 + hr;
             float mu;
@@ -955,8 +977,7 @@ __device__ __forceinline__ void ppo_rollout(Args G, Clk C = Clk{}, const smx_res
                 mu = outs[hr * RLDO + hj];
             }
             const float sd = sd0;
-            float act = noisy ? ev * sd + mu : mu;
-            if (act == act) act = fminf(fmaxf(act, -1.0f), 1.0f);
+            const float act = gauss_act(mu, sd, ev, noisy);
             s_act[hr * RMAX_A + hj] = act;
             if constexpr (!WIN) {
             // (the rollout tables are written once and read by a later launch: streaming stores, so that 3 MB of them per
@@ -1246,8 +1267,7 @@ __global__ __launch_bounds__(RNTH) void rollout16_kernel(RollArgs G) {
             const float mu = outs[hr * RLDO + hj];
             float sd = expf(G.log_var[hj]);
             if (G.noise_scale) sd = sd * G.noise_scale[a];
-            float act = noisy ? ev * sd + mu : mu;
-            if (act == act) act = fminf(fmaxf(act, -1.0f), 1.0f);
+            const float act = gauss_act(mu, sd, ev, noisy);
             s_act[hr * RMAX_A + hj] = act;
             if (G.act_roll) G.act_roll[(a * R + slot) * A + hj] = act;
             if (G.pd_roll) {
@@ -1280,11 +1300,6 @@ __global__ __launch_bounds__(RNTH) void rollout16_kernel(RollArgs G) {
 }
 
 // ---- DDPG ------------------------------------------------------------------------------------------------------------
-
-__device__ __forceinline__ float clip1(float a) {
-    if (a == a) a = fminf(fmaxf(a, -1.0f), 1.0f);          // (numpy's clip keeps a NaN)
-    return a;
-}
 
 // ddpg_agent.py:176-184 on one (actor, action) pair: clip, the exploration noise in fp64 rounded once into the fp32
 // action (action += noise() on a float32 array), clip.  x: the pair's OU state, zeroed at the episode start (pre_episode,
@@ -1513,11 +1528,11 @@ __global__ __launch_bounds__(RNTH) void ddpg_rollout_kernel(DdpgKernelArgs<POP, 
 // is episode first_episode + i of local actor a, and a launch over n actors x E episodes is n E rows on the 4-, 8- or
 // 16-row blocks of the rollouts above (RollBase.n: the rows; the tail block as there), each walked through exactly
 // episode_len steps.  A row begins where eval_start puts it -- the stream's draw, else init_state[a] -- and `state` is
-// never touched.  The policy step is the recording kernels': clear_tiles, layers4 with their NT / COLS choices, their
-// head expressions, EnvLanes::step with done = false throughout (the reset behind the final step is unobservable), so a
-// row's actions have the bits of the recording launches at every block size.  The owner lane of a row keeps its fp64
-// return in a register, 0.0 + (double)rew in step order (episode_step's sum), and stores it once at the end: no LDS
-// monitor words, no HBM traffic per step, no atomics.
+// never touched.  The policy step is the recording kernels': clear_tiles, layers4 with their NT / COLS choices, the split
+// output layer (written out as in ppo_rollout), gauss_act, lstm_cells, EnvLanes::step with done = false throughout (the
+// reset behind the final step is unobservable), so a row's actions have the bits of the recording launches at every
+// block size.  The owner lane of a row keeps its fp64 return in a register, 0.0 + (double)rew in step order
+// (episode_step's sum), and stores it once at the end: no LDS monitor words, no HBM traffic per step, no atomics.
 struct EvalTail {
     int E;                                      // episodes per actor
     smx_reset_stream rst;                       // rst.episode: first_episode (read by eval_start only)
@@ -1596,7 +1611,7 @@ struct EvalReturns {
 };
 struct EvalNoRow {};
 
-// PPO: ppo_window_kernel's / lstm_window_kernel's step (NT, COLS as there; the split output layer, the head) without a
+// PPO: ppo_window_kernel's / lstm_window_kernel's step (NT, COLS as there; gauss_act, lstm_cells) without a
 // record.  LSTM rows start from zero h, c (PPOAgent.reset, ppo_agent.py:169-178).  A sampling launch (nstream.enabled:
 // eval_stochastic) draws row (a, i)'s step t at normal(seed, actor_base + a, first_step + i L + t, j): what a serial run
 // of the actor's E episodes on that stream draws.
@@ -1639,7 +1654,7 @@ __global__ __launch_bounds__(RNTH) void ppo_eval_kernel(PEvalKernelArgs<SETS> G)
         for (int q = tid; q < RB * G.H; q += RNTH) cst[q] = 0.f;       // (h: the tile's cleared columns)
         SMX_LDS_BARRIER();
     }
-    // ---- the split output layer and the head's constants: ppo_rollout's ------------------------------------------------
+    // ---- the split output layer: ppo_rollout's, word for word (see there) ------------------------------------------------
     const int tiles3 = (A + 15) >> 4, C3 = pack_chunks(G.H2);
     const bool l3res = C3 <= RNWV && tiles3 <= 2;
     constexpr bool W3REG = RG < 4;
@@ -1655,7 +1670,8 @@ __global__ __launch_bounds__(RNTH) void ppo_eval_kernel(PEvalKernelArgs<SETS> G)
         }
     };
     if (W3REG) load_w3();
-    float* red3 = sm + G.off_red3;               // [RNWV][RB][32]: the waves' partial output sums
+    float* red3 = sm + G.off_red3;
+    // the head's per-pair constants
     const int hr = tid / A, hj = tid - hr * A;            // RB x A <= 512 pairs
     const float b3v = (G.b3 + shift)[hj];
     const float sd0 = expf((G.log_var + shift)[hj]);
@@ -1677,23 +1693,7 @@ __global__ __launch_bounds__(RNTH) void ppo_eval_kernel(PEvalKernelArgs<SETS> G)
             const PreLayer gate{G.Pg, G.bg, 4 * G.H, G.Dp + G.H, G.off_g, G.ldg};
             layers4<RG, NT, true>(G, sm, l3res ? 2 : 3, G.out_act, wv, lane, [&](int l) {
                 if (l >= 0) return;
-                // ---- the cell pass (smx_lstm.hip's gate functions and update order) ----
-                const float* gs = sm + G.off_g;
-                const int H = G.H, ldx = G.ldx, ldg = G.ldg, Hl = G.Hl;
-                float* cst = sm + G.off_c;
-#pragma unroll 1
-                for (int q = tid; q < RB * H; q += RNTH) {
-                    const int r = q / H, j = q - r * H;
-                    const float* g = gs + r * ldg + j;
-                    const float gi = fast_sigm(g[0]), gf = fast_sigm(g[H]), gg = fast_tanh(g[2 * H]),
-                                go = fast_sigm(g[3 * H]);
-                    float c = gf * cst[q] + gi * gg;
-                    float h = go * fast_tanh(c);
-                    if (j >= Hl) c = h = 0.f;            // (a padded unit: exactly zero whatever its weights)
-                    cst[q] = c;
-                    sm[r * ldx + G.Dp + j] = h;
-                }
-                SMX_LDS_BARRIER();
+                lstm_cells<RB>(G, sm, tid, [](int, int, const float&, float) {});
             }, G.Dp, G.H, gate, shift);
         } else {
             layers4<RG, NT>(G, sm, l3res ? 2 : 3, G.out_act, wv, lane, [](int) {}, 0, G.D, PreLayer{}, shift);
@@ -1703,35 +1703,35 @@ __global__ __launch_bounds__(RNTH) void ppo_eval_kernel(PEvalKernelArgs<SETS> G)
             constexpr int RC = RG < 4 ? RG : 1;
 #pragma unroll 1
             for (int rg0 = 0; rg0 < RG; rg0 += RC) {
-                const float* bp = h2s + (lane & 3) * ldh2 + 8 * kq + 32 * (wv < C3 ? wv : 0) + 4 * rg0 * ldh2;
-                f32x4 a3[2][RC];
+            const float* bp = h2s + (lane & 3) * ldh2 + 8 * kq + 32 * (wv < C3 ? wv : 0) + 4 * rg0 * ldh2;
+            f32x4 a3[2][RC];
 #pragma unroll
-                for (int g = 0; g < 2; ++g)
+            for (int g = 0; g < 2; ++g)
 #pragma unroll
-                    for (int r = 0; r < RC; ++r) a3[g][r] = (f32x4){0.f, 0.f, 0.f, 0.f};
-                float4 x0[RC], x1[RC];
+                for (int r = 0; r < RC; ++r) a3[g][r] = (f32x4){0.f, 0.f, 0.f, 0.f};
+            float4 x0[RC], x1[RC];
 #pragma unroll
-                for (int r = 0; r < RC; ++r) {
-                    x0[r] = *(const float4*)(bp + 4 * r * ldh2);
-                    x1[r] = *(const float4*)(bp + 4 * r * ldh2 + 4);
-                }
+            for (int r = 0; r < RC; ++r) {
+                x0[r] = *(const float4*)(bp + 4 * r * ldh2);
+                x1[r] = *(const float4*)(bp + 4 * r * ldh2 + 4);
+            }
 #define SMX_L3(X, W, E)                                                      \
-                _Pragma("unroll") for (int g = 0; g < 2; ++g)                    \
-                    _Pragma("unroll") for (int r = 0; r < RC; ++r) a3[g][r] = MFMA4(X[r].E, W[g].E, a3[g][r]);
-                SMX_L3(x0, w3a, x) SMX_L3(x0, w3a, y) SMX_L3(x0, w3a, z) SMX_L3(x0, w3a, w)
-                SMX_L3(x1, w3b, x) SMX_L3(x1, w3b, y) SMX_L3(x1, w3b, z) SMX_L3(x1, w3b, w)
+            _Pragma("unroll") for (int g = 0; g < 2; ++g)                    \
+                _Pragma("unroll") for (int r = 0; r < RC; ++r) a3[g][r] = MFMA4(X[r].E, W[g].E, a3[g][r]);
+            SMX_L3(x0, w3a, x) SMX_L3(x0, w3a, y) SMX_L3(x0, w3a, z) SMX_L3(x0, w3a, w)
+            SMX_L3(x1, w3b, x) SMX_L3(x1, w3b, y) SMX_L3(x1, w3b, z) SMX_L3(x1, w3b, w)
 #undef SMX_L3
 #pragma unroll
-                for (int g = 0; g < 2; ++g)
+            for (int g = 0; g < 2; ++g)
 #pragma unroll
-                    for (int r = 0; r < RC; ++r) {
-                        const float z = meet_rows(a3[g][r]);
-                        red3[(wv * RB + 4 * (rg0 + r) + kq) * 32 + 16 * g + fm] = z;
-                    }
+                for (int r = 0; r < RC; ++r) {
+                    const float z = meet_rows(a3[g][r]);
+                    red3[(wv * RB + 4 * (rg0 + r) + kq) * 32 + 16 * g + fm] = z;
+                }
             }
             SMX_LDS_BARRIER();
         }
-        // ---- the head (ppo_rollout's expressions): one (row, action) pair per lane -------------------------------------
+        // ---- the head: one (row, action) pair per lane -----------------------------------------------------------------
         if (hr < nrows) {
             float mu;
             if (l3res) {
@@ -1745,9 +1745,7 @@ __global__ __launch_bounds__(RNTH) void ppo_eval_kernel(PEvalKernelArgs<SETS> G)
             } else {
                 mu = outs[hr * RLDO + hj];
             }
-            float act = noisy ? ev * sd0 + mu : mu;
-            if (act == act) act = fminf(fmaxf(act, -1.0f), 1.0f);
-            s_act[hr * RMAX_A + hj] = act;
+            s_act[hr * RMAX_A + hj] = gauss_act(mu, sd0, ev, noisy);
         }
         SMX_LDS_BARRIER();
         E.step(s_act, false, [](long) { return EvalNoRow{}; }, [](long, EvalNoRow, int, float, float) {},
@@ -2139,8 +2137,8 @@ __global__ __launch_bounds__(256) void ppo_pixel_window_step_kernel(PWArgs G, PA
             const float m = mu[a * ld_mu + tid];
             float sd = expf(G.log_var[tid]);
             if (G.noise_scale) sd = sd * G.noise_scale[a];
-            float act = noise_on(G.eps, G.nstream) ? noise_pick(G.eps, a * A + tid, G.nstream, a, 0, tid) * sd + m : m;
-            if (act == act) act = fminf(fmaxf(act, -1.0f), 1.0f);
+            const float act =
+                clip1(noise_on(G.eps, G.nstream) ? noise_pick(G.eps, a * A + tid, G.nstream, a, 0, tid) * sd + m : m);
             s_act[tid] = act;
             float* ca = W.cact + (size_t)a * N * A + tid;
             float* cp = W.cpd + (size_t)a * N * 2 * A + tid;
@@ -2374,6 +2372,17 @@ int launch(const Args& G, int rb, int lds, smx_stream_t stream, int sets = 1) {
     if (rb == 4) return launch<K4>(G, rb, lds, stream, sets);
     if (rb == 8) return launch<K8>(G, rb, lds, stream, sets);
     return launch<K16>(G, rb, lds, stream, sets);
+}
+
+// the task of a call as a compile-time constant: f(std::integral_constant<int, SMX_TASK_...>) (the callers have checked
+// the id, synth_task_ok).  A later task is one case here, and its EnvLanes.
+template <typename F>
+int with_task(int task, F f) {
+    switch (task) {
+    case SMX_TASK_REACH: return f(std::integral_constant<int, SMX_TASK_REACH>{});
+    case SMX_TASK_ARM: return f(std::integral_constant<int, SMX_TASK_ARM>{});
+    default: return f(std::integral_constant<int, SMX_TASK_DRIFT>{});
+    }
 }
 
 // a task kernel's arguments from its drift twin's and the reset stream (null: none)
@@ -2689,13 +2698,14 @@ static int ppo_window_rollout(const smx_synth_ppo_window_rollout* args, const sm
         if (clocked)
             return launch<ppo_window_clk_kernel<1>, ppo_window_clk_kernel<2>, ppo_window_clk_kernel<4>>(
                 with_clocks(G, C), rb, lds, stream);
-        if (task == SMX_TASK_REACH)
-            return launch<ppo_window_task_kernel<1, SMX_TASK_REACH>, ppo_window_task_kernel<2, SMX_TASK_REACH>,
-                          ppo_window_task_kernel<4, SMX_TASK_REACH>>(with_resets(G, resets), rb, lds, stream);
-        if (task == SMX_TASK_ARM)
-            return launch<ppo_window_task_kernel<1, SMX_TASK_ARM>, ppo_window_task_kernel<2, SMX_TASK_ARM>,
-                          ppo_window_task_kernel<4, SMX_TASK_ARM>>(with_resets(G, resets), rb, lds, stream);
-        return launch<ppo_window_kernel<1>, ppo_window_kernel<2>, ppo_window_kernel<4>>(G, rb, lds, stream);
+        return with_task(task, [&](auto task_c) {
+            constexpr int TASK = decltype(task_c)::value;
+            if constexpr (TASK == SMX_TASK_DRIFT)
+                return launch<ppo_window_kernel<1>, ppo_window_kernel<2>, ppo_window_kernel<4>>(G, rb, lds, stream);
+            else
+                return launch<ppo_window_task_kernel<1, TASK>, ppo_window_task_kernel<2, TASK>,
+                              ppo_window_task_kernel<4, TASK>>(with_resets(G, resets), rb, lds, stream);
+        });
     }
     LArgsW G;
     memset(&G, 0, sizeof(G));
@@ -2706,13 +2716,14 @@ static int ppo_window_rollout(const smx_synth_ppo_window_rollout* args, const sm
     if (clocked)
         return launch<lstm_window_clk_kernel<1>, lstm_window_clk_kernel<2>, lstm_window_clk_kernel<4>>(
             with_clocks(G, C), rb, lds, stream);
-    if (task == SMX_TASK_REACH)
-        return launch<lstm_window_task_kernel<1, SMX_TASK_REACH>, lstm_window_task_kernel<2, SMX_TASK_REACH>,
-                      lstm_window_task_kernel<4, SMX_TASK_REACH>>(with_resets(G, resets), rb, lds, stream);
-    if (task == SMX_TASK_ARM)
-        return launch<lstm_window_task_kernel<1, SMX_TASK_ARM>, lstm_window_task_kernel<2, SMX_TASK_ARM>,
-                      lstm_window_task_kernel<4, SMX_TASK_ARM>>(with_resets(G, resets), rb, lds, stream);
-    return launch<lstm_window_kernel<1>, lstm_window_kernel<2>, lstm_window_kernel<4>>(G, rb, lds, stream);
+    return with_task(task, [&](auto task_c) {
+        constexpr int TASK = decltype(task_c)::value;
+        if constexpr (TASK == SMX_TASK_DRIFT)
+            return launch<lstm_window_kernel<1>, lstm_window_kernel<2>, lstm_window_kernel<4>>(G, rb, lds, stream);
+        else
+            return launch<lstm_window_task_kernel<1, TASK>, lstm_window_task_kernel<2, TASK>,
+                          lstm_window_task_kernel<4, TASK>>(with_resets(G, resets), rb, lds, stream);
+    });
 }
 
 extern "C" int smx_synth_ppo_window_rollout_f32(const smx_synth_ppo_window_rollout* args, smx_stream_t stream) {
@@ -2856,16 +2867,15 @@ static int ddpg_rollout_launch(const smx_ddpg_rollout_t* a, const smx_ddpg_actor
     if (clocked)
         return launch<ddpg_rollout_kernel<1, 3, POP, LN, true>, ddpg_rollout_kernel<2, 3, POP, LN, true>,
                       ddpg_rollout_kernel<4, 2, POP, LN, true>>(with_clocks(G, C), rb, lds, stream);
-    if (task == SMX_TASK_REACH)
-        return launch<ddpg_rollout_kernel<1, 3, POP, LN, false, SMX_TASK_REACH>,
-                      ddpg_rollout_kernel<2, 3, POP, LN, false, SMX_TASK_REACH>,
-                      ddpg_rollout_kernel<4, 2, POP, LN, false, SMX_TASK_REACH>>(with_resets(G, resets), rb, lds, stream);
-    if (task == SMX_TASK_ARM)
-        return launch<ddpg_rollout_kernel<1, 3, POP, LN, false, SMX_TASK_ARM>,
-                      ddpg_rollout_kernel<2, 3, POP, LN, false, SMX_TASK_ARM>,
-                      ddpg_rollout_kernel<4, 2, POP, LN, false, SMX_TASK_ARM>>(with_resets(G, resets), rb, lds, stream);
-    return launch<ddpg_rollout_kernel<1, 3, POP, LN>, ddpg_rollout_kernel<2, 3, POP, LN>,
-                  ddpg_rollout_kernel<4, 2, POP, LN>>(G, rb, lds, stream);
+    return with_task(task, [&](auto task_c) {
+        constexpr int TASK = decltype(task_c)::value;
+        if constexpr (TASK == SMX_TASK_DRIFT)
+            return launch<ddpg_rollout_kernel<1, 3, POP, LN>, ddpg_rollout_kernel<2, 3, POP, LN>,
+                          ddpg_rollout_kernel<4, 2, POP, LN>>(G, rb, lds, stream);
+        else
+            return launch<ddpg_rollout_kernel<1, 3, POP, LN, false, TASK>, ddpg_rollout_kernel<2, 3, POP, LN, false, TASK>,
+                          ddpg_rollout_kernel<4, 2, POP, LN, false, TASK>>(with_resets(G, resets), rb, lds, stream);
+    });
 }
 
 // the DDPG entry points: the actor variant picks the instantiation
@@ -3042,81 +3052,6 @@ static int eval_tail(int32_t n, int32_t episodes, int32_t episode_len, int32_t t
     return SMX_OK;
 }
 
-extern "C" int smx_synth_ppo_eval_f32(const struct smx_synth_ppo_eval* a, smx_stream_t stream) {
-    SMX_REQUIRE(a && a->net && a->packed && a->log_var && a->init_state && a->returns, SMX_E_NULL);
-    const bool lstm = a->lstm != nullptr;
-    SMX_REQUIRE(!lstm || a->lstm_packed, SMX_E_NULL);
-    SMX_REQUIRE((a->zsum == nullptr) == (a->zsumsq == nullptr) && (a->zsum == nullptr) == (a->zcount == nullptr), SMX_E_NULL);
-    const smx_mlp3_t& n = *a->net;
-    const int D = lstm ? a->lstm->D : n.D;
-    SMX_REQUIRE(!lstm || lstm_shape_ok(n, *a->lstm, a->hidden), SMX_E_SHAPE);
-    SMX_REQUIRE(smx_synth_eval_supported(0, a->task, D, lstm ? a->lstm->H : 0, n.H1, n.H2, n.OUT), SMX_E_UNSUPPORTED);
-    SMX_REQUIRE(block_ok(a->actors_per_workgroup) && noise_shape_ok(a->noise, a->n), SMX_E_SHAPE);
-    PEvalArgs G;
-    memset(&G, 0, sizeof(G));
-    const int rc = eval_tail(a->n, a->episodes, a->episode_len, a->task, a->resets, a->returns, G.ev);
-    if (rc != SMX_OK) return rc;
-    SMX_REQUIRE(aligned_ok(a->packed, n.b1, lstm ? a->lstm_packed : nullptr), SMX_E_ALIGN);
-    net_fields(n, a->packed, G);
-    G.D = D; G.A = n.OUT; G.out_act = a->out_act; G.log_var = a->log_var;
-    G.zsum = a->zsum; G.zsumsq = a->zsumsq; G.zcount = a->zcount; G.zeps = a->zeps;
-    G.init_state = a->init_state;
-    G.n = a->n * a->episodes;                        // the rows
-    G.steps = G.episode_len = a->episode_len;
-    if (a->noise.enabled) G.nstream = a->noise;
-    const int rb = pick_block(a->actors_per_workgroup, G.n);
-    const bool reach = a->task == SMX_TASK_REACH, arm = a->task == SMX_TASK_ARM;
-    if (!lstm) {
-        const int lds = carve(G, rb, /*mma16=*/false, /*split_out=*/true, /*ztables=*/true, G.D);
-        if (arm)
-            return launch<ppo_eval_kernel<1, 3, false, true, SMX_TASK_ARM>, ppo_eval_kernel<2, 3, false, true, SMX_TASK_ARM>,
-                          ppo_eval_kernel<4, 2, false, false, SMX_TASK_ARM>>(G, rb, lds, stream);
-        if (reach)
-            return launch<ppo_eval_kernel<1, 3, false, true, SMX_TASK_REACH>, ppo_eval_kernel<2, 3, false, true, SMX_TASK_REACH>,
-                          ppo_eval_kernel<4, 2, false, false, SMX_TASK_REACH>>(G, rb, lds, stream);
-        return launch<ppo_eval_kernel<1, 3, false, true, SMX_TASK_DRIFT>, ppo_eval_kernel<2, 3, false, true, SMX_TASK_DRIFT>,
-                      ppo_eval_kernel<4, 2, false, false, SMX_TASK_DRIFT>>(G, rb, lds, stream);
-    }
-    G.H = a->lstm->H; G.Hl = a->hidden;
-    G.Pg = a->lstm_packed; G.bg = a->lstm_packed + pack_words(4 * G.H, lstm_dp(D) + G.H) * 4;
-    const int lds = carve_lstm(G, rb);
-    if (arm)
-        return launch<ppo_eval_kernel<1, 3, true, true, SMX_TASK_ARM>, ppo_eval_kernel<2, 3, true, true, SMX_TASK_ARM>,
-                      ppo_eval_kernel<4, 2, true, false, SMX_TASK_ARM>>(G, rb, lds, stream);
-    if (reach)
-        return launch<ppo_eval_kernel<1, 3, true, true, SMX_TASK_REACH>, ppo_eval_kernel<2, 3, true, true, SMX_TASK_REACH>,
-                      ppo_eval_kernel<4, 2, true, false, SMX_TASK_REACH>>(G, rb, lds, stream);
-    return launch<ppo_eval_kernel<1, 3, true, true, SMX_TASK_DRIFT>, ppo_eval_kernel<2, 3, true, true, SMX_TASK_DRIFT>,
-                  ppo_eval_kernel<4, 2, true, false, SMX_TASK_DRIFT>>(G, rb, lds, stream);
-}
-
-extern "C" int smx_synth_ddpg_eval_f32(const struct smx_synth_ddpg_eval* a, smx_stream_t stream) {
-    SMX_REQUIRE(a && a->net && a->packed && a->init_state && a->returns, SMX_E_NULL);
-    const smx_mlp3_t& n = *a->net;
-    SMX_REQUIRE(smx_synth_eval_supported(1, a->task, n.D, 0, n.H1, n.H2, n.OUT), SMX_E_UNSUPPORTED);
-    SMX_REQUIRE(block_ok(a->actors_per_workgroup), SMX_E_SHAPE);
-    DEvalArgs G;
-    memset(&G, 0, sizeof(G));
-    const int rc = eval_tail(a->n, a->episodes, a->episode_len, a->task, a->resets, a->returns, G.ev);
-    if (rc != SMX_OK) return rc;
-    SMX_REQUIRE(aligned_ok(a->packed, n.b1, nullptr), SMX_E_ALIGN);
-    net_fields(n, a->packed, G);
-    G.D = n.D; G.A = n.OUT;
-    G.init_state = a->init_state;
-    G.n = a->n * a->episodes;                        // the rows
-    G.steps = G.episode_len = a->episode_len;
-    const int rb = pick_block(a->actors_per_workgroup, G.n);
-    const int lds = carve(G, rb, /*mma16=*/false, /*split_out=*/false, /*ztables=*/false, G.D);
-    if (a->task == SMX_TASK_ARM)
-        return launch<ddpg_eval_kernel<1, 3, SMX_TASK_ARM>, ddpg_eval_kernel<2, 3, SMX_TASK_ARM>,
-                      ddpg_eval_kernel<4, 2, SMX_TASK_ARM>>(G, rb, lds, stream);
-    if (a->task == SMX_TASK_REACH)
-        return launch<ddpg_eval_kernel<1, 3, SMX_TASK_REACH>, ddpg_eval_kernel<2, 3, SMX_TASK_REACH>,
-                      ddpg_eval_kernel<4, 2, SMX_TASK_REACH>>(G, rb, lds, stream);
-    return launch<ddpg_eval_kernel<1, 3, SMX_TASK_DRIFT>, ddpg_eval_kernel<2, 3, SMX_TASK_DRIFT>,
-                  ddpg_eval_kernel<4, 2, SMX_TASK_DRIFT>>(G, rb, lds, stream);
-}
-
 // ---- evaluation of several parameter sets in one launch ---------------------------------------------------------------------
 // A snapshot is one policy's parameters as one blob (smx_eval_snapshot_floats): [smx_epoch_pack_f32's copy of the actor |
 // b1 | b2 | b3], which is one agent's copy of a plain-actor population (pop_copy_floats); a PPO policy's goes on with
@@ -3214,15 +3149,114 @@ void snap_net_fields(const smx_mlp3_t& n, const float* blob, const SnapLayout& S
     net_fields(m, blob, G);
 }
 
-template <bool LSTM, int TASK, typename Args>
+// the evaluation kernels of a policy family and task at the three block sizes; SETS: the argument block ends with the stride
+template <bool LSTM, int TASK, bool SETS, typename Args>
 int ppo_eval_sets_launch(const Args& G, int rb, int lds, smx_stream_t stream, int sets) {
-    return launch<ppo_eval_kernel<1, 3, LSTM, true, TASK, true>, ppo_eval_kernel<2, 3, LSTM, true, TASK, true>,
-                  ppo_eval_kernel<4, 2, LSTM, false, TASK, true>>(G, rb, lds, stream, sets);
+    return launch<ppo_eval_kernel<1, 3, LSTM, true, TASK, SETS>, ppo_eval_kernel<2, 3, LSTM, true, TASK, SETS>,
+                  ppo_eval_kernel<4, 2, LSTM, false, TASK, SETS>>(G, rb, lds, stream, sets);
 }
-template <int TASK, typename Args>
+template <int TASK, bool SETS, typename Args>
 int ddpg_eval_sets_launch(const Args& G, int rb, int lds, smx_stream_t stream, int sets) {
-    return launch<ddpg_eval_kernel<1, 3, TASK, true>, ddpg_eval_kernel<2, 3, TASK, true>,
-                  ddpg_eval_kernel<4, 2, TASK, true>>(G, rb, lds, stream, sets);
+    return launch<ddpg_eval_kernel<1, 3, TASK, SETS>, ddpg_eval_kernel<2, 3, TASK, SETS>,
+                  ddpg_eval_kernel<4, 2, TASK, SETS>>(G, rb, lds, stream, sets);
+}
+
+// Both PPO evaluation entry points.  s null: the one policy of the block's own pointers (smx_synth_ppo_eval_f32); else the
+// parameter sets, every parameter pointer into set 0's snapshot (smx_synth_ppo_eval_sets_f32, which has checked s itself).
+// The checks run in the order either entry point has always had: the pointers, the shapes, the rows and the stream
+// (eval_tail), then the sets (sets_ok) or the single policy's alignment.
+int ppo_eval(const smx_synth_ppo_eval* a, const smx_eval_sets* s, smx_stream_t stream) {
+    SMX_REQUIRE(a && a->net && a->init_state && a->returns && (s ? s->blobs != nullptr : a->packed && a->log_var), SMX_E_NULL);
+    const bool lstm = a->lstm != nullptr;
+    SMX_REQUIRE(s || !lstm || a->lstm_packed, SMX_E_NULL);
+    SMX_REQUIRE(s || ((a->zsum == nullptr) == (a->zsumsq == nullptr) && (a->zsum == nullptr) == (a->zcount == nullptr)),
+                SMX_E_NULL);
+    const smx_mlp3_t& n = *a->net;
+    const int D = lstm ? a->lstm->D : n.D, H = lstm ? a->lstm->H : 0;
+    SMX_REQUIRE(!lstm || lstm_shape_ok(n, *a->lstm, a->hidden), SMX_E_SHAPE);
+    SMX_REQUIRE(smx_synth_eval_supported(0, a->task, D, H, n.H1, n.H2, n.OUT), SMX_E_UNSUPPORTED);
+    SMX_REQUIRE(block_ok(a->actors_per_workgroup) && noise_shape_ok(a->noise, a->n), SMX_E_SHAPE);
+    PEvalArgs G;
+    memset(&G, 0, sizeof(G));
+    int rc = eval_tail(a->n, a->episodes, a->episode_len, a->task, a->resets, a->returns, G.ev);
+    if (rc != SMX_OK) return rc;
+    G.n = a->n * a->episodes;                        // the rows (of one set)
+    const float* gate = nullptr;                     // the LSTM's gate pass
+    if (s) {
+        SMX_REQUIRE(s->zfilter == 0 || s->zfilter == 1, SMX_E_SHAPE);
+        const SnapLayout S = snap_layout(false, D, H, n.H1, n.H2, n.OUT, s->zfilter != 0);
+        rc = sets_ok(s, S.total, G.n);
+        if (rc != SMX_OK) return rc;
+        snap_net_fields(n, s->blobs, S, G);
+        G.log_var = s->blobs + S.log_var;
+        if (s->zfilter) {
+            G.zsum = s->blobs + S.zsum; G.zsumsq = s->blobs + S.zsumsq; G.zcount = s->blobs + S.zcount;
+        }
+        gate = s->blobs + S.lstm;
+    } else {
+        SMX_REQUIRE(aligned_ok(a->packed, n.b1, lstm ? a->lstm_packed : nullptr), SMX_E_ALIGN);
+        net_fields(n, a->packed, G);
+        G.log_var = a->log_var;
+        G.zsum = a->zsum; G.zsumsq = a->zsumsq; G.zcount = a->zcount;
+        gate = a->lstm_packed;
+    }
+    G.D = D; G.A = n.OUT; G.out_act = a->out_act; G.zeps = a->zeps;
+    G.init_state = a->init_state;
+    G.steps = G.episode_len = a->episode_len;
+    if (a->noise.enabled) G.nstream = a->noise;
+    const int sets = s ? s->sets : 1;
+    const int rb = pick_block(a->actors_per_workgroup, sets * G.n);
+    int lds;
+    if (lstm) {
+        G.H = H; G.Hl = a->hidden;
+        G.Pg = gate; G.bg = G.Pg + pack_words(4 * G.H, lstm_dp(D) + G.H) * 4;
+        lds = carve_lstm(G, rb);
+    } else {
+        lds = carve(G, rb, /*mma16=*/false, /*split_out=*/true, /*ztables=*/true, G.D);
+    }
+    auto go = [&](auto lstm_c, auto task_c) {
+        constexpr bool LSTM = decltype(lstm_c)::value;
+        constexpr int TASK = decltype(task_c)::value;
+        return s ? ppo_eval_sets_launch<LSTM, TASK, true>(with_sets(G, s->stride), rb, lds, stream, sets)
+                 : ppo_eval_sets_launch<LSTM, TASK, false>(G, rb, lds, stream, sets);
+    };
+    return with_task(a->task, [&](auto task_c) {
+        return lstm ? go(std::true_type{}, task_c) : go(std::false_type{}, task_c);
+    });
+}
+
+// both DDPG evaluation entry points, as ppo_eval
+int ddpg_eval(const smx_synth_ddpg_eval* a, const smx_eval_sets* s, smx_stream_t stream) {
+    SMX_REQUIRE(a && a->net && a->init_state && a->returns && (s ? s->blobs != nullptr : a->packed != nullptr), SMX_E_NULL);
+    const smx_mlp3_t& n = *a->net;
+    SMX_REQUIRE(smx_synth_eval_supported(1, a->task, n.D, 0, n.H1, n.H2, n.OUT), SMX_E_UNSUPPORTED);
+    SMX_REQUIRE(block_ok(a->actors_per_workgroup), SMX_E_SHAPE);
+    DEvalArgs G;
+    memset(&G, 0, sizeof(G));
+    int rc = eval_tail(a->n, a->episodes, a->episode_len, a->task, a->resets, a->returns, G.ev);
+    if (rc != SMX_OK) return rc;
+    G.n = a->n * a->episodes;                        // the rows (of one set)
+    if (s) {
+        SMX_REQUIRE(s->zfilter == 0, SMX_E_SHAPE);   // (a DDPG actor has no z-filter)
+        const SnapLayout S = snap_layout(true, n.D, 0, n.H1, n.H2, n.OUT, false);
+        rc = sets_ok(s, S.total, G.n);
+        if (rc != SMX_OK) return rc;
+        snap_net_fields(n, s->blobs, S, G);
+    } else {
+        SMX_REQUIRE(aligned_ok(a->packed, n.b1, nullptr), SMX_E_ALIGN);
+        net_fields(n, a->packed, G);
+    }
+    G.D = n.D; G.A = n.OUT;
+    G.init_state = a->init_state;
+    G.steps = G.episode_len = a->episode_len;
+    const int sets = s ? s->sets : 1;
+    const int rb = pick_block(a->actors_per_workgroup, sets * G.n);
+    const int lds = carve(G, rb, /*mma16=*/false, /*split_out=*/false, /*ztables=*/false, G.D);
+    return with_task(a->task, [&](auto task_c) {
+        constexpr int TASK = decltype(task_c)::value;
+        return s ? ddpg_eval_sets_launch<TASK, true>(with_sets(G, s->stride), rb, lds, stream, sets)
+                 : ddpg_eval_sets_launch<TASK, false>(G, rb, lds, stream, sets);
+    });
 }
 
 }  // namespace
@@ -3270,74 +3304,22 @@ extern "C" int smx_eval_snapshot_store_f32(const struct smx_eval_snapshot_src* s
     return SMX_OK;
 }
 
+extern "C" int smx_synth_ppo_eval_f32(const struct smx_synth_ppo_eval* a, smx_stream_t stream) {
+    return ppo_eval(a, nullptr, stream);
+}
+
+extern "C" int smx_synth_ddpg_eval_f32(const struct smx_synth_ddpg_eval* a, smx_stream_t stream) {
+    return ddpg_eval(a, nullptr, stream);
+}
+
 extern "C" int smx_synth_ppo_eval_sets_f32(const struct smx_synth_ppo_eval* a, const struct smx_eval_sets* s,
                                            smx_stream_t stream) {
-    SMX_REQUIRE(a && a->net && a->init_state && a->returns && s && s->blobs, SMX_E_NULL);
-    const bool lstm = a->lstm != nullptr;
-    const smx_mlp3_t& n = *a->net;
-    const int D = lstm ? a->lstm->D : n.D, H = lstm ? a->lstm->H : 0;
-    SMX_REQUIRE(!lstm || lstm_shape_ok(n, *a->lstm, a->hidden), SMX_E_SHAPE);
-    SMX_REQUIRE(smx_synth_eval_supported(0, a->task, D, H, n.H1, n.H2, n.OUT), SMX_E_UNSUPPORTED);
-    SMX_REQUIRE(block_ok(a->actors_per_workgroup) && noise_shape_ok(a->noise, a->n), SMX_E_SHAPE);
-    PEvalArgs G;
-    memset(&G, 0, sizeof(G));
-    int rc = eval_tail(a->n, a->episodes, a->episode_len, a->task, a->resets, a->returns, G.ev);
-    if (rc != SMX_OK) return rc;
-    SMX_REQUIRE(s->zfilter == 0 || s->zfilter == 1, SMX_E_SHAPE);
-    const SnapLayout S = snap_layout(false, D, H, n.H1, n.H2, n.OUT, s->zfilter != 0);
-    G.n = a->n * a->episodes;                        // the rows of one set
-    rc = sets_ok(s, S.total, G.n);
-    if (rc != SMX_OK) return rc;
-    snap_net_fields(n, s->blobs, S, G);
-    G.D = D; G.A = n.OUT; G.out_act = a->out_act; G.log_var = s->blobs + S.log_var;
-    if (s->zfilter) {
-        G.zsum = s->blobs + S.zsum; G.zsumsq = s->blobs + S.zsumsq; G.zcount = s->blobs + S.zcount;
-    }
-    G.zeps = a->zeps;
-    G.init_state = a->init_state;
-    G.steps = G.episode_len = a->episode_len;
-    if (a->noise.enabled) G.nstream = a->noise;
-    const int rb = pick_block(a->actors_per_workgroup, s->sets * G.n);
-    const bool reach = a->task == SMX_TASK_REACH;
-    if (!lstm) {
-        const int lds = carve(G, rb, /*mma16=*/false, /*split_out=*/true, /*ztables=*/true, G.D);
-        const auto X = with_sets(G, s->stride);
-        if (a->task == SMX_TASK_ARM) return ppo_eval_sets_launch<false, SMX_TASK_ARM>(X, rb, lds, stream, s->sets);
-        return reach ? ppo_eval_sets_launch<false, SMX_TASK_REACH>(X, rb, lds, stream, s->sets)
-                     : ppo_eval_sets_launch<false, SMX_TASK_DRIFT>(X, rb, lds, stream, s->sets);
-    }
-    G.H = H; G.Hl = a->hidden;
-    G.Pg = s->blobs + S.lstm; G.bg = G.Pg + pack_words(4 * G.H, lstm_dp(D) + G.H) * 4;
-    const int lds = carve_lstm(G, rb);
-    const auto X = with_sets(G, s->stride);
-    if (a->task == SMX_TASK_ARM) return ppo_eval_sets_launch<true, SMX_TASK_ARM>(X, rb, lds, stream, s->sets);
-    return reach ? ppo_eval_sets_launch<true, SMX_TASK_REACH>(X, rb, lds, stream, s->sets)
-                 : ppo_eval_sets_launch<true, SMX_TASK_DRIFT>(X, rb, lds, stream, s->sets);
+    SMX_REQUIRE(s, SMX_E_NULL);
+    return ppo_eval(a, s, stream);
 }
 
 extern "C" int smx_synth_ddpg_eval_sets_f32(const struct smx_synth_ddpg_eval* a, const struct smx_eval_sets* s,
                                             smx_stream_t stream) {
-    SMX_REQUIRE(a && a->net && a->init_state && a->returns && s && s->blobs, SMX_E_NULL);
-    const smx_mlp3_t& n = *a->net;
-    SMX_REQUIRE(smx_synth_eval_supported(1, a->task, n.D, 0, n.H1, n.H2, n.OUT), SMX_E_UNSUPPORTED);
-    SMX_REQUIRE(block_ok(a->actors_per_workgroup), SMX_E_SHAPE);
-    DEvalArgs G;
-    memset(&G, 0, sizeof(G));
-    int rc = eval_tail(a->n, a->episodes, a->episode_len, a->task, a->resets, a->returns, G.ev);
-    if (rc != SMX_OK) return rc;
-    SMX_REQUIRE(s->zfilter == 0, SMX_E_SHAPE);       // (a DDPG actor has no z-filter)
-    const SnapLayout S = snap_layout(true, n.D, 0, n.H1, n.H2, n.OUT, false);
-    G.n = a->n * a->episodes;                        // the rows of one set
-    rc = sets_ok(s, S.total, G.n);
-    if (rc != SMX_OK) return rc;
-    snap_net_fields(n, s->blobs, S, G);
-    G.D = n.D; G.A = n.OUT;
-    G.init_state = a->init_state;
-    G.steps = G.episode_len = a->episode_len;
-    const int rb = pick_block(a->actors_per_workgroup, s->sets * G.n);
-    const int lds = carve(G, rb, /*mma16=*/false, /*split_out=*/false, /*ztables=*/false, G.D);
-    const auto X = with_sets(G, s->stride);
-    if (a->task == SMX_TASK_ARM) return ddpg_eval_sets_launch<SMX_TASK_ARM>(X, rb, lds, stream, s->sets);
-    return a->task == SMX_TASK_REACH ? ddpg_eval_sets_launch<SMX_TASK_REACH>(X, rb, lds, stream, s->sets)
-                                     : ddpg_eval_sets_launch<SMX_TASK_DRIFT>(X, rb, lds, stream, s->sets);
+    SMX_REQUIRE(s, SMX_E_NULL);
+    return ddpg_eval(a, s, stream);
 }

@@ -972,6 +972,32 @@ class HipKernels(object):
         assert returns.dtype == torch.float64 and returns.is_contiguous() and tuple(returns.shape) == (n, episodes)
         return L.ptr(returns)
 
+    def _eval_block(self, p, net, init_state, episodes, episode_len, task, resets, actors_per_workgroup):
+        """what both evaluation blocks (p: a fresh SynthPpoEval / SynthDdpgEval) hold whether the parameters come from
+        the caller's tensors or from snapshots: the actor's shapes, the rows, the task and the reset stream -> (p, n)"""
+        n = init_state.shape[0]
+        assert init_state.is_contiguous() and init_state.dtype == torch.float32
+        p.net, p.n = ctypes.pointer(net.desc), n
+        p.episodes, p.episode_len, p.task = int(episodes), int(episode_len), self._task_id(task)
+        p.actors_per_workgroup = int(actors_per_workgroup)
+        p.init_state = L.ptr(init_state)
+        if resets is not None:
+            p.resets = self._reset_args(resets)
+        return p, n
+
+    def _ppo_eval_block(self, model, init_state, episodes, episode_len, zfilter, task, resets, noise,
+                        actors_per_workgroup, out_act):
+        """_eval_block for PPOModel `model`, with the LSTM stem's shapes, the z-filter's eps and the noise stream"""
+        p, n = self._eval_block(L.SynthPpoEval(), model.actor, init_state, episodes, episode_len, task, resets,
+                                actors_per_workgroup)
+        p.out_act = int(out_act)
+        if zfilter is not None:
+            p.zeps = float(zfilter.eps)
+        if model.if_rnn:
+            p.lstm, p.hidden = ctypes.pointer(model.rnn.desc), model.rnn_hidden_logical
+        p.noise = self._noise_args(noise)
+        return p, n
+
     def synth_ppo_eval(self, model, packed, lstm_packed, init_state, episodes, episode_len, returns, zfilter=None,
                        task='drift', resets=None, noise=None, actors_per_workgroup=0, out_act=L.SMX_ACT_TANH):
         """`episodes` whole episodes of every actor under PPOModel `model`'s policy, ONE launch, nothing recorded
@@ -980,39 +1006,22 @@ class HipKernels(object):
         first_episode) of the reset stream the episodes begin from, or None: every episode begins at init_state[a];
         noise: (seed, actor_base, first_step) -- the policy samples (eval_stochastic) -- or None: it acts on its mean;
         out_act: the output layer's activation (PPOModel's is tanh)"""
-        n = init_state.shape[0]
-        assert init_state.is_contiguous() and init_state.dtype == torch.float32
-        p = L.SynthPpoEval()
-        a = model.actor
-        p.net, p.packed, p.out_act, p.n = ctypes.pointer(a.desc), L.ptr(packed), int(out_act), n
-        p.log_var = L.ptr(model.log_var)
+        p, n = self._ppo_eval_block(model, init_state, episodes, episode_len, zfilter, task, resets, noise,
+                                    actors_per_workgroup, out_act)
+        p.packed, p.log_var = L.ptr(packed), L.ptr(model.log_var)
         if zfilter is not None:
             p.zsum, p.zsumsq, p.zcount = L.ptr(zfilter.running_sum), L.ptr(zfilter.running_sumsq), L.ptr(zfilter.count)
-            p.zeps = float(zfilter.eps)
-        p.episodes, p.episode_len, p.task = int(episodes), int(episode_len), self._task_id(task)
-        p.actors_per_workgroup = int(actors_per_workgroup)
         if model.if_rnn:
-            p.lstm, p.lstm_packed, p.hidden = ctypes.pointer(model.rnn.desc), L.ptr(lstm_packed), \
-                model.rnn_hidden_logical
-        p.init_state = L.ptr(init_state)
-        if resets is not None:
-            p.resets = self._reset_args(resets)
-        p.noise = self._noise_args(noise)
+            p.lstm_packed = L.ptr(lstm_packed)
         p.returns = self._eval_returns(returns, n, int(episodes))
         L.call('smx_synth_ppo_eval_f32', ctypes.byref(p), self._st())
 
     def synth_ddpg_eval(self, net, packed, init_state, episodes, episode_len, returns, task='drift', resets=None,
                         actors_per_workgroup=0):
         """the same for a plain DDPG actor `net` in a deterministic agent mode (smx_synth_ddpg_eval_f32)"""
-        n = init_state.shape[0]
-        assert init_state.is_contiguous() and init_state.dtype == torch.float32
-        p = L.SynthDdpgEval()
-        p.net, p.packed, p.n = ctypes.pointer(net.desc), L.ptr(packed), n
-        p.episodes, p.episode_len, p.task = int(episodes), int(episode_len), self._task_id(task)
-        p.actors_per_workgroup = int(actors_per_workgroup)
-        p.init_state = L.ptr(init_state)
-        if resets is not None:
-            p.resets = self._reset_args(resets)
+        p, n = self._eval_block(L.SynthDdpgEval(), net, init_state, episodes, episode_len, task, resets,
+                                actors_per_workgroup)
+        p.packed = L.ptr(packed)
         p.returns = self._eval_returns(returns, n, int(episodes))
         L.call('smx_synth_ddpg_eval_f32', ctypes.byref(p), self._st())
 
@@ -1062,20 +1071,8 @@ class HipKernels(object):
         """synth_ppo_eval for the blobs.shape[0] snapshots in the rows of blobs [sets, stride] in ONE launch
         (smx_synth_ppo_eval_sets_f32): returns [sets, n, episodes] fp64.  model gives the shapes alone -- its parameters
         are not read; zfilter: the ZFilter whose eps applies (the snapshots hold the sums), or None"""
-        n = init_state.shape[0]
-        assert init_state.is_contiguous() and init_state.dtype == torch.float32
-        p = L.SynthPpoEval()
-        p.net, p.out_act, p.n = ctypes.pointer(model.actor.desc), int(out_act), n
-        if zfilter is not None:
-            p.zeps = float(zfilter.eps)
-        p.episodes, p.episode_len, p.task = int(episodes), int(episode_len), self._task_id(task)
-        p.actors_per_workgroup = int(actors_per_workgroup)
-        if model.if_rnn:
-            p.lstm, p.hidden = ctypes.pointer(model.rnn.desc), model.rnn_hidden_logical
-        p.init_state = L.ptr(init_state)
-        if resets is not None:
-            p.resets = self._reset_args(resets)
-        p.noise = self._noise_args(noise)
+        p, n = self._ppo_eval_block(model, init_state, episodes, episode_len, zfilter, task, resets, noise,
+                                    actors_per_workgroup, out_act)
         s = self._eval_sets(blobs, blobs.shape[0], zfilter is not None, returns, n, int(episodes))
         p.returns = L.ptr(returns)
         L.call('smx_synth_ppo_eval_sets_f32', ctypes.byref(p), ctypes.byref(s), self._st())
@@ -1083,15 +1080,8 @@ class HipKernels(object):
     def synth_ddpg_eval_sets(self, net, blobs, init_state, episodes, episode_len, returns, task='drift', resets=None,
                              actors_per_workgroup=0):
         """the same for plain DDPG actors of net's shapes (smx_synth_ddpg_eval_sets_f32)"""
-        n = init_state.shape[0]
-        assert init_state.is_contiguous() and init_state.dtype == torch.float32
-        p = L.SynthDdpgEval()
-        p.net, p.n = ctypes.pointer(net.desc), n
-        p.episodes, p.episode_len, p.task = int(episodes), int(episode_len), self._task_id(task)
-        p.actors_per_workgroup = int(actors_per_workgroup)
-        p.init_state = L.ptr(init_state)
-        if resets is not None:
-            p.resets = self._reset_args(resets)
+        p, n = self._eval_block(L.SynthDdpgEval(), net, init_state, episodes, episode_len, task, resets,
+                                actors_per_workgroup)
         s = self._eval_sets(blobs, blobs.shape[0], False, returns, n, int(episodes))
         p.returns = L.ptr(returns)
         L.call('smx_synth_ddpg_eval_sets_f32', ctypes.byref(p), ctypes.byref(s), self._st())

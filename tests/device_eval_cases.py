@@ -48,6 +48,11 @@ RAGGED = (28, 20)
 POLICIES += [Policy('mlp-reach-J2-ragged', 'mlp', 'reach', 6, 2, RAGGED),
              Policy('lstm-reach-J2-ragged', 'lstm', 'reach', 6, 2, RAGGED),
              Policy('ddpg-reach-J2-ragged', 'ddpg', 'reach', 6, 2, RAGGED)]
+# the smallest H2 past the split output layer (pack_chunks(260) = 10 chunks > 8 waves): the recording and the evaluation
+# kernels both take the generic output-layer loop (rollout_envelope_cases.py's wide-24-260 pair)
+WIDE = (24, 260)
+POLICIES += [Policy('mlp-reach-J2-wide', 'mlp', 'reach', 6, 2, WIDE),
+             Policy('lstm-reach-J2-wide', 'lstm', 'reach', 6, 2, WIDE)]
 BY_ID = {p.id: p for p in POLICIES}
 
 

@@ -2,7 +2,8 @@
 (SyntheticVecEnv.evaluate, DeviceEvaluator; smx_synth_ppo_eval_f32 / smx_synth_ddpg_eval_f32: the eighteen ppo_eval_kernel /
 ddpg_eval_kernel instantiations).  Shapes (device_eval_cases): (n, E, L) = (5, 3, 7), (1, 1, 1), (9, 2, 4) -- 15 rows (a tail
 at every block size), 1 row, 18 rows (two blocks at 16 rows per workgroup) -- each at 4, 8 and 16 rows per workgroup; reach
-with 1, 2 and 21 masses, drift with (D, A) = (17, 6); hidden (32, 32) and the ragged (28, 20); an LSTM stem of 10 units
+with 1, 2 and 21 masses, drift with (D, A) = (17, 6); hidden (32, 32), the ragged (28, 20) and the wide (24, 260: the generic
+output-layer loop, H2 > 256); an LSTM stem of 10 units
 (padded to 12); z-filters with non-trivial running sums; first_episode 0 and 2^32 - 2, actor_base 0 and 2^32 - n.
 
 Every check is an equality of bits (fp64 returns compared as uint64); no tolerance anywhere:
@@ -16,7 +17,7 @@ Every check is an equality of bits (fp64 returns compared as uint64); no toleran
   6. DeviceEvaluator.run();
   7. the refusals, raised before any launch.
 
-59 tests, 3.5 s together on an MI355X.
+63 tests.
 """
 import numpy as np
 import pytest
