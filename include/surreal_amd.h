@@ -122,6 +122,18 @@ int smx_mlp3_forward_fused_f32(const float* packed, int32_t D, int32_t H1, int32
                                int64_t G, int32_t T0, int32_t T1, const float* zmean,
                                const float* zstd, float* out, int32_t out_act,
                                smx_stream_t stream);
+/* The same pass with layer 1 of the 16-row kernel on 3-way split-bf16 MFMA (split_bf16 != 0): W1 and the filtered x
+ * are each split into three bf16 planes that sum to the fp32 value exactly, and six of the nine plane products are
+ * accumulated in fp32 (everything down to 2^-23 of a product; DESIGN.md 3.1 states the measured error against
+ * float64).  smx_mlp3_pack*_f32 write the planes of W1 behind the fp32 image when `packed` has
+ * smx_mlp3_packed_bytes bytes; packed_bytes is that size.  Layers 2 and 3 are fp32 MFMA as before.  The fp32 kernel
+ * of smx_mlp3_forward_fused_f32 runs instead when split_bf16 is 0, the planes are missing, exact-z-filter mode is on
+ * or the shape is off the 16-row kernel.  A non-finite x or weight makes the affected outputs non-finite on both
+ * paths; an Inf may come out as NaN here (Inf - Inf in the residual planes). */
+int smx_mlp3_forward_fused_split_f32(const float* packed, size_t packed_bytes, int32_t split_bf16, int32_t D,
+                                     int32_t H1, int32_t H2, int32_t OUT, const float* x_main,
+                                     const float* x_tail, int64_t G, int32_t T0, int32_t T1, const float* zmean,
+                                     const float* zstd, float* out, int32_t out_act, smx_stream_t stream);
 
 /* --- one dense layer on FP32 MFMA (small-batch epochs) ------------------------
  * C[M,N] = act(A[M,K] . B[N,K]^T + bias[N]); every epoch-loop GEMM of

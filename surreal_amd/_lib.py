@@ -421,6 +421,8 @@ _SIGS = {
     'smx_mlp3_fused_exact_zfilter': (c_int32, [c_int32]),
     'smx_mlp3_forward_fused_f32': (c_int32, [_P, c_int32, c_int32, c_int32, c_int32, _P, _P,
                                              c_int64, c_int32, c_int32, _P, _P, _P, c_int32, _P]),
+    'smx_mlp3_forward_fused_split_f32': (c_int32, [_P, c_size_t, c_int32, c_int32, c_int32, c_int32, c_int32, _P, _P,
+                                                   c_int64, c_int32, c_int32, _P, _P, _P, c_int32, _P]),
     'smx_linear_f32': (c_int32, [_P, c_int32, c_int32, _P, c_int32, c_int32, _P, _P, c_int32,
                                  c_int32, c_int32, c_int32, c_int32, _P, _P, _P]),
     'smx_linear_wgrad_f32': (c_int32, [_P, c_int32, _P, c_int32, _P, c_int32, _P, c_int32, c_int32,

@@ -16,7 +16,13 @@
 //   * weights stream HBM/L2 -> registers -> LDS in K-chunks of 32 (double buffered, one barrier
 //     per chunk); x is read once from HBM with full 128-byte lines, z-filtered in registers on
 //     the way into LDS.  Rows of 36 floats (144 B) make every ds_read_b128 conflict-free.
-//   * FP32 MFMA (exact fp32, no bf16/xf32): 1e-5 parity with the CPU reference is the contract.
+//   * 1e-5 parity with the CPU reference is the contract.  This kernel, the 16-row kernel's layers 2 and 3 and all
+//     of its stem (h1 / h2 keeping) launches are FP32 MFMA: exact fp32 products, fp32 accumulation.  Layer 1 of the
+//     16-row critic pass may run on bf16 MFMA instead (smx_mlp3_forward_fused_split_f32): NOT by rounding operands to
+//     bf16, but with W1 and x each written as three bf16 planes that sum to the fp32 value exactly, and the six plane
+//     products down to 2^-23 of a product accumulated in fp32.  What is exact there: the operands.  What is not: the
+//     three dropped products (below 2^-24 of a product) and the order of the fp32 accumulation -- measured against
+//     float64 it errs no more than the FP32 MFMA path does (profiles/critic_split_accuracy.txt).
 #include "smx_common.h"
 #include "smx_mlp3_fused.inc.h"
 #include <string.h>
@@ -482,7 +488,7 @@ struct ZStatsRider {
 };
 
 __global__ __launch_bounds__(256) void mlp3_pack_kernel(smx_mlp3_t net, float* __restrict__ packed,
-                                                        int NT1, int NT2, int KC1, ZStatsRider Z) {
+                                                        int NT1, int NT2, int KC1, ZStatsRider Z, int planes) {
     if (Z.rs) {
         for (int k = blockIdx.x * 256 + threadIdx.x; k < Z.D; k += gridDim.x * 256) {
             const float c = Z.cnt[0];
@@ -530,6 +536,24 @@ __global__ __launch_bounds__(256) void mlp3_pack_kernel(smx_mlp3_t net, float* _
         }
         packed[i] = v;
     }
+    if (planes) {       // W1 again as three bf16 planes: one thread per (chunk, 16-feature tile, lane), 3 x 16 bytes
+        uint4* dst = reinterpret_cast<uint4*>(packed + L.pl);
+        const size_t items = (size_t)KC1 * NT1 * 2 * 64;
+        for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < items; i += (size_t)gridDim.x * 256) {
+            const int lane = (int)(i & 63);
+            const size_t ct = i >> 6;                       // chunk * (2 NT1) + tile
+            const int t = (int)(ct % (size_t)(NT1 * 2)), c = (int)(ct / (size_t)(NT1 * 2));
+            const int f = 16 * t + (lane & 15), k0 = 32 * c + 8 * (lane >> 4);
+            union { __bf16 h[8]; uint4 w; } P[3];
+#pragma unroll
+            for (int j = 0; j < 8; ++j) {
+                const float v = (f < net.H1 && k0 + j < net.D) ? net.W1[(size_t)f * net.D + k0 + j] : 0.f;
+                smxf::split3_bf16(v, P[0].h[j], P[1].h[j], P[2].h[j]);
+            }
+#pragma unroll
+            for (int p = 0; p < 3; ++p) dst[(ct * 3 + p) * 64 + lane] = P[p].w;
+        }
+    }
 }
 
 template <int NT1, int NT2>
@@ -575,7 +599,8 @@ extern "C" void smx_mlp3_fused_debug_tbuf(void* p) { g_fused_tbuf = (long long*)
 extern "C" size_t smx_mlp3_packed_bytes(int32_t D, int32_t H1, int32_t H2, int32_t OUT) {
     int nt1, nt2;
     if (D <= 0 || OUT <= 0 || OUT > 32 || !pick_variant(H1, H2, &nt1, &nt2)) return 0;
-    return pack_layout(nt1, nt2, (D + 31) / 32).total * sizeof(float);
+    const PackLayout L = pack_layout(nt1, nt2, (D + 31) / 32);
+    return (nt1 > 2 ? L.total_pl : L.total) * sizeof(float);     // the 16-row kernel's planes: large variant only
 }
 
 static int pack_launch(const smx_mlp3_t* net, float* packed, size_t packed_bytes, const ZStatsRider& Z,
@@ -591,8 +616,10 @@ static int pack_launch(const smx_mlp3_t* net, float* packed, size_t packed_bytes
     SMX_REQUIRE(((uintptr_t)packed & 15) == 0, SMX_E_ALIGN);
     unsigned blocks = (unsigned)((L.total + 255) / 256);
     if (blocks > 1024) blocks = 1024;
+    // a buffer of the fp32 image's size alone is packed as before (and then read by the fp32 kernels only)
+    const int planes = nt1 > 2 && packed_bytes >= L.total_pl * sizeof(float);
     hipLaunchKernelGGL(mlp3_pack_kernel, dim3(blocks), dim3(256), 0, smx_s(stream), *net, packed, nt1,
-                       nt2, KC1, Z);
+                       nt2, KC1, Z, planes);
     SMX_LAUNCH_CHECK();
     return SMX_OK;
 }
@@ -616,11 +643,10 @@ extern "C" int smx_mlp3_pack_zstats_f32(const smx_mlp3_t* net, float* packed, si
     return pack_launch(net, packed, packed_bytes, Z, stream);
 }
 
-extern "C" int smx_mlp3_forward_fused_f32(const float* packed, int32_t D, int32_t H1, int32_t H2,
-                                          int32_t OUT, const float* x_main, const float* x_tail,
-                                          int64_t G, int32_t T0, int32_t T1, const float* zmean,
-                                          const float* zstd, float* out, int32_t out_act,
-                                          smx_stream_t stream) {
+static int forward_fused(const float* packed, size_t packed_bytes, int32_t split_bf16, int32_t D, int32_t H1,
+                         int32_t H2, int32_t OUT, const float* x_main, const float* x_tail, int64_t G, int32_t T0,
+                         int32_t T1, const float* zmean, const float* zstd, float* out, int32_t out_act,
+                         smx_stream_t stream) {
     SMX_REQUIRE(packed && x_main && out, SMX_E_NULL);
     SMX_REQUIRE(T1 == 0 || x_tail, SMX_E_NULL);
     SMX_REQUIRE((zmean == nullptr) == (zstd == nullptr), SMX_E_NULL);
@@ -647,6 +673,10 @@ extern "C" int smx_mlp3_forward_fused_f32(const float* packed, int32_t D, int32_
     A.h1_out = A.h2_out = nullptr;
     A.H1 = H1; A.H2 = H2; A.out_ld = OUT;
     A.stop = nullptr;
+    {   // layer 1 on split bf16: asked for, and the planes are there (smx_mlp3_pack*_f32 into a buffer this large)
+        const PackLayout L = pack_layout(nt1, nt2, A.KC1);
+        A.planes = (split_bf16 && !g_exact_zfilter && nt1 > 2 && packed_bytes >= L.total_pl * sizeof(float)) ? packed + L.pl : nullptr;
+    }
     A.xvec = (D % 4 == 0) && (((uintptr_t)x_main & 15) == 0) &&
              (T1 == 0 || ((uintptr_t)x_tail & 15) == 0) &&
              (zmean == nullptr || ((((uintptr_t)zmean | (uintptr_t)zstd) & 15) == 0));
@@ -658,6 +688,25 @@ extern "C" int smx_mlp3_forward_fused_f32(const float* packed, int32_t D, int32_
         if (rc != SMX_E_UNSUPPORTED) return rc;
     }
     return launch_fused<10, 7>(A, smx_s(stream));
+}
+
+extern "C" int smx_mlp3_forward_fused_f32(const float* packed, int32_t D, int32_t H1, int32_t H2,
+                                          int32_t OUT, const float* x_main, const float* x_tail,
+                                          int64_t G, int32_t T0, int32_t T1, const float* zmean,
+                                          const float* zstd, float* out, int32_t out_act,
+                                          smx_stream_t stream) {
+    return forward_fused(packed, 0, 0, D, H1, H2, OUT, x_main, x_tail, G, T0, T1, zmean, zstd, out, out_act, stream);
+}
+
+// the same pass with the size of `packed` (what smx_mlp3_pack*_f32 was given) and the switch for layer 1 on 3-way
+// split bf16 MFMA; exact-z-filter mode, a missing plane image and shapes off the 16-row kernel run the fp32 path
+extern "C" int smx_mlp3_forward_fused_split_f32(const float* packed, size_t packed_bytes, int32_t split_bf16,
+                                                int32_t D, int32_t H1, int32_t H2, int32_t OUT,
+                                                const float* x_main, const float* x_tail, int64_t G, int32_t T0,
+                                                int32_t T1, const float* zmean, const float* zstd, float* out,
+                                                int32_t out_act, smx_stream_t stream) {
+    return forward_fused(packed, packed_bytes, split_bf16, D, H1, H2, OUT, x_main, x_tail, G, T0, T1, zmean, zstd,
+                         out, out_act, stream);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -695,6 +744,7 @@ extern "C" int smx_mlp3_forward_rows_f32(const smx_mlp3_t* net, const float* x, 
     A.out_act = out_act;
     A.tbuf = nullptr; A.exp = 0; A.xvec = 1;
     A.h1_out = h1; A.h2_out = h2;
+    A.planes = nullptr;
     A.H1 = net->H1; A.H2 = net->H2; A.out_ld = out_ld > 0 ? out_ld : net->OUT;
     A.stop = (const int*)stop_flag;
     return smx_rows16_launch(A, net->H1, net->H2, smx_s(stream));

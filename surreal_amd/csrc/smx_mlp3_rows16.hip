@@ -16,6 +16,10 @@
 //     IS the B operand of step r of sub-chunk t of the next layer: activations stay in registers.
 //   * the packed weights (smx_mlp3_pack_f32: [K chunk of 32][feature rows padded to 32][32]) are read
 //     as they are; rows past the last 16-feature tile are staged but never used.
+//   * SPLIT1 (the critic pass; not the launches that keep h1 / h2): layer 1, 65 % of the MFMA issue cycles, on
+//     v_mfma_f32_16x16x32_bf16 -- a sixteenth of the fp32 form's cycles per FLOP, six products per tile and chunk on
+//     three-plane operands (smx_mlp3_fused.inc.h split3_bf16), so 96 issue cycles instead of 256.  The bf16 form's C
+//     fragment is 16x16x4's: bias + ReLU, layers 2 and 3 are the same code on the same registers.
 #include "smx_mlp3_fused.inc.h"
 
 namespace {
@@ -76,20 +80,56 @@ __device__ __forceinline__ void stage_x16(float* dst, float4 v, const float4 zm,
 // SAVE: the hidden activations h1 / h2 (after bias + ReLU) also go to memory, row-major, straight from the accumulators
 // (a lane holds 4 consecutive features of one row per tile: one 16-byte store; the four lane groups of a row fill a
 // 64-byte segment) -- the forward half of a training step over B*E ~ 10^5 rows (the MLPs on top of a stem)
-template <int NT1, int NT2, bool OUT1, bool SAVE>
+// SPLIT1 (the critic pass, A.planes): layer 1 on v_mfma_f32_16x16x32_bf16 with W1 and x each split into three bf16
+// planes that sum to the fp32 value exactly, six of the nine plane products kept (everything down to 2^-23 of a
+// product); the C fragment has the layout of 16x16x4's, so everything behind layer 1 is the same code.
+template <int NT1, int NT2, bool SPLIT1>
+struct Lds16 {
+    static constexpr int P1 = (NT1 + 1) / 2, P2 = (NT2 + 1) / 2;
+    static constexpr int NW1 = (P1 * 32 + 63) / 64, NW2 = (P2 * 32 + 63) / 64;
+    static constexpr int WR = 64 * (NW1 > NW2 ? NW1 : NW2);
+    // SPLIT1: a staging buffer holds NT1 tiles x 3 planes x 1 KiB (and later layer 2's fp32 rows); no x buffers
+    static constexpr int WBF = SPLIT1 ? (NT1 * 768 > 64 * NW2 * LDS16 ? NT1 * 768 : 64 * NW2 * LDS16) : WR * LDS16;
+    static constexpr int XBF = SPLIT1 ? 0 : ROWS16 * LDS16;
+};
+
+typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+#define MFMAB(a, b, c) __builtin_amdgcn_mfma_f32_16x16x32_bf16((a), (b), (c), 0, 0, 0)
+
+// a lane's 8 consecutive k of one x row: z-filter (stage_x16's arithmetic), zero out of range, three planes
+__device__ __forceinline__ void split_x16(bf16x8 (&pl)[3], const float4 a, const float4 b, const float* zms,
+                                          const float* rzl, const int k, const bool hasz, const bool oka,
+                                          const bool okb) {
+    const float4 ma = *reinterpret_cast<const float4*>(zms + k), mb = *reinterpret_cast<const float4*>(zms + k + 4);
+    const float4 ra = *reinterpret_cast<const float4*>(rzl + k), rb = *reinterpret_cast<const float4*>(rzl + k + 4);
+    const float raw[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
+    const float m[8] = {ma.x, ma.y, ma.z, ma.w, mb.x, mb.y, mb.z, mb.w};
+    const float r[8] = {ra.x, ra.y, ra.z, ra.w, rb.x, rb.y, rb.z, rb.w};
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        const float z = zf16(raw[j], m[j], r[j]);
+        const float v = ((j < 4) ? oka : okb) ? (hasz ? z : raw[j]) : 0.f;
+        __bf16 h, mi, lo;
+        smxf::split3_bf16(v, h, mi, lo);
+        pl[0][j] = h; pl[1][j] = mi; pl[2][j] = lo;
+    }
+}
+
+template <int NT1, int NT2, bool OUT1, bool SAVE, bool SPLIT1>
 __global__ __launch_bounds__(NTHR, 1) void mlp3_rows16_kernel(FusedArgs A) {
     constexpr int P1 = (NT1 + 1) / 2, P2 = (NT2 + 1) / 2;      // 32-feature tiles of the packed layout
     constexpr int NW1 = (P1 * 32 + 63) / 64, NW2 = (P2 * 32 + 63) / 64;   // staging passes of 64 rows
-    constexpr int WR = 64 * (NW1 > NW2 ? NW1 : NW2);
+    constexpr int WBF = Lds16<NT1, NT2, SPLIT1>::WBF, XBF = Lds16<NT1, NT2, SPLIT1>::XBF;
     static_assert(NW1 <= 5 && NW2 <= 4, "staging registers are written out for <= 5 / <= 4 passes");
+    static_assert(!(SPLIT1 && SAVE), "the stem instantiations stay on fp32 MFMA");
     extern __shared__ float lds[];
     if (SAVE && A.stop && *A.stop) return;
     TSTAMP(0);
     float* Wb0 = lds;
-    float* Wb1 = Wb0 + WR * LDS16;
-    float* Xb0 = Wb1 + WR * LDS16;
-    float* Xb1 = Xb0 + ROWS16 * LDS16;
-    float* b1s = Xb1 + ROWS16 * LDS16;
+    float* Wb1 = Wb0 + WBF;
+    float* Xb0 = Wb1 + WBF;
+    float* Xb1 = Xb0 + XBF;
+    float* b1s = Xb1 + XBF;
     float* b2s = b1s + P1 * 32;
     float* w3s = b2s + P2 * 32;        // OUT1: row 0 of W3 (P2*32); else b3 (32)
     float* zms = w3s + P2 * 32;        // z-filter mean and 1 / std per input k (KC1 * 32 each): the divisions
@@ -145,7 +185,130 @@ __global__ __launch_bounds__(NTHR, 1) void mlp3_rows16_kernel(FusedArgs A) {
     f32x4 acc1[NT1];
 #pragma unroll
     for (int t = 0; t < NT1; ++t) acc1[t] = f32x4{0.f, 0.f, 0.f, 0.f};
+    const int woff = fm * LDS16 + 4 * g;
+#define SMX_PIN __builtin_amdgcn_sched_barrier(0)
 
+    if constexpr (SPLIT1) {
+    // Weight planes: NWORD 16-byte words per chunk, [tile][plane][lane], copied as they lie (thread tid takes words
+    // tid + 512 i): a fragment read is then 64 consecutive words, conflict-free with no padding.  x: lane (fm, g) of
+    // wavefront wv loads k = 32 c + 8 g .. + 7 of row 16 wv + fm itself (a wavefront covers 16 whole 128-byte lines),
+    // filters and splits it in registers; x never goes through LDS.  Loads run two chunks ahead, as below.
+    constexpr int NWORD = NT1 * 192, NPS = (NWORD + NTHR - 1) / NTHR, CW = P1 * 2 * 192;
+    static_assert(NPS == 8, "staging registers are written out for 8 passes");
+    const uint4* PL = reinterpret_cast<const uint4*>(A.planes);
+    uint4* Pb0 = reinterpret_cast<uint4*>(Wb0);
+    uint4* Pb1 = reinterpret_cast<uint4*>(Wb1);
+    const int last = A.KC1 - 1;
+    const float* xq;
+    bool xokq;
+    {
+        const int T = A.T0 + A.T1;
+        const long r = row0 + wv * 16 + fm;
+        xokq = r < A.total_rows;
+        const long rr = xokq ? r : 0;
+        const long gq = rr / T;
+        const int tt = (int)(rr - gq * T);
+        xq = (tt < A.T0) ? A.x_main + (gq * A.T0 + tt) * (long)A.D : A.x_tail + (gq * A.T1 + (tt - A.T0)) * (long)A.D;
+    }
+    // word index of pass i, clamped for the load (the store is guarded): the last pass is partly empty
+#define SMX_PIDX(i) ((tid + NTHR * (i) < NWORD) ? tid + NTHR * (i) : NWORD - 1)
+#define SMX_PLD(src, i) (src)[SMX_PIDX(i)]
+#define SMX_PST(dst, i, v) do { if (tid + NTHR * (i) < NWORD) (dst)[tid + NTHR * (i)] = (v); } while (0)
+#define SMX_XLD(c_, va, vb, ka, kb)                                                                        \
+    do {                                                                                                   \
+        const int k0_ = 32 * (c_) + 8 * g;                                                                 \
+        ka = k0_ < A.D; kb = k0_ + 4 < A.D;                                                                \
+        va = *reinterpret_cast<const float4*>(xq + (ka ? k0_ : A.D - 4));                                  \
+        vb = *reinterpret_cast<const float4*>(xq + (kb ? k0_ + 4 : A.D - 4));                              \
+    } while (0)
+    uint4 s0, s1, s2, s3, s4, s5, s6, s7;
+    float4 xa, xb;
+    bool ka, kb;
+    bf16x8 bx[3], bn[3];
+    {   // chunk 0
+        SMX_XLD(0, xa, xb, ka, kb);
+        s0 = SMX_PLD(PL, 0); s1 = SMX_PLD(PL, 1); s2 = SMX_PLD(PL, 2); s3 = SMX_PLD(PL, 3);
+        s4 = SMX_PLD(PL, 4); s5 = SMX_PLD(PL, 5); s6 = SMX_PLD(PL, 6); s7 = SMX_PLD(PL, 7);
+        SMX_PST(Pb0, 0, s0); SMX_PST(Pb0, 1, s1); SMX_PST(Pb0, 2, s2); SMX_PST(Pb0, 3, s3);
+        SMX_PST(Pb0, 4, s4); SMX_PST(Pb0, 5, s5); SMX_PST(Pb0, 6, s6); SMX_PST(Pb0, 7, s7);
+    }
+    __syncthreads();            // the staged planes and the zms / rzl tables
+    TSTAMP(1);
+    split_x16(bx, xa, xb, zms, rzl, 8 * g, hasz, xokq && ka, xokq && kb);
+    {
+        const int cn = 1 < last ? 1 : last;
+        const uint4* src = PL + (size_t)cn * CW;
+        SMX_PIN; s0 = SMX_PLD(src, 0); SMX_PIN; s1 = SMX_PLD(src, 1); SMX_PIN; s2 = SMX_PLD(src, 2); SMX_PIN;
+        s3 = SMX_PLD(src, 3); SMX_PIN; s4 = SMX_PLD(src, 4); SMX_PIN; s5 = SMX_PLD(src, 5); SMX_PIN;
+        s6 = SMX_PLD(src, 6); SMX_PIN; s7 = SMX_PLD(src, 7); SMX_PIN;
+        SMX_XLD(cn, xa, xb, ka, kb); SMX_PIN;
+    }
+    // fragments: a ring of three tiles (3 planes x 16 bytes each), read two tiles ahead of the six products
+    bf16x8 fr[3][3];
+#define SMX_RDF(slot, buf, t_)                                                                             \
+    _Pragma("unroll") for (int p_ = 0; p_ < 3; ++p_)                                                       \
+        fr[slot][p_] = *reinterpret_cast<const bf16x8*>((buf) + ((t_) * 3 + p_) * 64 + lane);
+    SMX_RDF(0, Pb0, 0)
+    SMX_RDF(1, Pb0, 1)
+    for (int c = 0; c < A.KC1; ++c) {
+        const uint4* Pc = (c & 1) ? Pb1 : Pb0;
+        uint4* Pn = (c & 1) ? Pb0 : Pb1;
+        const int cn = (c + 1 < A.KC1) ? c + 1 : c;            // the chunk the staging registers hold
+        const int c2 = (c + 2 < A.KC1) ? c + 2 : last;         // the chunk whose loads are issued in this iteration
+        const uint4* src = PL + (size_t)c2 * CW;
+        SMX_PIN;
+#pragma unroll
+        for (int t = 0; t < NT1; ++t) {
+            // the one barrier per chunk: behind the last fragment read of the current buffer (tile NT1 - 1, read
+            // at t = NT1 - 3) and every staging store; the next chunk's first fragments are read under the last
+            // two tiles' products
+            if (t == NT1 - 2) __syncthreads();
+            if (t + 2 < NT1) { SMX_RDF((t + 2) % 3, Pc, t + 2) } else { SMX_RDF((t + 2) % 3, Pn, t + 2 - NT1) }
+            SMX_PIN;
+            {   // smallest terms first: lo.hi, hi.lo, mid.mid, mid.hi, hi.mid, hi.hi  (W plane . x plane)
+                const bf16x8 wh = fr[t % 3][0], wm = fr[t % 3][1], wl = fr[t % 3][2];
+                f32x4 a = acc1[t];
+                a = MFMAB(wl, bx[0], a);
+                a = MFMAB(wh, bx[2], a);
+                a = MFMAB(wm, bx[1], a);
+                a = MFMAB(wm, bx[0], a);
+                a = MFMAB(wh, bx[1], a);
+                a = MFMAB(wh, bx[0], a);
+                acc1[t] = a;
+            }
+            SMX_PIN;
+            // the next chunk's planes go to LDS one pass per tile, each staging register re-loaded (chunk c + 2)
+            // right behind the store that frees it
+            if (t == 1) { SMX_PST(Pn, 0, s0); s0 = SMX_PLD(src, 0); }
+            if (t == 2) { SMX_PST(Pn, 1, s1); s1 = SMX_PLD(src, 1); }
+            if (t == 3) { SMX_PST(Pn, 2, s2); s2 = SMX_PLD(src, 2); }
+            if (t == 4) { SMX_PST(Pn, 3, s3); s3 = SMX_PLD(src, 3); }
+            if (t == 5) { SMX_PST(Pn, 4, s4); s4 = SMX_PLD(src, 4); }
+            if (t == 6) { SMX_PST(Pn, 5, s5); s5 = SMX_PLD(src, 5); }
+            if (t == 7) { SMX_PST(Pn, 6, s6); s6 = SMX_PLD(src, 6); }
+            if (t == 8) { SMX_PST(Pn, 7, s7); s7 = SMX_PLD(src, 7); }
+            if (t == 0) {       // the next chunk's x (loaded a whole iteration ago): filter and split, then the loads of chunk c + 2
+                asm volatile("" : "+v"(xa.x), "+v"(xa.y), "+v"(xa.z), "+v"(xa.w), "+v"(xb.x), "+v"(xb.y), "+v"(xb.z), "+v"(xb.w));
+                split_x16(bn, xa, xb, zms, rzl, 32 * cn + 8 * g, hasz, xokq && ka, xokq && kb);
+                SMX_XLD(c2, xa, xb, ka, kb);
+            }
+            SMX_PIN;
+        }
+        bx[0] = bn[0]; bx[1] = bn[1]; bx[2] = bn[2];
+        {   // the ring is indexed by the tile, and NT1 is no multiple of 3: tiles 0 and 1 back to slots 0 and 1
+            bf16x8 q0[3], q1[3];
+#pragma unroll
+            for (int p = 0; p < 3; ++p) { q0[p] = fr[NT1 % 3][p]; q1[p] = fr[(NT1 + 1) % 3][p]; }
+#pragma unroll
+            for (int p = 0; p < 3; ++p) { fr[0][p] = q0[p]; fr[1][p] = q1[p]; }
+        }
+    }
+#undef SMX_RDF
+#undef SMX_XLD
+#undef SMX_PST
+#undef SMX_PLD
+#undef SMX_PIDX
+    } else {
     {   // chunk 0
         const float4* wsrc = reinterpret_cast<const float4*>(W1p);
         const int kc = (sk4 < A.D) ? sk4 : A.D - 4;
@@ -195,8 +358,7 @@ __global__ __launch_bounds__(NTHR, 1) void mlp3_rows16_kernel(FusedArgs A) {
     _Pragma("unroll") for (int t = 0; t < HA; ++t) acc1[t] = MFMA16(fa[t].e, bq.e, acc1[t]);
 #define SMX_STEP_B(e)                                                             \
     _Pragma("unroll") for (int t = 0; t < HB; ++t) acc1[HA + t] = MFMA16(fb[t].e, bq.e, acc1[HA + t]);
-#define SMX_PIN __builtin_amdgcn_sched_barrier(0)
-    const int xoff = (wv * 16 + fm) * LDS16 + 4 * g, woff = fm * LDS16 + 4 * g;
+    const int xoff = (wv * 16 + fm) * LDS16 + 4 * g;
 
     // staging registers of the chunk after the next barrier (named scalars: see smx_mlp3_fused.hip)
     float4 x0, x1, w0, w1, w2, w3, w4;
@@ -321,6 +483,7 @@ __global__ __launch_bounds__(NTHR, 1) void mlp3_rows16_kernel(FusedArgs A) {
 #undef SMX_STEP_B
 #undef SMX_RD_A
 #undef SMX_RD_B
+    }
     __syncthreads();            // the trailing prefetch read a staging buffer that layer 2 overwrites
 
     TSTAMP(2);
@@ -523,15 +686,15 @@ __global__ __launch_bounds__(NTHR, 1) void mlp3_rows16_kernel(FusedArgs A) {
 #undef SMX_WST
 }
 
-template <int NT1, int NT2, bool SAVE>
+template <int NT1, int NT2, bool SAVE, bool SPLIT1>
 int launch16(const FusedArgs& A, hipStream_t st) {
     constexpr int P1 = (NT1 + 1) / 2, P2 = (NT2 + 1) / 2;
-    constexpr int NW1 = (P1 * 32 + 63) / 64, NW2 = (P2 * 32 + 63) / 64;
-    constexpr int WR = 64 * (NW1 > NW2 ? NW1 : NW2);
-    const size_t lds = (size_t)(2 * WR * LDS16 + 2 * ROWS16 * LDS16 + P1 * 32 + 2 * P2 * 32 + 2 * A.KC1 * 32) * sizeof(float);
+    constexpr int WBF = Lds16<NT1, NT2, SPLIT1>::WBF, XBF = Lds16<NT1, NT2, SPLIT1>::XBF;
+    const size_t lds = (size_t)(2 * WBF + 2 * XBF + P1 * 32 + 2 * P2 * 32 + 2 * A.KC1 * 32) * sizeof(float);
     if (lds > 160 * 1024) return SMX_E_UNSUPPORTED;     // very wide inputs: the 32-row kernel takes them
     const unsigned grid = (unsigned)((A.total_rows + ROWS16 - 1) / ROWS16);
-    void (*k)(FusedArgs) = (A.OUT == 1) ? mlp3_rows16_kernel<NT1, NT2, true, SAVE> : mlp3_rows16_kernel<NT1, NT2, false, SAVE>;
+    void (*k)(FusedArgs) = (A.OUT == 1) ? mlp3_rows16_kernel<NT1, NT2, true, SAVE, SPLIT1>
+                                        : mlp3_rows16_kernel<NT1, NT2, false, SAVE, SPLIT1>;
     hipError_t e = hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) return (int)e;
     hipLaunchKernelGGL(k, dim3(grid), dim3(NTHR), lds, st, A);
@@ -547,9 +710,13 @@ int smx_rows16_launch(const FusedArgs& A, int H1, int H2, hipStream_t st) {
     if (!A.xvec || A.D < 4 || A.OUT > 32 || H1 <= 64 || H2 <= 64 || H1 > 320 || H2 > 224) return SMX_E_UNSUPPORTED;
     if (save) {
         if ((H1 | H2) & 3) return SMX_E_UNSUPPORTED;
-        if (H1 <= 304 && H2 <= 208) return launch16<19, 13, true>(A, st);
-        return launch16<20, 14, true>(A, st);
+        if (H1 <= 304 && H2 <= 208) return launch16<19, 13, true, false>(A, st);
+        return launch16<20, 14, true, false>(A, st);
     }
-    if (H1 <= 304 && H2 <= 208) return launch16<19, 13, false>(A, st);
-    return launch16<20, 14, false>(A, st);
+    if (A.planes) {     // the critic pass with W1's bf16 planes packed and asked for; too wide an input falls through
+        const int rc = (H1 <= 304 && H2 <= 208) ? launch16<19, 13, false, true>(A, st) : launch16<20, 14, false, true>(A, st);
+        if (rc != SMX_E_UNSUPPORTED) return rc;
+    }
+    if (H1 <= 304 && H2 <= 208) return launch16<19, 13, false, false>(A, st);
+    return launch16<20, 14, false, false>(A, st);
 }

@@ -138,13 +138,15 @@ class HipKernels(object):
         (x - m) * (1 / s); the goldens run with the default (off), DESIGN.md 1"""
         L.call('smx_mlp3_fused_exact_zfilter', 1 if on else 0)
 
-    def mlp3_forward_fused(self, packed, net, x_main, x_tail, zmean, zstd, out, act):
+    def mlp3_forward_fused(self, packed, net, x_main, x_tail, zmean, zstd, out, act, split_bf16=True):
+        """split_bf16: layer 1 of the 16-row kernel on 3-way split-bf16 MFMA (session_config.learner.critic_split_bf16;
+        DESIGN.md 3.1) where `packed` carries W1's planes; False: fp32 MFMA throughout"""
         G, T0, D = x_main.shape
         T1 = 0 if x_tail is None else x_tail.shape[1]
         assert x_main.is_contiguous() and (x_tail is None or x_tail.is_contiguous())
-        L.call('smx_mlp3_forward_fused_f32', L.ptr(packed), net.D, net.H1, net.H2, net.OUT,
-               L.ptr(x_main), L.ptr(x_tail), G, T0, T1, L.ptr(zmean), L.ptr(zstd), L.ptr(out),
-               act, self._st())
+        L.call('smx_mlp3_forward_fused_split_f32', L.ptr(packed), packed.numel() * 4, 1 if split_bf16 else 0,
+               net.D, net.H1, net.H2, net.OUT, L.ptr(x_main), L.ptr(x_tail), G, T0, T1, L.ptr(zmean),
+               L.ptr(zstd), L.ptr(out), act, self._st())
 
     # rows from which the fused many-row forward pays: below, its 128-row workgroups leave most of the 256 CUs idle and
     # the layered GEMMs (32 x 32 / 64 x 64 tiles) win (7936 rows: 62 workgroups, measured equal)

@@ -207,6 +207,12 @@ class PPOLearner(Learner):
         # two chains on two streams inside the graph, and the weight gradients + Adam as one launch: each measured
         # equal or slower, DESIGN.md 3.2, and was removed in round 5.)
         self.fused_epochs = bool(lcfg.get('fused_epochs', True))
+        # layer 1 of the fused critic pass on 3-way split-bf16 MFMA (csrc/smx_mlp3_rows16.hip SPLIT1; accuracy and
+        # measurement: DESIGN.md 3.1, profiles/critic_split_*); False: fp32 MFMA throughout
+        self.critic_split_bf16 = bool(lcfg.get('critic_split_bf16', True))
+        # passed only when it departs from the kernels' default: a kernel set without the switch (the CPU double) is
+        # then never asked for it
+        self._critic_kw = {} if self.critic_split_bf16 else {'split_bf16': False}
         self._ws = None
         self._graphs = {}
         self._ctrl_host = None
@@ -605,12 +611,14 @@ class PPOLearner(Learner):
         else:
             K.mlp3_pack(m.critic, ws.packed)
         if not ws.split_tail:
-            K.mlp3_forward_fused(ws.packed, m.critic, obs, obs_next, zm, zs, ws.vals, L.SMX_ACT_NONE)
+            K.mlp3_forward_fused(ws.packed, m.critic, obs, obs_next, zm, zs, ws.vals, L.SMX_ACT_NONE,
+                                 **self._critic_kw)
             return None
         # B*(N+1) rows would need one more (nearly empty) round of workgroups over the chip
         # than B*N: the fused kernel takes the B*N step rows, the B obs_next rows go through
         # the layered small-batch kernels (same arithmetic, tests check both against the oracle)
-        K.mlp3_forward_fused(ws.packed, m.critic, obs, None, zm, zs, ws.vals[:B * N], L.SMX_ACT_NONE)
+        K.mlp3_forward_fused(ws.packed, m.critic, obs, None, zm, zs, ws.vals[:B * N], L.SMX_ACT_NONE,
+                             **self._critic_kw)
         if not filter_tail:
             pass
         elif self.use_z_filter:
